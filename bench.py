@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: paired-samples/sec of the img+jnt assoc-VAE train step on MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c1|c2|c2conv|c4|c5] [--no-cpu-baseline]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c1|c2|c2conv|c4|c5] [--no-cpu-baseline] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path (input staging, forward, fused losses, backward,
 [gradient all-reduce], Adam + shadow refresh) over one batch of synthetic paired samples that is
@@ -24,7 +24,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-HBM_PEAK_GBS = 8000.0        # MI355X HBM3E, /opt/skills/guides/MI355X_MICROARCH.md
+HBM_PEAK_GBS = 8000.0        # MI355X HBM3E
 MFMA_BF16_PEAK_TF = 2500.0   # dense bf16
 MFMA_F32_PEAK_TF = 157.3
 
@@ -262,11 +262,26 @@ def cpu_baseline(archs, B, budget_s=10.0):
 
 
 GEMM_LAUNCH_PREFIXES = ("fwd_enc", "fwd_dec", "fwd_head", "fwd_out_loss", "bwd_", "wgrad", "conv_enc", "conv_dec", "conv_bwd")
+DUMP_MAX_BYTES = 64 << 20
 
 
-def measure(name, args, world, rank, local_rank, steps, warmup, repeats, kernel_steps, dtype=None, comm=None, wire=None, local_only=False, buckets=None):
+def step_outputs(model):
+    """What a caller of the train step receives from its last step: the step's cost and the parameters it left (flat, as
+    get_params() returns them).  Float32, at most DUMP_MAX_BYTES in all: a larger parameter vector is reduced to a fixed
+    sample (seed 0, indices ascending) that depends only on its length."""
+    cost = model.cost_history(1).astype(np.float32)
+    params = model.get_params()
+    room = (DUMP_MAX_BYTES - cost.nbytes - 4096) // params.itemsize         # (4096: headroom for the two .npy headers)
+    if params.size > room:
+        params = params[np.sort(np.random.default_rng(0).choice(params.size, room, replace=False))]
+    return {"cost": cost, "params": params}
+
+
+def measure(name, args, world, rank, local_rank, steps, warmup, repeats, kernel_steps, dtype=None, comm=None, wire=None, local_only=False, buckets=None,
+            dump_dir=None):
     """Builds the model of config `name`, times `repeats` x `steps` train steps (each repeat bracketed by barrier +
-    synchronise; MAX over ranks per repeat), then one eager pass with per-launch HIP events.  Returns a dict."""
+    synchronise; MAX over ranks per repeat), then one eager pass with per-launch HIP events.  With `dump_dir`, rank 0
+    writes step_outputs() of the last timed step there before anything else runs on the model.  Returns a dict."""
     import torch
     import torch.distributed as dist
     from vae_assoc_amd.vae_assoc import AssocVariationalAutoEncoder
@@ -324,6 +339,10 @@ def measure(name, args, world, rank, local_rank, steps, warmup, repeats, kernel_
         dts.append(dt)
     dt = float(np.median(dts))
     last_cost = float(model.cost_history(1)[0])
+    if dump_dir and rank == 0:
+        os.makedirs(dump_dir, exist_ok=True)
+        for nm, a in step_outputs(model).items():
+            np.save(os.path.join(dump_dir, nm + ".npy"), a)
 
     pcie = None
     if args.host_input and world == 1:
@@ -524,6 +543,10 @@ def main():
                          "torch.distributed reference at north_star's 1e-3, times both and keeps the faster -- both are reported")
     ap.add_argument("--host-input", action="store_true",
                     help="also time the step fed from pinned host batches (PCIe-inclusive rate; reported beside `value`, never as it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps (--warmup steps, then --repeats x --steps timed ones), write what the last of them computed (its cost, the parameters it left) as DIR/<name>.npy, "
+                         "float32, at most 64 MB in all.  Inputs, weights and eps are seeded: the same arguments give the same inputs, "
+                         "so two builds can be compared output for output (bench_outputs/ is kept out of git)")
     args = ap.parse_args()
 
     import torch
@@ -578,7 +601,8 @@ def main():
                 buckets, wire = int(best[0]), best.split("_")[2]
         else:
             buckets, wire = b_opts[0], w_opts[0]
-    res = measure(args.config, args, world, rank, local_rank, args.steps, args.warmup, args.repeats, args.kernel_steps, args.dtype, comm=comm, buckets=buckets, wire=wire)
+    res = measure(args.config, args, world, rank, local_rank, args.steps, args.warmup, args.repeats, args.kernel_steps, args.dtype, comm=comm, buckets=buckets, wire=wire,
+                  dump_dir=args.dump_outputs)
     coll = None
     if world > 1:
         coll = {"backend": res["comm"], "buckets": res["buckets"], "wire": res["wire"], "selection": comm_log}

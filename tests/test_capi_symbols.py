@@ -113,6 +113,30 @@ def test_bench_accounting_matches_survey_figures():
         assert {"prep", "adam", "fwd_head", "fwd_out_loss", "bwd_out", "bwd_dec1_latent", "bwd_head"} <= set(work)
 
 
+def test_bench_dump_outputs_stay_within_budget():
+    """bench.py --dump-outputs: the last step's cost and the parameters, float32; a parameter vector past the 64 MB budget is
+    reduced to the same seeded sample on every run."""
+    import numpy as np
+    import bench
+
+    class Model:
+        def __init__(self, n):
+            self.params = np.arange(n, dtype=np.float32)
+
+        def cost_history(self, n):
+            return np.full(n, 123.5, np.float32)
+
+        def get_params(self):
+            return self.params.copy()
+    small = bench.step_outputs(Model(1468611))
+    assert small["cost"].dtype == np.float32 and small["cost"].tolist() == [123.5]
+    assert np.array_equal(small["params"], np.arange(1468611, dtype=np.float32))
+    big = [bench.step_outputs(Model(20 << 20)) for _ in range(2)]
+    assert sum(a.nbytes for a in big[0].values()) <= bench.DUMP_MAX_BYTES - 4096
+    assert big[0]["params"].dtype == np.float32 and np.array_equal(big[0]["params"], big[1]["params"])
+    assert np.all(np.diff(big[0]["params"]) >= 0)                            # (indices ascending)
+
+
 def test_dp_plan_is_host_only_and_tiles_the_gradient_buffer(capi):
     """avae_dp_plan (no GPU needed): the data-parallel buckets of a configuration.  MLP models: the master layout holds the encoder
     side of EVERY modality first, then every decoder side, then the cost slot, so that bucket 1 (encoder) and bucket 0 (decoder +
