@@ -186,6 +186,28 @@ int avae_generate(avae_handle* h, const float* z_dev, int32_t rows, float* const
 int avae_reconstruct(avae_handle* h, int32_t m, const float* x_dev, int32_t x_ld, const float* eps_dev,
                      int32_t rows, float* xhat_dev, void* stream);
 
+/* ---- per-row scoring (the reference has no counterpart: its only figure of merit is the batch cost, vae_assoc.py:388-391).
+ * Forward only; M modalities, P = M(M-1)/2 pairs (i<j) in lexicographic order, per row n:
+ *   recon[n,m]  Bernoulli -sum_d [x log(1e-3+p) + (1-x) log(1e-3+1-p)], Gaussian 0.5 sum_d (x - x_hat)^2; x_hat / p = decoder m on
+ *               z_m = mu_m + exp(lv_m/2) eps[n] (ONE eps row for every modality, as in training)
+ *   latent[n,m] -0.5 sum (1 + lv - mu^2 - e^lv)
+ *   assoc[n,p]  KL(q_i||q_j) + KL(q_j||q_i) summed over n_z
+ *   cost[n]     sum_m w_m (recon + latent) + assoc_lambda sum_p assoc
+ *   cross[n,s,d] (AVAE_SCORE_CROSS) the recon loss of modality d decoded from z = mu_s (no noise): source s predicting target d;
+ *               the diagonal is deterministic self-reconstruction
+ * For rows = batch_size and the same eps the columns give back avae_eval_cost (single replica):
+ *   eval_cost == sum_m w_m [mean_n latent + (binary_m ? mean_n recon : sum_n recon)] + assoc_lambda sum_p sum_n assoc */
+#define AVAE_SCORE_CROSS 1
+/* Host-only (no GPU): columns k of a score row = 1 + 2M + P (+ M*M with AVAE_SCORE_CROSS).  Unknown flags are rejected. */
+int avae_score_width(const avae_config* cfg, int32_t flags, int32_t* k);
+/* out_dev: device [rows, k] fp32, dense, columns cost | recon[M] | latent[M] | assoc[P] | cross[s*M+d].  Any rows >= 0 (0: no-op),
+ * worked in chunks of at most batch_size rows through the inference plans of avae_encode / avae_decode; x_dev[m] as in
+ * avae_train_step (x_ld NULL = dense, else x_ld[m] >= n_input).  eps_dev: device [rows, n_z] fp32, or NULL = the internal
+ * generator, a fresh draw per call keyed by (seed, draw counter, row of the whole input) as avae_reconstruct's.  As avae_encode,
+ * it changes nothing the next training step reads; on a data-parallel replica it scores the local rows, with no collective. */
+int avae_score(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, int32_t rows, const float* eps_dev, int32_t flags,
+               float* out_dev, void* stream);
+
 /* save_model / restore_model (vae_assoc.py:427-463): own flat file (config echo + params + Adam
  * slots + step); TF .ckpt files cannot be read offline. */
 int avae_save(avae_handle* h, const char* path);

@@ -18,6 +18,7 @@ AVAE_MAX_HIDDEN = 8
 AVAE_MAX_WORLD = 8
 AVAE_IPC_HANDLE_BYTES = 128
 COMM_NONE, COMM_RCCL, COMM_IPC = 0, 1, 2
+SCORE_CROSS = 1
 
 ACT_IDS = {"identity": 0, "relu": 1, "softplus": 2, "sigmoid": 3, "tanh": 4}
 DTYPE_IDS = {"fp32": 0, "f32": 0, "float32": 0, "bf16": 1, "bfloat16": 1}
@@ -32,6 +33,7 @@ SYMBOLS = [
     "avae_train_step", "avae_train_steps", "avae_stage_batches", "avae_grad_buffer", "avae_cost_history",
     "avae_dp_plan", "avae_dp_backward", "avae_dp_apply", "avae_comm_unique_id", "avae_comm_ipc_handle", "avae_comm_ipc_attach",
     "avae_eval_cost", "avae_encode", "avae_decode", "avae_generate", "avae_reconstruct", "avae_save", "avae_load",
+    "avae_score_width", "avae_score",
     "avae_synchronize", "avae_timing_enable", "avae_timing_report", "avae_debug_fetch", "avae_comm_allreduce",
 ]
 
@@ -99,6 +101,8 @@ def lib():
             L.avae_decode.argtypes = [vp, i32, vp, i32, vp, vp]
             L.avae_generate.argtypes = [vp, vp, i32, C.POINTER(vp), vp]
             L.avae_reconstruct.argtypes = [vp, i32, vp, i32, vp, i32, vp, vp]
+            L.avae_score_width.argtypes = [C.POINTER(Config), i32, C.POINTER(i32)]
+            L.avae_score.argtypes = [vp, C.POINTER(vp), C.POINTER(i32), i32, vp, i32, vp, vp]
             L.avae_save.argtypes = [vp, C.c_char_p]
             L.avae_load.argtypes = [vp, C.c_char_p]
             L.avae_synchronize.argtypes = [vp]

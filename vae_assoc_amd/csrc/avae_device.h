@@ -376,6 +376,30 @@ void launch_serve_in(int compute_dtype, const ServeInArgs& a, int grid_x, hipStr
 void launch_gather(int compute_dtype, const GatherArgs& a, int n_blocks, hipStream_t s);
 void launch_col2im(int compute_dtype, const Col2imArgs& a, int n_blocks, hipStream_t s);
 
+// Per-row scoring (avae_score): one wave64 per row, kScoreRows rows per workgroup; every sum is a fixed-order shuffle tree (no
+// atomics), so a row's score does not depend on the chunking or the launch shape.  Score rows are dense [rows][k] fp32 in the
+// order cost | recon[M] | latent[M] | assoc[P] | cross[s*M+d].
+constexpr int kScoreRows = kThreads / 64;
+struct ScoreLatentArgs {
+    const float* mulv[kMaxMod];    // [rows][2*n_z] fp32: [mu | log sigma^2] of every modality
+    void* Z[kMaxMod]; int ldz[kMaxMod];            // decoder inputs, compute dtype, [rows][ldz] (columns [0, n_z) written)
+    const float* eps; int ld_eps;  // [rows][ld_eps] fp32 (the sampled pass)
+    float* out; int k;             // score rows
+    int rows, nz, n_mod;
+    int src;                       // < 0: sampled pass (latent, assoc columns; z_m = mu_m + exp(lv_m/2) eps); else z = mu_src for every decoder
+};
+void launch_score_latent(int compute_dtype, const ScoreLatentArgs& a, hipStream_t s);
+struct ScoreRowsArgs {
+    const float* xhat; int ld32;   // decoder output of this pass: p (Bernoulli) or x_hat (Gaussian), fp32 [rows][ld32]
+    const float* x; long long ldx; // the caller's rows of that modality
+    float* out; int k;
+    int rows, n_in, binary, col;   // score column of this pass
+    int cost;                      // 1: also cost = sum_m w_m (recon_m + latent_m) + lambda sum_p assoc_p (the sampled pass's last modality)
+    int n_mod, n_pair;
+    float w[kMaxMod]; float lambda;
+};
+void launch_score_rows(const ScoreRowsArgs& a, hipStream_t s);
+
 // ---- gradient exchange (avae_comm.hip)
 // One-shot all-reduce over hipIpc peers ("a hand-rolled P2P reduce-scatter/all-gather over hipIpc peers"):
 // every rank owns an exchange block (uncached device memory, mapped by every peer); a range of the gradient buffer is cut into

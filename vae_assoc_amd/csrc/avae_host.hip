@@ -3184,6 +3184,97 @@ int avae_reconstruct(avae_handle* h, int32_t m, const float* x_dev, int32_t x_ld
     });
 }
 
+int avae_score_width(const avae_config* cfg, int32_t flags, int32_t* k) {
+    try {
+        if (!cfg || !k) throw Err("null argument");
+        check_config(*cfg);
+        if (flags & ~AVAE_SCORE_CROSS) throw Err("avae_score: unknown flags (only AVAE_SCORE_CROSS is defined)");
+        const int M = cfg->n_modalities;
+        *k = 1 + 2 * M + M * (M - 1) / 2 + ((flags & AVAE_SCORE_CROSS) ? M * M : 0);
+        return 0;
+    } catch (const std::exception& e) { g_create_error = e.what(); return 2; }
+}
+
+// Per chunk of at most batch_size rows: stage every modality (and eps) -> encoders -> k_score_latent (latent, assoc, z of every
+// modality) -> per modality decoder + k_score_rows (the last one also forms cost); with AVAE_SCORE_CROSS then per source s:
+// k_score_latent(z = mu_s) -> every decoder + k_score_rows.  The kernels write straight into the caller's score rows.
+int avae_score(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, int32_t rows, const float* eps_dev, int32_t flags,
+               float* out_dev, void* stream) {
+    return guarded(h, [&] {
+        if (flags & ~AVAE_SCORE_CROSS) throw Err("avae_score: unknown flags (only AVAE_SCORE_CROSS is defined)");
+        if (rows < 0) throw Err("avae_score: rows must be >= 0");
+        if (rows == 0) return;
+        if (!out_dev) throw Err("avae_score: out_dev is NULL");
+        if (!x_dev) throw Err("avae_score: x_dev is NULL");
+        const int M = h->M, P = M * (M - 1) / 2;
+        const bool cross = (flags & AVAE_SCORE_CROSS) != 0;
+        const int k = 1 + 2 * M + P + (cross ? M * M : 0);
+        int ld[kMaxMod];
+        for (int m = 0; m < M; ++m) {
+            if (!x_dev[m]) throw Err("avae_score: x_dev[" + std::to_string(m) + "] is NULL");
+            ld[m] = x_ld ? x_ld[m] : h->mods[m].n_in;
+            if (ld[m] < h->mods[m].n_in)
+                throw Err("avae_score: x_ld[" + std::to_string(m) + "] = " + std::to_string(ld[m]) + " is below n_input = " + std::to_string(h->mods[m].n_in));
+        }
+        hipStream_t s = on_stream(h, stream);
+        // a fresh eps per call, keyed as avae_reconstruct's: draw counter in the salt's high bits, row of the whole input
+        const unsigned long long draw = eps_dev ? 0ull : (unsigned long long)((++h->draw_id) & 0x3FFFFFu) << 34;
+        ScoreLatentArgs la;
+        std::memset(&la, 0, sizeof(la));
+        la.eps = h->at<float>(h->off_eps); la.ld_eps = h->ld_eps;
+        la.k = k; la.nz = h->nz; la.n_mod = M;
+        ScoreRowsArgs ra;
+        std::memset(&ra, 0, sizeof(ra));
+        ra.k = k; ra.n_mod = M; ra.n_pair = P; ra.lambda = h->cfg.assoc_lambda;
+        for (int m = 0; m < M; ++m) {
+            la.mulv[m] = h->at<float>(h->mods[m].mulv);
+            la.Z[m] = h->at<void>(h->mods[m].Z.rm); la.ldz[m] = h->mods[m].Z.ld;
+            ra.w[m] = h->cfg.mod[m].weight;
+        }
+        auto score_rows = [&](int m, int col, bool with_cost, int n) {
+            const Mod& md = h->mods[m];
+            ra.xhat = h->at<float>(md.out32); ra.ld32 = md.ld32;
+            ra.n_in = md.n_in; ra.binary = h->cfg.mod[m].binary ? 1 : 0;
+            ra.col = col; ra.cost = with_cost ? 1 : 0; ra.rows = n;
+            Timed t(h, s, "score_rows");
+            launch_score_rows(ra, s); LAUNCH_OK("score_rows");
+        };
+        for (int r0 = 0; r0 < rows; r0 += h->B) {
+            const int n = std::min(h->B, rows - r0);
+            for (int m = 0; m < M; ++m) {
+                const Mod& md = h->mods[m];
+                run_prep_single(h, x_dev[m] + (size_t)r0 * ld[m], ld[m], n, md.n_in, md.X0, nullptr, 0, m == 0,
+                                eps_dev ? eps_dev + (size_t)r0 * h->nz : nullptr, 0x73636f72ull /*scor*/ | draw, s, r0);
+                run_inference(h, m, true, n, s);
+            }
+            la.out = out_dev + (size_t)r0 * k; la.rows = n; la.src = -1;
+            ra.out = la.out;
+            {
+                Timed t(h, s, "score_latent");
+                launch_score_latent(h->cfg.compute_dtype, la, s); LAUNCH_OK("score_latent");
+            }
+            for (int m = 0; m < M; ++m) {
+                ra.x = x_dev[m] + (size_t)r0 * ld[m]; ra.ldx = ld[m];
+                run_inference(h, m, false, n, s);
+                score_rows(m, 1 + m, m == M - 1, n);
+            }
+            if (!cross) continue;
+            for (int src = 0; src < M; ++src) {
+                la.src = src;
+                {
+                    Timed t(h, s, "score_latent");
+                    launch_score_latent(h->cfg.compute_dtype, la, s); LAUNCH_OK("score_latent");
+                }
+                for (int d = 0; d < M; ++d) {
+                    ra.x = x_dev[d] + (size_t)r0 * ld[d]; ra.ldx = ld[d];
+                    run_inference(h, d, false, n, s);
+                    score_rows(d, 1 + 2 * M + P + src * M + d, false, n);
+                }
+            }
+        }
+    });
+}
+
 // ---- checkpoint: "AVAECKPT" | u32 version | u32 n_mod | u32 n_z | per modality {n_input, L, hs[L], conv, gener1, gener2} | u64 P | i64 step | theta | m | v
 int avae_save(avae_handle* h, const char* path) {
     return guarded(h, [&] {

@@ -3347,4 +3347,110 @@ void launch_fill(void* base, int elem_bytes, unsigned bits, long long start, lon
                        elem_bytes, bits, start, stride, count);
 }
 
+// ------------------------------------------------------------------ per-row scoring (avae_score)
+// Sum over the 64 lanes of a wave in a fixed order (shuffle tree); the total is valid in lane 0.
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    return v;
+}
+
+// One wave per row, one lane per latent dimension (n_z <= 64).  Sampled pass: latent[m] = KL(q_m || N(0,I)) and assoc[p] =
+// KL(q_i||q_j) + KL(q_j||q_i) with latent_item's formulas, and the decoder inputs z_m = mu_m + exp(lv_m/2) eps as the head epilogue
+// forms them.  Cross pass (src >= 0): z = mu_src into every modality's decoder input.
+template <typename CT>
+__global__ void __launch_bounds__(kThreads) k_score_latent(ScoreLatentArgs a) {
+    const int row = blockIdx.x * kScoreRows + (threadIdx.x >> 6), d = threadIdx.x & 63;
+    if (row >= a.rows) return;                     // wave-uniform: the shuffles below always run on whole waves
+    const int nz = a.nz, nz2 = 2 * a.nz;
+    const bool on = d < nz;
+    if (a.src >= 0) {
+        if (on) {
+            const float v = a.mulv[a.src][(size_t)row * nz2 + d];
+            for (int m = 0; m < a.n_mod; ++m) reinterpret_cast<CT*>(a.Z[m])[(size_t)row * a.ldz[m] + d] = to_ct<CT>(v);
+        }
+        return;
+    }
+    float mu[kMaxMod], lv[kMaxMod], en[kMaxMod];
+    const float eps_v = on ? a.eps[(size_t)row * a.ld_eps + d] : 0.0f;
+    float* orow = a.out + (size_t)row * a.k;
+#pragma unroll
+    for (int m = 0; m < kMaxMod; ++m) {
+        mu[m] = lv[m] = 0.0f; en[m] = 1.0f;
+        if (m < a.n_mod) {
+            if (on) {
+                mu[m] = a.mulv[m][(size_t)row * nz2 + d];
+                lv[m] = a.mulv[m][(size_t)row * nz2 + nz + d];
+            }
+            const float el = fexp(lv[m]);
+            en[m] = frcp(el);
+            const float kl = wave_sum(on ? -0.5f * (1.0f + lv[m] - mu[m] * mu[m] - el) : 0.0f);
+            if (d == 0) orow[1 + a.n_mod + m] = kl;
+            if (on) reinterpret_cast<CT*>(a.Z[m])[(size_t)row * a.ldz[m] + d] = to_ct<CT>(__builtin_fmaf(fexp(0.5f * lv[m]), eps_v, mu[m]));
+        }
+    }
+    int p = 0;
+#pragma unroll
+    for (int i = 0; i < kMaxMod; ++i) {
+#pragma unroll
+        for (int j = i + 1; j < kMaxMod; ++j) {
+            if (j < a.n_mod) {
+                const float al = lv[i] - lv[j], dl = mu[i] - mu[j];
+                const float sh = two_sinh(0.5f * al);
+                const float s = wave_sum(on ? 0.5f * (sh * sh + dl * dl * (en[i] + en[j])) : 0.0f);
+                if (d == 0) orow[1 + 2 * a.n_mod + p] = s;
+                ++p;
+            }
+        }
+    }
+}
+
+// Reconstruction loss of one row for one decode pass, from the decoder's fp32 output (p for Bernoulli, x_hat for Gaussian) with
+// loss_bernoulli / loss_gauss's arithmetic (contraction off); one wave per row, lanes stride the row, fixed-order tree.
+__global__ void __launch_bounds__(kThreads) k_score_rows(ScoreRowsArgs a) {
+#pragma clang fp contract(off)
+    const int row = blockIdx.x * kScoreRows + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= a.rows) return;                     // wave-uniform
+    const float* xh = a.xhat + (size_t)row * a.ld32;
+    const float* x = a.x + (size_t)row * a.ldx;
+    float acc = 0.0f;
+    if (a.binary) {
+        for (int c = lane; c < a.n_in; c += 64) {
+            const float p = xh[c], xv = x[c];
+            const float lp = 1e-3f + p, lq = 1e-3f + 1.0f - p;
+            acc += -(xv * flog(lp) + (1.0f - xv) * flog(lq));
+        }
+    } else {
+        for (int c = lane; c < a.n_in; c += 64) {
+            float sl, da;
+            loss_gauss(xh[c], x[c], 1.0f, sl, da);
+            acc += sl;
+        }
+    }
+    const float r = wave_sum(acc);
+    if (lane == 0) {
+        float* orow = a.out + (size_t)row * a.k;
+        orow[a.col] = r;
+        if (a.cost) {
+            float c = 0.0f;
+            for (int m = 0; m < a.n_mod; ++m) c += a.w[m] * ((1 + m == a.col ? r : orow[1 + m]) + orow[1 + a.n_mod + m]);
+            float as = 0.0f;
+            for (int q = 0; q < a.n_pair; ++q) as += orow[1 + 2 * a.n_mod + q];
+            orow[0] = c + a.lambda * as;
+        }
+    }
+}
+
+void launch_score_latent(int compute_dtype, const ScoreLatentArgs& a, hipStream_t s) {
+    if (a.rows <= 0) return;
+    const dim3 grid((a.rows + kScoreRows - 1) / kScoreRows);
+    if (compute_dtype == AVAE_BF16) AVAE_LAUNCH((k_score_latent<__bf16>), grid, dim3(kThreads), 0, s, a);
+    else AVAE_LAUNCH((k_score_latent<float>), grid, dim3(kThreads), 0, s, a);
+}
+
+void launch_score_rows(const ScoreRowsArgs& a, hipStream_t s) {
+    if (a.rows <= 0) return;
+    AVAE_LAUNCH(k_score_rows, dim3((a.rows + kScoreRows - 1) / kScoreRows), dim3(kThreads), 0, s, a);
+}
+
 }  // namespace avae

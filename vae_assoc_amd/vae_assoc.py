@@ -526,6 +526,50 @@ class AssocVariationalAutoEncoder(object):
             outs.append(o.cpu().numpy() if was_np else o)
         return outs
 
+    def score_samples(self, X, eps=None, cross_modal=False):
+        """Per-row terms of the training cost, for any number of rows (forward only; avae_score in include/avae.h).
+
+        ``X`` is a list over modalities with equal row counts; ``eps`` an [N, n_z] array shared by every modality, or None for
+        a fresh internal draw.  Returns a dict of ``cost [N]``, ``recon [N, M]``, ``latent [N, M]``, ``assoc [N, P]`` (pairs
+        (i<j) in lexicographic order) and, with ``cross_modal=True``, ``cross [N, M, M]``: cross[n, s, d] is the reconstruction
+        loss of modality d decoded from the posterior mean of modality s.  NumPy in gives NumPy out, device tensors in give
+        device tensors out."""
+        M = len(self.network_architectures)
+        if len(X) != M:
+            raise ValueError("expected a list of %d modalities, got %d" % (M, len(X)))
+        ts, was_np = [], True
+        for m, (x, na) in enumerate(zip(X, self.network_architectures)):
+            t, np_in = self._dev(x, int(na["n_input"]))
+            if m == 0:
+                was_np = np_in
+            if ts and t.shape[0] != ts[0].shape[0]:
+                raise ValueError("every modality needs the same row count: %d vs %d" % (t.shape[0], ts[0].shape[0]))
+            ts.append(t)
+        rows = ts[0].shape[0]
+        e = None
+        if eps is not None:
+            e, _ = self._dev(eps, self.n_z)
+            if e.shape[0] != rows:
+                raise ValueError("eps must be [%d, %d], got %s" % (rows, self.n_z, tuple(e.shape)))
+            e = e.contiguous()
+        flags = _capi.SCORE_CROSS if cross_modal else 0
+        k = C.c_int32(0)
+        _capi.check(None, self._L.avae_score_width(C.byref(self._cfg), flags, C.byref(k)), "avae_score_width")
+        out = torch.empty((rows, k.value), dtype=torch.float32, device=self.device)
+        if rows:
+            ptrs = (C.c_void_p * M)(*[t.data_ptr() for t in ts])
+            lds = (C.c_int32 * M)(*[t.stride(0) if rows > 1 else t.shape[1] for t in ts])
+            _capi.check(self._h, self._L.avae_score(self._h, ptrs, lds, rows, e.data_ptr() if e is not None else None, flags,
+                                                    out.data_ptr(), self._stream()), "avae_score")
+        if was_np:
+            out = out.cpu().numpy()
+        P = M * (M - 1) // 2
+        res = {"cost": out[:, 0], "recon": out[:, 1:1 + M], "latent": out[:, 1 + M:1 + 2 * M],
+               "assoc": out[:, 1 + 2 * M:1 + 2 * M + P]}
+        if cross_modal:
+            res["cross"] = out[:, 1 + 2 * M + P:].reshape(rows, M, M)
+        return res
+
     def save_model(self, fname=None):
         """reference vae_assoc.py:427-435 (default name: timestamp + batch size)."""
         if fname is None:
