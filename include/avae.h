@@ -208,6 +208,22 @@ int avae_score_width(const avae_config* cfg, int32_t flags, int32_t* k);
 int avae_score(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, int32_t rows, const float* eps_dev, int32_t flags,
                float* out_dev, void* stream);
 
+/* ---- importance-weighted log-likelihoods (IWAE, K = n_samples).  Per row n, proposal s (the encoder of modality s on x_s, as
+ * avae_encode gives it), noise eps_k shared by every proposal: z_{s,k} = mu_s + exp(lv_s/2) eps_k (fp32; the decoders read it in the
+ * compute dtype), l_d(z) = -recon_d(x_d, dec_d(z)) with avae_score's recon arithmetic (no weights, no 2 pi constant),
+ * r_{s,k} = sum_j (-z_j^2/2 + eps_j^2/2 + lv_{s,j}/2) = log N(z; 0, I) - log q_s(z | x_s), LSE_k = log-sum-exp over k:
+ *   marginal[s]       LSE_k(l_s(z_{s,k}) + r_{s,k}) - log K                 ~ log p(x_s)
+ *   joint[s]          LSE_k(sum_d l_d(z_{s,k}) + r_{s,k}) - log K           ~ log p(x_1..x_M), proposal q_s
+ *   conditional[s][d] LSE_k l_d(z_{s,k}) - log K                           ~ log p(x_d | x_s) (diagonal included)
+ * out_dev: [rows][2*M + M*M] fp32, row-major: marginal[M] | joint[M] | conditional[M][M] (s-major).
+ * eps_dev: [rows][n_samples][n_z] fp32, or NULL for a fresh Philox draw (keyed like avae_score: per-call draw counter, row of the
+ * whole input, sample index).  n_samples >= 1; rows == 0 is a no-op.  x_dev / x_ld as avae_score.  Worked in passes of at most
+ * batch_size decoded rows (n rows x kb samples); the result depends on batch_size only through the order of the fp32 sums.  As
+ * avae_score, it changes nothing the next training step reads; on a data-parallel replica it covers the local rows, with no
+ * collective. */
+int avae_loglik(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, int32_t rows, int32_t n_samples,
+                const float* eps_dev, float* out_dev, void* stream);
+
 /* save_model / restore_model (vae_assoc.py:427-463): own flat file (config echo + params + Adam
  * slots + step); TF .ckpt files cannot be read offline. */
 int avae_save(avae_handle* h, const char* path);

@@ -400,6 +400,37 @@ struct ScoreRowsArgs {
 };
 void launch_score_rows(const ScoreRowsArgs& a, hipStream_t s);
 
+// Importance-weighted log-likelihoods (avae_loglik).  A pass decodes rows * kc latent samples of ONE proposal src: decoded row
+// i = j * kc + k holds input row j (of the pass) and sample k0 + k.  Same shapes and no-atomics rule as the score kernels.
+struct IwLatentArgs {
+    const float* mulv;              // [rows][2*n_z] fp32 of the proposal's modality
+    const float* eps;               // caller's [all rows][K][n_z] fp32, at the pass's first input row; NULL: Philox
+    float* z32;                     // NULL, or [n_dec][n_z] fp32 (the serve route reads it)
+    void* Z[kMaxMod]; int ldz[kMaxMod]; int n_zdst;   // decoder inputs, compute dtype (the modality-by-modality route)
+    float* r;                       // [n_dec] log N(z;0,I) - log q(z|x)
+    int rows, kc, k0, K, nz;
+    long long row0;                 // Philox: row of the whole input of the pass's first row (row_offset included)
+    unsigned long long seed; unsigned draw;
+};
+void launch_iw_latent(int compute_dtype, const IwLatentArgs& a, hipStream_t s);
+struct IwRowsArgs {
+    const float* xhat[kMaxMod]; int ldh[kMaxMod];           // decoder outputs (p or x_hat) fp32, [n_dec][ldh]
+    const float* x[kMaxMod]; long long ldx[kMaxMod];        // the caller's rows, at the pass's first input row
+    int n_in[kMaxMod], binary[kMaxMod];
+    float* ell;                     // [n_dec][n_mod]: -recon
+    int n_dec, kc, n_mod;
+};
+void launch_iw_rows(const IwRowsArgs& a, hipStream_t s);
+struct IwReduceArgs {
+    const float* ell; const float* r;   // this pass's [n_dec][n_mod], [n_dec]
+    float* state;                   // [rows][n_mod][2 + n_mod][2] running (max, sum exp) per input row of the chunk
+    float* out; int width;          // the caller's rows [rows][width] at the pass's first input row
+    int rows, kc, src, n_mod;
+    int first, last;                // first / last sample block of the row
+    float log_k;
+};
+void launch_iw_reduce(const IwReduceArgs& a, hipStream_t s);
+
 // ---- gradient exchange (avae_comm.hip)
 // One-shot all-reduce over hipIpc peers ("a hand-rolled P2P reduce-scatter/all-gather over hipIpc peers"):
 // every rank owns an exchange block (uncached device memory, mapped by every peer); a range of the gradient buffer is cut into

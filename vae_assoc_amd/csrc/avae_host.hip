@@ -244,6 +244,8 @@ struct avae_handle {
     ServeSlot* serve_ring = nullptr;
     unsigned long long* serve_consumed = nullptr;
     unsigned long long serve_calls = 0;
+    // avae_loglik's scratch, allocated by its first call (z rows, r, log-weights, running log-sum-exp states of one pass)
+    float* iw_buf = nullptr;
     size_t off_chain = 0;
     size_t off_consts = 0, off_conv_tab = 0;   // 32 B {zeros | one, 0...}; device copy of conv_tab
     std::vector<ConvA> conv_tab;             // implicit patch matrices of the training plan
@@ -2668,6 +2670,32 @@ avae_handle::Serve& serve_plan(avae_handle* h, int bucket) {
     return sv;
 }
 
+// One call through a serve plan: sl.rows rows of fp32 z (sl.z) decoded by every modality into sl.out.  Eager: the staging launch
+// (which also runs the decoders' first layer) and the plan's launches; otherwise the staging launch and one graph replay.
+void serve_call(avae_handle* h, avae_handle::Serve& sv, const ServeSlot& sl, bool eager, hipStream_t s) {
+    if (sv.fused_in && sv.lean_in && eager) {          // no graph at all: the staging launch and the plan's launches, eagerly
+        sv.in_lean.call = sl;
+        launch_serve_in(h->cfg.compute_dtype, sv.in_lean, sv.in_lean_grid, s); LAUNCH_OK("serve_in+serve_dec1");
+        run_launches(h, sv.launches, s);
+        return;
+    }
+    if (sv.fused_in && sv.lean_in) {
+        sv.in_lean.call = sl;
+        launch_serve_in(h->cfg.compute_dtype, sv.in_lean, sv.in_lean_grid, s); LAUNCH_OK("serve_in+serve_dec1");
+    } else if (sv.fused_in) {    // the staging launch also runs the decoder's first layer: its items carry the call by value
+        Launch& L = sv.in_launch;
+        for (int m = 0; m < h->M; ++m) {
+            WorkItem& w = L.args.items[m];
+            w.aux0 = sl.z; w.n_slots = sl.rows;
+            w.out0 = sl.out[0]; w.out1 = sl.out[1]; w.out2 = sl.out[2]; w.aux1 = sl.out[3];
+        }
+        launch_grouped(h->cfg.compute_dtype, L.cfg, L.args, L.grid_x, L.grid_y, L.lds, h->state(), s, nullptr, 0); LAUNCH_OK("serve_in+serve_dec1");
+    } else {
+        launch_serve(h->cfg.compute_dtype, sv.in, sl, sv.in.blocks_per_mod * h->M, s); LAUNCH_OK("serve_in");
+    }
+    HIP_OK(hipGraphLaunch(sv.graph, s));
+}
+
 }  // namespace
 
 // ============================================================================= C ABI
@@ -2742,6 +2770,7 @@ void avae_destroy(avae_handle* h) {
     for (int b = 0; b < 2; ++b) for (hipGraphExec_t g : h->g_dp[b]) if (g) (void)hipGraphExecDestroy(g);
     for (avae_handle::Serve& sv : h->serve) { if (sv.graph) (void)hipGraphExecDestroy(sv.graph); for (hipGraphExec_t g : sv.ring_graph) if (g) (void)hipGraphExecDestroy(g); }
     if (h->serve_ring) (void)hipHostFree(h->serve_ring);
+    if (h->iw_buf) (void)hipFree(h->iw_buf);
     if (h->ev_switch) (void)hipEventDestroy(h->ev_switch);
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
     if (h->ev_side) (void)hipEventDestroy(h->ev_side);
@@ -3102,12 +3131,6 @@ int avae_generate(avae_handle* h, const float* z_dev, int32_t rows, float* const
             // of the first kernel reads the call record over PCIe, and the call was never host-bound.  AVAE_SERVE_GRAPH=1 /
             // AVAE_SERVE_RING=1 select the other two for A/B.
             static const bool use_ring = std::getenv("AVAE_SERVE_RING") != nullptr, eager = !use_ring && std::getenv("AVAE_SERVE_GRAPH") == nullptr;
-            if (sv.fused_in && sv.lean_in && eager) {          // no graph at all: the staging launch and the plan's launches, eagerly
-                sv.in_lean.call = sl;
-                launch_serve_in(h->cfg.compute_dtype, sv.in_lean, sv.in_lean_grid, s); LAUNCH_OK("serve_in+serve_dec1");
-                run_launches(h, sv.launches, s);
-                continue;
-            }
             if (sv.fused_in && sv.lean_in && use_ring) {
                 // ONE graph replay per call: the record goes into the pinned ring, the slot's graph starts with the staging launch
                 if (!h->serve_ring) {
@@ -3144,21 +3167,7 @@ int avae_generate(avae_handle* h, const float* z_dev, int32_t rows, float* const
                 ++h->serve_calls;
                 continue;
             }
-            if (sv.fused_in && sv.lean_in) {
-                sv.in_lean.call = sl;
-                launch_serve_in(h->cfg.compute_dtype, sv.in_lean, sv.in_lean_grid, s); LAUNCH_OK("serve_in+serve_dec1");
-            } else if (sv.fused_in) {    // the staging launch also runs the decoder's first layer: its items carry the call by value
-                Launch& L = sv.in_launch;
-                for (int m = 0; m < h->M; ++m) {
-                    WorkItem& w = L.args.items[m];
-                    w.aux0 = sl.z; w.n_slots = sl.rows;
-                    w.out0 = sl.out[0]; w.out1 = sl.out[1]; w.out2 = sl.out[2]; w.aux1 = sl.out[3];
-                }
-                launch_grouped(h->cfg.compute_dtype, L.cfg, L.args, L.grid_x, L.grid_y, L.lds, h->state(), s, nullptr, 0); LAUNCH_OK("serve_in+serve_dec1");
-            } else {
-                launch_serve(h->cfg.compute_dtype, sv.in, sl, sv.in.blocks_per_mod * h->M, s); LAUNCH_OK("serve_in");
-            }
-            HIP_OK(hipGraphLaunch(sv.graph, s));
+            serve_call(h, sv, sl, eager, s);
         }
     });
 }
@@ -3269,6 +3278,110 @@ int avae_score(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, i
                     ra.x = x_dev[d] + (size_t)r0 * ld[d]; ra.ldx = ld[d];
                     run_inference(h, d, false, n, s);
                     score_rows(d, 1 + 2 * M + P + src * M + d, false, n);
+                }
+            }
+        }
+    });
+}
+
+// Importance-weighted log-likelihoods.  Passes of at most batch_size decoded rows: n input rows x kb samples (K >= B: one row and
+// kb = B per pass, the row spanning several passes; else n = B / K rows and kb = K).  Per chunk of n rows: stage + encode every
+// modality once; per sample block and proposal src: k_iw_latent (z, r) -> every decoder (grouped launches of the serve route, or
+// modality by modality for conv nets / use_graph = 0 / timing) -> k_iw_rows (log-weights) -> k_iw_reduce (running log-sum-exp;
+// the row's last block writes the caller's row).  Scratch: iw_buf (allocated once) and the decoders' out32 / Z buffers.
+int avae_loglik(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, int32_t rows, int32_t n_samples,
+                const float* eps_dev, float* out_dev, void* stream) {
+    return guarded(h, [&] {
+        if (rows < 0) throw Err("avae_loglik: rows must be >= 0");
+        if (n_samples < 1) throw Err("avae_loglik: n_samples must be >= 1, got " + std::to_string(n_samples));
+        if (rows == 0) return;
+        if (!out_dev) throw Err("avae_loglik: out_dev is NULL");
+        if (!x_dev) throw Err("avae_loglik: x_dev is NULL");
+        const int M = h->M, B = h->B, nz = h->nz, K = n_samples;
+        int ld[kMaxMod];
+        for (int m = 0; m < M; ++m) {
+            if (!x_dev[m]) throw Err("avae_loglik: x_dev[" + std::to_string(m) + "] is NULL");
+            ld[m] = x_ld ? x_ld[m] : h->mods[m].n_in;
+            if (ld[m] < h->mods[m].n_in)
+                throw Err("avae_loglik: x_ld[" + std::to_string(m) + "] = " + std::to_string(ld[m]) + " is below n_input = " + std::to_string(h->mods[m].n_in));
+        }
+        hipStream_t s = on_stream(h, stream);
+        const int width = 2 * M + M * M;
+        const int n_rows = K >= B ? 1 : B / K, kb = K >= B ? B : K;
+        const size_t z_n = (size_t)B * nz, r_n = (size_t)B, ell_n = (size_t)B * M, st_n = (size_t)B * M * (2 + M) * 2;
+        if (!h->iw_buf) HIP_OK(hipMalloc(reinterpret_cast<void**>(&h->iw_buf), (z_n + r_n + ell_n + st_n) * sizeof(float)));
+        float* z32 = h->iw_buf;
+        float* rbuf = z32 + z_n;
+        float* ell = rbuf + r_n;
+        float* state = ell + ell_n;
+        bool any_conv = false;
+        for (const Mod& md : h->mods) any_conv = any_conv || md.conv;
+        const bool by_mod = any_conv || !h->cfg.use_graph || h->timing;     // as avae_generate
+        static const bool eager = std::getenv("AVAE_SERVE_GRAPH") == nullptr;
+        // a fresh eps per call, keyed as avae_score's: draw counter, row of the whole input (+ the sample index)
+        const unsigned draw = eps_dev ? 0u : (++h->draw_id) & 0x3FFFFFu;
+        IwLatentArgs la;
+        std::memset(&la, 0, sizeof(la));
+        la.nz = nz; la.K = K; la.seed = h->cfg.seed; la.draw = draw; la.r = rbuf;
+        if (by_mod) {
+            la.n_zdst = M;
+            for (int m = 0; m < M; ++m) { la.Z[m] = h->at<void>(h->mods[m].Z.rm); la.ldz[m] = h->mods[m].Z.ld; }
+        } else {
+            la.z32 = z32;
+        }
+        IwRowsArgs ra;
+        std::memset(&ra, 0, sizeof(ra));
+        ra.ell = ell; ra.n_mod = M;
+        ServeSlot sl;
+        std::memset(&sl, 0, sizeof(sl));
+        sl.z = z32;
+        for (int m = 0; m < M; ++m) {
+            const Mod& md = h->mods[m];
+            ra.xhat[m] = h->at<float>(md.out32);
+            ra.ldh[m] = by_mod ? md.ld32 : md.n_in;           // the serve route stores dense [rows][n_input]
+            ra.n_in[m] = md.n_in; ra.binary[m] = h->cfg.mod[m].binary ? 1 : 0;
+            sl.out[m] = h->at<float>(md.out32);
+        }
+        IwReduceArgs rd;
+        std::memset(&rd, 0, sizeof(rd));
+        rd.ell = ell; rd.r = rbuf; rd.state = state; rd.width = width; rd.n_mod = M; rd.log_k = std::log((float)K);
+        for (int r0 = 0; r0 < rows; r0 += n_rows) {
+            const int n = std::min(n_rows, rows - r0);
+            for (int m = 0; m < M; ++m) {
+                const Mod& md = h->mods[m];
+                run_prep_single(h, x_dev[m] + (size_t)r0 * ld[m], ld[m], n, md.n_in, md.X0, nullptr, 0, false, nullptr, 0, s, r0);
+                run_inference(h, m, true, n, s);
+                ra.x[m] = x_dev[m] + (size_t)r0 * ld[m]; ra.ldx[m] = ld[m];
+            }
+            la.eps = eps_dev ? eps_dev + (size_t)r0 * K * nz : nullptr;
+            la.row0 = (long long)h->cfg.row_offset + r0;
+            rd.out = out_dev + (size_t)r0 * width;
+            la.rows = rd.rows = n;
+            for (int k0 = 0; k0 < K; k0 += kb) {
+                const int kc = std::min(kb, K - k0), nd = n * kc;
+                la.k0 = k0; la.kc = ra.kc = rd.kc = kc; ra.n_dec = nd;
+                rd.first = k0 == 0; rd.last = k0 + kc == K;
+                for (int src = 0; src < M; ++src) {
+                    la.mulv = h->at<float>(h->mods[src].mulv);
+                    {
+                        Timed t(h, s, "iw_latent");
+                        launch_iw_latent(h->cfg.compute_dtype, la, s); LAUNCH_OK("iw_latent");
+                    }
+                    if (by_mod) {
+                        for (int d = 0; d < M; ++d) run_inference(h, d, false, nd, s);
+                    } else {
+                        sl.rows = nd;
+                        serve_call(h, serve_plan(h, (nd <= 64 && B > 64) ? 64 : B), sl, eager, s);
+                    }
+                    {
+                        Timed t(h, s, "iw_rows");
+                        launch_iw_rows(ra, s); LAUNCH_OK("iw_rows");
+                    }
+                    rd.src = src;
+                    {
+                        Timed t(h, s, "iw_reduce");
+                        launch_iw_reduce(rd, s); LAUNCH_OK("iw_reduce");
+                    }
                 }
             }
         }

@@ -3453,4 +3453,158 @@ void launch_score_rows(const ScoreRowsArgs& a, hipStream_t s) {
     AVAE_LAUNCH(k_score_rows, dim3((a.rows + kScoreRows - 1) / kScoreRows), dim3(kThreads), 0, s, a);
 }
 
+// ------------------------------------------------------------------ importance-weighted log-likelihoods (avae_loglik)
+// One wave per decoded row i = j * kc + k (input row j of the pass, sample k0 + k), one lane per latent dimension (n_z <= 64):
+// eps (the caller's, or Philox keyed by (row of the whole input, dim quad | draw << 8, sample, 'iwll')), z = mu + exp(lv/2) eps
+// in fp32 as k_score_latent forms it, into the fp32 z rows the serve route reads or into every decoder input (compute dtype),
+// and r = sum_j (-z^2/2 + eps^2/2 + lv/2) = log N(z;0,I) - log q(z|x) from the fp32 z.
+template <typename CT>
+__global__ void __launch_bounds__(kThreads) k_iw_latent(IwLatentArgs a) {
+#pragma clang fp contract(off)
+    const int i = blockIdx.x * kScoreRows + (threadIdx.x >> 6), d = threadIdx.x & 63;
+    if (i >= a.rows * a.kc) return;                // wave-uniform
+    const int j = i / a.kc, k = a.k0 + (i - j * a.kc), nz = a.nz;
+    const bool on = d < nz;
+    float mu = 0.0f, lv = 0.0f, e = 0.0f;
+    if (on) {
+        mu = a.mulv[(size_t)j * 2 * nz + d];
+        lv = a.mulv[(size_t)j * 2 * nz + nz + d];
+        if (a.eps) {
+            e = a.eps[((size_t)j * a.K + k) * nz + d];
+        } else {
+            unsigned r[4];
+            philox4x32_10((unsigned)(a.row0 + j), (unsigned)(d >> 2) | (a.draw << 8), (unsigned)k, 0x69776c6cu /*iwll*/,
+                          (unsigned)a.seed, (unsigned)(a.seed >> 32), r);
+            // k_prep's Box-Muller; lane d takes element d & 3 of its quad
+            const unsigned ua = (d & 2) ? r[2] : r[0], ub = (d & 2) ? r[3] : r[1];
+            const float u0 = ((ua >> 8) + 0.5f) * (1.0f / 16777216.0f), u1 = ((ub >> 8) + 0.5f) * (1.0f / 16777216.0f);
+            const float ra = sqrtf(-2.0f * flog(u0));
+            e = ra * ((d & 1) ? __builtin_amdgcn_sinf(u1) : __builtin_amdgcn_cosf(u1));
+        }
+    }
+    const float z = __builtin_fmaf(fexp(0.5f * lv), e, mu);
+    float t = -0.5f * z * z;
+    t += 0.5f * e * e;
+    t += 0.5f * lv;
+    const float r = wave_sum(on ? t : 0.0f);
+    if (on) {
+        if (a.z32) a.z32[(size_t)i * nz + d] = z;
+        for (int m = 0; m < a.n_zdst; ++m) reinterpret_cast<CT*>(a.Z[m])[(size_t)i * a.ldz[m] + d] = to_ct<CT>(z);
+    }
+    if (d == 0) a.r[i] = r;
+}
+
+// l_d = -recon_d of one decoded row for one modality: k_score_rows' loop (the same arithmetic, contraction off), one wave per
+// (decoded row, modality), modality-major.
+__global__ void __launch_bounds__(kThreads) k_iw_rows(IwRowsArgs a) {
+#pragma clang fp contract(off)
+    const int g = blockIdx.x * kScoreRows + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (g >= a.n_dec * a.n_mod) return;            // wave-uniform
+    const int m = g / a.n_dec, i = g - m * a.n_dec;
+    const float* xh = a.xhat[m] + (size_t)i * a.ldh[m];
+    const float* x = a.x[m] + (size_t)(i / a.kc) * a.ldx[m];
+    const int n_in = a.n_in[m];
+    float acc = 0.0f;
+    if (a.binary[m]) {
+        for (int c = lane; c < n_in; c += 64) {
+            const float p = xh[c], xv = x[c];
+            const float lp = 1e-3f + p, lq = 1e-3f + 1.0f - p;
+            acc += -(xv * flog(lp) + (1.0f - xv) * flog(lq));
+        }
+    } else {
+        for (int c = lane; c < n_in; c += 64) {
+            float sl, da;
+            loss_gauss(xh[c], x[c], 1.0f, sl, da);
+            acc += sl;
+        }
+    }
+    const float r = wave_sum(acc);
+    if (lane == 0) a.ell[(size_t)i * a.n_mod + m] = -r;
+}
+
+// Merge of two log-sum-exp states (max, sum of exp(v - max)); an empty state is (-inf, 0).  NaN on either side makes the result NaN
+// (fmaxf alone would drop it).
+__device__ __forceinline__ void lse_merge(float& m, float& s, float m2, float s2) {
+#pragma clang fp contract(off)
+    if (m != m || m2 != m2) { m = s = __builtin_nanf(""); return; }
+    const float mx = fmaxf(m, m2);
+    if (mx == -__builtin_inff()) return;
+    s = s * expf(m - mx) + s2 * expf(m2 - mx);
+    m = mx;
+}
+
+// One wave per input row of the pass (proposal src): the pass's kc log-weights of the 2 + M outputs (marginal, joint, conditional
+// [src][d]), lanes strided over the samples, then a fixed-order shuffle tree, then behind the row's running state (first block: no
+// state); the last block writes max + log(sum) - log K into the caller's row.
+__global__ void __launch_bounds__(kThreads) k_iw_reduce(IwReduceArgs a) {
+    constexpr int NQ = 2 + kMaxMod;
+    const int j = blockIdx.x * kScoreRows + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (j >= a.rows) return;                       // wave-uniform
+    const int M = a.n_mod, nq = 2 + M;
+    float mx[NQ], sm[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) { mx[q] = -__builtin_inff(); sm[q] = 0.0f; }
+    for (int k = lane; k < a.kc; k += 64) {
+        const int i = j * a.kc + k;
+        const float* e = a.ell + (size_t)i * M;
+        const float rr = a.r[i];
+        float v[NQ], tot = 0.0f;
+#pragma unroll
+        for (int d = 0; d < kMaxMod; ++d) {
+            v[2 + d] = 0.0f;
+            if (d < M) { v[2 + d] = e[d]; tot += e[d]; }
+        }
+        v[0] = e[a.src] + rr;
+        v[1] = tot + rr;
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) if (q < nq) lse_merge(mx[q], sm[q], v[q], 1.0f);
+    }
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+        if (q >= nq) continue;                     // wave-uniform
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float m2 = __shfl_down(mx[q], o, 64), s2 = __shfl_down(sm[q], o, 64);
+            lse_merge(mx[q], sm[q], m2, s2);
+        }
+    }
+    if (lane != 0) return;
+    float* st = a.state + (size_t)(j * M + a.src) * nq * 2;
+    float* orow = a.out + (size_t)j * a.width;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+        if (q >= nq) continue;
+        float m = mx[q], s = sm[q];
+        if (!a.first) {
+            m = st[2 * q]; s = st[2 * q + 1];
+            lse_merge(m, s, mx[q], sm[q]);
+        }
+        if (a.last) {
+            const int col = q == 0 ? a.src : q == 1 ? M + a.src : 2 * M + a.src * M + (q - 2);
+            orow[col] = m + logf(s) - a.log_k;
+        } else {
+            st[2 * q] = m; st[2 * q + 1] = s;
+        }
+    }
+}
+
+void launch_iw_latent(int compute_dtype, const IwLatentArgs& a, hipStream_t s) {
+    const int n = a.rows * a.kc;
+    if (n <= 0) return;
+    const dim3 grid((n + kScoreRows - 1) / kScoreRows);
+    if (compute_dtype == AVAE_BF16) AVAE_LAUNCH((k_iw_latent<__bf16>), grid, dim3(kThreads), 0, s, a);
+    else AVAE_LAUNCH((k_iw_latent<float>), grid, dim3(kThreads), 0, s, a);
+}
+
+void launch_iw_rows(const IwRowsArgs& a, hipStream_t s) {
+    const int n = a.n_dec * a.n_mod;
+    if (n <= 0) return;
+    AVAE_LAUNCH(k_iw_rows, dim3((n + kScoreRows - 1) / kScoreRows), dim3(kThreads), 0, s, a);
+}
+
+void launch_iw_reduce(const IwReduceArgs& a, hipStream_t s) {
+    if (a.rows <= 0) return;
+    AVAE_LAUNCH(k_iw_reduce, dim3((a.rows + kScoreRows - 1) / kScoreRows), dim3(kThreads), 0, s, a);
+}
+
 }  // namespace avae

@@ -570,6 +570,49 @@ class AssocVariationalAutoEncoder(object):
             res["cross"] = out[:, 1 + 2 * M + P:].reshape(rows, M, M)
         return res
 
+    def log_likelihood(self, X, n_samples=64, eps=None):
+        """Importance-weighted (IWAE) estimates of held-out log-likelihoods with K = ``n_samples`` samples per proposal (forward
+        only; avae_loglik in include/avae.h).
+
+        ``X`` is a list over modalities with equal row counts; ``eps`` an [N, n_samples, n_z] array (sample k of row n is shared by
+        every proposal), or None for a fresh internal draw.  The proposal of modality s is its encoder's posterior q_s(z | x_s);
+        the reconstruction terms are score_samples' (Bernoulli with the 1e-3 inside the log, Gaussian 0.5 ||x - x_hat||^2 without
+        the 2 pi constant; no modality weights, no assoc_lambda).  Returns a dict of natural-log estimates:
+        ``marginal [N, M]`` (log p(x_m), proposal q_m), ``joint [N, M]`` (log p(x_1..x_M), proposal q_s) and ``conditional
+        [N, M, M]``: conditional[n, s, d] estimates log p(x_d | x_s) = log E_{q_s}[p(x_d | z)], the diagonal included.  NumPy in
+        gives NumPy out, device tensors in give device tensors out.  Under data parallelism each replica scores its own rows:
+        there is no collective."""
+        M = len(self.network_architectures)
+        if len(X) != M:
+            raise ValueError("expected a list of %d modalities, got %d" % (M, len(X)))
+        if isinstance(n_samples, bool) or not isinstance(n_samples, (int, np.integer)) or n_samples < 1:
+            raise ValueError("n_samples must be an integer >= 1, got %r" % (n_samples,))
+        K = int(n_samples)
+        ts, was_np = [], True
+        for m, (x, na) in enumerate(zip(X, self.network_architectures)):
+            t, np_in = self._dev(x, int(na["n_input"]))
+            if m == 0:
+                was_np = np_in
+            if ts and t.shape[0] != ts[0].shape[0]:
+                raise ValueError("every modality needs the same row count: %d vs %d" % (t.shape[0], ts[0].shape[0]))
+            ts.append(t)
+        rows = ts[0].shape[0]
+        e = None
+        if eps is not None:
+            e = torch.as_tensor(np.asarray(eps, dtype=np.float32) if not torch.is_tensor(eps) else eps)
+            if tuple(e.shape) != (rows, K, self.n_z):
+                raise ValueError("eps must be [%d, %d, %d], got %s" % (rows, K, self.n_z, tuple(e.shape)))
+            e = e.to(device=self.device, dtype=torch.float32).contiguous()
+        out = torch.empty((rows, 2 * M + M * M), dtype=torch.float32, device=self.device)
+        if rows:
+            ptrs = (C.c_void_p * M)(*[t.data_ptr() for t in ts])
+            lds = (C.c_int32 * M)(*[t.stride(0) if rows > 1 else t.shape[1] for t in ts])
+            _capi.check(self._h, self._L.avae_loglik(self._h, ptrs, lds, rows, K, e.data_ptr() if e is not None else None,
+                                                     out.data_ptr(), self._stream()), "avae_loglik")
+        if was_np:
+            out = out.cpu().numpy()
+        return {"marginal": out[:, :M], "joint": out[:, M:2 * M], "conditional": out[:, 2 * M:].reshape(rows, M, M)}
+
     def save_model(self, fname=None):
         """reference vae_assoc.py:427-435 (default name: timestamp + batch size)."""
         if fname is None:
