@@ -58,14 +58,17 @@ def build_pair(V, archs, binary, weights, lam, act, B, dtype, lr=1e-3, p0=None, 
     return model, ref
 
 
-def check_step_parity(V, archs, binary, weights, lam, act, B, dtype, steps=3, seed=5, ref_config=False, drift_tol=None, **kw):
+def check_step_parity(V, archs, binary, weights, lam, act, B, dtype, steps=3, seed=5, ref_config=False, drift_tol=None,
+                      adam_rel=False, **kw):
     """HIP path vs oracle on the same weights / inputs / eps.
 
     fp32 operands: against the fp64 oracle at the fp32 tolerances of the module docstring.
     bf16 operands: (1) against the oracle run with quant='bf16', which rounds at exactly the points
     the kernels round (same relu decisions), tightly -- this is the correctness check of the bf16
     kernels; (2) against the plain fp64 oracle at the north_star tolerances (cost 1e-3 relative on the
-    reference configurations, mu/lv 2e-2 absolute) -- this is the measured price of bf16 operands."""
+    reference configurations, mu/lv 2e-2 absolute) -- this is the measured price of bf16 operands.
+    adam_rel: the Adam arithmetic bound 6e-8 is taken relative to max(1, |theta|) per element (fp32 resolves only ~5e-7 at
+    |theta| = 8-16, e.g. the head biases of posteriors far from the prior)."""
     fp32 = dtype == "fp32"
     lr = 1e-3
     rng = np.random.default_rng(seed + 100)
@@ -112,7 +115,9 @@ def check_step_parity(V, archs, binary, weights, lam, act, B, dtype, steps=3, se
             assert not bad, "gradient mismatch (rel to tensor max): %s" % bad
             # Adam arithmetic, decoupled from gradient conditioning: TF-1 update of p0 with the HIP gradient
             th1, _, _ = O.adam_step(p0, np.zeros_like(p0), np.zeros_like(p0), g.astype(np.float64), 1, lr)
-            assert np.abs(model.get_params() - th1).max() <= 6e-8, "Adam update arithmetic"
+            bound = 6e-8 * (np.maximum(1.0, np.abs(th1)) if adam_rel else 1.0)
+            assert np.all(np.abs(model.get_params() - th1) <= bound), "Adam update arithmetic: max err %.3e" % (
+                np.abs(model.get_params() - th1).max())
             for m in range(len(archs)):          # mu / lv of the training forward pass
                 mulv = fetch(model, "mulv%d" % m, (B, 2 * nz))
                 scale = max(1.0, np.abs(fw[m]["lv"]).max(), np.abs(fw[m]["mu"]).max())
