@@ -56,7 +56,6 @@ struct DeviceGuard {
         if (e_ != hipSuccess) throw Err(std::string("launch of ") + (what) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
-constexpr int kServeRing = 16;         // call records in the serving path's pinned-host ring (= graphs per serving plan, one per slot)
 constexpr int kMultiSteps = 16;         // most whole steps per replay of a multi-step graph (avae_train_steps) = staging sets
 constexpr int kMultiSizes[2] = {16, 4};  // captured replay lengths: a run of n batches goes 16,16,...,4,4,...,1,1
 
@@ -230,20 +229,13 @@ struct avae_handle {
     // inference tables: per modality, device slots at off_inf
     struct Inf { std::vector<WorkItem> items; std::vector<Launch> launches; int rows = -1; size_t dev_off = 0; };
     std::vector<Inf> inf_enc, inf_dec;
-    // serving (avae_generate): per row bucket one staging launch per call + one captured graph of [grouped decoder launches of all
-    // modalities, slot-indirect output move]
+    // serving (avae_generate): per row bucket one staging launch per call + the grouped decoder launches of all modalities (eager
+    // after k_serve_in, else one captured graph) with a slot-indirect output move
     struct Serve { int bucket = 0; std::vector<WorkItem> items; std::vector<Launch> launches; hipGraphExec_t graph = nullptr; ServeArgs in;
                    Launch in_launch; bool fused_in = false;
-                   ServeInArgs in_lean; int in_lean_grid = 0; bool lean_in = false;
-                   hipGraphExec_t ring_graph[kServeRing] = {}; };       // [staging launch reading ring record i, the plan's launches]
+                   ServeInArgs in_lean; int in_lean_grid = 0; bool lean_in = false; };
     std::vector<Serve> serve;
-    size_t off_slot = 0, off_serve_count = 0;
-    // Serving without a per-call eager launch: the call's record {z, rows, outputs} goes into a slot of a pinned-host ring and the
-    // graph of that slot is replayed -- its first kernel reads the record over PCIe.  `consumed` (pinned too) is the device's count
-    // of records read: the host never runs more than the ring ahead of it.
-    ServeSlot* serve_ring = nullptr;
-    unsigned long long* serve_consumed = nullptr;
-    unsigned long long serve_calls = 0;
+    size_t off_slot = 0;
     // avae_loglik's scratch, allocated by its first call (z rows, r, log-weights, running log-sum-exp states of one pass)
     float* iw_buf = nullptr;
     size_t off_chain = 0;
@@ -260,7 +252,7 @@ struct avae_handle {
     hipStream_t last_stream = nullptr;
     bool has_last_stream = false;
     hipEvent_t ev_switch = nullptr;
-    unsigned draw_id = 0;                   // eval / reconstruct calls that drew their own eps (keys the generator: a fresh draw per call)
+    unsigned draw_id = 0;                   // forward-only calls that drew their own eps (next_draw: keys the generator, a fresh draw per call)
     bool timing = false;
     bool debug_sync = false;
     std::vector<std::string> tnames;
@@ -594,7 +586,6 @@ void plan_memory(avae_handle* h) {
     h->off_adam = b.take(n_adam * sizeof(AdamItem));
     h->off_adam_b = b.take(n_adam * sizeof(AdamItem));
     h->off_slot = b.take(sizeof(ServeSlot));
-    h->off_serve_count = b.take(8);
     h->off_consts = b.take(32);
     h->off_chain = b.take((kMaxMod * 64 + 1) * 4);      // k_chain2: a ticket counter per (modality, row block), + its error word
     h->off_conv_tab = b.take(4 * kMaxConvA * kMaxMod * sizeof(ConvA));
@@ -2592,7 +2583,7 @@ void dp_step(avae_handle* h, int j, hipStream_t s, bool direct = false) {
 }
 
 // ----------------------------------------------------------------------------- serving
-// generate() of every (MLP) modality as ONE graph replay per call (the reference's CEM / GUI callers decode
+// generate() of every (MLP) modality in one submission per call (the reference's CEM / GUI callers decode
 // 10-50 times per iteration, baxter_vae_assoc_writer.py:141-147,259-304, vae_assoc_model_viewer.py:107-113).
 avae_handle::Serve& serve_plan(avae_handle* h, int bucket) {
     for (avae_handle::Serve& sv : h->serve) if (sv.bucket == bucket) return sv;
@@ -2662,27 +2653,27 @@ avae_handle::Serve& serve_plan(avae_handle* h, int bucket) {
     }
     a.blocks_per_mod = std::max(1, std::min(8, (bucket * h->nz + kThreads - 1) / kThreads));
     sv.in = a;                                                   // the per-call staging launch (ahead of the graph)
-    auto body = [&](hipStream_t cs) { run_launches(h, sv.launches, cs); };
-    const bool tsave = h->timing;
-    h->timing = false;
-    sv.graph = capture(h, body);
-    h->timing = tsave;
+    if (!(sv.fused_in && sv.lean_in)) {                          // serve_call replays a graph of the remaining launches
+        const bool tsave = h->timing;
+        h->timing = false;
+        sv.graph = capture(h, [&](hipStream_t cs) { run_launches(h, sv.launches, cs); });
+        h->timing = tsave;
+    }
     return sv;
 }
 
-// One call through a serve plan: sl.rows rows of fp32 z (sl.z) decoded by every modality into sl.out.  Eager: the staging launch
-// (which also runs the decoders' first layer) and the plan's launches; otherwise the staging launch and one graph replay.
-void serve_call(avae_handle* h, avae_handle::Serve& sv, const ServeSlot& sl, bool eager, hipStream_t s) {
-    if (sv.fused_in && sv.lean_in && eager) {          // no graph at all: the staging launch and the plan's launches, eagerly
+// One call through a serve plan: sl.rows rows of fp32 z (sl.z) decoded by every modality into sl.out.  With k_serve_in (which also
+// runs the decoders' first layer): that launch and the plan's launches, eagerly.  Measured (tools/serve_latency.py, one box, 1 / 64
+// rows, C ABI back to back, us per call): 14.6 / 15.6 eager against 19.1 / 19.9 for the staging launch + a graph replay of the rest,
+// GPU-bound at three dependent kernels and a replay boundary of ~5 us.  Every other plan: its staging launch and one graph replay.
+void serve_call(avae_handle* h, avae_handle::Serve& sv, const ServeSlot& sl, hipStream_t s) {
+    if (sv.fused_in && sv.lean_in) {
         sv.in_lean.call = sl;
         launch_serve_in(h->cfg.compute_dtype, sv.in_lean, sv.in_lean_grid, s); LAUNCH_OK("serve_in+serve_dec1");
         run_launches(h, sv.launches, s);
         return;
     }
-    if (sv.fused_in && sv.lean_in) {
-        sv.in_lean.call = sl;
-        launch_serve_in(h->cfg.compute_dtype, sv.in_lean, sv.in_lean_grid, s); LAUNCH_OK("serve_in+serve_dec1");
-    } else if (sv.fused_in) {    // the staging launch also runs the decoder's first layer: its items carry the call by value
+    if (sv.fused_in) {           // the staging launch also runs the decoder's first layer: its items carry the call by value
         Launch& L = sv.in_launch;
         for (int m = 0; m < h->M; ++m) {
             WorkItem& w = L.args.items[m];
@@ -2694,6 +2685,56 @@ void serve_call(avae_handle* h, avae_handle::Serve& sv, const ServeSlot& sl, boo
         launch_serve(h->cfg.compute_dtype, sv.in, sl, sv.in.blocks_per_mod * h->M, s); LAUNCH_OK("serve_in");
     }
     HIP_OK(hipGraphLaunch(sv.graph, s));
+}
+
+// The serve plan's row bucket for a call of n <= batch_size rows: the CEM / GUI callers' 1-64 rows, or a batch-sized chunk.
+int serve_bucket(const avae_handle* h, int n) { return (n <= 64 && h->B > 64) ? 64 : h->B; }
+
+// Conv decoders (and the diagnostic modes) decode modality by modality instead of through a serve plan.
+bool decode_by_mod(const avae_handle* h) {
+    for (const Mod& md : h->mods) if (md.conv) return true;
+    return !h->cfg.use_graph || h->timing;
+}
+
+// A fresh eps per call, as each sess.run of the reference draws one (vae_assoc.py:90,388-391): the handle's 22-bit draw counter
+// keys the generator; 0 when the caller gives eps.  Each caller places it in its own salt.
+unsigned next_draw(avae_handle* h, const float* eps_dev) { return eps_dev ? 0u : (++h->draw_id) & 0x3FFFFFu; }
+
+void run_inference(avae_handle* h, int m, bool enc, int rows, hipStream_t s) {
+    build_inference(h, m, enc, rows);
+    avae_handle::Inf& inf = enc ? h->inf_enc[m] : h->inf_dec[m];
+    run_launches(h, inf.launches, s);          // items travel by value in the kernel arguments
+}
+
+// n decoded rows of modality m (out32, padded rows) -> dense caller rows
+void copy_out32(avae_handle* h, int m, float* dst, int n, hipStream_t s) {
+    const Mod& md = h->mods[m];
+    copy_rows(dst, (size_t)md.n_in * 4, h->at<float>(md.out32), (size_t)md.ld32 * 4, (size_t)md.n_in * 4, n, s);
+}
+
+// rows rows of fp32 z (dense [rows][n_z]) through modality m's decoder into xhat (dense [rows][n_input]), batch_size at a time
+void decode_rows(avae_handle* h, int m, const float* z, int rows, float* xhat, hipStream_t s) {
+    const Mod& md = h->mods[m];
+    for (int r0 = 0; r0 < rows; r0 += h->B) {
+        const int n = std::min(h->B, rows - r0);
+        run_prep_single(h, z + (size_t)r0 * h->nz, h->nz, n, h->nz, md.Z, nullptr, 0, false, nullptr, 0, s);
+        run_inference(h, m, false, n, s);
+        copy_out32(h, m, xhat + (size_t)r0 * md.n_in, n, s);
+    }
+}
+
+// The row inputs of avae_score / avae_loglik: out_dev, x_dev and x_ld of every modality (x_ld NULL: dense rows) -> ld[]
+void check_row_inputs(const avae_handle* h, const char* what, const float* const* x_dev, const int32_t* x_ld, const float* out_dev,
+                      int* ld) {
+    const std::string w = what;
+    if (!out_dev) throw Err(w + ": out_dev is NULL");
+    if (!x_dev) throw Err(w + ": x_dev is NULL");
+    for (int m = 0; m < h->M; ++m) {
+        if (!x_dev[m]) throw Err(w + ": x_dev[" + std::to_string(m) + "] is NULL");
+        ld[m] = x_ld ? x_ld[m] : h->mods[m].n_in;
+        if (ld[m] < h->mods[m].n_in)
+            throw Err(w + ": x_ld[" + std::to_string(m) + "] = " + std::to_string(ld[m]) + " is below n_input = " + std::to_string(h->mods[m].n_in));
+    }
 }
 
 }  // namespace
@@ -2768,8 +2809,7 @@ void avae_destroy(avae_handle* h) {
     (void)hipDeviceSynchronize();
     for (hipGraphExec_t g : {h->g_full, h->g_multi[0], h->g_multi[1], h->g_eval}) if (g) (void)hipGraphExecDestroy(g);
     for (int b = 0; b < 2; ++b) for (hipGraphExec_t g : h->g_dp[b]) if (g) (void)hipGraphExecDestroy(g);
-    for (avae_handle::Serve& sv : h->serve) { if (sv.graph) (void)hipGraphExecDestroy(sv.graph); for (hipGraphExec_t g : sv.ring_graph) if (g) (void)hipGraphExecDestroy(g); }
-    if (h->serve_ring) (void)hipHostFree(h->serve_ring);
+    for (avae_handle::Serve& sv : h->serve) if (sv.graph) (void)hipGraphExecDestroy(sv.graph);
     if (h->iw_buf) (void)hipFree(h->iw_buf);
     if (h->ev_switch) (void)hipEventDestroy(h->ev_switch);
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
@@ -3048,19 +3088,11 @@ int avae_cost_history(avae_handle* h, int32_t n, float* host_dst, int64_t* last_
 int avae_eval_cost(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, const float* eps_dev, float* cost_host, void* stream) {
     return guarded(h, [&] {
         hipStream_t s = on_stream(h, stream);
-        // a fresh eps per call, as each sess.run of the reference draws one (vae_assoc.py:90,388-391): the draw counter keys it
-        const unsigned long long draw = eps_dev ? 0ull : (unsigned long long)((++h->draw_id) & 0x3FFFFFu) << 34;
-        run_prep_batch(h, x_dev, x_ld, eps_dev, h->B, 0x6576616cull /*eval*/ | draw, s);
+        run_prep_batch(h, x_dev, x_ld, eps_dev, h->B, 0x6576616cull /*eval*/ | (unsigned long long)next_draw(h, eps_dev) << 34, s);
         if (h->g_eval && !h->timing) HIP_OK(hipGraphLaunch(h->g_eval, s));
         else { run_launches(h, h->fwd, s); run_launches(h, std::vector<Launch>{h->cost_only}, s); }
         fetch_cost(h, cost_host, false, s);
     });
-}
-
-static void run_inference(avae_handle* h, int m, bool enc, int rows, hipStream_t s) {
-    build_inference(h, m, enc, rows);
-    avae_handle::Inf& inf = enc ? h->inf_enc[m] : h->inf_dec[m];
-    run_launches(h, inf.launches, s);          // items travel by value in the kernel arguments
 }
 
 int avae_encode(avae_handle* h, int32_t m, const float* x_dev, int32_t x_ld, int32_t rows, float* mu_dev, float* logvar_dev, void* stream) {
@@ -3085,14 +3117,7 @@ int avae_decode(avae_handle* h, int32_t m, const float* z_dev, int32_t rows, flo
     return guarded(h, [&] {
         if (m < 0 || m >= h->M) throw Err("modality index out of range");
         if (rows < 0) throw Err("rows must be >= 0");
-        hipStream_t s = on_stream(h, stream);
-        const Mod& md = h->mods[m];
-        for (int r0 = 0; r0 < rows; r0 += h->B) {
-            const int n = std::min(h->B, rows - r0);
-            run_prep_single(h, z_dev + (size_t)r0 * h->nz, h->nz, n, h->nz, md.Z, nullptr, 0, false, nullptr, 0, s);
-            run_inference(h, m, false, n, s);
-            copy_rows(xhat_dev + (size_t)r0 * md.n_in, (size_t)md.n_in * 4, h->at<float>(md.out32), (size_t)md.ld32 * 4, (size_t)md.n_in * 4, n, s);
-        }
+        decode_rows(h, m, z_dev, rows, xhat_dev, on_stream(h, stream));
     });
 }
 
@@ -3101,73 +3126,17 @@ int avae_generate(avae_handle* h, const float* z_dev, int32_t rows, float* const
         if (rows < 0) throw Err("rows must be >= 0");
         if (!z_dev || !xhat_dev) throw Err("null argument");
         hipStream_t s = on_stream(h, stream);
-        bool any_conv = false;
-        for (const Mod& md : h->mods) any_conv = any_conv || md.conv;
-        if (any_conv || !h->cfg.use_graph || h->timing) {     // conv decoders (and the diagnostic modes) go modality by modality
-            for (int m = 0; m < h->M; ++m) {
-                const Mod& md = h->mods[m];
-                for (int r0 = 0; r0 < rows; r0 += h->B) {
-                    const int n = std::min(h->B, rows - r0);
-                    run_prep_single(h, z_dev + (size_t)r0 * h->nz, h->nz, n, h->nz, md.Z, nullptr, 0, false, nullptr, 0, s);
-                    build_inference(h, m, false, n);
-                    run_launches(h, h->inf_dec[m].launches, s);
-                    copy_rows(xhat_dev[m] + (size_t)r0 * md.n_in, (size_t)md.n_in * 4, h->at<float>(md.out32), (size_t)md.ld32 * 4, (size_t)md.n_in * 4, n, s);
-                }
-            }
+        if (decode_by_mod(h)) {
+            for (int m = 0; m < h->M; ++m) decode_rows(h, m, z_dev, rows, xhat_dev[m], s);
             return;
         }
         for (int r0 = 0; r0 < rows; r0 += h->B) {
             const int n = std::min(h->B, rows - r0);
-            const int bucket = (n <= 64 && h->B > 64) ? 64 : h->B;       // the CEM / GUI callers' 1-64 rows, or a batch-sized chunk
-            avae_handle::Serve& sv = serve_plan(h, bucket);
             ServeSlot sl;
             std::memset(&sl, 0, sizeof(sl));
             sl.z = z_dev + (size_t)r0 * h->nz; sl.rows = n;
             for (int m = 0; m < h->M; ++m) sl.out[m] = xhat_dev[m] + (size_t)r0 * h->mods[m].n_in;
-            // Measured (tools/serve_latency.py, one box, 1 / 64 rows, C ABI back to back, us per call): staging launch + graph of the
-            // remaining launches 19.1 / 19.9 (host side 10.2: GPU-bound -- three dependent kernels and a replay boundary of ~5 us);
-            // every launch eager 14.6 / 15.6 (host-bound at 13.7 / 14.6: three launches) = the default since round 3; the pinned-host
-            // ring with the staging launch as the graph's first node (no eager launch: VERDICT r2 #9) 20.6 / 21.4 -- every workgroup
-            // of the first kernel reads the call record over PCIe, and the call was never host-bound.  AVAE_SERVE_GRAPH=1 /
-            // AVAE_SERVE_RING=1 select the other two for A/B.
-            static const bool use_ring = std::getenv("AVAE_SERVE_RING") != nullptr, eager = !use_ring && std::getenv("AVAE_SERVE_GRAPH") == nullptr;
-            if (sv.fused_in && sv.lean_in && use_ring) {
-                // ONE graph replay per call: the record goes into the pinned ring, the slot's graph starts with the staging launch
-                if (!h->serve_ring) {
-                    HIP_OK(hipHostMalloc(reinterpret_cast<void**>(&h->serve_ring), kServeRing * sizeof(ServeSlot) + 64, hipHostMallocMapped | hipHostMallocPortable));
-                    std::memset(h->serve_ring, 0, kServeRing * sizeof(ServeSlot) + 64);
-                    h->serve_consumed = reinterpret_cast<unsigned long long*>(reinterpret_cast<unsigned char*>(h->serve_ring) + kServeRing * sizeof(ServeSlot));
-                    HIP_OK(hipMemsetAsync(h->at<void>(h->off_serve_count), 0, 8, s));
-                }
-                const unsigned long long id = h->serve_calls;
-                const int slot = (int)(id % kServeRing);
-                // flow control: slot id % R was last used by call id - R; it is free once the device has STARTED call id - R + 1
-                // (calls run in order, so call id - R is over then)
-                while (id + 2 > __atomic_load_n(h->serve_consumed, __ATOMIC_ACQUIRE) + kServeRing) sched_yield();
-                h->serve_ring[slot] = sl;
-                __atomic_thread_fence(__ATOMIC_RELEASE);
-                if (!sv.ring_graph[slot]) {
-                    void* rec_dev = nullptr;
-                    void* con_dev = nullptr;
-                    HIP_OK(hipHostGetDevicePointer(&rec_dev, h->serve_ring + slot, 0));
-                    HIP_OK(hipHostGetDevicePointer(&con_dev, h->serve_consumed, 0));
-                    ServeInArgs ia = sv.in_lean;
-                    ia.rec = reinterpret_cast<const ServeSlot*>(rec_dev);
-                    ia.consumed = reinterpret_cast<unsigned long long*>(con_dev);
-                    ia.count = h->at<unsigned long long>(h->off_serve_count);
-                    const bool tsave = h->timing;
-                    h->timing = false;
-                    sv.ring_graph[slot] = capture(h, [&](hipStream_t cs) {
-                        launch_serve_in(h->cfg.compute_dtype, ia, sv.in_lean_grid, cs); LAUNCH_OK("serve_in+serve_dec1");
-                        run_launches(h, sv.launches, cs);
-                    });
-                    h->timing = tsave;
-                }
-                HIP_OK(hipGraphLaunch(sv.ring_graph[slot], s));
-                ++h->serve_calls;
-                continue;
-            }
-            serve_call(h, sv, sl, eager, s);
+            serve_call(h, serve_plan(h, serve_bucket(h, n)), sl, s);
         }
     });
 }
@@ -3179,16 +3148,16 @@ int avae_reconstruct(avae_handle* h, int32_t m, const float* x_dev, int32_t x_ld
         hipStream_t s = on_stream(h, stream);
         const Mod& md = h->mods[m];
         const int ld = x_ld > 0 ? x_ld : md.n_in;
-        // a fresh eps per call and per modality, as each sess.run of the reference draws one (vae_assoc.py:423-424): the salt's
-        // high word carries (draw counter, modality), the generator's row index is the row of the whole input (r0 + row)
-        const unsigned long long draw = eps_dev ? 0ull : ((unsigned long long)((++h->draw_id) & 0x3FFFFFu) << 34) | ((unsigned long long)m << 32);
+        // a fresh eps per call and per modality (vae_assoc.py:423-424): the salt's high word carries (draw counter, modality), the
+        // generator's row index is the row of the whole input (r0 + row)
+        const unsigned long long draw = eps_dev ? 0ull : ((unsigned long long)next_draw(h, eps_dev) << 34) | ((unsigned long long)m << 32);
         for (int r0 = 0; r0 < rows; r0 += h->B) {
             const int n = std::min(h->B, rows - r0);
             run_prep_single(h, x_dev + (size_t)r0 * ld, ld, n, md.n_in, md.X0, nullptr, 0, true,
                             eps_dev ? eps_dev + (size_t)r0 * h->nz : nullptr, 0x7265636full | draw, s, r0);
             run_inference(h, m, true, n, s);
             run_inference(h, m, false, n, s);
-            copy_rows(xhat_dev + (size_t)r0 * md.n_in, (size_t)md.n_in * 4, h->at<float>(md.out32), (size_t)md.ld32 * 4, (size_t)md.n_in * 4, n, s);
+            copy_out32(h, m, xhat_dev + (size_t)r0 * md.n_in, n, s);
         }
     });
 }
@@ -3213,21 +3182,14 @@ int avae_score(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, i
         if (flags & ~AVAE_SCORE_CROSS) throw Err("avae_score: unknown flags (only AVAE_SCORE_CROSS is defined)");
         if (rows < 0) throw Err("avae_score: rows must be >= 0");
         if (rows == 0) return;
-        if (!out_dev) throw Err("avae_score: out_dev is NULL");
-        if (!x_dev) throw Err("avae_score: x_dev is NULL");
+        int ld[kMaxMod];
+        check_row_inputs(h, "avae_score", x_dev, x_ld, out_dev, ld);
         const int M = h->M, P = M * (M - 1) / 2;
         const bool cross = (flags & AVAE_SCORE_CROSS) != 0;
         const int k = 1 + 2 * M + P + (cross ? M * M : 0);
-        int ld[kMaxMod];
-        for (int m = 0; m < M; ++m) {
-            if (!x_dev[m]) throw Err("avae_score: x_dev[" + std::to_string(m) + "] is NULL");
-            ld[m] = x_ld ? x_ld[m] : h->mods[m].n_in;
-            if (ld[m] < h->mods[m].n_in)
-                throw Err("avae_score: x_ld[" + std::to_string(m) + "] = " + std::to_string(ld[m]) + " is below n_input = " + std::to_string(h->mods[m].n_in));
-        }
         hipStream_t s = on_stream(h, stream);
         // a fresh eps per call, keyed as avae_reconstruct's: draw counter in the salt's high bits, row of the whole input
-        const unsigned long long draw = eps_dev ? 0ull : (unsigned long long)((++h->draw_id) & 0x3FFFFFu) << 34;
+        const unsigned long long draw = (unsigned long long)next_draw(h, eps_dev) << 34;
         ScoreLatentArgs la;
         std::memset(&la, 0, sizeof(la));
         la.eps = h->at<float>(h->off_eps); la.ld_eps = h->ld_eps;
@@ -3295,16 +3257,9 @@ int avae_loglik(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, 
         if (rows < 0) throw Err("avae_loglik: rows must be >= 0");
         if (n_samples < 1) throw Err("avae_loglik: n_samples must be >= 1, got " + std::to_string(n_samples));
         if (rows == 0) return;
-        if (!out_dev) throw Err("avae_loglik: out_dev is NULL");
-        if (!x_dev) throw Err("avae_loglik: x_dev is NULL");
-        const int M = h->M, B = h->B, nz = h->nz, K = n_samples;
         int ld[kMaxMod];
-        for (int m = 0; m < M; ++m) {
-            if (!x_dev[m]) throw Err("avae_loglik: x_dev[" + std::to_string(m) + "] is NULL");
-            ld[m] = x_ld ? x_ld[m] : h->mods[m].n_in;
-            if (ld[m] < h->mods[m].n_in)
-                throw Err("avae_loglik: x_ld[" + std::to_string(m) + "] = " + std::to_string(ld[m]) + " is below n_input = " + std::to_string(h->mods[m].n_in));
-        }
+        check_row_inputs(h, "avae_loglik", x_dev, x_ld, out_dev, ld);
+        const int M = h->M, B = h->B, nz = h->nz, K = n_samples;
         hipStream_t s = on_stream(h, stream);
         const int width = 2 * M + M * M;
         const int n_rows = K >= B ? 1 : B / K, kb = K >= B ? B : K;
@@ -3314,12 +3269,9 @@ int avae_loglik(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, 
         float* rbuf = z32 + z_n;
         float* ell = rbuf + r_n;
         float* state = ell + ell_n;
-        bool any_conv = false;
-        for (const Mod& md : h->mods) any_conv = any_conv || md.conv;
-        const bool by_mod = any_conv || !h->cfg.use_graph || h->timing;     // as avae_generate
-        static const bool eager = std::getenv("AVAE_SERVE_GRAPH") == nullptr;
+        const bool by_mod = decode_by_mod(h);
         // a fresh eps per call, keyed as avae_score's: draw counter, row of the whole input (+ the sample index)
-        const unsigned draw = eps_dev ? 0u : (++h->draw_id) & 0x3FFFFFu;
+        const unsigned draw = next_draw(h, eps_dev);
         IwLatentArgs la;
         std::memset(&la, 0, sizeof(la));
         la.nz = nz; la.K = K; la.seed = h->cfg.seed; la.draw = draw; la.r = rbuf;
@@ -3371,7 +3323,7 @@ int avae_loglik(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, 
                         for (int d = 0; d < M; ++d) run_inference(h, d, false, nd, s);
                     } else {
                         sl.rows = nd;
-                        serve_call(h, serve_plan(h, (nd <= 64 && B > 64) ? 64 : B), sl, eager, s);
+                        serve_call(h, serve_plan(h, serve_bucket(h, nd)), sl, s);
                     }
                     {
                         Timed t(h, s, "iw_rows");

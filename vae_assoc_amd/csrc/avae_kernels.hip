@@ -3203,7 +3203,7 @@ __global__ void __launch_bounds__(kThreads) k_serve(ServeArgs a, ServeSlot call)
 // The per-call launch of avae_generate for the small nets, lean: no K loop at all -- the call's fp32 z rows go into the tail's LDS
 // image (rows beyond the call's zero, constant-1 column included), the decoder's first layer of modality blockIdx.y is the tail
 // product (slice = 64 output columns per workgroup), workgroup (0, 0) publishes the call's slot.  A 300-byte argument block instead of
-// the grouped kernel's 3.4 KB: the host side of a call is the launch of this kernel + one graph replay.
+// the grouped kernel's 3.4 KB: the host side of a call is the launch of this kernel + the plan's remaining launches.
 template <typename CT>
 __global__ void __launch_bounds__(kThreads) k_serve_in(ServeInArgs a) {
     constexpr int ES = (int)sizeof(CT), TSL = ES == 2 ? 2 : 4;
@@ -3213,15 +3213,8 @@ __global__ void __launch_bounds__(kThreads) k_serve_in(ServeInArgs a) {
     if (tm >= a.tiles_m) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fr = lane & 15, fq = lane >> 4;
     const int m0 = tm * 32, nz = a.nz;
-    // the call: by value in the kernel arguments (eager launch per call), or -- as the first node of a captured graph -- from the
-    // record the host wrote into its pinned ring before the replay (one uniform read over PCIe per workgroup)
-    ServeSlot call_v = a.call;
-    if (a.rec) call_v = *a.rec;
-    const ServeSlot& call = call_v;
-    if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) {
-        *a.slot = call;
-        if (a.rec) { const unsigned long long n = *a.count + 1; *a.count = n; __hip_atomic_store(a.consumed, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
-    }
+    const ServeSlot& call = a.call;          // by value in the kernel arguments
+    if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) *a.slot = call;
     const int t_i = wave & 1, t_c0 = (2 * ts + (wave >> 1)) * 32, t_sl = 2 * md.kt;
     u32x4 tb[TSL][2];
 #pragma unroll
@@ -3405,29 +3398,33 @@ __global__ void __launch_bounds__(kThreads) k_score_latent(ScoreLatentArgs a) {
     }
 }
 
-// Reconstruction loss of one row for one decode pass, from the decoder's fp32 output (p for Bernoulli, x_hat for Gaussian) with
-// loss_bernoulli / loss_gauss's arithmetic (contraction off); one wave per row, lanes stride the row, fixed-order tree.
-__global__ void __launch_bounds__(kThreads) k_score_rows(ScoreRowsArgs a) {
+// Reconstruction loss of one row from the decoder's fp32 output xh (p for Bernoulli, x_hat for Gaussian) with loss_bernoulli /
+// loss_gauss's arithmetic (contraction off); one wave per row, lanes stride the row, fixed-order tree.  k_score_rows, k_iw_rows.
+__device__ __forceinline__ float recon_row(const float* xh, const float* x, int n_in, int binary, int lane) {
 #pragma clang fp contract(off)
-    const int row = blockIdx.x * kScoreRows + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (row >= a.rows) return;                     // wave-uniform
-    const float* xh = a.xhat + (size_t)row * a.ld32;
-    const float* x = a.x + (size_t)row * a.ldx;
     float acc = 0.0f;
-    if (a.binary) {
-        for (int c = lane; c < a.n_in; c += 64) {
+    if (binary) {
+        for (int c = lane; c < n_in; c += 64) {
             const float p = xh[c], xv = x[c];
             const float lp = 1e-3f + p, lq = 1e-3f + 1.0f - p;
             acc += -(xv * flog(lp) + (1.0f - xv) * flog(lq));
         }
     } else {
-        for (int c = lane; c < a.n_in; c += 64) {
+        for (int c = lane; c < n_in; c += 64) {
             float sl, da;
             loss_gauss(xh[c], x[c], 1.0f, sl, da);
             acc += sl;
         }
     }
-    const float r = wave_sum(acc);
+    return wave_sum(acc);
+}
+
+// Reconstruction loss of one row for one decode pass (recon_row) into the score row; the last modality's pass also forms the cost.
+__global__ void __launch_bounds__(kThreads) k_score_rows(ScoreRowsArgs a) {
+#pragma clang fp contract(off)
+    const int row = blockIdx.x * kScoreRows + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= a.rows) return;                     // wave-uniform
+    const float r = recon_row(a.xhat + (size_t)row * a.ld32, a.x + (size_t)row * a.ldx, a.n_in, a.binary, lane);
     if (lane == 0) {
         float* orow = a.out + (size_t)row * a.k;
         orow[a.col] = r;
@@ -3494,31 +3491,13 @@ __global__ void __launch_bounds__(kThreads) k_iw_latent(IwLatentArgs a) {
     if (d == 0) a.r[i] = r;
 }
 
-// l_d = -recon_d of one decoded row for one modality: k_score_rows' loop (the same arithmetic, contraction off), one wave per
-// (decoded row, modality), modality-major.
+// l_d = -recon_d of one decoded row for one modality (recon_row, as k_score_rows), one wave per (decoded row, modality),
+// modality-major.
 __global__ void __launch_bounds__(kThreads) k_iw_rows(IwRowsArgs a) {
-#pragma clang fp contract(off)
     const int g = blockIdx.x * kScoreRows + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (g >= a.n_dec * a.n_mod) return;            // wave-uniform
     const int m = g / a.n_dec, i = g - m * a.n_dec;
-    const float* xh = a.xhat[m] + (size_t)i * a.ldh[m];
-    const float* x = a.x[m] + (size_t)(i / a.kc) * a.ldx[m];
-    const int n_in = a.n_in[m];
-    float acc = 0.0f;
-    if (a.binary[m]) {
-        for (int c = lane; c < n_in; c += 64) {
-            const float p = xh[c], xv = x[c];
-            const float lp = 1e-3f + p, lq = 1e-3f + 1.0f - p;
-            acc += -(xv * flog(lp) + (1.0f - xv) * flog(lq));
-        }
-    } else {
-        for (int c = lane; c < n_in; c += 64) {
-            float sl, da;
-            loss_gauss(xh[c], x[c], 1.0f, sl, da);
-            acc += sl;
-        }
-    }
-    const float r = wave_sum(acc);
+    const float r = recon_row(a.xhat[m] + (size_t)i * a.ldh[m], a.x[m] + (size_t)(i / a.kc) * a.ldx[m], a.n_in[m], a.binary[m], lane);
     if (lane == 0) a.ell[(size_t)i * a.n_mod + m] = -r;
 }
 

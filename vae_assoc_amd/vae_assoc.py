@@ -323,19 +323,31 @@ class AssocVariationalAutoEncoder(object):
             t = t.contiguous()
         return t, was_np
 
+    def _rows_args(self, X, rows=None, what=None):
+        """X, one [N, n_input] array or tensor per modality -> (device tensors, N, was_numpy of X[0], ptrs, lds).  Every modality
+        needs the first one's row count, or ``rows`` (``what`` names it in the error) when given."""
+        M = len(self.network_architectures)
+        if len(X) != M:
+            raise ValueError("expected a list of %d modalities, got %d" % (M, len(X)))
+        ts, was_np = [], True
+        for m, (x, na) in enumerate(zip(X, self.network_architectures)):
+            t, np_in = self._dev(x, int(na["n_input"]))
+            if m == 0:
+                was_np = np_in
+            if rows is not None and t.shape[0] != rows:
+                raise ValueError("expected %d rows (%s), got %d" % (rows, what, t.shape[0]))
+            if ts and t.shape[0] != ts[0].shape[0]:
+                raise ValueError("every modality needs the same row count: %d vs %d" % (t.shape[0], ts[0].shape[0]))
+            ts.append(t)
+        ptrs = (C.c_void_p * M)(*[t.data_ptr() for t in ts])
+        lds = (C.c_int32 * M)(*[t.stride(0) if t.shape[0] > 1 else t.shape[1] for t in ts])
+        return ts, ts[0].shape[0], was_np, ptrs, lds
+
     def _batch_args(self, X, eps, n_steps=1):
         assert len(X) == len(self.network_architectures)
-        ts = []
         rows = self.batch_size * n_steps
-        for x, na in zip(X, self.network_architectures):
-            t, _ = self._dev(x, int(na["n_input"]))
-            if t.shape[0] != rows:
-                # the reference's eps has static shape (batch_size, n_z): every path through z
-                # needs exactly batch_size rows (vae_assoc.py:90)
-                raise ValueError("expected %d rows (batch_size%s), got %d" % (rows, " x n_steps" if n_steps > 1 else "", t.shape[0]))
-            ts.append(t)
-        ptrs = (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-        lds = (C.c_int32 * len(ts))(*[t.stride(0) if t.shape[0] > 1 else t.shape[1] for t in ts])
+        # the reference's eps has static shape (batch_size, n_z): every path through z needs exactly batch_size rows (vae_assoc.py:90)
+        ts, _, _, ptrs, lds = self._rows_args(X, rows, "batch_size" + (" x n_steps" if n_steps > 1 else ""))
         e = None
         if eps is not None:
             e, _ = self._dev(eps, self.n_z)
@@ -535,17 +547,7 @@ class AssocVariationalAutoEncoder(object):
         loss of modality d decoded from the posterior mean of modality s.  NumPy in gives NumPy out, device tensors in give
         device tensors out."""
         M = len(self.network_architectures)
-        if len(X) != M:
-            raise ValueError("expected a list of %d modalities, got %d" % (M, len(X)))
-        ts, was_np = [], True
-        for m, (x, na) in enumerate(zip(X, self.network_architectures)):
-            t, np_in = self._dev(x, int(na["n_input"]))
-            if m == 0:
-                was_np = np_in
-            if ts and t.shape[0] != ts[0].shape[0]:
-                raise ValueError("every modality needs the same row count: %d vs %d" % (t.shape[0], ts[0].shape[0]))
-            ts.append(t)
-        rows = ts[0].shape[0]
+        ts, rows, was_np, ptrs, lds = self._rows_args(X)
         e = None
         if eps is not None:
             e, _ = self._dev(eps, self.n_z)
@@ -557,8 +559,6 @@ class AssocVariationalAutoEncoder(object):
         _capi.check(None, self._L.avae_score_width(C.byref(self._cfg), flags, C.byref(k)), "avae_score_width")
         out = torch.empty((rows, k.value), dtype=torch.float32, device=self.device)
         if rows:
-            ptrs = (C.c_void_p * M)(*[t.data_ptr() for t in ts])
-            lds = (C.c_int32 * M)(*[t.stride(0) if rows > 1 else t.shape[1] for t in ts])
             _capi.check(self._h, self._L.avae_score(self._h, ptrs, lds, rows, e.data_ptr() if e is not None else None, flags,
                                                     out.data_ptr(), self._stream()), "avae_score")
         if was_np:
@@ -583,20 +583,10 @@ class AssocVariationalAutoEncoder(object):
         gives NumPy out, device tensors in give device tensors out.  Under data parallelism each replica scores its own rows:
         there is no collective."""
         M = len(self.network_architectures)
-        if len(X) != M:
-            raise ValueError("expected a list of %d modalities, got %d" % (M, len(X)))
         if isinstance(n_samples, bool) or not isinstance(n_samples, (int, np.integer)) or n_samples < 1:
             raise ValueError("n_samples must be an integer >= 1, got %r" % (n_samples,))
         K = int(n_samples)
-        ts, was_np = [], True
-        for m, (x, na) in enumerate(zip(X, self.network_architectures)):
-            t, np_in = self._dev(x, int(na["n_input"]))
-            if m == 0:
-                was_np = np_in
-            if ts and t.shape[0] != ts[0].shape[0]:
-                raise ValueError("every modality needs the same row count: %d vs %d" % (t.shape[0], ts[0].shape[0]))
-            ts.append(t)
-        rows = ts[0].shape[0]
+        ts, rows, was_np, ptrs, lds = self._rows_args(X)
         e = None
         if eps is not None:
             e = torch.as_tensor(np.asarray(eps, dtype=np.float32) if not torch.is_tensor(eps) else eps)
@@ -605,8 +595,6 @@ class AssocVariationalAutoEncoder(object):
             e = e.to(device=self.device, dtype=torch.float32).contiguous()
         out = torch.empty((rows, 2 * M + M * M), dtype=torch.float32, device=self.device)
         if rows:
-            ptrs = (C.c_void_p * M)(*[t.data_ptr() for t in ts])
-            lds = (C.c_int32 * M)(*[t.stride(0) if rows > 1 else t.shape[1] for t in ts])
             _capi.check(self._h, self._L.avae_loglik(self._h, ptrs, lds, rows, K, e.data_ptr() if e is not None else None,
                                                      out.data_ptr(), self._stream()), "avae_loglik")
         if was_np:
