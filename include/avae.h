@@ -164,6 +164,35 @@ int avae_comm_ipc_attach(avae_handle* h, const void* handles_by_rank);
 /* Costs of the most recent `n` applied steps (oldest first), without having synchronised per step. */
 int avae_cost_history(avae_handle* h, int32_t n, float* host_dst, int64_t* last_step);
 
+/* ---- partially paired batches (the reference has none: every row carries every modality, vae_assoc.py:90).
+ * present_dev: device uint8 [n_steps*batch_size][n_modalities], row-major, nonzero = row n has modality m (p[n,m]).  With B_g =
+ * batch_global (= batch_size on one replica) and recon / latent / assoc exactly avae_score's per-row columns (one eps row for every
+ * modality), the masked cost is
+ *   cost = sum_m w_m [ (1/B_g) sum_n p[n,m] latent[n,m] + (binary_m ? 1/B_g : 1) sum_n p[n,m] recon[n,m] ]
+ *        + assoc_lambda sum_{i<j} sum_n p[n,i] p[n,j] assoc[n,i,j]
+ * and the step's gradient is its gradient; Adam is unchanged.
+ *  - the divisor stays B_g, not the number of present rows: an all-present mask gives the unmasked step bit for bit and shards stay
+ *    additive.  Per-modality means: rescale the weights;
+ *  - absent entries are never read into the loss: the staging kernel writes zeros for every absent (row, modality) and the loss and
+ *    latent terms of absent entries are SELECTED away (not multiplied by 0) -- NaN / Inf / garbage there changes nothing, and an absent
+ *    (row, modality) adds exact zeros to every gradient entry of that modality's encoder and decoder.  A row with nothing present
+ *    contributes nothing;
+ *  - x_dev[m] == NULL: modality m is absent on every row, whatever its column of present_dev says (never read through);
+ *  - eps_dev NULL: the internal generator with the unmasked calls' keys ((seed, step, global row) for training, the eval salt and the
+ *    per-call draw counter for evaluation); both calls advance the same step / draw counters as their unmasked twins, so masked and
+ *    unmasked calls may be interleaved freely on one handle (one step counter, Adam state and cost history);
+ *  - present_dev == NULL is an error (use the unmasked entry points), and so is a data-parallel handle (world_size > 1 or use_comm !=
+ *    AVAE_COMM_NONE): these calls run on one replica.
+ * The first masked call builds the masked twin of the step (its captured graphs and a presence staging buffer of 16 * batch_size *
+ * n_modalities bytes, freed by avae_destroy); avae_workspace_bytes is unchanged.
+ * avae_train_steps_masked with n_steps = 1 is the masked partial_fit; for n_steps > 1 it follows avae_train_steps step for step (rows of
+ * present_dev as of x_dev), costs in avae_cost_history, avae_get_grads = the last step's gradient.  avae_eval_cost_masked: the masked
+ * evaluate_cost (batch_size rows, no update). */
+int avae_train_steps_masked(avae_handle* h, int32_t n_steps, const float* const* x_dev, const int32_t* x_ld,
+                            const uint8_t* present_dev, const float* eps_dev, float* cost_host, void* stream);
+int avae_eval_cost_masked(avae_handle* h, const float* const* x_dev, const int32_t* x_ld,
+                          const uint8_t* present_dev, const float* eps_dev, float* cost_host, void* stream);
+
 /* evaluate_cost (vae_assoc.py:388-391): forward + loss, no update. */
 int avae_eval_cost(avae_handle* h, const float* const* x_dev, const int32_t* x_ld,
                    const float* eps_dev, float* cost_host, void* stream);

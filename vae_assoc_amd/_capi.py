@@ -33,7 +33,7 @@ SYMBOLS = [
     "avae_train_step", "avae_train_steps", "avae_stage_batches", "avae_grad_buffer", "avae_cost_history",
     "avae_dp_plan", "avae_dp_backward", "avae_dp_apply", "avae_comm_unique_id", "avae_comm_ipc_handle", "avae_comm_ipc_attach",
     "avae_eval_cost", "avae_encode", "avae_decode", "avae_generate", "avae_reconstruct", "avae_save", "avae_load",
-    "avae_score_width", "avae_score", "avae_loglik",
+    "avae_score_width", "avae_score", "avae_loglik", "avae_train_steps_masked", "avae_eval_cost_masked",
     "avae_synchronize", "avae_timing_enable", "avae_timing_report", "avae_debug_fetch", "avae_comm_allreduce",
 ]
 
@@ -97,6 +97,8 @@ def lib():
             L.avae_comm_ipc_handle.argtypes = [vp, vp]
             L.avae_comm_ipc_attach.argtypes = [vp, vp]
             L.avae_eval_cost.argtypes = [vp, C.POINTER(vp), C.POINTER(i32), vp, fp, vp]
+            L.avae_train_steps_masked.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(i32), vp, vp, fp, vp]
+            L.avae_eval_cost_masked.argtypes = [vp, C.POINTER(vp), C.POINTER(i32), vp, vp, fp, vp]
             L.avae_encode.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp]
             L.avae_decode.argtypes = [vp, i32, vp, i32, vp, vp]
             L.avae_generate.argtypes = [vp, vp, i32, C.POINTER(vp), vp]

@@ -90,6 +90,11 @@ struct WorkItem {
     int tail_act;
     int tail_kt;             // K tiles of the consuming layer's product: 1, or 2 (fp32 [dmu | dlv] with n_z > 16)
     int conv;                // > 0: the A operand is an implicit patch matrix, descriptor conv - 1 of the launch's ConvA table (below)
+    // Masked steps (avae_train_steps_masked / avae_eval_cost_masked): the staged presence bytes of the batch, row n at
+    // present[n * present_ld] -- K_FWD_OUT_LOSS: already at the item's modality column; K_LATENT: modality m at + m.
+    // Nonzero = observed.  Null in every unmasked plan: the loss and latent sites then take no presence test at all.
+    const unsigned char* present;
+    int present_ld;
     // K_LATENT reuses the pointer fields: [mu|lv] inputs of modality 0..3 = A, B, aux0, aux1;
     // static-gradient outputs g0 of modality 0..3 = out0, out1, out2, aux2.
     // K_COST: scale = lr, lambda = beta1, inv_bg = beta2 (it also publishes this step's Adam lr_t).
@@ -244,6 +249,12 @@ struct PrepArgs {
     // j*set_stride bytes) and draws eps for step st->step + j.  blocks_per_step = total_tiles + eps_blocks.
     int n_steps, blocks_per_step;
     long long set_stride;
+    // masked staging (nullable; null = the unmasked staging above, unchanged): caller's presence bytes [n_steps*rows][pres_ld],
+    // nonzero = observed.  An absent (row, modality) -- and every row of a null seg[m].src -- is staged as zeros; the blocks of
+    // segment 0's first column tile copy the presence (0/1, a null source folded in) into set j of pres_dst at j*rows*pres_ld.
+    const unsigned char* pres_src;
+    unsigned char* pres_dst;
+    int pres_ld;
 };
 
 // Fixed-order sum of the split-K slices of a weight gradient: dst[i] = sum_s src[s*stride + i]  (no atomics: reproducible).
@@ -473,7 +484,7 @@ void launch_grouped_tn(int compute_dtype, int tile_cfg, const TnLaunchArgs& args
                        DevState* st, hipStream_t s, unsigned long long* stamps = nullptr, int launch_id = 0);
 void launch_adam(int compute_dtype, const AdamArgs& a, int n_blocks, hipStream_t s);
 void launch_prep(int compute_dtype, const PrepArgs& a, hipStream_t s);
-const void* prep_kernel(int compute_dtype);          // for hipGraphExecKernelNodeSetParams on the captured staging node
+const void* prep_kernel(int compute_dtype, bool masked);   // for hipGraphExecKernelNodeSetParams on the captured staging node
 void launch_fill(void* base, int elem_bytes, unsigned bits, long long start, long long stride, int count, hipStream_t s);
 void launch_sums(const ReduceArgs& a, int n_blocks, hipStream_t s);
 int small_head_lds_bytes();

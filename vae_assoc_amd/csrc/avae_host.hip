@@ -246,6 +246,16 @@ struct avae_handle {
     hipGraphExec_t g_multi[2] = {nullptr, nullptr};   // kMultiSizes[i] whole steps per replay (avae_train_steps)
     hipGraph_t g_full_graph = nullptr, g_multi_graph[2] = {nullptr, nullptr};   // templates, kept: their staging-kernel nodes are re-parameterised per replay
     hipGraphNode_t g_full_prep = nullptr, g_multi_prep[2] = {nullptr, nullptr};
+    // Masked steps (avae_train_steps_masked / avae_eval_cost_masked), built by the first masked call: the staged presence bytes (one set
+    // of [B][M] per staging set, allocated then -- the workspace does not grow) and the masked twin of the step -- the forward launches
+    // with WorkItem::present set in their loss and latent items; backward, weight gradients and Adam are the unmasked step's own.
+    unsigned char* pres_buf = nullptr;
+    size_t pres_set = 0;                    // bytes per staging set
+    bool masked_built = false;
+    std::vector<Launch> mfwd;
+    hipGraphExec_t gm_full = nullptr, gm_eval = nullptr, gm_multi[2] = {nullptr, nullptr};
+    hipGraph_t gm_full_graph = nullptr, gm_multi_graph[2] = {nullptr, nullptr};
+    hipGraphNode_t gm_full_prep = nullptr, gm_multi_prep[2] = {nullptr, nullptr};
 
     // Calls on one handle share its activation buffers and serving slot: a call on a different stream than the previous one is
     // ordered behind that one's work (an event recorded on the old stream when the switch is seen: nothing per call otherwise).
@@ -2065,7 +2075,7 @@ void run_adam(avae_handle* h, int mode, hipStream_t s, int bucket = -1) {
 
 // stages the caller's batch (and eps) into the internal compute-dtype buffers
 PrepArgs make_prep_batch(avae_handle* h, const float* const* x, const int32_t* x_ld, const float* eps, int rows,
-                         unsigned long long salt, int n_steps = 1) {
+                         unsigned long long salt, int n_steps = 1, const uint8_t* present = nullptr) {
     PrepArgs a;
     std::memset(&a, 0, sizeof(a));
     int base = 0;
@@ -2084,12 +2094,13 @@ PrepArgs make_prep_batch(avae_handle* h, const float* const* x, const int32_t* x
     a.eps_blocks = (rows * ((h->nz + 3) / 4) + kThreads - 1) / kThreads;
     a.row_offset = h->cfg.row_offset; a.seed = h->cfg.seed; a.st = h->state(); a.stream_salt = salt;
     a.n_steps = n_steps; a.blocks_per_step = a.total_tiles + a.eps_blocks; a.set_stride = (long long)h->stage_bytes;
+    if (present) { a.pres_src = present; a.pres_dst = h->pres_buf; a.pres_ld = h->M; }      // masked staging (set j at j * rows * M)
     return a;
 }
 
 void run_prep_batch(avae_handle* h, const float* const* x, const int32_t* x_ld, const float* eps, int rows,
-                    unsigned long long salt, hipStream_t s) {
-    const PrepArgs a = make_prep_batch(h, x, x_ld, eps, rows, salt);
+                    unsigned long long salt, hipStream_t s, const uint8_t* present = nullptr) {
+    const PrepArgs a = make_prep_batch(h, x, x_ld, eps, rows, salt, 1, present);
     Timed t(h, s, "prep");
     launch_prep(h->cfg.compute_dtype, a, s);
     LAUNCH_OK("prep");
@@ -2131,6 +2142,7 @@ Launch relocated(const avae_handle* h, const Launch& L0, int j) {
         WorkItem& w = L.args.items[i];
         fix(w.A); fix(w.B); fix(w.out0); fix(w.out1); fix(w.out2); fix(w.aux0); fix(w.aux1); fix(w.aux2); fix(w.eps);
         fix(w.tail_w); fix(w.tail_out); fix(w.tail_aux);
+        if (w.present) w.present += (size_t)j * h->pres_set;          // masked twin: presence set j (its own allocation)
     }
     for (int i = 0; i < L.targs.n_items && L.type == 0; ++i) { TnItem& t = L.targs.items[i]; fix(t.A); fix(t.B); fix(t.out); }
     for (int i = 0; i < L.ga.n_seg && L.type == 1; ++i) fix(L.ga.seg[i].src);
@@ -2174,12 +2186,12 @@ hipGraphExec_t capture_with_prep(avae_handle* h, const std::function<void(hipStr
 
 // Points one captured staging node at the caller's batch (or run of n_steps consecutive batches).
 void patch_prep(avae_handle* h, hipGraphExec_t ge, hipGraphNode_t node, const float* const* x, const int32_t* x_ld, const float* eps,
-                int n_steps = 1) {
-    PrepArgs a = make_prep_batch(h, x, x_ld, eps, h->B, 0x7261696eull, n_steps);
+                int n_steps = 1, const uint8_t* present = nullptr) {
+    PrepArgs a = make_prep_batch(h, x, x_ld, eps, h->B, 0x7261696eull, n_steps, present);
     void* kp[1] = {&a};
     hipKernelNodeParams np;
     std::memset(&np, 0, sizeof(np));
-    np.func = const_cast<void*>(prep_kernel(h->cfg.compute_dtype));
+    np.func = const_cast<void*>(prep_kernel(h->cfg.compute_dtype, present != nullptr));
     np.gridDim = dim3((a.total_tiles + a.eps_blocks) * n_steps); np.blockDim = dim3(kThreads);
     np.sharedMemBytes = 0; np.kernelParams = kp; np.extra = nullptr;
     HIP_OK(hipGraphExecKernelNodeSetParams(ge, node, &np));
@@ -2190,6 +2202,75 @@ void fill_ones(avae_handle* h, const Act& a, hipStream_t s) {
     const unsigned bits = h->es == 2 ? 0x3F80u : 0x3F800000u;
     launch_fill(h->at<void>(a.rm), h->es, bits, a.width, a.ld, h->B, s);             // column `width`, rows < B
     LAUNCH_OK("fill");
+}
+
+// One step on staging set j (forward launches `fwd`: the plan's own, or its masked twin) inside a capture; `pending` = the side
+// stream still carries the previous step's decoder bucket.
+void step_body(avae_handle* h, const std::vector<Launch>& fwd, hipStream_t cs, int j, bool& pending, int stamp_base) {
+    auto run = [&](const std::vector<Launch>& ls, size_t lo, size_t hi, hipStream_t st, int sb) {
+        std::vector<Launch> moved;
+        for (size_t i = lo; i < hi && i < ls.size(); ++i) moved.push_back(relocated(h, ls[i], j));
+        run_launches(h, moved, st, sb);
+    };
+    if (!h->overlap) {
+        run(fwd, 0, fwd.size(), cs, stamp_base); run(h->bwd, 0, h->bwd.size(), cs, stamp_base < 0 ? -1 : stamp_base + (int)fwd.size());
+        if (!h->wgrad_adam.empty()) {       // the optimiser rides in the weight-gradient launch
+            run(h->wgrad_adam, 0, 1, cs, stamp_base < 0 ? -1 : stamp_base + (int)(fwd.size() + h->bwd.size()));
+            return;
+        }
+        run(h->wgrad, 0, h->wgrad.size(), cs, stamp_base < 0 ? -1 : stamp_base + (int)(fwd.size() + h->bwd.size()));
+        run_adam(h, 0, cs);
+        return;
+    }
+    run(fwd, 0, (size_t)h->fwd_dec_first, cs, -1);
+    if (pending) { HIP_OK(hipStreamWaitEvent(cs, h->ev_side, 0)); pending = false; }      // decoder weights of the previous step are final
+    run(fwd, (size_t)h->fwd_dec_first, fwd.size(), cs, -1);
+    run(h->bwd, 0, (size_t)h->bwd_split, cs, -1);
+    if (h->ov_split_wgrad) {
+        HIP_OK(hipEventRecord(h->ev_fork, cs));
+        HIP_OK(hipStreamWaitEvent(h->side_stream, h->ev_fork, 0));
+        run(h->wgrad_b[0], 0, h->wgrad_b[0].size(), h->side_stream, -1);
+        run_adam(h, 0, h->side_stream, 0);
+        HIP_OK(hipEventRecord(h->ev_side, h->side_stream));
+        run(h->bwd, (size_t)h->bwd_split, h->bwd.size(), cs, -1);
+        run(h->wgrad_b[1], 0, h->wgrad_b[1].size(), cs, -1);
+        run_adam(h, 0, cs, 1);
+    } else {        // Adam of the encoder side first and alone (it is HBM-bound: two at once gain nothing), then the decoder side's beside
+                    // the next step's encoder forward (MFMA-bound launches with register-file room for Adam's small waves)
+        run(h->bwd, (size_t)h->bwd_split, h->bwd.size(), cs, -1);
+        run(h->wgrad, 0, h->wgrad.size(), cs, -1);
+        run_adam(h, 0, cs, 1);
+        HIP_OK(hipEventRecord(h->ev_fork, cs));
+        HIP_OK(hipStreamWaitEvent(h->side_stream, h->ev_fork, 0));
+        run_adam(h, 0, h->side_stream, 0);
+        HIP_OK(hipEventRecord(h->ev_side, h->side_stream));
+    }
+    pending = true;
+}
+
+// The captured graphs of a step whose forward launches are `fwd`: one whole step (staging kernel first), runs of kMultiSizes[gi] steps
+// and the eval pass.  `present` non-null: the masked twin (masked staging; the placeholder is patched per replay like the inputs).
+void capture_step_graphs(avae_handle* h, const std::vector<Launch>& fwd, const uint8_t* present, hipGraphExec_t* full, hipGraph_t* full_graph,
+                         hipGraphNode_t* full_prep, hipGraphExec_t* multi, hipGraph_t* multi_graph, hipGraphNode_t* multi_prep, hipGraphExec_t* eval) {
+    std::vector<const float*> x0(h->M, h->at<float>(h->mods[0].X32));    // placeholders, patched per step
+    auto one_step = [&](hipStream_t cs) {
+        run_prep_batch(h, x0.data(), nullptr, nullptr, h->B, 0x7261696eull, cs, present);
+        bool pending = false;
+        step_body(h, fwd, cs, 0, pending, 0);
+        if (pending) HIP_OK(hipStreamWaitEvent(cs, h->ev_side, 0));
+    };
+    *full = capture_with_prep(h, one_step, full_graph, full_prep);
+    // avae_train_steps: kMultiSteps whole steps per replay (a replay boundary costs ~5 us of idle GPU on this stack),
+    // their batches staged by ONE launch into the kMultiSteps staging sets; step j's launches read set j
+    for (int gi = 0; gi < 2; ++gi) multi[gi] = capture_with_prep(h, [&](hipStream_t cs) {
+        const PrepArgs a = make_prep_batch(h, x0.data(), nullptr, nullptr, h->B, 0x7261696eull, kMultiSizes[gi], present);
+        launch_prep(h->cfg.compute_dtype, a, cs);
+        LAUNCH_OK("prep");
+        bool pending = false;
+        for (int j = 0; j < kMultiSizes[gi]; ++j) step_body(h, fwd, cs, j, pending, -1);
+        if (pending) HIP_OK(hipStreamWaitEvent(cs, h->ev_side, 0));        // join before the graph ends
+    }, &multi_graph[gi], &multi_prep[gi]);
+    *eval = capture(h, [&](hipStream_t cs) { run_launches(h, fwd, cs); run_launches(h, std::vector<Launch>{h->cost_only}, cs); });
 }
 
 void init_device(avae_handle* h) {
@@ -2232,7 +2313,6 @@ void init_device(avae_handle* h) {
     if (h->cfg.use_graph) {
         const bool tsave = h->timing;
         h->timing = false;
-        std::vector<const float*> x0(h->M, h->at<float>(h->mods[0].X32));    // placeholders, patched per step
         if (h->overlap && h->n_buckets == 2) {
             HIP_OK(hipStreamCreateWithFlags(&h->side_stream, hipStreamNonBlocking));
             HIP_OK(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
@@ -2240,66 +2320,7 @@ void init_device(avae_handle* h) {
         } else {
             h->overlap = false;
         }
-        // one step on staging set j inside a capture; `pending` = the side stream still carries the previous step's decoder bucket
-        auto step_body = [&](hipStream_t cs, int j, bool& pending, int stamp_base) {
-            auto run = [&](const std::vector<Launch>& ls, size_t lo, size_t hi, hipStream_t st, int sb) {
-                std::vector<Launch> moved;
-                for (size_t i = lo; i < hi && i < ls.size(); ++i) moved.push_back(relocated(h, ls[i], j));
-                run_launches(h, moved, st, sb);
-            };
-            if (!h->overlap) {
-                run(h->fwd, 0, h->fwd.size(), cs, stamp_base); run(h->bwd, 0, h->bwd.size(), cs, stamp_base < 0 ? -1 : stamp_base + (int)h->fwd.size());
-                if (!h->wgrad_adam.empty()) {       // the optimiser rides in the weight-gradient launch
-                    run(h->wgrad_adam, 0, 1, cs, stamp_base < 0 ? -1 : stamp_base + (int)(h->fwd.size() + h->bwd.size()));
-                    return;
-                }
-                run(h->wgrad, 0, h->wgrad.size(), cs, stamp_base < 0 ? -1 : stamp_base + (int)(h->fwd.size() + h->bwd.size()));
-                run_adam(h, 0, cs);
-                return;
-            }
-            run(h->fwd, 0, (size_t)h->fwd_dec_first, cs, -1);
-            if (pending) { HIP_OK(hipStreamWaitEvent(cs, h->ev_side, 0)); pending = false; }      // decoder weights of the previous step are final
-            run(h->fwd, (size_t)h->fwd_dec_first, h->fwd.size(), cs, -1);
-            run(h->bwd, 0, (size_t)h->bwd_split, cs, -1);
-            if (h->ov_split_wgrad) {
-                HIP_OK(hipEventRecord(h->ev_fork, cs));
-                HIP_OK(hipStreamWaitEvent(h->side_stream, h->ev_fork, 0));
-                run(h->wgrad_b[0], 0, h->wgrad_b[0].size(), h->side_stream, -1);
-                run_adam(h, 0, h->side_stream, 0);
-                HIP_OK(hipEventRecord(h->ev_side, h->side_stream));
-                run(h->bwd, (size_t)h->bwd_split, h->bwd.size(), cs, -1);
-                run(h->wgrad_b[1], 0, h->wgrad_b[1].size(), cs, -1);
-                run_adam(h, 0, cs, 1);
-            } else {        // Adam of the encoder side first and alone (it is HBM-bound: two at once gain nothing), then the decoder side's beside
-                            // the next step's encoder forward (MFMA-bound launches with register-file room for Adam's small waves)
-                run(h->bwd, (size_t)h->bwd_split, h->bwd.size(), cs, -1);
-                run(h->wgrad, 0, h->wgrad.size(), cs, -1);
-                run_adam(h, 0, cs, 1);
-                HIP_OK(hipEventRecord(h->ev_fork, cs));
-                HIP_OK(hipStreamWaitEvent(h->side_stream, h->ev_fork, 0));
-                run_adam(h, 0, h->side_stream, 0);
-                HIP_OK(hipEventRecord(h->ev_side, h->side_stream));
-            }
-            pending = true;
-        };
-        auto one_step = [&](hipStream_t cs) {
-            run_prep_batch(h, x0.data(), nullptr, nullptr, h->B, 0x7261696eull, cs);
-            bool pending = false;
-            step_body(cs, 0, pending, 0);
-            if (pending) HIP_OK(hipStreamWaitEvent(cs, h->ev_side, 0));
-        };
-        h->g_full = capture_with_prep(h, one_step, &h->g_full_graph, &h->g_full_prep);
-        // avae_train_steps: kMultiSteps whole steps per replay (a replay boundary costs ~5 us of idle GPU on this stack),
-        // their batches staged by ONE launch into the kMultiSteps staging sets; step j's launches read set j
-        for (int gi = 0; gi < 2; ++gi) h->g_multi[gi] = capture_with_prep(h, [&](hipStream_t cs) {
-            const PrepArgs a = make_prep_batch(h, x0.data(), nullptr, nullptr, h->B, 0x7261696eull, kMultiSizes[gi]);
-            launch_prep(h->cfg.compute_dtype, a, cs);
-            LAUNCH_OK("prep");
-            bool pending = false;
-            for (int j = 0; j < kMultiSizes[gi]; ++j) step_body(cs, j, pending, -1);
-            if (pending) HIP_OK(hipStreamWaitEvent(cs, h->ev_side, 0));        // join before the graph ends
-        }, &h->g_multi_graph[gi], &h->g_multi_prep[gi]);
-        h->g_eval = capture(h, [&](hipStream_t cs) { run_launches(h, h->fwd, cs); run_launches(h, std::vector<Launch>{h->cost_only}, cs); });
+        capture_step_graphs(h, h->fwd, nullptr, &h->g_full, &h->g_full_graph, &h->g_full_prep, h->g_multi, h->g_multi_graph, h->g_multi_prep, &h->g_eval);
         h->timing = tsave;
     }
 }
@@ -2811,6 +2832,9 @@ void avae_destroy(avae_handle* h) {
     for (int b = 0; b < 2; ++b) for (hipGraphExec_t g : h->g_dp[b]) if (g) (void)hipGraphExecDestroy(g);
     for (avae_handle::Serve& sv : h->serve) if (sv.graph) (void)hipGraphExecDestroy(sv.graph);
     if (h->iw_buf) (void)hipFree(h->iw_buf);
+    for (hipGraphExec_t g : {h->gm_full, h->gm_multi[0], h->gm_multi[1], h->gm_eval}) if (g) (void)hipGraphExecDestroy(g);
+    for (hipGraph_t g : {h->gm_full_graph, h->gm_multi_graph[0], h->gm_multi_graph[1]}) if (g) (void)hipGraphDestroy(g);
+    if (h->pres_buf) (void)hipFree(h->pres_buf);
     if (h->ev_switch) (void)hipEventDestroy(h->ev_switch);
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
     if (h->ev_side) (void)hipEventDestroy(h->ev_side);
@@ -2982,6 +3006,119 @@ int avae_train_steps(avae_handle* h, int32_t n_steps, const float* const* x_dev,
             train_one(h, x.data(), x_ld, e, s);
         }
         fetch_cost(h, cost_host, true, s);
+    });
+}
+
+// ---- masked steps: per-row modality presence (include/avae.h).  The masked twin of the step is built on first use: the forward
+// launches with WorkItem::present pointing at the staged presence bytes in every loss and latent item, and their graphs.
+void build_masked(avae_handle* h) {
+    if (h->masked_built) return;
+    if (!h->pres_buf) {
+        h->pres_set = (size_t)h->B * h->M;         // = the staging kernel's set stride (PrepArgs::pres_dst: set j at j * rows * M)
+        HIP_OK(hipMalloc(reinterpret_cast<void**>(&h->pres_buf), h->pres_set * kMultiSteps));
+        HIP_OK(hipMemset(h->pres_buf, 0, h->pres_set * kMultiSteps));
+    }
+    std::vector<Launch> mf = h->fwd;
+    int n_loss = 0, n_latent = 0;
+    for (Launch& L : mf) {
+        if (L.type != 0 || L.tn) continue;
+        bool gated = false;
+        for (int i = 0; i < L.args.n_items; ++i) {
+            WorkItem& w = L.args.items[i];
+            if (w.kind == K_FWD_OUT_LOSS) {
+                int m = 0;
+                while (m < h->M && w.aux0 != h->at<void>(h->mods[m].X32)) ++m;      // the item's modality: whose exact inputs it reads
+                if (m == h->M) throw Err("internal error: a loss item of no modality");
+                w.present = h->pres_buf + m; w.present_ld = h->M;
+                gated = true; ++n_loss;
+            } else if (w.kind == K_LATENT) {
+                w.present = h->pres_buf; w.present_ld = h->M;
+                gated = true; ++n_latent;
+            }
+        }
+        // the kernels that carry the presence gate: k_grouped's 4-wave tiles (configurations 0, 1, 3, 4, 5), its 8-wave loss tile (6)
+        // and the small nets' loss kernel (9).  Any other route of a loss or latent item would ignore the mask: refuse.
+        const int c = L.cfg;
+        if (gated && !(c == 0 || c == 1 || c == 3 || c == 4 || c == 5 || c == 6 || c == 9))
+            throw Err("masked training is not available on this plan: launch " + L.name + " (tile configuration " + std::to_string(c) +
+                      ") carries a loss or latent item on a kernel without the presence gate");
+    }
+    if (n_loss != h->M || n_latent != 1) throw Err("internal error: the masked twin found " + std::to_string(n_loss) + " loss and " +
+                                                   std::to_string(n_latent) + " latent items");
+    h->mfwd.swap(mf);
+    if (h->cfg.use_graph) {
+        const bool tsave = h->timing;
+        h->timing = false;
+        try {
+            capture_step_graphs(h, h->mfwd, h->pres_buf, &h->gm_full, &h->gm_full_graph, &h->gm_full_prep, h->gm_multi, h->gm_multi_graph,
+                                h->gm_multi_prep, &h->gm_eval);
+        } catch (...) { h->timing = tsave; throw; }
+        h->timing = tsave;
+    }
+    h->masked_built = true;
+}
+
+void check_masked_call(avae_handle* h, const char* what, const float* const* x_dev, const uint8_t* present_dev) {
+    if (h->cfg.world_size > 1 || h->cfg.use_comm != AVAE_COMM_NONE || h->comm_on)
+        throw Err(std::string(what) + ": masked steps run on one replica only (world_size 1, use_comm AVAE_COMM_NONE)");
+    if (!x_dev) throw Err(std::string(what) + ": null x_dev");
+    if (!present_dev) throw Err(std::string(what) + ": present_dev is null (unmasked calls go through the unmasked entry points)");
+}
+
+void train_one_masked(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, const uint8_t* present, const float* eps_dev, hipStream_t s) {
+    if (h->gm_full && !h->timing) {
+        patch_prep(h, h->gm_full, h->gm_full_prep, x_dev, x_ld, eps_dev, 1, present);
+        HIP_OK(hipGraphLaunch(h->gm_full, s));
+        return;
+    }
+    run_prep_batch(h, x_dev, x_ld, eps_dev, h->B, 0x7261696eull, s, present);
+    run_launches(h, h->mfwd, s); run_launches(h, h->bwd, s);
+    if (!h->wgrad_adam.empty()) run_launches(h, h->wgrad_adam, s);
+    else { run_launches(h, h->wgrad, s); run_adam(h, 0, s); }
+}
+
+int avae_train_steps_masked(avae_handle* h, int32_t n_steps, const float* const* x_dev, const int32_t* x_ld, const uint8_t* present_dev,
+                            const float* eps_dev, float* cost_host, void* stream) {
+    return guarded(h, [&] {
+        check_masked_call(h, "avae_train_steps_masked", x_dev, present_dev);
+        if (n_steps < 1) throw Err("avae_train_steps_masked: n_steps must be >= 1");
+        build_masked(h);
+        hipStream_t s = on_stream(h, stream);
+        std::vector<const float*> x(h->M);
+        const uint8_t* pres = nullptr;
+        auto batch = [&](int i) {       // rows [i*B, (i+1)*B) of every modality, of the presence bytes and of eps
+            for (int m = 0; m < h->M; ++m) {
+                const size_t ld = (x_ld && x_ld[m] > 0) ? (size_t)x_ld[m] : (size_t)h->mods[m].n_in;
+                x[m] = x_dev[m] ? x_dev[m] + (size_t)i * h->B * ld : nullptr;
+            }
+            pres = present_dev + (size_t)i * h->B * h->M;
+            return eps_dev ? eps_dev + (size_t)i * h->B * h->nz : nullptr;
+        };
+        int i = 0;
+        for (int gi = 0; gi < 2 && !h->timing; ++gi)
+            for (; h->gm_multi[gi] && i + kMultiSizes[gi] <= n_steps; i += kMultiSizes[gi]) {
+                const float* e = batch(i);
+                patch_prep(h, h->gm_multi[gi], h->gm_multi_prep[gi], x.data(), x_ld, e, kMultiSizes[gi], pres);
+                HIP_OK(hipGraphLaunch(h->gm_multi[gi], s));
+            }
+        for (; i < n_steps; ++i) {
+            const float* e = batch(i);
+            train_one_masked(h, x.data(), x_ld, pres, e, s);
+        }
+        fetch_cost(h, cost_host, true, s);
+    });
+}
+
+int avae_eval_cost_masked(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, const uint8_t* present_dev, const float* eps_dev,
+                          float* cost_host, void* stream) {
+    return guarded(h, [&] {
+        check_masked_call(h, "avae_eval_cost_masked", x_dev, present_dev);
+        build_masked(h);
+        hipStream_t s = on_stream(h, stream);
+        run_prep_batch(h, x_dev, x_ld, eps_dev, h->B, 0x6576616cull /*eval*/ | (unsigned long long)next_draw(h, eps_dev) << 34, s, present_dev);
+        if (h->gm_eval && !h->timing) HIP_OK(hipGraphLaunch(h->gm_eval, s));
+        else { run_launches(h, h->mfwd, s); run_launches(h, std::vector<Launch>{h->cost_only}, s); }
+        fetch_cost(h, cost_host, false, s);
     });
 }
 

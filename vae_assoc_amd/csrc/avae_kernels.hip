@@ -19,6 +19,7 @@
 // :306-371 (losses), :373-374 (Adam); restated for CPU in oracle/vae_assoc_oracle.py.
 #include "avae_device.h"
 #include <hip/hip_ext.h>
+#include <stdexcept>
 #include "../../include/avae.h"
 
 namespace avae {
@@ -277,9 +278,11 @@ template <int LDC> __device__ __forceinline__ int cs_idx(int r, int c) { return 
 // load->wait->store chains): A) unconditional loads (addresses clamped into the allocation),
 // B) the fused element maths, C) predicated stores.  Partial quads are stored element-wise so the
 // zero padding and the constant-1 column are never touched.
-template <typename OT, typename AT, bool HAS_AUX, bool WRITEBACK, int BM, int BN, int NT = kThreads, typename Op>
+// ROWP (the loss pass of a masked step): rows whose byte rowp[row * rowp_ld] is 0 are handed to `op` as not ok.
+template <typename OT, typename AT, bool HAS_AUX, bool WRITEBACK, int BM, int BN, int NT = kThreads, bool ROWP = false, typename Op>
 __device__ __forceinline__ void tile_pass(float* Cs, OT* out, int ld0, const AT* aux, int ldx,
-                                          int M, int N, int m0, int n0, Op op) {
+                                          int M, int N, int m0, int n0, Op op,
+                                          const unsigned char* rowp = nullptr, int rowp_ld = 0) {
     constexpr int VW = Vec16<OT>::VW;                     // elements per 16-byte store
     constexpr int LDC = BN + 4, QC = BN / VW, NG = BM * QC;   // NG groups of VW elements in the tile
     constexpr int NQT = (NG + NT - 1) / NT;               // groups per thread (the smallest tile has fewer groups than threads)
@@ -313,7 +316,8 @@ __device__ __forceinline__ void tile_pass(float* Cs, OT* out, int ld0, const AT*
             const int raw = tid + (q0 + q) * NT;
             const bool mine = !PARTIAL || raw < NG;       // threads beyond the tile's last group compute on a clamped copy, store nothing
             const int idx = PARTIAL ? min(raw, NG - 1) : raw, row = idx / QC, c0 = (idx - row * QC) * VW;
-            const bool rok = mine && m0 + row < M;
+            bool rok = mine && m0 + row < M;
+            if (ROWP) rok = rok && rowp[(size_t)min(m0 + row, M - 1) * rowp_ld] != 0;
 #pragma unroll
             for (int e = 0; e < VW; ++e) c[q][e] = op(c[q][e], a[q][e], rok && (n0 + c0 + e < N));
             if (WRITEBACK && mine) {
@@ -337,7 +341,10 @@ __device__ __forceinline__ void tile_pass(float* Cs, OT* out, int ld0, const AT*
 // their gradients w.r.t. (mu, lv).  The log-determinant terms of the two directed KLs cancel, so
 // per sample and dimension  S = 1/2 [ e^a + e^-a - 2 + D^2 (e^-lvi + e^-lvj) ],  a = lvi-lvj,
 // D = mui-muj;  e^a + e^-a - 2 is evaluated as (2 sinh(a/2))^2 to avoid cancellation.
-template <int NW = 4> __device__ __forceinline__ void latent_item(const WorkItem& w, int t, float* red) {
+// MASK (masked steps, WorkItem::present): per row, the KL term of modality m and its (mu, lv) gradient count only where m is
+// present, the association term of a pair only where both are -- each gated by a SELECT of the value the unmasked item computes
+// (the same expression, so an all-present mask gives the same bits), never by a multiplication with 0.
+template <int NW, bool MASK> __device__ __forceinline__ void latent_item(const WorkItem& w, int t, float* red) {
     constexpr int kThreads = NW * 64;        // (shadows avae::kThreads: the 8-wave kernels run this item with 512 threads)
     const float* mulv[kMaxMod] = {reinterpret_cast<const float*>(w.A), reinterpret_cast<const float*>(w.B),
                                   reinterpret_cast<const float*>(w.aux0), reinterpret_cast<const float*>(w.aux1)};
@@ -350,13 +357,16 @@ template <int NW = 4> __device__ __forceinline__ void latent_item(const WorkItem
         const int grow = t * kLatentRows + row;
         if (grow >= M) continue;
         float mu[kMaxMod], lv[kMaxMod], gmu[kMaxMod], glv[kMaxMod], en[kMaxMod];
+        bool pm[kMaxMod];
         const float eps_v = w.eps[(size_t)grow * w.ldx + d];
 #pragma unroll
         for (int m = 0; m < kMaxMod; ++m) {
             mu[m] = lv[m] = gmu[m] = glv[m] = 0.0f; en[m] = 1.0f;
+            pm[m] = true;
             if (m < w.n_mod) {
                 mu[m] = mulv[m][(size_t)grow * nz2 + d];
                 lv[m] = mulv[m][(size_t)grow * nz2 + nz + d];
+                if (MASK) pm[m] = w.present[(size_t)grow * w.present_ld + m] != 0;
             }
         }
 #pragma unroll
@@ -365,9 +375,10 @@ template <int NW = 4> __device__ __forceinline__ void latent_item(const WorkItem
                 const float el = fexp(lv[m]);
                 en[m] = frcp(el);                                   // e^-lv
                 const float s = w.wts[m] * w.inv_bg;
-                csum += s * (-0.5f * (1.0f + lv[m] - mu[m] * mu[m] - el));
-                gmu[m] = s * mu[m];
-                glv[m] = 0.5f * s * (el - 1.0f);
+                const float c1 = csum + s * (-0.5f * (1.0f + lv[m] - mu[m] * mu[m] - el));
+                csum = pm[m] ? c1 : csum;
+                gmu[m] = pm[m] ? s * mu[m] : 0.0f;
+                glv[m] = pm[m] ? 0.5f * s * (el - 1.0f) : 0.0f;
             }
         }
 #pragma unroll
@@ -375,14 +386,18 @@ template <int NW = 4> __device__ __forceinline__ void latent_item(const WorkItem
 #pragma unroll
             for (int j = i + 1; j < kMaxMod; ++j) {
                 if (j < w.n_mod) {
+                    const bool pp = pm[i] && pm[j];
                     const float a = lv[i] - lv[j], dl = mu[i] - mu[j];
                     const float sh = two_sinh(0.5f * a);             // e^(a/2) - e^(-a/2)
                     const float dsh = two_sinh(a);                   // e^a - e^-a
-                    csum += w.lambda * 0.5f * (sh * sh + dl * dl * (en[i] + en[j]));
+                    const float c1 = csum + w.lambda * 0.5f * (sh * sh + dl * dl * (en[i] + en[j]));
+                    csum = pp ? c1 : csum;
                     const float gm = w.lambda * dl * (en[i] + en[j]);
-                    gmu[i] += gm; gmu[j] -= gm;
-                    glv[i] += 0.5f * w.lambda * (dsh - dl * dl * en[i]);
-                    glv[j] += 0.5f * w.lambda * (-dsh - dl * dl * en[j]);
+                    const float gmi = gmu[i] + gm, gmj = gmu[j] - gm;
+                    gmu[i] = pp ? gmi : gmu[i]; gmu[j] = pp ? gmj : gmu[j];
+                    const float gli = glv[i] + 0.5f * w.lambda * (dsh - dl * dl * en[i]);
+                    const float glj = glv[j] + 0.5f * w.lambda * (-dsh - dl * dl * en[j]);
+                    glv[i] = pp ? gli : glv[i]; glv[j] = pp ? glj : glv[j];
                 }
             }
         }
@@ -582,7 +597,9 @@ __device__ __forceinline__ WorkItem item_of(const TnLaunchArgs& args, int y) {
 // of 1 KiB and the CU's texture-address path takes them at 64 B/clk -- ~16 clocks each, 770 clocks per tile -- with the issuing
 // wave stalled meanwhile; issued by the multiplying waves those stalls (420 clocks per wave and tile) sat on the critical path
 // of every tile whichever way the waves were ordered.  Producers stall alone.
-template <typename CT, int BM, int BN, int RING, int NW = 4, bool TN = false, int NP = 0>
+// MASK: the masked twin's launches (WorkItem::present set in their loss and latent items, launch_grouped picks these instances) --
+// the loss of a row whose modality is absent and the latent terms of absent modalities are 0 by selection.
+template <typename CT, int BM, int BN, int RING, int NW = 4, bool TN = false, int NP = 0, bool MASK = false>
 __global__ void __launch_bounds__((NW + NP) * 64, (RING == 2 ? 2 : 1)) k_grouped(const typename ArgsOf<TN>::type args, DevState* st, int lds_bytes,
                                                       unsigned long long* stamps, int launch_id) {
     unsigned char* smem = avae_dyn_smem;
@@ -1095,7 +1112,30 @@ __global__ void __launch_bounds__((NW + NP) * 64, (RING == 2 ? 2 : 1)) k_grouped
                 CT* dA = reinterpret_cast<CT*>(w.out0);
                 const float sc = w.scale;
                 float csum = 0.0f;
-                if (w.binary) {
+                if constexpr (MASK) {
+                    // masked step: bit i of pmask = row ep_row + 16 i present -- loss and gradient of an absent row 0 by selection
+                    unsigned pmask = 0;
+#pragma unroll
+                    for (int i = 0; i < MI; ++i)
+                        pmask |= (ep_row + 16 * i < M && w.present[(size_t)(ep_row + 16 * i) * w.present_ld] != 0) ? 1u << i : 0u;
+                    if (w.binary) {
+                        regep_store<CT, MI, NI>(acc, dA, w.ld0, M, N, ep_row, cwave, lane, [&](int i, int j, int r, float a0) {
+                            const bool ok = ep_row + 16 * i < M && ep_col + 16 * j + r < N && ((pmask >> i) & 1u);
+                            float sl, da;
+                            loss_bernoulli(a0 + bias[j][r], xv[i][j][r], sc, sl, da);
+                            csum += ok ? sl : 0.0f;
+                            return ok ? da : 0.0f;
+                        });
+                    } else {
+                        regep_store<CT, MI, NI>(acc, dA, w.ld0, M, N, ep_row, cwave, lane, [&](int i, int j, int r, float a0) {
+                            const bool ok = ep_row + 16 * i < M && ep_col + 16 * j + r < N && ((pmask >> i) & 1u);
+                            float sl, da;
+                            loss_gauss(a0 + bias[j][r], xv[i][j][r], sc, sl, da);
+                            csum += ok ? sl : 0.0f;
+                            return ok ? da : 0.0f;
+                        });
+                    }
+                } else if (w.binary) {
                     regep_store<CT, MI, NI>(acc, dA, w.ld0, M, N, ep_row, cwave, lane, [&](int i, int j, int r, float a0) {
                         const bool ok = ep_row + 16 * i < M && ep_col + 16 * j + r < N;
                         float sl, da;
@@ -1207,26 +1247,30 @@ __global__ void __launch_bounds__((NW + NP) * 64, (RING == 2 ? 2 : 1)) k_grouped
       if constexpr (NW == 4) {     // 8-wave tiles carry the plain kinds only (host: finish_launch)
         // Bernoulli: -sum x log(1e-3+p) + (1-x) log(1e-3+1-p), p = sigmoid(a)  (:321-324), mean over batch (:340)
         // Gaussian : sum (x-a)^2 / 2 over the WHOLE batch, not averaged          (:327-328,:340)
+        // (masked step: rows whose modality is absent are not ok -- loss and gradient 0 by selection)
         CT* dA = reinterpret_cast<CT*>(w.out0);
         const float* X = reinterpret_cast<const float*>(w.aux0);
         const float sc = w.scale;
         float csum = 0.0f;
-        if (w.binary) {
-            tile_pass<CT, float, true, false, BM, BN>(Cs, dA, w.ld0, X, w.ldx, M, N, m0, n0,
-                [&csum, sc](float a, float x, bool ok) {
-                    float sl, da;
-                    loss_bernoulli(a, x, sc, sl, da);
-                    csum += ok ? sl : 0.0f;
-                    return ok ? da : 0.0f;
-                });
+        auto bern = [&csum, sc](float a, float x, bool ok) {
+            float sl, da;
+            loss_bernoulli(a, x, sc, sl, da);
+            csum += ok ? sl : 0.0f;
+            return ok ? da : 0.0f;
+        };
+        auto gauss = [&csum, sc](float a, float x, bool ok) {
+            float sl, da;
+            loss_gauss(a, x, sc, sl, da);
+            csum += ok ? sl : 0.0f;
+            return ok ? da : 0.0f;
+        };
+        if constexpr (MASK) {
+            if (w.binary) tile_pass<CT, float, true, false, BM, BN, kThreads, true>(Cs, dA, w.ld0, X, w.ldx, M, N, m0, n0, bern, w.present, w.present_ld);
+            else tile_pass<CT, float, true, false, BM, BN, kThreads, true>(Cs, dA, w.ld0, X, w.ldx, M, N, m0, n0, gauss, w.present, w.present_ld);
+        } else if (w.binary) {
+            tile_pass<CT, float, true, false, BM, BN>(Cs, dA, w.ld0, X, w.ldx, M, N, m0, n0, bern);
         } else {
-            tile_pass<CT, float, true, false, BM, BN>(Cs, dA, w.ld0, X, w.ldx, M, N, m0, n0,
-                [&csum, sc](float a, float x, bool ok) {
-                    float sl, da;
-                    loss_gauss(a, x, sc, sl, da);
-                    csum += ok ? sl : 0.0f;
-                    return ok ? da : 0.0f;
-                });
+            tile_pass<CT, float, true, false, BM, BN>(Cs, dA, w.ld0, X, w.ldx, M, N, m0, n0, gauss);
         }
         const float total = block_sum(csum, red);
         if (tid == 0) w.partial[w.slot_base + t] = total;
@@ -1346,7 +1390,7 @@ __global__ void __launch_bounds__((NW + NP) * 64, (RING == 2 ? 2 : 1)) k_grouped
     return;
     }   // GEMM kinds
     if constexpr (!TN && (NW == 4 || (NW == 8 && BN == 64))) {
-        if (w.kind == K_LATENT) latent_item<NW>(w, t, red);
+        if (w.kind == K_LATENT) latent_item<NW, MASK>(w, t, red);
         else cost_item<NW>(w, st, red);
         AVAE_STAMP(4)
         AVAE_STAMP_FLUSH()
@@ -1475,7 +1519,8 @@ template <typename K> static void set_max_lds(K kernel) {
 // The small nets' output + loss launch on the same lean frame (tile configuration 9): K_FWD_OUT_LOSS items (Bernoulli or Gaussian per
 // item) and the K_LATENT item that rides with them.  The exact fp32 inputs the loss compares with are fetched ahead of the first tile;
 // loss, gradient and the tile's cost partial come from the accumulators (one LDS round for the fixed-order block sum).
-template <typename CT>
+// MASK (the masked twin's launch, WorkItem::present set): the loss and gradient of a row whose modality is absent are 0 by selection.
+template <typename CT, bool MASK>
 __global__ void __launch_bounds__(kThreads) k_small_loss(const LaunchArgs args, unsigned long long* stamps, int launch_id) {
     constexpr int BM = 32, RING = 4, ES = (int)sizeof(CT);
     constexpr int kStage = 64 * kTileBytesK;
@@ -1496,7 +1541,7 @@ __global__ void __launch_bounds__(kThreads) k_small_loss(const LaunchArgs args, 
         t = (part < r ? part * (q + 1) : r * (q + 1) + (part - r) * q) + idx;
     }
     if (w.kind == K_LATENT) {
-        latent_item<4>(w, t, red);
+        latent_item<4, MASK>(w, t, red);
         AVAE_STAMP(4)
         AVAE_STAMP_FLUSH()
         return;
@@ -1513,6 +1558,7 @@ __global__ void __launch_bounds__(kThreads) k_small_loss(const LaunchArgs args, 
     const unsigned char* srcB = reinterpret_cast<const unsigned char*>(w.B) + (size_t)(n0 + prow) * w.ldb * ES + lc;
     const int orow = m0 + wr * 16 + fr, ocol = n0 + wc * 16 + 4 * fq;
     const f32x4 xq = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(w.aux0) + (size_t)min(orow, w.M - 1) * w.ldx + min(ocol, w.ldx - 4));
+    const bool rpres = !MASK || w.present[(size_t)min(orow, w.M - 1) * w.present_ld] != 0;      // this lane's row is present
 #define AVAE_S_DMA(kt, buf)                                                                                             \
     { __builtin_amdgcn_global_load_lds((gp_t)(srcA + (size_t)(kt) * kTileBytesK), (lp_t)(smem + (buf) * kStage + wave * 1024), 16, 0, 0);          \
       __builtin_amdgcn_global_load_lds((gp_t)(srcB + (size_t)(kt) * kTileBytesK), (lp_t)(smem + (buf) * kStage + (4 + wave) * 1024), 16, 0, 0); }
@@ -1546,7 +1592,7 @@ __global__ void __launch_bounds__(kThreads) k_small_loss(const LaunchArgs args, 
     float csum = 0.0f, v[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        const bool ok = orow < w.M && ocol + e < w.N;
+        const bool ok = orow < w.M && ocol + e < w.N && rpres;
         float sl, da;
         if (w.binary) loss_bernoulli(acc[e], xq[e], sc, sl, da);
         else loss_gauss(acc[e], xq[e], sc, sl, da);
@@ -1561,8 +1607,13 @@ __global__ void __launch_bounds__(kThreads) k_small_loss(const LaunchArgs args, 
 }
 void launch_small_loss(int compute_dtype, const LaunchArgs& args, int grid_x, int grid_y, int lds_bytes, hipStream_t s, unsigned long long* stamps, int launch_id) {
     const dim3 grid(grid_x, grid_y), block(kThreads);
-    if (compute_dtype == AVAE_BF16) AVAE_LAUNCH((k_small_loss<__bf16>), grid, block, lds_bytes, s, args, stamps, launch_id);
-    else AVAE_LAUNCH((k_small_loss<float>), grid, block, lds_bytes, s, args, stamps, launch_id);
+    bool masked = false;
+    for (int i = 0; i < args.n_items; ++i) masked = masked || args.items[i].present != nullptr;
+    if (masked) {
+        if (compute_dtype == AVAE_BF16) AVAE_LAUNCH((k_small_loss<__bf16, true>), grid, block, lds_bytes, s, args, stamps, launch_id);
+        else AVAE_LAUNCH((k_small_loss<float, true>), grid, block, lds_bytes, s, args, stamps, launch_id);
+    } else if (compute_dtype == AVAE_BF16) AVAE_LAUNCH((k_small_loss<__bf16, false>), grid, block, lds_bytes, s, args, stamps, launch_id);
+    else AVAE_LAUNCH((k_small_loss<float, false>), grid, block, lds_bytes, s, args, stamps, launch_id);
 }
 
 // ---- the two head launches of the small nets on the lean frame (tile configurations 10 and 11): 32x64 tile, narrow result into an
@@ -2309,10 +2360,37 @@ static void grouped_attrs_once() {
         else AVAE_LAUNCH((k_grouped<CT, 128, 128, 2, 4, TNF>), grid, block, lds_bytes, s, args, st, lds_bytes, stamps, launch_id);                    \
     } while (0)
 
+// The masked twin's launches (an item with WorkItem::present): the MASK instances of the configurations that carry loss / latent items.
+template <typename CT>
+static void launch_grouped_masked(int tile_cfg, const LaunchArgs& args, dim3 grid, dim3 block, int lds_bytes, DevState* st, hipStream_t s,
+                                  unsigned long long* stamps, int launch_id) {
+    static const bool once = [] {
+        set_max_lds(k_grouped<CT, 64, 64, 4, 4, false, 0, true>); set_max_lds(k_grouped<CT, 128, 128, 2, 4, false, 0, true>);
+        set_max_lds(k_grouped<CT, 32, 64, 4, 4, false, 0, true>); set_max_lds(k_grouped<CT, 64, 128, 4, 4, false, 0, true>);
+        set_max_lds(k_grouped<CT, 32, 32, 4, 4, false, 0, true>); set_max_lds(k_grouped<CT, 256, 64, 3, 8, false, 0, true>);
+        return true;
+    }();
+    (void)once;
+    if (tile_cfg == 6) AVAE_LAUNCH((k_grouped<CT, 256, 64, 3, 8, false, 0, true>), grid, block, lds_bytes, s, args, st, lds_bytes, stamps, launch_id);
+    else if (tile_cfg == 3) AVAE_LAUNCH((k_grouped<CT, 32, 64, 4, 4, false, 0, true>), grid, block, lds_bytes, s, args, st, lds_bytes, stamps, launch_id);
+    else if (tile_cfg == 5) AVAE_LAUNCH((k_grouped<CT, 32, 32, 4, 4, false, 0, true>), grid, block, lds_bytes, s, args, st, lds_bytes, stamps, launch_id);
+    else if (tile_cfg == 4) AVAE_LAUNCH((k_grouped<CT, 64, 128, 4, 4, false, 0, true>), grid, block, lds_bytes, s, args, st, lds_bytes, stamps, launch_id);
+    else if (tile_cfg == 0) AVAE_LAUNCH((k_grouped<CT, 64, 64, 4, 4, false, 0, true>), grid, block, lds_bytes, s, args, st, lds_bytes, stamps, launch_id);
+    else if (tile_cfg == 1) AVAE_LAUNCH((k_grouped<CT, 128, 128, 2, 4, false, 0, true>), grid, block, lds_bytes, s, args, st, lds_bytes, stamps, launch_id);
+    else throw std::runtime_error("internal error: a masked launch on a tile configuration without the presence gate");   // (the host refuses such plans)
+}
+
 void launch_grouped(int compute_dtype, int tile_cfg, const LaunchArgs& args, int grid_x, int grid_y, int lds_bytes,
                     DevState* st, hipStream_t s, unsigned long long* stamps, int launch_id) {
     grouped_attrs_once();
     dim3 grid(grid_x, grid_y), block(tile_cfg == 2 || tile_cfg == 6 ? 512 : kThreads);
+    bool masked = false;
+    for (int i = 0; i < args.n_items; ++i) masked = masked || args.items[i].present != nullptr;
+    if (masked) {
+        if (compute_dtype == AVAE_BF16) launch_grouped_masked<__bf16>(tile_cfg, args, grid, block, lds_bytes, st, s, stamps, launch_id);
+        else launch_grouped_masked<float>(tile_cfg, args, grid, block, lds_bytes, st, s, stamps, launch_id);
+        return;
+    }
     if (tile_cfg == 6) {
         if (compute_dtype == AVAE_BF16) AVAE_LAUNCH((k_grouped<__bf16, 256, 64, 3, 8, false, 0>), grid, block, lds_bytes, s, args, st, lds_bytes, stamps, launch_id);
         else AVAE_LAUNCH((k_grouped<float, 256, 64, 3, 8, false, 0>), grid, block, lds_bytes, s, args, st, lds_bytes, stamps, launch_id);
@@ -2444,7 +2522,8 @@ __device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned
     out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
 
-template <typename CT>
+// MASK: the masked staging (PrepArgs::pres_src set; launch_prep / prep_kernel pick the instance)
+template <typename CT, bool MASK>
 __global__ void __launch_bounds__(kThreads) k_prep(PrepArgs a) {
     const int tid = threadIdx.x;
     const int bstep = a.n_steps > 1 ? (int)blockIdx.x / a.blocks_per_step : 0;     // which of the batched steps
@@ -2497,6 +2576,38 @@ __global__ void __launch_bounds__(kThreads) k_prep(PrepArgs a) {
     // the caller's rows as one 16-byte load per quad whatever their alignment (column blocks of a [rows][931] matrix start anywhere)
     typedef float f32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));      // dword-aligned quad: one global_load_dwordx4 (the
                                                                                   // hardware takes any dword alignment in global memory)
+    if constexpr (MASK) {
+        // masked staging: an absent (row, modality) -- every row of a null source -- is never read and staged as zeros; the threads
+        // of segment 0's first column tile copy the step's presence bytes (0/1, null sources folded in) into staging set bstep
+        const unsigned char* pres = a.pres_src + (size_t)bstep * w.rows * a.pres_ld;
+        if (it == 0 && tc == 0 && tid < 64 && r0 + tid < w.rows) {
+            const int row = r0 + tid;
+            unsigned char* pd = a.pres_dst + ((size_t)bstep * w.rows + row) * a.pres_ld;
+            for (int m = 0; m < a.n_seg; ++m) pd[m] = (a.seg[m].src && pres[(size_t)row * a.pres_ld + m]) ? 1 : 0;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int r = (tid >> 4) + 16 * i;
+            const int grow = r0 + r, gcol = c0 + c4;
+            float v[4] = {0.f, 0.f, 0.f, 0.f};
+            if (grow < w.rows && gcol < w.cols) {
+                if (w.src && pres[(size_t)grow * a.pres_ld + it]) {          // (a null source: modality absent on every row)
+                    if (gcol + 3 < w.cols) {
+                        const f32x4_a4 q = *reinterpret_cast<const f32x4_a4*>(src + (size_t)grow * w.src_ld + gcol);
+                        v[0] = q[0]; v[1] = q[1]; v[2] = q[2]; v[3] = q[3];
+                    } else {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e)
+                            if (gcol + e < w.cols) v[e] = src[(size_t)grow * w.src_ld + gcol + e];
+                    }
+                }
+                const int nv = w.cols - gcol;
+                if (dst32) store_row<float>(dst32 + (size_t)grow * w.ld32 + gcol, v, nv);
+                store_row<CT>(dstc + (size_t)grow * w.ldc + gcol, v, nv);
+            }
+        }
+        return;
+    }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int r = (tid >> 4) + 16 * i;
@@ -2518,15 +2629,19 @@ __global__ void __launch_bounds__(kThreads) k_prep(PrepArgs a) {
     }
 }
 
-const void* prep_kernel(int compute_dtype) {
-    return compute_dtype == AVAE_BF16 ? reinterpret_cast<const void*>(k_prep<__bf16>) : reinterpret_cast<const void*>(k_prep<float>);
+const void* prep_kernel(int compute_dtype, bool masked) {
+    if (masked) return compute_dtype == AVAE_BF16 ? reinterpret_cast<const void*>(k_prep<__bf16, true>) : reinterpret_cast<const void*>(k_prep<float, true>);
+    return compute_dtype == AVAE_BF16 ? reinterpret_cast<const void*>(k_prep<__bf16, false>) : reinterpret_cast<const void*>(k_prep<float, false>);
 }
 
 void launch_prep(int compute_dtype, const PrepArgs& a, hipStream_t s) {
     const int n_blocks = (a.total_tiles + a.eps_blocks) * (a.n_steps > 1 ? a.n_steps : 1);
     if (n_blocks <= 0) return;
-    if (compute_dtype == AVAE_BF16) AVAE_LAUNCH((k_prep<__bf16>), dim3(n_blocks), dim3(kThreads), 0, s, a);
-    else AVAE_LAUNCH((k_prep<float>), dim3(n_blocks), dim3(kThreads), 0, s, a);
+    if (a.pres_src) {
+        if (compute_dtype == AVAE_BF16) AVAE_LAUNCH((k_prep<__bf16, true>), dim3(n_blocks), dim3(kThreads), 0, s, a);
+        else AVAE_LAUNCH((k_prep<float, true>), dim3(n_blocks), dim3(kThreads), 0, s, a);
+    } else if (compute_dtype == AVAE_BF16) AVAE_LAUNCH((k_prep<__bf16, false>), dim3(n_blocks), dim3(kThreads), 0, s, a);
+    else AVAE_LAUNCH((k_prep<float, false>), dim3(n_blocks), dim3(kThreads), 0, s, a);
 }
 
 // ------------------------------------------------------------------ conv branch: im2col / col2im

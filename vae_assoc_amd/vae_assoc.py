@@ -356,6 +356,50 @@ class AssocVariationalAutoEncoder(object):
             e = e.contiguous()
         return ts, ptrs, lds, e
 
+    def _masked_args(self, X, eps, present, n_steps=1):
+        """Arguments of the masked entry points: ``present`` [batch_size * n_steps, M] (bool or integer, array or tensor, any device;
+        nonzero = observed) -> uint8 device tensor; ``X[m] = None`` -> a NULL source (modality m absent on every row)."""
+        world = self._sync.world_size if self._sync is not None else 1
+        if world > 1:
+            raise RuntimeError("present= (partially paired batches) runs on one replica; this model is data parallel over %d ranks" % world)
+        M = len(self.network_architectures)
+        if len(X) != M:
+            raise ValueError("expected a list of %d modalities, got %d" % (M, len(X)))
+        rows = self.batch_size * n_steps
+        p = present if torch.is_tensor(present) else torch.as_tensor(np.asarray(present))
+        if p.dim() != 2 or p.shape[0] != rows or p.shape[1] != M:
+            raise ValueError("present must be [batch_size%s, %d] = [%d, %d], got %s"
+                             % (" x n_steps" if n_steps > 1 else "", M, rows, M, tuple(p.shape)))
+        p = (p != 0).to(device=self.device, dtype=torch.uint8).contiguous()
+        ts, ptrs, lds = [], [], []
+        for m, (x, na) in enumerate(zip(X, self.network_architectures)):
+            if x is None:
+                ptrs.append(None)
+                lds.append(0)
+                continue
+            t, _ = self._dev(x, int(na["n_input"]))
+            if t.shape[0] != rows:
+                raise ValueError("expected %d rows (batch_size%s), got %d" % (rows, " x n_steps" if n_steps > 1 else "", t.shape[0]))
+            ts.append(t)
+            ptrs.append(t.data_ptr())
+            lds.append(t.stride(0) if t.shape[0] > 1 else t.shape[1])
+        e = None
+        if eps is not None:
+            e, _ = self._dev(eps, self.n_z)
+            if e.shape[0] != rows:
+                raise ValueError("eps must be [batch_size%s, n_z]" % (" x n_steps" if n_steps > 1 else ""))
+            e = e.contiguous()
+        return ts, (C.c_void_p * M)(*ptrs), (C.c_int32 * M)(*lds), e, p
+
+    def _train_masked(self, X, n_steps, eps, present, return_cost):
+        ts, ptrs, lds, e, p = self._masked_args(X, eps, present, n_steps)
+        cost = C.c_float(0.0)
+        _capi.check(self._h, self._L.avae_train_steps_masked(self._h, n_steps, ptrs, lds, p.data_ptr(),
+                                                             e.data_ptr() if e is not None else None,
+                                                             C.byref(cost) if return_cost else None, self._stream()),
+                    "avae_train_steps_masked")
+        return cost.value if return_cost else None
+
     def get_params(self):
         out = np.empty(self.n_params, dtype=np.float32)
         _capi.check(self._h, self._L.avae_get_params(self._h, out.ctypes.data_as(C.c_void_p)), "avae_get_params")
@@ -422,10 +466,16 @@ class AssocVariationalAutoEncoder(object):
         return cost.value if want_cost else None
 
     # ------------------------------------------------------------------ reference surface
-    def partial_fit(self, X, eps=None, return_cost=True):
+    def partial_fit(self, X, eps=None, return_cost=True, present=None):
         """Train model based on mini-batch of input data.  Return cost of mini-batch.
         (reference vae_assoc.py:378-386).  ``return_cost=False`` skips the host synchronise;
-        the cost stays retrievable through ``cost_history``."""
+        the cost stays retrievable through ``cost_history``.
+
+        ``present`` (optional, one replica): [batch_size, M] presence flags, nonzero = row n has modality m.  The step then charges
+        every row only with the terms of the modalities it has (include/avae.h; the divisor stays batch_size),
+        and ``X[m]`` may be None for a modality absent from the whole batch."""
+        if present is not None:
+            return self._train_masked(X, 1, eps, present, return_cost)
         if self._sync is not None and self._sync.world_size > 1 and not self._comm_lib:
             # host-owned collective (torch.distributed) over the library's buckets
             cost = dp_train_step_bucketed(self, self._sync, self._buckets, X, eps)
@@ -437,12 +487,15 @@ class AssocVariationalAutoEncoder(object):
                     "avae_train_step")
         return cost.value if return_cost else None
 
-    def partial_fit_steps(self, X, n_steps, eps=None, return_cost=True):
+    def partial_fit_steps(self, X, n_steps, eps=None, return_cost=True, present=None):
         """``n_steps`` successive ``partial_fit`` calls in one submission: step i trains on rows
         [i*batch_size, (i+1)*batch_size) of every X[m] (and of ``eps``) -- what the reference's inner
         loop does with ``DataSet.next_batch``'s consecutive slices (vae_assoc.py:541-550).  Returns the
-        last step's cost; every step's cost is in ``cost_history``."""
+        last step's cost; every step's cost is in ``cost_history``.  ``present``: [n_steps * batch_size, M]
+        presence flags, as in ``partial_fit``."""
         n_steps = int(n_steps)
+        if present is not None:
+            return self._train_masked(X, n_steps, eps, present, return_cost)
         if self._sync is not None and self._sync.world_size > 1 and not self._comm_lib:
             # host-owned collective: the batches are staged 16 at a time, every step runs the bucketed schedule
             ts, ptrs, lds, e = self._batch_args(X, eps, n_steps)
@@ -470,8 +523,15 @@ class AssocVariationalAutoEncoder(object):
                     "avae_train_steps")
         return cost.value if return_cost else None
 
-    def evaluate_cost(self, X, eps=None):
-        """reference vae_assoc.py:388-391 (forward + loss with a fresh eps, no update)."""
+    def evaluate_cost(self, X, eps=None, present=None):
+        """reference vae_assoc.py:388-391 (forward + loss with a fresh eps, no update).  ``present``: [batch_size, M] presence
+        flags, as in ``partial_fit`` (one replica)."""
+        if present is not None:
+            ts, ptrs, lds, e, p = self._masked_args(X, eps, present)
+            cost = C.c_float(0.0)
+            _capi.check(self._h, self._L.avae_eval_cost_masked(self._h, ptrs, lds, p.data_ptr(), e.data_ptr() if e is not None else None,
+                                                               C.byref(cost), self._stream()), "avae_eval_cost_masked")
+            return cost.value
         ts, ptrs, lds, e = self._batch_args(X, eps)
         cost = C.c_float(0.0)
         _capi.check(self._h, self._L.avae_eval_cost(self._h, ptrs, lds, e.data_ptr() if e is not None else None,
