@@ -647,14 +647,16 @@ def test_graph_replay_equals_eager(V):
     rng = np.random.default_rng(3)
     X = synth_batch(rng, 256, [784, 147], [True, False])
     eps = rng.standard_normal((4, 256, 20)).astype(np.float32)
-    res = []
-    for use_graph in (True, False):
-        m = V.AssocVariationalAutoEncoder(archs, binary=[True, False], transfer_fct="relu", weights=[50, 1], assoc_lambda=8.0,
-                                          batch_size=256, compute_dtype="bf16", seed=1, use_graph=use_graph)
-        costs = [m.partial_fit(X, eps[s]) for s in range(4)]
-        res.append((costs, m.get_params()))
-    assert res[0][0] == res[1][0], "graph and eager costs differ (kernels are deterministic)"
-    assert np.array_equal(res[0][1], res[1][1])
+    present = rng.random((4, 256, 2)) < 0.6             # the masked plan: its graphs against its eager path
+    for P in (None, present):
+        res = []
+        for use_graph in (True, False):
+            m = V.AssocVariationalAutoEncoder(archs, binary=[True, False], transfer_fct="relu", weights=[50, 1], assoc_lambda=8.0,
+                                              batch_size=256, compute_dtype="bf16", seed=1, use_graph=use_graph)
+            costs = [m.partial_fit(X, eps[s], present=None if P is None else P[s]) for s in range(4)]
+            res.append((costs, m.get_params()))
+        assert res[0][0] == res[1][0], "graph and eager costs differ (kernels are deterministic)"
+        assert np.array_equal(res[0][1], res[1][1])
 
 
 @pytest.mark.parametrize("given_eps", [False, True])

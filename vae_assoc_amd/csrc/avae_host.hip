@@ -161,6 +161,27 @@ struct Launch {
 
 struct TimingRec { hipEvent_t a, b; int launch_name; };
 
+// A captured graph; for a step graph also its template and its staging-kernel root node, kept so that the caller's pointers can be
+// patched in before a replay (hipGraphExecKernelNodeSetParams).
+struct StepGraph {
+    hipGraphExec_t exec = nullptr;
+    hipGraph_t graph = nullptr;
+    hipGraphNode_t prep = nullptr;
+    void release() {
+        if (exec) (void)hipGraphExecDestroy(exec);
+        if (graph) (void)hipGraphDestroy(graph);
+        *this = StepGraph();
+    }
+};
+
+// One form of the training step: its forward launches and their graphs -- one whole step, runs of kMultiSizes[i] steps
+// (avae_train_steps), the eval pass.
+struct StepPlan {
+    std::vector<Launch> fwd;
+    StepGraph full, multi[2], eval;
+    void release() { full.release(); multi[0].release(); multi[1].release(); eval.release(); }
+};
+
 }  // namespace
 
 struct avae_handle {
@@ -182,7 +203,7 @@ struct avae_handle {
     hipStream_t cap_stream = nullptr;
 
     std::vector<WorkItem> items;            // training + eval tables (host mirror)
-    std::vector<Launch> fwd, bwd;           // training launches: forward, dgrad chain
+    std::vector<Launch> bwd;                // training launches (the forward ones are plain.fwd): dgrad chain
     std::vector<Launch> wgrad;              // all weight gradients (-> [all-reduce ->] k_adam)
     std::vector<Launch> wgrad_adam;         // small nets, one replica: the same launch with the Adam step in its epilogue (k_small_tn): no k_adam launch
     // Data-parallel buckets: bucket 0 = the decoder side of every modality (output layer, decoder layers: their weight gradients
@@ -210,19 +231,10 @@ struct avae_handle {
     IpcArgs ipc_args{};                     // layout + peers; off / granules / cost_idx are filled per call
     hipStream_t comm_stream = nullptr;
     hipEvent_t ev_grad[2] = {nullptr, nullptr}, ev_red[2] = {nullptr, nullptr};
-    std::vector<hipGraphExec_t> g_dp[2];    // per staging set: captured segment of bucket b (forward + backward part + its weight gradients)
+    std::vector<StepGraph> g_dp[2];         // per staging set: captured segment of bucket b (forward + backward part + its weight gradients)
     // whole runs of data-parallel steps as ONE graph (staging + per step: segments, all-reduces on the comm stream, Adam per bucket):
-    hipGraphExec_t g_dpm[2] = {nullptr, nullptr};
-    hipGraph_t g_dpm_graph[2] = {nullptr, nullptr};
-    hipGraphNode_t g_dpm_prep[2] = {nullptr, nullptr};
+    StepGraph g_dpm[2];
     bool dp_graph_failed = false;           // RCCL refused stream capture on this stack: host-stepped pipeline instead
-    // Single-replica overlap inside the captured graphs (the same buckets): the decoder side's weight gradients + Adam run on a side
-    // stream from the moment bwd_dec1_latent is done, beside the encoder's backward pass, its weight gradients / Adam and -- in the
-    // multi-step graphs -- the NEXT step's encoder forward; the next step's first decoder launch waits for them.
-    bool overlap = false, ov_split_wgrad = false;
-    int fwd_dec_first = 0;                  // index in fwd of the first launch that reads decoder weights
-    hipStream_t side_stream = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_side = nullptr;
     Launch cost_only;                       // eval: K_COST alone, no step bump
     std::vector<AdamItem> adam_items;
     int adam_blocks = 0;
@@ -242,20 +254,13 @@ struct avae_handle {
     size_t off_consts = 0, off_conv_tab = 0;   // 32 B {zeros | one, 0...}; device copy of conv_tab
     std::vector<ConvA> conv_tab;             // implicit patch matrices of the training plan
 
-    hipGraphExec_t g_full = nullptr, g_eval = nullptr;
-    hipGraphExec_t g_multi[2] = {nullptr, nullptr};   // kMultiSizes[i] whole steps per replay (avae_train_steps)
-    hipGraph_t g_full_graph = nullptr, g_multi_graph[2] = {nullptr, nullptr};   // templates, kept: their staging-kernel nodes are re-parameterised per replay
-    hipGraphNode_t g_full_prep = nullptr, g_multi_prep[2] = {nullptr, nullptr};
-    // Masked steps (avae_train_steps_masked / avae_eval_cost_masked), built by the first masked call: the staged presence bytes (one set
-    // of [B][M] per staging set, allocated then -- the workspace does not grow) and the masked twin of the step -- the forward launches
-    // with WorkItem::present set in their loss and latent items; backward, weight gradients and Adam are the unmasked step's own.
+    // The training step: `plain` (its forward launches are the planner's; graphs captured at create) and, built by the first masked call
+    // (avae_train_steps_masked / avae_eval_cost_masked), its masked twin -- the forward launches with WorkItem::present set in their
+    // loss and latent items, reading the staged presence bytes (one set of [B][M] per staging set, allocated then: the workspace does
+    // not grow).  Backward, weight gradients and Adam are shared.
+    StepPlan plain, masked;
     unsigned char* pres_buf = nullptr;
     size_t pres_set = 0;                    // bytes per staging set
-    bool masked_built = false;
-    std::vector<Launch> mfwd;
-    hipGraphExec_t gm_full = nullptr, gm_eval = nullptr, gm_multi[2] = {nullptr, nullptr};
-    hipGraph_t gm_full_graph = nullptr, gm_multi_graph[2] = {nullptr, nullptr};
-    hipGraphNode_t gm_full_prep = nullptr, gm_multi_prep[2] = {nullptr, nullptr};
 
     // Calls on one handle share its activation buffers and serving slot: a call on a different stream than the previous one is
     // ordered behind that one's work (an event recorded on the old stream when the switch is seen: nothing per call otherwise).
@@ -1209,7 +1214,7 @@ void xcd_pieces(Launch& L) {
 }
 
 void build_training_plan(avae_handle* h) {
-    h->items.clear(); h->fwd.clear(); h->bwd.clear(); h->wgrad.clear(); h->conv_tab.clear();
+    h->items.clear(); h->plain.fwd.clear(); h->bwd.clear(); h->wgrad.clear(); h->conv_tab.clear();
     Builder bd(h, h->items, h->B, true);
     int slot = 0;
     int Lmax = 0;
@@ -1326,15 +1331,15 @@ void build_training_plan(avae_handle* h) {
     // ---- forward.  Modalities with fewer hidden layers simply sit out a launch; data dependencies
     // are per modality and launches are stream-ordered, so this is always safe.
     for (int k = 0; k < Lmax; ++k)
-        group("fwd_enc" + std::to_string(k + 1), h->fwd, [&] {
+        group("fwd_enc" + std::to_string(k + 1), h->plain.fwd, [&] {
             for (Mod& md : h->mods) if (k < md.L) h->items.push_back(bd.fwd_hidden(k == 0 ? md.X0 : md.E[k - 1], md.enc[k], md.E[k]));
         });
     // Experiment (AVAE_CHAIN2=1): fwd_enc1 and fwd_enc2 of the small nets as ONE launch behind a row-block-local hand-off
     // (k_chain2) instead of a kernel boundary.  Needs both on the lean 32x32 kernel, equal widths (the same tile grid) and whole quads.
-    if (std::getenv("AVAE_CHAIN2") && !any_conv && h->fwd.size() == 2 && h->fwd[0].cfg == 7 && h->fwd[1].cfg == 7 && h->fwd[0].count == h->fwd[1].count
-        && 2 * h->fwd[0].count <= kMaxItemsPerLaunch) {
-        Launch& A = h->fwd[0];
-        const Launch& Bn = h->fwd[1];
+    if (std::getenv("AVAE_CHAIN2") && !any_conv && h->plain.fwd.size() == 2 && h->plain.fwd[0].cfg == 7 && h->plain.fwd[1].cfg == 7 && h->plain.fwd[0].count == h->plain.fwd[1].count
+        && 2 * h->plain.fwd[0].count <= kMaxItemsPerLaunch) {
+        Launch& A = h->plain.fwd[0];
+        const Launch& Bn = h->plain.fwd[1];
         bool ok = true;
         for (int i = 0; i < A.count; ++i) {
             const WorkItem& a = A.args.items[i];
@@ -1346,22 +1351,22 @@ void build_training_plan(avae_handle* h) {
             for (int i = 0; i < A.count; ++i) A.args.items[A.count + i] = Bn.args.items[i];
             A.args.n_items = 2 * A.count;
             A.cfg = 13; A.name += "+" + Bn.name;
-            h->fwd.pop_back();
+            h->plain.fwd.pop_back();
         }
     }
     if (any_conv) {   // conv encoder: three convs, then the flatten + dense heads.  Per modality and stage: implicit GEMM (the patch
                       // matrix is gathered by the GEMM's own operand loads), or im2col launch + GEMM where the channels are no whole chunks
         for (int i = 0; i < 3; ++i) {
             auto src_of = [&, i](Mod& md) { return i == 0 ? h->at<void>(md.X0.rm) : h->at<void>(md.cenc[i - 1].Y.rm); };
-            gather_launch("conv_enc" + std::to_string(i + 1) + "_im2col", h->fwd, [&](Mod& md) -> const ConvStage& { return md.cenc[i]; },
+            gather_launch("conv_enc" + std::to_string(i + 1) + "_im2col", h->plain.fwd, [&](Mod& md) -> const ConvStage& { return md.cenc[i]; },
                           src_of, [i](const Mod& md) { return !md.cenc[i].impl; });
-            group("conv_enc" + std::to_string(i + 1), h->fwd, [&] {
+            group("conv_enc" + std::to_string(i + 1), h->plain.fwd, [&] {
                 for (Mod& md : h->mods) if (md.conv) h->items.push_back(md.cenc[i].impl ? bd.conv_fwd_impl(md.cenc[i], src_of(md)) : bd.conv_fwd(md.cenc[i])); });
         }
-        gather_launch("conv_head_im2col", h->fwd, [&](Mod& md) -> const ConvStage& { return md.cenc[3]; },
+        gather_launch("conv_head_im2col", h->plain.fwd, [&](Mod& md) -> const ConvStage& { return md.cenc[3]; },
                       [&](Mod& md) { return h->at<void>(md.cenc[2].Y.rm); }, [](const Mod& md) { return !md.cenc[3].impl; });
     }
-    group("fwd_head", h->fwd, [&] { for (Mod& md : h->mods) h->items.push_back(bd.fwd_head(md, true, md.conv && md.cenc[3].impl)); });
+    group("fwd_head", h->plain.fwd, [&] { for (Mod& md : h->mods) h->items.push_back(bd.fwd_head(md, true, md.conv && md.cenc[3].impl)); });
     // KL + association terms and their (mu, lv) gradients need every modality's (mu, lv) (ready after fwd_head) and are needed by
     // bwd_dec1_latent.  Small nets: they ride in the fwd_out_loss launch (the decoder's hidden launches stay plain GEMM launches).
     // Big nets, whose loss launch runs one 144-KB workgroup per CU on the 8-wave tile: there the item's workgroups would each take a
@@ -1377,13 +1382,12 @@ void build_training_plan(avae_handle* h) {
         }
         latent_alone = t64 >= 192 && t128 >= 192 && !narrow && !std::getenv("AVAE_NO_LOSS8");      // = finish_launch's choice of cfg 6
     }
-    if (latent_alone) group("latent", h->fwd, [&] { h->items.push_back(bd.latent()); });
-    h->fwd_dec_first = (int)h->fwd.size();
+    if (latent_alone) group("latent", h->plain.fwd, [&] { h->items.push_back(bd.latent()); });
     for (int k = 0; k < std::max(Lmax, 1); ++k) {
-        group("fwd_dec" + std::to_string(k + 1), h->fwd, [&] {
+        group("fwd_dec" + std::to_string(k + 1), h->plain.fwd, [&] {
             for (Mod& md : h->mods) if (k < md.L) h->items.push_back(bd.fwd_hidden(k == 0 ? md.Z : md.D[k - 1], md.dec[k], md.D[k]));
         });
-        if (k == 0 && !any_conv && !latent_alone && fuse_tail(h->fwd, 1)) h->fwd_dec_first = (int)h->fwd.size() - 1;      // fwd_dec1 rides in fwd_head
+        if (k == 0 && !any_conv && !latent_alone) fuse_tail(h->plain.fwd, 1);      // fwd_dec1 rides in fwd_head
     }
     if (any_conv) {   // adjoint filter shadows of the transposed-conv stages that run through Padj / the scatter product (refreshed once per step)
         Launch L;
@@ -1396,7 +1400,7 @@ void build_training_plan(avae_handle* h) {
             g.block_base = base; base += (st.g.Cin * st.g.k * st.g.k * st.d.out + kThreads - 1) / kThreads;
         }
         L.blocks = base;
-        if (base > 0 && std::getenv("AVAE_NO_WADJ_FOLD")) h->fwd.push_back(L);       // default: k_adam writes these shadows (AdamItem::Wadj)
+        if (base > 0 && std::getenv("AVAE_NO_WADJ_FOLD")) h->plain.fwd.push_back(L);       // default: k_adam writes these shadows (AdamItem::Wadj)
     }
     if (any_conv) {   // deconv decoder: four transposed convs (+ bias + sigmoid each), then the dense output layer
         for (int i = 0; i < 4; ++i) {
@@ -1404,9 +1408,9 @@ void build_training_plan(avae_handle* h) {
             // GEMM in gather form, round 2's adjoint-frame scatter product, or im2col + GEMM
             auto plain = [&, i](const Mod& md) { return !md.cdec[i].thin && !md.cdec[i].adj && !md.cdec[i].impl; };
             auto src_of = [&, i](Mod& md) { return i == 0 ? h->at<void>(md.Z.rm) : h->at<void>(md.cdec[i - 1].Y.rm); };
-            if (is_thin(i)) thin_launch("conv_dec" + std::to_string(i + 1) + "_direct", h->fwd, 0, i);
+            if (is_thin(i)) thin_launch("conv_dec" + std::to_string(i + 1) + "_direct", h->plain.fwd, 0, i);
             if (is_adj(i)) {       // scatter product on the stage's (small) input, then overlap-add + bias + transfer function
-                group("conv_dec" + std::to_string(i + 1) + "_scatter", h->fwd, [&] {
+                group("conv_dec" + std::to_string(i + 1) + "_scatter", h->plain.fwd, [&] {
                     for (Mod& md : h->mods) if (md.conv && md.cdec[i].adj) h->items.push_back(bd.adj_fwd(md.cdec[i], md.cdec[i - 1])); });
                 Launch L;
                 L.name = "conv_dec" + std::to_string(i + 1) + "_overlap"; L.type = 2;
@@ -1417,19 +1421,19 @@ void build_training_plan(avae_handle* h) {
                     L.ca.seg[L.ca.n_seg++] = c;
                 }
                 L.blocks = base;
-                h->fwd.push_back(L);
+                h->plain.fwd.push_back(L);
             }
-            gather_launch("conv_dec" + std::to_string(i + 1) + "_im2col", h->fwd, [&](Mod& md) -> const ConvStage& { return md.cdec[i]; }, src_of, plain);
-            group("conv_dec" + std::to_string(i + 1), h->fwd, [&] {
+            gather_launch("conv_dec" + std::to_string(i + 1) + "_im2col", h->plain.fwd, [&](Mod& md) -> const ConvStage& { return md.cdec[i]; }, src_of, plain);
+            group("conv_dec" + std::to_string(i + 1), h->plain.fwd, [&] {
                 for (Mod& md : h->mods) if (md.conv) {
                     if (md.cdec[i].impl) h->items.push_back(bd.conv_fwd_impl(md.cdec[i], src_of(md)));
                     else if (plain(md)) h->items.push_back(bd.conv_fwd(md.cdec[i]));
                 } });
         }
-        gather_launch("conv_out_im2col", h->fwd, [&](Mod& md) -> const ConvStage& { return md.cdec[4]; },
+        gather_launch("conv_out_im2col", h->plain.fwd, [&](Mod& md) -> const ConvStage& { return md.cdec[4]; },
                       [&](Mod& md) { return h->at<void>(md.cdec[3].Y.rm); }, [](const Mod& md) { return !md.cdec[3].dense_map; });
     }
-    group("fwd_out_loss", h->fwd, [&] {
+    group("fwd_out_loss", h->plain.fwd, [&] {
         for (int m = 0; m < h->M; ++m) h->items.push_back(bd.fwd_out(h->mods[m], m, true));
         if (!latent_alone) h->items.push_back(bd.latent());
     });
@@ -1630,7 +1634,7 @@ void build_training_plan(avae_handle* h) {
                 --a;
             }
         };
-        sink(h->fwd, &h->fwd_dec_first, nullptr);
+        sink(h->plain.fwd, nullptr, nullptr);
         sink(h->bwd, &h->bwd_split, nullptr);
         hoist(h->bwd, &h->bwd_split);
     }
@@ -1707,15 +1711,6 @@ void build_training_plan(avae_handle* h) {
             }
             wgrad_launches(set[0], h->wgrad_b[0], "wgrad_dec");
             wgrad_launches(set[1], h->wgrad_b[1], "wgrad_enc");
-            long wide = 0;
-            for (const WorkItem& w : wg) if (!is_narrow(w)) wide += (long)((w.M + 127) / 128) * ((w.N + 127) / 128);
-            // Measured and switched off (AVAE_OVERLAP=1 turns it on, results are bitwise the same): C2 95.8 vs 64.1 us/step, C4 0.616
-            // vs 0.587 ms -- in the single-replica graphs the fork / join edges cost far more than the ~8 us of Adam they hide (the
-            // data-parallel graph, where the side stream carries the RCCL kernels, does gain: 71 us with the extra collective work).
-            h->overlap = std::getenv("AVAE_OVERLAP") != nullptr;
-            // small nets: the weight-gradient launch is a fraction of a round of the chip and splits for free; big nets keep it whole
-            // (C4: 134 us as one launch, 111 + 119 as two) and only Adam is cut
-            h->ov_split_wgrad = wide < 192;
         }
         for (int i = 1; i <= 3; ++i) if (is_thin(i)) thin_launch("conv_dec" + std::to_string(i + 1) + "_wgrad_direct", h->wgrad, 2, i);
         {   // bias gradients of the adjoint-frame stages = column sums of their output gradient, first level
@@ -1830,7 +1825,7 @@ void build_training_plan(avae_handle* h) {
     // Cache (see k_grouped); forward and backward form one sequence (the step graph runs them back to back)
     if (!std::getenv("AVAE_NO_WARM")) {
         std::vector<Launch*> seq;
-        for (Launch& L : h->fwd) seq.push_back(&L);
+        for (Launch& L : h->plain.fwd) seq.push_back(&L);
         for (Launch& L : h->bwd) seq.push_back(&L);
         for (size_t i = 0; i < seq.size(); ++i) {
             Launch& L = *seq[i];
@@ -1997,56 +1992,79 @@ struct Timed {
     }
 };
 
-void run_launches(avae_handle* h, const std::vector<Launch>& ls, hipStream_t s, int stamp_base = -1) {
-    int k = 0;
-    static const char* dup = std::getenv("AVAE_DUP");      // diagnostics: run the named launch twice, the second one timed as "<name>_again"
-    for (const Launch& L0 : ls) {
-      for (int rep = 0; rep < ((dup && h->timing && L0.name == dup) ? 2 : 1); ++rep) {
-        Launch Lr;
-        if (rep) { Lr = L0; Lr.name += "_again"; }
-        const Launch& L = rep ? Lr : L0;
-        Timed t(h, s, L.name);
-        unsigned long long* stamps = nullptr;
-#ifdef AVAE_STAMPS
-        if (stamp_base >= 0) stamps = h->at<unsigned long long>(h->off_stamps);
-#endif
-        if (L.type == 1) launch_gather(h->cfg.compute_dtype, L.ga, L.blocks, s);
-        else if (L.type == 2) launch_col2im(h->cfg.compute_dtype, L.ca, L.blocks, s);
-        else if (L.type == 3) launch_reduce(L.ra, L.blocks, s);
-        else if (L.type == 4) launch_thin(h->cfg.compute_dtype, L.ta, L.blocks, s);
-        else if (L.type == 5) launch_colsum(L.ra, L.blocks, s);
-        else if (L.type == 6) launch_wadj(h->cfg.compute_dtype, L.wa, L.blocks, s);
-        else if (L.type == 7) launch_gperm(L.gp, L.blocks, s);
-        else if (L.type == 8) launch_rowsum(h->cfg.compute_dtype, L.rs, L.blocks, s);
-        else if (L.type == 9) launch_sums(L.ra, L.blocks, s);
-        else if (L.cfg == 13) launch_chain2(h->cfg.compute_dtype, L.args, L.grid_x, L.grid_y, L.lds, h->at<unsigned>(h->off_chain), h->at<unsigned>(h->off_chain) + kMaxMod * 64, s);
-        else if (L.cfg == 11) launch_small_head(h->cfg.compute_dtype, L.lean_act, L.args, L.grid_x, L.grid_y, L.lds, s, stamps, stamp_base + k);
-        else if (L.cfg == 10) launch_small_latb(h->cfg.compute_dtype, L.lean_act, L.args, L.grid_x, L.grid_y, L.lds, h->state(), s, stamps, stamp_base + k);
-        else if (L.cfg == 9) launch_small_loss(h->cfg.compute_dtype, L.args, L.grid_x, L.grid_y, L.lds, s, stamps, stamp_base + k);
-        else if (L.cfg == 7) launch_small(h->cfg.compute_dtype, L.args, L.grid_x, L.grid_y, L.lds, s, stamps, stamp_base + k);
-        else if (L.tn && L.cfg == 12) launch_small_tn(h->cfg.compute_dtype, L.targs, L.grid_x, L.grid_y, s, stamps, stamp_base + k);
-        else if (L.tn) launch_grouped_tn(h->cfg.compute_dtype, L.cfg, L.targs, L.grid_x, L.grid_y, L.lds, h->state(), s, stamps, stamp_base + k);
-        else launch_grouped(h->cfg.compute_dtype, L.cfg, L.args, L.grid_x, L.grid_y, L.lds, h->state(), s, stamps, stamp_base + k);
-        LAUNCH_OK(L.name);
-        if (h->debug_sync) {      // AVAE_DEBUG_SYNC=1: name the launch a fault belongs to
-            std::fprintf(stderr, "[avae] launch %s type=%d cfg=%d items=%d blocks=%d\n", L.name.c_str(), L.type, L.cfg, L.count, L.blocks);
-            for (int i = 0; i < L.args.n_items && L.type == 0; ++i)
-                std::fprintf(stderr, "        item kind=%d M=%d N=%d K=%d lda=%d ldb=%d tiles=%dx%d\n", L.args.items[i].kind, L.args.items[i].M,
-                             L.args.items[i].N, L.args.items[i].K, L.args.items[i].lda, L.args.items[i].ldb, L.args.items[i].tiles_m, L.args.items[i].tiles_n);
-            for (int i = 0; i < L.ga.n_seg && L.type == 1; ++i)
-                std::fprintf(stderr, "        gather B=%d IH=%d Cin=%d OH=%d k=%d so=%d d=%d pad=%d sb=%d sp=%d ones=%d ldp=%d tiles=%dx%d\n", L.ga.seg[i].g.B, L.ga.seg[i].g.IH,
-                             L.ga.seg[i].g.Cin, L.ga.seg[i].g.OH, L.ga.seg[i].g.k, L.ga.seg[i].g.so, L.ga.seg[i].g.d, L.ga.seg[i].g.pad, L.ga.seg[i].g.src_sb, L.ga.seg[i].g.src_sp,
-                             L.ga.seg[i].g.ones, L.ga.seg[i].ldp, L.ga.seg[i].tiles_r, L.ga.seg[i].tiles_c);
-            for (int i = 0; i < L.ca.n_seg && L.type == 2; ++i)
-                std::fprintf(stderr, "        col2im B=%d IH=%d Cin=%d OH=%d k=%d lddp=%d lda=%d g0=%p tiles=%dx%d\n", L.ca.seg[i].g.B, L.ca.seg[i].g.IH, L.ca.seg[i].g.Cin,
-                             L.ca.seg[i].g.OH, L.ca.seg[i].g.k, L.ca.seg[i].lddp, L.ca.seg[i].lda, (const void*)L.ca.seg[i].g0, L.ca.seg[i].tiles_r, L.ca.seg[i].tiles_c);
-            std::fflush(stderr);
-            HIP_OK(hipStreamSynchronize(s));
-        }
-      }
-        ++k;
+// The same launch reading staging set j instead of set 0: every pointer into set 0 moves by j * stage_bytes.
+Launch relocated(const avae_handle* h, const Launch& L0, int j) {
+    Launch L = L0;
+    const unsigned char* lo = h->ws + h->stage_lo;
+    const unsigned char* hi = lo + h->stage_bytes;
+    const size_t delta = (size_t)j * h->stage_bytes;
+    auto fix = [&](auto& ptr) {
+        const unsigned char* q = reinterpret_cast<const unsigned char*>(ptr);
+        if (q >= lo && q < hi) ptr = reinterpret_cast<std::remove_reference_t<decltype(ptr)>>(const_cast<unsigned char*>(q) + delta);
+    };
+    for (int i = 0; i < L.args.n_items && L.type == 0; ++i) {
+        WorkItem& w = L.args.items[i];
+        fix(w.A); fix(w.B); fix(w.out0); fix(w.out1); fix(w.out2); fix(w.aux0); fix(w.aux1); fix(w.aux2); fix(w.eps);
+        fix(w.tail_w); fix(w.tail_out); fix(w.tail_aux);
+        if (w.present) w.present += (size_t)j * h->pres_set;          // masked twin: presence set j (its own allocation)
+    }
+    for (int i = 0; i < L.targs.n_items && L.type == 0; ++i) { TnItem& t = L.targs.items[i]; fix(t.A); fix(t.B); fix(t.out); }
+    for (int i = 0; i < L.ga.n_seg && L.type == 1; ++i) fix(L.ga.seg[i].src);
+    return L;
+}
+
+void run_launch(avae_handle* h, const Launch& L, hipStream_t s, unsigned long long* stamps, int stamp) {
+    Timed t(h, s, L.name);
+    if (L.type == 1) launch_gather(h->cfg.compute_dtype, L.ga, L.blocks, s);
+    else if (L.type == 2) launch_col2im(h->cfg.compute_dtype, L.ca, L.blocks, s);
+    else if (L.type == 3) launch_reduce(L.ra, L.blocks, s);
+    else if (L.type == 4) launch_thin(h->cfg.compute_dtype, L.ta, L.blocks, s);
+    else if (L.type == 5) launch_colsum(L.ra, L.blocks, s);
+    else if (L.type == 6) launch_wadj(h->cfg.compute_dtype, L.wa, L.blocks, s);
+    else if (L.type == 7) launch_gperm(L.gp, L.blocks, s);
+    else if (L.type == 8) launch_rowsum(h->cfg.compute_dtype, L.rs, L.blocks, s);
+    else if (L.type == 9) launch_sums(L.ra, L.blocks, s);
+    else if (L.cfg == 13) launch_chain2(h->cfg.compute_dtype, L.args, L.grid_x, L.grid_y, L.lds, h->at<unsigned>(h->off_chain), h->at<unsigned>(h->off_chain) + kMaxMod * 64, s);
+    else if (L.cfg == 11) launch_small_head(h->cfg.compute_dtype, L.lean_act, L.args, L.grid_x, L.grid_y, L.lds, s, stamps, stamp);
+    else if (L.cfg == 10) launch_small_latb(h->cfg.compute_dtype, L.lean_act, L.args, L.grid_x, L.grid_y, L.lds, h->state(), s, stamps, stamp);
+    else if (L.cfg == 9) launch_small_loss(h->cfg.compute_dtype, L.args, L.grid_x, L.grid_y, L.lds, s, stamps, stamp);
+    else if (L.cfg == 7) launch_small(h->cfg.compute_dtype, L.args, L.grid_x, L.grid_y, L.lds, s, stamps, stamp);
+    else if (L.tn && L.cfg == 12) launch_small_tn(h->cfg.compute_dtype, L.targs, L.grid_x, L.grid_y, s, stamps, stamp);
+    else if (L.tn) launch_grouped_tn(h->cfg.compute_dtype, L.cfg, L.targs, L.grid_x, L.grid_y, L.lds, h->state(), s, stamps, stamp);
+    else launch_grouped(h->cfg.compute_dtype, L.cfg, L.args, L.grid_x, L.grid_y, L.lds, h->state(), s, stamps, stamp);
+    LAUNCH_OK(L.name);
+    if (h->debug_sync) {      // AVAE_DEBUG_SYNC=1: name the launch a fault belongs to
+        std::fprintf(stderr, "[avae] launch %s type=%d cfg=%d items=%d blocks=%d\n", L.name.c_str(), L.type, L.cfg, L.count, L.blocks);
+        for (int i = 0; i < L.args.n_items && L.type == 0; ++i)
+            std::fprintf(stderr, "        item kind=%d M=%d N=%d K=%d lda=%d ldb=%d tiles=%dx%d\n", L.args.items[i].kind, L.args.items[i].M,
+                         L.args.items[i].N, L.args.items[i].K, L.args.items[i].lda, L.args.items[i].ldb, L.args.items[i].tiles_m, L.args.items[i].tiles_n);
+        for (int i = 0; i < L.ga.n_seg && L.type == 1; ++i)
+            std::fprintf(stderr, "        gather B=%d IH=%d Cin=%d OH=%d k=%d so=%d d=%d pad=%d sb=%d sp=%d ones=%d ldp=%d tiles=%dx%d\n", L.ga.seg[i].g.B, L.ga.seg[i].g.IH,
+                         L.ga.seg[i].g.Cin, L.ga.seg[i].g.OH, L.ga.seg[i].g.k, L.ga.seg[i].g.so, L.ga.seg[i].g.d, L.ga.seg[i].g.pad, L.ga.seg[i].g.src_sb, L.ga.seg[i].g.src_sp,
+                         L.ga.seg[i].g.ones, L.ga.seg[i].ldp, L.ga.seg[i].tiles_r, L.ga.seg[i].tiles_c);
+        for (int i = 0; i < L.ca.n_seg && L.type == 2; ++i)
+            std::fprintf(stderr, "        col2im B=%d IH=%d Cin=%d OH=%d k=%d lddp=%d lda=%d g0=%p tiles=%dx%d\n", L.ca.seg[i].g.B, L.ca.seg[i].g.IH, L.ca.seg[i].g.Cin,
+                         L.ca.seg[i].g.OH, L.ca.seg[i].g.k, L.ca.seg[i].lddp, L.ca.seg[i].lda, (const void*)L.ca.seg[i].g0, L.ca.seg[i].tiles_r, L.ca.seg[i].tiles_c);
+        std::fflush(stderr);
+        HIP_OK(hipStreamSynchronize(s));
     }
 }
+
+// Launches [lo, hi) of ls on staging set j: set 0 runs ls itself, set j > 0 relocated copies.  stamp_base >= 0 (AVAE_STAMPS builds):
+// the launches write their clock stamps from slot stamp_base on.
+void run_set(avae_handle* h, const std::vector<Launch>& ls, size_t lo, size_t hi, int j, hipStream_t s, int stamp_base = -1) {
+    unsigned long long* stamps = nullptr;
+#ifdef AVAE_STAMPS
+    if (stamp_base >= 0) stamps = h->at<unsigned long long>(h->off_stamps);
+#endif
+    for (size_t i = lo; i < hi && i < ls.size(); ++i) {
+        const int k = stamp_base + (int)(i - lo);
+        if (j == 0) run_launch(h, ls[i], s, stamps, k);
+        else run_launch(h, relocated(h, ls[i], j), s, stamps, k);
+    }
+}
+
+void run_launches(avae_handle* h, const std::vector<Launch>& ls, hipStream_t s) { run_set(h, ls, 0, ls.size(), 0, s); }
 
 void run_adam(avae_handle* h, int mode, hipStream_t s, int bucket = -1) {
     AdamArgs a;
@@ -2099,8 +2117,8 @@ PrepArgs make_prep_batch(avae_handle* h, const float* const* x, const int32_t* x
 }
 
 void run_prep_batch(avae_handle* h, const float* const* x, const int32_t* x_ld, const float* eps, int rows,
-                    unsigned long long salt, hipStream_t s, const uint8_t* present = nullptr) {
-    const PrepArgs a = make_prep_batch(h, x, x_ld, eps, rows, salt, 1, present);
+                    unsigned long long salt, hipStream_t s, const uint8_t* present = nullptr, int n_steps = 1) {
+    const PrepArgs a = make_prep_batch(h, x, x_ld, eps, rows, salt, n_steps, present);
     Timed t(h, s, "prep");
     launch_prep(h->cfg.compute_dtype, a, s);
     LAUNCH_OK("prep");
@@ -2127,65 +2145,35 @@ void run_prep_single(avae_handle* h, const float* src, int src_ld, int rows, int
     LAUNCH_OK("prep");
 }
 
-// The same launch reading staging set j instead of set 0: every pointer into set 0 moves by j * stage_bytes.
-Launch relocated(const avae_handle* h, const Launch& L0, int j) {
-    if (j == 0) return L0;
-    Launch L = L0;
-    const unsigned char* lo = h->ws + h->stage_lo;
-    const unsigned char* hi = lo + h->stage_bytes;
-    const size_t delta = (size_t)j * h->stage_bytes;
-    auto fix = [&](auto& ptr) {
-        const unsigned char* q = reinterpret_cast<const unsigned char*>(ptr);
-        if (q >= lo && q < hi) ptr = reinterpret_cast<std::remove_reference_t<decltype(ptr)>>(const_cast<unsigned char*>(q) + delta);
-    };
-    for (int i = 0; i < L.args.n_items && L.type == 0; ++i) {
-        WorkItem& w = L.args.items[i];
-        fix(w.A); fix(w.B); fix(w.out0); fix(w.out1); fix(w.out2); fix(w.aux0); fix(w.aux1); fix(w.aux2); fix(w.eps);
-        fix(w.tail_w); fix(w.tail_out); fix(w.tail_aux);
-        if (w.present) w.present += (size_t)j * h->pres_set;          // masked twin: presence set j (its own allocation)
-    }
-    for (int i = 0; i < L.targs.n_items && L.type == 0; ++i) { TnItem& t = L.targs.items[i]; fix(t.A); fix(t.B); fix(t.out); }
-    for (int i = 0; i < L.ga.n_seg && L.type == 1; ++i) fix(L.ga.seg[i].src);
-    return L;
-}
-
-hipGraphExec_t capture(avae_handle* h, const std::function<void(hipStream_t)>& body) {
-    hipGraph_t g = nullptr;
-    hipGraphExec_t ge = nullptr;
-    HIP_OK(hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
-    try { body(h->cap_stream); } catch (...) { (void)hipStreamEndCapture(h->cap_stream, &g); if (g) (void)hipGraphDestroy(g); throw; }
-    HIP_OK(hipStreamEndCapture(h->cap_stream, &g));
-    HIP_OK(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
-    HIP_OK(hipGraphDestroy(g));
-    return ge;
-}
-
-// Same, for a graph whose first node is the input-staging kernel: keeps the template graph and that node so the
-// caller's pointers can be patched in before a replay (hipGraphExecKernelNodeSetParams).
-hipGraphExec_t capture_with_prep(avae_handle* h, const std::function<void(hipStream_t)>& body, hipGraph_t* graph_out,
-                                 hipGraphNode_t* prep_node) {
-    hipGraph_t g = nullptr;
-    hipGraphExec_t ge = nullptr;
+// Captures body (timing off); with_prep: a step graph whose one root node is the input-staging kernel -- its template and that node
+// are kept for patch_prep.
+StepGraph capture(avae_handle* h, const std::function<void(hipStream_t)>& body, bool with_prep = false) {
+    StepGraph sg;
+    const bool tsave = h->timing;
+    h->timing = false;
     HIP_OK(hipStreamBeginCapture(h->cap_stream, hipStreamCaptureModeThreadLocal));
     try { body(h->cap_stream); }
-    catch (...) { (void)hipStreamEndCapture(h->cap_stream, &g); if (g) (void)hipGraphDestroy(g); throw; }
-    HIP_OK(hipStreamEndCapture(h->cap_stream, &g));
+    catch (...) { (void)hipStreamEndCapture(h->cap_stream, &sg.graph); sg.release(); h->timing = tsave; throw; }
+    h->timing = tsave;
+    HIP_OK(hipStreamEndCapture(h->cap_stream, &sg.graph));
     try {
-        size_t n_root = 0;
-        HIP_OK(hipGraphGetRootNodes(g, nullptr, &n_root));
-        if (n_root != 1) throw Err("internal error: the captured step is not a chain");
-        HIP_OK(hipGraphGetRootNodes(g, prep_node, &n_root));
-        hipGraphNodeType ty;
-        HIP_OK(hipGraphNodeGetType(*prep_node, &ty));
-        if (ty != hipGraphNodeTypeKernel) throw Err("internal error: the captured step does not start with the staging kernel");
-        HIP_OK(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
-    } catch (...) { (void)hipGraphDestroy(g); throw; }
-    *graph_out = g;
-    return ge;
+        if (with_prep) {
+            size_t n_root = 0;
+            HIP_OK(hipGraphGetRootNodes(sg.graph, nullptr, &n_root));
+            if (n_root != 1) throw Err("internal error: the captured step is not a chain");
+            HIP_OK(hipGraphGetRootNodes(sg.graph, &sg.prep, &n_root));
+            hipGraphNodeType ty;
+            HIP_OK(hipGraphNodeGetType(sg.prep, &ty));
+            if (ty != hipGraphNodeTypeKernel) throw Err("internal error: the captured step does not start with the staging kernel");
+        }
+        HIP_OK(hipGraphInstantiate(&sg.exec, sg.graph, nullptr, nullptr, 0));
+        if (!with_prep) { HIP_OK(hipGraphDestroy(sg.graph)); sg.graph = nullptr; }
+    } catch (...) { sg.release(); throw; }
+    return sg;
 }
 
-// Points one captured staging node at the caller's batch (or run of n_steps consecutive batches).
-void patch_prep(avae_handle* h, hipGraphExec_t ge, hipGraphNode_t node, const float* const* x, const int32_t* x_ld, const float* eps,
+// Points a step graph's staging node at the caller's batch (or run of n_steps consecutive batches).
+void patch_prep(avae_handle* h, const StepGraph& sg, const float* const* x, const int32_t* x_ld, const float* eps,
                 int n_steps = 1, const uint8_t* present = nullptr) {
     PrepArgs a = make_prep_batch(h, x, x_ld, eps, h->B, 0x7261696eull, n_steps, present);
     void* kp[1] = {&a};
@@ -2194,7 +2182,7 @@ void patch_prep(avae_handle* h, hipGraphExec_t ge, hipGraphNode_t node, const fl
     np.func = const_cast<void*>(prep_kernel(h->cfg.compute_dtype, present != nullptr));
     np.gridDim = dim3((a.total_tiles + a.eps_blocks) * n_steps); np.blockDim = dim3(kThreads);
     np.sharedMemBytes = 0; np.kernelParams = kp; np.extra = nullptr;
-    HIP_OK(hipGraphExecKernelNodeSetParams(ge, node, &np));
+    HIP_OK(hipGraphExecKernelNodeSetParams(sg.exec, sg.prep, &np));
 }
 
 void fill_ones(avae_handle* h, const Act& a, hipStream_t s) {
@@ -2204,73 +2192,37 @@ void fill_ones(avae_handle* h, const Act& a, hipStream_t s) {
     LAUNCH_OK("fill");
 }
 
-// One step on staging set j (forward launches `fwd`: the plan's own, or its masked twin) inside a capture; `pending` = the side
-// stream still carries the previous step's decoder bucket.
-void step_body(avae_handle* h, const std::vector<Launch>& fwd, hipStream_t cs, int j, bool& pending, int stamp_base) {
-    auto run = [&](const std::vector<Launch>& ls, size_t lo, size_t hi, hipStream_t st, int sb) {
-        std::vector<Launch> moved;
-        for (size_t i = lo; i < hi && i < ls.size(); ++i) moved.push_back(relocated(h, ls[i], j));
-        run_launches(h, moved, st, sb);
-    };
-    if (!h->overlap) {
-        run(fwd, 0, fwd.size(), cs, stamp_base); run(h->bwd, 0, h->bwd.size(), cs, stamp_base < 0 ? -1 : stamp_base + (int)fwd.size());
-        if (!h->wgrad_adam.empty()) {       // the optimiser rides in the weight-gradient launch
-            run(h->wgrad_adam, 0, 1, cs, stamp_base < 0 ? -1 : stamp_base + (int)(fwd.size() + h->bwd.size()));
-            return;
-        }
-        run(h->wgrad, 0, h->wgrad.size(), cs, stamp_base < 0 ? -1 : stamp_base + (int)(fwd.size() + h->bwd.size()));
-        run_adam(h, 0, cs);
+// One step on staging set j (forward launches `fwd`: a plan's): forward, backward, then the weight gradients with Adam in their
+// epilogue, or followed by k_adam.
+void step_body(avae_handle* h, const std::vector<Launch>& fwd, hipStream_t s, int j, int stamp_base = -1) {
+    auto sb = [&](size_t k) { return stamp_base < 0 ? -1 : stamp_base + (int)k; };
+    run_set(h, fwd, 0, fwd.size(), j, s, stamp_base);
+    run_set(h, h->bwd, 0, h->bwd.size(), j, s, sb(fwd.size()));
+    if (!h->wgrad_adam.empty()) {       // the optimiser rides in the weight-gradient launch
+        run_set(h, h->wgrad_adam, 0, h->wgrad_adam.size(), j, s, sb(fwd.size() + h->bwd.size()));
         return;
     }
-    run(fwd, 0, (size_t)h->fwd_dec_first, cs, -1);
-    if (pending) { HIP_OK(hipStreamWaitEvent(cs, h->ev_side, 0)); pending = false; }      // decoder weights of the previous step are final
-    run(fwd, (size_t)h->fwd_dec_first, fwd.size(), cs, -1);
-    run(h->bwd, 0, (size_t)h->bwd_split, cs, -1);
-    if (h->ov_split_wgrad) {
-        HIP_OK(hipEventRecord(h->ev_fork, cs));
-        HIP_OK(hipStreamWaitEvent(h->side_stream, h->ev_fork, 0));
-        run(h->wgrad_b[0], 0, h->wgrad_b[0].size(), h->side_stream, -1);
-        run_adam(h, 0, h->side_stream, 0);
-        HIP_OK(hipEventRecord(h->ev_side, h->side_stream));
-        run(h->bwd, (size_t)h->bwd_split, h->bwd.size(), cs, -1);
-        run(h->wgrad_b[1], 0, h->wgrad_b[1].size(), cs, -1);
-        run_adam(h, 0, cs, 1);
-    } else {        // Adam of the encoder side first and alone (it is HBM-bound: two at once gain nothing), then the decoder side's beside
-                    // the next step's encoder forward (MFMA-bound launches with register-file room for Adam's small waves)
-        run(h->bwd, (size_t)h->bwd_split, h->bwd.size(), cs, -1);
-        run(h->wgrad, 0, h->wgrad.size(), cs, -1);
-        run_adam(h, 0, cs, 1);
-        HIP_OK(hipEventRecord(h->ev_fork, cs));
-        HIP_OK(hipStreamWaitEvent(h->side_stream, h->ev_fork, 0));
-        run_adam(h, 0, h->side_stream, 0);
-        HIP_OK(hipEventRecord(h->ev_side, h->side_stream));
-    }
-    pending = true;
+    run_set(h, h->wgrad, 0, h->wgrad.size(), j, s, sb(fwd.size() + h->bwd.size()));
+    run_adam(h, 0, s);
 }
 
-// The captured graphs of a step whose forward launches are `fwd`: one whole step (staging kernel first), runs of kMultiSizes[gi] steps
-// and the eval pass.  `present` non-null: the masked twin (masked staging; the placeholder is patched per replay like the inputs).
-void capture_step_graphs(avae_handle* h, const std::vector<Launch>& fwd, const uint8_t* present, hipGraphExec_t* full, hipGraph_t* full_graph,
-                         hipGraphNode_t* full_prep, hipGraphExec_t* multi, hipGraph_t* multi_graph, hipGraphNode_t* multi_prep, hipGraphExec_t* eval) {
+// The graphs of plan p.  `present` non-null: the masked plan (masked staging; the placeholder is patched per replay like the inputs).
+// On failure p keeps no graph.
+void capture_plan(avae_handle* h, StepPlan& p, const uint8_t* present) {
     std::vector<const float*> x0(h->M, h->at<float>(h->mods[0].X32));    // placeholders, patched per step
-    auto one_step = [&](hipStream_t cs) {
-        run_prep_batch(h, x0.data(), nullptr, nullptr, h->B, 0x7261696eull, cs, present);
-        bool pending = false;
-        step_body(h, fwd, cs, 0, pending, 0);
-        if (pending) HIP_OK(hipStreamWaitEvent(cs, h->ev_side, 0));
-    };
-    *full = capture_with_prep(h, one_step, full_graph, full_prep);
-    // avae_train_steps: kMultiSteps whole steps per replay (a replay boundary costs ~5 us of idle GPU on this stack),
-    // their batches staged by ONE launch into the kMultiSteps staging sets; step j's launches read set j
-    for (int gi = 0; gi < 2; ++gi) multi[gi] = capture_with_prep(h, [&](hipStream_t cs) {
-        const PrepArgs a = make_prep_batch(h, x0.data(), nullptr, nullptr, h->B, 0x7261696eull, kMultiSizes[gi], present);
-        launch_prep(h->cfg.compute_dtype, a, cs);
-        LAUNCH_OK("prep");
-        bool pending = false;
-        for (int j = 0; j < kMultiSizes[gi]; ++j) step_body(h, fwd, cs, j, pending, -1);
-        if (pending) HIP_OK(hipStreamWaitEvent(cs, h->ev_side, 0));        // join before the graph ends
-    }, &multi_graph[gi], &multi_prep[gi]);
-    *eval = capture(h, [&](hipStream_t cs) { run_launches(h, fwd, cs); run_launches(h, std::vector<Launch>{h->cost_only}, cs); });
+    try {
+        p.full = capture(h, [&](hipStream_t cs) {
+            run_prep_batch(h, x0.data(), nullptr, nullptr, h->B, 0x7261696eull, cs, present);
+            step_body(h, p.fwd, cs, 0, 0);
+        }, true);
+        // avae_train_steps: kMultiSizes[gi] whole steps per replay (a replay boundary costs ~5 us of idle GPU on this stack), their
+        // batches staged by ONE launch into as many staging sets; step j's launches read set j
+        for (int gi = 0; gi < 2; ++gi) p.multi[gi] = capture(h, [&](hipStream_t cs) {
+            run_prep_batch(h, x0.data(), nullptr, nullptr, h->B, 0x7261696eull, cs, present, kMultiSizes[gi]);
+            for (int j = 0; j < kMultiSizes[gi]; ++j) step_body(h, p.fwd, cs, j);
+        }, true);
+        p.eval = capture(h, [&](hipStream_t cs) { run_launches(h, p.fwd, cs); run_launch(h, h->cost_only, cs, nullptr, -1); });
+    } catch (...) { p.release(); throw; }
 }
 
 void init_device(avae_handle* h) {
@@ -2310,19 +2262,7 @@ void init_device(avae_handle* h) {
         h->inf_dec[m].dev_off = off; off += ((size_t)h->mods[m].L + 1) * sizeof(WorkItem);
     }
     HIP_OK(hipStreamSynchronize(s));
-    if (h->cfg.use_graph) {
-        const bool tsave = h->timing;
-        h->timing = false;
-        if (h->overlap && h->n_buckets == 2) {
-            HIP_OK(hipStreamCreateWithFlags(&h->side_stream, hipStreamNonBlocking));
-            HIP_OK(hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming));
-            HIP_OK(hipEventCreateWithFlags(&h->ev_side, hipEventDisableTiming));
-        } else {
-            h->overlap = false;
-        }
-        capture_step_graphs(h, h->fwd, nullptr, &h->g_full, &h->g_full_graph, &h->g_full_prep, h->g_multi, h->g_multi_graph, h->g_multi_prep, &h->g_eval);
-        h->timing = tsave;
-    }
+    if (h->cfg.use_graph) capture_plan(h, h->plain, nullptr);
 }
 
 void comm_check_error(avae_handle* h);
@@ -2530,19 +2470,15 @@ void dp_segment(avae_handle* h, int j, int bucket, hipStream_t s, bool direct = 
     if (bucket < 0 || bucket >= h->n_buckets) throw Err("data-parallel bucket out of range");
     if (j < 0 || j >= kMultiSteps) throw Err("staging set out of range");
     auto body = [&](hipStream_t cs) {
-        auto run = [&](const std::vector<Launch>& ls, size_t lo, size_t hi) {
-            std::vector<Launch> moved;
-            for (size_t i = lo; i < hi && i < ls.size(); ++i) moved.push_back(relocated(h, ls[i], j));
-            run_launches(h, moved, cs);
-        };
-        if (h->n_buckets == 1) { run(h->fwd, 0, h->fwd.size()); run(h->bwd, 0, h->bwd.size()); run(h->wgrad, 0, h->wgrad.size()); return; }
-        if (bucket == 0) { run(h->fwd, 0, h->fwd.size()); run(h->bwd, 0, (size_t)h->bwd_split); run(h->wgrad_b[0], 0, h->wgrad_b[0].size()); }
+        auto run = [&](const std::vector<Launch>& ls, size_t lo, size_t hi) { run_set(h, ls, lo, hi, j, cs); };
+        if (h->n_buckets == 1) { run(h->plain.fwd, 0, h->plain.fwd.size()); run(h->bwd, 0, h->bwd.size()); run(h->wgrad, 0, h->wgrad.size()); return; }
+        if (bucket == 0) { run(h->plain.fwd, 0, h->plain.fwd.size()); run(h->bwd, 0, (size_t)h->bwd_split); run(h->wgrad_b[0], 0, h->wgrad_b[0].size()); }
         else { run(h->bwd, (size_t)h->bwd_split, h->bwd.size()); run(h->wgrad_b[1], 0, h->wgrad_b[1].size()); }
     };
     if (h->cfg.use_graph && !h->timing && !direct) {
-        if (h->g_dp[bucket].empty()) h->g_dp[bucket].assign(kMultiSteps, nullptr);
-        if (!h->g_dp[bucket][j]) h->g_dp[bucket][j] = capture(h, body);
-        HIP_OK(hipGraphLaunch(h->g_dp[bucket][j], s));
+        if (h->g_dp[bucket].empty()) h->g_dp[bucket].resize(kMultiSteps);
+        if (!h->g_dp[bucket][j].exec) h->g_dp[bucket][j] = capture(h, body);
+        HIP_OK(hipGraphLaunch(h->g_dp[bucket][j].exec, s));
     } else {
         body(s);
     }
@@ -2674,12 +2610,8 @@ avae_handle::Serve& serve_plan(avae_handle* h, int bucket) {
     }
     a.blocks_per_mod = std::max(1, std::min(8, (bucket * h->nz + kThreads - 1) / kThreads));
     sv.in = a;                                                   // the per-call staging launch (ahead of the graph)
-    if (!(sv.fused_in && sv.lean_in)) {                          // serve_call replays a graph of the remaining launches
-        const bool tsave = h->timing;
-        h->timing = false;
-        sv.graph = capture(h, [&](hipStream_t cs) { run_launches(h, sv.launches, cs); });
-        h->timing = tsave;
-    }
+    if (!(sv.fused_in && sv.lean_in))                            // serve_call replays a graph of the remaining launches
+        sv.graph = capture(h, [&](hipStream_t cs) { run_launches(h, sv.launches, cs); }).exec;
     return sv;
 }
 
@@ -2758,6 +2690,190 @@ void check_row_inputs(const avae_handle* h, const char* what, const float* const
     }
 }
 
+// ---- masked steps: per-row modality presence (include/avae.h).  The masked twin of the step is built on first use: the forward
+// launches with WorkItem::present pointing at the staged presence bytes in every loss and latent item, and their graphs.
+void build_masked(avae_handle* h) {
+    if (!h->masked.fwd.empty()) return;
+    if (!h->pres_buf) {
+        h->pres_set = (size_t)h->B * h->M;         // = the staging kernel's set stride (PrepArgs::pres_dst: set j at j * rows * M)
+        HIP_OK(hipMalloc(reinterpret_cast<void**>(&h->pres_buf), h->pres_set * kMultiSteps));
+        HIP_OK(hipMemset(h->pres_buf, 0, h->pres_set * kMultiSteps));
+    }
+    std::vector<Launch> mf = h->plain.fwd;
+    int n_loss = 0, n_latent = 0;
+    for (Launch& L : mf) {
+        if (L.type != 0 || L.tn) continue;
+        bool gated = false;
+        for (int i = 0; i < L.args.n_items; ++i) {
+            WorkItem& w = L.args.items[i];
+            if (w.kind == K_FWD_OUT_LOSS) {
+                int m = 0;
+                while (m < h->M && w.aux0 != h->at<void>(h->mods[m].X32)) ++m;      // the item's modality: whose exact inputs it reads
+                if (m == h->M) throw Err("internal error: a loss item of no modality");
+                w.present = h->pres_buf + m; w.present_ld = h->M;
+                gated = true; ++n_loss;
+            } else if (w.kind == K_LATENT) {
+                w.present = h->pres_buf; w.present_ld = h->M;
+                gated = true; ++n_latent;
+            }
+        }
+        // the kernels that carry the presence gate: k_grouped's 4-wave tiles (configurations 0, 1, 3, 4, 5), its 8-wave loss tile (6)
+        // and the small nets' loss kernel (9).  Any other route of a loss or latent item would ignore the mask: refuse.
+        const int c = L.cfg;
+        if (gated && !(c == 0 || c == 1 || c == 3 || c == 4 || c == 5 || c == 6 || c == 9))
+            throw Err("masked training is not available on this plan: launch " + L.name + " (tile configuration " + std::to_string(c) +
+                      ") carries a loss or latent item on a kernel without the presence gate");
+    }
+    if (n_loss != h->M || n_latent != 1) throw Err("internal error: the masked twin found " + std::to_string(n_loss) + " loss and " +
+                                                   std::to_string(n_latent) + " latent items");
+    h->masked.fwd.swap(mf);
+    if (h->cfg.use_graph) {
+        try { capture_plan(h, h->masked, h->pres_buf); } catch (...) { h->masked.fwd.clear(); throw; }      // the next masked call builds it again
+    }
+}
+
+void check_masked_call(avae_handle* h, const char* what, const float* const* x_dev, const uint8_t* present_dev) {
+    if (h->cfg.world_size > 1 || h->cfg.use_comm != AVAE_COMM_NONE || h->comm_on)
+        throw Err(std::string(what) + ": masked steps run on one replica only (world_size 1, use_comm AVAE_COMM_NONE)");
+    if (!x_dev) throw Err(std::string(what) + ": null x_dev");
+    if (!present_dev) throw Err(std::string(what) + ": present_dev is null (unmasked calls go through the unmasked entry points)");
+}
+
+// One single-replica step of plan p (present: the masked plan's presence bytes).  With a library-owned collective (plain plan only:
+// masked calls refuse it) the step is staged and runs the bucketed pipeline instead.
+void train_one(avae_handle* h, StepPlan& p, const float* const* x_dev, const int32_t* x_ld, const uint8_t* present, const float* eps_dev,
+               hipStream_t s) {
+    if (h->comm_on) {
+        run_prep_batch(h, x_dev, x_ld, eps_dev, h->B, 0x7261696eull, s);
+        dp_step(h, 0, s);
+        return;
+    }
+    if (p.full.exec && !h->timing) {    // the whole step, staging kernel included, is one graph replay
+        patch_prep(h, p.full, x_dev, x_ld, eps_dev, 1, present);
+        HIP_OK(hipGraphLaunch(p.full.exec, s));
+        return;
+    }
+    run_prep_batch(h, x_dev, x_ld, eps_dev, h->B, 0x7261696eull, s, present);
+    step_body(h, p.fwd, s, 0);
+    if (h->timing) {      // floor of the measurement: a one-store kernel (partial slot 0 is rewritten every step anyway)
+        Timed t(h, s, "_null_kernel");
+        launch_fill(h->at<void>(h->off_partial), 4, 0u, 0, 1, 1, s);
+        LAUNCH_OK("_null_kernel");
+    }
+}
+
+// Batch i of a run of consecutive batches: rows [i*B, (i+1)*B) of every modality (a null one stays null), of the presence bytes
+// and of eps.
+struct BatchRun {
+    const avae_handle* h;
+    const float* const* x_dev;
+    const int32_t* x_ld;
+    const uint8_t* present;
+    const float* eps_dev;
+    const float* x[kMaxMod] = {};
+    const uint8_t* pres = nullptr;
+    const float* eps = nullptr;
+    void at(int i) {
+        for (int m = 0; m < h->M; ++m) {
+            const size_t ld = (x_ld && x_ld[m] > 0) ? (size_t)x_ld[m] : (size_t)h->mods[m].n_in;
+            x[m] = x_dev[m] ? x_dev[m] + (size_t)i * h->B * ld : nullptr;
+        }
+        pres = present ? present + (size_t)i * h->B * h->M : nullptr;
+        eps = eps_dev ? eps_dev + (size_t)i * h->B * h->nz : nullptr;
+    }
+};
+
+// Replays runs of kMultiSizes[gi] batches (16, then 4) through g[gi] while ready(gi); returns the first batch not replayed.
+template <typename Ready>
+int replay_runs(avae_handle* h, StepGraph (&g)[2], BatchRun& b, int n_steps, hipStream_t s, Ready&& ready) {
+    int i = 0;
+    for (int gi = 0; gi < 2; ++gi)
+        for (; i + kMultiSizes[gi] <= n_steps && ready(gi); i += kMultiSizes[gi]) {
+            b.at(i);
+            patch_prep(h, g[gi], b.x, b.x_ld, b.eps, kMultiSizes[gi], b.pres);
+            HIP_OK(hipGraphLaunch(g[gi].exec, s));
+        }
+    return i;
+}
+
+// n_steps consecutive batches through plan p (avae_train_steps, avae_train_steps_masked)
+void train_steps(avae_handle* h, StepPlan& p, int n_steps, const float* const* x_dev, const int32_t* x_ld, const uint8_t* present,
+                 const float* eps_dev, float* cost_host, hipStream_t s) {
+    BatchRun b{h, x_dev, x_ld, present, eps_dev};
+    int i = 0;
+    if (h->comm_on) {               // data parallel: batches staged kMultiSteps at a time, then backward -> all-reduce -> Adam per bucket and step
+        // Runs of 16 (then 4) steps as ONE captured graph -- staging kernel, segments, ncclAllReduce on the comm stream (it
+        // joins the capture through the events), Adam per bucket -- so that the host is out of the loop exactly as in the
+        // single-replica path.  Captured on first use; if RCCL refuses capture on this stack the host steps the same pipeline.
+        if (h->cfg.use_graph && !h->timing)
+            i = replay_runs(h, h->g_dpm, b, n_steps, s, [&](int gi) {
+                if (h->dp_graph_failed) return false;
+                if (h->g_dpm[gi].exec) return true;
+                std::vector<const float*> x0(h->M, h->at<float>(h->mods[0].X32));
+                try {
+                    h->g_dpm[gi] = capture(h, [&](hipStream_t cs) {
+                        run_prep_batch(h, x0.data(), nullptr, nullptr, h->B, 0x7261696eull, cs, nullptr, kMultiSizes[gi]);
+                        for (int j = 0; j < kMultiSizes[gi]; ++j) dp_step(h, j, cs, true);
+                    }, true);
+                } catch (const std::exception& e) {
+                    h->dp_graph_failed = true;
+                    (void)hipGetLastError();
+                    if (std::getenv("AVAE_DEBUG_DP")) std::fprintf(stderr, "[avae] data-parallel graph capture failed (%s): host-stepped pipeline\n", e.what());
+                    return false;
+                }
+                return true;
+            });
+        for (; i < n_steps; i += kMultiSteps) {
+            const int n = std::min(kMultiSteps, n_steps - i);
+            b.at(i);
+            run_prep_batch(h, b.x, x_ld, b.eps, h->B, 0x7261696eull, s, nullptr, n);
+            for (int j = 0; j < n; ++j) dp_step(h, j, s);
+        }
+    } else {
+        if (!h->timing) i = replay_runs(h, p.multi, b, n_steps, s, [&](int gi) { return p.multi[gi].exec != nullptr; });
+        for (; i < n_steps; ++i) {
+            b.at(i);
+            train_one(h, p, b.x, x_ld, b.pres, b.eps, s);
+        }
+    }
+    fetch_cost(h, cost_host, true, s);
+}
+
+// Forward + cost of one batch through plan p, no update (avae_eval_cost, avae_eval_cost_masked).
+void eval_cost(avae_handle* h, StepPlan& p, const float* const* x_dev, const int32_t* x_ld, const uint8_t* present, const float* eps_dev,
+               float* cost_host, hipStream_t s) {
+    run_prep_batch(h, x_dev, x_ld, eps_dev, h->B, 0x6576616cull /*eval*/ | (unsigned long long)next_draw(h, eps_dev) << 34, s, present);
+    if (p.eval.exec && !h->timing) HIP_OK(hipGraphLaunch(p.eval.exec, s));
+    else { run_launches(h, p.fwd, s); run_launch(h, h->cost_only, s, nullptr, -1); }
+    fetch_cost(h, cost_host, false, s);
+}
+
+// Frees whatever the handle holds (a partly created one included), then the handle.
+void destroy_handle(avae_handle* h) {
+    int prev_dev = -1;
+    if (hipGetDevice(&prev_dev) != hipSuccess) prev_dev = -1;
+    (void)hipSetDevice(h->cfg.device);
+    (void)hipDeviceSynchronize();
+    h->plain.release();
+    h->masked.release();
+    for (StepGraph& g : h->g_dpm) g.release();
+    for (std::vector<StepGraph>& v : h->g_dp) for (StepGraph& g : v) g.release();
+    for (avae_handle::Serve& sv : h->serve) if (sv.graph) (void)hipGraphExecDestroy(sv.graph);
+    if (h->iw_buf) (void)hipFree(h->iw_buf);
+    if (h->pres_buf) (void)hipFree(h->pres_buf);
+    if (h->ev_switch) (void)hipEventDestroy(h->ev_switch);
+    if (h->comm) { try { (void)Rccl::get().destroy(h->comm); } catch (...) {} }
+    for (int r = 0; r < kMaxWorld; ++r) if (h->ipc_opened[r] && h->ipc_peer[r]) (void)hipIpcCloseMemHandle(h->ipc_peer[r]);
+    if (h->ipc_block) (void)hipFree(h->ipc_block);
+    for (int b = 0; b < 2; ++b) { if (h->ev_grad[b]) (void)hipEventDestroy(h->ev_grad[b]); if (h->ev_red[b]) (void)hipEventDestroy(h->ev_red[b]); }
+    if (h->comm_stream) (void)hipStreamDestroy(h->comm_stream);
+    for (TimingRec& r : h->trecs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
+    if (h->cap_stream) (void)hipStreamDestroy(h->cap_stream);
+    if (h->own_ws && h->ws) (void)hipFree(h->ws);
+    if (prev_dev >= 0 && prev_dev != h->cfg.device) (void)hipSetDevice(prev_dev);
+    delete h;
+}
+
 }  // namespace
 
 // ============================================================================= C ABI
@@ -2810,47 +2926,13 @@ int avae_create(const avae_config* cfg, avae_handle** out) {
         return 0;
     } catch (const std::exception& e) {
         g_create_error = e.what();
-        if (h) {
-            if (h->comm) { try { (void)Rccl::get().destroy(h->comm); } catch (...) {} }
-            if (h->comm_stream) (void)hipStreamDestroy(h->comm_stream);
-            if (h->ipc_block) (void)hipFree(h->ipc_block);
-            if (h->own_ws && h->ws) (void)hipFree(h->ws);
-            if (h->cap_stream) (void)hipStreamDestroy(h->cap_stream);
-            delete h;
-        }
+        if (h) destroy_handle(h);
         return 2;
     }
 }
 
 void avae_destroy(avae_handle* h) {
-    if (!h) return;
-    int prev_dev = -1;
-    if (hipGetDevice(&prev_dev) != hipSuccess) prev_dev = -1;
-    (void)hipSetDevice(h->cfg.device);
-    (void)hipDeviceSynchronize();
-    for (hipGraphExec_t g : {h->g_full, h->g_multi[0], h->g_multi[1], h->g_eval}) if (g) (void)hipGraphExecDestroy(g);
-    for (int b = 0; b < 2; ++b) for (hipGraphExec_t g : h->g_dp[b]) if (g) (void)hipGraphExecDestroy(g);
-    for (avae_handle::Serve& sv : h->serve) if (sv.graph) (void)hipGraphExecDestroy(sv.graph);
-    if (h->iw_buf) (void)hipFree(h->iw_buf);
-    for (hipGraphExec_t g : {h->gm_full, h->gm_multi[0], h->gm_multi[1], h->gm_eval}) if (g) (void)hipGraphExecDestroy(g);
-    for (hipGraph_t g : {h->gm_full_graph, h->gm_multi_graph[0], h->gm_multi_graph[1]}) if (g) (void)hipGraphDestroy(g);
-    if (h->pres_buf) (void)hipFree(h->pres_buf);
-    if (h->ev_switch) (void)hipEventDestroy(h->ev_switch);
-    if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-    if (h->ev_side) (void)hipEventDestroy(h->ev_side);
-    if (h->side_stream) (void)hipStreamDestroy(h->side_stream);
-    for (int gi = 0; gi < 2; ++gi) { if (h->g_dpm[gi]) (void)hipGraphExecDestroy(h->g_dpm[gi]); if (h->g_dpm_graph[gi]) (void)hipGraphDestroy(h->g_dpm_graph[gi]); }
-    if (h->comm) { try { (void)Rccl::get().destroy(h->comm); } catch (...) {} }
-    for (int r = 0; r < kMaxWorld; ++r) if (h->ipc_opened[r] && h->ipc_peer[r]) (void)hipIpcCloseMemHandle(h->ipc_peer[r]);
-    if (h->ipc_block) (void)hipFree(h->ipc_block);
-    for (int b = 0; b < 2; ++b) { if (h->ev_grad[b]) (void)hipEventDestroy(h->ev_grad[b]); if (h->ev_red[b]) (void)hipEventDestroy(h->ev_red[b]); }
-    if (h->comm_stream) (void)hipStreamDestroy(h->comm_stream);
-    for (hipGraph_t g : {h->g_full_graph, h->g_multi_graph[0], h->g_multi_graph[1]}) if (g) (void)hipGraphDestroy(g);
-    for (TimingRec& r : h->trecs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
-    if (h->cap_stream) (void)hipStreamDestroy(h->cap_stream);
-    if (h->own_ws && h->ws) (void)hipFree(h->ws);
-    if (prev_dev >= 0 && prev_dev != h->cfg.device) (void)hipSetDevice(prev_dev);
-    delete h;
+    if (h) destroy_handle(h);
 }
 
 const char* avae_last_error(const avae_handle* h) { return h ? h->err.c_str() : g_create_error.c_str(); }
@@ -2912,34 +2994,10 @@ int avae_stage_batches(avae_handle* h, int32_t n_steps, const float* const* x_de
     });
 }
 
-// one single-replica step
-void train_one(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, const float* eps_dev, hipStream_t s) {
-    if (h->comm_on) {                   // library-owned collective: stage, then the bucketed pipeline
-        const PrepArgs a = make_prep_batch(h, x_dev, x_ld, eps_dev, h->B, 0x7261696eull, 1);
-        { Timed t(h, s, "prep"); launch_prep(h->cfg.compute_dtype, a, s); LAUNCH_OK("prep"); }
-        dp_step(h, 0, s);
-        return;
-    }
-    if (h->g_full && !h->timing) {      // the whole step, staging kernel included, is one graph replay
-        patch_prep(h, h->g_full, h->g_full_prep, x_dev, x_ld, eps_dev);
-        HIP_OK(hipGraphLaunch(h->g_full, s));
-        return;
-    }
-    run_prep_batch(h, x_dev, x_ld, eps_dev, h->B, 0x7261696eull, s);
-    run_launches(h, h->fwd, s); run_launches(h, h->bwd, s);
-    if (!h->wgrad_adam.empty()) run_launches(h, h->wgrad_adam, s);
-    else { run_launches(h, h->wgrad, s); run_adam(h, 0, s); }
-    if (h->timing) {      // floor of the measurement: a one-store kernel (partial slot 0 is rewritten every step anyway)
-        Timed t(h, s, "_null_kernel");
-        launch_fill(h->at<void>(h->off_partial), 4, 0u, 0, 1, 1, s);
-        LAUNCH_OK("_null_kernel");
-    }
-}
-
 int avae_train_step(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, const float* eps_dev, float* cost_host, void* stream) {
     return guarded(h, [&] {
         hipStream_t s = on_stream(h, stream);
-        train_one(h, x_dev, x_ld, eps_dev, s);
+        train_one(h, h->plain, x_dev, x_ld, nullptr, eps_dev, s);
         fetch_cost(h, cost_host, true, s);
     });
 }
@@ -2948,133 +3006,8 @@ int avae_train_steps(avae_handle* h, int32_t n_steps, const float* const* x_dev,
                      float* cost_host, void* stream) {
     return guarded(h, [&] {
         if (n_steps < 1) throw Err("avae_train_steps: n_steps must be >= 1");
-        hipStream_t s = on_stream(h, stream);
-        std::vector<const float*> x(h->M);
-        auto batch = [&](int i) {       // rows [i*B, (i+1)*B) of every modality and of eps
-            for (int m = 0; m < h->M; ++m) {
-                const size_t ld = (x_ld && x_ld[m] > 0) ? (size_t)x_ld[m] : (size_t)h->mods[m].n_in;
-                x[m] = x_dev[m] + (size_t)i * h->B * ld;
-            }
-            return eps_dev ? eps_dev + (size_t)i * h->B * h->nz : nullptr;
-        };
-        int i = 0;
-        if (h->comm_on) {               // data parallel: batches staged kMultiSteps at a time, then backward -> all-reduce -> Adam per bucket and step
-            // Runs of 16 (then 4) steps as ONE captured graph -- staging kernel, segments, ncclAllReduce on the comm stream (it
-            // joins the capture through the events), Adam per bucket -- so that the host is out of the loop exactly as in the
-            // single-replica path.  If RCCL refuses capture on this stack the host steps the same pipeline.
-            for (int gi = 0; gi < 2 && h->cfg.use_graph && !h->timing && !h->dp_graph_failed; ++gi)
-                for (; i + kMultiSizes[gi] <= n_steps; i += kMultiSizes[gi]) {
-                    if (!h->g_dpm[gi]) {
-                        std::vector<const float*> x0(h->M, h->at<float>(h->mods[0].X32));
-                        try {
-                            h->g_dpm[gi] = capture_with_prep(h, [&](hipStream_t cs) {
-                                const PrepArgs a = make_prep_batch(h, x0.data(), nullptr, nullptr, h->B, 0x7261696eull, kMultiSizes[gi]);
-                                launch_prep(h->cfg.compute_dtype, a, cs);
-                                LAUNCH_OK("prep");
-                                for (int j = 0; j < kMultiSizes[gi]; ++j) dp_step(h, j, cs, true);
-                            }, &h->g_dpm_graph[gi], &h->g_dpm_prep[gi]);
-                        } catch (const std::exception& e) {
-                            h->dp_graph_failed = true;
-                            h->g_dpm[gi] = nullptr;
-                            (void)hipGetLastError();
-                            if (std::getenv("AVAE_DEBUG_DP")) std::fprintf(stderr, "[avae] data-parallel graph capture failed (%s): host-stepped pipeline\n", e.what());
-                            break;
-                        }
-                    }
-                    const float* e = batch(i);
-                    patch_prep(h, h->g_dpm[gi], h->g_dpm_prep[gi], x.data(), x_ld, e, kMultiSizes[gi]);
-                    HIP_OK(hipGraphLaunch(h->g_dpm[gi], s));
-                }
-            for (; i < n_steps; i += kMultiSteps) {
-                const int n = std::min(kMultiSteps, n_steps - i);
-                const float* e = batch(i);
-                const PrepArgs a = make_prep_batch(h, x.data(), x_ld, e, h->B, 0x7261696eull, n);
-                { Timed t(h, s, "prep"); launch_prep(h->cfg.compute_dtype, a, s); LAUNCH_OK("prep"); }
-                for (int j = 0; j < n; ++j) dp_step(h, j, s);
-            }
-            fetch_cost(h, cost_host, true, s);
-            return;
-        }
-        for (int gi = 0; gi < 2 && !h->timing; ++gi)
-            for (; h->g_multi[gi] && i + kMultiSizes[gi] <= n_steps; i += kMultiSizes[gi]) {
-                const float* e = batch(i);
-                patch_prep(h, h->g_multi[gi], h->g_multi_prep[gi], x.data(), x_ld, e, kMultiSizes[gi]);
-                HIP_OK(hipGraphLaunch(h->g_multi[gi], s));
-            }
-        for (; i < n_steps; ++i) {
-            const float* e = batch(i);
-            train_one(h, x.data(), x_ld, e, s);
-        }
-        fetch_cost(h, cost_host, true, s);
+        train_steps(h, h->plain, n_steps, x_dev, x_ld, nullptr, eps_dev, cost_host, on_stream(h, stream));
     });
-}
-
-// ---- masked steps: per-row modality presence (include/avae.h).  The masked twin of the step is built on first use: the forward
-// launches with WorkItem::present pointing at the staged presence bytes in every loss and latent item, and their graphs.
-void build_masked(avae_handle* h) {
-    if (h->masked_built) return;
-    if (!h->pres_buf) {
-        h->pres_set = (size_t)h->B * h->M;         // = the staging kernel's set stride (PrepArgs::pres_dst: set j at j * rows * M)
-        HIP_OK(hipMalloc(reinterpret_cast<void**>(&h->pres_buf), h->pres_set * kMultiSteps));
-        HIP_OK(hipMemset(h->pres_buf, 0, h->pres_set * kMultiSteps));
-    }
-    std::vector<Launch> mf = h->fwd;
-    int n_loss = 0, n_latent = 0;
-    for (Launch& L : mf) {
-        if (L.type != 0 || L.tn) continue;
-        bool gated = false;
-        for (int i = 0; i < L.args.n_items; ++i) {
-            WorkItem& w = L.args.items[i];
-            if (w.kind == K_FWD_OUT_LOSS) {
-                int m = 0;
-                while (m < h->M && w.aux0 != h->at<void>(h->mods[m].X32)) ++m;      // the item's modality: whose exact inputs it reads
-                if (m == h->M) throw Err("internal error: a loss item of no modality");
-                w.present = h->pres_buf + m; w.present_ld = h->M;
-                gated = true; ++n_loss;
-            } else if (w.kind == K_LATENT) {
-                w.present = h->pres_buf; w.present_ld = h->M;
-                gated = true; ++n_latent;
-            }
-        }
-        // the kernels that carry the presence gate: k_grouped's 4-wave tiles (configurations 0, 1, 3, 4, 5), its 8-wave loss tile (6)
-        // and the small nets' loss kernel (9).  Any other route of a loss or latent item would ignore the mask: refuse.
-        const int c = L.cfg;
-        if (gated && !(c == 0 || c == 1 || c == 3 || c == 4 || c == 5 || c == 6 || c == 9))
-            throw Err("masked training is not available on this plan: launch " + L.name + " (tile configuration " + std::to_string(c) +
-                      ") carries a loss or latent item on a kernel without the presence gate");
-    }
-    if (n_loss != h->M || n_latent != 1) throw Err("internal error: the masked twin found " + std::to_string(n_loss) + " loss and " +
-                                                   std::to_string(n_latent) + " latent items");
-    h->mfwd.swap(mf);
-    if (h->cfg.use_graph) {
-        const bool tsave = h->timing;
-        h->timing = false;
-        try {
-            capture_step_graphs(h, h->mfwd, h->pres_buf, &h->gm_full, &h->gm_full_graph, &h->gm_full_prep, h->gm_multi, h->gm_multi_graph,
-                                h->gm_multi_prep, &h->gm_eval);
-        } catch (...) { h->timing = tsave; throw; }
-        h->timing = tsave;
-    }
-    h->masked_built = true;
-}
-
-void check_masked_call(avae_handle* h, const char* what, const float* const* x_dev, const uint8_t* present_dev) {
-    if (h->cfg.world_size > 1 || h->cfg.use_comm != AVAE_COMM_NONE || h->comm_on)
-        throw Err(std::string(what) + ": masked steps run on one replica only (world_size 1, use_comm AVAE_COMM_NONE)");
-    if (!x_dev) throw Err(std::string(what) + ": null x_dev");
-    if (!present_dev) throw Err(std::string(what) + ": present_dev is null (unmasked calls go through the unmasked entry points)");
-}
-
-void train_one_masked(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, const uint8_t* present, const float* eps_dev, hipStream_t s) {
-    if (h->gm_full && !h->timing) {
-        patch_prep(h, h->gm_full, h->gm_full_prep, x_dev, x_ld, eps_dev, 1, present);
-        HIP_OK(hipGraphLaunch(h->gm_full, s));
-        return;
-    }
-    run_prep_batch(h, x_dev, x_ld, eps_dev, h->B, 0x7261696eull, s, present);
-    run_launches(h, h->mfwd, s); run_launches(h, h->bwd, s);
-    if (!h->wgrad_adam.empty()) run_launches(h, h->wgrad_adam, s);
-    else { run_launches(h, h->wgrad, s); run_adam(h, 0, s); }
 }
 
 int avae_train_steps_masked(avae_handle* h, int32_t n_steps, const float* const* x_dev, const int32_t* x_ld, const uint8_t* present_dev,
@@ -3083,29 +3016,7 @@ int avae_train_steps_masked(avae_handle* h, int32_t n_steps, const float* const*
         check_masked_call(h, "avae_train_steps_masked", x_dev, present_dev);
         if (n_steps < 1) throw Err("avae_train_steps_masked: n_steps must be >= 1");
         build_masked(h);
-        hipStream_t s = on_stream(h, stream);
-        std::vector<const float*> x(h->M);
-        const uint8_t* pres = nullptr;
-        auto batch = [&](int i) {       // rows [i*B, (i+1)*B) of every modality, of the presence bytes and of eps
-            for (int m = 0; m < h->M; ++m) {
-                const size_t ld = (x_ld && x_ld[m] > 0) ? (size_t)x_ld[m] : (size_t)h->mods[m].n_in;
-                x[m] = x_dev[m] ? x_dev[m] + (size_t)i * h->B * ld : nullptr;
-            }
-            pres = present_dev + (size_t)i * h->B * h->M;
-            return eps_dev ? eps_dev + (size_t)i * h->B * h->nz : nullptr;
-        };
-        int i = 0;
-        for (int gi = 0; gi < 2 && !h->timing; ++gi)
-            for (; h->gm_multi[gi] && i + kMultiSizes[gi] <= n_steps; i += kMultiSizes[gi]) {
-                const float* e = batch(i);
-                patch_prep(h, h->gm_multi[gi], h->gm_multi_prep[gi], x.data(), x_ld, e, kMultiSizes[gi], pres);
-                HIP_OK(hipGraphLaunch(h->gm_multi[gi], s));
-            }
-        for (; i < n_steps; ++i) {
-            const float* e = batch(i);
-            train_one_masked(h, x.data(), x_ld, pres, e, s);
-        }
-        fetch_cost(h, cost_host, true, s);
+        train_steps(h, h->masked, n_steps, x_dev, x_ld, present_dev, eps_dev, cost_host, on_stream(h, stream));
     });
 }
 
@@ -3114,11 +3025,7 @@ int avae_eval_cost_masked(avae_handle* h, const float* const* x_dev, const int32
     return guarded(h, [&] {
         check_masked_call(h, "avae_eval_cost_masked", x_dev, present_dev);
         build_masked(h);
-        hipStream_t s = on_stream(h, stream);
-        run_prep_batch(h, x_dev, x_ld, eps_dev, h->B, 0x6576616cull /*eval*/ | (unsigned long long)next_draw(h, eps_dev) << 34, s, present_dev);
-        if (h->gm_eval && !h->timing) HIP_OK(hipGraphLaunch(h->gm_eval, s));
-        else { run_launches(h, h->mfwd, s); run_launches(h, std::vector<Launch>{h->cost_only}, s); }
-        fetch_cost(h, cost_host, false, s);
+        eval_cost(h, h->masked, x_dev, x_ld, present_dev, eps_dev, cost_host, on_stream(h, stream));
     });
 }
 
@@ -3223,13 +3130,7 @@ int avae_cost_history(avae_handle* h, int32_t n, float* host_dst, int64_t* last_
 }
 
 int avae_eval_cost(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, const float* eps_dev, float* cost_host, void* stream) {
-    return guarded(h, [&] {
-        hipStream_t s = on_stream(h, stream);
-        run_prep_batch(h, x_dev, x_ld, eps_dev, h->B, 0x6576616cull /*eval*/ | (unsigned long long)next_draw(h, eps_dev) << 34, s);
-        if (h->g_eval && !h->timing) HIP_OK(hipGraphLaunch(h->g_eval, s));
-        else { run_launches(h, h->fwd, s); run_launches(h, std::vector<Launch>{h->cost_only}, s); }
-        fetch_cost(h, cost_host, false, s);
-    });
+    return guarded(h, [&] { eval_cost(h, h->plain, x_dev, x_ld, nullptr, eps_dev, cost_host, on_stream(h, stream)); });
 }
 
 int avae_encode(avae_handle* h, int32_t m, const float* x_dev, int32_t x_ld, int32_t rows, float* mu_dev, float* logvar_dev, void* stream) {

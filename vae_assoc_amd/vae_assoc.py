@@ -343,43 +343,36 @@ class AssocVariationalAutoEncoder(object):
         lds = (C.c_int32 * M)(*[t.stride(0) if t.shape[0] > 1 else t.shape[1] for t in ts])
         return ts, ts[0].shape[0], was_np, ptrs, lds
 
-    def _batch_args(self, X, eps, n_steps=1):
-        assert len(X) == len(self.network_architectures)
-        rows = self.batch_size * n_steps
-        # the reference's eps has static shape (batch_size, n_z): every path through z needs exactly batch_size rows (vae_assoc.py:90)
-        ts, _, _, ptrs, lds = self._rows_args(X, rows, "batch_size" + (" x n_steps" if n_steps > 1 else ""))
-        e = None
-        if eps is not None:
-            e, _ = self._dev(eps, self.n_z)
-            if e.shape[0] != rows:
-                raise ValueError("eps must be [batch_size%s, n_z]" % (" x n_steps" if n_steps > 1 else ""))
-            e = e.contiguous()
-        return ts, ptrs, lds, e
-
-    def _masked_args(self, X, eps, present, n_steps=1):
-        """Arguments of the masked entry points: ``present`` [batch_size * n_steps, M] (bool or integer, array or tensor, any device;
-        nonzero = observed) -> uint8 device tensor; ``X[m] = None`` -> a NULL source (modality m absent on every row)."""
-        world = self._sync.world_size if self._sync is not None else 1
-        if world > 1:
-            raise RuntimeError("present= (partially paired batches) runs on one replica; this model is data parallel over %d ranks" % world)
+    def _batch_args(self, X, eps, n_steps=1, present=None):
+        """Arguments of the training / eval entry points -> (device tensors, ptrs, lds, eps tensor or None, presence or None).
+        ``present`` (the masked entry points): [batch_size * n_steps, M] (bool or integer, array or tensor, any device; nonzero =
+        observed) -> uint8 device tensor, and ``X[m] = None`` -> a NULL source (modality m absent on every row)."""
         M = len(self.network_architectures)
-        if len(X) != M:
-            raise ValueError("expected a list of %d modalities, got %d" % (M, len(X)))
         rows = self.batch_size * n_steps
-        p = present if torch.is_tensor(present) else torch.as_tensor(np.asarray(present))
-        if p.dim() != 2 or p.shape[0] != rows or p.shape[1] != M:
-            raise ValueError("present must be [batch_size%s, %d] = [%d, %d], got %s"
-                             % (" x n_steps" if n_steps > 1 else "", M, rows, M, tuple(p.shape)))
-        p = (p != 0).to(device=self.device, dtype=torch.uint8).contiguous()
+        steps = " x n_steps" if n_steps > 1 else ""
+        p = None
+        if present is None:
+            assert len(X) == M
+        else:
+            world = self._sync.world_size if self._sync is not None else 1
+            if world > 1:
+                raise RuntimeError("present= (partially paired batches) runs on one replica; this model is data parallel over %d ranks" % world)
+            if len(X) != M:
+                raise ValueError("expected a list of %d modalities, got %d" % (M, len(X)))
+            p = present if torch.is_tensor(present) else torch.as_tensor(np.asarray(present))
+            if p.dim() != 2 or p.shape[0] != rows or p.shape[1] != M:
+                raise ValueError("present must be [batch_size%s, %d] = [%d, %d], got %s" % (steps, M, rows, M, tuple(p.shape)))
+            p = (p != 0).to(device=self.device, dtype=torch.uint8).contiguous()
+        # the reference's eps has static shape (batch_size, n_z): every path through z needs exactly batch_size rows (vae_assoc.py:90)
         ts, ptrs, lds = [], [], []
-        for m, (x, na) in enumerate(zip(X, self.network_architectures)):
-            if x is None:
+        for x, na in zip(X, self.network_architectures):
+            if x is None and p is not None:
                 ptrs.append(None)
                 lds.append(0)
                 continue
             t, _ = self._dev(x, int(na["n_input"]))
             if t.shape[0] != rows:
-                raise ValueError("expected %d rows (batch_size%s), got %d" % (rows, " x n_steps" if n_steps > 1 else "", t.shape[0]))
+                raise ValueError("expected %d rows (batch_size%s), got %d" % (rows, steps, t.shape[0]))
             ts.append(t)
             ptrs.append(t.data_ptr())
             lds.append(t.stride(0) if t.shape[0] > 1 else t.shape[1])
@@ -387,12 +380,12 @@ class AssocVariationalAutoEncoder(object):
         if eps is not None:
             e, _ = self._dev(eps, self.n_z)
             if e.shape[0] != rows:
-                raise ValueError("eps must be [batch_size%s, n_z]" % (" x n_steps" if n_steps > 1 else ""))
+                raise ValueError("eps must be [batch_size%s, n_z]" % steps)
             e = e.contiguous()
         return ts, (C.c_void_p * M)(*ptrs), (C.c_int32 * M)(*lds), e, p
 
     def _train_masked(self, X, n_steps, eps, present, return_cost):
-        ts, ptrs, lds, e, p = self._masked_args(X, eps, present, n_steps)
+        ts, ptrs, lds, e, p = self._batch_args(X, eps, n_steps, present)
         cost = C.c_float(0.0)
         _capi.check(self._h, self._L.avae_train_steps_masked(self._h, n_steps, ptrs, lds, p.data_ptr(),
                                                              e.data_ptr() if e is not None else None,
@@ -452,7 +445,7 @@ class AssocVariationalAutoEncoder(object):
 
     # bucketed seam (parallel.dp_train_step_bucketed): stage -> per bucket backward / all-reduce -> per bucket Adam
     def _stage(self, X, eps=None, n_steps=1):
-        ts, ptrs, lds, e = self._batch_args(X, eps, n_steps)
+        ts, ptrs, lds, e, _ = self._batch_args(X, eps, n_steps)
         _capi.check(self._h, self._L.avae_stage_batches(self._h, n_steps, ptrs, lds, e.data_ptr() if e is not None else None,
                                                         self._stream()), "avae_stage_batches")
         self._staged_j = 0
@@ -480,7 +473,7 @@ class AssocVariationalAutoEncoder(object):
             # host-owned collective (torch.distributed) over the library's buckets
             cost = dp_train_step_bucketed(self, self._sync, self._buckets, X, eps)
             return cost if return_cost else None
-        ts, ptrs, lds, e = self._batch_args(X, eps)      # (library-owned collective: avae_train_step runs the bucketed pipeline itself)
+        ts, ptrs, lds, e, _ = self._batch_args(X, eps)      # (library-owned collective: avae_train_step runs the bucketed pipeline itself)
         cost = C.c_float(0.0)
         _capi.check(self._h, self._L.avae_train_step(self._h, ptrs, lds, e.data_ptr() if e is not None else None,
                                                      C.byref(cost) if return_cost else None, self._stream()),
@@ -498,7 +491,7 @@ class AssocVariationalAutoEncoder(object):
             return self._train_masked(X, n_steps, eps, present, return_cost)
         if self._sync is not None and self._sync.world_size > 1 and not self._comm_lib:
             # host-owned collective: the batches are staged 16 at a time, every step runs the bucketed schedule
-            ts, ptrs, lds, e = self._batch_args(X, eps, n_steps)
+            ts, ptrs, lds, e, _ = self._batch_args(X, eps, n_steps)
             B, cost, st = self.batch_size, None, self._stream()
             for i0 in range(0, n_steps, 16):
                 n = min(16, n_steps - i0)
@@ -516,7 +509,7 @@ class AssocVariationalAutoEncoder(object):
                             w.wait()
                         cost = self._apply_bucket(b, return_cost and i0 + j == n_steps - 1 and b == len(self._buckets) - 1)
             return cost
-        ts, ptrs, lds, e = self._batch_args(X, eps, n_steps)
+        ts, ptrs, lds, e, _ = self._batch_args(X, eps, n_steps)
         cost = C.c_float(0.0)
         _capi.check(self._h, self._L.avae_train_steps(self._h, n_steps, ptrs, lds, e.data_ptr() if e is not None else None,
                                                       C.byref(cost) if return_cost else None, self._stream()),
@@ -527,12 +520,12 @@ class AssocVariationalAutoEncoder(object):
         """reference vae_assoc.py:388-391 (forward + loss with a fresh eps, no update).  ``present``: [batch_size, M] presence
         flags, as in ``partial_fit`` (one replica)."""
         if present is not None:
-            ts, ptrs, lds, e, p = self._masked_args(X, eps, present)
+            ts, ptrs, lds, e, p = self._batch_args(X, eps, present=present)
             cost = C.c_float(0.0)
             _capi.check(self._h, self._L.avae_eval_cost_masked(self._h, ptrs, lds, p.data_ptr(), e.data_ptr() if e is not None else None,
                                                                C.byref(cost), self._stream()), "avae_eval_cost_masked")
             return cost.value
-        ts, ptrs, lds, e = self._batch_args(X, eps)
+        ts, ptrs, lds, e, _ = self._batch_args(X, eps)
         cost = C.c_float(0.0)
         _capi.check(self._h, self._L.avae_eval_cost(self._h, ptrs, lds, e.data_ptr() if e is not None else None,
                                                     C.byref(cost), self._stream()), "avae_eval_cost")
