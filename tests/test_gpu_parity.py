@@ -14,6 +14,7 @@ import torch
 
 from conftest import GOLDEN, hip_relu_masks, make_arch, synth_batch, shadow_err
 from oracle import vae_assoc_oracle as O
+from plan_dump import step_plan
 
 pytestmark = pytest.mark.gpu
 
@@ -58,8 +59,57 @@ def build_pair(V, archs, binary, weights, lam, act, B, dtype, lr=1e-3, p0=None, 
     return model, ref
 
 
+U32 = 2.0 ** -23            # fp32 spacing at 1: one ulp of x is at most U32 * |x|
+TINY32 = 2.0 ** -126        # smallest normal fp32: a subnormal intermediate flushed to zero moves a result by less
+
+
+def adam_lr_t(lr, t):
+    """lr_t as the step's K_COST item forms it (avae_kernels.hip::cost_item): f32 lr and betas widened to double, rounded to f32"""
+    b1, b2 = float(np.float32(O.ADAM_BETA1)), float(np.float32(O.ADAM_BETA2))
+    return float(np.float32(float(np.float32(lr)) * np.sqrt(1.0 - b2 ** t) / (1.0 - b1 ** t)))
+
+
+def check_adam_step(before, after, g, lr):
+    """One optimiser step of the HIP path, decoupled from gradient conditioning: `before` / `after` = (theta, m, v, step) read
+    from the handle around the step, `g` = the step's gradient.  The kernel's expression (avae_kernels.hip::adam_update) is
+    evaluated in fp64 with its fp32 constants, omb = f32(1 - f32(beta)), and the bounds are the kernel's own roundings:
+      m_t = m + (g - m) omb1: two roundings, 1/2 ulp of |g - m| <= 2a times omb1 = 0.1 and 1/2 ulp of |m_t| <= a, a = max(|m|, |g|):
+          < 0.6 ulp of a                                                                                -> bound U32 * a
+      v_t = v + (g^2 - v) omb2: 1/2 ulp of |g^2 - v| <= b times 0.001 and 1/2 ulp of v_t <= b, b = max(v, g^2)  -> bound U32 * b
+      theta_t = theta - (m_t lr_t) / (sqrt(v_t) + eps) from HIP's own m_t, v_t: four roundings of 1/2 ulp in the update (product,
+          root, sum of non-negative terms, quotient) and 1/2 ulp of |theta_t| in the subtraction  -> U32 * (|theta_t| + 3 |update|)
+    plus TINY32 each (flushed subnormal intermediates).  The step counter must advance by one."""
+    th0, m0, v0, t0 = before
+    th1, m1, v1, t1 = after
+    assert t1 == t0 + 1, "step counter %d after a step from %d" % (t1, t0)
+    f32 = np.float32
+    omb1, omb2 = float(f32(1.0) - f32(O.ADAM_BETA1)), float(f32(1.0) - f32(O.ADAM_BETA2))
+    eps = float(f32(O.ADAM_EPS))
+    lr_t = adam_lr_t(lr, t1)
+    g, m0, v0, th0 = (np.asarray(a, np.float64) for a in (g, m0, v0, th0))
+    m1d, v1d = m1.astype(np.float64), v1.astype(np.float64)
+    m_want = m0 + (g - m0) * omb1
+    err = np.abs(m1d - m_want) - (U32 * np.maximum(np.abs(m0), np.abs(g)) + TINY32)
+    assert err.max() <= 0, "Adam m at step %d: worst element %d (m %r g %r -> %r, want %r)" % (
+        t1, int(err.argmax()), m0[err.argmax()], g[err.argmax()], m1d[err.argmax()], m_want[err.argmax()])
+    v_want = v0 + (g * g - v0) * omb2
+    err = np.abs(v1d - v_want) - (U32 * np.maximum(v0, g * g) + TINY32)
+    assert err.max() <= 0, "Adam v at step %d: worst element %d (v %r g %r -> %r, want %r)" % (
+        t1, int(err.argmax()), v0[err.argmax()], g[err.argmax()], v1d[err.argmax()], v_want[err.argmax()])
+    upd = m1d * lr_t / (np.sqrt(v1d) + eps)
+    th_want = th0 - upd
+    err = np.abs(th1.astype(np.float64) - th_want) - (U32 * (np.abs(th_want) + 3.0 * np.abs(upd)) + TINY32)
+    assert err.max() <= 0, "Adam theta at step %d: worst element %d (theta %r update %r -> %r, want %r)" % (
+        t1, int(err.argmax()), th0[err.argmax()], upd[err.argmax()], th1[err.argmax()], th_want[err.argmax()])
+
+
+def opt_snapshot(model):
+    m, v, t = model.get_opt_state()
+    return model.get_params(), m, v, t
+
+
 def check_step_parity(V, archs, binary, weights, lam, act, B, dtype, steps=3, seed=5, ref_config=False, drift_tol=None,
-                      adam_rel=False, **kw):
+                      adam_rel=False, grad_every_step=False, relu_masks=False, **kw):
     """HIP path vs oracle on the same weights / inputs / eps.
 
     fp32 operands: against the fp64 oracle at the fp32 tolerances of the module docstring.
@@ -68,7 +118,12 @@ def check_step_parity(V, archs, binary, weights, lam, act, B, dtype, steps=3, se
     kernels; (2) against the plain fp64 oracle at the north_star tolerances (cost 1e-3 relative on the
     reference configurations, mu/lv 2e-2 absolute) -- this is the measured price of bf16 operands.
     adam_rel: the Adam arithmetic bound 6e-8 is taken relative to max(1, |theta|) per element (fp32 resolves only ~5e-7 at
-    |theta| = 8-16, e.g. the head biases of posteriors far from the prior)."""
+    |theta| = 8-16, e.g. the head biases of posteriors far from the prior).
+    Every step: the optimiser arithmetic from HIP's own theta / m / v / step before it and gradient after it (check_adam_step).
+    grad_every_step: also HIP's gradient of every later step against the like-for-like oracle evaluated at HIP's weights of
+    that step (the free-running oracle drifts away from them) -- the gradients that run on shadows the optimiser wrote.
+    relu_masks (relu): the oracle takes the relu decisions of HIP's pass of the same step (hip_relu_masks), so a pre-activation
+    within rounding of the kink cannot fall on different sides in the two runs."""
     fp32 = dtype == "fp32"
     lr = 1e-3
     rng = np.random.default_rng(seed + 100)
@@ -97,9 +152,21 @@ def check_step_parity(V, archs, binary, weights, lam, act, B, dtype, steps=3, se
     # -- training steps: cost of the pre-update forward pass, gradients, Adam
     for s in range(steps):
         c_ref = ref.partial_fit(X, eps[s]) if not fp32 else None
-        c_emu, g_emu, fw = emu.cost_and_grads(X, eps[s])
-        emu.apply_gradients(g_emu)
+        before = opt_snapshot(model)
         c = model.partial_fit(X, eps[s])
+        g = model.get_grads()
+        masks = hip_relu_masks(model, archs) if relu_masks else None
+        check_adam_step(before, opt_snapshot(model), g, lr)
+        assert before[3] == s, "step counter %d before step %d" % (before[3], s)
+        c_emu, g_emu, fw = emu.cost_and_grads(X, eps[s], masks=masks)
+        emu.apply_gradients(g_emu)
+        if s > 0 and grad_every_step:
+            at = O.OracleAssocVAE(archs, binary, act, weights, lam, lr, B, params_flat=before[0].astype(np.float64),
+                                  quant=None if fp32 else "bf16")
+            c_at, g_at, _ = at.cost_and_grads(X, eps[s], masks=masks)
+            assert abs(c - c_at) <= c_tol0 * abs(c_at), "step %d cost %.6f vs oracle at HIP's weights %.6f" % (s, c, c_at)
+            bad = [(n, e) for n, e in per_tensor_err(archs, g, g_at) if e > g_tol]
+            assert not bad, "step %d gradient vs oracle at HIP's weights (rel to tensor max): %s" % (s, bad)
         # later steps start from weights that differ in the Adam-ill-conditioned elements (|g| ~ 1e-8)
         tol = c_tol0 if s == 0 else (2e-5 if fp32 else 3e-4)
         assert abs(c - c_emu) <= tol * abs(c_emu), "step %d cost %.6f vs like-for-like oracle %.6f (rel %.2e)" % (
@@ -109,7 +176,6 @@ def check_step_parity(V, archs, binary, weights, lam, act, B, dtype, steps=3, se
             assert abs(c - c_ref) <= ctol * abs(c_ref), "step %d bf16 cost %.6f vs fp64 oracle %.6f (rel %.2e)" % (
                 s, c, c_ref, abs(c - c_ref) / abs(c_ref))
         if s == 0:
-            g = model.get_grads()
             errs = per_tensor_err(archs, g, g_emu)
             bad = [(n, e) for n, e in errs if e > g_tol]
             assert not bad, "gradient mismatch (rel to tensor max): %s" % bad
@@ -407,7 +473,7 @@ def test_conv_deconv_branch(V, dtype):
     modality: the commented-out configuration of vae_assoc_ujichar_img_jnt.py:72-80 (depths 16/64, 64/16)."""
     img = dict(make_arch("image", 784, 16, 64, 20), hidden_conv=True, n_hidden_gener_1=64, n_hidden_gener_2=16)
     jnt = make_arch("joint", 147, 200, 200, 20)
-    model, emu, X, eps = check_step_parity(V, [img, jnt], [True, False], [50.0, 1.0], 8.0, "relu", 24, dtype, steps=2)
+    model, emu, X, eps = check_step_parity(V, [img, jnt], [True, False], [50.0, 1.0], 8.0, "relu", 24, dtype, steps=2, grad_every_step=True)
     # inference surface of the conv modality, any row count
     rng = np.random.default_rng(9)
     for rows in (1, 24, 31):
@@ -468,14 +534,14 @@ def test_conv_branch_with_wide_latents(V, monkeypatch, nz, policy):
         monkeypatch.setenv("AVAE_IMPL_POLICY", policy)
     archs = [dict(make_arch("image", 784, 16, 64, nz), hidden_conv=True, n_hidden_gener_1=64, n_hidden_gener_2=16),
              make_arch("joint", 147, 60, 40, nz)]
-    check_step_parity(V, archs, [True, False], [3.0, 1.0], 0.3, "relu", 17, "fp32", steps=2, drift_tol=2.5e-3)
+    check_step_parity(V, archs, [True, False], [3.0, 1.0], 0.3, "relu", 17, "fp32", steps=2, drift_tol=2.5e-3, grad_every_step=True)
 
 
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
 def test_conv_only_model(V, dtype):
     """A single conv modality (no MLP modality at all, no association term)."""
     img = dict(make_arch("image", 784, 8, 12, 6), hidden_conv=True, n_hidden_gener_1=12, n_hidden_gener_2=6)
-    check_step_parity(V, [img], True, 1.0, 1.0, "relu", 10, dtype, steps=2)
+    check_step_parity(V, [img], True, 1.0, 1.0, "relu", 10, dtype, steps=2, grad_every_step=True)
 
 
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
@@ -486,24 +552,57 @@ def test_two_conv_modalities_mixed_paths(V, dtype):
     not multiples of 4 on one stage (scalar gather paths) and multiples on the others."""
     a = dict(make_arch("img_a", 784, 8, 24, 5), hidden_conv=True, n_hidden_gener_1=144, n_hidden_gener_2=8)
     b = dict(make_arch("img_b", 784, 4, 16, 5), hidden_conv=True, n_hidden_gener_1=20, n_hidden_gener_2=12)
-    check_step_parity(V, [a, b], [True, True], [2.0, 1.0], 0.5, "relu", 12, dtype, steps=2)
+    check_step_parity(V, [a, b], [True, True], [2.0, 1.0], 0.5, "relu", 12, dtype, steps=2, grad_every_step=True)
+
+
+def _plan(V, monkeypatch, capfd, archs, binary, act, B, dtype, seed=5):
+    rng = np.random.default_rng(seed)
+    X = synth_batch(rng, B, [a["n_input"] for a in archs], binary)
+    eps = rng.standard_normal((B, archs[0]["n_z"])).astype(np.float32)
+    return step_plan(V, monkeypatch, capfd, archs, B, dtype, X, eps, binary=binary, transfer_fct=act, seed=seed)
 
 
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
-def test_large_tile_path(V, dtype):
-    """Wide layers and a large batch select the 128x128 tile configuration.  softplus, not relu:
-    with 2048 x 384 hidden units some pre-activation lands within fp32 rounding of the relu kink and
-    flips its derivative between the fp32 kernel and the fp64 oracle, which is not a kernel error."""
+def test_large_tile_path(V, monkeypatch, capfd, dtype):
+    """Wide-ish layers at a large batch.  softplus, not relu: with 2048 x 384 hidden units some pre-activation lands within fp32
+    rounding of the relu kink and flips its derivative between the fp32 kernel and the fp64 oracle, which is not a kernel error.
+    The plan dump shows that this shape does NOT reach the 128x128 tiles it was written for (its largest launch, fwd_out_loss,
+    has 144 of the 192 tiles cfg 1 needs): every GEMM launch runs on 64x64 or smaller tiles.  test_large_tile_path_128 is the
+    shape that does."""
     archs = [make_arch("a", 784, 0, 0, 32, n_hidden=[512, 384]), make_arch("b", 147, 0, 0, 32, n_hidden=[384, 256])]
-    check_step_parity(V, archs, [True, False], [5.0, 1.0], 0.5, "softplus", 2048, dtype, steps=2)
+    plan = _plan(V, monkeypatch, capfd, archs, [True, False], "softplus", 2048, dtype)
+    assert all(c in (0, 3, 5, 7, 9, 10, 11, 12) for _n, c, _i in plan), [(n, c) for n, c, _i in plan]
+    check_step_parity(V, archs, [True, False], [5.0, 1.0], 0.5, "softplus", 2048, dtype, steps=2, grad_every_step=True)
 
 
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
-def test_wide_tile_path(V, dtype):
+def test_large_tile_path_128(V, monkeypatch, capfd, dtype):
+    """The 128x128 tiles (cfg 1) on NT launches (forward into and dgrad of the 768-wide layers: 2 x 16 x 6 = 192 tiles of 128x128,
+    96 of 256x128) at
+    a batch that is not a multiple of any tile height (2000 = 15 x 128 + 80) and fan-ins that are not multiples of the K tile
+    (785, 148): the plan is asserted, then parity at every step."""
+    archs = [make_arch("a", 784, 0, 0, 32, n_hidden=[768, 384]), make_arch("b", 147, 0, 0, 32, n_hidden=[768, 256])]
+    B = 2000
+    plan = _plan(V, monkeypatch, capfd, archs, [True, False], "softplus", B, dtype)
+    cfg, items = [(c, it) for n, c, it in plan if n == "fwd_enc1"][0]
+    assert cfg == 1 and [(k, M, N) for k, M, N, _K in items] == [(0, B, 768), (0, B, 768)], (cfg, items)
+    dgrad = [it for n, c, its in plan if c == 1 for it in its if it[0] == 4]      # K_DGRAD_HIDDEN into the 768-wide layers
+    assert dgrad and all((M, N) == (B, 768) for _k, M, N, _K in dgrad), [(n, c) for n, c, _i in plan]
+    check_step_parity(V, archs, [True, False], [5.0, 1.0], 0.5, "softplus", B, dtype, steps=2, grad_every_step=True)
+
+
+@pytest.mark.parametrize("dtype", ["fp32", "bf16"])
+def test_wide_tile_path(V, monkeypatch, capfd, dtype):
     """Launches with >= 192 tiles of 256x128 run the 8-wave kernel (hidden-layer forward / dgrad and plain weight
-    gradients of the big nets, unfused Adam): parity at that size, softplus for the reason given above."""
+    gradients of the big nets, unfused Adam): parity at that size, softplus for the reason given above.  The plan dump must show
+    the 8-wave NT/TN tiles (cfg 2) and the 8-wave loss tiles (cfg 6)."""
     archs = [make_arch("a", 784, 0, 0, 16, n_hidden=[1024, 768]), make_arch("b", 147, 0, 0, 16, n_hidden=[1024, 768])]
-    check_step_parity(V, archs, [True, False], [5.0, 1.0], 0.5, "softplus", 4096, dtype, steps=1)
+    plan = _plan(V, monkeypatch, capfd, archs, [True, False], "softplus", 4096, dtype)
+    cf = {n: c for n, c, _i in plan}
+    wide_wgrad = [c for n, c, _i in plan if n.startswith("wgrad")][0]          # (wide products first: "wgrad" or "wgrad1")
+    assert cf["fwd_enc1"] == 2 and cf["fwd_out_loss"] == 6 and wide_wgrad == 2, cf
+    assert 12 not in cf.values(), cf
+    check_step_parity(V, archs, [True, False], [5.0, 1.0], 0.5, "softplus", 4096, dtype, steps=1, grad_every_step=True)
 
 
 @pytest.mark.parametrize("env", [{"AVAE_TN_G": "2"}, {"AVAE_TN_G": "8"}, {"AVAE_NO_TN_BALANCE": "1"}, {"AVAE_NO_BIAS_MFMA": "1"},
