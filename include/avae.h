@@ -253,6 +253,35 @@ int avae_score(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, i
 int avae_loglik(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, int32_t rows, int32_t n_samples,
                 const float* eps_dev, float* out_dev, void* stream);
 
+/* ---- gradient latent refinement for partially observed rows (the reference searches z around the encoder's guess by calling
+ * generate 10-50 times per iteration from the host, baxter_vae_assoc_writer.py:259-304,466-559; this is the deterministic,
+ * gradient-based counterpart, the whole loop on the device).  Per row n independently, z of n_z floats:
+ *   J_n(z) = sum_m w_m recon_obs_m(x[n,m], dec_m(z), o[n,m]) + prior_weight * 0.5 * |z|^2
+ * dec_m = the decoder of modality m as avae_decode runs it (z read in the compute dtype, fp32 output); o[n,m] an element mask
+ * [n_input_m], nonzero = observed; recon_obs_m = avae_score's per-row reconstruction arithmetic summed over the observed elements
+ * only (Bernoulli -sum o [x log(1e-3+p) + (1-x) log(1e-3+1-p)], Gaussian 0.5 sum o (x - x_hat)^2); w_m the modality weights.
+ * Unobserved elements are selected away, not multiplied by 0: they are never read, NaN / Inf there changes nothing.
+ * n_iters updates of per-row, per-element Adam on z in fp32, zero moments at the start, g = dJ_n/dz, t = 1..n_iters:
+ *   m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2;  z -= lr (m / (1-b1^t)) / (sqrt(v / (1-b2^t)) + adam_eps)
+ * (textbook Adam with bias correction; b1, b2, adam_eps = the config's beta1, beta2, adam_eps).  n_iters = 0 evaluates only.
+ *   x_dev[m], x_ld[m]  as avae_score; x_dev[m] == NULL: modality m is unobserved on every row (never read through)
+ *   obs_dev            NULL, or obs_dev[m] = device uint8 [rows][n_input_m], dense; NULL: every element of x_dev[m] is observed
+ *   z0_dev             device [rows][n_z] fp32, dense: the start
+ *   z_dev              device [rows][n_z]: the final z
+ *   obj_dev            optional [n_iters+1][rows]: J at z0 and after every update
+ *   grad_dev           optional [rows][n_z]: dJ/dz at z0
+ *   xhat_dev           optional; xhat_dev[m] optional [rows][n_input_m]: decoder m at the final z (NULL modalities included)
+ * rows == 0 is a no-op.  Any row count, worked in chunks of at most batch_size rows on the step's decoder buffers; per chunk one
+ * staging launch, then n_iters + 1 passes [decoders forward, masked output gradient + recon_obs, decoder input gradients from the
+ * W shadows, update] replayed from captured graphs with no host synchronise in between; the scratch (z, moments, dJ_m/dz) is
+ * allocated by the first call and freed by avae_destroy, avae_workspace_bytes is unchanged.  No atomics: the same inputs give
+ * bitwise the same outputs.  As avae_score, the call changes nothing the next training step reads (no weight gradient is formed,
+ * the gradient buffer is not written); on a data-parallel replica it covers the local rows, with no collective.  MLP decoders
+ * only: a model with a conv modality is refused; so are n_iters < 0 and a call whose x_dev[m] are all NULL. */
+int avae_complete(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, const uint8_t* const* obs_dev,
+                  const float* z0_dev, int32_t rows, int32_t n_iters, float lr, float prior_weight,
+                  float* z_dev, float* obj_dev, float* grad_dev, float* const* xhat_dev, void* stream);
+
 /* save_model / restore_model (vae_assoc.py:427-463): own flat file (config echo + params + Adam
  * slots + step); TF .ckpt files cannot be read offline. */
 int avae_save(avae_handle* h, const char* path);

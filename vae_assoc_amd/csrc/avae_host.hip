@@ -1,6 +1,7 @@
 // Host side of libavae: memory plan, work-item tables, hipGraph capture and the C ABI
 // (include/avae.h).  No per-step allocation: everything is carved once from one workspace.
 #include "avae_device.h"
+#include "avae_complete.h"
 #include "../../include/avae.h"
 
 #include <dlfcn.h>
@@ -261,6 +262,13 @@ struct avae_handle {
     StepPlan plain, masked;
     unsigned char* pres_buf = nullptr;
     size_t pres_set = 0;                    // bytes per staging set
+
+    // avae_complete: the launches of one refinement pass (decoders forward, then their input-gradient chain from the training plan's
+    // item builders on the same buffers), captured as runs of kCompleteSizes[i] passes; the kernels' arguments; the scratch behind
+    // them.  Built and allocated by the first call.
+    struct Complete { bool built = false; std::vector<WorkItem> items; std::vector<Launch> fwd, bwd; CompleteArgs args{};
+                      StepGraph g[3]; unsigned char* buf = nullptr; };
+    Complete cmpl;
 
     // Calls on one handle share its activation buffers and serving slot: a call on a different stream than the previous one is
     // ordered behind that one's work (an event recorded on the old stream when the switch is seen: nothing per call otherwise).
@@ -2690,6 +2698,99 @@ void check_row_inputs(const avae_handle* h, const char* what, const float* const
     }
 }
 
+// ---- gradient latent refinement (avae_complete; include/avae.h, avae_complete.h).  One pass over a chunk of <= batch_size rows:
+//   cmpl_dec<k>      the decoders' hidden layers from the current z (grouped over the modalities, as fwd_dec<k>)
+//   cmpl_out         output layers, p / x_hat as fp32 into out32 (the inference kind: no loss epilogue)
+//   k_complete_out   element-masked output gradient into dO + recon_obs per (row, modality)
+//   cmpl_bwd_out, cmpl_bwd_dec<k>   the training plan's decoder dgrad items (bwd_out, bwd_dec<k>), built again here from the same
+//                    builders: the training launches also carry the latent item's [dmu | dlv] conversion and the cost item
+//                    (step counter, lr_t), which must not run
+//   cmpl_bwd_dz      dz_m = dD1 . V1^T as plain fp32 (the conv branch's K_DGRAD_F32 kind) into the scratch
+//   k_complete_update   sum over modalities + prior, objective, Adam on z, new decoder inputs
+// = 2 L + 4 launches for L hidden layers (8 for the reference's two).  The plan's rows are batch_size, whatever the chunk holds:
+// the GEMM items are the training step's shapes, and rows beyond the chunk's are zeros that nobody reads.  No weight gradient,
+// no write to the gradient buffer, theta or the optimiser state.
+constexpr int kCompleteSizes[3] = {16, 4, 1};   // passes per captured graph
+
+void complete_pass(avae_handle* h, avae_handle::Complete& cp, hipStream_t s) {
+    run_launches(h, cp.fwd, s);
+    {
+        Timed t(h, s, "complete_out");
+        launch_complete_out(h->cfg.compute_dtype, cp.args, s); LAUNCH_OK("complete_out");
+    }
+    run_launches(h, cp.bwd, s);
+    {
+        Timed t(h, s, "complete_update");
+        launch_complete_update(h->cfg.compute_dtype, cp.args, s); LAUNCH_OK("complete_update");
+    }
+}
+
+avae_handle::Complete& complete_plan(avae_handle* h) {
+    avae_handle::Complete& cp = h->cmpl;
+    if (cp.built) return cp;
+    const int B = h->B, M = h->M, nz = h->nz, lddz = (int)rup(nz, 4);
+    Bump b;
+    const size_t off_call = b.take(sizeof(CompleteCall));
+    const size_t off_z = b.take((size_t)B * nz * 4), off_m = b.take((size_t)B * nz * 4), off_v = b.take((size_t)B * nz * 4);
+    const size_t off_recon = b.take((size_t)B * M * 4);
+    size_t off_dz[kMaxMod] = {0, 0, 0, 0};
+    for (int m = 0; m < M; ++m) off_dz[m] = b.take(rup(B, kRowAlign) * (size_t)lddz * 4);
+    if (!cp.buf) {
+        HIP_OK(hipMalloc(reinterpret_cast<void**>(&cp.buf), b.off));
+        HIP_OK(hipMemset(cp.buf, 0, b.off));
+    }
+    CompleteArgs& a = cp.args;
+    std::memset(&a, 0, sizeof(a));
+    a.call = reinterpret_cast<CompleteCall*>(cp.buf + off_call);
+    a.z32 = reinterpret_cast<float*>(cp.buf + off_z); a.m = reinterpret_cast<float*>(cp.buf + off_m); a.v = reinterpret_cast<float*>(cp.buf + off_v);
+    a.recon = reinterpret_cast<float*>(cp.buf + off_recon);
+    a.beta1 = h->cfg.beta1; a.beta2 = h->cfg.beta2; a.eps = h->cfg.adam_eps;
+    a.n_mod = M; a.nz = nz; a.bucket = B;
+    for (int m = 0; m < M; ++m) {
+        const Mod& md = h->mods[m];
+        a.Z[m] = h->at<void>(md.Z.rm); a.ldz[m] = md.Z.ld;
+        a.out32[m] = h->at<float>(md.out32); a.ld32[m] = md.ld32;
+        a.dO[m] = h->at<void>(md.dO.rm); a.lddo[m] = md.dO.ld;
+        a.dz[m] = reinterpret_cast<float*>(cp.buf + off_dz[m]); a.lddz[m] = lddz;
+        a.n_in[m] = md.n_in; a.binary[m] = h->cfg.mod[m].binary ? 1 : 0; a.w[m] = h->cfg.mod[m].weight;
+    }
+    cp.items.clear(); cp.fwd.clear(); cp.bwd.clear();
+    Builder bd(h, cp.items, B, false);
+    int slot = 0, Lmax = 0;
+    for (const Mod& md : h->mods) Lmax = std::max(Lmax, md.L);
+    auto group = [&](const std::string& name, std::vector<Launch>& dst, auto&& fill) {
+        const int first = (int)cp.items.size();
+        fill();
+        const int count = (int)cp.items.size() - first;
+        if (count > 0) dst.push_back(finish_launch(h, cp.items, first, count, name, &slot));
+    };
+    for (int k = 0; k < Lmax; ++k)
+        group("cmpl_dec" + std::to_string(k + 1), cp.fwd, [&] {
+            for (Mod& md : h->mods) if (k < md.L) cp.items.push_back(bd.fwd_hidden(k == 0 ? md.Z : md.D[k - 1], md.dec[k], md.D[k])); });
+    group("cmpl_out", cp.fwd, [&] { for (int m = 0; m < M; ++m) cp.items.push_back(bd.fwd_out(h->mods[m], m, false)); });
+    group("cmpl_bwd_out", cp.bwd, [&] {
+        for (Mod& md : h->mods) cp.items.push_back(bd.dgrad_hidden(md.dO, md.outl, md.D.back(), md.dD.back())); });
+    for (int k = Lmax - 1; k >= 1; --k)
+        group("cmpl_bwd_dec" + std::to_string(k + 1), cp.bwd, [&] {
+            for (Mod& md : h->mods) if (k < md.L) cp.items.push_back(bd.dgrad_hidden(md.dD[k], md.dec[k], md.D[k - 1], md.dD[k - 1])); });
+    group("cmpl_bwd_dz", cp.bwd, [&] {
+        for (int m = 0; m < M; ++m) {
+            const Mod& md = h->mods[m];
+            const Dense& d = md.dec[0];
+            WorkItem w = gemm_item(K_DGRAD_F32, B, nz, bd.K_of(d.out), h->at<void>(md.dD[0].rm), md.dD[0].ld, h->at<void>(d.W), d.ldw);
+            w.out0 = const_cast<float*>(a.dz[m]); w.ld0 = lddz;
+            cp.items.push_back(w);
+        } });
+    if (h->cfg.use_graph) {
+        try {
+            for (int i = 0; i < 3; ++i)
+                cp.g[i] = capture(h, [&](hipStream_t cs) { for (int j = 0; j < kCompleteSizes[i]; ++j) complete_pass(h, cp, cs); });
+        } catch (...) { for (StepGraph& g : cp.g) g.release(); throw; }
+    }
+    cp.built = true;
+    return cp;
+}
+
 // ---- masked steps: per-row modality presence (include/avae.h).  The masked twin of the step is built on first use: the forward
 // launches with WorkItem::present pointing at the staged presence bytes in every loss and latent item, and their graphs.
 void build_masked(avae_handle* h) {
@@ -2860,6 +2961,8 @@ void destroy_handle(avae_handle* h) {
     for (std::vector<StepGraph>& v : h->g_dp) for (StepGraph& g : v) g.release();
     for (avae_handle::Serve& sv : h->serve) if (sv.graph) (void)hipGraphExecDestroy(sv.graph);
     if (h->iw_buf) (void)hipFree(h->iw_buf);
+    for (StepGraph& g : h->cmpl.g) g.release();
+    if (h->cmpl.buf) (void)hipFree(h->cmpl.buf);
     if (h->pres_buf) (void)hipFree(h->pres_buf);
     if (h->ev_switch) (void)hipEventDestroy(h->ev_switch);
     if (h->comm) { try { (void)Rccl::get().destroy(h->comm); } catch (...) {} }
@@ -3379,6 +3482,60 @@ int avae_loglik(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, 
 }
 
 // ---- checkpoint: "AVAECKPT" | u32 version | u32 n_mod | u32 n_z | per modality {n_input, L, hs[L], conv, gener1, gener2} | u64 P | i64 step | theta | m | v
+int avae_complete(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, const uint8_t* const* obs_dev,
+                  const float* z0_dev, int32_t rows, int32_t n_iters, float lr, float prior_weight,
+                  float* z_dev, float* obj_dev, float* grad_dev, float* const* xhat_dev, void* stream) {
+    return guarded(h, [&] {
+        if (rows < 0) throw Err("avae_complete: rows must be >= 0");
+        if (n_iters < 0) throw Err("avae_complete: n_iters must be >= 0, got " + std::to_string(n_iters));
+        for (const Mod& md : h->mods)
+            if (md.conv) throw Err("avae_complete: MLP decoders only (this model has a conv modality)");
+        if (rows == 0) return;
+        if (!x_dev) throw Err("avae_complete: x_dev is NULL");
+        if (!z0_dev) throw Err("avae_complete: z0_dev is NULL");
+        if (!z_dev) throw Err("avae_complete: z_dev is NULL");
+        const int M = h->M, nz = h->nz;
+        int ld[kMaxMod] = {0, 0, 0, 0};
+        bool any = false;
+        for (int m = 0; m < M; ++m) {
+            if (!x_dev[m]) continue;
+            any = true;
+            ld[m] = x_ld ? x_ld[m] : h->mods[m].n_in;
+            if (ld[m] < h->mods[m].n_in)
+                throw Err("avae_complete: x_ld[" + std::to_string(m) + "] = " + std::to_string(ld[m]) + " is below n_input = " + std::to_string(h->mods[m].n_in));
+        }
+        if (!any) throw Err("avae_complete: every x_dev[m] is NULL (nothing is observed)");
+        hipStream_t s = on_stream(h, stream);
+        avae_handle::Complete& cp = complete_plan(h);
+        const bool graphs = h->cfg.use_graph && !h->timing;
+        for (int r0 = 0; r0 < rows; r0 += h->B) {
+            CompleteCall c;
+            std::memset(&c, 0, sizeof(c));
+            for (int m = 0; m < M; ++m) {
+                const size_t n_in = (size_t)h->mods[m].n_in;
+                if (x_dev[m]) {
+                    c.x[m] = x_dev[m] + (size_t)r0 * ld[m]; c.ldx[m] = ld[m];
+                    if (obs_dev && obs_dev[m]) c.obs[m] = obs_dev[m] + (size_t)r0 * n_in;
+                }
+                if (xhat_dev && xhat_dev[m]) c.xhat[m] = xhat_dev[m] + (size_t)r0 * n_in;
+            }
+            c.z0 = z0_dev + (size_t)r0 * nz; c.z_out = z_dev + (size_t)r0 * nz;
+            c.obj = obj_dev ? obj_dev + r0 : nullptr; c.obj_ld = rows;
+            c.grad = grad_dev ? grad_dev + (size_t)r0 * nz : nullptr;
+            c.rows = std::min(h->B, rows - r0); c.n_iters = n_iters; c.lr = lr; c.prior = prior_weight;
+            {
+                Timed t(h, s, "complete_begin");
+                launch_complete_begin(h->cfg.compute_dtype, cp.args, c, s); LAUNCH_OK("complete_begin");
+            }
+            int left = n_iters + 1;              // n_iters updating passes and the evaluation at the final z
+            if (graphs)
+                for (int i = 0; i < 3; ++i)
+                    for (; left >= kCompleteSizes[i]; left -= kCompleteSizes[i]) HIP_OK(hipGraphLaunch(cp.g[i].exec, s));
+            for (; left > 0; --left) complete_pass(h, cp, s);
+        }
+    });
+}
+
 int avae_save(avae_handle* h, const char* path) {
     return guarded(h, [&] {
         std::vector<float> I, th(h->P_flat), mm(h->P_flat), vv(h->P_flat);

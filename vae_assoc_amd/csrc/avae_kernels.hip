@@ -18,6 +18,7 @@
 // Reference maths: /root/reference/vae_assoc.py:163-222 (encoder), :243-304 (decoder),
 // :306-371 (losses), :373-374 (Adam); restated for CPU in oracle/vae_assoc_oracle.py.
 #include "avae_device.h"
+#include "avae_complete.h"
 #include <hip/hip_ext.h>
 #include <stdexcept>
 #include "../../include/avae.h"
@@ -3699,6 +3700,134 @@ void launch_iw_rows(const IwRowsArgs& a, hipStream_t s) {
 void launch_iw_reduce(const IwReduceArgs& a, hipStream_t s) {
     if (a.rows <= 0) return;
     AVAE_LAUNCH(k_iw_reduce, dim3((a.rows + kScoreRows - 1) / kScoreRows), dim3(kThreads), 0, s, a);
+}
+
+// ------------------------------------------------------------------ gradient latent refinement (avae_complete)
+// Same shapes and no-atomics rule as the score kernels: one wave64 per row (and modality), every sum a fixed-order shuffle tree.
+
+// The per-call launch ahead of the replayed passes: publishes the call, stages z0 into the fp32 z rows and every decoder's input
+// (rows beyond the call's rows: zeros) and clears the Adam moments.  One lane per latent dimension.
+template <typename CT>
+__global__ void __launch_bounds__(kThreads) k_complete_begin(CompleteArgs a, CompleteCall c) {
+    const int row = blockIdx.x * kScoreRows + (threadIdx.x >> 6), d = threadIdx.x & 63;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *a.call = c;
+    if (row >= a.bucket || d >= a.nz) return;
+    const float z = row < c.rows ? c.z0[(size_t)row * a.nz + d] : 0.0f;
+    const size_t i = (size_t)row * a.nz + d;
+    a.z32[i] = z; a.m[i] = 0.0f; a.v[i] = 0.0f;
+    for (int m = 0; m < a.n_mod; ++m) reinterpret_cast<CT*>(a.Z[m])[(size_t)row * a.ldz[m] + d] = to_ct<CT>(z);
+}
+
+// One wave per (row, modality) over the decoder's fp32 output xh (p for Bernoulli, x_hat for Gaussian): the output layer's
+// activation gradient w_m * dRecon/dlogit in the compute dtype -- loss_bernoulli's / loss_gauss's expressions, the 1e-3 inside the
+// log kept -- and the row's recon_obs with recon_row's arithmetic, both over the OBSERVED elements only: an unobserved element is
+// selected away (its x is never loaded, its gradient is a stored 0), and so is every element of a NULL modality and of the
+// plan's rows beyond the call's.  The last pass (no update follows) also hands the decoder output to the caller.
+template <typename CT>
+__global__ void __launch_bounds__(kThreads) k_complete_out(CompleteArgs a) {
+#pragma clang fp contract(off)
+    const int row = blockIdx.x * kScoreRows + (threadIdx.x >> 6), lane = threadIdx.x & 63, m = blockIdx.y;
+    CompleteCall* c = a.call;
+    const int pass = c->n_upd, rows = c->rows;
+    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) c->n_out = pass + 1;
+    if (row >= a.bucket) return;                    // wave-uniform, as every branch on row / m below
+    const int n_in = a.n_in[m];
+    const bool live = row < rows;
+    const float* xr = (live && c->x[m]) ? c->x[m] + (size_t)row * c->ldx[m] : nullptr;
+    const unsigned char* ob = (xr && c->obs[m]) ? c->obs[m] + (size_t)row * n_in : nullptr;
+    const float* xh = a.out32[m] + (size_t)row * a.ld32[m];
+    float* xo = (live && pass == c->n_iters && c->xhat[m]) ? c->xhat[m] + (size_t)row * n_in : nullptr;
+    CT* dO = reinterpret_cast<CT*>(a.dO[m]) + (size_t)row * a.lddo[m];
+    const float w = a.w[m];
+    const int binary = a.binary[m];
+    float acc = 0.0f;
+    for (int e = lane; e < n_in; e += 64) {
+        const float p = xh[e];
+        float da = 0.0f;
+        if (xr && (!ob || ob[e])) {
+            const float xv = xr[e];
+            if (binary) {
+                const float lp = 1e-3f + p, lq = 1e-3f + 1.0f - p;
+                acc += -(xv * flog(lp) + (1.0f - xv) * flog(lq));
+                da = w * p * (1.0f - p) * ((1.0f - xv) * lp - xv * lq) * frcp(lp * lq);
+            } else {
+                float sl;
+                loss_gauss(p, xv, 1.0f, sl, da);
+                acc += sl;
+                da = w * da;
+            }
+        }
+        dO[e] = to_ct<CT>(da);
+        if (xo) xo[e] = p;
+    }
+    const float r = wave_sum(acc);
+    if (lane == 0 && live) a.recon[(size_t)row * a.n_mod + m] = r;
+}
+
+// b^t for a small positive integer t, in double (the bias corrections 1 - b^t cancel badly in fp32 for the first steps)
+__device__ __forceinline__ double pow_int(double b, int t) {
+    double r = 1.0;
+    for (; t > 0; t >>= 1) { if (t & 1) r *= b; b *= b; }
+    return r;
+}
+
+// One wave per row, one lane per latent dimension (n_z <= 64): g = sum_m dz_m (fixed order) + prior * z,
+// J = sum_m w_m recon_m + prior * |z|^2 / 2 into the objective history, the first pass's g to the caller, then textbook Adam with
+// bias correction on z (fp32; the new z also goes into every decoder's input in the compute dtype).  The last pass (pass ==
+// n_iters) evaluates only and hands out z.
+template <typename CT>
+__global__ void __launch_bounds__(kThreads) k_complete_update(CompleteArgs a) {
+#pragma clang fp contract(off)
+    const int row = blockIdx.x * kScoreRows + (threadIdx.x >> 6), d = threadIdx.x & 63;
+    CompleteCall* c = a.call;
+    const int pass = c->n_out - 1, rows = c->rows, n_iters = c->n_iters;
+    const float prior = c->prior, lr = c->lr;
+    if (blockIdx.x == 0 && threadIdx.x == 0) c->n_upd = pass + 1;
+    if (row >= rows) return;                        // wave-uniform: the shuffles below always run on whole waves
+    const int nz = a.nz;
+    const bool on = d < nz;
+    const size_t i = (size_t)row * nz + d;
+    float z = on ? a.z32[i] : 0.0f;
+    float g = 0.0f;
+    for (int m = 0; m < a.n_mod; ++m) g += on ? a.dz[m][(size_t)row * a.lddz[m] + d] : 0.0f;
+    g += prior * z;
+    const float zz = wave_sum(on ? z * z : 0.0f);
+    if (d == 0 && c->obj) {
+        float J = 0.0f;
+        for (int m = 0; m < a.n_mod; ++m) J += a.w[m] * a.recon[(size_t)row * a.n_mod + m];
+        J += prior * (0.5f * zz);
+        c->obj[(size_t)pass * c->obj_ld + row] = J;
+    }
+    if (!on) return;
+    if (pass == 0 && c->grad) c->grad[i] = g;
+    if (pass >= n_iters) { c->z_out[i] = z; return; }
+    const int t = pass + 1;
+    const float b1 = a.beta1, b2 = a.beta2;
+    const float c1 = (float)(1.0 - pow_int((double)b1, t)), c2 = (float)(1.0 - pow_int((double)b2, t));
+    float mm = a.m[i], vv = a.v[i];
+    mm = b1 * mm + (1.0f - b1) * g;
+    vv = b2 * vv + (1.0f - b2) * (g * g);
+    z -= lr * (mm / c1) / (sqrtf(vv / c2) + a.eps);
+    a.z32[i] = z; a.m[i] = mm; a.v[i] = vv;
+    for (int m = 0; m < a.n_mod; ++m) reinterpret_cast<CT*>(a.Z[m])[(size_t)row * a.ldz[m] + d] = to_ct<CT>(z);
+}
+
+void launch_complete_begin(int compute_dtype, const CompleteArgs& a, const CompleteCall& call, hipStream_t s) {
+    const dim3 grid((a.bucket + kScoreRows - 1) / kScoreRows);
+    if (compute_dtype == AVAE_BF16) AVAE_LAUNCH((k_complete_begin<__bf16>), grid, dim3(kThreads), 0, s, a, call);
+    else AVAE_LAUNCH((k_complete_begin<float>), grid, dim3(kThreads), 0, s, a, call);
+}
+
+void launch_complete_out(int compute_dtype, const CompleteArgs& a, hipStream_t s) {
+    const dim3 grid((a.bucket + kScoreRows - 1) / kScoreRows, a.n_mod);
+    if (compute_dtype == AVAE_BF16) AVAE_LAUNCH((k_complete_out<__bf16>), grid, dim3(kThreads), 0, s, a);
+    else AVAE_LAUNCH((k_complete_out<float>), grid, dim3(kThreads), 0, s, a);
+}
+
+void launch_complete_update(int compute_dtype, const CompleteArgs& a, hipStream_t s) {
+    const dim3 grid((a.bucket + kScoreRows - 1) / kScoreRows);
+    if (compute_dtype == AVAE_BF16) AVAE_LAUNCH((k_complete_update<__bf16>), grid, dim3(kThreads), 0, s, a);
+    else AVAE_LAUNCH((k_complete_update<float>), grid, dim3(kThreads), 0, s, a);
 }
 
 }  // namespace avae

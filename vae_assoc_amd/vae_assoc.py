@@ -654,6 +654,74 @@ class AssocVariationalAutoEncoder(object):
             out = out.cpu().numpy()
         return {"marginal": out[:, :M], "joint": out[:, M:2 * M], "conditional": out[:, 2 * M:].reshape(rows, M, M)}
 
+    def complete(self, X, observed=None, n_iters=50, lr=0.05, prior_weight=1.0, z0=None, init=None):
+        """Gradient latent refinement for partially observed rows (avae_complete in include/avae.h): per
+        row, the z that minimises ``J(z) = sum_m w_m recon_obs_m(x_m, dec_m(z), o_m) + prior_weight * 0.5 |z|^2`` is searched with
+        ``n_iters`` steps of per-row Adam (step size ``lr``) through the decoders, the whole loop on the device, and every
+        modality is decoded from the result.
+
+        ``X`` is a list over modalities with equal row counts; ``X[m] = None`` means modality m is unobserved.  ``observed`` is
+        None (everything given is observed) or a list over modalities of ``[N, n_input_m]`` bool / integer element masks, nonzero
+        = observed, ``observed[m] = None`` = modality m fully observed.  Unobserved elements are never read: fill them with
+        anything.  The start is ``z0`` (``[N, n_z]``) or, without it, the posterior mean of modality ``init`` (default: the first
+        modality that is not None) encoded with its unobserved elements set to 0, as the reference encodes the blanked image
+        (baxter_vae_assoc_writer.py:501-511).  ``n_iters = 0`` evaluates only.
+
+        Returns a dict: ``z [N, n_z]``, ``x`` (list over modalities of ``[N, n_input_m]`` decoder outputs at ``z``, the unobserved
+        parts and modalities included), ``objective [n_iters + 1, N]`` (J at the start and after every update) and ``grad0
+        [N, n_z]`` (dJ/dz at the start).  NumPy in gives NumPy out, device tensors in give device tensors out."""
+        archs = self.network_architectures
+        M = len(archs)
+        if len(X) != M:
+            raise ValueError("expected a list of %d modalities, got %d" % (M, len(X)))
+        if observed is not None and len(observed) != M:
+            raise ValueError("observed must be None or a list of %d element masks, got %d" % (M, len(observed)))
+        if isinstance(n_iters, bool) or not isinstance(n_iters, (int, np.integer)) or n_iters < 0:
+            raise ValueError("n_iters must be an integer >= 0, got %r" % (n_iters,))
+        n_iters = int(n_iters)
+        ts, obs, rows, was_np = [None] * M, [None] * M, None, None
+        for m, (x, na) in enumerate(zip(X, archs)):
+            if x is None:
+                continue
+            ts[m], np_in = self._dev(x, int(na["n_input"]))
+            if was_np is None:
+                was_np = np_in
+            if rows is not None and ts[m].shape[0] != rows:
+                raise ValueError("every modality needs the same row count: %d vs %d" % (ts[m].shape[0], rows))
+            rows = ts[m].shape[0]
+            if observed is not None and observed[m] is not None:
+                o = observed[m] if torch.is_tensor(observed[m]) else torch.as_tensor(np.asarray(observed[m]))
+                if tuple(o.shape) != (rows, int(na["n_input"])):
+                    raise ValueError("observed[%d] must be [%d, %d] as X[%d], got %s" % (m, rows, int(na["n_input"]), m, tuple(o.shape)))
+                obs[m] = (o != 0).to(device=self.device, dtype=torch.uint8).contiguous()
+        if rows is None:
+            raise ValueError("every modality is None: nothing is observed")
+        if z0 is None:
+            init = next(m for m in range(M) if ts[m] is not None) if init is None else init
+            if isinstance(init, bool) or not isinstance(init, (int, np.integer)) or not 0 <= init < M or ts[init] is None:
+                raise ValueError("init must be the index of a modality that is not None, got %r" % (init,))
+            xi = ts[init] if obs[init] is None else torch.where(obs[init] != 0, ts[init], torch.zeros_like(ts[init]))
+            z = self._encode(init, xi)
+        else:
+            z, _ = self._dev(z0, self.n_z)
+            if z.shape[0] != rows:
+                raise ValueError("z0 must be [%d, %d], got %s" % (rows, self.n_z, tuple(z.shape)))
+        z = z.contiguous()
+        out_z = torch.empty((rows, self.n_z), dtype=torch.float32, device=self.device)
+        grad = torch.empty_like(out_z)
+        obj = torch.empty((n_iters + 1, rows), dtype=torch.float32, device=self.device)
+        outs = [torch.empty((rows, int(na["n_input"])), dtype=torch.float32, device=self.device) for na in archs]
+        xp = (C.c_void_p * M)(*[t.data_ptr() if t is not None else None for t in ts])
+        lds = (C.c_int32 * M)(*[0 if t is None else (t.stride(0) if rows > 1 else t.shape[1]) for t in ts])
+        op = (C.c_void_p * M)(*[o.data_ptr() if o is not None else None for o in obs])
+        hp = (C.c_void_p * M)(*[o.data_ptr() for o in outs])
+        if rows:
+            _capi.check(self._h, self._L.avae_complete(self._h, xp, lds, op, z.data_ptr(), rows, n_iters, float(lr), float(prior_weight),
+                                                       out_z.data_ptr(), obj.data_ptr(), grad.data_ptr(), hp, self._stream()),
+                        "avae_complete")
+        conv = (lambda a: a.cpu().numpy()) if was_np else (lambda a: a)
+        return {"z": conv(out_z), "x": [conv(o) for o in outs], "objective": conv(obj), "grad0": conv(grad)}
+
     def save_model(self, fname=None):
         """reference vae_assoc.py:427-435 (default name: timestamp + batch size)."""
         if fname is None:
