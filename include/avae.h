@@ -236,6 +236,24 @@ int avae_score_width(const avae_config* cfg, int32_t flags, int32_t* k);
  * it changes nothing the next training step reads; on a data-parallel replica it scores the local rows, with no collective. */
 int avae_score(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, int32_t rows, const float* eps_dev, int32_t flags,
                float* out_dev, void* stream);
+/* avae_score for partially paired rows.  present_dev: device uint8 [rows][M], row-major, nonzero = row n has modality m (p below), as
+ * in avae_train_steps_masked; NULL is an error (avae_score is the unmasked call).  x_dev[m] == NULL: modality m is absent on every
+ * row, whatever its column of present_dev says (never read through).  Everything else -- out_dev, eps_dev, the generator's keys and
+ * the per-call draw counter (ONE counter for masked and unmasked calls), rows == 0, chunking, the stream -- is avae_score's.
+ *   recon[n,m], latent[n,m]  the unmasked value where p[n,m], else +0.0
+ *   assoc[n,(i,j)]           the unmasked value where p[n,i] and p[n,j], else +0.0
+ *   cost[n]                  sum_m w_m (recon + latent) + assoc_lambda sum_p assoc over the stored columns (absent addends: +0.0)
+ *   cross[n,s,d]             the unmasked value where p[n,s] and p[n,d], else quiet NaN (a zero would read as a perfect prediction)
+ * For rows = batch_size and the same eps the columns give back avae_eval_cost_masked, with no need for p:
+ *   eval_cost_masked == sum_m w_m [(1/B) sum_n latent + (binary_m ? 1/B : 1) sum_n recon] + assoc_lambda sum_p sum_n assoc
+ * Absent entries are selected away, never multiplied by 0 and never read: staging stores zeros for them, the row kernels do not load
+ * them, and NaN / Inf / garbage there changes no bit of any output.  Every present output is a select of the unmasked expression:
+ * an all-present mask gives avae_score's output bit for bit, and every present column except cost is bitwise avae_score's value for
+ * the same rows and eps.  No atomics.  It changes nothing the next training step reads and works on a data-parallel replica as
+ * avae_score does; the presence bytes of a chunk (batch_size * M) are staged into a buffer allocated by the first masked scoring
+ * call and freed by avae_destroy; avae_workspace_bytes is unchanged. */
+int avae_score_masked(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, const uint8_t* present_dev, int32_t rows,
+                      const float* eps_dev, int32_t flags, float* out_dev, void* stream);
 
 /* ---- importance-weighted log-likelihoods (IWAE, K = n_samples).  Per row n, proposal s (the encoder of modality s on x_s, as
  * avae_encode gives it), noise eps_k shared by every proposal: z_{s,k} = mu_s + exp(lv_s/2) eps_k (fp32; the decoders read it in the
@@ -252,6 +270,16 @@ int avae_score(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, i
  * collective. */
 int avae_loglik(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, int32_t rows, int32_t n_samples,
                 const float* eps_dev, float* out_dev, void* stream);
+/* avae_loglik for partially paired rows; present_dev and x_dev[m] == NULL as in avae_score_masked, the rest as avae_loglik:
+ *   marginal[n,s]       the unmasked value where p[n,s], else NaN
+ *   conditional[n,s,d]  the unmasked value where p[n,s] and p[n,d], else NaN
+ *   joint[n,s]          LSE_k(sum_{d: p[n,d]} l_d(z_{s,k}) + r_{s,k}) - log K where p[n,s], else NaN: the log-likelihood of the
+ *                       modalities the row has, under proposal q_s.  The sum starts from 0.0f and adds the present l_d in modality
+ *                       order, so a row with only modality s has joint[s] bitwise equal to marginal[s]
+ * A row with nothing present is all NaN.  The selection rules, the bitwise ties with the unmasked call (every present output except
+ * joint) and the side-effect rules are avae_score_masked's. */
+int avae_loglik_masked(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, const uint8_t* present_dev, int32_t rows,
+                       int32_t n_samples, const float* eps_dev, float* out_dev, void* stream);
 
 /* ---- gradient latent refinement for partially observed rows (the reference searches z around the encoder's guess by calling
  * generate 10-50 times per iteration from the host, baxter_vae_assoc_writer.py:259-304,466-559; this is the deterministic,

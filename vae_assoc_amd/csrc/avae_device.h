@@ -394,6 +394,9 @@ struct ScoreLatentArgs {
     float* out; int k;             // score rows
     int rows, nz, n_mod;
     int src;                       // < 0: sampled pass (latent, assoc columns; z_m = mu_m + exp(lv_m/2) eps); else z = mu_src for every decoder
+    // masked scoring (avae_score_masked; nullable, null = the unmasked kernel): the chunk's staged presence bytes [rows][n_mod],
+    // 0 / 1.  An absent modality's latent column and every pair column it is part of hold +0.0, its decoder input zeros.
+    const unsigned char* present;
 };
 void launch_score_latent(int compute_dtype, const ScoreLatentArgs& a, hipStream_t s);
 struct ScoreRowsArgs {
@@ -404,6 +407,9 @@ struct ScoreRowsArgs {
     int cost;                      // 1: also cost = sum_m w_m (recon_m + latent_m) + lambda sum_p assoc_p (the sampled pass's last modality)
     int n_mod, n_pair;
     float w[kMaxMod]; float lambda;
+    // masked scoring (nullable): presence bytes as above.  The column holds the unmasked value where the row has modalities pa and
+    // pb (pa == pb for a recon column), else absent_bits (+0.0 for recon, quiet NaN for cross); an absent row's x is never loaded.
+    const unsigned char* present; int pa, pb; unsigned absent_bits;
 };
 void launch_score_rows(const ScoreRowsArgs& a, hipStream_t s);
 
@@ -418,6 +424,9 @@ struct IwLatentArgs {
     int rows, kc, k0, K, nz;
     long long row0;                 // Philox: row of the whole input of the pass's first row (row_offset included)
     unsigned long long seed; unsigned draw;
+    // masked log-likelihood (avae_loglik_masked; nullable): the proposal's column of the chunk's staged presence bytes, row stride
+    // pres_ld.  A row without the proposal's modality draws nothing: its decoder inputs are zeros and its r is NaN.
+    const unsigned char* present; int pres_ld;
 };
 void launch_iw_latent(int compute_dtype, const IwLatentArgs& a, hipStream_t s);
 struct IwRowsArgs {
@@ -426,6 +435,7 @@ struct IwRowsArgs {
     int n_in[kMaxMod], binary[kMaxMod];
     float* ell;                     // [n_dec][n_mod]: -recon
     int n_dec, kc, n_mod;
+    const unsigned char* present;   // masked (nullable): [rows][n_mod]; an absent target's x is never loaded, its ell holds +0.0
 };
 void launch_iw_rows(const IwRowsArgs& a, hipStream_t s);
 struct IwReduceArgs {
@@ -435,6 +445,9 @@ struct IwReduceArgs {
     int rows, kc, src, n_mod;
     int first, last;                // first / last sample block of the row
     float log_k;
+    // masked (nullable): [rows][n_mod].  A row without the proposal writes NaN to all its outputs of this proposal and keeps no
+    // state; else an absent target d stays out of the joint sum, its conditional is NaN and its running state is not touched.
+    const unsigned char* present;
 };
 void launch_iw_reduce(const IwReduceArgs& a, hipStream_t s);
 

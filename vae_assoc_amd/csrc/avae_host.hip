@@ -251,6 +251,7 @@ struct avae_handle {
     size_t off_slot = 0;
     // avae_loglik's scratch, allocated by its first call (z rows, r, log-weights, running log-sum-exp states of one pass)
     float* iw_buf = nullptr;
+    unsigned char* row_pres = nullptr;      // masked scoring: the chunk's staged presence bytes [batch_size][M] (first use)
     size_t off_chain = 0;
     size_t off_consts = 0, off_conv_tab = 0;   // 32 B {zeros | one, 0...}; device copy of conv_tab
     std::vector<ConvA> conv_tab;             // implicit patch matrices of the training plan
@@ -2133,10 +2134,14 @@ void run_prep_batch(avae_handle* h, const float* const* x, const int32_t* x_ld, 
 }
 
 void run_prep_single(avae_handle* h, const float* src, int src_ld, int rows, int cols, const Act& dst, float* dst32, int ld32,
-                     bool do_eps, const float* eps, unsigned long long salt, hipStream_t s, int row0 = 0) {
+                     bool do_eps, const float* eps, unsigned long long salt, hipStream_t s, int row0 = 0,
+                     const unsigned char* pres_src = nullptr, unsigned char* pres_dst = nullptr, int pres_ld = 0) {
     PrepArgs a;
     std::memset(&a, 0, sizeof(a));
-    if (src) {
+    // masked staging of one modality: pres_src / pres_dst point at its column of the [rows][pres_ld] presence arrays, so the
+    // segment's index 0 addresses it; a null src is then a modality absent on every row, staged as zeros
+    if (pres_src) { a.pres_src = pres_src; a.pres_dst = pres_dst; a.pres_ld = pres_ld; }
+    if (src || pres_src) {
         PrepSeg& g = a.seg[0];
         g.src = src; g.src_ld = src_ld; g.rows = rows; g.cols = cols;
         g.dst32 = dst32; g.ld32 = ld32;
@@ -2685,17 +2690,25 @@ void decode_rows(avae_handle* h, int m, const float* z, int rows, float* xhat, h
 }
 
 // The row inputs of avae_score / avae_loglik: out_dev, x_dev and x_ld of every modality (x_ld NULL: dense rows) -> ld[]
+// masked (the *_masked calls): a NULL x_dev[m] is a modality absent on every row (ld[m] = 0)
 void check_row_inputs(const avae_handle* h, const char* what, const float* const* x_dev, const int32_t* x_ld, const float* out_dev,
-                      int* ld) {
+                      int* ld, bool masked = false) {
     const std::string w = what;
     if (!out_dev) throw Err(w + ": out_dev is NULL");
     if (!x_dev) throw Err(w + ": x_dev is NULL");
     for (int m = 0; m < h->M; ++m) {
+        if (!x_dev[m] && masked) { ld[m] = 0; continue; }
         if (!x_dev[m]) throw Err(w + ": x_dev[" + std::to_string(m) + "] is NULL");
         ld[m] = x_ld ? x_ld[m] : h->mods[m].n_in;
         if (ld[m] < h->mods[m].n_in)
             throw Err(w + ": x_ld[" + std::to_string(m) + "] = " + std::to_string(ld[m]) + " is below n_input = " + std::to_string(h->mods[m].n_in));
     }
+}
+
+// The chunk presence buffer of the masked scoring calls (not part of the workspace; avae_destroy frees it)
+unsigned char* row_presence_buf(avae_handle* h) {
+    if (!h->row_pres) HIP_OK(hipMalloc(reinterpret_cast<void**>(&h->row_pres), (size_t)h->B * h->M));
+    return h->row_pres;
 }
 
 // ---- gradient latent refinement (avae_complete; include/avae.h, avae_complete.h).  One pass over a chunk of <= batch_size rows:
@@ -2961,6 +2974,7 @@ void destroy_handle(avae_handle* h) {
     for (std::vector<StepGraph>& v : h->g_dp) for (StepGraph& g : v) g.release();
     for (avae_handle::Serve& sv : h->serve) if (sv.graph) (void)hipGraphExecDestroy(sv.graph);
     if (h->iw_buf) (void)hipFree(h->iw_buf);
+    if (h->row_pres) (void)hipFree(h->row_pres);
     for (StepGraph& g : h->cmpl.g) g.release();
     if (h->cmpl.buf) (void)hipFree(h->cmpl.buf);
     if (h->pres_buf) (void)hipFree(h->pres_buf);
@@ -3317,14 +3331,18 @@ int avae_score_width(const avae_config* cfg, int32_t flags, int32_t* k) {
 // Per chunk of at most batch_size rows: stage every modality (and eps) -> encoders -> k_score_latent (latent, assoc, z of every
 // modality) -> per modality decoder + k_score_rows (the last one also forms cost); with AVAE_SCORE_CROSS then per source s:
 // k_score_latent(z = mu_s) -> every decoder + k_score_rows.  The kernels write straight into the caller's score rows.
-int avae_score(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, int32_t rows, const float* eps_dev, int32_t flags,
-               float* out_dev, void* stream) {
-    return guarded(h, [&] {
-        if (flags & ~AVAE_SCORE_CROSS) throw Err("avae_score: unknown flags (only AVAE_SCORE_CROSS is defined)");
-        if (rows < 0) throw Err("avae_score: rows must be >= 0");
+// present (avae_score_masked): the caller's [rows][M] presence bytes.  Staging copies each chunk's bytes (0 / 1, NULL sources folded
+// in) into row_pres, which the MASK kernel instances read; every launch of the unmasked call is kept, absent rows run as zeros
+// whose results the kernels select away.
+static void score_call(avae_handle* h, const char* what, const float* const* x_dev, const int32_t* x_ld, const uint8_t* present,
+                int32_t rows, const float* eps_dev, int32_t flags, float* out_dev, void* stream) {
+        const std::string w = what;
+        if (flags & ~AVAE_SCORE_CROSS) throw Err(w + ": unknown flags (only AVAE_SCORE_CROSS is defined)");
+        if (rows < 0) throw Err(w + ": rows must be >= 0");
         if (rows == 0) return;
         int ld[kMaxMod];
-        check_row_inputs(h, "avae_score", x_dev, x_ld, out_dev, ld);
+        check_row_inputs(h, what, x_dev, x_ld, out_dev, ld, present != nullptr);
+        unsigned char* pres = present ? row_presence_buf(h) : nullptr;
         const int M = h->M, P = M * (M - 1) / 2;
         const bool cross = (flags & AVAE_SCORE_CROSS) != 0;
         const int k = 1 + 2 * M + P + (cross ? M * M : 0);
@@ -3338,13 +3356,15 @@ int avae_score(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, i
         ScoreRowsArgs ra;
         std::memset(&ra, 0, sizeof(ra));
         ra.k = k; ra.n_mod = M; ra.n_pair = P; ra.lambda = h->cfg.assoc_lambda;
+        la.present = ra.present = pres;
         for (int m = 0; m < M; ++m) {
             la.mulv[m] = h->at<float>(h->mods[m].mulv);
             la.Z[m] = h->at<void>(h->mods[m].Z.rm); la.ldz[m] = h->mods[m].Z.ld;
             ra.w[m] = h->cfg.mod[m].weight;
         }
-        auto score_rows = [&](int m, int col, bool with_cost, int n) {
+        auto score_rows = [&](int m, int col, bool with_cost, int n, int src = -1) {
             const Mod& md = h->mods[m];
+            ra.pa = src < 0 ? m : src; ra.pb = m; ra.absent_bits = src < 0 ? 0u : 0x7FC00000u;      // (masked) +0.0 / quiet NaN
             ra.xhat = h->at<float>(md.out32); ra.ld32 = md.ld32;
             ra.n_in = md.n_in; ra.binary = h->cfg.mod[m].binary ? 1 : 0;
             ra.col = col; ra.cost = with_cost ? 1 : 0; ra.rows = n;
@@ -3355,8 +3375,9 @@ int avae_score(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, i
             const int n = std::min(h->B, rows - r0);
             for (int m = 0; m < M; ++m) {
                 const Mod& md = h->mods[m];
-                run_prep_single(h, x_dev[m] + (size_t)r0 * ld[m], ld[m], n, md.n_in, md.X0, nullptr, 0, m == 0,
-                                eps_dev ? eps_dev + (size_t)r0 * h->nz : nullptr, 0x73636f72ull /*scor*/ | draw, s, r0);
+                run_prep_single(h, x_dev[m] ? x_dev[m] + (size_t)r0 * ld[m] : nullptr, ld[m], n, md.n_in, md.X0, nullptr, 0, m == 0,
+                                eps_dev ? eps_dev + (size_t)r0 * h->nz : nullptr, 0x73636f72ull /*scor*/ | draw, s, r0,
+                                present ? present + (size_t)r0 * M + m : nullptr, present ? pres + m : nullptr, M);
                 run_inference(h, m, true, n, s);
             }
             la.out = out_dev + (size_t)r0 * k; la.rows = n; la.src = -1;
@@ -3366,7 +3387,7 @@ int avae_score(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, i
                 launch_score_latent(h->cfg.compute_dtype, la, s); LAUNCH_OK("score_latent");
             }
             for (int m = 0; m < M; ++m) {
-                ra.x = x_dev[m] + (size_t)r0 * ld[m]; ra.ldx = ld[m];
+                ra.x = x_dev[m] ? x_dev[m] + (size_t)r0 * ld[m] : nullptr; ra.ldx = ld[m];
                 run_inference(h, m, false, n, s);
                 score_rows(m, 1 + m, m == M - 1, n);
             }
@@ -3378,12 +3399,24 @@ int avae_score(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, i
                     launch_score_latent(h->cfg.compute_dtype, la, s); LAUNCH_OK("score_latent");
                 }
                 for (int d = 0; d < M; ++d) {
-                    ra.x = x_dev[d] + (size_t)r0 * ld[d]; ra.ldx = ld[d];
+                    ra.x = x_dev[d] ? x_dev[d] + (size_t)r0 * ld[d] : nullptr; ra.ldx = ld[d];
                     run_inference(h, d, false, n, s);
-                    score_rows(d, 1 + 2 * M + P + src * M + d, false, n);
+                    score_rows(d, 1 + 2 * M + P + src * M + d, false, n, src);
                 }
             }
         }
+}
+
+int avae_score(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, int32_t rows, const float* eps_dev, int32_t flags,
+               float* out_dev, void* stream) {
+    return guarded(h, [&] { score_call(h, "avae_score", x_dev, x_ld, nullptr, rows, eps_dev, flags, out_dev, stream); });
+}
+
+int avae_score_masked(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, const uint8_t* present_dev, int32_t rows,
+                      const float* eps_dev, int32_t flags, float* out_dev, void* stream) {
+    return guarded(h, [&] {
+        if (!present_dev) throw Err("avae_score_masked: present_dev is NULL (avae_score is the unmasked call)");
+        score_call(h, "avae_score_masked", x_dev, x_ld, present_dev, rows, eps_dev, flags, out_dev, stream);
     });
 }
 
@@ -3392,14 +3425,16 @@ int avae_score(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, i
 // modality once; per sample block and proposal src: k_iw_latent (z, r) -> every decoder (grouped launches of the serve route, or
 // modality by modality for conv nets / use_graph = 0 / timing) -> k_iw_rows (log-weights) -> k_iw_reduce (running log-sum-exp;
 // the row's last block writes the caller's row).  Scratch: iw_buf (allocated once) and the decoders' out32 / Z buffers.
-int avae_loglik(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, int32_t rows, int32_t n_samples,
-                const float* eps_dev, float* out_dev, void* stream) {
-    return guarded(h, [&] {
-        if (rows < 0) throw Err("avae_loglik: rows must be >= 0");
-        if (n_samples < 1) throw Err("avae_loglik: n_samples must be >= 1, got " + std::to_string(n_samples));
+// present (avae_loglik_masked): as score_call's.
+static void loglik_call(avae_handle* h, const char* what, const float* const* x_dev, const int32_t* x_ld, const uint8_t* present,
+                 int32_t rows, int32_t n_samples, const float* eps_dev, float* out_dev, void* stream) {
+        const std::string w = what;
+        if (rows < 0) throw Err(w + ": rows must be >= 0");
+        if (n_samples < 1) throw Err(w + ": n_samples must be >= 1, got " + std::to_string(n_samples));
         if (rows == 0) return;
         int ld[kMaxMod];
-        check_row_inputs(h, "avae_loglik", x_dev, x_ld, out_dev, ld);
+        check_row_inputs(h, what, x_dev, x_ld, out_dev, ld, present != nullptr);
+        unsigned char* pres = present ? row_presence_buf(h) : nullptr;
         const int M = h->M, B = h->B, nz = h->nz, K = n_samples;
         hipStream_t s = on_stream(h, stream);
         const int width = 2 * M + M * M;
@@ -3438,13 +3473,16 @@ int avae_loglik(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, 
         IwReduceArgs rd;
         std::memset(&rd, 0, sizeof(rd));
         rd.ell = ell; rd.r = rbuf; rd.state = state; rd.width = width; rd.n_mod = M; rd.log_k = std::log((float)K);
+        ra.present = rd.present = pres; la.pres_ld = M;
         for (int r0 = 0; r0 < rows; r0 += n_rows) {
             const int n = std::min(n_rows, rows - r0);
             for (int m = 0; m < M; ++m) {
                 const Mod& md = h->mods[m];
-                run_prep_single(h, x_dev[m] + (size_t)r0 * ld[m], ld[m], n, md.n_in, md.X0, nullptr, 0, false, nullptr, 0, s, r0);
+                const float* xm = x_dev[m] ? x_dev[m] + (size_t)r0 * ld[m] : nullptr;
+                run_prep_single(h, xm, ld[m], n, md.n_in, md.X0, nullptr, 0, false, nullptr, 0, s, r0,
+                                present ? present + (size_t)r0 * M + m : nullptr, present ? pres + m : nullptr, M);
                 run_inference(h, m, true, n, s);
-                ra.x[m] = x_dev[m] + (size_t)r0 * ld[m]; ra.ldx[m] = ld[m];
+                ra.x[m] = xm; ra.ldx[m] = ld[m];
             }
             la.eps = eps_dev ? eps_dev + (size_t)r0 * K * nz : nullptr;
             la.row0 = (long long)h->cfg.row_offset + r0;
@@ -3456,6 +3494,7 @@ int avae_loglik(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, 
                 rd.first = k0 == 0; rd.last = k0 + kc == K;
                 for (int src = 0; src < M; ++src) {
                     la.mulv = h->at<float>(h->mods[src].mulv);
+                    la.present = pres ? pres + src : nullptr;
                     {
                         Timed t(h, s, "iw_latent");
                         launch_iw_latent(h->cfg.compute_dtype, la, s); LAUNCH_OK("iw_latent");
@@ -3478,6 +3517,18 @@ int avae_loglik(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, 
                 }
             }
         }
+}
+
+int avae_loglik(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, int32_t rows, int32_t n_samples,
+                const float* eps_dev, float* out_dev, void* stream) {
+    return guarded(h, [&] { loglik_call(h, "avae_loglik", x_dev, x_ld, nullptr, rows, n_samples, eps_dev, out_dev, stream); });
+}
+
+int avae_loglik_masked(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, const uint8_t* present_dev, int32_t rows,
+                       int32_t n_samples, const float* eps_dev, float* out_dev, void* stream) {
+    return guarded(h, [&] {
+        if (!present_dev) throw Err("avae_loglik_masked: present_dev is NULL (avae_loglik is the unmasked call)");
+        loglik_call(h, "avae_loglik_masked", x_dev, x_ld, present_dev, rows, n_samples, eps_dev, out_dev, stream);
     });
 }
 

@@ -3464,18 +3464,36 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// Bit m = presence byte m of one row of a staged [rows][n_mod] presence array.  Every lane of the wave asks for the same row; the
+// result goes through readfirstlane, so it sits in an SGPR and every branch on it is a scalar branch: the shuffle trees behind such
+// a branch run on whole waves or not at all.
+__device__ __forceinline__ unsigned row_presence(const unsigned char* present, int row, int n_mod) {
+    const unsigned char* pr = present + (size_t)row * n_mod;
+    unsigned pm = 0;
+#pragma unroll
+    for (int m = 0; m < kMaxMod; ++m)
+        if (m < n_mod && pr[m]) pm |= 1u << m;
+    return (unsigned)__builtin_amdgcn_readfirstlane((int)pm);
+}
+
 // One wave per row, one lane per latent dimension (n_z <= 64).  Sampled pass: latent[m] = KL(q_m || N(0,I)) and assoc[p] =
 // KL(q_i||q_j) + KL(q_j||q_i) with latent_item's formulas, and the decoder inputs z_m = mu_m + exp(lv_m/2) eps as the head epilogue
 // forms them.  Cross pass (src >= 0): z = mu_src into every modality's decoder input.
-template <typename CT>
+// MASK (ScoreLatentArgs::present set; launch_score_latent picks the instance): an absent modality's KL column and every pair column
+// it is part of hold +0.0 and its decoder input zeros; a cross pass from an absent source feeds zeros.  Every gate is a
+// wave-uniform select of the unmasked expression (row_presence), never a product.
+template <typename CT, bool MASK>
 __global__ void __launch_bounds__(kThreads) k_score_latent(ScoreLatentArgs a) {
     const int row = blockIdx.x * kScoreRows + (threadIdx.x >> 6), d = threadIdx.x & 63;
     if (row >= a.rows) return;                     // wave-uniform: the shuffles below always run on whole waves
     const int nz = a.nz, nz2 = 2 * a.nz;
     const bool on = d < nz;
+    unsigned pm = ~0u;
+    if constexpr (MASK) pm = row_presence(a.present, row, a.n_mod);
     if (a.src >= 0) {
         if (on) {
-            const float v = a.mulv[a.src][(size_t)row * nz2 + d];
+            float v = 0.0f;
+            if (!MASK || (pm >> a.src & 1)) v = a.mulv[a.src][(size_t)row * nz2 + d];
             for (int m = 0; m < a.n_mod; ++m) reinterpret_cast<CT*>(a.Z[m])[(size_t)row * a.ldz[m] + d] = to_ct<CT>(v);
         }
         return;
@@ -3486,7 +3504,10 @@ __global__ void __launch_bounds__(kThreads) k_score_latent(ScoreLatentArgs a) {
 #pragma unroll
     for (int m = 0; m < kMaxMod; ++m) {
         mu[m] = lv[m] = 0.0f; en[m] = 1.0f;
-        if (m < a.n_mod) {
+        if (MASK && m < a.n_mod && !(pm >> m & 1)) {       // (wave-uniform)
+            if (d == 0) orow[1 + a.n_mod + m] = 0.0f;
+            if (on) reinterpret_cast<CT*>(a.Z[m])[(size_t)row * a.ldz[m] + d] = to_ct<CT>(0.0f);
+        } else if (m < a.n_mod) {
             if (on) {
                 mu[m] = a.mulv[m][(size_t)row * nz2 + d];
                 lv[m] = a.mulv[m][(size_t)row * nz2 + nz + d];
@@ -3503,7 +3524,10 @@ __global__ void __launch_bounds__(kThreads) k_score_latent(ScoreLatentArgs a) {
     for (int i = 0; i < kMaxMod; ++i) {
 #pragma unroll
         for (int j = i + 1; j < kMaxMod; ++j) {
-            if (j < a.n_mod) {
+            if (MASK && j < a.n_mod && (pm >> i & pm >> j & 1) == 0) {       // (wave-uniform)
+                if (d == 0) orow[1 + 2 * a.n_mod + p] = 0.0f;
+                ++p;
+            } else if (j < a.n_mod) {
                 const float al = lv[i] - lv[j], dl = mu[i] - mu[j];
                 const float sh = two_sinh(0.5f * al);
                 const float s = wave_sum(on ? 0.5f * (sh * sh + dl * dl * (en[i] + en[j])) : 0.0f);
@@ -3536,11 +3560,20 @@ __device__ __forceinline__ float recon_row(const float* xh, const float* x, int 
 }
 
 // Reconstruction loss of one row for one decode pass (recon_row) into the score row; the last modality's pass also forms the cost.
+// MASK: a row without modality pa or pb skips the row loop -- its x is never loaded -- and stores absent_bits; the cost loop reads
+// the stored, gated columns, so absent terms enter it as +0.0 addends.
+template <bool MASK>
 __global__ void __launch_bounds__(kThreads) k_score_rows(ScoreRowsArgs a) {
 #pragma clang fp contract(off)
     const int row = blockIdx.x * kScoreRows + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= a.rows) return;                     // wave-uniform
-    const float r = recon_row(a.xhat + (size_t)row * a.ld32, a.x + (size_t)row * a.ldx, a.n_in, a.binary, lane);
+    bool have = true;
+    if constexpr (MASK) {
+        const unsigned pm = row_presence(a.present, row, a.n_mod);
+        have = (pm >> a.pa & pm >> a.pb & 1) != 0;
+    }
+    float r = __uint_as_float(a.absent_bits);
+    if (have) r = recon_row(a.xhat + (size_t)row * a.ld32, a.x + (size_t)row * a.ldx, a.n_in, a.binary, lane);
     if (lane == 0) {
         float* orow = a.out + (size_t)row * a.k;
         orow[a.col] = r;
@@ -3557,13 +3590,18 @@ __global__ void __launch_bounds__(kThreads) k_score_rows(ScoreRowsArgs a) {
 void launch_score_latent(int compute_dtype, const ScoreLatentArgs& a, hipStream_t s) {
     if (a.rows <= 0) return;
     const dim3 grid((a.rows + kScoreRows - 1) / kScoreRows);
-    if (compute_dtype == AVAE_BF16) AVAE_LAUNCH((k_score_latent<__bf16>), grid, dim3(kThreads), 0, s, a);
-    else AVAE_LAUNCH((k_score_latent<float>), grid, dim3(kThreads), 0, s, a);
+    if (a.present) {
+        if (compute_dtype == AVAE_BF16) AVAE_LAUNCH((k_score_latent<__bf16, true>), grid, dim3(kThreads), 0, s, a);
+        else AVAE_LAUNCH((k_score_latent<float, true>), grid, dim3(kThreads), 0, s, a);
+    } else if (compute_dtype == AVAE_BF16) AVAE_LAUNCH((k_score_latent<__bf16, false>), grid, dim3(kThreads), 0, s, a);
+    else AVAE_LAUNCH((k_score_latent<float, false>), grid, dim3(kThreads), 0, s, a);
 }
 
 void launch_score_rows(const ScoreRowsArgs& a, hipStream_t s) {
     if (a.rows <= 0) return;
-    AVAE_LAUNCH(k_score_rows, dim3((a.rows + kScoreRows - 1) / kScoreRows), dim3(kThreads), 0, s, a);
+    const dim3 grid((a.rows + kScoreRows - 1) / kScoreRows);
+    if (a.present) AVAE_LAUNCH((k_score_rows<true>), grid, dim3(kThreads), 0, s, a);
+    else AVAE_LAUNCH((k_score_rows<false>), grid, dim3(kThreads), 0, s, a);
 }
 
 // ------------------------------------------------------------------ importance-weighted log-likelihoods (avae_loglik)
@@ -3571,13 +3609,24 @@ void launch_score_rows(const ScoreRowsArgs& a, hipStream_t s) {
 // eps (the caller's, or Philox keyed by (row of the whole input, dim quad | draw << 8, sample, 'iwll')), z = mu + exp(lv/2) eps
 // in fp32 as k_score_latent forms it, into the fp32 z rows the serve route reads or into every decoder input (compute dtype),
 // and r = sum_j (-z^2/2 + eps^2/2 + lv/2) = log N(z;0,I) - log q(z|x) from the fp32 z.
-template <typename CT>
+// MASK: a row without the proposal's modality draws nothing; its decoder inputs are zeros and its r is NaN.
+template <typename CT, bool MASK>
 __global__ void __launch_bounds__(kThreads) k_iw_latent(IwLatentArgs a) {
 #pragma clang fp contract(off)
     const int i = blockIdx.x * kScoreRows + (threadIdx.x >> 6), d = threadIdx.x & 63;
     if (i >= a.rows * a.kc) return;                // wave-uniform
     const int j = i / a.kc, k = a.k0 + (i - j * a.kc), nz = a.nz;
     const bool on = d < nz;
+    if constexpr (MASK) {
+        if (!__builtin_amdgcn_readfirstlane((int)a.present[(size_t)j * a.pres_ld])) {      // wave-uniform: every lane has the same j
+            if (on) {
+                if (a.z32) a.z32[(size_t)i * nz + d] = 0.0f;
+                for (int m = 0; m < a.n_zdst; ++m) reinterpret_cast<CT*>(a.Z[m])[(size_t)i * a.ldz[m] + d] = to_ct<CT>(0.0f);
+            }
+            if (d == 0) a.r[i] = __builtin_nanf("");
+            return;
+        }
+    }
     float mu = 0.0f, lv = 0.0f, e = 0.0f;
     if (on) {
         mu = a.mulv[(size_t)j * 2 * nz + d];
@@ -3608,11 +3657,18 @@ __global__ void __launch_bounds__(kThreads) k_iw_latent(IwLatentArgs a) {
 }
 
 // l_d = -recon_d of one decoded row for one modality (recon_row, as k_score_rows), one wave per (decoded row, modality),
-// modality-major.
+// modality-major.  MASK: an absent target's x row is never loaded; its l_d slot holds +0.0, which k_iw_reduce never reads.
+template <bool MASK>
 __global__ void __launch_bounds__(kThreads) k_iw_rows(IwRowsArgs a) {
     const int g = blockIdx.x * kScoreRows + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (g >= a.n_dec * a.n_mod) return;            // wave-uniform
     const int m = g / a.n_dec, i = g - m * a.n_dec;
+    if constexpr (MASK) {
+        if (!__builtin_amdgcn_readfirstlane((int)a.present[(size_t)(i / a.kc) * a.n_mod + m])) {      // wave-uniform
+            if (lane == 0) a.ell[(size_t)i * a.n_mod + m] = 0.0f;
+            return;
+        }
+    }
     const float r = recon_row(a.xhat[m] + (size_t)i * a.ldh[m], a.x[m] + (size_t)(i / a.kc) * a.ldx[m], a.n_in[m], a.binary[m], lane);
     if (lane == 0) a.ell[(size_t)i * a.n_mod + m] = -r;
 }
@@ -3631,11 +3687,27 @@ __device__ __forceinline__ void lse_merge(float& m, float& s, float m2, float s2
 // One wave per input row of the pass (proposal src): the pass's kc log-weights of the 2 + M outputs (marginal, joint, conditional
 // [src][d]), lanes strided over the samples, then a fixed-order shuffle tree, then behind the row's running state (first block: no
 // state); the last block writes max + log(sum) - log K into the caller's row.
+// MASK: a row without the proposal writes NaN into all its outputs of this proposal (last block) and keeps no state; else the joint
+// sums the present l_d only (from 0.0f, in modality order) and an absent target's conditional is NaN, its (max, sum) never merged,
+// stored or read.
+template <bool MASK>
 __global__ void __launch_bounds__(kThreads) k_iw_reduce(IwReduceArgs a) {
     constexpr int NQ = 2 + kMaxMod;
     const int j = blockIdx.x * kScoreRows + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (j >= a.rows) return;                       // wave-uniform
     const int M = a.n_mod, nq = 2 + M;
+    unsigned pm = ~0u;
+    if constexpr (MASK) {
+        pm = row_presence(a.present, j, M);
+        if (!(pm >> a.src & 1)) {
+            if (a.last && lane == 0) {
+                float* orow = a.out + (size_t)j * a.width;
+                orow[a.src] = orow[M + a.src] = __builtin_nanf("");
+                for (int d = 0; d < M; ++d) orow[2 * M + a.src * M + d] = __builtin_nanf("");
+            }
+            return;
+        }
+    }
     float mx[NQ], sm[NQ];
 #pragma unroll
     for (int q = 0; q < NQ; ++q) { mx[q] = -__builtin_inff(); sm[q] = 0.0f; }
@@ -3647,16 +3719,16 @@ __global__ void __launch_bounds__(kThreads) k_iw_reduce(IwReduceArgs a) {
 #pragma unroll
         for (int d = 0; d < kMaxMod; ++d) {
             v[2 + d] = 0.0f;
-            if (d < M) { v[2 + d] = e[d]; tot += e[d]; }
+            if (d < M && (!MASK || (pm >> d & 1))) { v[2 + d] = e[d]; tot += e[d]; }
         }
         v[0] = e[a.src] + rr;
         v[1] = tot + rr;
 #pragma unroll
-        for (int q = 0; q < NQ; ++q) if (q < nq) lse_merge(mx[q], sm[q], v[q], 1.0f);
+        for (int q = 0; q < NQ; ++q) if (q < nq && (!MASK || q < 2 || (pm >> (q - 2) & 1))) lse_merge(mx[q], sm[q], v[q], 1.0f);
     }
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
-        if (q >= nq) continue;                     // wave-uniform
+        if (q >= nq || (MASK && q >= 2 && !(pm >> (q - 2) & 1))) continue;      // wave-uniform
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
             const float m2 = __shfl_down(mx[q], o, 64), s2 = __shfl_down(sm[q], o, 64);
@@ -3669,6 +3741,10 @@ __global__ void __launch_bounds__(kThreads) k_iw_reduce(IwReduceArgs a) {
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
         if (q >= nq) continue;
+        if (MASK && q >= 2 && !(pm >> (q - 2) & 1)) {      // an absent target
+            if (a.last) orow[2 * M + a.src * M + (q - 2)] = __builtin_nanf("");
+            continue;
+        }
         float m = mx[q], s = sm[q];
         if (!a.first) {
             m = st[2 * q]; s = st[2 * q + 1];
@@ -3687,19 +3763,26 @@ void launch_iw_latent(int compute_dtype, const IwLatentArgs& a, hipStream_t s) {
     const int n = a.rows * a.kc;
     if (n <= 0) return;
     const dim3 grid((n + kScoreRows - 1) / kScoreRows);
-    if (compute_dtype == AVAE_BF16) AVAE_LAUNCH((k_iw_latent<__bf16>), grid, dim3(kThreads), 0, s, a);
-    else AVAE_LAUNCH((k_iw_latent<float>), grid, dim3(kThreads), 0, s, a);
+    if (a.present) {
+        if (compute_dtype == AVAE_BF16) AVAE_LAUNCH((k_iw_latent<__bf16, true>), grid, dim3(kThreads), 0, s, a);
+        else AVAE_LAUNCH((k_iw_latent<float, true>), grid, dim3(kThreads), 0, s, a);
+    } else if (compute_dtype == AVAE_BF16) AVAE_LAUNCH((k_iw_latent<__bf16, false>), grid, dim3(kThreads), 0, s, a);
+    else AVAE_LAUNCH((k_iw_latent<float, false>), grid, dim3(kThreads), 0, s, a);
 }
 
 void launch_iw_rows(const IwRowsArgs& a, hipStream_t s) {
     const int n = a.n_dec * a.n_mod;
     if (n <= 0) return;
-    AVAE_LAUNCH(k_iw_rows, dim3((n + kScoreRows - 1) / kScoreRows), dim3(kThreads), 0, s, a);
+    const dim3 grid((n + kScoreRows - 1) / kScoreRows);
+    if (a.present) AVAE_LAUNCH((k_iw_rows<true>), grid, dim3(kThreads), 0, s, a);
+    else AVAE_LAUNCH((k_iw_rows<false>), grid, dim3(kThreads), 0, s, a);
 }
 
 void launch_iw_reduce(const IwReduceArgs& a, hipStream_t s) {
     if (a.rows <= 0) return;
-    AVAE_LAUNCH(k_iw_reduce, dim3((a.rows + kScoreRows - 1) / kScoreRows), dim3(kThreads), 0, s, a);
+    const dim3 grid((a.rows + kScoreRows - 1) / kScoreRows);
+    if (a.present) AVAE_LAUNCH((k_iw_reduce<true>), grid, dim3(kThreads), 0, s, a);
+    else AVAE_LAUNCH((k_iw_reduce<false>), grid, dim3(kThreads), 0, s, a);
 }
 
 // ------------------------------------------------------------------ gradient latent refinement (avae_complete)

@@ -10,6 +10,9 @@ labels simply work.
 ``DeviceDataSet`` keeps the sample matrix resident in HBM with the SAME batch order (the
 permutation still comes from ``np.random.shuffle`` on the host; only the gather runs on the GPU),
 so ``train()`` feeds the step by pointer + row stride without a host->device copy per step.
+Both classes take an optional ``present`` array ([rows, M] modality presence flags of a partially paired data set): it is split
+and reshuffled with the rows, ``last_present()`` gives the presence rows of the slice handed out last, and without it nothing
+changes (the same ``np.random`` calls in the same order).
 ``extract_images`` / ``extract_jnt_fa_parms`` mirror the reference's pickle-schema readers
 (/root/reference/utils.py:142-158, 178-195) on an already-loaded ``{char_key: [arrays]}`` dict.
 """
@@ -24,11 +27,16 @@ class DataSet(object):
     """Rows (and optional labels) behind a cursor.  The private names ``_data`` and ``_num_examples`` are part of the contract:
     the reference's ``train()`` reads them (vae_assoc.py:510,543)."""
 
-    def __init__(self, data, labels=None):
+    def __init__(self, data, labels=None, present=None):
         rows = int(data.shape[0])
         if labels is not None:
             assert int(labels.shape[0]) == rows, "data.shape: %s labels.shape: %s" % (data.shape, labels.shape)
+        if present is not None:
+            if len(present.shape) != 2 or int(present.shape[0]) != rows:
+                raise ValueError("present must be [%d, M] as the rows of data, got %s" % (rows, tuple(present.shape)))
         self._data, self._labels = data, labels
+        self._present = present           # optional [rows, M] presence flags (nonzero = row n has modality m): travels with the rows
+        self._last = (0, 0)               # rows [lo, hi) of the current order that the last next_batch / next_batches returned
         self._num_examples = rows
         self._index_in_epoch = 0          # cursor: first row of the NEXT batch
         self._epochs_completed = 0
@@ -38,6 +46,16 @@ class DataSet(object):
         self._data = self._data[order]
         if self._labels is not None:
             self._labels = self._labels[order]
+        if self._present is not None:
+            self._present = self._present[order]
+
+    def last_rows(self):
+        """``(lo, hi)``: the rows of the current order that the last ``next_batch`` / ``next_batches`` returned"""
+        return self._last
+
+    def last_present(self):
+        """The presence rows of the slice that the last ``next_batch`` / ``next_batches`` returned (None without presence)"""
+        return None if self._present is None else self._present[self._last[0]:self._last[1]]
 
     def _wrap(self):
         """A batch would run past the end: the epoch is over.  ONE ``np.random.shuffle`` of ``arange(N)`` -- the RNG call the reference
@@ -50,6 +68,7 @@ class DataSet(object):
         self._index_in_epoch = 0
 
     def _slice(self, lo, hi):
+        self._last = (lo, hi)
         return self._data[lo:hi], (None if self._labels is None else self._labels[lo:hi])
 
     def next_batch(self, batch_size):
@@ -74,7 +93,7 @@ class DataSet(object):
         return d, l, n
 
 
-def construct_datasets(data, labels=None, shuffle=True, validation_ratio=.1, test_ratio=.1):
+def construct_datasets(data, labels=None, shuffle=True, validation_ratio=.1, test_ratio=.1, present=None):
     """Optional shuffle (one ``np.random.shuffle`` of ``arange(N)``), then train | validation | test at
     ``int((1 - validation_ratio - test_ratio) N)`` and ``int((1 - test_ratio) N)`` (dataset.py:45-72)."""
     rows = int(data.shape[0])
@@ -83,10 +102,12 @@ def construct_datasets(data, labels=None, shuffle=True, validation_ratio=.1, tes
         np.random.shuffle(order)
         data = data[order]
         labels = None if labels is None else labels[order]
+        present = None if present is None else present[order]
     cut_val, cut_test = int((1 - validation_ratio - test_ratio) * rows), int((1 - test_ratio) * rows)
     out = DataSets()
     for name, lo, hi in (("train", 0, cut_val), ("validation", cut_val, cut_test), ("test", cut_test, rows)):
-        setattr(out, name, DataSet(data[lo:hi, :], None if labels is None else labels[lo:hi]))
+        setattr(out, name, DataSet(data[lo:hi, :], None if labels is None else labels[lo:hi],
+                                   None if present is None else present[lo:hi]))
     return out
 
 
@@ -94,18 +115,25 @@ class DeviceDataSet(DataSet):
     """DataSet whose ``_data`` is a torch tensor on the GPU; ``next_batch`` returns device views.  The permutation still comes from
     ``np.random.shuffle`` on the host (same stream as the reference); only the gather runs on the device."""
 
-    def __init__(self, data, labels=None, device=None):
+    def __init__(self, data, labels=None, device=None, present=None):
         import torch
         if not torch.is_tensor(data):
             data = torch.as_tensor(np.ascontiguousarray(data, dtype=np.float32))
         data = data.to(device if device is not None else "cuda", dtype=torch.float32)
-        DataSet.__init__(self, data, labels)
+        if present is not None:       # presence lives next to the rows as a device uint8 tensor (0 / 1)
+            if not torch.is_tensor(present):
+                present = torch.as_tensor(np.ascontiguousarray(np.asarray(present) != 0))
+            present = (present != 0).to(device=data.device, dtype=torch.uint8)
+        DataSet.__init__(self, data, labels, present)
 
     def _take(self, order):
         import torch
-        self._data = self._data[torch.as_tensor(order, device=self._data.device)]
+        idx = torch.as_tensor(order, device=self._data.device)
+        self._data = self._data[idx]
         if self._labels is not None:
             self._labels = self._labels[order]
+        if self._present is not None:
+            self._present = self._present[idx]
 
 
 def to_device(data_sets, device=None):
@@ -113,7 +141,7 @@ def to_device(data_sets, device=None):
     out = DataSets()
     for name in ("train", "validation", "test"):
         ds = getattr(data_sets, name)
-        setattr(out, name, DeviceDataSet(ds._data, ds._labels, device))
+        setattr(out, name, DeviceDataSet(ds._data, ds._labels, device, getattr(ds, "_present", None)))
     return out
 
 

@@ -343,6 +343,36 @@ class AssocVariationalAutoEncoder(object):
         lds = (C.c_int32 * M)(*[t.stride(0) if t.shape[0] > 1 else t.shape[1] for t in ts])
         return ts, ts[0].shape[0], was_np, ptrs, lds
 
+    def _rows_args_masked(self, X, present):
+        """``_rows_args`` of the masked row calls: ``present`` [N, M] (bool or integer, array or tensor, any device; nonzero =
+        observed) gives the row count and becomes a uint8 device tensor; ``X[m] = None`` -> a NULL source (modality m absent on
+        every row).  -> (device tensors, N, was_numpy of the first given modality, ptrs, lds, presence)."""
+        M = len(self.network_architectures)
+        if len(X) != M:
+            raise ValueError("expected a list of %d modalities, got %d" % (M, len(X)))
+        p = present if torch.is_tensor(present) else torch.as_tensor(np.asarray(present))
+        if p.dim() != 2 or p.shape[1] != M:
+            raise ValueError("present must be [rows, %d], got %s" % (M, tuple(p.shape)))
+        rows = int(p.shape[0])
+        p = (p != 0).to(device=self.device, dtype=torch.uint8).contiguous()
+        ts, ptrs, lds, was_np = [], [], [], None
+        for m, (x, na) in enumerate(zip(X, self.network_architectures)):
+            if x is None:
+                ptrs.append(None)
+                lds.append(0)
+                continue
+            t, np_in = self._dev(x, int(na["n_input"]))
+            if was_np is None:
+                was_np = np_in
+            if t.shape[0] != rows:
+                raise ValueError("expected %d rows (present has %d), got %d for modality %d" % (rows, rows, t.shape[0], m))
+            ts.append(t)
+            ptrs.append(t.data_ptr())
+            lds.append(t.stride(0) if t.shape[0] > 1 else t.shape[1])
+        if was_np is None:
+            was_np = not torch.is_tensor(present)
+        return ts, rows, was_np, (C.c_void_p * M)(*ptrs), (C.c_int32 * M)(*lds), p
+
     def _batch_args(self, X, eps, n_steps=1, present=None):
         """Arguments of the training / eval entry points -> (device tensors, ptrs, lds, eps tensor or None, presence or None).
         ``present`` (the masked entry points): [batch_size * n_steps, M] (bool or integer, array or tensor, any device; nonzero =
@@ -599,8 +629,24 @@ class AssocVariationalAutoEncoder(object):
         (i<j) in lexicographic order) and, with ``cross_modal=True``, ``cross [N, M, M]``: cross[n, s, d] is the reconstruction
         loss of modality d decoded from the posterior mean of modality s.  NumPy in gives NumPy out, device tensors in give
         device tensors out."""
+        return self._score(X, None, eps, cross_modal)
+
+    def score_samples_masked(self, X, present, eps=None, cross_modal=False):
+        """``score_samples`` for partially paired rows (avae_score_masked in include/avae.h).
+
+        ``present`` is an [N, M] bool / integer array or tensor (any device), nonzero = row n has modality m; ``X[m] = None`` marks
+        a modality absent from every row.  Absent entries are never read: fill them with anything.  Returns ``score_samples``'
+        dict: ``recon`` / ``latent`` hold 0 where the row lacks the modality, ``assoc`` 0 where it lacks either of the pair, ``cost``
+        sums the terms the row has, and ``cross[n, s, d]`` is NaN where the row lacks s or d.  Every present entry except ``cost``
+        is bitwise ``score_samples``' value for the same rows and eps."""
+        return self._score(X, present, eps, cross_modal)
+
+    def _score(self, X, present, eps, cross_modal):
         M = len(self.network_architectures)
-        ts, rows, was_np, ptrs, lds = self._rows_args(X)
+        if present is None:
+            ts, rows, was_np, ptrs, lds = self._rows_args(X)
+        else:
+            ts, rows, was_np, ptrs, lds, p = self._rows_args_masked(X, present)
         e = None
         if eps is not None:
             e, _ = self._dev(eps, self.n_z)
@@ -611,9 +657,13 @@ class AssocVariationalAutoEncoder(object):
         k = C.c_int32(0)
         _capi.check(None, self._L.avae_score_width(C.byref(self._cfg), flags, C.byref(k)), "avae_score_width")
         out = torch.empty((rows, k.value), dtype=torch.float32, device=self.device)
-        if rows:
+        if rows and present is None:
             _capi.check(self._h, self._L.avae_score(self._h, ptrs, lds, rows, e.data_ptr() if e is not None else None, flags,
                                                     out.data_ptr(), self._stream()), "avae_score")
+        elif rows:
+            _capi.check(self._h, self._L.avae_score_masked(self._h, ptrs, lds, p.data_ptr(), rows,
+                                                           e.data_ptr() if e is not None else None, flags, out.data_ptr(),
+                                                           self._stream()), "avae_score_masked")
         if was_np:
             out = out.cpu().numpy()
         P = M * (M - 1) // 2
@@ -635,11 +685,25 @@ class AssocVariationalAutoEncoder(object):
         [N, M, M]``: conditional[n, s, d] estimates log p(x_d | x_s) = log E_{q_s}[p(x_d | z)], the diagonal included.  NumPy in
         gives NumPy out, device tensors in give device tensors out.  Under data parallelism each replica scores its own rows:
         there is no collective."""
+        return self._loglik(X, None, n_samples, eps)
+
+    def log_likelihood_masked(self, X, present, n_samples=64, eps=None):
+        """``log_likelihood`` for partially paired rows (avae_loglik_masked in include/avae.h).
+
+        ``present`` and ``X[m] = None`` as in ``score_samples_masked``.  Returns ``log_likelihood``'s dict: ``marginal[n, s]`` is
+        NaN where row n lacks s, ``conditional[n, s, d]`` NaN where it lacks s or d, and ``joint[n, s]`` is the log-likelihood of
+        the modalities the row has under proposal q_s (NaN where it lacks s).  A row with nothing present is all NaN."""
+        return self._loglik(X, present, n_samples, eps)
+
+    def _loglik(self, X, present, n_samples, eps):
         M = len(self.network_architectures)
         if isinstance(n_samples, bool) or not isinstance(n_samples, (int, np.integer)) or n_samples < 1:
             raise ValueError("n_samples must be an integer >= 1, got %r" % (n_samples,))
         K = int(n_samples)
-        ts, rows, was_np, ptrs, lds = self._rows_args(X)
+        if present is None:
+            ts, rows, was_np, ptrs, lds = self._rows_args(X)
+        else:
+            ts, rows, was_np, ptrs, lds, p = self._rows_args_masked(X, present)
         e = None
         if eps is not None:
             e = torch.as_tensor(np.asarray(eps, dtype=np.float32) if not torch.is_tensor(eps) else eps)
@@ -647,9 +711,13 @@ class AssocVariationalAutoEncoder(object):
                 raise ValueError("eps must be [%d, %d, %d], got %s" % (rows, K, self.n_z, tuple(e.shape)))
             e = e.to(device=self.device, dtype=torch.float32).contiguous()
         out = torch.empty((rows, 2 * M + M * M), dtype=torch.float32, device=self.device)
-        if rows:
+        if rows and present is None:
             _capi.check(self._h, self._L.avae_loglik(self._h, ptrs, lds, rows, K, e.data_ptr() if e is not None else None,
                                                      out.data_ptr(), self._stream()), "avae_loglik")
+        elif rows:
+            _capi.check(self._h, self._L.avae_loglik_masked(self._h, ptrs, lds, p.data_ptr(), rows, K,
+                                                            e.data_ptr() if e is not None else None, out.data_ptr(),
+                                                            self._stream()), "avae_loglik_masked")
         if was_np:
             out = out.cpu().numpy()
         return {"marginal": out[:, :M], "joint": out[:, M:2 * M], "conditional": out[:, 2 * M:].reshape(rows, M, M)}
@@ -803,6 +871,11 @@ def train_loop(vae_assoc, data_sets, network_architectures, batch_size, training
     hist_cap = 4096
     batch_global = batch_size * world
     lo, hi = rank * batch_size, (rank + 1) * batch_size
+    # a training split that carries presence (dataset.DataSet(present=)): masked steps, and a masked validation cost
+    masked = getattr(data_sets.train, "_present", None) is not None
+    if masked and (world > 1 or getattr(vae_assoc, "_comm_lib", False)):
+        raise RuntimeError("train() on a data set with presence (partially paired rows) runs on one replica; this model is "
+                           "data parallel (%d ranks%s)" % (world, ", library-owned collective" if world == 1 else ""))
     if world > 1:
         boot_dev = getattr(vae_assoc, "_agree_dev", "cpu" if dev is None else dev)
         np.random.seed(sync.broadcast_int(int(np.random.randint(0, 2 ** 31 - 1)), device=boot_dev))
@@ -836,6 +909,15 @@ def train_loop(vae_assoc, data_sets, network_architectures, batch_size, training
         t = batch_xs.reshape(n, batch_global, batch_xs.shape[1])[:, lo:hi]
         return t.reshape(n * batch_size, batch_xs.shape[1])
 
+    def pres(split):
+        """presence rows of the slice the split handed out last; a split without presence (a fully paired validation set next
+        to a partially paired training set) counts as all present"""
+        p = split.last_present()
+        if p is None:
+            lo_, hi_ = split.last_rows()
+            p = np.ones((hi_ - lo_, n_mod), dtype=np.uint8)
+        return p
+
     multi = hasattr(vae_assoc, "partial_fit_steps") and hasattr(vae_assoc, "cost_history")
     for epoch in range(training_epochs):
         avg_cost = 0.
@@ -846,6 +928,9 @@ def train_loop(vae_assoc, data_sets, network_architectures, batch_size, training
                 n_valid_batches = int(data_sets.validation._data.shape[0] / batch_global)
                 for i in range(n_valid_batches):
                     batch_xs, _ = data_sets.validation.next_batch(batch_global)
+                    if masked:
+                        curr_valid_cost += vae_assoc.evaluate_cost(seg(batch_xs), present=pres(data_sets.validation)) / n_valid_batches
+                        continue
                     curr_valid_cost += vae_assoc.evaluate_cost(seg(shard_run(batch_xs, 1))) / n_valid_batches
                 print("Validation cost=", "{:.9f}".format(curr_valid_cost))
                 if valid_cost is not None:
@@ -861,10 +946,16 @@ def train_loop(vae_assoc, data_sets, network_architectures, batch_size, training
             while got < chunk:
                 if multi and hasattr(data_sets.train, "next_batches"):     # a run of consecutive slices = one submission
                     batch_xs, _, n = data_sets.train.next_batches(batch_global, chunk - got)
-                    vae_assoc.partial_fit_steps(seg(shard_run(batch_xs, n)), n, return_cost=False)
+                    if masked:
+                        vae_assoc.partial_fit_steps(seg(batch_xs), n, return_cost=False, present=pres(data_sets.train))
+                    else:
+                        vae_assoc.partial_fit_steps(seg(shard_run(batch_xs, n)), n, return_cost=False)
                 else:                                             # a reference-style DataSet object
                     batch_xs, _ = data_sets.train.next_batch(batch_global)
-                    c = vae_assoc.partial_fit(seg(shard_run(batch_xs, 1)), **({"return_cost": False} if multi else {}))
+                    kw = {"return_cost": False} if multi else {}
+                    if masked:
+                        kw["present"] = pres(data_sets.train)
+                    c = vae_assoc.partial_fit(seg(shard_run(batch_xs, 1)), **kw)
                     costs.append(c)
                     n = 1
                 got += n
