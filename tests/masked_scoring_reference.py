@@ -1,7 +1,7 @@
 """fp64 reference of avae_score_masked / avae_loglik_masked (include/avae.h).
 
 The per-row columns come from ``masked_reference.per_row_terms`` and the log-likelihood arithmetic is ``ref_loglik``'s of
-tests/test_gpu_loglik.py (both imported, neither edited); absent entries are replaced by zeros before anything reads them and
+tests/scoring_reference.py (both imported, neither edited); absent entries are replaced by zeros before anything reads them and
 every gate is an ``np.where`` select, so NaN / Inf / None in an absent entry cannot reach a result.  ``ref`` is an
 ``OracleAssocVAE`` (its ``quant`` is handed through, so the same code gives the bf16 reference).
 
@@ -16,8 +16,7 @@ import numpy as np
 
 from masked_reference import patterns, per_row_terms
 from oracle import vae_assoc_oracle as O
-from test_gpu_loglik import logsumexp, ref_loglik
-from test_gpu_score import recon_rows, ref_scores
+from scoring_reference import logsumexp, recon_rows, ref_loglik, ref_scores
 
 
 def all_patterns_mask(N, M, shift=0):
@@ -114,7 +113,7 @@ def sub_model(ref, pat):
 
 
 def pattern_scores(ref, X, present, eps, cross=False):
-    """Pattern by pattern: test_gpu_score.ref_scores of the sub-model, its values on the pattern's rows scattered into full-width
+    """Pattern by pattern: scoring_reference.ref_scores of the sub-model, its values on the pattern's rows scattered into full-width
     columns (NaN marks what the pattern does not define, every column of a row with nothing present included)."""
     p, Xf = _fold(ref, X, present)
     N, M = p.shape
@@ -140,7 +139,7 @@ def pattern_scores(ref, X, present, eps, cross=False):
 
 
 def pattern_loglik(ref, X, present, eps):
-    """Pattern by pattern: test_gpu_loglik.ref_loglik of the sub-model, its values on the pattern's rows scattered (NaN elsewhere)."""
+    """Pattern by pattern: scoring_reference.ref_loglik of the sub-model, its values on the pattern's rows scattered (NaN elsewhere)."""
     p, Xf = _fold(ref, X, present)
     N, M = p.shape
     out = {"marginal": np.full((N, M), np.nan), "joint": np.full((N, M), np.nan), "conditional": np.full((N, M, M), np.nan)}

@@ -8,8 +8,8 @@ import pytest
 import torch
 
 from conftest import shadow_err, synth_batch
-from oracle import vae_assoc_oracle as O
-from test_gpu_score import MODELS, build_pair, c1_like, recon_rows
+from scoring_reference import logsumexp, ref_loglik
+from test_gpu_score import MODELS, build_pair, c1_like
 
 pytestmark = pytest.mark.gpu
 
@@ -21,34 +21,6 @@ def V():
     from vae_assoc_amd import vae_assoc
     assert torch.cuda.is_available()
     return vae_assoc
-
-
-def logsumexp(a, axis):
-    m = np.max(a, axis=axis, keepdims=True)
-    return np.squeeze(m, axis) + np.log(np.sum(np.exp(a - m), axis=axis))
-
-
-def ref_loglik(ref, X, eps):
-    """The definitions of include/avae.h, from O.encode / O.decode and a float64 log-sum-exp.  eps: [N, K, n_z].
-    Per proposal s: z_k = mu_s + exp(lv_s/2) eps_k, l_d(z) = -recon_d(x_d, dec_d(z)), r_k = sum(-z^2/2 + eps^2/2 + lv_s/2);
-    marginal[s] = LSE_k(l_s + r) - log K, joint[s] = LSE_k(sum_d l_d + r) - log K, conditional[s, d] = LSE_k l_d - log K."""
-    archs, binary, act, q = ref.network_architectures, ref.binary, ref.act, ref.quant
-    X = [np.asarray(x, np.float64) for x in X]
-    eps = np.asarray(eps, np.float64)
-    N, K, nz = eps.shape
-    M = len(archs)
-    marginal, joint, cond = np.zeros((N, M)), np.zeros((N, M)), np.zeros((N, M, M))
-    for s in range(M):
-        mu, lv = O.encode(archs[s], ref.params[s], X[s], act, q)[:2]
-        z = mu[:, None, :] + np.exp(0.5 * lv)[:, None, :] * eps                       # [N, K, n_z]
-        r = np.sum(-0.5 * z ** 2 + 0.5 * eps ** 2 + 0.5 * lv[:, None, :], axis=2)     # [N, K]
-        ell = np.stack([-recon_rows(np.repeat(X[d], K, axis=0),
-                                    O.decode(archs[d], ref.params[d], z.reshape(N * K, nz), act, binary[d], q)[0],
-                                    binary[d]).reshape(N, K) for d in range(M)], axis=2)    # [N, K, M]
-        marginal[:, s] = logsumexp(ell[:, :, s] + r, 1) - np.log(K)
-        joint[:, s] = logsumexp(ell.sum(2) + r, 1) - np.log(K)
-        cond[:, s, :] = logsumexp(ell, 1) - np.log(K)
-    return {"marginal": marginal, "joint": joint, "conditional": cond}
 
 
 def assert_columns(got, want, tol, what=""):

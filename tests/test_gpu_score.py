@@ -1,7 +1,6 @@
 """score_samples / avae_score on a real MI355X: per-row cost terms and cross-modal prediction error against the CPU oracle
 (fp64, and quant='bf16' for the bf16 path), any row count, the identity with evaluate_cost, and no side effects on training."""
 import ctypes as C
-from itertools import combinations
 
 import numpy as np
 import pytest
@@ -9,6 +8,7 @@ import torch
 
 from conftest import make_arch, shadow_err, synth_batch
 from oracle import vae_assoc_oracle as O
+from scoring_reference import recon_rows, ref_scores
 
 pytestmark = pytest.mark.gpu
 
@@ -38,38 +38,6 @@ def build_pair(V, archs, binary, weights, lam, act, B, dtype, seed=5, quant=None
     model.set_params(p0)
     ref = O.OracleAssocVAE(archs, binary, act, weights, lam, 1e-3, B, params_flat=p0.astype(np.float64), quant=quant)
     return model, ref
-
-
-def recon_rows(x, xhat, binary):
-    if binary:
-        return -np.sum(x * np.log(1e-3 + xhat) + (1 - x) * np.log(1e-3 + 1 - xhat), axis=1)
-    return 0.5 * np.sum((x - xhat) ** 2, axis=1)
-
-
-def ref_scores(ref, X, eps, cross=False):
-    """Per-row terms from O.forward / O.encode / O.decode (the definitions of include/avae.h)."""
-    archs, binary, act, q = ref.network_architectures, ref.binary, ref.act, ref.quant
-    X = [np.asarray(x, np.float64) for x in X]
-    fw = O.forward(archs, ref.params, X, np.asarray(eps, np.float64), binary, act, q)
-    recon = np.stack([recon_rows(x, f["xhat"], b) for x, f, b in zip(X, fw, binary)], 1)
-    latent = np.stack([-0.5 * np.sum(1 + f["lv"] - f["mu"] ** 2 - np.exp(f["lv"]), 1) for f in fw], 1)
-    assoc = [np.sum(0.5 * (np.exp(fw[i]["lv"] - fw[j]["lv"]) + np.exp(fw[j]["lv"] - fw[i]["lv"]) - 2.0
-                           + (fw[i]["mu"] - fw[j]["mu"]) ** 2 * (np.exp(-fw[i]["lv"]) + np.exp(-fw[j]["lv"]))), 1)
-             for i, j in combinations(range(len(archs)), 2)]
-    assoc = np.stack(assoc, 1) if assoc else np.zeros((X[0].shape[0], 0))
-    w = np.asarray(ref.weights, np.float64)
-    out = {"recon": recon, "latent": latent, "assoc": assoc,
-           "cost": ((recon + latent) * w).sum(1) + ref.assoc_lambda * assoc.sum(1)}
-    if cross:
-        M = len(archs)
-        mus = [f["mu"] for f in fw]
-        cr = np.zeros((X[0].shape[0], M, M))
-        for s in range(M):
-            for d in range(M):
-                xh = O.decode(archs[d], ref.params[d], mus[s], act, binary[d], q)[0]
-                cr[:, s, d] = recon_rows(X[d], xh, binary[d])
-        out["cross"] = cr
-    return out
 
 
 def assert_columns(got, want, tol, what=""):

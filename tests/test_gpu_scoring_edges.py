@@ -12,9 +12,9 @@ import torch
 
 from conftest import make_arch, synth_batch
 from oracle import vae_assoc_oracle as O
-from test_gpu_loglik import assert_columns, logsumexp, ref_loglik
+from scoring_reference import logsumexp, recon_rows, ref_loglik, ref_scores
+from test_gpu_loglik import assert_columns
 from test_gpu_parity import check_step_parity
-from test_gpu_score import recon_rows, ref_scores
 
 pytestmark = pytest.mark.gpu
 

@@ -1,5 +1,5 @@
 """CPU checks of the importance-weighted log-likelihoods: avae_loglik is declared, exported and bound, log_likelihood is part of
-the model surface, and the NumPy reference of test_gpu_loglik meets two closed forms on the oracle (the K = 1 identity with
+the model surface, and the NumPy reference of scoring_reference meets two closed forms on the oracle (the K = 1 identity with
 O.forward's reconstruction, and Jensen's inequality)."""
 import inspect
 import os
@@ -10,8 +10,7 @@ import pytest
 
 from conftest import ROOT, make_arch, synth_batch
 from oracle import vae_assoc_oracle as O
-from test_gpu_loglik import logsumexp, ref_loglik
-from test_gpu_score import recon_rows
+from scoring_reference import logsumexp, recon_rows, ref_loglik
 
 
 @pytest.fixture(scope="module")

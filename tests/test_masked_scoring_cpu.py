@@ -15,8 +15,7 @@ from masked_reference import masked_cost_and_grads, masked_cost_from_rows
 from masked_scoring_reference import (all_patterns_mask, has_every_pattern, pattern_loglik, pattern_scores, ref_loglik_masked,
                                       ref_scores_masked)
 from oracle import vae_assoc_oracle as O
-from test_gpu_loglik import ref_loglik
-from test_gpu_score import ref_scores
+from scoring_reference import ref_loglik, ref_scores
 from vae_assoc_amd import dataset
 
 CASES = [

@@ -115,6 +115,12 @@ def dp_train_step_bucketed(replica, sync, buckets, X_local, eps_local=None):
     ``_grad_tensor()`` and ``_apply_bucket(b, want_cost)``; the library-owned RCCL pipeline (avae_host.hip::dp_step) is this
     schedule on two HIP streams."""
     replica._stage(X_local, eps_local)
+    return dp_bucket_schedule(replica, sync, buckets)
+
+
+def dp_bucket_schedule(replica, sync, buckets, want_cost=True):
+    """The schedule of ``dp_train_step_bucketed`` on a batch the replica has already staged (``partial_fit_steps`` stages several
+    at once and runs this per step).  -> the step's cost, or None without ``want_cost`` (no host synchronise then)."""
     g = replica._grad_tensor()
     pending = []
     for b, ranges in enumerate(buckets):
@@ -124,5 +130,5 @@ def dp_train_step_bucketed(replica, sync, buckets, X_local, eps_local=None):
     for b in range(len(buckets)):
         for w in pending[b]:
             w.wait()
-        cost = replica._apply_bucket(b, b == len(buckets) - 1)
+        cost = replica._apply_bucket(b, want_cost and b == len(buckets) - 1)
     return cost

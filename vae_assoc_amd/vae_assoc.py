@@ -26,7 +26,8 @@ import numpy as np
 import torch
 
 from . import _capi
-from .parallel import GradSync, dp_train_step_bucketed
+from ._marshal import dev_array, dev_dense, dev_dense3, dev_flags, dev_modalities, dev_row_args, ld_of, ptr
+from .parallel import GradSync, dp_bucket_schedule, dp_train_step_bucketed
 
 _ARCH_KEYS = ("scope", "hidden_conv", "n_hidden_recog_1", "n_hidden_recog_2",
               "n_hidden_gener_1", "n_hidden_gener_2", "n_input", "n_z")
@@ -85,6 +86,183 @@ def layer_shapes(na):
     return shapes
 
 
+def build_config(network_architectures, binary, weights, transfer_fct, assoc_lambda, learning_rate, batch_size, compute_dtype,
+                 seed, use_graph, comm, comm_buckets, wire_dtype, placement):
+    """The constructor's arguments -> (``_capi.Config``, binary list, weights list, activation name, comm): every field but the
+    workspace and the collective's, after every check of the constructor in the constructor's order.  ``placement()`` ->
+    (device index, world, rank) is called where the constructor opens the device and the process group, between the
+    architecture checks and the collective's, so an input with several faults raises the same one first.  Pure host code:
+    needs neither a GPU nor libavae.so."""
+    n_mod = len(network_architectures)
+    # check if binary data (vae_assoc.py:31-35)
+    if type(binary) is list:
+        assert len(binary) == n_mod
+    else:
+        binary = [binary] * n_mod
+    if type(weights) is list:              # :37-41
+        assert len(weights) == n_mod
+    else:
+        weights = [weights] * n_mod
+    act = _act_name(transfer_fct)
+    batch_size = int(batch_size)
+    n_z = int(network_architectures[0]["n_z"])       # :89
+    if n_mod > _capi.AVAE_MAX_MODALITIES:
+        raise ValueError("at most %d modalities" % _capi.AVAE_MAX_MODALITIES)
+    for na in network_architectures:
+        if int(na["n_z"]) != n_z:
+            raise ValueError("all modalities must share n_z (the reference builds one eps of modality 0's n_z, :89-91)")
+        if na.get("hidden_conv") and int(na["n_input"]) != 784:
+            raise ValueError("hidden_conv=True needs n_input = 784: the reference's branch is hard-wired to 28x28 images")
+    if compute_dtype not in _capi.DTYPE_IDS:
+        raise ValueError("compute_dtype must be 'bf16' or 'fp32'")
+    device_index, world, rank = placement()
+    if comm not in (None, "library", "torch", "ipc"):
+        raise ValueError("comm must be None, 'library', 'ipc' or 'torch'")
+    if comm is None:
+        comm = "torch"
+    if comm_buckets not in (1, 2):
+        raise ValueError("comm_buckets must be 1 or 2")
+    if wire_dtype not in _capi.DTYPE_IDS:
+        raise ValueError("wire_dtype must be 'fp32' or 'bf16'")
+
+    cfg = _capi.Config()
+    cfg.abi_version = _capi.AVAE_ABI_VERSION
+    cfg.n_modalities = n_mod
+    for m, na in enumerate(network_architectures):
+        hs = hidden_sizes(na)
+        if len(hs) > _capi.AVAE_MAX_HIDDEN:
+            raise ValueError("at most %d hidden layers" % _capi.AVAE_MAX_HIDDEN)
+        cfg.mod[m].n_input = int(na["n_input"])
+        cfg.mod[m].n_hidden_layers = len(hs)
+        for k, hsz in enumerate(hs):
+            cfg.mod[m].n_hidden[k] = hsz
+        cfg.mod[m].binary = 1 if binary[m] else 0
+        cfg.mod[m].weight = float(weights[m])
+        cfg.mod[m].hidden_conv = 1 if na.get("hidden_conv") else 0
+        if na.get("hidden_conv"):
+            if not binary[m]:
+                raise ValueError("hidden_conv=True needs a binary modality (the reference's non-binary conv decoder "
+                                 "is shape-broken, vae_assoc.py:299)")
+            cfg.mod[m].n_hidden_layers = 2
+            cfg.mod[m].n_hidden[0], cfg.mod[m].n_hidden[1] = int(na["n_hidden_recog_1"]), int(na["n_hidden_recog_2"])
+            cfg.mod[m].conv_gener[0], cfg.mod[m].conv_gener[1] = int(na["n_hidden_gener_1"]), int(na["n_hidden_gener_2"])
+    cfg.n_z = n_z
+    cfg.batch_size = batch_size
+    cfg.batch_global = batch_size * world
+    cfg.row_offset = rank * batch_size
+    cfg.activation = _capi.ACT_IDS[act]
+    cfg.compute_dtype = _capi.DTYPE_IDS[compute_dtype]
+    cfg.device = device_index
+    cfg.use_graph = 1 if use_graph else 0
+    cfg.assoc_lambda = float(assoc_lambda)
+    cfg.learning_rate = float(learning_rate)
+    cfg.beta1 = cfg.beta2 = cfg.adam_eps = 0.0          # -> TF-1 AdamOptimizer defaults
+    cfg.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    cfg.comm_buckets = comm_buckets
+    cfg.wire_dtype = _capi.DTYPE_IDS[wire_dtype]
+    return cfg, binary, weights, act, comm
+
+
+def initial_params(network_architectures, seed):
+    """The initial flat parameter vector: xavier-uniform weights, zero biases (vae_assoc.py:185-215,257-300), drawn with NumPy
+    from ``seed`` in ``layer_shapes``' order.  Pure host code."""
+    rng = np.random.RandomState(int(seed) & 0x7FFFFFFF)
+    flat = []
+    for na in network_architectures:
+        for name, shp in layer_shapes(na):
+            if len(shp) == 2:
+                flat.append(xavier_init(shp[0], shp[1], rng=rng).reshape(-1))
+            elif len(shp) == 4 and name.startswith("enc_C"):
+                # weight_variable (vae_assoc.py:471-473): truncated_normal(stddev=0.1)
+                w = rng.standard_normal(shp)
+                while np.any(np.abs(w) > 2):
+                    bad = np.abs(w) > 2
+                    w[bad] = rng.standard_normal(int(bad.sum()))
+                flat.append((0.1 * w).astype(np.float32).reshape(-1))
+            elif len(shp) == 4:
+                # deconv.py:83-84: xavier over (out_depth*k*k, in_depth*k*k)
+                kk = shp[0] * shp[1]
+                lim = np.sqrt(6.0 / (shp[2] * kk + shp[3] * kk))
+                flat.append(rng.uniform(-lim, lim, size=shp).astype(np.float32).reshape(-1))
+            else:
+                flat.append(np.zeros(shp, dtype=np.float32))
+    return np.concatenate(flat)
+
+
+def create_replica(L, cfg, sync, comm, device, agree_dev):
+    """Workspace + ``avae_create`` with the collective ``comm`` brought up -> (handle, comm in use, workspace tensor, buckets).
+
+    Every step that needs the other ranks is agreed between them (``sync.sum_scalar``), in one fixed order on every rank: the
+    RCCL probe, the ncclUniqueId broadcast, the verdict on ``avae_create``, the hipIpc handle all-gather, the verdict on the
+    attach.  A collective that did not come up on every rank is dropped by all of them for 'torch'."""
+    world = sync.world_size if sync else 1
+    rank = sync.rank if sync else 0
+    if comm == "library" and world > 1:
+        # ncclCommInitRank below is collective: a rank that cannot even load RCCL would leave the others waiting inside it.  Every
+        # rank therefore probes the loader first (drawing an id is the cheapest call that needs it) and the ranks agree: all, or
+        # the torch.distributed collective on the same buckets for everybody.
+        probe = (C.c_uint8 * 128)()
+        ok = 1.0 if L.avae_comm_unique_id(probe) == 0 else 0.0
+        if sync.sum_scalar(ok, agree_dev) < world:
+            if rank == 0:
+                print("[vae_assoc_amd] RCCL cannot be loaded on every rank: gradient all-reduce through torch.distributed")
+            comm = "torch"
+    if comm == "library":
+        # bootstrap only: rank 0 draws the ncclUniqueId, torch.distributed hands it round; the communicator itself is the library's
+        idb = (C.c_uint8 * 128)()
+        if rank == 0:
+            _capi.check(None, L.avae_comm_unique_id(idb), "avae_comm_unique_id")
+        raw = sync.broadcast_bytes(bytes(idb), 128, device=agree_dev) if sync is not None else bytes(idb)
+        cfg.use_comm, cfg.world_size, cfg.rank = _capi.COMM_RCCL, world, rank
+        for i in range(128):
+            cfg.nccl_id[i] = raw[i]
+    elif comm == "ipc":
+        cfg.use_comm, cfg.world_size, cfg.rank = _capi.COMM_IPC, world, rank
+    # data-parallel buckets (host-only query): [[(offset, count), ...] per bucket]
+    nb, nr = C.c_int32(0), (C.c_int32 * 2)()
+    offs, cnts = (C.c_int64 * 2)(), (C.c_int64 * 2)()
+    _capi.check(None, L.avae_dp_plan(C.byref(cfg), C.byref(nb), nr, offs, cnts), "avae_dp_plan")
+    buckets = [[(int(offs[b]), int(cnts[b]))] for b in range(nb.value)]      # ONE contiguous range per bucket
+    nbytes = C.c_size_t(0)
+    _capi.check(None, L.avae_workspace_bytes(C.byref(cfg), C.byref(nbytes)), "avae_workspace_bytes")
+    # PyTorch is the device allocator: one uint8 tensor holds the whole replica state
+    ws = torch.empty(nbytes.value + 256, dtype=torch.uint8, device=device)
+    base = ws.data_ptr()
+    cfg.workspace = base + (-base) % 256
+    cfg.workspace_bytes = nbytes.value
+    h = C.c_void_p()
+    torch.cuda.synchronize(device)
+    rc = L.avae_create(C.byref(cfg), C.byref(h))
+    if comm in ("library", "ipc") and world > 1:
+        # Bring-up is agreed between the ranks at every collective step: a communicator / exchange that came up on some ranks
+        # only is of no use to any.  RCCL: ncclCommInitRank ran inside avae_create.  IPC: every rank that created its replica
+        # exports its exchange block, the handles go round (all_gather), every rank maps its peers' blocks.
+        ok = 1.0 if rc == 0 else 0.0
+        all_ok = sync.sum_scalar(ok, agree_dev) >= world
+        if all_ok and comm == "ipc":
+            mine = (C.c_uint8 * _capi.AVAE_IPC_HANDLE_BYTES)()
+            ok = 1.0 if L.avae_comm_ipc_handle(h, mine) == 0 else 0.0
+            blob = sync.all_gather_bytes(bytes(mine), _capi.AVAE_IPC_HANDLE_BYTES, device=agree_dev)
+            if ok:
+                buf = (C.c_uint8 * len(blob)).from_buffer_copy(blob)
+                ok = 1.0 if L.avae_comm_ipc_attach(h, buf) == 0 else 0.0
+                if not ok:
+                    print("[vae_assoc_amd] rank %d: %s" % (rank, L.avae_last_error(h).decode("utf-8", "replace")))
+            all_ok = sync.sum_scalar(ok, agree_dev) >= world
+        if not all_ok:
+            if rc == 0:
+                L.avae_destroy(h)
+            if rank == 0:
+                print("[vae_assoc_amd] the library's %s collective did not come up on every rank: gradient all-reduce "
+                      "through torch.distributed" % ("RCCL" if comm == "library" else "hipIpc"))
+            comm = "torch"
+            cfg.use_comm = _capi.COMM_NONE
+            h = C.c_void_p()
+            rc = L.avae_create(C.byref(cfg), C.byref(h))
+    _capi.check(None, rc, "avae_create")
+    return h, comm, ws, buckets
+
+
 class AssocVariationalAutoEncoder(object):
     """Associative VAE over M sensory modalities, trained on one MI355X (or one per rank).
 
@@ -113,160 +291,29 @@ class AssocVariationalAutoEncoder(object):
                  assoc_lambda=1.0, learning_rate=0.001, batch_size=100, *, compute_dtype="bf16",
                  device=None, seed=0, use_graph=True, data_parallel=False, process_group=None, comm=None,
                  comm_buckets=2, wire_dtype="fp32"):
+        def placement():
+            if not torch.cuda.is_available():
+                raise RuntimeError("vae_assoc_amd needs a HIP device (MI355X / gfx950); there is no CPU fallback")
+            dev = torch.cuda.current_device() if device is None else device
+            self.device = torch.device("cuda", dev if isinstance(dev, int) else torch.device(dev).index or 0)
+            self._sync = GradSync(process_group) if data_parallel else None
+            return (self.device.index,) + ((self._sync.world_size, self._sync.rank) if self._sync else (1, 0))
+
+        cfg, self.binary, self.weights, _act, comm = build_config(
+            network_architectures, binary, weights, transfer_fct, assoc_lambda, learning_rate, batch_size, compute_dtype, seed,
+            use_graph, comm, comm_buckets, wire_dtype, placement)
         self.network_architectures = network_architectures
         self.assoc_lambda = assoc_lambda
-        n_mod = len(network_architectures)
-        # check if binary data (vae_assoc.py:31-35)
-        if type(binary) is list:
-            assert len(binary) == n_mod
-            self.binary = binary
-        else:
-            self.binary = [binary] * n_mod
-        if type(weights) is list:              # :37-41
-            assert len(weights) == n_mod
-            self.weights = weights
-        else:
-            self.weights = [weights] * n_mod
         self.transfer_fct = transfer_fct
-        self._act = _act_name(transfer_fct)
         self.learning_rate = learning_rate
-        self.batch_size = int(batch_size)
-        self.n_z = int(network_architectures[0]["n_z"])       # :89
-        if n_mod > _capi.AVAE_MAX_MODALITIES:
-            raise ValueError("at most %d modalities" % _capi.AVAE_MAX_MODALITIES)
-        for na in network_architectures:
-            if int(na["n_z"]) != self.n_z:
-                raise ValueError("all modalities must share n_z (the reference builds one eps of modality 0's n_z, :89-91)")
-            if na.get("hidden_conv") and int(na["n_input"]) != 784:
-                raise ValueError("hidden_conv=True needs n_input = 784: the reference's branch is hard-wired to 28x28 images")
-        if compute_dtype not in _capi.DTYPE_IDS:
-            raise ValueError("compute_dtype must be 'bf16' or 'fp32'")
         self.compute_dtype = compute_dtype
-
-        if not torch.cuda.is_available():
-            raise RuntimeError("vae_assoc_amd needs a HIP device (MI355X / gfx950); there is no CPU fallback")
-        if device is None:
-            device = torch.cuda.current_device()
-        self.device = torch.device("cuda", device if isinstance(device, int) else torch.device(device).index or 0)
-        self._sync = GradSync(process_group) if data_parallel else None
-        world = self._sync.world_size if self._sync else 1
-        rank = self._sync.rank if self._sync else 0
-        if comm not in (None, "library", "torch", "ipc"):
-            raise ValueError("comm must be None, 'library', 'ipc' or 'torch'")
-        if comm is None:
-            comm = "torch"
-        if comm_buckets not in (1, 2):
-            raise ValueError("comm_buckets must be 1 or 2")
-        if wire_dtype not in _capi.DTYPE_IDS:
-            raise ValueError("wire_dtype must be 'fp32' or 'bf16'")
-        self._comm = comm
-        self._comm_lib = comm in ("library", "ipc")
-        self._wire_bf16 = _capi.DTYPE_IDS[wire_dtype] == 1
-
-        cfg = _capi.Config()
-        cfg.abi_version = _capi.AVAE_ABI_VERSION
-        cfg.n_modalities = n_mod
-        for m, na in enumerate(network_architectures):
-            hs = hidden_sizes(na)
-            if len(hs) > _capi.AVAE_MAX_HIDDEN:
-                raise ValueError("at most %d hidden layers" % _capi.AVAE_MAX_HIDDEN)
-            cfg.mod[m].n_input = int(na["n_input"])
-            cfg.mod[m].n_hidden_layers = len(hs)
-            for k, hsz in enumerate(hs):
-                cfg.mod[m].n_hidden[k] = hsz
-            cfg.mod[m].binary = 1 if self.binary[m] else 0
-            cfg.mod[m].weight = float(self.weights[m])
-            cfg.mod[m].hidden_conv = 1 if na.get("hidden_conv") else 0
-            if na.get("hidden_conv"):
-                if not self.binary[m]:
-                    raise ValueError("hidden_conv=True needs a binary modality (the reference's non-binary conv decoder "
-                                     "is shape-broken, vae_assoc.py:299)")
-                cfg.mod[m].n_hidden_layers = 2
-                cfg.mod[m].n_hidden[0], cfg.mod[m].n_hidden[1] = int(na["n_hidden_recog_1"]), int(na["n_hidden_recog_2"])
-                cfg.mod[m].conv_gener[0], cfg.mod[m].conv_gener[1] = int(na["n_hidden_gener_1"]), int(na["n_hidden_gener_2"])
-        cfg.n_z = self.n_z
-        cfg.batch_size = self.batch_size
-        cfg.batch_global = self.batch_size * world
-        cfg.row_offset = rank * self.batch_size
-        cfg.activation = _capi.ACT_IDS[self._act]
-        cfg.compute_dtype = _capi.DTYPE_IDS[compute_dtype]
-        cfg.device = self.device.index
-        cfg.use_graph = 1 if use_graph else 0
-        cfg.assoc_lambda = float(assoc_lambda)
-        cfg.learning_rate = float(learning_rate)
-        cfg.beta1 = cfg.beta2 = cfg.adam_eps = 0.0          # -> TF-1 AdamOptimizer defaults
-        cfg.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-
-        cfg.comm_buckets = comm_buckets
-        cfg.wire_dtype = _capi.DTYPE_IDS[wire_dtype]
+        self.batch_size, self.n_z = cfg.batch_size, cfg.n_z
+        self._widths = tuple(int(na["n_input"]) for na in network_architectures)
         L = _capi.lib()
-        agree_dev = self.device if (self._sync is not None and self._sync.backend == "nccl") else "cpu"
-        self._agree_dev = agree_dev
-        if self._comm == "library" and world > 1:
-            # ncclCommInitRank below is collective: a rank that cannot even load RCCL would leave the others waiting inside it.  Every
-            # rank therefore probes the loader first (drawing an id is the cheapest call that needs it) and the ranks agree: all, or
-            # the torch.distributed collective on the same buckets for everybody.
-            probe = (C.c_uint8 * 128)()
-            ok = 1.0 if L.avae_comm_unique_id(probe) == 0 else 0.0
-            if self._sync.sum_scalar(ok, agree_dev) < world:
-                if rank == 0:
-                    print("[vae_assoc_amd] RCCL cannot be loaded on every rank: gradient all-reduce through torch.distributed")
-                self._comm, self._comm_lib = "torch", False
-        if self._comm == "library":
-            # bootstrap only: rank 0 draws the ncclUniqueId, torch.distributed hands it round; the communicator itself is the library's
-            idb = (C.c_uint8 * 128)()
-            if rank == 0:
-                _capi.check(None, L.avae_comm_unique_id(idb), "avae_comm_unique_id")
-            raw = self._sync.broadcast_bytes(bytes(idb), 128, device=agree_dev) if self._sync is not None else bytes(idb)
-            cfg.use_comm, cfg.world_size, cfg.rank = _capi.COMM_RCCL, world, rank
-            for i in range(128):
-                cfg.nccl_id[i] = raw[i]
-        elif self._comm == "ipc":
-            cfg.use_comm, cfg.world_size, cfg.rank = _capi.COMM_IPC, world, rank
-        # data-parallel buckets (host-only query): [[(offset, count), ...] per bucket]
-        nb, nr = C.c_int32(0), (C.c_int32 * 2)()
-        offs, cnts = (C.c_int64 * 2)(), (C.c_int64 * 2)()
-        _capi.check(None, L.avae_dp_plan(C.byref(cfg), C.byref(nb), nr, offs, cnts), "avae_dp_plan")
-        self._buckets = [[(int(offs[b]), int(cnts[b]))] for b in range(nb.value)]      # ONE contiguous range per bucket
-        nbytes = C.c_size_t(0)
-        _capi.check(None, L.avae_workspace_bytes(C.byref(cfg), C.byref(nbytes)), "avae_workspace_bytes")
-        # PyTorch is the device allocator: one uint8 tensor holds the whole replica state
-        self._ws = torch.empty(nbytes.value + 256, dtype=torch.uint8, device=self.device)
-        base = self._ws.data_ptr()
-        self._ws_off = (-base) % 256
-        cfg.workspace = base + self._ws_off
-        cfg.workspace_bytes = nbytes.value
+        self._agree_dev = self.device if (self._sync is not None and self._sync.backend == "nccl") else "cpu"
+        h, self._comm, self._ws, self._buckets = create_replica(L, cfg, self._sync, comm, self.device, self._agree_dev)
+        self._comm_lib = self._comm in ("library", "ipc")
         self._cfg = cfg
-        h = C.c_void_p()
-        torch.cuda.synchronize(self.device)
-        rc = L.avae_create(C.byref(cfg), C.byref(h))
-        if self._comm_lib and world > 1:
-            # Bring-up is agreed between the ranks at every collective step: a communicator / exchange that came up on some ranks
-            # only is of no use to any.  RCCL: ncclCommInitRank ran inside avae_create.  IPC: every rank that created its replica
-            # exports its exchange block, the handles go round (all_gather), every rank maps its peers' blocks.
-            ok = 1.0 if rc == 0 else 0.0
-            all_ok = self._sync.sum_scalar(ok, agree_dev) >= world
-            if all_ok and self._comm == "ipc":
-                mine = (C.c_uint8 * _capi.AVAE_IPC_HANDLE_BYTES)()
-                ok = 1.0 if L.avae_comm_ipc_handle(h, mine) == 0 else 0.0
-                blob = self._sync.all_gather_bytes(bytes(mine), _capi.AVAE_IPC_HANDLE_BYTES, device=agree_dev)
-                if ok:
-                    buf = (C.c_uint8 * len(blob)).from_buffer_copy(blob)
-                    ok = 1.0 if L.avae_comm_ipc_attach(h, buf) == 0 else 0.0
-                    if not ok:
-                        print("[vae_assoc_amd] rank %d: %s" % (rank, L.avae_last_error(h).decode("utf-8", "replace")))
-                all_ok = self._sync.sum_scalar(ok, agree_dev) >= world
-            if not all_ok:
-                if rc == 0:
-                    L.avae_destroy(h)
-                if rank == 0:
-                    print("[vae_assoc_amd] the library's %s collective did not come up on every rank: gradient all-reduce "
-                          "through torch.distributed" % ("RCCL" if self._comm == "library" else "hipIpc"))
-                self._comm, self._comm_lib = "torch", False
-                cfg.use_comm = _capi.COMM_NONE
-                h = C.c_void_p()
-                rc = L.avae_create(C.byref(cfg), C.byref(h))
-        _capi.check(None, rc, "avae_create")
         self._h = h
         self._L = L
         n = C.c_size_t(0)
@@ -274,31 +321,9 @@ class AssocVariationalAutoEncoder(object):
         self.n_params = n.value
         gp, gn = C.c_void_p(), C.c_size_t(0)
         _capi.check(h, L.avae_grad_buffer(h, C.byref(gp), C.byref(gn)), "avae_grad_buffer")
-        goff = gp.value - base
+        goff = gp.value - self._ws.data_ptr()
         self._grad_view = self._ws[goff:goff + 4 * gn.value].view(torch.float32)
-
-        # initial weights: xavier-uniform, zero biases (vae_assoc.py:185-215,257-300)
-        rng = np.random.RandomState(int(seed) & 0x7FFFFFFF)
-        flat = []
-        for na in network_architectures:
-            for name, shp in layer_shapes(na):
-                if len(shp) == 2:
-                    flat.append(xavier_init(shp[0], shp[1], rng=rng).reshape(-1))
-                elif len(shp) == 4 and name.startswith("enc_C"):
-                    # weight_variable (vae_assoc.py:471-473): truncated_normal(stddev=0.1)
-                    w = rng.standard_normal(shp)
-                    while np.any(np.abs(w) > 2):
-                        bad = np.abs(w) > 2
-                        w[bad] = rng.standard_normal(int(bad.sum()))
-                    flat.append((0.1 * w).astype(np.float32).reshape(-1))
-                elif len(shp) == 4:
-                    # deconv.py:83-84: xavier over (out_depth*k*k, in_depth*k*k)
-                    kk = shp[0] * shp[1]
-                    lim = np.sqrt(6.0 / (shp[2] * kk + shp[3] * kk))
-                    flat.append(rng.uniform(-lim, lim, size=shp).astype(np.float32).reshape(-1))
-                else:
-                    flat.append(np.zeros(shp, dtype=np.float32))
-        self.set_params(np.concatenate(flat))
+        self.set_params(initial_params(network_architectures, seed))
 
     # ------------------------------------------------------------------ plumbing
     def __del__(self):
@@ -312,115 +337,39 @@ class AssocVariationalAutoEncoder(object):
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
-    def _dev(self, a, cols):
-        """-> (float32 device tensor [rows, cols] with unit column stride, was_numpy)."""
-        was_np = not torch.is_tensor(a)
-        t = torch.as_tensor(np.asarray(a, dtype=np.float32) if was_np else a)
-        if t.dim() != 2 or t.shape[1] != cols:
-            raise ValueError("expected a [rows, %d] array, got %s" % (cols, tuple(t.shape)))
-        t = t.to(device=self.device, dtype=torch.float32)
-        if t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < cols):
-            t = t.contiguous()
-        return t, was_np
-
-    def _rows_args(self, X, rows=None, what=None):
-        """X, one [N, n_input] array or tensor per modality -> (device tensors, N, was_numpy of X[0], ptrs, lds).  Every modality
-        needs the first one's row count, or ``rows`` (``what`` names it in the error) when given."""
-        M = len(self.network_architectures)
-        if len(X) != M:
-            raise ValueError("expected a list of %d modalities, got %d" % (M, len(X)))
-        ts, was_np = [], True
-        for m, (x, na) in enumerate(zip(X, self.network_architectures)):
-            t, np_in = self._dev(x, int(na["n_input"]))
-            if m == 0:
-                was_np = np_in
-            if rows is not None and t.shape[0] != rows:
-                raise ValueError("expected %d rows (%s), got %d" % (rows, what, t.shape[0]))
-            if ts and t.shape[0] != ts[0].shape[0]:
-                raise ValueError("every modality needs the same row count: %d vs %d" % (t.shape[0], ts[0].shape[0]))
-            ts.append(t)
-        ptrs = (C.c_void_p * M)(*[t.data_ptr() for t in ts])
-        lds = (C.c_int32 * M)(*[t.stride(0) if t.shape[0] > 1 else t.shape[1] for t in ts])
-        return ts, ts[0].shape[0], was_np, ptrs, lds
-
-    def _rows_args_masked(self, X, present):
-        """``_rows_args`` of the masked row calls: ``present`` [N, M] (bool or integer, array or tensor, any device; nonzero =
-        observed) gives the row count and becomes a uint8 device tensor; ``X[m] = None`` -> a NULL source (modality m absent on
-        every row).  -> (device tensors, N, was_numpy of the first given modality, ptrs, lds, presence)."""
-        M = len(self.network_architectures)
-        if len(X) != M:
-            raise ValueError("expected a list of %d modalities, got %d" % (M, len(X)))
-        p = present if torch.is_tensor(present) else torch.as_tensor(np.asarray(present))
-        if p.dim() != 2 or p.shape[1] != M:
-            raise ValueError("present must be [rows, %d], got %s" % (M, tuple(p.shape)))
-        rows = int(p.shape[0])
-        p = (p != 0).to(device=self.device, dtype=torch.uint8).contiguous()
-        ts, ptrs, lds, was_np = [], [], [], None
-        for m, (x, na) in enumerate(zip(X, self.network_architectures)):
-            if x is None:
-                ptrs.append(None)
-                lds.append(0)
-                continue
-            t, np_in = self._dev(x, int(na["n_input"]))
-            if was_np is None:
-                was_np = np_in
-            if t.shape[0] != rows:
-                raise ValueError("expected %d rows (present has %d), got %d for modality %d" % (rows, rows, t.shape[0], m))
-            ts.append(t)
-            ptrs.append(t.data_ptr())
-            lds.append(t.stride(0) if t.shape[0] > 1 else t.shape[1])
-        if was_np is None:
-            was_np = not torch.is_tensor(present)
-        return ts, rows, was_np, (C.c_void_p * M)(*ptrs), (C.c_int32 * M)(*lds), p
+    def _twin(self, name, head, p, tail):
+        """Call entry point ``name`` or, with presence bytes ``p``, its ``_masked`` twin, which takes them after (x, ld): the one
+        place where a call picks between the two."""
+        if p is not None:
+            name, head = name + "_masked", head + (p.data_ptr(),)
+        _capi.check(self._h, getattr(self._L, name)(self._h, *head, *tail, self._stream()), name)
 
     def _batch_args(self, X, eps, n_steps=1, present=None):
         """Arguments of the training / eval entry points -> (device tensors, ptrs, lds, eps tensor or None, presence or None).
-        ``present`` (the masked entry points): [batch_size * n_steps, M] (bool or integer, array or tensor, any device; nonzero =
-        observed) -> uint8 device tensor, and ``X[m] = None`` -> a NULL source (modality m absent on every row)."""
-        M = len(self.network_architectures)
+        ``present`` (the masked entry points): [batch_size * n_steps, M] -> uint8 device tensor, and ``X[m] = None`` -> a NULL
+        source (modality m absent on every row)."""
+        # the reference's eps has static shape (batch_size, n_z): every path through z needs exactly batch_size rows (vae_assoc.py:90)
         rows = self.batch_size * n_steps
-        steps = " x n_steps" if n_steps > 1 else ""
+        what = "batch_size x n_steps" if n_steps > 1 else "batch_size"
         p = None
         if present is None:
-            assert len(X) == M
+            assert len(X) == len(self._widths)
         else:
             world = self._sync.world_size if self._sync is not None else 1
             if world > 1:
                 raise RuntimeError("present= (partially paired batches) runs on one replica; this model is data parallel over %d ranks" % world)
-            if len(X) != M:
-                raise ValueError("expected a list of %d modalities, got %d" % (M, len(X)))
-            p = present if torch.is_tensor(present) else torch.as_tensor(np.asarray(present))
-            if p.dim() != 2 or p.shape[0] != rows or p.shape[1] != M:
-                raise ValueError("present must be [batch_size%s, %d] = [%d, %d], got %s" % (steps, M, rows, M, tuple(p.shape)))
-            p = (p != 0).to(device=self.device, dtype=torch.uint8).contiguous()
-        # the reference's eps has static shape (batch_size, n_z): every path through z needs exactly batch_size rows (vae_assoc.py:90)
-        ts, ptrs, lds = [], [], []
-        for x, na in zip(X, self.network_architectures):
-            if x is None and p is not None:
-                ptrs.append(None)
-                lds.append(0)
-                continue
-            t, _ = self._dev(x, int(na["n_input"]))
-            if t.shape[0] != rows:
-                raise ValueError("expected %d rows (batch_size%s), got %d" % (rows, steps, t.shape[0]))
-            ts.append(t)
-            ptrs.append(t.data_ptr())
-            lds.append(t.stride(0) if t.shape[0] > 1 else t.shape[1])
-        e = None
-        if eps is not None:
-            e, _ = self._dev(eps, self.n_z)
-            if e.shape[0] != rows:
-                raise ValueError("eps must be [batch_size%s, n_z]" % steps)
-            e = e.contiguous()
-        return ts, (C.c_void_p * M)(*ptrs), (C.c_int32 * M)(*lds), e, p
+            p = dev_flags(present, len(self._widths), self.device, rows, what)
+        ts, _, _, ptrs, lds = dev_modalities(X, self._widths, self.device, rows, what, allow_none=p is not None)
+        return ts, ptrs, lds, dev_dense(eps, self.n_z, self.device, rows, what), p
 
-    def _train_masked(self, X, n_steps, eps, present, return_cost):
+    def _train(self, X, n_steps, eps, present, return_cost, one_step=False):
         ts, ptrs, lds, e, p = self._batch_args(X, eps, n_steps, present)
         cost = C.c_float(0.0)
-        _capi.check(self._h, self._L.avae_train_steps_masked(self._h, n_steps, ptrs, lds, p.data_ptr(),
-                                                             e.data_ptr() if e is not None else None,
-                                                             C.byref(cost) if return_cost else None, self._stream()),
-                    "avae_train_steps_masked")
+        tail = (ptr(e), C.byref(cost) if return_cost else None)
+        if one_step and p is None:      # (library-owned collective: avae_train_step runs the bucketed pipeline itself)
+            self._twin("avae_train_step", (ptrs, lds), None, tail)
+        else:
+            self._twin("avae_train_steps", (n_steps, ptrs, lds), p, tail)
         return cost.value if return_cost else None
 
     def get_params(self):
@@ -476,8 +425,7 @@ class AssocVariationalAutoEncoder(object):
     # bucketed seam (parallel.dp_train_step_bucketed): stage -> per bucket backward / all-reduce -> per bucket Adam
     def _stage(self, X, eps=None, n_steps=1):
         ts, ptrs, lds, e, _ = self._batch_args(X, eps, n_steps)
-        _capi.check(self._h, self._L.avae_stage_batches(self._h, n_steps, ptrs, lds, e.data_ptr() if e is not None else None,
-                                                        self._stream()), "avae_stage_batches")
+        _capi.check(self._h, self._L.avae_stage_batches(self._h, n_steps, ptrs, lds, ptr(e), self._stream()), "avae_stage_batches")
         self._staged_j = 0
 
     def _backward_bucket(self, b):
@@ -497,18 +445,11 @@ class AssocVariationalAutoEncoder(object):
         ``present`` (optional, one replica): [batch_size, M] presence flags, nonzero = row n has modality m.  The step then charges
         every row only with the terms of the modalities it has (include/avae.h; the divisor stays batch_size),
         and ``X[m]`` may be None for a modality absent from the whole batch."""
-        if present is not None:
-            return self._train_masked(X, 1, eps, present, return_cost)
-        if self._sync is not None and self._sync.world_size > 1 and not self._comm_lib:
+        if present is None and self._sync is not None and self._sync.world_size > 1 and not self._comm_lib:
             # host-owned collective (torch.distributed) over the library's buckets
             cost = dp_train_step_bucketed(self, self._sync, self._buckets, X, eps)
             return cost if return_cost else None
-        ts, ptrs, lds, e, _ = self._batch_args(X, eps)      # (library-owned collective: avae_train_step runs the bucketed pipeline itself)
-        cost = C.c_float(0.0)
-        _capi.check(self._h, self._L.avae_train_step(self._h, ptrs, lds, e.data_ptr() if e is not None else None,
-                                                     C.byref(cost) if return_cost else None, self._stream()),
-                    "avae_train_step")
-        return cost.value if return_cost else None
+        return self._train(X, 1, eps, present, return_cost, one_step=True)
 
     def partial_fit_steps(self, X, n_steps, eps=None, return_cost=True, present=None):
         """``n_steps`` successive ``partial_fit`` calls in one submission: step i trains on rows
@@ -517,61 +458,39 @@ class AssocVariationalAutoEncoder(object):
         last step's cost; every step's cost is in ``cost_history``.  ``present``: [n_steps * batch_size, M]
         presence flags, as in ``partial_fit``."""
         n_steps = int(n_steps)
-        if present is not None:
-            return self._train_masked(X, n_steps, eps, present, return_cost)
-        if self._sync is not None and self._sync.world_size > 1 and not self._comm_lib:
-            # host-owned collective: the batches are staged 16 at a time, every step runs the bucketed schedule
-            ts, ptrs, lds, e, _ = self._batch_args(X, eps, n_steps)
-            B, cost, st = self.batch_size, None, self._stream()
-            for i0 in range(0, n_steps, 16):
-                n = min(16, n_steps - i0)
-                p_i = (C.c_void_p * len(ts))(*[t.data_ptr() + i0 * B * t.stride(0) * 4 for t in ts])
-                e_i = (e.data_ptr() + i0 * B * self.n_z * 4) if e is not None else None
-                _capi.check(self._h, self._L.avae_stage_batches(self._h, n, p_i, lds, e_i, st), "avae_stage_batches")
-                for j in range(n):
-                    self._staged_j = j
-                    pending = []
-                    for b, ranges in enumerate(self._buckets):
-                        self._backward_bucket(b)
-                        pending.append(self._sync.all_reduce_ranges_(self._grad_view, ranges, async_op=True))
-                    for b in range(len(self._buckets)):
-                        for w in pending[b]:
-                            w.wait()
-                        cost = self._apply_bucket(b, return_cost and i0 + j == n_steps - 1 and b == len(self._buckets) - 1)
-            return cost
+        if present is not None or self._sync is None or self._sync.world_size == 1 or self._comm_lib:
+            return self._train(X, n_steps, eps, present, return_cost)
+        # host-owned collective: the batches are staged 16 at a time, every step runs the bucketed schedule
         ts, ptrs, lds, e, _ = self._batch_args(X, eps, n_steps)
-        cost = C.c_float(0.0)
-        _capi.check(self._h, self._L.avae_train_steps(self._h, n_steps, ptrs, lds, e.data_ptr() if e is not None else None,
-                                                      C.byref(cost) if return_cost else None, self._stream()),
-                    "avae_train_steps")
-        return cost.value if return_cost else None
+        B, cost, st = self.batch_size, None, self._stream()
+        for i0 in range(0, n_steps, 16):
+            n = min(16, n_steps - i0)
+            p_i = (C.c_void_p * len(ts))(*[t.data_ptr() + i0 * B * t.stride(0) * 4 for t in ts])
+            e_i = (e.data_ptr() + i0 * B * self.n_z * 4) if e is not None else None
+            _capi.check(self._h, self._L.avae_stage_batches(self._h, n, p_i, lds, e_i, st), "avae_stage_batches")
+            for j in range(n):
+                self._staged_j = j
+                cost = dp_bucket_schedule(self, self._sync, self._buckets, return_cost and i0 + j == n_steps - 1)
+        return cost
 
     def evaluate_cost(self, X, eps=None, present=None):
         """reference vae_assoc.py:388-391 (forward + loss with a fresh eps, no update).  ``present``: [batch_size, M] presence
         flags, as in ``partial_fit`` (one replica)."""
-        if present is not None:
-            ts, ptrs, lds, e, p = self._batch_args(X, eps, present=present)
-            cost = C.c_float(0.0)
-            _capi.check(self._h, self._L.avae_eval_cost_masked(self._h, ptrs, lds, p.data_ptr(), e.data_ptr() if e is not None else None,
-                                                               C.byref(cost), self._stream()), "avae_eval_cost_masked")
-            return cost.value
-        ts, ptrs, lds, e, _ = self._batch_args(X, eps)
+        ts, ptrs, lds, e, p = self._batch_args(X, eps, present=present)
         cost = C.c_float(0.0)
-        _capi.check(self._h, self._L.avae_eval_cost(self._h, ptrs, lds, e.data_ptr() if e is not None else None,
-                                                    C.byref(cost), self._stream()), "avae_eval_cost")
+        self._twin("avae_eval_cost", (ptrs, lds), p, (ptr(e), C.byref(cost)))
         c = cost.value
-        if self._sync is not None and self._sync.world_size > 1:
+        if self._sync is not None and self._sync.world_size > 1:        # (never with ``present``: that runs on one replica)
             c = self._sync.sum_scalar(c, self.device)
         return c
 
     def _encode(self, m, x, want_logvar=False):
-        t, was_np = self._dev(x, int(self.network_architectures[m]["n_input"]))
+        t, was_np = dev_array(x, self._widths[m], self.device)
         rows = t.shape[0]
         mu = torch.empty((rows, self.n_z), dtype=torch.float32, device=self.device)
         lv = torch.empty_like(mu) if want_logvar else None
         if rows:
-            _capi.check(self._h, self._L.avae_encode(self._h, m, t.data_ptr(), t.stride(0) if rows > 1 else t.shape[1], rows,
-                                                     mu.data_ptr(), lv.data_ptr() if want_logvar else None,
+            _capi.check(self._h, self._L.avae_encode(self._h, m, t.data_ptr(), ld_of(t), rows, mu.data_ptr(), ptr(lv),
                                                      self._stream()), "avae_encode")
         conv = (lambda a: a.cpu().numpy()) if was_np else (lambda a: a)
         return (conv(mu), conv(lv)) if want_logvar else conv(mu)
@@ -591,32 +510,27 @@ class AssocVariationalAutoEncoder(object):
         RNG, batch_size rows (reference vae_assoc.py:405-419)."""
         if z_mu is None:
             z_mu = np.random.normal(size=(self.batch_size, self.n_z))
-        z, was_np = self._dev(z_mu, self.n_z)
-        z = z.contiguous()
+        z = dev_dense(z_mu, self.n_z, self.device)
         rows = z.shape[0]
-        outs = [torch.empty((rows, int(na["n_input"])), dtype=torch.float32, device=self.device) for na in self.network_architectures]
+        outs = [torch.empty((rows, cols), dtype=torch.float32, device=self.device) for cols in self._widths]
         if rows:       # every modality's decoder in one submission (avae_generate: one graph replay for 1-64 rows)
             ptrs = (C.c_void_p * len(outs))(*[o.data_ptr() for o in outs])
             _capi.check(self._h, self._L.avae_generate(self._h, z.data_ptr(), rows, ptrs, self._stream()), "avae_generate")
-        return [o.cpu().numpy() for o in outs] if was_np else outs
+        return outs if torch.is_tensor(z_mu) else [o.cpu().numpy() for o in outs]
 
     def reconstruct(self, X, eps=None):
         """Use VAE to reconstruct given data: encode -> sample z -> decode, per modality with its
         own eps draw as each sess.run of the reference makes one (vae_assoc.py:421-425).
         ``eps`` may be a list with one [rows, n_z] array per modality."""
         outs = []
-        for m, (x, na) in enumerate(zip(X, self.network_architectures)):
-            t, was_np = self._dev(x, int(na["n_input"]))
+        for m, (x, cols) in enumerate(zip(X, self._widths)):
+            t, was_np = dev_array(x, cols, self.device)
             rows = t.shape[0]
-            e = None
-            if eps is not None:
-                e, _ = self._dev(eps[m], self.n_z)
-                e = e.contiguous()
-                assert e.shape[0] == rows
-            o = torch.empty((rows, int(na["n_input"])), dtype=torch.float32, device=self.device)
+            e = dev_dense(eps[m], self.n_z, self.device) if eps is not None else None
+            assert e is None or e.shape[0] == rows
+            o = torch.empty((rows, cols), dtype=torch.float32, device=self.device)
             if rows:
-                _capi.check(self._h, self._L.avae_reconstruct(self._h, m, t.data_ptr(), t.stride(0) if rows > 1 else t.shape[1],
-                                                              e.data_ptr() if e is not None else None, rows, o.data_ptr(),
+                _capi.check(self._h, self._L.avae_reconstruct(self._h, m, t.data_ptr(), ld_of(t), ptr(e), rows, o.data_ptr(),
                                                               self._stream()), "avae_reconstruct")
             outs.append(o.cpu().numpy() if was_np else o)
         return outs
@@ -643,27 +557,14 @@ class AssocVariationalAutoEncoder(object):
 
     def _score(self, X, present, eps, cross_modal):
         M = len(self.network_architectures)
-        if present is None:
-            ts, rows, was_np, ptrs, lds = self._rows_args(X)
-        else:
-            ts, rows, was_np, ptrs, lds, p = self._rows_args_masked(X, present)
-        e = None
-        if eps is not None:
-            e, _ = self._dev(eps, self.n_z)
-            if e.shape[0] != rows:
-                raise ValueError("eps must be [%d, %d], got %s" % (rows, self.n_z, tuple(e.shape)))
-            e = e.contiguous()
+        ts, rows, was_np, ptrs, lds, p = dev_row_args(X, self._widths, self.device, present)
+        e = dev_dense(eps, self.n_z, self.device, rows)
         flags = _capi.SCORE_CROSS if cross_modal else 0
         k = C.c_int32(0)
         _capi.check(None, self._L.avae_score_width(C.byref(self._cfg), flags, C.byref(k)), "avae_score_width")
         out = torch.empty((rows, k.value), dtype=torch.float32, device=self.device)
-        if rows and present is None:
-            _capi.check(self._h, self._L.avae_score(self._h, ptrs, lds, rows, e.data_ptr() if e is not None else None, flags,
-                                                    out.data_ptr(), self._stream()), "avae_score")
-        elif rows:
-            _capi.check(self._h, self._L.avae_score_masked(self._h, ptrs, lds, p.data_ptr(), rows,
-                                                           e.data_ptr() if e is not None else None, flags, out.data_ptr(),
-                                                           self._stream()), "avae_score_masked")
+        if rows:
+            self._twin("avae_score", (ptrs, lds), p, (rows, ptr(e), flags, out.data_ptr()))
         if was_np:
             out = out.cpu().numpy()
         P = M * (M - 1) // 2
@@ -700,24 +601,11 @@ class AssocVariationalAutoEncoder(object):
         if isinstance(n_samples, bool) or not isinstance(n_samples, (int, np.integer)) or n_samples < 1:
             raise ValueError("n_samples must be an integer >= 1, got %r" % (n_samples,))
         K = int(n_samples)
-        if present is None:
-            ts, rows, was_np, ptrs, lds = self._rows_args(X)
-        else:
-            ts, rows, was_np, ptrs, lds, p = self._rows_args_masked(X, present)
-        e = None
-        if eps is not None:
-            e = torch.as_tensor(np.asarray(eps, dtype=np.float32) if not torch.is_tensor(eps) else eps)
-            if tuple(e.shape) != (rows, K, self.n_z):
-                raise ValueError("eps must be [%d, %d, %d], got %s" % (rows, K, self.n_z, tuple(e.shape)))
-            e = e.to(device=self.device, dtype=torch.float32).contiguous()
+        ts, rows, was_np, ptrs, lds, p = dev_row_args(X, self._widths, self.device, present)
+        e = dev_dense3(eps, (rows, K, self.n_z), self.device)
         out = torch.empty((rows, 2 * M + M * M), dtype=torch.float32, device=self.device)
-        if rows and present is None:
-            _capi.check(self._h, self._L.avae_loglik(self._h, ptrs, lds, rows, K, e.data_ptr() if e is not None else None,
-                                                     out.data_ptr(), self._stream()), "avae_loglik")
-        elif rows:
-            _capi.check(self._h, self._L.avae_loglik_masked(self._h, ptrs, lds, p.data_ptr(), rows, K,
-                                                            e.data_ptr() if e is not None else None, out.data_ptr(),
-                                                            self._stream()), "avae_loglik_masked")
+        if rows:
+            self._twin("avae_loglik", (ptrs, lds), p, (rows, K, ptr(e), out.data_ptr()))
         if was_np:
             out = out.cpu().numpy()
         return {"marginal": out[:, :M], "joint": out[:, M:2 * M], "conditional": out[:, 2 * M:].reshape(rows, M, M)}
@@ -738,8 +626,8 @@ class AssocVariationalAutoEncoder(object):
         Returns a dict: ``z [N, n_z]``, ``x`` (list over modalities of ``[N, n_input_m]`` decoder outputs at ``z``, the unobserved
         parts and modalities included), ``objective [n_iters + 1, N]`` (J at the start and after every update) and ``grad0
         [N, n_z]`` (dJ/dz at the start).  NumPy in gives NumPy out, device tensors in give device tensors out."""
-        archs = self.network_architectures
-        M = len(archs)
+        widths = self._widths
+        M = len(widths)
         if len(X) != M:
             raise ValueError("expected a list of %d modalities, got %d" % (M, len(X)))
         if observed is not None and len(observed) != M:
@@ -747,41 +635,26 @@ class AssocVariationalAutoEncoder(object):
         if isinstance(n_iters, bool) or not isinstance(n_iters, (int, np.integer)) or n_iters < 0:
             raise ValueError("n_iters must be an integer >= 0, got %r" % (n_iters,))
         n_iters = int(n_iters)
-        ts, obs, rows, was_np = [None] * M, [None] * M, None, None
-        for m, (x, na) in enumerate(zip(X, archs)):
-            if x is None:
-                continue
-            ts[m], np_in = self._dev(x, int(na["n_input"]))
-            if was_np is None:
-                was_np = np_in
-            if rows is not None and ts[m].shape[0] != rows:
-                raise ValueError("every modality needs the same row count: %d vs %d" % (ts[m].shape[0], rows))
-            rows = ts[m].shape[0]
-            if observed is not None and observed[m] is not None:
-                o = observed[m] if torch.is_tensor(observed[m]) else torch.as_tensor(np.asarray(observed[m]))
-                if tuple(o.shape) != (rows, int(na["n_input"])):
-                    raise ValueError("observed[%d] must be [%d, %d] as X[%d], got %s" % (m, rows, int(na["n_input"]), m, tuple(o.shape)))
-                obs[m] = (o != 0).to(device=self.device, dtype=torch.uint8).contiguous()
+        ts, rows, was_np, xp, lds = dev_modalities(X, widths, self.device, allow_none=True)
         if rows is None:
             raise ValueError("every modality is None: nothing is observed")
+        obs = [None] * M
+        for m, o in enumerate(() if observed is None else observed):
+            if o is not None and ts[m] is not None:
+                obs[m] = dev_flags(o, widths[m], self.device, rows, "as X[%d]" % m, "observed[%d]" % m)
         if z0 is None:
             init = next(m for m in range(M) if ts[m] is not None) if init is None else init
             if isinstance(init, bool) or not isinstance(init, (int, np.integer)) or not 0 <= init < M or ts[init] is None:
                 raise ValueError("init must be the index of a modality that is not None, got %r" % (init,))
             xi = ts[init] if obs[init] is None else torch.where(obs[init] != 0, ts[init], torch.zeros_like(ts[init]))
-            z = self._encode(init, xi)
+            z = self._encode(init, xi).contiguous()
         else:
-            z, _ = self._dev(z0, self.n_z)
-            if z.shape[0] != rows:
-                raise ValueError("z0 must be [%d, %d], got %s" % (rows, self.n_z, tuple(z.shape)))
-        z = z.contiguous()
+            z = dev_dense(z0, self.n_z, self.device, rows, name="z0")
         out_z = torch.empty((rows, self.n_z), dtype=torch.float32, device=self.device)
         grad = torch.empty_like(out_z)
         obj = torch.empty((n_iters + 1, rows), dtype=torch.float32, device=self.device)
-        outs = [torch.empty((rows, int(na["n_input"])), dtype=torch.float32, device=self.device) for na in archs]
-        xp = (C.c_void_p * M)(*[t.data_ptr() if t is not None else None for t in ts])
-        lds = (C.c_int32 * M)(*[0 if t is None else (t.stride(0) if rows > 1 else t.shape[1]) for t in ts])
-        op = (C.c_void_p * M)(*[o.data_ptr() if o is not None else None for o in obs])
+        outs = [torch.empty((rows, cols), dtype=torch.float32, device=self.device) for cols in widths]
+        op = (C.c_void_p * M)(*[ptr(o) for o in obs])
         hp = (C.c_void_p * M)(*[o.data_ptr() for o in outs])
         if rows:
             _capi.check(self._h, self._L.avae_complete(self._h, xp, lds, op, z.data_ptr(), rows, n_iters, float(lr), float(prior_weight),
