@@ -310,6 +310,42 @@ int avae_complete(avae_handle* h, const float* const* x_dev, const int32_t* x_ld
                   const float* z0_dev, int32_t rows, int32_t n_iters, float lr, float prior_weight,
                   float* z_dev, float* obj_dev, float* grad_dev, float* const* xhat_dev, void* stream);
 
+/* ---- fused-posterior prediction of missing modalities (the reference's deployed use, image -> joint trajectory,
+ * baxter_vae_assoc_writer.py:407-432, is transform on one modality followed by generate; this call uses every modality a row has
+ * and also gives the spread of the prediction).  Per row n: S = {m : present[n,m] != 0 and x_dev[m] != NULL}, (mu_m, lv_m) exactly
+ * avae_encode's output for modality m.  Fused posterior per latent dimension, fp32, modalities added in index order:
+ *   a_m = -lv_m;  A = max_{m in S} a_m;  w_m = exp(a_m - A)
+ *   mu_f = (sum_{m in S} w_m mu_m) / (sum_{m in S} w_m);   lv_f = -(A + log((sum_{m in S} w_m) / |S|))
+ * -- the precision is the mean of the precisions and the mean is precision-weighted: the minimiser over Gaussians q of
+ * sum_{m in S} KL(q || q_m), the divergence training drives to zero.  |S| = 1 is a select: (mu_f, lv_f) are bitwise that modality's
+ * avae_encode output.  |S| = 0 is the prior, mu_f = lv_f = +0.0 (the row gets the prior predictive, not NaN).
+ * Prediction, for EVERY modality d (for a present one it is a reconstruction):
+ *   n_samples = 0       mean_d = dec_d(mu_f), z read in the compute dtype as avae_generate reads it; var_dev is ignored
+ *   n_samples = K >= 1  z_k = mu_f + exp(lv_f/2) eps_k (formed as avae_loglik forms it), x_k = dec_d(z_k); mean and population
+ *                       variance over k per output element, fp32, sequentially in sample order k = 0..K-1 with Welford's update
+ *                         delta = x_k - mean;  mean += delta / (k+1);  M2 += delta * (x_k - mean);  var = M2 / K
+ *                       (K = 1: var = +0.0).  The running (mean, M2) is carried per element, so the result does not depend on how
+ *                       K is split into passes.
+ *   x_dev, x_ld   as avae_score_masked: x_dev[m] == NULL = modality m absent on every row (never offset, no encoder runs)
+ *   present_dev   device uint8 [rows][M] as in avae_score_masked, or NULL: every modality with a non-NULL x_dev[m] is present on
+ *                 every row
+ *   eps_dev       [rows][n_samples][n_z] fp32, or NULL: a fresh Philox draw keyed as avae_loglik's (it advances the ONE per-handle
+ *                 draw counter the scoring calls share; a call that decodes no sample draws nothing)
+ *   mu_dev, logvar_dev   optional [rows][n_z]: the fused posterior
+ *   mean_dev, var_dev    optional; mean_dev[d] / var_dev[d] optional [rows][n_input_d], dense.  A NULL output is skipped.
+ * rows == 0 is a no-op; n_samples < 0 is an error.  Any row count: the encoders run on chunks of at most batch_size rows, the
+ * decoders in passes of at most batch_size decoded rows laid out as avae_loglik's (input rows x samples, decoded row j*kc + k; a row
+ * with more samples than fit spans several passes; K = 0: chunks of batch_size rows).  Through the serve plans up to 16 passes
+ * (at most 16 MiB of decoder outputs, held in the call's scratch) share one sampling and one accumulate launch.
+ * Absent entries are selected away, never multiplied by 0 and never read: staging stores zeros for them, and NaN / Inf / garbage
+ * there changes no bit of any output.  No atomics: the same inputs give bitwise the same outputs.  Conv decoders go modality by
+ * modality, as in avae_loglik.  As avae_score, the call changes nothing the next training step reads; on a data-parallel replica
+ * it covers the local rows, with no collective.  Its scratch (fused rows, z rows and decoder outputs of one group of passes, the
+ * running (mean, M2) of one input row) is allocated by the first call and freed by avae_destroy; avae_workspace_bytes is unchanged. */
+int avae_impute(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, const uint8_t* present_dev,
+                int32_t rows, int32_t n_samples, const float* eps_dev,
+                float* mu_dev, float* logvar_dev, float* const* mean_dev, float* const* var_dev, void* stream);
+
 /* save_model / restore_model (vae_assoc.py:427-463): own flat file (config echo + params + Adam
  * slots + step); TF .ckpt files cannot be read offline. */
 int avae_save(avae_handle* h, const char* path);

@@ -33,7 +33,7 @@ SYMBOLS = [
     "avae_train_step", "avae_train_steps", "avae_stage_batches", "avae_grad_buffer", "avae_cost_history",
     "avae_dp_plan", "avae_dp_backward", "avae_dp_apply", "avae_comm_unique_id", "avae_comm_ipc_handle", "avae_comm_ipc_attach",
     "avae_eval_cost", "avae_encode", "avae_decode", "avae_generate", "avae_reconstruct", "avae_save", "avae_load",
-    "avae_score_width", "avae_score", "avae_loglik", "avae_score_masked", "avae_loglik_masked", "avae_train_steps_masked", "avae_eval_cost_masked", "avae_complete",
+    "avae_score_width", "avae_score", "avae_loglik", "avae_score_masked", "avae_loglik_masked", "avae_train_steps_masked", "avae_eval_cost_masked", "avae_complete", "avae_impute",
     "avae_synchronize", "avae_timing_enable", "avae_timing_report", "avae_debug_fetch", "avae_comm_allreduce",
 ]
 
@@ -110,6 +110,7 @@ def lib():
             L.avae_loglik_masked.argtypes = [vp, C.POINTER(vp), C.POINTER(i32), vp, i32, i32, vp, vp, vp]
             L.avae_complete.argtypes = [vp, C.POINTER(vp), C.POINTER(i32), C.POINTER(vp), vp, i32, i32, C.c_float, C.c_float,
                                         vp, vp, vp, C.POINTER(vp), vp]
+            L.avae_impute.argtypes = [vp, C.POINTER(vp), C.POINTER(i32), vp, i32, i32, vp, vp, vp, C.POINTER(vp), C.POINTER(vp), vp]
             L.avae_save.argtypes = [vp, C.c_char_p]
             L.avae_load.argtypes = [vp, C.c_char_p]
             L.avae_synchronize.argtypes = [vp]

@@ -451,6 +451,34 @@ struct IwReduceArgs {
 };
 void launch_iw_reduce(const IwReduceArgs& a, hipStream_t s);
 
+// Fused-posterior prediction (avae_impute).  k_impute_fuse: one wave64 per row, one lane per latent dimension; the Gaussian closest
+// to the present modalities' posteriors in sum_m KL(q || q_m): precision = mean of the precisions, mean precision-weighted,
+// max-shifted so exp stays in range.  One present modality is a select of its (mu, lv), none is the prior (+0.0, +0.0).
+struct ImputeFuseArgs {
+    const float* mulv[kMaxMod];    // [rows][2*n_z] fp32 of every modality (a modality outside `mods` is never read)
+    unsigned mods;                 // bit m: x_dev[m] was given (the presence of every row when `present` is NULL)
+    const unsigned char* present;  // NULL, or the chunk's staged presence bytes [rows][n_mod], 0 / 1, NULL sources folded in
+    float* fused;                  // [rows][2*n_z] fp32 [mu_f | lv_f]: the proposal k_iw_latent samples from
+    float* mu; float* lv;          // nullable: the caller's [rows][n_z] rows of this chunk
+    float* z32;                    // n_samples = 0 (nullable): mu_f as dense fp32 z rows (the serve route) ...
+    void* Z[kMaxMod]; int ldz[kMaxMod]; int n_zdst;   // ... or into every decoder input, compute dtype (the modality-by-modality route)
+    int rows, nz, n_mod;
+};
+void launch_impute_fuse(int compute_dtype, const ImputeFuseArgs& a, hipStream_t s);
+// k_impute_accum: one wave64 per (input row of the pass, modality, tile of 64 output columns), lanes on consecutive columns.
+// Welford's update over the pass's kc decoded rows of that input row, sequentially in sample order, in registers; the running
+// (mean, M2) crosses passes in `state`; the row's last sample block stores mean and M2 / K.  No atomics.
+struct ImputeAccumArgs {
+    const float* xhat[kMaxMod]; int ldh[kMaxMod];   // decoder outputs fp32, [n_dec][ldh], decoded row i = j * kc + k
+    float* mean[kMaxMod]; float* var[kMaxMod];      // nullable: the caller's dense [rows][n_input] rows, at the pass's first input row
+    int n_in[kMaxMod];
+    int tile0[kMaxMod + 1];        // prefix sums of the modalities' column tiles
+    int col0[kMaxMod];             // prefix sums of n_input: a modality's first column in a state row
+    float* state; int ld_state;    // [rows][ld_state = sum n_input][2] running (mean, M2)
+    int rows, kc, k0, K, n_mod;
+};
+void launch_impute_accum(const ImputeAccumArgs& a, hipStream_t s);
+
 // ---- gradient exchange (avae_comm.hip)
 // One-shot all-reduce over hipIpc peers ("a hand-rolled P2P reduce-scatter/all-gather over hipIpc peers"):
 // every rank owns an exchange block (uncached device memory, mapped by every peer); a range of the gradient buffer is cut into

@@ -251,6 +251,8 @@ struct avae_handle {
     size_t off_slot = 0;
     // avae_loglik's scratch, allocated by its first call (z rows, r, log-weights, running log-sum-exp states of one pass)
     float* iw_buf = nullptr;
+    // avae_impute's scratch, allocated by its first call (fused [mu | lv] rows, z rows, r, the running (mean, M2) of one input row)
+    float* imp_buf = nullptr;
     unsigned char* row_pres = nullptr;      // masked scoring: the chunk's staged presence bytes [batch_size][M] (first use)
     size_t off_chain = 0;
     size_t off_consts = 0, off_conv_tab = 0;   // 32 B {zeros | one, 0...}; device copy of conv_tab
@@ -2974,6 +2976,7 @@ void destroy_handle(avae_handle* h) {
     for (std::vector<StepGraph>& v : h->g_dp) for (StepGraph& g : v) g.release();
     for (avae_handle::Serve& sv : h->serve) if (sv.graph) (void)hipGraphExecDestroy(sv.graph);
     if (h->iw_buf) (void)hipFree(h->iw_buf);
+    if (h->imp_buf) (void)hipFree(h->imp_buf);
     if (h->row_pres) (void)hipFree(h->row_pres);
     for (StepGraph& g : h->cmpl.g) g.release();
     if (h->cmpl.buf) (void)hipFree(h->cmpl.buf);
@@ -3529,6 +3532,171 @@ int avae_loglik_masked(avae_handle* h, const float* const* x_dev, const int32_t*
     return guarded(h, [&] {
         if (!present_dev) throw Err("avae_loglik_masked: present_dev is NULL (avae_loglik is the unmasked call)");
         loglik_call(h, "avae_loglik_masked", x_dev, x_ld, present_dev, rows, n_samples, eps_dev, out_dev, stream);
+    });
+}
+
+// Fused-posterior prediction of every modality from the ones a row has (include/avae.h).  Per chunk of at
+// most batch_size rows: stage + encode every given modality once (a NULL x_dev[m] runs no encoder) -> k_impute_fuse ([mu_f | lv_f]
+// into the scratch and the caller's rows; n_samples = 0: mu_f as the decoders' z, decoded once).  Then loglik_call's layout over
+// the chunk's rows with `cap` decoded rows per group (n input rows x kb samples; K >= cap: one row over several groups): per group
+// the UNMASKED k_iw_latent on the fused rows (its r goes to scratch and is not read) -> the decoders in passes of at most
+// batch_size rows -> k_impute_accum.  Modality by modality (conv nets / use_graph = 0 / timing) a group is one pass, cap =
+// batch_size, on the decoders' Z / out32 buffers; the serve route keeps up to P passes of z and outputs in the scratch, so the two
+// row kernels run once per P decoder passes.  Scratch: imp_buf (allocated once).
+constexpr int kImputeGroupPasses = 16;                 // passes per group of the serve route, at most ...
+constexpr size_t kImputeGroupBytes = (size_t)16 << 20;  // ... and at most this many bytes of decoder outputs held per group
+static void impute_call(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, const uint8_t* present, int32_t rows,
+                        int32_t n_samples, const float* eps_dev, float* mu_dev, float* logvar_dev, float* const* mean_dev,
+                        float* const* var_dev, void* stream) {
+        const std::string w = "avae_impute";
+        if (rows < 0) throw Err(w + ": rows must be >= 0");
+        if (n_samples < 0) throw Err(w + ": n_samples must be >= 0, got " + std::to_string(n_samples));
+        if (rows == 0) return;
+        if (!x_dev) throw Err(w + ": x_dev is NULL");
+        const int M = h->M, B = h->B, nz = h->nz, K = n_samples;
+        int ld[kMaxMod] = {0, 0, 0, 0};
+        unsigned mods = 0;
+        for (int m = 0; m < M; ++m) {
+            if (!x_dev[m]) continue;
+            mods |= 1u << m;
+            ld[m] = x_ld ? x_ld[m] : h->mods[m].n_in;
+            if (ld[m] < h->mods[m].n_in)
+                throw Err(w + ": x_ld[" + std::to_string(m) + "] = " + std::to_string(ld[m]) + " is below n_input = " + std::to_string(h->mods[m].n_in));
+        }
+        float* mean_out[kMaxMod] = {nullptr, nullptr, nullptr, nullptr};
+        float* var_out[kMaxMod] = {nullptr, nullptr, nullptr, nullptr};
+        bool decode = false;
+        int n_all = 0;
+        for (int m = 0; m < M; ++m) {
+            mean_out[m] = mean_dev ? mean_dev[m] : nullptr;
+            var_out[m] = (var_dev && K > 0) ? var_dev[m] : nullptr;
+            decode = decode || mean_out[m] || var_out[m];
+            n_all += h->mods[m].n_in;
+        }
+        unsigned char* pres = present ? row_presence_buf(h) : nullptr;
+        hipStream_t s = on_stream(h, stream);
+        // The serve route decodes a GROUP of up to P passes between one k_iw_latent and one k_impute_accum launch: z and the decoder
+        // outputs of the group live in the scratch (serve_call takes any z / output pointers), at most kImputeGroupBytes of outputs.
+        // The modality-by-modality route works on the decoders' own Z / out32 buffers: one pass per group.
+        const int P = (int)std::max<size_t>(1, std::min<size_t>(kImputeGroupPasses, kImputeGroupBytes / ((size_t)B * n_all * sizeof(float))));
+        const size_t f_n = (size_t)B * 2 * nz, z_n = rup((size_t)P * B * nz, 2), r_n = rup((size_t)P * B, 2), st_n = (size_t)n_all * 2;
+        const size_t o_n = P > 1 ? (size_t)P * B * n_all : 0;
+        if (!h->imp_buf) HIP_OK(hipMalloc(reinterpret_cast<void**>(&h->imp_buf), (f_n + z_n + r_n + st_n + o_n) * sizeof(float)));
+        float* fused = h->imp_buf;
+        float* z32 = fused + f_n;
+        float* rbuf = z32 + z_n;
+        float* state = rbuf + r_n;                 // (an even float offset: k_impute_accum moves float2)
+        float* outs = state + st_n;
+        const bool by_mod = decode_by_mod(h);
+        const bool grouped = !by_mod && P > 1;
+        const int cap = grouped ? P * B : B;       // decoded rows of one group
+        const int n_rows = K == 0 ? B : K >= cap ? 1 : cap / K, kb = K >= cap ? cap : K;      // input rows, samples of one group
+        ImputeFuseArgs fa;
+        std::memset(&fa, 0, sizeof(fa));
+        fa.mods = mods; fa.present = pres; fa.fused = fused; fa.nz = nz; fa.n_mod = M;
+        for (int m = 0; m < M; ++m) fa.mulv[m] = h->at<float>(h->mods[m].mulv);
+        IwLatentArgs la;
+        std::memset(&la, 0, sizeof(la));
+        la.mulv = fused; la.nz = nz; la.K = K; la.seed = h->cfg.seed; la.r = rbuf; la.pres_ld = M;
+        // a fresh eps per sampled call, keyed as avae_loglik's: draw counter, row of the whole input, sample index
+        if (K > 0 && decode) la.draw = next_draw(h, eps_dev);
+        ServeSlot sl;
+        std::memset(&sl, 0, sizeof(sl));
+        sl.z = z32;
+        ImputeAccumArgs aa;
+        std::memset(&aa, 0, sizeof(aa));
+        aa.state = state; aa.ld_state = n_all; aa.K = K; aa.n_mod = M;
+        for (int m = 0; m < M; ++m) {
+            const Mod& md = h->mods[m];
+            aa.col0[m] = m ? aa.col0[m - 1] + h->mods[m - 1].n_in : 0;
+            aa.xhat[m] = grouped ? outs + (size_t)cap * aa.col0[m] : h->at<float>(md.out32);
+            aa.ldh[m] = by_mod ? md.ld32 : md.n_in;            // the serve route stores dense [rows][n_input]
+            aa.n_in[m] = md.n_in;
+            aa.tile0[m + 1] = aa.tile0[m] + (md.n_in + 63) / 64;
+            sl.out[m] = h->at<float>(md.out32);
+        }
+        if (decode && by_mod) {
+            la.n_zdst = M;
+            for (int m = 0; m < M; ++m) { la.Z[m] = h->at<void>(h->mods[m].Z.rm); la.ldz[m] = h->mods[m].Z.ld; }
+        } else if (decode) {
+            la.z32 = z32;
+        }
+        if (K == 0 && decode) {                    // the fuse launch stages z = mu_f itself
+            fa.z32 = la.z32; fa.n_zdst = la.n_zdst;
+            for (int m = 0; m < M; ++m) { fa.Z[m] = la.Z[m]; fa.ldz[m] = la.ldz[m]; }
+        }
+        for (int r0 = 0; r0 < rows; r0 += B) {
+            const int n = std::min(B, rows - r0);
+            for (int m = 0; m < M; ++m) {
+                if (!x_dev[m] && !present) continue;
+                const Mod& md = h->mods[m];
+                run_prep_single(h, x_dev[m] ? x_dev[m] + (size_t)r0 * ld[m] : nullptr, ld[m], n, md.n_in, md.X0, nullptr, 0, false,
+                                nullptr, 0, s, r0, present ? present + (size_t)r0 * M + m : nullptr, present ? pres + m : nullptr, M);
+                if (x_dev[m]) run_inference(h, m, true, n, s);
+            }
+            fa.rows = n;
+            fa.mu = mu_dev ? mu_dev + (size_t)r0 * nz : nullptr;
+            fa.lv = logvar_dev ? logvar_dev + (size_t)r0 * nz : nullptr;
+            {
+                Timed t(h, s, "impute_fuse");
+                launch_impute_fuse(h->cfg.compute_dtype, fa, s); LAUNCH_OK("impute_fuse");
+            }
+            if (!decode) continue;
+            if (K == 0) {
+                if (by_mod) {
+                    for (int d = 0; d < M; ++d) {
+                        if (!mean_out[d]) continue;
+                        run_inference(h, d, false, n, s);
+                        copy_out32(h, d, mean_out[d] + (size_t)r0 * h->mods[d].n_in, n, s);
+                    }
+                } else {                           // as avae_generate: the output launch stores straight into the caller's rows
+                    sl.rows = n;
+                    for (int d = 0; d < M; ++d)
+                        sl.out[d] = mean_out[d] ? mean_out[d] + (size_t)r0 * h->mods[d].n_in : h->at<float>(h->mods[d].out32);
+                    serve_call(h, serve_plan(h, serve_bucket(h, n)), sl, s);
+                }
+                continue;
+            }
+            for (int j0 = 0; j0 < n; j0 += n_rows) {           // the sample groups of this chunk's rows [j0, j0 + nj)
+                const int nj = std::min(n_rows, n - j0), q0 = r0 + j0;
+                la.mulv = fused + (size_t)j0 * 2 * nz;
+                la.eps = eps_dev ? eps_dev + (size_t)q0 * K * nz : nullptr;
+                la.row0 = (long long)h->cfg.row_offset + q0;
+                la.rows = aa.rows = nj;
+                for (int m = 0; m < M; ++m) {
+                    aa.mean[m] = mean_out[m] ? mean_out[m] + (size_t)q0 * h->mods[m].n_in : nullptr;
+                    aa.var[m] = var_out[m] ? var_out[m] + (size_t)q0 * h->mods[m].n_in : nullptr;
+                }
+                for (int k0 = 0; k0 < K; k0 += kb) {
+                    const int kc = std::min(kb, K - k0), nd = nj * kc;
+                    la.k0 = aa.k0 = k0; la.kc = aa.kc = kc;
+                    {
+                        Timed t(h, s, "impute_latent");
+                        launch_iw_latent(h->cfg.compute_dtype, la, s); LAUNCH_OK("impute_latent");
+                    }
+                    if (by_mod) {
+                        for (int d = 0; d < M; ++d) run_inference(h, d, false, nd, s);
+                    } else {
+                        for (int c0 = 0; c0 < nd; c0 += B) {   // passes of at most batch_size decoded rows (rows are independent)
+                            sl.z = z32 + (size_t)c0 * nz; sl.rows = std::min(B, nd - c0);
+                            for (int d = 0; d < M; ++d) sl.out[d] = const_cast<float*>(aa.xhat[d]) + (size_t)c0 * h->mods[d].n_in;
+                            serve_call(h, serve_plan(h, serve_bucket(h, sl.rows)), sl, s);
+                        }
+                    }
+                    {
+                        Timed t(h, s, "impute_accum");
+                        launch_impute_accum(aa, s); LAUNCH_OK("impute_accum");
+                    }
+                }
+            }
+        }
+}
+
+int avae_impute(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, const uint8_t* present_dev, int32_t rows,
+                int32_t n_samples, const float* eps_dev, float* mu_dev, float* logvar_dev, float* const* mean_dev,
+                float* const* var_dev, void* stream) {
+    return guarded(h, [&] {
+        impute_call(h, x_dev, x_ld, present_dev, rows, n_samples, eps_dev, mu_dev, logvar_dev, mean_dev, var_dev, stream);
     });
 }
 

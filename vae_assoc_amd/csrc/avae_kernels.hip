@@ -3785,6 +3785,121 @@ void launch_iw_reduce(const IwReduceArgs& a, hipStream_t s) {
     else AVAE_LAUNCH((k_iw_reduce<false>), grid, dim3(kThreads), 0, s, a);
 }
 
+// ------------------------------------------------------------------ fused-posterior prediction (avae_impute)
+// One wave per row, one lane per latent dimension (n_z <= 64; no cross-lane step, so lanes >= n_z leave at once).  S = the row's
+// present modalities (MASK: row_presence of the staged bytes, else the call's `mods`; either way an SGPR mask, every gate a scalar
+// branch).  a_m = -lv_m, A = max a_m, w_m = exp(a_m - A), added in modality order:
+//   mu_f = (sum w_m mu_m) / (sum w_m),   lv_f = -(A + log((sum w_m) / |S|))
+// |S| = 1 selects that modality's (mu, lv) bit for bit, |S| = 0 stores the prior (+0.0, +0.0).  An absent modality's mulv rows are
+// never loaded.  mu_f also goes out as z when the call decodes the mean (n_samples = 0).
+template <typename CT, bool MASK>
+__global__ void __launch_bounds__(kThreads) k_impute_fuse(ImputeFuseArgs a) {
+#pragma clang fp contract(off)
+    const int row = blockIdx.x * kScoreRows + (threadIdx.x >> 6), d = threadIdx.x & 63;
+    const int nz = a.nz;
+    if (row >= a.rows || d >= nz) return;
+    unsigned pm = a.mods;
+    if constexpr (MASK) pm &= row_presence(a.present, row, a.n_mod);
+    const int cnt = __builtin_popcount(pm);
+    float mu[kMaxMod], lv[kMaxMod];
+    float A = -__builtin_inff(), mu_f = 0.0f, lv_f = 0.0f;
+#pragma unroll
+    for (int m = 0; m < kMaxMod; ++m) {
+        mu[m] = lv[m] = 0.0f;
+        if (pm >> m & 1) {                         // (wave-uniform)
+            mu[m] = mu_f = a.mulv[m][(size_t)row * 2 * nz + d];
+            lv[m] = lv_f = a.mulv[m][(size_t)row * 2 * nz + nz + d];
+            A = fmaxf(A, -lv[m]);
+        }
+    }
+    if (cnt > 1) {                                 // (cnt == 1: mu_f / lv_f hold the one modality's values, cnt == 0: the prior)
+        float sw = 0.0f, smu = 0.0f;
+#pragma unroll
+        for (int m = 0; m < kMaxMod; ++m) {
+            if (pm >> m & 1) {
+                const float w = expf(-lv[m] - A);
+                sw += w;
+                smu += w * mu[m];
+            }
+        }
+        mu_f = smu / sw;
+        lv_f = -(A + logf(sw / (float)cnt));
+    }
+    a.fused[(size_t)row * 2 * nz + d] = mu_f;
+    a.fused[(size_t)row * 2 * nz + nz + d] = lv_f;
+    if (a.mu) a.mu[(size_t)row * nz + d] = mu_f;
+    if (a.lv) a.lv[(size_t)row * nz + d] = lv_f;
+    if (a.z32) a.z32[(size_t)row * nz + d] = mu_f;
+    for (int m = 0; m < a.n_zdst; ++m) reinterpret_cast<CT*>(a.Z[m])[(size_t)row * a.ldz[m] + d] = to_ct<CT>(mu_f);
+}
+
+// One wave per (input row j of the pass, modality, tile of 64 output columns), lanes on consecutive columns (coalesced loads of
+// every decoded row); the item index is wave-uniform, so the modality's pointers are scalar selects.  Welford's update over the
+// pass's kc decoded rows i = j * kc + k, sequentially in sample order with the running (mean, M2) in registers:
+//   delta = x - mean;  mean += delta / (k + 1);  M2 += delta * (x - mean)
+// A row that spans several passes carries (mean, M2) in `state`; its last sample block stores mean and M2 / K (the population
+// variance; K = 1 gives +0.0).  Per element the sequence of operations does not depend on how K is split into passes.
+__global__ void __launch_bounds__(kThreads) k_impute_accum(ImputeAccumArgs a) {
+#pragma clang fp contract(off)
+    const int g = __builtin_amdgcn_readfirstlane(blockIdx.x * kScoreRows + (threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const int tiles = a.tile0[a.n_mod];
+    if (g >= a.rows * tiles) return;               // wave-uniform
+    const int j = g / tiles, t = g - j * tiles;
+    const float* xh = a.xhat[0];
+    float* mean_p = a.mean[0];
+    float* var_p = a.var[0];
+    int ldh = a.ldh[0], n_in = a.n_in[0], t0 = 0, c0 = 0;
+#pragma unroll
+    for (int q = 1; q < kMaxMod; ++q) {
+        if (q < a.n_mod && t >= a.tile0[q]) {
+            xh = a.xhat[q]; mean_p = a.mean[q]; var_p = a.var[q];
+            ldh = a.ldh[q]; n_in = a.n_in[q]; t0 = a.tile0[q]; c0 = a.col0[q];
+        }
+    }
+    const int c = (t - t0) * 64 + lane;
+    if (c >= n_in) return;
+    float2* st = reinterpret_cast<float2*>(a.state) + ((size_t)j * a.ld_state + c0 + c);
+    float mean = 0.0f, M2 = 0.0f;
+    if (a.k0 > 0) { const float2 v = *st; mean = v.x; M2 = v.y; }
+    const float* p = xh + (size_t)j * a.kc * ldh + c;
+    auto update = [&](float x, int n) {            // n = samples seen, this one included
+        const float dl = x - mean;
+        mean += dl / (float)n;
+        M2 += dl * (x - mean);
+    };
+    int k = 0;
+    for (; k + 8 <= a.kc; k += 8) {                // eight independent loads in flight ahead of the dependent chain
+        float x[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) x[u] = p[(size_t)(k + u) * ldh];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) update(x[u], a.k0 + k + u + 1);
+    }
+    for (; k < a.kc; ++k) update(p[(size_t)k * ldh], a.k0 + k + 1);
+    if (a.k0 + a.kc == a.K) {
+        if (mean_p) mean_p[(size_t)j * n_in + c] = mean;
+        if (var_p) var_p[(size_t)j * n_in + c] = M2 / (float)a.K;
+    } else {
+        *st = make_float2(mean, M2);
+    }
+}
+
+void launch_impute_fuse(int compute_dtype, const ImputeFuseArgs& a, hipStream_t s) {
+    if (a.rows <= 0) return;
+    const dim3 grid((a.rows + kScoreRows - 1) / kScoreRows);
+    if (a.present) {
+        if (compute_dtype == AVAE_BF16) AVAE_LAUNCH((k_impute_fuse<__bf16, true>), grid, dim3(kThreads), 0, s, a);
+        else AVAE_LAUNCH((k_impute_fuse<float, true>), grid, dim3(kThreads), 0, s, a);
+    } else if (compute_dtype == AVAE_BF16) AVAE_LAUNCH((k_impute_fuse<__bf16, false>), grid, dim3(kThreads), 0, s, a);
+    else AVAE_LAUNCH((k_impute_fuse<float, false>), grid, dim3(kThreads), 0, s, a);
+}
+
+void launch_impute_accum(const ImputeAccumArgs& a, hipStream_t s) {
+    const int n = a.rows * a.tile0[a.n_mod];
+    if (n <= 0) return;
+    AVAE_LAUNCH(k_impute_accum, dim3((n + kScoreRows - 1) / kScoreRows), dim3(kThreads), 0, s, a);
+}
+
 // ------------------------------------------------------------------ gradient latent refinement (avae_complete)
 // Same shapes and no-atomics rule as the score kernels: one wave64 per row (and modality), every sum a fixed-order shuffle tree.
 

@@ -263,6 +263,26 @@ def create_replica(L, cfg, sync, comm, device, agree_dev):
     return h, comm, ws, buckets
 
 
+def impute_args(X, present, n_samples, eps, widths, n_z, device):
+    """The arguments of ``impute`` checked and marshalled -> (tensors, N, was_numpy, ptrs, lds, presence or None, K, eps or None).
+    Every shape or ``n_samples`` error is a ``ValueError`` raised here, ahead of any launch; touches neither a model nor the
+    library (``device="cpu"`` works)."""
+    if isinstance(n_samples, bool) or not isinstance(n_samples, (int, np.integer)) or n_samples < 0:
+        raise ValueError("n_samples must be an integer >= 0, got %r" % (n_samples,))
+    K = int(n_samples)
+    if present is None:
+        ts, rows, was_np, ptrs, lds = dev_modalities(X, widths, device, allow_none=True)
+        if rows is None:
+            raise ValueError("every modality is None and there is no present array: the row count is unknown")
+        p = None
+    else:
+        ts, rows, was_np, ptrs, lds, p = dev_row_args(X, widths, device, present)
+    if K == 0 and eps is not None:
+        raise ValueError("eps needs n_samples >= 1 (n_samples = 0 decodes the fused mean, without noise)")
+    e = dev_dense3(eps, (rows, K, n_z), device)
+    return ts, rows, was_np, ptrs, lds, p, K, e
+
+
 class AssocVariationalAutoEncoder(object):
     """Associative VAE over M sensory modalities, trained on one MI355X (or one per rank).
 
@@ -662,6 +682,39 @@ class AssocVariationalAutoEncoder(object):
                         "avae_complete")
         conv = (lambda a: a.cpu().numpy()) if was_np else (lambda a: a)
         return {"z": conv(out_z), "x": [conv(o) for o in outs], "objective": conv(obj), "grad0": conv(grad)}
+
+    def impute(self, X, present=None, n_samples=0, eps=None):
+        """Predict every modality from the ones each row has (avae_impute in include/avae.h): the
+        per-modality posteriors of the present modalities are fused into the Gaussian closest to all of them in the symmetric-KL
+        sense the model is trained with (precision = mean of the precisions, precision-weighted mean), and every decoder runs on it.
+
+        ``X`` is a list over modalities, ``X[m] = None`` a modality absent from every row; ``present`` is None (every given
+        modality is present on every row) or an [N, M] bool / integer array or tensor as in ``score_samples_masked``.  The row
+        count comes from ``present``, or else from the first modality that is not None.  Absent entries are never read.  A row
+        with one modality gets exactly that modality's posterior, a row with none the prior (mu = logvar = 0).
+        ``n_samples = 0`` decodes the fused mean once (``generate(mu)``); ``n_samples = K >= 1`` decodes K samples
+        ``z_k = mu + exp(logvar / 2) eps_k`` and returns the per-element mean and population variance over them, without ever
+        holding the ``N K n_input`` decoded values.  ``eps`` is an [N, K, n_z] array or None for a fresh internal draw (the draw
+        counter is the one ``score_samples`` / ``log_likelihood`` advance).
+
+        Returns a dict: ``mu [N, n_z]``, ``logvar [N, n_z]``, ``mean`` (list over modalities of ``[N, n_input_m]``, present
+        modalities included: for them it is a reconstruction) and ``var`` (such a list, or None when ``n_samples == 0``).  NumPy
+        in gives NumPy out, device tensors in give device tensors out."""
+        widths = self._widths
+        M = len(widths)
+        ts, rows, was_np, xp, lds, p, K, e = impute_args(X, present, n_samples, eps, widths, self.n_z, self.device)
+        new = lambda cols: torch.empty((rows, cols), dtype=torch.float32, device=self.device)
+        mu, lv = new(self.n_z), new(self.n_z)
+        mean = [new(cols) for cols in widths]
+        var = [new(cols) for cols in widths] if K else None
+        mp = (C.c_void_p * M)(*[o.data_ptr() for o in mean])
+        vp = (C.c_void_p * M)(*[o.data_ptr() for o in var]) if K else None
+        if rows:
+            _capi.check(self._h, self._L.avae_impute(self._h, xp, lds, ptr(p), rows, K, ptr(e), mu.data_ptr(), lv.data_ptr(), mp, vp,
+                                                     self._stream()), "avae_impute")
+        conv = (lambda a: a.cpu().numpy()) if was_np else (lambda a: a)
+        return {"mu": conv(mu), "logvar": conv(lv), "mean": [conv(o) for o in mean],
+                "var": [conv(o) for o in var] if K else None}
 
     def save_model(self, fname=None):
         """reference vae_assoc.py:427-435 (default name: timestamp + batch size)."""
