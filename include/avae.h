@@ -193,6 +193,53 @@ int avae_train_steps_masked(avae_handle* h, int32_t n_steps, const float* const*
 int avae_eval_cost_masked(avae_handle* h, const float* const* x_dev, const int32_t* x_ld,
                           const uint8_t* present_dev, const float* eps_dev, float* cost_host, void* stream);
 
+/* ---- denoising training (the reference has none: vae_assoc.py:90 feeds one placeholder to the encoder and to the loss).  Per
+ * modality m a step has a target x_m and an encoder input x~_m: the encoder (and its first layer's weight gradient) reads x~_m, the
+ * reconstruction term is charged against x_m, so
+ *   cost = loss_terms(forward(x~), x)      and the step's gradient is its gradient; presence masks gate as above; Adam is unchanged.
+ * x~_m is, in this order of precedence,
+ *  1. in_dev[m], an explicit input: device [rows, n_input_m] float32 with its own row stride in_ld[m] (NULL / 0 = dense), read
+ *     exactly as x_dev[m] is (any dword alignment, any column block of a wider matrix);
+ *  2. x_m corrupted on the device, when avae_set_corruption set a drop_prob or noise_std for m -- per element, iid:
+ *       x~ = dropped ? drop_value_m : (noise_std_m > 0 ? x + noise_std_m * n : x),   dropped ~ Bernoulli(drop_prob_m),  n ~ N(0,1)
+ *     the drop is a select: a NaN in a dropped element of x does not reach x~ (it still reaches the target, as ever);
+ *  3. x_m itself: staging then writes the bits it always wrote.
+ * The corruption stream is Philox4x32-10 under the handle's seed, like the eps stream but under salts of its own.  With R the global
+ * row (row_offset + local row), q the column quad (column / 4), t the step the batch belongs to (the device step counter + the
+ * batch's index in the submission), SALT_DROP = 0x64726f70, SALT_NOISE = 0x6e6f6973:
+ *   w = philox(counter = (R, q, t_lo, t_hi ^ (SALT + m)), key = (seed_lo, seed_hi))
+ *   drop : element e of the quad is dropped iff (w[e] >> 8) < floor(drop_prob_m * 2^24)        (the product taken in double)
+ *   noise: n[0..3] = the Box-Muller pairs of w, formed exactly as the internal eps is
+ * so x~ of step t is the same whether the step runs alone or inside a 16- or 4-step replay, masked or not, on one replica or as the
+ * shard [row_offset, row_offset + batch_size) of a global batch, and after avae_load / avae_set_opt_state restored the step
+ * counter.  Every rank of a data-parallel run must share the seed, as it must for eps.  A stream is drawn only for a modality whose
+ * parameter is nonzero.
+ * avae_set_corruption: NULL or all zero = off.  Errors (the message names the field): drop_prob outside [0, 1), a negative or
+ * non-finite noise_std, a non-finite drop_value.  The setting is handle state, set under the handle's mutex; it is not part of
+ * avae_save / avae_load, and work already enqueued keeps the setting it was enqueued with.  Once set, EVERY training call corrupts:
+ * avae_train_step, avae_train_steps, avae_train_steps_masked, avae_stage_batches and the library-owned data-parallel pipeline are
+ * the _in calls below with in_dev NULL.  Evaluation never corrupts: avae_eval_cost, avae_eval_cost_masked and every inference call
+ * are bit for bit what they are without it, and avae_eval_cost_in uses explicit inputs only (the objective on given corrupted
+ * inputs).
+ * The _in calls: in_dev NULL, or in_dev[m] NULL = no explicit input for m; present_dev NULL = unmasked, else the masked twin (an
+ * absent (row, m) reads neither x nor in; a data-parallel handle is refused as avae_train_steps_masked refuses it).  Errors:
+ * in_ld[m] < n_input_m; in_dev[m] set while x_dev[m] is NULL.  With every optional argument NULL and no corruption set they are
+ * bitwise avae_train_steps / avae_eval_cost / avae_stage_batches. */
+typedef struct avae_corruption {
+    float drop_prob[AVAE_MAX_MODALITIES];   /* in [0, 1) */
+    float drop_value[AVAE_MAX_MODALITIES];  /* finite; 0 = erased ink */
+    float noise_std[AVAE_MAX_MODALITIES];   /* >= 0 */
+} avae_corruption;
+int avae_set_corruption(avae_handle* h, const avae_corruption* corruption);
+int avae_train_steps_in(avae_handle* h, int32_t n_steps, const float* const* x_dev, const int32_t* x_ld,
+                        const float* const* in_dev, const int32_t* in_ld, const uint8_t* present_dev,
+                        const float* eps_dev, float* cost_host, void* stream);
+int avae_eval_cost_in(avae_handle* h, const float* const* x_dev, const int32_t* x_ld,
+                      const float* const* in_dev, const int32_t* in_ld, const uint8_t* present_dev,
+                      const float* eps_dev, float* cost_host, void* stream);
+int avae_stage_batches_in(avae_handle* h, int32_t n_steps, const float* const* x_dev, const int32_t* x_ld,
+                          const float* const* in_dev, const int32_t* in_ld, const float* eps_dev, void* stream);
+
 /* evaluate_cost (vae_assoc.py:388-391): forward + loss, no update. */
 int avae_eval_cost(avae_handle* h, const float* const* x_dev, const int32_t* x_ld,
                    const float* eps_dev, float* cost_host, void* stream);
@@ -366,7 +413,8 @@ int avae_comm_allreduce(avae_handle* h, int32_t bucket, void* stream);
 /* Copies a named internal tensor to the host as fp32 (tests): "mulv<m>" [batch,2*n_z], "eps" [batch,n_z], "E<m>_<k>" / "D<m>_<k>" the
  * stored output of encoder / decoder hidden layer k of modality m [batch, width] (the last forward pass's relu decisions);
  * "shadow_err" -> {max |W - theta|, max |W^T - theta|, layers checked, worst layer}: the compute-dtype weight shadows against the
- * parameters rounded once (must be 0, 0 after any call). */
+ * parameters rounded once (must be 0, 0 after any call); "X<m>" staging set 0's encoder input of modality m [batch, n_input] (the
+ * compute-dtype copy, widened), "T<m>" its exact loss target. */
 int avae_debug_fetch(avae_handle* h, const char* name, float* host_dst, size_t max_floats, size_t* n_floats);
 
 #ifdef __cplusplus

@@ -49,7 +49,7 @@ print("grad view:", g.dtype, tuple(g.shape), "offset %% 256 = %d" % (g.data_ptr(
 L, h, st = b._L, b._h, b._stream()
 for i0 in range(0, 21, 16):          # what partial_fit_steps does with a host-owned collective, the collective forced at world_size 1
     n = min(16, 21 - i0)
-    ts, ptrs, lds, e, _ = b._batch_args([x[i0 * B:(i0 + n) * B] for x in X], None, n)
+    ts, ptrs, lds, e, _, _ = b._batch_args([x[i0 * B:(i0 + n) * B] for x in X], None, n)
     assert L.avae_stage_batches(h, n, ptrs, lds, None, st) == 0
     for j in range(n):
         b._staged_j = j

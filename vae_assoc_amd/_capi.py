@@ -34,6 +34,7 @@ SYMBOLS = [
     "avae_dp_plan", "avae_dp_backward", "avae_dp_apply", "avae_comm_unique_id", "avae_comm_ipc_handle", "avae_comm_ipc_attach",
     "avae_eval_cost", "avae_encode", "avae_decode", "avae_generate", "avae_reconstruct", "avae_save", "avae_load",
     "avae_score_width", "avae_score", "avae_loglik", "avae_score_masked", "avae_loglik_masked", "avae_train_steps_masked", "avae_eval_cost_masked", "avae_complete", "avae_impute",
+    "avae_set_corruption", "avae_train_steps_in", "avae_eval_cost_in", "avae_stage_batches_in",
     "avae_synchronize", "avae_timing_enable", "avae_timing_report", "avae_debug_fetch", "avae_comm_allreduce",
 ]
 
@@ -56,6 +57,11 @@ class Config(C.Structure):
                 ("seed", C.c_uint64), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
                 ("use_comm", C.c_int32), ("world_size", C.c_int32), ("rank", C.c_int32), ("comm_buckets", C.c_int32),
                 ("nccl_id", C.c_uint8 * 128), ("wire_dtype", C.c_int32), ("reserved2", C.c_int32 * 3)]
+
+
+class Corruption(C.Structure):
+    _fields_ = [("drop_prob", C.c_float * AVAE_MAX_MODALITIES), ("drop_value", C.c_float * AVAE_MAX_MODALITIES),
+                ("noise_std", C.c_float * AVAE_MAX_MODALITIES)]
 
 
 _lib = None
@@ -99,6 +105,10 @@ def lib():
             L.avae_eval_cost.argtypes = [vp, C.POINTER(vp), C.POINTER(i32), vp, fp, vp]
             L.avae_train_steps_masked.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(i32), vp, vp, fp, vp]
             L.avae_eval_cost_masked.argtypes = [vp, C.POINTER(vp), C.POINTER(i32), vp, vp, fp, vp]
+            L.avae_set_corruption.argtypes = [vp, C.POINTER(Corruption)]
+            L.avae_train_steps_in.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(i32), C.POINTER(vp), C.POINTER(i32), vp, vp, fp, vp]
+            L.avae_eval_cost_in.argtypes = [vp, C.POINTER(vp), C.POINTER(i32), C.POINTER(vp), C.POINTER(i32), vp, vp, fp, vp]
+            L.avae_stage_batches_in.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(i32), C.POINTER(vp), C.POINTER(i32), vp, vp]
             L.avae_encode.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp]
             L.avae_decode.argtypes = [vp, i32, vp, i32, vp, vp]
             L.avae_generate.argtypes = [vp, vp, i32, C.POINTER(vp), vp]

@@ -64,6 +64,40 @@ def dev_modalities(X, widths, device, rows=None, what=None, allow_none=False):
     return ts, rows, was_np, (C.c_void_p * M)(*ptrs), (C.c_int32 * M)(*lds)
 
 
+def dev_inputs(inputs, ts, widths, device, rows, what=None):
+    """Explicit encoder inputs of the denoising calls: a list like ``X`` whose entries may be None (no explicit input for that
+    modality), marshalled exactly as ``X`` is -> (tensors, ptrs, lds).  ``ts`` are ``X``'s tensors: an input for a modality whose
+    ``X[m]`` is None has no target and is refused."""
+    its, _, _, ptrs, lds = dev_modalities(inputs, widths, device, rows, what, allow_none=True)
+    for m, (t, x) in enumerate(zip(its, ts)):
+        if t is not None and x is None:
+            raise ValueError("inputs[%d] is given while X[%d] is None: an encoder input needs its target" % (m, m))
+    return its, ptrs, lds
+
+
+def corruption_fields(drop, noise, drop_value, n_mod):
+    """The arguments of ``set_corruption`` -> (drop_prob, noise_std, drop_value), three lists of ``n_mod`` floats.  Each argument
+    is a scalar (every modality) or a list with one value per modality; ``drop=None`` is off (all zeros).  The ranges are
+    avae_set_corruption's, checked here so that a bad value raises ``ValueError`` ahead of the library."""
+    if drop is None:
+        return [0.0] * n_mod, [0.0] * n_mod, [0.0] * n_mod
+
+    def per_mod(v, name):
+        vs = [v] * n_mod if np.isscalar(v) else list(v)
+        if len(vs) != n_mod:
+            raise ValueError("%s must be a scalar or a list of %d values, got %d" % (name, n_mod, len(vs)))
+        return [float(np.float32(x)) for x in vs]
+    p, s, d = per_mod(drop, "drop"), per_mod(noise, "noise"), per_mod(drop_value, "drop_value")
+    for m in range(n_mod):
+        if not 0.0 <= p[m] < 1.0:
+            raise ValueError("drop[%d] (drop_prob) must be in [0, 1), got %r" % (m, p[m]))
+        if not (np.isfinite(s[m]) and s[m] >= 0.0):
+            raise ValueError("noise[%d] (noise_std) must be finite and >= 0, got %r" % (m, s[m]))
+        if not np.isfinite(d[m]):
+            raise ValueError("drop_value[%d] must be finite, got %r" % (m, d[m]))
+    return p, s, d
+
+
 def dev_row_args(X, widths, device, present=None):
     """Arguments of the row calls (any row count) -> (tensors, N, was_numpy, ptrs, lds, presence or None).  Unmasked, the first
     modality gives N.  Masked, ``present`` [N, M] does, ``X[m] = None`` is a modality absent on every row, and was_numpy is

@@ -231,6 +231,12 @@ struct PrepSeg {
     float* dst32; int ld32;        // nullable
     void* dstc; int ldc;           // row-major compute dtype
     int tiles_r, tiles_c, tile_base;
+    // denoising staging (PrepArgs::noisy; include/avae.h, avae_set_corruption): dst32 keeps the rows of src (the loss target), dstc
+    // gets the encoder's input -- the rows of src_in where the caller gave them, else src corrupted element by element: dropped
+    // (-> drop_value) where the top 24 bits of the element's Philox word are below drop_thr, else + noise_std * N(0,1)
+    const float* src_in; int in_ld;    // nullable
+    unsigned drop_thr;                 // floor(drop_prob * 2^24); 0 = no drop stream
+    float drop_value, noise_std;       // noise_std 0 = no noise stream
 };
 struct PrepArgs {
     PrepSeg seg[kMaxMod];
@@ -255,6 +261,7 @@ struct PrepArgs {
     const unsigned char* pres_src;
     unsigned char* pres_dst;
     int pres_ld;
+    int noisy;                     // some segment has a second source or a corruption: the NOISY instances (else the two above, unchanged)
 };
 
 // Fixed-order sum of the split-K slices of a weight gradient: dst[i] = sum_s src[s*stride + i]  (no atomics: reproducible).
@@ -525,7 +532,7 @@ void launch_grouped_tn(int compute_dtype, int tile_cfg, const TnLaunchArgs& args
                        DevState* st, hipStream_t s, unsigned long long* stamps = nullptr, int launch_id = 0);
 void launch_adam(int compute_dtype, const AdamArgs& a, int n_blocks, hipStream_t s);
 void launch_prep(int compute_dtype, const PrepArgs& a, hipStream_t s);
-const void* prep_kernel(int compute_dtype, bool masked);   // for hipGraphExecKernelNodeSetParams on the captured staging node
+const void* prep_kernel(int compute_dtype, bool masked, bool noisy);   // for hipGraphExecKernelNodeSetParams on the captured staging node
 void launch_fill(void* base, int elem_bytes, unsigned bits, long long start, long long stride, int count, hipStream_t s);
 void launch_sums(const ReduceArgs& a, int n_blocks, hipStream_t s);
 int small_head_lds_bytes();

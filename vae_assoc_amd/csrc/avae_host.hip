@@ -9,6 +9,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <cctype>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -265,6 +266,11 @@ struct avae_handle {
     StepPlan plain, masked;
     unsigned char* pres_buf = nullptr;
     size_t pres_set = 0;                    // bytes per staging set
+
+    // avae_set_corruption: what the training calls' staging does to the encoder's copy of a modality that came without an explicit
+    // input (all zero = off).  Handle state only: not saved, and PrepArgs carry it by value, so enqueued work keeps what it was given.
+    avae_corruption corr{};
+    unsigned drop_thr[kMaxMod] = {};        // floor(drop_prob * 2^24)
 
     // avae_complete: the launches of one refinement pass (decoders forward, then their input-gradient chain from the training plan's
     // item builders on the same buffers), captured as runs of kCompleteSizes[i] passes; the kernels' arguments; the scratch behind
@@ -2102,9 +2108,13 @@ void run_adam(avae_handle* h, int mode, hipStream_t s, int bucket = -1) {
     LAUNCH_OK(mode == 0 ? "adam" : "shadow_refresh");
 }
 
+// Where the encoder's copy of a staged batch comes from when it is not the batch itself (include/avae.h, denoising training):
+// the caller's explicit inputs (null, or null entries: none), else -- `corrupt`: the training calls -- the handle's corruption.
+struct PrepIn { const float* const* in = nullptr; const int32_t* in_ld = nullptr; bool corrupt = false; };
+
 // stages the caller's batch (and eps) into the internal compute-dtype buffers
 PrepArgs make_prep_batch(avae_handle* h, const float* const* x, const int32_t* x_ld, const float* eps, int rows,
-                         unsigned long long salt, int n_steps = 1, const uint8_t* present = nullptr) {
+                         unsigned long long salt, int n_steps = 1, const uint8_t* present = nullptr, const PrepIn& pin = PrepIn()) {
     PrepArgs a;
     std::memset(&a, 0, sizeof(a));
     int base = 0;
@@ -2112,6 +2122,13 @@ PrepArgs make_prep_batch(avae_handle* h, const float* const* x, const int32_t* x
         const Mod& md = h->mods[m];
         PrepSeg& g = a.seg[m];
         g.src = x[m]; g.src_ld = (x_ld && x_ld[m] > 0) ? x_ld[m] : md.n_in;
+        if (pin.in && pin.in[m]) {
+            g.src_in = pin.in[m]; g.in_ld = (pin.in_ld && pin.in_ld[m] > 0) ? pin.in_ld[m] : md.n_in;
+            a.noisy = 1;
+        } else if (pin.corrupt && (h->drop_thr[m] != 0u || h->corr.noise_std[m] > 0.0f)) {
+            g.drop_thr = h->drop_thr[m]; g.drop_value = h->corr.drop_value[m]; g.noise_std = h->corr.noise_std[m];
+            a.noisy = 1;
+        }
         g.rows = rows; g.cols = md.n_in;
         g.dst32 = h->at<float>(md.X32); g.ld32 = md.ld32;
         g.dstc = h->at<void>(md.X0.rm); g.ldc = md.X0.ld;
@@ -2128,8 +2145,8 @@ PrepArgs make_prep_batch(avae_handle* h, const float* const* x, const int32_t* x
 }
 
 void run_prep_batch(avae_handle* h, const float* const* x, const int32_t* x_ld, const float* eps, int rows,
-                    unsigned long long salt, hipStream_t s, const uint8_t* present = nullptr, int n_steps = 1) {
-    const PrepArgs a = make_prep_batch(h, x, x_ld, eps, rows, salt, n_steps, present);
+                    unsigned long long salt, hipStream_t s, const uint8_t* present = nullptr, int n_steps = 1, const PrepIn& pin = PrepIn()) {
+    const PrepArgs a = make_prep_batch(h, x, x_ld, eps, rows, salt, n_steps, present, pin);
     Timed t(h, s, "prep");
     launch_prep(h->cfg.compute_dtype, a, s);
     LAUNCH_OK("prep");
@@ -2189,12 +2206,12 @@ StepGraph capture(avae_handle* h, const std::function<void(hipStream_t)>& body, 
 
 // Points a step graph's staging node at the caller's batch (or run of n_steps consecutive batches).
 void patch_prep(avae_handle* h, const StepGraph& sg, const float* const* x, const int32_t* x_ld, const float* eps,
-                int n_steps = 1, const uint8_t* present = nullptr) {
-    PrepArgs a = make_prep_batch(h, x, x_ld, eps, h->B, 0x7261696eull, n_steps, present);
+                int n_steps, const uint8_t* present, const PrepIn& pin) {
+    PrepArgs a = make_prep_batch(h, x, x_ld, eps, h->B, 0x7261696eull, n_steps, present, pin);
     void* kp[1] = {&a};
     hipKernelNodeParams np;
     std::memset(&np, 0, sizeof(np));
-    np.func = const_cast<void*>(prep_kernel(h->cfg.compute_dtype, present != nullptr));
+    np.func = const_cast<void*>(prep_kernel(h->cfg.compute_dtype, present != nullptr, a.noisy != 0));
     np.gridDim = dim3((a.total_tiles + a.eps_blocks) * n_steps); np.blockDim = dim3(kThreads);
     np.sharedMemBytes = 0; np.kernelParams = kp; np.extra = nullptr;
     HIP_OK(hipGraphExecKernelNodeSetParams(sg.exec, sg.prep, &np));
@@ -2855,21 +2872,33 @@ void check_masked_call(avae_handle* h, const char* what, const float* const* x_d
     if (!present_dev) throw Err(std::string(what) + ": present_dev is null (unmasked calls go through the unmasked entry points)");
 }
 
+// The explicit encoder inputs of an _in call: a modality's input needs its target, and rows at least n_input wide.
+void check_inputs(avae_handle* h, const char* what, const float* const* x_dev, const float* const* in_dev, const int32_t* in_ld) {
+    if (!x_dev) throw Err(std::string(what) + ": null x_dev");
+    for (int m = 0; in_dev && m < h->M; ++m) {
+        if (!in_dev[m]) continue;
+        if (!x_dev[m]) throw Err(std::string(what) + ": in_dev[" + std::to_string(m) + "] is set while x_dev[" + std::to_string(m) + "] is null");
+        if (in_ld && in_ld[m] > 0 && in_ld[m] < h->mods[m].n_in)
+            throw Err(std::string(what) + ": in_ld[" + std::to_string(m) + "] = " + std::to_string(in_ld[m]) + " is below n_input = " +
+                      std::to_string(h->mods[m].n_in));
+    }
+}
+
 // One single-replica step of plan p (present: the masked plan's presence bytes).  With a library-owned collective (plain plan only:
 // masked calls refuse it) the step is staged and runs the bucketed pipeline instead.
 void train_one(avae_handle* h, StepPlan& p, const float* const* x_dev, const int32_t* x_ld, const uint8_t* present, const float* eps_dev,
-               hipStream_t s) {
+               const PrepIn& pin, hipStream_t s) {
     if (h->comm_on) {
-        run_prep_batch(h, x_dev, x_ld, eps_dev, h->B, 0x7261696eull, s);
+        run_prep_batch(h, x_dev, x_ld, eps_dev, h->B, 0x7261696eull, s, nullptr, 1, pin);
         dp_step(h, 0, s);
         return;
     }
     if (p.full.exec && !h->timing) {    // the whole step, staging kernel included, is one graph replay
-        patch_prep(h, p.full, x_dev, x_ld, eps_dev, 1, present);
+        patch_prep(h, p.full, x_dev, x_ld, eps_dev, 1, present, pin);
         HIP_OK(hipGraphLaunch(p.full.exec, s));
         return;
     }
-    run_prep_batch(h, x_dev, x_ld, eps_dev, h->B, 0x7261696eull, s, present);
+    run_prep_batch(h, x_dev, x_ld, eps_dev, h->B, 0x7261696eull, s, present, 1, pin);
     step_body(h, p.fwd, s, 0);
     if (h->timing) {      // floor of the measurement: a one-store kernel (partial slot 0 is rewritten every step anyway)
         Timed t(h, s, "_null_kernel");
@@ -2878,21 +2907,27 @@ void train_one(avae_handle* h, StepPlan& p, const float* const* x_dev, const int
     }
 }
 
-// Batch i of a run of consecutive batches: rows [i*B, (i+1)*B) of every modality (a null one stays null), of the presence bytes
-// and of eps.
+// Batch i of a run of consecutive batches: rows [i*B, (i+1)*B) of every modality (a null one stays null), of its explicit encoder
+// input, of the presence bytes and of eps.
 struct BatchRun {
     const avae_handle* h;
     const float* const* x_dev;
     const int32_t* x_ld;
     const uint8_t* present;
     const float* eps_dev;
+    const float* const* in_dev;
+    const int32_t* in_ld;
     const float* x[kMaxMod] = {};
+    const float* in[kMaxMod] = {};
     const uint8_t* pres = nullptr;
     const float* eps = nullptr;
+    PrepIn pin() const { return PrepIn{in, in_ld, true}; }      // (a training run: the handle's corruption applies)
     void at(int i) {
         for (int m = 0; m < h->M; ++m) {
             const size_t ld = (x_ld && x_ld[m] > 0) ? (size_t)x_ld[m] : (size_t)h->mods[m].n_in;
             x[m] = x_dev[m] ? x_dev[m] + (size_t)i * h->B * ld : nullptr;
+            const size_t ldi = (in_ld && in_ld[m] > 0) ? (size_t)in_ld[m] : (size_t)h->mods[m].n_in;
+            in[m] = (in_dev && in_dev[m]) ? in_dev[m] + (size_t)i * h->B * ldi : nullptr;
         }
         pres = present ? present + (size_t)i * h->B * h->M : nullptr;
         eps = eps_dev ? eps_dev + (size_t)i * h->B * h->nz : nullptr;
@@ -2906,16 +2941,16 @@ int replay_runs(avae_handle* h, StepGraph (&g)[2], BatchRun& b, int n_steps, hip
     for (int gi = 0; gi < 2; ++gi)
         for (; i + kMultiSizes[gi] <= n_steps && ready(gi); i += kMultiSizes[gi]) {
             b.at(i);
-            patch_prep(h, g[gi], b.x, b.x_ld, b.eps, kMultiSizes[gi], b.pres);
+            patch_prep(h, g[gi], b.x, b.x_ld, b.eps, kMultiSizes[gi], b.pres, b.pin());
             HIP_OK(hipGraphLaunch(g[gi].exec, s));
         }
     return i;
 }
 
 // n_steps consecutive batches through plan p (avae_train_steps, avae_train_steps_masked)
-void train_steps(avae_handle* h, StepPlan& p, int n_steps, const float* const* x_dev, const int32_t* x_ld, const uint8_t* present,
-                 const float* eps_dev, float* cost_host, hipStream_t s) {
-    BatchRun b{h, x_dev, x_ld, present, eps_dev};
+void train_steps(avae_handle* h, StepPlan& p, int n_steps, const float* const* x_dev, const int32_t* x_ld, const float* const* in_dev,
+                 const int32_t* in_ld, const uint8_t* present, const float* eps_dev, float* cost_host, hipStream_t s) {
+    BatchRun b{h, x_dev, x_ld, present, eps_dev, in_dev, in_ld};
     int i = 0;
     if (h->comm_on) {               // data parallel: batches staged kMultiSteps at a time, then backward -> all-reduce -> Adam per bucket and step
         // Runs of 16 (then 4) steps as ONE captured graph -- staging kernel, segments, ncclAllReduce on the comm stream (it
@@ -2942,23 +2977,25 @@ void train_steps(avae_handle* h, StepPlan& p, int n_steps, const float* const* x
         for (; i < n_steps; i += kMultiSteps) {
             const int n = std::min(kMultiSteps, n_steps - i);
             b.at(i);
-            run_prep_batch(h, b.x, x_ld, b.eps, h->B, 0x7261696eull, s, nullptr, n);
+            run_prep_batch(h, b.x, x_ld, b.eps, h->B, 0x7261696eull, s, nullptr, n, b.pin());
             for (int j = 0; j < n; ++j) dp_step(h, j, s);
         }
     } else {
         if (!h->timing) i = replay_runs(h, p.multi, b, n_steps, s, [&](int gi) { return p.multi[gi].exec != nullptr; });
         for (; i < n_steps; ++i) {
             b.at(i);
-            train_one(h, p, b.x, x_ld, b.pres, b.eps, s);
+            train_one(h, p, b.x, x_ld, b.pres, b.eps, b.pin(), s);
         }
     }
     fetch_cost(h, cost_host, true, s);
 }
 
 // Forward + cost of one batch through plan p, no update (avae_eval_cost, avae_eval_cost_masked).
-void eval_cost(avae_handle* h, StepPlan& p, const float* const* x_dev, const int32_t* x_ld, const uint8_t* present, const float* eps_dev,
-               float* cost_host, hipStream_t s) {
-    run_prep_batch(h, x_dev, x_ld, eps_dev, h->B, 0x6576616cull /*eval*/ | (unsigned long long)next_draw(h, eps_dev) << 34, s, present);
+// in_dev / in_ld: explicit encoder inputs (avae_eval_cost_in); the handle's corruption never applies to an evaluation.
+void eval_cost(avae_handle* h, StepPlan& p, const float* const* x_dev, const int32_t* x_ld, const float* const* in_dev, const int32_t* in_ld,
+               const uint8_t* present, const float* eps_dev, float* cost_host, hipStream_t s) {
+    run_prep_batch(h, x_dev, x_ld, eps_dev, h->B, 0x6576616cull /*eval*/ | (unsigned long long)next_draw(h, eps_dev) << 34, s, present, 1,
+                   PrepIn{in_dev, in_ld, false});
     if (p.eval.exec && !h->timing) HIP_OK(hipGraphLaunch(p.eval.exec, s));
     else { run_launches(h, p.fwd, s); run_launch(h, h->cost_only, s, nullptr, -1); }
     fetch_cost(h, cost_host, false, s);
@@ -3103,22 +3140,36 @@ int avae_set_opt_state(avae_handle* h, const float* host_m, const float* host_v,
 
 // Data-parallel runs of consecutive batches: one staging launch for up to kMultiSteps batches, then per step
 // backward on its staging set -> (caller's all-reduce) -> apply.
-int avae_stage_batches(avae_handle* h, int32_t n_steps, const float* const* x_dev, const int32_t* x_ld, const float* eps_dev, void* stream) {
+int avae_stage_batches_in(avae_handle* h, int32_t n_steps, const float* const* x_dev, const int32_t* x_ld, const float* const* in_dev,
+                          const int32_t* in_ld, const float* eps_dev, void* stream) {
     return guarded(h, [&] {
         if (n_steps < 1 || n_steps > kMultiSteps) throw Err("avae_stage_batches: n_steps must be in [1," + std::to_string(kMultiSteps) + "]");
-        hipStream_t s = on_stream(h, stream);
-        const PrepArgs a = make_prep_batch(h, x_dev, x_ld, eps_dev, h->B, 0x7261696eull, n_steps);
-        Timed t(h, s, "prep");
-        launch_prep(h->cfg.compute_dtype, a, s);
-        LAUNCH_OK("prep");
+        check_inputs(h, "avae_stage_batches_in", x_dev, in_dev, in_ld);
+        run_prep_batch(h, x_dev, x_ld, eps_dev, h->B, 0x7261696eull, on_stream(h, stream), nullptr, n_steps, PrepIn{in_dev, in_ld, true});
     });
+}
+
+int avae_stage_batches(avae_handle* h, int32_t n_steps, const float* const* x_dev, const int32_t* x_ld, const float* eps_dev, void* stream) {
+    return avae_stage_batches_in(h, n_steps, x_dev, x_ld, nullptr, nullptr, eps_dev, stream);
 }
 
 int avae_train_step(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, const float* eps_dev, float* cost_host, void* stream) {
     return guarded(h, [&] {
         hipStream_t s = on_stream(h, stream);
-        train_one(h, h->plain, x_dev, x_ld, nullptr, eps_dev, s);
+        train_one(h, h->plain, x_dev, x_ld, nullptr, eps_dev, PrepIn{nullptr, nullptr, true}, s);
         fetch_cost(h, cost_host, true, s);
+    });
+}
+
+int avae_train_steps_in(avae_handle* h, int32_t n_steps, const float* const* x_dev, const int32_t* x_ld, const float* const* in_dev,
+                        const int32_t* in_ld, const uint8_t* present_dev, const float* eps_dev, float* cost_host, void* stream) {
+    return guarded(h, [&] {
+        if (present_dev) check_masked_call(h, "avae_train_steps_in", x_dev, present_dev);
+        if (n_steps < 1) throw Err("avae_train_steps_in: n_steps must be >= 1");
+        check_inputs(h, "avae_train_steps_in", x_dev, in_dev, in_ld);
+        if (present_dev) build_masked(h);
+        train_steps(h, present_dev ? h->masked : h->plain, n_steps, x_dev, x_ld, in_dev, in_ld, present_dev, eps_dev, cost_host,
+                    on_stream(h, stream));
     });
 }
 
@@ -3126,7 +3177,25 @@ int avae_train_steps(avae_handle* h, int32_t n_steps, const float* const* x_dev,
                      float* cost_host, void* stream) {
     return guarded(h, [&] {
         if (n_steps < 1) throw Err("avae_train_steps: n_steps must be >= 1");
-        train_steps(h, h->plain, n_steps, x_dev, x_ld, nullptr, eps_dev, cost_host, on_stream(h, stream));
+        train_steps(h, h->plain, n_steps, x_dev, x_ld, nullptr, nullptr, nullptr, eps_dev, cost_host, on_stream(h, stream));
+    });
+}
+
+int avae_set_corruption(avae_handle* h, const avae_corruption* c) {
+    return guarded(h, [&] {
+        avae_corruption v{};
+        unsigned thr[kMaxMod] = {};
+        if (c) v = *c;
+        for (int m = 0; m < AVAE_MAX_MODALITIES; ++m) {
+            const std::string at = "[" + std::to_string(m) + "]";
+            if (!(v.drop_prob[m] >= 0.0f && v.drop_prob[m] < 1.0f)) throw Err("avae_set_corruption: drop_prob" + at + " must be in [0, 1)");
+            if (!std::isfinite(v.drop_value[m])) throw Err("avae_set_corruption: drop_value" + at + " must be finite");
+            if (!(v.noise_std[m] >= 0.0f) || !std::isfinite(v.noise_std[m]))
+                throw Err("avae_set_corruption: noise_std" + at + " must be finite and >= 0");
+            thr[m] = (unsigned)std::floor((double)v.drop_prob[m] * 16777216.0);
+        }
+        h->corr = v;
+        std::memcpy(h->drop_thr, thr, sizeof(thr));
     });
 }
 
@@ -3136,7 +3205,7 @@ int avae_train_steps_masked(avae_handle* h, int32_t n_steps, const float* const*
         check_masked_call(h, "avae_train_steps_masked", x_dev, present_dev);
         if (n_steps < 1) throw Err("avae_train_steps_masked: n_steps must be >= 1");
         build_masked(h);
-        train_steps(h, h->masked, n_steps, x_dev, x_ld, present_dev, eps_dev, cost_host, on_stream(h, stream));
+        train_steps(h, h->masked, n_steps, x_dev, x_ld, nullptr, nullptr, present_dev, eps_dev, cost_host, on_stream(h, stream));
     });
 }
 
@@ -3145,7 +3214,17 @@ int avae_eval_cost_masked(avae_handle* h, const float* const* x_dev, const int32
     return guarded(h, [&] {
         check_masked_call(h, "avae_eval_cost_masked", x_dev, present_dev);
         build_masked(h);
-        eval_cost(h, h->masked, x_dev, x_ld, present_dev, eps_dev, cost_host, on_stream(h, stream));
+        eval_cost(h, h->masked, x_dev, x_ld, nullptr, nullptr, present_dev, eps_dev, cost_host, on_stream(h, stream));
+    });
+}
+
+int avae_eval_cost_in(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, const float* const* in_dev, const int32_t* in_ld,
+                      const uint8_t* present_dev, const float* eps_dev, float* cost_host, void* stream) {
+    return guarded(h, [&] {
+        if (present_dev) check_masked_call(h, "avae_eval_cost_in", x_dev, present_dev);
+        check_inputs(h, "avae_eval_cost_in", x_dev, in_dev, in_ld);
+        if (present_dev) build_masked(h);
+        eval_cost(h, present_dev ? h->masked : h->plain, x_dev, x_ld, in_dev, in_ld, present_dev, eps_dev, cost_host, on_stream(h, stream));
     });
 }
 
@@ -3250,7 +3329,7 @@ int avae_cost_history(avae_handle* h, int32_t n, float* host_dst, int64_t* last_
 }
 
 int avae_eval_cost(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, const float* eps_dev, float* cost_host, void* stream) {
-    return guarded(h, [&] { eval_cost(h, h->plain, x_dev, x_ld, nullptr, eps_dev, cost_host, on_stream(h, stream)); });
+    return guarded(h, [&] { eval_cost(h, h->plain, x_dev, x_ld, nullptr, nullptr, nullptr, eps_dev, cost_host, on_stream(h, stream)); });
 }
 
 int avae_encode(avae_handle* h, int32_t m, const float* x_dev, int32_t x_ld, int32_t rows, float* mu_dev, float* logvar_dev, void* stream) {
@@ -3902,6 +3981,28 @@ int avae_debug_fetch(avae_handle* h, const char* name, float* host_dst, size_t m
                     if (h->es == 2) { const uint32_t u = (uint32_t)reinterpret_cast<const uint16_t*>(raw.data())[(size_t)r * a.ld + c] << 16; std::memcpy(&v, &u, 4); }
                     else v = reinterpret_cast<const float*>(raw.data())[(size_t)r * a.ld + c];
                     host_dst[(size_t)r * a.width + c] = v;
+                }
+            if (n_floats) *n_floats = cnt;
+            return;
+        }
+        else if ((n[0] == 'X' || n[0] == 'T') && n.size() >= 2 && std::isdigit((unsigned char)n[1])) {
+            // "X<m>" / "T<m>": staging set 0's encoder input (compute dtype) / exact loss target of modality m, dense [B][n_input] as fp32
+            const int m = std::atoi(n.c_str() + 1);
+            if (m < 0 || m >= h->M) throw Err("debug_fetch: modality out of range");
+            const Mod& md = h->mods[m];
+            const bool enc = n[0] == 'X';
+            const int ld = enc ? md.X0.ld : md.ld32, esz = enc ? h->es : 4;
+            cnt = (size_t)h->B * md.n_in;
+            if (cnt > max_floats) throw Err("debug_fetch: destination too small");
+            HIP_OK(hipDeviceSynchronize());
+            std::vector<unsigned char> raw((size_t)h->B * ld * esz);
+            HIP_OK(hipMemcpy(raw.data(), enc ? h->at<void>(md.X0.rm) : h->at<void>(md.X32), raw.size(), hipMemcpyDeviceToHost));
+            for (int r = 0; r < h->B; ++r)
+                for (int c = 0; c < md.n_in; ++c) {
+                    float v;
+                    if (esz == 2) { const uint32_t u = (uint32_t)reinterpret_cast<const uint16_t*>(raw.data())[(size_t)r * ld + c] << 16; std::memcpy(&v, &u, 4); }
+                    else v = reinterpret_cast<const float*>(raw.data())[(size_t)r * ld + c];
+                    host_dst[(size_t)r * md.n_in + c] = v;
                 }
             if (n_floats) *n_floats = cnt;
             return;

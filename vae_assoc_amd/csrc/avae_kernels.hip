@@ -2523,8 +2523,63 @@ __device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned
     out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
 
-// MASK: the masked staging (PrepArgs::pres_src set; launch_prep / prep_kernel pick the instance)
-template <typename CT, bool MASK>
+// four N(0,1) from one Philox block
+__device__ __forceinline__ void box_muller4(const unsigned r[4], float n[4]) {
+    // Box-Muller on (0,1) uniforms built from the top 24 bits
+    const float u0 = ((r[0] >> 8) + 0.5f) * (1.0f / 16777216.0f), u1 = ((r[1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
+    const float u2 = ((r[2] >> 8) + 0.5f) * (1.0f / 16777216.0f), u3 = ((r[3] >> 8) + 0.5f) * (1.0f / 16777216.0f);
+    const float ra = sqrtf(-2.0f * flog(u0)), rb = sqrtf(-2.0f * flog(u2));
+    // v_sin_f32 / v_cos_f32 take their argument in revolutions: sin(2*pi*u) directly
+    n[0] = ra * __builtin_amdgcn_cosf(u1); n[1] = ra * __builtin_amdgcn_sinf(u1);
+    n[2] = rb * __builtin_amdgcn_cosf(u3); n[3] = rb * __builtin_amdgcn_sinf(u3);
+}
+
+// the caller's rows as one 16-byte load per quad whatever their alignment (column blocks of a [rows][931] matrix start anywhere)
+typedef float f32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));      // dword-aligned quad: one global_load_dwordx4 (the
+                                                                              // hardware takes any dword alignment in global memory)
+
+// Denoising staging: the encoder's input x of the quad at (row grow, column gcol) of segment w (modality m) whose target quad is v.
+// With a second source it is that source's quad.  Else v corrupted per element from two Philox blocks keyed like the eps stream
+// under salts of their own -- counter (global row, column quad, step lo, step hi ^ (salt + m)), key = the seed -- so that a step's
+// corruption depends on neither the replay it runs in, nor the mask, nor the shard: first the noise, then the drop as a SELECT (a
+// dropped element takes drop_value whatever v holds, NaN included).  Each stream is drawn only where its parameter is set, which
+// is uniform over the segment.
+__device__ __forceinline__ void noisy_quad(const PrepArgs& a, const PrepSeg& w, int m, int bstep, int grow, int gcol, const float v[4],
+                                           float x[4]) {
+    if (w.src_in) {
+        const float* in = w.src_in + ((size_t)bstep * w.rows + grow) * w.in_ld + gcol;
+        if (gcol + 3 < w.cols) {
+            const f32x4_a4 q = *reinterpret_cast<const f32x4_a4*>(in);
+            x[0] = q[0]; x[1] = q[1]; x[2] = q[2]; x[3] = q[3];
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) x[e] = (gcol + e < w.cols) ? in[e] : 0.0f;
+        }
+        return;
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) x[e] = v[e];
+    if (w.drop_thr == 0u && !(w.noise_std > 0.0f)) return;
+    const unsigned long long step = (unsigned long long)a.st->step + (unsigned long long)bstep;
+    const unsigned c0 = (unsigned)(a.row_offset + grow), c1 = (unsigned)(gcol >> 2), c2 = (unsigned)step, c3 = (unsigned)(step >> 32);
+    unsigned r[4];
+    if (w.noise_std > 0.0f) {
+        float n[4];
+        philox4x32_10(c0, c1, c2, c3 ^ (0x6e6f6973u /*nois*/ + (unsigned)m), (unsigned)a.seed, (unsigned)(a.seed >> 32), r);
+        box_muller4(r, n);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) x[e] = __builtin_fmaf(w.noise_std, n[e], v[e]);
+    }
+    if (w.drop_thr != 0u) {
+        philox4x32_10(c0, c1, c2, c3 ^ (0x64726f70u /*drop*/ + (unsigned)m), (unsigned)a.seed, (unsigned)(a.seed >> 32), r);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) x[e] = (r[e] >> 8) < w.drop_thr ? w.drop_value : x[e];
+    }
+}
+
+// MASK: the masked staging (PrepArgs::pres_src set); NOISY: the denoising staging (PrepArgs::noisy: the encoder's input and the
+// loss target differ).  launch_prep / prep_kernel pick the instance.
+template <typename CT, bool MASK, bool NOISY = false>
 __global__ void __launch_bounds__(kThreads) k_prep(PrepArgs a) {
     const int tid = threadIdx.x;
     const int bstep = a.n_steps > 1 ? (int)blockIdx.x / a.blocks_per_step : 0;     // which of the batched steps
@@ -2550,13 +2605,7 @@ __global__ void __launch_bounds__(kThreads) k_prep(PrepArgs a) {
             philox4x32_10((unsigned)(a.row_offset + row), (unsigned)d4 ^ ((unsigned)(a.stream_salt >> 32) << 8), (unsigned)step,
                           (unsigned)(step >> 32) ^ (unsigned)a.stream_salt,
                           (unsigned)a.seed, (unsigned)(a.seed >> 32), r);
-            // Box-Muller on (0,1) uniforms built from the top 24 bits
-            const float u0 = ((r[0] >> 8) + 0.5f) * (1.0f / 16777216.0f), u1 = ((r[1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-            const float u2 = ((r[2] >> 8) + 0.5f) * (1.0f / 16777216.0f), u3 = ((r[3] >> 8) + 0.5f) * (1.0f / 16777216.0f);
-            const float ra = sqrtf(-2.0f * flog(u0)), rb = sqrtf(-2.0f * flog(u2));
-            // v_sin_f32 / v_cos_f32 take their argument in revolutions: sin(2*pi*u) directly
-            n[0] = ra * __builtin_amdgcn_cosf(u1); n[1] = ra * __builtin_amdgcn_sinf(u1);
-            n[2] = rb * __builtin_amdgcn_cosf(u3); n[3] = rb * __builtin_amdgcn_sinf(u3);
+            box_muller4(r, n);
         }
         float* eps_dst = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(a.eps_dst) + set_off);
 #pragma unroll
@@ -2574,9 +2623,6 @@ __global__ void __launch_bounds__(kThreads) k_prep(PrepArgs a) {
     const float* src = w.src + (size_t)bstep * w.rows * w.src_ld;
     float* dst32 = w.dst32 ? reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(w.dst32) + set_off) : nullptr;
     CT* dstc = reinterpret_cast<CT*>(reinterpret_cast<unsigned char*>(w.dstc) + set_off);
-    // the caller's rows as one 16-byte load per quad whatever their alignment (column blocks of a [rows][931] matrix start anywhere)
-    typedef float f32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));      // dword-aligned quad: one global_load_dwordx4 (the
-                                                                                  // hardware takes any dword alignment in global memory)
     if constexpr (MASK) {
         // masked staging: an absent (row, modality) -- every row of a null source -- is never read and staged as zeros; the threads
         // of segment 0's first column tile copy the step's presence bytes (0/1, null sources folded in) into staging set bstep
@@ -2591,6 +2637,7 @@ __global__ void __launch_bounds__(kThreads) k_prep(PrepArgs a) {
             const int r = (tid >> 4) + 16 * i;
             const int grow = r0 + r, gcol = c0 + c4;
             float v[4] = {0.f, 0.f, 0.f, 0.f};
+            [[maybe_unused]] float x[4] = {0.f, 0.f, 0.f, 0.f};            // NOISY: the encoder's quad (absent: zeros, like the target)
             if (grow < w.rows && gcol < w.cols) {
                 if (w.src && pres[(size_t)grow * a.pres_ld + it]) {          // (a null source: modality absent on every row)
                     if (gcol + 3 < w.cols) {
@@ -2601,10 +2648,11 @@ __global__ void __launch_bounds__(kThreads) k_prep(PrepArgs a) {
                         for (int e = 0; e < 4; ++e)
                             if (gcol + e < w.cols) v[e] = src[(size_t)grow * w.src_ld + gcol + e];
                     }
+                    if constexpr (NOISY) noisy_quad(a, w, it, bstep, grow, gcol, v, x);
                 }
                 const int nv = w.cols - gcol;
                 if (dst32) store_row<float>(dst32 + (size_t)grow * w.ld32 + gcol, v, nv);
-                store_row<CT>(dstc + (size_t)grow * w.ldc + gcol, v, nv);
+                store_row<CT>(dstc + (size_t)grow * w.ldc + gcol, NOISY ? x : v, nv);
             }
         }
         return;
@@ -2614,6 +2662,7 @@ __global__ void __launch_bounds__(kThreads) k_prep(PrepArgs a) {
         const int r = (tid >> 4) + 16 * i;
         const int grow = r0 + r, gcol = c0 + c4;
         float v[4] = {0.f, 0.f, 0.f, 0.f};
+        [[maybe_unused]] float x[4];
         if (grow < w.rows && gcol < w.cols) {
             if (gcol + 3 < w.cols) {
                 const f32x4_a4 q = *reinterpret_cast<const f32x4_a4*>(src + (size_t)grow * w.src_ld + gcol);
@@ -2623,26 +2672,36 @@ __global__ void __launch_bounds__(kThreads) k_prep(PrepArgs a) {
                 for (int e = 0; e < 4; ++e)
                     if (gcol + e < w.cols) v[e] = src[(size_t)grow * w.src_ld + gcol + e];
             }
+            if constexpr (NOISY) noisy_quad(a, w, it, bstep, grow, gcol, v, x);
             const int nv = w.cols - gcol;
             if (dst32) store_row<float>(dst32 + (size_t)grow * w.ld32 + gcol, v, nv);
-            store_row<CT>(dstc + (size_t)grow * w.ldc + gcol, v, nv);
+            store_row<CT>(dstc + (size_t)grow * w.ldc + gcol, NOISY ? x : v, nv);
         }
     }
 }
 
-const void* prep_kernel(int compute_dtype, bool masked) {
-    if (masked) return compute_dtype == AVAE_BF16 ? reinterpret_cast<const void*>(k_prep<__bf16, true>) : reinterpret_cast<const void*>(k_prep<float, true>);
-    return compute_dtype == AVAE_BF16 ? reinterpret_cast<const void*>(k_prep<__bf16, false>) : reinterpret_cast<const void*>(k_prep<float, false>);
+template <typename CT> const void* prep_instance(bool masked, bool noisy) {
+    if (noisy) return masked ? reinterpret_cast<const void*>(k_prep<CT, true, true>) : reinterpret_cast<const void*>(k_prep<CT, false, true>);
+    return masked ? reinterpret_cast<const void*>(k_prep<CT, true>) : reinterpret_cast<const void*>(k_prep<CT, false>);
+}
+
+const void* prep_kernel(int compute_dtype, bool masked, bool noisy) {
+    return compute_dtype == AVAE_BF16 ? prep_instance<__bf16>(masked, noisy) : prep_instance<float>(masked, noisy);
+}
+
+template <typename CT> void launch_prep_as(const PrepArgs& a, int n_blocks, hipStream_t s) {
+    if (a.noisy) {
+        if (a.pres_src) AVAE_LAUNCH((k_prep<CT, true, true>), dim3(n_blocks), dim3(kThreads), 0, s, a);
+        else AVAE_LAUNCH((k_prep<CT, false, true>), dim3(n_blocks), dim3(kThreads), 0, s, a);
+    } else if (a.pres_src) AVAE_LAUNCH((k_prep<CT, true>), dim3(n_blocks), dim3(kThreads), 0, s, a);
+    else AVAE_LAUNCH((k_prep<CT, false>), dim3(n_blocks), dim3(kThreads), 0, s, a);
 }
 
 void launch_prep(int compute_dtype, const PrepArgs& a, hipStream_t s) {
     const int n_blocks = (a.total_tiles + a.eps_blocks) * (a.n_steps > 1 ? a.n_steps : 1);
     if (n_blocks <= 0) return;
-    if (a.pres_src) {
-        if (compute_dtype == AVAE_BF16) AVAE_LAUNCH((k_prep<__bf16, true>), dim3(n_blocks), dim3(kThreads), 0, s, a);
-        else AVAE_LAUNCH((k_prep<float, true>), dim3(n_blocks), dim3(kThreads), 0, s, a);
-    } else if (compute_dtype == AVAE_BF16) AVAE_LAUNCH((k_prep<__bf16, false>), dim3(n_blocks), dim3(kThreads), 0, s, a);
-    else AVAE_LAUNCH((k_prep<float, false>), dim3(n_blocks), dim3(kThreads), 0, s, a);
+    if (compute_dtype == AVAE_BF16) launch_prep_as<__bf16>(a, n_blocks, s);
+    else launch_prep_as<float>(a, n_blocks, s);
 }
 
 // ------------------------------------------------------------------ conv branch: im2col / col2im

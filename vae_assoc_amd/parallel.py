@@ -108,13 +108,17 @@ def dp_train_step(replica, sync, X_local, eps_local=None):
     return replica._apply()
 
 
-def dp_train_step_bucketed(replica, sync, buckets, X_local, eps_local=None):
+def dp_train_step_bucketed(replica, sync, buckets, X_local, eps_local=None, inputs_local=None):
     """The same step cut into gradient buckets (a list of range lists, in the order their gradients become available):
     backward part b -> all-reduce of bucket b's ranges, started as soon as they exist and left running beside backward part
     b+1 -> Adam per bucket once its ranges have arrived.  The replica provides ``_stage(X, eps)``, ``_backward_bucket(b)``,
     ``_grad_tensor()`` and ``_apply_bucket(b, want_cost)``; the library-owned RCCL pipeline (avae_host.hip::dp_step) is this
-    schedule on two HIP streams."""
-    replica._stage(X_local, eps_local)
+    schedule on two HIP streams.  ``inputs_local`` (explicit encoder inputs of the local rows, denoising training) is handed to
+    ``_stage`` only when given: a replica without the keyword keeps working."""
+    if inputs_local is None:
+        replica._stage(X_local, eps_local)
+    else:
+        replica._stage(X_local, eps_local, inputs=inputs_local)
     return dp_bucket_schedule(replica, sync, buckets)
 
 

@@ -26,7 +26,8 @@ import numpy as np
 import torch
 
 from . import _capi
-from ._marshal import dev_array, dev_dense, dev_dense3, dev_flags, dev_modalities, dev_row_args, ld_of, ptr
+from ._marshal import (corruption_fields, dev_array, dev_dense, dev_dense3, dev_flags, dev_inputs, dev_modalities, dev_row_args,
+                       ld_of, ptr)
 from .parallel import GradSync, dp_bucket_schedule, dp_train_step_bucketed
 
 _ARCH_KEYS = ("scope", "hidden_conv", "n_hidden_recog_1", "n_hidden_recog_2",
@@ -305,12 +306,14 @@ class AssocVariationalAutoEncoder(object):
       comm_buckets   2 (default): decoder-side bucket first, its all-reduce beside the encoder's backward pass; 1: ONE all-reduce of
                      the whole gradient buffer after the backward pass (north_star's literal design)
       wire_dtype     'fp32' (default) or 'bf16': element type of the gradient on the wire (the cost always travels as fp32)
+      corruption     None, or a dict of ``set_corruption``'s arguments (``drop``, ``noise``, ``drop_value``): denoising training,
+                     every training step corrupts the encoder's copy of the batch on the device while the losses keep the clean one
     """
 
     def __init__(self, network_architectures, binary=True, transfer_fct="softplus", weights=1.0,
                  assoc_lambda=1.0, learning_rate=0.001, batch_size=100, *, compute_dtype="bf16",
                  device=None, seed=0, use_graph=True, data_parallel=False, process_group=None, comm=None,
-                 comm_buckets=2, wire_dtype="fp32"):
+                 comm_buckets=2, wire_dtype="fp32", corruption=None):
         def placement():
             if not torch.cuda.is_available():
                 raise RuntimeError("vae_assoc_amd needs a HIP device (MI355X / gfx950); there is no CPU fallback")
@@ -344,6 +347,8 @@ class AssocVariationalAutoEncoder(object):
         goff = gp.value - self._ws.data_ptr()
         self._grad_view = self._ws[goff:goff + 4 * gn.value].view(torch.float32)
         self.set_params(initial_params(network_architectures, seed))
+        if corruption is not None:
+            self.set_corruption(**corruption)
 
     # ------------------------------------------------------------------ plumbing
     def __del__(self):
@@ -364,10 +369,12 @@ class AssocVariationalAutoEncoder(object):
             name, head = name + "_masked", head + (p.data_ptr(),)
         _capi.check(self._h, getattr(self._L, name)(self._h, *head, *tail, self._stream()), name)
 
-    def _batch_args(self, X, eps, n_steps=1, present=None):
-        """Arguments of the training / eval entry points -> (device tensors, ptrs, lds, eps tensor or None, presence or None).
+    def _batch_args(self, X, eps, n_steps=1, present=None, inputs=None):
+        """Arguments of the training / eval entry points -> (device tensors, ptrs, lds, eps tensor or None, presence or None,
+        explicit inputs (tensors, ptrs, lds) or None).
         ``present`` (the masked entry points): [batch_size * n_steps, M] -> uint8 device tensor, and ``X[m] = None`` -> a NULL
-        source (modality m absent on every row)."""
+        source (modality m absent on every row).  ``inputs`` (the ``_in`` entry points): the encoder's rows, a list like ``X``
+        with None where a modality has no explicit input."""
         # the reference's eps has static shape (batch_size, n_z): every path through z needs exactly batch_size rows (vae_assoc.py:90)
         rows = self.batch_size * n_steps
         what = "batch_size x n_steps" if n_steps > 1 else "batch_size"
@@ -380,13 +387,21 @@ class AssocVariationalAutoEncoder(object):
                 raise RuntimeError("present= (partially paired batches) runs on one replica; this model is data parallel over %d ranks" % world)
             p = dev_flags(present, len(self._widths), self.device, rows, what)
         ts, _, _, ptrs, lds = dev_modalities(X, self._widths, self.device, rows, what, allow_none=p is not None)
-        return ts, ptrs, lds, dev_dense(eps, self.n_z, self.device, rows, what), p
+        ins = None if inputs is None else dev_inputs(inputs, ts, self._widths, self.device, rows, what)
+        return ts, ptrs, lds, dev_dense(eps, self.n_z, self.device, rows, what), p, ins
 
-    def _train(self, X, n_steps, eps, present, return_cost, one_step=False):
-        ts, ptrs, lds, e, p = self._batch_args(X, eps, n_steps, present)
+    def _call_in(self, name, head, ins, p, tail):
+        """Entry point ``name`` with explicit encoder inputs ``ins`` (and optional presence bytes ``p``): the ``_in`` calls take
+        both after (x, ld)."""
+        _capi.check(self._h, getattr(self._L, name)(self._h, *head, ins[1], ins[2], ptr(p), *tail, self._stream()), name)
+
+    def _train(self, X, n_steps, eps, present, return_cost, one_step=False, inputs=None):
+        ts, ptrs, lds, e, p, ins = self._batch_args(X, eps, n_steps, present, inputs)
         cost = C.c_float(0.0)
         tail = (ptr(e), C.byref(cost) if return_cost else None)
-        if one_step and p is None:      # (library-owned collective: avae_train_step runs the bucketed pipeline itself)
+        if ins is not None:
+            self._call_in("avae_train_steps_in", (n_steps, ptrs, lds), ins, p, tail)
+        elif one_step and p is None:    # (library-owned collective: avae_train_step runs the bucketed pipeline itself)
             self._twin("avae_train_step", (ptrs, lds), None, tail)
         else:
             self._twin("avae_train_steps", (n_steps, ptrs, lds), p, tail)
@@ -423,13 +438,29 @@ class AssocVariationalAutoEncoder(object):
                     "avae_cost_history")
         return out
 
+    def set_corruption(self, drop=0.0, noise=0.0, drop_value=0.0):
+        """Denoising training (avae_set_corruption in include/avae.h): from now on every training step
+        feeds the encoders a corrupted copy of the batch, drawn on the device, while the reconstruction terms are charged against
+        the clean batch.  Per element, independently: with probability ``drop`` it is replaced by ``drop_value`` (0 = erased
+        ink), else N(0, ``noise``^2) is added.  Each argument is a scalar (every modality) or a list with one value per modality;
+        ``set_corruption(None)`` (or all zeros) turns it off.  A modality given through ``inputs=`` is not corrupted.
+
+        Evaluation stays clean: ``evaluate_cost``, the early-stop validation cost of ``train`` and every inference call ignore
+        the setting.  The draw is keyed by (seed, step, global row, modality, column): under data parallelism every rank must be
+        built with the same ``seed``, as for eps.  The setting is not saved by ``save_model``."""
+        p, s, d = corruption_fields(drop, noise, drop_value, len(self._widths))
+        c = _capi.Corruption()
+        for m in range(len(self._widths)):
+            c.drop_prob[m], c.noise_std[m], c.drop_value[m] = p[m], s[m], d[m]
+        _capi.check(self._h, self._L.avae_set_corruption(self._h, C.byref(c)), "avae_set_corruption")
+
     def synchronize(self):
         _capi.check(self._h, self._L.avae_synchronize(self._h), "avae_synchronize")
 
     # ------------------------------------------------------------------ data-parallel seam (parallel.py protocol)
-    def _backward(self, X, eps=None):
+    def _backward(self, X, eps=None, inputs=None):
         """local forward + backward + every weight gradient: the gradient buffer (and the local cost in its last float) is complete"""
-        self._stage(X, eps)
+        self._stage(X, eps, inputs=inputs)
         for b in range(len(self._buckets)):
             self._backward_bucket(b)
 
@@ -443,10 +474,23 @@ class AssocVariationalAutoEncoder(object):
         return self._grad_view
 
     # bucketed seam (parallel.dp_train_step_bucketed): stage -> per bucket backward / all-reduce -> per bucket Adam
-    def _stage(self, X, eps=None, n_steps=1):
-        ts, ptrs, lds, e, _ = self._batch_args(X, eps, n_steps)
-        _capi.check(self._h, self._L.avae_stage_batches(self._h, n_steps, ptrs, lds, ptr(e), self._stream()), "avae_stage_batches")
+    def _stage(self, X, eps=None, n_steps=1, inputs=None):
+        ts, ptrs, lds, e, _, ins = self._batch_args(X, eps, n_steps, inputs=inputs)
+        self._stage_run(n_steps, ts, lds, e, ins, 0)
         self._staged_j = 0
+
+    def _stage_run(self, n, ts, lds, e, ins, i0):
+        """stages batches [i0, i0 + n) of the marshalled run (``avae_stage_batches``, or its ``_in`` twin with explicit inputs)"""
+        B = self.batch_size
+        at = lambda t: None if t is None else t.data_ptr() + i0 * B * t.stride(0) * 4
+        p_i = (C.c_void_p * len(ts))(*[at(t) for t in ts])
+        e_i = (e.data_ptr() + i0 * B * self.n_z * 4) if e is not None else None
+        if ins is None:
+            _capi.check(self._h, self._L.avae_stage_batches(self._h, n, p_i, lds, e_i, self._stream()), "avae_stage_batches")
+        else:
+            in_i = (C.c_void_p * len(ts))(*[at(t) for t in ins[0]])
+            _capi.check(self._h, self._L.avae_stage_batches_in(self._h, n, p_i, lds, in_i, ins[2], e_i, self._stream()),
+                        "avae_stage_batches_in")
 
     def _backward_bucket(self, b):
         _capi.check(self._h, self._L.avae_dp_backward(self._h, self._staged_j, b, self._stream()), "avae_dp_backward")
@@ -457,48 +501,55 @@ class AssocVariationalAutoEncoder(object):
         return cost.value if want_cost else None
 
     # ------------------------------------------------------------------ reference surface
-    def partial_fit(self, X, eps=None, return_cost=True, present=None):
+    def partial_fit(self, X, eps=None, return_cost=True, present=None, inputs=None):
         """Train model based on mini-batch of input data.  Return cost of mini-batch.
         (reference vae_assoc.py:378-386).  ``return_cost=False`` skips the host synchronise;
         the cost stays retrievable through ``cost_history``.
 
         ``present`` (optional, one replica): [batch_size, M] presence flags, nonzero = row n has modality m.  The step then charges
         every row only with the terms of the modalities it has (include/avae.h; the divisor stays batch_size),
-        and ``X[m]`` may be None for a modality absent from the whole batch."""
+        and ``X[m]`` may be None for a modality absent from the whole batch.
+
+        ``inputs`` (optional): explicit encoder inputs, a list like ``X`` whose entries may be None -- the encoder of modality m
+        reads ``inputs[m]`` while every loss term is charged against ``X[m]`` (denoising training with corruption of the caller's
+        own; ``set_corruption`` draws one on the device instead).  Column views of one wide matrix work without a copy, as for
+        ``X``."""
         if present is None and self._sync is not None and self._sync.world_size > 1 and not self._comm_lib:
             # host-owned collective (torch.distributed) over the library's buckets
-            cost = dp_train_step_bucketed(self, self._sync, self._buckets, X, eps)
+            cost = dp_train_step_bucketed(self, self._sync, self._buckets, X, eps, inputs)
             return cost if return_cost else None
-        return self._train(X, 1, eps, present, return_cost, one_step=True)
+        return self._train(X, 1, eps, present, return_cost, one_step=True, inputs=inputs)
 
-    def partial_fit_steps(self, X, n_steps, eps=None, return_cost=True, present=None):
+    def partial_fit_steps(self, X, n_steps, eps=None, return_cost=True, present=None, inputs=None):
         """``n_steps`` successive ``partial_fit`` calls in one submission: step i trains on rows
         [i*batch_size, (i+1)*batch_size) of every X[m] (and of ``eps``) -- what the reference's inner
         loop does with ``DataSet.next_batch``'s consecutive slices (vae_assoc.py:541-550).  Returns the
         last step's cost; every step's cost is in ``cost_history``.  ``present``: [n_steps * batch_size, M]
-        presence flags, as in ``partial_fit``."""
+        presence flags, ``inputs``: explicit encoder inputs of the same rows, both as in ``partial_fit``."""
         n_steps = int(n_steps)
         if present is not None or self._sync is None or self._sync.world_size == 1 or self._comm_lib:
-            return self._train(X, n_steps, eps, present, return_cost)
+            return self._train(X, n_steps, eps, present, return_cost, inputs=inputs)
         # host-owned collective: the batches are staged 16 at a time, every step runs the bucketed schedule
-        ts, ptrs, lds, e, _ = self._batch_args(X, eps, n_steps)
-        B, cost, st = self.batch_size, None, self._stream()
+        ts, ptrs, lds, e, _, ins = self._batch_args(X, eps, n_steps, inputs=inputs)
+        cost = None
         for i0 in range(0, n_steps, 16):
             n = min(16, n_steps - i0)
-            p_i = (C.c_void_p * len(ts))(*[t.data_ptr() + i0 * B * t.stride(0) * 4 for t in ts])
-            e_i = (e.data_ptr() + i0 * B * self.n_z * 4) if e is not None else None
-            _capi.check(self._h, self._L.avae_stage_batches(self._h, n, p_i, lds, e_i, st), "avae_stage_batches")
+            self._stage_run(n, ts, lds, e, ins, i0)
             for j in range(n):
                 self._staged_j = j
                 cost = dp_bucket_schedule(self, self._sync, self._buckets, return_cost and i0 + j == n_steps - 1)
         return cost
 
-    def evaluate_cost(self, X, eps=None, present=None):
+    def evaluate_cost(self, X, eps=None, present=None, inputs=None):
         """reference vae_assoc.py:388-391 (forward + loss with a fresh eps, no update).  ``present``: [batch_size, M] presence
-        flags, as in ``partial_fit`` (one replica)."""
-        ts, ptrs, lds, e, p = self._batch_args(X, eps, present=present)
+        flags, as in ``partial_fit`` (one replica).  ``inputs``: explicit encoder inputs as in ``partial_fit`` -- the objective on
+        given corrupted inputs; a corruption set with ``set_corruption`` never applies here."""
+        ts, ptrs, lds, e, p, ins = self._batch_args(X, eps, present=present, inputs=inputs)
         cost = C.c_float(0.0)
-        self._twin("avae_eval_cost", (ptrs, lds), p, (ptr(e), C.byref(cost)))
+        if ins is not None:
+            self._call_in("avae_eval_cost_in", (ptrs, lds), ins, p, (ptr(e), C.byref(cost)))
+        else:
+            self._twin("avae_eval_cost", (ptrs, lds), p, (ptr(e), C.byref(cost)))
         c = cost.value
         if self._sync is not None and self._sync.world_size > 1:        # (never with ``present``: that runs on one replica)
             c = self._sync.sum_scalar(c, self.device)
@@ -767,8 +818,12 @@ def train(data_sets, network_architectures, binary=True, weights=1.0, assoc_lamb
 
     ``data_parallel=True`` (one process per GPU): ``batch_size`` is the per-rank batch; every rank walks the SAME
     data set in the SAME order in global batches of ``world * batch_size`` rows and trains on its own rows of each
-    (see ``train_loop``), so the run equals the single-process run with ``batch_size * world``."""
-    vae_assoc = AssocVariationalAutoEncoder(network_architectures, binary, transfer_fct="relu", weights=weights,
+    (see ``train_loop``), so the run equals the single-process run with ``batch_size * world``.
+
+    ``corruption=dict(drop=..., noise=..., drop_value=...)`` (``set_corruption``'s arguments) trains with the denoising
+    criterion: every training step corrupts the encoders' copy of its batch on the device, the losses keep the clean rows.  The
+    validation cost of ``early_stop`` stays clean.  Under ``data_parallel`` every rank must pass the same ``seed``, as for eps."""
+    vae_assoc =AssocVariationalAutoEncoder(network_architectures, binary, transfer_fct="relu", weights=weights,
                                             assoc_lambda=assoc_lambda, learning_rate=learning_rate,
                                             batch_size=batch_size, **model_kwargs)
     return train_loop(vae_assoc, data_sets, network_architectures, batch_size, training_epochs, display_step, early_stop)
