@@ -184,6 +184,28 @@ struct StepPlan {
     void release() { full.release(); multi[0].release(); multi[1].release(); eval.release(); }
 };
 
+// Device scratch outside the workspace: allocated by the first call that needs it (the workspace does not grow), freed with its
+// owner.  Its size is a constant of the handle: another one later is an internal error, not a reallocation.  A first use that
+// fails leaves nothing behind, so the next call tries again.
+struct DevBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    void* ensure(size_t n, bool zero = false) {
+        if (p && n != bytes) throw Err("internal error: device scratch of " + std::to_string(bytes) + " bytes asked for as " + std::to_string(n));
+        if (p) return p;
+        void* q = nullptr;
+        HIP_OK(hipMalloc(&q, n));
+        if (zero && hipMemset(q, 0, n) != hipSuccess) { (void)hipFree(q); throw Err("hipMemset of fresh device scratch failed"); }
+        p = q; bytes = n;
+        return p;
+    }
+    template <typename T> T* as() const { return static_cast<T*>(p); }
+};
+
 }  // namespace
 
 struct avae_handle {
@@ -250,11 +272,10 @@ struct avae_handle {
                    ServeInArgs in_lean; int in_lean_grid = 0; bool lean_in = false; };
     std::vector<Serve> serve;
     size_t off_slot = 0;
-    // avae_loglik's scratch, allocated by its first call (z rows, r, log-weights, running log-sum-exp states of one pass)
-    float* iw_buf = nullptr;
-    // avae_impute's scratch, allocated by its first call (fused [mu | lv] rows, z rows, r, the running (mean, M2) of one input row)
-    float* imp_buf = nullptr;
-    unsigned char* row_pres = nullptr;      // masked scoring: the chunk's staged presence bytes [batch_size][M] (first use)
+    // First-use scratch (DevBuf), one allocation per entry point: calls on a handle are ordered on their streams, not exclusive.
+    DevBuf iw_buf;                          // avae_loglik: z rows, r, log-weights, running log-sum-exp states of one pass
+    DevBuf imp_buf;                         // avae_impute: fused [mu | lv] rows, z rows, r, the running (mean, M2) of one input row
+    DevBuf row_pres;                        // masked scoring / impute: the chunk's staged presence bytes [batch_size][M]
     size_t off_chain = 0;
     size_t off_consts = 0, off_conv_tab = 0;   // 32 B {zeros | one, 0...}; device copy of conv_tab
     std::vector<ConvA> conv_tab;             // implicit patch matrices of the training plan
@@ -264,7 +285,7 @@ struct avae_handle {
     // loss and latent items, reading the staged presence bytes (one set of [B][M] per staging set, allocated then: the workspace does
     // not grow).  Backward, weight gradients and Adam are shared.
     StepPlan plain, masked;
-    unsigned char* pres_buf = nullptr;
+    DevBuf pres_buf;
     size_t pres_set = 0;                    // bytes per staging set
 
     // avae_set_corruption: what the training calls' staging does to the encoder's copy of a modality that came without an explicit
@@ -276,7 +297,7 @@ struct avae_handle {
     // item builders on the same buffers), captured as runs of kCompleteSizes[i] passes; the kernels' arguments; the scratch behind
     // them.  Built and allocated by the first call.
     struct Complete { bool built = false; std::vector<WorkItem> items; std::vector<Launch> fwd, bwd; CompleteArgs args{};
-                      StepGraph g[3]; unsigned char* buf = nullptr; };
+                      StepGraph g[3]; DevBuf buf; };
     Complete cmpl;
 
     // Calls on one handle share its activation buffers and serving slot: a call on a different stream than the previous one is
@@ -1230,19 +1251,26 @@ void xcd_pieces(Launch& L) {
     a.grid_x = L.grid_x;
 }
 
+// Launch groups of the training, serve and completion plans: group(name, dst, fill) turns the work items that fill() pushes onto
+// the plan's table into one launch of dst (none when it pushed nothing).
+struct Groups {
+    avae_handle* h;
+    std::vector<WorkItem>& items;
+    int slot = 0;                          // finish_launch's running slot
+    template <typename Fill> void operator()(const std::string& name, std::vector<Launch>& dst, Fill&& fill) {
+        const int first = (int)items.size();
+        fill();
+        const int count = (int)items.size() - first;
+        if (count > 0) dst.push_back(finish_launch(h, items, first, count, name, &slot));
+    }
+};
+
 void build_training_plan(avae_handle* h) {
     h->items.clear(); h->plain.fwd.clear(); h->bwd.clear(); h->wgrad.clear(); h->conv_tab.clear();
     Builder bd(h, h->items, h->B, true);
-    int slot = 0;
+    Groups group{h, h->items};
     int Lmax = 0;
     for (const Mod& md : h->mods) Lmax = std::max(Lmax, md.L);
-    auto group = [&](const std::string& name, std::vector<Launch>& dst, auto&& fill) {
-        const int first = (int)h->items.size();
-        fill();
-        const int count = (int)h->items.size() - first;
-        if (count <= 0) return;
-        dst.push_back(finish_launch(h, h->items, first, count, name, &slot));
-    };
     // Small nets: the launch that follows the heads (the decoder's first layer, K = n_z + 1) and the one that follows bwd_dec1_latent
     // (the heads' input gradient, K = 2 n_z) multiply over one or two K tiles and are pure launch overhead (4.3 us each on C2).  When the
     // producing launch runs on 32x64 tiles they become the tail product of its items (WorkItem::tail_*) and disappear.  The weights
@@ -1866,7 +1894,7 @@ void build_training_plan(avae_handle* h) {
     {
         const int first = (int)h->items.size();
         h->items.push_back(bd.cost(false));
-        h->cost_only = finish_launch(h, h->items, first, 1, "cost_reduce", &slot);
+        h->cost_only = finish_launch(h, h->items, first, 1, "cost_reduce", &group.slot);
     }
 
     // ---- Adam tiles
@@ -2009,6 +2037,13 @@ struct Timed {
     }
 };
 
+// One kernel launch outside the plans' tables: its timing bracket, the launch, its error check -- both under `name`.
+template <typename F> void timed_launch(avae_handle* h, hipStream_t s, const char* name, F&& launch) {
+    Timed t(h, s, name);
+    launch();
+    LAUNCH_OK(name);
+}
+
 // The same launch reading staging set j instead of set 0: every pointer into set 0 moves by j * stage_bytes.
 Launch relocated(const avae_handle* h, const Launch& L0, int j) {
     Launch L = L0;
@@ -2112,16 +2147,40 @@ void run_adam(avae_handle* h, int mode, hipStream_t s, int bucket = -1) {
 // the caller's explicit inputs (null, or null entries: none), else -- `corrupt`: the training calls -- the handle's corruption.
 struct PrepIn { const float* const* in = nullptr; const int32_t* in_ld = nullptr; bool corrupt = false; };
 
+// The staging kernel's arguments (k_prep).  Three fillers shared by the batch form (every modality + eps, the training / eval
+// calls) and the single form (one source per launch, the forward-only calls): the generator's key, one segment, the eps block.
+PrepArgs new_prep(const avae_handle* h, unsigned long long salt, int row0 = 0) {
+    PrepArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.row_offset = h->cfg.row_offset + row0; a.seed = h->cfg.seed; a.st = h->state(); a.stream_salt = salt;
+    return a;
+}
+
+// rows x cols fp32 of src -> compute-dtype rows of dst (+ their exact fp32 copy in dst32); returns the segment's tiles
+int fill_prep_seg(const avae_handle* h, PrepSeg& g, const float* src, int src_ld, int rows, int cols, const Act& dst, float* dst32,
+                  int ld32, int tile_base) {
+    g.src = src; g.src_ld = src_ld; g.rows = rows; g.cols = cols;
+    g.dst32 = dst32; g.ld32 = ld32;
+    g.dstc = h->at<void>(dst.rm); g.ldc = dst.ld;
+    g.tiles_r = (rows + 63) / 64; g.tiles_c = (cols + 63) / 64; g.tile_base = tile_base;
+    return g.tiles_r * g.tiles_c;
+}
+
+// eps of `rows` rows into the eps buffer: the caller's, or (null) drawn by the generator
+void fill_prep_eps(const avae_handle* h, PrepArgs& a, const float* eps, int rows) {
+    a.eps_src = eps; a.eps_dst = h->at<float>(h->off_eps); a.eps_rows = rows; a.nz = h->nz; a.eps_ld = h->ld_eps;
+    a.eps_blocks = (rows * ((h->nz + 3) / 4) + kThreads - 1) / kThreads;
+}
+
 // stages the caller's batch (and eps) into the internal compute-dtype buffers
 PrepArgs make_prep_batch(avae_handle* h, const float* const* x, const int32_t* x_ld, const float* eps, int rows,
                          unsigned long long salt, int n_steps = 1, const uint8_t* present = nullptr, const PrepIn& pin = PrepIn()) {
-    PrepArgs a;
-    std::memset(&a, 0, sizeof(a));
+    PrepArgs a = new_prep(h, salt);
     int base = 0;
     for (int m = 0; m < h->M; ++m) {
         const Mod& md = h->mods[m];
         PrepSeg& g = a.seg[m];
-        g.src = x[m]; g.src_ld = (x_ld && x_ld[m] > 0) ? x_ld[m] : md.n_in;
+        base += fill_prep_seg(h, g, x[m], (x_ld && x_ld[m] > 0) ? x_ld[m] : md.n_in, rows, md.n_in, md.X0, h->at<float>(md.X32), md.ld32, base);
         if (pin.in && pin.in[m]) {
             g.src_in = pin.in[m]; g.in_ld = (pin.in_ld && pin.in_ld[m] > 0) ? pin.in_ld[m] : md.n_in;
             a.noisy = 1;
@@ -2129,50 +2188,46 @@ PrepArgs make_prep_batch(avae_handle* h, const float* const* x, const int32_t* x
             g.drop_thr = h->drop_thr[m]; g.drop_value = h->corr.drop_value[m]; g.noise_std = h->corr.noise_std[m];
             a.noisy = 1;
         }
-        g.rows = rows; g.cols = md.n_in;
-        g.dst32 = h->at<float>(md.X32); g.ld32 = md.ld32;
-        g.dstc = h->at<void>(md.X0.rm); g.ldc = md.X0.ld;
-        g.tiles_r = (rows + 63) / 64; g.tiles_c = (md.n_in + 63) / 64; g.tile_base = base;
-        base += g.tiles_r * g.tiles_c;
     }
     a.n_seg = h->M; a.total_tiles = base;
-    a.eps_src = eps; a.eps_dst = h->at<float>(h->off_eps); a.eps_rows = rows; a.nz = h->nz; a.eps_ld = h->ld_eps;
-    a.eps_blocks = (rows * ((h->nz + 3) / 4) + kThreads - 1) / kThreads;
-    a.row_offset = h->cfg.row_offset; a.seed = h->cfg.seed; a.st = h->state(); a.stream_salt = salt;
+    fill_prep_eps(h, a, eps, rows);
     a.n_steps = n_steps; a.blocks_per_step = a.total_tiles + a.eps_blocks; a.set_stride = (long long)h->stage_bytes;
-    if (present) { a.pres_src = present; a.pres_dst = h->pres_buf; a.pres_ld = h->M; }      // masked staging (set j at j * rows * M)
+    if (present) { a.pres_src = present; a.pres_dst = h->pres_buf.as<unsigned char>(); a.pres_ld = h->M; }      // masked staging (set j at j * rows * M)
     return a;
 }
 
 void run_prep_batch(avae_handle* h, const float* const* x, const int32_t* x_ld, const float* eps, int rows,
                     unsigned long long salt, hipStream_t s, const uint8_t* present = nullptr, int n_steps = 1, const PrepIn& pin = PrepIn()) {
     const PrepArgs a = make_prep_batch(h, x, x_ld, eps, rows, salt, n_steps, present, pin);
-    Timed t(h, s, "prep");
-    launch_prep(h->cfg.compute_dtype, a, s);
-    LAUNCH_OK("prep");
+    timed_launch(h, s, "prep", [&] { launch_prep(h->cfg.compute_dtype, a, s); });
 }
 
-void run_prep_single(avae_handle* h, const float* src, int src_ld, int rows, int cols, const Act& dst, float* dst32, int ld32,
-                     bool do_eps, const float* eps, unsigned long long salt, hipStream_t s, int row0 = 0,
-                     const unsigned char* pres_src = nullptr, unsigned char* pres_dst = nullptr, int pres_ld = 0) {
-    PrepArgs a;
-    std::memset(&a, 0, sizeof(a));
-    // masked staging of one modality: pres_src / pres_dst point at its column of the [rows][pres_ld] presence arrays, so the
+// One source staged by a launch of its own (the forward-only calls): `rows` rows of `cols` floats at src -> dst.  The rest is
+// optional and named.
+struct PrepOne {
+    const float* src; int src_ld, rows, cols;
+    const Act& dst;
+    int row0;                                  // the rows' index in the whole input (keys the generator: row0 + row)
+    PrepOne(const float* src_, int src_ld_, int rows_, int cols_, const Act& dst_, int row0_ = 0)
+        : src(src_), src_ld(src_ld_), rows(rows_), cols(cols_), dst(dst_), row0(row0_) {}
+    float* dst32 = nullptr; int ld32 = 0;      // an exact fp32 copy of the rows
+    bool eps = false;                          // also stage eps for these rows: eps_src, or (null) a draw keyed by salt and row
+    const float* eps_src = nullptr;
+    unsigned long long salt = 0;
+    PrepOne& with_eps(const float* e, unsigned long long salt_ = 0) { eps = true; eps_src = e; salt = salt_; return *this; }
+    // masked staging: this modality's column of the caller's [rows][pres_ld] presence bytes and of their staged copy, so that the
     // segment's index 0 addresses it; a null src is then a modality absent on every row, staged as zeros
-    if (pres_src) { a.pres_src = pres_src; a.pres_dst = pres_dst; a.pres_ld = pres_ld; }
-    if (src || pres_src) {
-        PrepSeg& g = a.seg[0];
-        g.src = src; g.src_ld = src_ld; g.rows = rows; g.cols = cols;
-        g.dst32 = dst32; g.ld32 = ld32;
-        g.dstc = h->at<void>(dst.rm); g.ldc = dst.ld;
-        g.tiles_r = (rows + 63) / 64; g.tiles_c = (cols + 63) / 64; g.tile_base = 0;
-        a.n_seg = 1; a.total_tiles = g.tiles_r * g.tiles_c;
+    const unsigned char* pres_src = nullptr; unsigned char* pres_dst = nullptr; int pres_ld = 0;
+};
+
+void run_prep_single(avae_handle* h, const PrepOne& p, hipStream_t s) {
+    PrepArgs a = new_prep(h, p.salt, p.row0);
+    if (p.pres_src) { a.pres_src = p.pres_src; a.pres_dst = p.pres_dst; a.pres_ld = p.pres_ld; }
+    if (p.src || p.pres_src) {
+        a.n_seg = 1;
+        a.total_tiles = fill_prep_seg(h, a.seg[0], p.src, p.src_ld, p.rows, p.cols, p.dst, p.dst32, p.ld32, 0);
     }
-    if (do_eps) {
-        a.eps_src = eps; a.eps_dst = h->at<float>(h->off_eps); a.eps_rows = rows; a.nz = h->nz; a.eps_ld = h->ld_eps;
-        a.eps_blocks = (rows * ((h->nz + 3) / 4) + kThreads - 1) / kThreads;
-    }
-    a.row_offset = h->cfg.row_offset + row0; a.seed = h->cfg.seed; a.st = h->state(); a.stream_salt = salt;
+    if (p.eps) fill_prep_eps(h, a, p.eps_src, p.rows);
     launch_prep(h->cfg.compute_dtype, a, s);
     LAUNCH_OK("prep");
 }
@@ -2580,14 +2635,9 @@ avae_handle::Serve& serve_plan(avae_handle* h, int bucket) {
     avae_handle::Serve& sv = h->serve.back();
     sv.bucket = bucket;
     Builder bd(h, sv.items, bucket, false);
-    int slot = 0, Lmax = 0;
+    Groups group{h, sv.items};
+    int Lmax = 0;
     for (const Mod& md : h->mods) Lmax = std::max(Lmax, md.L);
-    auto group = [&](const std::string& name, auto&& fill) {
-        const int first = (int)sv.items.size();
-        fill();
-        const int count = (int)sv.items.size() - first;
-        if (count > 0) sv.launches.push_back(finish_launch(h, sv.items, first, count, name, &slot));
-    };
     // The decoder's first layer (K = n_z + 1) rides in the per-call staging launch when that fits its tail product (K_SERVE_Z: one K
     // tile of bf16, two of fp32, at most 1024 units, 32-row tiles); otherwise it is the graph's first launch behind k_serve.
     {
@@ -2603,7 +2653,7 @@ avae_handle::Serve& serve_plan(avae_handle* h, int bucket) {
             sv.items.push_back(w);
         }
         if (fits) {
-            sv.in_launch = finish_launch(h, sv.items, first, (int)sv.items.size() - first, "serve_in+serve_dec1", &slot);
+            sv.in_launch = finish_launch(h, sv.items, first, (int)sv.items.size() - first, "serve_in+serve_dec1", &group.slot);
             if (sv.in_launch.cfg != 3) fits = false;
         }
         if (fits && !std::getenv("AVAE_NO_LEAN")) {            // the same launch as a kernel of its own with a small argument block (k_serve_in)
@@ -2625,8 +2675,8 @@ avae_handle::Serve& serve_plan(avae_handle* h, int bucket) {
         sv.fused_in = fits;
     }
     for (int k = sv.fused_in ? 1 : 0; k < Lmax; ++k)
-        group("serve_dec" + std::to_string(k + 1), [&] { for (Mod& md : h->mods) if (k < md.L) sv.items.push_back(bd.fwd_hidden(k == 0 ? md.Z : md.D[k - 1], md.dec[k], md.D[k])); });
-    group("serve_out", [&] {
+        group("serve_dec" + std::to_string(k + 1), sv.launches, [&] { for (Mod& md : h->mods) if (k < md.L) sv.items.push_back(bd.fwd_hidden(k == 0 ? md.Z : md.D[k - 1], md.dec[k], md.D[k])); });
+    group("serve_out", sv.launches, [&] {
         for (int m = 0; m < h->M; ++m) {
             WorkItem w = bd.fwd_out(h->mods[m], m, false);
             w.aux2 = h->at<void>(h->off_slot); w.n_mod = m;       // K_FWD_OUT_STORE: rows and destination come from the slot
@@ -2702,33 +2752,129 @@ void decode_rows(avae_handle* h, int m, const float* z, int rows, float* xhat, h
     const Mod& md = h->mods[m];
     for (int r0 = 0; r0 < rows; r0 += h->B) {
         const int n = std::min(h->B, rows - r0);
-        run_prep_single(h, z + (size_t)r0 * h->nz, h->nz, n, h->nz, md.Z, nullptr, 0, false, nullptr, 0, s);
+        run_prep_single(h, PrepOne(z + (size_t)r0 * h->nz, h->nz, n, h->nz, md.Z), s);
         run_inference(h, m, false, n, s);
         copy_out32(h, m, xhat + (size_t)r0 * md.n_in, n, s);
     }
 }
 
-// The row inputs of avae_score / avae_loglik: out_dev, x_dev and x_ld of every modality (x_ld NULL: dense rows) -> ld[]
-// masked (the *_masked calls): a NULL x_dev[m] is a modality absent on every row (ld[m] = 0)
-void check_row_inputs(const avae_handle* h, const char* what, const float* const* x_dev, const int32_t* x_ld, const float* out_dev,
-                      int* ld, bool masked = false) {
-    const std::string w = what;
-    if (!out_dev) throw Err(w + ": out_dev is NULL");
-    if (!x_dev) throw Err(w + ": x_dev is NULL");
+// ----------------------------------------------------------------------------- forward-only row calls: the shared helpers
+// avae_score / avae_loglik (+ _masked), avae_impute, avae_complete and avae_generate are put together from RowInputs, row_presence,
+// stage_and_encode, DecodeAll and SampleBlocks below, PrepOne (run_prep_single's named arguments) and timed_launch above, and DevBuf
+// (first-use scratch, one per entry point).  A new entry point starts from them.
+
+// What a NULL x_dev[m] is: an error (avae_score, avae_loglik); a modality absent on every row (the _masked calls, avae_impute);
+// an unobserved modality, of which at least one must be given (avae_complete).
+enum class NullRows { Required, Absent, Unobserved };
+
+// x_dev / x_ld of every modality (x_ld NULL: dense rows), resolved once per call; `what` prefixes the messages.  x_dev itself is
+// not NULL: every caller checks that first, under its own name.
+struct RowInputs {
+    const float* x[kMaxMod] = {nullptr, nullptr, nullptr, nullptr};
+    int ld[kMaxMod] = {0, 0, 0, 0};          // row stride; 0 for a NULL modality
+    unsigned mods = 0;                       // bit m: x_dev[m] was given
+    RowInputs(const avae_handle* h, const std::string& what, const float* const* x_dev, const int32_t* x_ld, NullRows rule) {
+        for (int m = 0; m < h->M; ++m) {
+            if (!x_dev[m]) {
+                if (rule == NullRows::Required) throw Err(what + ": x_dev[" + std::to_string(m) + "] is NULL");
+                continue;
+            }
+            x[m] = x_dev[m]; mods |= 1u << m;
+            ld[m] = x_ld ? x_ld[m] : h->mods[m].n_in;
+            if (ld[m] < h->mods[m].n_in)
+                throw Err(what + ": x_ld[" + std::to_string(m) + "] = " + std::to_string(ld[m]) + " is below n_input = " + std::to_string(h->mods[m].n_in));
+        }
+        if (rule == NullRows::Unobserved && !mods) throw Err(what + ": every x_dev[m] is NULL (nothing is observed)");
+    }
+    const float* at(int m, int r0) const { return x[m] ? x[m] + (size_t)r0 * ld[m] : nullptr; }
+};
+
+// Masked calls: the caller's [rows][M] presence bytes and the chunk's staged copy [batch_size][M] that the kernels read (0 / 1,
+// NULL sources folded in; DevBuf row_pres).  Both null for an unmasked call.
+struct RowPresence {
+    const uint8_t* src = nullptr;
+    unsigned char* staged = nullptr;
+    explicit operator bool() const { return src != nullptr; }
+};
+
+RowPresence row_presence(avae_handle* h, const uint8_t* present) {
+    if (!present) return {};
+    return {present, static_cast<unsigned char*>(h->row_pres.ensure((size_t)h->B * h->M))};
+}
+
+// eps staged together with the chunk's first modality (avae_score): the caller's rows (null: a draw) and the staging launches' salt
+struct StageEps { const float* src; unsigned long long salt; };
+
+// Rows [r0, r0 + n) of every modality -> its X0, with the chunk's presence bytes when masked, then its encoder.  A NULL modality
+// of an unmasked call is skipped; of a masked call it is staged (zeros, absent on every row) and encoded only with encode_null.
+void stage_and_encode(avae_handle* h, const RowInputs& in, const RowPresence& pres, int r0, int n, bool encode_null,
+                      const StageEps* eps, hipStream_t s) {
     for (int m = 0; m < h->M; ++m) {
-        if (!x_dev[m] && masked) { ld[m] = 0; continue; }
-        if (!x_dev[m]) throw Err(w + ": x_dev[" + std::to_string(m) + "] is NULL");
-        ld[m] = x_ld ? x_ld[m] : h->mods[m].n_in;
-        if (ld[m] < h->mods[m].n_in)
-            throw Err(w + ": x_ld[" + std::to_string(m) + "] = " + std::to_string(ld[m]) + " is below n_input = " + std::to_string(h->mods[m].n_in));
+        if (!in.x[m] && !pres) continue;
+        const Mod& md = h->mods[m];
+        PrepOne p(in.at(m, r0), in.ld[m], n, md.n_in, md.X0, r0);
+        if (eps && m == 0) p.with_eps(eps->src ? eps->src + (size_t)r0 * h->nz : nullptr);
+        if (eps) p.salt = eps->salt;
+        if (pres) { p.pres_src = pres.src + (size_t)r0 * h->M + m; p.pres_dst = pres.staged + m; p.pres_ld = h->M; }
+        run_prep_single(h, p, s);
+        if (in.x[m] || encode_null) run_inference(h, m, true, n, s);
     }
 }
 
-// The chunk presence buffer of the masked scoring calls (not part of the workspace; avae_destroy frees it)
-unsigned char* row_presence_buf(avae_handle* h) {
-    if (!h->row_pres) HIP_OK(hipMalloc(reinterpret_cast<void**>(&h->row_pres), (size_t)h->B * h->M));
-    return h->row_pres;
-}
+// "These z rows through every decoder."  The route is chosen once per call: by modality (conv decoders, use_graph = 0, timing),
+// every decoder's own launches from its Z into its out32 (rows of ld32); else the serve route, the grouped launches of a serve
+// plan in passes of at most batch_size rows, reading dense fp32 z and storing dense [rows][n_input] wherever the call points.
+struct DecodeAll {
+    avae_handle* h;
+    bool by_mod;
+    explicit DecodeAll(avae_handle* h_) : h(h_), by_mod(decode_by_mod(h_)) {}
+    // Where a latent kernel (IwLatentArgs, ImputeFuseArgs) leaves z for run(): every decoder's Z, or the dense fp32 rows z32
+    template <typename Args> void z_dest(Args& a, float* z32) const {
+        if (!by_mod) { a.z32 = z32; return; }
+        a.n_zdst = h->M;
+        for (int m = 0; m < h->M; ++m) { a.Z[m] = h->at<void>(h->mods[m].Z.rm); a.ldz[m] = h->mods[m].Z.ld; }
+    }
+    // row stride of outputs left in decoder m's out32 (dst[m] null)
+    int ld_out32(int m) const { return by_mod ? h->mods[m].ld32 : h->mods[m].n_in; }
+    // nd rows.  z: dense fp32 [nd][n_z] -- read by the serve route; by modality only with stage_z (the caller's own z, any nd),
+    // otherwise a latent kernel has filled the decoders' Z and nd <= batch_size.  dst (nullable, and per modality): dense
+    // [nd][n_input] destinations; without one the rows stay in the decoder's out32.  dst_only: by modality, a decoder without a
+    // destination does not run.
+    void run(int nd, const float* z, bool stage_z, float* const* dst, bool dst_only, hipStream_t s) const {
+        if (by_mod) {
+            for (int m = 0; m < h->M; ++m) {
+                float* out = dst ? dst[m] : nullptr;
+                if (dst_only && !out) continue;
+                if (stage_z) { decode_rows(h, m, z, nd, out, s); continue; }
+                run_inference(h, m, false, nd, s);
+                if (out) copy_out32(h, m, out, nd, s);
+            }
+            return;
+        }
+        ServeSlot sl;
+        std::memset(&sl, 0, sizeof(sl));
+        for (int c0 = 0; c0 < nd; c0 += h->B) {
+            sl.z = z + (size_t)c0 * h->nz; sl.rows = std::min(h->B, nd - c0);
+            for (int m = 0; m < h->M; ++m)
+                sl.out[m] = (dst && dst[m]) ? dst[m] + (size_t)c0 * h->mods[m].n_in : h->at<float>(h->mods[m].out32);
+            serve_call(h, serve_plan(h, serve_bucket(h, sl.rows)), sl, s);
+        }
+    }
+};
+
+// K samples of every input row, decoded in passes of at most `cap` rows: n_rows input rows x kb samples per pass (K >= cap: one
+// row and cap samples, the row spanning several passes; else cap / K rows with all their samples).
+struct SampleBlocks {
+    int K, n_rows, kb;
+    SampleBlocks(int K_, int cap) : K(K_), n_rows(K_ >= cap ? 1 : cap / std::max(K_, 1)), kb(K_ >= cap ? cap : K_) {}
+    // body(k0, kc, nd): samples [k0, k0 + kc) of nj input rows = nd decoded rows
+    template <typename F> void each(int nj, F&& body) const {
+        for (int k0 = 0; k0 < K; k0 += kb) {
+            const int kc = std::min(kb, K - k0);
+            body(k0, kc, nj * kc);
+        }
+    }
+};
 
 // ---- gradient latent refinement (avae_complete; include/avae.h, avae_complete.h).  One pass over a chunk of <= batch_size rows:
 //   cmpl_dec<k>      the decoders' hidden layers from the current z (grouped over the modalities, as fwd_dec<k>)
@@ -2746,15 +2892,9 @@ constexpr int kCompleteSizes[3] = {16, 4, 1};   // passes per captured graph
 
 void complete_pass(avae_handle* h, avae_handle::Complete& cp, hipStream_t s) {
     run_launches(h, cp.fwd, s);
-    {
-        Timed t(h, s, "complete_out");
-        launch_complete_out(h->cfg.compute_dtype, cp.args, s); LAUNCH_OK("complete_out");
-    }
+    timed_launch(h, s, "complete_out", [&] { launch_complete_out(h->cfg.compute_dtype, cp.args, s); });
     run_launches(h, cp.bwd, s);
-    {
-        Timed t(h, s, "complete_update");
-        launch_complete_update(h->cfg.compute_dtype, cp.args, s); LAUNCH_OK("complete_update");
-    }
+    timed_launch(h, s, "complete_update", [&] { launch_complete_update(h->cfg.compute_dtype, cp.args, s); });
 }
 
 avae_handle::Complete& complete_plan(avae_handle* h) {
@@ -2767,15 +2907,12 @@ avae_handle::Complete& complete_plan(avae_handle* h) {
     const size_t off_recon = b.take((size_t)B * M * 4);
     size_t off_dz[kMaxMod] = {0, 0, 0, 0};
     for (int m = 0; m < M; ++m) off_dz[m] = b.take(rup(B, kRowAlign) * (size_t)lddz * 4);
-    if (!cp.buf) {
-        HIP_OK(hipMalloc(reinterpret_cast<void**>(&cp.buf), b.off));
-        HIP_OK(hipMemset(cp.buf, 0, b.off));
-    }
+    unsigned char* buf = static_cast<unsigned char*>(cp.buf.ensure(b.off, true));
     CompleteArgs& a = cp.args;
     std::memset(&a, 0, sizeof(a));
-    a.call = reinterpret_cast<CompleteCall*>(cp.buf + off_call);
-    a.z32 = reinterpret_cast<float*>(cp.buf + off_z); a.m = reinterpret_cast<float*>(cp.buf + off_m); a.v = reinterpret_cast<float*>(cp.buf + off_v);
-    a.recon = reinterpret_cast<float*>(cp.buf + off_recon);
+    a.call = reinterpret_cast<CompleteCall*>(buf + off_call);
+    a.z32 = reinterpret_cast<float*>(buf + off_z); a.m = reinterpret_cast<float*>(buf + off_m); a.v = reinterpret_cast<float*>(buf + off_v);
+    a.recon = reinterpret_cast<float*>(buf + off_recon);
     a.beta1 = h->cfg.beta1; a.beta2 = h->cfg.beta2; a.eps = h->cfg.adam_eps;
     a.n_mod = M; a.nz = nz; a.bucket = B;
     for (int m = 0; m < M; ++m) {
@@ -2783,19 +2920,14 @@ avae_handle::Complete& complete_plan(avae_handle* h) {
         a.Z[m] = h->at<void>(md.Z.rm); a.ldz[m] = md.Z.ld;
         a.out32[m] = h->at<float>(md.out32); a.ld32[m] = md.ld32;
         a.dO[m] = h->at<void>(md.dO.rm); a.lddo[m] = md.dO.ld;
-        a.dz[m] = reinterpret_cast<float*>(cp.buf + off_dz[m]); a.lddz[m] = lddz;
+        a.dz[m] = reinterpret_cast<float*>(buf + off_dz[m]); a.lddz[m] = lddz;
         a.n_in[m] = md.n_in; a.binary[m] = h->cfg.mod[m].binary ? 1 : 0; a.w[m] = h->cfg.mod[m].weight;
     }
     cp.items.clear(); cp.fwd.clear(); cp.bwd.clear();
     Builder bd(h, cp.items, B, false);
-    int slot = 0, Lmax = 0;
+    Groups group{h, cp.items};
+    int Lmax = 0;
     for (const Mod& md : h->mods) Lmax = std::max(Lmax, md.L);
-    auto group = [&](const std::string& name, std::vector<Launch>& dst, auto&& fill) {
-        const int first = (int)cp.items.size();
-        fill();
-        const int count = (int)cp.items.size() - first;
-        if (count > 0) dst.push_back(finish_launch(h, cp.items, first, count, name, &slot));
-    };
     for (int k = 0; k < Lmax; ++k)
         group("cmpl_dec" + std::to_string(k + 1), cp.fwd, [&] {
             for (Mod& md : h->mods) if (k < md.L) cp.items.push_back(bd.fwd_hidden(k == 0 ? md.Z : md.D[k - 1], md.dec[k], md.D[k])); });
@@ -2827,11 +2959,8 @@ avae_handle::Complete& complete_plan(avae_handle* h) {
 // launches with WorkItem::present pointing at the staged presence bytes in every loss and latent item, and their graphs.
 void build_masked(avae_handle* h) {
     if (!h->masked.fwd.empty()) return;
-    if (!h->pres_buf) {
-        h->pres_set = (size_t)h->B * h->M;         // = the staging kernel's set stride (PrepArgs::pres_dst: set j at j * rows * M)
-        HIP_OK(hipMalloc(reinterpret_cast<void**>(&h->pres_buf), h->pres_set * kMultiSteps));
-        HIP_OK(hipMemset(h->pres_buf, 0, h->pres_set * kMultiSteps));
-    }
+    h->pres_set = (size_t)h->B * h->M;             // = the staging kernel's set stride (PrepArgs::pres_dst: set j at j * rows * M)
+    unsigned char* pres = static_cast<unsigned char*>(h->pres_buf.ensure(h->pres_set * kMultiSteps, true));
     std::vector<Launch> mf = h->plain.fwd;
     int n_loss = 0, n_latent = 0;
     for (Launch& L : mf) {
@@ -2843,10 +2972,10 @@ void build_masked(avae_handle* h) {
                 int m = 0;
                 while (m < h->M && w.aux0 != h->at<void>(h->mods[m].X32)) ++m;      // the item's modality: whose exact inputs it reads
                 if (m == h->M) throw Err("internal error: a loss item of no modality");
-                w.present = h->pres_buf + m; w.present_ld = h->M;
+                w.present = pres + m; w.present_ld = h->M;
                 gated = true; ++n_loss;
             } else if (w.kind == K_LATENT) {
-                w.present = h->pres_buf; w.present_ld = h->M;
+                w.present = pres; w.present_ld = h->M;
                 gated = true; ++n_latent;
             }
         }
@@ -2861,7 +2990,7 @@ void build_masked(avae_handle* h) {
                                                    std::to_string(n_latent) + " latent items");
     h->masked.fwd.swap(mf);
     if (h->cfg.use_graph) {
-        try { capture_plan(h, h->masked, h->pres_buf); } catch (...) { h->masked.fwd.clear(); throw; }      // the next masked call builds it again
+        try { capture_plan(h, h->masked, pres); } catch (...) { h->masked.fwd.clear(); throw; }      // the next masked call builds it again
     }
 }
 
@@ -2901,9 +3030,7 @@ void train_one(avae_handle* h, StepPlan& p, const float* const* x_dev, const int
     run_prep_batch(h, x_dev, x_ld, eps_dev, h->B, 0x7261696eull, s, present, 1, pin);
     step_body(h, p.fwd, s, 0);
     if (h->timing) {      // floor of the measurement: a one-store kernel (partial slot 0 is rewritten every step anyway)
-        Timed t(h, s, "_null_kernel");
-        launch_fill(h->at<void>(h->off_partial), 4, 0u, 0, 1, 1, s);
-        LAUNCH_OK("_null_kernel");
+        timed_launch(h, s, "_null_kernel", [&] { launch_fill(h->at<void>(h->off_partial), 4, 0u, 0, 1, 1, s); });
     }
 }
 
@@ -3012,12 +3139,7 @@ void destroy_handle(avae_handle* h) {
     for (StepGraph& g : h->g_dpm) g.release();
     for (std::vector<StepGraph>& v : h->g_dp) for (StepGraph& g : v) g.release();
     for (avae_handle::Serve& sv : h->serve) if (sv.graph) (void)hipGraphExecDestroy(sv.graph);
-    if (h->iw_buf) (void)hipFree(h->iw_buf);
-    if (h->imp_buf) (void)hipFree(h->imp_buf);
-    if (h->row_pres) (void)hipFree(h->row_pres);
     for (StepGraph& g : h->cmpl.g) g.release();
-    if (h->cmpl.buf) (void)hipFree(h->cmpl.buf);
-    if (h->pres_buf) (void)hipFree(h->pres_buf);
     if (h->ev_switch) (void)hipEventDestroy(h->ev_switch);
     if (h->comm) { try { (void)Rccl::get().destroy(h->comm); } catch (...) {} }
     for (int r = 0; r < kMaxWorld; ++r) if (h->ipc_opened[r] && h->ipc_peer[r]) (void)hipIpcCloseMemHandle(h->ipc_peer[r]);
@@ -3027,8 +3149,9 @@ void destroy_handle(avae_handle* h) {
     for (TimingRec& r : h->trecs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
     if (h->cap_stream) (void)hipStreamDestroy(h->cap_stream);
     if (h->own_ws && h->ws) (void)hipFree(h->ws);
-    if (prev_dev >= 0 && prev_dev != h->cfg.device) (void)hipSetDevice(prev_dev);
-    delete h;
+    const int dev = h->cfg.device;
+    delete h;                                   // (with its DevBuf scratch, while the handle's device is still current)
+    if (prev_dev >= 0 && prev_dev != dev) (void)hipSetDevice(prev_dev);
 }
 
 }  // namespace
@@ -3342,7 +3465,7 @@ int avae_encode(avae_handle* h, int32_t m, const float* x_dev, int32_t x_ld, int
         const size_t nzb = (size_t)h->nz * 4;
         for (int r0 = 0; r0 < rows; r0 += h->B) {
             const int n = std::min(h->B, rows - r0);
-            run_prep_single(h, x_dev + (size_t)r0 * ld, ld, n, md.n_in, md.X0, nullptr, 0, true, nullptr, 0x656e63ull, s);
+            run_prep_single(h, PrepOne(x_dev + (size_t)r0 * ld, ld, n, md.n_in, md.X0).with_eps(nullptr, 0x656e63ull), s);
             run_inference(h, m, true, n, s);
             if (mu_dev) copy_rows(mu_dev + (size_t)r0 * h->nz, nzb, h->at<float>(md.mulv), 2 * nzb, nzb, n, s);
             if (logvar_dev) copy_rows(logvar_dev + (size_t)r0 * h->nz, nzb, h->at<float>(md.mulv) + h->nz, 2 * nzb, nzb, n, s);
@@ -3363,18 +3486,7 @@ int avae_generate(avae_handle* h, const float* z_dev, int32_t rows, float* const
         if (rows < 0) throw Err("rows must be >= 0");
         if (!z_dev || !xhat_dev) throw Err("null argument");
         hipStream_t s = on_stream(h, stream);
-        if (decode_by_mod(h)) {
-            for (int m = 0; m < h->M; ++m) decode_rows(h, m, z_dev, rows, xhat_dev[m], s);
-            return;
-        }
-        for (int r0 = 0; r0 < rows; r0 += h->B) {
-            const int n = std::min(h->B, rows - r0);
-            ServeSlot sl;
-            std::memset(&sl, 0, sizeof(sl));
-            sl.z = z_dev + (size_t)r0 * h->nz; sl.rows = n;
-            for (int m = 0; m < h->M; ++m) sl.out[m] = xhat_dev[m] + (size_t)r0 * h->mods[m].n_in;
-            serve_call(h, serve_plan(h, serve_bucket(h, n)), sl, s);
-        }
+        DecodeAll(h).run(rows, z_dev, true, xhat_dev, false, s);
     });
 }
 
@@ -3390,8 +3502,8 @@ int avae_reconstruct(avae_handle* h, int32_t m, const float* x_dev, int32_t x_ld
         const unsigned long long draw = eps_dev ? 0ull : ((unsigned long long)next_draw(h, eps_dev) << 34) | ((unsigned long long)m << 32);
         for (int r0 = 0; r0 < rows; r0 += h->B) {
             const int n = std::min(h->B, rows - r0);
-            run_prep_single(h, x_dev + (size_t)r0 * ld, ld, n, md.n_in, md.X0, nullptr, 0, true,
-                            eps_dev ? eps_dev + (size_t)r0 * h->nz : nullptr, 0x7265636full | draw, s, r0);
+            run_prep_single(h, PrepOne(x_dev + (size_t)r0 * ld, ld, n, md.n_in, md.X0, r0)
+                                   .with_eps(eps_dev ? eps_dev + (size_t)r0 * h->nz : nullptr, 0x7265636full | draw), s);
             run_inference(h, m, true, n, s);
             run_inference(h, m, false, n, s);
             copy_out32(h, m, xhat_dev + (size_t)r0 * md.n_in, n, s);
@@ -3422,15 +3534,16 @@ static void score_call(avae_handle* h, const char* what, const float* const* x_d
         if (flags & ~AVAE_SCORE_CROSS) throw Err(w + ": unknown flags (only AVAE_SCORE_CROSS is defined)");
         if (rows < 0) throw Err(w + ": rows must be >= 0");
         if (rows == 0) return;
-        int ld[kMaxMod];
-        check_row_inputs(h, what, x_dev, x_ld, out_dev, ld, present != nullptr);
-        unsigned char* pres = present ? row_presence_buf(h) : nullptr;
+        if (!out_dev) throw Err(w + ": out_dev is NULL");
+        if (!x_dev) throw Err(w + ": x_dev is NULL");
+        const RowInputs in(h, w, x_dev, x_ld, present ? NullRows::Absent : NullRows::Required);
+        const RowPresence pres = row_presence(h, present);
         const int M = h->M, P = M * (M - 1) / 2;
         const bool cross = (flags & AVAE_SCORE_CROSS) != 0;
         const int k = 1 + 2 * M + P + (cross ? M * M : 0);
         hipStream_t s = on_stream(h, stream);
         // a fresh eps per call, keyed as avae_reconstruct's: draw counter in the salt's high bits, row of the whole input
-        const unsigned long long draw = (unsigned long long)next_draw(h, eps_dev) << 34;
+        const StageEps eps{eps_dev, 0x73636f72ull /*scor*/ | (unsigned long long)next_draw(h, eps_dev) << 34};
         ScoreLatentArgs la;
         std::memset(&la, 0, sizeof(la));
         la.eps = h->at<float>(h->off_eps); la.ld_eps = h->ld_eps;
@@ -3438,53 +3551,37 @@ static void score_call(avae_handle* h, const char* what, const float* const* x_d
         ScoreRowsArgs ra;
         std::memset(&ra, 0, sizeof(ra));
         ra.k = k; ra.n_mod = M; ra.n_pair = P; ra.lambda = h->cfg.assoc_lambda;
-        la.present = ra.present = pres;
+        la.present = ra.present = pres.staged;
         for (int m = 0; m < M; ++m) {
             la.mulv[m] = h->at<float>(h->mods[m].mulv);
             la.Z[m] = h->at<void>(h->mods[m].Z.rm); la.ldz[m] = h->mods[m].Z.ld;
             ra.w[m] = h->cfg.mod[m].weight;
         }
-        auto score_rows = [&](int m, int col, bool with_cost, int n, int src = -1) {
+        auto score_latent = [&](int src) {
+            la.src = src;
+            timed_launch(h, s, "score_latent", [&] { launch_score_latent(h->cfg.compute_dtype, la, s); });
+        };
+        // decoder m on the z in place, then its rows' terms into column col (src >= 0: cross term of source src)
+        auto score_rows = [&](int m, int r0, int col, bool with_cost, int n, int src = -1) {
             const Mod& md = h->mods[m];
+            run_inference(h, m, false, n, s);
+            ra.x = in.at(m, r0); ra.ldx = in.ld[m];
             ra.pa = src < 0 ? m : src; ra.pb = m; ra.absent_bits = src < 0 ? 0u : 0x7FC00000u;      // (masked) +0.0 / quiet NaN
             ra.xhat = h->at<float>(md.out32); ra.ld32 = md.ld32;
             ra.n_in = md.n_in; ra.binary = h->cfg.mod[m].binary ? 1 : 0;
             ra.col = col; ra.cost = with_cost ? 1 : 0; ra.rows = n;
-            Timed t(h, s, "score_rows");
-            launch_score_rows(ra, s); LAUNCH_OK("score_rows");
+            timed_launch(h, s, "score_rows", [&] { launch_score_rows(ra, s); });
         };
         for (int r0 = 0; r0 < rows; r0 += h->B) {
             const int n = std::min(h->B, rows - r0);
-            for (int m = 0; m < M; ++m) {
-                const Mod& md = h->mods[m];
-                run_prep_single(h, x_dev[m] ? x_dev[m] + (size_t)r0 * ld[m] : nullptr, ld[m], n, md.n_in, md.X0, nullptr, 0, m == 0,
-                                eps_dev ? eps_dev + (size_t)r0 * h->nz : nullptr, 0x73636f72ull /*scor*/ | draw, s, r0,
-                                present ? present + (size_t)r0 * M + m : nullptr, present ? pres + m : nullptr, M);
-                run_inference(h, m, true, n, s);
-            }
-            la.out = out_dev + (size_t)r0 * k; la.rows = n; la.src = -1;
-            ra.out = la.out;
-            {
-                Timed t(h, s, "score_latent");
-                launch_score_latent(h->cfg.compute_dtype, la, s); LAUNCH_OK("score_latent");
-            }
-            for (int m = 0; m < M; ++m) {
-                ra.x = x_dev[m] ? x_dev[m] + (size_t)r0 * ld[m] : nullptr; ra.ldx = ld[m];
-                run_inference(h, m, false, n, s);
-                score_rows(m, 1 + m, m == M - 1, n);
-            }
+            stage_and_encode(h, in, pres, r0, n, true, &eps, s);
+            la.out = ra.out = out_dev + (size_t)r0 * k; la.rows = n;
+            score_latent(-1);
+            for (int m = 0; m < M; ++m) score_rows(m, r0, 1 + m, m == M - 1, n);
             if (!cross) continue;
             for (int src = 0; src < M; ++src) {
-                la.src = src;
-                {
-                    Timed t(h, s, "score_latent");
-                    launch_score_latent(h->cfg.compute_dtype, la, s); LAUNCH_OK("score_latent");
-                }
-                for (int d = 0; d < M; ++d) {
-                    ra.x = x_dev[d] ? x_dev[d] + (size_t)r0 * ld[d] : nullptr; ra.ldx = ld[d];
-                    run_inference(h, d, false, n, s);
-                    score_rows(d, 1 + 2 * M + P + src * M + d, false, n, src);
-                }
+                score_latent(src);
+                for (int d = 0; d < M; ++d) score_rows(d, r0, 1 + 2 * M + P + src * M + d, false, n, src);
             }
         }
 }
@@ -3502,11 +3599,10 @@ int avae_score_masked(avae_handle* h, const float* const* x_dev, const int32_t* 
     });
 }
 
-// Importance-weighted log-likelihoods.  Passes of at most batch_size decoded rows: n input rows x kb samples (K >= B: one row and
-// kb = B per pass, the row spanning several passes; else n = B / K rows and kb = K).  Per chunk of n rows: stage + encode every
-// modality once; per sample block and proposal src: k_iw_latent (z, r) -> every decoder (grouped launches of the serve route, or
-// modality by modality for conv nets / use_graph = 0 / timing) -> k_iw_rows (log-weights) -> k_iw_reduce (running log-sum-exp;
-// the row's last block writes the caller's row).  Scratch: iw_buf (allocated once) and the decoders' out32 / Z buffers.
+// Importance-weighted log-likelihoods.  Passes of at most batch_size decoded rows (SampleBlocks).  Per chunk of n_rows input rows:
+// stage + encode every modality once; per sample block and proposal src: k_iw_latent (z, r) -> every decoder (DecodeAll) ->
+// k_iw_rows (log-weights) -> k_iw_reduce (running log-sum-exp; the row's last block writes the caller's row).  Scratch: iw_buf
+// and the decoders' out32 / Z buffers.
 // present (avae_loglik_masked): as score_call's.
 static void loglik_call(avae_handle* h, const char* what, const float* const* x_dev, const int32_t* x_ld, const uint8_t* present,
                  int32_t rows, int32_t n_samples, const float* eps_dev, float* out_dev, void* stream) {
@@ -3514,90 +3610,57 @@ static void loglik_call(avae_handle* h, const char* what, const float* const* x_
         if (rows < 0) throw Err(w + ": rows must be >= 0");
         if (n_samples < 1) throw Err(w + ": n_samples must be >= 1, got " + std::to_string(n_samples));
         if (rows == 0) return;
-        int ld[kMaxMod];
-        check_row_inputs(h, what, x_dev, x_ld, out_dev, ld, present != nullptr);
-        unsigned char* pres = present ? row_presence_buf(h) : nullptr;
+        if (!out_dev) throw Err(w + ": out_dev is NULL");
+        if (!x_dev) throw Err(w + ": x_dev is NULL");
+        const RowInputs in(h, w, x_dev, x_ld, present ? NullRows::Absent : NullRows::Required);
+        const RowPresence pres = row_presence(h, present);
         const int M = h->M, B = h->B, nz = h->nz, K = n_samples;
         hipStream_t s = on_stream(h, stream);
         const int width = 2 * M + M * M;
-        const int n_rows = K >= B ? 1 : B / K, kb = K >= B ? B : K;
+        const SampleBlocks blocks(K, B);
         const size_t z_n = (size_t)B * nz, r_n = (size_t)B, ell_n = (size_t)B * M, st_n = (size_t)B * M * (2 + M) * 2;
-        if (!h->iw_buf) HIP_OK(hipMalloc(reinterpret_cast<void**>(&h->iw_buf), (z_n + r_n + ell_n + st_n) * sizeof(float)));
-        float* z32 = h->iw_buf;
+        float* z32 = static_cast<float*>(h->iw_buf.ensure((z_n + r_n + ell_n + st_n) * sizeof(float)));
         float* rbuf = z32 + z_n;
         float* ell = rbuf + r_n;
         float* state = ell + ell_n;
-        const bool by_mod = decode_by_mod(h);
-        // a fresh eps per call, keyed as avae_score's: draw counter, row of the whole input (+ the sample index)
-        const unsigned draw = next_draw(h, eps_dev);
+        const DecodeAll dec(h);
         IwLatentArgs la;
         std::memset(&la, 0, sizeof(la));
-        la.nz = nz; la.K = K; la.seed = h->cfg.seed; la.draw = draw; la.r = rbuf;
-        if (by_mod) {
-            la.n_zdst = M;
-            for (int m = 0; m < M; ++m) { la.Z[m] = h->at<void>(h->mods[m].Z.rm); la.ldz[m] = h->mods[m].Z.ld; }
-        } else {
-            la.z32 = z32;
-        }
+        // a fresh eps per call, keyed as avae_score's: draw counter, row of the whole input (+ the sample index)
+        la.nz = nz; la.K = K; la.seed = h->cfg.seed; la.draw = next_draw(h, eps_dev); la.r = rbuf; la.pres_ld = M;
+        dec.z_dest(la, z32);
         IwRowsArgs ra;
         std::memset(&ra, 0, sizeof(ra));
-        ra.ell = ell; ra.n_mod = M;
-        ServeSlot sl;
-        std::memset(&sl, 0, sizeof(sl));
-        sl.z = z32;
+        ra.ell = ell; ra.n_mod = M; ra.present = pres.staged;
         for (int m = 0; m < M; ++m) {
             const Mod& md = h->mods[m];
-            ra.xhat[m] = h->at<float>(md.out32);
-            ra.ldh[m] = by_mod ? md.ld32 : md.n_in;           // the serve route stores dense [rows][n_input]
-            ra.n_in[m] = md.n_in; ra.binary[m] = h->cfg.mod[m].binary ? 1 : 0;
-            sl.out[m] = h->at<float>(md.out32);
+            ra.xhat[m] = h->at<float>(md.out32); ra.ldh[m] = dec.ld_out32(m);
+            ra.n_in[m] = md.n_in; ra.binary[m] = h->cfg.mod[m].binary ? 1 : 0; ra.ldx[m] = in.ld[m];
         }
         IwReduceArgs rd;
         std::memset(&rd, 0, sizeof(rd));
-        rd.ell = ell; rd.r = rbuf; rd.state = state; rd.width = width; rd.n_mod = M; rd.log_k = std::log((float)K);
-        ra.present = rd.present = pres; la.pres_ld = M;
-        for (int r0 = 0; r0 < rows; r0 += n_rows) {
-            const int n = std::min(n_rows, rows - r0);
-            for (int m = 0; m < M; ++m) {
-                const Mod& md = h->mods[m];
-                const float* xm = x_dev[m] ? x_dev[m] + (size_t)r0 * ld[m] : nullptr;
-                run_prep_single(h, xm, ld[m], n, md.n_in, md.X0, nullptr, 0, false, nullptr, 0, s, r0,
-                                present ? present + (size_t)r0 * M + m : nullptr, present ? pres + m : nullptr, M);
-                run_inference(h, m, true, n, s);
-                ra.x[m] = xm; ra.ldx[m] = ld[m];
-            }
+        rd.ell = ell; rd.r = rbuf; rd.state = state; rd.width = width; rd.n_mod = M; rd.log_k = std::log((float)K); rd.present = pres.staged;
+        for (int r0 = 0; r0 < rows; r0 += blocks.n_rows) {
+            const int n = std::min(blocks.n_rows, rows - r0);
+            stage_and_encode(h, in, pres, r0, n, true, nullptr, s);
+            for (int m = 0; m < M; ++m) ra.x[m] = in.at(m, r0);
             la.eps = eps_dev ? eps_dev + (size_t)r0 * K * nz : nullptr;
             la.row0 = (long long)h->cfg.row_offset + r0;
             rd.out = out_dev + (size_t)r0 * width;
             la.rows = rd.rows = n;
-            for (int k0 = 0; k0 < K; k0 += kb) {
-                const int kc = std::min(kb, K - k0), nd = n * kc;
+            blocks.each(n, [&](int k0, int kc, int nd) {
                 la.k0 = k0; la.kc = ra.kc = rd.kc = kc; ra.n_dec = nd;
                 rd.first = k0 == 0; rd.last = k0 + kc == K;
                 for (int src = 0; src < M; ++src) {
                     la.mulv = h->at<float>(h->mods[src].mulv);
-                    la.present = pres ? pres + src : nullptr;
-                    {
-                        Timed t(h, s, "iw_latent");
-                        launch_iw_latent(h->cfg.compute_dtype, la, s); LAUNCH_OK("iw_latent");
-                    }
-                    if (by_mod) {
-                        for (int d = 0; d < M; ++d) run_inference(h, d, false, nd, s);
-                    } else {
-                        sl.rows = nd;
-                        serve_call(h, serve_plan(h, serve_bucket(h, nd)), sl, s);
-                    }
-                    {
-                        Timed t(h, s, "iw_rows");
-                        launch_iw_rows(ra, s); LAUNCH_OK("iw_rows");
-                    }
+                    la.present = pres ? pres.staged + src : nullptr;
+                    timed_launch(h, s, "iw_latent", [&] { launch_iw_latent(h->cfg.compute_dtype, la, s); });
+                    dec.run(nd, z32, false, nullptr, false, s);
+                    timed_launch(h, s, "iw_rows", [&] { launch_iw_rows(ra, s); });
                     rd.src = src;
-                    {
-                        Timed t(h, s, "iw_reduce");
-                        launch_iw_reduce(rd, s); LAUNCH_OK("iw_reduce");
-                    }
+                    timed_launch(h, s, "iw_reduce", [&] { launch_iw_reduce(rd, s); });
                 }
-            }
+            });
         }
 }
 
@@ -3617,11 +3680,10 @@ int avae_loglik_masked(avae_handle* h, const float* const* x_dev, const int32_t*
 // Fused-posterior prediction of every modality from the ones a row has (include/avae.h).  Per chunk of at
 // most batch_size rows: stage + encode every given modality once (a NULL x_dev[m] runs no encoder) -> k_impute_fuse ([mu_f | lv_f]
 // into the scratch and the caller's rows; n_samples = 0: mu_f as the decoders' z, decoded once).  Then loglik_call's layout over
-// the chunk's rows with `cap` decoded rows per group (n input rows x kb samples; K >= cap: one row over several groups): per group
-// the UNMASKED k_iw_latent on the fused rows (its r goes to scratch and is not read) -> the decoders in passes of at most
-// batch_size rows -> k_impute_accum.  Modality by modality (conv nets / use_graph = 0 / timing) a group is one pass, cap =
-// batch_size, on the decoders' Z / out32 buffers; the serve route keeps up to P passes of z and outputs in the scratch, so the two
-// row kernels run once per P decoder passes.  Scratch: imp_buf (allocated once).
+// the chunk's rows with `cap` decoded rows per group (SampleBlocks): per group the UNMASKED k_iw_latent on the fused rows (its r
+// goes to scratch and is not read) -> the decoders (DecodeAll) -> k_impute_accum.  Modality by modality (conv nets / use_graph = 0
+// / timing) a group is one pass, cap = batch_size, on the decoders' Z / out32 buffers; the serve route keeps up to P passes of z
+// and outputs in the scratch, so the two row kernels run once per P decoder passes.  Scratch: imp_buf.
 constexpr int kImputeGroupPasses = 16;                 // passes per group of the serve route, at most ...
 constexpr size_t kImputeGroupBytes = (size_t)16 << 20;  // ... and at most this many bytes of decoder outputs held per group
 static void impute_call(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, const uint8_t* present, int32_t rows,
@@ -3633,15 +3695,7 @@ static void impute_call(avae_handle* h, const float* const* x_dev, const int32_t
         if (rows == 0) return;
         if (!x_dev) throw Err(w + ": x_dev is NULL");
         const int M = h->M, B = h->B, nz = h->nz, K = n_samples;
-        int ld[kMaxMod] = {0, 0, 0, 0};
-        unsigned mods = 0;
-        for (int m = 0; m < M; ++m) {
-            if (!x_dev[m]) continue;
-            mods |= 1u << m;
-            ld[m] = x_ld ? x_ld[m] : h->mods[m].n_in;
-            if (ld[m] < h->mods[m].n_in)
-                throw Err(w + ": x_ld[" + std::to_string(m) + "] = " + std::to_string(ld[m]) + " is below n_input = " + std::to_string(h->mods[m].n_in));
-        }
+        const RowInputs in(h, w, x_dev, x_ld, NullRows::Absent);
         float* mean_out[kMaxMod] = {nullptr, nullptr, nullptr, nullptr};
         float* var_out[kMaxMod] = {nullptr, nullptr, nullptr, nullptr};
         bool decode = false;
@@ -3652,92 +3706,61 @@ static void impute_call(avae_handle* h, const float* const* x_dev, const int32_t
             decode = decode || mean_out[m] || var_out[m];
             n_all += h->mods[m].n_in;
         }
-        unsigned char* pres = present ? row_presence_buf(h) : nullptr;
+        const RowPresence pres = row_presence(h, present);
         hipStream_t s = on_stream(h, stream);
-        // The serve route decodes a GROUP of up to P passes between one k_iw_latent and one k_impute_accum launch: z and the decoder
-        // outputs of the group live in the scratch (serve_call takes any z / output pointers), at most kImputeGroupBytes of outputs.
-        // The modality-by-modality route works on the decoders' own Z / out32 buffers: one pass per group.
+        // P = passes of one group of the serve route (z and outputs in the scratch, at most kImputeGroupBytes of outputs)
         const int P = (int)std::max<size_t>(1, std::min<size_t>(kImputeGroupPasses, kImputeGroupBytes / ((size_t)B * n_all * sizeof(float))));
         const size_t f_n = (size_t)B * 2 * nz, z_n = rup((size_t)P * B * nz, 2), r_n = rup((size_t)P * B, 2), st_n = (size_t)n_all * 2;
         const size_t o_n = P > 1 ? (size_t)P * B * n_all : 0;
-        if (!h->imp_buf) HIP_OK(hipMalloc(reinterpret_cast<void**>(&h->imp_buf), (f_n + z_n + r_n + st_n + o_n) * sizeof(float)));
-        float* fused = h->imp_buf;
+        float* fused = static_cast<float*>(h->imp_buf.ensure((f_n + z_n + r_n + st_n + o_n) * sizeof(float)));
         float* z32 = fused + f_n;
         float* rbuf = z32 + z_n;
         float* state = rbuf + r_n;                 // (an even float offset: k_impute_accum moves float2)
         float* outs = state + st_n;
-        const bool by_mod = decode_by_mod(h);
-        const bool grouped = !by_mod && P > 1;
+        const DecodeAll dec(h);
+        const bool grouped = !dec.by_mod && P > 1;
         const int cap = grouped ? P * B : B;       // decoded rows of one group
-        const int n_rows = K == 0 ? B : K >= cap ? 1 : cap / K, kb = K >= cap ? cap : K;      // input rows, samples of one group
+        const SampleBlocks blocks(K, cap);         // input rows, samples of one group
         ImputeFuseArgs fa;
         std::memset(&fa, 0, sizeof(fa));
-        fa.mods = mods; fa.present = pres; fa.fused = fused; fa.nz = nz; fa.n_mod = M;
+        fa.mods = in.mods; fa.present = pres.staged; fa.fused = fused; fa.nz = nz; fa.n_mod = M;
         for (int m = 0; m < M; ++m) fa.mulv[m] = h->at<float>(h->mods[m].mulv);
         IwLatentArgs la;
         std::memset(&la, 0, sizeof(la));
         la.mulv = fused; la.nz = nz; la.K = K; la.seed = h->cfg.seed; la.r = rbuf; la.pres_ld = M;
         // a fresh eps per sampled call, keyed as avae_loglik's: draw counter, row of the whole input, sample index
         if (K > 0 && decode) la.draw = next_draw(h, eps_dev);
-        ServeSlot sl;
-        std::memset(&sl, 0, sizeof(sl));
-        sl.z = z32;
+        if (decode) dec.z_dest(la, z32);
+        if (decode && K == 0) dec.z_dest(fa, z32);  // the fuse launch stages z = mu_f itself
         ImputeAccumArgs aa;
         std::memset(&aa, 0, sizeof(aa));
         aa.state = state; aa.ld_state = n_all; aa.K = K; aa.n_mod = M;
+        float* group_out[kMaxMod] = {nullptr, nullptr, nullptr, nullptr};     // grouped: the scratch rows the decoders store into
         for (int m = 0; m < M; ++m) {
             const Mod& md = h->mods[m];
             aa.col0[m] = m ? aa.col0[m - 1] + h->mods[m - 1].n_in : 0;
-            aa.xhat[m] = grouped ? outs + (size_t)cap * aa.col0[m] : h->at<float>(md.out32);
-            aa.ldh[m] = by_mod ? md.ld32 : md.n_in;            // the serve route stores dense [rows][n_input]
+            if (grouped) group_out[m] = outs + (size_t)cap * aa.col0[m];
+            aa.xhat[m] = grouped ? group_out[m] : h->at<float>(md.out32);
+            aa.ldh[m] = dec.ld_out32(m);
             aa.n_in[m] = md.n_in;
             aa.tile0[m + 1] = aa.tile0[m] + (md.n_in + 63) / 64;
-            sl.out[m] = h->at<float>(md.out32);
-        }
-        if (decode && by_mod) {
-            la.n_zdst = M;
-            for (int m = 0; m < M; ++m) { la.Z[m] = h->at<void>(h->mods[m].Z.rm); la.ldz[m] = h->mods[m].Z.ld; }
-        } else if (decode) {
-            la.z32 = z32;
-        }
-        if (K == 0 && decode) {                    // the fuse launch stages z = mu_f itself
-            fa.z32 = la.z32; fa.n_zdst = la.n_zdst;
-            for (int m = 0; m < M; ++m) { fa.Z[m] = la.Z[m]; fa.ldz[m] = la.ldz[m]; }
         }
         for (int r0 = 0; r0 < rows; r0 += B) {
             const int n = std::min(B, rows - r0);
-            for (int m = 0; m < M; ++m) {
-                if (!x_dev[m] && !present) continue;
-                const Mod& md = h->mods[m];
-                run_prep_single(h, x_dev[m] ? x_dev[m] + (size_t)r0 * ld[m] : nullptr, ld[m], n, md.n_in, md.X0, nullptr, 0, false,
-                                nullptr, 0, s, r0, present ? present + (size_t)r0 * M + m : nullptr, present ? pres + m : nullptr, M);
-                if (x_dev[m]) run_inference(h, m, true, n, s);
-            }
+            stage_and_encode(h, in, pres, r0, n, false, nullptr, s);
             fa.rows = n;
             fa.mu = mu_dev ? mu_dev + (size_t)r0 * nz : nullptr;
             fa.lv = logvar_dev ? logvar_dev + (size_t)r0 * nz : nullptr;
-            {
-                Timed t(h, s, "impute_fuse");
-                launch_impute_fuse(h->cfg.compute_dtype, fa, s); LAUNCH_OK("impute_fuse");
-            }
+            timed_launch(h, s, "impute_fuse", [&] { launch_impute_fuse(h->cfg.compute_dtype, fa, s); });
             if (!decode) continue;
-            if (K == 0) {
-                if (by_mod) {
-                    for (int d = 0; d < M; ++d) {
-                        if (!mean_out[d]) continue;
-                        run_inference(h, d, false, n, s);
-                        copy_out32(h, d, mean_out[d] + (size_t)r0 * h->mods[d].n_in, n, s);
-                    }
-                } else {                           // as avae_generate: the output launch stores straight into the caller's rows
-                    sl.rows = n;
-                    for (int d = 0; d < M; ++d)
-                        sl.out[d] = mean_out[d] ? mean_out[d] + (size_t)r0 * h->mods[d].n_in : h->at<float>(h->mods[d].out32);
-                    serve_call(h, serve_plan(h, serve_bucket(h, n)), sl, s);
-                }
+            if (K == 0) {                          // as avae_generate: the rows go straight to the caller (the decoders asked for)
+                float* dst[kMaxMod] = {nullptr, nullptr, nullptr, nullptr};
+                for (int d = 0; d < M; ++d) dst[d] = mean_out[d] ? mean_out[d] + (size_t)r0 * h->mods[d].n_in : nullptr;
+                dec.run(n, z32, false, dst, true, s);
                 continue;
             }
-            for (int j0 = 0; j0 < n; j0 += n_rows) {           // the sample groups of this chunk's rows [j0, j0 + nj)
-                const int nj = std::min(n_rows, n - j0), q0 = r0 + j0;
+            for (int j0 = 0; j0 < n; j0 += blocks.n_rows) {    // the sample groups of this chunk's rows [j0, j0 + nj)
+                const int nj = std::min(blocks.n_rows, n - j0), q0 = r0 + j0;
                 la.mulv = fused + (size_t)j0 * 2 * nz;
                 la.eps = eps_dev ? eps_dev + (size_t)q0 * K * nz : nullptr;
                 la.row0 = (long long)h->cfg.row_offset + q0;
@@ -3746,27 +3769,12 @@ static void impute_call(avae_handle* h, const float* const* x_dev, const int32_t
                     aa.mean[m] = mean_out[m] ? mean_out[m] + (size_t)q0 * h->mods[m].n_in : nullptr;
                     aa.var[m] = var_out[m] ? var_out[m] + (size_t)q0 * h->mods[m].n_in : nullptr;
                 }
-                for (int k0 = 0; k0 < K; k0 += kb) {
-                    const int kc = std::min(kb, K - k0), nd = nj * kc;
+                blocks.each(nj, [&](int k0, int kc, int nd) {
                     la.k0 = aa.k0 = k0; la.kc = aa.kc = kc;
-                    {
-                        Timed t(h, s, "impute_latent");
-                        launch_iw_latent(h->cfg.compute_dtype, la, s); LAUNCH_OK("impute_latent");
-                    }
-                    if (by_mod) {
-                        for (int d = 0; d < M; ++d) run_inference(h, d, false, nd, s);
-                    } else {
-                        for (int c0 = 0; c0 < nd; c0 += B) {   // passes of at most batch_size decoded rows (rows are independent)
-                            sl.z = z32 + (size_t)c0 * nz; sl.rows = std::min(B, nd - c0);
-                            for (int d = 0; d < M; ++d) sl.out[d] = const_cast<float*>(aa.xhat[d]) + (size_t)c0 * h->mods[d].n_in;
-                            serve_call(h, serve_plan(h, serve_bucket(h, sl.rows)), sl, s);
-                        }
-                    }
-                    {
-                        Timed t(h, s, "impute_accum");
-                        launch_impute_accum(aa, s); LAUNCH_OK("impute_accum");
-                    }
-                }
+                    timed_launch(h, s, "impute_latent", [&] { launch_iw_latent(h->cfg.compute_dtype, la, s); });
+                    dec.run(nd, z32, false, grouped ? group_out : nullptr, false, s);     // (rows are independent: any pass split)
+                    timed_launch(h, s, "impute_accum", [&] { launch_impute_accum(aa, s); });
+                });
             }
         }
 }
@@ -3779,7 +3787,6 @@ int avae_impute(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, 
     });
 }
 
-// ---- checkpoint: "AVAECKPT" | u32 version | u32 n_mod | u32 n_z | per modality {n_input, L, hs[L], conv, gener1, gener2} | u64 P | i64 step | theta | m | v
 int avae_complete(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, const uint8_t* const* obs_dev,
                   const float* z0_dev, int32_t rows, int32_t n_iters, float lr, float prior_weight,
                   float* z_dev, float* obj_dev, float* grad_dev, float* const* xhat_dev, void* stream) {
@@ -3793,16 +3800,7 @@ int avae_complete(avae_handle* h, const float* const* x_dev, const int32_t* x_ld
         if (!z0_dev) throw Err("avae_complete: z0_dev is NULL");
         if (!z_dev) throw Err("avae_complete: z_dev is NULL");
         const int M = h->M, nz = h->nz;
-        int ld[kMaxMod] = {0, 0, 0, 0};
-        bool any = false;
-        for (int m = 0; m < M; ++m) {
-            if (!x_dev[m]) continue;
-            any = true;
-            ld[m] = x_ld ? x_ld[m] : h->mods[m].n_in;
-            if (ld[m] < h->mods[m].n_in)
-                throw Err("avae_complete: x_ld[" + std::to_string(m) + "] = " + std::to_string(ld[m]) + " is below n_input = " + std::to_string(h->mods[m].n_in));
-        }
-        if (!any) throw Err("avae_complete: every x_dev[m] is NULL (nothing is observed)");
+        const RowInputs in(h, "avae_complete", x_dev, x_ld, NullRows::Unobserved);
         hipStream_t s = on_stream(h, stream);
         avae_handle::Complete& cp = complete_plan(h);
         const bool graphs = h->cfg.use_graph && !h->timing;
@@ -3811,8 +3809,8 @@ int avae_complete(avae_handle* h, const float* const* x_dev, const int32_t* x_ld
             std::memset(&c, 0, sizeof(c));
             for (int m = 0; m < M; ++m) {
                 const size_t n_in = (size_t)h->mods[m].n_in;
-                if (x_dev[m]) {
-                    c.x[m] = x_dev[m] + (size_t)r0 * ld[m]; c.ldx[m] = ld[m];
+                if (in.x[m]) {
+                    c.x[m] = in.at(m, r0); c.ldx[m] = in.ld[m];
                     if (obs_dev && obs_dev[m]) c.obs[m] = obs_dev[m] + (size_t)r0 * n_in;
                 }
                 if (xhat_dev && xhat_dev[m]) c.xhat[m] = xhat_dev[m] + (size_t)r0 * n_in;
@@ -3821,10 +3819,7 @@ int avae_complete(avae_handle* h, const float* const* x_dev, const int32_t* x_ld
             c.obj = obj_dev ? obj_dev + r0 : nullptr; c.obj_ld = rows;
             c.grad = grad_dev ? grad_dev + (size_t)r0 * nz : nullptr;
             c.rows = std::min(h->B, rows - r0); c.n_iters = n_iters; c.lr = lr; c.prior = prior_weight;
-            {
-                Timed t(h, s, "complete_begin");
-                launch_complete_begin(h->cfg.compute_dtype, cp.args, c, s); LAUNCH_OK("complete_begin");
-            }
+            timed_launch(h, s, "complete_begin", [&] { launch_complete_begin(h->cfg.compute_dtype, cp.args, c, s); });
             int left = n_iters + 1;              // n_iters updating passes and the evaluation at the final z
             if (graphs)
                 for (int i = 0; i < 3; ++i)
@@ -3834,6 +3829,7 @@ int avae_complete(avae_handle* h, const float* const* x_dev, const int32_t* x_ld
     });
 }
 
+// ---- checkpoint: "AVAECKPT" | u32 version | u32 n_mod | u32 n_z | per modality {n_input, L, hs[L], conv, gener1, gener2} | u64 P | i64 step | theta | m | v
 int avae_save(avae_handle* h, const char* path) {
     return guarded(h, [&] {
         std::vector<float> I, th(h->P_flat), mm(h->P_flat), vv(h->P_flat);

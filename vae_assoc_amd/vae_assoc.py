@@ -362,6 +362,20 @@ class AssocVariationalAutoEncoder(object):
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
+    def _new(self, rows, cols):
+        """uninitialised float32 [rows, cols] on the model's device: an output of a forward-only call"""
+        return torch.empty((rows, cols), dtype=torch.float32, device=self.device)
+
+    @staticmethod
+    def _ptrs(ts):
+        """per-modality tensors (None -> NULL) -> the ``void*[M]`` the library takes"""
+        return (C.c_void_p * len(ts))(*[ptr(t) for t in ts])
+
+    @staticmethod
+    def _like_input(was_np):
+        """NumPy in gives NumPy out, device tensors in give device tensors out -> the conversion of one output"""
+        return (lambda a: a.cpu().numpy()) if was_np else (lambda a: a)
+
     def _twin(self, name, head, p, tail):
         """Call entry point ``name`` or, with presence bytes ``p``, its ``_masked`` twin, which takes them after (x, ld): the one
         place where a call picks between the two."""
@@ -558,12 +572,12 @@ class AssocVariationalAutoEncoder(object):
     def _encode(self, m, x, want_logvar=False):
         t, was_np = dev_array(x, self._widths[m], self.device)
         rows = t.shape[0]
-        mu = torch.empty((rows, self.n_z), dtype=torch.float32, device=self.device)
+        mu = self._new(rows, self.n_z)
         lv = torch.empty_like(mu) if want_logvar else None
         if rows:
             _capi.check(self._h, self._L.avae_encode(self._h, m, t.data_ptr(), ld_of(t), rows, mu.data_ptr(), ptr(lv),
                                                      self._stream()), "avae_encode")
-        conv = (lambda a: a.cpu().numpy()) if was_np else (lambda a: a)
+        conv = self._like_input(was_np)
         return (conv(mu), conv(lv)) if want_logvar else conv(mu)
 
     def transform(self, X, sens_idx=None):
@@ -583,11 +597,11 @@ class AssocVariationalAutoEncoder(object):
             z_mu = np.random.normal(size=(self.batch_size, self.n_z))
         z = dev_dense(z_mu, self.n_z, self.device)
         rows = z.shape[0]
-        outs = [torch.empty((rows, cols), dtype=torch.float32, device=self.device) for cols in self._widths]
+        outs = [self._new(rows, cols) for cols in self._widths]
         if rows:       # every modality's decoder in one submission (avae_generate: one graph replay for 1-64 rows)
-            ptrs = (C.c_void_p * len(outs))(*[o.data_ptr() for o in outs])
-            _capi.check(self._h, self._L.avae_generate(self._h, z.data_ptr(), rows, ptrs, self._stream()), "avae_generate")
-        return outs if torch.is_tensor(z_mu) else [o.cpu().numpy() for o in outs]
+            _capi.check(self._h, self._L.avae_generate(self._h, z.data_ptr(), rows, self._ptrs(outs), self._stream()), "avae_generate")
+        conv = self._like_input(not torch.is_tensor(z_mu))
+        return [conv(o) for o in outs]
 
     def reconstruct(self, X, eps=None):
         """Use VAE to reconstruct given data: encode -> sample z -> decode, per modality with its
@@ -599,11 +613,11 @@ class AssocVariationalAutoEncoder(object):
             rows = t.shape[0]
             e = dev_dense(eps[m], self.n_z, self.device) if eps is not None else None
             assert e is None or e.shape[0] == rows
-            o = torch.empty((rows, cols), dtype=torch.float32, device=self.device)
+            o = self._new(rows, cols)
             if rows:
                 _capi.check(self._h, self._L.avae_reconstruct(self._h, m, t.data_ptr(), ld_of(t), ptr(e), rows, o.data_ptr(),
                                                               self._stream()), "avae_reconstruct")
-            outs.append(o.cpu().numpy() if was_np else o)
+            outs.append(self._like_input(was_np)(o))
         return outs
 
     def score_samples(self, X, eps=None, cross_modal=False):
@@ -633,11 +647,10 @@ class AssocVariationalAutoEncoder(object):
         flags = _capi.SCORE_CROSS if cross_modal else 0
         k = C.c_int32(0)
         _capi.check(None, self._L.avae_score_width(C.byref(self._cfg), flags, C.byref(k)), "avae_score_width")
-        out = torch.empty((rows, k.value), dtype=torch.float32, device=self.device)
+        out = self._new(rows, k.value)
         if rows:
             self._twin("avae_score", (ptrs, lds), p, (rows, ptr(e), flags, out.data_ptr()))
-        if was_np:
-            out = out.cpu().numpy()
+        out = self._like_input(was_np)(out)      # one [N, k] array: the entries below are views of it
         P = M * (M - 1) // 2
         res = {"cost": out[:, 0], "recon": out[:, 1:1 + M], "latent": out[:, 1 + M:1 + 2 * M],
                "assoc": out[:, 1 + 2 * M:1 + 2 * M + P]}
@@ -674,11 +687,10 @@ class AssocVariationalAutoEncoder(object):
         K = int(n_samples)
         ts, rows, was_np, ptrs, lds, p = dev_row_args(X, self._widths, self.device, present)
         e = dev_dense3(eps, (rows, K, self.n_z), self.device)
-        out = torch.empty((rows, 2 * M + M * M), dtype=torch.float32, device=self.device)
+        out = self._new(rows, 2 * M + M * M)
         if rows:
             self._twin("avae_loglik", (ptrs, lds), p, (rows, K, ptr(e), out.data_ptr()))
-        if was_np:
-            out = out.cpu().numpy()
+        out = self._like_input(was_np)(out)      # one [N, k] array: the entries below are views of it
         return {"marginal": out[:, :M], "joint": out[:, M:2 * M], "conditional": out[:, 2 * M:].reshape(rows, M, M)}
 
     def complete(self, X, observed=None, n_iters=50, lr=0.05, prior_weight=1.0, z0=None, init=None):
@@ -721,17 +733,13 @@ class AssocVariationalAutoEncoder(object):
             z = self._encode(init, xi).contiguous()
         else:
             z = dev_dense(z0, self.n_z, self.device, rows, name="z0")
-        out_z = torch.empty((rows, self.n_z), dtype=torch.float32, device=self.device)
-        grad = torch.empty_like(out_z)
-        obj = torch.empty((n_iters + 1, rows), dtype=torch.float32, device=self.device)
-        outs = [torch.empty((rows, cols), dtype=torch.float32, device=self.device) for cols in widths]
-        op = (C.c_void_p * M)(*[ptr(o) for o in obs])
-        hp = (C.c_void_p * M)(*[o.data_ptr() for o in outs])
+        out_z, grad, obj = self._new(rows, self.n_z), self._new(rows, self.n_z), self._new(n_iters + 1, rows)
+        outs = [self._new(rows, cols) for cols in widths]
         if rows:
-            _capi.check(self._h, self._L.avae_complete(self._h, xp, lds, op, z.data_ptr(), rows, n_iters, float(lr), float(prior_weight),
-                                                       out_z.data_ptr(), obj.data_ptr(), grad.data_ptr(), hp, self._stream()),
-                        "avae_complete")
-        conv = (lambda a: a.cpu().numpy()) if was_np else (lambda a: a)
+            _capi.check(self._h, self._L.avae_complete(self._h, xp, lds, self._ptrs(obs), z.data_ptr(), rows, n_iters, float(lr),
+                                                       float(prior_weight), out_z.data_ptr(), obj.data_ptr(), grad.data_ptr(),
+                                                       self._ptrs(outs), self._stream()), "avae_complete")
+        conv = self._like_input(was_np)
         return {"z": conv(out_z), "x": [conv(o) for o in outs], "objective": conv(obj), "grad0": conv(grad)}
 
     def impute(self, X, present=None, n_samples=0, eps=None):
@@ -752,18 +760,14 @@ class AssocVariationalAutoEncoder(object):
         modalities included: for them it is a reconstruction) and ``var`` (such a list, or None when ``n_samples == 0``).  NumPy
         in gives NumPy out, device tensors in give device tensors out."""
         widths = self._widths
-        M = len(widths)
         ts, rows, was_np, xp, lds, p, K, e = impute_args(X, present, n_samples, eps, widths, self.n_z, self.device)
-        new = lambda cols: torch.empty((rows, cols), dtype=torch.float32, device=self.device)
-        mu, lv = new(self.n_z), new(self.n_z)
-        mean = [new(cols) for cols in widths]
-        var = [new(cols) for cols in widths] if K else None
-        mp = (C.c_void_p * M)(*[o.data_ptr() for o in mean])
-        vp = (C.c_void_p * M)(*[o.data_ptr() for o in var]) if K else None
+        mu, lv = self._new(rows, self.n_z), self._new(rows, self.n_z)
+        mean = [self._new(rows, cols) for cols in widths]
+        var = [self._new(rows, cols) for cols in widths] if K else None
         if rows:
-            _capi.check(self._h, self._L.avae_impute(self._h, xp, lds, ptr(p), rows, K, ptr(e), mu.data_ptr(), lv.data_ptr(), mp, vp,
-                                                     self._stream()), "avae_impute")
-        conv = (lambda a: a.cpu().numpy()) if was_np else (lambda a: a)
+            _capi.check(self._h, self._L.avae_impute(self._h, xp, lds, ptr(p), rows, K, ptr(e), mu.data_ptr(), lv.data_ptr(),
+                                                     self._ptrs(mean), self._ptrs(var) if K else None, self._stream()), "avae_impute")
+        conv = self._like_input(was_np)
         return {"mu": conv(mu), "logvar": conv(lv), "mean": [conv(o) for o in mean],
                 "var": [conv(o) for o in var] if K else None}
 
