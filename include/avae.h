@@ -154,6 +154,8 @@ int avae_grad_buffer(avae_handle* h, float** dev_ptr, size_t* n_floats);
 int avae_dp_plan(const avae_config* cfg, int32_t* n_buckets, int32_t* n_ranges, int64_t* offs, int64_t* counts);
 int avae_dp_backward(avae_handle* h, int32_t j, int32_t bucket, void* stream);
 int avae_dp_apply(avae_handle* h, int32_t bucket, float* cost_host, void* stream);
+/* With avae_set_grad_clip on, avae_dp_apply(0) first sums the squares of the WHOLE gradient buffer, so in the call order above both
+ * all-reduces come before it (as documented: apply follows the last all-reduce); avae_dp_apply(1) reuses those partial sums. */
 /* 128 bytes of a fresh ncclUniqueId (rank 0 calls this; every rank passes the same bytes in avae_config.nccl_id). */
 int avae_comm_unique_id(void* id128);
 /* AVAE_COMM_IPC bring-up: AVAE_IPC_HANDLE_BYTES describing this replica's exchange block (a hipIpcMemHandle_t + its size and
@@ -239,6 +241,37 @@ int avae_eval_cost_in(avae_handle* h, const float* const* x_dev, const int32_t* 
                       const float* eps_dev, float* cost_host, void* stream);
 int avae_stage_batches_in(avae_handle* h, int32_t n_steps, const float* const* x_dev, const int32_t* x_ld,
                           const float* const* in_dev, const int32_t* in_ld, const float* eps_dev, void* stream);
+
+/* ---- global-norm gradient clipping and non-finite step skipping (the reference has neither: a bare tf.train.AdamOptimizer,
+ * vae_assoc.py:373-374; what a TF-1 caller writes as tf.clip_by_global_norm in front of apply_gradients).  Per step, with g the
+ * step's gradient over the whole model (one replica: the local gradient; data parallel: the all-reduced one; masked and denoising
+ * steps included; the cost slot excluded):
+ *   s    = sum g^2      fp32, in a fixed order that depends on the model's size alone (no atomics: the same inputs give the same bits)
+ *   norm = sqrtf(s)
+ *   c    = (max_norm > 0 && norm > max_norm) ? max_norm / norm : 1.0f          one fp32 division; a select, not a min
+ *   Adam consumes g * c (one fp32 multiplication per element; g * 1.0f == g), its arithmetic unchanged.
+ *  - max_norm = +inf is "monitor only": the norm is computed and recorded, c = 1, and every step is bit for bit the unclipped one;
+ *  - the gradient buffer keeps the RAW gradient: avae_get_grads, avae_grad_buffer and the cost slot are untouched;
+ *  - s not finite -- NaN, Inf, or an fp32 overflow of the sum of squares, tested as !(s <= FLT_MAX) -- with skip_nonfinite = 1: the
+ *    update is SKIPPED.  theta, m, v and every compute-dtype shadow are not written at all (an early exit, not a multiplication by
+ *    0).  A skipped step still consumes its step number: the step counter, lr_t, the eps / corruption keys and the cost history
+ *    (which records the step's own, usually NaN, cost) advance exactly as for an applied step; n_skipped counts such steps.  With
+ *    skip_nonfinite = 0 the NaN goes through Adam into the parameters, as in TensorFlow;
+ *  - the raw norm of every step goes into a device ring of the cost history's depth, indexed like it.
+ * max_norm: 0 = no clipping, > 0 (or +inf) = clip by global norm; NaN or negative: an error naming max_norm.  skip_nonfinite: 0 / 1.
+ * Both 0 = off (the default): the step is the one it was without this call, no norm is computed, avae_grad_norm_history has nothing.
+ * Handle state, set under the handle's mutex; it is not part of avae_save / avae_load.  The call synchronises the device; switching
+ * on <-> off captures the step graphs again (on: weight gradients -> sum of squares -> Adam as three launches, never the small nets'
+ * fused weight-gradient + Adam launch), changing the values alone does not.  Its device state (the threshold, the per-workgroup
+ * partial sums, the norm ring, n_skipped) is allocated by the first call that switches it on and freed by avae_destroy;
+ * avae_workspace_bytes is unchanged.  Every training call goes through it -- avae_train_step(s), the masked and _in calls, the
+ * library-owned data-parallel pipeline (both buckets' all-reduces then precede the first bucket's Adam) and avae_dp_apply;
+ * avae_eval_cost* and every inference call are untouched. */
+int avae_set_grad_clip(avae_handle* h, float max_norm, int32_t skip_nonfinite);
+/* Raw gradient norms of the most recent n steps (oldest first), the step of the last one and the number of steps skipped since
+ * the handle was created.  n may not exceed the history depth (4096) nor the number of steps submitted since clipping was last
+ * switched on (error otherwise); n = 0 is fine at any time.  Synchronises the device. */
+int avae_grad_norm_history(avae_handle* h, int32_t n, float* host_norms, int64_t* last_step, int64_t* n_skipped);
 
 /* evaluate_cost (vae_assoc.py:388-391): forward + loss, no update. */
 int avae_eval_cost(avae_handle* h, const float* const* x_dev, const int32_t* x_ld,

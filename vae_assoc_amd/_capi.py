@@ -35,6 +35,7 @@ SYMBOLS = [
     "avae_eval_cost", "avae_encode", "avae_decode", "avae_generate", "avae_reconstruct", "avae_save", "avae_load",
     "avae_score_width", "avae_score", "avae_loglik", "avae_score_masked", "avae_loglik_masked", "avae_train_steps_masked", "avae_eval_cost_masked", "avae_complete", "avae_impute",
     "avae_set_corruption", "avae_train_steps_in", "avae_eval_cost_in", "avae_stage_batches_in",
+    "avae_set_grad_clip", "avae_grad_norm_history",
     "avae_synchronize", "avae_timing_enable", "avae_timing_report", "avae_debug_fetch", "avae_comm_allreduce",
 ]
 
@@ -109,6 +110,8 @@ def lib():
             L.avae_train_steps_in.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(i32), C.POINTER(vp), C.POINTER(i32), vp, vp, fp, vp]
             L.avae_eval_cost_in.argtypes = [vp, C.POINTER(vp), C.POINTER(i32), C.POINTER(vp), C.POINTER(i32), vp, vp, fp, vp]
             L.avae_stage_batches_in.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(i32), C.POINTER(vp), C.POINTER(i32), vp, vp]
+            L.avae_set_grad_clip.argtypes = [vp, C.c_float, i32]
+            L.avae_grad_norm_history.argtypes = [vp, i32, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
             L.avae_encode.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp]
             L.avae_decode.argtypes = [vp, i32, vp, i32, vp, vp]
             L.avae_generate.argtypes = [vp, vp, i32, C.POINTER(vp), vp]

@@ -98,6 +98,35 @@ def corruption_fields(drop, noise, drop_value, n_mod):
     return p, s, d
 
 
+def grad_clip_fields(max_norm, skip_nonfinite):
+    """The arguments of ``set_grad_clip`` -> (max_norm as a float32-exact float, skip_nonfinite as 0 / 1).  ``max_norm`` None is 0
+    (no clipping), ``float('inf')`` monitors only.  The range is avae_set_grad_clip's, checked here so that a bad value raises
+    ``ValueError`` ahead of the library."""
+    mx = 0.0 if max_norm is None else max_norm
+    if isinstance(mx, (bool, np.bool_)) or not isinstance(mx, (int, float, np.integer, np.floating)):
+        raise ValueError("max_norm must be a number >= 0 (0 = off, inf = monitor only), got %r" % (max_norm,))
+    mx = float(np.float32(mx))
+    if not mx >= 0.0:
+        raise ValueError("max_norm must be >= 0 and not NaN (0 = off, inf = monitor only), got %r" % (max_norm,))
+    return mx, 1 if skip_nonfinite else 0
+
+
+def grad_clip_kwargs(grad_clip):
+    """The ``grad_clip=`` keyword of the constructor and of ``train`` -> the keyword arguments of ``set_grad_clip``: None (off),
+    a number (``max_norm``), or a dict with the keys ``max_norm`` and / or ``skip_nonfinite``."""
+    if grad_clip is None:
+        return {}
+    if isinstance(grad_clip, dict):
+        extra = set(grad_clip) - {"max_norm", "skip_nonfinite"}
+        if extra:
+            raise ValueError("grad_clip: unknown key(s) %s (max_norm, skip_nonfinite)" % ", ".join(sorted(map(str, extra))))
+        kw = dict(grad_clip)
+    else:
+        kw = {"max_norm": grad_clip}
+    grad_clip_fields(kw.get("max_norm", 0.0), kw.get("skip_nonfinite", False))
+    return kw
+
+
 def dev_row_args(X, widths, device, present=None):
     """Arguments of the row calls (any row count) -> (tensors, N, was_numpy, ptrs, lds, presence or None).  Unmasked, the first
     modality gives N.  Masked, ``present`` [N, M] does, ``X[m] = None`` is a modality absent on every row, and was_numpy is

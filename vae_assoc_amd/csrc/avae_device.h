@@ -17,6 +17,21 @@ constexpr int kAdamRows = 16;          // k_adam tiles are kAdamRows x 64: measu
                                        // lighter workgroups balance better over 256 CUs and overlap each other's load and store
                                        // phases); 8 rows (128 threads) 9.3 us and 16-byte segments in the transposed shadow
 constexpr int kCostHist = 4096;        // ring of per-step costs kept on the device
+// k_grad_sumsq (global-norm clipping): G = sumsq_blocks(P_int) workgroups of kSumsqThreads threads.  A thread owns the 16-byte quads
+// tid + k * G * kSumsqThreads of the gradient buffer (k = 0, 1, ...: sumsq_chain(P_int) of them at most) and keeps one accumulator per
+// quad element.  G depends on P_int alone -- never on the device -- so the order of the sum is a constant of the model.
+constexpr int kSumsqThreads = 256;
+constexpr int kSumsqMaxBlocks = 256;   // G <= 256: k_adam's wave 0 sums the partials, four per lane
+constexpr int kSumsqQuads = 8;         // quads per thread below which G grows instead of the chain (128 B in flight per lane)
+inline int sumsq_blocks(long long p_int) {
+    const long long quads = p_int / 4, per_block = (long long)kSumsqThreads * kSumsqQuads;
+    const long long g = (quads + per_block - 1) / per_block;
+    return (int)(g < 1 ? 1 : g > kSumsqMaxBlocks ? kSumsqMaxBlocks : g);
+}
+inline int sumsq_chain(long long p_int) {
+    const long long quads = p_int / 4, per_pass = (long long)kSumsqThreads * sumsq_blocks(p_int);
+    return (int)((quads + per_pass - 1) / per_pass);
+}
 
 // Work-item kinds.  Forward / dgrad kinds compute C[M,N] = sum_k A[m][k] * B[n][k] ("NT": both operands K-contiguous),
 // K_WGRAD computes C[M,N] = sum_k A[k][m] * B[k][n] ("TN": both operands as stored, K = batch); they differ otherwise
@@ -192,6 +207,16 @@ struct DevState {
     float cost_hist[kCostHist];
 };
 
+// Global-norm clipping and non-finite step skipping (include/avae.h, avae_set_grad_clip): a first-use allocation of its own.
+// max_norm / skip_nonfinite are read by the kernels, so changing their values re-captures no graph.
+struct ClipState {
+    float max_norm;                    // 0: no clipping; +inf: monitor only
+    int skip_nonfinite;
+    long long n_skipped;               // steps whose update was skipped
+    float partial[kSumsqMaxBlocks];    // k_grad_sumsq's per-workgroup sums of this step (entries >= G stay zero)
+    float norm_hist[kCostHist];        // raw gradient norm of every step, indexed like DevState::cost_hist
+};
+
 // One dense layer's optimiser tile table entry (Adam + compute-dtype shadow refresh).
 struct AdamItem {
     float* theta;
@@ -221,6 +246,8 @@ struct AdamArgs {
     float lr, beta1, beta2, eps;
     DevState* st;
     const float* cost_src;   // grad[cost slot]
+    ClipState* clip;         // k_adam<.., CLIP = true> only: the step's partial sums of squares, the threshold, the norm ring
+    int n_partial;           // ... and how many partials there are (G)
 };
 
 // Input staging ("prep"): fp32 rows -> compute-dtype copy (+ exact fp32 copy for the losses),
@@ -530,7 +557,8 @@ void launch_grouped(int compute_dtype, int tile_cfg, const LaunchArgs& args, int
                     DevState* st, hipStream_t s, unsigned long long* stamps = nullptr, int launch_id = 0);
 void launch_grouped_tn(int compute_dtype, int tile_cfg, const TnLaunchArgs& args, int grid_x, int grid_y, int lds_bytes,
                        DevState* st, hipStream_t s, unsigned long long* stamps = nullptr, int launch_id = 0);
-void launch_adam(int compute_dtype, const AdamArgs& a, int n_blocks, hipStream_t s);
+void launch_adam(int compute_dtype, const AdamArgs& a, int n_blocks, hipStream_t s);      // a.clip != null: the clip-aware instance
+void launch_grad_sumsq(const float* g, long long p_int, float* partial, hipStream_t s);
 void launch_prep(int compute_dtype, const PrepArgs& a, hipStream_t s);
 const void* prep_kernel(int compute_dtype, bool masked, bool noisy);   // for hipGraphExecKernelNodeSetParams on the captured staging node
 void launch_fill(void* base, int elem_bytes, unsigned bits, long long start, long long stride, int count, hipStream_t s);

@@ -10,6 +10,7 @@
 
 #include <algorithm>
 #include <cctype>
+#include <cstddef>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -292,6 +293,13 @@ struct avae_handle {
     // input (all zero = off).  Handle state only: not saved, and PrepArgs carry it by value, so enqueued work keeps what it was given.
     avae_corruption corr{};
     unsigned drop_thr[kMaxMod] = {};        // floor(drop_prob * 2^24)
+
+    // avae_set_grad_clip: global-norm clipping / non-finite step skipping.  clip_on switches the step's tail to weight gradients ->
+    // k_grad_sumsq -> clip-aware k_adam (never the fused wgrad+adam launch); the threshold and the skip flag live in clip_buf (a
+    // ClipState, allocated by the first call that switches clipping on), where the kernels read them.
+    bool clip_on = false;
+    DevBuf clip_buf;
+    long long clip_steps = 0;               // steps submitted since clipping was last switched on (bounds avae_grad_norm_history)
 
     // avae_complete: the launches of one refinement pass (decoders forward, then their input-gradient chain from the training plan's
     // item builders on the same buffers), captured as runs of kCompleteSizes[i] passes; the kernels' arguments; the scratch behind
@@ -2120,6 +2128,7 @@ void run_launches(avae_handle* h, const std::vector<Launch>& ls, hipStream_t s) 
 
 void run_adam(avae_handle* h, int mode, hipStream_t s, int bucket = -1) {
     AdamArgs a;
+    std::memset(&a, 0, sizeof(a));
     int blocks = h->adam_blocks;
     if (bucket < 0) {
         a.items = h->at<AdamItem>(h->off_adam);
@@ -2138,9 +2147,19 @@ void run_adam(avae_handle* h, int mode, hipStream_t s, int bucket = -1) {
     a.lr = h->cfg.learning_rate; a.beta1 = h->cfg.beta1; a.beta2 = h->cfg.beta2; a.eps = h->cfg.adam_eps;
     a.st = h->state();
     a.cost_src = h->grad() + h->P_int;
+    a.clip = (mode == 0 && h->clip_on) ? h->clip_buf.as<ClipState>() : nullptr;      // the clip-aware instance (mode 1 is never clipped)
+    a.n_partial = sumsq_blocks((long long)h->P_int);
     Timed t(h, s, mode == 0 ? (bucket < 0 ? "adam" : bucket == 0 ? "adam_dec" : "adam_enc") : "shadow_refresh");
     launch_adam(h->cfg.compute_dtype, a, blocks, s);
     LAUNCH_OK(mode == 0 ? "adam" : "shadow_refresh");
+}
+
+// Clipping on: the partial sums of squares of the whole gradient buffer [0, P_int) (the cost slot stays out), ahead of the step's
+// k_adam launch(es), which add them up.
+void run_grad_sumsq(avae_handle* h, hipStream_t s) {
+    ClipState* cs = h->clip_buf.as<ClipState>();
+    if (!cs) throw Err("internal error: clipping is on without its device state");
+    timed_launch(h, s, "grad_sumsq", [&] { launch_grad_sumsq(h->grad(), (long long)h->P_int, cs->partial, s); });
 }
 
 // Where the encoder's copy of a staged batch comes from when it is not the batch itself (include/avae.h, denoising training):
@@ -2280,22 +2299,24 @@ void fill_ones(avae_handle* h, const Act& a, hipStream_t s) {
 }
 
 // One step on staging set j (forward launches `fwd`: a plan's): forward, backward, then the weight gradients with Adam in their
-// epilogue, or followed by k_adam.
+// epilogue, or followed by k_adam; with clipping on always weight gradients -> k_grad_sumsq -> k_adam.
 void step_body(avae_handle* h, const std::vector<Launch>& fwd, hipStream_t s, int j, int stamp_base = -1) {
     auto sb = [&](size_t k) { return stamp_base < 0 ? -1 : stamp_base + (int)k; };
     run_set(h, fwd, 0, fwd.size(), j, s, stamp_base);
     run_set(h, h->bwd, 0, h->bwd.size(), j, s, sb(fwd.size()));
-    if (!h->wgrad_adam.empty()) {       // the optimiser rides in the weight-gradient launch
+    if (!h->wgrad_adam.empty() && !h->clip_on) {       // the optimiser rides in the weight-gradient launch
         run_set(h, h->wgrad_adam, 0, h->wgrad_adam.size(), j, s, sb(fwd.size() + h->bwd.size()));
         return;
     }
     run_set(h, h->wgrad, 0, h->wgrad.size(), j, s, sb(fwd.size() + h->bwd.size()));
+    if (h->clip_on) run_grad_sumsq(h, s);
     run_adam(h, 0, s);
 }
 
-// The graphs of plan p.  `present` non-null: the masked plan (masked staging; the placeholder is patched per replay like the inputs).
-// On failure p keeps no graph.
-void capture_plan(avae_handle* h, StepPlan& p, const uint8_t* present) {
+// The training graphs of plan p (what avae_set_grad_clip captures again when the step's tail changes; eval holds no optimiser).
+// `present` non-null: the masked plan (masked staging; the placeholder is patched per replay like the inputs).  On failure p keeps
+// none of them.
+void capture_steps(avae_handle* h, StepPlan& p, const uint8_t* present) {
     std::vector<const float*> x0(h->M, h->at<float>(h->mods[0].X32));    // placeholders, patched per step
     try {
         p.full = capture(h, [&](hipStream_t cs) {
@@ -2308,6 +2329,13 @@ void capture_plan(avae_handle* h, StepPlan& p, const uint8_t* present) {
             run_prep_batch(h, x0.data(), nullptr, nullptr, h->B, 0x7261696eull, cs, present, kMultiSizes[gi]);
             for (int j = 0; j < kMultiSizes[gi]; ++j) step_body(h, p.fwd, cs, j);
         }, true);
+    } catch (...) { p.full.release(); p.multi[0].release(); p.multi[1].release(); throw; }
+}
+
+// All graphs of plan p.  On failure p keeps no graph.
+void capture_plan(avae_handle* h, StepPlan& p, const uint8_t* present) {
+    try {
+        capture_steps(h, p, present);
         p.eval = capture(h, [&](hipStream_t cs) { run_launches(h, p.fwd, cs); run_launch(h, h->cost_only, cs, nullptr, -1); });
     } catch (...) { p.release(); throw; }
 }
@@ -2610,6 +2638,7 @@ void dp_step(avae_handle* h, int j, hipStream_t s, bool direct = false) {
         // costs fork / join edges (measured, one rank: 0.0583 -> see DESIGN section 6; the two-bucket pipeline pays 35 us for them)
         dp_segment(h, j, 0, s, direct);
         dp_allreduce(h, 0, s);
+        if (h->clip_on) run_grad_sumsq(h, s);       // the norm is that of the REDUCED gradient: every rank forms the same c
         run_adam(h, 0, s, -1);
         return;
     }
@@ -2619,6 +2648,12 @@ void dp_step(avae_handle* h, int j, hipStream_t s, bool direct = false) {
         HIP_OK(hipStreamWaitEvent(h->comm_stream, h->ev_grad[b], 0));
         dp_allreduce(h, b, h->comm_stream);
         HIP_OK(hipEventRecord(h->ev_red[b], h->comm_stream));
+    }
+    if (h->clip_on) {       // the norm needs BOTH reduced buckets before either is applied
+        for (int b = 0; b < h->n_buckets; ++b) HIP_OK(hipStreamWaitEvent(s, h->ev_red[b], 0));
+        run_grad_sumsq(h, s);
+        for (int b = 0; b < h->n_buckets; ++b) run_adam(h, 0, s, b);
+        return;
     }
     for (int b = 0; b < h->n_buckets; ++b) {
         HIP_OK(hipStreamWaitEvent(s, h->ev_red[b], 0));
@@ -3114,6 +3149,7 @@ void train_steps(avae_handle* h, StepPlan& p, int n_steps, const float* const* x
             train_one(h, p, b.x, x_ld, b.pres, b.eps, b.pin(), s);
         }
     }
+    if (h->clip_on) h->clip_steps += n_steps;
     fetch_cost(h, cost_host, true, s);
 }
 
@@ -3280,6 +3316,7 @@ int avae_train_step(avae_handle* h, const float* const* x_dev, const int32_t* x_
     return guarded(h, [&] {
         hipStream_t s = on_stream(h, stream);
         train_one(h, h->plain, x_dev, x_ld, nullptr, eps_dev, PrepIn{nullptr, nullptr, true}, s);
+        if (h->clip_on) ++h->clip_steps;
         fetch_cost(h, cost_host, true, s);
     });
 }
@@ -3319,6 +3356,58 @@ int avae_set_corruption(avae_handle* h, const avae_corruption* c) {
         }
         h->corr = v;
         std::memcpy(h->drop_thr, thr, sizeof(thr));
+    });
+}
+
+int avae_set_grad_clip(avae_handle* h, float max_norm, int32_t skip_nonfinite) {
+    return guarded(h, [&] {
+        if (!(max_norm >= 0.0f)) throw Err("avae_set_grad_clip: max_norm must be >= 0 (0 = no clipping, +inf = monitor only)");
+        if (skip_nonfinite != 0 && skip_nonfinite != 1) throw Err("avae_set_grad_clip: skip_nonfinite must be 0 or 1");
+        const bool on = max_norm > 0.0f || skip_nonfinite != 0;
+        HIP_OK(hipDeviceSynchronize());             // a rare call: enqueued work keeps the setting it was enqueued with
+        if (!on && !h->clip_buf.p) return;          // never switched on
+        ClipState* cs = static_cast<ClipState*>(h->clip_buf.ensure(sizeof(ClipState), true));
+        struct { float max_norm; int skip; } v = {max_norm, skip_nonfinite};
+        static_assert(offsetof(ClipState, skip_nonfinite) == sizeof(float), "the two settings are adjacent");
+        HIP_OK(hipMemcpy(cs, &v, sizeof(v), hipMemcpyHostToDevice));
+        // new values only: the kernels read them from the device (unless an earlier capture failed and left the plan without graphs)
+        if (on == h->clip_on && (!h->cfg.use_graph || h->plain.full.exec)) return;
+        // on <-> off: the step's tail changes, so every graph that holds an optimiser goes; the data-parallel segment graphs hold
+        // none and stay, g_dpm is captured again by its next use
+        h->plain.full.release(); h->plain.multi[0].release(); h->plain.multi[1].release();
+        h->masked.full.release(); h->masked.multi[0].release(); h->masked.multi[1].release();
+        for (StepGraph& g : h->g_dpm) g.release();
+        h->clip_on = on;
+        if (on) h->clip_steps = 0;
+        if (h->cfg.use_graph) {
+            capture_steps(h, h->plain, nullptr);
+            if (!h->masked.fwd.empty()) capture_steps(h, h->masked, h->pres_buf.as<unsigned char>());
+        }
+    });
+}
+
+int avae_grad_norm_history(avae_handle* h, int32_t n, float* host_norms, int64_t* last_step, int64_t* n_skipped) {
+    return guarded(h, [&] {
+        if (n < 0 || n > kCostHist) throw Err("avae_grad_norm_history: n must be in [0, " + std::to_string(kCostHist) + "]");
+        if (n > 0 && !host_norms) throw Err("avae_grad_norm_history: null host_norms");
+        if ((long long)n > (h->clip_on ? h->clip_steps : 0))
+            throw Err("avae_grad_norm_history: " + std::to_string(n) + " norms asked for, " + std::to_string(h->clip_on ? h->clip_steps : 0) +
+                      " steps submitted since clipping was switched on");
+        HIP_OK(hipDeviceSynchronize());
+        comm_check_error(h);
+        long long step = 0;
+        HIP_OK(hipMemcpy(&step, &h->state()->step, sizeof(step), hipMemcpyDeviceToHost));
+        long long skipped = 0;
+        if (h->clip_buf.p) {
+            std::vector<unsigned char> buf(sizeof(ClipState));
+            HIP_OK(hipMemcpy(buf.data(), h->clip_buf.p, sizeof(ClipState), hipMemcpyDeviceToHost));
+            const ClipState* cs = reinterpret_cast<const ClipState*>(buf.data());
+            if (step < n) throw Err("avae_grad_norm_history: fewer steps applied than requested");
+            for (int i = 0; i < n; ++i) host_norms[i] = cs->norm_hist[(step - n + i) % kCostHist];
+            skipped = cs->n_skipped;
+        }
+        if (last_step) *last_step = step;
+        if (n_skipped) *n_skipped = skipped;
     });
 }
 
@@ -3386,6 +3475,7 @@ int avae_dp_apply(avae_handle* h, int32_t bucket, float* cost_host, void* stream
     return guarded(h, [&] {
         if (bucket < 0 || bucket >= h->n_buckets) throw Err("data-parallel bucket out of range");
         hipStream_t s = on_stream(h, stream);
+        if (h->clip_on && bucket == 0) { run_grad_sumsq(h, s); ++h->clip_steps; }      // over the whole buffer: both all-reduces come before apply(0); apply(1) reuses the partials
         run_adam(h, 0, s, h->n_buckets == 1 ? -1 : bucket);
         fetch_cost(h, cost_host, true, s);
     });

@@ -227,6 +227,13 @@ __device__ __forceinline__ float act_bwd(int act, float y) {
 // store round trip (~1 us) in front of each barrier; the data exchanged here lives in LDS.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
+// Sum over the 64 lanes of a wave in a fixed order (shuffle tree); the total is valid in lane 0.
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    return v;
+}
+
 // Sum over the NW*64 threads of the block, same value returned to every thread, fixed order.
 template <int NW = 4> __device__ __forceinline__ float block_sum(float v, float* red) {
 #pragma unroll
@@ -2424,11 +2431,42 @@ void launch_grouped_tn(int compute_dtype, int tile_cfg, const TnLaunchArgs& args
 //   theta -= lr_t*m/(sqrt(v)+eps)                       (epsilon outside the bias correction)
 // Tile-wise over each layer's [in+1][out] matrix so the same pass emits the compute-dtype shadow
 // W (row-major, dgrad operand) and, through an LDS transpose, W^T (forward operand).
-template <typename CT, int TR>
+//
+// CLIP (avae_set_grad_clip; mode 0 only): k_grad_sumsq left G partial sums of squares of the step's gradient.  Wave 0 of EVERY
+// workgroup adds them in one fixed order (four per lane, then the shuffle tree), so every workgroup -- and every rank of a
+// data-parallel run, whose partials come from the same all-reduced bits -- forms bitwise the same s, norm and factor c, broadcast
+// through LDS.  The gradient is scaled by c on its way into adam_update (one fp32 multiplication; the buffer keeps the raw value).
+// A non-finite s with skip_nonfinite set ends the workgroup before it has stored anything: theta, m, v and every shadow keep their bits.
+template <typename CT, int TR, bool CLIP>
 __global__ void __launch_bounds__(kThreads) k_adam(AdamArgs a) {
     static_assert(TR % 16 == 0 && TR <= 64, "a pass covers 16 rows x 16 quads");
     constexpr int NTH = kThreads;
     __shared__ float T[TR][65];
+    float clip_c = 1.0f;
+    bool clip_skip = false;
+    if constexpr (CLIP) {
+        __shared__ float clip_sh[2];
+        if (threadIdx.x < 64) {
+            const int l = threadIdx.x;
+            float p[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) p[k] = (l + 64 * k < a.n_partial) ? a.clip->partial[l + 64 * k] : 0.0f;
+            const float s = wave_sum((p[0] + p[1]) + (p[2] + p[3]));
+            if (l == 0) {
+                const float norm = sqrtf(s), mx = a.clip->max_norm;
+                const bool skip = a.clip->skip_nonfinite != 0 && !(s <= 3.402823466e+38f);
+                clip_sh[0] = (mx > 0.0f && norm > mx) ? mx / norm : 1.0f;
+                clip_sh[1] = skip ? 1.0f : 0.0f;
+                if (a.book && blockIdx.x == gridDim.x - 1) {           // the workgroup that books the step's cost (bid == 0 below)
+                    a.clip->norm_hist[(a.st->step - 1) % kCostHist] = norm;
+                    if (skip) a.clip->n_skipped += 1;
+                }
+            }
+        }
+        lds_barrier();
+        clip_c = clip_sh[0];
+        clip_skip = clip_sh[1] != 0.0f;
+    }
     // Tiles are taken LAST FIRST: the launch streams 32 bytes per parameter through the Infinity Cache (256 MiB), so what it
     // touches last is what the next step's first launches find there -- the encoders' weight shadows, not the decoders'.
     const int bid = (int)gridDim.x - 1 - (int)blockIdx.x, tid = threadIdx.x;
@@ -2444,6 +2482,9 @@ __global__ void __launch_bounds__(kThreads) k_adam(AdamArgs a) {
         const float c = *a.cost_src;
         a.st->last_cost = c;
         a.st->cost_hist[(a.st->step - 1) % kCostHist] = c;
+    }
+    if constexpr (CLIP) {
+        if (clip_skip) return;      // block-uniform: a skipped step is booked (above) and stores nothing else
     }
     const float lr_t = a.mode == 0 ? a.st->lr_t : 0.0f;
     const float omb1 = 1.0f - a.beta1, omb2 = 1.0f - a.beta2;
@@ -2463,7 +2504,7 @@ __global__ void __launch_bounds__(kThreads) k_adam(AdamArgs a) {
                 load4<float>(w.m + off, m);
                 load4<float>(w.v + off, v);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) adam_update(g[e], m[e], v[e], th[e], omb1, omb2, lr_t, a.eps);
+                for (int e = 0; e < 4; ++e) adam_update(CLIP ? g[e] * clip_c : g[e], m[e], v[e], th[e], omb1, omb2, lr_t, a.eps);
                 const int nv = w.cols - gcol;
                 store_row<float>(w.theta + off, th, nv);
                 store_row<float>(w.m + off, m, nv);
@@ -2502,8 +2543,38 @@ __global__ void __launch_bounds__(kThreads) k_adam(AdamArgs a) {
 }
 
 void launch_adam(int compute_dtype, const AdamArgs& a, int n_blocks, hipStream_t s) {
-    if (compute_dtype == AVAE_BF16) AVAE_LAUNCH((k_adam<__bf16, kAdamRows>), dim3(n_blocks), dim3(kThreads), 0, s, a);
-    else AVAE_LAUNCH((k_adam<float, kAdamRows>), dim3(n_blocks), dim3(kThreads), 0, s, a);
+    if (a.clip && a.mode == 0) {
+        if (compute_dtype == AVAE_BF16) AVAE_LAUNCH((k_adam<__bf16, kAdamRows, true>), dim3(n_blocks), dim3(kThreads), 0, s, a);
+        else AVAE_LAUNCH((k_adam<float, kAdamRows, true>), dim3(n_blocks), dim3(kThreads), 0, s, a);
+        return;
+    }
+    if (compute_dtype == AVAE_BF16) AVAE_LAUNCH((k_adam<__bf16, kAdamRows, false>), dim3(n_blocks), dim3(kThreads), 0, s, a);
+    else AVAE_LAUNCH((k_adam<float, kAdamRows, false>), dim3(n_blocks), dim3(kThreads), 0, s, a);
+}
+
+// ------------------------------------------------------------------ sum of squares of the gradient (global-norm clipping)
+// partial[b] = sum of g^2 over the quads workgroup b owns; [0, p_int) is the gradient buffer without its cost slot (p_int % 32 == 0,
+// pads zero).  Thread t of workgroup b takes the 16-byte quads (b * kSumsqThreads + t) + k * G * kSumsqThreads, k = 0, 1, ... in
+// that order -- consecutive lanes on consecutive quads, a wave reading 1 KiB per pass -- with one accumulator per quad element
+// (explicit fused multiply-adds); then (e0 + e1) + (e2 + e3), the wave's shuffle tree, the four waves through LDS: one order for a
+// given p_int, whatever the device.  No atomics; the partial leaves by a plain store.
+__global__ void __launch_bounds__(kSumsqThreads) k_grad_sumsq(const float* __restrict__ g, long long n_quads, float* __restrict__ partial) {
+    __shared__ float red[kSumsqThreads / 64];
+    const long long stride = (long long)gridDim.x * kSumsqThreads;
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+    for (long long q = (long long)blockIdx.x * kSumsqThreads + threadIdx.x; q < n_quads; q += stride) {
+        float v[4];
+        load4<float>(g + q * 4, v);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[e] = __builtin_fmaf(v[e], v[e], acc[e]);
+    }
+    const float t = block_sum<kSumsqThreads / 64>((acc[0] + acc[1]) + (acc[2] + acc[3]), red);
+    if (threadIdx.x == 0) partial[blockIdx.x] = t;
+}
+
+void launch_grad_sumsq(const float* g, long long p_int, float* partial, hipStream_t s) {
+    AVAE_LAUNCH(k_grad_sumsq, dim3(sumsq_blocks(p_int)), dim3(kSumsqThreads), 0, s, g, p_int / 4, partial);
 }
 
 // ------------------------------------------------------------------ input staging + eps
@@ -3516,13 +3587,6 @@ void launch_fill(void* base, int elem_bytes, unsigned bits, long long start, lon
 }
 
 // ------------------------------------------------------------------ per-row scoring (avae_score)
-// Sum over the 64 lanes of a wave in a fixed order (shuffle tree); the total is valid in lane 0.
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
 // Bit m = presence byte m of one row of a staged [rows][n_mod] presence array.  Every lane of the wave asks for the same row; the
 // result goes through readfirstlane, so it sits in an SGPR and every branch on it is a scalar branch: the shuffle trees behind such
 // a branch run on whole waves or not at all.

@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from . import _capi
-from ._marshal import (corruption_fields, dev_array, dev_dense, dev_dense3, dev_flags, dev_inputs, dev_modalities, dev_row_args,
+from ._marshal import (corruption_fields, grad_clip_fields, grad_clip_kwargs, dev_array, dev_dense, dev_dense3, dev_flags, dev_inputs, dev_modalities, dev_row_args,
                        ld_of, ptr)
 from .parallel import GradSync, dp_bucket_schedule, dp_train_step_bucketed
 
@@ -308,12 +308,15 @@ class AssocVariationalAutoEncoder(object):
       wire_dtype     'fp32' (default) or 'bf16': element type of the gradient on the wire (the cost always travels as fp32)
       corruption     None, or a dict of ``set_corruption``'s arguments (``drop``, ``noise``, ``drop_value``): denoising training,
                      every training step corrupts the encoder's copy of the batch on the device while the losses keep the clean one
+      grad_clip      None, a number (``max_norm``) or a dict of ``set_grad_clip``'s arguments (``max_norm``, ``skip_nonfinite``):
+                     clip every step's gradient by its global norm and / or skip a step whose gradient is not finite
     """
 
     def __init__(self, network_architectures, binary=True, transfer_fct="softplus", weights=1.0,
                  assoc_lambda=1.0, learning_rate=0.001, batch_size=100, *, compute_dtype="bf16",
                  device=None, seed=0, use_graph=True, data_parallel=False, process_group=None, comm=None,
-                 comm_buckets=2, wire_dtype="fp32", corruption=None):
+                 comm_buckets=2, wire_dtype="fp32", corruption=None, grad_clip=None):
+        clip_kw = grad_clip_kwargs(grad_clip)        # (a bad value raises before anything is built)
         def placement():
             if not torch.cuda.is_available():
                 raise RuntimeError("vae_assoc_amd needs a HIP device (MI355X / gfx950); there is no CPU fallback")
@@ -349,6 +352,8 @@ class AssocVariationalAutoEncoder(object):
         self.set_params(initial_params(network_architectures, seed))
         if corruption is not None:
             self.set_corruption(**corruption)
+        if clip_kw:
+            self.set_grad_clip(**clip_kw)
 
     # ------------------------------------------------------------------ plumbing
     def __del__(self):
@@ -467,6 +472,28 @@ class AssocVariationalAutoEncoder(object):
         for m in range(len(self._widths)):
             c.drop_prob[m], c.noise_std[m], c.drop_value[m] = p[m], s[m], d[m]
         _capi.check(self._h, self._L.avae_set_corruption(self._h, C.byref(c)), "avae_set_corruption")
+
+    def set_grad_clip(self, max_norm=0.0, skip_nonfinite=False):
+        """Global-norm gradient clipping and non-finite step skipping (avae_set_grad_clip in include/avae.h, DESIGN.md section
+        15) -- where a TF-1 caller of the reference wrote ``tf.clip_by_global_norm`` in front of the optimiser.  From now on every
+        training step measures the norm of its whole gradient (the all-reduced one under data parallelism) and Adam consumes
+        ``g * max_norm / norm`` whenever ``norm > max_norm``; ``get_grads`` keeps returning the raw gradient.
+        ``max_norm=float('inf')`` only monitors (``grad_norm_history``), ``max_norm=0`` does not clip.  ``skip_nonfinite=True``:
+        a step whose gradient holds a NaN or Inf (or whose sum of squares overflows fp32) leaves the parameters and the Adam
+        moments untouched; it still counts as a step (step counter, eps keys, cost history).  Both off (the default) is the
+        step as it was.  The call synchronises the device; the setting is not saved by ``save_model``."""
+        mx, skip = grad_clip_fields(max_norm, skip_nonfinite)
+        _capi.check(self._h, self._L.avae_set_grad_clip(self._h, C.c_float(mx), skip), "avae_set_grad_clip")
+
+    def grad_norm_history(self, n):
+        """-> (norms, last_step, n_skipped): the raw (unclipped) gradient norms of the most recent ``n`` steps as a float32
+        array, oldest first; the step number of the last one; the number of steps skipped since the model was built.  ``n`` may
+        not exceed the number of steps trained since ``set_grad_clip`` switched the feature on (nor the history's 4096)."""
+        out = np.empty(n, dtype=np.float32)
+        last, skipped = C.c_int64(0), C.c_int64(0)
+        _capi.check(self._h, self._L.avae_grad_norm_history(self._h, n, out.ctypes.data_as(C.c_void_p), C.byref(last),
+                                                            C.byref(skipped)), "avae_grad_norm_history")
+        return out, last.value, skipped.value
 
     def synchronize(self):
         _capi.check(self._h, self._L.avae_synchronize(self._h), "avae_synchronize")
@@ -826,7 +853,10 @@ def train(data_sets, network_architectures, binary=True, weights=1.0, assoc_lamb
 
     ``corruption=dict(drop=..., noise=..., drop_value=...)`` (``set_corruption``'s arguments) trains with the denoising
     criterion: every training step corrupts the encoders' copy of its batch on the device, the losses keep the clean rows.  The
-    validation cost of ``early_stop`` stays clean.  Under ``data_parallel`` every rank must pass the same ``seed``, as for eps."""
+    validation cost of ``early_stop`` stays clean.  Under ``data_parallel`` every rank must pass the same ``seed``, as for eps.
+
+    ``grad_clip=max_norm`` or ``grad_clip=dict(max_norm=..., skip_nonfinite=...)`` (``set_grad_clip``'s arguments) clips every
+    step's gradient by its global norm and / or skips a step whose gradient is not finite."""
     vae_assoc =AssocVariationalAutoEncoder(network_architectures, binary, transfer_fct="relu", weights=weights,
                                             assoc_lambda=assoc_lambda, learning_rate=learning_rate,
                                             batch_size=batch_size, **model_kwargs)
