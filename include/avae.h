@@ -273,6 +273,61 @@ int avae_set_grad_clip(avae_handle* h, float max_norm, int32_t skip_nonfinite);
  * switched on (error otherwise); n = 0 is fine at any time.  Synchronises the device. */
 int avae_grad_norm_history(avae_handle* h, int32_t n, float* host_norms, int64_t* last_step, int64_t* n_skipped);
 
+/* ---- on-device training schedules: KL warm-up (beta annealing, monotone or cyclical), association ramp, learning-rate decay (the
+ * reference has none: its coefficients are Python constants, vae_assoc.py:26-31; what a TF-1 caller writes as
+ * tf.train.exponential_decay, or a placeholder fed per step).  Every training step has three fp32 multipliers kl_t, a_t, l_t, all 1
+ * by default.  With t the step number the update gets (the device step counter + 1 before the step, what avae_get_opt_state
+ * reports after it) and u = t - 1:
+ *   cost_t   = sum_m w_m [ kl_t * latent_m + recon_m ]  +  lambda_t * sum_pairs assoc
+ *   lambda_t = fl32(assoc_lambda * a_t)
+ *   lr_eff_t = fl32(learning_rate * l_t)
+ *   lr_t     = (float)((double)lr_eff_t * sqrt(1 - beta2^t) / (1 - beta1^t))        Adam's step size, learning_rate replaced
+ * and the step's gradient is the gradient of cost_t.  The mean / sum divisors, the presence selects, the denoising inputs and
+ * clipping are unchanged.  The KL weight of modality m is (w_m / B_g) * kl_t in this order, so kl_t = 1 gives the unscheduled bits.
+ * kl_t is a MULTIPLICATION, not a select: a multiplier of 0 does not hide a non-finite KL term (0 * inf = NaN).  The step's recorded
+ * cost (avae_cost_history, the cost returned by the training calls, the data-parallel cost slot) is cost_t.
+ * A schedule is a function of the step number alone:
+ *   AVAE_SCHED_NONE       1
+ *   AVAE_SCHED_PIECEWISE  n_knots in 1..8 knots (knot_step[i], knot_value[i]); knot_step[0] >= 0, strictly increasing; values finite
+ *                         and >= 0; period >= 0, and with period > 0: u <- u % period (cyclical annealing), knot_step[last] < period
+ *                         required.  Value: knot_value[0] for u <= knot_step[0], knot_value[last] for u >= knot_step[last], else for
+ *                         s_i <= u < s_{i+1}
+ *                           (float)((double)v_i + ((double)v_{i+1} - (double)v_i) * ((double)(u - s_i) / (double)(s_{i+1} - s_i)))
+ *                         without contraction, rounded once: host and device give the same bits
+ *   AVAE_SCHED_EXP        (float)pow((double)decay_rate, e),  e = staircase ? (double)(u / decay_steps) : (double)u / (double)decay_steps;
+ *                         decay_rate finite and > 0, decay_steps > 0
+ * so step t gets the same multipliers alone, inside a 16- or 4-step replay, masked or not, with or without graphs, on every
+ * data-parallel rank, and after avae_load / avae_set_opt_state restored the step counter; a step skipped by skip_nonfinite still
+ * consumes its number.  The values are evaluated on the device by the staging launch of each submission (no launch is added to
+ * the step, the host stays out of the multi-step replays).
+ * Evaluation and inference NEVER read a schedule: avae_eval_cost*, avae_score*, avae_loglik*, avae_complete and avae_impute are bit
+ * for bit what they are without one (multipliers 1: the configured objective), as for the denoising inputs.
+ * avae_set_schedule: NULL or kind AVAE_SCHED_NONE = off for that quantity; all three off is the default.  Errors name the field.
+ * Handle state, set under the handle's mutex; not part of avae_save / avae_load.  The call synchronises the device; switching on
+ * <-> off (any schedule set <-> none) captures the step graphs again, changing the schedules does not.  Its device state is
+ * allocated by the first call that switches it on and freed by avae_destroy; avae_workspace_bytes is unchanged. */
+#define AVAE_SCHED_NONE 0
+#define AVAE_SCHED_PIECEWISE 1
+#define AVAE_SCHED_EXP 2
+#define AVAE_SCHED_MAX_KNOTS 8
+typedef struct avae_schedule {
+    int32_t kind, n_knots;
+    int64_t period;
+    int64_t knot_step[AVAE_SCHED_MAX_KNOTS];
+    float knot_value[AVAE_SCHED_MAX_KNOTS];
+    float decay_rate;
+    int32_t staircase;
+    int64_t decay_steps;
+} avae_schedule;
+int avae_set_schedule(avae_handle* h, const avae_schedule* kl, const avae_schedule* assoc, const avae_schedule* lr);
+/* The multiplier of `schedule` at step number t >= 1 (host only, no GPU; the evaluator the device runs).  NULL schedule: 1.  A
+ * failure leaves its message in avae_last_error(NULL). */
+int avae_schedule_value(const avae_schedule* schedule, int64_t step, float* out);
+/* {kl_t, lambda_t, lr_eff_t} of the most recent n steps (oldest first, host_dst [n][3]) and the step of the last one.  n may not
+ * exceed the history depth (4096) nor the number of steps submitted since a schedule was last switched on; n = 0 is fine at any
+ * time.  Synchronises the device. */
+int avae_hyper_history(avae_handle* h, int32_t n, float* host_dst, int64_t* last_step);
+
 /* evaluate_cost (vae_assoc.py:388-391): forward + loss, no update. */
 int avae_eval_cost(avae_handle* h, const float* const* x_dev, const int32_t* x_ld,
                    const float* eps_dev, float* cost_host, void* stream);

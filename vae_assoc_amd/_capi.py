@@ -36,6 +36,7 @@ SYMBOLS = [
     "avae_score_width", "avae_score", "avae_loglik", "avae_score_masked", "avae_loglik_masked", "avae_train_steps_masked", "avae_eval_cost_masked", "avae_complete", "avae_impute",
     "avae_set_corruption", "avae_train_steps_in", "avae_eval_cost_in", "avae_stage_batches_in",
     "avae_set_grad_clip", "avae_grad_norm_history",
+    "avae_set_schedule", "avae_schedule_value", "avae_hyper_history",
     "avae_synchronize", "avae_timing_enable", "avae_timing_report", "avae_debug_fetch", "avae_comm_allreduce",
 ]
 
@@ -63,6 +64,16 @@ class Config(C.Structure):
 class Corruption(C.Structure):
     _fields_ = [("drop_prob", C.c_float * AVAE_MAX_MODALITIES), ("drop_value", C.c_float * AVAE_MAX_MODALITIES),
                 ("noise_std", C.c_float * AVAE_MAX_MODALITIES)]
+
+
+SCHED_NONE, SCHED_PIECEWISE, SCHED_EXP = 0, 1, 2
+SCHED_MAX_KNOTS = 8
+
+
+class Schedule(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("n_knots", C.c_int32), ("period", C.c_int64),
+                ("knot_step", C.c_int64 * SCHED_MAX_KNOTS), ("knot_value", C.c_float * SCHED_MAX_KNOTS),
+                ("decay_rate", C.c_float), ("staircase", C.c_int32), ("decay_steps", C.c_int64)]
 
 
 _lib = None
@@ -112,6 +123,9 @@ def lib():
             L.avae_stage_batches_in.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(i32), C.POINTER(vp), C.POINTER(i32), vp, vp]
             L.avae_set_grad_clip.argtypes = [vp, C.c_float, i32]
             L.avae_grad_norm_history.argtypes = [vp, i32, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+            L.avae_set_schedule.argtypes = [vp, C.POINTER(Schedule), C.POINTER(Schedule), C.POINTER(Schedule)]
+            L.avae_schedule_value.argtypes = [C.POINTER(Schedule), C.c_int64, fp]
+            L.avae_hyper_history.argtypes = [vp, i32, vp, C.POINTER(C.c_int64)]
             L.avae_encode.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp]
             L.avae_decode.argtypes = [vp, i32, vp, i32, vp, vp]
             L.avae_generate.argtypes = [vp, vp, i32, C.POINTER(vp), vp]

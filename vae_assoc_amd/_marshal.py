@@ -127,6 +127,160 @@ def grad_clip_kwargs(grad_clip):
     return kw
 
 
+SCHEDULE_NAMES = ("kl", "assoc", "lr")
+
+
+def _is_number(x):
+    return not isinstance(x, (bool, np.bool_)) and isinstance(x, (int, float, np.integer, np.floating))
+
+
+def _whole(x, name):
+    """A step count given as an int, or as a float that holds one."""
+    if not _is_number(x) or not np.isfinite(x) or float(x) != int(x):
+        raise ValueError("%s must be a whole number of steps, got %r" % (name, x))
+    return int(x)
+
+
+def schedule_spec(spec, name="schedule"):
+    """One argument of ``set_schedule`` -> None (off), or a checked dict in one of the two canonical forms
+    ``dict(knots=[(step, value), ...], period=int)`` / ``dict(decay_rate=, decay_steps=, staircase=)``.  A number is the constant
+    multiplier (one knot).  The ranges are avae_set_schedule's, checked here so that a bad value raises ``ValueError`` -- naming
+    the schedule and the field -- ahead of the library."""
+    if spec is None:
+        return None
+    if _is_number(spec):
+        spec = dict(knots=[(0, spec)])
+    if not isinstance(spec, dict):
+        raise ValueError("%s must be None, a number, dict(knots=, period=) or dict(decay_rate=, decay_steps=, staircase=), got %r"
+                         % (name, spec))
+    if "knots" in spec:
+        extra = set(spec) - {"knots", "period"}
+        if extra:
+            raise ValueError("%s: unknown key(s) %s (knots, period)" % (name, ", ".join(sorted(map(str, extra)))))
+        knots = list(spec["knots"])
+        if not 1 <= len(knots) <= 8:
+            raise ValueError("%s: knots (n_knots) must hold 1 to 8 (step, value) pairs, got %d" % (name, len(knots)))
+        out, prev = [], -1
+        for i, kv in enumerate(knots):
+            if len(kv) != 2:
+                raise ValueError("%s: knots[%d] must be a (step, value) pair, got %r" % (name, i, kv))
+            st = _whole(kv[0], "%s: knots[%d] step (knot_step)" % (name, i))
+            if st <= prev:
+                raise ValueError("%s: knots[%d] step (knot_step) = %d must be %s" % (name, i, st, ">= 0" if i == 0 else
+                                                                                     "above the previous knot's (strictly increasing)"))
+            if not _is_number(kv[1]) or not (np.isfinite(kv[1]) and float(np.float32(kv[1])) >= 0.0 and np.isfinite(np.float32(kv[1]))):
+                raise ValueError("%s: knots[%d] value (knot_value) must be finite and >= 0, got %r" % (name, i, kv[1]))
+            out.append((st, float(np.float32(kv[1]))))
+            prev = st
+        period = spec.get("period")
+        period = 0 if period is None else _whole(period, "%s: period" % name)
+        if period < 0:
+            raise ValueError("%s: period must be >= 0, got %d" % (name, period))
+        if period > 0 and out[-1][0] >= period:
+            raise ValueError("%s: the last knot's step (knot_step) = %d must be below period = %d" % (name, out[-1][0], period))
+        return dict(knots=out, period=period)
+    if "decay_rate" in spec or "decay_steps" in spec:
+        extra = set(spec) - {"decay_rate", "decay_steps", "staircase"}
+        if extra:
+            raise ValueError("%s: unknown key(s) %s (decay_rate, decay_steps, staircase)" % (name, ", ".join(sorted(map(str, extra)))))
+        rate, steps = spec.get("decay_rate"), spec.get("decay_steps")
+        if not _is_number(rate) or not (np.isfinite(np.float32(rate)) and float(np.float32(rate)) > 0.0):
+            raise ValueError("%s: decay_rate must be finite and > 0, got %r" % (name, rate))
+        steps = _whole(steps, "%s: decay_steps" % name)
+        if steps <= 0:
+            raise ValueError("%s: decay_steps must be > 0, got %d" % (name, steps))
+        return dict(decay_rate=float(np.float32(rate)), decay_steps=steps, staircase=bool(spec.get("staircase", False)))
+    raise ValueError("%s: a dict needs knots= or decay_rate= / decay_steps=, got keys %s" % (name, sorted(map(str, spec))))
+
+
+def schedule_struct(spec, name="schedule"):
+    """One argument of ``set_schedule`` -> its ``avae_schedule`` (``_capi.Schedule``), or None for off."""
+    from ._capi import SCHED_EXP, SCHED_PIECEWISE, Schedule
+    spec = schedule_spec(spec, name)
+    if spec is None:
+        return None
+    sc = Schedule()
+    if "knots" in spec:
+        sc.kind, sc.n_knots, sc.period = SCHED_PIECEWISE, len(spec["knots"]), spec["period"]
+        for i, (st, v) in enumerate(spec["knots"]):
+            sc.knot_step[i], sc.knot_value[i] = st, v
+    else:
+        sc.kind, sc.decay_rate, sc.decay_steps, sc.staircase = SCHED_EXP, spec["decay_rate"], spec["decay_steps"], int(spec["staircase"])
+    return sc
+
+
+def schedule_in_steps(spec, steps_per_unit, name="schedule"):
+    """A schedule whose knot steps, period and ``decay_steps`` count units of ``steps_per_unit`` steps (epochs) -> the same
+    schedule in steps, checked.  Fractions of a unit are fine where they come to whole steps."""
+    if spec is None or _is_number(spec):
+        return schedule_spec(spec, name)
+    if not isinstance(spec, dict):
+        return schedule_spec(spec, name)           # (raises)
+    if steps_per_unit < 1:
+        raise ValueError("%s: an epoch of this data set holds no step" % name)
+    out = dict(spec)
+
+    def conv(x, what):
+        if not _is_number(x) or not np.isfinite(x):
+            raise ValueError("%s: %s must be a number of epochs, got %r" % (name, what, x))
+        return _whole(round(float(x) * steps_per_unit, 9), "%s: %s in steps" % (name, what))
+    if "knots" in out:
+        out["knots"] = [(conv(kv[0], "knots[%d] step" % i), kv[1]) if len(kv) == 2 else kv for i, kv in enumerate(out["knots"])]
+        if out.get("period") is not None:
+            out["period"] = conv(out["period"], "period")
+    if out.get("decay_steps") is not None:
+        out["decay_steps"] = conv(out["decay_steps"], "decay_steps")
+    return schedule_spec(out, name)
+
+
+def schedule_kwargs(schedule, steps_per_epoch=None):
+    """The ``schedule=`` keyword of the constructor and of ``train`` -> the keyword arguments of ``set_schedule``: None (off) or a
+    dict with the keys ``kl``, ``assoc``, ``lr`` (each an argument of ``set_schedule``) and ``unit`` ('step', the default, or
+    'epoch').  With ``steps_per_epoch`` given, a schedule in epochs is converted to steps; without it the schedules are only
+    checked, as they stand (the ranges are the same in either unit)."""
+    if schedule is None:
+        return {}
+    if not isinstance(schedule, dict):
+        raise ValueError("schedule must be None or a dict with the keys kl, assoc, lr and unit, got %r" % (schedule,))
+    extra = set(schedule) - set(SCHEDULE_NAMES) - {"unit"}
+    if extra:
+        raise ValueError("schedule: unknown key(s) %s (kl, assoc, lr, unit)" % ", ".join(sorted(map(str, extra))))
+    unit = schedule.get("unit", "step")
+    if unit not in ("step", "epoch"):
+        raise ValueError("schedule: unit must be 'step' or 'epoch', got %r" % (unit,))
+    kw = {}
+    for name in SCHEDULE_NAMES:
+        if schedule.get(name) is None:
+            continue
+        if unit == "epoch":
+            kw[name] = schedule_in_steps(schedule[name], 1 if steps_per_epoch is None else steps_per_epoch, name)
+        else:
+            kw[name] = schedule_spec(schedule[name], name)
+    return kw
+
+
+def linear_warmup(n_steps, start=0.0):
+    """Multiplier rising linearly from ``start`` at the first step to 1 after ``n_steps`` steps, 1 from then on (KL warm-up)."""
+    return dict(knots=[(0, start), (n_steps, 1.0)], period=None)
+
+
+def cyclical(period, ramp=0.5, start=0.0):
+    """Cyclical annealing: every ``period`` steps the multiplier rises linearly from ``start`` to 1 over the first ``ramp``
+    fraction of the cycle and stays at 1 for the rest.  (In steps, ``period * ramp`` must be a whole number; in epochs --
+    ``train(schedule=dict(..., unit='epoch'))`` -- it must come to whole steps.)"""
+    up = period * ramp
+    if not 0 < up < period:
+        raise ValueError("cyclical: ramp must be in (0, 1) and period positive, got ramp %r, period %r" % (ramp, period))
+    if float(up) == int(up):
+        up = int(up)
+    return dict(knots=[(0, start), (up, 1.0)], period=period)
+
+
+def exponential_decay(rate, steps, staircase=False):
+    """Multiplier ``rate ** (step / steps)`` (``rate ** (step // steps)`` with ``staircase``): tf.train.exponential_decay."""
+    return dict(decay_rate=rate, decay_steps=steps, staircase=bool(staircase))
+
+
 def dev_row_args(X, widths, device, present=None):
     """Arguments of the row calls (any row count) -> (tensors, N, was_numpy, ptrs, lds, presence or None).  Unmasked, the first
     modality gives N.  Masked, ``present`` [N, M] does, ``X[m] = None`` is a modality absent on every row, and was_numpy is

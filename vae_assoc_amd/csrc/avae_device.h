@@ -4,7 +4,9 @@
 // changes after avae_create, which is what lets the whole step be captured once as a hipGraph.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
+#include "../../include/avae.h"
 
 namespace avae {
 
@@ -113,6 +115,9 @@ struct WorkItem {
     // K_LATENT reuses the pointer fields: [mu|lv] inputs of modality 0..3 = A, B, aux0, aux1;
     // static-gradient outputs g0 of modality 0..3 = out0, out1, out2, aux2.
     // K_COST: scale = lr, lambda = beta1, inv_bg = beta2 (it also publishes this step's Adam lr_t).
+    // K_LATENT / K_COST of a training step with a schedule set (avae_set_schedule): tail_w = the step's HyperEntry (below), which
+    // replaces lambda and scales the KL weight (K_LATENT) / replaces scale = lr (K_COST).  Null otherwise, and in every evaluation
+    // and inference launch: the by-value constants above are then all the item reads.
 };
 
 // One launch = up to kMaxItemsPerLaunch work items, passed BY VALUE in the kernel-argument
@@ -217,6 +222,45 @@ struct ClipState {
     float norm_hist[kCostHist];        // raw gradient norm of every step, indexed like DevState::cost_hist
 };
 
+// Training schedules (include/avae.h, avae_set_schedule): a first-use allocation of its own.  The staging launch of a training
+// submission evaluates the three schedules for each of its batches (step number = DevState::step + 1 + the batch's index) and
+// writes entry j of `tab` -- read by the latent and cost items of the step on staging set j -- and the history ring.  The schedules
+// themselves are read by that launch, so changing their values re-captures no graph.
+struct HyperEntry { float kl, lambda, lr, pad; };      // kl_t, lambda_t = fl32(assoc_lambda * a_t), lr_eff_t = fl32(learning_rate * l_t)
+constexpr int kHyperSets = 16;         // = the staging sets (kMultiSteps in avae_host.hip)
+struct SchedState {
+    avae_schedule sched[3];            // kl, assoc, lr
+    float lambda0, lr0;                // cfg.assoc_lambda, cfg.learning_rate
+    HyperEntry tab[kHyperSets];
+    float hist[kCostHist][3];          // {kl_t, lambda_t, lr_eff_t} of every step, indexed like DevState::cost_hist
+};
+
+// Multiplier of schedule s at step number t (the number the update gets: 1 for the first step; u = t - 1 counts the steps before
+// it) -- the ONE evaluator, used by avae_schedule_value on the host and by the staging kernel on the device.  The piecewise value is
+// IEEE double arithmetic without contraction, rounded once: host and device agree in every bit.  EXP goes through pow(double).
+// `s` has passed check_schedule (avae_host.hip).
+__host__ __device__ inline float schedule_value(const avae_schedule& s, long long t) {
+#pragma clang fp contract(off)
+    long long u = t - 1;
+    if (u < 0) u = 0;
+    if (s.kind == AVAE_SCHED_PIECEWISE) {
+        if (s.period > 0) u %= s.period;
+        const int last = s.n_knots - 1;
+        if (u <= s.knot_step[0]) return s.knot_value[0];
+        if (u >= s.knot_step[last]) return s.knot_value[last];
+        int i = 0;
+        while (i + 1 < last && u >= s.knot_step[i + 1]) ++i;
+        const double v0 = (double)s.knot_value[i], v1 = (double)s.knot_value[i + 1];
+        const double f = (double)(u - s.knot_step[i]) / (double)(s.knot_step[i + 1] - s.knot_step[i]);
+        return (float)(v0 + (v1 - v0) * f);
+    }
+    if (s.kind == AVAE_SCHED_EXP) {
+        const double e = s.staircase ? (double)(u / s.decay_steps) : (double)u / (double)s.decay_steps;
+        return (float)pow((double)s.decay_rate, e);
+    }
+    return 1.0f;
+}
+
 // One dense layer's optimiser tile table entry (Adam + compute-dtype shadow refresh).
 struct AdamItem {
     float* theta;
@@ -289,6 +333,8 @@ struct PrepArgs {
     unsigned char* pres_dst;
     int pres_ld;
     int noisy;                     // some segment has a second source or a corruption: the NOISY instances (else the two above, unchanged)
+    SchedState* sched;             // training staging with a schedule set (the SCHED instances; null: the instances above, unchanged):
+                                   // thread 0 of batch j's first block writes tab[j] and the history entry of step st->step + 1 + j
 };
 
 // Fixed-order sum of the split-K slices of a weight gradient: dst[i] = sum_s src[s*stride + i]  (no atomics: reproducible).
@@ -560,7 +606,7 @@ void launch_grouped_tn(int compute_dtype, int tile_cfg, const TnLaunchArgs& args
 void launch_adam(int compute_dtype, const AdamArgs& a, int n_blocks, hipStream_t s);      // a.clip != null: the clip-aware instance
 void launch_grad_sumsq(const float* g, long long p_int, float* partial, hipStream_t s);
 void launch_prep(int compute_dtype, const PrepArgs& a, hipStream_t s);
-const void* prep_kernel(int compute_dtype, bool masked, bool noisy);   // for hipGraphExecKernelNodeSetParams on the captured staging node
+const void* prep_kernel(int compute_dtype, bool masked, bool noisy, bool sched);   // for hipGraphExecKernelNodeSetParams on the captured staging node
 void launch_fill(void* base, int elem_bytes, unsigned bits, long long start, long long stride, int count, hipStream_t s);
 void launch_sums(const ReduceArgs& a, int n_blocks, hipStream_t s);
 int small_head_lds_bytes();

@@ -59,6 +59,8 @@ struct DeviceGuard {
         if (e_ != hipSuccess) throw Err(std::string("launch of ") + (what) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
+constexpr unsigned long long kTrainSalt = 0x7261696eull;      // "rain": the eps stream of the training calls (PrepArgs::stream_salt)
+static_assert(kHyperSets == 16, "one schedule table entry per staging set");
 constexpr int kMultiSteps = 16;         // most whole steps per replay of a multi-step graph (avae_train_steps) = staging sets
 constexpr int kMultiSizes[2] = {16, 4};  // captured replay lengths: a run of n batches goes 16,16,...,4,4,...,1,1
 
@@ -300,6 +302,14 @@ struct avae_handle {
     bool clip_on = false;
     DevBuf clip_buf;
     long long clip_steps = 0;               // steps submitted since clipping was last switched on (bounds avae_grad_norm_history)
+
+    // avae_set_schedule: KL / association / learning-rate schedules.  sched_on: the training staging launches run their SCHED
+    // instance (it fills the step table and the history ring of sched_buf, a SchedState allocated by the first call that switches a
+    // schedule on) and the latent and cost items of every training launch carry a pointer to their step's table entry.  The plans'
+    // launch tables stay unscheduled -- evaluation and inference run them as they are; run_set patches copies for the training routes.
+    bool sched_on = false;
+    DevBuf sched_buf;
+    long long sched_steps = 0;              // steps submitted since a schedule was last switched on (bounds avae_hyper_history)
 
     // avae_complete: the launches of one refinement pass (decoders forward, then their input-gradient chain from the training plan's
     // item builders on the same buffers), captured as runs of kCompleteSizes[i] passes; the kernels' arguments; the scratch behind
@@ -2052,8 +2062,9 @@ template <typename F> void timed_launch(avae_handle* h, hipStream_t s, const cha
     LAUNCH_OK(name);
 }
 
-// The same launch reading staging set j instead of set 0: every pointer into set 0 moves by j * stage_bytes.
-Launch relocated(const avae_handle* h, const Launch& L0, int j) {
+// The same launch reading staging set j instead of set 0: every pointer into set 0 moves by j * stage_bytes.  hyper (a scheduled
+// training step): its latent and cost items read entry j of the schedule table.
+Launch relocated(const avae_handle* h, const Launch& L0, int j, const HyperEntry* hyper = nullptr) {
     Launch L = L0;
     const unsigned char* lo = h->ws + h->stage_lo;
     const unsigned char* hi = lo + h->stage_bytes;
@@ -2067,6 +2078,7 @@ Launch relocated(const avae_handle* h, const Launch& L0, int j) {
         fix(w.A); fix(w.B); fix(w.out0); fix(w.out1); fix(w.out2); fix(w.aux0); fix(w.aux1); fix(w.aux2); fix(w.eps);
         fix(w.tail_w); fix(w.tail_out); fix(w.tail_aux);
         if (w.present) w.present += (size_t)j * h->pres_set;          // masked twin: presence set j (its own allocation)
+        if (hyper && (w.kind == K_LATENT || (w.kind == K_COST && w.bump_step))) w.tail_w = hyper + j;
     }
     for (int i = 0; i < L.targs.n_items && L.type == 0; ++i) { TnItem& t = L.targs.items[i]; fix(t.A); fix(t.B); fix(t.out); }
     for (int i = 0; i < L.ga.n_seg && L.type == 1; ++i) fix(L.ga.seg[i].src);
@@ -2110,17 +2122,30 @@ void run_launch(avae_handle* h, const Launch& L, hipStream_t s, unsigned long lo
     }
 }
 
+bool has_hyper_item(const Launch& L) {
+    for (int i = 0; i < L.args.n_items && L.type == 0; ++i)
+        if (L.args.items[i].kind == K_LATENT || (L.args.items[i].kind == K_COST && L.args.items[i].bump_step)) return true;
+    return false;
+}
+
 // Launches [lo, hi) of ls on staging set j: set 0 runs ls itself, set j > 0 relocated copies.  stamp_base >= 0 (AVAE_STAMPS builds):
-// the launches write their clock stamps from slot stamp_base on.
-void run_set(avae_handle* h, const std::vector<Launch>& ls, size_t lo, size_t hi, int j, hipStream_t s, int stamp_base = -1) {
+// the launches write their clock stamps from slot stamp_base on.  train: a training step -- with a schedule set its latent and cost
+// launches are copies that point at the step's schedule entry (every other caller runs the tables as they are: multipliers 1).
+void run_set(avae_handle* h, const std::vector<Launch>& ls, size_t lo, size_t hi, int j, hipStream_t s, int stamp_base = -1, bool train = false) {
     unsigned long long* stamps = nullptr;
 #ifdef AVAE_STAMPS
     if (stamp_base >= 0) stamps = h->at<unsigned long long>(h->off_stamps);
 #endif
+    const HyperEntry* hyper = nullptr;
+    if (train && h->sched_on) {
+        if (!h->sched_buf.p) throw Err("internal error: a schedule is on without its device state");
+        if (j < 0 || j >= kHyperSets) throw Err("internal error: staging set outside the schedule table");
+        hyper = h->sched_buf.as<SchedState>()->tab;
+    }
     for (size_t i = lo; i < hi && i < ls.size(); ++i) {
         const int k = stamp_base + (int)(i - lo);
-        if (j == 0) run_launch(h, ls[i], s, stamps, k);
-        else run_launch(h, relocated(h, ls[i], j), s, stamps, k);
+        if (j == 0 && !(hyper && has_hyper_item(ls[i]))) run_launch(h, ls[i], s, stamps, k);
+        else run_launch(h, relocated(h, ls[i], j, hyper), s, stamps, k);
     }
 }
 
@@ -2212,6 +2237,7 @@ PrepArgs make_prep_batch(avae_handle* h, const float* const* x, const int32_t* x
     fill_prep_eps(h, a, eps, rows);
     a.n_steps = n_steps; a.blocks_per_step = a.total_tiles + a.eps_blocks; a.set_stride = (long long)h->stage_bytes;
     if (present) { a.pres_src = present; a.pres_dst = h->pres_buf.as<unsigned char>(); a.pres_ld = h->M; }      // masked staging (set j at j * rows * M)
+    if (h->sched_on && salt == kTrainSalt) a.sched = h->sched_buf.as<SchedState>();      // training staging: this submission's schedule entries
     return a;
 }
 
@@ -2281,11 +2307,11 @@ StepGraph capture(avae_handle* h, const std::function<void(hipStream_t)>& body, 
 // Points a step graph's staging node at the caller's batch (or run of n_steps consecutive batches).
 void patch_prep(avae_handle* h, const StepGraph& sg, const float* const* x, const int32_t* x_ld, const float* eps,
                 int n_steps, const uint8_t* present, const PrepIn& pin) {
-    PrepArgs a = make_prep_batch(h, x, x_ld, eps, h->B, 0x7261696eull, n_steps, present, pin);
+    PrepArgs a = make_prep_batch(h, x, x_ld, eps, h->B, kTrainSalt, n_steps, present, pin);
     void* kp[1] = {&a};
     hipKernelNodeParams np;
     std::memset(&np, 0, sizeof(np));
-    np.func = const_cast<void*>(prep_kernel(h->cfg.compute_dtype, present != nullptr, a.noisy != 0));
+    np.func = const_cast<void*>(prep_kernel(h->cfg.compute_dtype, present != nullptr, a.noisy != 0, a.sched != nullptr));
     np.gridDim = dim3((a.total_tiles + a.eps_blocks) * n_steps); np.blockDim = dim3(kThreads);
     np.sharedMemBytes = 0; np.kernelParams = kp; np.extra = nullptr;
     HIP_OK(hipGraphExecKernelNodeSetParams(sg.exec, sg.prep, &np));
@@ -2302,13 +2328,13 @@ void fill_ones(avae_handle* h, const Act& a, hipStream_t s) {
 // epilogue, or followed by k_adam; with clipping on always weight gradients -> k_grad_sumsq -> k_adam.
 void step_body(avae_handle* h, const std::vector<Launch>& fwd, hipStream_t s, int j, int stamp_base = -1) {
     auto sb = [&](size_t k) { return stamp_base < 0 ? -1 : stamp_base + (int)k; };
-    run_set(h, fwd, 0, fwd.size(), j, s, stamp_base);
-    run_set(h, h->bwd, 0, h->bwd.size(), j, s, sb(fwd.size()));
+    run_set(h, fwd, 0, fwd.size(), j, s, stamp_base, true);
+    run_set(h, h->bwd, 0, h->bwd.size(), j, s, sb(fwd.size()), true);
     if (!h->wgrad_adam.empty() && !h->clip_on) {       // the optimiser rides in the weight-gradient launch
-        run_set(h, h->wgrad_adam, 0, h->wgrad_adam.size(), j, s, sb(fwd.size() + h->bwd.size()));
+        run_set(h, h->wgrad_adam, 0, h->wgrad_adam.size(), j, s, sb(fwd.size() + h->bwd.size()), true);
         return;
     }
-    run_set(h, h->wgrad, 0, h->wgrad.size(), j, s, sb(fwd.size() + h->bwd.size()));
+    run_set(h, h->wgrad, 0, h->wgrad.size(), j, s, sb(fwd.size() + h->bwd.size()), true);
     if (h->clip_on) run_grad_sumsq(h, s);
     run_adam(h, 0, s);
 }
@@ -2320,13 +2346,13 @@ void capture_steps(avae_handle* h, StepPlan& p, const uint8_t* present) {
     std::vector<const float*> x0(h->M, h->at<float>(h->mods[0].X32));    // placeholders, patched per step
     try {
         p.full = capture(h, [&](hipStream_t cs) {
-            run_prep_batch(h, x0.data(), nullptr, nullptr, h->B, 0x7261696eull, cs, present);
+            run_prep_batch(h, x0.data(), nullptr, nullptr, h->B, kTrainSalt, cs, present);
             step_body(h, p.fwd, cs, 0, 0);
         }, true);
         // avae_train_steps: kMultiSizes[gi] whole steps per replay (a replay boundary costs ~5 us of idle GPU on this stack), their
         // batches staged by ONE launch into as many staging sets; step j's launches read set j
         for (int gi = 0; gi < 2; ++gi) p.multi[gi] = capture(h, [&](hipStream_t cs) {
-            run_prep_batch(h, x0.data(), nullptr, nullptr, h->B, 0x7261696eull, cs, present, kMultiSizes[gi]);
+            run_prep_batch(h, x0.data(), nullptr, nullptr, h->B, kTrainSalt, cs, present, kMultiSizes[gi]);
             for (int j = 0; j < kMultiSizes[gi]; ++j) step_body(h, p.fwd, cs, j);
         }, true);
     } catch (...) { p.full.release(); p.multi[0].release(); p.multi[1].release(); throw; }
@@ -2404,6 +2430,49 @@ hipStream_t on_stream(avae_handle* h, void* stream) {
     }
     h->last_stream = s; h->has_last_stream = true;
     return s;
+}
+
+// avae_set_schedule / avae_schedule_value: the ranges of include/avae.h; `who` names the call and the schedule, the message the field.
+void check_schedule(const avae_schedule& c, const std::string& who) {
+    auto fail = [&](const std::string& what) { throw Err(who + ": " + what); };
+    if (c.kind == AVAE_SCHED_NONE) return;
+    if (c.kind == AVAE_SCHED_PIECEWISE) {
+        if (c.n_knots < 1 || c.n_knots > AVAE_SCHED_MAX_KNOTS)
+            fail("n_knots = " + std::to_string(c.n_knots) + " must be in [1, " + std::to_string(AVAE_SCHED_MAX_KNOTS) + "]");
+        if (c.period < 0) fail("period = " + std::to_string((long long)c.period) + " must be >= 0");
+        for (int i = 0; i < c.n_knots; ++i) {
+            if (i == 0 ? c.knot_step[0] < 0 : c.knot_step[i] <= c.knot_step[i - 1])
+                fail("knot_step[" + std::to_string(i) + "] = " + std::to_string((long long)c.knot_step[i]) +
+                     (i == 0 ? " must be >= 0" : " must be above knot_step[" + std::to_string(i - 1) + "] (strictly increasing)"));
+            if (!(c.knot_value[i] >= 0.0f) || std::isinf(c.knot_value[i]))
+                fail("knot_value[" + std::to_string(i) + "] must be finite and >= 0");
+        }
+        if (c.period > 0 && c.knot_step[c.n_knots - 1] >= c.period)
+            fail("knot_step[" + std::to_string(c.n_knots - 1) + "] = " + std::to_string((long long)c.knot_step[c.n_knots - 1]) +
+                 " must be below period = " + std::to_string((long long)c.period));
+        return;
+    }
+    if (c.kind == AVAE_SCHED_EXP) {
+        if (!(c.decay_rate > 0.0f) || std::isinf(c.decay_rate)) fail("decay_rate must be finite and > 0");
+        if (c.decay_steps <= 0) fail("decay_steps = " + std::to_string((long long)c.decay_steps) + " must be > 0");
+        if (c.staircase != 0 && c.staircase != 1) fail("staircase must be 0 or 1");
+        return;
+    }
+    fail("kind = " + std::to_string(c.kind) + " is none of AVAE_SCHED_NONE, AVAE_SCHED_PIECEWISE, AVAE_SCHED_EXP");
+}
+
+// A checked schedule with the fields its kind does not read zeroed (what the device keeps).
+avae_schedule canonical_schedule(const avae_schedule& c) {
+    avae_schedule o;
+    std::memset(&o, 0, sizeof(o));
+    o.kind = c.kind;
+    if (c.kind == AVAE_SCHED_PIECEWISE) {
+        o.n_knots = c.n_knots; o.period = c.period;
+        for (int i = 0; i < c.n_knots; ++i) { o.knot_step[i] = c.knot_step[i]; o.knot_value[i] = c.knot_value[i]; }
+    } else if (c.kind == AVAE_SCHED_EXP) {
+        o.decay_rate = c.decay_rate; o.staircase = c.staircase; o.decay_steps = c.decay_steps;
+    }
+    return o;
 }
 
 template <typename F> int guarded(avae_handle* h, F&& f) {
@@ -2585,7 +2654,7 @@ void dp_segment(avae_handle* h, int j, int bucket, hipStream_t s, bool direct = 
     if (bucket < 0 || bucket >= h->n_buckets) throw Err("data-parallel bucket out of range");
     if (j < 0 || j >= kMultiSteps) throw Err("staging set out of range");
     auto body = [&](hipStream_t cs) {
-        auto run = [&](const std::vector<Launch>& ls, size_t lo, size_t hi) { run_set(h, ls, lo, hi, j, cs); };
+        auto run = [&](const std::vector<Launch>& ls, size_t lo, size_t hi) { run_set(h, ls, lo, hi, j, cs, -1, true); };
         if (h->n_buckets == 1) { run(h->plain.fwd, 0, h->plain.fwd.size()); run(h->bwd, 0, h->bwd.size()); run(h->wgrad, 0, h->wgrad.size()); return; }
         if (bucket == 0) { run(h->plain.fwd, 0, h->plain.fwd.size()); run(h->bwd, 0, (size_t)h->bwd_split); run(h->wgrad_b[0], 0, h->wgrad_b[0].size()); }
         else { run(h->bwd, (size_t)h->bwd_split, h->bwd.size()); run(h->wgrad_b[1], 0, h->wgrad_b[1].size()); }
@@ -3053,7 +3122,7 @@ void check_inputs(avae_handle* h, const char* what, const float* const* x_dev, c
 void train_one(avae_handle* h, StepPlan& p, const float* const* x_dev, const int32_t* x_ld, const uint8_t* present, const float* eps_dev,
                const PrepIn& pin, hipStream_t s) {
     if (h->comm_on) {
-        run_prep_batch(h, x_dev, x_ld, eps_dev, h->B, 0x7261696eull, s, nullptr, 1, pin);
+        run_prep_batch(h, x_dev, x_ld, eps_dev, h->B, kTrainSalt, s, nullptr, 1, pin);
         dp_step(h, 0, s);
         return;
     }
@@ -3062,7 +3131,7 @@ void train_one(avae_handle* h, StepPlan& p, const float* const* x_dev, const int
         HIP_OK(hipGraphLaunch(p.full.exec, s));
         return;
     }
-    run_prep_batch(h, x_dev, x_ld, eps_dev, h->B, 0x7261696eull, s, present, 1, pin);
+    run_prep_batch(h, x_dev, x_ld, eps_dev, h->B, kTrainSalt, s, present, 1, pin);
     step_body(h, p.fwd, s, 0);
     if (h->timing) {      // floor of the measurement: a one-store kernel (partial slot 0 is rewritten every step anyway)
         timed_launch(h, s, "_null_kernel", [&] { launch_fill(h->at<void>(h->off_partial), 4, 0u, 0, 1, 1, s); });
@@ -3125,7 +3194,7 @@ void train_steps(avae_handle* h, StepPlan& p, int n_steps, const float* const* x
                 std::vector<const float*> x0(h->M, h->at<float>(h->mods[0].X32));
                 try {
                     h->g_dpm[gi] = capture(h, [&](hipStream_t cs) {
-                        run_prep_batch(h, x0.data(), nullptr, nullptr, h->B, 0x7261696eull, cs, nullptr, kMultiSizes[gi]);
+                        run_prep_batch(h, x0.data(), nullptr, nullptr, h->B, kTrainSalt, cs, nullptr, kMultiSizes[gi]);
                         for (int j = 0; j < kMultiSizes[gi]; ++j) dp_step(h, j, cs, true);
                     }, true);
                 } catch (const std::exception& e) {
@@ -3139,7 +3208,7 @@ void train_steps(avae_handle* h, StepPlan& p, int n_steps, const float* const* x
         for (; i < n_steps; i += kMultiSteps) {
             const int n = std::min(kMultiSteps, n_steps - i);
             b.at(i);
-            run_prep_batch(h, b.x, x_ld, b.eps, h->B, 0x7261696eull, s, nullptr, n, b.pin());
+            run_prep_batch(h, b.x, x_ld, b.eps, h->B, kTrainSalt, s, nullptr, n, b.pin());
             for (int j = 0; j < n; ++j) dp_step(h, j, s);
         }
     } else {
@@ -3150,6 +3219,7 @@ void train_steps(avae_handle* h, StepPlan& p, int n_steps, const float* const* x
         }
     }
     if (h->clip_on) h->clip_steps += n_steps;
+    if (h->sched_on) h->sched_steps += n_steps;
     fetch_cost(h, cost_host, true, s);
 }
 
@@ -3304,7 +3374,7 @@ int avae_stage_batches_in(avae_handle* h, int32_t n_steps, const float* const* x
     return guarded(h, [&] {
         if (n_steps < 1 || n_steps > kMultiSteps) throw Err("avae_stage_batches: n_steps must be in [1," + std::to_string(kMultiSteps) + "]");
         check_inputs(h, "avae_stage_batches_in", x_dev, in_dev, in_ld);
-        run_prep_batch(h, x_dev, x_ld, eps_dev, h->B, 0x7261696eull, on_stream(h, stream), nullptr, n_steps, PrepIn{in_dev, in_ld, true});
+        run_prep_batch(h, x_dev, x_ld, eps_dev, h->B, kTrainSalt, on_stream(h, stream), nullptr, n_steps, PrepIn{in_dev, in_ld, true});
     });
 }
 
@@ -3317,6 +3387,7 @@ int avae_train_step(avae_handle* h, const float* const* x_dev, const int32_t* x_
         hipStream_t s = on_stream(h, stream);
         train_one(h, h->plain, x_dev, x_ld, nullptr, eps_dev, PrepIn{nullptr, nullptr, true}, s);
         if (h->clip_on) ++h->clip_steps;
+        if (h->sched_on) ++h->sched_steps;
         fetch_cost(h, cost_host, true, s);
     });
 }
@@ -3411,6 +3482,79 @@ int avae_grad_norm_history(avae_handle* h, int32_t n, float* host_norms, int64_t
     });
 }
 
+int avae_set_schedule(avae_handle* h, const avae_schedule* kl, const avae_schedule* assoc, const avae_schedule* lr) {
+    return guarded(h, [&] {
+        const avae_schedule* in[3] = {kl, assoc, lr};
+        static const char* const names[3] = {"kl", "assoc", "lr"};
+        avae_schedule sc[3];
+        bool on = false;
+        for (int q = 0; q < 3; ++q) {
+            std::memset(&sc[q], 0, sizeof(sc[q]));
+            if (!in[q] || in[q]->kind == AVAE_SCHED_NONE) continue;
+            check_schedule(*in[q], std::string("avae_set_schedule: ") + names[q]);
+            sc[q] = canonical_schedule(*in[q]);
+            on = true;
+        }
+        HIP_OK(hipDeviceSynchronize());             // a rare call: enqueued work keeps the schedules it was enqueued with
+        if (!on && !h->sched_buf.p) return;         // never switched on
+        SchedState* ss = static_cast<SchedState*>(h->sched_buf.ensure(sizeof(SchedState), true));
+        static_assert(offsetof(SchedState, sched) == 0 && offsetof(SchedState, lambda0) == sizeof(sc) &&
+                      offsetof(SchedState, lr0) == sizeof(sc) + sizeof(float), "the settings lead the device state");
+        struct { avae_schedule sc[3]; float lambda0, lr0; } v;
+        std::memcpy(v.sc, sc, sizeof(sc));
+        v.lambda0 = h->cfg.assoc_lambda; v.lr0 = h->cfg.learning_rate;
+        HIP_OK(hipMemcpy(ss, &v, sizeof(sc) + 2 * sizeof(float), hipMemcpyHostToDevice));
+        // new schedules only: the staging launch reads them from the device (unless an earlier capture failed and left the plan without graphs)
+        if (on == h->sched_on && (!h->cfg.use_graph || h->plain.full.exec)) return;
+        // on <-> off: the staging instance and the latent / cost items' arguments change, so every graph that holds a training launch
+        // goes (the evaluation graphs hold neither and stay); the data-parallel graphs are captured again by their next use
+        h->plain.full.release(); h->plain.multi[0].release(); h->plain.multi[1].release();
+        h->masked.full.release(); h->masked.multi[0].release(); h->masked.multi[1].release();
+        for (StepGraph& g : h->g_dpm) g.release();
+        for (std::vector<StepGraph>& gv : h->g_dp) for (StepGraph& g : gv) g.release();
+        h->sched_on = on;
+        if (on) h->sched_steps = 0;
+        if (h->cfg.use_graph) {
+            capture_steps(h, h->plain, nullptr);
+            if (!h->masked.fwd.empty()) capture_steps(h, h->masked, h->pres_buf.as<unsigned char>());
+        }
+    });
+}
+
+int avae_schedule_value(const avae_schedule* schedule, int64_t step, float* out) {
+    try {
+        if (!out) throw Err("avae_schedule_value: null out");
+        if (step < 1) throw Err("avae_schedule_value: step must be >= 1 (the number the first update gets)");
+        if (!schedule || schedule->kind == AVAE_SCHED_NONE) { *out = 1.0f; return 0; }
+        check_schedule(*schedule, "avae_schedule_value: schedule");
+        *out = schedule_value(canonical_schedule(*schedule), (long long)step);
+        return 0;
+    } catch (const std::exception& e) { g_create_error = e.what(); return 2; }
+}
+
+int avae_hyper_history(avae_handle* h, int32_t n, float* host_dst, int64_t* last_step) {
+    return guarded(h, [&] {
+        if (n < 0 || n > kCostHist) throw Err("avae_hyper_history: n must be in [0, " + std::to_string(kCostHist) + "]");
+        if (n > 0 && !host_dst) throw Err("avae_hyper_history: null host_dst");
+        const long long have = h->sched_on ? h->sched_steps : 0;
+        if ((long long)n > have)
+            throw Err("avae_hyper_history: " + std::to_string(n) + " steps asked for, " + std::to_string(have) +
+                      " steps submitted since a schedule was switched on");
+        HIP_OK(hipDeviceSynchronize());
+        comm_check_error(h);
+        long long step = 0;
+        HIP_OK(hipMemcpy(&step, &h->state()->step, sizeof(step), hipMemcpyDeviceToHost));
+        if (n > 0) {
+            if (step < n) throw Err("avae_hyper_history: fewer steps applied than requested");
+            std::vector<float> ring((size_t)kCostHist * 3);
+            HIP_OK(hipMemcpy(ring.data(), reinterpret_cast<const unsigned char*>(h->sched_buf.p) + offsetof(SchedState, hist),
+                             ring.size() * sizeof(float), hipMemcpyDeviceToHost));
+            for (int i = 0; i < n; ++i) std::memcpy(host_dst + 3 * (size_t)i, &ring[3 * (size_t)((step - n + i) % kCostHist)], 3 * sizeof(float));
+        }
+        if (last_step) *last_step = step;
+    });
+}
+
 int avae_train_steps_masked(avae_handle* h, int32_t n_steps, const float* const* x_dev, const int32_t* x_ld, const uint8_t* present_dev,
                             const float* eps_dev, float* cost_host, void* stream) {
     return guarded(h, [&] {
@@ -3476,6 +3620,7 @@ int avae_dp_apply(avae_handle* h, int32_t bucket, float* cost_host, void* stream
         if (bucket < 0 || bucket >= h->n_buckets) throw Err("data-parallel bucket out of range");
         hipStream_t s = on_stream(h, stream);
         if (h->clip_on && bucket == 0) { run_grad_sumsq(h, s); ++h->clip_steps; }      // over the whole buffer: both all-reduces come before apply(0); apply(1) reuses the partials
+        if (h->sched_on && bucket == 0) ++h->sched_steps;
         run_adam(h, 0, s, h->n_buckets == 1 ? -1 : bucket);
         fetch_cost(h, cost_host, true, s);
     });

@@ -359,6 +359,10 @@ template <int NW, bool MASK> __device__ __forceinline__ void latent_item(const W
     float* g0[kMaxMod] = {reinterpret_cast<float*>(w.out0), reinterpret_cast<float*>(w.out1),
                           reinterpret_cast<float*>(w.out2), reinterpret_cast<float*>(const_cast<void*>(w.aux2))};
     const int nz = w.nz, nz2 = 2 * w.nz, M = w.M;
+    // a scheduled training step (WorkItem::tail_w = the step's HyperEntry, written by this submission's staging launch): kl_t scales
+    // the KL weight by a multiplication -- never a select -- and lambda_t stands in for the configured lambda
+    const HyperEntry* hy = reinterpret_cast<const HyperEntry*>(w.tail_w);
+    const float kl_t = hy ? hy->kl : 1.0f, lambda = hy ? hy->lambda : w.lambda;
     float csum = 0.0f;
     for (int idx = threadIdx.x; idx < kLatentRows * nz; idx += kThreads) {
         const int row = idx / nz, d = idx - row * nz;
@@ -382,7 +386,7 @@ template <int NW, bool MASK> __device__ __forceinline__ void latent_item(const W
             if (m < w.n_mod) {
                 const float el = fexp(lv[m]);
                 en[m] = frcp(el);                                   // e^-lv
-                const float s = w.wts[m] * w.inv_bg;
+                const float s = hy ? (w.wts[m] * w.inv_bg) * kl_t : w.wts[m] * w.inv_bg;
                 const float c1 = csum + s * (-0.5f * (1.0f + lv[m] - mu[m] * mu[m] - el));
                 csum = pm[m] ? c1 : csum;
                 gmu[m] = pm[m] ? s * mu[m] : 0.0f;
@@ -398,13 +402,13 @@ template <int NW, bool MASK> __device__ __forceinline__ void latent_item(const W
                     const float a = lv[i] - lv[j], dl = mu[i] - mu[j];
                     const float sh = two_sinh(0.5f * a);             // e^(a/2) - e^(-a/2)
                     const float dsh = two_sinh(a);                   // e^a - e^-a
-                    const float c1 = csum + w.lambda * 0.5f * (sh * sh + dl * dl * (en[i] + en[j]));
+                    const float c1 = csum + lambda * 0.5f * (sh * sh + dl * dl * (en[i] + en[j]));
                     csum = pp ? c1 : csum;
-                    const float gm = w.lambda * dl * (en[i] + en[j]);
+                    const float gm = lambda * dl * (en[i] + en[j]);
                     const float gmi = gmu[i] + gm, gmj = gmu[j] - gm;
                     gmu[i] = pp ? gmi : gmu[i]; gmu[j] = pp ? gmj : gmu[j];
-                    const float gli = glv[i] + 0.5f * w.lambda * (dsh - dl * dl * en[i]);
-                    const float glj = glv[j] + 0.5f * w.lambda * (-dsh - dl * dl * en[j]);
+                    const float gli = glv[i] + 0.5f * lambda * (dsh - dl * dl * en[i]);
+                    const float glj = glv[j] + 0.5f * lambda * (-dsh - dl * dl * en[j]);
                     glv[i] = pp ? gli : glv[i]; glv[j] = pp ? glj : glv[j];
                 }
             }
@@ -435,7 +439,9 @@ template <int NW = 4> __device__ __forceinline__ void cost_item(const WorkItem& 
             st->step = tnew;
             // TF-1 Adam: lr_t = lr*sqrt(1-b2^t)/(1-b1^t), published for the Adam kernel of this step
             const double b1t = pow((double)w.lambda, (double)tnew), b2t = pow((double)w.inv_bg, (double)tnew);
-            st->lr_t = (float)((double)w.scale * sqrt(1.0 - b2t) / (1.0 - b1t));
+            const HyperEntry* hy = reinterpret_cast<const HyperEntry*>(w.tail_w);      // a scheduled step: lr_eff_t of step tnew
+            const float lr = hy ? hy->lr : w.scale;
+            st->lr_t = (float)((double)lr * sqrt(1.0 - b2t) / (1.0 - b1t));
             st->last_cost = total;                                   // local cost; the multi-replica path
             st->cost_hist[(tnew - 1) % kCostHist] = total;           // overwrites it with the all-reduced one
         }
@@ -2648,14 +2654,30 @@ __device__ __forceinline__ void noisy_quad(const PrepArgs& a, const PrepSeg& w, 
     }
 }
 
+// Training schedules (PrepArgs::sched): the multipliers of step number t, the one batch bstep of this submission belongs to, into
+// entry bstep of the table its latent and cost items read and into the history ring.  One thread per batch; plain stores.
+__device__ __noinline__ void publish_hyper(SchedState* sc, long long t, int bstep) {
+    HyperEntry e;
+    e.kl = schedule_value(sc->sched[0], t);
+    e.lambda = sc->lambda0 * schedule_value(sc->sched[1], t);
+    e.lr = sc->lr0 * schedule_value(sc->sched[2], t);
+    e.pad = 0.0f;
+    sc->tab[bstep] = e;
+    float* hrow = sc->hist[(t - 1) % kCostHist];
+    hrow[0] = e.kl; hrow[1] = e.lambda; hrow[2] = e.lr;
+}
+
 // MASK: the masked staging (PrepArgs::pres_src set); NOISY: the denoising staging (PrepArgs::noisy: the encoder's input and the
-// loss target differ).  launch_prep / prep_kernel pick the instance.
-template <typename CT, bool MASK, bool NOISY = false>
+// loss target differ); SCHED: training staging with a schedule set (PrepArgs::sched).  launch_prep / prep_kernel pick the instance.
+template <typename CT, bool MASK, bool NOISY = false, bool SCHED = false>
 __global__ void __launch_bounds__(kThreads) k_prep(PrepArgs a) {
     const int tid = threadIdx.x;
     const int bstep = a.n_steps > 1 ? (int)blockIdx.x / a.blocks_per_step : 0;     // which of the batched steps
     const int bid = (int)blockIdx.x - bstep * a.blocks_per_step;
     const size_t set_off = (size_t)bstep * (size_t)a.set_stride;                      // bytes to that step's staging set
+    if constexpr (SCHED) {
+        if (bid == 0 && tid == 0 && bstep < kHyperSets) publish_hyper(a.sched, a.st->step + 1 + (long long)bstep, bstep);
+    }
     if (bid >= a.total_tiles) {
         // eps: one quad of dims per thread
         if (!a.eps_dst) return;
@@ -2751,16 +2773,30 @@ __global__ void __launch_bounds__(kThreads) k_prep(PrepArgs a) {
     }
 }
 
-template <typename CT> const void* prep_instance(bool masked, bool noisy) {
+template <typename CT, bool SCHED> const void* prep_instance_sched(bool masked, bool noisy) {
+    if (noisy) return masked ? reinterpret_cast<const void*>(k_prep<CT, true, true, SCHED>) : reinterpret_cast<const void*>(k_prep<CT, false, true, SCHED>);
+    return masked ? reinterpret_cast<const void*>(k_prep<CT, true, false, SCHED>) : reinterpret_cast<const void*>(k_prep<CT, false, false, SCHED>);
+}
+
+template <typename CT> const void* prep_instance(bool masked, bool noisy, bool sched) {
+    if (sched) return prep_instance_sched<CT, true>(masked, noisy);
     if (noisy) return masked ? reinterpret_cast<const void*>(k_prep<CT, true, true>) : reinterpret_cast<const void*>(k_prep<CT, false, true>);
     return masked ? reinterpret_cast<const void*>(k_prep<CT, true>) : reinterpret_cast<const void*>(k_prep<CT, false>);
 }
 
-const void* prep_kernel(int compute_dtype, bool masked, bool noisy) {
-    return compute_dtype == AVAE_BF16 ? prep_instance<__bf16>(masked, noisy) : prep_instance<float>(masked, noisy);
+const void* prep_kernel(int compute_dtype, bool masked, bool noisy, bool sched) {
+    return compute_dtype == AVAE_BF16 ? prep_instance<__bf16>(masked, noisy, sched) : prep_instance<float>(masked, noisy, sched);
 }
 
 template <typename CT> void launch_prep_as(const PrepArgs& a, int n_blocks, hipStream_t s) {
+    if (a.sched) {
+        if (a.noisy) {
+            if (a.pres_src) AVAE_LAUNCH((k_prep<CT, true, true, true>), dim3(n_blocks), dim3(kThreads), 0, s, a);
+            else AVAE_LAUNCH((k_prep<CT, false, true, true>), dim3(n_blocks), dim3(kThreads), 0, s, a);
+        } else if (a.pres_src) AVAE_LAUNCH((k_prep<CT, true, false, true>), dim3(n_blocks), dim3(kThreads), 0, s, a);
+        else AVAE_LAUNCH((k_prep<CT, false, false, true>), dim3(n_blocks), dim3(kThreads), 0, s, a);
+        return;
+    }
     if (a.noisy) {
         if (a.pres_src) AVAE_LAUNCH((k_prep<CT, true, true>), dim3(n_blocks), dim3(kThreads), 0, s, a);
         else AVAE_LAUNCH((k_prep<CT, false, true>), dim3(n_blocks), dim3(kThreads), 0, s, a);

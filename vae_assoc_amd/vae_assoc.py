@@ -27,7 +27,8 @@ import torch
 
 from . import _capi
 from ._marshal import (corruption_fields, grad_clip_fields, grad_clip_kwargs, dev_array, dev_dense, dev_dense3, dev_flags, dev_inputs, dev_modalities, dev_row_args,
-                       ld_of, ptr)
+                       ld_of, ptr, schedule_kwargs, schedule_struct)
+from ._marshal import cyclical, exponential_decay, linear_warmup  # noqa: F401  (schedule helpers, part of this module's surface)
 from .parallel import GradSync, dp_bucket_schedule, dp_train_step_bucketed
 
 _ARCH_KEYS = ("scope", "hidden_conv", "n_hidden_recog_1", "n_hidden_recog_2",
@@ -310,13 +311,18 @@ class AssocVariationalAutoEncoder(object):
                      every training step corrupts the encoder's copy of the batch on the device while the losses keep the clean one
       grad_clip      None, a number (``max_norm``) or a dict of ``set_grad_clip``'s arguments (``max_norm``, ``skip_nonfinite``):
                      clip every step's gradient by its global norm and / or skip a step whose gradient is not finite
+      schedule       None, or a dict of ``set_schedule``'s arguments (``kl``, ``assoc``, ``lr``; steps): KL warm-up, association
+                     ramp and learning-rate decay, evaluated on the device per training step
     """
 
     def __init__(self, network_architectures, binary=True, transfer_fct="softplus", weights=1.0,
                  assoc_lambda=1.0, learning_rate=0.001, batch_size=100, *, compute_dtype="bf16",
                  device=None, seed=0, use_graph=True, data_parallel=False, process_group=None, comm=None,
-                 comm_buckets=2, wire_dtype="fp32", corruption=None, grad_clip=None):
+                 comm_buckets=2, wire_dtype="fp32", corruption=None, grad_clip=None, schedule=None):
         clip_kw = grad_clip_kwargs(grad_clip)        # (a bad value raises before anything is built)
+        if schedule is not None and isinstance(schedule, dict) and schedule.get("unit", "step") != "step":
+            raise ValueError("schedule: the constructor counts in steps (unit='step'); train() converts unit='epoch'")
+        sched_kw = schedule_kwargs(schedule)
         def placement():
             if not torch.cuda.is_available():
                 raise RuntimeError("vae_assoc_amd needs a HIP device (MI355X / gfx950); there is no CPU fallback")
@@ -354,6 +360,8 @@ class AssocVariationalAutoEncoder(object):
             self.set_corruption(**corruption)
         if clip_kw:
             self.set_grad_clip(**clip_kw)
+        if sched_kw:
+            self.set_schedule(**sched_kw)
 
     # ------------------------------------------------------------------ plumbing
     def __del__(self):
@@ -450,6 +458,21 @@ class AssocVariationalAutoEncoder(object):
                                                         v.ctypes.data_as(C.c_void_p), C.byref(step)), "avae_get_opt_state")
         return m, v, step.value
 
+    def set_opt_state(self, m=None, v=None, step=0):
+        """Restores the Adam moments (flat float32 arrays in ``get_params``' order; None leaves one as it is) and the step
+        counter -- what ``get_opt_state`` returns.  The counter keys the eps / corruption streams and the training schedules."""
+        def arr(a):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=np.float32).ravel()
+            if a.size != self.n_params:
+                raise ValueError("expected %d values, got %d" % (self.n_params, a.size))
+            return a
+        m, v = arr(m), arr(v)
+        _capi.check(self._h, self._L.avae_set_opt_state(self._h, None if m is None else m.ctypes.data_as(C.c_void_p),
+                                                        None if v is None else v.ctypes.data_as(C.c_void_p), C.c_int64(int(step))),
+                    "avae_set_opt_state")
+
     def cost_history(self, n):
         out = np.empty(n, dtype=np.float32)
         last = C.c_int64(0)
@@ -494,6 +517,32 @@ class AssocVariationalAutoEncoder(object):
         _capi.check(self._h, self._L.avae_grad_norm_history(self._h, n, out.ctypes.data_as(C.c_void_p), C.byref(last),
                                                             C.byref(skipped)), "avae_grad_norm_history")
         return out, last.value, skipped.value
+
+    def set_schedule(self, kl=None, assoc=None, lr=None):
+        """Training schedules, evaluated on the device for every step (avae_set_schedule in include/avae.h, DESIGN.md section
+        16): ``kl`` multiplies the KL terms (beta warm-up / cyclical annealing), ``assoc`` multiplies ``assoc_lambda`` (ramping the
+        association penalty in), ``lr`` multiplies ``learning_rate`` (where a TF-1 caller wrote ``tf.train.exponential_decay``).
+        Each is None (off: multiplier 1), a number (constant multiplier), ``dict(knots=[(step, value), ...], period=None)`` --
+        linear between up to 8 knots, constant outside, repeating every ``period`` steps when given -- or ``dict(decay_rate=,
+        decay_steps=, staircase=False)``; ``linear_warmup``, ``cyclical`` and ``exponential_decay`` build such dicts.  ``step``
+        counts the steps taken before the one in question (0 for the first step of a fresh model); the value depends on the step
+        counter alone, so a restored model (``restore_model``, ``set_opt_state``) continues its schedule.
+
+        The KL multiplier is a multiplication: 0 does not hide a non-finite KL term.  Evaluation never reads a schedule:
+        ``evaluate_cost``, the early-stop cost of ``train`` and every inference call use the configured objective.
+        ``set_schedule()`` switches everything off.  The call synchronises the device; the setting is not saved by ``save_model``."""
+        sc = [schedule_struct(v, name) for v, name in ((kl, "kl"), (assoc, "assoc"), (lr, "lr"))]
+        _capi.check(self._h, self._L.avae_set_schedule(self._h, *[None if x is None else C.byref(x) for x in sc]), "avae_set_schedule")
+
+    def hyper_history(self, n):
+        """-> (values, last_step): ``values[i] = (kl_t, lambda_t, lr_eff_t)`` of the most recent ``n`` steps as a float32 array
+        [n, 3], oldest first -- the KL multiplier, the scheduled ``assoc_lambda`` and the scheduled ``learning_rate`` the step
+        used -- and the step number of the last one.  ``n`` may not exceed the number of steps trained since ``set_schedule``
+        switched a schedule on (nor the history's 4096)."""
+        out = np.empty((n, 3), dtype=np.float32)
+        last = C.c_int64(0)
+        _capi.check(self._h, self._L.avae_hyper_history(self._h, n, out.ctypes.data_as(C.c_void_p), C.byref(last)), "avae_hyper_history")
+        return out, last.value
 
     def synchronize(self):
         _capi.check(self._h, self._L.avae_synchronize(self._h), "avae_synchronize")
@@ -856,15 +905,24 @@ def train(data_sets, network_architectures, binary=True, weights=1.0, assoc_lamb
     validation cost of ``early_stop`` stays clean.  Under ``data_parallel`` every rank must pass the same ``seed``, as for eps.
 
     ``grad_clip=max_norm`` or ``grad_clip=dict(max_norm=..., skip_nonfinite=...)`` (``set_grad_clip``'s arguments) clips every
-    step's gradient by its global norm and / or skips a step whose gradient is not finite."""
+    step's gradient by its global norm and / or skips a step whose gradient is not finite.
+
+    ``schedule=dict(kl=..., assoc=..., lr=..., unit='step')`` (``set_schedule``'s arguments) anneals the KL weight, ramps the
+    association penalty and decays the learning rate on the device.  With ``unit='epoch'`` the knot steps, periods and
+    ``decay_steps`` count epochs of this loop: they are multiplied by its ``total_batch = n_samples // (batch_size * world)``.
+    The validation cost of ``early_stop`` is the configured objective, whatever the schedule."""
+    schedule = model_kwargs.pop("schedule", None)
+    # (a bad value raises before anything is built; train_loop converts again with the world size the model ends up with)
+    schedule_kwargs(schedule, steps_per_epoch=int(data_sets.train._data.shape[0] / batch_size))
     vae_assoc =AssocVariationalAutoEncoder(network_architectures, binary, transfer_fct="relu", weights=weights,
                                             assoc_lambda=assoc_lambda, learning_rate=learning_rate,
                                             batch_size=batch_size, **model_kwargs)
-    return train_loop(vae_assoc, data_sets, network_architectures, batch_size, training_epochs, display_step, early_stop)
+    return train_loop(vae_assoc, data_sets, network_architectures, batch_size, training_epochs, display_step, early_stop,
+                      schedule=schedule)
 
 
 def train_loop(vae_assoc, data_sets, network_architectures, batch_size, training_epochs=10, display_step=5,
-               early_stop=False, sync=None, device=None):
+               early_stop=False, sync=None, device=None, schedule=None):
     """The loop of ``train`` on an already built model (any object with ``partial_fit`` / ``evaluate_cost``, and optionally
     ``partial_fit_steps`` / ``cost_history``; the CPU tests drive it with an oracle-backed replica).
 
@@ -872,7 +930,10 @@ def train_loop(vae_assoc, data_sets, network_architectures, batch_size, training
     the global batch ``B_g = world * batch_size`` in the place of ``batch_size``: ``next_batch(B_g)`` on every rank -- rank 0's
     NumPy seed is broadcast first, and a checksum of the training matrix is compared, so that all ranks shuffle alike --
     rank r trains on rows [r*batch_size, (r+1)*batch_size) of it, ``total_batch = n_samples // B_g`` and the (already
-    all-reduced, global-batch) cost enters ``avg_cost`` with weight ``B_g / n_samples``."""
+    all-reduced, global-batch) cost enters ``avg_cost`` with weight ``B_g / n_samples``.
+
+    ``schedule`` (``train``'s keyword): handed to the model's ``set_schedule`` before the first step, a schedule in epochs
+    converted to steps with this loop's ``total_batch``."""
     if sync is None:
         sync = getattr(vae_assoc, "_sync", None)
     world = sync.world_size if sync is not None else 1
@@ -886,6 +947,8 @@ def train_loop(vae_assoc, data_sets, network_architectures, batch_size, training
     hist_cap = 4096
     batch_global = batch_size * world
     lo, hi = rank * batch_size, (rank + 1) * batch_size
+    if schedule is not None:
+        vae_assoc.set_schedule(**schedule_kwargs(schedule, steps_per_epoch=int(n_samples / batch_global)))
     # a training split that carries presence (dataset.DataSet(present=)): masked steps, and a masked validation cost
     masked = getattr(data_sets.train, "_present", None) is not None
     if masked and (world > 1 or getattr(vae_assoc, "_comm_lib", False)):
