@@ -328,6 +328,36 @@ int avae_schedule_value(const avae_schedule* schedule, int64_t step, float* out)
  * time.  Synchronises the device. */
 int avae_hyper_history(avae_handle* h, int32_t n, float* host_dst, int64_t* last_step);
 
+/* ---- parameter averaging: an exponential moving average of the parameters, kept on the device (the reference has none; what a
+ * TF-1 caller writes as tf.train.ExponentialMovingAverage(decay[, num_updates]).apply(vars) behind the optimiser, evaluating and
+ * serving from the shadow variables).  While it is on, the optimiser launch of every training step, having formed an element's new
+ * theta, also moves the element's average e towards it:
+ *   e   <- fmaf(theta - e, 1 - d_t, e)                  TF's shadow -= (shadow - var) * (1 - decay): two fp32 roundings, e kept where theta == e
+ *   d_t  = warmup ? fminf(decay, (1 + n) / (10 + n)) : decay,   n = (float)t, t the step number the update gets (1 for the first step)
+ * d_t depends on the settings and the step number alone: the same bits alone, inside a 16- or 4-step replay, masked or not, with or
+ * without graphs, on every data-parallel rank, and after avae_load / avae_set_opt_state restored the step counter.  theta, m, v, the
+ * costs and the step counter are bit for bit what they are without averaging.  A step skipped by skip_nonfinite leaves the average
+ * alone (and still consumes its number).
+ * avae_set_ema: decay in (0, 1) switches averaging on -- the average starts at the current theta -- or, while it is on, changes the
+ * settings and keeps the average; decay = 0 switches it off (and switches avae_use_averaged off first).  NaN, decay < 0 or >= 1, and
+ * warmup outside {0, 1}: an error naming the argument.  The call synchronises the device; switching on <-> off captures the step
+ * graphs again (on: weight gradients -> [sum of squares ->] Adam as separate launches, never the small nets' fused weight-gradient
+ * + Adam launch), changing the values alone does not.  The average (one more fp32 array of the parameters' internal size) and its
+ * settings are allocated by the first call that switches it on and freed by avae_destroy; avae_workspace_bytes is unchanged.
+ * avae_get_ema / avae_set_ema_params: the average in the flat order of avae_get_params, host memory; an error while averaging is off.
+ * avae_use_averaged(h, 1): one launch rebuilds every compute-dtype weight shadow from the average; from then on every forward-only
+ * entry point (avae_encode ... avae_impute) and avae_eval_cost* run on the averaged parameters, and every call that trains or stages
+ * a training step (avae_train_step(s), _masked, _in, avae_stage_batches*, avae_dp_backward, avae_dp_apply) fails with a message naming
+ * avae_use_averaged and changes nothing.  avae_use_averaged(h, 0) rebuilds the shadows from theta.  avae_get_params / avae_get_opt_state
+ * always return the live state.  avae_set_params and avae_load rebuild the shadows from theta: they leave the handle switched back.
+ * Checkpoints: with averaging off avae_save writes the version-2 file; with it on, version 3 = the version-2 body followed by
+ * f32 decay | u32 warmup | the average [P] (flat order).  avae_load reads both: a version-3 file switches averaging on with the
+ * file's settings and average; a version-2 file loaded while averaging is on restarts the average at the loaded theta. */
+int avae_set_ema(avae_handle* h, float decay, int32_t warmup);
+int avae_get_ema(avae_handle* h, float* host_dst);
+int avae_set_ema_params(avae_handle* h, const float* host_src);
+int avae_use_averaged(avae_handle* h, int32_t on);
+
 /* evaluate_cost (vae_assoc.py:388-391): forward + loss, no update. */
 int avae_eval_cost(avae_handle* h, const float* const* x_dev, const int32_t* x_ld,
                    const float* eps_dev, float* cost_host, void* stream);
@@ -482,7 +512,8 @@ int avae_impute(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, 
                 float* mu_dev, float* logvar_dev, float* const* mean_dev, float* const* var_dev, void* stream);
 
 /* save_model / restore_model (vae_assoc.py:427-463): own flat file (config echo + params + Adam
- * slots + step); TF .ckpt files cannot be read offline. */
+ * slots + step; with parameter averaging on also its settings and the average, see avae_set_ema);
+ * TF .ckpt files cannot be read offline. */
 int avae_save(avae_handle* h, const char* path);
 int avae_load(avae_handle* h, const char* path);
 
@@ -502,7 +533,8 @@ int avae_comm_allreduce(avae_handle* h, int32_t bucket, void* stream);
  * stored output of encoder / decoder hidden layer k of modality m [batch, width] (the last forward pass's relu decisions);
  * "shadow_err" -> {max |W - theta|, max |W^T - theta|, layers checked, worst layer}: the compute-dtype weight shadows against the
  * parameters rounded once (must be 0, 0 after any call); "X<m>" staging set 0's encoder input of modality m [batch, n_input] (the
- * compute-dtype copy, widened), "T<m>" its exact loss target. */
+ * compute-dtype copy, widened), "T<m>" its exact loss target; "ema_master" the parameter average as it lies in memory (the internal
+ * padded layout, padding included).  While avae_use_averaged is on, "shadow_err" compares against the average. */
 int avae_debug_fetch(avae_handle* h, const char* name, float* host_dst, size_t max_floats, size_t* n_floats);
 
 #ifdef __cplusplus

@@ -37,6 +37,7 @@ SYMBOLS = [
     "avae_set_corruption", "avae_train_steps_in", "avae_eval_cost_in", "avae_stage_batches_in",
     "avae_set_grad_clip", "avae_grad_norm_history",
     "avae_set_schedule", "avae_schedule_value", "avae_hyper_history",
+    "avae_set_ema", "avae_get_ema", "avae_set_ema_params", "avae_use_averaged",
     "avae_synchronize", "avae_timing_enable", "avae_timing_report", "avae_debug_fetch", "avae_comm_allreduce",
 ]
 
@@ -126,6 +127,10 @@ def lib():
             L.avae_set_schedule.argtypes = [vp, C.POINTER(Schedule), C.POINTER(Schedule), C.POINTER(Schedule)]
             L.avae_schedule_value.argtypes = [C.POINTER(Schedule), C.c_int64, fp]
             L.avae_hyper_history.argtypes = [vp, i32, vp, C.POINTER(C.c_int64)]
+            L.avae_set_ema.argtypes = [vp, C.c_float, i32]
+            L.avae_get_ema.argtypes = [vp, vp]
+            L.avae_set_ema_params.argtypes = [vp, vp]
+            L.avae_use_averaged.argtypes = [vp, i32]
             L.avae_encode.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp]
             L.avae_decode.argtypes = [vp, i32, vp, i32, vp, vp]
             L.avae_generate.argtypes = [vp, vp, i32, C.POINTER(vp), vp]

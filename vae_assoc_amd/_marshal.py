@@ -127,6 +127,39 @@ def grad_clip_kwargs(grad_clip):
     return kw
 
 
+def ema_fields(decay, warmup=False):
+    """The arguments of ``set_ema`` -> (decay as a float32-exact float, warmup as 0 / 1).  ``decay`` None or 0 switches averaging
+    off.  The range is avae_set_ema's, checked here so that a bad value raises ``ValueError`` ahead of the library: the decay the
+    kernel uses is the float32 value, so one that rounds to 1.0 is refused as well."""
+    d = 0.0 if decay is None else decay
+    if isinstance(d, (bool, np.bool_)) or not isinstance(d, (int, float, np.integer, np.floating)):
+        raise ValueError("decay must be a number in (0, 1) (None or 0 = off), got %r" % (decay,))
+    d = float(np.float32(d))
+    if not 0.0 <= d < 1.0:
+        raise ValueError("decay must be in (0, 1) as float32 and not NaN (None or 0 = off), got %r" % (decay,))
+    if not isinstance(warmup, (bool, np.bool_)) and warmup not in (0, 1):
+        raise ValueError("warmup must be True or False, got %r" % (warmup,))
+    return d, 1 if warmup else 0
+
+
+def ema_kwargs(ema):
+    """The ``ema=`` keyword of the constructor and of ``train`` -> the keyword arguments of ``set_ema``: None (off), a number
+    (``decay``), or a dict with the keys ``decay`` and / or ``warmup``."""
+    if ema is None:
+        return {}
+    if isinstance(ema, dict):
+        extra = set(ema) - {"decay", "warmup"}
+        if extra:
+            raise ValueError("ema: unknown key(s) %s (decay, warmup)" % ", ".join(sorted(map(str, extra))))
+        if "decay" not in ema:
+            raise ValueError("ema: the dict needs a decay (decay, warmup)")
+        kw = dict(ema)
+    else:
+        kw = {"decay": ema}
+    ema_fields(kw["decay"], kw.get("warmup", False))
+    return kw
+
+
 SCHEDULE_NAMES = ("kl", "assoc", "lr")
 
 

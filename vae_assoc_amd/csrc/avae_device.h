@@ -222,6 +222,16 @@ struct ClipState {
     float norm_hist[kCostHist];        // raw gradient norm of every step, indexed like DevState::cost_hist
 };
 
+// Parameter averaging (include/avae.h, avae_set_ema): a first-use allocation of its own -- this header, then the average itself,
+// P_int floats in the master layout (element i of theta has its average at avg[i]).  decay / warmup are read by k_adam, so changing
+// their values re-captures no graph.
+struct EmaState {
+    float decay;
+    int warmup;
+    int pad[30];                       // the average starts on a 128-byte line, as theta does
+};
+static_assert(sizeof(EmaState) == 128, "the average is line-aligned behind its settings");
+
 // Training schedules (include/avae.h, avae_set_schedule): a first-use allocation of its own.  The staging launch of a training
 // submission evaluates the three schedules for each of its batches (step number = DevState::step + 1 + the batch's index) and
 // writes entry j of `tab` -- read by the latent and cost items of the step on staging set j -- and the history ring.  The schedules
@@ -292,6 +302,11 @@ struct AdamArgs {
     const float* cost_src;   // grad[cost slot]
     ClipState* clip;         // k_adam<.., CLIP = true> only: the step's partial sums of squares, the threshold, the norm ring
     int n_partial;           // ... and how many partials there are (G)
+    // k_adam<.., EMA = true> only (avae_set_ema): the average of the element at theta0 + i is avg[i].  mode 0: it is updated from
+    // the new theta (decay / warmup from *ema); mode 1: the shadows are rebuilt from it instead of theta (avae_use_averaged)
+    const EmaState* ema;
+    float* avg;
+    const float* theta0;
 };
 
 // Input staging ("prep"): fp32 rows -> compute-dtype copy (+ exact fp32 copy for the losses),
@@ -603,7 +618,7 @@ void launch_grouped(int compute_dtype, int tile_cfg, const LaunchArgs& args, int
                     DevState* st, hipStream_t s, unsigned long long* stamps = nullptr, int launch_id = 0);
 void launch_grouped_tn(int compute_dtype, int tile_cfg, const TnLaunchArgs& args, int grid_x, int grid_y, int lds_bytes,
                        DevState* st, hipStream_t s, unsigned long long* stamps = nullptr, int launch_id = 0);
-void launch_adam(int compute_dtype, const AdamArgs& a, int n_blocks, hipStream_t s);      // a.clip != null: the clip-aware instance
+void launch_adam(int compute_dtype, const AdamArgs& a, int n_blocks, hipStream_t s);      // a.clip != null: the clip-aware instance; a.avg != null: the averaging one
 void launch_grad_sumsq(const float* g, long long p_int, float* partial, hipStream_t s);
 void launch_prep(int compute_dtype, const PrepArgs& a, hipStream_t s);
 const void* prep_kernel(int compute_dtype, bool masked, bool noisy, bool sched);   // for hipGraphExecKernelNodeSetParams on the captured staging node

@@ -311,6 +311,16 @@ struct avae_handle {
     DevBuf sched_buf;
     long long sched_steps = 0;              // steps submitted since a schedule was last switched on (bounds avae_hyper_history)
 
+    // avae_set_ema: exponential averaging of the parameters.  ema_on: every k_adam launch of a training step runs its EMA instance,
+    // which updates the average next to theta (small nets leave the fused weight-gradient + Adam launch, as for clipping); decay
+    // and warmup live in the EmaState that leads ema_buf, the average (P_int floats, master layout) behind it -- allocated by the
+    // first call that switches averaging on.  averaged (avae_use_averaged): the compute-dtype shadows currently hold the average,
+    // not theta -- inference and evaluation run on it, every training call is refused.
+    bool ema_on = false, averaged = false;
+    float ema_decay = 0.0f;
+    int ema_warmup = 0;
+    DevBuf ema_buf;
+
     // avae_complete: the launches of one refinement pass (decoders forward, then their input-gradient chain from the training plan's
     // item builders on the same buffers), captured as runs of kCompleteSizes[i] passes; the kernels' arguments; the scratch behind
     // them.  Built and allocated by the first call.
@@ -332,6 +342,7 @@ struct avae_handle {
     template <typename T> T* at(size_t off) const { return reinterpret_cast<T*>(ws + off); }
     DevState* state() const { return at<DevState>(off_state); }
     float* grad() const { return at<float>(off_g); }
+    float* ema_avg() const { return reinterpret_cast<float*>(ema_buf.as<unsigned char>() + sizeof(EmaState)); }
 };
 
 namespace {
@@ -2151,7 +2162,8 @@ void run_set(avae_handle* h, const std::vector<Launch>& ls, size_t lo, size_t hi
 
 void run_launches(avae_handle* h, const std::vector<Launch>& ls, hipStream_t s) { run_set(h, ls, 0, ls.size(), 0, s); }
 
-void run_adam(avae_handle* h, int mode, hipStream_t s, int bucket = -1) {
+// mode 0: the optimiser (with the average's update while averaging is on); mode 1: the shadows from theta, or -- from_avg -- from the average
+void run_adam(avae_handle* h, int mode, hipStream_t s, int bucket = -1, bool from_avg = false) {
     AdamArgs a;
     std::memset(&a, 0, sizeof(a));
     int blocks = h->adam_blocks;
@@ -2174,6 +2186,10 @@ void run_adam(avae_handle* h, int mode, hipStream_t s, int bucket = -1) {
     a.cost_src = h->grad() + h->P_int;
     a.clip = (mode == 0 && h->clip_on) ? h->clip_buf.as<ClipState>() : nullptr;      // the clip-aware instance (mode 1 is never clipped)
     a.n_partial = sumsq_blocks((long long)h->P_int);
+    if (mode == 0 ? h->ema_on : from_avg) {          // the averaging instance
+        if (!h->ema_buf.p) throw Err("internal error: averaging is on without its device state");
+        a.ema = h->ema_buf.as<EmaState>(); a.avg = h->ema_avg(); a.theta0 = h->at<float>(h->off_theta);
+    }
     Timed t(h, s, mode == 0 ? (bucket < 0 ? "adam" : bucket == 0 ? "adam_dec" : "adam_enc") : "shadow_refresh");
     launch_adam(h->cfg.compute_dtype, a, blocks, s);
     LAUNCH_OK(mode == 0 ? "adam" : "shadow_refresh");
@@ -2325,12 +2341,13 @@ void fill_ones(avae_handle* h, const Act& a, hipStream_t s) {
 }
 
 // One step on staging set j (forward launches `fwd`: a plan's): forward, backward, then the weight gradients with Adam in their
-// epilogue, or followed by k_adam; with clipping on always weight gradients -> k_grad_sumsq -> k_adam.
+// epilogue, or followed by k_adam; with clipping on always weight gradients -> k_grad_sumsq -> k_adam, with averaging on always
+// weight gradients -> k_adam (the fused epilogue knows neither).
 void step_body(avae_handle* h, const std::vector<Launch>& fwd, hipStream_t s, int j, int stamp_base = -1) {
     auto sb = [&](size_t k) { return stamp_base < 0 ? -1 : stamp_base + (int)k; };
     run_set(h, fwd, 0, fwd.size(), j, s, stamp_base, true);
     run_set(h, h->bwd, 0, h->bwd.size(), j, s, sb(fwd.size()), true);
-    if (!h->wgrad_adam.empty() && !h->clip_on) {       // the optimiser rides in the weight-gradient launch
+    if (!h->wgrad_adam.empty() && !h->clip_on && !h->ema_on) {       // the optimiser rides in the weight-gradient launch
         run_set(h, h->wgrad_adam, 0, h->wgrad_adam.size(), j, s, sb(fwd.size() + h->bwd.size()), true);
         return;
     }
@@ -2339,7 +2356,7 @@ void step_body(avae_handle* h, const std::vector<Launch>& fwd, hipStream_t s, in
     run_adam(h, 0, s);
 }
 
-// The training graphs of plan p (what avae_set_grad_clip captures again when the step's tail changes; eval holds no optimiser).
+// The training graphs of plan p (what avae_set_grad_clip / avae_set_ema capture again when the step's tail changes; eval holds no optimiser).
 // `present` non-null: the masked plan (masked staging; the placeholder is patched per replay like the inputs).  On failure p keeps
 // none of them.
 void capture_steps(avae_handle* h, StepPlan& p, const uint8_t* present) {
@@ -3234,6 +3251,68 @@ void eval_cost(avae_handle* h, StepPlan& p, const float* const* x_dev, const int
     fetch_cost(h, cost_host, false, s);
 }
 
+// Every call that trains or stages a training step: refused while the shadows hold the average.
+void require_live(const avae_handle* h, const char* who) {
+    if (h->averaged)
+        throw Err(std::string(who) + ": the handle runs on the averaged weights; call avae_use_averaged(h, 0) before training");
+}
+
+void ema_to_host(avae_handle* h, std::vector<float>& host) {
+    host.resize(h->P_int);
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipMemcpy(host.data(), h->ema_avg(), h->P_int * 4, hipMemcpyDeviceToHost));
+}
+void host_to_ema(avae_handle* h, const std::vector<float>& host) {
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipMemcpy(h->ema_avg(), host.data(), h->P_int * 4, hipMemcpyHostToDevice));
+}
+// average <- theta, on the device (padding included: zero in both)
+void ema_from_theta(avae_handle* h) {
+    HIP_OK(hipDeviceSynchronize());
+    HIP_OK(hipMemcpy(h->ema_avg(), h->at<void>(h->off_theta), h->P_int * 4, hipMemcpyDeviceToDevice));
+    HIP_OK(hipDeviceSynchronize());
+}
+
+// The mode-1 launch from the average (on) or from theta (off): the shadows every forward launch reads.
+void use_averaged(avae_handle* h, bool on) {
+    if (on && !h->ema_on) throw Err("avae_use_averaged: parameter averaging is off (avae_set_ema)");
+    if (on == h->averaged) return;
+    HIP_OK(hipDeviceSynchronize());
+    run_adam(h, 1, nullptr, -1, on);
+    HIP_OK(hipDeviceSynchronize());
+    h->averaged = on;
+}
+
+void set_ema(avae_handle* h, float decay, int32_t warmup) {
+    if (!(decay >= 0.0f && decay < 1.0f)) throw Err("avae_set_ema: decay must be in (0, 1), or 0 to switch averaging off");
+    if (warmup != 0 && warmup != 1) throw Err("avae_set_ema: warmup must be 0 or 1");
+    const bool on = decay > 0.0f;
+    HIP_OK(hipDeviceSynchronize());             // a rare call: enqueued work keeps the setting it was enqueued with
+    if (!on && !h->ema_buf.p) return;           // never switched on
+    if (!on && h->averaged) use_averaged(h, false);
+    h->ema_buf.ensure(sizeof(EmaState) + h->P_int * sizeof(float));
+    if (on) {
+        EmaState v;
+        std::memset(&v, 0, sizeof(v));
+        v.decay = decay; v.warmup = warmup;
+        HIP_OK(hipMemcpy(h->ema_buf.p, &v, sizeof(v), hipMemcpyHostToDevice));
+        h->ema_decay = decay; h->ema_warmup = warmup;
+    }
+    // new values only: k_adam reads them from the device (unless an earlier capture failed and left the plan without graphs)
+    if (on == h->ema_on && (!h->cfg.use_graph || h->plain.full.exec)) return;
+    if (on && !h->ema_on) ema_from_theta(h);    // the average starts at the current parameters
+    // on <-> off: the step's tail changes, so every graph that holds an optimiser goes; the data-parallel segment graphs hold
+    // none and stay, g_dpm is captured again by its next use
+    h->plain.full.release(); h->plain.multi[0].release(); h->plain.multi[1].release();
+    h->masked.full.release(); h->masked.multi[0].release(); h->masked.multi[1].release();
+    for (StepGraph& g : h->g_dpm) g.release();
+    h->ema_on = on;
+    if (h->cfg.use_graph) {
+        capture_steps(h, h->plain, nullptr);
+        if (!h->masked.fwd.empty()) capture_steps(h, h->masked, h->pres_buf.as<unsigned char>());
+    }
+}
+
 // Frees whatever the handle holds (a partly created one included), then the handle.
 void destroy_handle(avae_handle* h) {
     int prev_dev = -1;
@@ -3338,8 +3417,9 @@ int avae_set_params(avae_handle* h, const float* host_src) {
         std::vector<float> I(h->P_int, 0.0f);
         convert_params<true>(h, const_cast<float*>(host_src), I.data());
         host_to_master(h, h->off_theta, I);
-        run_adam(h, 1, nullptr);          // rebuild the compute-dtype shadows W / W^T
+        run_adam(h, 1, nullptr);          // rebuild the compute-dtype shadows W / W^T (from theta: avae_use_averaged is off after this)
         HIP_OK(hipDeviceSynchronize());
+        h->averaged = false;
     });
 }
 
@@ -3372,6 +3452,7 @@ int avae_set_opt_state(avae_handle* h, const float* host_m, const float* host_v,
 int avae_stage_batches_in(avae_handle* h, int32_t n_steps, const float* const* x_dev, const int32_t* x_ld, const float* const* in_dev,
                           const int32_t* in_ld, const float* eps_dev, void* stream) {
     return guarded(h, [&] {
+        require_live(h, "avae_stage_batches");
         if (n_steps < 1 || n_steps > kMultiSteps) throw Err("avae_stage_batches: n_steps must be in [1," + std::to_string(kMultiSteps) + "]");
         check_inputs(h, "avae_stage_batches_in", x_dev, in_dev, in_ld);
         run_prep_batch(h, x_dev, x_ld, eps_dev, h->B, kTrainSalt, on_stream(h, stream), nullptr, n_steps, PrepIn{in_dev, in_ld, true});
@@ -3384,6 +3465,7 @@ int avae_stage_batches(avae_handle* h, int32_t n_steps, const float* const* x_de
 
 int avae_train_step(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, const float* eps_dev, float* cost_host, void* stream) {
     return guarded(h, [&] {
+        require_live(h, "avae_train_step");
         hipStream_t s = on_stream(h, stream);
         train_one(h, h->plain, x_dev, x_ld, nullptr, eps_dev, PrepIn{nullptr, nullptr, true}, s);
         if (h->clip_on) ++h->clip_steps;
@@ -3395,6 +3477,7 @@ int avae_train_step(avae_handle* h, const float* const* x_dev, const int32_t* x_
 int avae_train_steps_in(avae_handle* h, int32_t n_steps, const float* const* x_dev, const int32_t* x_ld, const float* const* in_dev,
                         const int32_t* in_ld, const uint8_t* present_dev, const float* eps_dev, float* cost_host, void* stream) {
     return guarded(h, [&] {
+        require_live(h, "avae_train_steps_in");
         if (present_dev) check_masked_call(h, "avae_train_steps_in", x_dev, present_dev);
         if (n_steps < 1) throw Err("avae_train_steps_in: n_steps must be >= 1");
         check_inputs(h, "avae_train_steps_in", x_dev, in_dev, in_ld);
@@ -3407,6 +3490,7 @@ int avae_train_steps_in(avae_handle* h, int32_t n_steps, const float* const* x_d
 int avae_train_steps(avae_handle* h, int32_t n_steps, const float* const* x_dev, const int32_t* x_ld, const float* eps_dev,
                      float* cost_host, void* stream) {
     return guarded(h, [&] {
+        require_live(h, "avae_train_steps");
         if (n_steps < 1) throw Err("avae_train_steps: n_steps must be >= 1");
         train_steps(h, h->plain, n_steps, x_dev, x_ld, nullptr, nullptr, nullptr, eps_dev, cost_host, on_stream(h, stream));
     });
@@ -3479,6 +3563,38 @@ int avae_grad_norm_history(avae_handle* h, int32_t n, float* host_norms, int64_t
         }
         if (last_step) *last_step = step;
         if (n_skipped) *n_skipped = skipped;
+    });
+}
+
+int avae_set_ema(avae_handle* h, float decay, int32_t warmup) {
+    return guarded(h, [&] { set_ema(h, decay, warmup); });
+}
+
+int avae_get_ema(avae_handle* h, float* host_dst) {
+    return guarded(h, [&] {
+        if (!h->ema_on) throw Err("avae_get_ema: parameter averaging is off (avae_set_ema)");
+        if (!host_dst) throw Err("avae_get_ema: null host_dst");
+        std::vector<float> I;
+        ema_to_host(h, I);
+        convert_params<false>(h, host_dst, I.data());
+    });
+}
+
+int avae_set_ema_params(avae_handle* h, const float* host_src) {
+    return guarded(h, [&] {
+        if (!h->ema_on) throw Err("avae_set_ema_params: parameter averaging is off (avae_set_ema)");
+        if (!host_src) throw Err("avae_set_ema_params: null host_src");
+        std::vector<float> I(h->P_int, 0.0f);
+        convert_params<true>(h, const_cast<float*>(host_src), I.data());
+        host_to_ema(h, I);
+        if (h->averaged) { run_adam(h, 1, nullptr, -1, true); HIP_OK(hipDeviceSynchronize()); }      // the shadows follow
+    });
+}
+
+int avae_use_averaged(avae_handle* h, int32_t on) {
+    return guarded(h, [&] {
+        if (on != 0 && on != 1) throw Err("avae_use_averaged: on must be 0 or 1");
+        use_averaged(h, on != 0);
     });
 }
 
@@ -3558,6 +3674,7 @@ int avae_hyper_history(avae_handle* h, int32_t n, float* host_dst, int64_t* last
 int avae_train_steps_masked(avae_handle* h, int32_t n_steps, const float* const* x_dev, const int32_t* x_ld, const uint8_t* present_dev,
                             const float* eps_dev, float* cost_host, void* stream) {
     return guarded(h, [&] {
+        require_live(h, "avae_train_steps_masked");
         check_masked_call(h, "avae_train_steps_masked", x_dev, present_dev);
         if (n_steps < 1) throw Err("avae_train_steps_masked: n_steps must be >= 1");
         build_masked(h);
@@ -3612,11 +3729,12 @@ int avae_dp_plan(const avae_config* cfg, int32_t* n_buckets, int32_t* n_ranges, 
 }
 
 int avae_dp_backward(avae_handle* h, int32_t j, int32_t bucket, void* stream) {
-    return guarded(h, [&] { dp_segment(h, j, bucket, on_stream(h, stream)); });
+    return guarded(h, [&] { require_live(h, "avae_dp_backward"); dp_segment(h, j, bucket, on_stream(h, stream)); });
 }
 
 int avae_dp_apply(avae_handle* h, int32_t bucket, float* cost_host, void* stream) {
     return guarded(h, [&] {
+        require_live(h, "avae_dp_apply");
         if (bucket < 0 || bucket >= h->n_buckets) throw Err("data-parallel bucket out of range");
         hipStream_t s = on_stream(h, stream);
         if (h->clip_on && bucket == 0) { run_grad_sumsq(h, s); ++h->clip_steps; }      // over the whole buffer: both all-reduces come before apply(0); apply(1) reuses the partials
@@ -4065,9 +4183,11 @@ int avae_complete(avae_handle* h, const float* const* x_dev, const int32_t* x_ld
 }
 
 // ---- checkpoint: "AVAECKPT" | u32 version | u32 n_mod | u32 n_z | per modality {n_input, L, hs[L], conv, gener1, gener2} | u64 P | i64 step | theta | m | v
+// version 2: that; version 3 (written while parameter averaging is on): that, then f32 decay | u32 warmup | the average [P]
 int avae_save(avae_handle* h, const char* path) {
     return guarded(h, [&] {
-        std::vector<float> I, th(h->P_flat), mm(h->P_flat), vv(h->P_flat);
+        std::vector<float> I, th(h->P_flat), mm(h->P_flat), vv(h->P_flat), av;
+        if (h->ema_on) { av.resize(h->P_flat); ema_to_host(h, I); convert_params<false>(h, av.data(), I.data()); }
         master_to_host(h, h->off_theta, I); convert_params<false>(h, th.data(), I.data());
         master_to_host(h, h->off_m, I); convert_params<false>(h, mm.data(), I.data());
         master_to_host(h, h->off_v, I); convert_params<false>(h, vv.data(), I.data());
@@ -4077,7 +4197,7 @@ int avae_save(avae_handle* h, const char* path) {
         if (!f) throw Err(std::string("cannot open for writing: ") + path);
         auto w32 = [&](uint32_t v) { std::fwrite(&v, 4, 1, f); };
         std::fwrite("AVAECKPT", 1, 8, f);
-        w32(2); w32((uint32_t)h->M); w32((uint32_t)h->nz);
+        w32(h->ema_on ? 3 : 2); w32((uint32_t)h->M); w32((uint32_t)h->nz);
         for (int m = 0; m < h->M; ++m) {
             const Mod& md = h->mods[m];
             w32((uint32_t)md.n_in); w32((uint32_t)md.hs.size()); for (int x : md.hs) w32((uint32_t)x);
@@ -4086,6 +4206,12 @@ int avae_save(avae_handle* h, const char* path) {
         uint64_t P = h->P_flat; std::fwrite(&P, 8, 1, f);
         int64_t st = step; std::fwrite(&st, 8, 1, f);
         bool ok = std::fwrite(th.data(), 4, P, f) == P && std::fwrite(mm.data(), 4, P, f) == P && std::fwrite(vv.data(), 4, P, f) == P;
+        if (h->ema_on) {
+            const float decay = h->ema_decay;
+            ok = std::fwrite(&decay, 4, 1, f) == 1 && ok;
+            w32((uint32_t)h->ema_warmup);
+            ok = std::fwrite(av.data(), 4, P, f) == P && ok;
+        }
         ok = (std::fclose(f) == 0) && ok;
         if (!ok) throw Err(std::string("short write: ") + path);
     });
@@ -4095,13 +4221,16 @@ int avae_load(avae_handle* h, const char* path) {
     return guarded(h, [&] {
         FILE* f = std::fopen(path, "rb");
         if (!f) throw Err(std::string("cannot open for reading: ") + path);
-        std::vector<float> th, mm, vv;
+        std::vector<float> th, mm, vv, av;
         int64_t st = 0;
+        uint32_t version = 0, warmup = 0;
+        float decay = 0.0f;
         try {
             char magic[8];
             auto r32 = [&]() { uint32_t v = 0; if (std::fread(&v, 4, 1, f) != 1) throw Err("truncated checkpoint"); return v; };
             if (std::fread(magic, 1, 8, f) != 8 || std::memcmp(magic, "AVAECKPT", 8) != 0) throw Err("not an AVAE checkpoint");
-            if (r32() != 2) throw Err("unsupported checkpoint version");
+            version = r32();
+            if (version != 2 && version != 3) throw Err("unsupported checkpoint version");
             if ((int)r32() != h->M || (int)r32() != h->nz) throw Err("checkpoint architecture mismatch (modalities / n_z)");
             for (int m = 0; m < h->M; ++m) {
                 const Mod& md = h->mods[m];
@@ -4118,6 +4247,13 @@ int avae_load(avae_handle* h, const char* path) {
             th.resize(P); mm.resize(P); vv.resize(P);
             if (std::fread(th.data(), 4, P, f) != P || std::fread(mm.data(), 4, P, f) != P || std::fread(vv.data(), 4, P, f) != P)
                 throw Err("truncated checkpoint");
+            if (version == 3) {
+                if (std::fread(&decay, 4, 1, f) != 1) throw Err("truncated checkpoint");
+                warmup = r32();
+                if (!(decay > 0.0f && decay < 1.0f) || warmup > 1) throw Err("checkpoint holds invalid averaging settings");
+                av.resize(P);
+                if (std::fread(av.data(), 4, P, f) != P) throw Err("truncated checkpoint");
+            }
         } catch (...) { std::fclose(f); throw; }
         std::fclose(f);
         std::vector<float> I(h->P_int, 0.0f);
@@ -4126,8 +4262,15 @@ int avae_load(avae_handle* h, const char* path) {
         std::fill(I.begin(), I.end(), 0.0f); convert_params<true>(h, vv.data(), I.data()); host_to_master(h, h->off_v, I);
         long long step = st;
         HIP_OK(hipMemcpy(&h->state()->step, &step, sizeof(step), hipMemcpyHostToDevice));
-        run_adam(h, 1, nullptr);
+        run_adam(h, 1, nullptr);          // (from theta: avae_use_averaged is off after a load)
         HIP_OK(hipDeviceSynchronize());
+        h->averaged = false;
+        if (version == 3) {               // the file's settings and average
+            set_ema(h, decay, (int32_t)warmup);
+            std::fill(I.begin(), I.end(), 0.0f); convert_params<true>(h, av.data(), I.data()); host_to_ema(h, I);
+        } else if (h->ema_on) {
+            ema_from_theta(h);            // a file without an average: it starts again at the loaded parameters
+        }
     });
 }
 
@@ -4263,7 +4406,7 @@ int avae_debug_fetch(avae_handle* h, const char* name, float* host_dst, size_t m
                 if (d.in <= 0 || d.out <= 0) return;
                 std::vector<float> th((size_t)(d.in + 1) * d.ld);
                 std::vector<unsigned char> w((size_t)(d.in + 1) * d.ldw * h->es), wt((size_t)d.out * d.ldt * h->es);
-                HIP_OK(hipMemcpy(th.data(), h->at<float>(h->off_theta) + d.master, th.size() * 4, hipMemcpyDeviceToHost));
+                HIP_OK(hipMemcpy(th.data(), (h->averaged ? h->ema_avg() : h->at<float>(h->off_theta)) + d.master, th.size() * 4, hipMemcpyDeviceToHost));
                 HIP_OK(hipMemcpy(w.data(), h->at<void>(d.W), w.size(), hipMemcpyDeviceToHost));
                 HIP_OK(hipMemcpy(wt.data(), h->at<void>(d.Wt), wt.size(), hipMemcpyDeviceToHost));
                 float a = 0.f, b2 = 0.f;
@@ -4287,6 +4430,10 @@ int avae_debug_fetch(avae_handle* h, const char* name, float* host_dst, size_t m
             host_dst[0] = ew; host_dst[1] = et; host_dst[2] = (float)cnt; host_dst[3] = (float)worst;
             if (n_floats) *n_floats = 4;
             return;
+        }
+        else if (n == "ema_master") {       // the average as it lies in memory: P_int floats, master layout, padding included
+            if (!h->ema_on) throw Err("debug_fetch: parameter averaging is off");
+            src = h->ema_avg(); cnt = h->P_int;
         }
         else if (n.rfind("mulv", 0) == 0 || n.rfind("g0_", 0) == 0) {
             const bool g0 = n[0] == 'g';

@@ -255,6 +255,13 @@ __device__ __forceinline__ void adam_update(float g, float& m, float& v, float& 
     th -= (m * lr_t) / (sqrtf(v) + eps);
 }
 
+// One parameter's exponential average (avae_set_ema), TF-1's `shadow -= (shadow - var) * (1 - decay)` -- ONE definition, a difference
+// and an explicit fused multiply-add: two roundings, and e keeps its bits where th == e.
+__device__ __forceinline__ void ema_update(float th, float& e, float omd) {
+#pragma clang fp contract(off)
+    e = __builtin_fmaf(th - e, omd, e);
+}
+
 // Reconstruction loss of one element and its gradient w.r.t. the logit -- ONE definition for the three kernels that carry the loss
 // epilogue, with floating-point contraction off inside it, so that every route rounds alike (the routes are checked against each other
 // bitwise).  sl = scale * loss, da = scale * dloss/da.
@@ -2443,7 +2450,13 @@ void launch_grouped_tn(int compute_dtype, int tile_cfg, const TnLaunchArgs& args
 // data-parallel run, whose partials come from the same all-reduced bits -- forms bitwise the same s, norm and factor c, broadcast
 // through LDS.  The gradient is scaled by c on its way into adam_update (one fp32 multiplication; the buffer keeps the raw value).
 // A non-finite s with skip_nonfinite set ends the workgroup before it has stored anything: theta, m, v and every shadow keep their bits.
-template <typename CT, int TR, bool CLIP>
+//
+// EMA (avae_set_ema): mode 0 -- the thread that has just formed an element's new theta also loads, updates (ema_update) and stores
+// its average: the same quad, the same bounds, padding never touched; a skipped step has returned before.  The factor 1 - d_t is
+// formed by every thread in fp32 from the settings and the step number the update carries (DevState::step, already bumped):
+// TF's num_updates form d_t = min(decay, (1 + n) / (10 + n)) with warm-up, else decay.  mode 1 -- the shadows are rebuilt from
+// the average instead of theta (avae_use_averaged).
+template <typename CT, int TR, bool CLIP, bool EMA = false>
 __global__ void __launch_bounds__(kThreads) k_adam(AdamArgs a) {
     static_assert(TR % 16 == 0 && TR <= 64, "a pass covers 16 rows x 16 quads");
     constexpr int NTH = kThreads;
@@ -2494,6 +2507,14 @@ __global__ void __launch_bounds__(kThreads) k_adam(AdamArgs a) {
     }
     const float lr_t = a.mode == 0 ? a.st->lr_t : 0.0f;
     const float omb1 = 1.0f - a.beta1, omb2 = 1.0f - a.beta2;
+    float omd = 0.0f;
+    if constexpr (EMA) {
+        if (a.mode == 0) {
+#pragma clang fp contract(off)
+            const float d = a.ema->decay, n = (float)a.st->step;
+            omd = 1.0f - (a.ema->warmup ? fminf(d, (1.0f + n) / (10.0f + n)) : d);
+        }
+    }
 
     const int c4 = (tid & 15) * 4;
 #pragma unroll
@@ -2503,7 +2524,8 @@ __global__ void __launch_bounds__(kThreads) k_adam(AdamArgs a) {
         float th[4] = {0.f, 0.f, 0.f, 0.f};
         if (grow < w.rows && gcol < w.cols) {
             const size_t off = (size_t)grow * w.ld + gcol;   // ld % 4 == 0: the quad is in-row and 16-B aligned
-            load4<float>(w.theta + off, th);
+            if (EMA && a.mode != 0) load4<float>(a.avg + ((w.theta - a.theta0) + off), th);
+            else load4<float>(w.theta + off, th);
             if (a.mode == 0) {
                 float g[4], m[4], v[4];
                 load4<float>(w.g + off, g);
@@ -2515,6 +2537,14 @@ __global__ void __launch_bounds__(kThreads) k_adam(AdamArgs a) {
                 store_row<float>(w.theta + off, th, nv);
                 store_row<float>(w.m + off, m, nv);
                 store_row<float>(w.v + off, v, nv);
+                if constexpr (EMA) {
+                    float* ap = a.avg + ((w.theta - a.theta0) + off);
+                    float av[4];
+                    load4<float>(ap, av);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) ema_update(th[e], av[e], omd);
+                    store_row<float>(ap, av, nv);
+                }
             }
             store_row<CT>(reinterpret_cast<CT*>(w.W) + (size_t)grow * w.ldw + gcol, th, w.cols - gcol);
             if (w.adj_k > 0 && grow < w.adj_k * w.adj_k * w.adj_cin) {       // (not the bias row)
@@ -2549,6 +2579,17 @@ __global__ void __launch_bounds__(kThreads) k_adam(AdamArgs a) {
 }
 
 void launch_adam(int compute_dtype, const AdamArgs& a, int n_blocks, hipStream_t s) {
+    if (a.avg) {
+        const bool clip = a.clip && a.mode == 0;
+        if (compute_dtype == AVAE_BF16) {
+            if (clip) AVAE_LAUNCH((k_adam<__bf16, kAdamRows, true, true>), dim3(n_blocks), dim3(kThreads), 0, s, a);
+            else AVAE_LAUNCH((k_adam<__bf16, kAdamRows, false, true>), dim3(n_blocks), dim3(kThreads), 0, s, a);
+        } else {
+            if (clip) AVAE_LAUNCH((k_adam<float, kAdamRows, true, true>), dim3(n_blocks), dim3(kThreads), 0, s, a);
+            else AVAE_LAUNCH((k_adam<float, kAdamRows, false, true>), dim3(n_blocks), dim3(kThreads), 0, s, a);
+        }
+        return;
+    }
     if (a.clip && a.mode == 0) {
         if (compute_dtype == AVAE_BF16) AVAE_LAUNCH((k_adam<__bf16, kAdamRows, true>), dim3(n_blocks), dim3(kThreads), 0, s, a);
         else AVAE_LAUNCH((k_adam<float, kAdamRows, true>), dim3(n_blocks), dim3(kThreads), 0, s, a);

@@ -17,6 +17,7 @@ Deliberate, documented differences from the reference:
   * ``hidden_conv=True`` (conv encoder :169-210 / deconv decoder :249-291, deconv.py) is built for what
     the reference's branch can express: a binary 28x28 modality (n_input = 784).
 """
+import contextlib
 import ctypes as C
 import datetime
 import os
@@ -26,7 +27,7 @@ import numpy as np
 import torch
 
 from . import _capi
-from ._marshal import (corruption_fields, grad_clip_fields, grad_clip_kwargs, dev_array, dev_dense, dev_dense3, dev_flags, dev_inputs, dev_modalities, dev_row_args,
+from ._marshal import (corruption_fields, ema_fields, ema_kwargs, grad_clip_fields, grad_clip_kwargs, dev_array, dev_dense, dev_dense3, dev_flags, dev_inputs, dev_modalities, dev_row_args,
                        ld_of, ptr, schedule_kwargs, schedule_struct)
 from ._marshal import cyclical, exponential_decay, linear_warmup  # noqa: F401  (schedule helpers, part of this module's surface)
 from .parallel import GradSync, dp_bucket_schedule, dp_train_step_bucketed
@@ -313,13 +314,16 @@ class AssocVariationalAutoEncoder(object):
                      clip every step's gradient by its global norm and / or skip a step whose gradient is not finite
       schedule       None, or a dict of ``set_schedule``'s arguments (``kl``, ``assoc``, ``lr``; steps): KL warm-up, association
                      ramp and learning-rate decay, evaluated on the device per training step
+      ema            None, a number (``decay``) or a dict of ``set_ema``'s arguments (``decay``, ``warmup``): keep an exponential
+                     average of the parameters on the device; ``averaged()`` runs inference and evaluation on it
     """
 
     def __init__(self, network_architectures, binary=True, transfer_fct="softplus", weights=1.0,
                  assoc_lambda=1.0, learning_rate=0.001, batch_size=100, *, compute_dtype="bf16",
                  device=None, seed=0, use_graph=True, data_parallel=False, process_group=None, comm=None,
-                 comm_buckets=2, wire_dtype="fp32", corruption=None, grad_clip=None, schedule=None):
+                 comm_buckets=2, wire_dtype="fp32", corruption=None, grad_clip=None, schedule=None, ema=None):
         clip_kw = grad_clip_kwargs(grad_clip)        # (a bad value raises before anything is built)
+        ema_kw = ema_kwargs(ema)
         if schedule is not None and isinstance(schedule, dict) and schedule.get("unit", "step") != "step":
             raise ValueError("schedule: the constructor counts in steps (unit='step'); train() converts unit='epoch'")
         sched_kw = schedule_kwargs(schedule)
@@ -362,6 +366,8 @@ class AssocVariationalAutoEncoder(object):
             self.set_grad_clip(**clip_kw)
         if sched_kw:
             self.set_schedule(**sched_kw)
+        if ema_kw:
+            self.set_ema(**ema_kw)
 
     # ------------------------------------------------------------------ plumbing
     def __del__(self):
@@ -543,6 +549,50 @@ class AssocVariationalAutoEncoder(object):
         last = C.c_int64(0)
         _capi.check(self._h, self._L.avae_hyper_history(self._h, n, out.ctypes.data_as(C.c_void_p), C.byref(last)), "avae_hyper_history")
         return out, last.value
+
+    def set_ema(self, decay, warmup=False):
+        """Parameter averaging (avae_set_ema in include/avae.h) -- where a TF-1 caller of the reference
+        wrote ``tf.train.ExponentialMovingAverage(decay).apply(...)`` behind the optimiser.  From now on every training step also
+        moves an average of the parameters, kept on the device, towards the step's new parameters:
+        ``avg -= (avg - theta) * (1 - d_t)`` with ``d_t = decay``, or with ``warmup=True`` TF's ``num_updates`` form
+        ``d_t = min(decay, (1 + t) / (10 + t))``, t the step's number.  Switching it on starts the average at the current
+        parameters; training itself (parameters, moments, costs) is bit for bit what it is without it.  A step skipped by
+        ``skip_nonfinite`` leaves the average alone.  ``decay`` None or 0 switches it off; changing ``decay`` / ``warmup`` while
+        it is on keeps the average.  ``averaged()`` / ``use_averaged`` run inference on the average, ``get_ema_params`` reads it,
+        ``save_model`` stores it (with ``decay`` and ``warmup``) and ``restore_model`` brings it back.  The call synchronises
+        the device."""
+        d, w = ema_fields(decay, warmup)
+        _capi.check(self._h, self._L.avae_set_ema(self._h, C.c_float(d), w), "avae_set_ema")
+
+    def get_ema_params(self):
+        """The averaged parameters, flat float32 in ``get_params``' order (an error while averaging is off)."""
+        out = np.empty(self.n_params, dtype=np.float32)
+        _capi.check(self._h, self._L.avae_get_ema(self._h, out.ctypes.data_as(C.c_void_p)), "avae_get_ema")
+        return out
+
+    def set_ema_params(self, flat):
+        """Replaces the averaged parameters (flat, ``get_params``' order; an error while averaging is off)."""
+        flat = np.ascontiguousarray(flat, dtype=np.float32).reshape(-1)
+        if flat.size != self.n_params:
+            raise ValueError("expected %d parameters, got %d" % (self.n_params, flat.size))
+        _capi.check(self._h, self._L.avae_set_ema_params(self._h, flat.ctypes.data_as(C.c_void_p)), "avae_set_ema_params")
+
+    def use_averaged(self, on=True):
+        """``on``: every inference call (``transform``, ``generate``, ``reconstruct``, ``score_samples``, ``log_likelihood``,
+        ``complete``, ``impute``, their masked twins) and ``evaluate_cost`` run on the averaged parameters from now on, and every
+        training call raises; ``on=False`` switches back to the live ones.  One launch that rebuilds the compute-dtype weights;
+        ``get_params`` keeps returning the live parameters.  ``set_params`` and ``restore_model`` leave the model on the live
+        parameters."""
+        _capi.check(self._h, self._L.avae_use_averaged(self._h, 1 if on else 0), "avae_use_averaged")
+
+    @contextlib.contextmanager
+    def averaged(self):
+        """``with model.averaged(): ...`` -- ``use_averaged(True)`` for the block, always switched back after it."""
+        self.use_averaged(True)
+        try:
+            yield self
+        finally:
+            self.use_averaged(False)
 
     def synchronize(self):
         _capi.check(self._h, self._L.avae_synchronize(self._h), "avae_synchronize")
@@ -910,7 +960,11 @@ def train(data_sets, network_architectures, binary=True, weights=1.0, assoc_lamb
     ``schedule=dict(kl=..., assoc=..., lr=..., unit='step')`` (``set_schedule``'s arguments) anneals the KL weight, ramps the
     association penalty and decays the learning rate on the device.  With ``unit='epoch'`` the knot steps, periods and
     ``decay_steps`` count epochs of this loop: they are multiplied by its ``total_batch = n_samples // (batch_size * world)``.
-    The validation cost of ``early_stop`` is the configured objective, whatever the schedule."""
+    The validation cost of ``early_stop`` is the configured objective, whatever the schedule.
+
+    ``ema=decay`` or ``ema=dict(decay=..., warmup=True)`` (``set_ema``'s arguments) keeps an exponential average of the parameters
+    on the device; use the returned model's ``averaged()`` for inference on it.  The validation cost of ``early_stop`` stays on
+    the live parameters."""
     schedule = model_kwargs.pop("schedule", None)
     # (a bad value raises before anything is built; train_loop converts again with the world size the model ends up with)
     schedule_kwargs(schedule, steps_per_epoch=int(data_sets.train._data.shape[0] / batch_size))
