@@ -511,6 +511,48 @@ int avae_impute(avae_handle* h, const float* const* x_dev, const int32_t* x_ld, 
                 int32_t rows, int32_t n_samples, const float* eps_dev,
                 float* mu_dev, float* logvar_dev, float* const* mean_dev, float* const* var_dev, void* stream);
 
+/* ---- cross-modal retrieval: fused latent distance + top-k (the reference's search cost is a distance of two latent codes evaluated
+ * one row at a time on the host, baxter_vae_assoc_writer.py:164-166; this is recall from a memory of encoded examples with no
+ * decoder in the loop, and what cross-modal recall@k is computed from).  Queries and gallery are posteriors as avae_encode writes
+ * them: device fp32 [rows, n_z] / [gallery_rows, n_z], dense.  Distance of query n and gallery row g, in fp32, the dimensions
+ * added in index order j = 0 .. n_z-1 to a sum that starts at +0.0f, with v = expf(lv), iv = expf(-lv) (the precise expf, formed once
+ * per row and tile), d = mu_q - mu_g, t = v_q - v_g:
+ *   AVAE_METRIC_L2     sum_j d*d                                               sum = fmaf(d, d, sum)
+ *   AVAE_METRIC_SYMKL  0.5 * sum_j [ (t*iv_q)*(t*iv_g) + (d*d)*(iv_q + iv_g) ]    sum = fmaf(t*iv_q, t*iv_g, sum); sum = fmaf(d*d, iv_q + iv_g, sum)
+ * SYMKL is KL(q_n||q_g) + KL(q_g||q_n), the assoc column of avae_score, rewritten through 0.5 (r + 1/r) - 1 = (v_q - v_g)^2 / (2 v_q v_g)
+ * so that every addend is non-negative (no "- n_z" to cancel against), two identical rows give exactly +0.0 and the sum overflows
+ * only where the true value does.  The value of a pair is a pure function of the two rows' bits, n_z and the metric: the same
+ * bits whichever tile, split or lane formed it, whatever rows, gallery_rows and k are.
+ * Result for query n: the first k gallery rows under the total order (isnan(dist), dist, index) ascending -- NaN distances rank
+ * behind +Inf, equal floats tie to the lower index.  index_dev [rows, k] int32 and dist_dev [rows, k] fp32, dense; either may be
+ * NULL.  A NaN distance is returned as the canonical quiet NaN.  k > gallery_rows fills the tail with index -1, dist +Inf (so
+ * gallery_rows == 0 gives nothing else); rows == 0 is a no-op.  With AVAE_METRIC_L2 both log-variance pointers may be NULL and are
+ * never read.  Errors (with a message): k < 1, k > AVAE_TOPK_MAX, an unknown metric, rows or gallery_rows < 0, a NULL mu (with rows
+ * / gallery_rows > 0), a NULL logvar under SYMKL.
+ * No atomics: the result does not depend on rows, on the split count or on the stream.  Two launches per chunk of queries, shaped
+ * by avae_latent_topk_plan: k_latent_topk on a grid of query tiles x gallery splits (each workgroup keeps the k best of its slice
+ * per query; the rows x gallery_rows matrix never exists in memory) and k_latent_topk_merge over the splits' lists.  The lists
+ * live in a scratch allocated by the first call (one allocation of the plan's upper bound, 40 MiB) and freed by avae_destroy;
+ * avae_workspace_bytes is unchanged.  As avae_score, the call changes nothing a training step reads, works on any replica with no
+ * collective, and inside avae_use_averaged (it only sees latents). */
+#define AVAE_METRIC_SYMKL 0
+#define AVAE_METRIC_L2    1
+#define AVAE_TOPK_MAX     64
+int avae_latent_topk(avae_handle* h,
+                     const float* q_mu_dev, const float* q_logvar_dev, int32_t rows,
+                     const float* g_mu_dev, const float* g_logvar_dev, int32_t gallery_rows,
+                     int32_t metric, int32_t k,
+                     int32_t* index_dev, float* dist_dev, void* stream);
+/* Host-only (no GPU): the launch shapes avae_latent_topk uses.  Queries go in chunks of chunk = min(rows, 16384) rows; per chunk
+ * k_latent_topk runs ceil(chunk / query_tile) x n_splits workgroups, split s covering the gallery tiles [s*T, min(tiles, (s+1)*T))
+ * of gallery_tile rows each, tiles = ceil(gallery_rows / gallery_tile), T = ceil(tiles / n_splits) -- no split is empty; few
+ * queries mean many splits, so that one query against a large gallery still occupies the device.  scratch_bytes = chunk *
+ * n_splits * k * 8, at most 40 MiB however many rows.  gallery_rows == 0: n_splits = 0.  Any output pointer may be NULL; k outside
+ * [1, AVAE_TOPK_MAX] and negative row counts are errors, the message in avae_last_error(NULL). */
+int avae_latent_topk_plan(const avae_config* cfg, int32_t rows, int32_t gallery_rows, int32_t k,
+                          int32_t* query_tile, int32_t* gallery_tile, int32_t* n_splits,
+                          size_t* scratch_bytes);
+
 /* save_model / restore_model (vae_assoc.py:427-463): own flat file (config echo + params + Adam
  * slots + step; with parameter averaging on also its settings and the average, see avae_set_ema);
  * TF .ckpt files cannot be read offline. */

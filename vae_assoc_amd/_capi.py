@@ -19,6 +19,9 @@ AVAE_MAX_WORLD = 8
 AVAE_IPC_HANDLE_BYTES = 128
 COMM_NONE, COMM_RCCL, COMM_IPC = 0, 1, 2
 SCORE_CROSS = 1
+METRIC_SYMKL, METRIC_L2 = 0, 1
+METRIC_IDS = {"symkl": METRIC_SYMKL, "l2": METRIC_L2}
+TOPK_MAX = 64
 
 ACT_IDS = {"identity": 0, "relu": 1, "softplus": 2, "sigmoid": 3, "tanh": 4}
 DTYPE_IDS = {"fp32": 0, "f32": 0, "float32": 0, "bf16": 1, "bfloat16": 1}
@@ -38,6 +41,7 @@ SYMBOLS = [
     "avae_set_grad_clip", "avae_grad_norm_history",
     "avae_set_schedule", "avae_schedule_value", "avae_hyper_history",
     "avae_set_ema", "avae_get_ema", "avae_set_ema_params", "avae_use_averaged",
+    "avae_latent_topk", "avae_latent_topk_plan",
     "avae_synchronize", "avae_timing_enable", "avae_timing_report", "avae_debug_fetch", "avae_comm_allreduce",
 ]
 
@@ -143,6 +147,9 @@ def lib():
             L.avae_complete.argtypes = [vp, C.POINTER(vp), C.POINTER(i32), C.POINTER(vp), vp, i32, i32, C.c_float, C.c_float,
                                         vp, vp, vp, C.POINTER(vp), vp]
             L.avae_impute.argtypes = [vp, C.POINTER(vp), C.POINTER(i32), vp, i32, i32, vp, vp, vp, C.POINTER(vp), C.POINTER(vp), vp]
+            L.avae_latent_topk.argtypes = [vp, vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp]
+            L.avae_latent_topk_plan.argtypes = [C.POINTER(Config), i32, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32),
+                                                C.POINTER(sz)]
             L.avae_save.argtypes = [vp, C.c_char_p]
             L.avae_load.argtypes = [vp, C.c_char_p]
             L.avae_synchronize.argtypes = [vp]

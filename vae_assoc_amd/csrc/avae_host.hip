@@ -2,6 +2,7 @@
 // (include/avae.h).  No per-step allocation: everything is carved once from one workspace.
 #include "avae_device.h"
 #include "avae_complete.h"
+#include "avae_retrieve.h"
 #include "../../include/avae.h"
 
 #include <dlfcn.h>
@@ -279,6 +280,7 @@ struct avae_handle {
     DevBuf iw_buf;                          // avae_loglik: z rows, r, log-weights, running log-sum-exp states of one pass
     DevBuf imp_buf;                         // avae_impute: fused [mu | lv] rows, z rows, r, the running (mean, M2) of one input row
     DevBuf row_pres;                        // masked scoring / impute: the chunk's staged presence bytes [batch_size][M]
+    DevBuf topk_buf;                        // avae_latent_topk: the (query, split) lists of one chunk of queries (kTopkScratchBytes)
     size_t off_chain = 0;
     size_t off_consts = 0, off_conv_tab = 0;   // 32 B {zeros | one, 0...}; device copy of conv_tab
     std::vector<ConvA> conv_tab;             // implicit patch matrices of the training plan
@@ -4178,6 +4180,66 @@ int avae_complete(avae_handle* h, const float* const* x_dev, const int32_t* x_ld
                 for (int i = 0; i < 3; ++i)
                     for (; left >= kCompleteSizes[i]; left -= kCompleteSizes[i]) HIP_OK(hipGraphLaunch(cp.g[i].exec, s));
             for (; left > 0; --left) complete_pass(h, cp, s);
+        }
+    });
+}
+
+// ---- cross-modal retrieval (include/avae.h, avae_retrieve.h)
+static void check_topk_shape(const std::string& w, int32_t rows, int32_t gallery_rows, int32_t k) {
+    if (k < 1 || k > AVAE_TOPK_MAX)
+        throw Err(w + ": k = " + std::to_string(k) + " must be in [1, " + std::to_string(AVAE_TOPK_MAX) + "] (AVAE_TOPK_MAX)");
+    if (rows < 0) throw Err(w + ": rows must be >= 0");
+    if (gallery_rows < 0) throw Err(w + ": gallery_rows must be >= 0");
+}
+
+int avae_latent_topk_plan(const avae_config* cfg, int32_t rows, int32_t gallery_rows, int32_t k, int32_t* query_tile,
+                          int32_t* gallery_tile, int32_t* n_splits, size_t* scratch_bytes) {
+    try {
+        if (!cfg) throw Err("null argument");
+        check_config(*cfg);
+        check_topk_shape("avae_latent_topk_plan", rows, gallery_rows, k);
+        const TopkPlan p = topk_plan(rows, gallery_rows, k);
+        if (query_tile) *query_tile = p.query_tile;
+        if (gallery_tile) *gallery_tile = p.gallery_tile;
+        if (n_splits) *n_splits = p.n_splits;
+        if (scratch_bytes) *scratch_bytes = p.scratch_bytes;
+        return 0;
+    } catch (const std::exception& e) { g_create_error = e.what(); return 2; }
+}
+
+int avae_latent_topk(avae_handle* h, const float* q_mu_dev, const float* q_logvar_dev, int32_t rows, const float* g_mu_dev,
+                     const float* g_logvar_dev, int32_t gallery_rows, int32_t metric, int32_t k, int32_t* index_dev,
+                     float* dist_dev, void* stream) {
+    return guarded(h, [&] {
+        const std::string w = "avae_latent_topk";
+        check_topk_shape(w, rows, gallery_rows, k);
+        if (metric != AVAE_METRIC_SYMKL && metric != AVAE_METRIC_L2)
+            throw Err(w + ": metric = " + std::to_string(metric) + " is neither AVAE_METRIC_SYMKL nor AVAE_METRIC_L2");
+        const bool kl = metric == AVAE_METRIC_SYMKL;
+        if (rows > 0 && !q_mu_dev) throw Err(w + ": q_mu_dev is NULL");
+        if (gallery_rows > 0 && !g_mu_dev) throw Err(w + ": g_mu_dev is NULL");
+        if (kl && rows > 0 && !q_logvar_dev) throw Err(w + ": q_logvar_dev is NULL (AVAE_METRIC_SYMKL reads the log-variances)");
+        if (kl && gallery_rows > 0 && !g_logvar_dev) throw Err(w + ": g_logvar_dev is NULL (AVAE_METRIC_SYMKL reads the log-variances)");
+        if (rows == 0 || (!index_dev && !dist_dev)) return;
+        static_assert(kTopkMaxNz >= 64, "check_config bounds n_z by 64");
+        const int nz = h->nz;
+        const TopkPlan p = topk_plan(rows, gallery_rows, k);
+        if (p.scratch_bytes > kTopkScratchBytes) throw Err("internal error: " + w + " plans more scratch than its bound");
+        hipStream_t s = on_stream(h, stream);
+        TopkArgs a;
+        std::memset(&a, 0, sizeof(a));
+        a.g_mu = g_mu_dev; a.g_lv = kl ? g_logvar_dev : nullptr;
+        a.gallery_rows = gallery_rows; a.nz = nz; a.k = k; a.metric = metric;
+        a.n_splits = p.n_splits; a.tiles_per_split = p.tiles_per_split;
+        if (p.n_splits > 0) a.part = static_cast<unsigned long long*>(h->topk_buf.ensure(kTopkScratchBytes));
+        for (int r0 = 0; r0 < rows; r0 += p.chunk_rows) {
+            a.rows = std::min(p.chunk_rows, rows - r0);
+            a.q_mu = q_mu_dev + (size_t)r0 * nz;
+            a.q_lv = kl ? q_logvar_dev + (size_t)r0 * nz : nullptr;
+            a.index = index_dev ? index_dev + (size_t)r0 * k : nullptr;
+            a.dist = dist_dev ? dist_dev + (size_t)r0 * k : nullptr;
+            if (p.n_splits > 0) timed_launch(h, s, "latent_topk", [&] { launch_latent_topk(a, s); });
+            timed_launch(h, s, "latent_topk_merge", [&] { launch_latent_topk_merge(a, s); });
         }
     });
 }

@@ -286,6 +286,37 @@ def impute_args(X, present, n_samples, eps, widths, n_z, device):
     return ts, rows, was_np, ptrs, lds, p, K, e
 
 
+def topk_args(query, gallery, k, metric, n_z, device):
+    """The arguments of ``latent_topk`` checked and marshalled -> (q_mu, q_logvar or None, g_mu, g_logvar or None, k, metric id,
+    was_numpy).  ``query`` and ``gallery`` are ``(mu, logvar)`` pairs of ``[rows, n_z]`` arrays or tensors; ``logvar`` may be None
+    under ``metric="l2"``, which never reads it.  Every shape, ``k`` or metric error is a ``ValueError`` raised here, ahead of any
+    launch; touches neither a model nor the library (``device="cpu"`` works)."""
+    if not isinstance(metric, str) or metric.lower() not in _capi.METRIC_IDS:
+        raise ValueError("metric must be 'symkl' or 'l2', got %r" % (metric,))
+    mid = _capi.METRIC_IDS[metric.lower()]
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= _capi.TOPK_MAX:
+        raise ValueError("k must be an integer in [1, %d], got %r" % (_capi.TOPK_MAX, k))
+    out, was_np = [], None
+    for name, pair in (("query", query), ("gallery", gallery)):
+        if not isinstance(pair, (tuple, list)) or len(pair) != 2:
+            raise ValueError("%s must be a (mu, logvar) pair, got %r" % (name, type(pair).__name__))
+        mu, lv = pair
+        if mu is None:
+            raise ValueError("%s: mu is None" % name)
+        if lv is None and mid == _capi.METRIC_SYMKL:
+            raise ValueError("%s: logvar is None, and metric='symkl' reads the log-variances (metric='l2' does not)" % name)
+        try:
+            t = dev_dense(mu, n_z, device, name="%s mu" % name)
+            if was_np is None:
+                was_np = not torch.is_tensor(mu)
+            rows = t.shape[0]
+            lt = None if mid == _capi.METRIC_L2 else dev_dense(lv, n_z, device, rows, "as mu", name="%s logvar" % name)
+        except ValueError as e:
+            raise ValueError("%s: %s" % (name, e))
+        out += [t, lt]
+    return out[0], out[1], out[2], out[3], int(k), mid, was_np
+
+
 class AssocVariationalAutoEncoder(object):
     """Associative VAE over M sensory modalities, trained on one MI355X (or one per rank).
 
@@ -714,6 +745,64 @@ class AssocVariationalAutoEncoder(object):
             return [self._encode(m, x) for m, x in enumerate(X)]
         assert sens_idx < len(self.network_architectures)
         return self._encode(sens_idx, X)
+
+    # ------------------------------------------------------------------ cross-modal retrieval
+    def posterior(self, X, sens_idx=None):
+        """``transform`` with the spread: the posterior ``(mu, logvar)`` of each modality, ``[rows, n_z]`` each -- what
+        ``latent_topk`` takes as a query or a gallery.  ``sens_idx`` is None (X = list over modalities, returns a list of pairs)
+        or an integer (X = one array, returns one pair).  ``mu`` is bitwise ``transform``'s output."""
+        if sens_idx is None:
+            return [self._encode(m, x, want_logvar=True) for m, x in enumerate(X)]
+        assert sens_idx < len(self.network_architectures)
+        return self._encode(sens_idx, X, want_logvar=True)
+
+    def latent_topk(self, query, gallery, k=1, metric="symkl"):
+        """The ``k`` nearest gallery posteriors of every query posterior, in one fused pass on the device (avae_latent_topk in
+        include/avae.h): the [N, G] distance matrix is never formed.
+
+        ``query`` and ``gallery`` are ``(mu, logvar)`` pairs as ``posterior`` returns them (``logvar`` may be None for
+        ``metric="l2"``).  ``metric="symkl"`` is KL(q_n || q_g) + KL(q_g || q_n), the divergence the association term trains on;
+        ``"l2"`` the squared distance of the means.  ``1 <= k <= 64``.  Returns ``dict(index=[N, k] int32, distance=[N, k]
+        float32)``, each row in ascending (isnan(distance), distance, index) order; ``k`` beyond the gallery pads with index -1,
+        distance +inf.  NumPy in gives NumPy out, tensors in give device tensors out."""
+        qm, ql, gm, gl, k, mid, was_np = topk_args(query, gallery, k, metric, self.n_z, self.device)
+        rows = qm.shape[0]
+        index = torch.empty((rows, k), dtype=torch.int32, device=self.device)
+        dist = self._new(rows, k)
+        if rows:
+            _capi.check(self._h, self._L.avae_latent_topk(self._h, qm.data_ptr(), ptr(ql), rows, gm.data_ptr(), ptr(gl), gm.shape[0],
+                                                          mid, k, index.data_ptr(), dist.data_ptr(), self._stream()),
+                        "avae_latent_topk")
+        conv = self._like_input(was_np)
+        return {"index": conv(index), "distance": conv(dist)}
+
+    def retrieve(self, X, sens_idx, gallery, k=1, metric="symkl"):
+        """Encode the rows ``X`` of modality ``sens_idx`` and look their posteriors up in ``gallery`` (a ``(mu, logvar)`` pair,
+        usually ``posterior`` of another modality's stored examples): ``latent_topk(posterior(X, sens_idx), gallery, k, metric)``."""
+        return self.latent_topk(self.posterior(X, sens_idx), gallery, k=k, metric=metric)
+
+    def retrieval_recall(self, X, ks=(1, 5, 10), metric="symkl"):
+        """Cross-modal recall@k of paired rows: ``X`` is a list over modalities with equal row counts, row n of every modality
+        belonging together.  Returns ``[M, M, len(ks)]`` float64: entry (s, d, i) is the share of rows n whose own partner --
+        row n of modality d's posteriors -- is among the ``ks[i]`` nearest of the query from modality s.  The diagonal is the
+        trivial self-retrieval (1.0 wherever the rows' posteriors are distinct).  ``max(ks) <= 64``."""
+        ks = [int(k) for k in ks]
+        if not ks or min(ks) < 1 or max(ks) > _capi.TOPK_MAX:
+            raise ValueError("ks must hold integers in [1, %d], got %r" % (_capi.TOPK_MAX, ks))
+        ts, rows, _, _, _ = dev_modalities(X, self._widths, self.device)
+        post = [self._encode(m, t, want_logvar=True) for m, t in enumerate(ts)]
+        M = len(post)
+        out = np.zeros((M, M, len(ks)), dtype=np.float64)
+        if not rows:
+            return out
+        own = torch.arange(rows, dtype=torch.int32, device=self.device)[:, None]
+        for s_ in range(M):
+            for d in range(M):
+                idx = self.latent_topk(post[s_], post[d], k=max(ks), metric=metric)["index"]
+                hit = idx == own                                     # [N, kmax]: at most one True per row
+                for i, k in enumerate(ks):
+                    out[s_, d, i] = float(hit[:, :k].any(dim=1).double().mean().item())
+        return out
 
     def generate(self, z_mu=None):
         """Generate data by sampling from latent space: decoder only, z fed directly; returns the
