@@ -553,6 +553,60 @@ int avae_latent_topk_plan(const avae_config* cfg, int32_t rows, int32_t gallery_
                           int32_t* query_tile, int32_t* gallery_tile, int32_t* n_splits,
                           size_t* scratch_bytes);
 
+/* ---- per-dimension posterior diagnostics: which latent dimensions are alive, where the encoders agree, how far the aggregate
+ * posterior is from the prior generate() samples from -- one fused pass over the posteriors of a data set.
+ * Inputs: the posteriors of n_mod modalities, 1 <= n_mod <= AVAE_MAX_MODALITIES (n_mod need not be the handle's modality count;
+ * n_z is the handle's):
+ *   mu_dev[m], logvar_dev[m]   device fp32 [rows, n_z], dense, as avae_encode writes them.  mu_dev[m] == NULL: modality m is
+ *                              absent from every row (logvar_dev[m] is then ignored)
+ *   present_dev                device uint8 [rows][n_mod], nonzero = row n has modality m, or NULL: every given modality on every row
+ * R_sd = the rows that have both s and d, R_mm the rows that have m.  Outputs (device, dense, any may be NULL and is then
+ * skipped; a NULL cov also skips the Gram, most of the arithmetic), fp64 except the count, defined in float64 arithmetic on the
+ * float32 inputs, means and (co)variances in the population form (divided by the count):
+ *   count    [n_mod][n_mod] int64   |R_sd|
+ *   mean     [n_mod][n_mod][n_z]    mean of mu_s[:, j] over R_sd
+ *   var      [n_mod][n_mod][n_z]    variance of mu_s[:, j] over R_sd; the diagonal [m][m] is the active-units statistic
+ *   xcov     [n_mod][n_mod][n_z]    covariance of mu_s[:, j] and mu_d[:, j] over R_sd; the diagonal equals var, bit for bit
+ *   assoc    [n_mod][n_mod][n_z]    mean over R_sd of 0.5 * [ (t*iv_s)*(t*iv_d) + (d*d)*(iv_s + iv_d) ], v = expf(lv), iv = expf(-lv),
+ *                                   t = v_s - v_d, d = mu_s - mu_d: the per-dimension addend of AVAE_METRIC_SYMKL; diagonal exactly 0
+ *   post_var [n_mod][n_z]           mean of expf(lv_m[:, j]) over R_mm
+ *   kl       [n_mod][n_z]           mean of 0.5 * (mu^2 + expf(lv) - lv - 1) over R_mm: the per-dimension KL to the prior
+ *   cov      [n_mod][n_z][n_z]      covariance matrix of mu_m over R_mm (aggregate posterior covariance = cov + diag(post_var))
+ * An empty set has count 0 and NaN everywhere else; rows == 0 is valid and writes exactly that.  A set of one row has var, xcov
+ * and cov exactly +0.0 and the row itself as mean.  Absent entries are selected away, never multiplied by 0 and never read: NaN /
+ * Inf / garbage there changes no bit of any output.  A non-finite value in a present entry (m, column j) changes only what column
+ * j of modality m enters by the definitions: [m][.][j] and [.][m][j] of the tables, post_var[m][j], kl[m][j], row j and column j
+ * of cov[m]; every other output keeps the bits it has with that value replaced by 0.
+ * Arithmetic: expf in fp32 (the precise one, once per element), everything else in fp64 on values shifted by the column's value in
+ * the first row of the set inside the slice, the slices' (count, mean, M2, co-moment) combined in slice order by Chan's formula: the
+ * accuracy does not depend on |mean| / std.  The Gram behind cov takes the shifted values rounded to fp32 as factors (products
+ * and sums in fp64).  No atomics, one fixed order of every sum: the result is a pure function of the input bits, rows, n_z and the
+ * flags -- the same on any stream and on repetition, all-ones flags give the bits of present_dev == NULL -- and the entries [s][d],
+ * [m] depend on modalities s, d (m) and their flag columns alone: a call on a subset of the modalities gives the same bits for
+ * the entries it shares with the full call (the row partition is a function of rows alone).
+ * Errors (with a message naming the argument, outputs untouched): n_mod outside [1, AVAE_MAX_MODALITIES], rows < 0, a NULL out, a
+ * NULL mu_dev array, a non-NULL mu_dev[m] with a NULL logvar_dev[m].  Asynchronous on `stream`.  Two launches, shaped by
+ * avae_latent_stats_plan: k_latent_stats on a grid of row slices x work items (one item per modality, one per pair s < d), one
+ * partial per (slice, item) to a scratch, and k_latent_stats_merge.  The scratch is allocated by the first call (one allocation
+ * of the plan's upper bound: 256 slices, 4 modalities, n_z = 64 -- 42,487,808 bytes) and freed by avae_destroy;
+ * avae_workspace_bytes is unchanged.  As avae_latent_topk, the call changes nothing a training step reads, works on any replica
+ * with no collective, and inside avae_use_averaged (it only sees latents). */
+typedef struct avae_latent_stats_out {      /* device pointers, dense, any may be NULL */
+    int64_t* count;
+    double *mean, *var, *xcov, *assoc, *post_var, *kl, *cov;
+} avae_latent_stats_out;
+int avae_latent_stats(avae_handle* h, int32_t n_mod,
+                      const float* const* mu_dev, const float* const* logvar_dev,
+                      const uint8_t* present_dev, int32_t rows,
+                      const avae_latent_stats_out* out, void* stream);
+/* Host-only (no GPU): the row partition avae_latent_stats uses, a function of rows alone.  Slice i covers the rows
+ * [i * row_tile, min(rows, (i + 1) * row_tile)); row_tile = max(256, ceil(rows / 256) rounded up to a multiple of 64), so there are
+ * at most 256 slices, none empty, and n_slices == 0 only for rows == 0.  scratch_bytes = n_slices * (M * (1 + 5 n_z + n_z^2) +
+ * M (M - 1) / 2 * (1 + 8 n_z)) * 8 for the configuration's M = n_modalities and n_z: at most 42,487,808.  Any output pointer may be
+ * NULL; rows < 0 is an error, the message in avae_last_error(NULL). */
+int avae_latent_stats_plan(const avae_config* cfg, int32_t rows, int32_t* row_tile, int32_t* n_slices,
+                           size_t* scratch_bytes);
+
 /* save_model / restore_model (vae_assoc.py:427-463): own flat file (config echo + params + Adam
  * slots + step; with parameter averaging on also its settings and the average, see avae_set_ema);
  * TF .ckpt files cannot be read offline. */

@@ -42,6 +42,7 @@ SYMBOLS = [
     "avae_set_schedule", "avae_schedule_value", "avae_hyper_history",
     "avae_set_ema", "avae_get_ema", "avae_set_ema_params", "avae_use_averaged",
     "avae_latent_topk", "avae_latent_topk_plan",
+    "avae_latent_stats", "avae_latent_stats_plan",
     "avae_synchronize", "avae_timing_enable", "avae_timing_report", "avae_debug_fetch", "avae_comm_allreduce",
 ]
 
@@ -79,6 +80,10 @@ class Schedule(C.Structure):
     _fields_ = [("kind", C.c_int32), ("n_knots", C.c_int32), ("period", C.c_int64),
                 ("knot_step", C.c_int64 * SCHED_MAX_KNOTS), ("knot_value", C.c_float * SCHED_MAX_KNOTS),
                 ("decay_rate", C.c_float), ("staircase", C.c_int32), ("decay_steps", C.c_int64)]
+
+
+class LatentStatsOut(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in ("count", "mean", "var", "xcov", "assoc", "post_var", "kl", "cov")]
 
 
 _lib = None
@@ -150,6 +155,8 @@ def lib():
             L.avae_latent_topk.argtypes = [vp, vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp]
             L.avae_latent_topk_plan.argtypes = [C.POINTER(Config), i32, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32),
                                                 C.POINTER(sz)]
+            L.avae_latent_stats.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(vp), vp, i32, C.POINTER(LatentStatsOut), vp]
+            L.avae_latent_stats_plan.argtypes = [C.POINTER(Config), i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(sz)]
             L.avae_save.argtypes = [vp, C.c_char_p]
             L.avae_load.argtypes = [vp, C.c_char_p]
             L.avae_synchronize.argtypes = [vp]

@@ -3,6 +3,7 @@
 #include "avae_device.h"
 #include "avae_complete.h"
 #include "avae_retrieve.h"
+#include "avae_latent_stats.h"
 #include "../../include/avae.h"
 
 #include <dlfcn.h>
@@ -281,6 +282,7 @@ struct avae_handle {
     DevBuf imp_buf;                         // avae_impute: fused [mu | lv] rows, z rows, r, the running (mean, M2) of one input row
     DevBuf row_pres;                        // masked scoring / impute: the chunk's staged presence bytes [batch_size][M]
     DevBuf topk_buf;                        // avae_latent_topk: the (query, split) lists of one chunk of queries (kTopkScratchBytes)
+    DevBuf stats_buf;                       // avae_latent_stats: one partial per (row slice, work item) (kStatsScratchBytes)
     size_t off_chain = 0;
     size_t off_consts = 0, off_conv_tab = 0;   // 32 B {zeros | one, 0...}; device copy of conv_tab
     std::vector<ConvA> conv_tab;             // implicit patch matrices of the training plan
@@ -4241,6 +4243,51 @@ int avae_latent_topk(avae_handle* h, const float* q_mu_dev, const float* q_logva
             if (p.n_splits > 0) timed_launch(h, s, "latent_topk", [&] { launch_latent_topk(a, s); });
             timed_launch(h, s, "latent_topk_merge", [&] { launch_latent_topk_merge(a, s); });
         }
+    });
+}
+
+// ---- per-dimension posterior diagnostics (include/avae.h, avae_latent_stats.h)
+int avae_latent_stats_plan(const avae_config* cfg, int32_t rows, int32_t* row_tile, int32_t* n_slices, size_t* scratch_bytes) {
+    try {
+        if (!cfg) throw Err("null argument");
+        check_config(*cfg);
+        if (rows < 0) throw Err("avae_latent_stats_plan: rows must be >= 0");
+        const StatsPlan p = stats_plan(rows);
+        if (row_tile) *row_tile = p.row_tile;
+        if (n_slices) *n_slices = p.n_slices;
+        if (scratch_bytes) *scratch_bytes = stats_scratch_bytes(p.n_slices, cfg->n_modalities, cfg->n_z);
+        return 0;
+    } catch (const std::exception& e) { g_create_error = e.what(); return 2; }
+}
+
+int avae_latent_stats(avae_handle* h, int32_t n_mod, const float* const* mu_dev, const float* const* logvar_dev,
+                      const uint8_t* present_dev, int32_t rows, const avae_latent_stats_out* out, void* stream) {
+    return guarded(h, [&] {
+        const std::string w = "avae_latent_stats";
+        if (n_mod < 1 || n_mod > AVAE_MAX_MODALITIES)
+            throw Err(w + ": n_mod = " + std::to_string(n_mod) + " must be in [1, " + std::to_string(AVAE_MAX_MODALITIES) + "] (AVAE_MAX_MODALITIES)");
+        if (rows < 0) throw Err(w + ": rows must be >= 0");
+        if (!out) throw Err(w + ": out is NULL");
+        if (!mu_dev) throw Err(w + ": mu_dev is NULL (the array of pointers; a NULL entry marks an absent modality)");
+        for (int m = 0; m < n_mod; ++m)
+            if (mu_dev[m] && (!logvar_dev || !logvar_dev[m]))
+                throw Err(w + ": logvar_dev[" + std::to_string(m) + "] is NULL while mu_dev[" + std::to_string(m) + "] is given");
+        if (!out->count && !out->mean && !out->var && !out->xcov && !out->assoc && !out->post_var && !out->kl && !out->cov) return;
+        static_assert(kStatsMaxNz >= 64 && kMaxMod == AVAE_MAX_MODALITIES, "check_config bounds n_z by 64");
+        const StatsPlan p = stats_plan(rows);
+        if (stats_scratch_bytes(p.n_slices, n_mod, h->nz) > kStatsScratchBytes)
+            throw Err("internal error: " + w + " plans more scratch than its bound");
+        hipStream_t s = on_stream(h, stream);
+        StatsArgs a;
+        std::memset(&a, 0, sizeof(a));
+        for (int m = 0; m < n_mod; ++m) { a.mu[m] = mu_dev[m]; a.lv[m] = mu_dev[m] ? logvar_dev[m] : nullptr; }
+        a.present = present_dev; a.rows = rows; a.n_mod = n_mod; a.nz = h->nz;
+        a.n_slices = p.n_slices; a.row_tile = p.row_tile; a.want_cov = out->cov ? 1 : 0; a.out = *out;
+        if (p.n_slices > 0) {
+            a.scratch = static_cast<double*>(h->stats_buf.ensure(kStatsScratchBytes));
+            timed_launch(h, s, "latent_stats", [&] { launch_latent_stats(a, s); });
+        }
+        timed_launch(h, s, "latent_stats_merge", [&] { launch_latent_stats_merge(a, s); });
     });
 }
 

@@ -317,6 +317,47 @@ def topk_args(query, gallery, k, metric, n_z, device):
     return out[0], out[1], out[2], out[3], int(k), mid, was_np
 
 
+def latent_stats_args(posteriors, present, n_z, device):
+    """The arguments of ``latent_stats`` checked and marshalled -> (mus, logvars, rows, presence or None, was_numpy): two lists
+    over the modalities of ``[rows, n_z]`` tensors, None where the modality is absent everywhere.  ``posteriors`` is a list of 1 to
+    4 ``(mu, logvar)`` pairs or None; ``present`` [rows, M] flags or None.  Every shape error is a ``ValueError`` raised here, ahead
+    of any launch; touches neither a model nor the library (``device="cpu"`` works)."""
+    if not isinstance(posteriors, (list, tuple)) or not 1 <= len(posteriors) <= _capi.AVAE_MAX_MODALITIES:
+        raise ValueError("posteriors must be a list over 1 to %d modalities of (mu, logvar) pairs or None, got %r"
+                         % (_capi.AVAE_MAX_MODALITIES, type(posteriors).__name__ if not isinstance(posteriors, (list, tuple))
+                            else len(posteriors)))
+    M = len(posteriors)
+    p = None if present is None else dev_flags(present, M, device)
+    rows, what = (None, None) if p is None else (int(p.shape[0]), "as present")
+    mus, lvs, was_np = [], [], None
+    for m, pair in enumerate(posteriors):
+        if pair is None:
+            mus.append(None)
+            lvs.append(None)
+            continue
+        if not isinstance(pair, (tuple, list)) or len(pair) != 2:
+            raise ValueError("posteriors[%d] must be a (mu, logvar) pair or None, got %r" % (m, type(pair).__name__))
+        mu, lv = pair
+        if mu is None:
+            raise ValueError("posteriors[%d]: mu is None (None in place of the pair marks a modality absent everywhere)" % m)
+        if lv is None:
+            raise ValueError("posteriors[%d]: logvar is None: a mu needs its logvar" % m)
+        try:
+            t = dev_dense(mu, n_z, device, rows, what, name="mu")
+            if rows is None:
+                rows, what = t.shape[0], "as posteriors[%d]" % m
+            lt = dev_dense(lv, n_z, device, rows, "as mu", name="logvar")
+        except ValueError as e:
+            raise ValueError("posteriors[%d]: %s" % (m, e))
+        if was_np is None:
+            was_np = not torch.is_tensor(mu)
+        mus.append(t)
+        lvs.append(lt)
+    if rows is None:
+        raise ValueError("every modality is None and there is no present array: the row count is unknown")
+    return mus, lvs, rows, p, (not torch.is_tensor(present)) if was_np is None else was_np
+
+
 class AssocVariationalAutoEncoder(object):
     """Associative VAE over M sensory modalities, trained on one MI355X (or one per rank).
 
@@ -803,6 +844,60 @@ class AssocVariationalAutoEncoder(object):
                 for i, k in enumerate(ks):
                     out[s_, d, i] = float(hit[:, :k].any(dim=1).double().mean().item())
         return out
+
+    # ------------------------------------------------------------------ posterior diagnostics
+    STATS_SHAPES = (("count", "MM"), ("mean", "MMz"), ("var", "MMz"), ("xcov", "MMz"), ("assoc", "MMz"), ("post_var", "Mz"),
+                    ("kl", "Mz"), ("cov", "Mzz"))
+
+    def latent_stats(self, posteriors, present=None):
+        """Per-dimension statistics of a data set's posteriors, in one fused pass on the device (avae_latent_stats in
+        include/avae.h): which latent dimensions are alive, where the encoders agree, how far the aggregate posterior is from the
+        prior.
+
+        ``posteriors`` is a list over modalities of ``(mu, logvar)`` pairs as ``posterior`` returns them, or None for a modality
+        absent everywhere; ``present`` an [N, M] bool / integer array or tensor, or None (every given modality on every row).
+        With R_sd the rows that have both s and d, returns a dict of float64 arrays (and one int64 count), population form:
+        ``count [M, M]`` = |R_sd|; ``mean`` / ``var [M, M, n_z]`` of mu_s over R_sd (``var[m, m]`` is the active-units statistic);
+        ``xcov [M, M, n_z]`` the covariance of mu_s and mu_d; ``assoc [M, M, n_z]`` the mean per-dimension symmetric KL of the two
+        posteriors; ``post_var`` / ``kl [M, n_z]`` the mean of exp(logvar_m) and of the per-dimension KL to the prior;
+        ``cov [M, n_z, n_z]`` the covariance matrix of mu_m.  An empty set gives count 0 and NaN.  The result is bit-reproducible
+        and its accuracy does not depend on |mean| / std.  NumPy in gives NumPy out, tensors in give device tensors out."""
+        mus, lvs, rows, p, was_np = latent_stats_args(posteriors, present, self.n_z, self.device)
+        dims = {"M": len(mus), "z": self.n_z}
+        res = {name: torch.empty([dims[c] for c in shape], dtype=torch.int64 if name == "count" else torch.float64, device=self.device)
+               for name, shape in self.STATS_SHAPES}
+        out = _capi.LatentStatsOut(**{name: t.data_ptr() for name, t in res.items()})
+        _capi.check(self._h, self._L.avae_latent_stats(self._h, len(mus), self._ptrs(mus), self._ptrs(lvs), ptr(p), rows,
+                                                       C.byref(out), self._stream()), "avae_latent_stats")
+        conv = self._like_input(was_np)
+        return {name: conv(t) for name, t in res.items()}
+
+    def latent_diagnostics(self, X, present=None, au_threshold=0.01):
+        """Encode ``X`` (a list over modalities; ``X[m] = None`` is a modality absent everywhere) and diagnose the posteriors:
+        ``latent_stats`` of them plus ``active [M, n_z]`` bool = ``var[m, m] > au_threshold`` (the active units of Burda et al.),
+        ``active_units [M]`` their number, ``corr [M, M, n_z]`` = ``xcov[s, d] / sqrt(var[s, d] * var[d, s])`` (NaN where a
+        variance is 0) and ``agg_cov [M, n_z, n_z]`` = ``cov + diag(post_var)``, the aggregate posterior's covariance.  Inside
+        ``with model.averaged():`` it diagnoses the averaged encoders."""
+        if len(X) != len(self._widths):
+            raise ValueError("expected a list of %d modalities, got %d" % (len(self._widths), len(X)))
+        post, was_np = [], None
+        for m, x in enumerate(X):
+            if x is None:
+                post.append(None)
+                continue
+            t, np_in = dev_array(x, self._widths[m], self.device)
+            was_np = np_in if was_np is None else was_np
+            post.append(self._encode(m, t, want_logvar=True))
+        st = self.latent_stats(post, None if present is None else dev_flags(present, len(X), self.device))
+        M = len(X)
+        own = st["var"][torch.arange(M), torch.arange(M)]
+        st["active"] = own > au_threshold
+        st["active_units"] = st["active"].sum(dim=1)
+        prod = st["var"] * st["var"].transpose(0, 1)
+        st["corr"] = torch.where(prod > 0, st["xcov"] / torch.sqrt(prod), torch.full_like(prod, float("nan")))
+        st["agg_cov"] = st["cov"] + torch.diag_embed(st["post_var"])
+        conv = self._like_input(not torch.is_tensor(present) if was_np is None else was_np)
+        return {name: conv(t) for name, t in st.items()}
 
     def generate(self, z_mu=None):
         """Generate data by sampling from latent space: decoder only, z fed directly; returns the
