@@ -607,6 +607,56 @@ int avae_latent_stats(avae_handle* h, int32_t n_mod,
 int avae_latent_stats_plan(const avae_config* cfg, int32_t rows, int32_t* row_tile, int32_t* n_slices,
                            size_t* scratch_bytes);
 
+/* ---- aggregate-posterior log-density: log q_agg(z), q_agg(z) = 1/G' sum_g q(z | x_g), the mixture of a gallery's posteriors, and
+ * its per-dimension marginals, as one streamed log-sum-exp.  It is what the ELBO decomposition KL = index-code
+ * MI + total correlation + dimension-wise KL (Hoffman & Johnson 2016, Chen et al. 2018), the divergence of two encoders' aggregate
+ * posteriors and a leave-one-out novelty score are computed from.
+ *   z_dev                    query points, device fp32 [rows, n_z], dense
+ *   g_mu_dev, g_logvar_dev   the gallery's posteriors as avae_encode writes them, device fp32 [gallery_rows, n_z], dense
+ *   exclude_dev              device int32 [rows] or NULL.  E_n = the gallery rows counted for query n: every row, minus row
+ *                            exclude[n] when 0 <= exclude[n] < gallery_rows (any other value excludes nothing); G' = |E_n|
+ *   joint_dev                device fp32 [rows] or NULL;  marginal_dev  device fp32 [rows, n_z] or NULL
+ * With c = 0.5 log(2 pi):
+ *   l(n,g,j)      = -0.5 (lv_gj + (z_nj - mu_gj)^2 exp(-lv_gj))
+ *   marginal[n,j] = log sum_{g in E_n} exp(l(n,g,j))        - log G' - c
+ *   joint[n]      = log sum_{g in E_n} exp(sum_j l(n,g,j))  - log G' - n_z c
+ * Arithmetic: iv = expf(-lv) (the precise expf, formed once per gallery element while staging), d = z - mu,
+ * l = -0.5f * fmaf(d*d, iv, lv) (evaluated as fmaf(d*d, -0.5f*iv, -0.5f*lv): the same bits, a scaling by a power of two); the joint
+ * exponent is the sum of l over j = 0 .. n_z-1 in index order, added to +0.0f.  The log-sum-exp is a running (max, sum scaled by it)
+ * in fp32 per query and per column: gallery rows join in blocks of 8 -- rows [8b, 8b+8) of the gallery -- the block's max against
+ * the running max, one rescale, the 8 exponentials exp(l - max) added in row order; the exponential inside the sums is the hardware
+ * exp2 on the argument times log2(e).  Marginals take the blocks of a slice in order; the joint keeps one running pair per block
+ * position b mod 8 and combines the 8 in position order when the slice is done.  The merge launch combines the slices' pairs in
+ * slice order in fp64, subtracts log G' and the constant in fp64 and rounds once to fp32.
+ * Edges, by the definition: a query whose every term is -Inf gives -Inf, not NaN; a gallery row with lv = +Inf contributes 0;
+ * G' = 0 (gallery_rows == 0, or gallery_rows == 1 with that row excluded) gives NaN, "no estimate"; rows == 0 is a no-op.  A NaN at
+ * gallery (g, j) makes marginal[n, j] and joint[n] NaN for every query that counts row g and changes no other output bit; a NaN at
+ * z[n, j] changes marginal[n, j] and joint[n] only.  An excluded row is selected away, never multiplied by 0: NaN / Inf / garbage in
+ * it changes no bit of that query's outputs.  A NULL marginal_dev skips the per-dimension sums (n_z of the n_z + 1 exponentials per
+ * pair), a NULL joint_dev the joint sum; both NULL is an error.
+ * Errors (with a message naming the argument, outputs untouched): rows or gallery_rows < 0, a NULL z_dev with rows > 0, a NULL
+ * g_mu_dev or g_logvar_dev with gallery_rows > 0, joint_dev and marginal_dev both NULL.
+ * No atomics; the gallery partition is a function of gallery_rows alone: the result for a query does not depend on rows, on the
+ * query's position in the call, on the stream or on repetition, and joint is the same bits with or without marginal_dev (and the
+ * other way round).  Two launches per chunk of queries, shaped by avae_agg_logpdf_plan: k_agg_logpdf on a grid of query tiles x
+ * gallery slices and k_agg_logpdf_merge.  The slices' pairs live in a scratch allocated by the first call (one allocation of the
+ * plan's upper bound, 68,157,440 bytes) and freed by avae_destroy; avae_workspace_bytes is unchanged.  As avae_latent_topk, the call
+ * changes nothing a training step reads, works on any replica with no collective, and inside avae_use_averaged (it only sees
+ * latents). */
+int avae_agg_logpdf(avae_handle* h,
+                    const float* z_dev, int32_t rows,
+                    const float* g_mu_dev, const float* g_logvar_dev, int32_t gallery_rows,
+                    const int32_t* exclude_dev,
+                    float* joint_dev, float* marginal_dev, void* stream);
+/* Host-only (no GPU): the launch shapes avae_agg_logpdf uses.  slice_rows = max(1024, ceil(gallery_rows / 64) rounded up to a
+ * multiple of 64) and n_slices = ceil(gallery_rows / slice_rows) -- at most 64 slices, none empty, a function of gallery_rows alone;
+ * gallery_rows == 0: n_slices = 0.  Queries go in chunks of chunk_rows = min(rows, 2048); per chunk k_agg_logpdf runs
+ * ceil(chunk / query_tile) x n_slices workgroups.  scratch_bytes = chunk_rows * n_slices * (1 + n_z) * 8 for the configuration's
+ * n_z: at most 68,157,440.  Any output pointer may be NULL; negative row counts are errors, the message in avae_last_error(NULL). */
+int avae_agg_logpdf_plan(const avae_config* cfg, int32_t rows, int32_t gallery_rows,
+                         int32_t* query_tile, int32_t* chunk_rows, int32_t* slice_rows, int32_t* n_slices,
+                         size_t* scratch_bytes);
+
 /* save_model / restore_model (vae_assoc.py:427-463): own flat file (config echo + params + Adam
  * slots + step; with parameter averaging on also its settings and the average, see avae_set_ema);
  * TF .ckpt files cannot be read offline. */

@@ -43,6 +43,7 @@ SYMBOLS = [
     "avae_set_ema", "avae_get_ema", "avae_set_ema_params", "avae_use_averaged",
     "avae_latent_topk", "avae_latent_topk_plan",
     "avae_latent_stats", "avae_latent_stats_plan",
+    "avae_agg_logpdf", "avae_agg_logpdf_plan",
     "avae_synchronize", "avae_timing_enable", "avae_timing_report", "avae_debug_fetch", "avae_comm_allreduce",
 ]
 
@@ -157,6 +158,9 @@ def lib():
                                                 C.POINTER(sz)]
             L.avae_latent_stats.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(vp), vp, i32, C.POINTER(LatentStatsOut), vp]
             L.avae_latent_stats_plan.argtypes = [C.POINTER(Config), i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(sz)]
+            L.avae_agg_logpdf.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, vp, vp]
+            L.avae_agg_logpdf_plan.argtypes = [C.POINTER(Config), i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32),
+                                               C.POINTER(i32), C.POINTER(sz)]
             L.avae_save.argtypes = [vp, C.c_char_p]
             L.avae_load.argtypes = [vp, C.c_char_p]
             L.avae_synchronize.argtypes = [vp]

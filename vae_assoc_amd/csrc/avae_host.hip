@@ -4,6 +4,7 @@
 #include "avae_complete.h"
 #include "avae_retrieve.h"
 #include "avae_latent_stats.h"
+#include "avae_aggpost.h"
 #include "../../include/avae.h"
 
 #include <dlfcn.h>
@@ -283,6 +284,7 @@ struct avae_handle {
     DevBuf row_pres;                        // masked scoring / impute: the chunk's staged presence bytes [batch_size][M]
     DevBuf topk_buf;                        // avae_latent_topk: the (query, split) lists of one chunk of queries (kTopkScratchBytes)
     DevBuf stats_buf;                       // avae_latent_stats: one partial per (row slice, work item) (kStatsScratchBytes)
+    DevBuf agg_buf;                         // avae_agg_logpdf: the (query, slice, column) pairs of one chunk of queries (kAggScratchBytes)
     size_t off_chain = 0;
     size_t off_consts = 0, off_conv_tab = 0;   // 32 B {zeros | one, 0...}; device copy of conv_tab
     std::vector<ConvA> conv_tab;             // implicit patch matrices of the training plan
@@ -4288,6 +4290,61 @@ int avae_latent_stats(avae_handle* h, int32_t n_mod, const float* const* mu_dev,
             timed_launch(h, s, "latent_stats", [&] { launch_latent_stats(a, s); });
         }
         timed_launch(h, s, "latent_stats_merge", [&] { launch_latent_stats_merge(a, s); });
+    });
+}
+
+// ---- aggregate-posterior log-density (include/avae.h, avae_aggpost.h)
+static void check_agg_shape(const std::string& w, int32_t rows, int32_t gallery_rows) {
+    if (rows < 0) throw Err(w + ": rows must be >= 0");
+    if (gallery_rows < 0) throw Err(w + ": gallery_rows must be >= 0");
+}
+
+int avae_agg_logpdf_plan(const avae_config* cfg, int32_t rows, int32_t gallery_rows, int32_t* query_tile, int32_t* chunk_rows,
+                         int32_t* slice_rows, int32_t* n_slices, size_t* scratch_bytes) {
+    try {
+        if (!cfg) throw Err("null argument");
+        check_config(*cfg);
+        check_agg_shape("avae_agg_logpdf_plan", rows, gallery_rows);
+        const AggPlan p = agg_plan(rows, gallery_rows);
+        if (query_tile) *query_tile = p.query_tile;
+        if (chunk_rows) *chunk_rows = p.chunk_rows;
+        if (slice_rows) *slice_rows = p.slice_rows;
+        if (n_slices) *n_slices = p.n_slices;
+        if (scratch_bytes) *scratch_bytes = agg_scratch_bytes(p, cfg->n_z);
+        return 0;
+    } catch (const std::exception& e) { g_create_error = e.what(); return 2; }
+}
+
+int avae_agg_logpdf(avae_handle* h, const float* z_dev, int32_t rows, const float* g_mu_dev, const float* g_logvar_dev,
+                    int32_t gallery_rows, const int32_t* exclude_dev, float* joint_dev, float* marginal_dev, void* stream) {
+    return guarded(h, [&] {
+        const std::string w = "avae_agg_logpdf";
+        check_agg_shape(w, rows, gallery_rows);
+        if (rows > 0 && !z_dev) throw Err(w + ": z_dev is NULL");
+        if (gallery_rows > 0 && !g_mu_dev) throw Err(w + ": g_mu_dev is NULL");
+        if (gallery_rows > 0 && !g_logvar_dev) throw Err(w + ": g_logvar_dev is NULL");
+        if (!joint_dev && !marginal_dev) throw Err(w + ": joint_dev and marginal_dev are both NULL");
+        if (rows == 0) return;
+        static_assert(kAggMaxNz >= 64, "check_config bounds n_z by 64");
+        const int nz = h->nz;
+        const AggPlan p = agg_plan(rows, gallery_rows);
+        if (agg_scratch_bytes(p, nz) > kAggScratchBytes || agg_lds_bytes(nz) > 160 * 1024)
+            throw Err("internal error: " + w + " plans more scratch or LDS than its bound");
+        hipStream_t s = on_stream(h, stream);
+        AggArgs a;
+        std::memset(&a, 0, sizeof(a));
+        a.g_mu = g_mu_dev; a.g_lv = g_logvar_dev; a.gallery_rows = gallery_rows; a.nz = nz;
+        a.n_slices = p.n_slices; a.slice_rows = p.slice_rows;
+        if (p.n_slices > 0) a.part = static_cast<float2*>(h->agg_buf.ensure(kAggScratchBytes));
+        for (int r0 = 0; r0 < rows; r0 += p.chunk_rows) {
+            a.rows = std::min(p.chunk_rows, rows - r0);
+            a.z = z_dev + (size_t)r0 * nz;
+            a.exclude = exclude_dev ? exclude_dev + r0 : nullptr;
+            a.joint = joint_dev ? joint_dev + r0 : nullptr;
+            a.marginal = marginal_dev ? marginal_dev + (size_t)r0 * nz : nullptr;
+            if (p.n_slices > 0) timed_launch(h, s, "agg_logpdf", [&] { launch_agg_logpdf(a, s); });
+            timed_launch(h, s, "agg_logpdf_merge", [&] { launch_agg_logpdf_merge(a, s); });
+        }
     });
 }
 

@@ -317,6 +317,36 @@ def topk_args(query, gallery, k, metric, n_z, device):
     return out[0], out[1], out[2], out[3], int(k), mid, was_np
 
 
+def agg_args(z, gallery, exclude, marginals, n_z, device):
+    """The arguments of ``aggregate_log_density`` checked and marshalled -> (z, g_mu, g_logvar, exclude or None, marginals,
+    was_numpy).  ``z`` is ``[N, n_z]``, ``gallery`` a ``(mu, logvar)`` pair of ``[G, n_z]`` arrays or tensors, ``exclude`` None or
+    ``[N]`` integers.  Every shape or type error is a ``ValueError`` raised here, ahead of any launch; touches neither a model nor
+    the library (``device="cpu"`` works)."""
+    if z is None:
+        raise ValueError("z is None")
+    if not isinstance(gallery, (tuple, list)) or len(gallery) != 2:
+        raise ValueError("gallery must be a (mu, logvar) pair, got %r" % type(gallery).__name__)
+    mu, lv = gallery
+    if mu is None or lv is None:
+        raise ValueError("gallery: %s is None: the density reads both" % ("mu" if mu is None else "logvar"))
+    zt = dev_dense(z, n_z, device, name="z")
+    try:
+        gm = dev_dense(mu, n_z, device, name="mu")
+        gl = dev_dense(lv, n_z, device, gm.shape[0], "as mu", name="logvar")
+    except ValueError as e:
+        raise ValueError("gallery: %s" % e)
+    ex = None
+    if exclude is not None:
+        ex = torch.as_tensor(exclude if torch.is_tensor(exclude) else np.asarray(exclude))
+        if ex.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
+            raise ValueError("exclude must hold integers (gallery row numbers), got %s" % ex.dtype)
+        if tuple(ex.shape) != (zt.shape[0],):
+            raise ValueError("exclude must be [%d] (one gallery row per row of z), got %s" % (zt.shape[0], tuple(ex.shape)))
+        big = torch.iinfo(torch.int32).max
+        ex = ex.to(device=device, dtype=torch.int64).clamp(-1, big).to(torch.int32).contiguous()      # (anything outside the gallery excludes nothing)
+    return zt, gm, gl, ex, bool(marginals), not torch.is_tensor(z)
+
+
 def latent_stats_args(posteriors, present, n_z, device):
     """The arguments of ``latent_stats`` checked and marshalled -> (mus, logvars, rows, presence or None, was_numpy): two lists
     over the modalities of ``[rows, n_z]`` tensors, None where the modality is absent everywhere.  ``posteriors`` is a list of 1 to
@@ -898,6 +928,90 @@ class AssocVariationalAutoEncoder(object):
         st["agg_cov"] = st["cov"] + torch.diag_embed(st["post_var"])
         conv = self._like_input(not torch.is_tensor(present) if was_np is None else was_np)
         return {name: conv(t) for name, t in st.items()}
+
+    # ------------------------------------------------------------------ aggregate posterior
+    def aggregate_log_density(self, z, gallery, exclude=None, marginals=True):
+        """``log q_agg(z)`` of every row of ``z`` under the aggregate posterior of a gallery, ``q_agg(z) = 1/G sum_g q(z | x_g)``,
+        in one fused pass on the device (avae_agg_logpdf in include/avae.h): the [N, G, n_z] tensor of exponents is never formed.
+
+        ``z`` is ``[N, n_z]``; ``gallery`` a ``(mu, logvar)`` pair as ``posterior`` returns it; ``exclude`` None or ``[N]``
+        integers: gallery row ``exclude[n]`` is left out of query n's mixture (leave-one-out; a value outside ``[0, G)`` leaves
+        nothing out).  Returns ``dict(joint=[N] float32, marginal=[N, n_z] float32)``: the log-density of the mixture and of its
+        per-dimension marginals; ``marginal`` is None with ``marginals=False``, which skips most of the work.  An empty mixture
+        gives NaN.  The result is bit-reproducible and a query's value does not depend on the other queries.  NumPy in gives
+        NumPy out, tensors in give device tensors out."""
+        zt, gm, gl, ex, marg, was_np = agg_args(z, gallery, exclude, marginals, self.n_z, self.device)
+        rows = zt.shape[0]
+        joint = torch.empty((rows,), dtype=torch.float32, device=self.device)
+        marginal = self._new(rows, self.n_z) if marg else None
+        if rows:
+            _capi.check(self._h, self._L.avae_agg_logpdf(self._h, zt.data_ptr(), rows, ptr(gm), ptr(gl), gm.shape[0], ptr(ex),
+                                                         joint.data_ptr(), ptr(marginal), self._stream()), "avae_agg_logpdf")
+        conv = self._like_input(was_np)
+        return {"joint": conv(joint), "marginal": conv(marginal) if marg else None}
+
+    def elbo_decomposition(self, X, n_samples=1, eps=None, seed=0, leave_one_out=False):
+        """Where the KL term of the ELBO goes (Hoffman & Johnson 2016; Chen et al. 2018): per modality,
+        ``kl = mi + tc + sum_j dimwise_kl`` with the aggregate posterior ``q_agg^m`` of the rows of ``X[m]`` -- plus how far apart
+        the encoders' aggregate posteriors are.
+
+        ``X`` is a list over modalities with equal row counts N; ``X[m] = None`` makes that modality's entries NaN.  Every given
+        modality is encoded once; ``z^m = mu_m + exp(0.5 logvar_m) * eps`` for ``n_samples`` draws per row, ``eps``
+        ``[n_samples, N, n_z]`` shared by the modalities as a training step shares its draw (None: drawn on the device from
+        ``seed``).  Returns float64, means over the ``n_samples * N`` samples:
+        ``kl [M]`` of ``log q(z|x) - log p(z)``; ``mi [M]`` of ``log q(z|x) - log q_agg(z)``, the index-code mutual information;
+        ``tc [M]`` of ``log q_agg(z) - sum_j log q_agg,j(z_j)``, the total correlation; ``dimwise_kl [M, n_z]`` of
+        ``log q_agg,j(z_j) - log p(z_j)``; ``marginal_kl [M]`` = ``tc + sum_j dimwise_kl``, the estimate of KL(q_agg || p);
+        ``cross [M, M]``: ``cross[s, d]`` the mean of ``log q_agg^s(z^s) - log q_agg^d(z^s)``, the estimate of
+        KL(q_agg^s || q_agg^d), diagonal exactly 0; ``log_n`` = log N.
+
+        Without ``leave_one_out`` the mixture counts the sample's own posterior: the standard form of the estimator, biased
+        towards ``mi -> log N`` (its ceiling) when the posteriors hardly overlap.  ``leave_one_out=True`` leaves row n's own
+        posterior out of the mixtures its samples are scored under.  Inside ``with model.averaged():`` it decomposes the averaged
+        encoders; on a data-parallel replica it covers the local rows."""
+        if isinstance(n_samples, bool) or not isinstance(n_samples, (int, np.integer)) or n_samples < 1:
+            raise ValueError("n_samples must be an integer >= 1, got %r" % (n_samples,))
+        S, nz = int(n_samples), self.n_z
+        ts, N, was_np, _, _ = dev_modalities(X, self._widths, self.device, allow_none=True)
+        if N is None:
+            raise ValueError("every modality is None: the row count is unknown")
+        e = dev_dense3(eps, (S, N, nz), self.device)
+        if e is None:
+            gen = torch.Generator(device=self.device)
+            gen.manual_seed(int(seed))
+            e = torch.randn((S, N, nz), generator=gen, device=self.device, dtype=torch.float32)
+        M, c = len(ts), 0.5 * float(np.log(2.0 * np.pi))
+        post = [None if t is None else self._encode(m, t, want_logvar=True) for m, t in enumerate(ts)]
+        own = torch.arange(N, dtype=torch.int32, device=self.device).repeat(S) if leave_one_out else None
+        nan = float("nan")
+        a = torch.full((M,), nan, dtype=torch.float64, device=self.device)          # mean log q(z|x)
+        b = torch.full((M, M), nan, dtype=torch.float64, device=self.device)        # b[s, d]: mean log q_agg^d(z^s)
+        cj = torch.full((M, nz), nan, dtype=torch.float64, device=self.device)      # mean log q_agg,j^s(z^s_j)
+        pj = torch.full((M, nz), nan, dtype=torch.float64, device=self.device)      # mean log p(z^s_j)
+        e64 = e.double()
+        for s_ in range(M):
+            if post[s_] is None:
+                continue
+            mu, lv = post[s_][0].double(), post[s_][1].double()
+            z64 = (mu[None] + torch.exp(0.5 * lv)[None] * e64).reshape(S * N, nz)
+            z = z64.float()
+            a[s_] = (-0.5 * e64 * e64 - 0.5 * lv[None] - c).sum(dim=2).mean() if S * N else nan
+            pj[s_] = (-0.5 * z64 * z64 - c).mean(dim=0)
+            for d in range(M):
+                if post[d] is None:
+                    continue
+                r = self.aggregate_log_density(z, post[d], exclude=own, marginals=(d == s_))
+                b[s_, d] = r["joint"].double().mean()
+                if d == s_:
+                    cj[s_] = r["marginal"].double().mean(dim=0)
+        own_b = torch.diagonal(b)
+        out = {"kl": a - pj.sum(dim=1), "mi": a - own_b, "tc": own_b - cj.sum(dim=1), "dimwise_kl": cj - pj}
+        out["marginal_kl"] = out["tc"] + out["dimwise_kl"].sum(dim=1)
+        out["cross"] = own_b[:, None] - b
+        conv = self._like_input(bool(was_np))
+        out = {name: conv(t) for name, t in out.items()}
+        out["log_n"] = float(np.log(N)) if N else float("-inf")
+        return out
 
     def generate(self, z_mu=None):
         """Generate data by sampling from latent space: decoder only, z fed directly; returns the
