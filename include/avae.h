@@ -657,6 +657,66 @@ int avae_agg_logpdf_plan(const avae_config* cfg, int32_t rows, int32_t gallery_r
                          int32_t* query_tile, int32_t* chunk_rows, int32_t* slice_rows, int32_t* n_slices,
                          size_t* scratch_bytes);
 
+/* ---- mixture prior fitted to the posteriors: p(z) = sum_k pi_k N(z; m_k, diag exp(s_k)), 1 <= K <= 64, fitted after training to
+ * the encoders' posteriors q_n = N(mu_n, diag v_n), v_n = exp(logvar_n), by EM on the Jensen lower bound of
+ * 1/N sum_n E_{q_n}[log p(z)] (ex-post density estimation, Ghosh et al. 2020).  It is what replaces the
+ * N(0, I) draw of avae_generate's caller when the aggregate posterior is a handful of clusters, and it is an unsupervised
+ * clustering of the codes.
+ *   mu_dev, logvar_dev   the posteriors as avae_encode writes them, device fp32 [rows, n_z], dense; logvar_dev NULL: points, v = 0
+ *   weights_dev [K], means_dev [K, n_z], logvars_dev [K, n_z]   device fp32, dense; avae_gmm_fit: in the initial, out the fitted
+ *   bound_dev            device fp64 [n_iters + 1]: bound[t] is the bound of the parameters ENTERING iteration t, bound[n_iters] that
+ *                        of the returned ones (a last pass that only scores)
+ *   n_used_dev           device int32 [1]: the rows counted
+ * One iteration, over the used rows (a row with any non-finite mu or logvar entry is skipped, never added to a sum):
+ *   E_nk  = log pi_k - 1/2 sum_j [log 2pi + s_kj + ((mu_nj - m_kj)^2 + v_nj) exp(-s_kj)]
+ *   ll_n  = logsumexp_k E_nk,  r_nk = exp(E_nk - ll_n),  bound = mean ll_n
+ *   R_k = sum r_nk,  S1_kj = sum r_nk (mu_nj - m_kj),  S2_kj = sum r_nk ((mu_nj - m_kj)^2 + v_nj)
+ *   pi_k = R_k / sum_k R_k,  m'_kj = m_kj + S1_kj / R_k,  s'_kj = log max(S2_kj / R_k - (S1_kj / R_k)^2, var_floor)
+ * The sums are shifted by the CURRENT mean, so the variance never comes from a difference of large numbers.  A component with
+ * R_k < 1e-8 keeps its mean and log-variance and gets the weight R_k / sum R (no re-seeding).  With no used row the parameters stay
+ * as given and the bound is NaN; rows == 0 is that case, not an error.  n_iters == 0 scores the initial parameters and leaves them
+ * untouched.  There is no early stop: the caller reads bound.
+ * Arithmetic: the exponent is c_k = logf(pi_k) - 0.5f * sum_j (s_kj + log 2pi) followed by the chain
+ * E = fmaf(fmaf(d, d, v), -0.5f * expf(-s_kj), E), d = mu_nj - m_kj, over j = 0 .. n_z-1 in index order; v = expf(logvar) formed
+ * once per element; p_k = expf(E_k - max_k E_k), their sum in k order, ll = max + logf(sum), r_k = p_k / sum -- all fp32.  The
+ * sums of r d, r (d^2 + v) and r run in fp32 over a tile of 64 rows in row order and are folded into fp64 per tile, ll is added
+ * in fp64 (per row position of the tiles, the 64 positions in order at the end of a slice); a skipped row is selected away, it
+ * enters every sum as +-0; the slices' partials are combined in slice order and the update is evaluated in fp64, then rounded to fp32:
+ * the parameters are fp32 between iterations, so a fit of a iterations continued for b more from its own output gives the bits
+ * of a fit of a + b.  No atomics, one fixed order of every sum; the row partition is a function of rows alone (avae_gmm_plan):
+ * the result is a pure function of the input bits -- the same on any stream and on repetition.
+ * The whole loop is enqueued on `stream` with no host synchronisation inside: two launches per iteration (k_gmm_estep on a grid
+ * of row slices, one partial per slice to a scratch; k_gmm_mstep, one thread per (k, j)) and two for the last scoring pass.  The scratch
+ * is allocated by the first call (one allocation of the plan's upper bound, 16,978,432 bytes) and freed by avae_destroy;
+ * avae_workspace_bytes is unchanged.
+ * Errors (with a message naming the argument, outputs untouched): rows < 0, n_components outside [1, 64], n_iters < 0, var_floor
+ * <= 0 or not finite, a NULL mu_dev with rows > 0, a NULL weights_dev / means_dev / logvars_dev / bound_dev / n_used_dev.
+ * As avae_latent_topk, the calls change nothing a training step reads, work on any replica with no collective, and inside
+ * avae_use_averaged (they only see latents). */
+int avae_gmm_fit(avae_handle* h,
+                 const float* mu_dev, const float* logvar_dev, int32_t rows,
+                 int32_t n_components, int32_t n_iters, float var_floor,
+                 float* weights_dev, float* means_dev, float* logvars_dev,
+                 double* bound_dev, int32_t* n_used_dev, void* stream);
+/* The E-step alone, with per-row outputs: ll_dev fp32 [rows] = ll_n (for points exactly log p(z)), component_dev int32 [rows] = the
+ * argmax of r_n. (ties to the lower index), resp_dev fp32 [rows, K] = r_nk.  Any output may be NULL, not all of them.  A skipped
+ * (non-finite) row gives ll = NaN, component = -1, resp = NaN.  A row's outputs are a pure function of its own bits and the
+ * parameters: they do not depend on the other rows, on which outputs are asked for, on the stream or on repetition, and ll is
+ * the number avae_gmm_fit averages into bound.  rows == 0 is a no-op.  Errors: rows < 0, n_components outside [1, 64], a NULL
+ * mu_dev with rows > 0, a NULL weights_dev / means_dev / logvars_dev, all three outputs NULL.  One launch of k_gmm_estep. */
+int avae_gmm_score(avae_handle* h,
+                   const float* mu_dev, const float* logvar_dev, int32_t rows, int32_t n_components,
+                   const float* weights_dev, const float* means_dev, const float* logvars_dev,
+                   float* ll_dev, int32_t* component_dev, float* resp_dev, void* stream);
+/* Host-only (no GPU): the row partition both calls use, a function of rows alone.  Slice i covers the rows
+ * [i * slice_rows, min(rows, (i + 1) * slice_rows)); slice_rows = max(64, ceil(rows / 256) rounded up to a multiple of 64), so
+ * there are at most 256 slices, each a whole number of 64-row tiles (the last one apart), none empty, and n_slices == 0 only for
+ * rows == 0.  scratch_bytes = n_slices * (2 + K + 2 K n_z) * 8 + 2 * (K + 2 K n_z) * 4 for the configuration's n_z: at most
+ * 16,978,432.  Any output pointer may be NULL; rows < 0 or n_components outside [1, 64] is an error, the message in
+ * avae_last_error(NULL). */
+int avae_gmm_plan(const avae_config* cfg, int32_t rows, int32_t n_components,
+                  int32_t* slice_rows, int32_t* n_slices, size_t* scratch_bytes);
+
 /* save_model / restore_model (vae_assoc.py:427-463): own flat file (config echo + params + Adam
  * slots + step; with parameter averaging on also its settings and the average, see avae_set_ema);
  * TF .ckpt files cannot be read offline. */

@@ -22,6 +22,7 @@ SCORE_CROSS = 1
 METRIC_SYMKL, METRIC_L2 = 0, 1
 METRIC_IDS = {"symkl": METRIC_SYMKL, "l2": METRIC_L2}
 TOPK_MAX = 64
+GMM_MAX_COMPONENTS = 64
 
 ACT_IDS = {"identity": 0, "relu": 1, "softplus": 2, "sigmoid": 3, "tanh": 4}
 DTYPE_IDS = {"fp32": 0, "f32": 0, "float32": 0, "bf16": 1, "bfloat16": 1}
@@ -44,6 +45,7 @@ SYMBOLS = [
     "avae_latent_topk", "avae_latent_topk_plan",
     "avae_latent_stats", "avae_latent_stats_plan",
     "avae_agg_logpdf", "avae_agg_logpdf_plan",
+    "avae_gmm_fit", "avae_gmm_score", "avae_gmm_plan",
     "avae_synchronize", "avae_timing_enable", "avae_timing_report", "avae_debug_fetch", "avae_comm_allreduce",
 ]
 
@@ -161,6 +163,9 @@ def lib():
             L.avae_agg_logpdf.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, vp, vp]
             L.avae_agg_logpdf_plan.argtypes = [C.POINTER(Config), i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32),
                                                C.POINTER(i32), C.POINTER(sz)]
+            L.avae_gmm_fit.argtypes = [vp, vp, vp, i32, i32, i32, C.c_float, vp, vp, vp, vp, vp, vp]
+            L.avae_gmm_score.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+            L.avae_gmm_plan.argtypes = [C.POINTER(Config), i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(sz)]
             L.avae_save.argtypes = [vp, C.c_char_p]
             L.avae_load.argtypes = [vp, C.c_char_p]
             L.avae_synchronize.argtypes = [vp]

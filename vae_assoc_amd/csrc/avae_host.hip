@@ -4,6 +4,7 @@
 #include "avae_complete.h"
 #include "avae_retrieve.h"
 #include "avae_latent_stats.h"
+#include "avae_gmm.h"
 #include "avae_aggpost.h"
 #include "../../include/avae.h"
 
@@ -285,6 +286,7 @@ struct avae_handle {
     DevBuf topk_buf;                        // avae_latent_topk: the (query, split) lists of one chunk of queries (kTopkScratchBytes)
     DevBuf stats_buf;                       // avae_latent_stats: one partial per (row slice, work item) (kStatsScratchBytes)
     DevBuf agg_buf;                         // avae_agg_logpdf: the (query, slice, column) pairs of one chunk of queries (kAggScratchBytes)
+    DevBuf gmm_buf;                         // avae_gmm_fit: one partial per row slice and two parameter sets (kGmmScratchBytes)
     size_t off_chain = 0;
     size_t off_consts = 0, off_conv_tab = 0;   // 32 B {zeros | one, 0...}; device copy of conv_tab
     std::vector<ConvA> conv_tab;             // implicit patch matrices of the training plan
@@ -4345,6 +4347,101 @@ int avae_agg_logpdf(avae_handle* h, const float* z_dev, int32_t rows, const floa
             if (p.n_slices > 0) timed_launch(h, s, "agg_logpdf", [&] { launch_agg_logpdf(a, s); });
             timed_launch(h, s, "agg_logpdf_merge", [&] { launch_agg_logpdf_merge(a, s); });
         }
+    });
+}
+
+// ---- mixture prior fitted to the posteriors (include/avae.h, avae_gmm.h)
+static void check_gmm_shape(const std::string& w, int32_t rows, int32_t K) {
+    if (rows < 0) throw Err(w + ": rows must be >= 0");
+    if (K < 1 || K > kGmmMaxK)
+        throw Err(w + ": n_components = " + std::to_string(K) + " must be in [1, " + std::to_string(kGmmMaxK) + "]");
+}
+
+int avae_gmm_plan(const avae_config* cfg, int32_t rows, int32_t n_components, int32_t* slice_rows, int32_t* n_slices,
+                  size_t* scratch_bytes) {
+    try {
+        if (!cfg) throw Err("null argument");
+        check_config(*cfg);
+        check_gmm_shape("avae_gmm_plan", rows, n_components);
+        const GmmPlan p = gmm_plan(rows);
+        if (slice_rows) *slice_rows = p.slice_rows;
+        if (n_slices) *n_slices = p.n_slices;
+        if (scratch_bytes) *scratch_bytes = gmm_scratch_bytes(p.n_slices, n_components, cfg->n_z);
+        return 0;
+    } catch (const std::exception& e) { g_create_error = e.what(); return 2; }
+}
+
+int avae_gmm_fit(avae_handle* h, const float* mu_dev, const float* logvar_dev, int32_t rows, int32_t n_components, int32_t n_iters,
+                 float var_floor, float* weights_dev, float* means_dev, float* logvars_dev, double* bound_dev, int32_t* n_used_dev,
+                 void* stream) {
+    return guarded(h, [&] {
+        const std::string w = "avae_gmm_fit";
+        check_gmm_shape(w, rows, n_components);
+        if (n_iters < 0) throw Err(w + ": n_iters must be >= 0");
+        if (!(var_floor > 0.0f) || !std::isfinite(var_floor)) throw Err(w + ": var_floor must be positive and finite");
+        if (rows > 0 && !mu_dev) throw Err(w + ": mu_dev is NULL");
+        if (!weights_dev) throw Err(w + ": weights_dev is NULL");
+        if (!means_dev) throw Err(w + ": means_dev is NULL");
+        if (!logvars_dev) throw Err(w + ": logvars_dev is NULL");
+        if (!bound_dev) throw Err(w + ": bound_dev is NULL");
+        if (!n_used_dev) throw Err(w + ": n_used_dev is NULL");
+        static_assert(kGmmMaxNz >= 64, "check_config bounds n_z by 64");
+        const int nz = h->nz, K = n_components;
+        const GmmPlan p = gmm_plan(rows);
+        if (gmm_scratch_bytes(p.n_slices, K, nz) > kGmmScratchBytes || gmm_lds_bytes(K, nz) > 160 * 1024)
+            throw Err("internal error: " + w + " plans more scratch or LDS than its bound");
+        hipStream_t s = on_stream(h, stream);
+        GmmArgs a;
+        std::memset(&a, 0, sizeof(a));
+        a.mu = mu_dev; a.lv = logvar_dev; a.rows = rows; a.nz = nz; a.K = K;
+        a.n_slices = p.n_slices; a.slice_rows = p.slice_rows; a.var_floor = var_floor; a.n_used = n_used_dev;
+        a.part = static_cast<double*>(h->gmm_buf.ensure(kGmmScratchBytes));
+        // iteration t reads the set iteration t - 1 wrote: the caller's arrays first, the scratch's two sets in turn between, and the
+        // last one writes the caller's arrays again (every element is read and written by the same thread where the two coincide)
+        const size_t pf = gmm_param_floats(K, nz);
+        float* sets[2];
+        sets[0] = reinterpret_cast<float*>(a.part + (size_t)kGmmMaxSlices * gmm_part_stride(kGmmMaxK, kGmmMaxNz));
+        sets[1] = sets[0] + pf;
+        auto point = [&](float* base, float*& pw, float*& pmean, float*& ps) { pw = base; pmean = base + K; ps = base + K + (size_t)K * nz; };
+        const float *wi = weights_dev, *mi = means_dev, *si = logvars_dev;
+        for (int t = 0; t <= n_iters; ++t) {
+            const bool last = t == n_iters;
+            a.w_in = wi; a.m_in = mi; a.s_in = si;
+            a.want_stats = last ? 2 : 1; a.final_pass = last ? 1 : 0;
+            a.bound = bound_dev + t;
+            if (last) { a.w_out = nullptr; a.m_out = nullptr; a.s_out = nullptr; }
+            else if (t == n_iters - 1) { a.w_out = weights_dev; a.m_out = means_dev; a.s_out = logvars_dev; }
+            else point(sets[t & 1], a.w_out, a.m_out, a.s_out);
+            if (p.n_slices > 0) timed_launch(h, s, "gmm_estep", [&] { launch_gmm_estep(a, s); });
+            timed_launch(h, s, "gmm_mstep", [&] { launch_gmm_mstep(a, s); });
+            wi = a.w_out; mi = a.m_out; si = a.s_out;
+        }
+    });
+}
+
+int avae_gmm_score(avae_handle* h, const float* mu_dev, const float* logvar_dev, int32_t rows, int32_t n_components,
+                   const float* weights_dev, const float* means_dev, const float* logvars_dev, float* ll_dev, int32_t* component_dev,
+                   float* resp_dev, void* stream) {
+    return guarded(h, [&] {
+        const std::string w = "avae_gmm_score";
+        check_gmm_shape(w, rows, n_components);
+        if (rows > 0 && !mu_dev) throw Err(w + ": mu_dev is NULL");
+        if (!weights_dev) throw Err(w + ": weights_dev is NULL");
+        if (!means_dev) throw Err(w + ": means_dev is NULL");
+        if (!logvars_dev) throw Err(w + ": logvars_dev is NULL");
+        if (!ll_dev && !component_dev && !resp_dev) throw Err(w + ": ll_dev, component_dev and resp_dev are all NULL");
+        if (rows == 0) return;
+        const int nz = h->nz;
+        const GmmPlan p = gmm_plan(rows);
+        if (gmm_lds_bytes(n_components, nz) > 160 * 1024) throw Err("internal error: " + w + " plans more LDS than its bound");
+        hipStream_t s = on_stream(h, stream);
+        GmmArgs a;
+        std::memset(&a, 0, sizeof(a));
+        a.mu = mu_dev; a.lv = logvar_dev; a.rows = rows; a.nz = nz; a.K = n_components;
+        a.n_slices = p.n_slices; a.slice_rows = p.slice_rows;
+        a.w_in = weights_dev; a.m_in = means_dev; a.s_in = logvars_dev;
+        a.ll = ll_dev; a.component = component_dev; a.resp = resp_dev;
+        timed_launch(h, s, "gmm_score", [&] { launch_gmm_estep(a, s); });
     });
 }
 

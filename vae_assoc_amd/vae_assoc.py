@@ -347,6 +347,106 @@ def agg_args(z, gallery, exclude, marginals, n_z, device):
     return zt, gm, gl, ex, bool(marginals), not torch.is_tensor(z)
 
 
+def _is_pair(x):
+    """a ``(mu, logvar)`` pair of arrays or tensors (``logvar`` may be None), as opposed to a list of such pairs"""
+    return isinstance(x, (tuple, list)) and len(x) == 2 and hasattr(x[0], "shape") and (x[1] is None or hasattr(x[1], "shape"))
+
+
+def prior_arrays(prior, n_z, device, name="prior", n_components=None):
+    """A mixture prior checked and marshalled -> (weights [K], means [K, n_z], logvars [K, n_z] contiguous float32 tensors on
+    ``device``, was_numpy).  ``prior`` is a dict with the keys ``weights``, ``means`` and ``logvars`` (what ``fit_latent_prior``
+    returns; further keys are ignored).  Every error is a ``ValueError``; touches neither a model nor the library."""
+    if not isinstance(prior, dict) or any(k not in prior for k in ("weights", "means", "logvars")):
+        raise ValueError("%s must be a dict with the keys weights, means and logvars, got %r"
+                         % (name, sorted(prior) if isinstance(prior, dict) else type(prior).__name__))
+    w, was_np = prior["weights"], not torch.is_tensor(prior["weights"])
+    w = torch.as_tensor(np.asarray(w, dtype=np.float32) if was_np else w).to(device=device, dtype=torch.float32).contiguous()
+    if w.dim() != 1 or not 1 <= w.shape[0] <= _capi.GMM_MAX_COMPONENTS:
+        raise ValueError("%s: weights must be [K] with 1 <= K <= %d, got %s" % (name, _capi.GMM_MAX_COMPONENTS, tuple(w.shape)))
+    K = int(w.shape[0])
+    if n_components is not None and K != n_components:
+        raise ValueError("%s: weights must be [%d] (n_components), got %s" % (name, n_components, tuple(w.shape)))
+    if not bool(torch.isfinite(w).all()) or bool((w < 0).any()) or not float(w.sum()) > 0:
+        raise ValueError("%s: weights must be finite, non-negative and not all zero" % name)
+    try:
+        m = dev_dense(prior["means"], n_z, device, K, "as weights", name="means")
+        lv = dev_dense(prior["logvars"], n_z, device, K, "as weights", name="logvars")
+    except ValueError as e:
+        raise ValueError("%s: %s" % (name, e))
+    if m is None or lv is None:
+        raise ValueError("%s: %s is None" % (name, "means" if m is None else "logvars"))
+    return w, m, lv, was_np
+
+
+def latent_prior_args(posteriors, n_components, n_iters, init, seed, var_floor, n_z, device):
+    """The arguments of ``fit_latent_prior`` checked and marshalled -> (mu, logvar or None, K, n_iters, var_floor, init, seed_rows,
+    was_numpy).  ``posteriors`` is a ``(mu, logvar)`` pair of ``[N, n_z]`` arrays or tensors (``logvar`` may be None: points) or
+    a list of such pairs, whose rows are concatenated in list order (every pair with a logvar, or none).  ``init`` comes back as
+    the ``(weights, means, logvars)`` tensors of the given dict (copies: the fit works in place) and ``seed_rows`` as None, or,
+    for ``init=None``, ``init`` is None and ``seed_rows`` a LongTensor of the K rows the means start from:
+    ``np.random.default_rng(seed).permutation(F)[:K]`` over the F rows without a non-finite entry, in row order.  Every shape or
+    value error is a ``ValueError`` raised here, ahead of any launch; touches neither a model nor the library (``device="cpu"``
+    works)."""
+    if isinstance(n_components, bool) or not isinstance(n_components, (int, np.integer)) \
+            or not 1 <= n_components <= _capi.GMM_MAX_COMPONENTS:
+        raise ValueError("n_components must be an integer in [1, %d], got %r" % (_capi.GMM_MAX_COMPONENTS, n_components))
+    if isinstance(n_iters, bool) or not isinstance(n_iters, (int, np.integer)) or n_iters < 0:
+        raise ValueError("n_iters must be an integer >= 0, got %r" % (n_iters,))
+    try:
+        vf = float(var_floor)
+    except (TypeError, ValueError):
+        raise ValueError("var_floor must be a positive finite number, got %r" % (var_floor,))
+    if not (vf > 0.0 and np.isfinite(vf) and float(np.float32(vf)) > 0.0 and np.isfinite(np.float32(vf))):
+        raise ValueError("var_floor must be a positive finite number (in float32), got %r" % (var_floor,))
+    K = int(n_components)
+    pairs = [posteriors] if _is_pair(posteriors) else posteriors
+    if not isinstance(pairs, (list, tuple)) or not pairs or not all(_is_pair(p) for p in pairs):
+        raise ValueError("posteriors must be a (mu, logvar) pair or a non-empty list of such pairs, got %r" % type(posteriors).__name__)
+    if len({p[1] is None for p in pairs}) != 1:
+        raise ValueError("posteriors: every pair needs a logvar, or none may have one (points)")
+    mus, lvs = [], []
+    for i, (mu, lv) in enumerate(pairs):
+        try:
+            t = dev_dense(mu, n_z, device, name="mu")
+            mus.append(t)
+            if lv is not None:
+                lvs.append(dev_dense(lv, n_z, device, t.shape[0], "as mu", name="logvar"))
+        except ValueError as e:
+            raise ValueError("posteriors[%d]: %s" % (i, e))
+    was_np = not torch.is_tensor(pairs[0][0])
+    mu = mus[0] if len(mus) == 1 else torch.cat(mus).contiguous()
+    lv = None if not lvs else (lvs[0] if len(lvs) == 1 else torch.cat(lvs).contiguous())
+    if init is not None:
+        w, m, s, _ = prior_arrays(init, n_z, device, name="init", n_components=K)
+        return mu, lv, K, int(n_iters), vf, (w.clone(), m.clone(), s.clone()), None, was_np
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or seed < 0:
+        raise ValueError("seed must be an integer >= 0, got %r" % (seed,))
+    fin = torch.isfinite(mu).all(dim=1)
+    if lv is not None:
+        fin &= torch.isfinite(lv).all(dim=1)
+    rows = torch.nonzero(fin).reshape(-1).cpu()
+    F = int(rows.shape[0])
+    if K > F:
+        raise ValueError("n_components = %d is more than the %d rows without a non-finite entry that the means are drawn from" % (K, F))
+    pick = np.random.default_rng(int(seed)).permutation(F)[:K]
+    return mu, lv, K, int(n_iters), vf, None, rows[torch.from_numpy(pick.astype(np.int64))], was_np
+
+
+def latent_score_args(z, prior, n_z, device):
+    """The arguments of ``latent_prior_score`` checked and marshalled -> (mu, logvar or None, weights, means, logvars,
+    was_numpy).  ``z`` is a ``[N, n_z]`` array or tensor (points) or a ``(mu, logvar)`` pair."""
+    if z is None:
+        raise ValueError("z is None")
+    mu, lv = z if _is_pair(z) else (z, None)
+    try:
+        mt = dev_dense(mu, n_z, device, name="mu" if _is_pair(z) else "z")
+        lt = dev_dense(lv, n_z, device, mt.shape[0], "as mu", name="logvar")
+    except ValueError as e:
+        raise ValueError("z: %s" % e)
+    w, m, s, _ = prior_arrays(prior, n_z, device)
+    return mt, lt, w, m, s, not torch.is_tensor(mu)
+
+
 def latent_stats_args(posteriors, present, n_z, device):
     """The arguments of ``latent_stats`` checked and marshalled -> (mus, logvars, rows, presence or None, was_numpy): two lists
     over the modalities of ``[rows, n_z]`` tensors, None where the modality is absent everywhere.  ``posteriors`` is a list of 1 to
@@ -1012,6 +1112,85 @@ class AssocVariationalAutoEncoder(object):
         out = {name: conv(t) for name, t in out.items()}
         out["log_n"] = float(np.log(N)) if N else float("-inf")
         return out
+
+    # ------------------------------------------------------------------ mixture prior
+    def _gmm_fit(self, mu, lv, K, n_iters, var_floor, w, m, s):
+        """avae_gmm_fit in place on the contiguous float32 device tensors ``w``, ``m``, ``s`` -> (bound [n_iters + 1] float64,
+        n_used [1] int32), device tensors"""
+        bound = torch.empty((n_iters + 1,), dtype=torch.float64, device=self.device)
+        n_used = torch.empty((1,), dtype=torch.int32, device=self.device)
+        _capi.check(self._h, self._L.avae_gmm_fit(self._h, ptr(mu), ptr(lv), mu.shape[0], K, n_iters, var_floor, w.data_ptr(),
+                                                  m.data_ptr(), s.data_ptr(), bound.data_ptr(), n_used.data_ptr(), self._stream()),
+                    "avae_gmm_fit")
+        return bound, n_used
+
+    def fit_latent_prior(self, posteriors, n_components=10, n_iters=50, init=None, seed=0, var_floor=1e-6):
+        """Fit a diagonal Gaussian mixture ``p(z) = sum_k pi_k N(z; m_k, diag exp(s_k))`` to posteriors, on the device
+        (avae_gmm_fit in include/avae.h): the prior to sample from instead of N(0, I) once the aggregate posterior is a handful of
+        clusters with holes between them (ex-post density estimation), and an unsupervised clustering of the codes.
+
+        ``posteriors`` is a ``(mu, logvar)`` pair as ``posterior`` returns it, or a list of such pairs whose rows are concatenated
+        -- one prior for every encoder's codes, the one ``generate`` decodes for all modalities.  ``logvar`` may be None (points:
+        textbook EM); with it the fit maximises the Jensen bound of ``mean_n E_{q_n}[log p(z)]``.  ``1 <= n_components <= 64``;
+        ``n_iters`` EM iterations, no early stop.  ``init=None`` starts the means at ``n_components`` rows picked by
+        ``np.random.default_rng(seed).permutation`` over the rows without a non-finite entry, every log-variance at the data's total
+        per-dimension variance and the weights at 1/K; or ``init=dict(weights=, means=, logvars=)`` to warm-start.  A row with a
+        non-finite entry is skipped; a component that loses all its rows keeps its place with weight 0.
+
+        Returns ``dict(weights [K], means [K, n_z], logvars [K, n_z] float32, bound [n_iters + 1] float64, n_used int)``:
+        ``bound[t]`` is the bound of the parameters entering iteration t, ``bound[-1]`` that of the returned ones.  The result is
+        bit-reproducible, and a fit continued from its own output gives the bits of the longer fit.  NumPy in gives NumPy out,
+        tensors in give device tensors out."""
+        mu, lv, K, T, vf, start, seed_rows, was_np = latent_prior_args(posteriors, n_components, n_iters, init, seed, var_floor,
+                                                                       self.n_z, self.device)
+        if start is None:
+            m = mu[seed_rows.to(self.device)].contiguous()
+            w1 = torch.ones((1,), dtype=torch.float32, device=self.device)
+            m1, s1 = m[:1].clone(), torch.zeros((1, self.n_z), dtype=torch.float32, device=self.device)
+            self._gmm_fit(mu, lv, 1, 1, vf, w1, m1, s1)             # one K = 1 iteration: s1 = log of the total variance
+            w = torch.full((K,), 1.0 / K, dtype=torch.float32, device=self.device)
+            s = s1.expand(K, self.n_z).contiguous()
+        else:
+            w, m, s = start
+        bound, n_used = self._gmm_fit(mu, lv, K, T, vf, w, m, s)
+        conv = self._like_input(was_np)
+        return {"weights": conv(w), "means": conv(m), "logvars": conv(s), "bound": conv(bound), "n_used": int(n_used.item())}
+
+    def latent_prior_score(self, z, prior, responsibilities=False):
+        """Score rows under a mixture prior (avae_gmm_score in include/avae.h).  ``z`` is a ``[N, n_z]`` array (points) or a
+        ``(mu, logvar)`` pair; ``prior`` a dict of ``weights``, ``means``, ``logvars`` as ``fit_latent_prior`` returns it.
+        Returns ``dict(log_density [N] float32, component [N] int32, responsibilities [N, K] float32 or None)``: for points
+        ``log_density`` is exactly ``log p(z)`` -- a novelty score against K components instead of a whole gallery -- for pairs the
+        per-row term of the fit's bound; ``component`` is the most responsible component (ties to the lower index).  A row with
+        a non-finite entry gives NaN, -1 and NaN.  A row's result does not depend on the other rows."""
+        mu, lv, w, m, s, was_np = latent_score_args(z, prior, self.n_z, self.device)
+        rows, K = mu.shape[0], w.shape[0]
+        ll = torch.empty((rows,), dtype=torch.float32, device=self.device)
+        comp = torch.empty((rows,), dtype=torch.int32, device=self.device)
+        resp = self._new(rows, K) if responsibilities else None
+        if rows:
+            _capi.check(self._h, self._L.avae_gmm_score(self._h, mu.data_ptr(), ptr(lv), rows, K, w.data_ptr(), m.data_ptr(),
+                                                        s.data_ptr(), ll.data_ptr(), comp.data_ptr(), ptr(resp), self._stream()),
+                        "avae_gmm_score")
+        conv = self._like_input(was_np)
+        return {"log_density": conv(ll), "component": conv(comp), "responsibilities": conv(resp) if responsibilities else None}
+
+    def sample_latent_prior(self, prior, n, seed=0):
+        """``n`` draws ``[n, n_z]`` from a mixture prior: the component from ``weights``, then its Gaussian, with a device generator
+        seeded by ``seed``.  ``generate(sample_latent_prior(prior, 64))`` replaces ``generate(None)``'s N(0, I) draw.  NumPy
+        prior gives NumPy out, a tensor prior device tensors."""
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 0:
+            raise ValueError("n must be an integer >= 0, got %r" % (n,))
+        w, m, s, was_np = prior_arrays(prior, self.n_z, self.device)
+        gen = torch.Generator(device=self.device)
+        gen.manual_seed(int(seed))
+        if n:
+            comp = torch.multinomial(w.double(), int(n), replacement=True, generator=gen)
+        else:
+            comp = torch.empty((0,), dtype=torch.int64, device=self.device)
+        eps = torch.randn((int(n), self.n_z), generator=gen, device=self.device, dtype=torch.float32)
+        z = m[comp] + torch.exp(0.5 * s[comp]) * eps
+        return self._like_input(was_np)(z)
 
     def generate(self, z_mu=None):
         """Generate data by sampling from latent space: decoder only, z fed directly; returns the
