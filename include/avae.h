@@ -678,8 +678,10 @@ int avae_agg_logpdf_plan(const avae_config* cfg, int32_t rows, int32_t gallery_r
  * untouched.  There is no early stop: the caller reads bound.
  * Arithmetic: the exponent is c_k = logf(pi_k) - 0.5f * sum_j (s_kj + log 2pi) followed by the chain
  * E = fmaf(fmaf(d, d, v), -0.5f * expf(-s_kj), E), d = mu_nj - m_kj, over j = 0 .. n_z-1 in index order; v = expf(logvar) formed
- * once per element; p_k = expf(E_k - max_k E_k), their sum in k order, ll = max + logf(sum), r_k = p_k / sum -- all fp32.  The
- * sums of r d, r (d^2 + v) and r run in fp32 over a tile of 64 rows in row order and are folded into fp64 per tile, ll is added
+ * once per element; p_k = expf(E_k - max_k E_k), ll = max + logf(sum), r_k = p_k / sum -- all fp32 but sum, the p_k added in k
+ * order in fp64 and rounded to fp32 once, so that a row of r sums to 1 within 2^-23 for every K.  The
+ * sums of r d, r (d^2 + v) and r run in fp64 over a slice's rows in row order (d = mu_nj - m_kj formed in fp64 here, fused
+ * multiply-adds: the products are exact, so S2 / R - (S1 / R)^2 loses nothing to the rounding of d^2), ll is added
  * in fp64 (per row position of the tiles, the 64 positions in order at the end of a slice); a skipped row is selected away, it
  * enters every sum as +-0; the slices' partials are combined in slice order and the update is evaluated in fp64, then rounded to fp32:
  * the parameters are fp32 between iterations, so a fit of a iterations continued for b more from its own output gives the bits

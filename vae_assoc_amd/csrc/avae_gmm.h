@@ -6,10 +6,10 @@
 //                per-component constant log pi_k - 1/2 sum_j (s_kj + log 2pi) -- and streams its slice in tiles of 64 rows (mu, and
 //                v = expf(lv) formed while staging; the next tile is on its way from memory meanwhile).  Phase 1, lane = row, wave w =
 //                the components [4w, 4w + 4), [4w + 16, 4w + 20), ...: the exponents as fp32 fused multiply-add chains over j in
-//                index order, the row's max, p = expf(E - max), their sum in k order, ll = max + logf(sum), r = p / sum into an LDS
-//                tile [64][K + 1].  Phase 2, thread = column j and the components g, g + G, ...: the tile's rows in order, r (mu - m)
-//                and r ((mu - m)^2 + v) in fp32 over the tile, folded into fp64 registers that live for the whole slice; R_k
-//                likewise.  ll is added in fp64 per row position of the tiles (lane = row), the 64 positions in order at the end.
+//                index order, the row's max, p = expf(E - max), their sum in k order (in fp64, rounded once), ll = max + logf(sum),
+//                r = p / sum into an LDS tile [64][K + 1].  Phase 2, thread = column j and the components g, g + G, ...: the tile's rows in order, r (mu - m)
+//                and r ((mu - m)^2 + v) as fp64 fused multiply-adds (mu - m formed in fp64: the products are exact) into
+//                registers that live for the whole slice; R_k likewise.  ll is added in fp64 per row position of the tiles (lane = row), the 64 positions in order at the end.
 //                A row with a non-finite entry is selected away (zeros staged, r = 0).  ONE partial per slice goes to the scratch.
 //   k_gmm_mstep  one thread per (k, j), in blocks of 256: the slices' partials combined in slice order in fp64, the update, the
 //                next fp32 parameters and bound[t].  After the last E-step one block only writes bound[n_iters] and n_used.

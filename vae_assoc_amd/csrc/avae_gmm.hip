@@ -68,14 +68,14 @@ __global__ void __launch_bounds__(kGmmThreads) k_gmm_estep(GmmArgs a) {
     const int pj = tid & (JW - 1), pg = tid / JW;
     const int pjj = pj < nz ? pj : nz - 1;                         // (an idle thread reads a valid column and writes nothing)
     double S1[OWN], S2[OWN], RR[OWN], sum_ll = 0.0;                // sum_ll, used: wave 0, lane = row of every tile
-    float mk[OWN];
+    double mk[OWN];
     int kk[OWN], used = 0;
     if (STATS == 1) {
 #pragma unroll
         for (int c = 0; c < OWN; ++c) {
             S1[c] = 0.0; S2[c] = 0.0; RR[c] = 0.0;
             kk[c] = min(pg + KG * c, K - 1);
-            mk[c] = a.m_in[kk[c] * nz + pjj];
+            mk[c] = (double)a.m_in[kk[c] * nz + pjj];
         }
     }
 
@@ -158,9 +158,12 @@ __global__ void __launch_bounds__(kGmmThreads) k_gmm_estep(GmmArgs a) {
                 if (k0 + i < K) rt[lane * K1 + k0 + i] = pv[ch][i];
         }
         __syncthreads();
-        float sum = 0.0f;
+        // the K terms in k order in fp64, rounded once: with r = p / sum correctly rounded, a row of r sums to 1 within 2^-23
+        // whatever K is (an fp32 running sum of 64 terms is off by several ulp, and every r of the row with it)
+        double sum64 = 0.0;
 #pragma unroll 8
-        for (int k = 0; k < K; ++k) sum = sum + rt[lane * K1 + k];
+        for (int k = 0; k < K; ++k) sum64 += (double)rt[lane * K1 + k];
+        const float sum = (float)sum64;
         __syncthreads();
 #pragma unroll
         for (int ch = 0; ch < NCH; ++ch) {
@@ -198,27 +201,25 @@ __global__ void __launch_bounds__(kGmmThreads) k_gmm_estep(GmmArgs a) {
         }
 
         // ---- phase 2: thread = column pj and the components pg, pg + KG, ...; the tile's rows in order
+        // In fp64: d = mu - m and the products r d, d d are then exact, so the M-step's S2 / R - (S1 / R)^2 cancels d^2 against
+        // itself and not against its fp32 rounding (one row with d^2 >> v: the variance is v, not v +- 1e-7 d^2).  An fp64
+        // fused multiply-add issues at the rate of an unpacked fp32 one.
         if (STATS == 1) {
-            float a1[OWN], a2[OWN], aR[OWN];
-#pragma unroll
-            for (int c = 0; c < OWN; ++c) { a1[c] = 0.0f; a2[c] = 0.0f; aR[c] = 0.0f; }
 #pragma unroll 2
             for (int row = 0; row < nr; ++row) {
-                const float x = mt[pjj * LD + row], v = vt[pjj * LD + row];
+                const double x = (double)mt[pjj * LD + row], v = (double)vt[pjj * LD + row];
                 const float* rr = rt + row * K1;
 #pragma unroll
                 for (int c = 0; c < OWN; ++c) {
                     if (c * KG < K) {
-                        const float r = rr[kk[c]];
-                        const float d = x - mk[c];
-                        a1[c] = __builtin_fmaf(r, d, a1[c]);
-                        a2[c] = __builtin_fmaf(r, __builtin_fmaf(d, d, v), a2[c]);
-                        aR[c] = aR[c] + r;
+                        const double r = (double)rr[kk[c]];
+                        const double d = x - mk[c];
+                        S1[c] = __builtin_fma(r, d, S1[c]);
+                        S2[c] = __builtin_fma(r, __builtin_fma(d, d, v), S2[c]);
+                        RR[c] = RR[c] + r;
                     }
                 }
             }
-#pragma unroll
-            for (int c = 0; c < OWN; ++c) { S1[c] += (double)a1[c]; S2[c] += (double)a2[c]; RR[c] += (double)aR[c]; }
         }
     }
 
