@@ -719,6 +719,83 @@ int avae_gmm_score(avae_handle* h,
 int avae_gmm_plan(const avae_config* cfg, int32_t rows, int32_t n_components,
                   int32_t* slice_rows, int32_t* n_slices, size_t* scratch_bytes);
 
+/* ---- 2-D t-SNE map of the posteriors (van der Maaten & Hinton 2008): where the codes of every modality lie,
+ * as a picture.  The affinities are built from avae_latent_topk's metric -- under AVAE_METRIC_SYMKL from the divergence the
+ * association term is trained on, variances included -- and the N x N matrix never exists: p_ij is recomputed in every iteration
+ * from the pair's distance and three numbers per row.
+ *   mu_dev, logvar_dev   the posteriors as avae_encode writes them, device fp32 [rows, n_z], dense.  AVAE_METRIC_L2 never reads
+ *                        logvar_dev (it may be NULL: points)
+ * D_ij is the distance of rows i and j exactly as avae_latent_topk states it (the same chain of fused multiply-adds over
+ * j = 0 .. n_z-1 from +0.0f, v = expf(lv), iv = expf(-lv) formed once per row and tile): one device function serves the
+ * calibration and the force pass, so D_ij has the same bits in both, D_ij == D_ji, and D_ij - min_j D_ij >= 0.
+ * A row with a non-finite mu (or, under SYMKL, logvar) entry is skipped: it is selected away, never multiplied by 0, it enters
+ * every sum as +-0, its outputs are NaN and no bit of another row's output depends on what it held.  F = the used rows.
+ *
+ * avae_embed_calibrate: per used row i the search for beta_i with entropy log(perplexity).
+ *   m_i = min_{j != i} D_ij,  e_ij = expf(-(beta_i * (D_ij - m_i))),  S0_i = sum_{j != i} e_ij,  S1_i = sum (D_ij - m_i) e_ij,
+ *   H_i = log S0_i + beta_i S1_i / S0_i
+ * beta starts at 1; while |H - log(perplexity)| > tol and fewer than max_tries values were tried: H too large -> the lower bound
+ * becomes beta and beta = 2 beta (no upper bound yet) or (beta + upper) / 2; else the upper bound becomes beta and beta = beta / 2
+ * (no lower bound yet) or (beta + lower) / 2.  beta stays inside [2^-100, 2^100].  Outputs, device, dense [rows] (NaN / 0 tries on
+ * a skipped row, and on every row when F < 2): beta_dev, shift_dev = m_i, norm_dev = S0_i AT the returned beta_i (all fp32),
+ * tries_dev int32 = the values tried; n_used_dev int32 [1] = F.  A row's (beta, shift, norm, tries) is a function of its own
+ * distances, in row order, alone.  Arithmetic: e and (D - m) e in fp32, added in fp32 over the 4 columns a thread holds of a
+ * 64-row tile, in fp64 over the tiles in order and over the 16 threads of a row (a fixed tree); H and the comparison in fp64;
+ * beta and its bounds are fp32.  One workgroup owns 64 rows and streams all rows once for the minima and once per try
+ * (O(rows^2 x tries): rows <= 65,536); finished rows freeze.
+ *
+ * avae_embed_iterate: n_iters iterations of gradient descent on KL(P || Q) from the state (y, vel, gain), device fp32 [rows, 2]
+ * each, updated in place.  With c_i = 1 / (2 F norm_i):
+ *   p_ij = e_ij c_i + e_ji c_j  (i != j; two fp32 products and their sum: p_ij == p_ji bit for bit),  p_ii = 0
+ *   w_ij = 1 / (1 + |y_i - y_j|^2),  w_ii = 0,  Z = sum_{i != j} w_ij
+ *   A_i = sum_j p_ij w_ij (y_i - y_j),  R_i = sum_j w_ij^2 (y_i - y_j),  grad_i = 4 (alpha A_i - R_i / Z)
+ *   KL = sum_{p_ij > 0} p_ij (log p_ij - log w_ij) + log Z      (always with the unexaggerated p)
+ * Iteration t = it0 + s (s = 0 .. n_iters-1): alpha = early_exaggeration and mom = momentum0 while t < exaggeration_iters, then
+ * alpha = 1 and mom = momentum1; per element  gain = ((grad > 0) != (vel > 0)) ? gain + 0.2 : gain * 0.8,  gain = max(gain, 0.01),
+ * vel = mom vel - lr gain grad,  y += vel  (evaluated in fp64 from the fp32 state and the fp64 gradient; gain, vel and y each rounded
+ * to fp32 once).  kl_dev fp64 [n_iters + 1]: kl[s] belongs to the Y ENTERING iteration it0 + s, kl[n_iters] to the returned Y (a last
+ * pass that only evaluates); n_iters == 0 evaluates and leaves y, vel and gain untouched.  grad_dev: NULL, or fp32 [rows, 2], the
+ * gradient at the entering Y of the call's first pass (no other output bit depends on it being asked for).  The forces are
+ * translation invariant and the map is not centred inside the loop; with center != 0 (and n_iters > 0) a last launch subtracts the
+ * mean of the used rows of the returned Y (fp64, fixed order).  A skipped row's y, vel, gain and grad come back NaN; with F < 2
+ * kl is NaN and the used rows' state stays as given.
+ * Arithmetic: everything per pair in fp32 (expf, logf and the division are the precise ones), added in fp32 over the 4 columns a
+ * thread holds of a tile, in fp64 over the tiles of a split in order and over the 16 threads of a row (a fixed tree); the splits in
+ * split order, Z and the KL (thread t of a block the rows t, t + 256, ..., then the 256 sums in order), the gradient and the
+ * update in fp64.  sum p log p does not depend on Y: the first pass of a call forms it and the later ones reuse it.
+ * The state is fp32 between iterations, so a iterations followed by b more from the returned (y, vel, gain) with it0 = a give the
+ * bits of a + b iterations run with center = 0.  No atomics, one fixed order of every sum; the split plan is a function of rows
+ * alone (avae_embed_plan): the outputs are a pure function of the input bits -- the same on any stream and on repetition.
+ * The whole loop is enqueued on `stream` with no host synchronisation inside: k_embed_scan once, then two launches per pass
+ * (k_embed_forces on a grid of row tiles x splits, one partial per (row, split) to a scratch; k_embed_update).  The scratch is
+ * allocated by the first call of either entry (one allocation of the plan's upper bound, 7,406,720 bytes) and freed by
+ * avae_destroy; avae_workspace_bytes is unchanged.
+ * rows == 0 is a no-op.  Errors (with a message naming the argument, outputs untouched): rows < 0 or > 65,536, an unknown metric,
+ * perplexity outside [1, rows - 1], tol <= 0, max_tries < 1, n_iters < 0, it0 < 0, learning_rate <= 0 or not finite, a NULL
+ * mu_dev, a NULL logvar_dev under SYMKL, any other NULL pointer but grad_dev.
+ * As avae_latent_topk, the calls change nothing a training step reads, work on any replica with no collective, and inside
+ * avae_use_averaged (they only see latents). */
+int avae_embed_calibrate(avae_handle* h,
+                         const float* mu_dev, const float* logvar_dev, int32_t rows, int32_t metric,
+                         double perplexity, double tol, int32_t max_tries,
+                         float* beta_dev, float* shift_dev, float* norm_dev, int32_t* tries_dev,
+                         int32_t* n_used_dev, void* stream);
+int avae_embed_iterate(avae_handle* h,
+                       const float* mu_dev, const float* logvar_dev, int32_t rows, int32_t metric,
+                       const float* beta_dev, const float* shift_dev, const float* norm_dev,
+                       float* y_dev, float* vel_dev, float* gain_dev,
+                       int32_t it0, int32_t n_iters, float learning_rate,
+                       float early_exaggeration, int32_t exaggeration_iters, float momentum0, float momentum1,
+                       int32_t center, double* kl_dev, float* grad_dev, void* stream);
+/* Host-only (no GPU): the launch shapes of k_embed_forces, a function of rows alone.  tiles = ceil(rows / row_tile) tiles of
+ * row_tile = 64 rows; the streamed side is cut into n_splits = ceil(tiles / tiles_per_split) splits of tiles_per_split =
+ * ceil(tiles / min(tiles, ceil(1024 / tiles))) tiles -- about 1024 workgroups, so small inputs are split too (32 tiles: 32 splits
+ * of one); split s covers the tiles [s * tiles_per_split, min(tiles, (s + 1) * tiles_per_split)), none is empty; rows == 0:
+ * n_splits = 0.  scratch_bytes = 66,688 + 7 * rows * n_splits * 8 (rows * n_splits <= 131,072).  Any output pointer may be NULL;
+ * rows < 0 or > 65,536 is an error, the message in avae_last_error(NULL). */
+int avae_embed_plan(const avae_config* cfg, int32_t rows,
+                    int32_t* row_tile, int32_t* n_splits, int32_t* tiles_per_split, size_t* scratch_bytes);
+
 /* save_model / restore_model (vae_assoc.py:427-463): own flat file (config echo + params + Adam
  * slots + step; with parameter averaging on also its settings and the average, see avae_set_ema);
  * TF .ckpt files cannot be read offline. */

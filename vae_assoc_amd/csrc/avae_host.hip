@@ -5,6 +5,7 @@
 #include "avae_retrieve.h"
 #include "avae_latent_stats.h"
 #include "avae_gmm.h"
+#include "avae_embed.h"
 #include "avae_aggpost.h"
 #include "../../include/avae.h"
 
@@ -287,6 +288,7 @@ struct avae_handle {
     DevBuf stats_buf;                       // avae_latent_stats: one partial per (row slice, work item) (kStatsScratchBytes)
     DevBuf agg_buf;                         // avae_agg_logpdf: the (query, slice, column) pairs of one chunk of queries (kAggScratchBytes)
     DevBuf gmm_buf;                         // avae_gmm_fit: one partial per row slice and two parameter sets (kGmmScratchBytes)
+    DevBuf embed_buf;                       // avae_embed_*: used bytes, block counts and one partial per (row, split) (kEmbedScratchBytes)
     size_t off_chain = 0;
     size_t off_consts = 0, off_conv_tab = 0;   // 32 B {zeros | one, 0...}; device copy of conv_tab
     std::vector<ConvA> conv_tab;             // implicit patch matrices of the training plan
@@ -4442,6 +4444,122 @@ int avae_gmm_score(avae_handle* h, const float* mu_dev, const float* logvar_dev,
         a.w_in = weights_dev; a.m_in = means_dev; a.s_in = logvars_dev;
         a.ll = ll_dev; a.component = component_dev; a.resp = resp_dev;
         timed_launch(h, s, "gmm_score", [&] { launch_gmm_estep(a, s); });
+    });
+}
+
+// ---- 2-D t-SNE map of the posteriors (include/avae.h, avae_embed.h)
+static bool check_embed_shape(const std::string& w, int32_t rows, int32_t metric) {
+    if (rows < 0) throw Err(w + ": rows must be >= 0");
+    if (rows > kEmbedMaxRows)
+        throw Err(w + ": rows = " + std::to_string(rows) + " is more than " + std::to_string(kEmbedMaxRows) + " (the work is quadratic in rows)");
+    if (metric != AVAE_METRIC_SYMKL && metric != AVAE_METRIC_L2)
+        throw Err(w + ": metric = " + std::to_string(metric) + " is neither AVAE_METRIC_SYMKL nor AVAE_METRIC_L2");
+    return metric == AVAE_METRIC_SYMKL;
+}
+
+int avae_embed_plan(const avae_config* cfg, int32_t rows, int32_t* row_tile, int32_t* n_splits, int32_t* tiles_per_split,
+                    size_t* scratch_bytes) {
+    try {
+        if (!cfg) throw Err("null argument");
+        check_config(*cfg);
+        check_embed_shape("avae_embed_plan", rows, AVAE_METRIC_L2);
+        const EmbedPlan p = embed_plan(rows);
+        if (row_tile) *row_tile = p.row_tile;
+        if (n_splits) *n_splits = p.n_splits;
+        if (tiles_per_split) *tiles_per_split = p.tiles_per_split;
+        if (scratch_bytes) *scratch_bytes = p.scratch_bytes;
+        return 0;
+    } catch (const std::exception& e) { g_create_error = e.what(); return 2; }
+}
+
+// the fields every launch of the family reads, and the scratch
+static EmbedArgs embed_args(avae_handle* h, const std::string& w, const float* mu_dev, const float* logvar_dev, int32_t rows, bool kl) {
+    static_assert(kEmbedMaxNz >= 64, "check_config bounds n_z by 64");
+    const EmbedPlan p = embed_plan(rows);
+    const int metric = kl ? AVAE_METRIC_SYMKL : AVAE_METRIC_L2;
+    if ((size_t)rows * p.n_splits > kEmbedMaxSlots || p.scratch_bytes > kEmbedScratchBytes || embed_lds_bytes(h->nz, metric) > 160 * 1024)
+        throw Err("internal error: " + w + " plans more scratch or LDS than its bound");
+    unsigned char* base = static_cast<unsigned char*>(h->embed_buf.ensure(kEmbedScratchBytes));
+    EmbedArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.mu = mu_dev; a.lv = kl ? logvar_dev : nullptr;           // the L2 metric never reads the log-variances
+    a.rows = rows; a.nz = h->nz; a.metric = metric;
+    a.n_splits = p.n_splits; a.tiles_per_split = p.tiles_per_split;
+    a.used = base;
+    a.count = reinterpret_cast<int32_t*>(base + kEmbedOffCount);
+    a.mean = reinterpret_cast<double*>(base + kEmbedOffMean);
+    a.part = reinterpret_cast<double*>(base + kEmbedOffPart);
+    a.part_stride = (size_t)rows * p.n_splits;
+    a.plogp = a.part + (size_t)kEmbedParts * a.part_stride;
+    return a;
+}
+
+int avae_embed_calibrate(avae_handle* h, const float* mu_dev, const float* logvar_dev, int32_t rows, int32_t metric, double perplexity,
+                         double tol, int32_t max_tries, float* beta_dev, float* shift_dev, float* norm_dev, int32_t* tries_dev,
+                         int32_t* n_used_dev, void* stream) {
+    return guarded(h, [&] {
+        const std::string w = "avae_embed_calibrate";
+        const bool kl = check_embed_shape(w, rows, metric);
+        if (rows == 0) return;
+        if (!(perplexity >= 1.0 && perplexity <= (double)(rows - 1)))
+            throw Err(w + ": perplexity must be in [1, rows - 1] = [1, " + std::to_string(rows - 1) + "]");
+        if (!(tol > 0.0)) throw Err(w + ": tol must be > 0");
+        if (max_tries < 1) throw Err(w + ": max_tries must be >= 1");
+        if (!mu_dev) throw Err(w + ": mu_dev is NULL");
+        if (kl && !logvar_dev) throw Err(w + ": logvar_dev is NULL (AVAE_METRIC_SYMKL reads the log-variances)");
+        if (!beta_dev) throw Err(w + ": beta_dev is NULL");
+        if (!shift_dev) throw Err(w + ": shift_dev is NULL");
+        if (!norm_dev) throw Err(w + ": norm_dev is NULL");
+        if (!tries_dev) throw Err(w + ": tries_dev is NULL");
+        if (!n_used_dev) throw Err(w + ": n_used_dev is NULL");
+        EmbedArgs a = embed_args(h, w, mu_dev, logvar_dev, rows, kl);
+        hipStream_t s = on_stream(h, stream);
+        a.beta = beta_dev; a.shift = shift_dev; a.norm = norm_dev; a.tries = tries_dev; a.n_used = n_used_dev;
+        a.log_perp = std::log(perplexity); a.tol = tol; a.max_tries = max_tries;
+        timed_launch(h, s, "embed_scan", [&] { launch_embed_scan(a, s); });
+        timed_launch(h, s, "embed_calibrate", [&] { launch_embed_calibrate(a, s); });
+    });
+}
+
+int avae_embed_iterate(avae_handle* h, const float* mu_dev, const float* logvar_dev, int32_t rows, int32_t metric, const float* beta_dev,
+                       const float* shift_dev, const float* norm_dev, float* y_dev, float* vel_dev, float* gain_dev, int32_t it0,
+                       int32_t n_iters, float learning_rate, float early_exaggeration, int32_t exaggeration_iters, float momentum0,
+                       float momentum1, int32_t center, double* kl_dev, float* grad_dev, void* stream) {
+    return guarded(h, [&] {
+        const std::string w = "avae_embed_iterate";
+        const bool kl = check_embed_shape(w, rows, metric);
+        if (rows == 0) return;
+        if (n_iters < 0) throw Err(w + ": n_iters must be >= 0");
+        if (it0 < 0) throw Err(w + ": it0 must be >= 0");
+        if (!(learning_rate > 0.0f) || !std::isfinite(learning_rate)) throw Err(w + ": learning_rate must be positive and finite");
+        if (!mu_dev) throw Err(w + ": mu_dev is NULL");
+        if (kl && !logvar_dev) throw Err(w + ": logvar_dev is NULL (AVAE_METRIC_SYMKL reads the log-variances)");
+        if (!beta_dev) throw Err(w + ": beta_dev is NULL");
+        if (!shift_dev) throw Err(w + ": shift_dev is NULL");
+        if (!norm_dev) throw Err(w + ": norm_dev is NULL");
+        if (!y_dev) throw Err(w + ": y_dev is NULL");
+        if (!vel_dev) throw Err(w + ": vel_dev is NULL");
+        if (!gain_dev) throw Err(w + ": gain_dev is NULL");
+        if (!kl_dev) throw Err(w + ": kl_dev is NULL");
+        EmbedArgs a = embed_args(h, w, mu_dev, logvar_dev, rows, kl);
+        hipStream_t s = on_stream(h, stream);
+        a.beta = const_cast<float*>(beta_dev); a.shift = const_cast<float*>(shift_dev); a.norm = const_cast<float*>(norm_dev);
+        a.y = y_dev; a.vel = vel_dev; a.gain = gain_dev; a.lr = learning_rate;
+        timed_launch(h, s, "embed_scan", [&] { launch_embed_scan(a, s); });
+        for (int i = 0; i <= n_iters; ++i) {
+            const long long t = (long long)it0 + i;
+            const bool last = i == n_iters;
+            a.first_pass = i == 0 ? 1 : 0;
+            a.evaluate = last ? 1 : 0;
+            a.center = last && center != 0 && n_iters > 0 ? 1 : 0;
+            a.alpha = t < exaggeration_iters ? early_exaggeration : 1.0f;
+            a.mom = t < exaggeration_iters ? momentum0 : momentum1;
+            a.kl = kl_dev + i;
+            a.grad = i == 0 ? grad_dev : nullptr;
+            timed_launch(h, s, "embed_forces", [&] { launch_embed_forces(a, s); });
+            timed_launch(h, s, "embed_update", [&] { launch_embed_update(a, s); });
+            if (a.center) timed_launch(h, s, "embed_center", [&] { launch_embed_center(a, s); });
+        }
     });
 }
 

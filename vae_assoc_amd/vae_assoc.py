@@ -432,6 +432,115 @@ def latent_prior_args(posteriors, n_components, n_iters, init, seed, var_floor, 
     return mu, lv, K, int(n_iters), vf, None, rows[torch.from_numpy(pick.astype(np.int64))], was_np
 
 
+def embed_args(posteriors, perplexity, n_iters, metric, learning_rate, early_exaggeration, exaggeration_iters, momentum, init,
+               seed, state, n_z, device):
+    """The arguments of ``embed_latents`` checked and marshalled -> dict(mu, logvar (None under ``metric="l2"``), metric id, rows,
+    n_used, perplexity, n_iters, learning_rate, early_exaggeration, exaggeration_iters, momentum, y, vel, gain, it0, calibration
+    (None: to be computed), was_numpy).  ``posteriors`` is a ``(mu, logvar)`` pair of ``[N, n_z]`` arrays or tensors or a list of
+    such pairs, concatenated in list order, as in ``latent_prior_args``; ``logvar=None`` needs ``metric="l2"``.  ``y`` is a copy of
+    ``init`` or, for ``init=None``, ``np.random.default_rng(seed).normal(0, 1e-4, (N, 2))``; ``state`` (what ``embed_latents``
+    returned) replaces velocity, gains, iteration number and calibration, and ``init`` then defaults to its embedding.
+    ``learning_rate="auto"`` is ``max(F / 48, 50)`` over the F rows without a non-finite entry.  Every shape or value error is a
+    ``ValueError`` raised here, ahead of any launch; touches neither a model nor the library (``device="cpu"`` works)."""
+    if not isinstance(metric, str) or metric.lower() not in _capi.METRIC_IDS:
+        raise ValueError("metric must be 'symkl' or 'l2', got %r" % (metric,))
+    mid = _capi.METRIC_IDS[metric.lower()]
+    if isinstance(n_iters, bool) or not isinstance(n_iters, (int, np.integer)) or n_iters < 0:
+        raise ValueError("n_iters must be an integer >= 0, got %r" % (n_iters,))
+    if isinstance(exaggeration_iters, bool) or not isinstance(exaggeration_iters, (int, np.integer)) or exaggeration_iters < 0:
+        raise ValueError("exaggeration_iters must be an integer >= 0, got %r" % (exaggeration_iters,))
+
+    def number(x, name, lo=None):
+        try:
+            v = float(x)
+        except (TypeError, ValueError):
+            v = float("nan")
+        if isinstance(x, bool) or not np.isfinite(v) or not np.isfinite(np.float32(v)) or (lo is not None and not v > lo):
+            raise ValueError("%s must be a finite number%s, got %r" % (name, "" if lo is None else " > %g" % lo, x))
+        return v
+    ee = number(early_exaggeration, "early_exaggeration", 0.0)
+    if not isinstance(momentum, (tuple, list)) or len(momentum) != 2:
+        raise ValueError("momentum must be a pair (during the early exaggeration, after it), got %r" % (momentum,))
+    mom = (number(momentum[0], "momentum[0]"), number(momentum[1], "momentum[1]"))
+    pairs = [posteriors] if _is_pair(posteriors) else posteriors
+    if not isinstance(pairs, (list, tuple)) or not pairs or not all(_is_pair(p) for p in pairs):
+        raise ValueError("posteriors must be a (mu, logvar) pair or a non-empty list of such pairs, got %r" % type(posteriors).__name__)
+    if mid == _capi.METRIC_SYMKL and any(p[1] is None for p in pairs):
+        raise ValueError("posteriors: logvar is None, and metric='symkl' reads the log-variances (metric='l2' does not)")
+    mus, lvs = [], []
+    for i, (mu, lv) in enumerate(pairs):
+        try:
+            t = dev_dense(mu, n_z, device, name="mu")
+            mus.append(t)
+            if mid == _capi.METRIC_SYMKL:
+                lvs.append(dev_dense(lv, n_z, device, t.shape[0], "as mu", name="logvar"))
+        except ValueError as e:
+            raise ValueError("posteriors[%d]: %s" % (i, e))
+    was_np = not torch.is_tensor(pairs[0][0])
+    mu = mus[0] if len(mus) == 1 else torch.cat(mus).contiguous()
+    lv = None if not lvs else (lvs[0] if len(lvs) == 1 else torch.cat(lvs).contiguous())
+    N = int(mu.shape[0])
+    if N > _capi.EMBED_MAX_ROWS:
+        raise ValueError("%d rows are more than the %d one map takes (the work is quadratic in the rows)" % (N, _capi.EMBED_MAX_ROWS))
+    fin = torch.isfinite(mu).all(dim=1)
+    if lv is not None:
+        fin &= torch.isfinite(lv).all(dim=1)
+    F = int(fin.sum().item())
+    perp = number(perplexity, "perplexity")
+    if N < 2 or not 1.0 <= perp <= F - 1:
+        raise ValueError("perplexity = %r must be in [1, F - 1] for the F = %d rows without a non-finite entry (of %d rows)"
+                         % (perplexity, F, N))
+    if isinstance(learning_rate, str):
+        if learning_rate != "auto":
+            raise ValueError("learning_rate must be 'auto' or a positive number, got %r" % (learning_rate,))
+        lr = max(F / 48.0, 50.0)
+    else:
+        lr = number(learning_rate, "learning_rate", 0.0)
+
+    def map_array(x, name):
+        t = dev_dense(x, 2, device, N, "as the posteriors", name=name)
+        if t is None:
+            raise ValueError("%s is None" % name)
+        return t.clone()
+
+    def row_vector(x, name):
+        t = torch.as_tensor(x if torch.is_tensor(x) else np.asarray(x, dtype=np.float32)).to(device=device, dtype=torch.float32)
+        if tuple(t.shape) != (N,):
+            raise ValueError("%s must be [%d] (as the posteriors), got %s" % (name, N, tuple(t.shape)))
+        return t.contiguous().clone()
+    it0, calib, vel, gain = 0, None, None, None
+    if state is not None:
+        keys = ("velocity", "gains", "iteration", "beta", "shift", "norm")
+        if not isinstance(state, dict) or any(k not in state for k in keys + ("embedding",)):
+            raise ValueError("state must be the state dict embed_latents returned (keys embedding, %s), got %r"
+                             % (", ".join(keys), sorted(state) if isinstance(state, dict) else type(state).__name__))
+        it0 = state["iteration"]
+        if isinstance(it0, bool) or not isinstance(it0, (int, np.integer)) or it0 < 0:
+            raise ValueError("state: iteration must be an integer >= 0, got %r" % (it0,))
+        try:
+            vel, gain = map_array(state["velocity"], "velocity"), map_array(state["gains"], "gains")
+            calib = tuple(row_vector(state[k], k) for k in ("beta", "shift", "norm"))
+            if init is None:
+                init = state["embedding"]
+        except ValueError as e:
+            raise ValueError("state: %s" % e)
+    if init is None:
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or seed < 0:
+            raise ValueError("seed must be an integer >= 0, got %r" % (seed,))
+        y = torch.from_numpy(np.random.default_rng(int(seed)).normal(0.0, 1e-4, (N, 2)).astype(np.float32)).to(device)
+    else:
+        try:
+            y = map_array(init, "init")
+        except ValueError as e:
+            raise ValueError("init: %s" % e)
+    if vel is None:
+        vel = torch.zeros((N, 2), dtype=torch.float32, device=device)
+        gain = torch.ones((N, 2), dtype=torch.float32, device=device)
+    return {"mu": mu, "logvar": lv, "metric": mid, "rows": N, "n_used": F, "perplexity": perp, "n_iters": int(n_iters),
+            "learning_rate": lr, "early_exaggeration": ee, "exaggeration_iters": int(exaggeration_iters), "momentum": mom,
+            "y": y, "vel": vel, "gain": gain, "it0": int(it0), "calibration": calib, "was_numpy": was_np}
+
+
 def latent_score_args(z, prior, n_z, device):
     """The arguments of ``latent_prior_score`` checked and marshalled -> (mu, logvar or None, weights, means, logvars,
     was_numpy).  ``z`` is a ``[N, n_z]`` array or tensor (points) or a ``(mu, logvar)`` pair."""
@@ -1191,6 +1300,63 @@ class AssocVariationalAutoEncoder(object):
         eps = torch.randn((int(n), self.n_z), generator=gen, device=self.device, dtype=torch.float32)
         z = m[comp] + torch.exp(0.5 * s[comp]) * eps
         return self._like_input(was_np)(z)
+
+    # ------------------------------------------------------------------ 2-D map of the posteriors
+    def embed_latents(self, posteriors, perplexity=30.0, n_iters=1000, metric="symkl", learning_rate="auto", early_exaggeration=12.0,
+                      exaggeration_iters=250, momentum=(0.5, 0.8), init=None, seed=0, state=None):
+        """A 2-D t-SNE map of posteriors, computed on the device (avae_embed_calibrate / avae_embed_iterate in include/avae.h):
+        where the codes lie, as a picture.  The N x N affinities are never stored; the sums are exact (no Barnes-Hut) and the
+        result is bit-reproducible.
+
+        ``posteriors`` is a ``(mu, logvar)`` pair as ``posterior`` returns it, or a list of such pairs whose rows are concatenated
+        into one map.  ``metric="symkl"`` builds the affinities from KL(q_i || q_j) + KL(q_j || q_i), the divergence the
+        association term trains on (variances included); ``"l2"`` from the squared distance of the means (``logvar`` may then be
+        None).  ``learning_rate="auto"`` is ``max(F / 48, 50)``; ``init=None`` starts at
+        ``np.random.default_rng(seed).normal(0, 1e-4, (N, 2))``.  A row with a non-finite entry is skipped and comes back NaN.
+        At most 65,536 rows.
+
+        Returns ``dict(embedding [N, 2] float32, kl [n_iters + 1] float64, beta [N] float32, n_used int, state)``: ``kl[s]`` is
+        the divergence of the map entering iteration s, ``kl[-1]`` that of the returned one (centred on the used rows' mean);
+        ``state`` (embedding, velocity, gains, iteration, calibration) passed back as ``state=`` continues the run for
+        ``n_iters`` more iterations without calibrating again.  NumPy in gives NumPy out, tensors in give device tensors out."""
+        a = embed_args(posteriors, perplexity, n_iters, metric, learning_rate, early_exaggeration, exaggeration_iters, momentum, init,
+                       seed, state, self.n_z, self.device)
+        mu, lv, N = a["mu"], a["logvar"], a["rows"]
+        if a["calibration"] is None:
+            beta, shift, norm = (torch.empty((N,), dtype=torch.float32, device=self.device) for _ in range(3))
+            tries = torch.empty((N,), dtype=torch.int32, device=self.device)
+            n_used = torch.empty((1,), dtype=torch.int32, device=self.device)
+            _capi.check(self._h, self._L.avae_embed_calibrate(self._h, mu.data_ptr(), ptr(lv), N, a["metric"], a["perplexity"], 1e-5, 64,
+                                                              beta.data_ptr(), shift.data_ptr(), norm.data_ptr(), tries.data_ptr(),
+                                                              n_used.data_ptr(), self._stream()), "avae_embed_calibrate")
+        else:
+            beta, shift, norm = a["calibration"]
+        y, vel, gain, T = a["y"], a["vel"], a["gain"], a["n_iters"]
+        kl = torch.empty((T + 1,), dtype=torch.float64, device=self.device)
+        _capi.check(self._h, self._L.avae_embed_iterate(self._h, mu.data_ptr(), ptr(lv), N, a["metric"], beta.data_ptr(), shift.data_ptr(),
+                                                        norm.data_ptr(), y.data_ptr(), vel.data_ptr(), gain.data_ptr(), a["it0"], T,
+                                                        a["learning_rate"], a["early_exaggeration"], a["exaggeration_iters"],
+                                                        a["momentum"][0], a["momentum"][1], 1, kl.data_ptr(), None, self._stream()),
+                    "avae_embed_iterate")
+        conv = self._like_input(a["was_numpy"])
+        out_state = {"embedding": conv(y), "velocity": conv(vel), "gains": conv(gain), "iteration": a["it0"] + T,
+                     "beta": conv(beta), "shift": conv(shift), "norm": conv(norm)}
+        return {"embedding": out_state["embedding"], "kl": conv(kl), "beta": out_state["beta"], "n_used": a["n_used"], "state": out_state}
+
+    def latent_map(self, X, **kw):
+        """Encode every modality of ``X`` (a list over modalities with equal row counts N) with ``posterior`` and embed all M * N
+        codes in ONE map (``embed_latents``, which takes ``kw``): the reference's picture of associated encodings -- paired rows
+        of a well-associated model land on each other.  Returns ``embed_latents``' dict with ``embedding`` reshaped to
+        ``[M, N, 2]``: ``embedding[m, n]`` is where modality m's code of row n lies.  Inside ``with model.averaged():`` it maps the
+        averaged encoders' codes."""
+        ts, rows, was_np, _, _ = dev_modalities(X, self._widths, self.device)
+        post = [self._encode(m, t, want_logvar=True) for m, t in enumerate(ts)]
+        out = self.embed_latents(post, **kw)
+        conv = self._like_input(bool(was_np))
+        out = {k: (conv(v) if torch.is_tensor(v) else v) for k, v in out.items()}
+        out["state"] = {k: (conv(v) if torch.is_tensor(v) else v) for k, v in out["state"].items()}
+        out["embedding"] = out["embedding"].reshape(len(post), rows, 2)
+        return out
 
     def generate(self, z_mu=None):
         """Generate data by sampling from latent space: decoder only, z fed directly; returns the
