@@ -346,6 +346,7 @@ struct avae_handle {
     unsigned draw_id = 0;                   // forward-only calls that drew their own eps (next_draw: keys the generator, a fresh draw per call)
     bool timing = false;
     bool debug_sync = false;
+    bool plan_dump = false;                 // AVAE_PLAN_DUMP=1: serve_plan prints the plan it builds (nothing else changes)
     std::vector<std::string> tnames;
     std::vector<TimingRec> trecs;
 
@@ -2106,6 +2107,21 @@ Launch relocated(const avae_handle* h, const Launch& L0, int j, const HyperEntry
     return L;
 }
 
+// One launch of a plan as the dumps print it (AVAE_DEBUG_SYNC=1: every launch that runs; AVAE_PLAN_DUMP=1: a serve plan when it is built)
+void dump_launch(const Launch& L) {
+    std::fprintf(stderr, "[avae] launch %s type=%d cfg=%d items=%d blocks=%d\n", L.name.c_str(), L.type, L.cfg, L.count, L.blocks);
+    for (int i = 0; i < L.args.n_items && L.type == 0; ++i)
+        std::fprintf(stderr, "        item kind=%d M=%d N=%d K=%d lda=%d ldb=%d tiles=%dx%d\n", L.args.items[i].kind, L.args.items[i].M,
+                     L.args.items[i].N, L.args.items[i].K, L.args.items[i].lda, L.args.items[i].ldb, L.args.items[i].tiles_m, L.args.items[i].tiles_n);
+    for (int i = 0; i < L.ga.n_seg && L.type == 1; ++i)
+        std::fprintf(stderr, "        gather B=%d IH=%d Cin=%d OH=%d k=%d so=%d d=%d pad=%d sb=%d sp=%d ones=%d ldp=%d tiles=%dx%d\n", L.ga.seg[i].g.B, L.ga.seg[i].g.IH,
+                     L.ga.seg[i].g.Cin, L.ga.seg[i].g.OH, L.ga.seg[i].g.k, L.ga.seg[i].g.so, L.ga.seg[i].g.d, L.ga.seg[i].g.pad, L.ga.seg[i].g.src_sb, L.ga.seg[i].g.src_sp,
+                     L.ga.seg[i].g.ones, L.ga.seg[i].ldp, L.ga.seg[i].tiles_r, L.ga.seg[i].tiles_c);
+    for (int i = 0; i < L.ca.n_seg && L.type == 2; ++i)
+        std::fprintf(stderr, "        col2im B=%d IH=%d Cin=%d OH=%d k=%d lddp=%d lda=%d g0=%p tiles=%dx%d\n", L.ca.seg[i].g.B, L.ca.seg[i].g.IH, L.ca.seg[i].g.Cin,
+                     L.ca.seg[i].g.OH, L.ca.seg[i].g.k, L.ca.seg[i].lddp, L.ca.seg[i].lda, (const void*)L.ca.seg[i].g0, L.ca.seg[i].tiles_r, L.ca.seg[i].tiles_c);
+}
+
 void run_launch(avae_handle* h, const Launch& L, hipStream_t s, unsigned long long* stamps, int stamp) {
     Timed t(h, s, L.name);
     if (L.type == 1) launch_gather(h->cfg.compute_dtype, L.ga, L.blocks, s);
@@ -2127,17 +2143,7 @@ void run_launch(avae_handle* h, const Launch& L, hipStream_t s, unsigned long lo
     else launch_grouped(h->cfg.compute_dtype, L.cfg, L.args, L.grid_x, L.grid_y, L.lds, h->state(), s, stamps, stamp);
     LAUNCH_OK(L.name);
     if (h->debug_sync) {      // AVAE_DEBUG_SYNC=1: name the launch a fault belongs to
-        std::fprintf(stderr, "[avae] launch %s type=%d cfg=%d items=%d blocks=%d\n", L.name.c_str(), L.type, L.cfg, L.count, L.blocks);
-        for (int i = 0; i < L.args.n_items && L.type == 0; ++i)
-            std::fprintf(stderr, "        item kind=%d M=%d N=%d K=%d lda=%d ldb=%d tiles=%dx%d\n", L.args.items[i].kind, L.args.items[i].M,
-                         L.args.items[i].N, L.args.items[i].K, L.args.items[i].lda, L.args.items[i].ldb, L.args.items[i].tiles_m, L.args.items[i].tiles_n);
-        for (int i = 0; i < L.ga.n_seg && L.type == 1; ++i)
-            std::fprintf(stderr, "        gather B=%d IH=%d Cin=%d OH=%d k=%d so=%d d=%d pad=%d sb=%d sp=%d ones=%d ldp=%d tiles=%dx%d\n", L.ga.seg[i].g.B, L.ga.seg[i].g.IH,
-                         L.ga.seg[i].g.Cin, L.ga.seg[i].g.OH, L.ga.seg[i].g.k, L.ga.seg[i].g.so, L.ga.seg[i].g.d, L.ga.seg[i].g.pad, L.ga.seg[i].g.src_sb, L.ga.seg[i].g.src_sp,
-                         L.ga.seg[i].g.ones, L.ga.seg[i].ldp, L.ga.seg[i].tiles_r, L.ga.seg[i].tiles_c);
-        for (int i = 0; i < L.ca.n_seg && L.type == 2; ++i)
-            std::fprintf(stderr, "        col2im B=%d IH=%d Cin=%d OH=%d k=%d lddp=%d lda=%d g0=%p tiles=%dx%d\n", L.ca.seg[i].g.B, L.ca.seg[i].g.IH, L.ca.seg[i].g.Cin,
-                         L.ca.seg[i].g.OH, L.ca.seg[i].g.k, L.ca.seg[i].lddp, L.ca.seg[i].lda, (const void*)L.ca.seg[i].g0, L.ca.seg[i].tiles_r, L.ca.seg[i].tiles_c);
+        dump_launch(L);
         std::fflush(stderr);
         HIP_OK(hipStreamSynchronize(s));
     }
@@ -2825,6 +2831,13 @@ avae_handle::Serve& serve_plan(avae_handle* h, int bucket) {
     sv.in = a;                                                   // the per-call staging launch (ahead of the graph)
     if (!(sv.fused_in && sv.lean_in))                            // serve_call replays a graph of the remaining launches
         sv.graph = capture(h, [&](hipStream_t cs) { run_launches(h, sv.launches, cs); }).exec;
+    if (h->plan_dump) {       // AVAE_PLAN_DUMP=1: the route and every launch of the plan, the staging launch first
+        std::fprintf(stderr, "[avae] serve plan bucket=%d fused_in=%d lean_in=%d in_lean_grid=%d\n", bucket, sv.fused_in ? 1 : 0,
+                     sv.lean_in ? 1 : 0, sv.in_lean_grid);
+        if (sv.fused_in) dump_launch(sv.in_launch);
+        for (const Launch& L : sv.launches) dump_launch(L);
+        std::fflush(stderr);
+    }
     return sv;
 }
 
@@ -3375,6 +3388,7 @@ int avae_create(const avae_config* cfg, avae_handle** out) {
         h->cfg = *cfg;
         if (const char* e = std::getenv("AVAE_DEBUG_SYNC")) h->debug_sync = e[0] == '1';
         if (h->debug_sync) h->cfg.use_graph = 0;
+        if (const char* e = std::getenv("AVAE_PLAN_DUMP")) h->plan_dump = e[0] == '1';
         if (h->cfg.beta1 == 0.f && h->cfg.beta2 == 0.f && h->cfg.adam_eps == 0.f) { h->cfg.beta1 = 0.9f; h->cfg.beta2 = 0.999f; h->cfg.adam_eps = 1e-8f; }
         int ndev = 0;
         HIP_OK(hipGetDeviceCount(&ndev));
