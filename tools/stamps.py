@@ -2,7 +2,9 @@
 """Diagnostic (not part of the product): builds libavae with -DAVAE_STAMPS into
 gpurun_out/stamps/, runs the bench workload and prints, per launch of one graph-replayed step,
 where a block's time goes (item lookup / first tile / K loop / epilogue), the block start spread
-and the shader clock.  Read the SHARES, not the absolute length (stamps fence the schedule)."""
+and the shader clock.  Read the SHARES, not the absolute length (stamps fence the schedule).
+The build uses the project's own sources and flags.  $STAMPS_OUT names another build directory; `stamps.py c2 --build-only` stops
+after the build, and a run that finds a library in the build directory does not compile again."""
 import ctypes as C
 import os
 import shutil
@@ -17,14 +19,20 @@ sys.path.insert(0, ROOT)
 
 def main():
     cfg = sys.argv[1] if len(sys.argv) > 1 else "c2"
+    import __graft_entry__ as g
     out = os.path.join(ROOT, "gpurun_out", "stamps")
+    if os.environ.get("STAMPS_OUT"):      # another place for the stamps build (--build-only leaves it there for a later run)
+        out = os.environ["STAMPS_OUT"]
     pkg = os.path.join(out, "vae_assoc_amd")
-    if os.path.exists(out):
-        shutil.rmtree(out)
-    shutil.copytree(os.path.join(ROOT, "vae_assoc_amd"), pkg, ignore=shutil.ignore_patterns("*.so", "__pycache__"))
-    src = [os.path.join(ROOT, "vae_assoc_amd", "csrc", f) for f in ("avae_kernels.hip", "avae_host.hip", "avae_comm.hip", "avae_retrieve.hip")]
-    subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-DAVAE_STAMPS"] + os.environ.get("EXTRA_DEFS", "").split()
-                   + src + ["-o", os.path.join(pkg, "libavae.so")], check=True)
+    if not os.path.exists(os.path.join(pkg, "libavae.so")):
+        if os.path.exists(out):
+            shutil.rmtree(out)
+        shutil.copytree(os.path.join(ROOT, "vae_assoc_amd"), pkg, ignore=shutil.ignore_patterns("*.so", "*.so.*", "__pycache__"))
+        src = [os.path.join(ROOT, "vae_assoc_amd", "csrc", f) for f in g.SOURCES]
+        subprocess.run(["/opt/rocm/bin/hipcc"] + g.FLAGS + ["-DAVAE_STAMPS"] + os.environ.get("EXTRA_DEFS", "").split()
+                       + src + ["-o", os.path.join(pkg, "libavae.so")], check=True)
+    if "--build-only" in sys.argv:
+        return
     import torch
     import bench
     sys.path.insert(0, out)      # after bench (which puts ROOT first): the stamps build must win

@@ -205,6 +205,46 @@ struct TnLaunchArgs {
 };
 static_assert(sizeof(TnLaunchArgs) <= 4096, "kernel arguments are passed by value: 4 KiB");
 
+// Per-workgroup launch descriptors (small-net training plan: the k_small and k_small_tn launches of a step).  What a workgroup's
+// prologue works out from its item -- the tile split over the XCDs, t / tiles_n, the operand rows of its tile -- depends on the
+// plan alone, so the host resolves it once per workgroup and launch into ONE 64-byte record of a device table: the kernel reads
+// record blockIdx.x in one scalar burst and goes on to its per-lane offsets.  Record x runs on XCD x % 8 (workgroups are dealt
+// round-robin), so XCD ownership of a tile is the order of the records; the grid is exactly the tile count.  The table's address
+// comes in the preloaded leading kernel arguments, and the launch before warms the records (DescWarm).
+struct alignas(64) SmallDesc {        // k_small_desc: hidden forward / hidden dgrad, 32x32 tile (m0, n0)
+    const unsigned char* a;          // A + m0 * lda * ES
+    const unsigned char* b;          // B + n0 * ldb * ES
+    void* out;                       // out0 + m0 * ld0 + n0
+    const void* aux;                 // dgrad: aux0 + m0 * ldx + n0 (the stored output act' is taken of)
+    int lda, ldb, ld0, ldx;
+    int nk;                          // K tiles
+    int mrem, nrem, xrem;            // M - m0, N - n0, ldx - n0
+};
+struct alignas(64) TnDesc {           // k_small_tn_desc: 64x64 tile (m0, n0) of one layer's weight gradient, Adam in the epilogue
+    const unsigned char* a;          // A + m0 * ES
+    const unsigned char* b;          // B + n0 * ES
+    float* out;                      // gradient + m0 * ld0 + n0 (theta / m / v at + TnDescArgs::d_*)
+    void* w;                         // W + m0 * ldw + n0
+    void* wt;                        // Wt + n0 * ldt + m0
+    int lda, ldb, ld0, ldw, ldt;
+    unsigned ext;                    // K tiles | min(M - m0, 64) << 16 | min(N - n0, 64) << 24  (one dword: a scalar load has no narrower form)
+    static constexpr unsigned pack(int nk, int mrem, int nrem) { return (unsigned)nk | (unsigned)(mrem < 64 ? mrem : 64) << 16 | (unsigned)(nrem < 64 ? nrem : 64) << 24; }
+};
+static_assert(sizeof(SmallDesc) == 64 && sizeof(TnDesc) == 64, "a descriptor is one cache line");
+// The records the NEXT launch of the run will read, n of them from `lines` on: workgroup x of this launch touches record
+// (x & 7) + 8 * (4 * (x >> 3) + wave), which a workgroup on its own XCD will read -- so the line waits in that XCD's L2.  A speed
+// matter only: n = 0, or a record nobody warmed, is the cold read it always was.
+struct DescWarm { const void* lines; int n; };
+struct TnDescArgs {                   // launch-wide constants of k_small_tn_desc (TnLaunchArgs' of the same names)
+    long long d_theta, d_m, d_v;
+    float beta1, beta2, eps;
+    const DevState* st;
+};
+// They are the first kTnDescHead lines of that launch's table, one copy per XCD (workgroup x reads copy x & 7, which the launch
+// before warmed on that XCD like any record); record x is line kTnDescHead + x, so it still runs on XCD (line index) % 8.
+constexpr int kTnDescHead = 8;
+static_assert(sizeof(TnDescArgs) <= 64, "a copy of the constants is one line of the table");
+
 struct DevState {
     long long step;          // number of applied Adam steps
     float last_cost;
@@ -632,6 +672,9 @@ void launch_small_head(int compute_dtype, int act, const LaunchArgs& args, int g
 void launch_small_tn(int compute_dtype, const TnLaunchArgs& args, int grid_x, int grid_y, hipStream_t s, unsigned long long* stamps, int launch_id);
 void launch_small_loss(int compute_dtype, const LaunchArgs& args, int grid_x, int grid_y, int lds_bytes, hipStream_t s, unsigned long long* stamps, int launch_id);
 void launch_small(int compute_dtype, const LaunchArgs& args, int grid_x, int grid_y, int lds_bytes, hipStream_t s, unsigned long long* stamps, int launch_id);
+void launch_small_desc(int compute_dtype, bool dgrad, int act, const SmallDesc* tab, int n_tiles, int lds_bytes, DescWarm warm, hipStream_t s,
+                       unsigned long long* stamps, int launch_id);
+void launch_small_tn_desc(int compute_dtype, const TnDesc* tab, int n_tiles, DescWarm warm, hipStream_t s, unsigned long long* stamps, int launch_id);
 void launch_reduce(const ReduceArgs& a, int n_blocks, hipStream_t s);
 void launch_chain2(int compute_dtype, const LaunchArgs& args, int grid_x, int grid_y, int lds_bytes, unsigned* counters, unsigned* err, hipStream_t s);
 

@@ -160,6 +160,11 @@ struct Launch {
     bool tn = false;              // K-major operands (the weight-gradient launches)
     LaunchArgs args{};
     TnLaunchArgs targs{};         // tn launches carry compact items instead
+    // Per-workgroup descriptors (build_descriptors: the training plan's k_small and k_small_tn launches).  desc_n > 0: the launch runs
+    // on desc_n records instead of its by-value arguments; staging set j's copy of them starts at byte desc_off + j * desc_stride of
+    // the handle's table, and desc_set is the set this copy of the launch runs on (relocated()).
+    int desc_n = 0, desc_set = 0;
+    size_t desc_off = 0, desc_stride = 0;
     GatherArgs ga{};
     Col2imArgs ca{};
     ReduceArgs ra{};
@@ -289,6 +294,7 @@ struct avae_handle {
     DevBuf agg_buf;                         // avae_agg_logpdf: the (query, slice, column) pairs of one chunk of queries (kAggScratchBytes)
     DevBuf gmm_buf;                         // avae_gmm_fit: one partial per row slice and two parameter sets (kGmmScratchBytes)
     DevBuf embed_buf;                       // avae_embed_*: used bytes, block counts and one partial per (row, split) (kEmbedScratchBytes)
+    DevBuf desc_buf;                        // the training plan's per-workgroup descriptors (build_descriptors; Launch::desc_off)
     size_t off_chain = 0;
     size_t off_consts = 0, off_conv_tab = 0;   // 32 B {zeros | one, 0...}; device copy of conv_tab
     std::vector<ConvA> conv_tab;             // implicit patch matrices of the training plan
@@ -2104,12 +2110,149 @@ Launch relocated(const avae_handle* h, const Launch& L0, int j, const HyperEntry
     }
     for (int i = 0; i < L.targs.n_items && L.type == 0; ++i) { TnItem& t = L.targs.items[i]; fix(t.A); fix(t.B); fix(t.out); }
     for (int i = 0; i < L.ga.n_seg && L.type == 1; ++i) fix(L.ga.seg[i].src);
+    L.desc_set = j;
     return L;
+}
+
+// Deals the tiles that the by-value kernels run on XCD p (lists[p], in their order there) into ONE order in which record x runs on
+// XCD x % 8 with exactly as many records as tiles: where an XCD's list is shorter than the others', the hole takes a tile from the
+// end of a longer one.
+template <typename D> std::vector<D> deal_to_xcds(const std::vector<D> (&lists)[8]) {
+    size_t total = 0;
+    for (const auto& l : lists) total += l.size();
+    std::vector<D> out(total), spill;
+    std::vector<char> set(total, 0);
+    for (int p = 0; p < 8; ++p)
+        for (size_t i = 0; i < lists[p].size(); ++i) {
+            const size_t x = 8 * i + p;
+            if (x < total) { out[x] = lists[p][i]; set[x] = 1; } else spill.push_back(lists[p][i]);
+        }
+    size_t k = 0;
+    for (size_t x = 0; x < total; ++x) if (!set[x]) out[x] = spill[k++];
+    return out;
+}
+
+// The records of one k_small launch (tile configuration 7, hidden forward or hidden dgrad items): every (item, tile) the by-value
+// kernel would run, resolved as its prologue resolves it.  Empty: the launch stays on its by-value arguments.
+std::vector<SmallDesc> small_descs(const avae_handle* h, const Launch& L) {
+    std::vector<SmallDesc> lists[8];
+    const int es = h->es;
+    for (int y = 0; y < L.args.n_items; ++y) {
+        const WorkItem& w = L.args.items[y];
+        if (w.kind != L.args.items[0].kind || w.act != L.args.items[0].act || (w.kind != K_FWD_HIDDEN && w.kind != K_DGRAD_HIDDEN)) return {};
+        const int nt = w.tiles_m * w.tiles_n, q = nt >> 3, r = nt & 7;
+        for (int part = 0; part < 8; ++part)
+            for (int idx = 0; idx < q + (part < r ? 1 : 0); ++idx) {
+                const int t = (part < r ? part * (q + 1) : r * (q + 1) + (part - r) * q) + idx;
+                const int tm = t / w.tiles_n, tn = t - tm * w.tiles_n, m0 = tm * 32, n0 = tn * 32;
+                SmallDesc d{};
+                d.a = static_cast<const unsigned char*>(w.A) + (size_t)m0 * w.lda * es;
+                d.b = static_cast<const unsigned char*>(w.B) + (size_t)n0 * w.ldb * es;
+                d.out = static_cast<unsigned char*>(w.out0) + ((size_t)m0 * w.ld0 + n0) * es;
+                d.aux = w.kind == K_DGRAD_HIDDEN ? static_cast<const unsigned char*>(w.aux0) + ((size_t)m0 * w.ldx + n0) * es : nullptr;
+                d.lda = w.lda; d.ldb = w.ldb; d.ld0 = w.ld0; d.ldx = w.ldx;
+                d.nk = (w.K * es) / kTileBytesK;
+                d.mrem = w.M - m0; d.nrem = w.N - n0; d.xrem = w.ldx - n0;
+                lists[part].push_back(d);
+            }
+    }
+    return deal_to_xcds(lists);
+}
+
+// The records of the k_small_tn launch (tile configuration 12): the tiles of XCD p are its pieces' (TnLaunchArgs::pieces), or its
+// share of every entry, exactly as the by-value kernel finds them.
+std::vector<TnDesc> tn_descs(const avae_handle* h, const Launch& L) {
+    std::vector<TnDesc> lists[8];
+    const TnLaunchArgs& a = L.targs;
+    const int es = h->es;
+    for (int y = 0; y < L.grid_y; ++y)
+        for (int x = 0; x < L.grid_x; ++x) {
+            const int part = x & 7, idx = x >> 3;
+            int entry = y, t = -1;
+            if (a.xcd_pieces) {
+                int e = 0, lo = 0;
+                for (int i = 0; i < kTnPieces; ++i) { const int ce = a.pieces[part][i].cum_end; if (idx >= ce) { e = i + 1; lo = ce; } }
+                if (e >= kTnPieces) continue;
+                entry = a.pieces[part][e].item; t = a.pieces[part][e].tile_off + idx - lo;
+            } else {
+                if (entry >= a.n_items) continue;
+                const int nt = a.items[entry].tile_cnt, q = nt >> 3, r = nt & 7;
+                if (idx >= q + (part < r ? 1 : 0)) continue;
+                t = (part < r ? part * (q + 1) : r * (q + 1) + (part - r) * q) + idx + a.items[entry].tile_off;
+            }
+            const TnItem& w = a.items[entry];
+            const int tm = t / w.tiles_n, tn = t - tm * w.tiles_n, m0 = tm * 64, n0 = tn * 64;
+            const int nk = (w.K * es) / kTileBytesK;
+            if (nk > 65535 || !w.W || !w.Wt) return {};
+            TnDesc d{};
+            d.a = static_cast<const unsigned char*>(w.A) + (size_t)m0 * es;
+            d.b = static_cast<const unsigned char*>(w.B) + (size_t)n0 * es;
+            d.out = w.out + (size_t)m0 * w.ld0 + n0;
+            d.w = static_cast<unsigned char*>(w.W) + ((size_t)m0 * w.ldw + n0) * es;
+            d.wt = static_cast<unsigned char*>(w.Wt) + ((size_t)n0 * w.ldt + m0) * es;
+            d.lda = w.lda; d.ldb = w.ldb; d.ld0 = w.ld0; d.ldw = w.ldw; d.ldt = w.ldt;
+            d.ext = TnDesc::pack(nk, w.M - m0, w.N - n0);
+            lists[part].push_back(d);
+        }
+    return deal_to_xcds(lists);
+}
+
+// Builds the device table of per-workgroup descriptors for the training plan's k_small and k_small_tn launches and points the
+// launches at it (avae_device.h: SmallDesc).  One copy of a launch's records per staging set (a record holds resolved addresses,
+// and some of them point into the set).  AVAE_NO_DESC=1 keeps every launch on its by-value arguments (A/B).
+void build_descriptors(avae_handle* h, hipStream_t s) {
+    if (std::getenv("AVAE_NO_DESC")) return;
+    std::vector<unsigned char> tab;
+    auto add = [&](Launch& L) {
+        if (L.type != 0 || !((L.cfg == 7 && !L.tn) || (L.cfg == 12 && L.tn && L.targs.adam))) return;
+        const size_t off = tab.size();
+        size_t stride = 0;
+        int n = 0;
+        for (int j = 0; j < kMultiSteps; ++j) {
+            const Launch Lj = j == 0 ? L : relocated(h, L, j);
+            const size_t at = tab.size();
+            if (L.tn) {
+                const std::vector<TnDesc> d = tn_descs(h, Lj);
+                if (d.empty()) { tab.resize(off); return; }
+                const TnDescArgs ca = {L.targs.d_theta, L.targs.d_m, L.targs.d_v, L.targs.beta1, L.targs.beta2, L.targs.eps, L.targs.st};
+                tab.resize(at + (kTnDescHead + d.size()) * 64, 0);
+                for (int p = 0; p < kTnDescHead; ++p) std::memcpy(tab.data() + at + 64 * p, &ca, sizeof(ca));
+                std::memcpy(tab.data() + at + 64 * kTnDescHead, d.data(), d.size() * 64);
+                n = (int)d.size();
+            } else {
+                const std::vector<SmallDesc> d = small_descs(h, Lj);
+                if (d.empty()) { tab.resize(off); return; }
+                tab.resize(at + d.size() * 64);
+                std::memcpy(tab.data() + at, d.data(), d.size() * 64);
+                n = (int)d.size();
+            }
+            stride = tab.size() - at;
+        }
+        L.desc_n = n; L.desc_off = off; L.desc_stride = stride;
+    };
+    for (Launch& L : h->plain.fwd) add(L);
+    for (Launch& L : h->bwd) add(L);
+    for (Launch& L : h->wgrad_adam) add(L);
+    if (tab.empty()) return;
+    HIP_OK(hipMemcpyAsync(h->desc_buf.ensure(tab.size()), tab.data(), tab.size(), hipMemcpyHostToDevice, s));
+    HIP_OK(hipStreamSynchronize(s));      // (tab is a local)
+}
+
+template <typename D> const D* desc_of(const avae_handle* h, const Launch& L) {
+    return reinterpret_cast<const D*>(h->desc_buf.as<unsigned char>() + L.desc_off + (size_t)L.desc_set * L.desc_stride);
+}
+
+// What a launch warms for the one that runs after it (next, on staging set next_set; null: nothing runs after it in this graph)
+DescWarm warm_for(const avae_handle* h, const Launch* next, int next_set) {
+    if (!next || next->desc_n == 0 || next_set >= kMultiSteps) return DescWarm{nullptr, 0};
+    return DescWarm{h->desc_buf.as<unsigned char>() + next->desc_off + (size_t)next_set * next->desc_stride,
+                    next->desc_n + (next->tn ? kTnDescHead : 0)};
 }
 
 // One launch of a plan as the dumps print it (AVAE_DEBUG_SYNC=1: every launch that runs; AVAE_PLAN_DUMP=1: a serve plan when it is built)
 void dump_launch(const Launch& L) {
     std::fprintf(stderr, "[avae] launch %s type=%d cfg=%d items=%d blocks=%d\n", L.name.c_str(), L.type, L.cfg, L.count, L.blocks);
+    if (L.desc_n) std::fprintf(stderr, "        descriptors=%d set=%d\n", L.desc_n, L.desc_set);      // runs on its records, not on the items below
     for (int i = 0; i < L.args.n_items && L.type == 0; ++i)
         std::fprintf(stderr, "        item kind=%d M=%d N=%d K=%d lda=%d ldb=%d tiles=%dx%d\n", L.args.items[i].kind, L.args.items[i].M,
                      L.args.items[i].N, L.args.items[i].K, L.args.items[i].lda, L.args.items[i].ldb, L.args.items[i].tiles_m, L.args.items[i].tiles_n);
@@ -2122,7 +2265,7 @@ void dump_launch(const Launch& L) {
                      L.ca.seg[i].g.OH, L.ca.seg[i].g.k, L.ca.seg[i].lddp, L.ca.seg[i].lda, (const void*)L.ca.seg[i].g0, L.ca.seg[i].tiles_r, L.ca.seg[i].tiles_c);
 }
 
-void run_launch(avae_handle* h, const Launch& L, hipStream_t s, unsigned long long* stamps, int stamp) {
+void run_launch(avae_handle* h, const Launch& L, hipStream_t s, unsigned long long* stamps, int stamp, DescWarm warm = DescWarm{nullptr, 0}) {
     Timed t(h, s, L.name);
     if (L.type == 1) launch_gather(h->cfg.compute_dtype, L.ga, L.blocks, s);
     else if (L.type == 2) launch_col2im(h->cfg.compute_dtype, L.ca, L.blocks, s);
@@ -2137,7 +2280,9 @@ void run_launch(avae_handle* h, const Launch& L, hipStream_t s, unsigned long lo
     else if (L.cfg == 11) launch_small_head(h->cfg.compute_dtype, L.lean_act, L.args, L.grid_x, L.grid_y, L.lds, s, stamps, stamp);
     else if (L.cfg == 10) launch_small_latb(h->cfg.compute_dtype, L.lean_act, L.args, L.grid_x, L.grid_y, L.lds, h->state(), s, stamps, stamp);
     else if (L.cfg == 9) launch_small_loss(h->cfg.compute_dtype, L.args, L.grid_x, L.grid_y, L.lds, s, stamps, stamp);
+    else if (L.cfg == 7 && L.desc_n) launch_small_desc(h->cfg.compute_dtype, L.args.items[0].kind == K_DGRAD_HIDDEN, L.args.items[0].act, desc_of<SmallDesc>(h, L), L.desc_n, L.lds, warm, s, stamps, stamp);
     else if (L.cfg == 7) launch_small(h->cfg.compute_dtype, L.args, L.grid_x, L.grid_y, L.lds, s, stamps, stamp);
+    else if (L.tn && L.cfg == 12 && L.desc_n) launch_small_tn_desc(h->cfg.compute_dtype, desc_of<TnDesc>(h, L), L.desc_n, warm, s, stamps, stamp);
     else if (L.tn && L.cfg == 12) launch_small_tn(h->cfg.compute_dtype, L.targs, L.grid_x, L.grid_y, s, stamps, stamp);
     else if (L.tn) launch_grouped_tn(h->cfg.compute_dtype, L.cfg, L.targs, L.grid_x, L.grid_y, L.lds, h->state(), s, stamps, stamp);
     else launch_grouped(h->cfg.compute_dtype, L.cfg, L.args, L.grid_x, L.grid_y, L.lds, h->state(), s, stamps, stamp);
@@ -2158,7 +2303,9 @@ bool has_hyper_item(const Launch& L) {
 // Launches [lo, hi) of ls on staging set j: set 0 runs ls itself, set j > 0 relocated copies.  stamp_base >= 0 (AVAE_STAMPS builds):
 // the launches write their clock stamps from slot stamp_base on.  train: a training step -- with a schedule set its latent and cost
 // launches are copies that point at the step's schedule entry (every other caller runs the tables as they are: multipliers 1).
-void run_set(avae_handle* h, const std::vector<Launch>& ls, size_t lo, size_t hi, int j, hipStream_t s, int stamp_base = -1, bool train = false) {
+// after / after_set: the launch that runs behind ls[hi - 1] and its staging set -- the last launch warms its descriptors (warm_for).
+void run_set(avae_handle* h, const std::vector<Launch>& ls, size_t lo, size_t hi, int j, hipStream_t s, int stamp_base = -1, bool train = false,
+             const Launch* after = nullptr, int after_set = 0) {
     unsigned long long* stamps = nullptr;
 #ifdef AVAE_STAMPS
     if (stamp_base >= 0) stamps = h->at<unsigned long long>(h->off_stamps);
@@ -2171,8 +2318,10 @@ void run_set(avae_handle* h, const std::vector<Launch>& ls, size_t lo, size_t hi
     }
     for (size_t i = lo; i < hi && i < ls.size(); ++i) {
         const int k = stamp_base + (int)(i - lo);
-        if (j == 0 && !(hyper && has_hyper_item(ls[i]))) run_launch(h, ls[i], s, stamps, k);
-        else run_launch(h, relocated(h, ls[i], j, hyper), s, stamps, k);
+        const bool last = i + 1 >= hi || i + 1 >= ls.size();
+        const DescWarm warm = last ? warm_for(h, after, after_set) : warm_for(h, &ls[i + 1], j);
+        if (j == 0 && !(hyper && has_hyper_item(ls[i]))) run_launch(h, ls[i], s, stamps, k, warm);
+        else run_launch(h, relocated(h, ls[i], j, hyper), s, stamps, k, warm);
     }
 }
 
@@ -2359,12 +2508,15 @@ void fill_ones(avae_handle* h, const Act& a, hipStream_t s) {
 // One step on staging set j (forward launches `fwd`: a plan's): forward, backward, then the weight gradients with Adam in their
 // epilogue, or followed by k_adam; with clipping on always weight gradients -> k_grad_sumsq -> k_adam, with averaging on always
 // weight gradients -> k_adam (the fused epilogue knows neither).
-void step_body(avae_handle* h, const std::vector<Launch>& fwd, hipStream_t s, int j, int stamp_base = -1) {
+// more: step j + 1 of the same graph follows (its first launch's descriptors are warmed by this step's last launch).
+void step_body(avae_handle* h, const std::vector<Launch>& fwd, hipStream_t s, int j, int stamp_base = -1, bool more = false) {
     auto sb = [&](size_t k) { return stamp_base < 0 ? -1 : stamp_base + (int)k; };
-    run_set(h, fwd, 0, fwd.size(), j, s, stamp_base, true);
-    run_set(h, h->bwd, 0, h->bwd.size(), j, s, sb(fwd.size()), true);
-    if (!h->wgrad_adam.empty() && !h->clip_on && !h->ema_on) {       // the optimiser rides in the weight-gradient launch
-        run_set(h, h->wgrad_adam, 0, h->wgrad_adam.size(), j, s, sb(fwd.size() + h->bwd.size()), true);
+    auto first_of = [](const std::vector<Launch>& ls) { return ls.empty() ? nullptr : &ls[0]; };
+    const bool fused = !h->wgrad_adam.empty() && !h->clip_on && !h->ema_on;
+    run_set(h, fwd, 0, fwd.size(), j, s, stamp_base, true, first_of(h->bwd), j);
+    run_set(h, h->bwd, 0, h->bwd.size(), j, s, sb(fwd.size()), true, fused ? first_of(h->wgrad_adam) : nullptr, j);
+    if (fused) {       // the optimiser rides in the weight-gradient launch
+        run_set(h, h->wgrad_adam, 0, h->wgrad_adam.size(), j, s, sb(fwd.size() + h->bwd.size()), true, more ? first_of(fwd) : nullptr, j + 1);
         return;
     }
     run_set(h, h->wgrad, 0, h->wgrad.size(), j, s, sb(fwd.size() + h->bwd.size()), true);
@@ -2386,7 +2538,7 @@ void capture_steps(avae_handle* h, StepPlan& p, const uint8_t* present) {
         // batches staged by ONE launch into as many staging sets; step j's launches read set j
         for (int gi = 0; gi < 2; ++gi) p.multi[gi] = capture(h, [&](hipStream_t cs) {
             run_prep_batch(h, x0.data(), nullptr, nullptr, h->B, kTrainSalt, cs, present, kMultiSizes[gi]);
-            for (int j = 0; j < kMultiSizes[gi]; ++j) step_body(h, p.fwd, cs, j);
+            for (int j = 0; j < kMultiSizes[gi]; ++j) step_body(h, p.fwd, cs, j, -1, j + 1 < kMultiSizes[gi]);
         }, true);
     } catch (...) { p.full.release(); p.multi[0].release(); p.multi[1].release(); throw; }
 }
@@ -2414,6 +2566,7 @@ void init_device(avae_handle* h) {
         if (md.conv && md.cdec[3].dense_map) fill_ones(h, md.cdec[3].Y, s);      // the dense 28x28 map feeds the output layer: its bias column
     }
     build_training_plan(h);
+    build_descriptors(h, s);
     HIP_OK(hipMemcpyAsync(h->at<void>(h->off_adam), h->adam_items.data(), h->adam_items.size() * sizeof(AdamItem), hipMemcpyHostToDevice, s));
     HIP_OK(hipMemcpyAsync(h->at<void>(h->off_adam_b), h->adam_items_b.data(), h->adam_items_b.size() * sizeof(AdamItem), hipMemcpyHostToDevice, s));
     {   // the two constant chunks an implicit patch matrix reads instead of an invalid tap / as its bias column, and the descriptors

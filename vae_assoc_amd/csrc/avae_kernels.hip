@@ -1517,6 +1517,87 @@ __global__ void __launch_bounds__(kThreads) k_small(const LaunchArgs args, unsig
     AVAE_STAMP_FLUSH()
 }
 
+// One descriptor record of the next launch per wave (DescWarm), as a scalar load: the line is in this XCD's L2 when the workgroup
+// that owns it starts.  A scalar load counts in lgkmcnt only, so no counted vmcnt wait of the K loops moves; the LDS reads' waits can
+// only get stricter (an extra operation outstanding never lets lgkmcnt reach a value early).  The caller names the result in an
+// empty statement at its very end, which keeps the load and leaves the compiler's own wait for it behind all useful work.
+__device__ __forceinline__ unsigned desc_warm(const void* lines, int n, int wave) {
+    typedef const __attribute__((address_space(4))) unsigned* cu_t;
+    const int i = (blockIdx.x & 7) + 8 * (4 * (blockIdx.x >> 3) + wave);
+    return i < n ? *(cu_t)((unsigned long long)lines + 64ull * (unsigned)i) : 0u;
+}
+
+// k_small on per-workgroup descriptors (training plan; avae_device.h: SmallDesc): record blockIdx.x holds the tile's operand rows,
+// output and edge extents already resolved, so the prologue is one scalar burst -- no item, no tile split, no division -- beside
+// which the per-lane offsets are computed.  Same K order, same rounding points, same addresses as k_small: bitwise the same results
+// (AVAE_NO_DESC=1 keeps k_small for A/B).  The table pointer comes in the preloaded kernel arguments.
+template <typename CT, int KIND, int ACT>
+__global__ void __launch_bounds__(kThreads) k_small_desc(const SmallDesc* __restrict__ tab, unsigned long long* stamps, int launch_id,
+                                                         const void* warm_lines, int warm_n) {
+    constexpr int RING = 4, ES = (int)sizeof(CT);
+    constexpr int kStage = 64 * kTileBytesK;
+    unsigned char* smem = avae_dyn_smem;
+#ifdef AVAE_STAMPS
+    unsigned long long sv[kStampWords] = {0, 0, 0, 0, 0, 0, 0, 0};
+#endif
+    AVAE_STAMP(0)
+    const SmallDesc d = tab[blockIdx.x];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wr = wave >> 1, wc = wave & 1, fr = lane & 15, fq = lane >> 4;
+    const int nk = d.nk;
+    typedef const __attribute__((address_space(1))) void* gp_t;
+    typedef __attribute__((address_space(3))) void* lp_t;
+    const int prow = wave * 8 + (lane >> 3), lc = ((lane & 7) ^ ((prow >> 1) & 7)) * 16;
+    const unsigned char* srcA = d.a + (size_t)prow * d.lda * ES + lc;
+    const unsigned char* srcB = d.b + (size_t)prow * d.ldb * ES + lc;
+    // dgrad: act'(stored output of the layer below) -- older than every tile, as in k_small
+    const int lrow = wr * 16 + fr, lcol = wc * 16 + 4 * fq;
+    typename Quad<CT>::raw yq;
+    if constexpr (KIND == 1)
+        yq = *reinterpret_cast<const typename Quad<CT>::raw*>(reinterpret_cast<const CT*>(d.aux) + (ptrdiff_t)min(lrow, d.mrem - 1) * d.ldx + min(lcol, d.xrem - 4));
+#define AVAE_S_DMA(kt, buf)                                                                                             \
+    { __builtin_amdgcn_global_load_lds((gp_t)(srcA + (size_t)(kt) * kTileBytesK), (lp_t)(smem + (buf) * kStage + wave * 1024), 16, 0, 0);          \
+      __builtin_amdgcn_global_load_lds((gp_t)(srcB + (size_t)(kt) * kTileBytesK), (lp_t)(smem + (buf) * kStage + (4 + wave) * 1024), 16, 0, 0); }
+    AVAE_STAMP(1)
+    const int npro = nk < RING - 1 ? nk : RING - 1;
+    for (int p = 0; p < npro; ++p) AVAE_S_DMA(p, p)
+    const unsigned warmed = desc_warm(warm_lines, warm_n, wave);       // behind the prologue's tiles; scalar: no vmcnt below counts it
+    const int sw0 = (fq ^ (fr >> 1)) * 16;
+    const int aoff = (wr * 16 + fr) * kTileBytesK, boff = (32 + wc * 16 + fr) * kTileBytesK;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    int buf = 0;
+    for (int kt = 0; kt < nk; ++kt) {
+        const int rem = nk - 1 - kt;
+        if (rem >= 2) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");          // two younger tiles (2 pieces each) may be on their way
+        else if (rem == 1) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        asm volatile("s_barrier" ::: "memory");
+        if (kt == 0) { AVAE_STAMP(2) }
+        const unsigned char* Sb = smem + buf * kStage;
+        const u32x4 a0 = *reinterpret_cast<const u32x4*>(Sb + aoff + sw0), b0 = *reinterpret_cast<const u32x4*>(Sb + boff + sw0);
+        const int fill = buf == 0 ? RING - 1 : buf - 1;
+        if (kt + RING - 1 < nk) AVAE_S_DMA(kt + RING - 1, fill)
+        const u32x4 a1 = *reinterpret_cast<const u32x4*>(Sb + aoff + (sw0 ^ 64)), b1 = *reinterpret_cast<const u32x4*>(Sb + boff + (sw0 ^ 64));
+        mma<CT>(b0, a0, acc);                                  // swapped: acc[e] = C[row fr][col 4 fq + e]
+        mma<CT>(b1, a1, acc);
+        buf = buf + 1 == RING ? 0 : buf + 1;
+    }
+#undef AVAE_S_DMA
+    AVAE_STAMP(3)
+    if (lrow < d.mrem && lcol < d.nrem) {
+        float v[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if constexpr (KIND == 0) v[e] = act_fwd_t<ACT>(acc[e]);
+            else v[e] = acc[e] * act_bwd_t<ACT>(quad_elem<CT>(yq, e));
+        }
+        store_row<CT>(reinterpret_cast<CT*>(d.out) + (size_t)lrow * d.ld0 + lcol, v, d.nrem - lcol);
+    }
+    asm volatile("" :: "s"(warmed));
+    AVAE_STAMP(4)
+    AVAE_STAMP_FLUSH()
+}
+
 // Timing mode (avae_timing_enable): the host arms one (start, stop) event pair per launch; the launch then
 // goes through hipExtLaunchKernelGGL, which stamps the events with the dispatch's own begin/end timestamps --
 // the same signal times rocprofv3 --kernel-trace reports -- instead of bracketing it with marker packets.
@@ -1984,43 +2065,21 @@ void launch_small_latb(int compute_dtype, int act, const LaunchArgs& args, int g
 // is applied to theta / m / v as it leaves the accumulators (adam_update, the arithmetic of k_adam), the gradient itself is still
 // stored (avae_get_grads, the cost slot's neighbours), and both compute-dtype shadows of the layer are refreshed -- k_adam's launch,
 // its boundary and the gradient's read-back disappear.  Launches with split-K or all-ones bias rows stay on the general kernel.
-template <typename CT, bool ADAM>
-__global__ void __launch_bounds__(kThreads) k_small_tn(const TnLaunchArgs args, unsigned long long* stamps, int launch_id) {
+// The tile itself is small_tn_tile, on a resolved descriptor (avae_device.h: TnDesc): k_small_tn works the descriptor out of its
+// by-value item, k_small_tn_desc (the training plan) reads it from the plan's table.  behind_prologue() is called once, behind the
+// prologue's tiles, and returns the step's lr_t.
+#ifdef AVAE_STAMPS
+#define AVAE_SV sv
+#else
+#define AVAE_SV nullptr
+#endif
+template <typename CT, bool ADAM, typename F>
+__device__ __forceinline__ void small_tn_tile(const TnDesc& d, const TnDescArgs& ca, F&& behind_prologue, unsigned char* smem, unsigned long long* sv) {
     constexpr int BM = 64, RING = 4, ES = (int)sizeof(CT), EPR = kTileBytesK / ES, NCH = 4;
     constexpr int kStage = 2 * BM * kTileBytesK;               // A part (BM columns) then B part: 16 KiB, EPR k-rows
-    unsigned char* smem = avae_dyn_smem;
-#ifdef AVAE_STAMPS
-    unsigned long long sv[kStampWords] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
-    AVAE_STAMP(0)
-    const int part = blockIdx.x & 7, idx = blockIdx.x >> 3;
-    int entry = blockIdx.y, t_piece = -1;
-    if (args.xcd_pieces) {       // XCD-owned pieces: this XCD's list of (layer, tile range); one more kernel-argument round trip than below
-        const TnPiece* row = args.pieces[part];
-        int e = 0, lo = 0;
-#pragma unroll
-        for (int i = 0; i < kTnPieces; ++i) { const int ce = row[i].cum_end; if (idx >= ce) { e = i + 1; lo = ce; } }
-        if (e >= kTnPieces) return;                                   // behind this XCD's last tile
-        entry = row[e].item; t_piece = row[e].tile_off + idx - lo;
-    }
-    const TnItem w = args.items[entry];
-    asm volatile("" :: "s"(w.A), "s"(w.B), "s"(w.out), "s"(w.lda), "s"(w.ldb), "s"(w.K), "s"(w.ld0), "s"(w.tile_off));
-    float lr_t = 0.f;
-    if constexpr (ADAM) lr_t = args.st->lr_t;        // older than every tile: whatever load it becomes, the counted waits hold
-    int t;
-    if (t_piece >= 0) {
-        t = t_piece;
-    } else {
-        const int nt = w.tile_cnt;
-        const int q = nt >> 3, r = nt & 7;
-        if (idx >= q + (part < r ? 1 : 0)) return;
-        t = (part < r ? part * (q + 1) : r * (q + 1) + (part - r) * q) + idx + w.tile_off;
-    }
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave >> 1, wc = wave & 1, fr = lane & 15, fq = lane >> 4;
-    const int tm = t / w.tiles_n, tn = t - tm * w.tiles_n;
-    const int m0 = tm * BM, n0 = tn * BM;
-    const int nk = (w.K * ES) / kTileBytesK;
+    const int nk = d.ext & 0xFFFF, mrem = (d.ext >> 16) & 0xFF, nrem = d.ext >> 24;
     typedef const __attribute__((address_space(1))) void* gp_t;
     typedef __attribute__((address_space(3))) void* lp_t;
     const unsigned char* src[NCH];
@@ -2031,9 +2090,9 @@ __global__ void __launch_bounds__(kThreads) k_small_tn(const TnLaunchArgs args, 
         const bool is_a = c < 2;
         const int rr = is_a ? r : r - BM, sub = rr / EPR, k = rr - sub * EPR;
         const int lc = (lane & 7) ^ tn_swz<CT>(k);
-        const size_t ld_b = (size_t)(is_a ? w.lda : w.ldb) * ES;
+        const size_t ld_b = (size_t)(is_a ? d.lda : d.ldb) * ES;
         kadv[c] = (size_t)EPR * ld_b;
-        src[c] = reinterpret_cast<const unsigned char*>(is_a ? w.A : w.B) + (size_t)(is_a ? m0 : n0) * ES + (size_t)k * ld_b + (size_t)sub * kTileBytesK + lc * 16;
+        src[c] = (is_a ? d.a : d.b) + (size_t)k * ld_b + (size_t)sub * kTileBytesK + lc * 16;
     }
 #define AVAE_T_DMA(kt, buf)                                                                                             \
     { _Pragma("unroll") for (int c = 0; c < NCH; ++c)                                                                   \
@@ -2044,6 +2103,7 @@ __global__ void __launch_bounds__(kThreads) k_small_tn(const TnLaunchArgs args, 
     AVAE_STAMP(1)
     const int npro = nk < RING - 1 ? nk : RING - 1;
     for (int p = 0; p < npro; ++p) AVAE_T_DMA(p, p)
+    const float lr_t = behind_prologue();
     // ADAM: this thread's theta / m / v of the block (4 rows x 16 bytes x 3 arrays), fetched in ONE burst at the top of the epilogue
     // (clamped addresses: every lane loads something valid).  Fetching them beside the K loop instead (behind the prologue's tiles,
     // counted in the loop's waits) was built and measured: no faster (C2: 12.4 us either way) -- the launch is paced by the bytes its
@@ -2053,12 +2113,12 @@ __global__ void __launch_bounds__(kThreads) k_small_tn(const TnLaunchArgs args, 
     auto fetch_state = [&]() {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const int grow = m0 + (tid >> 4) + 16 * k, gcol = n0 + c4;
-            const bool ok = grow < w.M && gcol < w.N;
-            const float* gp = w.out + (size_t)(ok ? grow : m0) * w.ld0 + (ok ? gcol : n0);
-            pth[k] = *reinterpret_cast<const f32x4*>(gp + args.d_theta);
-            pmm[k] = *reinterpret_cast<const f32x4*>(gp + args.d_m);
-            pvv[k] = *reinterpret_cast<const f32x4*>(gp + args.d_v);
+            const int lrow = (tid >> 4) + 16 * k;
+            const bool ok = lrow < mrem && c4 < nrem;
+            const float* gp = d.out + (size_t)(ok ? lrow : 0) * d.ld0 + (ok ? c4 : 0);
+            pth[k] = *reinterpret_cast<const f32x4*>(gp + ca.d_theta);
+            pmm[k] = *reinterpret_cast<const f32x4*>(gp + ca.d_m);
+            pvv[k] = *reinterpret_cast<const f32x4*>(gp + ca.d_v);
         }
     };
     f32x4 acc[2][2];
@@ -2098,13 +2158,13 @@ __global__ void __launch_bounds__(kThreads) k_small_tn(const TnLaunchArgs args, 
     if constexpr (!ADAM) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            const int row = m0 + wr * 32 + i * 16 + fr;
+            const int row = wr * 32 + i * 16 + fr;
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                const int col = n0 + wc * 32 + j * 16 + 4 * fq;
-                if (row < w.M && col < w.N) {
+                const int col = wc * 32 + j * 16 + 4 * fq;
+                if (row < mrem && col < nrem) {
                     const float g[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
-                    store_row<float>(w.out + (size_t)row * w.ld0 + col, g, w.N - col);
+                    store_row<float>(d.out + (size_t)row * d.ld0 + col, g, nrem - col);
                 }
             }
         }
@@ -2123,7 +2183,7 @@ __global__ void __launch_bounds__(kThreads) k_small_tn(const TnLaunchArgs args, 
 #pragma unroll
                 for (int e = 0; e < 4; ++e) T[(wr * 32 + i * 16 + fr) * LDT + wc * 32 + j * 16 + 4 * fq + e] = acc[i][j][e];
         lds_barrier();
-        const float omb1 = 1.0f - args.beta1, omb2 = 1.0f - args.beta2;
+        const float omb1 = 1.0f - ca.beta1, omb2 = 1.0f - ca.beta2;
         const int r4 = (tid & 15) * 4;                          // W^T: a lane takes four consecutive rows (m) of one column (n)
         // The update itself runs for all four row groups of the thread BEFORE any store and outside any branch (clamped addresses
         // made every fetched value a number): the wait for the twelve loads then sits in straight-line code.  Placed behind a
@@ -2136,36 +2196,36 @@ __global__ void __launch_bounds__(kThreads) k_small_tn(const TnLaunchArgs args, 
 #pragma unroll
             for (int e = 0; e < 4; ++e) { g[k][e] = T[r * LDT + c4 + e]; th[k][e] = pth[k][e]; m[k][e] = pmm[k][e]; v[k][e] = pvv[k][e]; }
 #pragma unroll
-            for (int e = 0; e < 4; ++e) adam_update(g[k][e], m[k][e], v[k][e], th[k][e], omb1, omb2, lr_t, args.eps);
+            for (int e = 0; e < 4; ++e) adam_update(g[k][e], m[k][e], v[k][e], th[k][e], omb1, omb2, lr_t, ca.eps);
 #pragma unroll
             for (int e = 0; e < 4; ++e) T[r * LDT + c4 + e] = th[k][e];
         }
-        const bool full = m0 + BM <= w.M && n0 + BM <= w.N;     // a tile inside the layer (most of them): whole 16-byte stores, no bounds
+        const bool full = mrem >= BM && nrem >= BM;             // a tile inside the layer (most of them): whole 16-byte stores, no bounds
         auto store_group = [&](int k, float* gp, CT* wp) {
             store4<float>(gp, g[k]);
-            store4<float>(gp + args.d_theta, th[k]); store4<float>(gp + args.d_m, m[k]); store4<float>(gp + args.d_v, v[k]);
+            store4<float>(gp + ca.d_theta, th[k]); store4<float>(gp + ca.d_m, m[k]); store4<float>(gp + ca.d_v, v[k]);
             store4<CT>(wp, th[k]);
         };
         if (full) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                const int grow = m0 + (tid >> 4) + 16 * k, gcol = n0 + c4;
-                store_group(k, w.out + (size_t)grow * w.ld0 + gcol, reinterpret_cast<CT*>(w.W) + (size_t)grow * w.ldw + gcol);
+                const int lrow = (tid >> 4) + 16 * k;
+                store_group(k, d.out + (size_t)lrow * d.ld0 + c4, reinterpret_cast<CT*>(d.w) + (size_t)lrow * d.ldw + c4);
             }
         } else {
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                const int grow = m0 + (tid >> 4) + 16 * k, gcol = n0 + c4;
-                float* gp = w.out + (size_t)grow * w.ld0 + gcol;
-                CT* wp = reinterpret_cast<CT*>(w.W) + (size_t)grow * w.ldw + gcol;
-                const int nv = w.N - gcol;
-                if (grow < w.M && nv >= 4) {
+                const int lrow = (tid >> 4) + 16 * k;
+                float* gp = d.out + (size_t)lrow * d.ld0 + c4;
+                CT* wp = reinterpret_cast<CT*>(d.w) + (size_t)lrow * d.ldw + c4;
+                const int nv = nrem - c4;
+                if (lrow < mrem && nv >= 4) {
                     store_group(k, gp, wp);
-                } else if (grow < w.M && nv > 0) {
+                } else if (lrow < mrem && nv > 0) {
                     // a partial quad never touches the padding behind column N
 #pragma unroll
                     for (int e = 0; e < 3; ++e) if (e < nv) {
-                        gp[e] = g[k][e]; gp[args.d_theta + e] = th[k][e]; gp[args.d_m + e] = m[k][e]; gp[args.d_v + e] = v[k][e]; wp[e] = to_ct<CT>(th[k][e]);
+                        gp[e] = g[k][e]; gp[ca.d_theta + e] = th[k][e]; gp[ca.d_m + e] = m[k][e]; gp[ca.d_v + e] = v[k][e]; wp[e] = to_ct<CT>(th[k][e]);
                     }
                     // Keeps this arm's last store from being merged with the 16-byte stores of the other arm: hipcc (ROCm 7.2) sank
                     // the two into one shared "fourth dword" store and left its value unset on the whole-quad lanes -- fp32
@@ -2177,18 +2237,96 @@ __global__ void __launch_bounds__(kThreads) k_small_tn(const TnLaunchArgs args, 
         lds_barrier();
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const int c = (tid >> 4) + 16 * k;
-            const int gcol = n0 + c, grow = m0 + r4;
+            const int cc = (tid >> 4) + 16 * k;
             float t[4];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) t[e] = T[(r4 + e) * LDT + c];
-            CT* tp = reinterpret_cast<CT*>(w.Wt) + (size_t)gcol * w.ldt + grow;
+            for (int e = 0; e < 4; ++e) t[e] = T[(r4 + e) * LDT + cc];
+            CT* tp = reinterpret_cast<CT*>(d.wt) + (size_t)cc * d.ldt + r4;
             if (full) store4<CT>(tp, t);
-            else if (gcol < w.N && grow < w.M) store_row<CT>(tp, t, w.M - grow);
+            else if (cc < nrem && r4 < mrem) store_row<CT>(tp, t, mrem - r4);
         }
     }
+}
+
+template <typename CT, bool ADAM>
+__global__ void __launch_bounds__(kThreads) k_small_tn(const TnLaunchArgs args, unsigned long long* stamps, int launch_id) {
+    constexpr int BM = 64, ES = (int)sizeof(CT);
+    unsigned char* smem = avae_dyn_smem;
+#ifdef AVAE_STAMPS
+    unsigned long long sv[kStampWords] = {0, 0, 0, 0, 0, 0, 0, 0};
+#endif
+    AVAE_STAMP(0)
+    const int part = blockIdx.x & 7, idx = blockIdx.x >> 3;
+    int entry = blockIdx.y, t_piece = -1;
+    if (args.xcd_pieces) {       // XCD-owned pieces: this XCD's list of (layer, tile range); one more kernel-argument round trip than below
+        const TnPiece* row = args.pieces[part];
+        int e = 0, lo = 0;
+#pragma unroll
+        for (int i = 0; i < kTnPieces; ++i) { const int ce = row[i].cum_end; if (idx >= ce) { e = i + 1; lo = ce; } }
+        if (e >= kTnPieces) return;                                   // behind this XCD's last tile
+        entry = row[e].item; t_piece = row[e].tile_off + idx - lo;
+    }
+    const TnItem w = args.items[entry];
+    asm volatile("" :: "s"(w.A), "s"(w.B), "s"(w.out), "s"(w.lda), "s"(w.ldb), "s"(w.K), "s"(w.ld0), "s"(w.tile_off));
+    float lr_t = 0.f;
+    if constexpr (ADAM) lr_t = args.st->lr_t;        // older than every tile: whatever load it becomes, the counted waits hold
+    int t;
+    if (t_piece >= 0) {
+        t = t_piece;
+    } else {
+        const int nt = w.tile_cnt;
+        const int q = nt >> 3, r = nt & 7;
+        if (idx >= q + (part < r ? 1 : 0)) return;
+        t = (part < r ? part * (q + 1) : r * (q + 1) + (part - r) * q) + idx + w.tile_off;
+    }
+    const int tm = t / w.tiles_n, tn = t - tm * w.tiles_n;
+    const int m0 = tm * BM, n0 = tn * BM;
+    TnDesc d;
+    d.a = reinterpret_cast<const unsigned char*>(w.A) + (size_t)m0 * ES;
+    d.b = reinterpret_cast<const unsigned char*>(w.B) + (size_t)n0 * ES;
+    d.out = w.out + (size_t)m0 * w.ld0 + n0;
+    d.w = reinterpret_cast<CT*>(w.W) + (size_t)m0 * w.ldw + n0;
+    d.wt = reinterpret_cast<CT*>(w.Wt) + (size_t)n0 * w.ldt + m0;
+    d.lda = w.lda; d.ldb = w.ldb; d.ld0 = w.ld0; d.ldw = w.ldw; d.ldt = w.ldt;
+    d.ext = TnDesc::pack((w.K * ES) / kTileBytesK, w.M - m0, w.N - n0);
+    const TnDescArgs ca = {args.d_theta, args.d_m, args.d_v, args.beta1, args.beta2, args.eps, args.st};
+    small_tn_tile<CT, ADAM>(d, ca, [lr_t]() { return lr_t; }, smem, AVAE_SV);
     AVAE_STAMP(4)
     AVAE_STAMP_FLUSH()
+}
+
+// The training plan's instance: the launch-wide constants (TnDescArgs) are the table's first lines, one copy per XCD, the records
+// follow (kTnDescHead).  Both come in one scalar burst off the preloaded table pointer; lr_t (two more dependent
+// trips: the state's address, then the value) is fetched behind the prologue's tiles and first needed in the epilogue.  It and the
+// warm-up touch are SCALAR loads (constant address space: the K_COST item that published lr_t ran in an earlier launch), so they
+// count in lgkmcnt, not in the vmcnt the K loop's waits are written in.
+template <typename CT>
+__global__ void __launch_bounds__(kThreads) k_small_tn_desc(const TnDesc* __restrict__ tab, unsigned long long* stamps, int launch_id,
+                                                            const void* warm_lines, int warm_n) {
+    unsigned char* smem = avae_dyn_smem;
+#ifdef AVAE_STAMPS
+    unsigned long long sv[kStampWords] = {0, 0, 0, 0, 0, 0, 0, 0};
+#endif
+    AVAE_STAMP(0)
+    const TnDescArgs ca = *reinterpret_cast<const TnDescArgs*>(tab + (blockIdx.x & 7));
+    const TnDesc d = tab[kTnDescHead + blockIdx.x];
+    unsigned warmed = 0;
+    small_tn_tile<CT, true>(d, ca, [&]() {
+        typedef const __attribute__((address_space(4))) float* cf_t;
+        const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+        const float lr_t = *(cf_t)(unsigned long long)&ca.st->lr_t;
+        warmed = desc_warm(warm_lines, warm_n, wave);
+        return lr_t;
+    }, smem, AVAE_SV);
+    asm volatile("" :: "s"(warmed));
+    AVAE_STAMP(4)
+    AVAE_STAMP_FLUSH()
+}
+void launch_small_tn_desc(int compute_dtype, const TnDesc* tab, int n_tiles, DescWarm warm, hipStream_t s, unsigned long long* stamps, int launch_id) {
+    const dim3 grid(n_tiles), block(kThreads);
+    const int lds_bytes = 4 * 2 * 64 * kTileBytesK;
+    if (compute_dtype == AVAE_BF16) AVAE_LAUNCH((k_small_tn_desc<__bf16>), grid, block, lds_bytes, s, tab, stamps, launch_id, warm.lines, warm.n);
+    else AVAE_LAUNCH((k_small_tn_desc<float>), grid, block, lds_bytes, s, tab, stamps, launch_id, warm.lines, warm.n);
 }
 void launch_small_tn(int compute_dtype, const TnLaunchArgs& args, int grid_x, int grid_y, hipStream_t s, unsigned long long* stamps, int launch_id) {
     const dim3 grid(grid_x, grid_y), block(kThreads);
@@ -2225,6 +2363,25 @@ void launch_small(int compute_dtype, const LaunchArgs& args, int grid_x, int gri
     }
     if (compute_dtype == AVAE_BF16) { if (kind) launch_small_act<__bf16, 1>(act, args, grid, lds_bytes, s, stamps, launch_id); else launch_small_act<__bf16, 0>(act, args, grid, lds_bytes, s, stamps, launch_id); }
     else { if (kind) launch_small_act<float, 1>(act, args, grid, lds_bytes, s, stamps, launch_id); else launch_small_act<float, 0>(act, args, grid, lds_bytes, s, stamps, launch_id); }
+}
+
+template <typename CT, int KIND>
+static void launch_small_desc_act(int act, const SmallDesc* tab, dim3 grid, int lds_bytes, DescWarm warm, hipStream_t s, unsigned long long* stamps, int launch_id) {
+    const dim3 block(kThreads);
+    switch (act) {
+        case AVAE_ACT_RELU: AVAE_LAUNCH((k_small_desc<CT, KIND, AVAE_ACT_RELU>), grid, block, lds_bytes, s, tab, stamps, launch_id, warm.lines, warm.n); break;
+        case AVAE_ACT_SOFTPLUS: AVAE_LAUNCH((k_small_desc<CT, KIND, AVAE_ACT_SOFTPLUS>), grid, block, lds_bytes, s, tab, stamps, launch_id, warm.lines, warm.n); break;
+        case AVAE_ACT_SIGMOID: AVAE_LAUNCH((k_small_desc<CT, KIND, AVAE_ACT_SIGMOID>), grid, block, lds_bytes, s, tab, stamps, launch_id, warm.lines, warm.n); break;
+        case AVAE_ACT_TANH: AVAE_LAUNCH((k_small_desc<CT, KIND, AVAE_ACT_TANH>), grid, block, lds_bytes, s, tab, stamps, launch_id, warm.lines, warm.n); break;
+        default: AVAE_LAUNCH((k_small_desc<CT, KIND, AVAE_ACT_IDENTITY>), grid, block, lds_bytes, s, tab, stamps, launch_id, warm.lines, warm.n); break;
+    }
+}
+// tile_cfg 7 of the training plan on descriptors: dgrad = the launch's kind is K_DGRAD_HIDDEN (else K_FWD_HIDDEN), one transfer function
+void launch_small_desc(int compute_dtype, bool dgrad, int act, const SmallDesc* tab, int n_tiles, int lds_bytes, DescWarm warm, hipStream_t s,
+                       unsigned long long* stamps, int launch_id) {
+    const dim3 grid(n_tiles);
+    if (compute_dtype == AVAE_BF16) { if (dgrad) launch_small_desc_act<__bf16, 1>(act, tab, grid, lds_bytes, warm, s, stamps, launch_id); else launch_small_desc_act<__bf16, 0>(act, tab, grid, lds_bytes, warm, s, stamps, launch_id); }
+    else { if (dgrad) launch_small_desc_act<float, 1>(act, tab, grid, lds_bytes, warm, s, stamps, launch_id); else launch_small_desc_act<float, 0>(act, tab, grid, lds_bytes, warm, s, stamps, launch_id); }
 }
 
 // ------------------------------------------------------------------ experiment: two chain links in ONE launch
