@@ -231,9 +231,50 @@ struct alignas(64) TnDesc {           // k_small_tn_desc: 64x64 tile (m0, n0) of
     static constexpr unsigned pack(int nk, int mrem, int nrem) { return (unsigned)nk | (unsigned)(mrem < 64 ? mrem : 64) << 16 | (unsigned)(nrem < 64 ? nrem : 64) << 24; }
 };
 static_assert(sizeof(SmallDesc) == 64 && sizeof(TnDesc) == 64, "a descriptor is one cache line");
-// The records the NEXT launch of the run will read, n of them from `lines` on: workgroup x of this launch touches record
-// (x & 7) + 8 * (4 * (x >> 3) + wave), which a workgroup on its own XCD will read -- so the line waits in that XCD's L2.  A speed
-// matter only: n = 0, or a record nobody warmed, is the cold read it always was.
+// The step's other three launches (output + loss, the two fused head launches) resolve more per workgroup than one line holds: their
+// records are two lines, read in one scalar burst like the others (several 64-byte scalar loads issued together cost what one
+// does).  Narrow values share a dword; a scalar load has no narrower form.
+struct alignas(128) LossRec {         // k_loss_rec: 32x32 tile (m0, n0) of an output layer + its loss, or one tile of the latent item
+    const unsigned char* a;          // A + m0 * lda * ES
+    const unsigned char* b;          // B + n0 * ldb * ES
+    void* out;                       // out0 + m0 * ld0 + n0 (the gradient w.r.t. the logits)
+    const float* x;                  // aux0 + m0 * ldx + n0 (the exact fp32 input the loss compares with)
+    float* slot;                     // partial + slot_base + t (the tile's cost partial)
+    int lda, ldb, ld0, ldx;
+    int nk;                          // K tiles
+    int mrem, nrem, xrem;            // M - m0, N - n0, ldx - n0
+    float scale;
+    int binary;
+    int item, tile;                  // item >= 0: no GEMM tile -- tile `tile` of the by-value K_LATENT item `item` (the launch's trailing LaunchArgs)
+    int pad_[10];
+};
+struct alignas(128) HeadRec {         // k_head_rec / k_latb_rec: 32x64 head tile of row block m0, tail slice ts (WorkItem::tail_*)
+    const unsigned char* a;          // A + m0 * lda * ES
+    const unsigned char* b;          // B (all 64 columns of the head)
+    void* out0;                      // head: mulv + m0 * ld0;  latb: dH + m0 * ld0  (stored by slice 0)
+    void* out1;                      // head: Z + m0 * ld1 (slice 0)
+    const float* aux;                // head: eps + m0 * ldx;  latb: g0 + m0 * 3 * roundup(nz, 4)
+    const unsigned char* tail_w;     // the consuming layer's weight shadow (whole: rows are clamped at tail_n - 1)
+    void* tail_out;                  // tail_out + m0 * tail_ldo
+    const void* tail_aux;            // latb: tail_aux + m0 * tail_ldx
+    int lda, ldb, ld0, ld1, ldx;
+    int tail_ldw, tail_ldo, tail_ldx;
+    int nk, nz;
+    int mrem;                        // M - m0
+    int tail_n;
+    unsigned tk;                     // tail_kt | slice index << 8 (slice 0 also stores the head's own results)
+    int item;                        // item >= 0: no GEMM tile -- the by-value K_COST item `item` (the launch's trailing LaunchArgs)
+    int pad_[2];
+    static constexpr unsigned pack(int tail_kt, int ts) { return (unsigned)tail_kt | (unsigned)ts << 8; }
+};
+static_assert(sizeof(LossRec) == 128 && sizeof(HeadRec) == 128, "a head or loss record is two cache lines");
+static_assert(sizeof(LaunchArgs) + 64 <= 4096, "the record kernels pass LaunchArgs by value behind their leading arguments: 4 KiB");
+// The records the NEXT launch of the run will read, as n 64-byte lines from `lines` on: wave `wave` of workgroup x of this launch
+// makes touch i = (x & 7) + 8 * (4 * (x >> 3) + wave).  One-line records: touch i is line i = record i.  Two-line records
+// (kWarmPairs set in n): touch i is line 2 r + h of record r = (i & 7) + 8 * (i >> 4), h = (i >> 3) & 1.  Either way r % 8 = x % 8:
+// a workgroup on this XCD will read the record, so the line waits in that XCD's L2.  A speed matter only: n = 0, or a line nobody
+// warmed, is the cold read it always was.
+constexpr int kWarmPairs = 1 << 30;
 struct DescWarm { const void* lines; int n; };
 struct TnDescArgs {                   // launch-wide constants of k_small_tn_desc (TnLaunchArgs' of the same names)
     long long d_theta, d_m, d_v;
@@ -675,6 +716,13 @@ void launch_small(int compute_dtype, const LaunchArgs& args, int grid_x, int gri
 void launch_small_desc(int compute_dtype, bool dgrad, int act, const SmallDesc* tab, int n_tiles, int lds_bytes, DescWarm warm, hipStream_t s,
                        unsigned long long* stamps, int launch_id);
 void launch_small_tn_desc(int compute_dtype, const TnDesc* tab, int n_tiles, DescWarm warm, hipStream_t s, unsigned long long* stamps, int launch_id);
+// the output + loss and the two head launches of the training plan on records; `args` rides along for the latent / cost item alone
+void launch_loss_rec(int compute_dtype, const LossRec* tab, int n_recs, int lds_bytes, DescWarm warm, const LaunchArgs& args, hipStream_t s,
+                     unsigned long long* stamps, int launch_id);
+void launch_head_rec(int compute_dtype, int act, const HeadRec* tab, int n_recs, int lds_bytes, DescWarm warm, hipStream_t s,
+                     unsigned long long* stamps, int launch_id);
+void launch_latb_rec(int compute_dtype, int act, const HeadRec* tab, int n_recs, int lds_bytes, DescWarm warm, DevState* st, const LaunchArgs& args,
+                     hipStream_t s, unsigned long long* stamps, int launch_id);
 void launch_reduce(const ReduceArgs& a, int n_blocks, hipStream_t s);
 void launch_chain2(int compute_dtype, const LaunchArgs& args, int grid_x, int grid_y, int lds_bytes, unsigned* counters, unsigned* err, hipStream_t s);
 

@@ -2197,21 +2197,114 @@ std::vector<TnDesc> tn_descs(const avae_handle* h, const Launch& L) {
     return deal_to_xcds(lists);
 }
 
-// Builds the device table of per-workgroup descriptors for the training plan's k_small and k_small_tn launches and points the
-// launches at it (avae_device.h: SmallDesc).  One copy of a launch's records per staging set (a record holds resolved addresses,
-// and some of them point into the set).  AVAE_NO_DESC=1 keeps every launch on its by-value arguments (A/B).
+// The tiles of item w that the by-value kernels run on XCD `part`, in their order there: f(t)
+template <typename F> void tiles_of_part(const WorkItem& w, int part, F&& f) {
+    const int nt = w.tiles_m * w.tiles_n, q = nt >> 3, r = nt & 7;
+    for (int idx = 0; idx < q + (part < r ? 1 : 0); ++idx) f((part < r ? part * (q + 1) : r * (q + 1) + (part - r) * q) + idx);
+}
+
+// The records of the output + loss launch (tile configuration 9): the 32x32 tiles of its K_FWD_OUT_LOSS items as k_small_loss
+// resolves them, and one record per tile of the K_LATENT item that names item and tile.  Empty (the launch stays by-value): an item
+// of another kind, a masked twin's item, an implicit patch matrix.
+std::vector<LossRec> loss_recs(const avae_handle* h, const Launch& L) {
+    std::vector<LossRec> lists[8];
+    const int es = h->es;
+    for (int y = 0; y < L.args.n_items; ++y) {
+        const WorkItem& w = L.args.items[y];
+        if ((w.kind != K_FWD_OUT_LOSS && w.kind != K_LATENT) || w.present || w.conv > 0 || w.bias_ep) return {};
+        for (int part = 0; part < 8; ++part)
+            tiles_of_part(w, part, [&](int t) {
+                LossRec d{};
+                d.item = -1;
+                if (w.kind == K_LATENT) { d.item = y; d.tile = t; lists[part].push_back(d); return; }
+                const int tm = t / w.tiles_n, tn = t - tm * w.tiles_n, m0 = tm * 32, n0 = tn * 32;
+                d.a = static_cast<const unsigned char*>(w.A) + (size_t)m0 * w.lda * es;
+                d.b = static_cast<const unsigned char*>(w.B) + (size_t)n0 * w.ldb * es;
+                d.out = static_cast<unsigned char*>(w.out0) + ((size_t)m0 * w.ld0 + n0) * es;
+                d.x = static_cast<const float*>(w.aux0) + (size_t)m0 * w.ldx + n0;
+                d.slot = w.partial + w.slot_base + t;
+                d.lda = w.lda; d.ldb = w.ldb; d.ld0 = w.ld0; d.ldx = w.ldx;
+                d.nk = (w.K * es) / kTileBytesK;
+                d.mrem = w.M - m0; d.nrem = w.N - n0; d.xrem = w.ldx - n0;
+                d.scale = w.scale; d.binary = w.binary;
+                lists[part].push_back(d);
+            });
+    }
+    return deal_to_xcds(lists);
+}
+
+// The records of a fused head launch: fwd_head + fwd_dec1 (tile configuration 11, K_FWD_HEAD items with a forward tail) or
+// bwd_dec1_latent + bwd_head (10, K_DGRAD_LATENT items with a dgrad tail, and the step's K_COST item as a record that names it).
+std::vector<HeadRec> head_recs(const avae_handle* h, const Launch& L) {
+    std::vector<HeadRec> lists[8];
+    const int es = h->es;
+    const bool bwd = L.cfg == 10;
+    for (int y = 0; y < L.args.n_items; ++y) {
+        const WorkItem& w = L.args.items[y];
+        const bool cost = bwd && w.kind == K_COST;
+        if (!cost && (w.kind != (bwd ? K_DGRAD_LATENT : K_FWD_HEAD) || w.tail_mode != (bwd ? 2 : 1) || w.tail_act != L.lean_act)) return {};
+        if (!cost && (w.present || w.conv > 0 || w.bias_ep || w.tail_kt < 1 || w.tail_kt > 2)) return {};
+        for (int part = 0; part < 8; ++part)
+            tiles_of_part(w, part, [&](int t) {
+                HeadRec d{};
+                d.item = -1;
+                if (cost) { d.item = y; lists[part].push_back(d); return; }
+                const int tm = t / w.tiles_n, ts = t - tm * w.tiles_n, m0 = tm * 32;
+                d.a = static_cast<const unsigned char*>(w.A) + (size_t)m0 * w.lda * es;
+                d.b = static_cast<const unsigned char*>(w.B);
+                d.tail_w = static_cast<const unsigned char*>(w.tail_w);
+                d.tail_out = static_cast<unsigned char*>(w.tail_out) + (size_t)m0 * w.tail_ldo * es;
+                if (bwd) {
+                    d.out0 = static_cast<unsigned char*>(w.out0) + (size_t)m0 * w.ld0 * es;                    // dH, compute dtype
+                    d.aux = static_cast<const float*>(w.aux2) + (size_t)m0 * 3 * ((w.nz + 3) & ~3);           // [g0mu | g0lv | F]
+                    d.tail_aux = static_cast<const unsigned char*>(w.tail_aux) + (size_t)m0 * w.tail_ldx * es;
+                } else {
+                    d.out0 = static_cast<float*>(w.out0) + (size_t)m0 * w.ld0;                                // mulv, fp32
+                    d.out1 = static_cast<unsigned char*>(w.out1) + (size_t)m0 * w.ld1 * es;                    // Z
+                    d.aux = static_cast<const float*>(w.aux0) + (size_t)m0 * w.ldx;                           // eps
+                }
+                d.lda = w.lda; d.ldb = w.ldb; d.ld0 = w.ld0; d.ld1 = w.ld1; d.ldx = w.ldx;
+                d.tail_ldw = w.tail_ldw; d.tail_ldo = w.tail_ldo; d.tail_ldx = w.tail_ldx;
+                d.nk = (w.K * es) / kTileBytesK; d.nz = w.nz;
+                d.mrem = w.M - m0; d.tail_n = w.tail_n;
+                d.tk = HeadRec::pack(w.tail_kt, ts);
+                lists[part].push_back(d);
+            });
+    }
+    return deal_to_xcds(lists);
+}
+
+// Tile configurations whose training-plan launches run on two-line records (LossRec, HeadRec)
+bool two_line_records(const Launch& L) { return L.type == 0 && !L.tn && (L.cfg == 9 || L.cfg == 10 || L.cfg == 11); }
+
+// Builds the device table of per-workgroup descriptors for the training plan's launches and points the launches at it
+// (avae_device.h: SmallDesc, TnDesc, LossRec, HeadRec).  One copy of a launch's records per staging set (a record holds resolved
+// addresses, and some of them point into the set).  AVAE_NO_DESC=1 keeps every launch on its by-value arguments (A/B).
 void build_descriptors(avae_handle* h, hipStream_t s) {
     if (std::getenv("AVAE_NO_DESC")) return;
     std::vector<unsigned char> tab;
     auto add = [&](Launch& L) {
-        if (L.type != 0 || !((L.cfg == 7 && !L.tn) || (L.cfg == 12 && L.tn && L.targs.adam))) return;
+        if (L.type != 0 || !((L.cfg == 7 && !L.tn) || (L.cfg == 12 && L.tn && L.targs.adam) || two_line_records(L))) return;
+        tab.resize((tab.size() + 127) & ~(size_t)127);        // (two-line records start on an even line)
         const size_t off = tab.size();
         size_t stride = 0;
         int n = 0;
+        auto put = [&](const auto& d) {                       // the records of one staging set; false: the launch stays by-value
+            if (d.empty()) { tab.resize(off); return false; }
+            const size_t at = tab.size(), bytes = d.size() * sizeof(d[0]);
+            tab.resize(at + bytes);
+            std::memcpy(tab.data() + at, d.data(), bytes);
+            n = (int)d.size();
+            return true;
+        };
         for (int j = 0; j < kMultiSteps; ++j) {
             const Launch Lj = j == 0 ? L : relocated(h, L, j);
             const size_t at = tab.size();
-            if (L.tn) {
+            if (L.cfg == 9) {
+                if (!put(loss_recs(h, Lj))) return;
+            } else if (L.cfg == 10 || L.cfg == 11) {
+                if (!put(head_recs(h, Lj))) return;
+            } else if (L.tn) {
                 const std::vector<TnDesc> d = tn_descs(h, Lj);
                 if (d.empty()) { tab.resize(off); return; }
                 const TnDescArgs ca = {L.targs.d_theta, L.targs.d_m, L.targs.d_v, L.targs.beta1, L.targs.beta2, L.targs.eps, L.targs.st};
@@ -2245,14 +2338,15 @@ template <typename D> const D* desc_of(const avae_handle* h, const Launch& L) {
 // What a launch warms for the one that runs after it (next, on staging set next_set; null: nothing runs after it in this graph)
 DescWarm warm_for(const avae_handle* h, const Launch* next, int next_set) {
     if (!next || next->desc_n == 0 || next_set >= kMultiSteps) return DescWarm{nullptr, 0};
-    return DescWarm{h->desc_buf.as<unsigned char>() + next->desc_off + (size_t)next_set * next->desc_stride,
-                    next->desc_n + (next->tn ? kTnDescHead : 0)};
+    const int lines = two_line_records(*next) ? 2 * next->desc_n | kWarmPairs : next->desc_n + (next->tn ? kTnDescHead : 0);      // 64-byte lines
+    return DescWarm{h->desc_buf.as<unsigned char>() + next->desc_off + (size_t)next_set * next->desc_stride, lines};
 }
 
 // One launch of a plan as the dumps print it (AVAE_DEBUG_SYNC=1: every launch that runs; AVAE_PLAN_DUMP=1: a serve plan when it is built)
 void dump_launch(const Launch& L) {
     std::fprintf(stderr, "[avae] launch %s type=%d cfg=%d items=%d blocks=%d\n", L.name.c_str(), L.type, L.cfg, L.count, L.blocks);
-    if (L.desc_n) std::fprintf(stderr, "        descriptors=%d set=%d\n", L.desc_n, L.desc_set);      // runs on its records, not on the items below
+    // runs on its records, not on the items below (two-line records: only the latent / cost item is still read from them)
+    if (L.desc_n) std::fprintf(stderr, two_line_records(L) ? "        records=%d set=%d\n" : "        descriptors=%d set=%d\n", L.desc_n, L.desc_set);
     for (int i = 0; i < L.args.n_items && L.type == 0; ++i)
         std::fprintf(stderr, "        item kind=%d M=%d N=%d K=%d lda=%d ldb=%d tiles=%dx%d\n", L.args.items[i].kind, L.args.items[i].M,
                      L.args.items[i].N, L.args.items[i].K, L.args.items[i].lda, L.args.items[i].ldb, L.args.items[i].tiles_m, L.args.items[i].tiles_n);
@@ -2277,6 +2371,9 @@ void run_launch(avae_handle* h, const Launch& L, hipStream_t s, unsigned long lo
     else if (L.type == 8) launch_rowsum(h->cfg.compute_dtype, L.rs, L.blocks, s);
     else if (L.type == 9) launch_sums(L.ra, L.blocks, s);
     else if (L.cfg == 13) launch_chain2(h->cfg.compute_dtype, L.args, L.grid_x, L.grid_y, L.lds, h->at<unsigned>(h->off_chain), h->at<unsigned>(h->off_chain) + kMaxMod * 64, s);
+    else if (L.cfg == 11 && L.desc_n) launch_head_rec(h->cfg.compute_dtype, L.lean_act, desc_of<HeadRec>(h, L), L.desc_n, L.lds, warm, s, stamps, stamp);
+    else if (L.cfg == 10 && L.desc_n) launch_latb_rec(h->cfg.compute_dtype, L.lean_act, desc_of<HeadRec>(h, L), L.desc_n, L.lds, warm, h->state(), L.args, s, stamps, stamp);
+    else if (L.cfg == 9 && L.desc_n) launch_loss_rec(h->cfg.compute_dtype, desc_of<LossRec>(h, L), L.desc_n, L.lds, warm, L.args, s, stamps, stamp);
     else if (L.cfg == 11) launch_small_head(h->cfg.compute_dtype, L.lean_act, L.args, L.grid_x, L.grid_y, L.lds, s, stamps, stamp);
     else if (L.cfg == 10) launch_small_latb(h->cfg.compute_dtype, L.lean_act, L.args, L.grid_x, L.grid_y, L.lds, h->state(), s, stamps, stamp);
     else if (L.cfg == 9) launch_small_loss(h->cfg.compute_dtype, L.args, L.grid_x, L.grid_y, L.lds, s, stamps, stamp);
@@ -2304,8 +2401,9 @@ bool has_hyper_item(const Launch& L) {
 // the launches write their clock stamps from slot stamp_base on.  train: a training step -- with a schedule set its latent and cost
 // launches are copies that point at the step's schedule entry (every other caller runs the tables as they are: multipliers 1).
 // after / after_set: the launch that runs behind ls[hi - 1] and its staging set -- the last launch warms its descriptors (warm_for).
+// records2 = false (a masked step): the launches on two-line records run on their by-value arguments.
 void run_set(avae_handle* h, const std::vector<Launch>& ls, size_t lo, size_t hi, int j, hipStream_t s, int stamp_base = -1, bool train = false,
-             const Launch* after = nullptr, int after_set = 0) {
+             const Launch* after = nullptr, int after_set = 0, bool records2 = true) {
     unsigned long long* stamps = nullptr;
 #ifdef AVAE_STAMPS
     if (stamp_base >= 0) stamps = h->at<unsigned long long>(h->off_stamps);
@@ -2320,8 +2418,11 @@ void run_set(avae_handle* h, const std::vector<Launch>& ls, size_t lo, size_t hi
         const int k = stamp_base + (int)(i - lo);
         const bool last = i + 1 >= hi || i + 1 >= ls.size();
         const DescWarm warm = last ? warm_for(h, after, after_set) : warm_for(h, &ls[i + 1], j);
-        if (j == 0 && !(hyper && has_hyper_item(ls[i]))) run_launch(h, ls[i], s, stamps, k, warm);
-        else run_launch(h, relocated(h, ls[i], j, hyper), s, stamps, k, warm);
+        const bool strip = !records2 && ls[i].desc_n && two_line_records(ls[i]);
+        if (j == 0 && !(hyper && has_hyper_item(ls[i])) && !strip) { run_launch(h, ls[i], s, stamps, k, warm); continue; }
+        Launch L = relocated(h, ls[i], j, hyper);
+        if (strip) L.desc_n = 0;
+        run_launch(h, L, s, stamps, k, warm);
     }
 }
 
@@ -2514,7 +2615,8 @@ void step_body(avae_handle* h, const std::vector<Launch>& fwd, hipStream_t s, in
     auto first_of = [](const std::vector<Launch>& ls) { return ls.empty() ? nullptr : &ls[0]; };
     const bool fused = !h->wgrad_adam.empty() && !h->clip_on && !h->ema_on;
     run_set(h, fwd, 0, fwd.size(), j, s, stamp_base, true, first_of(h->bwd), j);
-    run_set(h, h->bwd, 0, h->bwd.size(), j, s, sb(fwd.size()), true, fused ? first_of(h->wgrad_adam) : nullptr, j);
+    const bool plain = &fwd == &h->plain.fwd;      // (the masked twin's head and loss launches stay by-value; the backward launches are shared)
+    run_set(h, h->bwd, 0, h->bwd.size(), j, s, sb(fwd.size()), true, fused ? first_of(h->wgrad_adam) : nullptr, j, plain);
     if (fused) {       // the optimiser rides in the weight-gradient launch
         run_set(h, h->wgrad_adam, 0, h->wgrad_adam.size(), j, s, sb(fwd.size() + h->bwd.size()), true, more ? first_of(fwd) : nullptr, j + 1);
         return;
@@ -3285,6 +3387,7 @@ void build_masked(avae_handle* h) {
     }
     if (n_loss != h->M || n_latent != 1) throw Err("internal error: the masked twin found " + std::to_string(n_loss) + " loss and " +
                                                    std::to_string(n_latent) + " latent items");
+    for (Launch& L : mf) if (two_line_records(L)) L.desc_n = 0;      // the records know no presence bytes: the twin's launches stay by-value
     h->masked.fwd.swap(mf);
     if (h->cfg.use_graph) {
         try { capture_plan(h, h->masked, pres); } catch (...) { h->masked.fwd.clear(); throw; }      // the next masked call builds it again

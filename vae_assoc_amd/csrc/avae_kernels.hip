@@ -1517,14 +1517,16 @@ __global__ void __launch_bounds__(kThreads) k_small(const LaunchArgs args, unsig
     AVAE_STAMP_FLUSH()
 }
 
-// One descriptor record of the next launch per wave (DescWarm), as a scalar load: the line is in this XCD's L2 when the workgroup
+// One line of the next launch's records per wave (DescWarm), as a scalar load: the line is in this XCD's L2 when the workgroup
 // that owns it starts.  A scalar load counts in lgkmcnt only, so no counted vmcnt wait of the K loops moves; the LDS reads' waits can
 // only get stricter (an extra operation outstanding never lets lgkmcnt reach a value early).  The caller names the result in an
 // empty statement at its very end, which keeps the load and leaves the compiler's own wait for it behind all useful work.
+// kWarmPairs in n: the records are two lines each, and the touches of this XCD are dealt over both lines of its records.
 __device__ __forceinline__ unsigned desc_warm(const void* lines, int n, int wave) {
     typedef const __attribute__((address_space(4))) unsigned* cu_t;
     const int i = (blockIdx.x & 7) + 8 * (4 * (blockIdx.x >> 3) + wave);
-    return i < n ? *(cu_t)((unsigned long long)lines + 64ull * (unsigned)i) : 0u;
+    const int line = (n & kWarmPairs) ? 2 * ((i & 7) + 8 * (i >> 4)) + ((i >> 3) & 1) : i;
+    return line < (n & ~kWarmPairs) ? *(cu_t)((unsigned long long)lines + 64ull * (unsigned)line) : 0u;
 }
 
 // k_small on per-workgroup descriptors (training plan; avae_device.h: SmallDesc): record blockIdx.x holds the tile's operand rows,
@@ -1622,6 +1624,83 @@ template <typename K> static void set_max_lds(K kernel) {
 // item) and the K_LATENT item that rides with them.  The exact fp32 inputs the loss compares with are fetched ahead of the first tile;
 // loss, gradient and the tile's cost partial come from the accumulators (one LDS round for the fixed-order block sum).
 // MASK (the masked twin's launch, WorkItem::present set): the loss and gradient of a row whose modality is absent are 0 by selection.
+// The tile itself is small_loss_tile, on a resolved record (avae_device.h: LossRec): k_small_loss works the record out of its by-value
+// item, k_loss_rec (the training plan) reads it from the plan's table.  present: the presence bytes at the tile's first row (MASK
+// only).  behind_prologue() is called once, behind the prologue's tiles.
+#ifdef AVAE_STAMPS
+#define AVAE_SV sv
+#else
+#define AVAE_SV nullptr
+#endif
+// A pointer read from a record is generic to the compiler (one from the kernel arguments is known to be global): accesses through it
+// would become flat_* instructions, which count in lgkmcnt as well and, behind an LDS-DMA, get a vmcnt(0) of the compiler's in front
+// of them.  Through this cast the record kernels' accesses are the by-value kernels' global_* ones.
+template <typename T> __device__ __forceinline__ T* as_global(T* p) {
+    return (T*)(__attribute__((address_space(1))) T*)(unsigned long long)p;      // (through an integer: a pointer-to-pointer cast pair is folded away)
+}
+template <typename CT, bool MASK, typename F>
+__device__ __forceinline__ void small_loss_tile(const LossRec& d, const unsigned char* present, int present_ld, F&& behind_prologue,
+                                                unsigned char* smem, float* red, unsigned long long* sv) {
+    constexpr int RING = 4, ES = (int)sizeof(CT);
+    constexpr int kStage = 64 * kTileBytesK;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wr = wave >> 1, wc = wave & 1, fr = lane & 15, fq = lane >> 4;
+    const int nk = d.nk;
+    typedef const __attribute__((address_space(1))) void* gp_t;
+    typedef __attribute__((address_space(3))) void* lp_t;
+    const int prow = wave * 8 + (lane >> 3), lc = ((lane & 7) ^ ((prow >> 1) & 7)) * 16;
+    const unsigned char* srcA = d.a + (size_t)prow * d.lda * ES + lc;
+    const unsigned char* srcB = d.b + (size_t)prow * d.ldb * ES + lc;
+    const int lrow = wr * 16 + fr, lcol = wc * 16 + 4 * fq;
+    const f32x4 xq = *reinterpret_cast<const f32x4*>(as_global(d.x) + (ptrdiff_t)min(lrow, d.mrem - 1) * d.ldx + min(lcol, d.xrem - 4));
+    bool rpres = true;                                             // this lane's row is present
+    if constexpr (MASK) rpres = as_global(present)[(size_t)min(lrow, d.mrem - 1) * present_ld] != 0;
+#define AVAE_S_DMA(kt, buf)                                                                                             \
+    { __builtin_amdgcn_global_load_lds((gp_t)(srcA + (size_t)(kt) * kTileBytesK), (lp_t)(smem + (buf) * kStage + wave * 1024), 16, 0, 0);          \
+      __builtin_amdgcn_global_load_lds((gp_t)(srcB + (size_t)(kt) * kTileBytesK), (lp_t)(smem + (buf) * kStage + (4 + wave) * 1024), 16, 0, 0); }
+    AVAE_STAMP(1)
+    const int npro = nk < RING - 1 ? nk : RING - 1;
+    for (int p = 0; p < npro; ++p) AVAE_S_DMA(p, p)
+    behind_prologue();
+    const int sw0 = (fq ^ (fr >> 1)) * 16;
+    const int aoff = (wr * 16 + fr) * kTileBytesK, boff = (32 + wc * 16 + fr) * kTileBytesK;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    int buf = 0;
+    for (int kt = 0; kt < nk; ++kt) {
+        const int rem = nk - 1 - kt;
+        if (rem >= 2) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+        else if (rem == 1) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        asm volatile("s_barrier" ::: "memory");
+        if (kt == 0) { AVAE_STAMP(2) }
+        const unsigned char* Sb = smem + buf * kStage;
+        const u32x4 a0 = *reinterpret_cast<const u32x4*>(Sb + aoff + sw0), b0 = *reinterpret_cast<const u32x4*>(Sb + boff + sw0);
+        const int fill = buf == 0 ? RING - 1 : buf - 1;
+        if (kt + RING - 1 < nk) AVAE_S_DMA(kt + RING - 1, fill)
+        const u32x4 a1 = *reinterpret_cast<const u32x4*>(Sb + aoff + (sw0 ^ 64)), b1 = *reinterpret_cast<const u32x4*>(Sb + boff + (sw0 ^ 64));
+        mma<CT>(b0, a0, acc);
+        mma<CT>(b1, a1, acc);
+        buf = buf + 1 == RING ? 0 : buf + 1;
+    }
+#undef AVAE_S_DMA
+    AVAE_STAMP(3)
+    // (loss_bernoulli / loss_gauss; the Bernoulli term is a mean over the batch, the Gaussian a sum over the WHOLE batch: w.scale, :340)
+    const float sc = d.scale;
+    float csum = 0.0f, v[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const bool ok = lrow < d.mrem && lcol + e < d.nrem && rpres;
+        float sl, da;
+        if (d.binary) loss_bernoulli(acc[e], xq[e], sc, sl, da);
+        else loss_gauss(acc[e], xq[e], sc, sl, da);
+        csum += ok ? sl : 0.0f;
+        v[e] = ok ? da : 0.0f;
+    }
+    if (lrow < d.mrem && lcol < d.nrem) store_row<CT>(as_global(reinterpret_cast<CT*>(d.out)) + (size_t)lrow * d.ld0 + lcol, v, d.nrem - lcol);
+    const float total = block_sum<4>(csum, red);
+    if (tid == 0) *as_global(d.slot) = total;
+}
+
 template <typename CT, bool MASK>
 __global__ void __launch_bounds__(kThreads) k_small_loss(const LaunchArgs args, unsigned long long* stamps, int launch_id) {
     constexpr int BM = 32, RING = 4, ES = (int)sizeof(CT);
@@ -1648,64 +1727,59 @@ __global__ void __launch_bounds__(kThreads) k_small_loss(const LaunchArgs args, 
         AVAE_STAMP_FLUSH()
         return;
     }
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wr = wave >> 1, wc = wave & 1, fr = lane & 15, fq = lane >> 4;
     const int tm = t / w.tiles_n, tn = t - tm * w.tiles_n;
     const int m0 = tm * BM, n0 = tn * 32;
-    const int nk = (w.K * ES) / kTileBytesK;
-    typedef const __attribute__((address_space(1))) void* gp_t;
-    typedef __attribute__((address_space(3))) void* lp_t;
-    const int prow = wave * 8 + (lane >> 3), lc = ((lane & 7) ^ ((prow >> 1) & 7)) * 16;
-    const unsigned char* srcA = reinterpret_cast<const unsigned char*>(w.A) + (size_t)(m0 + prow) * w.lda * ES + lc;
-    const unsigned char* srcB = reinterpret_cast<const unsigned char*>(w.B) + (size_t)(n0 + prow) * w.ldb * ES + lc;
-    const int orow = m0 + wr * 16 + fr, ocol = n0 + wc * 16 + 4 * fq;
-    const f32x4 xq = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(w.aux0) + (size_t)min(orow, w.M - 1) * w.ldx + min(ocol, w.ldx - 4));
-    const bool rpres = !MASK || w.present[(size_t)min(orow, w.M - 1) * w.present_ld] != 0;      // this lane's row is present
-#define AVAE_S_DMA(kt, buf)                                                                                             \
-    { __builtin_amdgcn_global_load_lds((gp_t)(srcA + (size_t)(kt) * kTileBytesK), (lp_t)(smem + (buf) * kStage + wave * 1024), 16, 0, 0);          \
-      __builtin_amdgcn_global_load_lds((gp_t)(srcB + (size_t)(kt) * kTileBytesK), (lp_t)(smem + (buf) * kStage + (4 + wave) * 1024), 16, 0, 0); }
-    AVAE_STAMP(1)
-    const int npro = nk < RING - 1 ? nk : RING - 1;
-    for (int p = 0; p < npro; ++p) AVAE_S_DMA(p, p)
-    const int sw0 = (fq ^ (fr >> 1)) * 16;
-    const int aoff = (wr * 16 + fr) * kTileBytesK, boff = (32 + wc * 16 + fr) * kTileBytesK;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    int buf = 0;
-    for (int kt = 0; kt < nk; ++kt) {
-        const int rem = nk - 1 - kt;
-        if (rem >= 2) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        else if (rem == 1) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        asm volatile("s_barrier" ::: "memory");
-        if (kt == 0) { AVAE_STAMP(2) }
-        const unsigned char* Sb = smem + buf * kStage;
-        const u32x4 a0 = *reinterpret_cast<const u32x4*>(Sb + aoff + sw0), b0 = *reinterpret_cast<const u32x4*>(Sb + boff + sw0);
-        const int fill = buf == 0 ? RING - 1 : buf - 1;
-        if (kt + RING - 1 < nk) AVAE_S_DMA(kt + RING - 1, fill)
-        const u32x4 a1 = *reinterpret_cast<const u32x4*>(Sb + aoff + (sw0 ^ 64)), b1 = *reinterpret_cast<const u32x4*>(Sb + boff + (sw0 ^ 64));
-        mma<CT>(b0, a0, acc);
-        mma<CT>(b1, a1, acc);
-        buf = buf + 1 == RING ? 0 : buf + 1;
-    }
-#undef AVAE_S_DMA
-    AVAE_STAMP(3)
-    // (loss_bernoulli / loss_gauss; the Bernoulli term is a mean over the batch, the Gaussian a sum over the WHOLE batch: w.scale, :340)
-    const float sc = w.scale;
-    float csum = 0.0f, v[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const bool ok = orow < w.M && ocol + e < w.N && rpres;
-        float sl, da;
-        if (w.binary) loss_bernoulli(acc[e], xq[e], sc, sl, da);
-        else loss_gauss(acc[e], xq[e], sc, sl, da);
-        csum += ok ? sl : 0.0f;
-        v[e] = ok ? da : 0.0f;
-    }
-    if (orow < w.M && ocol < w.N) store_row<CT>(reinterpret_cast<CT*>(w.out0) + (size_t)orow * w.ld0 + ocol, v, w.N - ocol);
-    const float total = block_sum<4>(csum, red);
-    if (tid == 0) w.partial[w.slot_base + t] = total;
+    LossRec d;
+    d.a = reinterpret_cast<const unsigned char*>(w.A) + (size_t)m0 * w.lda * ES;
+    d.b = reinterpret_cast<const unsigned char*>(w.B) + (size_t)n0 * w.ldb * ES;
+    d.out = reinterpret_cast<CT*>(w.out0) + (size_t)m0 * w.ld0 + n0;
+    d.x = reinterpret_cast<const float*>(w.aux0) + (size_t)m0 * w.ldx + n0;
+    d.slot = w.partial + w.slot_base + t;
+    d.lda = w.lda; d.ldb = w.ldb; d.ld0 = w.ld0; d.ldx = w.ldx;
+    d.nk = (w.K * ES) / kTileBytesK;
+    d.mrem = w.M - m0; d.nrem = w.N - n0; d.xrem = w.ldx - n0;
+    d.scale = w.scale; d.binary = w.binary;
+    const unsigned char* present = nullptr;
+    if constexpr (MASK) present = w.present + (size_t)m0 * w.present_ld;
+    small_loss_tile<CT, MASK>(d, present, w.present_ld, []() {}, smem, red, AVAE_SV);
     AVAE_STAMP(4)
     AVAE_STAMP_FLUSH()
+}
+
+// The training plan's instance: record blockIdx.x in one scalar burst off the preloaded table pointer, the successor's records
+// warmed behind the prologue's tiles.  A record of the K_LATENT item names the item and its tile; the item itself is read from the
+// by-value arguments as before (a step with a schedule set patches it per step: relocated()).
+template <typename CT>
+__global__ void __launch_bounds__(kThreads) k_loss_rec(const LossRec* __restrict__ tab, unsigned long long* stamps, int launch_id,
+                                                       const void* warm_lines, int warm_n, const LaunchArgs args) {
+    unsigned char* smem = avae_dyn_smem;
+    float* red = reinterpret_cast<float*>(smem + 4 * 64 * kTileBytesK);
+#ifdef AVAE_STAMPS
+    unsigned long long sv[kStampWords] = {0, 0, 0, 0, 0, 0, 0, 0};
+#endif
+    AVAE_STAMP(0)
+    const LossRec d = tab[blockIdx.x];
+    // (named here: both lines come in ONE burst ahead of the branch, not field by field as the code below gets to them)
+    asm volatile("" :: "s"(d.a), "s"(d.b), "s"(d.out), "s"(d.x), "s"(d.slot), "s"(d.lda), "s"(d.ldb), "s"(d.ld0), "s"(d.ldx), "s"(d.nk), "s"(d.mrem),
+                 "s"(d.nrem), "s"(d.xrem), "s"(d.scale), "s"(d.binary), "s"(d.item), "s"(d.tile));
+    if (d.item >= 0) {
+        latent_item<4, false>(args.items[d.item], d.tile, red);
+        AVAE_STAMP(4)
+        AVAE_STAMP_FLUSH()
+        return;
+    }
+    unsigned warmed = 0;
+    small_loss_tile<CT, false>(d, nullptr, 0, [&]() { warmed = desc_warm(warm_lines, warm_n, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6)); },
+                               smem, red, AVAE_SV);
+    asm volatile("" :: "s"(warmed));
+    AVAE_STAMP(4)
+    AVAE_STAMP_FLUSH()
+}
+void launch_loss_rec(int compute_dtype, const LossRec* tab, int n_recs, int lds_bytes, DescWarm warm, const LaunchArgs& args, hipStream_t s,
+                     unsigned long long* stamps, int launch_id) {
+    const dim3 grid(n_recs), block(kThreads);
+    if (compute_dtype == AVAE_BF16) AVAE_LAUNCH((k_loss_rec<__bf16>), grid, block, lds_bytes, s, tab, stamps, launch_id, warm.lines, warm.n, args);
+    else AVAE_LAUNCH((k_loss_rec<float>), grid, block, lds_bytes, s, tab, stamps, launch_id, warm.lines, warm.n, args);
 }
 void launch_small_loss(int compute_dtype, const LaunchArgs& args, int grid_x, int grid_y, int lds_bytes, hipStream_t s, unsigned long long* stamps, int launch_id) {
     const dim3 grid(grid_x, grid_y), block(kThreads);
@@ -1732,49 +1806,29 @@ template <typename CT> __device__ __forceinline__ void img_put(unsigned char* im
 // bwd_dec1_latent + bwd_head: dz = dA . V1^T from the accumulators; dmu = dz + g0mu, dlv = dz * F + g0lv per lane (the latent item's
 // static gradients fetched ahead of the first tile); [dmu | dlv] -> dH and -> the image; tail = the heads' input gradient.  The step's
 // K_COST item rides in the launch.
-template <typename CT, int ACT>
-__global__ void __launch_bounds__(kThreads) k_small_latb(const LaunchArgs args, DevState* st, unsigned long long* stamps, int launch_id) {
+// The tile itself is small_latb_tile, on a resolved record (avae_device.h: HeadRec): k_small_latb works the record out of its
+// by-value item, k_latb_rec (the training plan) reads it from the plan's table.  behind_prologue() is called once, behind the
+// prologue's tiles and the kExtra loads.
+template <typename CT, int ACT, typename F>
+__device__ __forceinline__ void small_latb_tile(const HeadRec& d, F&& behind_prologue, unsigned char* smem, unsigned long long* sv) {
     constexpr int RING = 4, ES = (int)sizeof(CT), TSL = ES == 2 ? 2 : 4;
-    unsigned char* smem = avae_dyn_smem;
     unsigned char* img = smem + RING * kHeadStage;
-    float* red = reinterpret_cast<float*>(img + kHeadImg);
-#ifdef AVAE_STAMPS
-    unsigned long long sv[kStampWords] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
-    AVAE_STAMP(0)
-    const int part = blockIdx.x & 7, idx = blockIdx.x >> 3;
-    const WorkItem w = args.items[blockIdx.y];
-    asm volatile("" :: "s"(w.A), "s"(w.B), "s"(w.out0), "s"(w.aux2), "s"(w.lda), "s"(w.ldb), "s"(w.K), "s"(w.ld0), "s"(w.tail_w), "s"(w.tail_out), "s"(w.tail_aux));
-    int t;
-    {
-        const int nt = w.tiles_m * w.tiles_n;
-        const int q = nt >> 3, r = nt & 7;
-        if (idx >= q + (part < r ? 1 : 0)) return;
-        t = (part < r ? part * (q + 1) : r * (q + 1) + (part - r) * q) + idx;
-    }
-    if (w.kind == K_COST) {
-        cost_item<4>(w, st, red);
-        AVAE_STAMP(4)
-        AVAE_STAMP_FLUSH()
-        return;
-    }
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave >> 1, wc = wave & 1, fr = lane & 15, fq = lane >> 4;
-    const int tm = t / w.tiles_n, ts = t - tm * w.tiles_n;     // row block, tail slice
-    const int m0 = tm * 32;
-    const int nk = (w.K * ES) / kTileBytesK, nz = w.nz;
+    const int ts = d.tk >> 8;                                  // tail slice
+    const int nk = d.nk, nz = d.nz;
     typedef const __attribute__((address_space(1))) void* gp_t;
     typedef __attribute__((address_space(3))) void* lp_t;
     reinterpret_cast<f32x4*>(img)[tid] = f32x4{0.f, 0.f, 0.f, 0.f};                 // the image's padding columns: zero (8 KiB = 2 x 256 x 16 B)
     reinterpret_cast<f32x4*>(img)[tid + kThreads] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int orow = m0 + wr * 16 + fr;
+    const int lrow = wr * 16 + fr;
     const int lde = (nz + 3) & ~3;
-    const int t_i = wave & 1, t_c0 = (2 * ts + (wave >> 1)) * 32, t_sl = 2 * w.tail_kt;
+    const int t_i = wave & 1, t_c0 = (2 * ts + (wave >> 1)) * 32, t_sl = 2 * (int)(d.tk & 0xFF);
     // ---- K loop: three 1-KiB pieces per wave and stage (A rows 8 wave .., B rows 8 wave .. and 32 + 8 wave ..)
     const int prow = wave * 8 + (lane >> 3), lc = ((lane & 7) ^ ((prow >> 1) & 7)) * 16;
-    const unsigned char* srcA = reinterpret_cast<const unsigned char*>(w.A) + (size_t)(m0 + prow) * w.lda * ES + lc;
-    const unsigned char* srcB = reinterpret_cast<const unsigned char*>(w.B) + (size_t)prow * w.ldb * ES + lc;
-    const size_t b32 = (size_t)32 * w.ldb * ES;
+    const unsigned char* srcA = d.a + (size_t)prow * d.lda * ES + lc;
+    const unsigned char* srcB = d.b + (size_t)prow * d.ldb * ES + lc;
+    const size_t b32 = (size_t)32 * d.ldb * ES;
 #define AVAE_H_DMA(kt, buf)                                                                                             \
     { __builtin_amdgcn_global_load_lds((gp_t)(srcA + (size_t)(kt) * kTileBytesK), (lp_t)(smem + (buf) * kHeadStage + wave * 1024), 16, 0, 0);       \
       __builtin_amdgcn_global_load_lds((gp_t)(srcB + (size_t)(kt) * kTileBytesK), (lp_t)(smem + (buf) * kHeadStage + (4 + wave) * 1024), 16, 0, 0); \
@@ -1790,20 +1844,21 @@ __global__ void __launch_bounds__(kThreads) k_small_latb(const LaunchArgs args, 
     f32x4 gm[2], gl[2], gf[2];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-        const float* gr = reinterpret_cast<const float*>(w.aux2) + (size_t)min(orow, w.M - 1) * 3 * lde + min(wc * 32 + j * 16 + 4 * fq, lde - 4);
+        const float* gr = as_global(d.aux) + (size_t)min(lrow, d.mrem - 1) * 3 * lde + min(wc * 32 + j * 16 + 4 * fq, lde - 4);
         gm[j] = *reinterpret_cast<const f32x4*>(gr); gl[j] = *reinterpret_cast<const f32x4*>(gr + lde); gf[j] = *reinterpret_cast<const f32x4*>(gr + 2 * lde);
     }
     u32x4 tb[TSL][2];
     typename Quad<CT>::raw ty[2];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-        const unsigned char* pw = reinterpret_cast<const unsigned char*>(w.tail_w) + (size_t)min(t_c0 + 16 * j + fr, w.tail_n - 1) * w.tail_ldw * ES + fq * 16;
+        const unsigned char* pw = as_global(d.tail_w) + (size_t)min(t_c0 + 16 * j + fr, d.tail_n - 1) * d.tail_ldw * ES + fq * 16;
 #pragma unroll
         for (int sl = 0; sl < TSL; ++sl) tb[sl][j] = *reinterpret_cast<const u32x4*>(pw + (sl < t_sl ? 64 * sl : 0));
-        ty[j] = *reinterpret_cast<const typename Quad<CT>::raw*>(reinterpret_cast<const CT*>(w.tail_aux) + (size_t)min(m0 + 16 * t_i + fr, w.M - 1) * w.tail_ldx
-                                                                   + min(t_c0 + 16 * j + 4 * fq, w.tail_ldx - 4));
+        ty[j] = *reinterpret_cast<const typename Quad<CT>::raw*>(as_global(reinterpret_cast<const CT*>(d.tail_aux)) + (size_t)min(16 * t_i + fr, d.mrem - 1) * d.tail_ldx
+                                                                   + min(t_c0 + 16 * j + 4 * fq, d.tail_ldx - 4));
     }
     asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0);
+    behind_prologue();
     const int sw0 = (fq ^ (fr >> 1)) * 16;
     const int aoff = (wr * 16 + fr) * kTileBytesK, boff = (32 + wc * 32 + fr) * kTileBytesK;
     f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
@@ -1841,20 +1896,19 @@ __global__ void __launch_bounds__(kThreads) k_small_latb(const LaunchArgs args, 
     AVAE_STAMP(3)
     // ---- dz -> (dmu, dlv): into the image (every slice) and into dH (slice 0)
     {
-        CT* dH = reinterpret_cast<CT*>(w.out0) + (size_t)orow * w.ld0;
-        const bool store = ts == 0 && orow < w.M;
-        const int lrow = wr * 16 + fr;
+        CT* dH = as_global(reinterpret_cast<CT*>(d.out0)) + (size_t)lrow * d.ld0;
+        const bool store = ts == 0 && lrow < d.mrem;
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const int d = wc * 32 + j * 16 + 4 * fq + e;
-                if (d < nz) {
+                const int dim = wc * 32 + j * 16 + 4 * fq + e;
+                if (dim < nz) {
                     const float dz = acc[j][e];
                     const float dmu = dz + gm[j][e], dlv = __builtin_fmaf(dz, gf[j][e], gl[j][e]);
-                    img_put<CT>(img, lrow, d, dmu);
-                    img_put<CT>(img, lrow, nz + d, dlv);
-                    if (store) { dH[d] = to_ct<CT>(dmu); dH[nz + d] = to_ct<CT>(dlv); }
+                    img_put<CT>(img, lrow, dim, dmu);
+                    img_put<CT>(img, lrow, nz + dim, dlv);
+                    if (store) { dH[dim] = to_ct<CT>(dmu); dH[nz + dim] = to_ct<CT>(dlv); }
                 }
             }
     }
@@ -1871,28 +1925,23 @@ __global__ void __launch_bounds__(kThreads) k_small_latb(const LaunchArgs args, 
                 mma<CT>(tb[sl][0], ta, tacc[0][0]);
                 mma<CT>(tb[sl][1], ta, tacc[0][1]);
             }
-        regep_store<CT, 1, 2>(tacc, reinterpret_cast<CT*>(w.tail_out), w.tail_ldo, w.M, w.tail_n, m0 + arow, t_c0, lane,
+        regep_store<CT, 1, 2>(tacc, as_global(reinterpret_cast<CT*>(d.tail_out)), d.tail_ldo, d.mrem, d.tail_n, arow, t_c0, lane,
             [&](int, int j, int r, float v) { return v * act_bwd_t<ACT>(quad_elem<CT>(ty[j], r)); });
     }
-    AVAE_STAMP(4)
-    AVAE_STAMP_FLUSH()
 }
-// fwd_head + fwd_dec1: [mu | lv] from the accumulators -> mulv (fp32, slice 0) and -> an fp32 tile in LDS (the ring is free by then);
-// z = mu + exp(lv / 2) * eps by one thread per (row, four latent dims) with eps fetched ahead of the first tile -> Z (slice 0) and
-// -> the image, with its constant-1 column; tail = the decoder's first layer.
+
 template <typename CT, int ACT>
-__global__ void __launch_bounds__(kThreads) k_small_head(const LaunchArgs args, unsigned long long* stamps, int launch_id) {
-    constexpr int RING = 4, ES = (int)sizeof(CT), TSL = ES == 2 ? 2 : 4, LDM = 68;
+__global__ void __launch_bounds__(kThreads) k_small_latb(const LaunchArgs args, DevState* st, unsigned long long* stamps, int launch_id) {
+    constexpr int ES = (int)sizeof(CT);
     unsigned char* smem = avae_dyn_smem;
-    unsigned char* img = smem + RING * kHeadStage;
-    float* MV = reinterpret_cast<float*>(smem);                // [32][LDM] fp32, over the ring (after the loop's last barrier)
+    float* red = reinterpret_cast<float*>(smem + 4 * kHeadStage + kHeadImg);
 #ifdef AVAE_STAMPS
     unsigned long long sv[kStampWords] = {0, 0, 0, 0, 0, 0, 0, 0};
 #endif
     AVAE_STAMP(0)
     const int part = blockIdx.x & 7, idx = blockIdx.x >> 3;
     const WorkItem w = args.items[blockIdx.y];
-    asm volatile("" :: "s"(w.A), "s"(w.B), "s"(w.out0), "s"(w.out1), "s"(w.aux0), "s"(w.lda), "s"(w.ldb), "s"(w.K), "s"(w.ld0), "s"(w.tail_w), "s"(w.tail_out));
+    asm volatile("" :: "s"(w.A), "s"(w.B), "s"(w.out0), "s"(w.aux2), "s"(w.lda), "s"(w.ldb), "s"(w.K), "s"(w.ld0), "s"(w.tail_w), "s"(w.tail_out), "s"(w.tail_aux));
     int t;
     {
         const int nt = w.tiles_m * w.tiles_n;
@@ -1900,30 +1949,90 @@ __global__ void __launch_bounds__(kThreads) k_small_head(const LaunchArgs args, 
         if (idx >= q + (part < r ? 1 : 0)) return;
         t = (part < r ? part * (q + 1) : r * (q + 1) + (part - r) * q) + idx;
     }
+    if (w.kind == K_COST) {
+        cost_item<4>(w, st, red);
+        AVAE_STAMP(4)
+        AVAE_STAMP_FLUSH()
+        return;
+    }
+    const int tm = t / w.tiles_n, ts = t - tm * w.tiles_n;     // row block, tail slice
+    const int m0 = tm * 32;
+    HeadRec d;
+    d.a = reinterpret_cast<const unsigned char*>(w.A) + (size_t)m0 * w.lda * ES;
+    d.b = reinterpret_cast<const unsigned char*>(w.B);
+    d.out0 = reinterpret_cast<CT*>(w.out0) + (size_t)m0 * w.ld0;
+    d.aux = reinterpret_cast<const float*>(w.aux2) + (size_t)m0 * 3 * ((w.nz + 3) & ~3);
+    d.tail_w = reinterpret_cast<const unsigned char*>(w.tail_w);
+    d.tail_out = reinterpret_cast<CT*>(w.tail_out) + (size_t)m0 * w.tail_ldo;
+    d.tail_aux = reinterpret_cast<const CT*>(w.tail_aux) + (size_t)m0 * w.tail_ldx;
+    d.lda = w.lda; d.ldb = w.ldb; d.ld0 = w.ld0;
+    d.tail_ldw = w.tail_ldw; d.tail_ldo = w.tail_ldo; d.tail_ldx = w.tail_ldx;
+    d.nk = (w.K * ES) / kTileBytesK; d.nz = w.nz;
+    d.mrem = w.M - m0; d.tail_n = w.tail_n;
+    d.tk = HeadRec::pack(w.tail_kt, ts);
+    small_latb_tile<CT, ACT>(d, []() {}, smem, AVAE_SV);
+    AVAE_STAMP(4)
+    AVAE_STAMP_FLUSH()
+}
+
+// The training plan's instance (see k_loss_rec).  A record of the K_COST item names the item, which is read from the by-value
+// arguments as before.
+template <typename CT, int ACT>
+__global__ void __launch_bounds__(kThreads) k_latb_rec(const HeadRec* __restrict__ tab, unsigned long long* stamps, int launch_id,
+                                                       const void* warm_lines, int warm_n, DevState* st, const LaunchArgs args) {
+    unsigned char* smem = avae_dyn_smem;
+#ifdef AVAE_STAMPS
+    unsigned long long sv[kStampWords] = {0, 0, 0, 0, 0, 0, 0, 0};
+#endif
+    AVAE_STAMP(0)
+    const HeadRec d = tab[blockIdx.x];
+    asm volatile("" :: "s"(d.a), "s"(d.b), "s"(d.out0), "s"(d.aux), "s"(d.tail_w), "s"(d.tail_out), "s"(d.tail_aux), "s"(d.lda), "s"(d.ldb), "s"(d.ld0),
+                 "s"(d.tail_ldw), "s"(d.tail_ldo), "s"(d.tail_ldx), "s"(d.nk), "s"(d.nz), "s"(d.mrem), "s"(d.tail_n), "s"(d.tk), "s"(d.item));      // one burst
+    if (d.item >= 0) {
+        cost_item<4>(args.items[d.item], st, reinterpret_cast<float*>(smem + 4 * kHeadStage + kHeadImg));
+        AVAE_STAMP(4)
+        AVAE_STAMP_FLUSH()
+        return;
+    }
+    unsigned warmed = 0;
+    small_latb_tile<CT, ACT>(d, [&]() { warmed = desc_warm(warm_lines, warm_n, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6)); }, smem, AVAE_SV);
+    asm volatile("" :: "s"(warmed));
+    AVAE_STAMP(4)
+    AVAE_STAMP_FLUSH()
+}
+// fwd_head + fwd_dec1: [mu | lv] from the accumulators -> mulv (fp32, slice 0) and -> an fp32 tile in LDS (the ring is free by then);
+// z = mu + exp(lv / 2) * eps by one thread per (row, four latent dims) with eps fetched ahead of the first tile -> Z (slice 0) and
+// -> the image, with its constant-1 column; tail = the decoder's first layer.
+// The tile itself is small_head_tile, on a resolved record (HeadRec); k_small_head works it out of its by-value item, k_head_rec (the
+// training plan) reads it from the plan's table.  behind_prologue() is called once, behind the prologue's tiles.
+template <typename CT, int ACT, typename F>
+__device__ __forceinline__ void small_head_tile(const HeadRec& d, F&& behind_prologue, unsigned char* smem, unsigned long long* sv) {
+    constexpr int RING = 4, ES = (int)sizeof(CT), TSL = ES == 2 ? 2 : 4, LDM = 68;
+    unsigned char* img = smem + RING * kHeadStage;
+    float* MV = reinterpret_cast<float*>(smem);                // [32][LDM] fp32, over the ring (after the loop's last barrier)
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave >> 1, wc = wave & 1, fr = lane & 15, fq = lane >> 4;
-    const int tm = t / w.tiles_n, ts = t - tm * w.tiles_n;
-    const int m0 = tm * 32;
-    const int nk = (w.K * ES) / kTileBytesK, nz = w.nz;
+    const int ts = d.tk >> 8;
+    const int nk = d.nk, nz = d.nz;
     typedef const __attribute__((address_space(1))) void* gp_t;
     typedef __attribute__((address_space(3))) void* lp_t;
     reinterpret_cast<f32x4*>(img)[tid] = f32x4{0.f, 0.f, 0.f, 0.f};
     reinterpret_cast<f32x4*>(img)[tid + kThreads] = f32x4{0.f, 0.f, 0.f, 0.f};
     // ---- fetched ahead of the first tile: eps of this thread's (row, four dims), the tail's weight fragments
     const int zrow = tid >> 3, zg = tid & 7;
-    const f32x4 ev = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(w.aux0) + (size_t)min(m0 + zrow, w.M - 1) * w.ldx + min(4 * zg, w.ldx - 4));
-    const int t_i = wave & 1, t_c0 = (2 * ts + (wave >> 1)) * 32, t_sl = 2 * w.tail_kt;
+    const f32x4 ev = *reinterpret_cast<const f32x4*>(as_global(d.aux) + (size_t)min(zrow, d.mrem - 1) * d.ldx + min(4 * zg, d.ldx - 4));
+    const int t_i = wave & 1, t_c0 = (2 * ts + (wave >> 1)) * 32, t_sl = 2 * (int)(d.tk & 0xFF);
     u32x4 tb[TSL][2];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-        const unsigned char* pw = reinterpret_cast<const unsigned char*>(w.tail_w) + (size_t)min(t_c0 + 16 * j + fr, w.tail_n - 1) * w.tail_ldw * ES + fq * 16;
+        const unsigned char* pw = as_global(d.tail_w) + (size_t)min(t_c0 + 16 * j + fr, d.tail_n - 1) * d.tail_ldw * ES + fq * 16;
 #pragma unroll
         for (int sl = 0; sl < TSL; ++sl) if (TSL == 2 || sl < t_sl) tb[sl][j] = *reinterpret_cast<const u32x4*>(pw + 64 * sl);
     }
     const int prow = wave * 8 + (lane >> 3), lc = ((lane & 7) ^ ((prow >> 1) & 7)) * 16;
-    const unsigned char* srcA = reinterpret_cast<const unsigned char*>(w.A) + (size_t)(m0 + prow) * w.lda * ES + lc;
-    const unsigned char* srcB = reinterpret_cast<const unsigned char*>(w.B) + (size_t)prow * w.ldb * ES + lc;
-    const size_t b32 = (size_t)32 * w.ldb * ES;
+    const unsigned char* srcA = d.a + (size_t)prow * d.lda * ES + lc;
+    const unsigned char* srcB = d.b + (size_t)prow * d.ldb * ES + lc;
+    const size_t b32 = (size_t)32 * d.ldb * ES;
 #define AVAE_H_DMA(kt, buf)                                                                                             \
     { __builtin_amdgcn_global_load_lds((gp_t)(srcA + (size_t)(kt) * kTileBytesK), (lp_t)(smem + (buf) * kHeadStage + wave * 1024), 16, 0, 0);       \
       __builtin_amdgcn_global_load_lds((gp_t)(srcB + (size_t)(kt) * kTileBytesK), (lp_t)(smem + (buf) * kHeadStage + (4 + wave) * 1024), 16, 0, 0); \
@@ -1931,6 +2040,7 @@ __global__ void __launch_bounds__(kThreads) k_small_head(const LaunchArgs args, 
     AVAE_STAMP(1)
     const int npro = nk < RING - 1 ? nk : RING - 1;
     for (int p = 0; p < npro; ++p) AVAE_H_DMA(p, p)
+    behind_prologue();
     const int sw0 = (fq ^ (fr >> 1)) * 16;
     const int aoff = (wr * 16 + fr) * kTileBytesK, boff = (32 + wc * 32 + fr) * kTileBytesK;
     f32x4 acc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
@@ -1958,9 +2068,9 @@ __global__ void __launch_bounds__(kThreads) k_small_head(const LaunchArgs args, 
     AVAE_STAMP(3)
     // ---- [mu | lv]: into MV (every slice) and into mulv (slice 0), columns [0, nz) = mu, [nz, 2 nz) = log sigma^2 (vae_assoc.py:217-221)
     {
-        const int orow = m0 + wr * 16 + fr, lrow = wr * 16 + fr;
-        float* mulv = reinterpret_cast<float*>(w.out0) + (size_t)orow * w.ld0;
-        const bool store = ts == 0 && orow < w.M;
+        const int lrow = wr * 16 + fr;
+        float* mulv = as_global(reinterpret_cast<float*>(d.out0)) + (size_t)lrow * d.ld0;
+        const bool store = ts == 0 && lrow < d.mrem;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int c0 = wc * 32 + j * 16 + 4 * fq;
@@ -1975,15 +2085,15 @@ __global__ void __launch_bounds__(kThreads) k_small_head(const LaunchArgs args, 
     AVAE_STAMP(5)
     // ---- z = mu + sqrt(exp(lv)) * eps (:102-103): thread (row, four dims) -> Z (slice 0) and the image; [z | 1] is the tail's operand
     {
-        CT* Z = reinterpret_cast<CT*>(w.out1) + (size_t)(m0 + zrow) * w.ld1;
-        const bool store = ts == 0 && m0 + zrow < w.M;
+        CT* Z = as_global(reinterpret_cast<CT*>(d.out1)) + (size_t)zrow * d.ld1;
+        const bool store = ts == 0 && zrow < d.mrem;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const int d = 4 * zg + e;
-            if (d < nz) {
-                const float z = __builtin_fmaf(fexp(0.5f * MV[zrow * LDM + nz + d]), ev[e], MV[zrow * LDM + d]);
-                img_put<CT>(img, zrow, d, z);
-                if (store) Z[d] = to_ct<CT>(z);
+            const int dim = 4 * zg + e;
+            if (dim < nz) {
+                const float z = __builtin_fmaf(fexp(0.5f * MV[zrow * LDM + nz + dim]), ev[e], MV[zrow * LDM + dim]);
+                img_put<CT>(img, zrow, dim, z);
+                if (store) Z[dim] = to_ct<CT>(z);
             }
         }
         if (tid < 32) img_put<CT>(img, tid, nz, 1.0f);         // the constant-1 (bias) column of [z | 1]
@@ -2001,9 +2111,64 @@ __global__ void __launch_bounds__(kThreads) k_small_head(const LaunchArgs args, 
                 mma<CT>(tb[sl][0], ta, tacc[0][0]);
                 mma<CT>(tb[sl][1], ta, tacc[0][1]);
             }
-        regep_store<CT, 1, 2>(tacc, reinterpret_cast<CT*>(w.tail_out), w.tail_ldo, w.M, w.tail_n, m0 + arow, t_c0, lane,
+        regep_store<CT, 1, 2>(tacc, as_global(reinterpret_cast<CT*>(d.tail_out)), d.tail_ldo, d.mrem, d.tail_n, arow, t_c0, lane,
             [&](int, int, int, float v) { return act_fwd_t<ACT>(v); });
     }
+}
+
+template <typename CT, int ACT>
+__global__ void __launch_bounds__(kThreads) k_small_head(const LaunchArgs args, unsigned long long* stamps, int launch_id) {
+    constexpr int ES = (int)sizeof(CT);
+    unsigned char* smem = avae_dyn_smem;
+#ifdef AVAE_STAMPS
+    unsigned long long sv[kStampWords] = {0, 0, 0, 0, 0, 0, 0, 0};
+#endif
+    AVAE_STAMP(0)
+    const int part = blockIdx.x & 7, idx = blockIdx.x >> 3;
+    const WorkItem w = args.items[blockIdx.y];
+    asm volatile("" :: "s"(w.A), "s"(w.B), "s"(w.out0), "s"(w.out1), "s"(w.aux0), "s"(w.lda), "s"(w.ldb), "s"(w.K), "s"(w.ld0), "s"(w.tail_w), "s"(w.tail_out));
+    int t;
+    {
+        const int nt = w.tiles_m * w.tiles_n;
+        const int q = nt >> 3, r = nt & 7;
+        if (idx >= q + (part < r ? 1 : 0)) return;
+        t = (part < r ? part * (q + 1) : r * (q + 1) + (part - r) * q) + idx;
+    }
+    const int tm = t / w.tiles_n, ts = t - tm * w.tiles_n;
+    const int m0 = tm * 32;
+    HeadRec d;
+    d.a = reinterpret_cast<const unsigned char*>(w.A) + (size_t)m0 * w.lda * ES;
+    d.b = reinterpret_cast<const unsigned char*>(w.B);
+    d.out0 = reinterpret_cast<float*>(w.out0) + (size_t)m0 * w.ld0;
+    d.out1 = reinterpret_cast<CT*>(w.out1) + (size_t)m0 * w.ld1;
+    d.aux = reinterpret_cast<const float*>(w.aux0) + (size_t)m0 * w.ldx;
+    d.tail_w = reinterpret_cast<const unsigned char*>(w.tail_w);
+    d.tail_out = reinterpret_cast<CT*>(w.tail_out) + (size_t)m0 * w.tail_ldo;
+    d.lda = w.lda; d.ldb = w.ldb; d.ld0 = w.ld0; d.ld1 = w.ld1; d.ldx = w.ldx;
+    d.tail_ldw = w.tail_ldw; d.tail_ldo = w.tail_ldo;
+    d.nk = (w.K * ES) / kTileBytesK; d.nz = w.nz;
+    d.mrem = w.M - m0; d.tail_n = w.tail_n;
+    d.tk = HeadRec::pack(w.tail_kt, ts);
+    small_head_tile<CT, ACT>(d, []() {}, smem, AVAE_SV);
+    AVAE_STAMP(4)
+    AVAE_STAMP_FLUSH()
+}
+
+// The training plan's instance (see k_loss_rec); every record of this launch is a GEMM tile.
+template <typename CT, int ACT>
+__global__ void __launch_bounds__(kThreads) k_head_rec(const HeadRec* __restrict__ tab, unsigned long long* stamps, int launch_id,
+                                                       const void* warm_lines, int warm_n) {
+    unsigned char* smem = avae_dyn_smem;
+#ifdef AVAE_STAMPS
+    unsigned long long sv[kStampWords] = {0, 0, 0, 0, 0, 0, 0, 0};
+#endif
+    AVAE_STAMP(0)
+    const HeadRec d = tab[blockIdx.x];
+    asm volatile("" :: "s"(d.a), "s"(d.b), "s"(d.out0), "s"(d.out1), "s"(d.aux), "s"(d.tail_w), "s"(d.tail_out), "s"(d.lda), "s"(d.ldb), "s"(d.ld0),
+                 "s"(d.ld1), "s"(d.ldx), "s"(d.tail_ldw), "s"(d.tail_ldo), "s"(d.nk), "s"(d.nz), "s"(d.mrem), "s"(d.tail_n), "s"(d.tk));      // one burst
+    unsigned warmed = 0;
+    small_head_tile<CT, ACT>(d, [&]() { warmed = desc_warm(warm_lines, warm_n, __builtin_amdgcn_readfirstlane(threadIdx.x >> 6)); }, smem, AVAE_SV);
+    asm volatile("" :: "s"(warmed));
     AVAE_STAMP(4)
     AVAE_STAMP_FLUSH()
 }
@@ -2058,6 +2223,35 @@ void launch_small_latb(int compute_dtype, int act, const LaunchArgs& args, int g
 #undef K_LATB_B
 #undef K_LATB_F
 }
+#define AVAE_ACT_SWITCH(act, K, ...)                                                         \
+    switch (act) {                                                                           \
+        case AVAE_ACT_RELU: AVAE_LAUNCH((K(AVAE_ACT_RELU)), __VA_ARGS__); break;             \
+        case AVAE_ACT_SOFTPLUS: AVAE_LAUNCH((K(AVAE_ACT_SOFTPLUS)), __VA_ARGS__); break;     \
+        case AVAE_ACT_SIGMOID: AVAE_LAUNCH((K(AVAE_ACT_SIGMOID)), __VA_ARGS__); break;       \
+        case AVAE_ACT_TANH: AVAE_LAUNCH((K(AVAE_ACT_TANH)), __VA_ARGS__); break;             \
+        default: AVAE_LAUNCH((K(AVAE_ACT_IDENTITY)), __VA_ARGS__); break;                    \
+    }
+void launch_head_rec(int compute_dtype, int act, const HeadRec* tab, int n_recs, int lds_bytes, DescWarm warm, hipStream_t s,
+                     unsigned long long* stamps, int launch_id) {
+    const dim3 grid(n_recs), block(kThreads);
+#define K_HEAD_B(A) k_head_rec<__bf16, A>
+#define K_HEAD_F(A) k_head_rec<float, A>
+    if (compute_dtype == AVAE_BF16) { AVAE_ACT_SWITCH(act, K_HEAD_B, grid, block, lds_bytes, s, tab, stamps, launch_id, warm.lines, warm.n) }
+    else { AVAE_ACT_SWITCH(act, K_HEAD_F, grid, block, lds_bytes, s, tab, stamps, launch_id, warm.lines, warm.n) }
+#undef K_HEAD_B
+#undef K_HEAD_F
+}
+void launch_latb_rec(int compute_dtype, int act, const HeadRec* tab, int n_recs, int lds_bytes, DescWarm warm, DevState* st, const LaunchArgs& args,
+                     hipStream_t s, unsigned long long* stamps, int launch_id) {
+    const dim3 grid(n_recs), block(kThreads);
+#define K_LATB_B(A) k_latb_rec<__bf16, A>
+#define K_LATB_F(A) k_latb_rec<float, A>
+    if (compute_dtype == AVAE_BF16) { AVAE_ACT_SWITCH(act, K_LATB_B, grid, block, lds_bytes, s, tab, stamps, launch_id, warm.lines, warm.n, st, args) }
+    else { AVAE_ACT_SWITCH(act, K_LATB_F, grid, block, lds_bytes, s, tab, stamps, launch_id, warm.lines, warm.n, st, args) }
+#undef K_LATB_B
+#undef K_LATB_F
+}
+#undef AVAE_ACT_SWITCH
 
 // ---- the small nets' weight-gradient launch on the lean frame, with the optimiser in its epilogue (tile configuration 12):
 // dW[m][n] = sum_k X[k][m] * dA[k][n], 64x64 tiles, K-major operand images and fragment reads exactly as k_grouped's TN instance
@@ -2068,11 +2262,6 @@ void launch_small_latb(int compute_dtype, int act, const LaunchArgs& args, int g
 // The tile itself is small_tn_tile, on a resolved descriptor (avae_device.h: TnDesc): k_small_tn works the descriptor out of its
 // by-value item, k_small_tn_desc (the training plan) reads it from the plan's table.  behind_prologue() is called once, behind the
 // prologue's tiles, and returns the step's lr_t.
-#ifdef AVAE_STAMPS
-#define AVAE_SV sv
-#else
-#define AVAE_SV nullptr
-#endif
 template <typename CT, bool ADAM, typename F>
 __device__ __forceinline__ void small_tn_tile(const TnDesc& d, const TnDescArgs& ca, F&& behind_prologue, unsigned char* smem, unsigned long long* sv) {
     constexpr int BM = 64, RING = 4, ES = (int)sizeof(CT), EPR = kTileBytesK / ES, NCH = 4;
