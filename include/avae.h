@@ -119,7 +119,10 @@ const char* avae_last_error(const avae_handle* h);
 int avae_param_count(const avae_handle* h, size_t* n);
 int avae_get_params(avae_handle* h, float* host_dst);         /* flat order above, host memory */
 int avae_set_params(avae_handle* h, const float* host_src);
-int avae_get_grads(avae_handle* h, float* host_dst);          /* gradient of the last step, flat order (parity tests) */
+/* Gradient of the last applied step, flat order (parity tests).  Inside a run (avae_train_steps) the small nets' fused step stores
+ * the gradient only on the last step of each replayed graph -- the earlier ones would be overwritten before the host could ask --
+ * so what this returns is unchanged: the last step's. */
+int avae_get_grads(avae_handle* h, float* host_dst);
 /* Adam slots + step counter: what tf.train.Saver checkpoints besides the weights (vae_assoc.py:70,427-463). */
 int avae_get_opt_state(avae_handle* h, float* host_m, float* host_v, int64_t* step);
 int avae_set_opt_state(avae_handle* h, const float* host_m, const float* host_v, int64_t step);
@@ -819,7 +822,9 @@ int avae_comm_allreduce(avae_handle* h, int32_t bucket, void* stream);
  * "shadow_err" -> {max |W - theta|, max |W^T - theta|, layers checked, worst layer}: the compute-dtype weight shadows against the
  * parameters rounded once (must be 0, 0 after any call); "X<m>" staging set 0's encoder input of modality m [batch, n_input] (the
  * compute-dtype copy, widened), "T<m>" its exact loss target; "ema_master" the parameter average as it lies in memory (the internal
- * padded layout, padding included).  While avae_use_averaged is on, "shadow_err" compares against the average. */
+ * padded layout, padding included).  While avae_use_averaged is on, "shadow_err" compares against the average.
+ * "grad_keep" (the plain plan; "grad_keep_masked": the masked one) -> per captured step of the plan's training graphs, the 16-step
+ * graph's first, then the 4-step graph's, then the single step's (21 values): 1 = that step stores its gradient. */
 int avae_debug_fetch(avae_handle* h, const char* name, float* host_dst, size_t max_floats, size_t* n_floats);
 
 #ifdef __cplusplus

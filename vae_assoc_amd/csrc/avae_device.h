@@ -715,7 +715,7 @@ void launch_small_loss(int compute_dtype, const LaunchArgs& args, int grid_x, in
 void launch_small(int compute_dtype, const LaunchArgs& args, int grid_x, int grid_y, int lds_bytes, hipStream_t s, unsigned long long* stamps, int launch_id);
 void launch_small_desc(int compute_dtype, bool dgrad, int act, const SmallDesc* tab, int n_tiles, int lds_bytes, DescWarm warm, hipStream_t s,
                        unsigned long long* stamps, int launch_id);
-void launch_small_tn_desc(int compute_dtype, const TnDesc* tab, int n_tiles, DescWarm warm, hipStream_t s, unsigned long long* stamps, int launch_id);
+void launch_small_tn_desc(int compute_dtype, const TnDesc* tab, int n_tiles, bool grad, DescWarm warm, hipStream_t s, unsigned long long* stamps, int launch_id);
 // the output + loss and the two head launches of the training plan on records; `args` rides along for the latent / cost item alone
 void launch_loss_rec(int compute_dtype, const LossRec* tab, int n_recs, int lds_bytes, DescWarm warm, const LaunchArgs& args, hipStream_t s,
                      unsigned long long* stamps, int launch_id);

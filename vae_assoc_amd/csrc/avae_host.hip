@@ -182,6 +182,7 @@ struct StepGraph {
     hipGraphExec_t exec = nullptr;
     hipGraph_t graph = nullptr;
     hipGraphNode_t prep = nullptr;
+    std::vector<unsigned char> grad_keep;   // a training graph: per captured step, 1 = the step stores its gradient (step_body's return)
     void release() {
         if (exec) (void)hipGraphExecDestroy(exec);
         if (graph) (void)hipGraphDestroy(graph);
@@ -353,6 +354,7 @@ struct avae_handle {
     bool timing = false;
     bool debug_sync = false;
     bool plan_dump = false;                 // AVAE_PLAN_DUMP=1: serve_plan prints the plan it builds (nothing else changes)
+    bool keep_grads = false;                // AVAE_KEEP_GRADS=1: every fused wgrad+adam launch stores its gradient (step_body; A/B and the tests' twin)
     std::vector<std::string> tnames;
     std::vector<TimingRec> trecs;
 
@@ -2359,7 +2361,9 @@ void dump_launch(const Launch& L) {
                      L.ca.seg[i].g.OH, L.ca.seg[i].g.k, L.ca.seg[i].lddp, L.ca.seg[i].lda, (const void*)L.ca.seg[i].g0, L.ca.seg[i].tiles_r, L.ca.seg[i].tiles_c);
 }
 
-void run_launch(avae_handle* h, const Launch& L, hipStream_t s, unsigned long long* stamps, int stamp, DescWarm warm = DescWarm{nullptr, 0}) {
+// keep_grad = false (the descriptor wgrad+adam launch only): the launch does not store its gradient
+void run_launch(avae_handle* h, const Launch& L, hipStream_t s, unsigned long long* stamps, int stamp, DescWarm warm = DescWarm{nullptr, 0},
+                bool keep_grad = true) {
     Timed t(h, s, L.name);
     if (L.type == 1) launch_gather(h->cfg.compute_dtype, L.ga, L.blocks, s);
     else if (L.type == 2) launch_col2im(h->cfg.compute_dtype, L.ca, L.blocks, s);
@@ -2379,7 +2383,7 @@ void run_launch(avae_handle* h, const Launch& L, hipStream_t s, unsigned long lo
     else if (L.cfg == 9) launch_small_loss(h->cfg.compute_dtype, L.args, L.grid_x, L.grid_y, L.lds, s, stamps, stamp);
     else if (L.cfg == 7 && L.desc_n) launch_small_desc(h->cfg.compute_dtype, L.args.items[0].kind == K_DGRAD_HIDDEN, L.args.items[0].act, desc_of<SmallDesc>(h, L), L.desc_n, L.lds, warm, s, stamps, stamp);
     else if (L.cfg == 7) launch_small(h->cfg.compute_dtype, L.args, L.grid_x, L.grid_y, L.lds, s, stamps, stamp);
-    else if (L.tn && L.cfg == 12 && L.desc_n) launch_small_tn_desc(h->cfg.compute_dtype, desc_of<TnDesc>(h, L), L.desc_n, warm, s, stamps, stamp);
+    else if (L.tn && L.cfg == 12 && L.desc_n) launch_small_tn_desc(h->cfg.compute_dtype, desc_of<TnDesc>(h, L), L.desc_n, keep_grad, warm, s, stamps, stamp);
     else if (L.tn && L.cfg == 12) launch_small_tn(h->cfg.compute_dtype, L.targs, L.grid_x, L.grid_y, s, stamps, stamp);
     else if (L.tn) launch_grouped_tn(h->cfg.compute_dtype, L.cfg, L.targs, L.grid_x, L.grid_y, L.lds, h->state(), s, stamps, stamp);
     else launch_grouped(h->cfg.compute_dtype, L.cfg, L.args, L.grid_x, L.grid_y, L.lds, h->state(), s, stamps, stamp);
@@ -2402,8 +2406,9 @@ bool has_hyper_item(const Launch& L) {
 // launches are copies that point at the step's schedule entry (every other caller runs the tables as they are: multipliers 1).
 // after / after_set: the launch that runs behind ls[hi - 1] and its staging set -- the last launch warms its descriptors (warm_for).
 // records2 = false (a masked step): the launches on two-line records run on their by-value arguments.
+// keep_grad: run_launch's.
 void run_set(avae_handle* h, const std::vector<Launch>& ls, size_t lo, size_t hi, int j, hipStream_t s, int stamp_base = -1, bool train = false,
-             const Launch* after = nullptr, int after_set = 0, bool records2 = true) {
+             const Launch* after = nullptr, int after_set = 0, bool records2 = true, bool keep_grad = true) {
     unsigned long long* stamps = nullptr;
 #ifdef AVAE_STAMPS
     if (stamp_base >= 0) stamps = h->at<unsigned long long>(h->off_stamps);
@@ -2419,10 +2424,10 @@ void run_set(avae_handle* h, const std::vector<Launch>& ls, size_t lo, size_t hi
         const bool last = i + 1 >= hi || i + 1 >= ls.size();
         const DescWarm warm = last ? warm_for(h, after, after_set) : warm_for(h, &ls[i + 1], j);
         const bool strip = !records2 && ls[i].desc_n && two_line_records(ls[i]);
-        if (j == 0 && !(hyper && has_hyper_item(ls[i])) && !strip) { run_launch(h, ls[i], s, stamps, k, warm); continue; }
+        if (j == 0 && !(hyper && has_hyper_item(ls[i])) && !strip) { run_launch(h, ls[i], s, stamps, k, warm, keep_grad); continue; }
         Launch L = relocated(h, ls[i], j, hyper);
         if (strip) L.desc_n = 0;
-        run_launch(h, L, s, stamps, k, warm);
+        run_launch(h, L, s, stamps, k, warm, keep_grad);
     }
 }
 
@@ -2609,8 +2614,11 @@ void fill_ones(avae_handle* h, const Act& a, hipStream_t s) {
 // One step on staging set j (forward launches `fwd`: a plan's): forward, backward, then the weight gradients with Adam in their
 // epilogue, or followed by k_adam; with clipping on always weight gradients -> k_grad_sumsq -> k_adam, with averaging on always
 // weight gradients -> k_adam (the fused epilogue knows neither).
-// more: step j + 1 of the same graph follows (its first launch's descriptors are warmed by this step's last launch).
-void step_body(avae_handle* h, const std::vector<Launch>& fwd, hipStream_t s, int j, int stamp_base = -1, bool more = false) {
+// more: step j + 1 of the same graph follows (its first launch's descriptors are warmed by this step's last launch).  That step
+// overwrites this one's gradient before any host code runs, and in the fused plan nothing on the device reads the gradient, so the
+// descriptor wgrad+adam launches of such a step do not store it (k_small_tn_nograd); the last step of every graph and every eager
+// step do, and AVAE_KEEP_GRADS=1 makes every step.  Returns whether this step's gradient is in the gradient buffer afterwards.
+bool step_body(avae_handle* h, const std::vector<Launch>& fwd, hipStream_t s, int j, int stamp_base = -1, bool more = false) {
     auto sb = [&](size_t k) { return stamp_base < 0 ? -1 : stamp_base + (int)k; };
     auto first_of = [](const std::vector<Launch>& ls) { return ls.empty() ? nullptr : &ls[0]; };
     const bool fused = !h->wgrad_adam.empty() && !h->clip_on && !h->ema_on;
@@ -2618,12 +2626,15 @@ void step_body(avae_handle* h, const std::vector<Launch>& fwd, hipStream_t s, in
     const bool plain = &fwd == &h->plain.fwd;      // (the masked twin's head and loss launches stay by-value; the backward launches are shared)
     run_set(h, h->bwd, 0, h->bwd.size(), j, s, sb(fwd.size()), true, fused ? first_of(h->wgrad_adam) : nullptr, j, plain);
     if (fused) {       // the optimiser rides in the weight-gradient launch
-        run_set(h, h->wgrad_adam, 0, h->wgrad_adam.size(), j, s, sb(fwd.size() + h->bwd.size()), true, more ? first_of(fwd) : nullptr, j + 1);
-        return;
+        bool keep = !more || h->keep_grads;
+        for (const Launch& L : h->wgrad_adam) keep = keep || !(L.tn && L.cfg == 12 && L.desc_n);     // a by-value launch always stores
+        run_set(h, h->wgrad_adam, 0, h->wgrad_adam.size(), j, s, sb(fwd.size() + h->bwd.size()), true, more ? first_of(fwd) : nullptr, j + 1, true, keep);
+        return keep;
     }
     run_set(h, h->wgrad, 0, h->wgrad.size(), j, s, sb(fwd.size() + h->bwd.size()), true);
     if (h->clip_on) run_grad_sumsq(h, s);
     run_adam(h, 0, s);
+    return true;
 }
 
 // The training graphs of plan p (what avae_set_grad_clip / avae_set_ema capture again when the step's tail changes; eval holds no optimiser).
@@ -2632,16 +2643,22 @@ void step_body(avae_handle* h, const std::vector<Launch>& fwd, hipStream_t s, in
 void capture_steps(avae_handle* h, StepPlan& p, const uint8_t* present) {
     std::vector<const float*> x0(h->M, h->at<float>(h->mods[0].X32));    // placeholders, patched per step
     try {
+        std::vector<unsigned char> keep;
         p.full = capture(h, [&](hipStream_t cs) {
             run_prep_batch(h, x0.data(), nullptr, nullptr, h->B, kTrainSalt, cs, present);
-            step_body(h, p.fwd, cs, 0, 0);
+            keep.push_back(step_body(h, p.fwd, cs, 0, 0));
         }, true);
+        p.full.grad_keep = keep;
         // avae_train_steps: kMultiSizes[gi] whole steps per replay (a replay boundary costs ~5 us of idle GPU on this stack), their
         // batches staged by ONE launch into as many staging sets; step j's launches read set j
-        for (int gi = 0; gi < 2; ++gi) p.multi[gi] = capture(h, [&](hipStream_t cs) {
-            run_prep_batch(h, x0.data(), nullptr, nullptr, h->B, kTrainSalt, cs, present, kMultiSizes[gi]);
-            for (int j = 0; j < kMultiSizes[gi]; ++j) step_body(h, p.fwd, cs, j, -1, j + 1 < kMultiSizes[gi]);
-        }, true);
+        for (int gi = 0; gi < 2; ++gi) {
+            keep.clear();
+            p.multi[gi] = capture(h, [&](hipStream_t cs) {
+                run_prep_batch(h, x0.data(), nullptr, nullptr, h->B, kTrainSalt, cs, present, kMultiSizes[gi]);
+                for (int j = 0; j < kMultiSizes[gi]; ++j) keep.push_back(step_body(h, p.fwd, cs, j, -1, j + 1 < kMultiSizes[gi]));
+            }, true);
+            p.multi[gi].grad_keep = keep;
+        }
     } catch (...) { p.full.release(); p.multi[0].release(); p.multi[1].release(); throw; }
 }
 
@@ -3645,6 +3662,7 @@ int avae_create(const avae_config* cfg, avae_handle** out) {
         if (const char* e = std::getenv("AVAE_DEBUG_SYNC")) h->debug_sync = e[0] == '1';
         if (h->debug_sync) h->cfg.use_graph = 0;
         if (const char* e = std::getenv("AVAE_PLAN_DUMP")) h->plan_dump = e[0] == '1';
+        if (const char* e = std::getenv("AVAE_KEEP_GRADS")) h->keep_grads = e[0] == '1';
         if (h->cfg.beta1 == 0.f && h->cfg.beta2 == 0.f && h->cfg.adam_eps == 0.f) { h->cfg.beta1 = 0.9f; h->cfg.beta2 = 0.999f; h->cfg.adam_eps = 1e-8f; }
         int ndev = 0;
         HIP_OK(hipGetDeviceCount(&ndev));
@@ -5080,6 +5098,18 @@ int avae_debug_fetch(avae_handle* h, const char* name, float* host_dst, size_t m
             }
             host_dst[0] = ew; host_dst[1] = et; host_dst[2] = (float)cnt; host_dst[3] = (float)worst;
             if (n_floats) *n_floats = 4;
+            return;
+        }
+        else if (n == "grad_keep" || n == "grad_keep_masked") {
+            // per captured step of the plan's training graphs, 16-step graph first, then the 4-step graph, then the single step:
+            // 1 = the step stores its gradient (recorded by capture_steps).  "grad_keep": the plain plan, "grad_keep_masked": the masked one.
+            const StepPlan& p = n == "grad_keep" ? h->plain : h->masked;
+            if (!p.full.exec || !p.multi[0].exec || !p.multi[1].exec) throw Err("debug_fetch: the plan has no captured training graphs");
+            for (const StepGraph* g : {&p.multi[0], &p.multi[1], &p.full}) {
+                if (cnt + g->grad_keep.size() > max_floats) throw Err("debug_fetch: destination too small");
+                for (unsigned char k : g->grad_keep) host_dst[cnt++] = (float)k;
+            }
+            if (n_floats) *n_floats = cnt;
             return;
         }
         else if (n == "ema_master") {       // the average as it lies in memory: P_int floats, master layout, padding included

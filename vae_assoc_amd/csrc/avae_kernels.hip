@@ -2261,8 +2261,9 @@ void launch_latb_rec(int compute_dtype, int act, const HeadRec* tab, int n_recs,
 // its boundary and the gradient's read-back disappear.  Launches with split-K or all-ones bias rows stay on the general kernel.
 // The tile itself is small_tn_tile, on a resolved descriptor (avae_device.h: TnDesc): k_small_tn works the descriptor out of its
 // by-value item, k_small_tn_desc (the training plan) reads it from the plan's table.  behind_prologue() is called once, behind the
-// prologue's tiles, and returns the step's lr_t.
-template <typename CT, bool ADAM, typename F>
+// prologue's tiles, and returns the step's lr_t.  GRAD = false (ADAM only; a step inside a replay of several, whose gradient the next
+// step overwrites before the host can ask for it): the epilogue issues no store to d.out, everything else is the same code.
+template <typename CT, bool ADAM, bool GRAD, typename F>
 __device__ __forceinline__ void small_tn_tile(const TnDesc& d, const TnDescArgs& ca, F&& behind_prologue, unsigned char* smem, unsigned long long* sv) {
     constexpr int BM = 64, RING = 4, ES = (int)sizeof(CT), EPR = kTileBytesK / ES, NCH = 4;
     constexpr int kStage = 2 * BM * kTileBytesK;               // A part (BM columns) then B part: 16 KiB, EPR k-rows
@@ -2391,7 +2392,7 @@ __device__ __forceinline__ void small_tn_tile(const TnDesc& d, const TnDescArgs&
         }
         const bool full = mrem >= BM && nrem >= BM;             // a tile inside the layer (most of them): whole 16-byte stores, no bounds
         auto store_group = [&](int k, float* gp, CT* wp) {
-            store4<float>(gp, g[k]);
+            if constexpr (GRAD) store4<float>(gp, g[k]);
             store4<float>(gp + ca.d_theta, th[k]); store4<float>(gp + ca.d_m, m[k]); store4<float>(gp + ca.d_v, v[k]);
             store4<CT>(wp, th[k]);
         };
@@ -2414,7 +2415,8 @@ __device__ __forceinline__ void small_tn_tile(const TnDesc& d, const TnDescArgs&
                     // a partial quad never touches the padding behind column N
 #pragma unroll
                     for (int e = 0; e < 3; ++e) if (e < nv) {
-                        gp[e] = g[k][e]; gp[ca.d_theta + e] = th[k][e]; gp[ca.d_m + e] = m[k][e]; gp[ca.d_v + e] = v[k][e]; wp[e] = to_ct<CT>(th[k][e]);
+                        if constexpr (GRAD) gp[e] = g[k][e];
+                        gp[ca.d_theta + e] = th[k][e]; gp[ca.d_m + e] = m[k][e]; gp[ca.d_v + e] = v[k][e]; wp[e] = to_ct<CT>(th[k][e]);
                     }
                     // Keeps this arm's last store from being merged with the 16-byte stores of the other arm: hipcc (ROCm 7.2) sank
                     // the two into one shared "fourth dword" store and left its value unset on the whole-quad lanes -- fp32
@@ -2479,7 +2481,7 @@ __global__ void __launch_bounds__(kThreads) k_small_tn(const TnLaunchArgs args, 
     d.lda = w.lda; d.ldb = w.ldb; d.ld0 = w.ld0; d.ldw = w.ldw; d.ldt = w.ldt;
     d.ext = TnDesc::pack((w.K * ES) / kTileBytesK, w.M - m0, w.N - n0);
     const TnDescArgs ca = {args.d_theta, args.d_m, args.d_v, args.beta1, args.beta2, args.eps, args.st};
-    small_tn_tile<CT, ADAM>(d, ca, [lr_t]() { return lr_t; }, smem, AVAE_SV);
+    small_tn_tile<CT, ADAM, true>(d, ca, [lr_t]() { return lr_t; }, smem, AVAE_SV);
     AVAE_STAMP(4)
     AVAE_STAMP_FLUSH()
 }
@@ -2489,9 +2491,12 @@ __global__ void __launch_bounds__(kThreads) k_small_tn(const TnLaunchArgs args, 
 // trips: the state's address, then the value) is fetched behind the prologue's tiles and first needed in the epilogue.  It and the
 // warm-up touch are SCALAR loads (constant address space: the K_COST item that published lr_t ran in an earlier launch), so they
 // count in lgkmcnt, not in the vmcnt the K loop's waits are written in.
-template <typename CT>
-__global__ void __launch_bounds__(kThreads) k_small_tn_desc(const TnDesc* __restrict__ tab, unsigned long long* stamps, int launch_id,
-                                                            const void* warm_lines, int warm_n) {
+// Two kernels on one body: k_small_tn_desc stores the gradient (small_tn_tile's GRAD), k_small_tn_nograd does not -- the steps of a
+// replay that another step of the same replay follows (avae_host.hip: step_body).  GRAD is a template parameter of the body and each
+// kernel is one instance of it: a run-time flag in the epilogue would put a branch and its wait between the update and the stores.
+template <typename CT, bool GRAD>
+__device__ __forceinline__ void small_tn_desc_body(const TnDesc* __restrict__ tab, unsigned long long* stamps, int launch_id,
+                                                   const void* warm_lines, int warm_n) {
     unsigned char* smem = avae_dyn_smem;
 #ifdef AVAE_STAMPS
     unsigned long long sv[kStampWords] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -2500,7 +2505,7 @@ __global__ void __launch_bounds__(kThreads) k_small_tn_desc(const TnDesc* __rest
     const TnDescArgs ca = *reinterpret_cast<const TnDescArgs*>(tab + (blockIdx.x & 7));
     const TnDesc d = tab[kTnDescHead + blockIdx.x];
     unsigned warmed = 0;
-    small_tn_tile<CT, true>(d, ca, [&]() {
+    small_tn_tile<CT, true, GRAD>(d, ca, [&]() {
         typedef const __attribute__((address_space(4))) float* cf_t;
         const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
         const float lr_t = *(cf_t)(unsigned long long)&ca.st->lr_t;
@@ -2511,11 +2516,27 @@ __global__ void __launch_bounds__(kThreads) k_small_tn_desc(const TnDesc* __rest
     AVAE_STAMP(4)
     AVAE_STAMP_FLUSH()
 }
-void launch_small_tn_desc(int compute_dtype, const TnDesc* tab, int n_tiles, DescWarm warm, hipStream_t s, unsigned long long* stamps, int launch_id) {
+template <typename CT>
+__global__ void __launch_bounds__(kThreads) k_small_tn_desc(const TnDesc* __restrict__ tab, unsigned long long* stamps, int launch_id,
+                                                            const void* warm_lines, int warm_n) {
+    small_tn_desc_body<CT, true>(tab, stamps, launch_id, warm_lines, warm_n);
+}
+template <typename CT>
+__global__ void __launch_bounds__(kThreads) k_small_tn_nograd(const TnDesc* __restrict__ tab, unsigned long long* stamps, int launch_id,
+                                                              const void* warm_lines, int warm_n) {
+    small_tn_desc_body<CT, false>(tab, stamps, launch_id, warm_lines, warm_n);
+}
+// grad = false: the launch leaves the gradient buffer as it is (the caller knows that nothing reads this step's gradient)
+void launch_small_tn_desc(int compute_dtype, const TnDesc* tab, int n_tiles, bool grad, DescWarm warm, hipStream_t s, unsigned long long* stamps, int launch_id) {
     const dim3 grid(n_tiles), block(kThreads);
     const int lds_bytes = 4 * 2 * 64 * kTileBytesK;
-    if (compute_dtype == AVAE_BF16) AVAE_LAUNCH((k_small_tn_desc<__bf16>), grid, block, lds_bytes, s, tab, stamps, launch_id, warm.lines, warm.n);
-    else AVAE_LAUNCH((k_small_tn_desc<float>), grid, block, lds_bytes, s, tab, stamps, launch_id, warm.lines, warm.n);
+    if (compute_dtype == AVAE_BF16) {
+        if (grad) AVAE_LAUNCH((k_small_tn_desc<__bf16>), grid, block, lds_bytes, s, tab, stamps, launch_id, warm.lines, warm.n);
+        else AVAE_LAUNCH((k_small_tn_nograd<__bf16>), grid, block, lds_bytes, s, tab, stamps, launch_id, warm.lines, warm.n);
+    } else {
+        if (grad) AVAE_LAUNCH((k_small_tn_desc<float>), grid, block, lds_bytes, s, tab, stamps, launch_id, warm.lines, warm.n);
+        else AVAE_LAUNCH((k_small_tn_nograd<float>), grid, block, lds_bytes, s, tab, stamps, launch_id, warm.lines, warm.n);
+    }
 }
 void launch_small_tn(int compute_dtype, const TnLaunchArgs& args, int grid_x, int grid_y, hipStream_t s, unsigned long long* stamps, int launch_id) {
     const dim3 grid(grid_x, grid_y), block(kThreads);
