@@ -799,6 +799,48 @@ int avae_embed_iterate(avae_handle* h,
 int avae_embed_plan(const avae_config* cfg, int32_t rows,
                     int32_t* row_tile, int32_t* n_splits, int32_t* tiles_per_split, size_t* scratch_bytes);
 
+/* ---- motion decoding: the joint modality's rows as joint trajectories.  A row of the joint modality holds
+ * P = D * Kb standardised parameters of the reference's function approximator, D joints x (Kb - 1 basis weights + 1 offset), row-major
+ * [D][Kb] (baxter_writer.py:53-82, baxter_vae_assoc_writer.py:109-111); after every generate the reference un-normalises them,
+ * evaluates the approximators over the phase points and clamps to the joint limits (baxter_vae_assoc_writer.py:145-150, 439-458,
+ * pyrbf_funcapprox.py:123-143), and its training data are least-squares fits of the same basis (pyrbf_funcapprox.py:104-121).  The
+ * device sees only matrices (vae_assoc_amd/motion.py builds them on the host).  Dense device fp32 everywhere but saturated_dev
+ * (int32); trajectories are [rows][T][D].
+ *   theta[r][d][k] = params[r][d*Kb + k] * scale[d*Kb + k] + shift[d*Kb + k]        (one fma; NULL scale / shift: 1 / 0)
+ *   q[r][t][d]     = sum_k phi[t][k] theta[r][d][k]  (+ sum_c anchor_gain[t][c] anchor_target[r][d][c])
+ * every sum an fp32 fma chain in index order from 0, then q is clamped to [limits[d][0], limits[d][1]] for each joint whose upper
+ * limit is above its lower one -- by comparison, so a NaN stays NaN.  A linear equality constraint of the reference
+ * (pyrbf_funcapprox.py:41-61) is theta -> A theta + B target: the caller passes phi already multiplied by A and anchor_gain =
+ * phi_raw B, the kernels know nothing of constraints.
+ * avae_motion_eval: traj_dev = q; saturated_dev[r][d] = the number of clamped points; with a reference, rmse_dev[r][d] =
+ *   sqrt(mean_t (q - q_ref)^2) and maxabs_dev[r][d] = max_t |q - q_ref| (NaN if any difference is).  The reference is ref_traj_dev as
+ *   it is, or ref_params_dev evaluated by the same code with the same scale, shift and limits and no anchor -- the bits eval gives for
+ *   those parameters.  Every output may be NULL, but not all; the error outputs need a reference; both references is an error.
+ * avae_motion_fit: theta[r][d][:] = pinv [Kb][T] times traj[r][:][d] (t ascending), params_out = (theta - shift) / scale.
+ * avae_motion_moments: each of a row's S samples [rows][S][P] is evaluated exactly as by avae_motion_eval, clamp included, and folded
+ *   in sample order into a per-element running mean and M2 by the sequential update of avae_impute (delta = x - mean;
+ *   mean += delta / (k + 1); M2 += delta * (x - mean), the last an fma); var = M2 / S (population variance); saturated_frac[r][d] =
+ *   clamped points over all samples / (S * T).  The [rows][S][T][D] values are never stored.  S = 1: var is 0 and the mean is
+ *   avae_motion_eval's trajectory, bit for bit.
+ * rows == 0 is a no-op.  Errors (message in avae_last_error, nothing launched): rows < 0, D outside [1, 16], Kb outside [1, 64], T
+ * outside [1, 1024], nc outside [0, 4], S < 1, a NULL required pointer (anchor_gain / anchor_target with nc > 0 included).
+ * No atomics, one fixed order of every sum, and a workgroup's work is a function of its own rows alone: a row's outputs are a pure
+ * function of its bits and the matrices -- the same alone or among other rows, on any stream, on repetition and whichever optional
+ * outputs are asked for; a non-finite parameter affects only its own (row, joint).  One launch each, no scratch, nothing of the
+ * handle is read or written: the calls change nothing a training step reads, work on any replica with no collective, and inside
+ * avae_use_averaged. */
+int avae_motion_eval(avae_handle* h, const float* params_dev, int32_t rows, int32_t D, int32_t Kb, int32_t T,
+                     const float* phi_dev, const float* scale_dev, const float* shift_dev, const float* limits_dev,
+                     const float* anchor_gain_dev, const float* anchor_target_dev, int32_t nc,
+                     const float* ref_traj_dev, const float* ref_params_dev,
+                     float* traj_dev, int32_t* saturated_dev, float* rmse_dev, float* maxabs_dev, void* stream);
+int avae_motion_fit(avae_handle* h, const float* traj_dev, int32_t rows, int32_t D, int32_t Kb, int32_t T,
+                    const float* pinv_dev, const float* scale_dev, const float* shift_dev, float* params_dev, void* stream);
+int avae_motion_moments(avae_handle* h, const float* samples_dev, int32_t rows, int32_t S, int32_t D, int32_t Kb, int32_t T,
+                        const float* phi_dev, const float* scale_dev, const float* shift_dev, const float* limits_dev,
+                        const float* anchor_gain_dev, const float* anchor_target_dev, int32_t nc,
+                        float* mean_dev, float* var_dev, float* saturated_frac_dev, void* stream);
+
 /* save_model / restore_model (vae_assoc.py:427-463): own flat file (config echo + params + Adam
  * slots + step; with parameter averaging on also its settings and the average, see avae_set_ema);
  * TF .ckpt files cannot be read offline. */

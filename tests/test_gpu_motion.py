@@ -1,0 +1,490 @@
+"""Motion decoding (avae_motion_eval / _fit / _moments, motion_eval / motion_fit / motion_moments / predict_motion / motion_error)
+on a real MI355X (include/avae.h) against tests/motion_reference.py.
+
+1. eval, fit and the errors against the float64 definition, within 4x the float32 restatement's own worst error over the same
+   inputs (|err| / (|ref| + 1) per quantity); ``saturated`` by sandwich; 2. moments; 3. bit reproducibility and independence;
+4. non-finite input; 5. edges and errors of the C ABI; 6. the model level; 7. no side effects on training.
+
+Rows (1, 3, 4, 5, 15, 16, 17, 300): the kernels' row tile is 4.  (D, Kb, T) in ((7, 21, 100), (1, 1, 1), (16, 64, 257), (3, 9, 2)),
+each with and without scale / shift, limits and anchors (n_c = 1, 2); theta ~ N(0, 1), limits at +-1.5 standard deviations, seeded.
+
+Measured 2026-10-19 (kernel's worst / the float32 restatement's worst, the bound being 4x the latter; trajectory, rmse, max_abs,
+fitted parameters): (7, 21, 100) 1.37e-6 / 1.31e-6, 6.3e-7 / 7.4e-7, 2.94e-6 / 2.94e-6, 1.14e-5 / 1.22e-5; (1, 1, 1) 3.0e-8 / 6.7e-8,
+1.2e-7 / 2.9e-7, 1.2e-7 / 2.9e-7, 6.7e-8 / 6.7e-8; (16, 64, 257) 3.13e-6 / 3.84e-6, 4.26e-6 / 4.23e-6, 8.76e-6 / 8.76e-6, 2.05e-5 /
+2.05e-5; (3, 9, 2) 3.9e-7 / 3.8e-7, 8.2e-7 / 8.8e-7, 1.53e-6 / 1.53e-6, 9.8e-8 / 9.8e-8; gaussian (7, 21, 100) 3.2e-7 / 3.6e-7, 2.0e-7 /
+3.3e-7, 4.4e-7 / 5.5e-7, 8.5e-2 / 8.3e-2.  Moments, S = 1, 2, 7, 64: mean 9.5e-7, 1.30e-6, 6.8e-7, 4.5e-7 at (7, 21, 100) and 3.72e-6,
+4.27e-6, 2.18e-6, 8.2e-7 at (16, 64, 257), the restatement's own the same; variance 0, 3.5e-7 / 3.7e-7, 2.7e-7 / 3.3e-7, 4.3e-7 / 4.3e-7
+and 0, 6.0e-7 / 6.1e-7, 6.9e-7 / 6.9e-7, 4.6e-7 / 5.1e-7 of max var."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import motion_reference as R
+from conftest import make_arch, shadow_err, synth_batch
+
+pytestmark = pytest.mark.gpu
+
+B = 16
+WIDTHS = (784, 147)
+NZ = 20
+
+
+@pytest.fixture(scope="module")
+def V():
+    import __graft_entry__ as g
+    g.build()
+    from vae_assoc_amd import vae_assoc
+    assert torch.cuda.is_available()
+    return vae_assoc
+
+
+_MODELS = {}
+
+
+def _model(V, fresh=False, **kw):
+    """one small fp32 relu model, shared by the tests that only need a handle"""
+    if fresh or "m" not in _MODELS:
+        archs = [make_arch("image", 784, 96, 80, NZ), make_arch("joint", 147, 72, 40, NZ)]
+        m = V.AssocVariationalAutoEncoder(archs, binary=[True, False], transfer_fct="relu", weights=[50, 1], assoc_lambda=8.0,
+                                          learning_rate=1e-3, batch_size=B, compute_dtype="fp32", device=0, seed=3, **kw)
+        if fresh:
+            return m
+        _MODELS["m"] = m
+    return _MODELS["m"]
+
+
+def _bits(a):
+    a = a.cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def _same(a, b):
+    return all(np.array_equal(_bits(x), _bits(y)) for x, y in zip(a, b))
+
+
+def _dev(model, a):
+    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(model.device)
+
+
+def _p(t):
+    return None if t is None else t.data_ptr()
+
+
+def _stream(model):
+    return C.c_void_p(torch.cuda.current_stream(model.device).cuda_stream)
+
+
+def _eval(model, c, params=None, want=("traj", "sat"), ref_traj=None, ref_params=None, anchor=True):
+    """avae_motion_eval on a case of motion_reference.case -> dict of the NumPy outputs asked for (``want``)"""
+    params = c["params"] if params is None else params
+    N = params.shape[0]
+    D, Kb, T = c["D"], c["Kb"], c["T"]
+    out = {}
+    if "traj" in want:
+        out["traj"] = torch.full((N, T, D), -7.0, device=model.device)
+    if "sat" in want:
+        out["sat"] = torch.full((N, D), -7, dtype=torch.int32, device=model.device)
+    for k in ("rmse", "maxabs"):
+        if k in want:
+            out[k] = torch.full((N, D), -7.0, device=model.device)
+    nc = c["nc"] if anchor else 0
+    ts = [_dev(model, x) for x in (params, c["phi"], c["scale"], c["shift"], c["limits"], c["gain"] if nc else None,
+                                   c["target"] if nc else None, ref_traj, ref_params)]
+    rc = model._L.avae_motion_eval(model._h, _p(ts[0]), N, D, Kb, T, _p(ts[1]), _p(ts[2]), _p(ts[3]), _p(ts[4]), _p(ts[5]),
+                                   _p(ts[6]), nc, _p(ts[7]), _p(ts[8]), _p(out.get("traj")), _p(out.get("sat")),
+                                   _p(out.get("rmse")), _p(out.get("maxabs")), _stream(model))
+    assert rc == 0, model._L.avae_last_error(model._h)
+    torch.cuda.synchronize()
+    return {k: v.cpu().numpy() for k, v in out.items()}
+
+
+def _fit(model, c, traj):
+    N = traj.shape[0]
+    out = torch.full((N, c["D"] * c["Kb"]), -7.0, device=model.device)
+    ts = [_dev(model, x) for x in (traj, c["pinv"], c["scale"], c["shift"])]
+    rc = model._L.avae_motion_fit(model._h, _p(ts[0]), N, c["D"], c["Kb"], c["T"], _p(ts[1]), _p(ts[2]), _p(ts[3]), _p(out),
+                                  _stream(model))
+    assert rc == 0, model._L.avae_last_error(model._h)
+    return out.cpu().numpy()
+
+
+def _moments(model, c, samples=None, want=("mean", "var", "frac")):
+    samples = c["params"] if samples is None else samples
+    N, S = samples.shape[:2]
+    D, Kb, T = c["D"], c["Kb"], c["T"]
+    out = {"mean": torch.full((N, T, D), -7.0, device=model.device)}
+    if "var" in want:
+        out["var"] = torch.full((N, T, D), -7.0, device=model.device)
+    if "frac" in want:
+        out["frac"] = torch.full((N, D), -7.0, device=model.device)
+    ts = [_dev(model, x) for x in (samples, c["phi"], c["scale"], c["shift"], c["limits"], c["gain"], c["target"])]
+    rc = model._L.avae_motion_moments(model._h, _p(ts[0]), N, S, D, Kb, T, _p(ts[1]), _p(ts[2]), _p(ts[3]), _p(ts[4]), _p(ts[5]),
+                                      _p(ts[6]), c["nc"], _p(out["mean"]), _p(out.get("var")), _p(out.get("frac")), _stream(model))
+    assert rc == 0, model._L.avae_last_error(model._h)
+    return {k: v.cpu().numpy() for k, v in out.items()}
+
+
+def _ref_params(c, seed=99):
+    """a second parameter set close to the case's: the reference of the error outputs"""
+    rng = np.random.default_rng([seed, c["rows"], c["D"]])
+    return (c["params"] + 0.1 * rng.standard_normal(c["params"].shape)).astype(np.float32)
+
+
+# ------------------------------------------------------------------------------------------------ 1. eval, fit, errors
+@pytest.mark.parametrize("shape,kind", [(s, "sigmoid") for s in R.SHAPES] + [((7, 21, 100), "gaussian")])
+def test_eval_fit_and_errors_against_the_definition(V, shape, kind):
+    """The measured pairs are in the module docstring and in README.md."""
+    model = _model(V)
+    names = ("trajectory", "rmse", "max_abs", "fit")
+    own, got = dict.fromkeys(names, 0.0), dict.fromkeys(names, 0.0)
+    for rows in R.ROWS:
+        for variant in R.VARIANTS:
+            c = R.case(shape, rows, variant, kind=kind)
+            kw, D, Kb = R.eval_kw(c), c["D"], c["Kb"]
+            q64, _ = R.eval64(c["params"], c["phi"], D, **kw)
+            q32, _ = R.eval32(c["params"], c["phi"], D, **kw)
+            refp = _ref_params(c)
+            kw_ref = dict(kw, gain=None, target=None)
+            qr64, qr32 = R.eval64(refp, c["phi"], D, **kw_ref)[0], R.eval32(refp, c["phi"], D, **kw_ref)[0]
+            e64, e32 = R.errors64(q64, qr64), R.errors32(q32, qr32, Kb)
+            g = _eval(model, c, want=("traj", "sat", "rmse", "maxabs"), ref_params=refp)
+            traj32 = q64.astype(np.float32)
+            f64, f32, gf = R.fit64(traj32, c["pinv"], c["scale"], c["shift"]), R.fit32(traj32, c["pinv"], c["scale"], c["shift"]), \
+                _fit(model, c, traj32)
+            for name, r32, r64, gk in (("trajectory", q32, q64, g["traj"]), ("rmse", e32[0], e64[0], g["rmse"]),
+                                       ("max_abs", e32[1], e64[1], g["maxabs"]), ("fit", f32, f64, gf)):
+                own[name] = max(own[name], R.rel_err(r32, r64))
+                got[name] = max(got[name], R.rel_err(gk, r64))
+            # a reference trajectory, used as it is, against the definition on the same reference
+            g2 = _eval(model, c, want=("rmse", "maxabs"), ref_traj=qr64.astype(np.float32))
+            t64 = R.errors64(q64, qr64.astype(np.float32))
+            t32 = R.errors32(q32, qr64.astype(np.float32), Kb)
+            own["rmse"], got["rmse"] = max(own["rmse"], R.rel_err(t32[0], t64[0])), max(got["rmse"], R.rel_err(g2["rmse"], t64[0]))
+            own["max_abs"] = max(own["max_abs"], R.rel_err(t32[1], t64[1]))
+            got["max_abs"] = max(got["max_abs"], R.rel_err(g2["maxabs"], t64[1]))
+            # saturated: no exclusions
+            raw = R.unclamped(c["params"], c["phi"], D, c["scale"], c["shift"], c["gain"], c["target"])
+            lo, hi = R.sandwich(raw, c["limits"], 4.0 * float(np.abs(q32 - q64).max()), 1)
+            assert (lo <= g["sat"]).all() and (g["sat"] <= hi).all(), (rows, variant)
+            if c["limits"] is None:
+                assert not g["sat"].any()
+    for name in names:
+        print("%s %s %s: kernel %.3e, restatement %.3e (bound 4x)" % (shape, kind, name, got[name], own[name]))
+    for name in names:
+        assert got[name] <= 4.0 * own[name], name
+
+
+# ------------------------------------------------------------------------------------------------ 2. moments
+@pytest.mark.parametrize("S", [1, 2, 7, 64])
+@pytest.mark.parametrize("shape", [R.SHAPES[0], R.SHAPES[2]])
+def test_moments_against_the_definition(V, shape, S):
+    model = _model(V)
+    own, got = [0.0, 0.0], [0.0, 0.0]
+    for rows in R.ROWS:
+        for variant in ("plain", "all"):
+            c = R.case(shape, rows, variant, S=S)
+            kw, D = R.eval_kw(c), c["D"]
+            both = R.moments_both(c["params"], c["phi"], D, **kw)
+            (m64, v64, _), (m32, v32) = both["r64"], both["r32"]
+            lo, hi = both["counts"](4.0 * both["worst"])
+            g = _moments(model, c)
+            own = [max(own[0], R.rel_err(m32, m64)), max(own[1], R.var_err(v32, v64) if S > 1 else 0.0)]
+            got = [max(got[0], R.rel_err(g["mean"], m64)), max(got[1], R.var_err(g["var"], v64) if S > 1 else 0.0)]
+            n = g["frac"].astype(np.float64) * (S * c["T"])              # (the fraction is float32: the count to within 0.01)
+            assert (lo - 0.01 <= n).all() and (n <= hi + 0.01).all(), (rows, variant)
+            flat = dict(c, params=c["params"].reshape(rows * S, -1),
+                        target=None if c["target"] is None else np.repeat(c["target"], S, axis=0))
+            if S == 1:                                   # variance exactly 0, the mean bitwise eval's trajectory
+                e = _eval(model, flat, want=("traj",))
+                assert not g["var"].any() and np.array_equal(_bits(g["mean"]), _bits(e["traj"]))
+            elif rows * S <= 2100:                       # the moments of motion_eval applied to each sample
+                e = _eval(model, flat, want=("traj",))["traj"].reshape(rows, S, c["T"], D).astype(np.float64)
+                got = [max(got[0], R.rel_err(g["mean"], e.mean(1))), max(got[1], R.var_err(g["var"], e.var(1)))]
+    print("%s S=%d: mean kernel %.3e, restatement %.3e; var kernel %.3e, restatement %.3e (bound 4x)"
+          % (shape, S, got[0], own[0], got[1], own[1]))
+    assert got[0] <= 4.0 * own[0] and got[1] <= 4.0 * own[1]
+
+
+# ------------------------------------------------------------------------------------------------ 3. bits
+def test_bit_reproducibility_and_independence(V):
+    model = _model(V)
+    c = R.case((7, 21, 100), 300, "all")
+    refp = _ref_params(c)
+    every = ("traj", "sat", "rmse", "maxabs")
+    full = _eval(model, c, want=every, ref_params=refp)
+    again = _eval(model, c, want=every, ref_params=refp)
+    assert _same(full.values(), again.values())
+    with torch.cuda.stream(torch.cuda.Stream(model.device)):
+        other = _eval(model, c, want=every, ref_params=refp)
+    assert _same(full.values(), other.values())
+    for r in (5, 298):                                   # a row alone
+        one = dict(c, params=c["params"][r:r + 1], target=c["target"][r:r + 1])
+        alone = _eval(model, one, want=every, ref_params=refp[r:r + 1])
+        assert all(np.array_equal(_bits(alone[k][0]), _bits(full[k][r])) for k in every), r
+    for want in (("traj",), ("sat",), ("rmse",), ("maxabs",), ("sat", "maxabs")):
+        sub = _eval(model, c, want=want, ref_params=refp)
+        assert all(np.array_equal(_bits(sub[k]), _bits(full[k])) for k in want), want
+    # ref_params gives the bits of ref_traj when ref_traj is eval's own trajectory of those parameters (no anchor)
+    own = _eval(model, c, params=refp, want=("traj",), anchor=False)["traj"]
+    by_traj = _eval(model, c, want=("rmse", "maxabs"), ref_traj=own)
+    assert _same(by_traj.values(), [full["rmse"], full["maxabs"]])
+    # fit and moments
+    fit = _fit(model, c, full["traj"])
+    assert np.array_equal(_bits(fit), _bits(_fit(model, c, full["traj"])))
+    assert np.array_equal(_bits(fit[5]), _bits(_fit(model, c, full["traj"][5:6])[0]))
+    cs = R.case((7, 21, 100), 300, "all", S=7)
+    mo = _moments(model, cs)
+    with torch.cuda.stream(torch.cuda.Stream(model.device)):
+        mo2 = _moments(model, cs)
+    assert _same(mo.values(), mo2.values())
+    one = _moments(model, dict(cs, params=cs["params"][5:6], target=cs["target"][5:6]))
+    assert all(np.array_equal(_bits(one[k][0]), _bits(mo[k][5])) for k in mo)
+    only_mean = _moments(model, cs, want=())
+    assert np.array_equal(_bits(only_mean["mean"]), _bits(mo["mean"]))
+
+
+# ------------------------------------------------------------------------------------------------ 4. non-finite input
+def test_a_nan_parameter_stays_in_its_row_and_joint(V):
+    model = _model(V)
+    c = R.case((7, 21, 100), 17, "all")
+    refp = _ref_params(c)
+    every = ("traj", "sat", "rmse", "maxabs")
+    clean = _eval(model, c, want=every, ref_params=refp)
+    bad = c["params"].copy()
+    r, d, k = 6, 2, 4
+    bad[r, d * 21 + k] = np.nan
+    dirty = _eval(model, c, params=bad, want=every, ref_params=refp)
+    mask = np.ones((17, 7), bool)
+    mask[r, d] = False
+    for key in every:
+        a, b = clean[key], dirty[key]
+        if key == "traj":
+            a, b = a.transpose(0, 2, 1), b.transpose(0, 2, 1)
+        assert np.array_equal(_bits(a[mask]), _bits(b[mask])), key
+    assert np.isnan(dirty["traj"][r, c["phi"][:, k] != 0, d]).all() and (c["phi"][:, k] != 0).any()
+    assert np.isnan(dirty["rmse"][r, d]) and np.isnan(dirty["maxabs"][r, d]) and dirty["sat"][r, d] == 0
+    cs = R.case((7, 21, 100), 5, "all", S=7)
+    clean = _moments(model, cs)
+    bad = cs["params"].copy()
+    bad[3, 4, d * 21 + k] = np.nan
+    dirty = _moments(model, dict(cs, params=bad))
+    mask = np.ones((5, 7), bool)
+    mask[3, d] = False
+    for key in ("mean", "var"):
+        assert np.array_equal(_bits(clean[key].transpose(0, 2, 1)[mask]), _bits(dirty[key].transpose(0, 2, 1)[mask])), key
+    assert np.array_equal(_bits(clean["frac"][mask]), _bits(dirty["frac"][mask]))
+    assert not np.isfinite(dirty["mean"][3, :, d]).any()
+
+
+# ------------------------------------------------------------------------------------------------ 5. C ABI edges
+def test_c_abi_edges_and_errors(V):
+    model = _model(V)
+    L, h = model._L, model._h
+    c = R.case((7, 21, 100), 3, "all")
+    refp = _ref_params(c)
+    dev = {k: _dev(model, c[k]) for k in ("params", "phi", "scale", "shift", "limits", "gain", "target", "pinv")}
+    dev["refp"] = _dev(model, refp)
+    traj = torch.full((3, 100, 7), -7.0, device=model.device)
+    keep = torch.full((3, 147), -7.0, device=model.device)
+    s = _stream(model)
+
+    def ev(rows=3, D=7, Kb=21, T=100, nc=2, params="params", phi="phi", gain="gain", target="target", ref_traj=None, refp=None,
+           out=traj, sat=None, rmse=None, mx=None):
+        g = lambda k: None if k is None else (dev[k].data_ptr() if isinstance(k, str) else k.data_ptr())     # noqa: E731
+        return L.avae_motion_eval(h, g(params), rows, D, Kb, T, g(phi), g("scale"), g("shift"), g("limits"), g(gain), g(target), nc,
+                                  g(ref_traj), g(refp), g(out), g(sat), g(rmse), g(mx), s)
+
+    def mo(rows=3, S=1, D=7, Kb=21, T=100, nc=2, samples="params", phi="phi", mean=traj):
+        g = lambda k: None if k is None else (dev[k].data_ptr() if isinstance(k, str) else k.data_ptr())     # noqa: E731
+        return L.avae_motion_moments(h, g(samples), rows, S, D, Kb, T, g(phi), g("scale"), g("shift"), g("limits"), g("gain"),
+                                     g("target"), nc, g(mean), None, None, s)
+
+    def fi(rows=3, D=7, Kb=21, T=100, tr=traj, pinv="pinv", out=keep):
+        g = lambda k: None if k is None else (dev[k].data_ptr() if isinstance(k, str) else k.data_ptr())     # noqa: E731
+        return L.avae_motion_fit(h, g(tr), rows, D, Kb, T, g(pinv), g("scale"), g("shift"), g(out), s)
+
+    assert ev(rows=0) == 0 and mo(rows=0) == 0 and fi(rows=0) == 0
+    torch.cuda.synchronize()
+    assert (traj == -7.0).all() and (keep == -7.0).all()
+    some = torch.full((3, 7), -7.0, device=model.device)
+    bad = [(ev, dict(rows=-1), "rows"), (ev, dict(D=0), "D"), (ev, dict(D=17), "D"), (ev, dict(Kb=0), "Kb"), (ev, dict(Kb=65), "Kb"),
+           (ev, dict(T=0), "T"), (ev, dict(T=1025), "T"), (ev, dict(nc=-1), "nc"), (ev, dict(nc=5), "nc"),
+           (ev, dict(params=None), "params_dev"), (ev, dict(phi=None), "phi_dev"), (ev, dict(gain=None), "anchor_gain_dev"),
+           (ev, dict(target=None), "anchor_target_dev"), (ev, dict(out=None), "output"),
+           (ev, dict(ref_traj=traj, refp="refp", rmse=some), "both"), (ev, dict(rmse=some), "reference"),
+           (ev, dict(mx=some), "reference"),
+           (mo, dict(rows=-1), "rows"), (mo, dict(S=0), "S"), (mo, dict(S=-3), "S"), (mo, dict(D=17), "D"), (mo, dict(Kb=65), "Kb"),
+           (mo, dict(T=1025), "T"), (mo, dict(nc=5), "nc"), (mo, dict(samples=None), "samples_dev"), (mo, dict(phi=None), "phi_dev"),
+           (mo, dict(mean=None), "mean_dev"),
+           (fi, dict(rows=-1), "rows"), (fi, dict(D=0), "D"), (fi, dict(Kb=65), "Kb"), (fi, dict(T=0), "T"), (fi, dict(T=1025), "T"),
+           (fi, dict(tr=None), "traj_dev"), (fi, dict(pinv=None), "pinv_dev"), (fi, dict(out=None), "params_dev")]
+    for f, kw, needle in bad:
+        assert f(**kw) != 0, kw
+        assert needle in L.avae_last_error(h).decode(), (kw, L.avae_last_error(h))
+    torch.cuda.synchronize()
+    assert (traj == -7.0).all() and (keep == -7.0).all() and (some == -7.0).all()      # nothing was launched
+    assert ev() == 0 and fi() == 0                                                      # and the handle still works
+    torch.cuda.synchronize()
+    assert np.isfinite(traj.cpu().numpy()).all() and np.isfinite(keep.cpu().numpy()).all()
+
+
+# ------------------------------------------------------------------------------------------------ 6. the model level
+def _basis(V, seed=4):
+    from vae_assoc_amd.motion import MotionBasis
+    rng = np.random.default_rng(seed)
+    return MotionBasis(param_mean=0.3 * rng.standard_normal(147), param_std=rng.uniform(0.5, 1.5, 147),
+                       limits=np.c_[-np.ones(7), np.ones(7)])
+
+
+def _pattern(N):
+    return np.stack([(np.arange(N) % 3) != 1, (np.arange(N) % 3) != 0], 1)
+
+
+def test_python_surface_against_the_definition(V):
+    """motion_eval / motion_fit / motion_moments: NumPy in and out, device tensors in and out, against the float64 definition"""
+    model, b = _model(V), _basis(V)
+    rng = np.random.default_rng(8)
+    N, S = 21, 5
+    p = rng.standard_normal((N, 147)).astype(np.float32)
+    anchor = dict(phases=[0.0, 1.0], target=rng.standard_normal((N, 7, 2)).astype(np.float32))
+    phi, gain = b.eval_matrices(anchor["phases"])
+    sc, sh = b.scale_shift()
+    lim = b.limits.astype(np.float32)
+    q64, s64 = R.eval64(p, phi.astype(np.float32), 7, sc, sh, lim, gain.astype(np.float32), anchor["target"])
+    out = model.motion_eval(p, b, anchor=anchor, reference_params=p)
+    assert isinstance(out["trajectory"], np.ndarray) and out["saturated"].dtype == np.int32
+    assert R.rel_err(out["trajectory"], q64) < 1e-5 and np.abs(out["saturated"] - s64).max() <= 1
+    plain = model.motion_eval(p, b)
+    assert plain["rmse"] is None and plain["max_abs"] is None
+    assert np.array_equal(model.motion_eval(p, b, reference=plain["trajectory"])["rmse"], np.zeros((N, 7), np.float32))
+    assert np.array_equal(model.motion_eval(p, b, reference_params=p)["max_abs"], np.zeros((N, 7), np.float32))
+    t = model.motion_eval(torch.from_numpy(p).to(model.device), b, anchor=anchor)
+    assert torch.is_tensor(t["trajectory"]) and np.array_equal(_bits(t["trajectory"]), _bits(out["trajectory"]))
+    free = type(b)(param_mean=b.param_mean, param_std=b.param_std)            # no limits: the trajectories lie in the span
+    full = model.motion_eval(p, free)["trajectory"]
+    back = model.motion_fit(full, free)
+    assert back.shape == (N, 147) and R.rel_err(back, R.fit64(full, free.pinv(100).astype(np.float32), sc, sh)) < 1e-4
+    assert R.rel_err(model.motion_eval(back, free)["trajectory"], full) < 1e-4   # fit then evaluate reproduces the trajectory
+    assert model.motion_fit(np.zeros((2, 8, 7), np.float32), free).shape == (2, 147)
+    s = rng.standard_normal((N, S, 147)).astype(np.float32)
+    mo = model.motion_moments(s, b, anchor=anchor)
+    m64, v64, f64 = R.moments64(s, phi.astype(np.float32), 7, sc, sh, lim, gain.astype(np.float32), anchor["target"])
+    assert R.rel_err(mo["mean"], m64) < 1e-5 and R.var_err(mo["var"], v64) < 1e-5 and np.abs(mo["saturated_frac"] - f64).max() < 0.01
+    assert model.motion_eval(np.zeros((0, 147), np.float32), b)["trajectory"].shape == (0, 100, 7)
+    with pytest.raises(ValueError):
+        model.motion_eval(p[:, :146], b)
+    with pytest.raises(ValueError):
+        model.motion_moments(s, b, anchor=dict(phases=[0.0], target=anchor["target"]))
+
+
+def test_predict_motion_and_motion_error(V):
+    model, b = _model(V), _basis(V)
+    rng = np.random.default_rng(12)
+    N, S = 37, 5
+    X = synth_batch(rng, N, WIDTHS, [True, False])
+    present = _pattern(N)
+    anchor = dict(phases=[0.0], target=rng.standard_normal((N, 7, 1)).astype(np.float32))
+    for pres in (None, present):
+        imp = model.impute(X, pres)
+        want = model.motion_eval(imp["mean"][1], b, anchor=anchor)
+        got = model.predict_motion(X, b, present=pres, anchor=anchor)
+        assert got["var"] is None and np.array_equal(_bits(got["trajectory"]), _bits(want["trajectory"]))
+        assert np.array_equal(_bits(got["mu"]), _bits(imp["mu"])) and np.array_equal(_bits(got["logvar"]), _bits(imp["logvar"]))
+        assert np.allclose(got["saturated_frac"] * 100, want["saturated"])
+    # samples: impute's posterior, generate on the S latents, the float64 moments
+    eps = rng.standard_normal((N, S, NZ)).astype(np.float32)
+    imp = model.impute(X, present)
+    z = (imp["mu"][:, None, :] + np.exp(np.float32(0.5) * imp["logvar"])[:, None, :] * eps).astype(np.float32)
+    samples = model.generate(z.reshape(N * S, NZ))[1].reshape(N, S, 147)
+    phi, gain = b.eval_matrices(anchor["phases"])
+    sc, sh = b.scale_shift()
+    lim = b.limits.astype(np.float32)
+    args = (phi.astype(np.float32), 7, sc, sh, lim, gain.astype(np.float32), anchor["target"])
+    m64, v64, f64 = R.moments64(samples, *args)
+    got = model.predict_motion(X, b, present=present, n_samples=S, eps=eps, anchor=anchor)
+    tol = 2e-5                                           # the fp32 decode tolerance of the impute tests
+    em, ev = np.abs(got["trajectory"] - m64).max(), np.abs(got["var"] - v64).max()
+    print("predict_motion: mean err %.3e, var err %.3e" % (em, ev))
+    assert em <= tol * max(1.0, np.abs(m64).max()) and ev <= tol * max(1.0, v64.max())
+    raw = R.unclamped(samples, args[0], 7, sc, sh, args[5], anchor["target"][:, None])
+    lo, hi = R.sandwich(raw, lim, tol * max(1.0, np.abs(raw).max()), (1, 2))
+    n = got["saturated_frac"].astype(np.float64) * (S * 100)
+    assert (lo - 0.01 <= n).all() and (n <= hi + 0.01).all() and hi.sum() > 0
+    # independent of the chunk size
+    keys = ("mu", "logvar", "trajectory", "var", "saturated_frac")
+    default = model._motion_chunk
+    try:
+        for chunk in (S, 3 * S, 16 * S + 1):
+            model._motion_chunk = chunk
+            other = model.predict_motion(X, b, present=present, n_samples=S, eps=eps, anchor=anchor)
+            assert all(np.array_equal(_bits(other[k]), _bits(got[k])) for k in keys), chunk
+    finally:
+        model._motion_chunk = default
+    fresh = model.predict_motion(X, b, n_samples=3)      # a fresh draw
+    assert np.isfinite(fresh["trajectory"]).all() and (fresh["var"] >= 0).all()
+    dev_in = model.predict_motion([torch.from_numpy(x).to(model.device) for x in X], b, n_samples=S,
+                                  eps=torch.from_numpy(eps).to(model.device))
+    assert torch.is_tensor(dev_in["trajectory"]) and dev_in["trajectory"].shape == (N, 100, 7)
+    # the cross-modal error in joint units
+    for source in (0, 1):
+        pred = model.impute([X[m] if m == source else None for m in range(2)])["mean"][1]
+        want = model.motion_eval(pred, b, reference_params=X[1])
+        err = model.motion_error(X, b, source=source)
+        assert np.array_equal(_bits(err["rmse"]), _bits(want["rmse"])) and np.array_equal(_bits(err["max_abs"]), _bits(want["max_abs"]))
+        assert (err["rmse"] <= err["max_abs"]).all() and (err["rmse"] > 0).any()
+    with pytest.raises(ValueError):
+        model.predict_motion(X, b, modality=0)
+    with pytest.raises(ValueError):
+        model.motion_error(X, b, source=2)
+
+
+def test_motion_calls_inside_averaged(V):
+    model, b = _model(V, fresh=True, ema=0.9), _basis(V)
+    rng = np.random.default_rng(14)
+    X = synth_batch(rng, 2 * B, WIDTHS, [True, False])
+    for i in range(2):
+        model.partial_fit([x[i * B:(i + 1) * B] for x in X], rng.standard_normal((B, NZ)).astype(np.float32))
+    eps = rng.standard_normal((2 * B, 3, NZ)).astype(np.float32)
+    live = model.predict_motion(X, b)
+    with model.averaged():
+        avg = model.predict_motion(X, b)
+        want = model.motion_eval(model.impute(X)["mean"][1], b)
+        sampled = model.predict_motion(X, b, n_samples=3, eps=eps)
+        err = model.motion_error(X, b)
+    assert np.array_equal(_bits(avg["trajectory"]), _bits(want["trajectory"]))
+    assert not np.array_equal(avg["trajectory"], live["trajectory"])            # the averaged weights are other weights
+    assert np.isfinite(sampled["var"]).all() and np.isfinite(err["rmse"]).all()
+    assert np.array_equal(_bits(model.predict_motion(X, b)["trajectory"]), _bits(live["trajectory"]))
+
+
+# ------------------------------------------------------------------------------------------------ 7. no side effects
+def test_motion_calls_have_no_side_effects_on_training(V):
+    b = _basis(V)
+    rng = np.random.default_rng(21)
+    Xt = synth_batch(rng, 2 * B, WIDTHS, [True, False])
+    et = rng.standard_normal((2 * B, NZ)).astype(np.float32)
+    Xq = synth_batch(rng, 40, WIDTHS, [True, False])
+    state = lambda m: m.get_opt_state() + (m.get_params(), m.cost_history(1))      # noqa: E731
+    runs = []
+    for with_calls in (False, True):
+        model = _model(V, fresh=True)
+        model.partial_fit([x[:B] for x in Xt], et[:B])
+        before = state(model)
+        if with_calls:
+            tr = model.motion_eval(Xq[1], b, reference_params=Xq[1][::-1].copy())["trajectory"]
+            model.motion_fit(tr, b)
+            model.motion_moments(Xq[1].reshape(8, 5, 147), b)
+            model.predict_motion(Xq, b, n_samples=4, eps=rng.standard_normal((40, 4, NZ)).astype(np.float32))
+            model.predict_motion(Xq, b, present=_pattern(40))
+            model.motion_error(Xq, b)
+            model.synchronize()
+            for x, y in zip(before, state(model)):
+                assert np.array_equal(np.asarray(x), np.asarray(y))
+        cost = model.partial_fit([x[B:] for x in Xt], et[B:])
+        model.synchronize()
+        assert shadow_err(model)[:2] == (0.0, 0.0)
+        runs.append((np.float32(cost), model.get_grads()) + state(model))
+    for x, y in zip(*runs):
+        assert np.array_equal(np.asarray(x), np.asarray(y))

@@ -7,7 +7,8 @@ from . import dataset  # noqa: F401
 
 _LAZY = {"AssocVariationalAutoEncoder": "vae_assoc", "train": "vae_assoc", "xavier_init": "vae_assoc",
          "GradSync": "parallel", "dp_train_step": "parallel",
-         "linear_warmup": "_marshal", "cyclical": "_marshal", "exponential_decay": "_marshal"}
+         "linear_warmup": "_marshal", "cyclical": "_marshal", "exponential_decay": "_marshal",
+         "MotionBasis": "motion"}
 
 
 def __getattr__(name):

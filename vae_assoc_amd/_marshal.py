@@ -356,3 +356,14 @@ def dev_dense3(a, shape, device, name="eps"):
     if tuple(t.shape) != tuple(shape):
         raise ValueError("%s must be [%s], got %s" % (name, ", ".join("%d" % s for s in shape), tuple(t.shape)))
     return t.to(device=device, dtype=torch.float32).contiguous()
+
+
+def dev_block3(a, tail, device, name, rows=None):
+    """[rows, tail[0], tail[1]] block (None in ``tail`` = any size) -> (contiguous float32 tensor on ``device``, was_numpy)"""
+    was_np = not torch.is_tensor(a)
+    t = torch.as_tensor(np.asarray(a, dtype=np.float32) if was_np else a)
+    ok = t.dim() == 3 and all(w is None or t.shape[i + 1] == w for i, w in enumerate(tail))
+    if not ok or (rows is not None and t.shape[0] != rows):
+        want = ", ".join(["rows" if rows is None else "%d" % rows] + ["any" if w is None else "%d" % w for w in tail])
+        raise ValueError("%s must be [%s], got %s" % (name, want, tuple(t.shape)))
+    return t.to(device=device, dtype=torch.float32).contiguous(), was_np

@@ -4,6 +4,7 @@
 #include "avae_complete.h"
 #include "avae_retrieve.h"
 #include "avae_latent_stats.h"
+#include "avae_motion.h"
 #include "avae_gmm.h"
 #include "avae_embed.h"
 #include "avae_aggpost.h"
@@ -4582,6 +4583,93 @@ int avae_latent_stats(avae_handle* h, int32_t n_mod, const float* const* mu_dev,
             timed_launch(h, s, "latent_stats", [&] { launch_latent_stats(a, s); });
         }
         timed_launch(h, s, "latent_stats_merge", [&] { launch_latent_stats_merge(a, s); });
+    });
+}
+
+// ---- motion decoding (include/avae.h, avae_motion.h)
+static void check_motion_shape(const std::string& w, int32_t rows, int32_t D, int32_t Kb, int32_t T, int32_t nc) {
+    auto range = [&](const char* name, int v, int lo, int hi) {
+        if (v < lo || v > hi)
+            throw Err(w + ": " + name + " = " + std::to_string(v) + " must be in [" + std::to_string(lo) + ", " + std::to_string(hi) + "]");
+    };
+    if (rows < 0) throw Err(w + ": rows must be >= 0");
+    range("D", D, 1, kMotionMaxD);
+    range("Kb", Kb, 1, kMotionMaxKb);
+    range("T", T, 1, kMotionMaxT);
+    range("nc", nc, 0, kMotionMaxNc);
+}
+
+static MotionArgs motion_args(const std::string& w, const float* params, int32_t rows, int32_t S, int32_t D, int32_t Kb, int32_t T,
+                              const float* phi, const float* scale, const float* shift, const float* limits, const float* gain,
+                              const float* target, int32_t nc, bool moments) {
+    check_motion_shape(w, rows, D, Kb, T, nc);
+    if (S < 1) throw Err(w + ": S = " + std::to_string(S) + " must be >= 1");
+    if (!params) throw Err(w + (moments ? ": samples_dev is NULL" : ": params_dev is NULL"));
+    if (!phi) throw Err(w + ": phi_dev is NULL");
+    if (nc > 0 && !gain) throw Err(w + ": anchor_gain_dev is NULL with nc > 0");
+    if (nc > 0 && !target) throw Err(w + ": anchor_target_dev is NULL with nc > 0");
+    if (motion_lds_bytes(D, Kb, T, nc, moments, true) > kMotionMaxLds) throw Err("internal error: " + w + " plans more LDS than its bound");
+    MotionArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.params = params; a.phi = phi; a.scale = scale; a.shift = shift; a.limits = limits;
+    a.gain = nc > 0 ? gain : nullptr; a.target = nc > 0 ? target : nullptr;
+    a.rows = rows; a.S = S; a.D = D; a.Kb = Kb; a.T = T; a.nc = nc;
+    return a;
+}
+
+int avae_motion_eval(avae_handle* h, const float* params_dev, int32_t rows, int32_t D, int32_t Kb, int32_t T,
+                     const float* phi_dev, const float* scale_dev, const float* shift_dev, const float* limits_dev,
+                     const float* anchor_gain_dev, const float* anchor_target_dev, int32_t nc,
+                     const float* ref_traj_dev, const float* ref_params_dev,
+                     float* traj_dev, int32_t* saturated_dev, float* rmse_dev, float* maxabs_dev, void* stream) {
+    return guarded(h, [&] {
+        const std::string w = "avae_motion_eval";
+        MotionArgs a = motion_args(w, params_dev, rows, 1, D, Kb, T, phi_dev, scale_dev, shift_dev, limits_dev, anchor_gain_dev,
+                                   anchor_target_dev, nc, false);
+        if (ref_traj_dev && ref_params_dev) throw Err(w + ": ref_traj_dev and ref_params_dev are both given; pass one reference");
+        if ((rmse_dev || maxabs_dev) && !ref_traj_dev && !ref_params_dev)
+            throw Err(w + ": rmse_dev / maxabs_dev need a reference (ref_traj_dev or ref_params_dev)");
+        if (!traj_dev && !saturated_dev && !rmse_dev && !maxabs_dev) throw Err(w + ": every output is NULL");
+        if (rows == 0) return;
+        a.ref_traj = ref_traj_dev; a.ref_params = ref_params_dev;
+        a.traj = traj_dev; a.saturated = saturated_dev; a.rmse = rmse_dev; a.maxabs = maxabs_dev;
+        if (!rmse_dev && !maxabs_dev) { a.ref_traj = nullptr; a.ref_params = nullptr; }      // (a reference nobody reads)
+        hipStream_t s = on_stream(h, stream);
+        timed_launch(h, s, "motion_eval", [&] { launch_motion_eval(a, s); });
+    });
+}
+
+int avae_motion_fit(avae_handle* h, const float* traj_dev, int32_t rows, int32_t D, int32_t Kb, int32_t T,
+                    const float* pinv_dev, const float* scale_dev, const float* shift_dev, float* params_dev, void* stream) {
+    return guarded(h, [&] {
+        const std::string w = "avae_motion_fit";
+        check_motion_shape(w, rows, D, Kb, T, 0);
+        if (!traj_dev) throw Err(w + ": traj_dev is NULL");
+        if (!pinv_dev) throw Err(w + ": pinv_dev is NULL");
+        if (!params_dev) throw Err(w + ": params_dev is NULL");
+        if (rows == 0) return;
+        MotionFitArgs a;
+        std::memset(&a, 0, sizeof(a));
+        a.traj = traj_dev; a.pinv = pinv_dev; a.scale = scale_dev; a.shift = shift_dev; a.params = params_dev;
+        a.rows = rows; a.D = D; a.Kb = Kb; a.T = T;
+        hipStream_t s = on_stream(h, stream);
+        timed_launch(h, s, "motion_fit", [&] { launch_motion_fit(a, s); });
+    });
+}
+
+int avae_motion_moments(avae_handle* h, const float* samples_dev, int32_t rows, int32_t S, int32_t D, int32_t Kb, int32_t T,
+                        const float* phi_dev, const float* scale_dev, const float* shift_dev, const float* limits_dev,
+                        const float* anchor_gain_dev, const float* anchor_target_dev, int32_t nc,
+                        float* mean_dev, float* var_dev, float* saturated_frac_dev, void* stream) {
+    return guarded(h, [&] {
+        const std::string w = "avae_motion_moments";
+        MotionArgs a = motion_args(w, samples_dev, rows, S, D, Kb, T, phi_dev, scale_dev, shift_dev, limits_dev, anchor_gain_dev,
+                                   anchor_target_dev, nc, true);
+        if (!mean_dev) throw Err(w + ": mean_dev is NULL");
+        if (rows == 0) return;
+        a.traj = mean_dev; a.var = var_dev; a.sat_frac = saturated_frac_dev;
+        hipStream_t s = on_stream(h, stream);
+        timed_launch(h, s, "motion_moments", [&] { launch_motion_moments(a, s); });
     });
 }
 

@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from . import _capi
-from ._marshal import (corruption_fields, ema_fields, ema_kwargs, grad_clip_fields, grad_clip_kwargs, dev_array, dev_dense, dev_dense3, dev_flags, dev_inputs, dev_modalities, dev_row_args,
+from ._marshal import (corruption_fields, ema_fields, ema_kwargs, grad_clip_fields, grad_clip_kwargs, dev_array, dev_block3, dev_dense, dev_dense3, dev_flags, dev_inputs, dev_modalities, dev_row_args,
                        ld_of, ptr, schedule_kwargs, schedule_struct)
 from ._marshal import cyclical, exponential_decay, linear_warmup  # noqa: F401  (schedule helpers, part of this module's surface)
 from .parallel import GradSync, dp_bucket_schedule, dp_train_step_bucketed
@@ -595,6 +595,94 @@ def latent_stats_args(posteriors, present, n_z, device):
     if rows is None:
         raise ValueError("every modality is None and there is no present array: the row count is unknown")
     return mus, lvs, rows, p, (not torch.is_tensor(present)) if was_np is None else was_np
+
+
+def motion_matrices(basis, device, anchor=None, rows=None, T=None):
+    """A ``MotionBasis`` (and an optional anchor) -> the device matrices of the motion calls: dict of ``phi [T, Kb]``, ``scale``,
+    ``shift [P]`` or None, ``limits [D, 2]`` or None, ``gain [T, n_c]`` and ``target [rows, D, n_c]`` or None, ``nc``.  ``anchor`` is
+    None or ``dict(phases=[...], target=[rows, D, n_c])``: the trajectories are those of the parameters projected onto
+    ``features(phases) theta == target`` (1 to 4 phases).  The matrices are cached on the basis per device, phases and T."""
+    from .motion import MotionBasis
+    if not isinstance(basis, MotionBasis):
+        raise ValueError("basis must be a MotionBasis, got %r" % (type(basis).__name__,))
+    phases = target = None
+    if anchor is not None:
+        if not isinstance(anchor, dict) or set(anchor) != {"phases", "target"}:
+            raise ValueError("anchor must be None or dict(phases=, target=)")
+        phases = np.atleast_1d(np.asarray(anchor["phases"], dtype=np.float64))
+        basis.constraint(phases)                       # (checks the phases)
+        target, _ = dev_block3(anchor["target"], (basis.n_dof, len(phases)), device, "anchor target", rows)
+    key = ("device", str(device), None if phases is None else phases.tobytes(), T)
+    if key not in basis._cache:
+        def up(a):
+            return None if a is None else torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).to(device)
+        phi, gain = basis.eval_matrices(phases, T)
+        sc, sh = basis.scale_shift()
+        basis._cache[key] = dict(phi=up(phi), gain=up(gain), scale=up(sc), shift=up(sh), limits=up(basis.limits))
+    out = dict(basis._cache[key])
+    out.update(target=target, nc=0 if phases is None else len(phases))
+    return out
+
+
+def motion_eval_args(params, basis, anchor, reference, reference_params, device):
+    """The arguments of ``motion_eval`` checked and marshalled -> (params [N, P], matrices, reference trajectory or None, reference
+    parameters or None, was_numpy).  Every shape error is a ``ValueError`` raised here, ahead of any launch; touches neither a model
+    nor the library (``device="cpu"`` works)."""
+    from .motion import MotionBasis
+    if not isinstance(basis, MotionBasis):
+        raise ValueError("basis must be a MotionBasis, got %r" % (type(basis).__name__,))
+    if reference is not None and reference_params is not None:
+        raise ValueError("reference and reference_params are both given: pass one reference")
+    p, was_np = dev_array(params, basis.n_params, device)
+    p = p.contiguous()
+    rows = p.shape[0]
+    mats = motion_matrices(basis, device, anchor, rows)
+    ref = None if reference is None else dev_block3(reference, (basis.n_points, basis.n_dof), device, "reference", rows)[0]
+    refp = dev_dense(reference_params, basis.n_params, device, rows, "as params", name="reference_params")
+    return p, mats, ref, refp, was_np
+
+
+def motion_fit_args(trajectories, basis, device):
+    """The arguments of ``motion_fit`` -> (trajectories [N, T, D], pinv [Kb, T], scale, shift, was_numpy); ``ValueError`` ahead of
+    any launch, usable with ``device="cpu"``."""
+    from .motion import MAX_POINTS, MotionBasis
+    if not isinstance(basis, MotionBasis):
+        raise ValueError("basis must be a MotionBasis, got %r" % (type(basis).__name__,))
+    t, was_np = dev_block3(trajectories, (None, basis.n_dof), device, "trajectories")
+    T = int(t.shape[1])
+    if not 1 <= T <= MAX_POINTS:
+        raise ValueError("trajectories must hold 1 to %d time points, got %d" % (MAX_POINTS, T))
+    key = ("device pinv", str(device), T)
+    if key not in basis._cache:
+        basis._cache[key] = torch.as_tensor(np.ascontiguousarray(basis.pinv(T), dtype=np.float32)).to(device)
+    mats = motion_matrices(basis, device)
+    return t, basis._cache[key], mats["scale"], mats["shift"], was_np
+
+
+def motion_moments_args(samples, basis, anchor, device):
+    """The arguments of ``motion_moments`` -> (samples [N, S, P], matrices, was_numpy); ``ValueError`` ahead of any launch, usable
+    with ``device="cpu"``."""
+    from .motion import MotionBasis
+    if not isinstance(basis, MotionBasis):
+        raise ValueError("basis must be a MotionBasis, got %r" % (type(basis).__name__,))
+    t, was_np = dev_block3(samples, (None, basis.n_params), device, "samples")
+    if t.shape[1] < 1:
+        raise ValueError("samples must hold at least one sample per row, got %s" % (tuple(t.shape),))
+    return t, motion_matrices(basis, device, anchor, int(t.shape[0])), was_np
+
+
+def predict_motion_args(X, basis, modality, present, n_samples, eps, anchor, widths, n_z, device):
+    """The arguments of ``predict_motion`` -> (``impute_args``' tuple with K = 0 and the eps block [N, S, n_z] or None in its last
+    two places, matrices); ``ValueError`` ahead of any launch, usable with ``device="cpu"``."""
+    from .motion import MotionBasis
+    if not isinstance(basis, MotionBasis):
+        raise ValueError("basis must be a MotionBasis, got %r" % (type(basis).__name__,))
+    if isinstance(modality, bool) or not isinstance(modality, (int, np.integer)) or not 0 <= modality < len(widths):
+        raise ValueError("modality must be an index in [0, %d), got %r" % (len(widths), modality))
+    if basis.n_params != widths[modality]:
+        raise ValueError("basis.n_params = %d must be n_input = %d of modality %d" % (basis.n_params, widths[modality], modality))
+    ts, rows, was_np, xp, lds, p, S, e = impute_args(X, present, n_samples, eps, widths, n_z, device)
+    return (ts, rows, was_np, xp, lds, p, S, e), motion_matrices(basis, device, anchor, rows)
 
 
 class AssocVariationalAutoEncoder(object):
@@ -1539,6 +1627,147 @@ class AssocVariationalAutoEncoder(object):
         conv = self._like_input(was_np)
         return {"mu": conv(mu), "logvar": conv(lv), "mean": [conv(o) for o in mean],
                 "var": [conv(o) for o in var] if K else None}
+
+    # ------------------------------------------------------------------ motion decoding
+    _motion_chunk = 16384      # decoded rows (input rows x samples) predict_motion holds at a time
+
+    def _motion_eval(self, p, mats, basis, ref=None, refp=None):
+        """avae_motion_eval on device tensors -> (trajectory [N, T, D], saturated [N, D] int32, rmse, max_abs [N, D] or None)"""
+        N, T, D = p.shape[0], basis.n_points, basis.n_dof
+        traj = torch.empty((N, T, D), dtype=torch.float32, device=self.device)
+        sat = torch.empty((N, D), dtype=torch.int32, device=self.device)
+        has_ref = ref is not None or refp is not None
+        rmse, mx = (self._new(N, D), self._new(N, D)) if has_ref else (None, None)
+        if N:
+            _capi.check(self._h, self._L.avae_motion_eval(
+                self._h, p.data_ptr(), N, D, basis.n_kb, T, mats["phi"].data_ptr(), ptr(mats["scale"]), ptr(mats["shift"]),
+                ptr(mats["limits"]), ptr(mats["gain"]), ptr(mats["target"]), mats["nc"], ptr(ref), ptr(refp),
+                traj.data_ptr(), sat.data_ptr(), ptr(rmse), ptr(mx), self._stream()), "avae_motion_eval")
+        return traj, sat, rmse, mx
+
+    def motion_eval(self, params, basis, anchor=None, reference=None, reference_params=None):
+        """Standardised approximator parameters -> joint trajectories (avae_motion_eval in include/avae.h): what the reference does
+        after every ``generate`` (baxter_vae_assoc_writer.py:145-150, 439-458) -- un-normalise with the basis' ``param_mean`` /
+        ``param_std``, evaluate every joint's approximator at the basis' phase points, clamp to the joint limits.
+
+        ``params`` is ``[N, basis.n_params]``; ``anchor`` None or ``dict(phases=[...], target=[N, n_dof, n_c])``: the trajectory
+        of the parameters projected onto passing through ``target`` at ``phases`` (pyrbf_funcapprox.py:41-61).  ``reference``
+        (``[N, n_points, n_dof]`` trajectories) or ``reference_params`` (``[N, n_params]``, evaluated the same way, without
+        anchor) asks for the error against it.  Returns a dict: ``trajectory [N, n_points, n_dof]``, ``saturated [N, n_dof]``
+        (int32, the number of clamped points) and ``rmse`` / ``max_abs [N, n_dof]`` over the time points (None without a
+        reference).  NumPy in gives NumPy out, device tensors in give device tensors out."""
+        p, mats, ref, refp, was_np = motion_eval_args(params, basis, anchor, reference, reference_params, self.device)
+        traj, sat, rmse, mx = self._motion_eval(p, mats, basis, ref, refp)
+        conv = self._like_input(was_np)
+        return {"trajectory": conv(traj), "saturated": conv(sat), "rmse": None if rmse is None else conv(rmse),
+                "max_abs": None if mx is None else conv(mx)}
+
+    def motion_fit(self, trajectories, basis):
+        """Joint trajectories ``[N, T, n_dof]`` -> standardised parameters ``[N, basis.n_params]`` (avae_motion_fit): the
+        least-squares fit of the basis at ``linspace(0, 1, T)`` with the reference's truncated pseudo-inverse, per joint, then
+        ``(theta - param_mean) / param_std`` (baxter_writer.py:77-82, 193).  T is the input's own."""
+        t, pinv, sc, sh, was_np = motion_fit_args(trajectories, basis, self.device)
+        N, T = t.shape[0], t.shape[1]
+        out = self._new(N, basis.n_params)
+        if N:
+            _capi.check(self._h, self._L.avae_motion_fit(self._h, t.data_ptr(), N, basis.n_dof, basis.n_kb, T, pinv.data_ptr(),
+                                                         ptr(sc), ptr(sh), out.data_ptr(), self._stream()), "avae_motion_fit")
+        return self._like_input(was_np)(out)
+
+    def _motion_moments(self, s, N, S, mats, basis, mean, var, frac):
+        """avae_motion_moments on N rows of S dense samples at ``s`` into (slices of) the outputs"""
+        _capi.check(self._h, self._L.avae_motion_moments(
+            self._h, s.data_ptr(), N, S, basis.n_dof, basis.n_kb, basis.n_points, mats["phi"].data_ptr(), ptr(mats["scale"]),
+            ptr(mats["shift"]), ptr(mats["limits"]), ptr(mats["gain"]), ptr(mats["target"]), mats["nc"],
+            mean.data_ptr(), ptr(var), ptr(frac), self._stream()), "avae_motion_moments")
+
+    def motion_moments(self, samples, basis, anchor=None):
+        """Per-point mean and population variance of the trajectories of S parameter samples per row (avae_motion_moments):
+        ``samples`` is ``[N, S, basis.n_params]``, every sample evaluated as by ``motion_eval`` (clamp included) and folded into
+        running moments on the device; the ``N S n_points n_dof`` trajectory values are never stored.  Returns a dict: ``mean`` and
+        ``var [N, n_points, n_dof]`` and ``saturated_frac [N, n_dof]``, the share of clamped points over samples and time."""
+        s, mats, was_np = motion_moments_args(samples, basis, anchor, self.device)
+        N, S = s.shape[0], s.shape[1]
+        shape = (N, basis.n_points, basis.n_dof)
+        mean, var = (torch.empty(shape, dtype=torch.float32, device=self.device) for _ in range(2))
+        frac = self._new(N, basis.n_dof)
+        if N:
+            self._motion_moments(s, N, S, mats, basis, mean, var, frac)
+        conv = self._like_input(was_np)
+        return {"mean": conv(mean), "var": conv(var), "saturated_frac": conv(frac)}
+
+    def _fused_decode(self, xp, lds, p, rows, modality, want_mean):
+        """avae_impute with no samples -> (mu, logvar, the decoded fused mean of ``modality`` or None)"""
+        mu, lv = self._new(rows, self.n_z), self._new(rows, self.n_z)
+        mean = [None] * len(self._widths)
+        if want_mean:
+            mean[modality] = self._new(rows, self._widths[modality])
+        if rows:
+            _capi.check(self._h, self._L.avae_impute(self._h, xp, lds, ptr(p), rows, 0, None, mu.data_ptr(), lv.data_ptr(),
+                                                     self._ptrs(mean), None, self._stream()), "avae_impute")
+        return mu, lv, mean[modality]
+
+    def predict_motion(self, X, basis, modality=1, present=None, n_samples=0, eps=None, anchor=None):
+        """From the modalities each row has to the joint trajectory of modality ``modality`` (the writer's
+        ``derive_robot_motion_from_img``, baxter_vae_assoc_writer.py:439-458, up to the trajectory): ``impute``'s fused posterior,
+        decoded and evaluated with ``basis`` (``basis.n_params`` must be the modality's ``n_input``).
+
+        ``X`` / ``present`` as in ``impute``.  ``n_samples = 0``: the trajectory of the decoded fused mean, bitwise
+        ``motion_eval(impute(X, present)["mean"][modality], basis, anchor)``.  ``n_samples = S >= 1``: the per-point mean and
+        population variance over the trajectories of S samples ``z = mu + exp(logvar / 2) eps`` (``eps`` [N, S, n_z], or None for
+        a fresh draw from torch's generator), computed in row chunks: a chunk's latents are decoded and their trajectories
+        folded into the moments on the device, so only one chunk's decoded parameters ever exist.
+
+        Returns a dict: ``mu``, ``logvar [N, n_z]``, ``trajectory [N, n_points, n_dof]`` (with samples: their mean), ``var``
+        (None without samples) and ``saturated_frac [N, n_dof]``, the share of clamped points."""
+        (ts, rows, was_np, xp, lds, p, S, e), mats = predict_motion_args(X, basis, modality, present, n_samples, eps, anchor,
+                                                                         self._widths, self.n_z, self.device)
+        conv = self._like_input(was_np)
+        mu, lv, mean = self._fused_decode(xp, lds, p, rows, modality, S == 0)
+        out = {"mu": conv(mu), "logvar": conv(lv), "var": None}
+        if S == 0:
+            traj, sat, _, _ = self._motion_eval(mean, mats, basis)
+            out.update(trajectory=conv(traj), saturated_frac=conv(sat.to(torch.float32) / float(basis.n_points)))
+            return out
+        shape = (rows, basis.n_points, basis.n_dof)
+        traj, var = (torch.empty(shape, dtype=torch.float32, device=self.device) for _ in range(2))
+        frac = self._new(rows, basis.n_dof)
+        if e is None:
+            e = torch.randn((rows, S, self.n_z), dtype=torch.float32, device=self.device)
+        sd = torch.exp(0.5 * lv)
+        chunk = max(1, int(self._motion_chunk) // S)
+        dec = self._new(min(chunk, rows) * S, basis.n_params)
+        target = mats["target"]
+        for r0 in range(0, rows, chunk):
+            n = min(chunk, rows - r0)
+            z = (mu[r0:r0 + n, None, :] + sd[r0:r0 + n, None, :] * e[r0:r0 + n]).reshape(n * S, self.n_z).contiguous()
+            _capi.check(self._h, self._L.avae_decode(self._h, modality, z.data_ptr(), n * S, dec.data_ptr(), self._stream()),
+                        "avae_decode")
+            m = dict(mats, target=None if target is None else target[r0:r0 + n])
+            self._motion_moments(dec, n, S, m, basis, traj[r0:r0 + n], var[r0:r0 + n], frac[r0:r0 + n])
+        out.update(trajectory=conv(traj), var=conv(var), saturated_frac=conv(frac))
+        return out
+
+    def motion_error(self, X, basis, source=0, modality=1):
+        """The cross-modal prediction error in joint units: the trajectory decoded from the posterior mean of modality ``source``
+        against the trajectory of the row's own parameters ``X[modality]``, both evaluated with ``basis``.  Returns a dict of
+        ``rmse`` and ``max_abs [N, n_dof]`` over the time points -- ``motion_eval(impute(only source)["mean"][modality], basis,
+        reference_params=X[modality])``."""
+        M = len(self._widths)
+        if isinstance(source, bool) or not isinstance(source, (int, np.integer)) or not 0 <= source < M:
+            raise ValueError("source must be an index in [0, %d), got %r" % (M, source))
+        if len(X) != M:
+            raise ValueError("expected a list of %d modalities, got %d" % (M, len(X)))
+        only = [X[m] if m == source else None for m in range(M)]
+        (ts, rows, was_np, xp, lds, p, _, _), mats = predict_motion_args(only, basis, modality, None, 0, None, None, self._widths,
+                                                                        self.n_z, self.device)
+        if X[modality] is None:
+            raise ValueError("X[%d] is None: the error needs the row's own parameters" % modality)
+        refp = dev_dense(X[modality], basis.n_params, self.device, rows, "as X[%d]" % source, name="X[%d]" % modality)
+        _, _, mean = self._fused_decode(xp, lds, p, rows, modality, True)
+        _, _, rmse, mx = self._motion_eval(mean, mats, basis, None, refp)
+        conv = self._like_input(was_np)
+        return {"rmse": conv(rmse), "max_abs": conv(mx)}
 
     def save_model(self, fname=None):
         """reference vae_assoc.py:427-435 (default name: timestamp + batch size)."""
