@@ -10,9 +10,10 @@ forces use_graph = 0 and with it the by-modality route.  A handle created with A
 builds the serve plan of a row bucket, ``[avae] serve plan bucket=B fused_in=0|1 lean_in=0|1 in_lean_grid=G`` and the same launch and
 item lines for the plan's launches, the fused staging launch first (parse_serve, serve_plan).
 
-Tile configurations (avae_host.hip::finish_launch): 0 = 64x64, 1 = 128x128, 2 = 256x128 8-wave NT/TN, 3 = 32x64, 4 = 64x128
-(wide-latent heads), 5 = 32x32, 6 = 256x64 8-wave loss, 7/9/10/11 = the lean small-net kernels, 12 = small-net weight gradients
-with Adam in the epilogue."""
+Tile configurations (the source is the enumeration TileCfg in vae_assoc_amd/csrc/avae_device.h, whose values are pinned for this
+text format; avae_host.hip::choose_cfg picks one per launch): 0 = 64x64, 1 = 128x128, 2 = 256x128 8-wave NT/TN, 3 = 32x64,
+4 = 64x128 (wide-latent heads), 5 = 32x32, 6 = 256x64 8-wave loss, 7/9/10/11 = the lean small-net kernels, 12 = small-net weight
+gradients with Adam in the epilogue.  `type` is LaunchType of the same header (0 = a grouped GEMM launch)."""
 import re
 
 import numpy as np

@@ -55,6 +55,67 @@ enum Kind : int {
                          // output pointers of modality 0..3).  Launched per call with these fields patched by value.
 };
 
+// What a launch of a plan runs (host: Launch::type) and, for the grouped GEMM launches, on which tile configuration (Launch::cfg).
+// The values are pinned: the plan dumps print them as integers ("type=%d cfg=%d"), and tests/plan_dump.py, the tests' cfg
+// assertions and the logs under profiles/ read those numbers.
+enum LaunchType : int {
+    kGrouped = 0,        // a grouped GEMM kernel (k_grouped, the k_small family) on Launch::cfg
+    kGather = 1,         // k_gather (im2col)
+    kCol2im = 2,         // k_col2im
+    kReduce = 3,         // k_reduce (split-K slices -> gradient)
+    kThin = 4,           // k_thin (the direct one-channel stage)
+    kColsum = 5,         // k_colsum
+    kWadj = 6,           // k_wadj
+    kGperm = 7,          // k_gperm
+    kRowsum = 8,         // k_rowsum
+    kSums = 9,           // k_sums (column sums + slice sums in one launch)
+};
+enum TileCfg : int {
+    k64x64 = 0,          // 4-stage ring
+    k128x128 = 1,        // 2-stage ring, two workgroups per CU
+    k256x128 = 2,        // 8 waves, 3-stage ring, one workgroup per CU (big single-C-tile kinds only)
+    k32x64 = 3,          // NT launches with too few 64x64 tiles to occupy the chip
+    k64x128 = 4,         // wide-latent head / latent-dgrad launches with few tiles
+    k32x32 = 5,          // as k32x64, for launches without head kinds
+    k256x64Loss = 6,     // 8 waves, register epilogue: the output + loss launch of the big nets
+    kLean = 7,           // k_small: one kind and one transfer function per launch
+                         // (8 is unused: a closed experiment's number, kept free so that old logs stay readable)
+    kLeanLoss = 9,       // k_small_loss: output + loss, the latent item riding along
+    kLeanLatb = 10,      // k_small_latb: bwd_dec1_latent + bwd_head
+    kLeanHead = 11,      // k_small_head: fwd_head + fwd_dec1
+    kLeanTnAdam = 12,    // k_small_tn: every weight gradient with Adam in the epilogue
+    kChain2 = 13,        // k_chain2 (AVAE_CHAIN2)
+};
+// The one table of tile geometry: tile rows x columns, threads of a workgroup (NT instance), stages of the operand ring, and what
+// the kernel behind the configuration can do.
+struct TileGeom {
+    int rows, cols, threads, ring;
+    bool waves8;         // the 8-wave tiles: bias epilogue, weight warm-up, one workgroup per CU
+    bool lean;           // a kernel of the k_small family (its own LDS frame)
+    bool gather;         // carries the implicit-GEMM gather (WorkItem::conv)
+    bool masked;         // has an instance with the presence gate (WorkItem::present)
+    int records;         // lines of a per-workgroup record the training plan may run it on (0: by-value arguments only)
+};
+constexpr int kTileCfgs = 14;
+constexpr TileGeom kTileGeom[kTileCfgs] = {
+    {64, 64, 256, 4, false, false, true, true, 0},        // k64x64
+    {128, 128, 256, 2, false, false, false, true, 0},     // k128x128
+    {256, 128, 512, 3, true, false, false, false, 0},     // k256x128
+    {32, 64, 256, 4, false, false, true, true, 0},        // k32x64
+    {64, 128, 256, 4, false, false, false, true, 0},      // k64x128
+    {32, 32, 256, 4, false, false, true, true, 0},        // k32x32
+    {256, 64, 512, 3, true, false, false, true, 0},       // k256x64Loss
+    {32, 32, 256, 4, false, true, false, false, 1},       // kLean
+    {0, 0, 0, 0, false, false, false, false, 0},          // (unused)
+    {32, 32, 256, 4, false, true, false, true, 2},        // kLeanLoss
+    {32, 64, 256, 4, false, true, false, false, 2},       // kLeanLatb
+    {32, 64, 256, 4, false, true, false, false, 2},       // kLeanHead
+    {64, 64, 256, 4, false, true, false, false, 1},       // kLeanTnAdam
+    {32, 32, 256, 4, false, true, false, false, 0},       // kChain2
+};
+constexpr const TileGeom& tile_geom(int cfg) { return kTileGeom[cfg]; }
+constexpr int tile_ring_bytes(int cfg) { return kTileGeom[cfg].ring * (kTileGeom[cfg].rows + kTileGeom[cfg].cols) * kTileBytesK; }
+
 struct WorkItem {
     int kind;
     int M, N, K;             // K is the padded extent (multiple of the K unit)

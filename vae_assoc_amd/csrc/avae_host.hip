@@ -154,9 +154,10 @@ struct Mod {
 
 struct Launch {
     std::string name;
-    int type = 0;          // 0: grouped GEMM kernel, 1: k_gather (im2col), 2: k_col2im, 3: k_reduce (split-K slices -> gradient)
-    int cfg = 0, first = 0, count = 0, blocks = 0, lds = 0;
-    int lean_act = 0;      // tile configurations 10 / 11 (lean head launches): the tail's transfer function
+    LaunchType type = kGrouped;
+    TileCfg cfg = k64x64;  // kGrouped launches only
+    int first = 0, count = 0, blocks = 0, lds = 0;
+    int lean_act = 0;      // kLeanLatb / kLeanHead: the tail's transfer function
     int grid_x = 1, grid_y = 1;   // grouped kernel: tile slot x item
     bool tn = false;              // K-major operands (the weight-gradient launches)
     LaunchArgs args{};
@@ -220,6 +221,89 @@ struct DevBuf {
     }
     template <typename T> T* as() const { return static_cast<T*>(p); }
 };
+
+// The environment switches (A/B runs, diagnostics, tests): read ONCE per handle, by read_switches() at the top of avae_create (and
+// of the temporary handles of avae_workspace_bytes / avae_dp_plan), before anything is planned.  Every plan of the handle -- the
+// training plan and the serve, inference, masked and completion plans built by a later first call -- follows this copy: a switch
+// set or cleared after avae_create does not reach the handle.
+struct PlanSwitches {
+    // present = on, whatever the value
+    bool no_ld_spread = false, no_implicit = false, no_thin = false, no_thin_fast = false, no_adj = false;
+    bool no_256 = false, no_32 = false, no_32x32 = false, no_lean = false, no_lean_loss = false, no_lean_head = false, no_64x128 = false,
+         no_loss8 = false, no_bias_ep = false, no_bias_mfma = false, no_tn_slices = false, no_tn_balance = false;
+    bool no_tail = false, no_wadj_fold = false, no_sink = false, no_sums_merge = false, no_adam_fuse = false, no_xcd_pieces = false,
+         no_warm = false, no_desc = false;
+    bool chain2 = false, debug_dp = false, comm_no_prio = false;
+    // "1" = on
+    bool debug_sync = false, plan_dump = false, keep_grads = false;
+    // values
+    bool tn_g_set = false;
+    int tn_g = 1;
+    int sched = 0;
+    int thin_fast_split[3] = {1, 4, 1};      // measured on c2conv (tools/thin_split_ab.sh): forward 7.1 us at 1 (12.3 at 2, 21.6 at 4), dX 10.4 / 7.6 / 5.8, dF 8.3 / 8.1 / 10.5
+    std::string impl_policy = "E:fw,H:fwb,D1:fwb,DT:";
+    int ipc_blocks = 256;                    // one workgroup per CU: the exchange is three memory passes over the range, and 64
+                                             // workgroups moved them at < 1 TB/s (14 us for C2's 6 MB with one rank, measured)
+    double ipc_timeout_ms = 20000.0;         // a peer that is this late has failed: raise the error word instead of hanging
+};
+
+struct SwitchRow {
+    const char* name;
+    bool PlanSwitches::* present;                      // presence-only switches; null: parse() reads the value
+    void (*parse)(PlanSwitches&, const char*);
+    const char* what;
+};
+#define AVAE_ONE(member) nullptr, +[](PlanSwitches& s, const char* e) { s.member = e[0] == '1'; }
+const SwitchRow kSwitches[] = {
+    {"AVAE_NO_LD_SPREAD", &PlanSwitches::no_ld_spread, nullptr, "row strides that are a multiple of 512 bytes stay as they are (spread_ld)"},
+    {"AVAE_NO_IMPLICIT", &PlanSwitches::no_implicit, nullptr, "no implicit-GEMM conv route; round 2's compact map layout"},
+    {"AVAE_NO_THIN", &PlanSwitches::no_thin, nullptr, "the one-channel stage runs im2col -> GEMM -> col2im, not k_thin"},
+    {"AVAE_NO_THIN_FAST", &PlanSwitches::no_thin_fast, nullptr, "k_thin without the block-structured path of the reference's geometry"},
+    {"AVAE_NO_ADJ", &PlanSwitches::no_adj, nullptr, "transposed convs keep their fp32 patch gradients (no adjoint-frame route)"},
+    {"AVAE_NO_256", &PlanSwitches::no_256, nullptr, "k128x128 where k256x128 would be chosen"},
+    {"AVAE_NO_32", &PlanSwitches::no_32, nullptr, "k64x64 where a 32-row tile (and everything lean) would be chosen"},
+    {"AVAE_NO_32x32", &PlanSwitches::no_32x32, nullptr, "k32x64 where k32x32 would be chosen"},
+    {"AVAE_NO_LEAN", &PlanSwitches::no_lean, nullptr, "no kernel of the k_small family, no k_serve_in, no fused wgrad+adam"},
+    {"AVAE_NO_LEAN_LOSS", &PlanSwitches::no_lean_loss, nullptr, "the output + loss launch stays on k32x32"},
+    {"AVAE_NO_LEAN_HEAD", &PlanSwitches::no_lean_head, nullptr, "the fused head launches stay on k32x64"},
+    {"AVAE_NO_64x128", &PlanSwitches::no_64x128, nullptr, "k128x128 for the wide-latent head launches"},
+    {"AVAE_NO_LOSS8", &PlanSwitches::no_loss8, nullptr, "no k256x64Loss; the latent item rides in fwd_out_loss"},
+    {"AVAE_NO_BIAS_EP", &PlanSwitches::no_bias_ep, nullptr, "8-wave tiles: the bias row stays in the K loop"},
+    {"AVAE_NO_BIAS_MFMA", &PlanSwitches::no_bias_mfma, nullptr, "weight gradients: the bias gradient stays a tile row"},
+    {"AVAE_NO_TN_SLICES", &PlanSwitches::no_tn_slices, nullptr, "weight-gradient items are not cut into entries"},
+    {"AVAE_NO_TN_BALANCE", &PlanSwitches::no_tn_balance, nullptr, "weight-gradient entries keep plan order over the XCD groups"},
+    {"AVAE_NO_TAIL", &PlanSwitches::no_tail, nullptr, "no tail product: fwd_dec1 / bwd_head / serve_dec1 are launches of their own"},
+    {"AVAE_NO_WADJ_FOLD", &PlanSwitches::no_wadj_fold, nullptr, "the adjoint filter shadows come from k_wadj, not from k_adam"},
+    {"AVAE_NO_SINK", &PlanSwitches::no_sink, nullptr, "mixed models: the MLP modalities' launches stay launches of their own"},
+    {"AVAE_NO_SUMS_MERGE", &PlanSwitches::no_sums_merge, nullptr, "column sums, slice sums and k_gperm stay separate launches"},
+    {"AVAE_NO_ADAM_FUSE", &PlanSwitches::no_adam_fuse, nullptr, "small nets: k_adam stays a launch of its own"},
+    {"AVAE_NO_XCD_PIECES", &PlanSwitches::no_xcd_pieces, nullptr, "wgrad+adam without XCD-owned pieces"},
+    {"AVAE_NO_WARM", &PlanSwitches::no_warm, nullptr, "8-wave tiles do not warm the next launch's weight panels"},
+    {"AVAE_NO_DESC", &PlanSwitches::no_desc, nullptr, "every launch stays on its by-value arguments (no descriptor table)"},
+    {"AVAE_CHAIN2", &PlanSwitches::chain2, nullptr, "experiment: fwd_enc1 + fwd_enc2 of the small nets as one launch (k_chain2)"},
+    {"AVAE_DEBUG_DP", &PlanSwitches::debug_dp, nullptr, "say why a data-parallel graph capture fell back"},
+    {"AVAE_COMM_NO_PRIO", &PlanSwitches::comm_no_prio, nullptr, "the collective's stream gets no priority"},
+    {"AVAE_DEBUG_SYNC", AVAE_ONE(debug_sync), "=1: print and synchronise every launch that runs"},
+    {"AVAE_PLAN_DUMP", AVAE_ONE(plan_dump), "=1: serve_plan prints the plan it builds"},
+    {"AVAE_KEEP_GRADS", AVAE_ONE(keep_grads), "=1: every fused wgrad+adam launch stores its gradient"},
+    {"AVAE_TN_G", nullptr, +[](PlanSwitches& s, const char* e) { s.tn_g_set = true; s.tn_g = std::atoi(e); }, "XCD group of the weight-gradient launches: 1, 2, 4 or 8 (checked by wgrad_entries)"},
+    {"AVAE_SCHED", nullptr, +[](PlanSwitches& s, const char* e) { s.sched = std::atoi(e); }, "LaunchArgs::sched of every grouped launch"},
+    {"AVAE_THIN_FAST_SPLIT", nullptr, +[](PlanSwitches& s, const char* e) { std::sscanf(e, "%d,%d,%d", &s.thin_fast_split[0], &s.thin_fast_split[1], &s.thin_fast_split[2]); },
+     "\"a,b,c\": workgroups per image of the direct stage in mode 0 / 1 / 2"},
+    {"AVAE_IMPL_POLICY", nullptr, +[](PlanSwitches& s, const char* e) { s.impl_policy = e; }, "which conv products run as implicit GEMMs (plan_memory)"},
+    {"AVAE_IPC_BLOCKS", nullptr, +[](PlanSwitches& s, const char* e) { s.ipc_blocks = std::atoi(e); }, "workgroups of the hipIpc all-reduce (checked by comm_init_ipc)"},
+    {"AVAE_IPC_TIMEOUT_MS", nullptr, +[](PlanSwitches& s, const char* e) { s.ipc_timeout_ms = std::atof(e); }, "bound of every wait of the hipIpc all-reduce"},
+};
+#undef AVAE_ONE
+
+PlanSwitches read_switches() {
+    PlanSwitches s;
+    for (const SwitchRow& r : kSwitches)
+        if (const char* e = std::getenv(r.name)) {
+            if (r.present) s.*r.present = true; else r.parse(s, e);
+        }
+    return s;
+}
 
 }  // namespace
 
@@ -353,9 +437,7 @@ struct avae_handle {
     hipEvent_t ev_switch = nullptr;
     unsigned draw_id = 0;                   // forward-only calls that drew their own eps (next_draw: keys the generator, a fresh draw per call)
     bool timing = false;
-    bool debug_sync = false;
-    bool plan_dump = false;                 // AVAE_PLAN_DUMP=1: serve_plan prints the plan it builds (nothing else changes)
-    bool keep_grads = false;                // AVAE_KEEP_GRADS=1: every fused wgrad+adam launch stores its gradient (step_body; A/B and the tests' twin)
+    PlanSwitches sw;                        // the environment as avae_create found it
     std::vector<std::string> tnames;
     std::vector<TimingRec> trecs;
 
@@ -370,29 +452,29 @@ namespace {
 // Row strides that are a multiple of 512 bytes put the rows of an operand tile (one 128-byte chunk per row and K step) on a
 // handful of the L2's address-interleaved channels (a 2048-byte stride: C4's W shadows, 1024 x bf16 -- its dgrad K loop ran
 // 1.03 us per tile against 0.90 for the forward's 2176-byte rows).  One more K unit (128 bytes) of zero padding per row avoids it.
-inline int spread_ld(int ld, int KU, int es) {
-    static const bool off = std::getenv("AVAE_NO_LD_SPREAD") != nullptr;
-    return (!off && ((size_t)ld * es) % 512 == 0) ? ld + KU : ld;
+// (`spread`: false under AVAE_NO_LD_SPREAD)
+inline int spread_ld(int ld, int KU, int es, bool spread) {
+    return (spread && ((size_t)ld * es) % 512 == 0) ? ld + KU : ld;
 }
 
-Act make_act(Bump& b, int width, bool ones, int rows, int KU, int es, int ld = 0) {
+Act make_act(Bump& b, int width, bool ones, int rows, int KU, int es, bool spread, int ld = 0) {
     Act a;
     a.width = width;
     a.rows = rows;
     a.ones = ones;
-    a.ld = ld > 0 ? ld : spread_ld((int)rup(width + 1, KU), KU, es);       // ld given: a buffer that is never a GEMM operand
+    a.ld = ld > 0 ? ld : spread_ld((int)rup(width + 1, KU), KU, es, spread);       // ld given: a buffer that is never a GEMM operand
     a.rm = b.take(rup(rows, kRowAlign) * (size_t)a.ld * es);
     return a;
 }
 
-Dense make_dense(Bump& b, size_t& pint, int in, int out, int KU, int es, bool head) {
+Dense make_dense(Bump& b, size_t& pint, int in, int out, int KU, int es, bool spread, bool head) {
     Dense d;
     d.in = in; d.out = out; d.head = head;
     d.ld = (int)rup(out, 32);                      // theta / m / v / g rows: whole 128-byte lines (k_adam streams them: rows cut at 16 bytes
                                                    // cost it 9.0 -> 11.75 us on C2), not padded to the K unit.  This layout is what the gradient
                                                    // all-reduce puts on the wire: 6.13 MB for C2's 5.87 MB of parameters (6.6 MB padded to K)
-    d.ldw = spread_ld((int)rup(out, KU), KU, es);
-    d.ldt = spread_ld((int)rup(in + 1, KU), KU, es);
+    d.ldw = spread_ld((int)rup(out, KU), KU, es, spread);
+    d.ldt = spread_ld((int)rup(in + 1, KU), KU, es, spread);
     d.master = pint;
     pint += (size_t)(in + 1) * d.ld;
     d.W = b.take(rup(in + 1, kRowAlign) * (size_t)d.ldw * es);
@@ -428,13 +510,11 @@ void check_config(const avae_config& c) {
 
 // Lays out the whole workspace; with h->ws == nullptr it only computes sizes.
 // workgroups per image of the direct one-channel stage: 1 on the block-structured path (the reference's geometry), else kThinSplit
-inline bool thin_fast(const ConvGeom& g) { return thin_fast_geometry(g) && !std::getenv("AVAE_NO_THIN_FAST"); }
+inline bool thin_fast(const PlanSwitches& sw, const ConvGeom& g) { return thin_fast_geometry(g) && !sw.no_thin_fast; }
 // workgroups per image of the direct one-channel stage in mode 0 / 1 / 2 (AVAE_THIN_FAST_SPLIT="a,b,c": A/B runs)
-inline int thin_split(const ConvGeom& g, int mode) {
-    if (!thin_fast(g)) return kThinSplit;
-    int sp[3] = {1, 4, 1};       // measured on c2conv (tools/thin_split_ab.sh): forward 7.1 us at 1 (12.3 at 2, 21.6 at 4), dX 10.4 / 7.6 / 5.8, dF 8.3 / 8.1 / 10.5
-    if (const char* e = std::getenv("AVAE_THIN_FAST_SPLIT")) std::sscanf(e, "%d,%d,%d", &sp[0], &sp[1], &sp[2]);
-    const int v = sp[mode];
+inline int thin_split(const PlanSwitches& sw, const ConvGeom& g, int mode) {
+    if (!thin_fast(sw, g)) return kThinSplit;
+    const int v = sw.thin_fast_split[mode];
     return v == 1 || v == 2 || v == 4 ? v : 1;
 }
 
@@ -449,6 +529,8 @@ void plan_memory(avae_handle* h) {
     h->ld_eps = (int)rup(c.n_z, 4);
     h->M = c.n_modalities;
     const int KU = h->KU, es = h->es, Bp = h->Bp, ldB = h->ldB, nz = h->nz, B = h->B;
+    const PlanSwitches& sw = h->sw;
+    const bool spread = !sw.no_ld_spread;
     Bump b;
     size_t pint = 0, pflat = 0;
     h->mods.clear();
@@ -460,7 +542,7 @@ void plan_memory(avae_handle* h) {
     h->stage_lo = b.off;
     for (int m = 0; m < h->M; ++m) {
         const avae_modality& mo = c.mod[m];
-        stage_x0[m] = make_act(b, mo.n_input, mo.hidden_conv == 0, B, KU, es);
+        stage_x0[m] = make_act(b, mo.n_input, mo.hidden_conv == 0, B, KU, es, spread);
         stage_x32[m] = b.take((size_t)B * rup(mo.n_input, 8) * 4);
     }
     h->off_eps = b.take((size_t)B * h->ld_eps * 4);
@@ -473,15 +555,15 @@ void plan_memory(avae_handle* h) {
         md.L = mo.n_hidden_layers;
         md.hs.assign(mo.n_hidden, mo.n_hidden + md.L);
         md.conv = mo.hidden_conv != 0;
-        auto act_B = [&](int width, bool ones) { return make_act(b, width, ones, B, KU, es); };
+        auto act_B = [&](int width, bool ones) { return make_act(b, width, ones, B, KU, es, spread); };
         if (!md.conv) {
             int prev = md.n_in;
-            for (int k = 0; k < md.L; ++k) { md.enc.push_back(make_dense(b, pint, prev, md.hs[k], KU, es, false)); pflat += (size_t)(prev + 1) * md.hs[k]; prev = md.hs[k]; }
-            md.head = make_dense(b, pint, prev, 2 * nz, KU, es, true);
+            for (int k = 0; k < md.L; ++k) { md.enc.push_back(make_dense(b, pint, prev, md.hs[k], KU, es, spread, false)); pflat += (size_t)(prev + 1) * md.hs[k]; prev = md.hs[k]; }
+            md.head = make_dense(b, pint, prev, 2 * nz, KU, es, spread, true);
             pflat += (size_t)(prev + 1) * 2 * nz;
             prev = nz;
-            for (int k = 0; k < md.L; ++k) { md.dec.push_back(make_dense(b, pint, prev, md.hs[k], KU, es, false)); pflat += (size_t)(prev + 1) * md.hs[k]; prev = md.hs[k]; }
-            md.outl = make_dense(b, pint, prev, md.n_in, KU, es, false);
+            for (int k = 0; k < md.L; ++k) { md.dec.push_back(make_dense(b, pint, prev, md.hs[k], KU, es, spread, false)); pflat += (size_t)(prev + 1) * md.hs[k]; prev = md.hs[k]; }
+            md.outl = make_dense(b, pint, prev, md.n_in, KU, es, spread, false);
             pflat += (size_t)(prev + 1) * md.n_in;
             md.X0 = stage_x0[m];
             for (int k = 0; k < md.L; ++k) md.E.push_back(act_B(md.hs[k], true));
@@ -498,7 +580,7 @@ void plan_memory(avae_handle* h) {
             md.Z = act_B(nz, false);
             md.dH = act_B(2 * nz, false);
             md.dO = act_B(md.n_in, false);
-            const bool no_impl = std::getenv("AVAE_NO_IMPLICIT") != nullptr;
+            const bool no_impl = sw.no_implicit;
             auto stage = [&](int IH, int Cin_in, int OH, int Cout, int k, int so, int d, int pad, bool bias, int act, int flat, bool plain_out, bool has_dgrad) {
                 ConvStage st;
                 // whole 16-byte chunks of channels per tap where that takes a few zero channels (the first decoder stage reads z: n_z
@@ -509,10 +591,9 @@ void plan_memory(avae_handle* h) {
                 st.g = ConvGeom{B, IH, IH, Cin, OH, OH, k, so, d, pad, 0, 0, bias ? 1 : 0};
                 st.bias = bias; st.act = act; st.flat = flat;
                 const int K = k * k * Cin, rows = B * OH * OH;
-                st.d = make_dense(b, pint, K, Cout, KU, es, flat == 3);
-                st.P = make_act(b, K, bias, rows, KU, es);
-                const bool thin = Cout == 1 && plain_out && flat == 1 && IH > 1 && IH * IH * Cin <= kThinIn && OH * OH <= kThinOut && K + 1 <= kThinF &&
-                                  !std::getenv("AVAE_NO_THIN");
+                st.d = make_dense(b, pint, K, Cout, KU, es, spread, flat == 3);
+                st.P = make_act(b, K, bias, rows, KU, es, spread);
+                const bool thin = Cout == 1 && plain_out && flat == 1 && IH > 1 && IH * IH * Cin <= kThinIn && OH * OH <= kThinOut && K + 1 <= kThinF && !sw.no_thin;
                 // (the dense layer behind the flattened 28x28 map, flat == 2, is never a conv: it reads the map as stored -- dense_map -- or its flatten gather)
                 // (row -> (image, pixel) by magic-number division: exact while rows x pixels-per-image < 2^32)
                 const bool fits = (uint64_t)rows * (uint64_t)(OH * OH) < (1ull << 32) && (uint64_t)B * IH * IH * (uint64_t)(IH * IH) < (1ull << 32);
@@ -529,8 +610,7 @@ void plan_memory(avae_handle* h) {
                     //   DT transposed convs   round 2's adjoint-frame route (scatter product + overlap-add, Padj for both gradients);
                     //                         their implicit input gradient alone ("DT:b": 8.3 us vs 5.9 with Padj at hand) 0.2436
                     // Letters f / w / b = forward / filter gradient / input gradient; AVAE_IMPL_POLICY overrides (A/B runs, tests).
-                    const char* pol = std::getenv("AVAE_IMPL_POLICY");
-                    const std::string policy = pol ? pol : "E:fw,H:fwb,D1:fwb,DT:";
+                    const std::string& policy = sw.impl_policy;      // (default "E:fw,H:fwb,D1:fwb,DT:")
                     const std::string cls = flat == 0 ? "E" : flat == 3 ? "H" : (flat == 1 && IH == 1) ? "D1" : flat == 1 ? "DT" : "X";
                     std::string letters;
                     for (size_t pos = 0; pos < policy.size();) {
@@ -557,12 +637,12 @@ void plan_memory(avae_handle* h) {
                     // reads its input.  AVAE_NO_IMPLICIT keeps round 2's compact 8-elements-per-pixel layout + flatten gather.)
                     st.dense_map = thin && OH == 28 && !no_impl;
                     if (st.dense_map) {
-                        st.Y = make_act(b, OH * OH, true, B, KU, es);
-                        st.dY = make_act(b, OH * OH, false, B, KU, es);
+                        st.Y = make_act(b, OH * OH, true, B, KU, es, spread);
+                        st.dY = make_act(b, OH * OH, false, B, KU, es, spread);
                     } else {
                         const int compact = thin && OH == 28 ? 8 : 0;
-                        st.Y = make_act(b, Cout, false, rows, KU, es, compact);
-                        st.dY = make_act(b, Cout, false, rows, KU, es, compact);
+                        st.Y = make_act(b, Cout, false, rows, KU, es, spread, compact);
+                        st.dY = make_act(b, Cout, false, rows, KU, es, spread, compact);
                     }
                 }
                 st.lddp = (int)rup(K, 8);
@@ -580,9 +660,9 @@ void plan_memory(avae_handle* h) {
                 // transposed convs that upsample (d > 1) or pad heavily have an OUTPUT far larger than their input: the fp32 patch
                 // gradients [B*OH*OW][k*k*Cin] of the plain path (160 MB for 7x7x32 -> 14x14x16) are replaced by the compute-type
                 // patch matrix of the output gradient, [B*IH*IW][k*k*Cout] (11 MB), times the adjoint filter
-                if (flat == 1 && plain_out && !thin && !st.impl && IH > 1 && Cout <= 64 && (long)IH * IH * Cout < (long)OH * OH * Cin * 2 && !std::getenv("AVAE_NO_ADJ")) {
+                if (flat == 1 && plain_out && !thin && !st.impl && IH > 1 && Cout <= 64 && (long)IH * IH * Cout < (long)OH * OH * Cin * 2 && !sw.no_adj) {
                     st.adj = true;
-                    st.Padj = make_act(b, k * k * Cout, false, B * IH * IH, KU, es);
+                    st.Padj = make_act(b, k * k * Cout, false, B * IH * IH, KU, es, spread);
                     st.ldadj = (int)rup(k * k * Cout, KU);
                     st.Wadj = b.take(rup(Cin, kRowAlign) * (size_t)st.ldadj * es);
                     const int KA = k * k * Cout, rin = B * IH * IH;
@@ -611,7 +691,7 @@ void plan_memory(avae_handle* h) {
                 if (thin) {
                     st.thin = true;
                     st.thin_kp = (int)rup(K + 1, 4);
-                    st.thin_blocks = B * thin_split(st.g, 2);      // filter-gradient partial sums: one slice per workgroup
+                    st.thin_blocks = B * thin_split(sw, st.g, 2);      // filter-gradient partial sums: one slice per workgroup
                     st.thin_part = b.take((size_t)st.thin_blocks * st.thin_kp * 4);
                 }
                 pflat += (size_t)k * k * Cin_in * Cout + (flat == 0 ? 0 : Cout);
@@ -892,7 +972,7 @@ struct Builder {
         t.act = st.act; t.act_in = prev.act;
         t.dY = p<void>(st.dY.rm); t.lddy = st.dY.ld;
         if (st.dense_map) { t.img_y = st.Y.ld; t.ldy = 1; t.img_dy = st.dY.ld; t.lddy = 1; }      // dense rows: pixel stride 1, image stride = row stride
-        t.split = thin_split(st.g, 0); t.fast = thin_fast(st.g) ? 1 : 0;      // (the training launches set the split of their mode: thin_launch)
+        t.split = thin_split(h->sw, st.g, 0); t.fast = thin_fast(h->sw, st.g) ? 1 : 0;      // (the training launches set the split of their mode: thin_launch)
         t.dX = p<void>(prev.dY.rm); t.lddx = prev.dY.ld;
         t.part = p<float>(st.thin_part); t.Kp = st.thin_kp;
         return t;
@@ -1038,10 +1118,8 @@ struct Builder {
 
 inline bool is_gemm(int kind) { return kind <= K_WGRAD || kind == K_DGRAD_F32 || kind == K_SERVE_Z; }
 
-// Fixes the tile configuration of one launch and lays its items' tiles out back to back.
-Launch finish_launch(avae_handle* h, std::vector<WorkItem>& items, int first, int count, const std::string& name, int* next_slot) {
-    Launch L;
-    L.name = name; L.first = first; L.count = count;
+// finish_launch, step 1: the tile configuration of a launch of items [first, first + count) -- a function of the items and the switches.
+TileCfg choose_cfg(const std::vector<WorkItem>& items, int first, int count, const PlanSwitches& sw) {
     bool need128 = false, narrow = false;
     long tiles128 = 0;
     for (int i = first; i < first + count; ++i) {
@@ -1050,20 +1128,20 @@ Launch finish_launch(avae_handle* h, std::vector<WorkItem>& items, int first, in
         if (is_gemm(w.kind)) tiles128 += (long)((w.M + 127) / 128) * ((w.N + 127) / 128);
         if (is_gemm(w.kind) && (w.N <= 64 || w.M <= 64 || w.conv > 0)) narrow = true;      // a 128-wide tile would be mostly padding (implicit patch matrices: small tiles only)
     }
-    L.cfg = (need128 || (tiles128 >= 192 && !narrow)) ? 1 : 0;
+    TileCfg cfg = (need128 || (tiles128 >= 192 && !narrow)) ? k128x128 : k64x64;
     {   // 256x128 tiles, 8 waves, one workgroup per CU: a third more flops per operand byte pulled from L2 into LDS,
         // and that fill rate (~60-70 GB/s per CU) is what bounds the 128x128 loop.  Plain single-C-tile kinds on big
         // problems only.  (AVAE_NO_256=1 keeps the 128x128 kernel: A/B measurements.)
-        bool plain = std::getenv("AVAE_NO_256") == nullptr;
+        bool plain = !sw.no_256;
         long tiles256 = 0;
         for (int i = first; i < first + count; ++i) {
             const WorkItem& w = items[i];
             plain = plain && (w.kind == K_FWD_HIDDEN || w.kind == K_DGRAD_HIDDEN || w.kind == K_WGRAD);
             tiles256 += (long)((w.M + 255) / 256) * ((w.N + 127) / 128);
         }
-        if (L.cfg == 1 && plain && tiles256 >= 192) L.cfg = 2;
+        if (cfg == k128x128 && plain && tiles256 >= 192) cfg = k256x128;
     }
-    if (L.cfg == 0 && !std::getenv("AVAE_NO_32")) {      // few 64x64 tiles: half-height tiles put twice the CUs on the launch
+    if (cfg == k64x64 && !sw.no_32) {      // few 64x64 tiles: half-height tiles put twice the CUs on the launch
         long t64 = 0;
         bool nt = true;
         for (int i = first; i < first + count; ++i) {
@@ -1071,28 +1149,28 @@ Launch finish_launch(avae_handle* h, std::vector<WorkItem>& items, int first, in
             if (is_gemm(w.kind)) t64 += (long)((w.M + 63) / 64) * ((w.N + 63) / 64);
             nt = nt && w.kind != K_WGRAD && w.kind != K_DGRAD_F32;
         }
-        if (nt && t64 > 0 && t64 <= 128) L.cfg = 3;
+        if (nt && t64 > 0 && t64 <= 128) cfg = k32x64;
         bool head = false;
         for (int i = first; i < first + count; ++i) head = head || items[i].kind == K_FWD_HEAD || items[i].kind == K_DGRAD_LATENT || items[i].kind == K_SERVE_Z;
-        if (L.cfg == 3 && !head && !std::getenv("AVAE_NO_32x32")) L.cfg = 5;      // no kind that needs 2*n_z columns in one tile
-        if (L.cfg == 5 && !std::getenv("AVAE_NO_LEAN")) {       // the chain's two kinds, one of them (and one transfer function) per launch: the lean kernel (k_small)
+        if (cfg == k32x64 && !head && !sw.no_32x32) cfg = k32x32;      // no kind that needs 2*n_z columns in one tile
+        if (cfg == k32x32 && !sw.no_lean) {       // the chain's two kinds, one of them (and one transfer function) per launch: the lean kernel (k_small)
             bool lean = true;
             const int k0 = items[first].kind, a0 = items[first].act;
             for (int i = first; i < first + count; ++i)
                 lean = lean && items[i].kind == k0 && items[i].act == a0 && !items[i].bias_ep && items[i].K > 0 && items[i].conv == 0;
-            if (lean && (k0 == K_FWD_HIDDEN || k0 == K_DGRAD_HIDDEN)) L.cfg = 7;
+            if (lean && (k0 == K_FWD_HIDDEN || k0 == K_DGRAD_HIDDEN)) cfg = kLean;
             bool store = true;                                    // the inference / serving output launch: k_small's third kind
             for (int i = first; i < first + count; ++i) store = store && items[i].kind == K_FWD_OUT_STORE && !items[i].bias_ep && items[i].K > 0 && items[i].conv == 0;
-            if (store) L.cfg = 7;
+            if (store) cfg = kLean;
             bool loss = false, only_loss = true;                  // the output + loss launch (with the latent item riding in it): k_small_loss
             for (int i = first; i < first + count; ++i) {
                 loss = loss || items[i].kind == K_FWD_OUT_LOSS;
                 only_loss = only_loss && ((items[i].kind == K_FWD_OUT_LOSS && !items[i].bias_ep && items[i].K > 0 && items[i].conv == 0) || items[i].kind == K_LATENT);
             }
-            if (L.cfg == 5 && loss && only_loss && !std::getenv("AVAE_NO_LEAN_LOSS")) L.cfg = 9;
+            if (cfg == k32x32 && loss && only_loss && !sw.no_lean_loss) cfg = kLeanLoss;
         }
     }
-    if (L.cfg == 1 && need128 && !std::getenv("AVAE_NO_64x128")) {      // wide-latent head launches: few tiles, K loop = load latency
+    if (cfg == k128x128 && need128 && !sw.no_64x128) {      // wide-latent head launches: few tiles, K loop = load latency
         long t = 0;
         bool nt = true;
         for (int i = first; i < first + count; ++i) {
@@ -1100,33 +1178,40 @@ Launch finish_launch(avae_handle* h, std::vector<WorkItem>& items, int first, in
             if (is_gemm(w.kind)) t += (long)((w.M + 63) / 64) * ((w.N + 127) / 128);
             nt = nt && w.kind != K_WGRAD && w.kind != K_DGRAD_F32;
         }
-        if (nt && t <= 256) L.cfg = 4;
+        if (nt && t <= 256) cfg = k64x128;
     }
-    if (L.cfg == 1 && !std::getenv("AVAE_NO_LOSS8")) {      // the output + loss launch of the big nets: 256x64 tiles, 8 waves, register epilogue
+    if (cfg == k128x128 && !sw.no_loss8) {      // the output + loss launch of the big nets: 256x64 tiles, 8 waves, register epilogue
         long t = 0;
         bool loss_only = true;
         for (int i = first; i < first + count; ++i) {
             const WorkItem& w = items[i];
             if (is_gemm(w.kind)) { loss_only = loss_only && w.kind == K_FWD_OUT_LOSS; t += (long)((w.M + 255) / 256) * ((w.N + 63) / 64); }
         }
-        if (loss_only && t >= 192) L.cfg = 6;
+        if (loss_only && t >= 192) cfg = k256x64Loss;
     }
     for (int i = first; i < first + count; ++i)
-        if (items[i].conv > 0 && !(L.cfg == 0 || L.cfg == 3 || L.cfg == 5)) throw Err("internal error: an implicit patch matrix on a tile configuration without the gather");
-    const int T = (L.cfg == 1 || L.cfg == 2 || L.cfg == 4) ? 128 : (L.cfg == 5 || L.cfg == 7 || L.cfg == 9) ? 32 : 64;
-    const int TM = (L.cfg == 2 || L.cfg == 6) ? 256 : (L.cfg == 3 || L.cfg == 5 || L.cfg == 7 || L.cfg == 9) ? 32 : L.cfg == 4 ? 64 : T;
-    if ((L.cfg == 2 || L.cfg == 6) && !std::getenv("AVAE_NO_BIAS_EP"))      // 8-wave NT tiles: bias in the epilogue where that saves a K tile
-        for (int i = first; i < first + count; ++i) {
-            WorkItem& w = items[i];
-            if ((w.kind == K_FWD_HIDDEN || w.kind == K_FWD_OUT_LOSS) && w.kin > 0 && w.kin % h->KU == 0 && w.K == w.kin + h->KU) { w.K = w.kin; w.bias_ep = 1; }
-        }
+        if (items[i].conv > 0 && !tile_geom(cfg).gather) throw Err("internal error: an implicit patch matrix on a tile configuration without the gather");
+    return cfg;
+}
+
+// step 2 (8-wave NT tiles): the bias moves into the epilogue where that saves a K tile
+void fold_bias_epilogue(std::vector<WorkItem>& items, int first, int count, int KU) {
+    for (int i = first; i < first + count; ++i) {
+        WorkItem& w = items[i];
+        if ((w.kind == K_FWD_HIDDEN || w.kind == K_FWD_OUT_LOSS) && w.kin > 0 && w.kin % KU == 0 && w.K == w.kin + KU) { w.K = w.kin; w.bias_ep = 1; }
+    }
+}
+
+// step 3: the items' tiles on the configuration's tile shape and their cost-partial slots; returns the longest item's tile count
+int layout_tiles(std::vector<WorkItem>& items, int first, int count, TileCfg cfg, const PlanSwitches& sw, int* next_slot) {
+    const int T = tile_geom(cfg).cols, TM = tile_geom(cfg).rows;
     int max_tiles = 1;
     for (int i = first; i < first + count; ++i) {
         WorkItem& w = items[i];
         if (is_gemm(w.kind)) {
             if (w.bias_row >= 0) {       // (< 0: a product without a bias row, e.g. the adjoint-frame filter gradients)
                 w.bias_row = 0;
-                if (w.kind == K_WGRAD && w.M > 1 && (w.M - 1) % TM == 0 && !std::getenv("AVAE_NO_BIAS_MFMA")) w.bias_row = w.M - 1;
+                if (w.kind == K_WGRAD && w.M > 1 && (w.M - 1) % TM == 0 && !sw.no_bias_mfma) w.bias_row = w.M - 1;
             }
             w.tiles_m = (w.M - (w.bias_row > 0 ? 1 : 0) + TM - 1) / TM;
             w.tiles_n = (w.N + T - 1) / T;
@@ -1141,87 +1226,111 @@ Launch finish_launch(avae_handle* h, std::vector<WorkItem>& items, int first, in
         }
         max_tiles = std::max(max_tiles, w.tiles_m * w.tiles_n * (w.kind == K_WGRAD && w.ksplit > 1 ? w.ksplit : 1));
     }
+    return max_tiles;
+}
+
+// step 4 (weight-gradient launches): the entry table of L.targs.  The grid is (longest entry) x (entries), so layers of very
+// different size would make it mostly padding workgroups (C2: 1248 workgroups for 416 tiles).  Items are therefore cut into
+// entries of at most SX tiles, SX chosen to launch the fewest workgroups within the entry table's size.  Returns the entry
+// count; *G = the XCD group, *SX = the slice width.
+int wgrad_entries(Launch& L, const std::vector<WorkItem>& items, const PlanSwitches& sw, int* G_out, int* SX_out) {
+    const int first = L.first, count = L.count;
+    // big weight gradients: concentrate each item on 8/G XCDs (the launch is bound by L2 misses); G must leave no XCD
+    // without an item, so it divides the item count
+    int G = 1;
+    if (L.cfg == k256x128) for (int g : {4, 2}) if (count % g == 0) { G = g; break; }
+    if (sw.tn_g_set) G = sw.tn_g;
+    if (G != 1 && G != 2 && G != 4 && G != 8) throw Err("AVAE_TN_G must be 1, 2, 4 or 8");
+    auto tiles_of = [&](const WorkItem& w) { return w.tiles_m * w.tiles_n * (w.ksplit > 1 ? w.ksplit : 1); };
+    int SX = L.grid_x;
+    if (G == 1 && !sw.no_tn_slices) {
+        long best = -1;
+        for (int sx = 8; sx <= L.grid_x; sx += 8) {
+            long entries = 0;
+            for (int i = first; i < first + count; ++i) entries += (tiles_of(items[i]) + sx - 1) / sx;
+            if (entries > kMaxTnItems) continue;
+            if (best < 0 || entries * sx <= best) { best = entries * sx; SX = sx; }
+        }
+    }
+    int n = 0;
+    for (int i = 0; i < count; ++i) {
+        const WorkItem& w = items[first + i];
+        const int nt = tiles_of(w);
+        for (int off = 0; off < nt; off += SX) {
+            if (n >= kMaxTnItems) throw Err("internal error: too many weight-gradient entries");
+            TnItem& t = L.targs.items[n++];
+            t.A = w.A; t.B = w.B; t.out = reinterpret_cast<float*>(w.ksplit > 1 ? w.out1 : w.out0);
+            t.bias_row = std::max(w.bias_row, 0);
+            t.M = w.bias_row > 0 ? w.M - 1 : w.M; t.N = w.N; t.K = w.K; t.lda = w.lda; t.ldb = w.ldb; t.ld0 = w.ld0;
+            t.tiles_m = w.tiles_m; t.tiles_n = w.tiles_n; t.ksplit = w.ksplit; t.kchunk = w.kchunk;
+            t.tile_off = off; t.tile_cnt = std::min(SX, nt - off); t.conv = w.conv;
+        }
+    }
+    *G_out = G; *SX_out = SX;
+    return n;
+}
+
+// step 5 (G > 1): entries over the XCD groups.  Returns the new entry count; *G may drop from 4 to 2.
+int balance_xcd_groups(Launch& L, int n, const PlanSwitches& sw, int* G_io) {
+    int G = *G_io;
+    // Entry y of a group of G runs on XCDs [ (y % G) * 8/G, ... ): its position decides WHERE its tiles run.  Layers
+    // differ in size (C4: 32, 28, 8 and 4 tiles), and in plan order two of the four XCD pairs end up with 66 tiles per
+    // XCD -- a third round of 62 us for four tiles on a 32-CU XCD (195 us; the other XCDs are done after 138).  Longest
+    // first onto the lightest position balances the positions; G = 4 or 2 by the fewest rounds that leaves.
+    std::vector<TnItem> ent(L.targs.items, L.targs.items + n);
+    std::stable_sort(ent.begin(), ent.end(), [](const TnItem& a, const TnItem& b) { return a.tile_cnt > b.tile_cnt; });
+    auto pack = [&](int g, std::vector<std::vector<TnItem>>& bins) {
+        bins.assign(g, {});
+        std::vector<long> load(g, 0);
+        const int cap = kMaxTnItems / g;
+        for (const TnItem& e : ent) {
+            int best = -1;
+            for (int p = 0; p < g; ++p) if ((int)bins[p].size() < cap && (best < 0 || load[p] < load[best])) best = p;
+            bins[best].push_back(e); load[best] += e.tile_cnt;
+        }
+        const long per_xcd = (*std::max_element(load.begin(), load.end()) * g + 7) / 8;
+        return (per_xcd + 31) / 32;                       // rounds on a 32-CU XCD at one workgroup per CU
+    };
+    std::vector<std::vector<TnItem>> bins, bins2;
+    if (!sw.tn_g_set && G == 4 && n * 2 <= kMaxTnItems * 2) {
+        const long r4 = pack(4, bins), r2 = pack(2, bins2);
+        if (r2 < r4) { G = 2; bins.swap(bins2); }
+    } else {
+        pack(G, bins);
+    }
+    size_t groups = 0;
+    for (const auto& bn : bins) groups = std::max(groups, bn.size());
+    std::memset(L.targs.items, 0, sizeof(L.targs.items));
+    for (size_t g = 0; g < groups; ++g)
+        for (int p = 0; p < G; ++p) if (g < bins[p].size()) L.targs.items[g * G + p] = bins[p][g];      // holes: tile_cnt 0
+    n = (int)groups * G;
+    *G_io = G;
+    return n;
+}
+
+// Fixes the tile configuration of one launch and lays its items' tiles out back to back.
+Launch finish_launch(avae_handle* h, std::vector<WorkItem>& items, int first, int count, const std::string& name, int* next_slot) {
+    const PlanSwitches& sw = h->sw;
+    Launch L;
+    L.name = name; L.first = first; L.count = count;
+    L.cfg = choose_cfg(items, first, count, sw);
+    if (tile_geom(L.cfg).waves8 && !sw.no_bias_ep) fold_bias_epilogue(items, first, count, h->KU);
+    const int max_tiles = layout_tiles(items, first, count, L.cfg, sw, next_slot);
     // grid: x = tile slot (multiple of 8: the kernel's XCD-aware tile order needs it), y = item
     L.grid_x = (max_tiles + 7) & ~7; L.grid_y = count;
     L.blocks = L.grid_x * L.grid_y;
-    {
-        bool two = false;
-        for (int i = first; i < first + count; ++i) two = two || items[i].kind == K_FWD_HEAD || items[i].kind == K_DGRAD_LATENT || items[i].kind == K_SERVE_Z;
-        L.lds = L.cfg == 7 ? 4 * 64 * kTileBytesK : L.cfg == 9 ? 4 * 64 * kTileBytesK + 64 : tile_lds_bytes(L.cfg, two);
-    }
+    bool two = false;
+    for (int i = first; i < first + count; ++i) two = two || items[i].kind == K_FWD_HEAD || items[i].kind == K_DGRAD_LATENT || items[i].kind == K_SERVE_Z;
+    L.lds = L.cfg == kLean ? tile_ring_bytes(kLean) : L.cfg == kLeanLoss ? tile_ring_bytes(kLeanLoss) + 64 : tile_lds_bytes(L.cfg, two);
     L.tn = true;
     for (int i = first; i < first + count; ++i) L.tn = L.tn && items[i].kind == K_WGRAD;
     if (count > (L.tn ? kMaxTnItems : kMaxItemsPerLaunch)) throw Err("internal error: too many items in one launch");
     std::memset(&L.args, 0, sizeof(L.args));
     std::memset(&L.targs, 0, sizeof(L.targs));
     if (L.tn) {
-        // big weight gradients: concentrate each item on 8/G XCDs (the launch is bound by L2 misses); G must leave no XCD
-        // without an item, so it divides the item count
-        int G = 1;
-        if (L.cfg == 2) for (int g : {4, 2}) if (count % g == 0) { G = g; break; }
-        if (const char* e = std::getenv("AVAE_TN_G")) G = std::atoi(e);
-        if (G != 1 && G != 2 && G != 4 && G != 8) throw Err("AVAE_TN_G must be 1, 2, 4 or 8");
-        auto tiles_of = [&](const WorkItem& w) { return w.tiles_m * w.tiles_n * (w.ksplit > 1 ? w.ksplit : 1); };
-        // The grid is (longest entry) x (entries), so layers of very different size would make it mostly padding
-        // workgroups (C2: 1248 workgroups for 416 tiles).  Items are therefore cut into entries of at most SX tiles, SX
-        // chosen to launch the fewest workgroups within the entry table's size.
-        int SX = L.grid_x;
-        if (G == 1 && !std::getenv("AVAE_NO_TN_SLICES")) {
-            long best = -1;
-            for (int sx = 8; sx <= L.grid_x; sx += 8) {
-                long entries = 0;
-                for (int i = first; i < first + count; ++i) entries += (tiles_of(items[i]) + sx - 1) / sx;
-                if (entries > kMaxTnItems) continue;
-                if (best < 0 || entries * sx <= best) { best = entries * sx; SX = sx; }
-            }
-        }
-        int n = 0;
-        for (int i = 0; i < count; ++i) {
-            const WorkItem& w = items[first + i];
-            const int nt = tiles_of(w);
-            for (int off = 0; off < nt; off += SX) {
-                if (n >= kMaxTnItems) throw Err("internal error: too many weight-gradient entries");
-                TnItem& t = L.targs.items[n++];
-                t.A = w.A; t.B = w.B; t.out = reinterpret_cast<float*>(w.ksplit > 1 ? w.out1 : w.out0);
-                t.bias_row = std::max(w.bias_row, 0);
-                t.M = w.bias_row > 0 ? w.M - 1 : w.M; t.N = w.N; t.K = w.K; t.lda = w.lda; t.ldb = w.ldb; t.ld0 = w.ld0;
-                t.tiles_m = w.tiles_m; t.tiles_n = w.tiles_n; t.ksplit = w.ksplit; t.kchunk = w.kchunk;
-                t.tile_off = off; t.tile_cnt = std::min(SX, nt - off); t.conv = w.conv;
-            }
-        }
-        if (G > 1 && !std::getenv("AVAE_NO_TN_BALANCE")) {
-            // Entry y of a group of G runs on XCDs [ (y % G) * 8/G, ... ): its position decides WHERE its tiles run.  Layers
-            // differ in size (C4: 32, 28, 8 and 4 tiles), and in plan order two of the four XCD pairs end up with 66 tiles per
-            // XCD -- a third round of 62 us for four tiles on a 32-CU XCD (195 us; the other XCDs are done after 138).  Longest
-            // first onto the lightest position balances the positions; G = 4 or 2 by the fewest rounds that leaves.
-            std::vector<TnItem> ent(L.targs.items, L.targs.items + n);
-            std::stable_sort(ent.begin(), ent.end(), [](const TnItem& a, const TnItem& b) { return a.tile_cnt > b.tile_cnt; });
-            auto pack = [&](int g, std::vector<std::vector<TnItem>>& bins) {
-                bins.assign(g, {});
-                std::vector<long> load(g, 0);
-                const int cap = kMaxTnItems / g;
-                for (const TnItem& e : ent) {
-                    int best = -1;
-                    for (int p = 0; p < g; ++p) if ((int)bins[p].size() < cap && (best < 0 || load[p] < load[best])) best = p;
-                    bins[best].push_back(e); load[best] += e.tile_cnt;
-                }
-                const long per_xcd = (*std::max_element(load.begin(), load.end()) * g + 7) / 8;
-                return (per_xcd + 31) / 32;                       // rounds on a 32-CU XCD at one workgroup per CU
-            };
-            std::vector<std::vector<TnItem>> bins, bins2;
-            if (!std::getenv("AVAE_TN_G") && G == 4 && n * 2 <= kMaxTnItems * 2) {
-                const long r4 = pack(4, bins), r2 = pack(2, bins2);
-                if (r2 < r4) { G = 2; bins.swap(bins2); }
-            } else {
-                pack(G, bins);
-            }
-            size_t groups = 0;
-            for (const auto& bn : bins) groups = std::max(groups, bn.size());
-            std::memset(L.targs.items, 0, sizeof(L.targs.items));
-            for (size_t g = 0; g < groups; ++g)
-                for (int p = 0; p < G; ++p) if (g < bins[p].size()) L.targs.items[g * G + p] = bins[p][g];      // holes: tile_cnt 0
-            n = (int)groups * G;
-        }
+        int G = 1, SX = L.grid_x;
+        int n = wgrad_entries(L, items, sw, &G, &SX);
+        if (G > 1 && !sw.no_tn_balance) n = balance_xcd_groups(L, n, sw, &G);
         L.grid_x = SX;
         L.targs.n_items = n;
         L.targs.grid_x = L.grid_x;
@@ -1234,7 +1343,7 @@ Launch finish_launch(avae_handle* h, std::vector<WorkItem>& items, int first, in
         for (int i = 0; i < count; ++i) L.args.items[i] = items[first + i];
     }
     L.args.conv_tab = L.targs.conv_tab = h->at<ConvA>(h->off_conv_tab);
-    if (const char* e = std::getenv("AVAE_SCHED")) L.args.sched = L.targs.sched = std::atoi(e);
+    L.args.sched = L.targs.sched = sw.sched;
     if (*next_slot > h->n_partial) throw Err("internal error: cost partial slots overflow");
     return L;
 }
@@ -1314,123 +1423,111 @@ struct Groups {
     }
 };
 
-void build_training_plan(avae_handle* h) {
-    h->items.clear(); h->plain.fwd.clear(); h->bwd.clear(); h->wgrad.clear(); h->conv_tab.clear();
-    Builder bd(h, h->items, h->B, true);
-    Groups group{h, h->items};
-    int Lmax = 0;
-    for (const Mod& md : h->mods) Lmax = std::max(Lmax, md.L);
-    // Small nets: the launch that follows the heads (the decoder's first layer, K = n_z + 1) and the one that follows bwd_dec1_latent
-    // (the heads' input gradient, K = 2 n_z) multiply over one or two K tiles and are pure launch overhead (4.3 us each on C2).  When the
-    // producing launch runs on 32x64 tiles they become the tail product of its items (WorkItem::tail_*) and disappear.  The weights
-    // they read are final since the previous step's Adam, their inputs exist only in the producing workgroup -- nothing else changes.
-    auto fuse_tail = [&](std::vector<Launch>& ls, int mode) {
-        if (ls.size() < 2 || std::getenv("AVAE_NO_TAIL")) return false;
-        Launch& Lp = ls[ls.size() - 2];          // producer: fwd_head / bwd_dec1_latent
-        Launch& Lc = ls[ls.size() - 1];          // consumer: one K tile
-        if (Lp.type != 0 || Lc.type != 0 || Lp.tn || Lc.tn || Lp.cfg != 3) return false;
-        const int want_p = mode == 1 ? K_FWD_HEAD : K_DGRAD_LATENT, want_c = mode == 1 ? K_FWD_HIDDEN : K_DGRAD_HIDDEN;
-        std::vector<int> prod(Lc.count, -1);
-        for (int i = 0; i < Lc.count; ++i) {
-            const WorkItem& c = h->items[Lc.first + i];
-            if (c.kind != want_c || c.bias_ep || c.K > 2 * h->KU || c.N > 1024) return false;      // (the narrow result is one 64-column tile)
-            for (int k = 0; k < Lp.count; ++k) {
-                const WorkItem& n = h->items[Lp.first + k];
-                if (n.kind != want_p || n.M != c.M) continue;
-                const void* res = mode == 1 ? n.out1 : n.out0;
-                const int ldres = mode == 1 ? n.ld1 : n.ld0;
-                if (res && res == c.A && ldres == c.lda) prod[i] = k;
-            }
-            if (prod[i] < 0) return false;
+// Small nets: the launch that follows the heads (the decoder's first layer, K = n_z + 1) and the one that follows bwd_dec1_latent
+// (the heads' input gradient, K = 2 n_z) multiply over one or two K tiles and are pure launch overhead (4.3 us each on C2).  When the
+// producing launch runs on 32x64 tiles they become the tail product of its items (WorkItem::tail_*) and disappear.  The weights
+// they read are final since the previous step's Adam, their inputs exist only in the producing workgroup -- nothing else changes.
+bool fuse_tail(avae_handle* h, std::vector<Launch>& ls, int mode) {
+    if (ls.size() < 2 || h->sw.no_tail) return false;
+    Launch& Lp = ls[ls.size() - 2];          // producer: fwd_head / bwd_dec1_latent
+    Launch& Lc = ls[ls.size() - 1];          // consumer: one K tile
+    if (Lp.type != kGrouped || Lc.type != kGrouped || Lp.tn || Lc.tn || Lp.cfg != k32x64) return false;
+    const int want_p = mode == 1 ? K_FWD_HEAD : K_DGRAD_LATENT, want_c = mode == 1 ? K_FWD_HIDDEN : K_DGRAD_HIDDEN;
+    std::vector<int> prod(Lc.count, -1);
+    for (int i = 0; i < Lc.count; ++i) {
+        const WorkItem& c = h->items[Lc.first + i];
+        if (c.kind != want_c || c.bias_ep || c.K > 2 * h->KU || c.N > 1024) return false;      // (the narrow result is one 64-column tile)
+        for (int k = 0; k < Lp.count; ++k) {
+            const WorkItem& n = h->items[Lp.first + k];
+            if (n.kind != want_p || n.M != c.M) continue;
+            const void* res = mode == 1 ? n.out1 : n.out0;
+            const int ldres = mode == 1 ? n.ld1 : n.ld0;
+            if (res && res == c.A && ldres == c.lda) prod[i] = k;
         }
-        for (int i = 0; i < Lc.count; ++i) {
-            const WorkItem c = h->items[Lc.first + i];
-            for (WorkItem* n : {&h->items[Lp.first + prod[i]], &Lp.args.items[prod[i]]}) {
-                n->tail_mode = mode; n->tail_w = c.B; n->tail_ldw = c.ldb; n->tail_n = c.N; n->tail_out = c.out0; n->tail_ldo = c.ld0;
-                n->tail_aux = c.aux0; n->tail_ldx = c.ldx; n->tail_act = c.act; n->tail_kt = c.K / h->KU;
-                n->tiles_n = (c.N + 63) / 64;                    // tail slices of 64 columns, a workgroup each
-            }
+        if (prod[i] < 0) return false;
+    }
+    for (int i = 0; i < Lc.count; ++i) {
+        const WorkItem c = h->items[Lc.first + i];
+        for (WorkItem* n : {&h->items[Lp.first + prod[i]], &Lp.args.items[prod[i]]}) {
+            n->tail_mode = mode; n->tail_w = c.B; n->tail_ldw = c.ldb; n->tail_n = c.N; n->tail_out = c.out0; n->tail_ldo = c.ld0;
+            n->tail_aux = c.aux0; n->tail_ldx = c.ldx; n->tail_act = c.act; n->tail_kt = c.K / h->KU;
+            n->tiles_n = (c.N + 63) / 64;                    // tail slices of 64 columns, a workgroup each
         }
-        int max_tiles = 1;
-        for (int k = 0; k < Lp.count; ++k) max_tiles = std::max(max_tiles, h->items[Lp.first + k].tiles_m * h->items[Lp.first + k].tiles_n);
-        Lp.grid_x = (max_tiles + 7) & ~7; Lp.blocks = Lp.grid_x * Lp.grid_y; Lp.args.grid_x = Lp.grid_x;
-        Lp.name += "+" + Lc.name;
-        ls.pop_back();
-        // the lean frame for the fused head launches (k_small_latb): every GEMM item of the kind, one transfer function, its narrow result and
-        // the consumer's K within the 8-KiB image
-        if (!std::getenv("AVAE_NO_LEAN") && !std::getenv("AVAE_NO_LEAN_HEAD")) {
-            bool lean = true;
-            int act = -1;
-            for (int k = 0; k < Lp.count; ++k) {
-                const WorkItem& n = h->items[Lp.first + k];
-                if (n.kind == K_COST) continue;
-                lean = lean && n.kind == want_p && n.tail_mode == mode
-                            && (act < 0 || act == n.tail_act) && n.K > 0 && 2 * n.nz <= 64 && n.tail_kt >= 1 && n.tail_kt <= 2;
-                act = n.tail_act;
-            }
-            if (lean && mode == 1)
-                for (int k = 0; k < Lp.count; ++k) lean = lean && h->items[Lp.first + k].kind == K_FWD_HEAD && h->items[Lp.first + k].out1 != nullptr;
-            if (lean) { Lp.cfg = mode == 2 ? 10 : 11; Lp.lds = small_head_lds_bytes(); Lp.lean_act = act; }
+    }
+    int max_tiles = 1;
+    for (int k = 0; k < Lp.count; ++k) max_tiles = std::max(max_tiles, h->items[Lp.first + k].tiles_m * h->items[Lp.first + k].tiles_n);
+    Lp.grid_x = (max_tiles + 7) & ~7; Lp.blocks = Lp.grid_x * Lp.grid_y; Lp.args.grid_x = Lp.grid_x;
+    Lp.name += "+" + Lc.name;
+    ls.pop_back();
+    // the lean frame for the fused head launches (k_small_latb): every GEMM item of the kind, one transfer function, its narrow result and
+    // the consumer's K within the 8-KiB image
+    if (!h->sw.no_lean && !h->sw.no_lean_head) {
+        bool lean = true;
+        int act = -1;
+        for (int k = 0; k < Lp.count; ++k) {
+            const WorkItem& n = h->items[Lp.first + k];
+            if (n.kind == K_COST) continue;
+            lean = lean && n.kind == want_p && n.tail_mode == mode
+                        && (act < 0 || act == n.tail_act) && n.K > 0 && 2 * n.nz <= 64 && n.tail_kt >= 1 && n.tail_kt <= 2;
+            act = n.tail_act;
         }
-        return true;
-    };
-    // conv-branch helper launches (one segment per conv modality)
-    // (`want`: which conv modalities take part -- stages route per modality: patch-matrix, adjoint-frame or direct)
-    auto every_conv = [](const Mod&) { return true; };
-    auto gather_launch = [&](const std::string& name, std::vector<Launch>& dst, auto&& stage_of, auto&& src_of, auto&& want) {
-        Launch L;
-        L.name = name; L.type = 1;
-        int base = 0;
-        for (Mod& md : h->mods) if (md.conv && want(md)) {
-            GatherSeg g = bd.gather_seg(stage_of(md), src_of(md));
-            g.tile_base = base; base += g.tiles_r * g.tiles_c;
-            L.ga.seg[L.ga.n_seg++] = g;
-        }
-        L.blocks = base;
-        if (base > 0) dst.push_back(L);
-    };
-    auto col2im_launch = [&](const std::string& name, std::vector<Launch>& dst, auto&& stage_of, auto&& prev_of, auto&& want) {
-        Launch L;
-        L.name = name; L.type = 2;
-        int base = 0;
-        for (Mod& md : h->mods) if (md.conv && want(md)) {
-            Col2imSeg c = bd.col2im_seg(stage_of(md), prev_of(md), md);
-            c.tile_base = base; base += c.tiles_r * c.tiles_c;
-            L.ca.seg[L.ca.n_seg++] = c;
-        }
-        L.blocks = base;
-        if (base > 0) dst.push_back(L);
-    };
-    // the decoder's last transposed conv (one output channel) runs as direct kernels: mode 0 forward, 1 input gradient,
-    // 2 filter-gradient partial sums
-    auto thin_launch = [&](const std::string& name, std::vector<Launch>& dst, int mode, int i) {
-        Launch L;
-        L.name = name; L.type = 4;
-        L.ta.mode = mode;
-        int base = 0;
-        for (Mod& md : h->mods) if (md.conv && md.cdec[i].thin) {
-            ThinSeg t = bd.thin_seg(md.cdec[i], md.cdec[i - 1]);
-            t.split = thin_split(md.cdec[i].g, mode);
-            t.block_base = base;
-            base += h->B * t.split;                        // workgroups per image
-            L.ta.seg[L.ta.n_seg++] = t;
-        }
-        L.blocks = base;
-        if (base > 0) dst.push_back(L);
-    };
-    auto is_adj = [&](int i) { bool t = false; for (const Mod& md : h->mods) t = t || (md.conv && i >= 0 && i <= 3 && md.cdec[i].adj); return t; };
-    auto is_thin = [&](int i) { bool t = false; for (const Mod& md : h->mods) t = t || (md.conv && md.cdec[i].thin); return t; };
-    bool any_conv = false;
-    for (const Mod& md : h->mods) any_conv = any_conv || md.conv;
-    // ---- forward.  Modalities with fewer hidden layers simply sit out a launch; data dependencies
-    // are per modality and launches are stream-ordered, so this is always safe.
-    for (int k = 0; k < Lmax; ++k)
-        group("fwd_enc" + std::to_string(k + 1), h->plain.fwd, [&] {
-            for (Mod& md : h->mods) if (k < md.L) h->items.push_back(bd.fwd_hidden(k == 0 ? md.X0 : md.E[k - 1], md.enc[k], md.E[k]));
-        });
-    // Experiment (AVAE_CHAIN2=1): fwd_enc1 and fwd_enc2 of the small nets as ONE launch behind a row-block-local hand-off
-    // (k_chain2) instead of a kernel boundary.  Needs both on the lean 32x32 kernel, equal widths (the same tile grid) and whole quads.
-    if (std::getenv("AVAE_CHAIN2") && !any_conv && h->plain.fwd.size() == 2 && h->plain.fwd[0].cfg == 7 && h->plain.fwd[1].cfg == 7 && h->plain.fwd[0].count == h->plain.fwd[1].count
+        if (lean && mode == 1)
+            for (int k = 0; k < Lp.count; ++k) lean = lean && h->items[Lp.first + k].kind == K_FWD_HEAD && h->items[Lp.first + k].out1 != nullptr;
+        if (lean) { Lp.cfg = mode == 2 ? kLeanLatb : kLeanHead; Lp.lds = small_head_lds_bytes(); Lp.lean_act = act; }
+    }
+    return true;
+}
+
+// conv-branch helper launches (one segment per conv modality)
+// (`want`: which conv modalities take part -- stages route per modality: patch-matrix, adjoint-frame or direct)
+template <typename StageOf, typename SrcOf, typename Want>
+void gather_launch(avae_handle* h, Builder& bd, const std::string& name, std::vector<Launch>& dst, StageOf&& stage_of, SrcOf&& src_of, Want&& want) {
+    Launch L;
+    L.name = name; L.type = kGather;
+    int base = 0;
+    for (Mod& md : h->mods) if (md.conv && want(md)) {
+        GatherSeg g = bd.gather_seg(stage_of(md), src_of(md));
+        g.tile_base = base; base += g.tiles_r * g.tiles_c;
+        L.ga.seg[L.ga.n_seg++] = g;
+    }
+    L.blocks = base;
+    if (base > 0) dst.push_back(L);
+}
+template <typename StageOf, typename PrevOf, typename Want>
+void col2im_launch(avae_handle* h, Builder& bd, const std::string& name, std::vector<Launch>& dst, StageOf&& stage_of, PrevOf&& prev_of, Want&& want) {
+    Launch L;
+    L.name = name; L.type = kCol2im;
+    int base = 0;
+    for (Mod& md : h->mods) if (md.conv && want(md)) {
+        Col2imSeg c = bd.col2im_seg(stage_of(md), prev_of(md), md);
+        c.tile_base = base; base += c.tiles_r * c.tiles_c;
+        L.ca.seg[L.ca.n_seg++] = c;
+    }
+    L.blocks = base;
+    if (base > 0) dst.push_back(L);
+}
+// the decoder's last transposed conv (one output channel) runs as direct kernels: mode 0 forward, 1 input gradient,
+// 2 filter-gradient partial sums
+void thin_launch(avae_handle* h, Builder& bd, const std::string& name, std::vector<Launch>& dst, int mode, int i) {
+    Launch L;
+    L.name = name; L.type = kThin;
+    L.ta.mode = mode;
+    int base = 0;
+    for (Mod& md : h->mods) if (md.conv && md.cdec[i].thin) {
+        ThinSeg t = bd.thin_seg(md.cdec[i], md.cdec[i - 1]);
+        t.split = thin_split(h->sw, md.cdec[i].g, mode);
+        t.block_base = base;
+        base += h->B * t.split;                        // workgroups per image
+        L.ta.seg[L.ta.n_seg++] = t;
+    }
+    L.blocks = base;
+    if (base > 0) dst.push_back(L);
+}
+
+// Experiment (AVAE_CHAIN2=1): fwd_enc1 and fwd_enc2 of the small nets as ONE launch behind a row-block-local hand-off
+// (k_chain2) instead of a kernel boundary.  Needs both on the lean 32x32 kernel, equal widths (the same tile grid) and whole quads.
+void chain_enc12(avae_handle* h) {
+    if (h->plain.fwd.size() == 2 && h->plain.fwd[0].cfg == kLean && h->plain.fwd[1].cfg == kLean && h->plain.fwd[0].count == h->plain.fwd[1].count
         && 2 * h->plain.fwd[0].count <= kMaxItemsPerLaunch) {
         Launch& A = h->plain.fwd[0];
         const Launch& Bn = h->plain.fwd[1];
@@ -1444,449 +1541,274 @@ void build_training_plan(avae_handle* h) {
         if (ok) {
             for (int i = 0; i < A.count; ++i) A.args.items[A.count + i] = Bn.args.items[i];
             A.args.n_items = 2 * A.count;
-            A.cfg = 13; A.name += "+" + Bn.name;
+            A.cfg = kChain2; A.name += "+" + Bn.name;
             h->plain.fwd.pop_back();
         }
     }
-    if (any_conv) {   // conv encoder: three convs, then the flatten + dense heads.  Per modality and stage: implicit GEMM (the patch
-                      // matrix is gathered by the GEMM's own operand loads), or im2col launch + GEMM where the channels are no whole chunks
-        for (int i = 0; i < 3; ++i) {
-            auto src_of = [&, i](Mod& md) { return i == 0 ? h->at<void>(md.X0.rm) : h->at<void>(md.cenc[i - 1].Y.rm); };
-            gather_launch("conv_enc" + std::to_string(i + 1) + "_im2col", h->plain.fwd, [&](Mod& md) -> const ConvStage& { return md.cenc[i]; },
-                          src_of, [i](const Mod& md) { return !md.cenc[i].impl; });
-            group("conv_enc" + std::to_string(i + 1), h->plain.fwd, [&] {
-                for (Mod& md : h->mods) if (md.conv) h->items.push_back(md.cenc[i].impl ? bd.conv_fwd_impl(md.cenc[i], src_of(md)) : bd.conv_fwd(md.cenc[i])); });
+}
+
+// Launches are classified by their names: the conv modality's own launches start with "conv_", and a launch that has taken
+// another one in carries a '+'.
+inline bool is_conv_launch(const Launch& L) { return L.name.compare(0, 5, "conv_") == 0; }
+inline bool is_merged(const Launch& L) { return L.name.find('+') != std::string::npos; }
+
+// ---- mixed models: the MLP modalities' hidden-layer launches (a few tiles, 4-5 us each as launches of their own) ride in plain
+// GEMM launches of the conv modality.  Taken from the end of each chain backwards, a launch SINKS into the LATEST such launch
+// that still runs before the first reader of its outputs -- so a chain enc1 -> enc2 ends up in two consecutive conv launches.
+// Where no such launch lies between a launch and its reader (the backward pass: the MLP modality's dgrad layers come after the
+// conv decoder's), it is HOISTED into the earliest one behind the writer of its input gradient.
+// Safe: every buffer is written once per step, so a product may run any time between its inputs' writers and its readers.
+void sink_and_hoist(avae_handle* h) {
+    auto plain_kind = [](int k) { return k == K_FWD_HIDDEN || k == K_DGRAD_HIDDEN || k == K_DGRAD_F32; };
+    // only launches of the MLP modalities move: an item that writes a conv modality's buffer stays where the plan put it (its readers
+    // include helper launches -- the direct stage, im2col / col2im -- that the dependency scans below do not look into)
+    std::vector<const void*> conv_bufs;
+    for (const Mod& md : h->mods) if (md.conv) {
+        for (const Act* a : {&md.Z, &md.dH, &md.dO}) conv_bufs.push_back(h->at<void>(a->rm));
+        for (const std::vector<ConvStage>* side : {&md.cenc, &md.cdec})
+            for (const ConvStage& st : *side) { conv_bufs.push_back(h->at<void>(st.Y.rm)); conv_bufs.push_back(h->at<void>(st.dY.rm)); }
+    }
+    auto mlp_item = [&](const WorkItem& w) {
+        if (w.conv > 0) return false;
+        for (const void* q : conv_bufs) if (q == w.out0 || q == w.A) return false;
+        return true;
+    };
+    auto reads = [&](const Launch& L, const std::vector<const void*>& outs) {
+        if (L.type != kGrouped) return false;           // the conv helper launches touch the conv modality's buffers only
+        for (int i = 0; i < L.count; ++i) {
+            const WorkItem& w = h->items[L.first + i];
+            const void* csrc = w.conv > 0 ? h->conv_tab[w.conv - 1].src : nullptr;      // (an implicit patch matrix reads its source map)
+            for (const void* q : {w.A, w.B, w.aux0, w.aux1, w.aux2, (const void*)w.tail_w, (const void*)w.tail_aux, csrc})
+                for (const void* o : outs) if (q && q == o) return true;
         }
-        gather_launch("conv_head_im2col", h->plain.fwd, [&](Mod& md) -> const ConvStage& { return md.cenc[3]; },
-                      [&](Mod& md) { return h->at<void>(md.cenc[2].Y.rm); }, [](const Mod& md) { return !md.cenc[3].impl; });
-    }
-    group("fwd_head", h->plain.fwd, [&] { for (Mod& md : h->mods) h->items.push_back(bd.fwd_head(md, true, md.conv && md.cenc[3].impl)); });
-    // KL + association terms and their (mu, lv) gradients need every modality's (mu, lv) (ready after fwd_head) and are needed by
-    // bwd_dec1_latent.  Small nets: they ride in the fwd_out_loss launch (the decoder's hidden launches stay plain GEMM launches).
-    // Big nets, whose loss launch runs one 144-KB workgroup per CU on the 8-wave tile: there the item's workgroups would each take a
-    // CU's only slot and send the launch into a second round (C4: 512 workgroups, 33 us), so it gets a launch of its own here.
-    bool latent_alone = false;
-    {
-        long t64 = 0, t128 = 0;
-        bool narrow = false;
-        for (const Mod& md : h->mods) {
-            t64 += (long)((h->B + 255) / 256) * ((md.n_in + 63) / 64);
-            t128 += (long)((h->B + 127) / 128) * ((md.n_in + 127) / 128);
-            narrow = narrow || md.n_in <= 64 || h->B <= 64;
+        return false;
+    };
+    auto writes = [&](const Launch& L, const std::vector<const void*>& ins) {
+        if (L.type != kGrouped) return false;
+        for (int i = 0; i < L.count; ++i) {
+            const WorkItem& w = h->items[L.first + i];
+            for (const void* q : {(const void*)w.out0, (const void*)w.out1, (const void*)w.tail_out})
+                for (const void* o : ins) if (q && q == o) return true;
         }
-        latent_alone = t64 >= 192 && t128 >= 192 && !narrow && !std::getenv("AVAE_NO_LOSS8");      // = finish_launch's choice of cfg 6
+        return false;
+    };
+    // may launch P move?  An unmerged launch of MLP hidden layers; `ends` gets its items' outputs (outs) or inputs.
+    auto movable = [&](const Launch& P, bool outs, std::vector<const void*>& ends) {
+        if (P.type != kGrouped || P.tn || is_conv_launch(P) || is_merged(P)) return false;
+        for (int i = 0; i < P.count; ++i) {
+            const WorkItem& w = h->items[P.first + i];
+            if (!((w.kind == K_FWD_HIDDEN || w.kind == K_DGRAD_HIDDEN) && !w.bias_ep && mlp_item(w))) return false;
+            ends.push_back(outs ? w.out0 : w.A);
+        }
+        return true;
+    };
+    // may launch Q take P in?  A plain GEMM launch of the conv modality off the 8-wave tiles, with room for P's items.
+    auto hosts = [&](const Launch& Q, const Launch& P) {
+        bool ok = Q.type == kGrouped && !Q.tn && is_conv_launch(Q) && Q.count + P.count <= kMaxItemsPerLaunch && !tile_geom(Q.cfg).waves8;
+        for (int i = 0; ok && i < Q.count; ++i) ok = plain_kind(h->items[Q.first + i].kind);
+        return ok;
+    };
+    // ls[a] rides in ls[target]: the items of both, laid out again as one launch; `split` (an index into ls) follows the removal
+    auto merge = [&](std::vector<Launch>& ls, int a, int target, int* split) {
+        const Launch &P = ls[a], &Q = ls[target];
+        const int first = (int)h->items.size();
+        for (int i = 0; i < Q.count; ++i) { const WorkItem w = h->items[Q.first + i]; h->items.push_back(w); }
+        for (int i = 0; i < P.count; ++i) { const WorkItem w = h->items[P.first + i]; h->items.push_back(w); }
+        int dummy_slot = 0;                          // (no kind in here owns cost-partial slots)
+        Launch merged = finish_launch(h, h->items, first, Q.count + P.count, Q.name + "+" + P.name, &dummy_slot);
+        ls[target] = merged;
+        ls.erase(ls.begin() + a);
+        if (split && a < *split) --*split;
+    };
+    auto sink = [&](std::vector<Launch>& ls, int* split) {
+        for (int a = (int)ls.size() - 1; a >= 0; --a) {
+            std::vector<const void*> outs;
+            if (!movable(ls[a], true, outs)) continue;
+            int target = -1;
+            for (int q = a + 1; q < (int)ls.size() && !reads(ls[q], outs); ++q)
+                if (hosts(ls[q], ls[a])) target = q;
+            if (target >= 0) merge(ls, a, target, split);
+        }
+    };
+    auto hoist = [&](std::vector<Launch>& ls, int* split) {
+        for (int a = 0; a < (int)ls.size(); ++a) {
+            std::vector<const void*> ins;
+            if (!movable(ls[a], false, ins)) continue;
+            int writer = -1;
+            for (int q = 0; q < a; ++q) if (writes(ls[q], ins)) writer = q;
+            if (writer < 0) continue;                    // (its input comes from the other list: leave it where the plan put it)
+            int target = -1;
+            for (int q = writer + 1; q < a && target < 0; ++q)
+                if (hosts(ls[q], ls[a])) target = q;
+            if (target >= 0) { merge(ls, a, target, split); --a; }
+        }
+    };
+    sink(h->plain.fwd, nullptr);
+    sink(h->bwd, &h->bwd_split);
+    hoist(h->bwd, &h->bwd_split);
+}
+
+// does some conv modality route decoder stage i through the adjoint frame / the direct kernels?
+bool any_adj(const avae_handle* h, int i) { bool t = false; for (const Mod& md : h->mods) t = t || (md.conv && i >= 0 && i <= 3 && md.cdec[i].adj); return t; }
+bool any_thin(const avae_handle* h, int i) { bool t = false; for (const Mod& md : h->mods) t = t || (md.conv && md.cdec[i].thin); return t; }
+
+// Every weight gradient in the last launch(es) of the step: they depend only on stored activations /
+// activation gradients, and nothing reads the weights after them, so k_adam follows directly (after the all-reduce
+// under data parallelism).  Fusing Adam into these epilogues was measured and dropped: equal on the small nets
+// (C2 91.5 vs 91.2 us/step), slower on the big ones (C4 958 vs 922: a fused tile streams 448 KB and stalls the
+// MFMA loops it alternates with).
+void plan_weight_gradients(avae_handle* h, Builder& bd, Groups& group) {
+    std::vector<WorkItem> wg;
+    for (Mod& md : h->mods) {
+        if (md.conv) {
+            if (md.cdec[3].dense_map) wg.push_back(bd.wgrad(md.cdec[3].Y, md.cdec[4].d, md.dO));       // the dense output layer on the dense map
+            else wg.push_back(bd.wgrad_stage(md.cdec[4], md.dO));
+            for (int i = 3; i >= 0; --i) {
+                const ConvStage& st = md.cdec[i];
+                if (st.thin) continue;
+                if (st.impl_w) wg.push_back(bd.wgrad_impl(st, i == 0 ? h->at<void>(md.Z.rm) : h->at<void>(md.cdec[i - 1].Y.rm), st.dY));
+                else if (st.adj) wg.push_back(bd.adj_wgrad(st, md.cdec[i - 1]));
+                else wg.push_back(bd.wgrad_stage(st, st.dY));
+            }
+            if (md.cenc[3].impl_w) wg.push_back(bd.wgrad_impl(md.cenc[3], h->at<void>(md.cenc[2].Y.rm), md.dH));
+            else wg.push_back(bd.wgrad_stage(md.cenc[3], md.dH));
+            for (int i = 2; i >= 0; --i) {
+                const ConvStage& st = md.cenc[i];
+                if (st.impl_w) wg.push_back(bd.wgrad_impl(st, i == 0 ? h->at<void>(md.X0.rm) : h->at<void>(md.cenc[i - 1].Y.rm), st.dY));
+                else wg.push_back(bd.wgrad_stage(st, st.dY));
+            }
+            continue;
+        }
+        wg.push_back(bd.wgrad(md.D.back(), md.outl, md.dO));
+        for (int k = md.L - 1; k >= 1; --k) wg.push_back(bd.wgrad(md.D[k - 1], md.dec[k], md.dD[k]));
+        wg.push_back(bd.wgrad(md.Z, md.dec[0], md.dD[0]));
+        wg.push_back(bd.wgrad(md.E.back(), md.head, md.dH));
+        for (int k = md.L - 1; k >= 1; --k) wg.push_back(bd.wgrad(md.E[k - 1], md.enc[k], md.dE[k]));
+        wg.push_back(bd.wgrad(md.X0, md.enc[0], md.dE[0]));
     }
-    if (latent_alone) group("latent", h->plain.fwd, [&] { h->items.push_back(bd.latent()); });
-    for (int k = 0; k < std::max(Lmax, 1); ++k) {
-        group("fwd_dec" + std::to_string(k + 1), h->plain.fwd, [&] {
-            for (Mod& md : h->mods) if (k < md.L) h->items.push_back(bd.fwd_hidden(k == 0 ? md.Z : md.D[k - 1], md.dec[k], md.D[k]));
-        });
-        if (k == 0 && !any_conv && !latent_alone) fuse_tail(h->plain.fwd, 1);      // fwd_dec1 rides in fwd_head
+    // big problems: the narrow products (heads, first decoder layer) get launches of their own, or their presence
+    // would hold the wide ones on 64x64 tiles (finish_launch picks one tile shape per launch)
+    auto is_narrow = [](const WorkItem& w) { return w.N <= 64 || w.M <= 64 || w.conv > 0; };    // (implicit patch matrices: small tiles only)
+    auto wgrad_launches = [&](const std::vector<WorkItem>& set, std::vector<Launch>& dst, const std::string& prefix) {
+        long wide128 = 0;
+        for (const WorkItem& w : set) if (!is_narrow(w)) wide128 += (long)((w.M + 127) / 128) * ((w.N + 127) / 128);
+        std::vector<std::vector<WorkItem>> chunks;
+        auto chunk_up = [&](const std::vector<WorkItem>& v) {
+            for (size_t i0 = 0; i0 < v.size(); i0 += kMaxTnItems)
+                chunks.emplace_back(v.begin() + i0, v.begin() + std::min(v.size(), i0 + (size_t)kMaxTnItems));
+        };
+        if (wide128 >= 192) {
+            std::vector<WorkItem> wide, narrow;
+            for (const WorkItem& w : set) (is_narrow(w) ? narrow : wide).push_back(w);
+            chunk_up(wide); chunk_up(narrow);
+        } else {
+            chunk_up(set);
+        }
+        for (size_t c = 0; c < chunks.size(); ++c) {
+            group(prefix + (chunks.size() > 1 ? std::to_string(c + 1) : std::string()), dst,
+                  [&] { for (const WorkItem& w : chunks[c]) h->items.push_back(w); });
+        }
+    };
+    wgrad_launches(wg, h->wgrad, "wgrad");
+    // the same weight gradients cut into the two data-parallel buckets (MLP-only models)
+    h->wgrad_b[0].clear(); h->wgrad_b[1].clear();
+    dp_ranges(h, &h->n_buckets, h->ranges_b);
+    if (h->n_buckets == 2) {
+        std::vector<WorkItem> set[2];
+        for (Mod& md : h->mods) {
+            set[0].push_back(bd.wgrad(md.D.back(), md.outl, md.dO));
+            for (int k = md.L - 1; k >= 1; --k) set[0].push_back(bd.wgrad(md.D[k - 1], md.dec[k], md.dD[k]));
+            set[0].push_back(bd.wgrad(md.Z, md.dec[0], md.dD[0]));
+            set[1].push_back(bd.wgrad(md.E.back(), md.head, md.dH));
+            for (int k = md.L - 1; k >= 1; --k) set[1].push_back(bd.wgrad(md.E[k - 1], md.enc[k], md.dE[k]));
+            set[1].push_back(bd.wgrad(md.X0, md.enc[0], md.dE[0]));
+        }
+        wgrad_launches(set[0], h->wgrad_b[0], "wgrad_dec");
+        wgrad_launches(set[1], h->wgrad_b[1], "wgrad_enc");
     }
-    if (any_conv) {   // adjoint filter shadows of the transposed-conv stages that run through Padj / the scatter product (refreshed once per step)
+    for (int i = 1; i <= 3; ++i) if (any_thin(h, i)) thin_launch(h, bd, "conv_dec" + std::to_string(i + 1) + "_wgrad_direct", h->wgrad, 2, i);
+    {   // bias gradients of the adjoint-frame stages = column sums of their output gradient, first level
         Launch L;
-        L.name = "conv_wadj"; L.type = 6;
+        L.name = "conv_bias_rowsum"; L.type = kRowsum;
         int base = 0;
-        for (Mod& md : h->mods) if (md.conv) for (const ConvStage& st : md.cdec) if (st.adj) {
-            WadjSeg& g = L.wa.seg[L.wa.n_seg++];
-            g.Wt = h->at<void>(st.d.Wt); g.Wadj = h->at<void>(st.Wadj); g.Wf = h->at<void>(st.Wf); g.ldt = st.d.ldt; g.ldadj = st.ldadj; g.ldf = st.ldf;
+        for (Mod& md : h->mods) if (md.conv) for (const ConvStage& st : md.cdec) if (st.adj && !st.impl_w) {
+            RowsumSeg& g = L.rs.seg[L.rs.n_seg++];
+            g.src = h->at<void>(st.dY.rm); g.part = h->at<float>(st.rs_part); g.ld = st.dY.ld;
+            g.rows = h->B * st.g.OH * st.g.OW; g.cols = st.d.out; g.cols4 = st.rs_cols4; g.n_blocks = kRowsumBlocks;
+            g.cpow = 4; while (g.cpow < g.cols4) g.cpow *= 2;
+            if (g.cpow > 64) throw Err("internal error: bias row sums hold at most 64 columns");
+            g.block_base = base; base += kRowsumBlocks;
+        }
+        L.blocks = base;
+        if (base > 0) h->wgrad.push_back(L);
+    }
+    {   // ... and its per-image partial sums -> the gradient buffer (one column of the padded matrix)
+        Launch R;
+        R.name = "conv_wgrad_sums"; R.type = kColsum;
+        int base = 0;
+        for (Mod& md : h->mods) if (md.conv) for (const ConvStage& st : md.cdec) if (st.adj && !st.impl_w) {      // second level of the row sums
+            ReduceSeg& g = R.ra.seg[R.ra.n_seg++];
+            g.dst = h->grad() + st.d.master + (size_t)st.d.in * st.d.ld; g.src = h->at<float>(st.rs_part);
+            g.n = st.d.out; g.parts = kRowsumBlocks; g.stride = st.rs_cols4; g.dst_ld = 1;
+            g.block_base = base; base += (g.n + 3) / 4;
+        }
+        for (Mod& md : h->mods) if (md.conv) for (const ConvStage& st : md.cdec) if (st.thin) {
+            ReduceSeg& g = R.ra.seg[R.ra.n_seg++];
+            g.dst = h->grad() + st.d.master; g.src = h->at<float>(st.thin_part);
+            g.n = st.d.in + 1; g.parts = st.thin_blocks; g.stride = st.thin_kp; g.dst_ld = st.d.ld;
+            g.block_base = base; base += (g.n + 3) / 4;
+        }
+        R.blocks = base;
+        for (int i = 0; i < R.ra.n_seg; ++i) { R.ra.seg[i].colsum = 1; R.ra.seg[i].perm_k = 0; }
+        if (base > 0) h->wgrad.push_back(R);
+    }
+    {   // the split-K slices of the conv stages' weight gradients -> the gradient buffer, in fixed order
+        Launch R;
+        R.name = "wgrad_reduce"; R.type = kReduce;
+        int base = 0;
+        // (the column sums above write other destinations: when both exist they share one launch, k_sums)
+        Launch* prev = (!h->wgrad.empty() && h->wgrad.back().type == kColsum && !h->sw.no_sums_merge) ? &h->wgrad.back() : nullptr;
+        if (prev) { R = *prev; R.name = prev->name + "+wgrad_reduce"; R.type = kSums; base = prev->blocks; }
+        for (const WorkItem& w : wg) if (w.ksplit > 1) {
+            if (R.ra.n_seg >= kMaxReduceSegs) throw Err("internal error: too many split weight gradients");
+            ReduceSeg& g = R.ra.seg[R.ra.n_seg++];
+            g.dst = reinterpret_cast<float*>(w.out0); g.src = reinterpret_cast<const float*>(w.out1);
+            g.n = w.M * w.ld0; g.parts = w.ksplit; g.stride = (long long)w.M * w.ld0;
+            g.colsum = 0; g.perm_k = 0;
+            // an adjoint-frame filter gradient: its slice sums go straight into the gradient buffer's layout (no k_gperm pass)
+            if (!h->sw.no_sums_merge)
+                for (Mod& md : h->mods) if (md.conv) for (const ConvStage& st : md.cdec) if (st.adj && st.aksplit > 1 && g.dst == h->at<float>(st.Gadj)) {
+                    g.dst = h->grad() + st.d.master;
+                    g.perm_k = st.g.k; g.perm_cin = st.g.Cin; g.perm_cout = st.d.out; g.perm_ldga = st.ldga; g.perm_ld = st.d.ld;
+                }
+            g.block_base = base; base += (g.n / 4 + kThreads - 1) / kThreads;
+        }
+        R.blocks = base;
+        if (prev && base > prev->blocks) *prev = R;              // merged: replaces the column-sum launch
+        else if (!prev && base > 0) h->wgrad.push_back(R);
+    }
+    {   // adjoint-frame filter gradients -> the gradient buffer's layout
+        Launch L;
+        L.name = "conv_wgrad_perm"; L.type = kGperm;
+        int base = 0;
+        for (Mod& md : h->mods) if (md.conv) for (const ConvStage& st : md.cdec) if (st.adj && !st.impl_w) {
+            if (st.aksplit > 1 && !h->sw.no_sums_merge) continue;      // permuted by its slice sum (ReduceSeg::perm_*)
+            GpermSeg& g = L.gp.seg[L.gp.n_seg++];
+            g.Gadj = h->at<float>(st.Gadj); g.G = h->grad() + st.d.master; g.ldga = st.ldga; g.ld = st.d.ld;
             g.k = st.g.k; g.Cin = st.g.Cin; g.Cout = st.d.out;
             g.block_base = base; base += (st.g.Cin * st.g.k * st.g.k * st.d.out + kThreads - 1) / kThreads;
         }
         L.blocks = base;
-        if (base > 0 && std::getenv("AVAE_NO_WADJ_FOLD")) h->plain.fwd.push_back(L);       // default: k_adam writes these shadows (AdamItem::Wadj)
+        if (base > 0) h->wgrad.push_back(L);
     }
-    if (any_conv) {   // deconv decoder: four transposed convs (+ bias + sigmoid each), then the dense output layer
-        for (int i = 0; i < 4; ++i) {
-            // every modality routes its stage i on its own (depths differ between modalities): direct (one output channel), implicit
-            // GEMM in gather form, round 2's adjoint-frame scatter product, or im2col + GEMM
-            auto plain = [&, i](const Mod& md) { return !md.cdec[i].thin && !md.cdec[i].adj && !md.cdec[i].impl; };
-            auto src_of = [&, i](Mod& md) { return i == 0 ? h->at<void>(md.Z.rm) : h->at<void>(md.cdec[i - 1].Y.rm); };
-            if (is_thin(i)) thin_launch("conv_dec" + std::to_string(i + 1) + "_direct", h->plain.fwd, 0, i);
-            if (is_adj(i)) {       // scatter product on the stage's (small) input, then overlap-add + bias + transfer function
-                group("conv_dec" + std::to_string(i + 1) + "_scatter", h->plain.fwd, [&] {
-                    for (Mod& md : h->mods) if (md.conv && md.cdec[i].adj) h->items.push_back(bd.adj_fwd(md.cdec[i], md.cdec[i - 1])); });
-                Launch L;
-                L.name = "conv_dec" + std::to_string(i + 1) + "_overlap"; L.type = 2;
-                int base = 0;
-                for (Mod& md : h->mods) if (md.conv && md.cdec[i].adj) {
-                    Col2imSeg c = bd.adj_overlap_seg(md.cdec[i]);
-                    c.tile_base = base; base += c.tiles_r * c.tiles_c;
-                    L.ca.seg[L.ca.n_seg++] = c;
-                }
-                L.blocks = base;
-                h->plain.fwd.push_back(L);
-            }
-            gather_launch("conv_dec" + std::to_string(i + 1) + "_im2col", h->plain.fwd, [&](Mod& md) -> const ConvStage& { return md.cdec[i]; }, src_of, plain);
-            group("conv_dec" + std::to_string(i + 1), h->plain.fwd, [&] {
-                for (Mod& md : h->mods) if (md.conv) {
-                    if (md.cdec[i].impl) h->items.push_back(bd.conv_fwd_impl(md.cdec[i], src_of(md)));
-                    else if (plain(md)) h->items.push_back(bd.conv_fwd(md.cdec[i]));
-                } });
-        }
-        gather_launch("conv_out_im2col", h->plain.fwd, [&](Mod& md) -> const ConvStage& { return md.cdec[4]; },
-                      [&](Mod& md) { return h->at<void>(md.cdec[3].Y.rm); }, [](const Mod& md) { return !md.cdec[3].dense_map; });
-    }
-    group("fwd_out_loss", h->plain.fwd, [&] {
-        for (int m = 0; m < h->M; ++m) h->items.push_back(bd.fwd_out(h->mods[m], m, true));
-        if (!latent_alone) h->items.push_back(bd.latent());
-    });
-    // ---- backward: the dgrad chain (one launch per layer, all modalities), then EVERY weight gradient in the last
-    // launch(es), then k_adam.  Conv stages go GEMM (fp32 patch gradients) -> k_col2im (sum + act' -> gradient of the
-    // producing stage).
-    group("bwd_out", h->bwd, [&] {
-        for (Mod& md : h->mods) {
-            if (md.conv && md.cdec[3].dense_map) {      // the 28x28 map is a dense row: an ordinary dense dgrad, sigmoid' of the stored map
-                const ConvStage& s3 = md.cdec[3];
-                WorkItem w = bd.dgrad_hidden(md.dO, md.outl, s3.Y, s3.dY);
-                w.act = s3.act;
-                h->items.push_back(w);
-            }
-            else if (md.conv) h->items.push_back(bd.conv_dgrad(md.cdec[4], md.dO));
-            else h->items.push_back(bd.dgrad_hidden(md.dO, md.outl, md.D.back(), md.dD.back()));
-        }
-    });
-    bool latent_conv_impl = false;          // some conv modality's first decoder stage takes the implicit latent dgrad (rides in bwd_dec1_latent)
-    if (any_conv) {
-        for (int i = 4; i >= 1; --i) {       // stage i's patch gradients -> dY of stage i-1; then stage i-1's input gradient
-            // (per modality; a direct, adjoint-frame or implicit stage has no patch gradients: its own launch wrote the producing stage's gradient)
-            auto explicit_i = [&, i](const Mod& md) { return !md.cdec[i].thin && !md.cdec[i].adj && !md.cdec[i].impl_bwd && !(i == 4 && md.cdec[3].dense_map); };
-            auto plain_j = [&, i](const Mod& md) { return !md.cdec[i - 1].thin && !md.cdec[i - 1].adj && !md.cdec[i - 1].impl_bwd; };
-            col2im_launch("conv_dec" + std::to_string(i) + "_col2im", h->bwd, [&](Mod& md) -> const ConvStage& { return md.cdec[i]; },
-                          [&](Mod& md) -> const ConvStage* { return &md.cdec[i - 1]; }, explicit_i);
-            if (is_thin(i - 1)) thin_launch("conv_bwd_dec" + std::to_string(i) + "_direct", h->bwd, 1, i - 1);
-            if (is_adj(i - 1)) {     // patch matrix of stage i-1's output gradient -> GEMM with the adjoint filter -> dY of stage i-2
-                Launch L;
-                L.name = "conv_bwd_dec" + std::to_string(i) + "_adj_im2col"; L.type = 1;
-                int base = 0;
-                for (Mod& md : h->mods) if (md.conv && md.cdec[i - 1].adj && (!md.cdec[i - 1].impl_bwd || !md.cdec[i - 1].impl_w)) {      // (Padj feeds the adjoint dgrad and the adjoint-frame filter gradient)
-                    GatherSeg g = bd.adj_gather_seg(md.cdec[i - 1]);
-                    g.tile_base = base; base += g.tiles_r * g.tiles_c;
-                    L.ga.seg[L.ga.n_seg++] = g;
-                }
-                L.blocks = base;
-                if (base > 0) h->bwd.push_back(L);
-                group("conv_bwd_dec" + std::to_string(i) + "_adj", h->bwd, [&] {
-                    for (Mod& md : h->mods) if (md.conv && md.cdec[i - 1].adj && !md.cdec[i - 1].impl_bwd) h->items.push_back(bd.adj_dgrad(md.cdec[i - 1], md.cdec[i - 2])); });
-            }
-            group("conv_bwd_dec" + std::to_string(i), h->bwd, [&] {
-                for (Mod& md : h->mods) if (md.conv) {
-                    const ConvStage& st = md.cdec[i - 1];
-                    if (st.impl_bwd && i - 1 >= 1)          // implicit GEMM on stage i-1's own output gradient: writes dY of stage i-2
-                        h->items.push_back(bd.adj_dgrad_impl(st, h->at<void>(st.dY.rm), st.g.OH * st.g.OW * st.dY.ld, st.dY.ld, md.cdec[i - 2].act, md.cdec[i - 2].Y, md.cdec[i - 2].dY));
-                    else if (st.impl_bwd) latent_conv_impl = true;
-                    else if (plain_j(md)) h->items.push_back(bd.conv_dgrad(st, st.dY));
-                } });
-        }
-        // first decoder stage: its input is z -> latent mode turns dz into [dmu | dlv]
-        col2im_launch("conv_dec1_latent", h->bwd, [&](Mod& md) -> const ConvStage& { return md.cdec[0]; },
-                      [&](Mod&) -> const ConvStage* { return nullptr; }, [](const Mod& md) { return !md.cdec[0].impl_bwd; });
-    }
-    for (int k = Lmax - 1; k >= 1; --k)
-        group("bwd_dec" + std::to_string(k + 1), h->bwd, [&] {
-            for (Mod& md : h->mods) if (k < md.L) h->items.push_back(bd.dgrad_hidden(md.dD[k], md.dec[k], md.D[k - 1], md.dD[k - 1]));
-        });
-    group("bwd_dec1_latent", h->bwd, [&] {
-        for (Mod& md : h->mods) {
-            if (!md.conv) h->items.push_back(bd.dgrad_latent(md));
-            else if (md.cdec[0].impl_bwd) h->items.push_back(bd.adj_dgrad_latent_impl(md.cdec[0], md));
-        }
-        h->items.push_back(bd.cost(true));                       // every cost partial is final since fwd_out_loss: cost, step counter, lr_t
-    });
-    (void)latent_conv_impl;
-    h->bwd_split = (int)h->bwd.size();      // everything from here on belongs to the encoder side
-    group("bwd_head", h->bwd, [&] {
-        for (Mod& md : h->mods) {
-            if (md.conv && md.cenc[3].impl_bwd)     // implicit: the heads' input gradient straight into the 3x3 map's gradient rows
-                h->items.push_back(bd.adj_dgrad_impl(md.cenc[3], h->at<void>(md.dH.rm), md.dH.ld, md.dH.ld, md.cenc[2].act, md.cenc[2].Y, md.cenc[2].dY));
-            else if (md.conv) h->items.push_back(bd.conv_dgrad(md.cenc[3], md.dH));
-            else h->items.push_back(bd.dgrad_hidden(md.dH, md.head, md.E.back(), md.dE.back()));
-        }
-    });
-    if (!any_conv) fuse_tail(h->bwd, 2);                                      // bwd_head rides in bwd_dec1_latent
-    if (any_conv) {
-        for (int i = 3; i >= 1; --i) {
-            col2im_launch("conv_enc" + std::to_string(i) + "_col2im", h->bwd, [&](Mod& md) -> const ConvStage& { return md.cenc[i]; },
-                          [&](Mod& md) -> const ConvStage* { return &md.cenc[i - 1]; }, [i](const Mod& md) { return !md.cenc[i].impl_bwd; });
-            if (i >= 2) group("conv_bwd_enc" + std::to_string(i), h->bwd, [&] {
-                for (Mod& md : h->mods) if (md.conv) {
-                    const ConvStage& st = md.cenc[i - 1];
-                    if (st.impl_bwd) h->items.push_back(bd.adj_dgrad_impl(st, h->at<void>(st.dY.rm), st.g.OH * st.g.OW * st.dY.ld, st.dY.ld, md.cenc[i - 2].act, md.cenc[i - 2].Y, md.cenc[i - 2].dY));
-                    else h->items.push_back(bd.conv_dgrad(st, st.dY));
-                } });
-        }
-    }
-    for (int k = Lmax - 1; k >= 1; --k) {
-        group("bwd_enc" + std::to_string(k + 1), h->bwd, [&] {
-            for (Mod& md : h->mods) if (k < md.L) h->items.push_back(bd.dgrad_hidden(md.dE[k], md.enc[k], md.E[k - 1], md.dE[k - 1]));
-        });
-    }
-    // ---- mixed models: the MLP modalities' hidden-layer launches (a few tiles, 4-5 us each as launches of their own) ride in plain
-    // GEMM launches of the conv modality.  Taken from the end of each chain backwards, a launch sinks into the LATEST such launch
-    // that still runs before the first reader of its outputs -- so a chain enc1 -> enc2 ends up in two consecutive conv launches.
-    // Safe: every buffer is written once per step, so a product may run any time between its inputs' writers and its readers.
-    if (any_conv && !std::getenv("AVAE_NO_SINK")) {
-        auto plain_kind = [](int k) { return k == K_FWD_HIDDEN || k == K_DGRAD_HIDDEN || k == K_DGRAD_F32; };
-        // only launches of the MLP modalities move: an item that writes a conv modality's buffer stays where the plan put it (its readers
-        // include helper launches -- the direct stage, im2col / col2im -- that the dependency scan below does not look into)
-        std::vector<const void*> conv_bufs;
-        for (const Mod& md : h->mods) if (md.conv) {
-            for (const Act* a : {&md.Z, &md.dH, &md.dO}) conv_bufs.push_back(h->at<void>(a->rm));
-            for (const std::vector<ConvStage>* side : {&md.cenc, &md.cdec})
-                for (const ConvStage& st : *side) { conv_bufs.push_back(h->at<void>(st.Y.rm)); conv_bufs.push_back(h->at<void>(st.dY.rm)); }
-        }
-        auto mlp_item = [&](const WorkItem& w) {
-            if (w.conv > 0) return false;
-            for (const void* q : conv_bufs) if (q == w.out0 || q == w.A) return false;
-            return true;
-        };
-        auto reads = [&](const Launch& L, const std::vector<const void*>& outs) {
-            if (L.type != 0) return false;                  // the conv helper launches touch the conv modality's buffers only
-            for (int i = 0; i < L.count; ++i) {
-                const WorkItem& w = h->items[L.first + i];
-                const void* csrc = w.conv > 0 ? h->conv_tab[w.conv - 1].src : nullptr;      // (an implicit patch matrix reads its source map)
-                for (const void* q : {w.A, w.B, w.aux0, w.aux1, w.aux2, (const void*)w.tail_w, (const void*)w.tail_aux, csrc})
-                    for (const void* o : outs) if (q && q == o) return true;
-            }
-            return false;
-        };
-        auto sink = [&](std::vector<Launch>& ls, int* index_a, int* index_b) {
-            for (int a = (int)ls.size() - 1; a >= 0; --a) {
-                Launch& P = ls[a];
-                if (P.type != 0 || P.tn || P.name.compare(0, 5, "conv_") == 0 || P.name.find('+') != std::string::npos) continue;
-                bool movable = true;
-                std::vector<const void*> outs;
-                for (int i = 0; i < P.count; ++i) {
-                    const WorkItem& w = h->items[P.first + i];
-                    movable = movable && (w.kind == K_FWD_HIDDEN || w.kind == K_DGRAD_HIDDEN) && !w.bias_ep && mlp_item(w);
-                    outs.push_back(w.out0);
-                }
-                if (!movable) continue;
-                int target = -1;
-                for (int q = a + 1; q < (int)ls.size(); ++q) {
-                    const Launch& Q = ls[q];
-                    if (reads(Q, outs)) break;
-                    bool ok = Q.type == 0 && !Q.tn && Q.name.compare(0, 5, "conv_") == 0 && Q.count + P.count <= kMaxItemsPerLaunch && Q.cfg != 2 && Q.cfg != 6;
-                    for (int i = 0; ok && i < Q.count; ++i) ok = plain_kind(h->items[Q.first + i].kind);
-                    if (ok) target = q;
-                }
-                if (target < 0) continue;
-                Launch& Q = ls[target];
-                const int first = (int)h->items.size();
-                for (int i = 0; i < Q.count; ++i) { const WorkItem w = h->items[Q.first + i]; h->items.push_back(w); }
-                for (int i = 0; i < P.count; ++i) { const WorkItem w = h->items[P.first + i]; h->items.push_back(w); }
-                int dummy_slot = 0;                          // (no kind in here owns cost-partial slots)
-                Launch merged = finish_launch(h, h->items, first, Q.count + P.count, Q.name + "+" + P.name, &dummy_slot);
-                ls[target] = merged;
-                ls.erase(ls.begin() + a);
-                for (int* ix : {index_a, index_b}) if (ix && a < *ix) --*ix;
-            }
-        };
-        // ... and where no such launch lies between a launch and its reader (the backward pass: the MLP modality's dgrad layers come
-        // after the conv decoder's), it is HOISTED into the earliest one behind the writer of its input gradient.
-        auto writes = [&](const Launch& L, const std::vector<const void*>& ins) {
-            if (L.type != 0) return false;
-            for (int i = 0; i < L.count; ++i) {
-                const WorkItem& w = h->items[L.first + i];
-                for (const void* q : {(const void*)w.out0, (const void*)w.out1, (const void*)w.tail_out})
-                    for (const void* o : ins) if (q && q == o) return true;
-            }
-            return false;
-        };
-        auto hoist = [&](std::vector<Launch>& ls, int* index_a) {
-            for (int a = 0; a < (int)ls.size(); ++a) {
-                Launch& P = ls[a];
-                if (P.type != 0 || P.tn || P.name.compare(0, 5, "conv_") == 0 || P.name.find('+') != std::string::npos) continue;
-                bool movable = true;
-                std::vector<const void*> ins;
-                for (int i = 0; i < P.count; ++i) {
-                    const WorkItem& w = h->items[P.first + i];
-                    movable = movable && (w.kind == K_FWD_HIDDEN || w.kind == K_DGRAD_HIDDEN) && !w.bias_ep && mlp_item(w);
-                    ins.push_back(w.A);
-                }
-                if (!movable) continue;
-                int writer = -1;
-                for (int q = 0; q < a; ++q) if (writes(ls[q], ins)) writer = q;
-                if (writer < 0) continue;                    // (its input comes from the other list: leave it where the plan put it)
-                int target = -1;
-                for (int q = writer + 1; q < a && target < 0; ++q) {
-                    const Launch& Q = ls[q];
-                    bool ok = Q.type == 0 && !Q.tn && Q.name.compare(0, 5, "conv_") == 0 && Q.count + P.count <= kMaxItemsPerLaunch && Q.cfg != 2 && Q.cfg != 6;
-                    for (int i = 0; ok && i < Q.count; ++i) ok = plain_kind(h->items[Q.first + i].kind);
-                    if (ok) target = q;
-                }
-                if (target < 0) continue;
-                Launch& Q = ls[target];
-                const int first = (int)h->items.size();
-                for (int i = 0; i < Q.count; ++i) { const WorkItem w = h->items[Q.first + i]; h->items.push_back(w); }
-                for (int i = 0; i < P.count; ++i) { const WorkItem w = h->items[P.first + i]; h->items.push_back(w); }
-                int dummy_slot = 0;
-                Launch merged = finish_launch(h, h->items, first, Q.count + P.count, Q.name + "+" + P.name, &dummy_slot);
-                ls[target] = merged;
-                ls.erase(ls.begin() + a);
-                if (index_a && a < *index_a) --*index_a;
-                --a;
-            }
-        };
-        sink(h->plain.fwd, nullptr, nullptr);
-        sink(h->bwd, &h->bwd_split, nullptr);
-        hoist(h->bwd, &h->bwd_split);
-    }
-    // ---- every weight gradient in the last launch(es) of the step: they depend only on stored activations /
-    // activation gradients, and nothing reads the weights after them, so k_adam follows directly (after the all-reduce
-    // under data parallelism).  Fusing Adam into these epilogues was measured and dropped: equal on the small nets
-    // (C2 91.5 vs 91.2 us/step), slower on the big ones (C4 958 vs 922: a fused tile streams 448 KB and stalls the
-    // MFMA loops it alternates with).
-    {
-        std::vector<WorkItem> wg;
-        for (Mod& md : h->mods) {
-            if (md.conv) {
-                if (md.cdec[3].dense_map) wg.push_back(bd.wgrad(md.cdec[3].Y, md.cdec[4].d, md.dO));       // the dense output layer on the dense map
-                else wg.push_back(bd.wgrad_stage(md.cdec[4], md.dO));
-                for (int i = 3; i >= 0; --i) {
-                    const ConvStage& st = md.cdec[i];
-                    if (st.thin) continue;
-                    if (st.impl_w) wg.push_back(bd.wgrad_impl(st, i == 0 ? h->at<void>(md.Z.rm) : h->at<void>(md.cdec[i - 1].Y.rm), st.dY));
-                    else if (st.adj) wg.push_back(bd.adj_wgrad(st, md.cdec[i - 1]));
-                    else wg.push_back(bd.wgrad_stage(st, st.dY));
-                }
-                if (md.cenc[3].impl_w) wg.push_back(bd.wgrad_impl(md.cenc[3], h->at<void>(md.cenc[2].Y.rm), md.dH));
-                else wg.push_back(bd.wgrad_stage(md.cenc[3], md.dH));
-                for (int i = 2; i >= 0; --i) {
-                    const ConvStage& st = md.cenc[i];
-                    if (st.impl_w) wg.push_back(bd.wgrad_impl(st, i == 0 ? h->at<void>(md.X0.rm) : h->at<void>(md.cenc[i - 1].Y.rm), st.dY));
-                    else wg.push_back(bd.wgrad_stage(st, st.dY));
-                }
-                continue;
-            }
-            wg.push_back(bd.wgrad(md.D.back(), md.outl, md.dO));
-            for (int k = md.L - 1; k >= 1; --k) wg.push_back(bd.wgrad(md.D[k - 1], md.dec[k], md.dD[k]));
-            wg.push_back(bd.wgrad(md.Z, md.dec[0], md.dD[0]));
-            wg.push_back(bd.wgrad(md.E.back(), md.head, md.dH));
-            for (int k = md.L - 1; k >= 1; --k) wg.push_back(bd.wgrad(md.E[k - 1], md.enc[k], md.dE[k]));
-            wg.push_back(bd.wgrad(md.X0, md.enc[0], md.dE[0]));
-        }
-        // big problems: the narrow products (heads, first decoder layer) get launches of their own, or their presence
-        // would hold the wide ones on 64x64 tiles (finish_launch picks one tile shape per launch)
-        auto is_narrow = [](const WorkItem& w) { return w.N <= 64 || w.M <= 64 || w.conv > 0; };    // (implicit patch matrices: small tiles only)
-        auto wgrad_launches = [&](const std::vector<WorkItem>& set, std::vector<Launch>& dst, const std::string& prefix) {
-            long wide128 = 0;
-            for (const WorkItem& w : set) if (!is_narrow(w)) wide128 += (long)((w.M + 127) / 128) * ((w.N + 127) / 128);
-            std::vector<std::vector<WorkItem>> chunks;
-            auto chunk_up = [&](const std::vector<WorkItem>& v) {
-                for (size_t i0 = 0; i0 < v.size(); i0 += kMaxTnItems)
-                    chunks.emplace_back(v.begin() + i0, v.begin() + std::min(v.size(), i0 + (size_t)kMaxTnItems));
-            };
-            if (wide128 >= 192) {
-                std::vector<WorkItem> wide, narrow;
-                for (const WorkItem& w : set) (is_narrow(w) ? narrow : wide).push_back(w);
-                chunk_up(wide); chunk_up(narrow);
-            } else {
-                chunk_up(set);
-            }
-            for (size_t c = 0; c < chunks.size(); ++c) {
-                group(prefix + (chunks.size() > 1 ? std::to_string(c + 1) : std::string()), dst,
-                      [&] { for (const WorkItem& w : chunks[c]) h->items.push_back(w); });
-            }
-        };
-        wgrad_launches(wg, h->wgrad, "wgrad");
-        // the same weight gradients cut into the two data-parallel buckets (MLP-only models)
-        h->wgrad_b[0].clear(); h->wgrad_b[1].clear();
-        dp_ranges(h, &h->n_buckets, h->ranges_b);
-        if (h->n_buckets == 2) {
-            std::vector<WorkItem> set[2];
-            for (Mod& md : h->mods) {
-                set[0].push_back(bd.wgrad(md.D.back(), md.outl, md.dO));
-                for (int k = md.L - 1; k >= 1; --k) set[0].push_back(bd.wgrad(md.D[k - 1], md.dec[k], md.dD[k]));
-                set[0].push_back(bd.wgrad(md.Z, md.dec[0], md.dD[0]));
-                set[1].push_back(bd.wgrad(md.E.back(), md.head, md.dH));
-                for (int k = md.L - 1; k >= 1; --k) set[1].push_back(bd.wgrad(md.E[k - 1], md.enc[k], md.dE[k]));
-                set[1].push_back(bd.wgrad(md.X0, md.enc[0], md.dE[0]));
-            }
-            wgrad_launches(set[0], h->wgrad_b[0], "wgrad_dec");
-            wgrad_launches(set[1], h->wgrad_b[1], "wgrad_enc");
-        }
-        for (int i = 1; i <= 3; ++i) if (is_thin(i)) thin_launch("conv_dec" + std::to_string(i + 1) + "_wgrad_direct", h->wgrad, 2, i);
-        {   // bias gradients of the adjoint-frame stages = column sums of their output gradient, first level
-            Launch L;
-            L.name = "conv_bias_rowsum"; L.type = 8;
-            int base = 0;
-            for (Mod& md : h->mods) if (md.conv) for (const ConvStage& st : md.cdec) if (st.adj && !st.impl_w) {
-                RowsumSeg& g = L.rs.seg[L.rs.n_seg++];
-                g.src = h->at<void>(st.dY.rm); g.part = h->at<float>(st.rs_part); g.ld = st.dY.ld;
-                g.rows = h->B * st.g.OH * st.g.OW; g.cols = st.d.out; g.cols4 = st.rs_cols4; g.n_blocks = kRowsumBlocks;
-                g.cpow = 4; while (g.cpow < g.cols4) g.cpow *= 2;
-                if (g.cpow > 64) throw Err("internal error: bias row sums hold at most 64 columns");
-                g.block_base = base; base += kRowsumBlocks;
-            }
-            L.blocks = base;
-            if (base > 0) h->wgrad.push_back(L);
-        }
-        {   // ... and its per-image partial sums -> the gradient buffer (one column of the padded matrix)
-            Launch R;
-            R.name = "conv_wgrad_sums"; R.type = 5;
-            int base = 0;
-            for (Mod& md : h->mods) if (md.conv) for (const ConvStage& st : md.cdec) if (st.adj && !st.impl_w) {      // second level of the row sums
-                ReduceSeg& g = R.ra.seg[R.ra.n_seg++];
-                g.dst = h->grad() + st.d.master + (size_t)st.d.in * st.d.ld; g.src = h->at<float>(st.rs_part);
-                g.n = st.d.out; g.parts = kRowsumBlocks; g.stride = st.rs_cols4; g.dst_ld = 1;
-                g.block_base = base; base += (g.n + 3) / 4;
-            }
-            for (Mod& md : h->mods) if (md.conv) for (const ConvStage& st : md.cdec) if (st.thin) {
-                ReduceSeg& g = R.ra.seg[R.ra.n_seg++];
-                g.dst = h->grad() + st.d.master; g.src = h->at<float>(st.thin_part);
-                g.n = st.d.in + 1; g.parts = st.thin_blocks; g.stride = st.thin_kp; g.dst_ld = st.d.ld;
-                g.block_base = base; base += (g.n + 3) / 4;
-            }
-            R.blocks = base;
-            for (int i = 0; i < R.ra.n_seg; ++i) { R.ra.seg[i].colsum = 1; R.ra.seg[i].perm_k = 0; }
-            if (base > 0) h->wgrad.push_back(R);
-        }
-        {   // the split-K slices of the conv stages' weight gradients -> the gradient buffer, in fixed order
-            Launch R;
-            R.name = "wgrad_reduce"; R.type = 3;
-            int base = 0;
-            // (the column sums above write other destinations: when both exist they share one launch, k_sums)
-            Launch* prev = (!h->wgrad.empty() && h->wgrad.back().type == 5 && !std::getenv("AVAE_NO_SUMS_MERGE")) ? &h->wgrad.back() : nullptr;
-            if (prev) { R = *prev; R.name = prev->name + "+wgrad_reduce"; R.type = 9; base = prev->blocks; }
-            for (const WorkItem& w : wg) if (w.ksplit > 1) {
-                if (R.ra.n_seg >= kMaxReduceSegs) throw Err("internal error: too many split weight gradients");
-                ReduceSeg& g = R.ra.seg[R.ra.n_seg++];
-                g.dst = reinterpret_cast<float*>(w.out0); g.src = reinterpret_cast<const float*>(w.out1);
-                g.n = w.M * w.ld0; g.parts = w.ksplit; g.stride = (long long)w.M * w.ld0;
-                g.colsum = 0; g.perm_k = 0;
-                // an adjoint-frame filter gradient: its slice sums go straight into the gradient buffer's layout (no k_gperm pass)
-                if (!std::getenv("AVAE_NO_SUMS_MERGE"))
-                    for (Mod& md : h->mods) if (md.conv) for (const ConvStage& st : md.cdec) if (st.adj && st.aksplit > 1 && g.dst == h->at<float>(st.Gadj)) {
-                        g.dst = h->grad() + st.d.master;
-                        g.perm_k = st.g.k; g.perm_cin = st.g.Cin; g.perm_cout = st.d.out; g.perm_ldga = st.ldga; g.perm_ld = st.d.ld;
-                    }
-                g.block_base = base; base += (g.n / 4 + kThreads - 1) / kThreads;
-            }
-            R.blocks = base;
-            if (prev && base > prev->blocks) *prev = R;              // merged: replaces the column-sum launch
-            else if (!prev && base > 0) h->wgrad.push_back(R);
-        }
-        {   // adjoint-frame filter gradients -> the gradient buffer's layout
-            Launch L;
-            L.name = "conv_wgrad_perm"; L.type = 7;
-            int base = 0;
-            for (Mod& md : h->mods) if (md.conv) for (const ConvStage& st : md.cdec) if (st.adj && !st.impl_w) {
-                if (st.aksplit > 1 && !std::getenv("AVAE_NO_SUMS_MERGE")) continue;      // permuted by its slice sum (ReduceSeg::perm_*)
-                GpermSeg& g = L.gp.seg[L.gp.n_seg++];
-                g.Gadj = h->at<float>(st.Gadj); g.G = h->grad() + st.d.master; g.ldga = st.ldga; g.ld = st.d.ld;
-                g.k = st.g.k; g.Cin = st.g.Cin; g.Cout = st.d.out;
-                g.block_base = base; base += (st.g.Cin * st.g.k * st.g.k * st.d.out + kThreads - 1) / kThreads;
-            }
-            L.blocks = base;
-            if (base > 0) h->wgrad.push_back(L);
-        }
-    }
-    // ---- small nets: the optimiser in the epilogue of the (single) weight-gradient launch.  Only for the plain single-replica step
-    // (under data parallelism the all-reduce sits between the two; avae_dp_backward / avae_dp_apply keep them apart as well).
+}
+
+// Small nets: the optimiser in the epilogue of the (single) weight-gradient launch.  Only for the plain single-replica step
+// (under data parallelism the all-reduce sits between the two; avae_dp_backward / avae_dp_apply keep them apart as well).
+void fuse_adam(avae_handle* h, bool any_conv) {
     h->wgrad_adam.clear();
-    if (!any_conv && h->wgrad.size() == 1 && h->wgrad[0].tn && h->wgrad[0].cfg == 0 && h->wgrad[0].targs.xcd_group == 1
-        && !std::getenv("AVAE_NO_LEAN") && !std::getenv("AVAE_NO_ADAM_FUSE")) {
+    if (!any_conv && h->wgrad.size() == 1 && h->wgrad[0].tn && h->wgrad[0].cfg == k64x64 && h->wgrad[0].targs.xcd_group == 1
+        && !h->sw.no_lean && !h->sw.no_adam_fuse) {
         Launch L = h->wgrad[0];
         bool ok = true;
         for (int i = 0; i < L.targs.n_items && ok; ++i) {
@@ -1904,49 +1826,46 @@ void build_training_plan(avae_handle* h) {
             if (ok) { t.W = h->at<void>(dm->W); t.Wt = h->at<void>(dm->Wt); t.ldw = dm->ldw; t.ldt = dm->ldt; }
         }
         if (ok) {
-            L.cfg = 12; L.name = "wgrad+adam";
+            L.cfg = kLeanTnAdam; L.name = "wgrad+adam";
             L.targs.adam = 1;
             L.targs.d_theta = h->at<float>(h->off_theta) - h->grad();
             L.targs.d_m = h->at<float>(h->off_m) - h->grad();
             L.targs.d_v = h->at<float>(h->off_v) - h->grad();
             L.targs.beta1 = h->cfg.beta1; L.targs.beta2 = h->cfg.beta2; L.targs.eps = h->cfg.adam_eps;
             L.targs.st = h->state();
-            if (!std::getenv("AVAE_NO_XCD_PIECES")) xcd_pieces(L);
+            if (!h->sw.no_xcd_pieces) xcd_pieces(L);
             h->wgrad_adam.push_back(L);
         }
     }
-    // ---- weight warm-up: a launch on the 8-wave NT tiles pulls the weight panels of the next grouped NT launch into the Infinity
-    // Cache (see k_grouped); forward and backward form one sequence (the step graph runs them back to back)
-    if (!std::getenv("AVAE_NO_WARM")) {
-        std::vector<Launch*> seq;
-        for (Launch& L : h->plain.fwd) seq.push_back(&L);
-        for (Launch& L : h->bwd) seq.push_back(&L);
-        for (size_t i = 0; i < seq.size(); ++i) {
-            Launch& L = *seq[i];
-            if (L.type != 0 || L.tn || (L.cfg != 2 && L.cfg != 6)) continue;
-            for (size_t j = i + 1; j < seq.size(); ++j) {
-                const Launch& Nx = *seq[j];
-                if (Nx.type != 0) continue;                 // helper launches of the conv branch in between
-                if (Nx.tn) break;
-                for (int k = 0; k < Nx.args.n_items && L.args.n_pf < kMaxPf; ++k) {
-                    const WorkItem& w = Nx.args.items[k];
-                    if (!is_gemm(w.kind) || w.kind == K_WGRAD) continue;
-                    const long bytes = (long)w.N * w.ldb * h->es;          // B = weight shadow: N rows of ldb elements
-                    if (bytes < 128 * 1024) continue;                     // small panels come with the first tile anyway
-                    L.args.pf_ptr[L.args.n_pf] = w.B; L.args.pf_lines[L.args.n_pf] = (int)(bytes / 128); ++L.args.n_pf;
-                }
-                break;
+}
+
+// Weight warm-up: a launch on the 8-wave NT tiles pulls the weight panels of the next grouped NT launch into the Infinity
+// Cache (see k_grouped); forward and backward form one sequence (the step graph runs them back to back)
+void plan_weight_warmup(avae_handle* h) {
+    std::vector<Launch*> seq;
+    for (Launch& L : h->plain.fwd) seq.push_back(&L);
+    for (Launch& L : h->bwd) seq.push_back(&L);
+    for (size_t i = 0; i < seq.size(); ++i) {
+        Launch& L = *seq[i];
+        if (L.type != kGrouped || L.tn || !tile_geom(L.cfg).waves8) continue;
+        for (size_t j = i + 1; j < seq.size(); ++j) {
+            const Launch& Nx = *seq[j];
+            if (Nx.type != kGrouped) continue;               // helper launches of the conv branch in between
+            if (Nx.tn) break;
+            for (int k = 0; k < Nx.args.n_items && L.args.n_pf < kMaxPf; ++k) {
+                const WorkItem& w = Nx.args.items[k];
+                if (!is_gemm(w.kind) || w.kind == K_WGRAD) continue;
+                const long bytes = (long)w.N * w.ldb * h->es;          // B = weight shadow: N rows of ldb elements
+                if (bytes < 128 * 1024) continue;                     // small panels come with the first tile anyway
+                L.args.pf_ptr[L.args.n_pf] = w.B; L.args.pf_lines[L.args.n_pf] = (int)(bytes / 128); ++L.args.n_pf;
             }
+            break;
         }
     }
-    // ---- eval: forward launches + a lone cost reduction that does not bump the step
-    {
-        const int first = (int)h->items.size();
-        h->items.push_back(bd.cost(false));
-        h->cost_only = finish_launch(h, h->items, first, 1, "cost_reduce", &group.slot);
-    }
+}
 
-    // ---- Adam tiles
+// The training plan's Adam tiles: one item per dense layer / conv stage, and the bucket-ordered copy of the data-parallel step.
+void build_adam_tables(avae_handle* h) {
     h->adam_items.clear();
     int base = 0;
     auto add = [&](const Dense& d) {
@@ -1969,7 +1888,7 @@ void build_training_plan(avae_handle* h) {
                     add(st.d);
                     // adjoint filter shadows by the same pass (no k_wadj launch): the implicit input gradients' B operand, and -- round 2's
                     // adjoint-frame route -- the forward scatter product's
-                    if ((st.adj && !std::getenv("AVAE_NO_WADJ_FOLD")) || st.impl_bwd) {
+                    if ((st.adj && !h->sw.no_wadj_fold) || st.impl_bwd) {
                         AdamItem& a = h->adam_items.back();
                         a.Wadj = h->at<void>(st.Wadj); a.ldadj = st.ldadj; a.adj_k = st.g.k; a.adj_cin = st.g.Cin;
                         if (st.adj) { a.Wf = h->at<void>(st.Wf); a.ldf = st.ldf; }
@@ -2006,6 +1925,207 @@ void build_training_plan(avae_handle* h) {
     }
 }
 
+void build_training_plan(avae_handle* h) {
+    h->items.clear(); h->plain.fwd.clear(); h->bwd.clear(); h->wgrad.clear(); h->conv_tab.clear();
+    Builder bd(h, h->items, h->B, true);
+    Groups group{h, h->items};
+    int Lmax = 0;
+    for (const Mod& md : h->mods) Lmax = std::max(Lmax, md.L);
+    bool any_conv = false;
+    for (const Mod& md : h->mods) any_conv = any_conv || md.conv;
+    // ---- forward.  Modalities with fewer hidden layers simply sit out a launch; data dependencies
+    // are per modality and launches are stream-ordered, so this is always safe.
+    for (int k = 0; k < Lmax; ++k)
+        group("fwd_enc" + std::to_string(k + 1), h->plain.fwd, [&] {
+            for (Mod& md : h->mods) if (k < md.L) h->items.push_back(bd.fwd_hidden(k == 0 ? md.X0 : md.E[k - 1], md.enc[k], md.E[k]));
+        });
+    if (h->sw.chain2 && !any_conv) chain_enc12(h);
+    if (any_conv) {   // conv encoder: three convs, then the flatten + dense heads.  Per modality and stage: implicit GEMM (the patch
+                      // matrix is gathered by the GEMM's own operand loads), or im2col launch + GEMM where the channels are no whole chunks
+        for (int i = 0; i < 3; ++i) {
+            auto src_of = [&, i](Mod& md) { return i == 0 ? h->at<void>(md.X0.rm) : h->at<void>(md.cenc[i - 1].Y.rm); };
+            gather_launch(h, bd, "conv_enc" + std::to_string(i + 1) + "_im2col", h->plain.fwd, [&](Mod& md) -> const ConvStage& { return md.cenc[i]; },
+                          src_of, [i](const Mod& md) { return !md.cenc[i].impl; });
+            group("conv_enc" + std::to_string(i + 1), h->plain.fwd, [&] {
+                for (Mod& md : h->mods) if (md.conv) h->items.push_back(md.cenc[i].impl ? bd.conv_fwd_impl(md.cenc[i], src_of(md)) : bd.conv_fwd(md.cenc[i])); });
+        }
+        gather_launch(h, bd, "conv_head_im2col", h->plain.fwd, [&](Mod& md) -> const ConvStage& { return md.cenc[3]; },
+                      [&](Mod& md) { return h->at<void>(md.cenc[2].Y.rm); }, [](const Mod& md) { return !md.cenc[3].impl; });
+    }
+    group("fwd_head", h->plain.fwd, [&] { for (Mod& md : h->mods) h->items.push_back(bd.fwd_head(md, true, md.conv && md.cenc[3].impl)); });
+    // KL + association terms and their (mu, lv) gradients need every modality's (mu, lv) (ready after fwd_head) and are needed by
+    // bwd_dec1_latent.  Small nets: they ride in the fwd_out_loss launch (the decoder's hidden launches stay plain GEMM launches).
+    // Big nets, whose loss launch runs one 144-KB workgroup per CU on the 8-wave tile: there the item's workgroups would each take a
+    // CU's only slot and send the launch into a second round (C4: 512 workgroups, 33 us), so it gets a launch of its own here.
+    bool latent_alone = false;
+    {
+        long t64 = 0, t128 = 0;
+        bool narrow = false;
+        for (const Mod& md : h->mods) {
+            t64 += (long)((h->B + 255) / 256) * ((md.n_in + 63) / 64);
+            t128 += (long)((h->B + 127) / 128) * ((md.n_in + 127) / 128);
+            narrow = narrow || md.n_in <= 64 || h->B <= 64;
+        }
+        latent_alone = t64 >= 192 && t128 >= 192 && !narrow && !h->sw.no_loss8;      // = choose_cfg's choice of k256x64Loss
+    }
+    if (latent_alone) group("latent", h->plain.fwd, [&] { h->items.push_back(bd.latent()); });
+    for (int k = 0; k < std::max(Lmax, 1); ++k) {
+        group("fwd_dec" + std::to_string(k + 1), h->plain.fwd, [&] {
+            for (Mod& md : h->mods) if (k < md.L) h->items.push_back(bd.fwd_hidden(k == 0 ? md.Z : md.D[k - 1], md.dec[k], md.D[k]));
+        });
+        if (k == 0 && !any_conv && !latent_alone) fuse_tail(h, h->plain.fwd, 1);      // fwd_dec1 rides in fwd_head
+    }
+    if (any_conv) {   // adjoint filter shadows of the transposed-conv stages that run through Padj / the scatter product (refreshed once per step)
+        Launch L;
+        L.name = "conv_wadj"; L.type = kWadj;
+        int base = 0;
+        for (Mod& md : h->mods) if (md.conv) for (const ConvStage& st : md.cdec) if (st.adj) {
+            WadjSeg& g = L.wa.seg[L.wa.n_seg++];
+            g.Wt = h->at<void>(st.d.Wt); g.Wadj = h->at<void>(st.Wadj); g.Wf = h->at<void>(st.Wf); g.ldt = st.d.ldt; g.ldadj = st.ldadj; g.ldf = st.ldf;
+            g.k = st.g.k; g.Cin = st.g.Cin; g.Cout = st.d.out;
+            g.block_base = base; base += (st.g.Cin * st.g.k * st.g.k * st.d.out + kThreads - 1) / kThreads;
+        }
+        L.blocks = base;
+        if (base > 0 && h->sw.no_wadj_fold) h->plain.fwd.push_back(L);       // default: k_adam writes these shadows (AdamItem::Wadj)
+    }
+    if (any_conv) {   // deconv decoder: four transposed convs (+ bias + sigmoid each), then the dense output layer
+        for (int i = 0; i < 4; ++i) {
+            // every modality routes its stage i on its own (depths differ between modalities): direct (one output channel), implicit
+            // GEMM in gather form, round 2's adjoint-frame scatter product, or im2col + GEMM
+            auto plain = [&, i](const Mod& md) { return !md.cdec[i].thin && !md.cdec[i].adj && !md.cdec[i].impl; };
+            auto src_of = [&, i](Mod& md) { return i == 0 ? h->at<void>(md.Z.rm) : h->at<void>(md.cdec[i - 1].Y.rm); };
+            if (any_thin(h, i)) thin_launch(h, bd, "conv_dec" + std::to_string(i + 1) + "_direct", h->plain.fwd, 0, i);
+            if (any_adj(h, i)) {       // scatter product on the stage's (small) input, then overlap-add + bias + transfer function
+                group("conv_dec" + std::to_string(i + 1) + "_scatter", h->plain.fwd, [&] {
+                    for (Mod& md : h->mods) if (md.conv && md.cdec[i].adj) h->items.push_back(bd.adj_fwd(md.cdec[i], md.cdec[i - 1])); });
+                Launch L;
+                L.name = "conv_dec" + std::to_string(i + 1) + "_overlap"; L.type = kCol2im;
+                int base = 0;
+                for (Mod& md : h->mods) if (md.conv && md.cdec[i].adj) {
+                    Col2imSeg c = bd.adj_overlap_seg(md.cdec[i]);
+                    c.tile_base = base; base += c.tiles_r * c.tiles_c;
+                    L.ca.seg[L.ca.n_seg++] = c;
+                }
+                L.blocks = base;
+                h->plain.fwd.push_back(L);
+            }
+            gather_launch(h, bd, "conv_dec" + std::to_string(i + 1) + "_im2col", h->plain.fwd, [&](Mod& md) -> const ConvStage& { return md.cdec[i]; }, src_of, plain);
+            group("conv_dec" + std::to_string(i + 1), h->plain.fwd, [&] {
+                for (Mod& md : h->mods) if (md.conv) {
+                    if (md.cdec[i].impl) h->items.push_back(bd.conv_fwd_impl(md.cdec[i], src_of(md)));
+                    else if (plain(md)) h->items.push_back(bd.conv_fwd(md.cdec[i]));
+                } });
+        }
+        gather_launch(h, bd, "conv_out_im2col", h->plain.fwd, [&](Mod& md) -> const ConvStage& { return md.cdec[4]; },
+                      [&](Mod& md) { return h->at<void>(md.cdec[3].Y.rm); }, [](const Mod& md) { return !md.cdec[3].dense_map; });
+    }
+    group("fwd_out_loss", h->plain.fwd, [&] {
+        for (int m = 0; m < h->M; ++m) h->items.push_back(bd.fwd_out(h->mods[m], m, true));
+        if (!latent_alone) h->items.push_back(bd.latent());
+    });
+    // ---- backward: the dgrad chain (one launch per layer, all modalities), then EVERY weight gradient in the last
+    // launch(es), then k_adam.  Conv stages go GEMM (fp32 patch gradients) -> k_col2im (sum + act' -> gradient of the
+    // producing stage).
+    group("bwd_out", h->bwd, [&] {
+        for (Mod& md : h->mods) {
+            if (md.conv && md.cdec[3].dense_map) {      // the 28x28 map is a dense row: an ordinary dense dgrad, sigmoid' of the stored map
+                const ConvStage& s3 = md.cdec[3];
+                WorkItem w = bd.dgrad_hidden(md.dO, md.outl, s3.Y, s3.dY);
+                w.act = s3.act;
+                h->items.push_back(w);
+            }
+            else if (md.conv) h->items.push_back(bd.conv_dgrad(md.cdec[4], md.dO));
+            else h->items.push_back(bd.dgrad_hidden(md.dO, md.outl, md.D.back(), md.dD.back()));
+        }
+    });
+    bool latent_conv_impl = false;          // some conv modality's first decoder stage takes the implicit latent dgrad (rides in bwd_dec1_latent)
+    if (any_conv) {
+        for (int i = 4; i >= 1; --i) {       // stage i's patch gradients -> dY of stage i-1; then stage i-1's input gradient
+            // (per modality; a direct, adjoint-frame or implicit stage has no patch gradients: its own launch wrote the producing stage's gradient)
+            auto explicit_i = [&, i](const Mod& md) { return !md.cdec[i].thin && !md.cdec[i].adj && !md.cdec[i].impl_bwd && !(i == 4 && md.cdec[3].dense_map); };
+            auto plain_j = [&, i](const Mod& md) { return !md.cdec[i - 1].thin && !md.cdec[i - 1].adj && !md.cdec[i - 1].impl_bwd; };
+            col2im_launch(h, bd, "conv_dec" + std::to_string(i) + "_col2im", h->bwd, [&](Mod& md) -> const ConvStage& { return md.cdec[i]; },
+                          [&](Mod& md) -> const ConvStage* { return &md.cdec[i - 1]; }, explicit_i);
+            if (any_thin(h, i - 1)) thin_launch(h, bd, "conv_bwd_dec" + std::to_string(i) + "_direct", h->bwd, 1, i - 1);
+            if (any_adj(h, i - 1)) {     // patch matrix of stage i-1's output gradient -> GEMM with the adjoint filter -> dY of stage i-2
+                Launch L;
+                L.name = "conv_bwd_dec" + std::to_string(i) + "_adj_im2col"; L.type = kGather;
+                int base = 0;
+                for (Mod& md : h->mods) if (md.conv && md.cdec[i - 1].adj && (!md.cdec[i - 1].impl_bwd || !md.cdec[i - 1].impl_w)) {      // (Padj feeds the adjoint dgrad and the adjoint-frame filter gradient)
+                    GatherSeg g = bd.adj_gather_seg(md.cdec[i - 1]);
+                    g.tile_base = base; base += g.tiles_r * g.tiles_c;
+                    L.ga.seg[L.ga.n_seg++] = g;
+                }
+                L.blocks = base;
+                if (base > 0) h->bwd.push_back(L);
+                group("conv_bwd_dec" + std::to_string(i) + "_adj", h->bwd, [&] {
+                    for (Mod& md : h->mods) if (md.conv && md.cdec[i - 1].adj && !md.cdec[i - 1].impl_bwd) h->items.push_back(bd.adj_dgrad(md.cdec[i - 1], md.cdec[i - 2])); });
+            }
+            group("conv_bwd_dec" + std::to_string(i), h->bwd, [&] {
+                for (Mod& md : h->mods) if (md.conv) {
+                    const ConvStage& st = md.cdec[i - 1];
+                    if (st.impl_bwd && i - 1 >= 1)          // implicit GEMM on stage i-1's own output gradient: writes dY of stage i-2
+                        h->items.push_back(bd.adj_dgrad_impl(st, h->at<void>(st.dY.rm), st.g.OH * st.g.OW * st.dY.ld, st.dY.ld, md.cdec[i - 2].act, md.cdec[i - 2].Y, md.cdec[i - 2].dY));
+                    else if (st.impl_bwd) latent_conv_impl = true;
+                    else if (plain_j(md)) h->items.push_back(bd.conv_dgrad(st, st.dY));
+                } });
+        }
+        // first decoder stage: its input is z -> latent mode turns dz into [dmu | dlv]
+        col2im_launch(h, bd, "conv_dec1_latent", h->bwd, [&](Mod& md) -> const ConvStage& { return md.cdec[0]; },
+                      [&](Mod&) -> const ConvStage* { return nullptr; }, [](const Mod& md) { return !md.cdec[0].impl_bwd; });
+    }
+    for (int k = Lmax - 1; k >= 1; --k)
+        group("bwd_dec" + std::to_string(k + 1), h->bwd, [&] {
+            for (Mod& md : h->mods) if (k < md.L) h->items.push_back(bd.dgrad_hidden(md.dD[k], md.dec[k], md.D[k - 1], md.dD[k - 1]));
+        });
+    group("bwd_dec1_latent", h->bwd, [&] {
+        for (Mod& md : h->mods) {
+            if (!md.conv) h->items.push_back(bd.dgrad_latent(md));
+            else if (md.cdec[0].impl_bwd) h->items.push_back(bd.adj_dgrad_latent_impl(md.cdec[0], md));
+        }
+        h->items.push_back(bd.cost(true));                       // every cost partial is final since fwd_out_loss: cost, step counter, lr_t
+    });
+    (void)latent_conv_impl;
+    h->bwd_split = (int)h->bwd.size();      // everything from here on belongs to the encoder side
+    group("bwd_head", h->bwd, [&] {
+        for (Mod& md : h->mods) {
+            if (md.conv && md.cenc[3].impl_bwd)     // implicit: the heads' input gradient straight into the 3x3 map's gradient rows
+                h->items.push_back(bd.adj_dgrad_impl(md.cenc[3], h->at<void>(md.dH.rm), md.dH.ld, md.dH.ld, md.cenc[2].act, md.cenc[2].Y, md.cenc[2].dY));
+            else if (md.conv) h->items.push_back(bd.conv_dgrad(md.cenc[3], md.dH));
+            else h->items.push_back(bd.dgrad_hidden(md.dH, md.head, md.E.back(), md.dE.back()));
+        }
+    });
+    if (!any_conv) fuse_tail(h, h->bwd, 2);                                      // bwd_head rides in bwd_dec1_latent
+    if (any_conv) {
+        for (int i = 3; i >= 1; --i) {
+            col2im_launch(h, bd, "conv_enc" + std::to_string(i) + "_col2im", h->bwd, [&](Mod& md) -> const ConvStage& { return md.cenc[i]; },
+                          [&](Mod& md) -> const ConvStage* { return &md.cenc[i - 1]; }, [i](const Mod& md) { return !md.cenc[i].impl_bwd; });
+            if (i >= 2) group("conv_bwd_enc" + std::to_string(i), h->bwd, [&] {
+                for (Mod& md : h->mods) if (md.conv) {
+                    const ConvStage& st = md.cenc[i - 1];
+                    if (st.impl_bwd) h->items.push_back(bd.adj_dgrad_impl(st, h->at<void>(st.dY.rm), st.g.OH * st.g.OW * st.dY.ld, st.dY.ld, md.cenc[i - 2].act, md.cenc[i - 2].Y, md.cenc[i - 2].dY));
+                    else h->items.push_back(bd.conv_dgrad(st, st.dY));
+                } });
+        }
+    }
+    for (int k = Lmax - 1; k >= 1; --k) {
+        group("bwd_enc" + std::to_string(k + 1), h->bwd, [&] {
+            for (Mod& md : h->mods) if (k < md.L) h->items.push_back(bd.dgrad_hidden(md.dE[k], md.enc[k], md.E[k - 1], md.dE[k - 1]));
+        });
+    }
+    if (any_conv && !h->sw.no_sink) sink_and_hoist(h);
+    plan_weight_gradients(h, bd, group);
+    fuse_adam(h, any_conv);
+    if (!h->sw.no_warm) plan_weight_warmup(h);
+    // ---- eval: forward launches + a lone cost reduction that does not bump the step
+    {
+        const int first = (int)h->items.size();
+        h->items.push_back(bd.cost(false));
+        h->cost_only = finish_launch(h, h->items, first, 1, "cost_reduce", &group.slot);
+    }
+    build_adam_tables(h);
+}
+
 void build_inference(avae_handle* h, int m, bool enc, int rows) {
     avae_handle::Inf& inf = enc ? h->inf_enc[m] : h->inf_dec[m];
     if (inf.rows == rows) return;
@@ -2019,7 +2139,7 @@ void build_inference(avae_handle* h, int m, bool enc, int rows) {
     };
     auto gather1 = [&](const ConvStage& st, const void* src, const std::string& name) {
         Launch L;
-        L.name = name; L.type = 1;
+        L.name = name; L.type = kGather;
         GatherSeg g = bd.gather_seg(st, src);
         g.tile_base = 0;
         L.ga.seg[0] = g; L.ga.n_seg = 1;
@@ -2040,7 +2160,7 @@ void build_inference(avae_handle* h, int m, bool enc, int rows) {
         for (int i = 0; i < 4; ++i) {
             if (md.cdec[i].dense_map) {      // the one-channel 28x28 stage writes dense rows: the direct kernel, as in training
                 Launch L;
-                L.name = "inf_conv_dec_direct"; L.type = 4;
+                L.name = "inf_conv_dec_direct"; L.type = kThin;
                 L.ta.mode = 0;
                 ThinSeg t = bd.thin_seg(md.cdec[i], md.cdec[i - 1]);
                 t.block_base = 0;
@@ -2104,15 +2224,15 @@ Launch relocated(const avae_handle* h, const Launch& L0, int j, const HyperEntry
         const unsigned char* q = reinterpret_cast<const unsigned char*>(ptr);
         if (q >= lo && q < hi) ptr = reinterpret_cast<std::remove_reference_t<decltype(ptr)>>(const_cast<unsigned char*>(q) + delta);
     };
-    for (int i = 0; i < L.args.n_items && L.type == 0; ++i) {
+    for (int i = 0; i < L.args.n_items && L.type == kGrouped; ++i) {
         WorkItem& w = L.args.items[i];
         fix(w.A); fix(w.B); fix(w.out0); fix(w.out1); fix(w.out2); fix(w.aux0); fix(w.aux1); fix(w.aux2); fix(w.eps);
         fix(w.tail_w); fix(w.tail_out); fix(w.tail_aux);
         if (w.present) w.present += (size_t)j * h->pres_set;          // masked twin: presence set j (its own allocation)
         if (hyper && (w.kind == K_LATENT || (w.kind == K_COST && w.bump_step))) w.tail_w = hyper + j;
     }
-    for (int i = 0; i < L.targs.n_items && L.type == 0; ++i) { TnItem& t = L.targs.items[i]; fix(t.A); fix(t.B); fix(t.out); }
-    for (int i = 0; i < L.ga.n_seg && L.type == 1; ++i) fix(L.ga.seg[i].src);
+    for (int i = 0; i < L.targs.n_items && L.type == kGrouped; ++i) { TnItem& t = L.targs.items[i]; fix(t.A); fix(t.B); fix(t.out); }
+    for (int i = 0; i < L.ga.n_seg && L.type == kGather; ++i) fix(L.ga.seg[i].src);
     L.desc_set = j;
     return L;
 }
@@ -2241,7 +2361,7 @@ std::vector<LossRec> loss_recs(const avae_handle* h, const Launch& L) {
 std::vector<HeadRec> head_recs(const avae_handle* h, const Launch& L) {
     std::vector<HeadRec> lists[8];
     const int es = h->es;
-    const bool bwd = L.cfg == 10;
+    const bool bwd = L.cfg == kLeanLatb;
     for (int y = 0; y < L.args.n_items; ++y) {
         const WorkItem& w = L.args.items[y];
         const bool cost = bwd && w.kind == K_COST;
@@ -2278,16 +2398,16 @@ std::vector<HeadRec> head_recs(const avae_handle* h, const Launch& L) {
 }
 
 // Tile configurations whose training-plan launches run on two-line records (LossRec, HeadRec)
-bool two_line_records(const Launch& L) { return L.type == 0 && !L.tn && (L.cfg == 9 || L.cfg == 10 || L.cfg == 11); }
+bool two_line_records(const Launch& L) { return L.type == kGrouped && !L.tn && tile_geom(L.cfg).records == 2; }
 
 // Builds the device table of per-workgroup descriptors for the training plan's launches and points the launches at it
 // (avae_device.h: SmallDesc, TnDesc, LossRec, HeadRec).  One copy of a launch's records per staging set (a record holds resolved
 // addresses, and some of them point into the set).  AVAE_NO_DESC=1 keeps every launch on its by-value arguments (A/B).
 void build_descriptors(avae_handle* h, hipStream_t s) {
-    if (std::getenv("AVAE_NO_DESC")) return;
+    if (h->sw.no_desc) return;
     std::vector<unsigned char> tab;
     auto add = [&](Launch& L) {
-        if (L.type != 0 || !((L.cfg == 7 && !L.tn) || (L.cfg == 12 && L.tn && L.targs.adam) || two_line_records(L))) return;
+        if (L.type != kGrouped || !((L.cfg == kLean && !L.tn) || (L.cfg == kLeanTnAdam && L.tn && L.targs.adam) || two_line_records(L))) return;
         tab.resize((tab.size() + 127) & ~(size_t)127);        // (two-line records start on an even line)
         const size_t off = tab.size();
         size_t stride = 0;
@@ -2303,9 +2423,9 @@ void build_descriptors(avae_handle* h, hipStream_t s) {
         for (int j = 0; j < kMultiSteps; ++j) {
             const Launch Lj = j == 0 ? L : relocated(h, L, j);
             const size_t at = tab.size();
-            if (L.cfg == 9) {
+            if (L.cfg == kLeanLoss) {
                 if (!put(loss_recs(h, Lj))) return;
-            } else if (L.cfg == 10 || L.cfg == 11) {
+            } else if (L.cfg == kLeanLatb || L.cfg == kLeanHead) {
                 if (!put(head_recs(h, Lj))) return;
             } else if (L.tn) {
                 const std::vector<TnDesc> d = tn_descs(h, Lj);
@@ -2350,14 +2470,14 @@ void dump_launch(const Launch& L) {
     std::fprintf(stderr, "[avae] launch %s type=%d cfg=%d items=%d blocks=%d\n", L.name.c_str(), L.type, L.cfg, L.count, L.blocks);
     // runs on its records, not on the items below (two-line records: only the latent / cost item is still read from them)
     if (L.desc_n) std::fprintf(stderr, two_line_records(L) ? "        records=%d set=%d\n" : "        descriptors=%d set=%d\n", L.desc_n, L.desc_set);
-    for (int i = 0; i < L.args.n_items && L.type == 0; ++i)
+    for (int i = 0; i < L.args.n_items && L.type == kGrouped; ++i)
         std::fprintf(stderr, "        item kind=%d M=%d N=%d K=%d lda=%d ldb=%d tiles=%dx%d\n", L.args.items[i].kind, L.args.items[i].M,
                      L.args.items[i].N, L.args.items[i].K, L.args.items[i].lda, L.args.items[i].ldb, L.args.items[i].tiles_m, L.args.items[i].tiles_n);
-    for (int i = 0; i < L.ga.n_seg && L.type == 1; ++i)
+    for (int i = 0; i < L.ga.n_seg && L.type == kGather; ++i)
         std::fprintf(stderr, "        gather B=%d IH=%d Cin=%d OH=%d k=%d so=%d d=%d pad=%d sb=%d sp=%d ones=%d ldp=%d tiles=%dx%d\n", L.ga.seg[i].g.B, L.ga.seg[i].g.IH,
                      L.ga.seg[i].g.Cin, L.ga.seg[i].g.OH, L.ga.seg[i].g.k, L.ga.seg[i].g.so, L.ga.seg[i].g.d, L.ga.seg[i].g.pad, L.ga.seg[i].g.src_sb, L.ga.seg[i].g.src_sp,
                      L.ga.seg[i].g.ones, L.ga.seg[i].ldp, L.ga.seg[i].tiles_r, L.ga.seg[i].tiles_c);
-    for (int i = 0; i < L.ca.n_seg && L.type == 2; ++i)
+    for (int i = 0; i < L.ca.n_seg && L.type == kCol2im; ++i)
         std::fprintf(stderr, "        col2im B=%d IH=%d Cin=%d OH=%d k=%d lddp=%d lda=%d g0=%p tiles=%dx%d\n", L.ca.seg[i].g.B, L.ca.seg[i].g.IH, L.ca.seg[i].g.Cin,
                      L.ca.seg[i].g.OH, L.ca.seg[i].g.k, L.ca.seg[i].lddp, L.ca.seg[i].lda, (const void*)L.ca.seg[i].g0, L.ca.seg[i].tiles_r, L.ca.seg[i].tiles_c);
 }
@@ -2366,30 +2486,30 @@ void dump_launch(const Launch& L) {
 void run_launch(avae_handle* h, const Launch& L, hipStream_t s, unsigned long long* stamps, int stamp, DescWarm warm = DescWarm{nullptr, 0},
                 bool keep_grad = true) {
     Timed t(h, s, L.name);
-    if (L.type == 1) launch_gather(h->cfg.compute_dtype, L.ga, L.blocks, s);
-    else if (L.type == 2) launch_col2im(h->cfg.compute_dtype, L.ca, L.blocks, s);
-    else if (L.type == 3) launch_reduce(L.ra, L.blocks, s);
-    else if (L.type == 4) launch_thin(h->cfg.compute_dtype, L.ta, L.blocks, s);
-    else if (L.type == 5) launch_colsum(L.ra, L.blocks, s);
-    else if (L.type == 6) launch_wadj(h->cfg.compute_dtype, L.wa, L.blocks, s);
-    else if (L.type == 7) launch_gperm(L.gp, L.blocks, s);
-    else if (L.type == 8) launch_rowsum(h->cfg.compute_dtype, L.rs, L.blocks, s);
-    else if (L.type == 9) launch_sums(L.ra, L.blocks, s);
-    else if (L.cfg == 13) launch_chain2(h->cfg.compute_dtype, L.args, L.grid_x, L.grid_y, L.lds, h->at<unsigned>(h->off_chain), h->at<unsigned>(h->off_chain) + kMaxMod * 64, s);
-    else if (L.cfg == 11 && L.desc_n) launch_head_rec(h->cfg.compute_dtype, L.lean_act, desc_of<HeadRec>(h, L), L.desc_n, L.lds, warm, s, stamps, stamp);
-    else if (L.cfg == 10 && L.desc_n) launch_latb_rec(h->cfg.compute_dtype, L.lean_act, desc_of<HeadRec>(h, L), L.desc_n, L.lds, warm, h->state(), L.args, s, stamps, stamp);
-    else if (L.cfg == 9 && L.desc_n) launch_loss_rec(h->cfg.compute_dtype, desc_of<LossRec>(h, L), L.desc_n, L.lds, warm, L.args, s, stamps, stamp);
-    else if (L.cfg == 11) launch_small_head(h->cfg.compute_dtype, L.lean_act, L.args, L.grid_x, L.grid_y, L.lds, s, stamps, stamp);
-    else if (L.cfg == 10) launch_small_latb(h->cfg.compute_dtype, L.lean_act, L.args, L.grid_x, L.grid_y, L.lds, h->state(), s, stamps, stamp);
-    else if (L.cfg == 9) launch_small_loss(h->cfg.compute_dtype, L.args, L.grid_x, L.grid_y, L.lds, s, stamps, stamp);
-    else if (L.cfg == 7 && L.desc_n) launch_small_desc(h->cfg.compute_dtype, L.args.items[0].kind == K_DGRAD_HIDDEN, L.args.items[0].act, desc_of<SmallDesc>(h, L), L.desc_n, L.lds, warm, s, stamps, stamp);
-    else if (L.cfg == 7) launch_small(h->cfg.compute_dtype, L.args, L.grid_x, L.grid_y, L.lds, s, stamps, stamp);
-    else if (L.tn && L.cfg == 12 && L.desc_n) launch_small_tn_desc(h->cfg.compute_dtype, desc_of<TnDesc>(h, L), L.desc_n, keep_grad, warm, s, stamps, stamp);
-    else if (L.tn && L.cfg == 12) launch_small_tn(h->cfg.compute_dtype, L.targs, L.grid_x, L.grid_y, s, stamps, stamp);
+    if (L.type == kGather) launch_gather(h->cfg.compute_dtype, L.ga, L.blocks, s);
+    else if (L.type == kCol2im) launch_col2im(h->cfg.compute_dtype, L.ca, L.blocks, s);
+    else if (L.type == kReduce) launch_reduce(L.ra, L.blocks, s);
+    else if (L.type == kThin) launch_thin(h->cfg.compute_dtype, L.ta, L.blocks, s);
+    else if (L.type == kColsum) launch_colsum(L.ra, L.blocks, s);
+    else if (L.type == kWadj) launch_wadj(h->cfg.compute_dtype, L.wa, L.blocks, s);
+    else if (L.type == kGperm) launch_gperm(L.gp, L.blocks, s);
+    else if (L.type == kRowsum) launch_rowsum(h->cfg.compute_dtype, L.rs, L.blocks, s);
+    else if (L.type == kSums) launch_sums(L.ra, L.blocks, s);
+    else if (L.cfg == kChain2) launch_chain2(h->cfg.compute_dtype, L.args, L.grid_x, L.grid_y, L.lds, h->at<unsigned>(h->off_chain), h->at<unsigned>(h->off_chain) + kMaxMod * 64, s);
+    else if (L.cfg == kLeanHead && L.desc_n) launch_head_rec(h->cfg.compute_dtype, L.lean_act, desc_of<HeadRec>(h, L), L.desc_n, L.lds, warm, s, stamps, stamp);
+    else if (L.cfg == kLeanLatb && L.desc_n) launch_latb_rec(h->cfg.compute_dtype, L.lean_act, desc_of<HeadRec>(h, L), L.desc_n, L.lds, warm, h->state(), L.args, s, stamps, stamp);
+    else if (L.cfg == kLeanLoss && L.desc_n) launch_loss_rec(h->cfg.compute_dtype, desc_of<LossRec>(h, L), L.desc_n, L.lds, warm, L.args, s, stamps, stamp);
+    else if (L.cfg == kLeanHead) launch_small_head(h->cfg.compute_dtype, L.lean_act, L.args, L.grid_x, L.grid_y, L.lds, s, stamps, stamp);
+    else if (L.cfg == kLeanLatb) launch_small_latb(h->cfg.compute_dtype, L.lean_act, L.args, L.grid_x, L.grid_y, L.lds, h->state(), s, stamps, stamp);
+    else if (L.cfg == kLeanLoss) launch_small_loss(h->cfg.compute_dtype, L.args, L.grid_x, L.grid_y, L.lds, s, stamps, stamp);
+    else if (L.cfg == kLean && L.desc_n) launch_small_desc(h->cfg.compute_dtype, L.args.items[0].kind == K_DGRAD_HIDDEN, L.args.items[0].act, desc_of<SmallDesc>(h, L), L.desc_n, L.lds, warm, s, stamps, stamp);
+    else if (L.cfg == kLean) launch_small(h->cfg.compute_dtype, L.args, L.grid_x, L.grid_y, L.lds, s, stamps, stamp);
+    else if (L.tn && L.cfg == kLeanTnAdam && L.desc_n) launch_small_tn_desc(h->cfg.compute_dtype, desc_of<TnDesc>(h, L), L.desc_n, keep_grad, warm, s, stamps, stamp);
+    else if (L.tn && L.cfg == kLeanTnAdam) launch_small_tn(h->cfg.compute_dtype, L.targs, L.grid_x, L.grid_y, s, stamps, stamp);
     else if (L.tn) launch_grouped_tn(h->cfg.compute_dtype, L.cfg, L.targs, L.grid_x, L.grid_y, L.lds, h->state(), s, stamps, stamp);
     else launch_grouped(h->cfg.compute_dtype, L.cfg, L.args, L.grid_x, L.grid_y, L.lds, h->state(), s, stamps, stamp);
     LAUNCH_OK(L.name);
-    if (h->debug_sync) {      // AVAE_DEBUG_SYNC=1: name the launch a fault belongs to
+    if (h->sw.debug_sync) {      // AVAE_DEBUG_SYNC=1: name the launch a fault belongs to
         dump_launch(L);
         std::fflush(stderr);
         HIP_OK(hipStreamSynchronize(s));
@@ -2397,7 +2517,7 @@ void run_launch(avae_handle* h, const Launch& L, hipStream_t s, unsigned long lo
 }
 
 bool has_hyper_item(const Launch& L) {
-    for (int i = 0; i < L.args.n_items && L.type == 0; ++i)
+    for (int i = 0; i < L.args.n_items && L.type == kGrouped; ++i)
         if (L.args.items[i].kind == K_LATENT || (L.args.items[i].kind == K_COST && L.args.items[i].bump_step)) return true;
     return false;
 }
@@ -2627,8 +2747,8 @@ bool step_body(avae_handle* h, const std::vector<Launch>& fwd, hipStream_t s, in
     const bool plain = &fwd == &h->plain.fwd;      // (the masked twin's head and loss launches stay by-value; the backward launches are shared)
     run_set(h, h->bwd, 0, h->bwd.size(), j, s, sb(fwd.size()), true, fused ? first_of(h->wgrad_adam) : nullptr, j, plain);
     if (fused) {       // the optimiser rides in the weight-gradient launch
-        bool keep = !more || h->keep_grads;
-        for (const Launch& L : h->wgrad_adam) keep = keep || !(L.tn && L.cfg == 12 && L.desc_n);     // a by-value launch always stores
+        bool keep = !more || h->sw.keep_grads;
+        for (const Launch& L : h->wgrad_adam) keep = keep || !(L.tn && L.cfg == kLeanTnAdam && L.desc_n);     // a by-value launch always stores
         run_set(h, h->wgrad_adam, 0, h->wgrad_adam.size(), j, s, sb(fwd.size() + h->bwd.size()), true, more ? first_of(fwd) : nullptr, j + 1, true, keep);
         return keep;
     }
@@ -2857,7 +2977,7 @@ static_assert(kMaxWorld == AVAE_MAX_WORLD, "world size limit");
 void comm_streams(avae_handle* h) {
     int lo = 0, hi = 0;                          // the collective's kernels should start the moment their gradients exist
     (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-    if (std::getenv("AVAE_COMM_NO_PRIO")) hi = 0;     // (A/B)
+    if (h->sw.comm_no_prio) hi = 0;     // (A/B)
     HIP_OK(hipStreamCreateWithPriority(&h->comm_stream, hipStreamNonBlocking, hi));
     for (int b = 0; b < 2; ++b) {
         HIP_OK(hipEventCreateWithFlags(&h->ev_grad[b], hipEventDisableTiming));
@@ -2889,9 +3009,7 @@ void comm_init_ipc(avae_handle* h) {
     const int N = h->cfg.world_size;
     IpcArgs& a = h->ipc_args;
     std::memset(&a, 0, sizeof(a));
-    int blocks = 256;                             // one workgroup per CU: the exchange is three memory passes over the range, and 64
-                                                  // workgroups moved them at < 1 TB/s (14 us for C2's 6 MB with one rank, measured)
-    if (const char* e = std::getenv("AVAE_IPC_BLOCKS")) blocks = std::atoi(e);
+    const int blocks = h->sw.ipc_blocks;
     if (blocks < 1 || blocks > 1024) throw Err("AVAE_IPC_BLOCKS out of range");
     const bool bf = h->cfg.wire_dtype == AVAE_BF16;
     const size_t gb = bf ? 16 : 32, G = h->P_int / 8, S = (G + N - 1) / N;        // (P_int is a multiple of 32 floats)
@@ -2907,9 +3025,7 @@ void comm_init_ipc(avae_handle* h) {
     a.off_res = (long long)take(G * gb);
     h->ipc_bytes = off;
     a.g = h->grad(); a.world = N; a.rank = h->cfg.rank; a.wire_bf16 = bf ? 1 : 0; a.blocks = blocks;
-    double ms = 20000.0;                          // a peer that is this late has failed: raise the error word instead of hanging
-    if (const char* e = std::getenv("AVAE_IPC_TIMEOUT_MS")) ms = std::atof(e);
-    a.timeout_ticks = (unsigned long long)(ms * 1e5);                             // 100 MHz wall clock
+    a.timeout_ticks = (unsigned long long)(h->sw.ipc_timeout_ms * 1e5);                            // 100 MHz wall clock
     // uncached: neither this device's L2s nor a peer's keep lines of it (RCCL allocates its own buffers the same way)
     HIP_OK(hipExtMallocWithFlags(reinterpret_cast<void**>(&h->ipc_block), h->ipc_bytes, hipDeviceMallocUncached));
     HIP_OK(hipMemset(h->ipc_block, 0, h->ipc_bytes));
@@ -3052,7 +3168,7 @@ avae_handle::Serve& serve_plan(avae_handle* h, int bucket) {
     // tile of bf16, two of fp32, at most 1024 units, 32-row tiles); otherwise it is the graph's first launch behind k_serve.
     {
         const int first = (int)sv.items.size();
-        bool fits = !std::getenv("AVAE_NO_TAIL") && bucket <= 4096;
+        bool fits = !h->sw.no_tail && bucket <= 4096;
         for (Mod& md : h->mods) {
             const WorkItem c = bd.fwd_hidden(md.Z, md.dec[0], md.D[0]);
             fits = fits && c.K <= (h->es == 2 ? 1 : 2) * h->KU && c.N <= 1024 && h->nz + 1 <= 64;
@@ -3064,9 +3180,9 @@ avae_handle::Serve& serve_plan(avae_handle* h, int bucket) {
         }
         if (fits) {
             sv.in_launch = finish_launch(h, sv.items, first, (int)sv.items.size() - first, "serve_in+serve_dec1", &group.slot);
-            if (sv.in_launch.cfg != 3) fits = false;
+            if (sv.in_launch.cfg != k32x64) fits = false;
         }
-        if (fits && !std::getenv("AVAE_NO_LEAN")) {            // the same launch as a kernel of its own with a small argument block (k_serve_in)
+        if (fits && !h->sw.no_lean) {            // the same launch as a kernel of its own with a small argument block (k_serve_in)
             ServeInArgs& ia = sv.in_lean;
             std::memset(&ia, 0, sizeof(ia));
             ia.slot = h->at<ServeSlot>(h->off_slot); ia.n_mod = h->M; ia.nz = h->nz; ia.bucket = bucket; ia.tiles_m = (bucket + 31) / 32;
@@ -3104,7 +3220,7 @@ avae_handle::Serve& serve_plan(avae_handle* h, int bucket) {
     sv.in = a;                                                   // the per-call staging launch (ahead of the graph)
     if (!(sv.fused_in && sv.lean_in))                            // serve_call replays a graph of the remaining launches
         sv.graph = capture(h, [&](hipStream_t cs) { run_launches(h, sv.launches, cs); }).exec;
-    if (h->plan_dump) {       // AVAE_PLAN_DUMP=1: the route and every launch of the plan, the staging launch first
+    if (h->sw.plan_dump) {       // AVAE_PLAN_DUMP=1: the route and every launch of the plan, the staging launch first
         std::fprintf(stderr, "[avae] serve plan bucket=%d fused_in=%d lean_in=%d in_lean_grid=%d\n", bucket, sv.fused_in ? 1 : 0,
                      sv.lean_in ? 1 : 0, sv.in_lean_grid);
         if (sv.fused_in) dump_launch(sv.in_launch);
@@ -3381,7 +3497,7 @@ void build_masked(avae_handle* h) {
     std::vector<Launch> mf = h->plain.fwd;
     int n_loss = 0, n_latent = 0;
     for (Launch& L : mf) {
-        if (L.type != 0 || L.tn) continue;
+        if (L.type != kGrouped || L.tn) continue;
         bool gated = false;
         for (int i = 0; i < L.args.n_items; ++i) {
             WorkItem& w = L.args.items[i];
@@ -3396,11 +3512,10 @@ void build_masked(avae_handle* h) {
                 gated = true; ++n_latent;
             }
         }
-        // the kernels that carry the presence gate: k_grouped's 4-wave tiles (configurations 0, 1, 3, 4, 5), its 8-wave loss tile (6)
-        // and the small nets' loss kernel (9).  Any other route of a loss or latent item would ignore the mask: refuse.
-        const int c = L.cfg;
-        if (gated && !(c == 0 || c == 1 || c == 3 || c == 4 || c == 5 || c == 6 || c == 9))
-            throw Err("masked training is not available on this plan: launch " + L.name + " (tile configuration " + std::to_string(c) +
+        // the kernels that carry the presence gate (TileGeom::masked): k_grouped's 4-wave tiles, its 8-wave loss tile and the small
+        // nets' loss kernel.  Any other route of a loss or latent item would ignore the mask: refuse.
+        if (gated && !tile_geom(L.cfg).masked)
+            throw Err("masked training is not available on this plan: launch " + L.name + " (tile configuration " + std::to_string((int)L.cfg) +
                       ") carries a loss or latent item on a kernel without the presence gate");
     }
     if (n_loss != h->M || n_latent != 1) throw Err("internal error: the masked twin found " + std::to_string(n_loss) + " loss and " +
@@ -3514,7 +3629,7 @@ void train_steps(avae_handle* h, StepPlan& p, int n_steps, const float* const* x
                 } catch (const std::exception& e) {
                     h->dp_graph_failed = true;
                     (void)hipGetLastError();
-                    if (std::getenv("AVAE_DEBUG_DP")) std::fprintf(stderr, "[avae] data-parallel graph capture failed (%s): host-stepped pipeline\n", e.what());
+                    if (h->sw.debug_dp) std::fprintf(stderr, "[avae] data-parallel graph capture failed (%s): host-stepped pipeline\n", e.what());
                     return false;
                 }
                 return true;
@@ -3647,6 +3762,7 @@ int avae_workspace_bytes(const avae_config* cfg, size_t* bytes) {
         check_config(*cfg);
         avae_handle tmp;
         tmp.cfg = *cfg;
+        tmp.sw = read_switches();
         plan_memory(&tmp);
         *bytes = tmp.ws_bytes;
         return 0;
@@ -3660,10 +3776,8 @@ int avae_create(const avae_config* cfg, avae_handle** out) {
         check_config(*cfg);
         h = new avae_handle();
         h->cfg = *cfg;
-        if (const char* e = std::getenv("AVAE_DEBUG_SYNC")) h->debug_sync = e[0] == '1';
-        if (h->debug_sync) h->cfg.use_graph = 0;
-        if (const char* e = std::getenv("AVAE_PLAN_DUMP")) h->plan_dump = e[0] == '1';
-        if (const char* e = std::getenv("AVAE_KEEP_GRADS")) h->keep_grads = e[0] == '1';
+        h->sw = read_switches();
+        if (h->sw.debug_sync) h->cfg.use_graph = 0;
         if (h->cfg.beta1 == 0.f && h->cfg.beta2 == 0.f && h->cfg.adam_eps == 0.f) { h->cfg.beta1 = 0.9f; h->cfg.beta2 = 0.999f; h->cfg.adam_eps = 1e-8f; }
         int ndev = 0;
         HIP_OK(hipGetDeviceCount(&ndev));
@@ -4013,6 +4127,7 @@ int avae_dp_plan(const avae_config* cfg, int32_t* n_buckets, int32_t* n_ranges, 
         check_config(*cfg);
         avae_handle tmp;
         tmp.cfg = *cfg;
+        tmp.sw = read_switches();
         plan_memory(&tmp);
         std::vector<avae_handle::Range> r[2];
         int nb = 0;

@@ -542,27 +542,27 @@ template <int BM, int BN, int RING> struct TileSmem {
     static constexpr int kStages = RING * kStage;
     static constexpr int kC = BM * (BN + 4) * 4;               // one fp32 accumulator tile
 };
-// tile_cfg: 0 = 64x64 tile, 4-stage ring; 1 = 128x128 tile, 2-stage ring, two workgroups per CU;
-//           2 = 256x128 tile, 3-stage ring, one workgroup per CU (big single-C-tile kinds only)
-//           3 = 32x64 tile, 4-stage ring (NT launches with too few 64x64 tiles to occupy the chip; a 6-stage ring is slower:
-//               issuing five tiles up front costs more than the latency it hides, 69.1 vs 67.1 us/step on C2)
-//           4 = 64x128 tile, 4-stage ring (wide-latent head / latent-dgrad launches with few tiles: three K tiles in
-//               flight instead of one, twice the workgroups of cfg 1)
-//           5 = 32x32 tile, 4-stage ring (as 3, for launches without head kinds: a wave issues 2 refill pieces per K tile
-//               instead of 3, and the issue cost of those pieces is what paces the K loop of a lone workgroup)
-//           6 = 256x64 tile, 8 waves, 3-stage ring: the output + reconstruction-loss launch of the big nets (its epilogue is
-//               bound by ~5 transcendentals per element: 256x64 tiles of a 784 + 147-column output give one tile per CU)
-int tile_lds_bytes(int tile_cfg, bool two_c_tiles) {
-    if (tile_cfg == 6) return TileSmem<256, 64, 3>::kStages + 64;
-    if (tile_cfg == 5) return TileSmem<32, 32, 4>::kStages + 64;
-    if (tile_cfg == 4) {
-        const int st = TileSmem<64, 128, 4>::kStages, c4 = TileSmem<64, 128, 4>::kC * (two_c_tiles ? 2 : 1);
-        return (st > c4 ? st : c4) + 64;
-    }
-    const int stages = tile_cfg == 3 ? TileSmem<32, 64, 4>::kStages : tile_cfg == 2 ? TileSmem<256, 128, 3>::kStages : tile_cfg == 1 ? TileSmem<128, 128, 2>::kStages : TileSmem<64, 64, 4>::kStages;
-    const int c = (tile_cfg == 3 ? TileSmem<32, 64, 4>::kC : tile_cfg == 2 ? TileSmem<256, 128, 3>::kC : tile_cfg == 1 ? TileSmem<128, 128, 2>::kC : TileSmem<64, 64, 4>::kC) * (two_c_tiles ? 2 : 1);
-    return (stages > c ? stages : c) + 64;                     // + block-reduction scratch
+// The tile configurations (TileCfg, avae_device.h) of k_grouped; what measurements chose them:
+//   k32x64       a 6-stage ring is slower: issuing five tiles up front costs more than the latency it hides, 69.1 vs 67.1 us/step on C2
+//   k64x128      three K tiles in flight instead of one, twice the workgroups of k128x128
+//   k32x32       a wave issues 2 refill pieces per K tile instead of 3, and the issue cost of those pieces is what paces the K loop
+//                of a lone workgroup
+//   k256x64Loss  its epilogue is bound by ~5 transcendentals per element: 256x64 tiles of a 784 + 147-column output give one tile
+//                per CU; the epilogue runs in registers (no C tile in LDS)
+// LDS of one workgroup: the operand ring or the fp32 accumulator tile(s), whichever is larger, + block-reduction scratch.
+constexpr int tile_lds(int cfg, bool two_c_tiles) {
+    const TileGeom& g = tile_geom(cfg);
+    const int c = cfg == k256x64Loss ? 0 : g.rows * (g.cols + 4) * 4 * (two_c_tiles ? 2 : 1);
+    return (tile_ring_bytes(cfg) > c ? tile_ring_bytes(cfg) : c) + 64;
 }
+template <int CFG, int BM, int BN, int RING> constexpr bool tile_matches() {
+    return tile_geom(CFG).rows == BM && tile_geom(CFG).cols == BN && tile_ring_bytes(CFG) == TileSmem<BM, BN, RING>::kStages &&
+           (CFG == k256x64Loss || tile_lds(CFG, true) == (TileSmem<BM, BN, RING>::kStages > 2 * TileSmem<BM, BN, RING>::kC ? TileSmem<BM, BN, RING>::kStages : 2 * TileSmem<BM, BN, RING>::kC) + 64);
+}
+static_assert(tile_matches<k64x64, 64, 64, 4>() && tile_matches<k128x128, 128, 128, 2>() && tile_matches<k256x128, 256, 128, 3>() &&
+              tile_matches<k32x64, 32, 64, 4>() && tile_matches<k64x128, 64, 128, 4>() && tile_matches<k32x32, 32, 32, 4>() &&
+              tile_matches<k256x64Loss, 256, 64, 3>(), "the geometry table and the kernels' template arguments agree");
+int tile_lds_bytes(int tile_cfg, bool two_c_tiles) { return tile_lds(tile_cfg, two_c_tiles); }
 
 extern __shared__ __attribute__((aligned(16))) unsigned char avae_dyn_smem[];
 
@@ -2561,7 +2561,7 @@ static void launch_small_act(int act, const LaunchArgs& args, dim3 grid, int lds
         default: AVAE_LAUNCH((k_small<CT, KIND, AVAE_ACT_IDENTITY>), grid, block, lds_bytes, s, args, stamps, launch_id); break;
     }
 }
-// tile_cfg 7 (host: finish_launch): every item of the launch is of ONE kind (hidden forward, hidden dgrad or output store) and one transfer function
+// kLean (host: choose_cfg): every item of the launch is of ONE kind (hidden forward, hidden dgrad or output store) and one transfer function
 void launch_small(int compute_dtype, const LaunchArgs& args, int grid_x, int grid_y, int lds_bytes, hipStream_t s, unsigned long long* stamps, int launch_id) {
     const dim3 grid(grid_x, grid_y);
     const int kind = args.items[0].kind == K_DGRAD_HIDDEN ? 1 : 0, act = args.items[0].act;
@@ -2586,7 +2586,7 @@ static void launch_small_desc_act(int act, const SmallDesc* tab, dim3 grid, int 
         default: AVAE_LAUNCH((k_small_desc<CT, KIND, AVAE_ACT_IDENTITY>), grid, block, lds_bytes, s, tab, stamps, launch_id, warm.lines, warm.n); break;
     }
 }
-// tile_cfg 7 of the training plan on descriptors: dgrad = the launch's kind is K_DGRAD_HIDDEN (else K_FWD_HIDDEN), one transfer function
+// kLean of the training plan on descriptors: dgrad = the launch's kind is K_DGRAD_HIDDEN (else K_FWD_HIDDEN), one transfer function
 void launch_small_desc(int compute_dtype, bool dgrad, int act, const SmallDesc* tab, int n_tiles, int lds_bytes, DescWarm warm, hipStream_t s,
                        unsigned long long* stamps, int launch_id) {
     const dim3 grid(n_tiles);
@@ -2743,8 +2743,8 @@ static void grouped_attrs_once() {
 
 #define AVAE_GO(CT, TNF)                                                                                                     \
     do {                                                                                                                     \
-        if (tile_cfg == 0) AVAE_LAUNCH((k_grouped<CT, 64, 64, 4, 4, TNF>), grid, block, lds_bytes, s, args, st, lds_bytes, stamps, launch_id);        \
-        else if (tile_cfg == 2) AVAE_LAUNCH((k_grouped<CT, 256, 128, 3, 8, TNF, (TNF ? kProducers : 0)>), grid, block, lds_bytes, s, args, st, lds_bytes, stamps, launch_id); \
+        if (tile_cfg == k64x64) AVAE_LAUNCH((k_grouped<CT, 64, 64, 4, 4, TNF>), grid, block, lds_bytes, s, args, st, lds_bytes, stamps, launch_id);        \
+        else if (tile_cfg == k256x128) AVAE_LAUNCH((k_grouped<CT, 256, 128, 3, 8, TNF, (TNF ? kProducers : 0)>), grid, block, lds_bytes, s, args, st, lds_bytes, stamps, launch_id); \
         else AVAE_LAUNCH((k_grouped<CT, 128, 128, 2, 4, TNF>), grid, block, lds_bytes, s, args, st, lds_bytes, stamps, launch_id);                    \
     } while (0)
 
@@ -2759,19 +2759,19 @@ static void launch_grouped_masked(int tile_cfg, const LaunchArgs& args, dim3 gri
         return true;
     }();
     (void)once;
-    if (tile_cfg == 6) AVAE_LAUNCH((k_grouped<CT, 256, 64, 3, 8, false, 0, true>), grid, block, lds_bytes, s, args, st, lds_bytes, stamps, launch_id);
-    else if (tile_cfg == 3) AVAE_LAUNCH((k_grouped<CT, 32, 64, 4, 4, false, 0, true>), grid, block, lds_bytes, s, args, st, lds_bytes, stamps, launch_id);
-    else if (tile_cfg == 5) AVAE_LAUNCH((k_grouped<CT, 32, 32, 4, 4, false, 0, true>), grid, block, lds_bytes, s, args, st, lds_bytes, stamps, launch_id);
-    else if (tile_cfg == 4) AVAE_LAUNCH((k_grouped<CT, 64, 128, 4, 4, false, 0, true>), grid, block, lds_bytes, s, args, st, lds_bytes, stamps, launch_id);
-    else if (tile_cfg == 0) AVAE_LAUNCH((k_grouped<CT, 64, 64, 4, 4, false, 0, true>), grid, block, lds_bytes, s, args, st, lds_bytes, stamps, launch_id);
-    else if (tile_cfg == 1) AVAE_LAUNCH((k_grouped<CT, 128, 128, 2, 4, false, 0, true>), grid, block, lds_bytes, s, args, st, lds_bytes, stamps, launch_id);
+    if (tile_cfg == k256x64Loss) AVAE_LAUNCH((k_grouped<CT, 256, 64, 3, 8, false, 0, true>), grid, block, lds_bytes, s, args, st, lds_bytes, stamps, launch_id);
+    else if (tile_cfg == k32x64) AVAE_LAUNCH((k_grouped<CT, 32, 64, 4, 4, false, 0, true>), grid, block, lds_bytes, s, args, st, lds_bytes, stamps, launch_id);
+    else if (tile_cfg == k32x32) AVAE_LAUNCH((k_grouped<CT, 32, 32, 4, 4, false, 0, true>), grid, block, lds_bytes, s, args, st, lds_bytes, stamps, launch_id);
+    else if (tile_cfg == k64x128) AVAE_LAUNCH((k_grouped<CT, 64, 128, 4, 4, false, 0, true>), grid, block, lds_bytes, s, args, st, lds_bytes, stamps, launch_id);
+    else if (tile_cfg == k64x64) AVAE_LAUNCH((k_grouped<CT, 64, 64, 4, 4, false, 0, true>), grid, block, lds_bytes, s, args, st, lds_bytes, stamps, launch_id);
+    else if (tile_cfg == k128x128) AVAE_LAUNCH((k_grouped<CT, 128, 128, 2, 4, false, 0, true>), grid, block, lds_bytes, s, args, st, lds_bytes, stamps, launch_id);
     else throw std::runtime_error("internal error: a masked launch on a tile configuration without the presence gate");   // (the host refuses such plans)
 }
 
 void launch_grouped(int compute_dtype, int tile_cfg, const LaunchArgs& args, int grid_x, int grid_y, int lds_bytes,
                     DevState* st, hipStream_t s, unsigned long long* stamps, int launch_id) {
     grouped_attrs_once();
-    dim3 grid(grid_x, grid_y), block(tile_cfg == 2 || tile_cfg == 6 ? 512 : kThreads);
+    dim3 grid(grid_x, grid_y), block(tile_geom(tile_cfg).threads);
     bool masked = false;
     for (int i = 0; i < args.n_items; ++i) masked = masked || args.items[i].present != nullptr;
     if (masked) {
@@ -2779,27 +2779,27 @@ void launch_grouped(int compute_dtype, int tile_cfg, const LaunchArgs& args, int
         else launch_grouped_masked<float>(tile_cfg, args, grid, block, lds_bytes, st, s, stamps, launch_id);
         return;
     }
-    if (tile_cfg == 6) {
+    if (tile_cfg == k256x64Loss) {
         if (compute_dtype == AVAE_BF16) AVAE_LAUNCH((k_grouped<__bf16, 256, 64, 3, 8, false, 0>), grid, block, lds_bytes, s, args, st, lds_bytes, stamps, launch_id);
         else AVAE_LAUNCH((k_grouped<float, 256, 64, 3, 8, false, 0>), grid, block, lds_bytes, s, args, st, lds_bytes, stamps, launch_id);
-    } else if (tile_cfg == 3) {
+    } else if (tile_cfg == k32x64) {
         if (compute_dtype == AVAE_BF16) AVAE_LAUNCH((k_grouped<__bf16, 32, 64, 4>), grid, block, lds_bytes, s, args, st, lds_bytes, stamps, launch_id);
         else AVAE_LAUNCH((k_grouped<float, 32, 64, 4>), grid, block, lds_bytes, s, args, st, lds_bytes, stamps, launch_id);
-    } else if (tile_cfg == 5) {
+    } else if (tile_cfg == k32x32) {
         if (compute_dtype == AVAE_BF16) AVAE_LAUNCH((k_grouped<__bf16, 32, 32, 4>), grid, block, lds_bytes, s, args, st, lds_bytes, stamps, launch_id);
         else AVAE_LAUNCH((k_grouped<float, 32, 32, 4>), grid, block, lds_bytes, s, args, st, lds_bytes, stamps, launch_id);
-    } else if (tile_cfg == 4) {
+    } else if (tile_cfg == k64x128) {
         if (compute_dtype == AVAE_BF16) AVAE_LAUNCH((k_grouped<__bf16, 64, 128, 4>), grid, block, lds_bytes, s, args, st, lds_bytes, stamps, launch_id);
         else AVAE_LAUNCH((k_grouped<float, 64, 128, 4>), grid, block, lds_bytes, s, args, st, lds_bytes, stamps, launch_id);
     } else if (compute_dtype == AVAE_BF16) AVAE_GO(__bf16, false);
     else AVAE_GO(float, false);
 }
 
-// The weight-gradient launches: K-major operands, compact items (tile shapes 0, 1, 2 only).
+// The weight-gradient launches: K-major operands, compact items (k64x64, k128x128, k256x128 only).
 void launch_grouped_tn(int compute_dtype, int tile_cfg, const TnLaunchArgs& args, int grid_x, int grid_y, int lds_bytes,
                        DevState* st, hipStream_t s, unsigned long long* stamps, int launch_id) {
     grouped_attrs_once();
-    dim3 grid(grid_x, grid_y), block(tile_cfg == 2 ? (8 + kProducers) * 64 : kThreads);
+    dim3 grid(grid_x, grid_y), block(tile_geom(tile_cfg).threads + (tile_geom(tile_cfg).waves8 ? kProducers * 64 : 0));      // the 8-wave TN tile: + its producer waves
     if (compute_dtype == AVAE_BF16) AVAE_GO(__bf16, true);
     else AVAE_GO(float, true);
 }
