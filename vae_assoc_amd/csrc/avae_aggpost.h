@@ -16,11 +16,7 @@
 // No atomics.  The gallery partition is a function of gallery_rows alone and every block of 8 is the gallery rows [8b, 8b + 8), so
 // the value of a query is a pure function of its own bits, its exclude entry and the gallery.
 #pragma once
-#include <stddef.h>
-#include <stdint.h>
-#include <algorithm>
-#include <hip/hip_runtime.h>
-#include "../../include/avae.h"
+#include "avae_latent_common.h"
 
 namespace avae {
 
@@ -49,10 +45,8 @@ struct AggPlan {
 inline AggPlan agg_plan(long long rows, long long gallery_rows) {
     AggPlan p;
     p.chunk_rows = (int)std::min<long long>(std::max<long long>(rows, 0), kAggChunkRows);
-    if (gallery_rows <= 0) return p;
-    const long long per = (gallery_rows + kAggMaxSlices - 1) / kAggMaxSlices;
-    p.slice_rows = (int)std::max<long long>(kAggMinSliceRows, (per + kAggGalleryTile - 1) / kAggGalleryTile * kAggGalleryTile);
-    p.n_slices = (int)((gallery_rows + p.slice_rows - 1) / p.slice_rows);
+    const RowSlices r = row_slices(gallery_rows, kAggMaxSlices, kAggMinSliceRows, kAggGalleryTile);
+    p.slice_rows = r.slice_rows; p.n_slices = r.n_slices;
     return p;
 }
 // Scratch: part[query of the chunk][slice][1 + n_z] pairs (running max, sum scaled by it) of fp32; column 0 is the joint.
@@ -67,7 +61,7 @@ constexpr size_t kAggScratchBytes = (size_t)kAggChunkRows * kAggMaxSlices * (1 +
 inline size_t agg_lds_bytes(int nz) {
     return ((size_t)nz * (kAggQueryLd + 3 * kAggGalleryLd) + (size_t)kAggWaves * kAggQueryTile * 2) * sizeof(float);
 }
-static_assert(((size_t)kAggMaxNz * (kAggQueryLd + 3 * kAggGalleryLd) + (size_t)kAggWaves * kAggQueryTile * 2) * sizeof(float) <= 160 * 1024,
+static_assert(((size_t)kAggMaxNz * (kAggQueryLd + 3 * kAggGalleryLd) + (size_t)kAggWaves * kAggQueryTile * 2) * sizeof(float) <= kMaxDynLds,
               "n_z = 64 has to fit the LDS of one CU");
 
 struct AggArgs {

@@ -3,8 +3,6 @@
 // shapes: avae_aggpost.h).  The rows x gallery_rows x n_z tensor of exponents lives in registers only.
 #include "avae_device.h"
 #include "avae_aggpost.h"
-#include <hip/hip_ext.h>
-#include "../../include/avae.h"
 
 namespace avae {
 
@@ -239,25 +237,14 @@ __global__ void __launch_bounds__(256) k_agg_logpdf_merge(AggArgs a) {
     }
 }
 
-template <typename K, typename... Args>
-void agg_launch(K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t s, const Args&... args) {
-    if (t_launch_events.start) {
-        hipExtLaunchKernelGGL(kernel, grid, block, lds, s, t_launch_events.start, t_launch_events.stop, 0, args...);
-        t_launch_events = LaunchEvents{nullptr, nullptr};
-    } else {
-        hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
-    }
-}
-
 }  // namespace
 
 void launch_agg_logpdf(const AggArgs& a, hipStream_t s) {
     const size_t lds = agg_lds_bytes(a.nz);
     const dim3 grid((unsigned)((a.rows + kAggQueryTile - 1) / kAggQueryTile), (unsigned)a.n_slices);
     auto go = [&](auto kernel) {
-        // more than 64 KiB of dynamic LDS has to be opted into (once per kernel; cheap to repeat)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        agg_launch(kernel, grid, dim3(kAggThreads), lds, s, a);
+        allow_max_lds(kernel);
+        launch_kernel(kernel, grid, dim3(kAggThreads), lds, s, a);
     };
     if (a.marginal && a.joint) go(k_agg_logpdf<true, true>);
     else if (a.marginal) go(k_agg_logpdf<true, false>);
@@ -265,7 +252,7 @@ void launch_agg_logpdf(const AggArgs& a, hipStream_t s) {
 }
 
 void launch_agg_logpdf_merge(const AggArgs& a, hipStream_t s) {
-    agg_launch(k_agg_logpdf_merge, dim3((unsigned)((a.rows + 3) / 4)), dim3(256), 0, s, a);
+    launch_kernel(k_agg_logpdf_merge, dim3((unsigned)((a.rows + 3) / 4)), dim3(256), 0, s, a);
 }
 
 }  // namespace avae

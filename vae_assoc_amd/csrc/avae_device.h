@@ -4,6 +4,7 @@
 // changes after avae_create, which is what lets the whole step be captured once as a hipGraph.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
 #include <math.h>
 #include <stdint.h>
 #include "../../include/avae.h"
@@ -751,6 +752,22 @@ void launch_wire_unpack(float* g, const void* wire, long long n, hipStream_t s);
 // the end, plus s_memtime (shader clock) at entry and end.  No stamp executes in the product build.
 struct LaunchEvents { hipEvent_t start, stop; };
 extern thread_local LaunchEvents t_launch_events;   // armed by the host in timing mode, consumed by the next launch
+// Every kernel launch of the library: the one place that knows the two modes (timing mode: avae_kernels.hip, at t_launch_events).
+template <typename K, typename... Args>
+void launch_kernel(K kernel, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t stream, const Args&... args) {
+    if (t_launch_events.start) {
+        hipExtLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, t_launch_events.start, t_launch_events.stop, 0, args...);
+        t_launch_events = LaunchEvents{nullptr, nullptr};
+    } else {
+        hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, args...);
+    }
+}
+// The LDS of one CU, all of which a kernel may ask for as dynamic LDS -- once it has opted in: more than 64 KiB has to be allowed
+// per kernel (cheap to repeat).
+constexpr size_t kMaxDynLds = 160 * 1024;
+template <typename K> void allow_max_lds(K kernel) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynLds);
+}
 
 constexpr int kStampLaunches = 32, kStampBlocks = 1024, kStampWords = 8;
 

@@ -17,11 +17,7 @@
 //   k_embed_center     subtracts the mean the last k_embed_update left in the scratch
 // No atomics, one fixed order of every sum.  The split plan is a function of rows alone.
 #pragma once
-#include <stddef.h>
-#include <stdint.h>
-#include <algorithm>
-#include <hip/hip_runtime.h>
-#include "../../include/avae.h"
+#include "avae_latent_common.h"
 
 namespace avae {
 
@@ -59,9 +55,8 @@ inline EmbedPlan embed_plan(long long rows) {
     if (rows <= 0) return p;
     const long long tiles = (rows + kEmbedTile - 1) / kEmbedTile;
     const long long want = std::max<long long>(1, std::min<long long>(tiles, (kEmbedTargetGroups + tiles - 1) / tiles));
-    const long long per = (tiles + want - 1) / want;
-    p.tiles_per_split = (int)per;
-    p.n_splits = (int)((tiles + per - 1) / per);
+    const TileSplits t = tile_splits(tiles, want, 1);
+    p.tiles_per_split = t.tiles_per_split; p.n_splits = t.n_splits;
     p.scratch_bytes = kEmbedOffPart + (kEmbedParts + 1) * (size_t)rows * p.n_splits * sizeof(double);
     return p;
 }
@@ -74,7 +69,7 @@ __host__ __device__ inline size_t embed_lds_bytes(int nz, int metric) {
     const size_t images = metric == AVAE_METRIC_L2 ? 1 : 3;
     return (2 * images * nz * kEmbedLd + 2 * (size_t)kEmbedRowWords * kEmbedTile) * sizeof(float);
 }
-static_assert((2 * (size_t)3 * kEmbedMaxNz * kEmbedLd + 2 * (size_t)kEmbedRowWords * kEmbedTile) * sizeof(float) <= 160 * 1024,
+static_assert((2 * (size_t)3 * kEmbedMaxNz * kEmbedLd + 2 * (size_t)kEmbedRowWords * kEmbedTile) * sizeof(float) <= kMaxDynLds,
               "n_z = 64 under SYMKL has to fit the LDS of one CU");
 
 struct EmbedArgs {

@@ -3,8 +3,6 @@
 // DESIGN.md section 22).  The rows x rows matrices of distances and affinities live in registers only.
 #include "avae_device.h"
 #include "avae_embed.h"
-#include <hip/hip_ext.h>
-#include "../../include/avae.h"
 
 namespace avae {
 
@@ -19,22 +17,7 @@ static_assert(PER * kEmbedThreads == T * kEmbedMaxNz && kEmbedThreads == 256 && 
 // per-row words of a tile side in LDS, [word][64]
 enum { W_BETA = 0, W_SHIFT = 1, W_C = 2, W_Y0 = 3, W_Y1 = 4, W_USED = 5, W_LO = 6, W_HI = 7 };
 
-__device__ __forceinline__ bool embed_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
-
-// One latent dimension of one pair, added to the running sum: avae_latent_topk's metric, operation for operation (include/avae.h).
-// THE distance of this file: a chain of these over j = 0 .. n_z - 1 starting from +0.0f, then embed_dist_finish.  Symmetric in its
-// two rows bit for bit (d enters squared, t as a product of both sides, iv as a sum).
-template <int METRIC>
-__device__ __forceinline__ float embed_dist_step(float acc, float mq, float vq, float iq, float mg, float vg, float ig) {
-    const float d = mq - mg;
-    if (METRIC == AVAE_METRIC_L2) return __builtin_fmaf(d, d, acc);
-    const float t = vq - vg;
-    acc = __builtin_fmaf(t * iq, t * ig, acc);
-    return __builtin_fmaf(d * d, iq + ig, acc);
-}
-template <int METRIC> __device__ __forceinline__ float embed_dist_finish(float acc) {
-    return METRIC == AVAE_METRIC_L2 ? acc : 0.5f * acc;
-}
+// The distance of a pair is avae_latent_topk's (include/avae.h): the same latent_dist_step / latent_dist_finish (avae_latent_common.h).
 
 // The tile of rows [r0, r0 + 64) on its way from memory: element e = tid + i * 256 of the tile, row-major as in memory.  Rows past
 // the end read as zeros (finite arithmetic, selected away by their used byte).
@@ -93,12 +76,12 @@ __device__ __forceinline__ void embed_dist_block(const float* qi, const float* g
 #pragma unroll
         for (int r = 0; r < 4; ++r)
 #pragma unroll
-            for (int c = 0; c < 4; ++c) D[r][c] = embed_dist_step<METRIC>(D[r][c], mqa[r], vqa[r], iqa[r], mga[c], vga[c], iga[c]);
+            for (int c = 0; c < 4; ++c) D[r][c] = latent_dist_step<METRIC>(D[r][c], mqa[r], vqa[r], iqa[r], mga[c], vga[c], iga[c]);
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r)
 #pragma unroll
-        for (int c = 0; c < 4; ++c) D[r][c] = embed_dist_finish<METRIC>(D[r][c]);
+        for (int c = 0; c < 4; ++c) D[r][c] = latent_dist_finish<METRIC>(D[r][c]);
 }
 
 // The 16 threads of a row (consecutive lanes of one wave) combined by a fixed tree; every lane ends with the result.
@@ -128,10 +111,10 @@ __global__ void __launch_bounds__(kEmbedThreads) k_embed_scan(EmbedArgs a) {
     bool ok = row < a.rows;
     if (ok) {
         const float* m = a.mu + (size_t)row * a.nz;
-        for (int j = 0; j < a.nz; ++j) ok = ok && embed_finite(m[j]);
+        for (int j = 0; j < a.nz; ++j) ok = ok && latent_finite(m[j]);
         if (a.lv) {
             const float* l = a.lv + (size_t)row * a.nz;
-            for (int j = 0; j < a.nz; ++j) ok = ok && embed_finite(l[j]);
+            for (int j = 0; j < a.nz; ++j) ok = ok && latent_finite(l[j]);
         }
         a.used[row] = ok ? 1 : 0;
     }
@@ -475,20 +458,9 @@ __global__ void __launch_bounds__(kEmbedThreads) k_embed_center(EmbedArgs a) {
     a.y[2 * row + 1] = (float)((double)a.y[2 * row + 1] - a.mean[1]);
 }
 
-template <typename K, typename... Args>
-void embed_launch(K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t s, const Args&... args) {
-    if (t_launch_events.start) {
-        hipExtLaunchKernelGGL(kernel, grid, block, lds, s, t_launch_events.start, t_launch_events.stop, 0, args...);
-        t_launch_events = LaunchEvents{nullptr, nullptr};
-    } else {
-        hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
-    }
-}
-
 template <typename K> void embed_tiled(K kernel, dim3 grid, const EmbedArgs& a, hipStream_t s) {
-    // more than 64 KiB of dynamic LDS has to be opted into (once per kernel; cheap to repeat)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    embed_launch(kernel, grid, dim3(kEmbedThreads), embed_lds_bytes(a.nz, a.metric), s, a);
+    allow_max_lds(kernel);
+    launch_kernel(kernel, grid, dim3(kEmbedThreads), embed_lds_bytes(a.nz, a.metric), s, a);
 }
 
 unsigned embed_row_blocks(const EmbedArgs& a) { return (unsigned)((a.rows + kEmbedScanRows - 1) / kEmbedScanRows); }
@@ -497,7 +469,7 @@ unsigned embed_row_tiles(const EmbedArgs& a) { return (unsigned)((a.rows + kEmbe
 }  // namespace
 
 void launch_embed_scan(const EmbedArgs& a, hipStream_t s) {
-    embed_launch(k_embed_scan, dim3(embed_row_blocks(a)), dim3(kEmbedThreads), 0, s, a);
+    launch_kernel(k_embed_scan, dim3(embed_row_blocks(a)), dim3(kEmbedThreads), 0, s, a);
 }
 
 void launch_embed_calibrate(const EmbedArgs& a, hipStream_t s) {
@@ -517,11 +489,11 @@ void launch_embed_forces(const EmbedArgs& a, hipStream_t s) {
 }
 
 void launch_embed_update(const EmbedArgs& a, hipStream_t s) {
-    embed_launch(k_embed_update, dim3(embed_row_blocks(a)), dim3(kEmbedThreads), 0, s, a);
+    launch_kernel(k_embed_update, dim3(embed_row_blocks(a)), dim3(kEmbedThreads), 0, s, a);
 }
 
 void launch_embed_center(const EmbedArgs& a, hipStream_t s) {
-    embed_launch(k_embed_center, dim3(embed_row_blocks(a)), dim3(kEmbedThreads), 0, s, a);
+    launch_kernel(k_embed_center, dim3(embed_row_blocks(a)), dim3(kEmbedThreads), 0, s, a);
 }
 
 }  // namespace avae

@@ -16,11 +16,7 @@
 // avae_gmm_score is k_gmm_estep with the per-row outputs switched on and the sums switched off.
 // No atomics, one fixed order of every sum.  The row partition is a function of rows alone.
 #pragma once
-#include <stddef.h>
-#include <stdint.h>
-#include <algorithm>
-#include <hip/hip_runtime.h>
-#include "../../include/avae.h"
+#include "avae_latent_common.h"
 
 namespace avae {
 
@@ -42,12 +38,8 @@ struct GmmPlan {
 
 // The row partition: a function of rows alone.
 inline GmmPlan gmm_plan(long long rows) {
-    GmmPlan p;
-    if (rows <= 0) return p;
-    const long long per = (rows + kGmmMaxSlices - 1) / kGmmMaxSlices;
-    p.slice_rows = (int)std::max<long long>(kGmmMinSliceRows, (per + kGmmTile - 1) / kGmmTile * kGmmTile);
-    p.n_slices = (int)((rows + p.slice_rows - 1) / p.slice_rows);
-    return p;
+    const RowSlices r = row_slices(rows, kGmmMaxSlices, kGmmMinSliceRows, kGmmTile);
+    return GmmPlan{r.slice_rows, r.n_slices};
 }
 
 // Scratch, in doubles.  The partial of a slice at slice * gmm_part_stride(K, nz):

@@ -3,8 +3,6 @@
 // avae_gmm.h).  The rows x K x n_z tensor of exponents lives in registers only.
 #include "avae_device.h"
 #include "avae_gmm.h"
-#include <hip/hip_ext.h>
-#include "../../include/avae.h"
 
 namespace avae {
 
@@ -15,8 +13,6 @@ namespace {
 #pragma clang fp contract(off)
 
 constexpr float kLog2PiF = 1.83787706640934548356f;
-
-__device__ __forceinline__ bool gmm_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
 
 // grid = row slices, kGmmThreads threads.  STATS 0: per-row outputs only (avae_gmm_score); 1: the slice's sufficient statistics;
 // 2: the slice's sum of ll and used-row count only (the pass that scores the returned parameters).
@@ -91,7 +87,7 @@ __global__ void __launch_bounds__(kGmmThreads) k_gmm_estep(GmmArgs a) {
             if (e < n_el) {
                 const int row = e / nz, j = e - row * nz;
                 const float x = fm[i], g = fl[i];
-                if (!gmm_finite(x) || !gmm_finite(g)) s_bad[row] = 1;
+                if (!latent_finite(x) || !latent_finite(g)) s_bad[row] = 1;
                 mt[j * LD + row] = x;
                 vt[j * LD + row] = a.lv ? expf(g) : 0.0f;          // (rows past the end: expf(0) = 1, finite; r = 0)
             }
@@ -308,24 +304,13 @@ __global__ void __launch_bounds__(kGmmThreads) k_gmm_mstep(GmmArgs a) {
     a.s_out[e] = (float)log(var);
 }
 
-template <typename K, typename... Args>
-void gmm_launch(K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t s, const Args&... args) {
-    if (t_launch_events.start) {
-        hipExtLaunchKernelGGL(kernel, grid, block, lds, s, t_launch_events.start, t_launch_events.stop, 0, args...);
-        t_launch_events = LaunchEvents{nullptr, nullptr};
-    } else {
-        hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
-    }
-}
-
 }  // namespace
 
 void launch_gmm_estep(const GmmArgs& a, hipStream_t s) {
     const size_t lds = gmm_lds_bytes(a.K, a.nz);
     auto go = [&](auto kernel) {
-        // more than 64 KiB of dynamic LDS has to be opted into (once per kernel; cheap to repeat)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        gmm_launch(kernel, dim3((unsigned)a.n_slices), dim3(kGmmThreads), lds, s, a);
+        allow_max_lds(kernel);
+        launch_kernel(kernel, dim3((unsigned)a.n_slices), dim3(kGmmThreads), lds, s, a);
     };
     if (a.want_stats == 0) go(k_gmm_estep<0>);
     else if (a.want_stats == 1) go(k_gmm_estep<1>);
@@ -334,7 +319,7 @@ void launch_gmm_estep(const GmmArgs& a, hipStream_t s) {
 
 void launch_gmm_mstep(const GmmArgs& a, hipStream_t s) {
     const unsigned blocks = a.final_pass ? 1u : (unsigned)((a.K * a.nz + kGmmThreads - 1) / kGmmThreads);
-    gmm_launch(k_gmm_mstep, dim3(blocks), dim3(kGmmThreads), 0, s, a);
+    launch_kernel(k_gmm_mstep, dim3(blocks), dim3(kGmmThreads), 0, s, a);
 }
 
 }  // namespace avae

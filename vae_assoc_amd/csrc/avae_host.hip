@@ -3751,6 +3751,39 @@ void destroy_handle(avae_handle* h) {
     if (prev_dev >= 0 && prev_dev != dev) (void)hipSetDevice(prev_dev);
 }
 
+// ---- the latent-space features (DESIGN.md sections 18-23): what their entry points (in the C ABI below) share
+// A *_plan query: it has no handle, so what it throws goes where avae_create's errors go.
+template <typename F> int plan_query(const avae_config* cfg, F&& query) {
+    try {
+        if (!cfg) throw Err("null argument");
+        check_config(*cfg);
+        query();
+        return 0;
+    } catch (const std::exception& e) { g_create_error = e.what(); return 2; }
+}
+template <typename T> void put(T* out, T v) { if (out) *out = v; }     // an optional output
+void need(const std::string& w, const void* p, const char* name, const char* why = nullptr) {
+    if (!p) throw Err(w + ": " + name + " is NULL" + (why ? " (" + std::string(why) + ")" : std::string()));
+}
+void check_rows(const std::string& w, long long rows, const char* name) {
+    if (rows < 0) throw Err(w + ": " + name + " must be >= 0");
+}
+bool check_metric(const std::string& w, int32_t metric) {             // true: AVAE_METRIC_SYMKL
+    if (metric != AVAE_METRIC_SYMKL && metric != AVAE_METRIC_L2)
+        throw Err(w + ": metric = " + std::to_string(metric) + " is neither AVAE_METRIC_SYMKL nor AVAE_METRIC_L2");
+    return metric == AVAE_METRIC_SYMKL;
+}
+const char* const kNeedsLogvar = "AVAE_METRIC_SYMKL reads the log-variances";
+// The handle's scratch of a feature, allocated once at its bound.  A plan beyond the bound (lds_bytes given: or beyond a CU's LDS)
+// is a mistake of the plan, not of the caller.
+template <typename T>
+T* scratch_of(DevBuf& buf, const std::string& w, size_t need_bytes, size_t bound_bytes, size_t lds_bytes = 0) {
+    if (need_bytes > bound_bytes || lds_bytes > kMaxDynLds)
+        throw Err("internal error: " + w + " plans more " + (lds_bytes ? "scratch or LDS" : "scratch") + " than its bound");
+    return static_cast<T*>(buf.ensure(bound_bytes));
+}
+template <typename T> T zeroed() { T a; std::memset(&a, 0, sizeof(a)); return a; }   // kernel arguments start as zeros, pads included
+
 }  // namespace
 
 // ============================================================================= C ABI
@@ -4600,23 +4633,18 @@ int avae_complete(avae_handle* h, const float* const* x_dev, const int32_t* x_ld
 static void check_topk_shape(const std::string& w, int32_t rows, int32_t gallery_rows, int32_t k) {
     if (k < 1 || k > AVAE_TOPK_MAX)
         throw Err(w + ": k = " + std::to_string(k) + " must be in [1, " + std::to_string(AVAE_TOPK_MAX) + "] (AVAE_TOPK_MAX)");
-    if (rows < 0) throw Err(w + ": rows must be >= 0");
-    if (gallery_rows < 0) throw Err(w + ": gallery_rows must be >= 0");
+    check_rows(w, rows, "rows");
+    check_rows(w, gallery_rows, "gallery_rows");
 }
 
 int avae_latent_topk_plan(const avae_config* cfg, int32_t rows, int32_t gallery_rows, int32_t k, int32_t* query_tile,
                           int32_t* gallery_tile, int32_t* n_splits, size_t* scratch_bytes) {
-    try {
-        if (!cfg) throw Err("null argument");
-        check_config(*cfg);
+    return plan_query(cfg, [&] {
         check_topk_shape("avae_latent_topk_plan", rows, gallery_rows, k);
         const TopkPlan p = topk_plan(rows, gallery_rows, k);
-        if (query_tile) *query_tile = p.query_tile;
-        if (gallery_tile) *gallery_tile = p.gallery_tile;
-        if (n_splits) *n_splits = p.n_splits;
-        if (scratch_bytes) *scratch_bytes = p.scratch_bytes;
-        return 0;
-    } catch (const std::exception& e) { g_create_error = e.what(); return 2; }
+        put(query_tile, p.query_tile); put(gallery_tile, p.gallery_tile); put(n_splits, p.n_splits);
+        put(scratch_bytes, p.scratch_bytes);
+    });
 }
 
 int avae_latent_topk(avae_handle* h, const float* q_mu_dev, const float* q_logvar_dev, int32_t rows, const float* g_mu_dev,
@@ -4625,25 +4653,21 @@ int avae_latent_topk(avae_handle* h, const float* q_mu_dev, const float* q_logva
     return guarded(h, [&] {
         const std::string w = "avae_latent_topk";
         check_topk_shape(w, rows, gallery_rows, k);
-        if (metric != AVAE_METRIC_SYMKL && metric != AVAE_METRIC_L2)
-            throw Err(w + ": metric = " + std::to_string(metric) + " is neither AVAE_METRIC_SYMKL nor AVAE_METRIC_L2");
-        const bool kl = metric == AVAE_METRIC_SYMKL;
-        if (rows > 0 && !q_mu_dev) throw Err(w + ": q_mu_dev is NULL");
-        if (gallery_rows > 0 && !g_mu_dev) throw Err(w + ": g_mu_dev is NULL");
-        if (kl && rows > 0 && !q_logvar_dev) throw Err(w + ": q_logvar_dev is NULL (AVAE_METRIC_SYMKL reads the log-variances)");
-        if (kl && gallery_rows > 0 && !g_logvar_dev) throw Err(w + ": g_logvar_dev is NULL (AVAE_METRIC_SYMKL reads the log-variances)");
+        const bool kl = check_metric(w, metric);
+        if (rows > 0) need(w, q_mu_dev, "q_mu_dev");
+        if (gallery_rows > 0) need(w, g_mu_dev, "g_mu_dev");
+        if (kl && rows > 0) need(w, q_logvar_dev, "q_logvar_dev", kNeedsLogvar);
+        if (kl && gallery_rows > 0) need(w, g_logvar_dev, "g_logvar_dev", kNeedsLogvar);
         if (rows == 0 || (!index_dev && !dist_dev)) return;
         static_assert(kTopkMaxNz >= 64, "check_config bounds n_z by 64");
         const int nz = h->nz;
         const TopkPlan p = topk_plan(rows, gallery_rows, k);
-        if (p.scratch_bytes > kTopkScratchBytes) throw Err("internal error: " + w + " plans more scratch than its bound");
         hipStream_t s = on_stream(h, stream);
-        TopkArgs a;
-        std::memset(&a, 0, sizeof(a));
+        TopkArgs a = zeroed<TopkArgs>();
         a.g_mu = g_mu_dev; a.g_lv = kl ? g_logvar_dev : nullptr;
         a.gallery_rows = gallery_rows; a.nz = nz; a.k = k; a.metric = metric;
         a.n_splits = p.n_splits; a.tiles_per_split = p.tiles_per_split;
-        if (p.n_splits > 0) a.part = static_cast<unsigned long long*>(h->topk_buf.ensure(kTopkScratchBytes));
+        if (p.n_splits > 0) a.part = scratch_of<unsigned long long>(h->topk_buf, w, p.scratch_bytes, kTopkScratchBytes);
         for (int r0 = 0; r0 < rows; r0 += p.chunk_rows) {
             a.rows = std::min(p.chunk_rows, rows - r0);
             a.q_mu = q_mu_dev + (size_t)r0 * nz;
@@ -4658,16 +4682,12 @@ int avae_latent_topk(avae_handle* h, const float* q_mu_dev, const float* q_logva
 
 // ---- per-dimension posterior diagnostics (include/avae.h, avae_latent_stats.h)
 int avae_latent_stats_plan(const avae_config* cfg, int32_t rows, int32_t* row_tile, int32_t* n_slices, size_t* scratch_bytes) {
-    try {
-        if (!cfg) throw Err("null argument");
-        check_config(*cfg);
-        if (rows < 0) throw Err("avae_latent_stats_plan: rows must be >= 0");
+    return plan_query(cfg, [&] {
+        check_rows("avae_latent_stats_plan", rows, "rows");
         const StatsPlan p = stats_plan(rows);
-        if (row_tile) *row_tile = p.row_tile;
-        if (n_slices) *n_slices = p.n_slices;
-        if (scratch_bytes) *scratch_bytes = stats_scratch_bytes(p.n_slices, cfg->n_modalities, cfg->n_z);
-        return 0;
-    } catch (const std::exception& e) { g_create_error = e.what(); return 2; }
+        put(row_tile, p.row_tile); put(n_slices, p.n_slices);
+        put(scratch_bytes, stats_scratch_bytes(p.n_slices, cfg->n_modalities, cfg->n_z));
+    });
 }
 
 int avae_latent_stats(avae_handle* h, int32_t n_mod, const float* const* mu_dev, const float* const* logvar_dev,
@@ -4676,25 +4696,22 @@ int avae_latent_stats(avae_handle* h, int32_t n_mod, const float* const* mu_dev,
         const std::string w = "avae_latent_stats";
         if (n_mod < 1 || n_mod > AVAE_MAX_MODALITIES)
             throw Err(w + ": n_mod = " + std::to_string(n_mod) + " must be in [1, " + std::to_string(AVAE_MAX_MODALITIES) + "] (AVAE_MAX_MODALITIES)");
-        if (rows < 0) throw Err(w + ": rows must be >= 0");
-        if (!out) throw Err(w + ": out is NULL");
-        if (!mu_dev) throw Err(w + ": mu_dev is NULL (the array of pointers; a NULL entry marks an absent modality)");
+        check_rows(w, rows, "rows");
+        need(w, out, "out");
+        need(w, mu_dev, "mu_dev", "the array of pointers; a NULL entry marks an absent modality");
         for (int m = 0; m < n_mod; ++m)
             if (mu_dev[m] && (!logvar_dev || !logvar_dev[m]))
                 throw Err(w + ": logvar_dev[" + std::to_string(m) + "] is NULL while mu_dev[" + std::to_string(m) + "] is given");
         if (!out->count && !out->mean && !out->var && !out->xcov && !out->assoc && !out->post_var && !out->kl && !out->cov) return;
         static_assert(kStatsMaxNz >= 64 && kMaxMod == AVAE_MAX_MODALITIES, "check_config bounds n_z by 64");
         const StatsPlan p = stats_plan(rows);
-        if (stats_scratch_bytes(p.n_slices, n_mod, h->nz) > kStatsScratchBytes)
-            throw Err("internal error: " + w + " plans more scratch than its bound");
         hipStream_t s = on_stream(h, stream);
-        StatsArgs a;
-        std::memset(&a, 0, sizeof(a));
+        StatsArgs a = zeroed<StatsArgs>();
         for (int m = 0; m < n_mod; ++m) { a.mu[m] = mu_dev[m]; a.lv[m] = mu_dev[m] ? logvar_dev[m] : nullptr; }
         a.present = present_dev; a.rows = rows; a.n_mod = n_mod; a.nz = h->nz;
         a.n_slices = p.n_slices; a.row_tile = p.row_tile; a.want_cov = out->cov ? 1 : 0; a.out = *out;
         if (p.n_slices > 0) {
-            a.scratch = static_cast<double*>(h->stats_buf.ensure(kStatsScratchBytes));
+            a.scratch = scratch_of<double>(h->stats_buf, w, stats_scratch_bytes(p.n_slices, n_mod, h->nz), kStatsScratchBytes);
             timed_launch(h, s, "latent_stats", [&] { launch_latent_stats(a, s); });
         }
         timed_launch(h, s, "latent_stats_merge", [&] { launch_latent_stats_merge(a, s); });
@@ -4707,7 +4724,7 @@ static void check_motion_shape(const std::string& w, int32_t rows, int32_t D, in
         if (v < lo || v > hi)
             throw Err(w + ": " + name + " = " + std::to_string(v) + " must be in [" + std::to_string(lo) + ", " + std::to_string(hi) + "]");
     };
-    if (rows < 0) throw Err(w + ": rows must be >= 0");
+    check_rows(w, rows, "rows");
     range("D", D, 1, kMotionMaxD);
     range("Kb", Kb, 1, kMotionMaxKb);
     range("T", T, 1, kMotionMaxT);
@@ -4719,13 +4736,12 @@ static MotionArgs motion_args(const std::string& w, const float* params, int32_t
                               const float* target, int32_t nc, bool moments) {
     check_motion_shape(w, rows, D, Kb, T, nc);
     if (S < 1) throw Err(w + ": S = " + std::to_string(S) + " must be >= 1");
-    if (!params) throw Err(w + (moments ? ": samples_dev is NULL" : ": params_dev is NULL"));
-    if (!phi) throw Err(w + ": phi_dev is NULL");
+    need(w, params, moments ? "samples_dev" : "params_dev");
+    need(w, phi, "phi_dev");
     if (nc > 0 && !gain) throw Err(w + ": anchor_gain_dev is NULL with nc > 0");
     if (nc > 0 && !target) throw Err(w + ": anchor_target_dev is NULL with nc > 0");
     if (motion_lds_bytes(D, Kb, T, nc, moments, true) > kMotionMaxLds) throw Err("internal error: " + w + " plans more LDS than its bound");
-    MotionArgs a;
-    std::memset(&a, 0, sizeof(a));
+    MotionArgs a = zeroed<MotionArgs>();
     a.params = params; a.phi = phi; a.scale = scale; a.shift = shift; a.limits = limits;
     a.gain = nc > 0 ? gain : nullptr; a.target = nc > 0 ? target : nullptr;
     a.rows = rows; a.S = S; a.D = D; a.Kb = Kb; a.T = T; a.nc = nc;
@@ -4759,12 +4775,9 @@ int avae_motion_fit(avae_handle* h, const float* traj_dev, int32_t rows, int32_t
     return guarded(h, [&] {
         const std::string w = "avae_motion_fit";
         check_motion_shape(w, rows, D, Kb, T, 0);
-        if (!traj_dev) throw Err(w + ": traj_dev is NULL");
-        if (!pinv_dev) throw Err(w + ": pinv_dev is NULL");
-        if (!params_dev) throw Err(w + ": params_dev is NULL");
+        need(w, traj_dev, "traj_dev"); need(w, pinv_dev, "pinv_dev"); need(w, params_dev, "params_dev");
         if (rows == 0) return;
-        MotionFitArgs a;
-        std::memset(&a, 0, sizeof(a));
+        MotionFitArgs a = zeroed<MotionFitArgs>();
         a.traj = traj_dev; a.pinv = pinv_dev; a.scale = scale_dev; a.shift = shift_dev; a.params = params_dev;
         a.rows = rows; a.D = D; a.Kb = Kb; a.T = T;
         hipStream_t s = on_stream(h, stream);
@@ -4780,7 +4793,7 @@ int avae_motion_moments(avae_handle* h, const float* samples_dev, int32_t rows, 
         const std::string w = "avae_motion_moments";
         MotionArgs a = motion_args(w, samples_dev, rows, S, D, Kb, T, phi_dev, scale_dev, shift_dev, limits_dev, anchor_gain_dev,
                                    anchor_target_dev, nc, true);
-        if (!mean_dev) throw Err(w + ": mean_dev is NULL");
+        need(w, mean_dev, "mean_dev");
         if (rows == 0) return;
         a.traj = mean_dev; a.var = var_dev; a.sat_frac = saturated_frac_dev;
         hipStream_t s = on_stream(h, stream);
@@ -4790,24 +4803,18 @@ int avae_motion_moments(avae_handle* h, const float* samples_dev, int32_t rows, 
 
 // ---- aggregate-posterior log-density (include/avae.h, avae_aggpost.h)
 static void check_agg_shape(const std::string& w, int32_t rows, int32_t gallery_rows) {
-    if (rows < 0) throw Err(w + ": rows must be >= 0");
-    if (gallery_rows < 0) throw Err(w + ": gallery_rows must be >= 0");
+    check_rows(w, rows, "rows");
+    check_rows(w, gallery_rows, "gallery_rows");
 }
 
 int avae_agg_logpdf_plan(const avae_config* cfg, int32_t rows, int32_t gallery_rows, int32_t* query_tile, int32_t* chunk_rows,
                          int32_t* slice_rows, int32_t* n_slices, size_t* scratch_bytes) {
-    try {
-        if (!cfg) throw Err("null argument");
-        check_config(*cfg);
+    return plan_query(cfg, [&] {
         check_agg_shape("avae_agg_logpdf_plan", rows, gallery_rows);
         const AggPlan p = agg_plan(rows, gallery_rows);
-        if (query_tile) *query_tile = p.query_tile;
-        if (chunk_rows) *chunk_rows = p.chunk_rows;
-        if (slice_rows) *slice_rows = p.slice_rows;
-        if (n_slices) *n_slices = p.n_slices;
-        if (scratch_bytes) *scratch_bytes = agg_scratch_bytes(p, cfg->n_z);
-        return 0;
-    } catch (const std::exception& e) { g_create_error = e.what(); return 2; }
+        put(query_tile, p.query_tile); put(chunk_rows, p.chunk_rows); put(slice_rows, p.slice_rows); put(n_slices, p.n_slices);
+        put(scratch_bytes, agg_scratch_bytes(p, cfg->n_z));
+    });
 }
 
 int avae_agg_logpdf(avae_handle* h, const float* z_dev, int32_t rows, const float* g_mu_dev, const float* g_logvar_dev,
@@ -4815,22 +4822,18 @@ int avae_agg_logpdf(avae_handle* h, const float* z_dev, int32_t rows, const floa
     return guarded(h, [&] {
         const std::string w = "avae_agg_logpdf";
         check_agg_shape(w, rows, gallery_rows);
-        if (rows > 0 && !z_dev) throw Err(w + ": z_dev is NULL");
-        if (gallery_rows > 0 && !g_mu_dev) throw Err(w + ": g_mu_dev is NULL");
-        if (gallery_rows > 0 && !g_logvar_dev) throw Err(w + ": g_logvar_dev is NULL");
+        if (rows > 0) need(w, z_dev, "z_dev");
+        if (gallery_rows > 0) { need(w, g_mu_dev, "g_mu_dev"); need(w, g_logvar_dev, "g_logvar_dev"); }
         if (!joint_dev && !marginal_dev) throw Err(w + ": joint_dev and marginal_dev are both NULL");
         if (rows == 0) return;
         static_assert(kAggMaxNz >= 64, "check_config bounds n_z by 64");
         const int nz = h->nz;
         const AggPlan p = agg_plan(rows, gallery_rows);
-        if (agg_scratch_bytes(p, nz) > kAggScratchBytes || agg_lds_bytes(nz) > 160 * 1024)
-            throw Err("internal error: " + w + " plans more scratch or LDS than its bound");
         hipStream_t s = on_stream(h, stream);
-        AggArgs a;
-        std::memset(&a, 0, sizeof(a));
+        AggArgs a = zeroed<AggArgs>();
         a.g_mu = g_mu_dev; a.g_lv = g_logvar_dev; a.gallery_rows = gallery_rows; a.nz = nz;
         a.n_slices = p.n_slices; a.slice_rows = p.slice_rows;
-        if (p.n_slices > 0) a.part = static_cast<float2*>(h->agg_buf.ensure(kAggScratchBytes));
+        if (p.n_slices > 0) a.part = scratch_of<float2>(h->agg_buf, w, agg_scratch_bytes(p, nz), kAggScratchBytes, agg_lds_bytes(nz));
         for (int r0 = 0; r0 < rows; r0 += p.chunk_rows) {
             a.rows = std::min(p.chunk_rows, rows - r0);
             a.z = z_dev + (size_t)r0 * nz;
@@ -4845,23 +4848,19 @@ int avae_agg_logpdf(avae_handle* h, const float* z_dev, int32_t rows, const floa
 
 // ---- mixture prior fitted to the posteriors (include/avae.h, avae_gmm.h)
 static void check_gmm_shape(const std::string& w, int32_t rows, int32_t K) {
-    if (rows < 0) throw Err(w + ": rows must be >= 0");
+    check_rows(w, rows, "rows");
     if (K < 1 || K > kGmmMaxK)
         throw Err(w + ": n_components = " + std::to_string(K) + " must be in [1, " + std::to_string(kGmmMaxK) + "]");
 }
 
 int avae_gmm_plan(const avae_config* cfg, int32_t rows, int32_t n_components, int32_t* slice_rows, int32_t* n_slices,
                   size_t* scratch_bytes) {
-    try {
-        if (!cfg) throw Err("null argument");
-        check_config(*cfg);
+    return plan_query(cfg, [&] {
         check_gmm_shape("avae_gmm_plan", rows, n_components);
         const GmmPlan p = gmm_plan(rows);
-        if (slice_rows) *slice_rows = p.slice_rows;
-        if (n_slices) *n_slices = p.n_slices;
-        if (scratch_bytes) *scratch_bytes = gmm_scratch_bytes(p.n_slices, n_components, cfg->n_z);
-        return 0;
-    } catch (const std::exception& e) { g_create_error = e.what(); return 2; }
+        put(slice_rows, p.slice_rows); put(n_slices, p.n_slices);
+        put(scratch_bytes, gmm_scratch_bytes(p.n_slices, n_components, cfg->n_z));
+    });
 }
 
 int avae_gmm_fit(avae_handle* h, const float* mu_dev, const float* logvar_dev, int32_t rows, int32_t n_components, int32_t n_iters,
@@ -4872,23 +4871,17 @@ int avae_gmm_fit(avae_handle* h, const float* mu_dev, const float* logvar_dev, i
         check_gmm_shape(w, rows, n_components);
         if (n_iters < 0) throw Err(w + ": n_iters must be >= 0");
         if (!(var_floor > 0.0f) || !std::isfinite(var_floor)) throw Err(w + ": var_floor must be positive and finite");
-        if (rows > 0 && !mu_dev) throw Err(w + ": mu_dev is NULL");
-        if (!weights_dev) throw Err(w + ": weights_dev is NULL");
-        if (!means_dev) throw Err(w + ": means_dev is NULL");
-        if (!logvars_dev) throw Err(w + ": logvars_dev is NULL");
-        if (!bound_dev) throw Err(w + ": bound_dev is NULL");
-        if (!n_used_dev) throw Err(w + ": n_used_dev is NULL");
+        if (rows > 0) need(w, mu_dev, "mu_dev");
+        need(w, weights_dev, "weights_dev"); need(w, means_dev, "means_dev"); need(w, logvars_dev, "logvars_dev");
+        need(w, bound_dev, "bound_dev"); need(w, n_used_dev, "n_used_dev");
         static_assert(kGmmMaxNz >= 64, "check_config bounds n_z by 64");
         const int nz = h->nz, K = n_components;
         const GmmPlan p = gmm_plan(rows);
-        if (gmm_scratch_bytes(p.n_slices, K, nz) > kGmmScratchBytes || gmm_lds_bytes(K, nz) > 160 * 1024)
-            throw Err("internal error: " + w + " plans more scratch or LDS than its bound");
         hipStream_t s = on_stream(h, stream);
-        GmmArgs a;
-        std::memset(&a, 0, sizeof(a));
+        GmmArgs a = zeroed<GmmArgs>();
         a.mu = mu_dev; a.lv = logvar_dev; a.rows = rows; a.nz = nz; a.K = K;
         a.n_slices = p.n_slices; a.slice_rows = p.slice_rows; a.var_floor = var_floor; a.n_used = n_used_dev;
-        a.part = static_cast<double*>(h->gmm_buf.ensure(kGmmScratchBytes));
+        a.part = scratch_of<double>(h->gmm_buf, w, gmm_scratch_bytes(p.n_slices, K, nz), kGmmScratchBytes, gmm_lds_bytes(K, nz));
         // iteration t reads the set iteration t - 1 wrote: the caller's arrays first, the scratch's two sets in turn between, and the
         // last one writes the caller's arrays again (every element is read and written by the same thread where the two coincide)
         const size_t pf = gmm_param_floats(K, nz);
@@ -4918,18 +4911,15 @@ int avae_gmm_score(avae_handle* h, const float* mu_dev, const float* logvar_dev,
     return guarded(h, [&] {
         const std::string w = "avae_gmm_score";
         check_gmm_shape(w, rows, n_components);
-        if (rows > 0 && !mu_dev) throw Err(w + ": mu_dev is NULL");
-        if (!weights_dev) throw Err(w + ": weights_dev is NULL");
-        if (!means_dev) throw Err(w + ": means_dev is NULL");
-        if (!logvars_dev) throw Err(w + ": logvars_dev is NULL");
+        if (rows > 0) need(w, mu_dev, "mu_dev");
+        need(w, weights_dev, "weights_dev"); need(w, means_dev, "means_dev"); need(w, logvars_dev, "logvars_dev");
         if (!ll_dev && !component_dev && !resp_dev) throw Err(w + ": ll_dev, component_dev and resp_dev are all NULL");
         if (rows == 0) return;
         const int nz = h->nz;
         const GmmPlan p = gmm_plan(rows);
-        if (gmm_lds_bytes(n_components, nz) > 160 * 1024) throw Err("internal error: " + w + " plans more LDS than its bound");
+        if (gmm_lds_bytes(n_components, nz) > kMaxDynLds) throw Err("internal error: " + w + " plans more LDS than its bound");
         hipStream_t s = on_stream(h, stream);
-        GmmArgs a;
-        std::memset(&a, 0, sizeof(a));
+        GmmArgs a = zeroed<GmmArgs>();
         a.mu = mu_dev; a.lv = logvar_dev; a.rows = rows; a.nz = nz; a.K = n_components;
         a.n_slices = p.n_slices; a.slice_rows = p.slice_rows;
         a.w_in = weights_dev; a.m_in = means_dev; a.s_in = logvars_dev;
@@ -4940,27 +4930,20 @@ int avae_gmm_score(avae_handle* h, const float* mu_dev, const float* logvar_dev,
 
 // ---- 2-D t-SNE map of the posteriors (include/avae.h, avae_embed.h)
 static bool check_embed_shape(const std::string& w, int32_t rows, int32_t metric) {
-    if (rows < 0) throw Err(w + ": rows must be >= 0");
+    check_rows(w, rows, "rows");
     if (rows > kEmbedMaxRows)
         throw Err(w + ": rows = " + std::to_string(rows) + " is more than " + std::to_string(kEmbedMaxRows) + " (the work is quadratic in rows)");
-    if (metric != AVAE_METRIC_SYMKL && metric != AVAE_METRIC_L2)
-        throw Err(w + ": metric = " + std::to_string(metric) + " is neither AVAE_METRIC_SYMKL nor AVAE_METRIC_L2");
-    return metric == AVAE_METRIC_SYMKL;
+    return check_metric(w, metric);
 }
 
 int avae_embed_plan(const avae_config* cfg, int32_t rows, int32_t* row_tile, int32_t* n_splits, int32_t* tiles_per_split,
                     size_t* scratch_bytes) {
-    try {
-        if (!cfg) throw Err("null argument");
-        check_config(*cfg);
+    return plan_query(cfg, [&] {
         check_embed_shape("avae_embed_plan", rows, AVAE_METRIC_L2);
         const EmbedPlan p = embed_plan(rows);
-        if (row_tile) *row_tile = p.row_tile;
-        if (n_splits) *n_splits = p.n_splits;
-        if (tiles_per_split) *tiles_per_split = p.tiles_per_split;
-        if (scratch_bytes) *scratch_bytes = p.scratch_bytes;
-        return 0;
-    } catch (const std::exception& e) { g_create_error = e.what(); return 2; }
+        put(row_tile, p.row_tile); put(n_splits, p.n_splits); put(tiles_per_split, p.tiles_per_split);
+        put(scratch_bytes, p.scratch_bytes);
+    });
 }
 
 // the fields every launch of the family reads, and the scratch
@@ -4968,11 +4951,9 @@ static EmbedArgs embed_args(avae_handle* h, const std::string& w, const float* m
     static_assert(kEmbedMaxNz >= 64, "check_config bounds n_z by 64");
     const EmbedPlan p = embed_plan(rows);
     const int metric = kl ? AVAE_METRIC_SYMKL : AVAE_METRIC_L2;
-    if ((size_t)rows * p.n_splits > kEmbedMaxSlots || p.scratch_bytes > kEmbedScratchBytes || embed_lds_bytes(h->nz, metric) > 160 * 1024)
-        throw Err("internal error: " + w + " plans more scratch or LDS than its bound");
-    unsigned char* base = static_cast<unsigned char*>(h->embed_buf.ensure(kEmbedScratchBytes));
-    EmbedArgs a;
-    std::memset(&a, 0, sizeof(a));
+    static_assert(kEmbedOffPart + (kEmbedParts + 1) * kEmbedMaxSlots * sizeof(double) == kEmbedScratchBytes, "the bytes bound the slots");
+    unsigned char* base = scratch_of<unsigned char>(h->embed_buf, w, p.scratch_bytes, kEmbedScratchBytes, embed_lds_bytes(h->nz, metric));
+    EmbedArgs a = zeroed<EmbedArgs>();
     a.mu = mu_dev; a.lv = kl ? logvar_dev : nullptr;           // the L2 metric never reads the log-variances
     a.rows = rows; a.nz = h->nz; a.metric = metric;
     a.n_splits = p.n_splits; a.tiles_per_split = p.tiles_per_split;
@@ -4996,13 +4977,10 @@ int avae_embed_calibrate(avae_handle* h, const float* mu_dev, const float* logva
             throw Err(w + ": perplexity must be in [1, rows - 1] = [1, " + std::to_string(rows - 1) + "]");
         if (!(tol > 0.0)) throw Err(w + ": tol must be > 0");
         if (max_tries < 1) throw Err(w + ": max_tries must be >= 1");
-        if (!mu_dev) throw Err(w + ": mu_dev is NULL");
-        if (kl && !logvar_dev) throw Err(w + ": logvar_dev is NULL (AVAE_METRIC_SYMKL reads the log-variances)");
-        if (!beta_dev) throw Err(w + ": beta_dev is NULL");
-        if (!shift_dev) throw Err(w + ": shift_dev is NULL");
-        if (!norm_dev) throw Err(w + ": norm_dev is NULL");
-        if (!tries_dev) throw Err(w + ": tries_dev is NULL");
-        if (!n_used_dev) throw Err(w + ": n_used_dev is NULL");
+        need(w, mu_dev, "mu_dev");
+        if (kl) need(w, logvar_dev, "logvar_dev", kNeedsLogvar);
+        need(w, beta_dev, "beta_dev"); need(w, shift_dev, "shift_dev"); need(w, norm_dev, "norm_dev");
+        need(w, tries_dev, "tries_dev"); need(w, n_used_dev, "n_used_dev");
         EmbedArgs a = embed_args(h, w, mu_dev, logvar_dev, rows, kl);
         hipStream_t s = on_stream(h, stream);
         a.beta = beta_dev; a.shift = shift_dev; a.norm = norm_dev; a.tries = tries_dev; a.n_used = n_used_dev;
@@ -5023,15 +5001,10 @@ int avae_embed_iterate(avae_handle* h, const float* mu_dev, const float* logvar_
         if (n_iters < 0) throw Err(w + ": n_iters must be >= 0");
         if (it0 < 0) throw Err(w + ": it0 must be >= 0");
         if (!(learning_rate > 0.0f) || !std::isfinite(learning_rate)) throw Err(w + ": learning_rate must be positive and finite");
-        if (!mu_dev) throw Err(w + ": mu_dev is NULL");
-        if (kl && !logvar_dev) throw Err(w + ": logvar_dev is NULL (AVAE_METRIC_SYMKL reads the log-variances)");
-        if (!beta_dev) throw Err(w + ": beta_dev is NULL");
-        if (!shift_dev) throw Err(w + ": shift_dev is NULL");
-        if (!norm_dev) throw Err(w + ": norm_dev is NULL");
-        if (!y_dev) throw Err(w + ": y_dev is NULL");
-        if (!vel_dev) throw Err(w + ": vel_dev is NULL");
-        if (!gain_dev) throw Err(w + ": gain_dev is NULL");
-        if (!kl_dev) throw Err(w + ": kl_dev is NULL");
+        need(w, mu_dev, "mu_dev");
+        if (kl) need(w, logvar_dev, "logvar_dev", kNeedsLogvar);
+        need(w, beta_dev, "beta_dev"); need(w, shift_dev, "shift_dev"); need(w, norm_dev, "norm_dev");
+        need(w, y_dev, "y_dev"); need(w, vel_dev, "vel_dev"); need(w, gain_dev, "gain_dev"); need(w, kl_dev, "kl_dev");
         EmbedArgs a = embed_args(h, w, mu_dev, logvar_dev, rows, kl);
         hipStream_t s = on_stream(h, stream);
         a.beta = const_cast<float*>(beta_dev); a.shift = const_cast<float*>(shift_dev); a.norm = const_cast<float*>(norm_dev);

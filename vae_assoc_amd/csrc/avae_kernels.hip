@@ -19,7 +19,6 @@
 // :306-371 (losses), :373-374 (Adam); restated for CPU in oracle/vae_assoc_oracle.py.
 #include "avae_device.h"
 #include "avae_complete.h"
-#include <hip/hip_ext.h>
 #include <stdexcept>
 #include "../../include/avae.h"
 
@@ -1605,20 +1604,7 @@ __global__ void __launch_bounds__(kThreads) k_small_desc(const SmallDesc* __rest
 // the same signal times rocprofv3 --kernel-trace reports -- instead of bracketing it with marker packets.
 thread_local LaunchEvents t_launch_events = {nullptr, nullptr};
 
-#define AVAE_LAUNCH(kernel, grid, block, lds, stream, ...)                                                   \
-    do {                                                                                                     \
-        if (t_launch_events.start) {                                                                         \
-            hipExtLaunchKernelGGL(kernel, grid, block, lds, stream, t_launch_events.start, t_launch_events.stop, 0, __VA_ARGS__); \
-            t_launch_events = LaunchEvents{nullptr, nullptr};                                                \
-        } else {                                                                                             \
-            hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__);                               \
-        }                                                                                                    \
-    } while (0)
-
-template <typename K> static void set_max_lds(K kernel) {
-    // > 64 KiB of dynamic LDS has to be opted into once per kernel
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-}
+#define AVAE_LAUNCH(kernel, grid, block, lds, stream, ...) launch_kernel(kernel, grid, block, lds, stream, __VA_ARGS__)
 
 // The small nets' output + loss launch on the same lean frame (tile configuration 9): K_FWD_OUT_LOSS items (Bernoulli or Gaussian per
 // item) and the K_LATENT item that rides with them.  The exact fp32 inputs the loss compares with are fetched ahead of the first tile;
@@ -2728,14 +2714,14 @@ constexpr int kProducers = 4;
 
 static void grouped_attrs_once() {
     static const bool once = [] {
-        set_max_lds(k_grouped<__bf16, 64, 64, 4>); set_max_lds(k_grouped<__bf16, 128, 128, 2>); set_max_lds(k_grouped<__bf16, 256, 128, 3, 8, false, 0>);
-        set_max_lds(k_grouped<float, 64, 64, 4>); set_max_lds(k_grouped<float, 128, 128, 2>); set_max_lds(k_grouped<float, 256, 128, 3, 8, false, 0>);
-        set_max_lds(k_grouped<__bf16, 32, 64, 4>); set_max_lds(k_grouped<float, 32, 64, 4>);
-        set_max_lds(k_grouped<__bf16, 64, 128, 4>); set_max_lds(k_grouped<float, 64, 128, 4>);
-        set_max_lds(k_grouped<__bf16, 32, 32, 4>); set_max_lds(k_grouped<float, 32, 32, 4>);
-        set_max_lds(k_grouped<__bf16, 256, 64, 3, 8, false, 0>); set_max_lds(k_grouped<float, 256, 64, 3, 8, false, 0>);
-        set_max_lds(k_grouped<__bf16, 64, 64, 4, 4, true>); set_max_lds(k_grouped<__bf16, 128, 128, 2, 4, true>); set_max_lds(k_grouped<__bf16, 256, 128, 3, 8, true, kProducers>);
-        set_max_lds(k_grouped<float, 64, 64, 4, 4, true>); set_max_lds(k_grouped<float, 128, 128, 2, 4, true>); set_max_lds(k_grouped<float, 256, 128, 3, 8, true, kProducers>);
+        allow_max_lds(k_grouped<__bf16, 64, 64, 4>); allow_max_lds(k_grouped<__bf16, 128, 128, 2>); allow_max_lds(k_grouped<__bf16, 256, 128, 3, 8, false, 0>);
+        allow_max_lds(k_grouped<float, 64, 64, 4>); allow_max_lds(k_grouped<float, 128, 128, 2>); allow_max_lds(k_grouped<float, 256, 128, 3, 8, false, 0>);
+        allow_max_lds(k_grouped<__bf16, 32, 64, 4>); allow_max_lds(k_grouped<float, 32, 64, 4>);
+        allow_max_lds(k_grouped<__bf16, 64, 128, 4>); allow_max_lds(k_grouped<float, 64, 128, 4>);
+        allow_max_lds(k_grouped<__bf16, 32, 32, 4>); allow_max_lds(k_grouped<float, 32, 32, 4>);
+        allow_max_lds(k_grouped<__bf16, 256, 64, 3, 8, false, 0>); allow_max_lds(k_grouped<float, 256, 64, 3, 8, false, 0>);
+        allow_max_lds(k_grouped<__bf16, 64, 64, 4, 4, true>); allow_max_lds(k_grouped<__bf16, 128, 128, 2, 4, true>); allow_max_lds(k_grouped<__bf16, 256, 128, 3, 8, true, kProducers>);
+        allow_max_lds(k_grouped<float, 64, 64, 4, 4, true>); allow_max_lds(k_grouped<float, 128, 128, 2, 4, true>); allow_max_lds(k_grouped<float, 256, 128, 3, 8, true, kProducers>);
         return true;
     }();
     (void)once;
@@ -2753,9 +2739,9 @@ template <typename CT>
 static void launch_grouped_masked(int tile_cfg, const LaunchArgs& args, dim3 grid, dim3 block, int lds_bytes, DevState* st, hipStream_t s,
                                   unsigned long long* stamps, int launch_id) {
     static const bool once = [] {
-        set_max_lds(k_grouped<CT, 64, 64, 4, 4, false, 0, true>); set_max_lds(k_grouped<CT, 128, 128, 2, 4, false, 0, true>);
-        set_max_lds(k_grouped<CT, 32, 64, 4, 4, false, 0, true>); set_max_lds(k_grouped<CT, 64, 128, 4, 4, false, 0, true>);
-        set_max_lds(k_grouped<CT, 32, 32, 4, 4, false, 0, true>); set_max_lds(k_grouped<CT, 256, 64, 3, 8, false, 0, true>);
+        allow_max_lds(k_grouped<CT, 64, 64, 4, 4, false, 0, true>); allow_max_lds(k_grouped<CT, 128, 128, 2, 4, false, 0, true>);
+        allow_max_lds(k_grouped<CT, 32, 64, 4, 4, false, 0, true>); allow_max_lds(k_grouped<CT, 64, 128, 4, 4, false, 0, true>);
+        allow_max_lds(k_grouped<CT, 32, 32, 4, 4, false, 0, true>); allow_max_lds(k_grouped<CT, 256, 64, 3, 8, false, 0, true>);
         return true;
     }();
     (void)once;

@@ -14,11 +14,7 @@
 // partition is a function of rows alone and an item reads only its own modalities and flag columns, so a call on a subset of the
 // modalities gives the bits of the full call.
 #pragma once
-#include <stddef.h>
-#include <stdint.h>
-#include <algorithm>
-#include <hip/hip_runtime.h>
-#include "../../include/avae.h"
+#include "avae_latent_common.h"
 
 namespace avae {
 
@@ -37,12 +33,8 @@ struct StatsPlan {
 
 // The row partition: a function of rows alone.
 inline StatsPlan stats_plan(long long rows) {
-    StatsPlan p;
-    if (rows <= 0) return p;
-    const long long per = (rows + kStatsMaxSlices - 1) / kStatsMaxSlices;
-    p.row_tile = (int)std::max<long long>(kStatsMinSliceRows, (per + kStatsChunk - 1) / kStatsChunk * kStatsChunk);
-    p.n_slices = (int)((rows + p.row_tile - 1) / p.row_tile);
-    return p;
+    const RowSlices r = row_slices(rows, kStatsMaxSlices, kStatsMinSliceRows, kStatsChunk);
+    return StatsPlan{r.slice_rows, r.n_slices};
 }
 
 // Scratch layout, in doubles.  Modality partial (slice, m) at ((slice * M + m) * mod_stride):

@@ -2,8 +2,6 @@
 // the launch shapes: avae_latent_stats.h; DESIGN.md section 19.
 #include "avae_device.h"
 #include "avae_latent_stats.h"
-#include <hip/hip_ext.h>
-#include "../../include/avae.h"
 
 namespace avae {
 
@@ -273,25 +271,15 @@ __global__ void __launch_bounds__(256) k_latent_stats_merge(StatsArgs a) {
     a.out.cov[e] = r.n > 0.0 ? c : nan;
 }
 
-template <typename K, typename... Args>
-void stats_launch(K kernel, dim3 grid, dim3 block, hipStream_t s, const Args&... args) {
-    if (t_launch_events.start) {
-        hipExtLaunchKernelGGL(kernel, grid, block, 0, s, t_launch_events.start, t_launch_events.stop, 0, args...);
-        t_launch_events = LaunchEvents{nullptr, nullptr};
-    } else {
-        hipLaunchKernelGGL(kernel, grid, block, 0, s, args...);
-    }
-}
-
 }  // namespace
 
 void launch_latent_stats(const StatsArgs& a, hipStream_t s) {
-    stats_launch(k_latent_stats, dim3((unsigned)a.n_slices, (unsigned)(a.n_mod + stats_pairs(a.n_mod))), dim3(kStatsThreads), s, a);
+    launch_kernel(k_latent_stats, dim3((unsigned)a.n_slices, (unsigned)(a.n_mod + stats_pairs(a.n_mod))), dim3(kStatsThreads), 0, s, a);
 }
 
 void launch_latent_stats_merge(const StatsArgs& a, hipStream_t s) {
     const long long entries = (long long)a.n_mod * a.n_mod * a.nz + (a.want_cov ? (long long)a.n_mod * a.nz * a.nz : 0);
-    stats_launch(k_latent_stats_merge, dim3((unsigned)((entries + 255) / 256)), dim3(256), s, a);
+    launch_kernel(k_latent_stats_merge, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, s, a);
 }
 
 }  // namespace avae

@@ -18,11 +18,7 @@
 //                     kFitSlab points of pinv and of the rows' trajectories staged in LDS, one fma chain over t per parameter.
 // No atomics, no scratch, nothing of the handle is read or written.
 #pragma once
-#include <stddef.h>
-#include <stdint.h>
-#include <algorithm>
-#include <hip/hip_runtime.h>
-#include "../../include/avae.h"
+#include "avae_latent_common.h"
 
 namespace avae {
 

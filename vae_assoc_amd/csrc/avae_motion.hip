@@ -1,8 +1,6 @@
 // Motion decoding kernels (avae_motion.h, include/avae.h): k_motion_eval, k_motion_moments, k_motion_fit.
 #include "avae_device.h"
 #include "avae_motion.h"
-#include <hip/hip_ext.h>
-#include "../../include/avae.h"
 
 namespace avae {
 
@@ -399,30 +397,20 @@ __global__ __launch_bounds__(kMotionThreads) void k_motion_fit(const MotionFitAr
     }
 }
 
-template <typename K, typename A>
-void motion_launch(K kernel, dim3 grid, size_t lds, hipStream_t s, const A& args) {
-    if (t_launch_events.start) {
-        hipExtLaunchKernelGGL(kernel, grid, dim3(kMotionThreads), lds, s, t_launch_events.start, t_launch_events.stop, 0, args);
-        t_launch_events = LaunchEvents{nullptr, nullptr};
-    } else {
-        hipLaunchKernelGGL(kernel, grid, dim3(kMotionThreads), lds, s, args);
-    }
-}
-
 }  // namespace
 
 void launch_motion_eval(const MotionArgs& a, hipStream_t s) {
     const long long tiles = (a.rows + kMotionRows - 1) / kMotionRows;
-    motion_launch(k_motion_eval, dim3((unsigned)tiles), motion_lds_bytes(a.D, a.Kb, a.T, a.nc, false, a.ref_params != nullptr), s, a);
+    launch_kernel(k_motion_eval, dim3((unsigned)tiles), dim3(kMotionThreads), motion_lds_bytes(a.D, a.Kb, a.T, a.nc, false, a.ref_params != nullptr), s, a);
 }
 
 void launch_motion_moments(const MotionArgs& a, hipStream_t s) {
-    motion_launch(k_motion_moments, dim3((unsigned)a.rows), motion_lds_bytes(a.D, a.Kb, a.T, a.nc, true, false), s, a);
+    launch_kernel(k_motion_moments, dim3((unsigned)a.rows), dim3(kMotionThreads), motion_lds_bytes(a.D, a.Kb, a.T, a.nc, true, false), s, a);
 }
 
 void launch_motion_fit(const MotionFitArgs& a, hipStream_t s) {
     const long long tiles = (a.rows + kMotionRows - 1) / kMotionRows;
-    motion_launch(k_motion_fit, dim3((unsigned)tiles), 0, s, a);
+    launch_kernel(k_motion_fit, dim3((unsigned)tiles), dim3(kMotionThreads), 0, s, a);
 }
 
 }  // namespace avae

@@ -12,11 +12,7 @@
 // non-negative addends, so in fact always their own bits with the top bit set), every NaN has the key of the canonical quiet NaN,
 // and an empty slot is all ones (it sorts last and comes out as index -1, distance +Inf).
 #pragma once
-#include <stddef.h>
-#include <stdint.h>
-#include <algorithm>
-#include <hip/hip_runtime.h>
-#include "../../include/avae.h"
+#include "avae_latent_common.h"
 
 namespace avae {
 
@@ -52,9 +48,8 @@ inline TopkPlan topk_plan(long long rows, long long gallery_rows, int k) {
     const long long g_tiles = (gallery_rows + kTopkGalleryTile - 1) / kTopkGalleryTile;
     long long want = (kTopkTargetGroups + q_tiles - 1) / q_tiles;
     want = std::max<long long>(1, std::min<long long>(want, kTopkMaxSplits));
-    const long long per = std::max<long long>(kTopkMinTilesPerSplit, (g_tiles + want - 1) / want);
-    p.tiles_per_split = (int)per;
-    p.n_splits = (int)((g_tiles + per - 1) / per);
+    const TileSplits t = tile_splits(g_tiles, want, kTopkMinTilesPerSplit);
+    p.tiles_per_split = t.tiles_per_split; p.n_splits = t.n_splits;
     p.scratch_bytes = (size_t)p.chunk_rows * p.n_splits * k * sizeof(unsigned long long);
     return p;
 }

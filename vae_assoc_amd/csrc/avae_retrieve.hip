@@ -4,33 +4,17 @@
 // of distances lives in registers only.
 #include "avae_device.h"
 #include "avae_retrieve.h"
-#include <hip/hip_ext.h>
-#include "../../include/avae.h"
 
 namespace avae {
 
 namespace {
 
 // Every float operation below is the one written: the value of a pair must not depend on which instantiation, tile or lane
-// formed it, so nothing is left to the contraction pass.
+// formed it, so nothing is left to the contraction pass.  (The distance itself: latent_dist_step, avae_latent_common.h.)
 #pragma clang fp contract(off)
 
-// One latent dimension of one (query, gallery row) pair, added to the running sum.  THE definition of the distance: every
-// distance the library returns comes out of a chain of these over j = 0 .. n_z - 1 starting from +0.0f, then dist_finish.
-template <int METRIC>
-__device__ __forceinline__ float dist_step(float acc, float mq, float vq, float iq, float mg, float vg, float ig) {
-    const float d = mq - mg;
-    if (METRIC == AVAE_METRIC_L2) return __builtin_fmaf(d, d, acc);
-    const float t = vq - vg;
-    acc = __builtin_fmaf(t * iq, t * ig, acc);
-    return __builtin_fmaf(d * d, iq + ig, acc);
-}
-template <int METRIC> __device__ __forceinline__ float dist_finish(float acc) {
-    return METRIC == AVAE_METRIC_L2 ? acc : 0.5f * acc;
-}
-
 // (order key of the distance) << 32 | index: unsigned order == (isnan, dist, index) ascending.  -0.0f cannot come out of
-// dist_finish (the addends are squares and products of equal signs, the sum starts from +0.0f); adding +0.0f maps it to +0.0f anyway.
+// latent_dist_finish (the addends are squares and products of equal signs, the sum starts from +0.0f); adding +0.0f maps it to +0.0f anyway.
 __device__ __forceinline__ unsigned long long topk_entry(float dist, unsigned index) {
     unsigned b = __float_as_uint(dist + 0.0f);
     if (dist != dist) b = 0x7fc00000u;
@@ -149,8 +133,8 @@ __global__ void __launch_bounds__(kTopkThreads) k_latent_topk(TopkArgs a) {
             const float mqa[4] = {mq.x, mq.y, mq.z, mq.w}, vqa[4] = {vq.x, vq.y, vq.z, vq.w}, iqa[4] = {iq.x, iq.y, iq.z, iq.w};
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                acc[i][0] = dist_step<METRIC>(acc[i][0], mqa[i], vqa[i], iqa[i], mg.x, vg.x, ig.x);
-                acc[i][1] = dist_step<METRIC>(acc[i][1], mqa[i], vqa[i], iqa[i], mg.y, vg.y, ig.y);
+                acc[i][0] = latent_dist_step<METRIC>(acc[i][0], mqa[i], vqa[i], iqa[i], mg.x, vg.x, ig.x);
+                acc[i][1] = latent_dist_step<METRIC>(acc[i][1], mqa[i], vqa[i], iqa[i], mg.y, vg.y, ig.y);
             }
         }
         // selection.  Almost every candidate fails its query's filter, and then the wave does nothing more for this tile.
@@ -163,7 +147,7 @@ __global__ void __launch_bounds__(kTopkThreads) k_latent_topk(TopkArgs a) {
         for (int i = 0; i < 4; ++i) {
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
-                acc[i][c] = dist_finish<METRIC>(acc[i][c]);
+                acc[i][c] = latent_dist_finish<METRIC>(acc[i][c]);
                 any = any || (4 * ty + i < nq && 2 * tx + c < ng && !(acc[i][c] >= fa[i]));
             }
         }
@@ -255,32 +239,21 @@ __global__ void __launch_bounds__(256) k_latent_topk_merge(TopkArgs a) {
     }
 }
 
-template <typename K, typename... Args>
-void topk_launch(K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t s, const Args&... args) {
-    if (t_launch_events.start) {
-        hipExtLaunchKernelGGL(kernel, grid, block, lds, s, t_launch_events.start, t_launch_events.stop, 0, args...);
-        t_launch_events = LaunchEvents{nullptr, nullptr};
-    } else {
-        hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
-    }
-}
-
 }  // namespace
 
 void launch_latent_topk(const TopkArgs& a, hipStream_t s) {
     const size_t lds = topk_lds_bytes(a.nz, a.k, a.metric);
     const dim3 grid((unsigned)((a.rows + kTopkQueryTile - 1) / kTopkQueryTile), (unsigned)a.n_splits);
     auto go = [&](auto kernel) {
-        // more than 64 KiB of dynamic LDS has to be opted into (once per kernel; cheap to repeat)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        topk_launch(kernel, grid, dim3(kTopkThreads), lds, s, a);
+        allow_max_lds(kernel);
+        launch_kernel(kernel, grid, dim3(kTopkThreads), lds, s, a);
     };
     if (a.metric == AVAE_METRIC_L2) go(k_latent_topk<AVAE_METRIC_L2>);
     else go(k_latent_topk<AVAE_METRIC_SYMKL>);
 }
 
 void launch_latent_topk_merge(const TopkArgs& a, hipStream_t s) {
-    topk_launch(k_latent_topk_merge, dim3((unsigned)((a.rows + 3) / 4)), dim3(256), 0, s, a);
+    launch_kernel(k_latent_topk_merge, dim3((unsigned)((a.rows + 3) / 4)), dim3(256), 0, s, a);
 }
 
 }  // namespace avae
