@@ -139,14 +139,15 @@ def check_all_present_bitwise(V, net, dtype, act, steps=3):
     return a, b
 
 
-def check_against_reference(V, net, dtype, act, variants=None, seed=7):
-    """one masked step per mask variant on a fresh handle: cost, every gradient tensor and the Adam update against the reference"""
+def check_against_reference(V, net, dtype, act, variants=None, seed=7, extra=None):
+    """one masked step per mask variant on a fresh handle: cost, every gradient tensor and the Adam update against the reference.
+    ``extra``: {name: [B, M] mask}, further variants of the caller's"""
     fp32 = dtype == "fp32"
     p0 = _p0(net, seed)
     rng, X, eps = _data(net, seed + 1)
     B, M, archs = net["B"], len(net["archs"]), net["archs"]
     sl = _slices(archs)
-    for name, P in _masks(rng, B, M).items():
+    for name, P in dict(_masks(rng, B, M), **(extra or {})).items():
         if variants and name not in variants:
             continue
         m = _model(V, net, dtype, act, p0)
