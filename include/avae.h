@@ -841,6 +841,39 @@ int avae_motion_moments(avae_handle* h, const float* samples_dev, int32_t rows, 
                         const float* anchor_gain_dev, const float* anchor_target_dev, int32_t nc,
                         float* mean_dev, float* var_dev, float* saturated_frac_dev, void* stream);
 
+/* ---- pen-path kinematics and stroke rendering: from a joint trajectory to the picture it writes.  The
+ * reference turns every predicted trajectory into a Cartesian pen path, one PyKDL call per time point
+ * (baxter_vae_assoc_writer.py:448-449), draws it with matplotlib, crops the drawing to its ink and shrinks it to 28 x 28 with OpenCV
+ * (utils.py:240-257), and compares that picture with the one the robot was shown (baxter_vae_assoc_writer.py:344-399).  These two
+ * calls are the project's own definition of that picture, not a bit copy of Agg and cv2.INTER_AREA.  Dense device fp32 everywhere.
+ * avae_motion_fk: path[r][t] = the tip of a serial chain of D revolute joints at the angles traj[r][t][:],
+ *   T(q) = F_0 Rot(axis_0, q_0) F_1 Rot(axis_1, q_1) ... F_{D-1} Rot(axis_{D-1}, q_{D-1}) F_D,  tip = T[:3, 3],
+ *   frames_dev [D + 1][3][4] the fixed transforms between the joints (rotation | translation, vae_assoc_amd/kinematics.py packs them
+ *   from URDF-style joints), axes_dev [D][3] unit vectors, Rot Rodrigues' formula with the precise sincosf; the operations and their
+ *   order are written in csrc/avae_render.h.
+ * avae_stroke_render: a row's path p_t, t < T, drawn as a line of half width half_width with round caps and joins:
+ *   c_t = (u . (p_t - mean), v . (p_t - mean)) with plane_dev [3][3] = rows u, v, n and mean the mean over t; the ink box lo = min_t
+ *   c_t - half_width, hi = max_t c_t + half_width (exact), its centre ctr and longer side L; the window W = (1 + margin) L, sampled
+ *   on a grid of pitch delta = W / (H ss): sample (a, b), a, b < H ss, lies at u = ctr_u - W / 2 + (b + 1/2) delta, v = ctr_v + W / 2 -
+ *   (a + 1/2) delta (image row 0 is the top); its coverage is clamp(1/2 + (half_width - d) / delta, 0, 1) with d its distance to the
+ *   polyline (the minimum over the T - 1 segments, the foot clamped to the segment; a segment shorter than 1e-15 is a point, T = 1 a
+ *   dot); image[r][i * H + j] is the mean of the ss x ss coverages of pixel (i, j).  window[r] = (ctr_u, ctr_v, W).  With
+ *   target_dev, img_l2[r] = sqrt(sum (image - target)^2); with height_dev, height_l2[r] = sqrt(sum_t (n . p_t - height[r])^2).
+ *   Every sum has one fixed order (csrc/avae_render.h writes it down); pixels that cannot hold ink are skipped, which changes no bit.
+ *   A row whose path holds a non-finite value gets NaN in every output and touches no other row.
+ * rows == 0 is a no-op.  Errors (message in avae_last_error, nothing launched): rows < 0, D outside [1, 16], T outside [1, 1024],
+ * H outside [1, 64], ss not 1, 2, 4 or 8, half_width not > 0, margin not >= 0, a NULL required pointer, every output NULL, img_l2_dev
+ * without target_dev, height_l2_dev without height_dev.
+ * One launch each, no atomics, no scratch, nothing of the handle is read or written: a row's outputs are a pure function of its
+ * bits and the constants -- the same alone or among other rows, on any stream, on repetition and whichever optional outputs are
+ * asked for -- and the calls work on any replica and inside avae_use_averaged. */
+int avae_motion_fk(avae_handle* h, const float* traj_dev, int32_t rows, int32_t T, int32_t D,
+                   const float* frames_dev, const float* axes_dev, float* path_dev, void* stream);
+int avae_stroke_render(avae_handle* h, const float* path_dev, int32_t rows, int32_t T, const float* plane_dev,
+                       float half_width, float margin, int32_t H, int32_t ss,
+                       const float* target_dev, const float* height_dev,
+                       float* image_dev, float* window_dev, float* img_l2_dev, float* height_l2_dev, void* stream);
+
 /* save_model / restore_model (vae_assoc.py:427-463): own flat file (config echo + params + Adam
  * slots + step; with parameter averaging on also its settings and the average, see avae_set_ema);
  * TF .ckpt files cannot be read offline. */

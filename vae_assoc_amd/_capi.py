@@ -25,6 +25,7 @@ TOPK_MAX = 64
 GMM_MAX_COMPONENTS = 64
 EMBED_MAX_ROWS = 65536
 MOTION_MAX_DOF, MOTION_MAX_KB, MOTION_MAX_POINTS, MOTION_MAX_ANCHORS = 16, 64, 1024, 4
+RENDER_MAX_SIZE, RENDER_SUPERSAMPLES = 64, (1, 2, 4, 8)
 
 ACT_IDS = {"identity": 0, "relu": 1, "softplus": 2, "sigmoid": 3, "tanh": 4}
 DTYPE_IDS = {"fp32": 0, "f32": 0, "float32": 0, "bf16": 1, "bfloat16": 1}
@@ -50,6 +51,7 @@ SYMBOLS = [
     "avae_gmm_fit", "avae_gmm_score", "avae_gmm_plan",
     "avae_embed_calibrate", "avae_embed_iterate", "avae_embed_plan",
     "avae_motion_eval", "avae_motion_fit", "avae_motion_moments",
+    "avae_motion_fk", "avae_stroke_render",
     "avae_synchronize", "avae_timing_enable", "avae_timing_report", "avae_debug_fetch", "avae_comm_allreduce",
 ]
 
@@ -177,6 +179,8 @@ def lib():
             L.avae_motion_eval.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
             L.avae_motion_fit.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
             L.avae_motion_moments.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
+            L.avae_motion_fk.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp]
+            L.avae_stroke_render.argtypes = [vp, vp, i32, i32, vp, C.c_float, C.c_float, i32, i32, vp, vp, vp, vp, vp, vp, vp]
             L.avae_save.argtypes = [vp, C.c_char_p]
             L.avae_load.argtypes = [vp, C.c_char_p]
             L.avae_synchronize.argtypes = [vp]

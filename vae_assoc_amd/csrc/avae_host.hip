@@ -5,6 +5,7 @@
 #include "avae_retrieve.h"
 #include "avae_latent_stats.h"
 #include "avae_motion.h"
+#include "avae_render.h"
 #include "avae_gmm.h"
 #include "avae_embed.h"
 #include "avae_aggpost.h"
@@ -4798,6 +4799,57 @@ int avae_motion_moments(avae_handle* h, const float* samples_dev, int32_t rows, 
         a.traj = mean_dev; a.var = var_dev; a.sat_frac = saturated_frac_dev;
         hipStream_t s = on_stream(h, stream);
         timed_launch(h, s, "motion_moments", [&] { launch_motion_moments(a, s); });
+    });
+}
+
+// ---- pen-path kinematics and stroke rendering (include/avae.h, avae_render.h)
+static void check_range(const std::string& w, const char* name, int v, int lo, int hi) {
+    if (v < lo || v > hi)
+        throw Err(w + ": " + name + " = " + std::to_string(v) + " must be in [" + std::to_string(lo) + ", " + std::to_string(hi) + "]");
+}
+
+int avae_motion_fk(avae_handle* h, const float* traj_dev, int32_t rows, int32_t T, int32_t D,
+                   const float* frames_dev, const float* axes_dev, float* path_dev, void* stream) {
+    return guarded(h, [&] {
+        const std::string w = "avae_motion_fk";
+        check_rows(w, rows, "rows");
+        check_range(w, "T", T, 1, kRenderMaxT);
+        check_range(w, "D", D, 1, kFkMaxD);
+        need(w, traj_dev, "traj_dev"); need(w, frames_dev, "frames_dev"); need(w, axes_dev, "axes_dev"); need(w, path_dev, "path_dev");
+        if (rows == 0) return;
+        FkArgs a = zeroed<FkArgs>();
+        a.traj = traj_dev; a.frames = frames_dev; a.axes = axes_dev; a.path = path_dev;
+        a.points = (long long)rows * T; a.D = D;
+        hipStream_t s = on_stream(h, stream);
+        timed_launch(h, s, "motion_fk", [&] { launch_motion_fk(a, s); });
+    });
+}
+
+int avae_stroke_render(avae_handle* h, const float* path_dev, int32_t rows, int32_t T, const float* plane_dev,
+                       float half_width, float margin, int32_t H, int32_t ss,
+                       const float* target_dev, const float* height_dev,
+                       float* image_dev, float* window_dev, float* img_l2_dev, float* height_l2_dev, void* stream) {
+    return guarded(h, [&] {
+        const std::string w = "avae_stroke_render";
+        check_rows(w, rows, "rows");
+        check_range(w, "T", T, 1, kRenderMaxT);
+        check_range(w, "H", H, 1, kRenderMaxH);
+        if (ss != 1 && ss != 2 && ss != 4 && ss != 8) throw Err(w + ": ss = " + std::to_string(ss) + " must be 1, 2, 4 or 8");
+        if (!(half_width > 0.0f) || !std::isfinite(half_width)) throw Err(w + ": half_width must be finite and > 0");
+        if (!(margin >= 0.0f) || !std::isfinite(margin)) throw Err(w + ": margin must be finite and >= 0");
+        need(w, path_dev, "path_dev"); need(w, plane_dev, "plane_dev");
+        if (!image_dev && !window_dev && !img_l2_dev && !height_l2_dev) throw Err(w + ": every output is NULL");
+        if (img_l2_dev && !target_dev) throw Err(w + ": img_l2_dev needs target_dev");
+        if (height_l2_dev && !height_dev) throw Err(w + ": height_l2_dev needs height_dev");
+        if (render_lds_bytes(T, H) > 65536) throw Err("internal error: " + w + " plans more LDS than its bound");
+        if (rows == 0) return;
+        RenderArgs a = zeroed<RenderArgs>();
+        a.path = path_dev; a.plane = plane_dev; a.target = img_l2_dev ? target_dev : nullptr;       // (a target nobody reads)
+        a.height = height_l2_dev ? height_dev : nullptr;
+        a.image = image_dev; a.window = window_dev; a.img_l2 = img_l2_dev; a.height_l2 = height_l2_dev;
+        a.half_width = half_width; a.margin = margin; a.T = T; a.H = H; a.ss = ss;
+        hipStream_t s = on_stream(h, stream);
+        timed_launch(h, s, "stroke_render", [&] { launch_stroke_render(a, rows, s); });
     });
 }
 

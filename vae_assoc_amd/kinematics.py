@@ -1,0 +1,194 @@
+"""The host side of pen-path kinematics and stroke rendering (avae_motion_fk / avae_stroke_render in include/avae.h, DESIGN.md
+section 24): a serial chain of URDF-style joints packed into the matrices the device call takes, and the canvas a pen path is
+drawn on.
+
+The reference turns a joint trajectory into a pen path with one PyKDL call per time point (``derive_cartesian_trajectory``,
+baxter_vae_assoc_writer.py:448-449) and draws it with matplotlib, crops it to the ink and shrinks it to 28 x 28 with OpenCV
+(utils.py:240-257).  ``KinematicChain`` is the first half, ``StrokeCanvas`` the framing of the second.  Everything here is NumPy
+float64 and needs no GPU."""
+import numpy as np
+
+MAX_DOF, MAX_POINTS, MAX_SIZE = 16, 1024, 64
+SUPERSAMPLES = (1, 2, 4, 8)
+
+
+def _vec3(a, name, unit=False):
+    try:
+        v = np.array(a, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("%s must be three numbers, got %r" % (name, a))
+    if v.shape != (3,) or not np.isfinite(v).all():
+        raise ValueError("%s must be three finite numbers, got %r" % (name, a))
+    if unit:
+        n = np.linalg.norm(v)
+        if abs(n - 1.0) > 1e-6:
+            raise ValueError("%s must be a unit vector, got %r (norm %.9g)" % (name, a, n))
+        v = v / n
+    return v
+
+
+def origin_matrix(xyz, rpy):
+    """``Trans(xyz) Rz(yaw) Ry(pitch) Rx(roll)`` as a 4 x 4 matrix (the URDF ``origin`` of a joint)"""
+    r, p, y = rpy
+    cr, sr, cp, sp, cy, sy = np.cos(r), np.sin(r), np.cos(p), np.sin(p), np.cos(y), np.sin(y)
+    rx = np.array([[1.0, 0.0, 0.0], [0.0, cr, -sr], [0.0, sr, cr]])
+    ry = np.array([[cp, 0.0, sp], [0.0, 1.0, 0.0], [-sp, 0.0, cp]])
+    rz = np.array([[cy, -sy, 0.0], [sy, cy, 0.0], [0.0, 0.0, 1.0]])
+    m = np.eye(4)
+    m[:3, :3] = rz @ ry @ rx
+    m[:3, 3] = xyz
+    return m
+
+
+def axis_rotation(axis, q):
+    """Rodrigues' formula: the rotation by ``q`` about the unit vector ``axis``, 3 x 3"""
+    a = np.asarray(axis, dtype=np.float64)
+    k = np.array([[0.0, -a[2], a[1]], [a[2], 0.0, -a[0]], [-a[1], a[0], 0.0]])
+    return np.cos(q) * np.eye(3) + np.sin(q) * k + (1.0 - np.cos(q)) * np.outer(a, a)
+
+
+class KinematicChain(object):
+    """A serial chain from base to tip.  ``joints`` is a list of dicts: ``type`` 'fixed' or 'revolute', ``xyz`` and ``rpy`` of the
+    joint's origin (default zeros), ``axis`` (a unit vector; revolute joints only, default (1, 0, 0) as in URDF), and optionally
+    ``name``, ``lower`` and ``upper``.  The pose is ``T(q) = prod_j O_j Rot(axis_j, q_j)`` in chain order, with no rotation for a
+    fixed joint and ``O_j = Trans(xyz) Rz(yaw) Ry(pitch) Rx(roll)``; the pen tip is ``T[:3, 3]``."""
+
+    def __init__(self, joints):
+        self.joints = []
+        for i, j in enumerate(joints):
+            if not isinstance(j, dict):
+                raise ValueError("joints[%d] must be a dict, got %r" % (i, type(j).__name__))
+            kind = j.get("type")
+            if kind not in ("fixed", "revolute"):
+                raise ValueError("joints[%d]: type must be 'fixed' or 'revolute', got %r" % (i, kind))
+            xyz = _vec3(j.get("xyz") if j.get("xyz") is not None else (0.0, 0.0, 0.0), "joints[%d]: xyz" % i)
+            rpy = _vec3(j.get("rpy") if j.get("rpy") is not None else (0.0, 0.0, 0.0), "joints[%d]: rpy" % i)
+            axis = None
+            if kind == "revolute":
+                axis = _vec3(j.get("axis") if j.get("axis") is not None else (1.0, 0.0, 0.0), "joints[%d]: axis" % i, unit=True)
+            self.joints.append(dict(name=j.get("name"), type=kind, xyz=xyz, rpy=rpy, axis=axis, lower=j.get("lower"),
+                                    upper=j.get("upper")))
+        self.n_dof = sum(1 for j in self.joints if j["type"] == "revolute")
+        if not 1 <= self.n_dof <= MAX_DOF:
+            raise ValueError("the chain must hold 1 to %d revolute joints (n_dof), got %d" % (MAX_DOF, self.n_dof))
+        self._cache = {}
+
+    @classmethod
+    def from_urdf(cls, path, base, tip):
+        """The chain from link ``base`` to link ``tip`` of a URDF file (or of a string that holds one): walks the parent links
+        from the tip.  ``continuous`` joints count as revolute; any other moving joint is refused."""
+        import os
+        import xml.etree.ElementTree as ET
+        text = str(path)
+        root = ET.fromstring(text) if text.lstrip().startswith("<") else ET.parse(os.fspath(path)).getroot()
+        by_child = {}
+        for j in root.iter("joint"):
+            child, parent = j.find("child"), j.find("parent")
+            if child is not None and parent is not None:
+                by_child[child.get("link")] = j
+
+        def numbers(el, attr, default):
+            s = None if el is None else el.get(attr)
+            return default if s is None else [float(x) for x in s.split()]
+        joints, link = [], tip
+        while link != base:
+            j = by_child.get(link)
+            if j is None:
+                raise ValueError("no joint chain leads from link %r to link %r" % (base, tip))
+            kind = {"continuous": "revolute"}.get(j.get("type"), j.get("type"))
+            if kind not in ("fixed", "revolute"):
+                raise ValueError("joint %r is %r: only fixed and revolute joints are supported" % (j.get("name"), j.get("type")))
+            lim = j.find("limit")
+            joints.append(dict(name=j.get("name"), type=kind, xyz=numbers(j.find("origin"), "xyz", [0.0, 0.0, 0.0]),
+                               rpy=numbers(j.find("origin"), "rpy", [0.0, 0.0, 0.0]),
+                               axis=numbers(j.find("axis"), "xyz", [1.0, 0.0, 0.0]) if kind == "revolute" else None,
+                               lower=None if lim is None or lim.get("lower") is None else float(lim.get("lower")),
+                               upper=None if lim is None or lim.get("upper") is None else float(lim.get("upper"))))
+            link = j.find("parent").get("link")
+        return cls(joints[::-1])
+
+    @property
+    def limits(self):
+        """[n_dof, 2] (lower, upper) of the revolute joints, or None when one of them has no limits"""
+        rev = [j for j in self.joints if j["type"] == "revolute"]
+        if any(j["lower"] is None or j["upper"] is None for j in rev):
+            return None
+        return np.array([[j["lower"], j["upper"]] for j in rev], dtype=np.float64)
+
+    def packed(self, dtype=np.float32):
+        """-> (``frames [n_dof + 1, 3, 4]``, ``axes [n_dof, 3]``): frame j < n_dof is the product of the fixed origins since the
+        previous revolute joint and the origin of revolute joint j, frame n_dof the fixed origins behind the last revolute joint
+        (the identity if there are none), so that ``T(q) = F_0 Rot_0 F_1 ... Rot_{D-1} F_D``.  The products are formed in float64
+        and rounded once to ``dtype`` (float32: what the device call takes)."""
+        if "packed" not in self._cache:
+            frames, axes, run = [], [], np.eye(4)
+            for j in self.joints:
+                run = run @ origin_matrix(j["xyz"], j["rpy"])
+                if j["type"] == "revolute":
+                    frames.append(run[:3])
+                    axes.append(j["axis"])
+                    run = np.eye(4)
+            frames.append(run[:3])
+            self._cache["packed"] = (np.array(frames, dtype=np.float64), np.array(axes, dtype=np.float64))
+        f, a = self._cache["packed"]
+        return np.ascontiguousarray(f, dtype=dtype).copy(), np.ascontiguousarray(a, dtype=dtype).copy()
+
+    def forward(self, q):
+        """Joint angles ``[..., n_dof]`` -> pen tips ``[..., 3]``, float64, joint by joint as the definition is written"""
+        q = np.asarray(q, dtype=np.float64)
+        if q.shape[-1:] != (self.n_dof,):
+            raise ValueError("q must be [..., %d], got %s" % (self.n_dof, q.shape))
+        flat = q.reshape(-1, self.n_dof)
+        out = np.empty((flat.shape[0], 3))
+        origins = [origin_matrix(j["xyz"], j["rpy"]) for j in self.joints]
+        for i, row in enumerate(flat):
+            m, d = np.eye(4), 0
+            for j, o in zip(self.joints, origins):
+                m = m @ o
+                if j["type"] == "revolute":
+                    r = np.eye(4)
+                    r[:3, :3] = axis_rotation(j["axis"], row[d])
+                    m = m @ r
+                    d += 1
+            out[i] = m[:3, 3]
+        return out.reshape(q.shape[:-1] + (3,))
+
+
+class StrokeCanvas(object):
+    """How a pen path becomes a picture.  ``plane [3, 3]`` holds the rows u (image x, to the right), v (image y, upwards) and n (the
+    height above the paper); by default u = -y / scale, v = x / scale, n = z, the reference's writing plane with its 0.03 m per
+    unit (baxter_writer.py:30).  ``half_width`` is half the line's width in plane units (0.0625: a 12 pt line at 100 dpi on a
+    400 px canvas of 3 units), ``size`` the picture's side in pixels, ``supersample`` the samples per pixel side (1, 2, 4 or 8)
+    and ``margin`` the border around the ink as a share of its longer side (0.6, utils.py:240-257)."""
+
+    def __init__(self, scale=0.03, half_width=0.0625, size=28, supersample=4, margin=0.6, plane=None):
+        def number(x, name):
+            if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, float, np.integer, np.floating)) or not np.isfinite(x):
+                raise ValueError("%s must be a finite number, got %r" % (name, x))
+            return float(x)
+        self.scale = number(scale, "scale")
+        if not self.scale > 0.0:
+            raise ValueError("scale must be > 0, got %r" % (scale,))
+        self.half_width = float(np.float32(number(half_width, "half_width")))
+        if not self.half_width > 0.0:
+            raise ValueError("half_width must be > 0, got %r" % (half_width,))
+        self.margin = float(np.float32(number(margin, "margin")))
+        if not self.margin >= 0.0:
+            raise ValueError("margin must be >= 0, got %r" % (margin,))
+        if isinstance(size, (bool, np.bool_)) or not isinstance(size, (int, np.integer)) or not 1 <= size <= MAX_SIZE:
+            raise ValueError("size must be an integer in [1, %d], got %r" % (MAX_SIZE, size))
+        self.size = int(size)
+        if isinstance(supersample, (bool, np.bool_)) or supersample not in SUPERSAMPLES:
+            raise ValueError("supersample must be one of %s, got %r" % (SUPERSAMPLES, supersample))
+        self.supersample = int(supersample)
+        if plane is None:
+            plane = np.array([[0.0, -1.0 / self.scale, 0.0], [1.0 / self.scale, 0.0, 0.0], [0.0, 0.0, 1.0]])
+        plane = np.array(plane, dtype=np.float64)
+        if plane.shape != (3, 3) or not np.isfinite(plane).all():
+            raise ValueError("plane must be a finite [3, 3] array (rows u, v, n), got shape %s" % (plane.shape,))
+        self.plane = plane
+        self._cache = {}
+
+    @property
+    def n_pixels(self):
+        return self.size * self.size

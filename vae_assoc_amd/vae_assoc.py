@@ -685,6 +685,92 @@ def predict_motion_args(X, basis, modality, present, n_samples, eps, anchor, wid
     return (ts, rows, was_np, xp, lds, p, S, e), motion_matrices(basis, device, anchor, rows)
 
 
+def chain_matrices(chain, device):
+    """A ``KinematicChain`` -> (``frames [n_dof + 1, 3, 4]``, ``axes [n_dof, 3]``) as float32 tensors on ``device``, cached on the
+    chain per device."""
+    from .kinematics import KinematicChain
+    if not isinstance(chain, KinematicChain):
+        raise ValueError("chain must be a KinematicChain, got %r" % (type(chain).__name__,))
+    key = ("device", str(device))
+    if key not in chain._cache:
+        chain._cache[key] = tuple(torch.as_tensor(a).to(device) for a in chain.packed())
+    return chain._cache[key]
+
+
+def motion_fk_args(trajectories, chain, device):
+    """The arguments of ``motion_fk`` -> (trajectories [N, T, n_dof], frames, axes, was_numpy); ``ValueError`` ahead of any launch,
+    usable with ``device="cpu"``."""
+    from .kinematics import MAX_POINTS
+    frames, axes = chain_matrices(chain, device)
+    t, was_np = dev_block3(trajectories, (None, chain.n_dof), device, "trajectories")
+    if not 1 <= t.shape[1] <= MAX_POINTS:
+        raise ValueError("trajectories must hold 1 to %d time points, got %d" % (MAX_POINTS, t.shape[1]))
+    return t, frames, axes, was_np
+
+
+def canvas_args(canvas, rows, target, height, device):
+    """A ``StrokeCanvas`` and the optional inputs of a drawing of ``rows`` rows -> (plane [3, 3], target [rows, H * H] or None,
+    height [rows] or None) on ``device`` (the plane cached on the canvas per device).  ``target`` may be one picture ``[H * H]`` for
+    every row, ``height`` one number."""
+    from .kinematics import StrokeCanvas
+    if not isinstance(canvas, StrokeCanvas):
+        raise ValueError("canvas must be a StrokeCanvas, got %r" % (type(canvas).__name__,))
+    key = ("device", str(device))
+    if key not in canvas._cache:
+        canvas._cache[key] = torch.as_tensor(np.ascontiguousarray(canvas.plane, dtype=np.float32)).to(device)
+    plane = canvas._cache[key]
+    if target is not None:
+        t = target if torch.is_tensor(target) else torch.as_tensor(np.asarray(target, dtype=np.float32))
+        if t.dim() == 1:
+            t = t.reshape(1, -1).expand(rows, -1)
+        target = dev_dense(t, canvas.n_pixels, device, rows, "as the paths", name="target")
+    if height is not None:
+        h = height if torch.is_tensor(height) else torch.as_tensor(np.asarray(height, dtype=np.float32))
+        if h.dim() == 0:
+            h = h.reshape(1).expand(rows)
+        if h.dim() != 1 or h.shape[0] != rows:
+            raise ValueError("height must be a number or [%d] (as the paths), got %s" % (rows, tuple(h.shape)))
+        height = h.to(device=device, dtype=torch.float32).contiguous()
+    return plane, target, height
+
+
+def render_args(path, canvas, target, height, device):
+    """The arguments of ``render_strokes`` -> (path [N, T, 3], plane [3, 3], target [N, H * H] or None, height [N] or None,
+    was_numpy); ``ValueError`` ahead of any launch, usable with ``device="cpu"``."""
+    from .kinematics import MAX_POINTS
+    p, was_np = dev_block3(path, (None, 3), device, "path")
+    if not 1 <= p.shape[1] <= MAX_POINTS:
+        raise ValueError("path must hold 1 to %d points, got %d" % (MAX_POINTS, p.shape[1]))
+    return (p,) + canvas_args(canvas, int(p.shape[0]), target, height, device) + (was_np,)
+
+
+def draw_args(params, basis, chain, canvas, anchor, target, height, device):
+    """The arguments of ``draw_motion`` -> (params [N, P], matrices, frames, axes, plane, target, height, was_numpy)"""
+    p, mats, _, _, was_np = motion_eval_args(params, basis, anchor, None, None, device)
+    frames, axes = chain_matrices(chain, device)
+    if chain.n_dof != basis.n_dof:
+        raise ValueError("chain.n_dof = %d must be basis.n_dof = %d" % (chain.n_dof, basis.n_dof))
+    return (p, mats, frames, axes) + canvas_args(canvas, int(p.shape[0]), target, height, device) + (was_np,)
+
+
+def writing_cost_args(weights, image_modality, canvas, widths):
+    """``writing_cost``'s own arguments checked -> the three weights as floats"""
+    from .kinematics import StrokeCanvas
+    if not isinstance(canvas, StrokeCanvas):
+        raise ValueError("canvas must be a StrokeCanvas, got %r" % (type(canvas).__name__,))
+    if isinstance(image_modality, bool) or not isinstance(image_modality, (int, np.integer)) or not 0 <= image_modality < len(widths):
+        raise ValueError("image_modality must be an index in [0, %d), got %r" % (len(widths), image_modality))
+    if canvas.n_pixels != widths[image_modality]:
+        raise ValueError("the canvas draws %d pixels, modality %d holds %d" % (canvas.n_pixels, image_modality, widths[image_modality]))
+    try:
+        w = [float(x) for x in weights]
+    except (TypeError, ValueError):
+        raise ValueError("weights must be three numbers (image, height, latent), got %r" % (weights,))
+    if len(w) != 3 or not all(np.isfinite(w)):
+        raise ValueError("weights must be three finite numbers (image, height, latent), got %r" % (weights,))
+    return w
+
+
 class AssocVariationalAutoEncoder(object):
     """Associative VAE over M sensory modalities, trained on one MI355X (or one per rank).
 
@@ -1768,6 +1854,128 @@ class AssocVariationalAutoEncoder(object):
         _, _, rmse, mx = self._motion_eval(mean, mats, basis, None, refp)
         conv = self._like_input(was_np)
         return {"rmse": conv(rmse), "max_abs": conv(mx)}
+
+    # ------------------------------------------------------------------ pen path and drawing
+    def _motion_fk(self, t, frames, axes):
+        """avae_motion_fk on device tensors: trajectories [N, T, D] -> pen path [N, T, 3]"""
+        N, T, D = t.shape
+        path = torch.empty((N, T, 3), dtype=torch.float32, device=self.device)
+        if N:
+            _capi.check(self._h, self._L.avae_motion_fk(self._h, t.data_ptr(), N, T, D, frames.data_ptr(), axes.data_ptr(),
+                                                        path.data_ptr(), self._stream()), "avae_motion_fk")
+        return path
+
+    def _render(self, p, plane, canvas, target, height):
+        """avae_stroke_render on device tensors -> dict of device tensors (``img_l2`` / ``height_l2`` None without their input)"""
+        N, T, H = p.shape[0], p.shape[1], canvas.size
+        image, window = self._new(N, H * H), self._new(N, 3)
+        l2 = None if target is None else torch.empty(N, dtype=torch.float32, device=self.device)
+        hl2 = None if height is None else torch.empty(N, dtype=torch.float32, device=self.device)
+        if N:
+            _capi.check(self._h, self._L.avae_stroke_render(
+                self._h, p.data_ptr(), N, T, plane.data_ptr(), canvas.half_width, canvas.margin, H, canvas.supersample,
+                ptr(target), ptr(height), image.data_ptr(), window.data_ptr(), ptr(l2), ptr(hl2), self._stream()),
+                "avae_stroke_render")
+        return {"image": image, "window": window, "img_l2": l2, "height_l2": hl2}
+
+    def motion_fk(self, trajectories, chain):
+        """Joint trajectories ``[N, T, chain.n_dof]`` -> the pen tip's path ``[N, T, 3]`` (avae_motion_fk in include/avae.h): the
+        reference's ``derive_cartesian_trajectory`` (baxter_vae_assoc_writer.py:448-449), one launch for every row and time point
+        instead of one PyKDL call per point."""
+        t, frames, axes, was_np = motion_fk_args(trajectories, chain, self.device)
+        return self._like_input(was_np)(self._motion_fk(t, frames, axes))
+
+    def render_strokes(self, path, canvas, target=None, height=None):
+        """Pen paths ``[N, T, 3]`` -> the pictures they write (avae_stroke_render): the path projected on the canvas' plane, drawn as
+        a line of the canvas' width, cropped to its ink plus the margin and sampled to ``size x size`` pixels -- the project's own
+        definition of what the reference does with matplotlib and OpenCV (``derive_img_from_robot_cart_motion``, utils.py:240-257),
+        not a bit copy of it.  ``target`` (``[N, size * size]``, or one picture for every row) asks for the pixel distance,
+        ``height`` (``[N]`` or one number) for the distance of the path from that height above the plane.  Returns a dict:
+        ``image [N, size * size]`` (row 0 the top), ``window [N, 3]`` (centre u, v and side of the drawn window in plane units),
+        ``img_l2`` and ``height_l2 [N]`` (None without their input).  A row with a non-finite path is NaN throughout."""
+        p, plane, tg, hg, was_np = render_args(path, canvas, target, height, self.device)
+        conv = self._like_input(was_np)
+        return {k: None if v is None else conv(v) for k, v in self._render(p, plane, canvas, tg, hg).items()}
+
+    def draw_motion(self, params, basis, chain, canvas, anchor=None, target=None, height=None):
+        """Standardised approximator parameters -> the picture the motion writes: ``motion_eval``, ``motion_fk`` and
+        ``render_strokes`` chained on the device.  Returns ``render_strokes``' dict with ``trajectory [N, n_points, n_dof]`` and
+        ``path [N, n_points, 3]`` added; every piece is bitwise what the separate calls give."""
+        p, mats, frames, axes, plane, tg, hg, was_np = draw_args(params, basis, chain, canvas, anchor, target, height, self.device)
+        traj = self._motion_eval(p, mats, basis)[0]
+        path = self._motion_fk(traj, frames, axes)
+        out = self._render(path, plane, canvas, tg, hg)
+        out.update(trajectory=traj, path=path)
+        conv = self._like_input(was_np)
+        return {k: None if v is None else conv(v) for k, v in out.items()}
+
+    def writing_cost(self, params, basis, chain, canvas, target_image, target_latent=None, height=None, weights=(0.3, 10.0, 0.7),
+                     image_modality=0):
+        """The reference's ``cost_robot_joint_motion_fa_img`` (baxter_vae_assoc_writer.py:344-399) for N candidate motions at
+        once: each row of ``params`` is drawn (``draw_motion``) and compared with ``target_image`` (``[N, n_pixels]`` or one
+        picture) pixel by pixel and, after encoding the drawing with modality ``image_modality``, in latent space against
+        ``target_latent`` (``[N, n_z]`` or one row; default: the encoding of ``target_image``).  ``height`` is the height the pen
+        should keep (default: the row's own mean height, so a flat stroke costs nothing).
+        ``cost = w0 (img_l2 + w1 height_l2) + w2 latent_l2``; returns a dict of ``cost``, ``img_l2``, ``height_l2``,
+        ``latent_l2 [N]``, ``image``, ``path`` and ``trajectory``."""
+        w = writing_cost_args(weights, image_modality, canvas, self._widths)
+        if target_image is None:
+            raise ValueError("target_image is None: the cost needs the picture to compare with")
+        p, mats, frames, axes, plane, tg, hg, was_np = draw_args(params, basis, chain, canvas, None, target_image, height,
+                                                                 self.device)
+        rows = int(p.shape[0])
+        zt = None
+        if target_latent is not None:
+            zt = target_latent if torch.is_tensor(target_latent) else torch.as_tensor(np.asarray(target_latent, dtype=np.float32))
+            if zt.dim() == 1:
+                zt = zt.reshape(1, -1).expand(rows, -1)
+            zt = dev_dense(zt, self.n_z, self.device, rows, "as params", name="target_latent")
+        traj = self._motion_eval(p, mats, basis)[0]
+        path = self._motion_fk(traj, frames, axes)
+        if hg is None:
+            hg = (path @ plane[2]).mean(1).contiguous()
+        out = self._render(path, plane, canvas, tg, hg)
+        if zt is None:
+            zt = self._encode(image_modality, tg)
+        lat = torch.linalg.vector_norm(self._encode(image_modality, out["image"]) - zt, dim=1)
+        lat = torch.where(torch.isnan(out["img_l2"]), out["img_l2"], lat)      # (a row that could not be drawn)
+        cost = w[0] * (out["img_l2"] + w[1] * out["height_l2"]) + w[2] * lat
+        conv = self._like_input(was_np)
+        return {"cost": conv(cost), "img_l2": conv(out["img_l2"]), "height_l2": conv(out["height_l2"]), "latent_l2": conv(lat),
+                "image": conv(out["image"]), "path": conv(path), "trajectory": conv(traj)}
+
+    def cycle_error(self, X, basis, chain, canvas, source=0, modality=1):
+        """Does the motion predicted from a picture write that picture?  ``predict_motion`` from modality ``source`` alone, the
+        drawing of the predicted trajectory, and its distance from ``X[source]`` pixel by pixel (``img_l2``) and between the two
+        pictures' encodings (``latent_l2``).  With ``X[modality]`` given, the same two figures for the drawing of the row's own
+        recorded parameters: the floor set by the renderer and the data.  Returns ``dict(predicted=dict(img_l2, latent_l2, image),
+        own=dict(...) or None)``."""
+        M = len(self._widths)
+        if isinstance(source, bool) or not isinstance(source, (int, np.integer)) or not 0 <= source < M:
+            raise ValueError("source must be an index in [0, %d), got %r" % (M, source))
+        if len(X) != M:
+            raise ValueError("expected a list of %d modalities, got %d" % (M, len(X)))
+        writing_cost_args((0.0, 0.0, 0.0), source, canvas, self._widths)
+        only = [X[m] if m == source else None for m in range(M)]
+        (ts, rows, was_np, xp, lds, p, _, _), mats = predict_motion_args(only, basis, modality, None, 0, None, None, self._widths,
+                                                                        self.n_z, self.device)
+        frames, axes = chain_matrices(chain, self.device)
+        if chain.n_dof != basis.n_dof:
+            raise ValueError("chain.n_dof = %d must be basis.n_dof = %d" % (chain.n_dof, basis.n_dof))
+        own_p = None if X[modality] is None else dev_dense(X[modality], basis.n_params, self.device, rows, "as X[%d]" % source,
+                                                           name="X[%d]" % modality)
+        seen = ts[source].contiguous()
+        plane = canvas_args(canvas, rows, None, None, self.device)[0]
+        z_seen = self._encode(source, seen)
+        conv = self._like_input(was_np)
+
+        def drawn(params):
+            traj = self._motion_eval(params, mats, basis)[0]
+            out = self._render(self._motion_fk(traj, frames, axes), plane, canvas, seen, None)
+            lat = torch.linalg.vector_norm(self._encode(source, out["image"]) - z_seen, dim=1)
+            return {"img_l2": conv(out["img_l2"]), "latent_l2": conv(lat), "image": conv(out["image"])}
+        _, _, mean = self._fused_decode(xp, lds, p, rows, modality, True)
+        return {"predicted": drawn(mean), "own": None if own_p is None else drawn(own_p)}
 
     def save_model(self, fname=None):
         """reference vae_assoc.py:427-435 (default name: timestamp + batch size)."""
