@@ -874,6 +874,60 @@ int avae_stroke_render(avae_handle* h, const float* path_dev, int32_t rows, int3
                        const float* target_dev, const float* height_dev,
                        float* image_dev, float* window_dev, float* img_l2_dev, float* height_l2_dev, void* stream);
 
+/* ---- black-box search around a cost: batched PI-BB / CEM iterations on the device.  The reference refines a
+ * predicted motion by drawing rollouts from a Gaussian, pricing each and refitting the Gaussian to the cost-weighted rollouts
+ * (pygcem.py:28-151, driven from baxter_vae_assoc_writer.py:259-342).  Here P such searches ("problems") advance at once: problem p
+ * owns N(mean[p], diag(var[p])) over n dimensions and draws R rollouts per iteration; the caller prices x [P][R][n] into cost [P][R]
+ * between the two calls.  Dense device fp32 everywhere but n_applied_dev / frozen_dev (int32).
+ * avae_search_sample: x[p][r][d] = fma(sqrtf(var[p][d]), N, mean[p][d]), N the Box-Muller normal of the library's eps stream
+ *   (Philox4x32-10, the block's four normals to four consecutive dimensions) under a key of the call's own:
+ *     counter = (problem_offset + p, r, d / 4, iteration),  key = (seed lo, seed hi ^ 0x73726368 'srch').
+ *   The key is the call's seed, not the handle's, and the handle's draw counter is neither read nor advanced: the stream depends on
+ *   nothing else the handle did, and a caller who prices P problems in chunks passes each chunk's first problem as problem_offset
+ *   and gets the bits of the whole.  With proj_A_dev [G][g][g] and proj_b_dev [P][n] (G * g == n, g <= 64; both or neither) group
+ *   k of g consecutive dimensions is mapped  x_k <- A_k x_k + b[p]_k,  element j as  acc = b; acc = fma(A[j][i], x[i], acc), i
+ *   ascending -- what gaussian_sampling does under a linear constraint (pyrbf_funcapprox.py:163-171); the kernel knows nothing of
+ *   constraints, vae_assoc_amd/motion.py folds them into (A, b).
+ * avae_search_update: one GaussianCEM.fit per problem over the rollouts with a finite cost (a NaN or Inf cost, which is how a
+ *   motion that cannot be drawn is priced, has weight 0 and enters no statistic), in IEEE double, rounded once into the outputs:
+ *     weights   PI-BB : w = exp(-eliteness (c - min) / (max - min + 1e-6));  CEM: the mu = eliteness lowest costs get 1 / mu, ties
+ *               to the lower rollout;  CMA-ES: those get log(mu + 1/2) - log(rank + 1);  all 1 where std(c) <= 1e-8 |mean(c)|
+ *               (population std); then w / sum w
+ *     mean'     = sum_r w_r x_r
+ *     var'      = (1 - lr) var + lr sum_r w_r (x_r - m)^2,  m the old mean (cov_update PI-BB) or mean' (CEM); diagonal only
+ *     bounds    (each off when negative) var' = min(var', abs_upper); then var' = max(var', max(abs_lower, rel_lower max_d var'))
+ *     moved     = |mean' - mean|_2;  moved < tol sets frozen[p]: from the next call on the problem is left alone (tol 0: never)
+ *   A problem with no finite cost, or frozen on entry, keeps mean, var and n_applied bit for bit and gets NaN in avg_cost, min_cost
+ *   and moved; else n_applied[p] += 1, avg_cost / min_cost = the mean / minimum of the finite costs.  best_cost / best_x keep the
+ *   lowest finite cost over every rollout the calls saw and its x (a later equal cost does not replace it; start best_cost at +inf).
+ *   avg_cost_dev, min_cost_dev, moved_dev may be NULL.  csrc/avae_search.h writes every operation and the order of every sum down.
+ * P == 0 is a no-op.  Errors (message in avae_last_error, nothing launched): P < 0, n or R outside [1, 1024], iteration < 0,
+ * problem_offset < 0 or problem_offset + P > 2^32, one of proj_A / proj_b without the other, G * g != n, g outside [1, 64], an
+ * unknown weighting or cov_update, eliteness not finite and >= 0 (CEM / CMA-ES: not a whole number >= 1), learning_rate outside
+ * [0, 1], rel_lower > 1, a bound or tol that is NaN or infinite, tol < 0, a NULL required pointer.
+ * One launch each, no atomics, no scratch, one fixed order of every sum, nothing of the handle is read or written: a problem's
+ * outputs are a pure function of its own bits and the options -- the same alone or among other problems, on any stream, on
+ * repetition and whichever optional outputs are asked for -- and the calls work on any replica and inside avae_use_averaged. */
+#define AVAE_SEARCH_PIBB 0
+#define AVAE_SEARCH_CEM 1
+#define AVAE_SEARCH_CMAES 2
+typedef struct avae_search_options {
+    int32_t weighting;          /* AVAE_SEARCH_PIBB, _CEM or _CMAES */
+    int32_t cov_update;         /* AVAE_SEARCH_PIBB (deviations from the old mean) or AVAE_SEARCH_CEM (from the new one) */
+    double eliteness;           /* PI-BB: h;  CEM / CMA-ES: mu */
+    double learning_rate;
+    double rel_lower, abs_lower, abs_upper;   /* variance bounds; negative: off */
+    double tol;
+} avae_search_options;
+int avae_search_sample(avae_handle* h, const float* mean_dev, const float* var_dev, int32_t P, int32_t R, int32_t n,
+                       uint64_t seed, int32_t iteration, int64_t problem_offset,
+                       const float* proj_A_dev, const float* proj_b_dev, int32_t G, int32_t g, float* x_dev, void* stream);
+int avae_search_update(avae_handle* h, const float* x_dev, const float* cost_dev, int32_t P, int32_t R, int32_t n,
+                       const avae_search_options* opt,
+                       float* mean_dev, float* var_dev, int32_t* n_applied_dev, int32_t* frozen_dev,
+                       float* best_cost_dev, float* best_x_dev,
+                       float* avg_cost_dev, float* min_cost_dev, float* moved_dev, void* stream);
+
 /* save_model / restore_model (vae_assoc.py:427-463): own flat file (config echo + params + Adam
  * slots + step; with parameter averaging on also its settings and the average, see avae_set_ema);
  * TF .ckpt files cannot be read offline. */

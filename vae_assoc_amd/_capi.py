@@ -52,6 +52,7 @@ SYMBOLS = [
     "avae_embed_calibrate", "avae_embed_iterate", "avae_embed_plan",
     "avae_motion_eval", "avae_motion_fit", "avae_motion_moments",
     "avae_motion_fk", "avae_stroke_render",
+    "avae_search_sample", "avae_search_update",
     "avae_synchronize", "avae_timing_enable", "avae_timing_report", "avae_debug_fetch", "avae_comm_allreduce",
 ]
 
@@ -93,6 +94,15 @@ class Schedule(C.Structure):
 
 class LatentStatsOut(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in ("count", "mean", "var", "xcov", "assoc", "post_var", "kl", "cov")]
+
+
+SEARCH_MAX_DIMS, SEARCH_MAX_ROLLOUTS, SEARCH_MAX_GROUP = 1024, 1024, 64
+SEARCH_IDS = {"PI-BB": 0, "CEM": 1, "CMA-ES": 2}
+
+
+class SearchOptions(C.Structure):
+    _fields_ = [("weighting", C.c_int32), ("cov_update", C.c_int32), ("eliteness", C.c_double), ("learning_rate", C.c_double),
+                ("rel_lower", C.c_double), ("abs_lower", C.c_double), ("abs_upper", C.c_double), ("tol", C.c_double)]
 
 
 _lib = None
@@ -181,6 +191,8 @@ def lib():
             L.avae_motion_moments.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
             L.avae_motion_fk.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp]
             L.avae_stroke_render.argtypes = [vp, vp, i32, i32, vp, C.c_float, C.c_float, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+            L.avae_search_sample.argtypes = [vp, vp, vp, i32, i32, i32, C.c_uint64, i32, C.c_int64, vp, vp, i32, i32, vp, vp]
+            L.avae_search_update.argtypes = [vp, vp, vp, i32, i32, i32, C.POINTER(SearchOptions), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
             L.avae_save.argtypes = [vp, C.c_char_p]
             L.avae_load.argtypes = [vp, C.c_char_p]
             L.avae_synchronize.argtypes = [vp]

@@ -6,6 +6,7 @@
 #include "avae_latent_stats.h"
 #include "avae_motion.h"
 #include "avae_render.h"
+#include "avae_search.h"
 #include "avae_gmm.h"
 #include "avae_embed.h"
 #include "avae_aggpost.h"
@@ -4850,6 +4851,78 @@ int avae_stroke_render(avae_handle* h, const float* path_dev, int32_t rows, int3
         a.half_width = half_width; a.margin = margin; a.T = T; a.H = H; a.ss = ss;
         hipStream_t s = on_stream(h, stream);
         timed_launch(h, s, "stroke_render", [&] { launch_stroke_render(a, rows, s); });
+    });
+}
+
+// ---- black-box search (include/avae.h, avae_search.h)
+static void check_search_shape(const std::string& w, int32_t P, int32_t R, int32_t n) {
+    check_rows(w, P, "P");
+    check_range(w, "R", R, 1, kSearchMaxR);
+    check_range(w, "n", n, 1, kSearchMaxN);
+}
+
+int avae_search_sample(avae_handle* h, const float* mean_dev, const float* var_dev, int32_t P, int32_t R, int32_t n,
+                       uint64_t seed, int32_t iteration, int64_t problem_offset,
+                       const float* proj_A_dev, const float* proj_b_dev, int32_t G, int32_t g, float* x_dev, void* stream) {
+    return guarded(h, [&] {
+        const std::string w = "avae_search_sample";
+        check_search_shape(w, P, R, n);
+        if (iteration < 0) throw Err(w + ": iteration = " + std::to_string(iteration) + " must be >= 0");
+        if (problem_offset < 0 || problem_offset + (int64_t)P > ((int64_t)1 << 32))
+            throw Err(w + ": problem_offset = " + std::to_string(problem_offset) + " must be >= 0 and problem_offset + P <= 2^32");
+        if ((proj_A_dev != nullptr) != (proj_b_dev != nullptr)) throw Err(w + ": proj_A_dev and proj_b_dev go together; one of them is NULL");
+        if (proj_A_dev) {
+            check_range(w, "g", g, 1, kSearchMaxG);
+            if (G < 1 || (long long)G * g != n)
+                throw Err(w + ": G * g = " + std::to_string(G) + " * " + std::to_string(g) + " must be n = " + std::to_string(n));
+        }
+        need(w, mean_dev, "mean_dev"); need(w, var_dev, "var_dev"); need(w, x_dev, "x_dev");
+        if (P == 0) return;
+        static_assert(kSearchTileFloats >= 4 * ((kSearchMaxN + 3) / 4), "a sample tile holds at least one row");
+        SearchSampleArgs a = zeroed<SearchSampleArgs>();
+        a.mean = mean_dev; a.var = var_dev; a.proj_A = proj_A_dev; a.proj_b = proj_b_dev; a.x = x_dev;
+        a.rows = (long long)P * R; a.seed = seed; a.problem0 = (unsigned)problem_offset; a.iteration = (unsigned)iteration;
+        a.R = R; a.n = n; a.G = proj_A_dev ? G : 0; a.g = proj_A_dev ? g : 0;
+        if ((a.rows + search_tile_rows(n) - 1) / search_tile_rows(n) > 0x7fffffffLL) throw Err(w + ": P * R is too large for one launch");
+        hipStream_t s = on_stream(h, stream);
+        timed_launch(h, s, "search_sample", [&] { launch_search_sample(a, s); });
+    });
+}
+
+int avae_search_update(avae_handle* h, const float* x_dev, const float* cost_dev, int32_t P, int32_t R, int32_t n,
+                       const avae_search_options* opt,
+                       float* mean_dev, float* var_dev, int32_t* n_applied_dev, int32_t* frozen_dev,
+                       float* best_cost_dev, float* best_x_dev,
+                       float* avg_cost_dev, float* min_cost_dev, float* moved_dev, void* stream) {
+    return guarded(h, [&] {
+        const std::string w = "avae_search_update";
+        check_search_shape(w, P, R, n);
+        need(w, opt, "opt");
+        if (opt->weighting != AVAE_SEARCH_PIBB && opt->weighting != AVAE_SEARCH_CEM && opt->weighting != AVAE_SEARCH_CMAES)
+            throw Err(w + ": weighting = " + std::to_string(opt->weighting) + " is none of AVAE_SEARCH_PIBB, _CEM, _CMAES");
+        if (opt->cov_update != AVAE_SEARCH_PIBB && opt->cov_update != AVAE_SEARCH_CEM)
+            throw Err(w + ": cov_update = " + std::to_string(opt->cov_update) + " is neither AVAE_SEARCH_PIBB nor AVAE_SEARCH_CEM");
+        if (!std::isfinite(opt->eliteness) || opt->eliteness < 0.0) throw Err(w + ": eliteness must be finite and >= 0");
+        if (opt->weighting != AVAE_SEARCH_PIBB && (opt->eliteness < 1.0 || opt->eliteness > 1e9 || opt->eliteness != std::floor(opt->eliteness)))
+            throw Err(w + ": eliteness must be a whole number >= 1 for CEM / CMA-ES weighting (the number of rollouts kept)");
+        if (!(opt->learning_rate >= 0.0 && opt->learning_rate <= 1.0)) throw Err(w + ": learning_rate must be in [0, 1]");
+        if (!std::isfinite(opt->rel_lower) || !std::isfinite(opt->abs_lower) || !std::isfinite(opt->abs_upper))
+            throw Err(w + ": rel_lower, abs_lower and abs_upper must be finite (negative: off)");
+        if (opt->rel_lower > 1.0) throw Err(w + ": rel_lower must be <= 1");
+        if (!std::isfinite(opt->tol) || opt->tol < 0.0) throw Err(w + ": tol must be finite and >= 0");
+        need(w, x_dev, "x_dev"); need(w, cost_dev, "cost_dev"); need(w, mean_dev, "mean_dev"); need(w, var_dev, "var_dev");
+        need(w, n_applied_dev, "n_applied_dev"); need(w, frozen_dev, "frozen_dev");
+        need(w, best_cost_dev, "best_cost_dev"); need(w, best_x_dev, "best_x_dev");
+        if (P == 0) return;
+        SearchUpdateArgs a = zeroed<SearchUpdateArgs>();
+        a.x = x_dev; a.cost = cost_dev; a.mean = mean_dev; a.var = var_dev; a.n_applied = n_applied_dev; a.frozen = frozen_dev;
+        a.best_cost = best_cost_dev; a.best_x = best_x_dev; a.avg_cost = avg_cost_dev; a.min_cost = min_cost_dev; a.moved = moved_dev;
+        a.R = R; a.n = n; a.weighting = opt->weighting; a.cov_update = opt->cov_update;
+        a.mu = opt->weighting != AVAE_SEARCH_PIBB ? (int)opt->eliteness : 0;
+        a.h = opt->eliteness; a.lr = opt->learning_rate; a.rel_lower = opt->rel_lower; a.abs_lower = opt->abs_lower;
+        a.abs_upper = opt->abs_upper; a.tol = opt->tol;
+        hipStream_t s = on_stream(h, stream);
+        timed_launch(h, s, "search_update", [&] { launch_search_update(a, P, s); });
     });
 }
 

@@ -117,6 +117,22 @@ class MotionBasis(object):
         A, B = self._cache[key]
         return A.copy(), B.copy()
 
+    def projection(self, phases, target):
+        """``constraint(phases)`` in the standardised space, per joint: -> (A [n_dof, Kb, Kb], b [rows, n_params]) in float64
+        with  s' = A[d] s + b[:, d]  the standardised parameters of joint d whose raw values theta = s * param_std + param_mean
+        are the projection of the raw s onto ``features(phases) theta == target[:, d]`` -- what ``search`` takes as ``project``
+        (pyrbf_funcapprox.py:163-171 samples under the constraint this way).  ``target`` is [rows, n_dof, n_c]."""
+        A, B = self.constraint(phases)
+        t = np.asarray(target, dtype=np.float64)
+        if t.ndim != 3 or t.shape[1:] != (self.n_dof, B.shape[1]):
+            raise ValueError("target must be [rows, %d, %d], got %s" % (self.n_dof, B.shape[1], t.shape))
+        std = np.ones(self.n_params) if self.param_std is None else self.param_std
+        mean = np.zeros(self.n_params) if self.param_mean is None else self.param_mean
+        std, mean = std.reshape(self.n_dof, self.n_kb), mean.reshape(self.n_dof, self.n_kb)
+        As = A[None, :, :] * std[:, None, :] / std[:, :, None]
+        b = (np.einsum("jk,dk->dj", A, mean)[None] + np.einsum("jc,rdc->rdj", B, t) - mean[None]) / std[None]
+        return As, b.reshape(t.shape[0], self.n_params)
+
     # ---- what the device calls take
     def scale_shift(self):
         """(param_std or None, param_mean or None) as float32: theta = params * scale + shift"""

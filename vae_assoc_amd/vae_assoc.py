@@ -771,6 +771,129 @@ def writing_cost_args(weights, image_modality, canvas, widths):
     return w
 
 
+SEARCH_STATE_KEYS = ("mean", "var", "n_applied", "frozen", "best_cost", "best_x", "iteration")
+
+
+def search_args(x0, var0, n_rollouts, n_iters, eliteness, weighting, cov_update, learning_rate, covar_bounds, tol, project, seed,
+                state, device):
+    """The arguments of ``search`` checked and marshalled -> (state: a fresh one from ``x0`` / ``var0`` or a copy of ``state``,
+    ``_capi.SearchOptions``, n_rollouts, n_iters, (A, b, G, g) or None, seed, was_numpy).  Every error is a ``ValueError`` raised
+    here, ahead of any launch; touches neither a model nor the library (``device="cpu"`` works).  Values of device tensors are not
+    looked at: that would be a host round trip."""
+    def whole(v, name, lo, hi=None):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < lo or (hi is not None and v > hi):
+            raise ValueError("%s must be an integer %s, got %r" % (name, ">= %d" % lo if hi is None else "in [%d, %d]" % (lo, hi), v))
+        return int(v)
+
+    def number(v, name, lo=None, hi=None):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+            raise ValueError("%s must be a finite number, got %r" % (name, v))
+        if (lo is not None and v < lo) or (hi is not None and v > hi):
+            raise ValueError("%s must be in [%s, %s], got %r" % (name, "-inf" if lo is None else lo, "inf" if hi is None else hi, v))
+        return float(v)
+    R = whole(n_rollouts, "n_rollouts", 1, _capi.SEARCH_MAX_ROLLOUTS)
+    n_iters = whole(n_iters, "n_iters", 0, 1 << 30)
+    seed = whole(seed, "seed", 0, (1 << 64) - 1)
+    if weighting not in _capi.SEARCH_IDS:
+        raise ValueError("weighting must be 'PI-BB', 'CEM' or 'CMA-ES', got %r" % (weighting,))
+    if cov_update not in ("PI-BB", "CEM"):
+        raise ValueError("cov_update must be 'PI-BB' or 'CEM', got %r" % (cov_update,))
+    opt = _capi.SearchOptions()
+    opt.weighting, opt.cov_update = _capi.SEARCH_IDS[weighting], _capi.SEARCH_IDS[cov_update]
+    opt.eliteness = number(eliteness, "eliteness", 0.0)
+    if weighting != "PI-BB" and (opt.eliteness < 1 or opt.eliteness != int(opt.eliteness)):
+        raise ValueError("eliteness must be a whole number >= 1 with %s weighting (the candidates kept), got %r" % (weighting, eliteness))
+    opt.learning_rate = number(learning_rate, "learning_rate", 0.0, 1.0)
+    opt.tol = number(tol, "tol", 0.0)
+    bounds = [] if covar_bounds is None else list(np.atleast_1d(covar_bounds))
+    if len(bounds) > 3:
+        raise ValueError("covar_bounds must be None or up to three numbers (relative lower, absolute lower, absolute upper), got %r"
+                         % (covar_bounds,))
+    bounds = [number(b, "covar_bounds[%d]" % i) for i, b in enumerate(bounds)] + [-1.0] * (3 - len(bounds))
+    if bounds[0] > 1.0:
+        raise ValueError("covar_bounds[0] (the relative lower bound) must be <= 1, got %r" % (bounds[0],))
+    opt.rel_lower, opt.abs_lower, opt.abs_upper = [b if b >= 0 else -1.0 for b in bounds]
+
+    def f32(a, name):
+        t = a if torch.is_tensor(a) else torch.as_tensor(np.asarray(a, dtype=np.float32))
+        if t.dtype not in (torch.float32, torch.float64, torch.float16, torch.bfloat16):
+            raise ValueError("%s must hold floating-point values, got %s" % (name, t.dtype))
+        return t.to(device=device, dtype=torch.float32)
+    if state is None:
+        if x0 is None or var0 is None:
+            raise ValueError("x0 and var0 are needed where there is no state to continue")
+        was_np = not torch.is_tensor(x0)
+        mean = f32(x0, "x0")
+        if mean.dim() != 2 or not 1 <= mean.shape[1] <= _capi.SEARCH_MAX_DIMS:
+            raise ValueError("x0 must be [P, n] with n in [1, %d], got %s" % (_capi.SEARCH_MAX_DIMS, tuple(mean.shape)))
+        P, n = int(mean.shape[0]), int(mean.shape[1])
+        if not torch.is_tensor(var0) and not (np.all(np.isfinite(var0)) and np.all(np.asarray(var0) >= 0)):
+            raise ValueError("var0 must be finite and >= 0")
+        if isinstance(var0, (int, float, np.integer, np.floating)):      # (filled on the device: no copy from the host)
+            var = torch.full((), float(var0), dtype=torch.float32, device=device)
+        else:
+            var = f32(var0, "var0")
+        if tuple(var.shape) not in ((), (n,), (P, n)):
+            raise ValueError("var0 must be a number, [%d] or [%d, %d], got %s" % (n, P, n, tuple(var.shape)))
+        st = dict(mean=mean.clone().contiguous(), var=var.expand(P, n).clone().contiguous(),
+                  n_applied=torch.zeros(P, dtype=torch.int32, device=device), frozen=torch.zeros(P, dtype=torch.int32, device=device),
+                  best_cost=torch.full((P,), float("inf"), dtype=torch.float32, device=device),
+                  best_x=torch.zeros((P, n), dtype=torch.float32, device=device), iteration=0)
+    else:
+        if not isinstance(state, dict) or set(state) != set(SEARCH_STATE_KEYS):
+            raise ValueError("state must be the dict a search returned (keys %s)" % ", ".join(SEARCH_STATE_KEYS))
+        was_np = False
+        if not torch.is_tensor(state["mean"]) or state["mean"].dim() != 2:
+            raise ValueError("state['mean'] must be a [P, n] tensor")
+        P, n = int(state["mean"].shape[0]), int(state["mean"].shape[1])
+        st = {"iteration": whole(state["iteration"], "state['iteration']", 0)}
+        for k, shape, dt in (("mean", (P, n), torch.float32), ("var", (P, n), torch.float32), ("best_x", (P, n), torch.float32),
+                             ("best_cost", (P,), torch.float32), ("n_applied", (P,), torch.int32), ("frozen", (P,), torch.int32)):
+            t = state[k]
+            if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dt:
+                raise ValueError("state[%r] must be a %s tensor of shape %s" % (k, dt, shape))
+            st[k] = t.to(device).clone().contiguous()
+    if st["iteration"] + n_iters >= 1 << 31:
+        raise ValueError("the run's iterations must stay below 2^31")
+    proj = None
+    if project is not None:
+        if not isinstance(project, (tuple, list)) or len(project) != 2:
+            raise ValueError("project must be None or (A [G, g, g], b [P, n])")
+        A, b = f32(project[0], "project A").contiguous(), f32(project[1], "project b").contiguous()
+        if A.dim() != 3 or A.shape[1] != A.shape[2] or A.shape[0] * A.shape[1] != n or not 1 <= A.shape[1] <= _capi.SEARCH_MAX_GROUP:
+            raise ValueError("project A must be [G, g, g] with G * g = n = %d and g <= %d, got %s"
+                             % (n, _capi.SEARCH_MAX_GROUP, tuple(A.shape)))
+        if tuple(b.shape) != (P, n):
+            raise ValueError("project b must be [%d, %d], got %s" % (P, n, tuple(b.shape)))
+        proj = (A, b, int(A.shape[0]), int(A.shape[1]))
+    return st, opt, R, n_iters, proj, seed, was_np
+
+
+def refine_motion_args(basis, chain, space, n_rollouts, modality, search_options, widths):
+    """``refine_motion``'s own arguments checked -> (n_rollouts with the space's default, the options passed on to ``search``)"""
+    from .kinematics import KinematicChain
+    from .motion import MotionBasis
+    if not isinstance(basis, MotionBasis):
+        raise ValueError("basis must be a MotionBasis, got %r" % (type(basis).__name__,))
+    if not isinstance(chain, KinematicChain):
+        raise ValueError("chain must be a KinematicChain, got %r" % (type(chain).__name__,))
+    if chain.n_dof != basis.n_dof:
+        raise ValueError("chain.n_dof = %d must be basis.n_dof = %d" % (chain.n_dof, basis.n_dof))
+    if space not in ("latent", "params"):
+        raise ValueError("space must be 'latent' or 'params', got %r" % (space,))
+    if isinstance(modality, bool) or not isinstance(modality, (int, np.integer)) or not 0 <= modality < len(widths):
+        raise ValueError("modality must be an index in [0, %d), got %r" % (len(widths), modality))
+    if basis.n_params != widths[modality]:
+        raise ValueError("basis.n_params = %d must be n_input = %d of modality %d" % (basis.n_params, widths[modality], modality))
+    allowed = {"eliteness", "weighting", "cov_update", "learning_rate", "covar_bounds", "tol", "seed"}
+    extra = set(search_options) - allowed
+    if extra:
+        raise ValueError("unknown option(s) %s (search takes %s)" % (", ".join(sorted(map(str, extra))), ", ".join(sorted(allowed))))
+    if n_rollouts is None:
+        n_rollouts = 10 if space == "latent" else 20
+    return n_rollouts, dict(search_options)
+
+
 class AssocVariationalAutoEncoder(object):
     """Associative VAE over M sensory modalities, trained on one MI355X (or one per rank).
 
@@ -1930,6 +2053,13 @@ class AssocVariationalAutoEncoder(object):
             if zt.dim() == 1:
                 zt = zt.reshape(1, -1).expand(rows, -1)
             zt = dev_dense(zt, self.n_z, self.device, rows, "as params", name="target_latent")
+        out = self._writing_cost(p, mats, basis, frames, axes, plane, canvas, tg, hg, zt, w, image_modality)
+        conv = self._like_input(was_np)
+        return {k: conv(out[k]) for k in ("cost", "img_l2", "height_l2", "latent_l2", "image", "path", "trajectory")}
+
+    def _writing_cost(self, p, mats, basis, frames, axes, plane, canvas, tg, hg, zt, w, image_modality):
+        """``writing_cost`` on device tensors, with no host round trip: parameters ``p [N, P]`` and their targets (``hg`` None: the
+        row's own mean height, ``zt`` None: the encoding of ``tg``) -> dict of device tensors, ``height`` (the one used) among them"""
         traj = self._motion_eval(p, mats, basis)[0]
         path = self._motion_fk(traj, frames, axes)
         if hg is None:
@@ -1940,9 +2070,144 @@ class AssocVariationalAutoEncoder(object):
         lat = torch.linalg.vector_norm(self._encode(image_modality, out["image"]) - zt, dim=1)
         lat = torch.where(torch.isnan(out["img_l2"]), out["img_l2"], lat)      # (a row that could not be drawn)
         cost = w[0] * (out["img_l2"] + w[1] * out["height_l2"]) + w[2] * lat
+        return {"cost": cost, "img_l2": out["img_l2"], "height_l2": out["height_l2"], "latent_l2": lat, "image": out["image"],
+                "path": path, "trajectory": traj, "height": hg}
+
+    # ------------------------------------------------------------------ black-box search
+    def _search_sample(self, st, R, seed, iteration, proj, x):
+        """avae_search_sample on the state's Gaussians into ``x [P, R, n]`` (all problems in one call: problem_offset 0)"""
+        P, n = st["mean"].shape
+        A, b, G, g = proj if proj is not None else (None, None, 0, 0)
+        _capi.check(self._h, self._L.avae_search_sample(
+            self._h, st["mean"].data_ptr(), st["var"].data_ptr(), P, R, n, seed, iteration, 0, ptr(A), ptr(b), G, g,
+            x.data_ptr(), self._stream()), "avae_search_sample")
+
+    def _search_update(self, st, x, c, opt, avg=None, mn=None, moved=None):
+        """avae_search_update of the state in place from the rollouts ``x [P, R, n]`` and their costs ``c [P, R]``"""
+        P, R, n = x.shape
+        _capi.check(self._h, self._L.avae_search_update(
+            self._h, x.data_ptr(), c.data_ptr(), P, R, n, C.byref(opt), st["mean"].data_ptr(), st["var"].data_ptr(),
+            st["n_applied"].data_ptr(), st["frozen"].data_ptr(), st["best_cost"].data_ptr(), st["best_x"].data_ptr(),
+            ptr(avg), ptr(mn), ptr(moved), self._stream()), "avae_search_update")
+
+    def search(self, cost, x0, var0, n_rollouts=10, n_iters=10, eliteness=10, weighting="PI-BB", cov_update="PI-BB",
+               learning_rate=1.0, covar_bounds=(0.1,), tol=1e-6, project=None, seed=0, state=None):
+        """Black-box search for P problems at once (avae_search_sample / avae_search_update in include/avae.h): the reference's
+        ``GaussianCEM`` loop (pygcem.py:28-151, 154-183) with every problem's rollouts drawn, priced and refitted on the device.
+
+        Problem p starts from N(``x0[p]``, diag(``var0``)) (``x0 [P, n]``; ``var0`` a number, ``[n]`` or ``[P, n]``); each of
+        ``n_iters`` iterations draws ``n_rollouts`` candidates per problem, prices them with ``cost(candidates [rows, n],
+        problem_index [rows]) -> [rows]`` and refits.  ``cost`` gets and returns device tensors and must not synchronise; it is
+        called on chunks of whole problems (at most ``_motion_chunk`` rows), and the result does not depend on the chunking.  A
+        NaN or Inf cost marks a candidate that could not be priced: it has no weight.  ``weighting`` 'PI-BB' (``eliteness`` = h),
+        'CEM' or 'CMA-ES' (``eliteness`` = the number of candidates kept); ``cov_update`` 'PI-BB' (deviations from the old mean)
+        or 'CEM' (from the new); ``covar_bounds`` None or up to three numbers (relative lower, absolute lower, absolute upper
+        bound of the variances; -1 = none), as the reference's; a problem whose mean moved less than ``tol`` stops changing.
+        ``project`` None or ``(A [G, g, g], b [P, n])``: every candidate's group k of g dimensions is mapped to ``A[k] x + b``.
+        The draws depend on ``seed``, the iteration and the problem's index alone.
+
+        Returns a dict of ``mean``, ``var``, ``best_x [P, n]``, ``best_cost``, ``n_applied [P]``, the histories ``avg_cost``,
+        ``min_cost``, ``moved [n_iters, P]`` (NaN where a problem was not updated) and ``state``; ``search(..., state=state)``
+        continues the run (``x0`` / ``var0`` are then ignored): k iterations and then m more are the bits of k + m.  The whole
+        loop is enqueued without a host round trip.  NumPy in gives NumPy out (``state`` stays on the device)."""
+        st, opt, R, n_iters, proj, seed, was_np = search_args(x0, var0, n_rollouts, n_iters, eliteness, weighting, cov_update,
+                                                              learning_rate, covar_bounds, tol, project, seed, state, self.device)
+        if not callable(cost):
+            raise ValueError("cost must be callable: cost(candidates [rows, n], problem_index [rows]) -> [rows]")
+        P, n = st["mean"].shape
+        x = torch.empty((P, R, n), dtype=torch.float32, device=self.device)
+        c = torch.empty((P, R), dtype=torch.float32, device=self.device)
+        hist = {k: torch.full((n_iters, P), float("nan"), dtype=torch.float32, device=self.device)
+                for k in ("avg_cost", "min_cost", "moved")}
+        pidx = torch.div(torch.arange(P * R, device=self.device), R, rounding_mode="floor")
+        chunk = max(1, int(self._motion_chunk) // R)
+        for i in range(n_iters if P else 0):
+            self._search_sample(st, R, seed, st["iteration"] + i, proj, x)
+            for p0 in range(0, P, chunk):
+                p1 = min(P, p0 + chunk)
+                out = cost(x[p0:p1].reshape(-1, n), pidx[p0 * R:p1 * R])
+                if not torch.is_tensor(out) or out.numel() != (p1 - p0) * R:
+                    raise ValueError("cost must return a tensor of [%d] values, one per candidate" % ((p1 - p0) * R))
+                c[p0:p1] = out.reshape(p1 - p0, R)
+            self._search_update(st, x, c, opt, hist["avg_cost"][i], hist["min_cost"][i], hist["moved"][i])
+        st["iteration"] += n_iters
         conv = self._like_input(was_np)
-        return {"cost": conv(cost), "img_l2": conv(out["img_l2"]), "height_l2": conv(out["height_l2"]), "latent_l2": conv(lat),
-                "image": conv(out["image"]), "path": conv(path), "trajectory": conv(traj)}
+        res = {k: conv(st[k]) for k in ("mean", "var", "best_x", "best_cost", "n_applied")}
+        res.update({k: conv(v) for k, v in hist.items()})
+        res["state"] = st
+        return res
+
+    def refine_motion(self, target_image, basis, chain, canvas, space="latent", init=None, n_rollouts=None, n_iters=10, var0=None,
+                      anchor_start=True, weights=(0.3, 10.0, 0.7), image_modality=0, modality=1, **search_options):
+        """The reference's posterior refinement of a written motion (``derive_robot_motion_from_img_posterior_rl`` and
+        ``..._rl_latent``, baxter_vae_assoc_writer.py:259-342) for P pictures at once: a ``search`` whose cost is
+        ``writing_cost``'s against ``target_image [P, n_pixels]``.
+
+        The start is the encoding of ``target_image`` and its decoded motion (or ``init``: ``[P, n_z]`` latents, for
+        ``space='params'`` ``[P, n_params]`` parameters).  Every candidate of problem p is priced against the picture p, the
+        picture's encoding and the mean pen height of p's initial motion.  ``space='latent'``: the candidates are latents,
+        decoded by modality ``modality``'s decoder and drawn (``var0`` 0.01, 10 rollouts by default).  ``space='params'``: the
+        candidates are the standardised parameters themselves (``var0`` ``0.001 / param_std**2``, 20 rollouts); with
+        ``anchor_start`` every candidate is projected onto starting where the initial trajectory starts, joint by joint.
+        ``search_options`` are ``search``'s (eliteness, weighting, cov_update, learning_rate, covar_bounds, tol, seed).
+
+        Returns ``search``'s dict and ``params [P, n_params]`` (the refined mean motion; latent space: its decoding), ``z`` (latent
+        space: the refined latent, else None), ``height [P]``, ``initial`` and ``final`` (dicts of ``cost``, ``img_l2``,
+        ``height_l2``, ``latent_l2`` at the start and at ``params``: ``writing_cost``'s values at ``height``) and ``image``, the
+        drawing of ``params``."""
+        w = writing_cost_args(weights, image_modality, canvas, self._widths)
+        R, extra = refine_motion_args(basis, chain, space, n_rollouts, modality, search_options, self._widths)
+        if target_image is None:
+            raise ValueError("target_image is None: the refinement needs the pictures to write")
+        tg, was_np = dev_array(target_image, canvas.n_pixels, self.device)
+        tg = tg.contiguous()
+        P = int(tg.shape[0])
+        latent = space == "latent"
+        start = None if init is None else dev_dense(init, self.n_z if latent else basis.n_params, self.device, P,
+                                                    "as target_image", name="init")
+        mats = motion_matrices(basis, self.device)
+        frames, axes = chain_matrices(chain, self.device)
+        plane = canvas_args(canvas, P, None, None, self.device)[0]
+        zt = self._encode(image_modality, tg)
+
+        def decode(z):
+            out = self._new(z.shape[0], basis.n_params)
+            if z.shape[0]:
+                _capi.check(self._h, self._L.avae_decode(self._h, modality, z.data_ptr(), z.shape[0], out.data_ptr(),
+                                                         self._stream()), "avae_decode")
+            return out
+        if latent or start is None:
+            z0 = zt.clone() if start is None else start
+            p0 = decode(z0)
+        else:
+            p0 = start
+        first = self._writing_cost(p0, mats, basis, frames, axes, plane, canvas, tg, None, zt, w, image_modality)
+        h0 = first["height"]
+        project = None
+        if latent:
+            x0, v0 = z0, 0.01 if var0 is None else var0
+        else:
+            x0 = p0
+            v0 = var0
+            if v0 is None:
+                v0 = 0.001 if basis.param_std is None else 0.001 / basis.param_std ** 2
+            if anchor_start:
+                A, b = basis.projection([0.0], first["trajectory"][:, 0, :].reshape(P, basis.n_dof, 1).cpu().numpy())
+                project = (torch.as_tensor(A.astype(np.float32)).to(self.device), torch.as_tensor(b.astype(np.float32)).to(self.device))
+
+        def price(cand, pidx):
+            return self._writing_cost(decode(cand) if latent else cand, mats, basis, frames, axes, plane, canvas,
+                                      tg.index_select(0, pidx), h0.index_select(0, pidx), zt.index_select(0, pidx), w,
+                                      image_modality)["cost"]
+        res = self.search(price, x0, v0, n_rollouts=R, n_iters=n_iters, project=project, **extra)
+        params = decode(res["mean"]) if latent else res["mean"]
+        last = self._writing_cost(params, mats, basis, frames, axes, plane, canvas, tg, h0, zt, w, image_modality)
+        conv = self._like_input(was_np)
+        terms = ("cost", "img_l2", "height_l2", "latent_l2")
+        out = {k: (v if k == "state" else conv(v)) for k, v in res.items()}
+        out.update(params=conv(params), z=conv(res["mean"]) if latent else None, height=conv(h0), image=conv(last["image"]),
+                   initial={k: conv(first[k]) for k in terms}, final={k: conv(last[k]) for k in terms})
+        return out
 
     def cycle_error(self, X, basis, chain, canvas, source=0, modality=1):
         """Does the motion predicted from a picture write that picture?  ``predict_motion`` from modality ``source`` alone, the
