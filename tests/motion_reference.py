@@ -152,7 +152,20 @@ def errors32(q, q_ref, Kb):
 
 
 def fit32(traj, pinv, scale=None, shift=None):
-    return fit64(traj, np.asarray(pinv, np.float32), scale, shift, dt=np.float32)
+    """k_motion_fit restated: theta[r][d][k] = sum_t pinv[k][t] traj[r][t][d] as one fma per t, t ascending, from 0 (a fused
+    multiply-add is formed in float64 and rounded once), then (theta - shift) / scale in float32.  (A float32 matrix product is
+    not that: a BLAS adds in several partial sums, which at T = 1024 is ten times closer to float64 than the kernel's one chain.)"""
+    traj, pinv = np.asarray(traj, np.float32), np.asarray(pinv, np.float32)
+    R, T, D = traj.shape
+    th = np.zeros((R, pinv.shape[0], D), np.float32)
+    for t in range(T):
+        th = (pinv[None, :, t, None].astype(np.float64) * traj[:, None, t, :].astype(np.float64) + th.astype(np.float64)).astype(np.float32)
+    th = np.swapaxes(th, -1, -2).reshape(R, -1)
+    sc = np.ones(th.shape[1], np.float32) if scale is None else np.asarray(scale, np.float32)
+    sh = np.zeros(th.shape[1], np.float32) if shift is None else np.asarray(shift, np.float32)
+    out = (th - sh) / sc
+    assert out.dtype == np.float32
+    return out
 
 
 def moments32(samples, phi, D, scale=None, shift=None, limits=None, gain=None, target=None):
@@ -260,6 +273,18 @@ def sandwich(q64_unclamped, limits, delta, axes):
 SHAPES = ((7, 21, 100), (1, 1, 1), (16, 64, 257), (3, 9, 2))           # (D, Kb, T)
 ROWS = (1, ROW_TILE - 1, ROW_TILE, ROW_TILE + 1, 15, 16, 17, 300)       # the kernel's row tile is 4: 3, 4, 5 straddle it
 VARIANTS = ("plain", "scaled", "limits", "anchor1", "anchor2", "all")
+# The slab classes of avae_motion.h (slab_of: min(4 (256 / D), 4096 / (Kb | 1), 512, T) points):
+#   (1, 5, 1024)   the 512 cap: two slabs, two points a thread
+#   (7, 21, 1024)  limited by 4 TQ = 144: 8 slabs, the last of 16 points
+#   (5, 13, 205)   204-point slabs and a last slab of one point
+#   (2, 64, 64)    63-point slabs (the phi budget, Kb | 1 = 65) and a last slab of one point
+#   (16, 20, 300)  64-point slabs, 44 in the last (three points a thread); P = 320: k_motion_fit's second parameter for 64 threads
+CLASS_SHAPES = ((1, 5, 1024), (7, 21, 1024), (5, 13, 205), (2, 64, 64), (16, 20, 300))
+CLASS_ROWS = (1, ROW_TILE + 1, 17)
+CLASS_VARIANTS = VARIANTS + ("anchor3", "anchor4")                     # n_c = 3, 4: the phases ANCHOR_PHASES[:n_c]
+ANCHOR_PHASES = (0.0, 0.25, 0.5, 1.0)
+MOMENT_CLASS_SHAPES = ((16, 64, 257), (7, 21, 1024))                   # several slabs each
+MOMENT_CLASS_S = (3, 5, 9)              # tiles of 4 samples: one short tile; a last tile of one sample; an odd count of 3 tiles
 
 
 def matrices(D, Kb, T, kind="sigmoid"):
@@ -275,7 +300,7 @@ def case(shape, rows, variant, seed=0, kind="sigmoid", S=None):
     some do not."""
     D, Kb, T = shape
     P = D * Kb
-    rng = np.random.default_rng([seed, D, Kb, T, rows, VARIANTS.index(variant), 0 if S is None else S])
+    rng = np.random.default_rng([seed, D, Kb, T, rows, CLASS_VARIANTS.index(variant), 0 if S is None else S])
     F, pinv = matrices(D, Kb, T, kind)
     c = dict(D=D, Kb=Kb, T=T, rows=rows, scale=None, shift=None, limits=None, gain=None, target=None, nc=0, F=F)
     theta = rng.standard_normal((rows, P) if S is None else (rows, S, P))
@@ -285,9 +310,9 @@ def case(shape, rows, variant, seed=0, kind="sigmoid", S=None):
         theta = (theta - sh) / sc
     c["params"] = theta.astype(np.float32)
     phi = F
-    nc = {"anchor1": 1, "anchor2": 2, "all": 2}.get(variant, 0)
+    nc = {"anchor1": 1, "anchor2": 2, "all": 2, "anchor3": 3, "anchor4": 4}.get(variant, 0)
     if nc:
-        ph = np.array([0.0, 1.0][:nc])
+        ph = np.array([0.0, 1.0][:nc] if nc <= 2 else ANCHOR_PHASES[:nc])
         A, Bm = constraint64(features64(kind, Kb - 1, ph))
         phi, c["gain"], c["nc"] = F @ A, (F @ Bm).astype(np.float32), nc
         c["target"] = rng.standard_normal((rows, D, nc)).astype(np.float32)

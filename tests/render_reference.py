@@ -19,6 +19,31 @@ FK_SHAPES = ((1, 1, 1), (3, 2, 3), (5, 100, 7), (2, 257, 16))
 RENDER_SHAPES = ((1, 28, 4), (2, 28, 1), (100, 28, 4), (100, 28, 8), (1024, 64, 2), (7, 5, 4))
 HALF_WIDTH, MARGIN, SCALE = 0.0625, 0.6, 0.03
 
+# The classes the kernels' own control flow distinguishes (csrc/avae_render.hip).  FK (rows, T, D): one tile of exactly 256 points
+# with D = 2 (row length D | 1 = 3), 256 points with D = 4 (row length 5), exactly 512 points with D = 8 (row length 9), 513 points
+# (a third tile of one point) with the odd D = 15.  FK_WILD: angles drawn uniformly in +-4 pi, past every joint limit.
+FK_CLASS_SHAPES = ((1, 256, 2), (4, 64, 4), (2, 256, 8), (3, 171, 15))
+FK_WILD = (5, 100, 7)
+# The renderer (T, H, ss), by the 64-pixel chunks of step 4 (two per wave and trip: k0, k0 + 4, stride 8), the passes of step 5
+# (256 / ss pixels each) and T against the 256 threads:
+#   (3, 1, 8)     one pixel: a chunk of one lane, 8 items
+#   (256, 8, 2)   exactly one full chunk (lane 63 owns a pixel), 255 segments
+#   (257, 16, 1)  4 chunks (every wave's second chunk is out of range), thread 0 owns two points, the segment loop is one trip
+#   (258, 20, 4)  7 chunks (the second element partly valid), 257 segments: a second trip of one
+#   (513, 23, 2)  9 chunks (a second trip for wave 0 only), a third point for thread 0
+#   (2, 64, 1)    64 chunks, ss = 1 on one segment, 256 pixels a pass
+#   (100, 64, 8)  H ss = 512 (the size the header's culling argument is made at), 32 pixels a pass
+RENDER_CLASS_SHAPES = ((3, 1, 8), (256, 8, 2), (257, 16, 1), (258, 20, 4), (513, 23, 2), (2, 64, 1), (100, 64, 8))
+# (half_width, margin): the writer's; a hairline in a window without margin (r / delta small: the half diagonal dominates the
+# culling threshold); a broad pen in a wide margin (r / delta large)
+RENDER_CLASS_PARAMS = ((HALF_WIDTH, MARGIN), (0.002, 0.0), (0.5, 3.0))
+RENDER_BIG = (100, 64, 8)                     # the definition and the restatement cost about 1.5 s a row here
+
+
+def class_params(shape):
+    """the (half_width, margin) pairs of a class shape: all three, the largest shape without the broad pen"""
+    return RENDER_CLASS_PARAMS[:2] if tuple(shape) == RENDER_BIG else RENDER_CLASS_PARAMS
+
 
 def rel_err(got, ref):
     """worst |err| / (|ref| + 1)"""
@@ -59,12 +84,16 @@ def random_joints(D, seed):
     return out
 
 
-def fk_case(shape, seed=0):
-    """-> dict(chain, frames, axes (float32), traj [rows, T, D] float32 inside the joint limits)"""
+def fk_case(shape, seed=0, wild=False):
+    """-> dict(chain, frames, axes (float32), traj [rows, T, D] float32 inside the joint limits; ``wild``: uniform in +-4 pi,
+    whatever the limits say)"""
     from vae_assoc_amd.kinematics import KinematicChain
     rows, T, D = shape
     chain = KinematicChain(fixture_joints(D) if D <= 7 else random_joints(D, seed))
-    rng = np.random.default_rng([seed, rows, T, D])
+    rng = np.random.default_rng([seed, rows, T, D] + ([1] if wild else []))
+    if wild:
+        frames, axes = chain.packed()
+        return dict(chain=chain, frames=frames, axes=axes, traj=rng.uniform(-4.0 * np.pi, 4.0 * np.pi, size=(rows, T, D)).astype(F32))
     lim = chain.limits
     q = rng.uniform(lim[:, 0], lim[:, 1], size=(rows, T, D))
     # a smooth motion between two poses, as a trajectory is, plus the random pose
@@ -322,6 +351,16 @@ def path_uv(family, T, rng):
     if family == "repeated":
         c = letter_uv((T + 1) // 2, rng)
         return np.repeat(c, 2, axis=0)[:T]
+    if family == "diagonal":                                            # the box test passes everywhere: the distance culls alone
+        return np.stack([tau, tau], 1)
+    if family == "frame":                                               # the square's outline, once: ink at the window's edge
+        s = np.linspace(0.0, 8.0, T)                                    # around an empty middle
+        side = np.minimum(s // 2.0, 3.0).astype(int)
+        a = s - 2.0 * side - 1.0                                        # -1 .. 1 along the side
+        one = np.ones(T)
+        u = np.select([side == 0, side == 1, side == 2, side == 3], [a, one, -a, -one])
+        v = np.select([side == 0, side == 1, side == 2, side == 3], [-one, a, one, -a])
+        return np.stack([u, v], 1)
     raise ValueError(family)
 
 
@@ -369,6 +408,59 @@ def render_refs(shape, seed=0):
                         render32(path, plane, r, mg, H, ss, target, height)))
         _CACHE[key] = out
     return _CACHE[key]
+
+
+CLASS_FAMILIES = FAMILIES + ("diagonal", "frame")
+SHORT_FAMILIES = ("dot", "line_u", "line_v", "diagonal", "scribble")     # what a path of two or three points can be
+
+
+def class_batches(shape, seed=0):
+    """The calls of one class shape: [(name, plane, path, height)], one call under the default plane and one under the rotated
+    one.  Every family under the first and six of them under the second; paths of two or three points take the families that
+    make sense at that length; the largest shape takes two rows a call."""
+    T = shape[0]
+    if tuple(shape) == RENDER_BIG:
+        plans = (("f", default_plane(), ("diagonal", "letter")), ("g", rotated_plane(), ("frame", "scribble")))
+    elif T < 5:
+        plans = (("f", default_plane(), SHORT_FAMILIES), ("g", rotated_plane(), ("diagonal", "scribble", "line_u")))
+    else:
+        plans = (("f", default_plane(), CLASS_FAMILIES),
+                 ("g", rotated_plane(), ("letter", "outlier", "scribble", "repeated", "diagonal", "frame")))
+    out = []
+    for name, plane, fams in plans:
+        rng = np.random.default_rng([seed, T, ord(name)])
+        path = np.stack([lift(path_uv(f, T, rng), plane, rng) for f in fams]).astype(F32)
+        pl32 = plane.astype(F32)
+        height = (path.astype(np.float64) @ pl32[2].astype(np.float64)).mean(1).astype(F32)
+        out.append((name, pl32, path, height))
+    return out
+
+
+def class_target(shape, name, rows, seed=0):
+    return np.random.default_rng([seed, shape[1], ord(name)]).random((rows, shape[1] * shape[1])).astype(F32)
+
+
+def class_refs(shape, params, seed=0):
+    """[(name, plane, path, height, target, r64, r32)] of ``class_batches(shape)`` drawn with params = (half_width, margin),
+    computed once per process"""
+    key = ("class", tuple(shape), tuple(params), seed)
+    if key not in _CACHE:
+        T, H, ss = shape
+        r, mg = F32(params[0]), F32(params[1])
+        out = []
+        for name, plane, path, height in class_batches(shape, seed):
+            target = class_target(shape, name, path.shape[0], seed)
+            out.append((name, plane, path, height, target, render64(path, plane, r, mg, H, ss, target, height),
+                        render32(path, plane, r, mg, H, ss, target, height)))
+        _CACHE[key] = out
+    return _CACHE[key]
+
+
+def class_coverage(shape, refs):
+    """What a class case has to exercise, from the definition alone -> (smallest inked share of a row, largest number of step-5
+    items, inked pixels x ss, of a row) over the calls of ``refs``"""
+    inked = np.concatenate([(r64["image"] > 0.0).sum(1) for _, _, _, _, _, r64, _ in refs])
+    return float(inked.min()) / (shape[1] * shape[1]), int(inked.max()) * shape[2]
 
 
 def render_errors(got, ref):

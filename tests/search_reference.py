@@ -4,6 +4,8 @@ kernel's order in every sum), the loop around them, and the cases the GPU tests 
 
 The stream: Philox4x32-10, key = (seed lo, seed hi ^ 'srch'), counter (problem_offset + p, r, dimension quad, iteration); the
 normals are the Box-Muller pairs of the block, formed as the internal eps is (tests/denoise_reference.py)."""
+import itertools
+
 import numpy as np
 
 from denoise_reference import philox4x32_10
@@ -248,6 +250,55 @@ SAMPLE_SHAPES = [(1, 1, 1), (3, 10, 20), (2, 20, 147), (5, 7, 63), (2, 3, 1000)]
 SAMPLE_GROUPS = {147: (7, 21), 1: (1, 1)}                               # n -> (G, g) of the cases run with a map
 UPDATE_SHAPES = SAMPLE_SHAPES + [(2, 300, 1000), (1, 1024, 64)]
 FAMILIES = ("spread", "equal", "two", "one_nan", "all_nan", "inf", "cem_ties")
+
+# The classes k_search_sample's tiling distinguishes: a tile holds 1024 / (4 ceil(n / 4)) rows of P R.
+#   (3, 100, 3)   256-row tiles, the one quad partial, a tile straddling three problems    (4, 1024, 2)  R = 1024, 16 such tiles
+#   (2, 5, 1024)  256 full quads, one row a tile                                            (2, 3, 1021)  the last quad partial
+#   (1, 7, 513)   129 quads: one row a tile, 508 floats of it idle                          (2, 9, 340)   a tile of 3 rows
+#   (3, 6, 128)   8 rows a tile, g = 64 in 2 groups                                         (7, 50, 5)    g = 1 with G = n
+#   (2, 17, 64)   G = 1 with g = n = 64
+SAMPLE_CLASS_SHAPES = [(3, 100, 3), (4, 1024, 2), (2, 5, 1024), (2, 3, 1021), (1, 7, 513), (2, 9, 340), (3, 6, 128), (7, 50, 5),
+                       (2, 17, 64)]
+SAMPLE_CLASS_GROUPS = {1024: (16, 64), 128: (2, 64), 5: (5, 1), 64: (1, 64)}
+# k_search_update: a thread owns the rollouts and the dimensions i, i + 256, ...: R and n at 255 / 256 / 257, both at 1024, n = 1
+# under 255 rollouts, two rollouts under three dimensions a thread
+UPDATE_CLASS_SHAPES = [(1, 257, 257), (3, 256, 256), (1, 1024, 1024), (2, 255, 1), (2, 2, 513)]
+
+
+def option_grid():
+    """every (family, weighting) pair twice: the covariance rule, the learning rate and the bounds alternate so that every value
+    of each meets every weighting"""
+    out = []
+    for i, (family, (weighting, e)) in enumerate(itertools.product(FAMILIES, ((PIBB, 10.0), (CEM, 3), (CMAES, 3)))):
+        for j in range(2):
+            k = i + j
+            bounds = dict(rel_lower=0.1, abs_lower=0.02, abs_upper=0.9) if (k // 2) % 2 == 0 else dict(rel_lower=-1.0)
+            out.append((family, options(weighting=weighting, eliteness=e, cov_update=(PIBB, CEM)[j], lr=(1.0, 0.5)[k % 2],
+                                        tol=1e-6, **bounds)))
+    return out
+
+
+def class_options():
+    """[(family, options, rel)] run at every UPDATE_CLASS_SHAPES next to the grid of test_gpu_search.py.  ``rel`` is None or a
+    factor: then ``abs_lower`` is to be set to rel_lower * vmax * rel, vmax the definition's own largest variance of problem 0 under
+    the same options without an absolute floor (``with_abs_lower``), which puts rel_lower * vmax just below or just above it."""
+    return [
+        ("spread", options(weighting=PIBB, eliteness=2000.0), None),                # exp underflows: w == 0 under PI-BB
+        ("spread", options(weighting=PIBB, eliteness=0.0, lr=0.5), None),           # every weight 1
+        ("spread", options(weighting=CEM, eliteness=1, cov_update=CEM, rel_lower=-1.0, abs_lower=0.3), None),
+        ("one_nan", options(weighting=CMAES, eliteness=4096, rel_lower=-1.0, abs_upper=0.2), None),    # mu >= R
+        ("spread", options(lr=0.0, rel_lower=0.5), None),
+        ("spread", options(rel_lower=0.0, abs_lower=0.0, abs_upper=0.0), None),
+        ("spread", options(weighting=CEM, eliteness=3, lr=0.5, rel_lower=0.25), 1.0 + 1e-3),   # rel_lower * vmax just below abs_lower
+        ("spread", options(weighting=CEM, eliteness=3, lr=0.5, rel_lower=0.25), 1.0 - 1e-3),   # ... just above
+    ]
+
+
+def with_abs_lower(x, cost, state, opt, rel):
+    """``opt`` with the absolute floor ``class_options`` describes"""
+    free, _ = update(x, cost, state, dict(opt, rel_lower=-1.0, abs_lower=-1.0))    # the variances behind the cap, before a floor
+    assert free["n_applied"][0] == 1
+    return dict(opt, abs_lower=float(opt["rel_lower"] * free["var"][0].max() * rel))
 
 
 def costs(family, P, R, rng, mu=3):

@@ -7,12 +7,14 @@ on a real MI355X (include/avae.h) against tests/motion_ref
 
 Rows (1, 3, 4, 5, 15, 16, 17, 300): the kernels' row tile is 4.  (D, Kb, T) in ((7, 21, 100), (1, 1, 1), (16, 64, 257), (3, 9, 2)),
 each with and without scale / shift, limits and anchors (n_c = 1, 2); theta ~ N(0, 1), limits at +-1.5 standard deviations, seeded.
+The slab, tile and alignment classes of the kernels (motion_reference.CLASS_SHAPES, MOMENT_CLASS_SHAPES; n_c = 3, 4; parameters
+that do not start on a 16-byte boundary) have tests of their own, whose docstrings name them; their pairs are in DESIGN.md section 23.
 
 Measured 2026-10-19 (kernel's worst / the float32 restatement's worst, the bound being 4x the latter; trajectory, rmse, max_abs,
-fitted parameters): (7, 21, 100) 1.37e-6 / 1.31e-6, 6.3e-7 / 7.4e-7, 2.94e-6 / 2.94e-6, 1.14e-5 / 1.22e-5; (1, 1, 1) 3.0e-8 / 6.7e-8,
+fitted parameters): (7, 21, 100) 1.37e-6 / 1.31e-6, 6.3e-7 / 7.4e-7, 2.94e-6 / 2.94e-6, 1.14e-5 / 1.14e-5; (1, 1, 1) 3.0e-8 / 6.7e-8,
 1.2e-7 / 2.9e-7, 1.2e-7 / 2.9e-7, 6.7e-8 / 6.7e-8; (16, 64, 257) 3.13e-6 / 3.84e-6, 4.26e-6 / 4.23e-6, 8.76e-6 / 8.76e-6, 2.05e-5 /
 2.05e-5; (3, 9, 2) 3.9e-7 / 3.8e-7, 8.2e-7 / 8.8e-7, 1.53e-6 / 1.53e-6, 9.8e-8 / 9.8e-8; gaussian (7, 21, 100) 3.2e-7 / 3.6e-7, 2.0e-7 /
-3.3e-7, 4.4e-7 / 5.5e-7, 8.5e-2 / 8.3e-2.  Moments, S = 1, 2, 7, 64: mean 9.5e-7, 1.30e-6, 6.8e-7, 4.5e-7 at (7, 21, 100) and 3.72e-6,
+3.3e-7, 4.4e-7 / 5.5e-7, 8.5e-2 / 8.5e-2.  Moments, S = 1, 2, 7, 64: mean 9.5e-7, 1.30e-6, 6.8e-7, 4.5e-7 at (7, 21, 100) and 3.72e-6,
 4.27e-6, 2.18e-6, 8.2e-7 at (16, 64, 257), the restatement's own the same; variance 0, 3.5e-7 / 3.7e-7, 2.7e-7 / 3.3e-7, 4.3e-7 / 4.3e-7
 and 0, 6.0e-7 / 6.1e-7, 6.9e-7 / 6.9e-7, 4.6e-7 / 5.1e-7 of max var."""
 import ctypes as C
@@ -68,6 +70,17 @@ def _dev(model, a):
     return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(model.device)
 
 
+def _dev_off(model, a, off):
+    """``a`` in a device buffer that starts ``off`` floats past a 16-byte boundary"""
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    buf = torch.empty(a.size + 4, dtype=torch.float32, device=model.device)
+    assert buf.data_ptr() % 16 == 0
+    view = buf[off:off + a.size].view(a.shape)
+    view.copy_(torch.from_numpy(a))
+    assert view.data_ptr() % 16 == 4 * off
+    return view
+
+
 def _p(t):
     return None if t is None else t.data_ptr()
 
@@ -76,8 +89,9 @@ def _stream(model):
     return C.c_void_p(torch.cuda.current_stream(model.device).cuda_stream)
 
 
-def _eval(model, c, params=None, want=("traj", "sat"), ref_traj=None, ref_params=None, anchor=True):
-    """avae_motion_eval on a case of motion_reference.case -> dict of the NumPy outputs asked for (``want``)"""
+def _eval(model, c, params=None, want=("traj", "sat"), ref_traj=None, ref_params=None, anchor=True, off=0):
+    """avae_motion_eval on a case of motion_reference.case -> dict of the NumPy outputs asked for (``want``).  ``off``: params
+    and ref_params start that many floats past a 16-byte boundary."""
     params = c["params"] if params is None else params
     N = params.shape[0]
     D, Kb, T = c["D"], c["Kb"], c["T"]
@@ -92,6 +106,8 @@ def _eval(model, c, params=None, want=("traj", "sat"), ref_traj=None, ref_params
     nc = c["nc"] if anchor else 0
     ts = [_dev(model, x) for x in (params, c["phi"], c["scale"], c["shift"], c["limits"], c["gain"] if nc else None,
                                    c["target"] if nc else None, ref_traj, ref_params)]
+    if off:
+        ts[0], ts[8] = _dev_off(model, params, off), None if ref_params is None else _dev_off(model, ref_params, off)
     rc = model._L.avae_motion_eval(model._h, _p(ts[0]), N, D, Kb, T, _p(ts[1]), _p(ts[2]), _p(ts[3]), _p(ts[4]), _p(ts[5]),
                                    _p(ts[6]), nc, _p(ts[7]), _p(ts[8]), _p(out.get("traj")), _p(out.get("sat")),
                                    _p(out.get("rmse")), _p(out.get("maxabs")), _stream(model))
@@ -100,17 +116,19 @@ def _eval(model, c, params=None, want=("traj", "sat"), ref_traj=None, ref_params
     return {k: v.cpu().numpy() for k, v in out.items()}
 
 
-def _fit(model, c, traj):
+def _fit(model, c, traj, off=0):
     N = traj.shape[0]
     out = torch.full((N, c["D"] * c["Kb"]), -7.0, device=model.device)
     ts = [_dev(model, x) for x in (traj, c["pinv"], c["scale"], c["shift"])]
+    if off:
+        ts[0] = _dev_off(model, traj, off)
     rc = model._L.avae_motion_fit(model._h, _p(ts[0]), N, c["D"], c["Kb"], c["T"], _p(ts[1]), _p(ts[2]), _p(ts[3]), _p(out),
                                   _stream(model))
     assert rc == 0, model._L.avae_last_error(model._h)
     return out.cpu().numpy()
 
 
-def _moments(model, c, samples=None, want=("mean", "var", "frac")):
+def _moments(model, c, samples=None, want=("mean", "var", "frac"), off=0):
     samples = c["params"] if samples is None else samples
     N, S = samples.shape[:2]
     D, Kb, T = c["D"], c["Kb"], c["T"]
@@ -120,6 +138,8 @@ def _moments(model, c, samples=None, want=("mean", "var", "frac")):
     if "frac" in want:
         out["frac"] = torch.full((N, D), -7.0, device=model.device)
     ts = [_dev(model, x) for x in (samples, c["phi"], c["scale"], c["shift"], c["limits"], c["gain"], c["target"])]
+    if off:
+        ts[0] = _dev_off(model, samples, off)
     rc = model._L.avae_motion_moments(model._h, _p(ts[0]), N, S, D, Kb, T, _p(ts[1]), _p(ts[2]), _p(ts[3]), _p(ts[4]), _p(ts[5]),
                                       _p(ts[6]), c["nc"], _p(out["mean"]), _p(out.get("var")), _p(out.get("frac")), _stream(model))
     assert rc == 0, model._L.avae_last_error(model._h)
@@ -133,14 +153,12 @@ def _ref_params(c, seed=99):
 
 
 # ------------------------------------------------------------------------------------------------ 1. eval, fit, errors
-@pytest.mark.parametrize("shape,kind", [(s, "sigmoid") for s in R.SHAPES] + [((7, 21, 100), "gaussian")])
-def test_eval_fit_and_errors_against_the_definition(V, shape, kind):
-    """The measured pairs are in the module docstring and in README.md."""
-    model = _model(V)
+def _check_eval_fit(model, shape, kind, rows_list, variants):
+    """the 4x rule on the trajectory, both errors and the fitted parameters over ``rows_list`` x ``variants``; saturated by sandwich"""
     names = ("trajectory", "rmse", "max_abs", "fit")
     own, got = dict.fromkeys(names, 0.0), dict.fromkeys(names, 0.0)
-    for rows in R.ROWS:
-        for variant in R.VARIANTS:
+    for rows in rows_list:
+        for variant in variants:
             c = R.case(shape, rows, variant, kind=kind)
             kw, D, Kb = R.eval_kw(c), c["D"], c["Kb"]
             q64, _ = R.eval64(c["params"], c["phi"], D, **kw)
@@ -176,13 +194,25 @@ def test_eval_fit_and_errors_against_the_definition(V, shape, kind):
         assert got[name] <= 4.0 * own[name], name
 
 
+@pytest.mark.parametrize("shape,kind", [(s, "sigmoid") for s in R.SHAPES] + [((7, 21, 100), "gaussian")])
+def test_eval_fit_and_errors_against_the_definition(V, shape, kind):
+    """The measured pairs are in the module docstring and in README.md."""
+    _check_eval_fit(_model(V), shape, kind, R.ROWS, R.VARIANTS)
+
+
+@pytest.mark.parametrize("shape", R.CLASS_SHAPES)
+def test_eval_fit_and_errors_at_every_slab_class(V, shape):
+    """The slab classes of k_motion_eval (motion_reference.CLASS_SHAPES; a slab is min(4 (256 / D), 4096 / (Kb | 1), 512, T) points):
+    (1, 5, 1024) the 512 cap, two slabs; (7, 21, 1024) slabs of 4 TQ = 144, the last of 16; (5, 13, 205) and (2, 64, 64) a last slab
+    of one point; (16, 20, 300) 64-point slabs with 44 in the last, and P = 320 (k_motion_fit's threads 0..63 own a second
+    parameter).  Rows 1, 5, 17; every variant and anchors at three and four phases (n_c = 3, 4).  The pairs: DESIGN.md section 23."""
+    _check_eval_fit(_model(V), shape, "sigmoid", R.CLASS_ROWS, R.CLASS_VARIANTS)
+
+
 # ------------------------------------------------------------------------------------------------ 2. moments
-@pytest.mark.parametrize("S", [1, 2, 7, 64])
-@pytest.mark.parametrize("shape", [R.SHAPES[0], R.SHAPES[2]])
-def test_moments_against_the_definition(V, shape, S):
-    model = _model(V)
+def _check_moments(model, shape, S, rows_list):
     own, got = [0.0, 0.0], [0.0, 0.0]
-    for rows in R.ROWS:
+    for rows in rows_list:
         for variant in ("plain", "all"):
             c = R.case(shape, rows, variant, S=S)
             kw, D = R.eval_kw(c), c["D"]
@@ -207,7 +237,41 @@ def test_moments_against_the_definition(V, shape, S):
     assert got[0] <= 4.0 * own[0] and got[1] <= 4.0 * own[1]
 
 
+@pytest.mark.parametrize("S", [1, 2, 7, 64])
+@pytest.mark.parametrize("shape", [R.SHAPES[0], R.SHAPES[2]])
+def test_moments_against_the_definition(V, shape, S):
+    _check_moments(_model(V), shape, S, R.ROWS)
+
+
+@pytest.mark.parametrize("S", R.MOMENT_CLASS_S)
+@pytest.mark.parametrize("shape", R.MOMENT_CLASS_SHAPES)
+def test_moments_at_every_tile_class(V, shape, S):
+    """k_motion_moments double-buffers tiles of 4 samples; with several slabs ((16, 64, 257): 5, (7, 21, 1024): 8) S = 3 is one
+    short tile, S = 5 a last tile of one sample, S = 9 an odd count of tiles.  Rows 1 and 5."""
+    _check_moments(_model(V), shape, S, (1, 5))
+
+
 # ------------------------------------------------------------------------------------------------ 3. bits
+@pytest.mark.parametrize("shape", [(7, 21, 1024), (16, 20, 300)], ids=["P_odd", "P_even"])
+def test_a_misaligned_base_gives_the_same_bits(V, shape):
+    """tile_load / tile_store take a head of up to 3 scalars when the source is not 16-byte aligned: parameters, reference
+    parameters, samples and trajectories 1, 2 and 3 floats past a 16-byte boundary give the bits of the aligned call.  P = 147
+    (odd: the rows of a tile change alignment among themselves) and P = 320."""
+    model = _model(V)
+    every = ("traj", "sat", "rmse", "maxabs")
+    c = R.case(shape, 5, "all")
+    refp = _ref_params(c)
+    full = _eval(model, c, want=every, ref_params=refp)
+    fit = _fit(model, c, full["traj"])
+    cs = R.case(shape, 2, "all", S=5)
+    mo = _moments(model, cs)
+    for off in (1, 2, 3):
+        assert _same(_eval(model, c, want=every, ref_params=refp, off=off).values(), full.values()), off
+        assert np.array_equal(_bits(_fit(model, c, full["traj"], off=off)), _bits(fit)), off
+        assert _same(_moments(model, cs, off=off).values(), mo.values()), off
+    assert np.isfinite(full["traj"]).all() and np.isfinite(fit).all() and np.isfinite(mo["mean"]).all()
+
+
 def test_bit_reproducibility_and_independence(V):
     model = _model(V)
     c = R.case((7, 21, 100), 300, "all")
@@ -377,6 +441,21 @@ def test_python_surface_against_the_definition(V):
         model.motion_eval(p[:, :146], b)
     with pytest.raises(ValueError):
         model.motion_moments(s, b, anchor=dict(phases=[0.0], target=anchor["target"]))
+
+
+def test_a_slice_of_a_device_tensor_evaluates_to_the_rows_of_the_whole(V):
+    """P = 147 is odd: ``p[k:]`` starts 3, 2, 1 floats past a 16-byte boundary for k = 1, 2, 3 and is handed on as it is"""
+    model, b = _model(V), _basis(V)
+    rng = np.random.default_rng(9)
+    p = torch.from_numpy(rng.standard_normal((9, 147)).astype(np.float32)).to(model.device)
+    anchor = dict(phases=[0.0, 1.0], target=rng.standard_normal((9, 7, 2)).astype(np.float32))
+    whole = model.motion_eval(p, b, anchor=anchor, reference_params=p.flip(0))
+    for k in (1, 2, 3):
+        assert p[k:].data_ptr() % 16 == 4 * (4 - k) and p[k:].is_contiguous()
+        part = model.motion_eval(p[k:], b, anchor=dict(anchor, target=anchor["target"][k:]), reference_params=p.flip(0)[k:])
+        for key in ("trajectory", "saturated", "rmse", "max_abs"):
+            assert np.array_equal(_bits(part[key]), _bits(whole[key][k:])), (k, key)
+    assert np.isfinite(whole["trajectory"].cpu().numpy()).all() and (whole["rmse"] > 0).any()
 
 
 def test_predict_motion_and_motion_error(V):

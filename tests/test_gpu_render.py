@@ -7,7 +7,9 @@ reproducibility and independence; 4. non-finite paths; 5. edges and errors of th
 
 The shapes, path families and planes are render_reference's: FK (rows, T, D) = (1, 1, 1), (3, 2, 3), (5, 100, 7) on the fixture chain
 inside its joint limits and (2, 257, 16) on a random chain; the renderer at (T, H, ss) = (1, 28, 4), (2, 28, 1), (100, 28, 4),
-(100, 28, 8), (1024, 64, 2), (7, 5, 4), calls of 1 to 5 rows.  The measured pairs are in README.md and DESIGN.md section 24."""
+(100, 28, 8), (1024, 64, 2), (7, 5, 4), calls of 1 to 5 rows.  The ``*_classes_*`` tests sweep the classes of shape the kernels'
+control flow distinguishes (render_reference.FK_CLASS_SHAPES, RENDER_CLASS_SHAPES, RENDER_CLASS_PARAMS; each test's docstring
+names them).  The measured pairs are in README.md and DESIGN.md section 24."""
 import ctypes as C
 
 import numpy as np
@@ -115,6 +117,25 @@ def test_fk_against_the_definition(V, shape):
     assert _same(model.motion_fk(torch.from_numpy(c["traj"][-1:]).to(model.device), chain), got[-1:])
 
 
+@pytest.mark.parametrize("shape,wild", [(s, False) for s in R.FK_CLASS_SHAPES] + [(R.FK_WILD, True)])
+def test_fk_classes_against_the_definition(V, shape, wild):
+    """The tile and row-length classes of k_motion_fk (render_reference.FK_CLASS_SHAPES): (1, 256, 2) one tile of exactly 256 points,
+    LDS rows of D | 1 = 3; (4, 64, 4) 256 points over four rows, rows of 5; (2, 256, 8) exactly two tiles, rows of 9; (3, 171, 15)
+    513 points: a third tile of one point, the odd D = 15.  (5, 100, 7) with angles uniform in +-4 pi: sincosf past +-pi, which
+    the limits of the other cases never reach.  The 4x rule, the bits of a repeat and of the last row alone."""
+    model = _model(V)
+    c = R.fk_case(shape, wild=wild)
+    assert not wild or np.abs(c["traj"]).max() > 3.0 * np.pi
+    r64, r32 = R.fk64(c["traj"], c["frames"], c["axes"]), R.fk32(c["traj"], c["frames"], c["axes"])
+    got = _fk(model, c["traj"], c["frames"], c["axes"])
+    own, err = R.rel_err(r32, r64), R.rel_err(got, r64)
+    print("fk %s%s: kernel %.3e, restatement %.3e (bound 4x)" % (shape, " wild" if wild else "", err, own))
+    assert got.shape == r64.shape and err <= 4.0 * own
+    assert _same(_fk(model, c["traj"], c["frames"], c["axes"]), got)
+    assert _same(_fk(model, c["traj"][-1:], c["frames"], c["axes"]), got[-1:])
+    assert _same(model.motion_fk(c["traj"], c["chain"]), got)
+
+
 def test_fk_seed_pose_lands_on_the_block_center(V):
     from vae_assoc_amd.kinematics import KinematicChain
     model, fx = _model(V), R.fixture()
@@ -141,7 +162,70 @@ def test_render_against_the_definition(V, shape):
         assert got[k] <= 4.0 * own[k], k
 
 
+CLASS_CASES = [(s, p) for s in R.RENDER_CLASS_SHAPES for p in R.class_params(s)]
+CLASS_IDS = ["%d-%d-%d r%g m%g" % (s + p) for s, p in CLASS_CASES]
+
+
+@pytest.mark.parametrize("shape,params", CLASS_CASES, ids=CLASS_IDS)
+def test_render_classes_against_the_definition(V, shape, params):
+    """The classes k_stroke_render's control flow distinguishes (render_reference.RENDER_CLASS_SHAPES), by the 64-pixel chunks of
+    step 4, the passes of step 5 and T against the 256 threads: (3, 1, 8) one pixel; (256, 8, 2) exactly one full chunk;
+    (257, 16, 1) 4 chunks, thread 0 owns two points; (258, 20, 4) 7 chunks, 257 segments; (513, 23, 2) 9 chunks; (2, 64, 1)
+    64 chunks, ss = 1, 256 pixels a pass; (100, 64, 8) H ss = 512, 32 pixels a pass.  Each with (half_width, margin) = the
+    writer's, a hairline without margin and a broad pen in a wide margin (the culling threshold depends on r / delta and the
+    margin), every family and the two that leave the culling to the distance test (``diagonal``, ``frame``), under both planes.
+
+    a. the 4x rule on every output; b. no pixel the restatement (which does not cull) inks is exactly +0 in the kernel's image;
+    c. on the definition alone: a row with fewer than half its pixels inked (at H = 1 the one pixel is inked: nothing can be
+    culled and the condition is that it is), and where H H ss > 256 a row whose inked pixels x ss exceed 256, so step 5 takes a
+    second pass.  At margin 3 the ink box spans a quarter of the window, at most (H / 4 + 2)^2 pixels; at H <= 23 that is one pass
+    whatever the path and at (2, 64, 1) a two-point path cannot fill it: the second condition is asserted for margins below 1."""
+    model = _model(V)
+    T, H, ss = shape
+    r, mg = float(np.float32(params[0])), float(np.float32(params[1]))
+    refs = R.class_refs(shape, params)
+    share, items = R.class_coverage(shape, refs)
+    assert share < 0.5 if H > 1 else share == 1.0, share
+    if H * H * ss > R.THREADS and mg < 1.0:
+        assert items > R.THREADS, items
+    own, got = dict.fromkeys(OUTPUTS, 0.0), dict.fromkeys(OUTPUTS, 0.0)
+    for name, plane, path, height, target, r64, r32 in refs:
+        g = _render(model, path, plane, H, ss, target, height, r=r, margin=mg)
+        e_own, e_got = R.render_errors(r32, r64), R.render_errors(g, r64)
+        for k in OUTPUTS:
+            own[k], got[k] = max(own[k], e_own[k]), max(got[k], e_got[k])
+        lost = (r32["image"] != 0.0) & (_bits(g["image"]) == 0)
+        assert not lost.any(), (name, np.argwhere(lost)[:4])
+    for k in OUTPUTS:
+        print("render %s r=%g margin=%g %s: kernel %.3e, restatement %.3e (bound 4x)" % (shape, r, mg, k, got[k], own[k]))
+    for k in OUTPUTS:
+        assert got[k] <= 4.0 * own[k], k
+
+
 # ------------------------------------------------------------------------------------------------ 3. bits
+@pytest.mark.parametrize("params", R.RENDER_CLASS_PARAMS[:2], ids=["writer", "margin0"])
+@pytest.mark.parametrize("shape", [(257, 16, 1), R.RENDER_BIG])
+def test_class_rows_outputs_and_streams_give_the_same_bits(V, shape, params):
+    """A row alone, an output alone and a second stream at (257, 16, 1) (4 chunks, two points for thread 0) and (100, 64, 8)
+    (32 pixels a pass, lists of thousands of items), with the writer's margin and with none"""
+    model = _model(V)
+    T, H, ss = shape
+    kw = dict(r=float(np.float32(params[0])), margin=float(np.float32(params[1])))
+    name, plane, path, height = R.class_batches(shape)[0]
+    target = R.class_target(shape, name, path.shape[0])
+    full = _render(model, path, plane, H, ss, target, height, **kw)
+    for i in range(path.shape[0]):
+        one = _render(model, path[i:i + 1], plane, H, ss, target[i:i + 1], height[i:i + 1], **kw)
+        assert all(_same(one[k], full[k][i:i + 1]) for k in OUTPUTS), (shape, i)
+    for k in OUTPUTS:
+        assert _same(_render(model, path, plane, H, ss, target, height, want=(k,), **kw)[k], full[k]), (shape, k)
+    side = torch.cuda.Stream(device=model.device)
+    with torch.cuda.stream(side):
+        other = _render(model, path, plane, H, ss, target, height, **kw)
+    assert all(_same(other[k], full[k]) for k in OUTPUTS)
+    assert (full["image"] > 0).any(1).all() and not (full["image"] == -7.0).any()
+
+
 def test_rows_outputs_streams_and_repetition_give_the_same_bits(V):
     model = _model(V)
     for shape in ((100, 28, 4), (7, 5, 4), (1024, 64, 2)):

@@ -3,10 +3,10 @@ section 25) against tests/search_reference.py.
 
 1. the sampler and 2. the update against the float64 definition, within 4x the restatement's own worst error over the same inputs
 (|err| / (|ref| + 1) per quantity, variances relative to the problem's largest), bit reproducibility and independence; 3. the loop;
-4. refine_motion on the small fp32 model of test_gpu_render.py; 5. edges and errors of the C ABI.  The measured pairs are in
-README.md and DESIGN.md section 25."""
+4. refine_motion on the small fp32 model of test_gpu_render.py; 5. edges and errors of the C ABI.  The ``*_classes_*`` tests sweep
+the tile and ownership classes of the two kernels (search_reference.SAMPLE_CLASS_SHAPES, UPDATE_CLASS_SHAPES, class_options; each
+test's docstring names them).  The measured pairs are in README.md and DESIGN.md section 25."""
 import ctypes as C
-import itertools
 
 import numpy as np
 import pytest
@@ -128,22 +128,20 @@ def _var_err(got, ref):
 
 
 # ------------------------------------------------------------------------------------------------ 1. the sampler
-def _sample_case(shape, seed=0):
+def _sample_case(shape, seed=0, groups=S.SAMPLE_GROUPS):
     P, R, n = shape
     rng = np.random.default_rng(seed)
     mean, var = rng.standard_normal((P, n)).astype(np.float32), (0.05 + rng.random((P, n))).astype(np.float32)
     proj = None
-    if n in S.SAMPLE_GROUPS:
-        G, g = S.SAMPLE_GROUPS[n]
+    if n in groups:
+        G, g = groups[n]
         proj = ((rng.standard_normal((G, g, g)) / np.sqrt(g)).astype(np.float32), rng.standard_normal((P, n)).astype(np.float32))
     return mean, var, proj
 
 
-@pytest.mark.parametrize("shape", S.SAMPLE_SHAPES)
-def test_sample_against_the_definition(V, shape):
-    model = _model(V)
+def _check_sample(model, shape, mean, var, proj):
+    """the 4x rule without and with the map, the last problem alone with its problem_offset, repetition, other draws"""
     P, R, n = shape
-    mean, var, proj = _sample_case(shape)
     for pr in (None,) + ((proj,) if proj is not None else ()):
         r64, r32 = S.sample(mean, var, 5, 3, R, 0, pr), S.sample_restated(mean, var, 5, 3, R, 0, pr)
         got = _sample(model, mean, var, R, proj=pr)
@@ -158,6 +156,34 @@ def test_sample_against_the_definition(V, shape):
             assert (_sample(model, mean, var, R, proj=pr, **kw) != got).any(-1).all(), kw
 
 
+@pytest.mark.parametrize("shape", S.SAMPLE_SHAPES)
+def test_sample_against_the_definition(V, shape):
+    _check_sample(_model(V), shape, *_sample_case(shape))
+
+
+@pytest.mark.parametrize("shape", S.SAMPLE_CLASS_SHAPES)
+def test_sample_classes_against_the_definition(V, shape):
+    """The tile classes of k_search_sample (search_reference.SAMPLE_CLASS_SHAPES; a tile is 1024 / (4 ceil(n / 4)) rows):
+    (3, 100, 3) 256-row tiles that straddle problems, the one quad partial; (4, 1024, 2) R = 1024; (2, 5, 1024) 256 full quads, one
+    row a tile; (2, 3, 1021) the last quad partial; (1, 7, 513) 129 quads; (2, 9, 340) tiles of 3 rows; (3, 6, 128) with (G, g) =
+    (2, 64), the largest g; (7, 50, 5) g = 1 with G = n; (2, 17, 64) G = 1 with g = n; n = 1024 with (16, 64).  Next to the checks of
+    the workload shapes: a variance of zero gives the mean, bit for bit, and with a map the map of the mean within 4x."""
+    model = _model(V)
+    P, R, n = shape
+    mean, var, proj = _sample_case(shape, groups=S.SAMPLE_CLASS_GROUPS)
+    assert (proj is not None) == (n in S.SAMPLE_CLASS_GROUPS)
+    _check_sample(model, shape, mean, var, proj)
+    zero = np.zeros_like(var)
+    got = _sample(model, mean, zero, R)
+    assert _same(got, np.broadcast_to(mean[:, None, :], (P, R, n)))
+    if proj is not None:
+        r64, r32 = S.sample(mean, zero, 5, 3, R, 0, proj), S.sample_restated(mean, zero, 5, 3, R, 0, proj)
+        got = _sample(model, mean, zero, R, proj=proj)
+        own, err = _rel(r32, r64), _rel(got, r64)
+        print("sample %s mapped, var = 0: kernel %.3e, restatement %.3e (bound 4x)" % (shape, err, own))
+        assert err <= 4.0 * own and _same(got, np.broadcast_to(got[:, :1], got.shape))
+
+
 def test_sample_moments(V):
     model = _model(V)
     rng = np.random.default_rng(1)
@@ -170,28 +196,17 @@ def test_sample_moments(V):
 
 
 # ------------------------------------------------------------------------------------------------ 2. the update
-def _option_grid():
-    """every (family, weighting) pair twice: the covariance rule, the learning rate and the bounds alternate so that every value
-    of each meets every weighting"""
-    out = []
-    for i, (family, (weighting, e)) in enumerate(itertools.product(S.FAMILIES, ((S.PIBB, 10.0), (S.CEM, 3), (S.CMAES, 3)))):
-        for j in range(2):
-            k = i + j
-            bounds = dict(rel_lower=0.1, abs_lower=0.02, abs_upper=0.9) if (k // 2) % 2 == 0 else dict(rel_lower=-1.0)
-            out.append((family, S.options(weighting=weighting, eliteness=e, cov_update=(S.PIBB, S.CEM)[j], lr=(1.0, 0.5)[k % 2],
-                                          tol=1e-6, **bounds)))
-    return out
-
-
-@pytest.mark.parametrize("shape", S.UPDATE_SHAPES)
-def test_update_against_the_definition(V, shape):
-    model = _model(V)
+def _check_update(V, model, shape, cases, seed=2):
+    """``cases``: [(family, options, rel)] (rel: search_reference.class_options).  n_applied and frozen equal to both references,
+    the best rollout bitwise the restatement's, every history entry written, untouched problems unchanged, the 4x rule on the rest"""
     P, R, n = shape
-    rng = np.random.default_rng(2)
+    rng = np.random.default_rng(seed)
     own = dict(mean=0.0, var=0.0, avg_cost=0.0, min_cost=0.0, moved=0.0)
     err = dict(own)
-    for family, opt in _option_grid():
+    for family, opt, rel in cases:
         x, c, st = S.update_case(P, R, n, family, rng)
+        if rel is not None:
+            opt = S.with_abs_lower(x, c, st, opt, rel)
         d64, h64 = S.update(x, c, st, opt)
         d32, h32 = S.update_restated(x, c, st, opt)
         got, hg = _update(V, model, x, c, st, opt)
@@ -209,6 +224,23 @@ def test_update_against_the_definition(V, shape):
     for k in own:
         print("update %s %s: kernel %.3e, restatement %.3e (bound 4x)" % (shape, k, err[k], own[k]))
         assert err[k] <= 4.0 * own[k], k
+
+
+@pytest.mark.parametrize("shape", S.UPDATE_SHAPES)
+def test_update_against_the_definition(V, shape):
+    _check_update(V, _model(V), shape, [(family, opt, None) for family, opt in S.option_grid()])
+
+
+@pytest.mark.parametrize("shape", S.UPDATE_CLASS_SHAPES)
+def test_update_classes_against_the_definition(V, shape):
+    """The ownership classes of k_search_update (search_reference.UPDATE_CLASS_SHAPES; a thread owns the rollouts and the dimensions
+    i, i + 256, ...): (1, 257, 257) one rollout and one dimension past the first trip; (3, 256, 256) exactly one trip; (1, 1024,
+    1024) four of each; (2, 255, 1) one thread without a rollout, one dimension; (2, 2, 513) two rollouts, a third dimension for
+    thread 0.  Over the option grid of the workload shapes and search_reference.class_options: PI-BB with eliteness 2000 (exp
+    underflows, the w == 0 skip) and 0; CEM keeping one rollout with its own covariance rule and abs_lower alone; CMA-ES keeping
+    more than there are, a NaN among them, abs_upper alone; learning rate 0 with rel_lower 0.5; every bound 0; rel_lower * vmax
+    just below and just above abs_lower."""
+    _check_update(V, _model(V), shape, [(family, opt, None) for family, opt in S.option_grid()] + S.class_options())
 
 
 def test_update_alone_frozen_streams_and_optional_outputs_give_the_same_bits(V):

@@ -109,6 +109,73 @@ def test_restatement_is_close_to_the_definition(shape, variant):
     assert p32.dtype == np.float32 and R.rel_err(p32, p64) < 1e-3
 
 
+def test_class_shapes_stand_for_their_slab_classes():
+    assert [R.slab_of(*s) for s in R.CLASS_SHAPES] == [(512, 256), (144, 36), (204, 51), (63, 128), (64, 16)]
+    assert [s[2] % R.slab_of(*s)[0] for s in R.CLASS_SHAPES] == [0, 16, 1, 1, 44]                 # the last slab
+    assert [-(-s[2] // R.slab_of(*s)[0]) for s in R.MOMENT_CLASS_SHAPES] == [5, 8]                # slabs of the moment cases
+    assert R.CLASS_ROWS == (1, 5, 17) and R.CLASS_VARIANTS[:len(R.VARIANTS)] == R.VARIANTS
+    assert [(S + 3) // 4 for S in R.MOMENT_CLASS_S] == [1, 2, 3] and [S % 4 for S in R.MOMENT_CLASS_S] == [3, 1, 1]
+
+
+@pytest.mark.parametrize("shape", R.CLASS_SHAPES)
+def test_restatement_is_close_to_the_definition_at_the_class_shapes(shape):
+    """test_gpu_motion.py's class sweep: every quantity under its 4x rule has a non-zero restatement error over the rows and
+    variants it runs, some points clamp and some do not, and the anchors of three and four phases hold"""
+    D, Kb, T = shape
+    worst = dict.fromkeys(("trajectory", "rmse", "max_abs", "fit"), 0.0)
+    for rows in R.CLASS_ROWS:
+        for variant in R.CLASS_VARIANTS:
+            c = R.case(shape, rows, variant)
+            again = R.case(shape, rows, variant)
+            assert all(np.array_equal(c[k], again[k]) for k in ("params", "phi", "pinv")) and c["rows"] == rows
+            assert not np.array_equal(c["params"], R.case(shape, rows, variant, seed=1)["params"])
+            kw = R.eval_kw(c)
+            q64, s64 = R.eval64(c["params"], c["phi"], D, **kw)
+            q32, s32 = R.eval32(c["params"], c["phi"], D, **kw)
+            raw = R.unclamped(c["params"], c["phi"], D, c["scale"], c["shift"], c["gain"], c["target"])
+            lo, hi = R.sandwich(raw, c["limits"], 4 * float(np.abs(q32 - q64).max()), 1)
+            assert (lo <= s32).all() and (s32 <= hi).all() and (lo <= s64).all() and (s64 <= hi).all()
+            if c["limits"] is not None:
+                assert 0 < s64.sum() < s64.size * T
+            if variant in ("anchor3", "anchor4"):
+                nc = c["nc"]
+                assert nc == int(variant[-1]) and c["gain"].shape == (T, nc) and c["target"].shape == (rows, D, nc)
+                F = R.features64("sigmoid", Kb - 1, np.array(R.ANCHOR_PHASES[:nc]))      # the trajectory at the anchored phases
+                A, Bm = R.constraint64(F)
+                th = c["params"].astype(np.float64).reshape(rows, D, Kb)
+                at = np.einsum("ck,rdk->rdc", F @ A, th) + np.einsum("cj,rdj->rdc", F @ Bm, c["target"].astype(np.float64))
+                assert np.abs(at - c["target"]).max() < 1e-9 * (1 + np.abs(raw).max())
+                assert np.abs(raw[:, [0, T - 1][:1 if nc == 3 else 2], :].transpose(0, 2, 1)
+                              - c["target"][:, :, [0, 3][:1 if nc == 3 else 2]]).max() < 1e-4 * (1 + np.abs(raw).max())
+            refp = (c["params"] + 0.1).astype(np.float32)
+            kw_ref = dict(kw, gain=None, target=None)
+            e64 = R.errors64(q64, R.eval64(refp, c["phi"], D, **kw_ref)[0])
+            e32 = R.errors32(q32, R.eval32(refp, c["phi"], D, **kw_ref)[0], Kb)
+            f64, f32 = R.fit64(q64.astype(np.float32), c["pinv"], c["scale"], c["shift"]), \
+                R.fit32(q64.astype(np.float32), c["pinv"], c["scale"], c["shift"])
+            for name, a, b in (("trajectory", q32, q64), ("rmse", e32[0], e64[0]), ("max_abs", e32[1], e64[1]), ("fit", f32, f64)):
+                worst[name] = max(worst[name], R.rel_err(a, b))
+    assert all(0.0 < v < 1e-3 for v in worst.values()), worst
+    assert worst["trajectory"] < 1e-5 and worst["rmse"] < 1e-5 and worst["max_abs"] < 1e-4
+
+
+@pytest.mark.parametrize("S", R.MOMENT_CLASS_S)
+@pytest.mark.parametrize("shape", R.MOMENT_CLASS_SHAPES)
+def test_moments_restatement_at_the_tile_classes(shape, S):
+    worst = [0.0, 0.0]
+    for rows in (1, 5):
+        for variant in ("plain", "all"):
+            c = R.case(shape, rows, variant, S=S)
+            assert c["params"].shape == (rows, S, shape[0] * shape[1])
+            both = R.moments_both(c["params"], c["phi"], shape[0], **R.eval_kw(c))
+            (m64, v64, _), (m32, v32) = both["r64"], both["r32"]
+            worst = [max(worst[0], R.rel_err(m32, m64)), max(worst[1], R.var_err(v32, v64))]
+            lo, hi = both["counts"](4.0 * both["worst"])
+            assert (lo <= hi).all() and 0 < both["worst"] < 1e-4
+            assert np.array_equal(R.case(shape, rows, variant, S=S)["params"], c["params"])
+    assert 0.0 < worst[0] < 1e-5 and 0.0 < worst[1] < 1e-5, worst
+
+
 def test_moments_restatement():
     c = R.case((7, 21, 100), 5, "all", S=7)
     kw = R.eval_kw(c)

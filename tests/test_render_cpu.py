@@ -206,6 +206,62 @@ def test_render_restatement_is_close_to_the_definition(shape):
     assert sorted(rows) == [1, 2, 3, 4, 5]
 
 
+@pytest.mark.parametrize("shape,wild", [(s, False) for s in R.FK_CLASS_SHAPES] + [(R.FK_WILD, True)])
+def test_fk_restatement_is_close_to_the_definition_at_the_class_shapes(shape, wild):
+    c = R.fk_case(shape, wild=wild)
+    r64, r32 = R.fk64(c["traj"], c["frames"], c["axes"]), R.fk32(c["traj"], c["frames"], c["axes"])
+    assert r32.dtype == np.float32 and r32.shape == shape[:2] + (3,)
+    assert 0.0 < R.rel_err(r32, r64) < 2e-6
+    again = R.fk_case(shape, wild=wild)
+    assert np.array_equal(again["traj"], c["traj"]) and np.array_equal(again["frames"], c["frames"])
+    lim = c["chain"].limits.astype(np.float32)
+    inside = ((c["traj"] >= lim[:, 0]) & (c["traj"] <= lim[:, 1])).all()
+    assert inside != wild and (not wild or np.abs(c["traj"]).max() > 3.0 * np.pi)
+    if shape[2] > 7:
+        assert shape[2] == c["chain"].n_dof and not np.array_equal(c["traj"], R.fk_case(shape, seed=1)["traj"])
+
+
+def test_the_new_path_families_are_what_they_say_and_seeded():
+    for T in (5, 9, 100, 257):
+        d, f = R.path_uv("diagonal", T, None), R.path_uv("frame", T, None)
+        assert d.shape == f.shape == (T, 2)
+        assert np.array_equal(d[:, 0], d[:, 1]) and d[0].tolist() == [-1.0, -1.0] and d[-1].tolist() == [1.0, 1.0]
+        assert np.abs(f).max(1).min() == 1.0 and np.abs(f).max() == 1.0            # every point on the square's outline
+        assert np.array_equal(f[0], f[-1]) and f[0].tolist() == [-1.0, -1.0]       # traversed once, closed
+        step = np.abs(np.diff(f, axis=0)).sum(1)
+        assert np.abs(step.sum() - 8.0) < 1e-12 and step.max() <= 8.0 / (T - 1) + 1e-12
+    # the frame's ink hugs the window's edge around an empty middle; the diagonal passes the box test everywhere
+    out = _draw(R.path_uv("frame", 100, None), r=0.002, margin=0.0, H=16, ss=1)["image"][0].reshape(16, 16)
+    assert (out[[0, -1]] > 0).all() and (out[:, [0, -1]] > 0).all() and not out[1:-1, 1:-1].any()
+    out = _draw(R.path_uv("diagonal", 100, None), r=0.002, margin=0.0, H=16, ss=1)["image"][0].reshape(16, 16)
+    assert (np.diag(out[::-1]) > 0).all() and (out > 0).sum() <= 3 * 16
+    for shape in R.RENDER_CLASS_SHAPES:
+        a, b = R.class_batches(shape), R.class_batches(shape)
+        assert len(a) == 2 and all(np.array_equal(x[2], y[2]) and np.array_equal(x[1], y[1]) for x, y in zip(a, b))
+        assert not np.array_equal(a[0][2], R.class_batches(shape, seed=1)[0][2])
+        assert not np.array_equal(a[0][1], a[1][1])                                # the default plane and the rotated one
+
+
+@pytest.mark.parametrize("shape,params", [(s, p) for s in R.RENDER_CLASS_SHAPES for p in R.class_params(s)])
+def test_render_restatement_is_close_to_the_definition_at_the_class_shapes(shape, params):
+    """What test_gpu_render.py's class sweep leans on: a non-zero restatement error for every output, and that each case
+    exercises what it is for (a sparsely inked row; a second pass of step 5 where the shape and the margin leave room for one)"""
+    T, H, ss = shape
+    refs = R.class_refs(shape, params)
+    worst = dict.fromkeys(("image", "window", "img_l2", "height_l2"), 0.0)
+    for name, plane, path, height, target, r64, r32 in refs:
+        e = R.render_errors(r32, r64)
+        assert e["image"] < 2e-5 and e["window"] < 1e-5 and e["img_l2"] < 1e-5 and e["height_l2"] < 1e-5, (name, e)
+        assert r32["image"].shape == (path.shape[0], H * H) and (r64["image"].sum(1) > 0).all()
+        worst = {k: max(worst[k], e[k]) for k in worst}
+    assert all(v > 0.0 for v in worst.values()), worst
+    share, items = R.class_coverage(shape, refs)
+    assert share < 0.5 if H > 1 else share == 1.0
+    if H * H * ss > R.THREADS and params[1] < 1.0:
+        assert items > R.THREADS
+    assert R.class_refs(shape, params) is refs                                     # computed once
+
+
 # ------------------------------------------------------------------------------------------------ errors
 def test_marshalling_errors_on_cpu():
     dev = torch.device("cpu")

@@ -176,6 +176,89 @@ def test_restated_update_follows_the_definition_on_every_family():
     assert worst < 1.2e-7                                            # one float32 rounding of an O(1) value
 
 
+# ------------------------------------------------------------------------------------------------ the class shapes
+def _rel(got, ref):
+    return float((np.abs(np.asarray(got, np.float64) - ref) / (np.abs(ref) + 1.0)).max())
+
+
+@pytest.mark.parametrize("shape", S.SAMPLE_CLASS_SHAPES)
+def test_sample_restated_follows_the_definition_at_the_class_shapes(shape):
+    """test_gpu_search.py's inputs: a non-zero restatement error without and with the map, a zero variance gives the mean"""
+    P, R, n = shape
+    rng = np.random.default_rng(0)
+    mean, var = rng.standard_normal((P, n)).astype(np.float32), (0.05 + rng.random((P, n))).astype(np.float32)
+    proj = None
+    if n in S.SAMPLE_CLASS_GROUPS:
+        G, g = S.SAMPLE_CLASS_GROUPS[n]
+        assert G * g == n and g <= 64
+        proj = ((rng.standard_normal((G, g, g)) / np.sqrt(g)).astype(np.float32), rng.standard_normal((P, n)).astype(np.float32))
+    for pr in (None,) + ((proj,) if proj is not None else ()):
+        r64, r32 = S.sample(mean, var, 5, 3, R, 0, pr), S.sample_restated(mean, var, 5, 3, R, 0, pr)
+        assert r32.dtype == np.float32 and r32.shape == (P, R, n) and 0.0 < _rel(r32, r64) < 2e-6
+        assert np.array_equal(S.sample_restated(mean[-1:], var[-1:], 5, 3, R, P - 1, None if pr is None else (pr[0], pr[1][-1:])), r32[-1:])
+        z64, z32 = S.sample(mean, 0 * var, 5, 3, R, 0, pr), S.sample_restated(mean, 0 * var, 5, 3, R, 0, pr)
+        if pr is None:
+            assert np.array_equal(z32, np.broadcast_to(mean[:, None, :], (P, R, n))) and np.array_equal(z64, z32.astype(np.float64))
+        else:
+            assert 0.0 < _rel(z32, z64) < 2e-6 and np.array_equal(z32, np.broadcast_to(z32[:, :1], z32.shape))
+    tile = 1024 // (4 * ((n + 3) // 4))                          # rows of a tile: the classes the shapes stand for
+    assert tile == {3: 256, 2: 256, 1024: 1, 1021: 1, 513: 1, 340: 3, 128: 8, 5: 128, 64: 16}[n]
+
+
+@pytest.mark.parametrize("shape", S.UPDATE_CLASS_SHAPES)
+def test_restated_update_follows_the_definition_at_the_class_shapes(shape):
+    """The whole grid and ``class_options`` as test_gpu_search.py runs them: n_applied and frozen agree, every quantity under the
+    4x rule has a non-zero restatement error (min_cost is exact by construction), the special options do what they are for"""
+    P, R, n = shape
+    rng = np.random.default_rng(2)
+    worst = dict(mean=0.0, var=0.0, avg_cost=0.0, min_cost=0.0, moved=0.0)
+    cases = [(f, o, None) for f, o in S.option_grid()] + S.class_options()
+    assert len(cases) == 42 + 8
+    for i, (family, opt, rel) in enumerate(cases):
+        x, c, st = S.update_case(P, R, n, family, rng)
+        if rel is not None:
+            opt = S.with_abs_lower(x, c, st, opt, rel)
+        d, hd = S.update(x, c, st, opt)
+        r, hr = S.update_restated(x, c, st, opt)
+        assert np.array_equal(d["n_applied"], r["n_applied"]) and np.array_equal(d["frozen"], r["frozen"]), (family, opt)
+        assert np.array_equal(d["best_cost"], r["best_cost"].astype(np.float64)) and np.array_equal(d["best_x"], r["best_x"])
+        ok = d["n_applied"] > 0
+        for k in ("avg_cost", "min_cost", "moved"):
+            assert np.array_equal(np.isnan(hd[k]), ~ok) and np.array_equal(np.isnan(hr[k]), ~ok)
+            if ok.any():
+                worst[k] = max(worst[k], _rel(hr[k][ok], hd[k][ok]))
+        worst["mean"] = max(worst["mean"], _rel(r["mean"], d["mean"]))
+        top = d["var"].max(1)
+        worst["var"] = max(worst["var"], float((np.abs(r["var"] - d["var"]).max(1) / np.where(top > 0, top, 1.0)).max()))
+        if i < 42:
+            continue
+        free, _ = S.update(x, c, st, dict(opt, rel_lower=-1.0, abs_lower=-1.0))
+        vmax = free["var"].max(1)
+        j = i - 42
+        if j == 0:                                               # eliteness 2000: some weights underflow to exactly 0, not all
+            cp = c[0].astype(np.float64)
+            w = np.exp(-2000.0 * (cp - cp.min()) / (cp.max() - cp.min() + 1e-6))
+            assert 0 < (w == 0.0).sum() < R
+        elif j == 1:                                             # eliteness 0: the plain mean
+            assert np.abs(d["mean"] - x.astype(np.float64).mean(1)).max() < 1e-12
+        elif j == 2:                                             # one rollout kept: its x, no spread, the floor everywhere
+            assert np.array_equal(d["mean"], x[np.arange(P), c.argmin(1)].astype(np.float64)) and (d["var"] == 0.3).all()
+        elif j == 3:                                             # mu >= R: every counting rollout weighs, the cap alone
+            assert d["var"].max() <= 0.2 and (free["var"] == d["var"]).all() and np.isnan(c).sum() == P
+        elif j == 4:                                             # lr = 0: the old variances, floored
+            assert np.array_equal(d["var"], np.maximum(st["var"], 0.5 * st["var"].max(1, keepdims=True)))
+        elif j == 5:
+            assert not d["var"].any()
+        else:                                                    # problem 0: rel_lower * vmax on either side of abs_lower
+            rel_floor = opt["rel_lower"] * vmax[0]
+            assert (opt["abs_lower"] > rel_floor) == (j == 6) and abs(opt["abs_lower"] / rel_floor - 1.0) < 2e-3
+            assert np.array_equal(d["var"][0], np.maximum(free["var"][0], max(opt["abs_lower"], rel_floor)))
+    assert all(v > 0.0 for k, v in worst.items() if k != "min_cost") and worst["min_cost"] == 0.0, worst
+    assert max(worst.values()) < 2e-7
+    a, b = (S.update_case(P, R, n, "spread", np.random.default_rng(2)) for _ in range(2))     # seeded
+    assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and np.array_equal(a[2]["best_cost"], b[2]["best_cost"])
+
+
 # ------------------------------------------------------------------------------------------------ affine sets
 def _basis(rng=None):
     rng = np.random.default_rng(0) if rng is None else rng
