@@ -874,6 +874,47 @@ int avae_stroke_render(avae_handle* h, const float* path_dev, int32_t rows, int3
                        const float* target_dev, const float* height_dev,
                        float* image_dev, float* window_dev, float* img_l2_dev, float* height_l2_dev, void* stream);
 
+/* ---- pose, Jacobian and inverse kinematics: from a pen path back to joint angles.  The reference builds every
+ * joint-modality row it trains on by solving one PyKDL inverse_kinematics per time point of a stroke, each seeded with the previous
+ * point's solution (derive_ik_trajectory, baxter_writer.py:84-96), and returns from its Cartesian refinement to joint space the same
+ * way (baxter_vae_assoc_writer.py:254).  These two calls are the project's own definition of what KDL's ChainIkSolverPos_NR over
+ * ChainIkSolverVel_pinv does (baxter_pykdl_revised.py:165-204) -- damped least squares in place of a truncated-SVD pseudo-inverse --
+ * not a bit copy of it.  Dense device fp32 everywhere but iterations_dev / status_dev (int32).  The chain is avae_motion_fk's
+ * (frames_dev [D + 1][3][4], axes_dev [D][3]), walked from base to tip:  R_j, o_j the rotation and origin after F_j,  z_j = R_j axis_j.
+ * avae_motion_pose: position[r][t] = the tip p, rotation[r][t] = the tip's rotation R (row-major 3 x 3), jacobian[r][t] the geometric
+ *   Jacobian [6][D]:  J[0:3][j] = z_j x (p - o_j),  J[3:6][j] = z_j.  Each output may be NULL, not all three.  The position is the
+ *   value of avae_motion_fk, not its bits: the chain is walked in the other direction.
+ * avae_motion_ik: row r follows the T points path[r][:] from the angles seed[r][:].  Point 0 starts from the seed, point t from the
+ *   angles point t - 1 ended with, whatever its status.  At a point, for k = 0, 1, ...:
+ *     e_p = target - p;  with orient_dev (one goal R_g for every row, orient_rows = 1, or one per row, orient_rows = rows):
+ *     e_w = 1/2 sum_i R[:, i] x R_g[:, i]  (sin(angle) times the axis: meant for goals within 90 degrees),  e = [e_p; e_w], m = 6;
+ *     without a goal e = e_p, m = 3.   residual = |e_p|, rot_residual = |e_w| (NaN without a goal).
+ *     status 0 (converged) when residual < tol and, with a goal, rot_residual < rot_tol -- strict, so tol = 0 never stops;
+ *     status 1 (iteration cap) when k == n_iters;  else  M = J J^T + damping^2 I  over the m rows used,  M = L L^T (Cholesky; a
+ *     pivot that is not > 0 ends the point with status 2),  dq = J^T M^-1 e,  scaled by max_step / max_j |dq_j| where that is below
+ *     1,  q <- q + dq, clamped to limits_dev [D][2] when given.
+ *   traj[r][t] = the last q, residual / rot_residual those at that q (a pose evaluation: n_iters steps take n_iters + 1 of them),
+ *   iterations the steps taken.  A non-finite target point gets NaN angles and residuals, 0 iterations and status 3 and leaves the
+ *   carried angles alone (the next point behaves as if it had been deleted from the path); a non-finite seed does that to every
+ *   point of its row.  Neither touches another row.  fp32 bottoms out near 2e-7 m on an arm of 1 m: a tol below about 1e-6 cannot
+ *   be met.  csrc/avae_ik.h writes every operation and its order down.
+ * rows == 0 is a no-op.  Errors (message in avae_last_error, nothing launched): rows < 0, D outside [1, 16], T outside [1, 1024],
+ * n_iters outside [0, 1000], damping or max_step not > 0, tol or rot_tol negative or not finite, orient_rows neither 1 nor rows
+ * (with orient_dev), a NULL required pointer (traj_dev of avae_motion_ik is required, its other outputs are optional), every
+ * output of avae_motion_pose NULL.
+ * One launch each, no atomics, no scratch, nothing of the handle is read or written: a row's outputs are a pure function of its
+ * bits and the arguments -- the same alone or among other rows, on any stream, on repetition and whichever optional outputs are
+ * asked for -- and the calls work on any replica and inside avae_use_averaged. */
+int avae_motion_pose(avae_handle* h, const float* traj_dev, int32_t rows, int32_t T, int32_t D,
+                     const float* frames_dev, const float* axes_dev,
+                     float* position_dev, float* rotation_dev, float* jacobian_dev, void* stream);
+int avae_motion_ik(avae_handle* h, const float* path_dev, int32_t rows, int32_t T, int32_t D,
+                   const float* frames_dev, const float* axes_dev, const float* seed_dev,
+                   const float* orient_dev, int32_t orient_rows, const float* limits_dev,
+                   int32_t n_iters, float tol, float rot_tol, float damping, float max_step,
+                   float* traj_dev, float* residual_dev, float* rot_residual_dev, int32_t* iterations_dev, int32_t* status_dev,
+                   void* stream);
+
 /* ---- black-box search around a cost: batched PI-BB / CEM iterations on the device.  The reference refines a
  * predicted motion by drawing rollouts from a Gaussian, pricing each and refitting the Gaussian to the cost-weighted rollouts
  * (pygcem.py:28-151, driven from baxter_vae_assoc_writer.py:259-342).  Here P such searches ("problems") advance at once: problem p

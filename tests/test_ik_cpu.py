@@ -1,0 +1,230 @@
+"""Inverse kinematics without a GPU: the host side of the chain (``KinematicChain.pose`` / ``.jacobian``,
+``StrokeCanvas.lift``), the float64 definition of tests/ik_reference.py on the fixture arm, and the validators of the Python
+surface, which run on ``device="cpu"``."""
+import numpy as np
+import pytest
+import torch
+
+import ik_cases as IC
+import ik_reference as K
+import render_reference as R
+from vae_assoc_amd import _marshal as M
+from vae_assoc_amd.kinematics import KinematicChain, StrokeCanvas
+from vae_assoc_amd.motion import MotionBasis
+
+
+def _chains():
+    return [IC.fixture_chain(), KinematicChain(R.random_joints(16, 0)), KinematicChain(R.fixture_joints(1))]
+
+
+def _angles(chain, n, seed):
+    return np.random.default_rng(seed).uniform(-2.0, 2.0, (n, chain.n_dof))
+
+
+# ------------------------------------------------------------------------------------------------ pose, Jacobian, lift
+@pytest.mark.parametrize("k", range(3))
+def test_pose_is_forward_with_an_orthonormal_rotation(k):
+    chain = _chains()[k]
+    q = _angles(chain, 20, k).reshape(4, 5, chain.n_dof)
+    p, rot = chain.pose(q)
+    assert p.shape == (4, 5, 3) and rot.shape == (4, 5, 3, 3)
+    assert np.abs(p - chain.forward(q)).max() < 1e-12
+    assert np.abs(rot @ np.swapaxes(rot, -1, -2) - np.eye(3)).max() < 1e-12
+    assert np.abs(np.linalg.det(rot) - 1.0).max() < 1e-12
+    with pytest.raises(ValueError):
+        chain.pose(np.zeros(chain.n_dof + 1))
+
+
+@pytest.mark.parametrize("k", range(3))
+def test_jacobian_agrees_with_central_differences(k):
+    """h = 1e-6: the truncation error is about 1e-12 and the rounding error about 1e-10 of entries of order 1, so 1e-7 of the largest
+    entry has room.  The rotational rows through R(q + h) R(q - h)^T = I + 2 h [w]x."""
+    chain = _chains()[k]
+    q = _angles(chain, 6, 10 + k)
+    J = chain.jacobian(q)
+    assert J.shape == (6, 6, chain.n_dof)
+    h, num = 1e-6, np.empty_like(J)
+    for j in range(chain.n_dof):
+        d = np.zeros(chain.n_dof)
+        d[j] = h
+        (p1, r1), (p0, r0) = chain.pose(q + d), chain.pose(q - d)
+        num[:, :3, j] = (p1 - p0) / (2.0 * h)
+        dr = r1 @ np.swapaxes(r0, -1, -2)
+        num[:, 3:, j] = np.stack([dr[:, 2, 1] - dr[:, 1, 2], dr[:, 0, 2] - dr[:, 2, 0], dr[:, 1, 0] - dr[:, 0, 1]], -1) / (4.0 * h)
+    err = np.abs(J - num).max()
+    print("jacobian %d joints: |J - central differences| = %.3e, largest entry %.3f" % (chain.n_dof, err, np.abs(J).max()))
+    assert err <= 1e-7 * np.abs(J).max()
+    # the definition the GPU tests compare with is the same Jacobian on the same constants
+    f, a = chain.packed(np.float64)
+    assert np.abs(K.pose(q, f, a)["jacobian"] - J).max() < 1e-12
+
+
+def test_lift_inverts_the_projection_and_reproduces_the_reference_placement():
+    rng = np.random.default_rng(3)
+    strokes = rng.uniform(-1.5, 1.5, (4, 9, 2))
+    center = np.array([0.844, -0.357, 0.257])
+    for plane in (None, R.rotated_plane()):
+        canvas = StrokeCanvas(plane=plane)
+        path = canvas.lift(strokes, center, height=0.01)
+        back = (path - center) @ canvas.plane.T
+        assert path.shape == (4, 9, 3) and np.abs(back[..., :2] - strokes).max() < 1e-12 and np.abs(back[..., 2] - 0.01).max() < 1e-12
+    # generate_spatial_trajectory after the flip (-y, -x): a hand-written stroke in image-style coordinates (x right, y down)
+    char = np.array([[0.0, 0.0], [1.0, 0.0], [1.0, -1.5], [-0.5, 0.75]])
+    want = np.array([[0.844, -0.357, 0.257], [0.844, -0.387, 0.257], [0.889, -0.387, 0.257], [0.8215, -0.342, 0.257]])
+    got = StrokeCanvas().lift(np.stack([char[:, 0], -char[:, 1]], 1), center)
+    assert np.abs(got - want).max() < 1e-12
+    for bad in (np.zeros((3, 3)), np.zeros(2)[:1]):
+        with pytest.raises(ValueError):
+            StrokeCanvas().lift(bad, center)
+    with pytest.raises(ValueError):
+        StrokeCanvas().lift(char, center[:2])
+    with pytest.raises(ValueError):
+        StrokeCanvas().lift(char, center, height=float("nan"))
+    with pytest.raises(ValueError):
+        StrokeCanvas(plane=np.ones((3, 3))).lift(char, center)
+
+
+# ------------------------------------------------------------------------------------------------ the definition
+def _letters64(**kw):
+    c = IC.letter_case()
+    f, a = c["chain"].packed(np.float64)
+    return c, K.ik(c["path"], f, a, c["seed"].astype(np.float64), limits=c["chain"].limits, **kw)
+
+
+@pytest.mark.parametrize("goal", [False, True])
+@pytest.mark.parametrize("damping,cap", [(0.01, 8), (0.05, 8)])
+def test_definition_follows_the_letters(goal, damping, cap):
+    """Every point of the six letters converges to 1e-6 within 8 steps (3 are needed at damping 0.01, 5 at 0.05: the cap has room and
+    a broken solver still fails it), the pen tip recomputed with ``forward`` is where it was asked to be, and the arm does not jump."""
+    c, out = _letters64(orient=IC.letter_case()["orient"].astype(np.float64) if goal else None, n_iters=cap, tol=1e-6, damping=damping)
+    print("letters goal=%s damping=%g: iterations <= %d, residual <= %.2e, largest jump %.4f rad"
+          % (goal, damping, out["iterations"].max(), out["residual"].max(), np.abs(np.diff(out["trajectory"], axis=1)).max()))
+    assert (out["status"] == 0).all() and out["iterations"].max() <= cap
+    tip = np.linalg.norm(c["chain"].forward(out["trajectory"]) - c["path"].astype(np.float64), axis=-1)
+    assert tip.max() < 1e-6 and np.abs(tip - out["residual"]).max() < 1e-12
+    assert np.abs(np.diff(out["trajectory"], axis=1)).max() < 0.1
+    lim = c["chain"].limits
+    assert (out["trajectory"] > lim[:, 0]).all() and (out["trajectory"] < lim[:, 1]).all()          # no point ends on a limit
+    if goal:
+        assert out["rot_residual"].max() < 1e-4
+    else:
+        assert out["rot_residual"] is None
+
+
+def test_restatement_follows_the_letters_to_the_fp32_floor():
+    c = IC.letter_case()
+    out = K.ik(c["path"], c["frames"], c["axes"], c["seed"], c["orient"], c["limits"], n_iters=8, tol=2e-6, dt=np.float32)
+    assert out["trajectory"].dtype == np.float32 and (out["status"] == 0).all()
+    ref = K.ik(c["path"], c["frames"], c["axes"], c["seed"], c["orient"], c["limits"], n_iters=4, tol=0.0)
+    got = K.ik(c["path"], c["frames"], c["axes"], c["seed"], c["orient"], c["limits"], n_iters=4, tol=0.0, dt=np.float32)
+    assert (ref["status"] == 1).all() and (ref["iterations"] == 4).all() and (got["iterations"] == 4).all()      # tol = 0 never stops
+    assert np.abs(got["trajectory"] - ref["trajectory"]).max() < 1e-5
+
+
+def test_a_nan_point_is_a_deleted_point():
+    c = IC.letter_case()
+    f, a = c["chain"].packed(np.float64)
+    path = c["path"][:2, :20].astype(np.float64)
+    holed = path.copy()
+    holed[1, 7] = [np.nan, 0.8, 0.2]
+    kw = dict(limits=c["chain"].limits, n_iters=8, tol=1e-6)
+    out = K.ik(holed, f, a, c["seed"][:2].astype(np.float64), **kw)
+    cut = K.ik(np.delete(path[1:], 7, axis=1), f, a, c["seed"][1:2].astype(np.float64), **kw)
+    whole = K.ik(path[:1], f, a, c["seed"][:1].astype(np.float64), **kw)
+    assert np.isnan(out["trajectory"][1, 7]).all() and np.isnan(out["residual"][1, 7]) and out["status"][1, 7] == 3
+    assert out["iterations"][1, 7] == 0
+    for key in ("trajectory", "residual", "iterations", "status"):
+        assert np.array_equal(np.delete(out[key][1:], 7, axis=1), cut[key]), key
+        assert np.array_equal(out[key][:1], whole[key]), key                    # the other row is untouched
+    seed = c["seed"][:2].astype(np.float64)
+    seed[0, 3] = np.inf
+    out = K.ik(path, f, a, seed, **kw)
+    assert np.isnan(out["trajectory"][0]).all() and (out["status"][0] == 3).all() and (out["status"][1] == 0).all()
+
+
+def test_an_out_of_reach_target_gives_finite_angles_and_the_cap():
+    c = IC.letter_case()
+    path = c["path"][:1, :3].astype(np.float64) + np.array([2.0, 0.0, 0.0])
+    for dt in (np.float64, np.float32):
+        out = K.ik(path, c["frames"], c["axes"], c["seed"][:1], limits=c["limits"], n_iters=20, dt=dt)
+        assert np.isfinite(out["trajectory"]).all() and np.isfinite(out["residual"]).all()
+        assert (out["status"] == 1).all() and (out["iterations"] == 20).all() and out["residual"].min() > 0.5
+
+
+def test_a_one_joint_chain_follows_its_circle():
+    """J J^T of one joint has rank 1: the damping alone makes the Cholesky factor exist"""
+    chain = KinematicChain(R.fixture_joints(1))
+    f, a = chain.packed(np.float64)
+    q = np.linspace(-0.8, 0.9, 30)[None, :, None]
+    out = K.ik(chain.forward(q), f, a, q[:, 0] + 0.05, n_iters=20, tol=1e-6, damping=0.01)
+    assert (out["status"] == 0).all() and np.abs(out["trajectory"] - q).max() < 1e-4
+    assert np.abs(np.linalg.norm(chain.forward(out["trajectory"]) - chain.forward(q), axis=-1)).max() < 1e-6
+
+
+# ------------------------------------------------------------------------------------------------ the validators
+def test_motion_pose_and_ik_validators_refuse_with_value_errors():
+    chain = IC.fixture_chain()
+    path, seed = np.zeros((3, 5, 3), np.float32), np.zeros((3, 7), np.float32)
+    t, frames, axes, want, was_np = M.motion_pose_args(np.zeros((2, 4, 7)), chain, True, "cpu")
+    assert t.shape == (2, 4, 7) and frames.shape == (8, 3, 4) and axes.shape == (7, 3) and want and was_np
+    for bad in (lambda: M.motion_pose_args(np.zeros((2, 4, 6)), chain, False, "cpu"),
+                lambda: M.motion_pose_args(np.zeros((2, 4, 7)), "chain", False, "cpu"),
+                lambda: M.motion_pose_args(np.zeros((2, 4, 7)), chain, 1, "cpu"),
+                lambda: M.motion_pose_args(np.zeros((2, 1025, 7)), chain, False, "cpu")):
+        with pytest.raises(ValueError):
+            bad()
+
+    def ik(path=path, chain=chain, seed=seed, orientation=None, n_iters=20, tol=1e-5, rot_tol=1e-4, damping=0.01, max_step=0.5,
+           limits=True):
+        return M.motion_ik_args(path, chain, seed, orientation, n_iters, tol, rot_tol, damping, max_step, limits, "cpu")
+    p, frames, axes, s, orient, lim, opts, was_np = ik()
+    assert p.shape == (3, 5, 3) and s.shape == (3, 7) and orient is None and lim.shape == (7, 2) and was_np
+    assert opts == (20, float(np.float32(1e-5)), float(np.float32(1e-4)), float(np.float32(0.01)), 0.5)
+    assert ik(seed=seed[0])[3].shape == (3, 7) and ik(limits=None)[5] is None
+    assert ik(orientation="seed")[4].shape == (3, 3, 3) and ik(seed=seed[0], orientation="seed")[4].shape == (1, 3, 3)
+    assert ik(seed=torch.zeros(3, 7), orientation="seed")[4] == "seed"                  # a device seed: its pose is taken on the device
+    assert ik(orientation=np.eye(3))[4].shape == (1, 3, 3) and ik(orientation=np.tile(np.eye(3), (3, 1, 1)))[4].shape == (3, 3, 3)
+    assert torch.equal(ik(orientation="seed")[4][0], torch.as_tensor(chain.pose(np.zeros(7))[1].astype(np.float32)))
+    for kw in (dict(path=np.zeros((3, 5, 2))), dict(path=np.zeros((3, 1025, 3))), dict(path=np.zeros((5, 3))), dict(chain=None),
+               dict(seed=None), dict(seed=np.zeros(6)), dict(seed=np.zeros((2, 7))), dict(orientation="tip"),
+               dict(orientation=np.eye(4)), dict(orientation=np.zeros((2, 3, 3))), dict(n_iters=-1), dict(n_iters=1001),
+               dict(n_iters=2.0), dict(n_iters=True), dict(tol=-1e-6), dict(tol=float("nan")), dict(tol="small"),
+               dict(rot_tol=-1.0), dict(rot_tol=float("inf")), dict(damping=0.0), dict(damping=-0.1), dict(damping=1e-60),
+               dict(damping=float("nan")), dict(max_step=0.0), dict(max_step=float("inf")), dict(limits=np.zeros((6, 2))),
+               dict(limits=np.array([[1.0, -1.0]] * 7)), dict(limits=np.full((7, 2), np.nan))):
+        with pytest.raises(ValueError):
+            ik(**kw)
+    free = KinematicChain([dict(type="revolute", axis=(0, 0, 1), xyz=(0.1, 0, 0))])
+    assert ik(path=path, chain=free, seed=np.zeros(1))[5] is None                        # limits=True: the chain has none
+
+
+def test_composed_call_validators_refuse_with_value_errors():
+    chain, canvas = IC.fixture_chain(), StrokeCanvas()
+    basis = MotionBasis(n_basis=20, n_dof=7, n_points=10)
+    strokes, center, seed = np.zeros((2, 10, 2)), [0.844, -0.357, 0.257], np.zeros(7)
+
+    def s2m(strokes=strokes, basis=basis, chain=chain, canvas=canvas, center=center, seed=seed, height=0.0, **options):
+        return M.strokes_to_motion_args(strokes, basis, chain, canvas, center, seed, height, options, "cpu")
+    (p, frames, axes, s, orient, lim, opts), was_np = s2m(orientation="seed", damping=0.05)
+    assert p.shape == (2, 10, 3) and p.dtype == torch.float32 and orient.shape == (1, 3, 3) and was_np
+    assert opts[3] == float(np.float32(0.05)) and opts[0] == 20
+    assert torch.equal(p, torch.as_tensor(canvas.lift(strokes, center).astype(np.float32)))
+    for kw in (dict(strokes=np.zeros((2, 10, 3))), dict(strokes=np.zeros((10, 2))), dict(basis=None), dict(chain=None),
+               dict(canvas=None), dict(basis=MotionBasis(n_dof=6, n_points=10)), dict(basis=MotionBasis(n_dof=7, n_points=11)),
+               dict(center=[0.0, 1.0]), dict(seed=np.zeros(6)), dict(height=float("inf")), dict(damping=0.0), dict(stiffness=1.0),
+               dict(orientation="tip")):
+        with pytest.raises(ValueError):
+            s2m(**kw)
+
+    widths = [784, 147]
+
+    def rpp(basis=MotionBasis(n_basis=20, n_dof=7), chain=chain, canvas=canvas, n_rollouts=50, image_modality=0, modality=1, **options):
+        return M.refine_pen_path_args(basis, chain, canvas, n_rollouts, options, widths, image_modality, modality)
+    ik, search = rpp(tol=1e-4, tol_search=1e-3, eliteness=5, seed=3)
+    assert ik["tol"] == 1e-4 and ik["n_iters"] == 20 and search == dict(tol=1e-3, eliteness=5, seed=3)
+    for kw in (dict(basis=None), dict(chain=None), dict(canvas=None), dict(basis=MotionBasis(n_basis=20, n_dof=6)),
+               dict(basis=MotionBasis(n_basis=10, n_dof=7)), dict(canvas=StrokeCanvas(size=20)), dict(n_rollouts=0),
+               dict(n_rollouts=2.5), dict(image_modality=2), dict(modality=-1), dict(space="cartesian"), dict(damping=-1.0),
+               dict(canvas=StrokeCanvas(plane=np.ones((3, 3))))):
+        with pytest.raises(ValueError):
+            rpp(**kw)

@@ -52,6 +52,7 @@ SYMBOLS = [
     "avae_embed_calibrate", "avae_embed_iterate", "avae_embed_plan",
     "avae_motion_eval", "avae_motion_fit", "avae_motion_moments",
     "avae_motion_fk", "avae_stroke_render",
+    "avae_motion_pose", "avae_motion_ik",
     "avae_search_sample", "avae_search_update",
     "avae_synchronize", "avae_timing_enable", "avae_timing_report", "avae_debug_fetch", "avae_comm_allreduce",
 ]
@@ -191,7 +192,10 @@ def lib():
             L.avae_motion_moments.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
             L.avae_motion_fk.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp]
             L.avae_stroke_render.argtypes = [vp, vp, i32, i32, vp, C.c_float, C.c_float, i32, i32, vp, vp, vp, vp, vp, vp, vp]
-            L.avae_search_sample.argtypes = [vp, vp, vp, i32, i32, i32, C.c_uint64, i32, C.c_int64, vp, vp, i32, i32, vp, vp]
+            L.avae_motion_pose.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]
+            L.avae_motion_ik.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, i32, vp, i32, C.c_float, C.c_float, C.c_float,
+                                         C.c_float, vp, vp, vp, vp, vp, vp]
+            L.avae_search_sample.argtypes =[vp, vp, vp, i32, i32, i32, C.c_uint64, i32, C.c_int64, vp, vp, i32, i32, vp, vp]
             L.avae_search_update.argtypes = [vp, vp, vp, i32, i32, i32, C.POINTER(SearchOptions), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
             L.avae_save.argtypes = [vp, C.c_char_p]
             L.avae_load.argtypes = [vp, C.c_char_p]

@@ -6,6 +6,7 @@
 #include "avae_latent_stats.h"
 #include "avae_motion.h"
 #include "avae_render.h"
+#include "avae_ik.h"
 #include "avae_search.h"
 #include "avae_gmm.h"
 #include "avae_embed.h"
@@ -4851,6 +4852,59 @@ int avae_stroke_render(avae_handle* h, const float* path_dev, int32_t rows, int3
         a.half_width = half_width; a.margin = margin; a.T = T; a.H = H; a.ss = ss;
         hipStream_t s = on_stream(h, stream);
         timed_launch(h, s, "stroke_render", [&] { launch_stroke_render(a, rows, s); });
+    });
+}
+
+// ---- pose, Jacobian and inverse kinematics (include/avae.h, avae_ik.h)
+int avae_motion_pose(avae_handle* h, const float* traj_dev, int32_t rows, int32_t T, int32_t D,
+                     const float* frames_dev, const float* axes_dev,
+                     float* position_dev, float* rotation_dev, float* jacobian_dev, void* stream) {
+    return guarded(h, [&] {
+        const std::string w = "avae_motion_pose";
+        check_rows(w, rows, "rows");
+        check_range(w, "T", T, 1, kIkMaxT);
+        check_range(w, "D", D, 1, kIkMaxD);
+        need(w, traj_dev, "traj_dev"); need(w, frames_dev, "frames_dev"); need(w, axes_dev, "axes_dev");
+        if (!position_dev && !rotation_dev && !jacobian_dev) throw Err(w + ": every output is NULL");
+        if (rows == 0) return;
+        PoseArgs a = zeroed<PoseArgs>();
+        a.traj = traj_dev; a.frames = frames_dev; a.axes = axes_dev;
+        a.position = position_dev; a.rotation = rotation_dev; a.jacobian = jacobian_dev;
+        a.points = (long long)rows * T; a.D = D;
+        hipStream_t s = on_stream(h, stream);
+        timed_launch(h, s, "motion_pose", [&] { launch_motion_pose(a, s); });
+    });
+}
+
+int avae_motion_ik(avae_handle* h, const float* path_dev, int32_t rows, int32_t T, int32_t D,
+                   const float* frames_dev, const float* axes_dev, const float* seed_dev,
+                   const float* orient_dev, int32_t orient_rows, const float* limits_dev,
+                   int32_t n_iters, float tol, float rot_tol, float damping, float max_step,
+                   float* traj_dev, float* residual_dev, float* rot_residual_dev, int32_t* iterations_dev, int32_t* status_dev,
+                   void* stream) {
+    return guarded(h, [&] {
+        const std::string w = "avae_motion_ik";
+        check_rows(w, rows, "rows");
+        check_range(w, "T", T, 1, kIkMaxT);
+        check_range(w, "D", D, 1, kIkMaxD);
+        check_range(w, "n_iters", n_iters, 0, kIkMaxIters);
+        if (!(damping > 0.0f) || !std::isfinite(damping)) throw Err(w + ": damping must be finite and > 0");
+        if (!(max_step > 0.0f) || !std::isfinite(max_step)) throw Err(w + ": max_step must be finite and > 0");
+        if (!(tol >= 0.0f) || !std::isfinite(tol)) throw Err(w + ": tol must be finite and >= 0");
+        if (!(rot_tol >= 0.0f) || !std::isfinite(rot_tol)) throw Err(w + ": rot_tol must be finite and >= 0");
+        if (orient_dev && orient_rows != 1 && orient_rows != rows)
+            throw Err(w + ": orient_rows = " + std::to_string(orient_rows) + " must be 1 or rows = " + std::to_string(rows));
+        need(w, path_dev, "path_dev"); need(w, frames_dev, "frames_dev"); need(w, axes_dev, "axes_dev");
+        need(w, seed_dev, "seed_dev"); need(w, traj_dev, "traj_dev");
+        if (rows == 0) return;
+        IkArgs a = zeroed<IkArgs>();
+        a.path = path_dev; a.frames = frames_dev; a.axes = axes_dev; a.seed = seed_dev; a.orient = orient_dev; a.limits = limits_dev;
+        a.traj = traj_dev; a.residual = residual_dev; a.rot_residual = rot_residual_dev; a.iterations = iterations_dev;
+        a.status = status_dev;
+        a.tol = tol; a.rot_tol = rot_tol; a.damping = damping; a.max_step = max_step;
+        a.rows = rows; a.T = T; a.D = D; a.n_iters = n_iters; a.orient_per_row = orient_dev && orient_rows == rows && rows > 1 ? 1 : 0;
+        hipStream_t s = on_stream(h, stream);
+        timed_launch(h, s, "motion_ik", [&] { launch_motion_ik(a, s); });
     });
 }
 

@@ -153,6 +153,48 @@ class KinematicChain(object):
             out[i] = m[:3, 3]
         return out.reshape(q.shape[:-1] + (3,))
 
+    def _walk(self, q):
+        """The packed chain walked from base to tip at ``q [n, n_dof]`` (float64) -> (tip position ``[n, 3]``, tip rotation
+        ``[n, 3, 3]``, joint origins ``o [n, n_dof, 3]``, joint axes in the base frame ``z [n, n_dof, 3]``): ``o_j`` and
+        ``z_j = R_j axis_j`` are taken after frame j, ahead of joint j's own rotation."""
+        frames, axes = self.packed(np.float64)
+        n = q.shape[0]
+        R = np.broadcast_to(np.eye(3), (n, 3, 3)).copy()
+        p = np.zeros((n, 3))
+        o, z = np.empty((n, self.n_dof, 3)), np.empty((n, self.n_dof, 3))
+        for j in range(self.n_dof):
+            p = p + R @ frames[j, :, 3]
+            R = R @ frames[j, :, :3]
+            o[:, j], z[:, j] = p, R @ axes[j]
+            a = axes[j]
+            K = np.array([[0.0, -a[2], a[1]], [a[2], 0.0, -a[0]], [-a[1], a[0], 0.0]])
+            c, s = np.cos(q[:, j])[:, None, None], np.sin(q[:, j])[:, None, None]
+            R = R @ (c * np.eye(3) + s * K + (1.0 - c) * np.outer(a, a))
+        p = p + R @ frames[self.n_dof, :, 3]
+        R = R @ frames[self.n_dof, :, :3]
+        return p, R, o, z
+
+    def _angles(self, q):
+        q = np.asarray(q, dtype=np.float64)
+        if q.shape[-1:] != (self.n_dof,):
+            raise ValueError("q must be [..., %d], got %s" % (self.n_dof, q.shape))
+        return q, q.reshape(-1, self.n_dof)
+
+    def pose(self, q):
+        """Joint angles ``[..., n_dof]`` -> (pen tip ``[..., 3]``, its rotation ``[..., 3, 3]``), float64: ``T(q)[:3, 3]`` and
+        ``T(q)[:3, :3]``.  The tip is ``forward(q)`` up to rounding (the packed frames are products formed ahead)."""
+        q, flat = self._angles(q)
+        p, R, _, _ = self._walk(flat)
+        return p.reshape(q.shape[:-1] + (3,)), R.reshape(q.shape[:-1] + (3, 3))
+
+    def jacobian(self, q):
+        """Joint angles ``[..., n_dof]`` -> the geometric Jacobian ``[..., 6, n_dof]``, float64: column j holds
+        ``z_j x (tip - o_j)`` over ``z_j``, the tip's linear and angular velocity per unit speed of joint j, in the base frame."""
+        q, flat = self._angles(q)
+        p, _, o, z = self._walk(flat)
+        J = np.concatenate([np.cross(z, p[:, None, :] - o), z], axis=-1)          # [n, D, 6]
+        return np.swapaxes(J, -1, -2).reshape(q.shape[:-1] + (6, self.n_dof))
+
 
 class StrokeCanvas(object):
     """How a pen path becomes a picture.  ``plane [3, 3]`` holds the rows u (image x, to the right), v (image y, upwards) and n (the
@@ -192,3 +234,21 @@ class StrokeCanvas(object):
     @property
     def n_pixels(self):
         return self.size * self.size
+
+    def lift(self, strokes, center, height=0.0):
+        """Strokes in plane units ``[..., 2]`` (u to the right, v upwards) -> the pen path ``[..., 3]`` that draws them around
+        ``center`` at ``height`` above the paper: ``center + P^-1 (u, v, height)`` with ``P = plane``, the inverse of the
+        projection ``render_strokes`` applies.  With the default plane and the reference's image-style stroke coordinates,
+        ``(u, v) = (char_x, -char_y)`` gives ``generate_spatial_trajectory`` after the flip of baxter_writer.py:156.  NumPy
+        float64."""
+        s = np.asarray(strokes, dtype=np.float64)
+        if s.shape[-1:] != (2,):
+            raise ValueError("strokes must be [..., 2], got %s" % (s.shape,))
+        c = _vec3(center, "center")
+        if isinstance(height, (bool, np.bool_)) or not isinstance(height, (int, float, np.integer, np.floating)) or not np.isfinite(height):
+            raise ValueError("height must be a finite number, got %r" % (height,))
+        try:
+            inv = np.linalg.inv(self.plane)
+        except np.linalg.LinAlgError:
+            raise ValueError("plane is singular: its rows u, v, n do not span the space")
+        return c + s @ inv[:, :2].T + float(height) * inv[:, 2]

@@ -30,6 +30,7 @@ from . import _capi
 from ._marshal import (corruption_fields, ema_fields, ema_kwargs, grad_clip_fields, grad_clip_kwargs, dev_array, dev_block3, dev_dense, dev_dense3, dev_flags, dev_inputs, dev_modalities, dev_row_args,
                        ld_of, ptr, schedule_kwargs, schedule_struct)
 from ._marshal import cyclical, exponential_decay, linear_warmup  # noqa: F401  (schedule helpers, part of this module's surface)
+from ._marshal import motion_ik_args, motion_pose_args, refine_pen_path_args, strokes_to_motion_args
 from .parallel import GradSync, dp_bucket_schedule, dp_train_step_bucketed
 
 _ARCH_KEYS = ("scope", "hidden_conv", "n_hidden_recog_1", "n_hidden_recog_2",
@@ -1876,12 +1877,16 @@ class AssocVariationalAutoEncoder(object):
         least-squares fit of the basis at ``linspace(0, 1, T)`` with the reference's truncated pseudo-inverse, per joint, then
         ``(theta - param_mean) / param_std`` (baxter_writer.py:77-82, 193).  T is the input's own."""
         t, pinv, sc, sh, was_np = motion_fit_args(trajectories, basis, self.device)
+        return self._like_input(was_np)(self._motion_fit(t, pinv, sc, sh, basis))
+
+    def _motion_fit(self, t, pinv, sc, sh, basis):
+        """avae_motion_fit on device tensors: trajectories [N, T, D] -> standardised parameters [N, P]"""
         N, T = t.shape[0], t.shape[1]
         out = self._new(N, basis.n_params)
         if N:
             _capi.check(self._h, self._L.avae_motion_fit(self._h, t.data_ptr(), N, basis.n_dof, basis.n_kb, T, pinv.data_ptr(),
                                                          ptr(sc), ptr(sh), out.data_ptr(), self._stream()), "avae_motion_fit")
-        return self._like_input(was_np)(out)
+        return out
 
     def _motion_moments(self, s, N, S, mats, basis, mean, var, frac):
         """avae_motion_moments on N rows of S dense samples at ``s`` into (slices of) the outputs"""
@@ -2241,6 +2246,175 @@ class AssocVariationalAutoEncoder(object):
             return {"img_l2": conv(out["img_l2"]), "latent_l2": conv(lat), "image": conv(out["image"])}
         _, _, mean = self._fused_decode(xp, lds, p, rows, modality, True)
         return {"predicted": drawn(mean), "own": None if own_p is None else drawn(own_p)}
+
+    # ------------------------------------------------------------------ inverse kinematics
+    def _motion_pose(self, t, frames, axes, position=True, rotation=True, jacobian=False):
+        """avae_motion_pose on device tensors: trajectories [N, T, D] -> (position [N, T, 3], rotation [N, T, 3, 3], jacobian
+        [N, T, 6, D]), None for an output that is not asked for"""
+        N, T, D = t.shape
+
+        def new(want, *tail):
+            return torch.empty((N, T) + tail, dtype=torch.float32, device=self.device) if want else None
+        pos, rot, jac = new(position, 3), new(rotation, 3, 3), new(jacobian, 6, D)
+        if N:
+            _capi.check(self._h, self._L.avae_motion_pose(self._h, t.data_ptr(), N, T, D, frames.data_ptr(), axes.data_ptr(),
+                                                          ptr(pos), ptr(rot), ptr(jac), self._stream()), "avae_motion_pose")
+        return pos, rot, jac
+
+    def motion_pose(self, trajectories, chain, jacobian=False):
+        """Joint trajectories ``[N, T, chain.n_dof]`` -> the pen tip's pose at every point (avae_motion_pose in include/avae.h):
+        a dict of ``position [N, T, 3]``, ``rotation [N, T, 3, 3]`` and, with ``jacobian=True``, the geometric Jacobian
+        ``jacobian [N, T, 6, n_dof]`` (linear over angular rows, base frame; None otherwise) -- ``KinematicChain.pose`` and
+        ``.jacobian`` for every row and time point in one launch.  ``position`` is ``motion_fk``'s value, not its bits."""
+        t, frames, axes, want, was_np = motion_pose_args(trajectories, chain, jacobian, self.device)
+        pos, rot, jac = self._motion_pose(t, frames, axes, jacobian=want)
+        conv = self._like_input(was_np)
+        return {"position": conv(pos), "rotation": conv(rot), "jacobian": None if jac is None else conv(jac)}
+
+    def _motion_ik(self, p, frames, axes, seed, orient, lim, opts):
+        """avae_motion_ik on device tensors, in chunks of ``_motion_chunk`` rows (rows are independent: the chunk changes no
+        bit) -> dict of device tensors.  ``orient`` None, [1, 3, 3], [N, 3, 3] or 'seed': the orientation of the seed's pose."""
+        N, T, D = p.shape[0], p.shape[1], seed.shape[1]
+        if isinstance(orient, str):
+            orient = self._motion_pose(seed.reshape(N, 1, D), frames, axes, position=False)[1].reshape(N, 3, 3)
+        n_iters, tol, rot_tol, damping, max_step = opts
+        traj = torch.empty((N, T, D), dtype=torch.float32, device=self.device)
+        res = self._new(N, T)
+        rres = None if orient is None else self._new(N, T)
+        its, st = (torch.empty((N, T), dtype=torch.int32, device=self.device) for _ in range(2))
+        chunk = max(1, int(self._motion_chunk))
+        for r0 in range(0, N, chunk):
+            n = min(chunk, N - r0)
+            o = None if orient is None else (orient if orient.shape[0] == 1 else orient[r0:r0 + n])
+            _capi.check(self._h, self._L.avae_motion_ik(
+                self._h, p[r0:r0 + n].data_ptr(), n, T, D, frames.data_ptr(), axes.data_ptr(), seed[r0:r0 + n].data_ptr(),
+                ptr(o), 0 if o is None else int(o.shape[0]), ptr(lim), n_iters, tol, rot_tol, damping, max_step,
+                traj[r0:r0 + n].data_ptr(), res[r0:r0 + n].data_ptr(), None if rres is None else rres[r0:r0 + n].data_ptr(),
+                its[r0:r0 + n].data_ptr(), st[r0:r0 + n].data_ptr(), self._stream()), "avae_motion_ik")
+        return {"trajectory": traj, "residual": res, "rot_residual": rres, "iterations": its, "status": st, "converged": st == 0}
+
+    def motion_ik(self, path, chain, seed, orientation=None, n_iters=20, tol=1e-5, rot_tol=1e-4, damping=0.01, max_step=0.5,
+                  limits=True):
+        """Pen paths ``[N, T, 3]`` -> the joint trajectories that follow them (avae_motion_ik in include/avae.h): the reference's
+        ``derive_ik_trajectory`` (baxter_writer.py:84-96) for N paths at once, every point solved by damped least squares from
+        the angles the previous point ended with -- the project's own definition of what PyKDL's Newton-Raphson solver does
+        there, not a bit copy of it.
+
+        ``seed`` (``[n_dof]`` or ``[N, n_dof]``) are the angles point 0 starts from.  ``orientation`` is None (position only), a
+        ``[3, 3]`` rotation for every row, ``[N, 3, 3]``, or ``'seed'``: the orientation of ``chain.pose(seed)``, the reference's
+        ``seed_pose[3:7]`` (a goal should lie within 90 degrees of the pose it is approached from).  A point is done when its
+        position error is below ``tol`` (metres; fp32 cannot meet a ``tol`` under about 1e-6) and its orientation error
+        (sin of the angle) below ``rot_tol``, or after ``n_iters`` steps; ``damping`` is the least-squares damping, ``max_step``
+        the largest change of one angle in one step (radians).  ``limits``: True (the chain's own, if every joint has them), None
+        or ``[n_dof, 2]``.
+
+        Returns a dict: ``trajectory [N, T, n_dof]``, ``residual`` / ``rot_residual [N, T]`` (the errors at the returned angles;
+        ``rot_residual`` None without a goal), ``iterations`` and ``status [N, T]`` (int32; 0 converged, 1 iteration cap, 2 a
+        failed Cholesky pivot, 3 a non-finite target or seed: NaN angles, and the next point starts as if that point were not
+        there) and ``converged = status == 0``.  NumPy in gives NumPy out, device tensors in give device tensors out."""
+        p, frames, axes, s, orient, lim, opts, was_np = motion_ik_args(path, chain, seed, orientation, n_iters, tol, rot_tol,
+                                                                       damping, max_step, limits, self.device)
+        conv = self._like_input(was_np)
+        return {k: None if v is None else conv(v) for k, v in self._motion_ik(p, frames, axes, s, orient, lim, opts).items()}
+
+    def strokes_to_motion(self, strokes, basis, chain, canvas, center, seed, height=0.0, **ik_options):
+        """The reference's data pipeline (``build_ik_joint_traj_for_chars`` and ``build_fa_for_joint_trajs``,
+        baxter_writer.py:147-196) for N strokes at once: ``strokes [N, T, 2]`` in the canvas' plane units are lifted around
+        ``center`` at ``height`` above the paper (``canvas.lift``), followed by the arm (``motion_ik`` from ``seed`` with
+        ``ik_options``), fitted (``motion_fit`` with ``basis``, whose ``n_points`` must be T) and drawn (``render_strokes``).
+
+        Returns a dict: ``path [N, T, 3]``, ``trajectory [N, T, n_dof]``, ``params [N, n_params]`` (a joint-modality row),
+        ``image [N, n_pixels]`` (the image-modality row), ``converged [N]`` (every point of the row), ``fit_rmse [N, n_dof]``
+        (``motion_eval`` of the fitted parameters against the trajectory) and ``tip_error [N]`` (the worst distance of the pen
+        tip of the fitted motion from the path: what approximator and solver lose together).  Every piece is bitwise what the
+        separate calls give."""
+        (p, frames, axes, s, orient, lim, opts), was_np = strokes_to_motion_args(strokes, basis, chain, canvas, center, seed, height,
+                                                                                 ik_options, self.device)
+        ik = self._motion_ik(p, frames, axes, s, orient, lim, opts)
+        t, pinv, sc, sh, _ = motion_fit_args(ik["trajectory"], basis, self.device)
+        params = self._motion_fit(t, pinv, sc, sh, basis)
+        ev, _, rmse, _ = self._motion_eval(params, motion_matrices(basis, self.device), basis, ref=t)
+        tip = torch.linalg.vector_norm(self._motion_fk(ev, frames, axes) - p, dim=2).amax(1)
+        plane = canvas_args(canvas, int(p.shape[0]), None, None, self.device)[0]
+        image = self._render(p, plane, canvas, None, None)["image"]
+        conv = self._like_input(was_np)
+        return {"path": conv(p), "trajectory": conv(t), "params": conv(params), "image": conv(image),
+                "converged": conv(ik["converged"].all(1)), "fit_rmse": conv(rmse), "tip_error": conv(tip)}
+
+    def refine_pen_path(self, target_image, basis, chain, canvas, init=None, n_rollouts=50, n_iters=20, var0=1e-5,
+                        anchor_start=True, seed_angles=None, image_modality=0, modality=1, ik_n_iters=20, **options):
+        """The reference's Cartesian refinement (``derive_robot_motion_from_img_posterior_rl_cartesian``,
+        baxter_vae_assoc_writer.py:182-257) for P pictures at once: a ``search`` over the pen path's own approximator parameters
+        and the way back to joint space.
+
+        The start is the motion decoded from the encoding of ``target_image [P, n_pixels]`` (or ``init``: ``[P, n_params]``
+        standardised parameters), evaluated and run through ``motion_fk``.  The two in-plane coordinates of that path are fitted
+        with a two-joint basis of ``basis.n_basis`` features (``motion_fit``); with ``anchor_start`` every candidate is projected
+        onto starting where that path starts.  The candidates (``2 (n_basis + 1)`` numbers, ``var0`` their first variance) are
+        evaluated, put back at the initial path's own height point by point, drawn and priced by ``img_l2`` against the picture
+        -- the image term of the reference's ``cost_robot_cart_motion_img`` alone.  The refined mean is evaluated the same way,
+        followed by ``motion_ik`` (seeded with the initial motion's first angles, or ``seed_angles [P, n_dof]``) and fitted with
+        ``basis``.  ``n_iters`` counts the search's iterations, ``ik_n_iters`` is the solver's cap.  ``options`` are
+        ``motion_ik``'s (orientation, tol, rot_tol, damping, max_step, limits) and ``search``'s (eliteness, weighting, cov_update,
+        learning_rate, covar_bounds, seed, and ``tol_search`` for its ``tol``: ``tol`` is the solver's).  Between the first draw
+        and the last fit there is no host round trip.
+
+        Returns ``search``'s dict and ``path [P, T, 3]`` (the refined pen path), ``trajectory [P, T, n_dof]``, ``params
+        [P, n_params]`` (bitwise ``motion_fit(motion_ik(path, ...)["trajectory"], basis)``), ``converged [P]``, ``initial`` and
+        ``final`` (dicts of ``img_l2 [P]`` of the initial path and of ``path``) and ``image``, the drawing of ``path``."""
+        from .motion import MotionBasis
+        ik, search_options = refine_pen_path_args(basis, chain, canvas, n_rollouts, dict(options, n_iters=ik_n_iters), self._widths,
+                                                  image_modality, modality)
+        if target_image is None:
+            raise ValueError("target_image is None: the refinement needs the pictures to write")
+        tg, was_np = dev_array(target_image, canvas.n_pixels, self.device)
+        tg = tg.contiguous()
+        P, T = int(tg.shape[0]), basis.n_points
+        if init is None:
+            z0 = self._encode(image_modality, tg)
+            p0 = self._new(P, basis.n_params)
+            if P:
+                _capi.check(self._h, self._L.avae_decode(self._h, modality, z0.data_ptr(), P, p0.data_ptr(), self._stream()),
+                            "avae_decode")
+        else:
+            p0 = dev_dense(init, basis.n_params, self.device, P, "as target_image", name="init")
+        mats = motion_matrices(basis, self.device)
+        frames, axes = chain_matrices(chain, self.device)
+        plane = canvas_args(canvas, P, None, None, self.device)[0]
+        back = torch.as_tensor(np.ascontiguousarray(np.linalg.inv(canvas.plane).T, dtype=np.float32)).to(self.device)
+        traj0 = self._motion_eval(p0, mats, basis)[0]
+        path0 = self._motion_fk(traj0, frames, axes)
+        uvn = path0 @ plane.T                                                       # [P, T, 3]: in-plane u, v and the height n
+        flat = MotionBasis(kind=basis.kind, n_basis=basis.n_basis, n_dof=2, n_points=T, normalize=basis.normalize)
+        fmats = motion_matrices(flat, self.device)
+        uv0, n0 = uvn[:, :, :2].contiguous(), uvn[:, :, 2:].contiguous()
+        x0 = self._motion_fit(*motion_fit_args(uv0, flat, self.device)[:4], flat)
+        project = None
+        if anchor_start and P:
+            A, b = flat.projection([0.0], uv0[:, 0, :].reshape(P, 2, 1).cpu().numpy())
+            project = (torch.as_tensor(A.astype(np.float32)).to(self.device), torch.as_tensor(b.astype(np.float32)).to(self.device))
+        seed = traj0[:, 0, :] if seed_angles is None else seed_angles
+
+        def pen_path(x, height):
+            return (torch.cat([self._motion_eval(x, fmats, flat)[0], height], dim=2) @ back).contiguous()
+
+        def price(cand, pidx):
+            return self._render(pen_path(cand, n0.index_select(0, pidx)), plane, canvas, tg.index_select(0, pidx), None)["img_l2"]
+        first = self._render(path0, plane, canvas, tg, None)
+        res = self.search(price, x0, var0, n_rollouts=n_rollouts, n_iters=n_iters, project=project, **search_options)
+        path = pen_path(res["mean"], n0)
+        p, frames, axes, s, orient, lim, opts, _ = motion_ik_args(path, chain, seed, ik["orientation"], ik["n_iters"], ik["tol"],
+                                                                  ik["rot_tol"], ik["damping"], ik["max_step"], ik["limits"],
+                                                                  self.device)
+        sol = self._motion_ik(p, frames, axes, s, orient, lim, opts)
+        params = self._motion_fit(*motion_fit_args(sol["trajectory"], basis, self.device)[:4], basis)
+        last = self._render(path, plane, canvas, tg, None)
+        conv = self._like_input(was_np)
+        out = {k: (v if k == "state" else conv(v)) for k, v in res.items()}
+        out.update(path=conv(path), trajectory=conv(sol["trajectory"]), params=conv(params),
+                   converged=conv(sol["converged"].all(1)), image=conv(last["image"]),
+                   initial={"img_l2": conv(first["img_l2"])}, final={"img_l2": conv(last["img_l2"])})
+        return out
 
     def save_model(self, fname=None):
         """reference vae_assoc.py:427-435 (default name: timestamp + batch size)."""
