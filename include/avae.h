@@ -892,7 +892,11 @@ int avae_stroke_render(avae_handle* h, const float* path_dev, int32_t rows, int3
  *     status 0 (converged) when residual < tol and, with a goal, rot_residual < rot_tol -- strict, so tol = 0 never stops;
  *     status 1 (iteration cap) when k == n_iters;  else  M = J J^T + damping^2 I  over the m rows used,  M = L L^T (Cholesky; a
  *     pivot that is not > 0 ends the point with status 2),  dq = J^T M^-1 e,  scaled by max_step / max_j |dq_j| where that is below
- *     1,  q <- q + dq, clamped to limits_dev [D][2] when given.
+ *     1,  q <- q + dq, clamped to limits_dev [D][2] when given.  A step is committed only when every new angle q_j + dq_j
+ *     (after the scaling, before the clamp) is finite; otherwise none is stored and the point ends with status 2 as well.
+ *   Status 2 is "the solve failed: a pivot not > 0 or a non-finite step" (a damping whose square underflows, a finite target so
+ *   far away that M^-1 e overflows, about 1e36): the point keeps the last good q, the residuals at it and the steps taken so far,
+ *   and the next point starts from that q.  With a finite seed no angle the call returns under status 0, 1 or 2 is NaN.
  *   traj[r][t] = the last q, residual / rot_residual those at that q (a pose evaluation: n_iters steps take n_iters + 1 of them),
  *   iterations the steps taken.  A non-finite target point gets NaN angles and residuals, 0 iterations and status 3 and leaves the
  *   carried angles alone (the next point behaves as if it had been deleted from the path); a non-finite seed does that to every

@@ -6,7 +6,11 @@ chain; the targets are its pen tips (``KinematicChain.forward``, rounded to floa
 target can be reached.  Variants: position only, one goal (the orientation every row starts in), per-row goals (the orientation the
 row starts in); limits on, off, and a box that binds.  A goal that stays fixed while the arm moves on cannot be met along the whole
 path, so the goal variants are compared step for step (``tol = 0``) and the contract at the defaults is asked of the position-only
-variants, of the goal variants whose path is one point, and of ``letter_case``, the reference's own use of a goal."""
+variants, of the goal variants whose path is one point, and of ``letter_case``, the reference's own use of a goal.
+
+Below ``letter_case``: one case per branch of the solver that the smooth cases never enter -- a planar arm for status 2 (by a pivot
+that is exactly 0 and by a step that is not finite), a seed on its target, targets too far away for an uncut step, a pinned
+joint."""
 import numpy as np
 
 import ik_reference as K
@@ -31,6 +35,14 @@ VARIANTS = (("none", "chain"), ("one", "chain"), ("rows", "off"), ("none", "bind
 # 4x rule compares the kernel's draw of such an error with the restatement's, and the ratio of two draws of one dominant term
 # exceeds 4 about one time in six whichever code is right; at 0.1, y is of order 1 and the errors are sums of many terms again.
 STEP_DAMPING = dict(none=0.01, one=0.1, rows=0.1)
+
+# The `c < D` skip inside a class, run under VARIANTS with STEP_DAMPING.  D = 2: a joint skipped in the class D <= 4; D = 5 and 9:
+# the lower edges of the classes D <= 8 and D <= 16 (three and seven joints skipped); D = 12 and 15: the widest class, the one at
+# the register limit, with four joints and with one joint skipped; (2, 1024, 2): T = kIkMaxT, the longest row a lane walks.
+IK_CLASS_SHAPES = ((3, 4, 2), (3, 4, 5), (3, 4, 9), (3, 4, 12), (3, 4, 15), (2, 1024, 2))
+# avae_motion_pose at the same class edges.  In k_motion_pose<16> the LDS rows are 17 floats apart while the copy-in divides the
+# tile's flat index by D: D = 9, 15 and, over two tiles (257 points), 12 are the only shapes where the two differ.
+POSE_CLASS_SHAPES = ((2, 3, 2), (2, 3, 5), (2, 3, 9), (2, 3, 15), (1, 257, 12))
 
 _CACHE = {}
 
@@ -142,6 +154,109 @@ def letter_case(n=6, T=100):
                     orient=chain.pose(np.asarray(fx["seed_pos"]))[1].astype(F32), limits=chain.limits.astype(F32),
                     shape=("letters", n, T), goal="one", limits_mode="chain")
     return _cached(("letter_case", n, T), make)
+
+
+# ------------------------------------------------------------------------------------------------ the branches of the solver
+LINK = 0.25
+
+
+def planar_chain(D):
+    """D revolute joints about z, links of 0.25 m along x (the tip one link behind the last joint), limits +-3 rad: the arm never
+    leaves the plane z = 0, the third row of its positional Jacobian and with it the third row and column of J J^T are exactly 0"""
+    def make():
+        from vae_assoc_amd.kinematics import KinematicChain
+        joints = [dict(type="revolute", xyz=(0.0 if d == 0 else LINK, 0.0, 0.0), axis=(0.0, 0.0, 1.0), lower=-3.0, upper=3.0)
+                  for d in range(D)]
+        return KinematicChain(joints + [dict(type="fixed", xyz=(LINK, 0.0, 0.0))])
+    return _cached(("planar_chain", D), make)
+
+
+def planar_case(D, lifted=False, limits="chain", rows=3, T=4):
+    """A case like ``case``'s on ``planar_chain(D)``: the targets are the tips of a straight move between two poses with every angle
+    in [0.3, 1.2] (a curled arm: no singular pose on the way), the seed the first pose plus 0.05.
+    In the plane (z = 0 exactly): the branch "pivot not > 0" -- with a damping whose square underflows to 0 the third pivot of the
+    position-only solve is exactly 0.  ``lifted`` (z = 0.1 m, out of the arm's reach): the branch "non-finite step" -- with a
+    damping whose square is a subnormal number the third pivot is > 0, e_z / damping^2 overflows and inf * 0 in J^T y is NaN."""
+    def make():
+        chain = planar_chain(D)
+        rng = np.random.default_rng([26, D, rows, T])
+        a, b = rng.uniform(0.3, 1.2, (rows, 1, D)), rng.uniform(0.3, 1.2, (rows, 1, D))
+        tau = np.linspace(0.0, 1.0, T)[None, :, None]
+        q = a + (b - a) * tau
+        path = chain.forward(q).astype(F32)
+        path[..., 2] = 0.1 if lifted else 0.0
+        frames, axes = chain.packed()
+        lim = None if limits == "off" else chain.limits.astype(F32)
+        return dict(chain=chain, frames=frames, axes=axes, path=path, seed=(q[:, 0] + 0.05).astype(F32), orient=None, limits=lim,
+                    truth=q, shape=("planar", D, bool(lifted), rows, T), goal="none", limits_mode=limits)
+    return _cached(("planar_case", D, bool(lifted), limits, rows, T), make)
+
+
+def on_target(c, rows=None):
+    """A case whose rows ``rows`` (default: all) start where they are asked to be: their path is their point 0 at every point and
+    their seed the angles the restatement converges to there at ``tol = 1e-6`` (ten times inside the default ``tol``, so that no
+    rounding of the kernel's can push the residual across it) -- the branch "done at k = 0", status 0 after 0 steps"""
+    rows = list(range(c["path"].shape[0])) if rows is None else list(rows)
+
+    def make():
+        first = K.ik(c["path"][rows, :1], c["frames"], c["axes"], c["seed"][rows], c["orient"], c["limits"], tol=1e-6, dt=F32)
+        assert (first["status"] == 0).all() and (first["residual"] < 1e-6).all()
+        path, seed = c["path"].copy(), c["seed"].copy()
+        path[rows], seed[rows] = path[rows, :1], first["trajectory"][:, 0]
+        return dict(c, path=path, seed=seed, shape=("on_target", tuple(rows)) + tuple(c["shape"]))
+    assert c["orient"] is None
+    return _cached(("on_target", tuple(rows), c["shape"], c["goal"], c["limits_mode"]), make)
+
+
+FAR_POINTS = 5
+
+
+def far_case(limits="chain"):
+    """The branch ``s > max_step``: the rows of ``case((5, 100, 7))``, their first five points, with every target 0.6 m further
+    along x (up to 1.7 m from the base: most of them out of reach).  At ``max_step = 0.5`` four steps in five are cut, at 0.05
+    nine in ten.  Five points, not a hundred: an arm stretched towards a target it cannot reach sits next to a singular pose,
+    where float32 and float64 part ways point after point (after 100 points the restatement is 0.2 rad from the definition,
+    after five 6e-6), and a bound of 4x that would let any kernel pass."""
+    def make():
+        c = case((5, 100, 7), "none", limits)
+        path = c["path"][:, :FAR_POINTS].copy()
+        path[..., 0] += F32(0.6)
+        return dict(c, path=path, truth=c["truth"][:, :FAR_POINTS], shape=("far",) + tuple(c["shape"]))
+    return _cached(("far_case", limits), make)
+
+
+def far_refs(limits, max_step):
+    """-> (definition, restatement, the definition's steps) of ``far_case(limits)`` after four steps a point at ``tol = 0``"""
+    def make():
+        c, steps = far_case(limits), []
+        opt = dict(n_iters=4, tol=0.0, max_step=max_step)
+        r64 = K.ik(c["path"], c["frames"], c["axes"], c["seed"], None, c["limits"], steps=steps, **opt)
+        return r64, solve(c, F32, **opt), steps
+    return _cached(("far_refs", limits, max_step), make)
+
+
+def shrink_is_active(steps, max_step):
+    """what the shrink tests ask of the definition's steps: some steps are cut, some are not, and the largest |dq| of a step that
+    was cut is max_step (dq * (max_step / s) at the entry that made s: within two roundings of it)"""
+    ms = float(F32(max_step))
+    big = np.concatenate([np.abs(s["dq"]).max(axis=1) for s in steps])
+    cut = np.concatenate([s["shrunk"] for s in steps])
+    return bool(cut.any() and (~cut).any() and (np.abs(big[cut] - ms) <= 4.0 * np.finfo(big.dtype).eps * ms).all()
+                and (big[~cut] <= ms).all())
+
+
+PIN_JOINT = 6
+
+
+def pinned_case():
+    """The branch ``lo == hi``: ``case((5, 100, 7))`` with the last joint (the wrist's roll, which hardly moves the pen) pinned to
+    the middle of its range.  Six free joints still reach every target, so the restatement converges at the defaults."""
+    def make():
+        c = case((5, 100, 7), "none", "chain")
+        lim = c["limits"].copy()
+        lim[PIN_JOINT] = F32(0.5) * (lim[PIN_JOINT, 0] + lim[PIN_JOINT, 1])
+        return dict(c, limits=lim, shape=("pinned",) + tuple(c["shape"]), limits_mode="pinned")
+    return _cached("pinned_case", make)
 
 
 def rel_err(got, ref):

@@ -8,7 +8,7 @@ definition), so that the three of them start from the same bits."""
 import numpy as np
 
 F32 = np.float32
-STATUS_OK, STATUS_CAP, STATUS_PIVOT, STATUS_NONFINITE = 0, 1, 2, 3
+STATUS_OK, STATUS_CAP, STATUS_PIVOT, STATUS_NONFINITE = 0, 1, 2, 3     # 2: the solve failed (pivot not > 0 or a non-finite step)
 
 
 # ------------------------------------------------------------------------------------------------ the walk
@@ -93,9 +93,19 @@ def _norm3(e):
     return np.sqrt((e[:, 0] * e[:, 0] + e[:, 1] * e[:, 1]) + e[:, 2] * e[:, 2])
 
 
+def fmaxf(a, b):
+    """C's fmaxf, elementwise: a NaN operand is dropped where the other is a number (``np.maximum`` returns the NaN)"""
+    return np.fmax(a, b)
+
+
+def fminf(a, b):
+    """C's fminf, elementwise: a NaN operand is dropped where the other is a number (``np.minimum`` returns the NaN)"""
+    return np.fmin(a, b)
+
+
 def _step(J, e, damp2, max_step):
     """One damped least-squares step on [n] problems, every operation in the order of csrc/avae_ik.h and in the dtype of J ->
-    (dq [n, D], pivot_ok [n])"""
+    (dq [n, D] after the shrink, pivot_ok [n], shrunk [n]).  ``dq`` may hold non-finite values: ``ik`` refuses such a step."""
     n, m, D = J.shape
     M = J[:, :, None, 0] * J[:, None, :, 0]
     for c in range(1, D):
@@ -104,7 +114,7 @@ def _step(J, e, damp2, max_step):
     for i in range(m):
         L[:, i, i] = L[:, i, i] + damp2
     ok = np.ones(n, dtype=bool)
-    with np.errstate(invalid="ignore", divide="ignore"):
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore", under="ignore"):
         for j in range(m):
             s = L[:, j, j].copy()
             for k in range(j):
@@ -131,19 +141,25 @@ def _step(J, e, damp2, max_step):
         dq = J[:, 0, :] * y[:, 0, None]
         for i in range(1, m):
             dq = dq + J[:, i, :] * y[:, i, None]
-        big = np.abs(dq).max(axis=1)
+        big = np.zeros(n, dtype=J.dtype)
+        for c in range(D):                                       # the kernel's fold from 0: fmaxf drops a NaN
+            big = fmaxf(big, np.abs(dq[:, c]))
         shrink = big > max_step
         f = max_step / big
         dq = np.where(shrink[:, None], dq * f[:, None], dq)
     assert dq.dtype == J.dtype
-    return dq, ok
+    return dq, ok, shrink
 
 
+@np.errstate(over="ignore", under="ignore", invalid="ignore")    # targets of 1e30 and a damping of 1e-20 are cases, not mistakes
 def ik(path, frames, axes, seed, orient=None, limits=None, n_iters=20, tol=1e-5, rot_tol=1e-4, damping=0.01, max_step=0.5,
-       dt=np.float64):
+       dt=np.float64, steps=None):
     """avae_motion_ik in ``dt``: path [N, T, 3], seed [N, D], orient None, [3, 3] or [N, 3, 3], limits None or [D, 2] -> dict of
     trajectory [N, T, D], residual, rot_residual [N, T], iterations, status [N, T] (int32).  float64 is the definition; float32
-    restates the kernel (the options rounded to float32 first, as the C call takes them, in both)."""
+    restates the kernel (the options rounded to float32 first, as the C call takes them, in both).  Status 2 (STATUS_PIVOT) is
+    "the solve failed": a pivot that is not > 0, or a step after which an angle would not be finite (after the shrink, before the
+    clamp); such a step is not taken, the point keeps its last good q, the residuals at it and the steps taken so far.
+    ``steps``: a list that receives, per solver step, dict(t, k, rows, dq [n, D] (after the shrink), shrunk [n], taken [n])."""
     walk = walk64 if dt == np.float64 else walk32
     path, q = np.asarray(path, dtype=dt), np.array(seed, dtype=dt)
     N, T = path.shape[:2]
@@ -184,11 +200,15 @@ def ik(path, frames, axes, seed, orient=None, limits=None, n_iters=20, tol=1e-5,
             if go.any():
                 sub = idx[go]
                 J = _jacobian(p[go], o[go], z[go])
-                dq, ok = _step(J[:, :e.shape[1]], e[go], damp2, max_step)
+                dq, ok, shrunk = _step(J[:, :e.shape[1]], e[go], damp2, max_step)
+                x = q[sub] + dq
+                ok &= np.isfinite(x).all(axis=1)                 # a step is committed only when every new angle is finite
                 status[sub[~ok], t] = STATUS_PIVOT
-                x = q[sub[ok]] + dq[ok]
+                if steps is not None:
+                    steps.append(dict(t=t, k=k, rows=sub, dq=dq, shrunk=shrunk, taken=ok.copy()))
+                x = x[ok]
                 if lim is not None:
-                    x = np.minimum(np.maximum(x, lim[:, 0]), lim[:, 1])
+                    x = fminf(fmaxf(x, lim[:, 0]), lim[:, 1])
                 q[sub[ok]] = x
                 active[sub[ok]] = True
             k += 1

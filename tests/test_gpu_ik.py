@@ -4,8 +4,10 @@ refine_pen_path) on a real MI355X (include/avae.h) against
 1. the pose kernel and 2. the solver step for step (``tol = 0``: no early-stop decision can differ) against the float64 definition,
 within 4x the float32 restatement's own worst error over the same inputs (the rule of test_gpu_motion.py; |err| / (|ref| + 1) per
 quantity); 3. the contract at the default options; 4. bit reproducibility and independence; 5. non-finite and unreachable
-targets, edges and errors of the C ABI; 6. the composed calls.  The shapes and variants are tests/ik_cases.py's; the measured pairs
-are in README.md and DESIGN.md section 26."""
+targets, edges and errors of the C ABI; 6. the composed calls; 7. every joint count class from the inside (D < DC) and every branch
+of the solver: the shrink, status 2 by a zero pivot and by a step that is not finite, huge targets, zero steps, a seed on its
+target, a pinned joint and a seed outside the box.  The shapes and variants are tests/ik_cases.py's; the measured pairs are in
+README.md and DESIGN.md section 26."""
 import ctypes as C
 
 import numpy as np
@@ -406,3 +408,245 @@ def test_refine_pen_path_is_search_ik_and_fit(V):
         model.refine_motion(img, basis, chain, canvas, space="cartesian")
     with pytest.raises(ValueError):
         model.refine_pen_path(img, basis, chain, canvas, stiffness=1.0)
+
+
+# ------------------------------------------------------------------------------------------------ 7. every class and branch
+def _steps_against_the_definition(model, c, label, variant, ns=(1, 4), **more):
+    """``n_iters`` steps at ``tol = 0`` at every point: status 1, ``n_iters`` iterations, angles and residuals within 4x the
+    restatement's own distance from the definition -> the kernel's outputs of the last ``n_iters``"""
+    for n in ns:
+        opt = dict(n_iters=n, tol=0.0, damping=IC.STEP_DAMPING[variant[0]], **more)
+        r64, r32 = IC.solve(c, np.float64, **opt), IC.solve(c, np.float32, **opt)
+        got = _ik(model, c, **opt)
+        assert (got["status"] == 1).all() and (got["iterations"] == n).all() and (r64["status"] == 1).all()
+        for k in ("trajectory", "residual", "rot_residual"):
+            if r64[k] is None:
+                assert got[k] is None
+                continue
+            own, err = IC.rel_err(r32[k], r64[k]), IC.rel_err(got[k], r64[k])
+            print("ik %s %s n_iters=%d %s: kernel %.3e, restatement %.3e (bound 4x)" % (label, variant, n, k, err, own))
+            assert got[k].shape == r64[k].shape and np.isfinite(got[k]).all() and err <= 4.0 * own, (k, n)
+    return got
+
+
+@pytest.mark.parametrize("variant", IC.VARIANTS, ids=["-".join(v) for v in IC.VARIANTS])
+@pytest.mark.parametrize("shape", IC.IK_CLASS_SHAPES)
+def test_ik_steps_inside_the_joint_classes(V, shape, variant):
+    """The joints ``c >= D`` a class skips: D = 2 in the class D <= 4, D = 5 in D <= 8, D = 9, 12 and 15 in D <= 16 (the
+    instantiations at the register limit, which the other shapes enter only with all sixteen joints), and T = 1024, the longest
+    row.  A joint that is skipped where it should not be, or not skipped, moves the angles by far more than 4x a rounding error."""
+    model = _model(V)
+    c = IC.case(shape, *variant)
+    got = _steps_against_the_definition(model, c, shape, variant)
+    if variant[1] == "binding":
+        lo, hi = c["limits"][0]
+        assert (got["trajectory"][..., 0] >= lo).all() and (got["trajectory"][..., 0] <= hi).all()
+    if shape == (3, 4, 12):                                                                # purity where DC = 16 and D < 16
+        opt = dict(n_iters=4, tol=0.0, damping=IC.STEP_DAMPING[variant[0]])
+        for r in range(3):
+            alone = _ik(model, c, rows=slice(r, r + 1), **opt)
+            assert all(_same(alone[k], got[k][r:r + 1]) for k in OUTPUTS if got[k] is not None), r
+        for want in (("trajectory",), ("trajectory", "status"), ("trajectory", "residual", "iterations")):
+            part = _ik(model, c, want=want, **opt)
+            assert all(_same(part[k], got[k]) for k in want), want
+        assert _same(_ik(model, c, **opt)["trajectory"], got["trajectory"])
+
+
+@pytest.mark.parametrize("shape", IC.POSE_CLASS_SHAPES)
+def test_pose_inside_the_joint_classes(V, shape):
+    """D = 2, 5, 9, 15 and 12 over two tiles: inside a class the LDS rows of the angles are ``DC | 1`` floats apart while the
+    copy-in divides by D, and the Jacobian's columns ``c >= D`` must not be stored.  All three outputs, and each alone."""
+    model = _model(V)
+    c, r64, r32 = IC.pose_refs(shape)
+    got = _pose(model, c["traj"], c["frames"], c["axes"])
+    for k in ("position", "rotation", "jacobian"):
+        own, err = IC.rel_err(r32[k], r64[k]), IC.rel_err(got[k], r64[k])
+        print("pose %s %s: kernel %.3e, restatement %.3e (bound 4x)" % (shape, k, err, own))
+        assert got[k].shape == r64[k].shape and np.isfinite(got[k]).all() and err <= 4.0 * own, k
+    for want in (("position",), ("rotation",), ("jacobian",)):
+        part = _pose(model, c["traj"], c["frames"], c["axes"], want)
+        assert set(part) == set(want) and _same(part[want[0]], got[want[0]]), want
+    last = _pose(model, c["traj"][-1:, -1:], c["frames"], c["axes"])
+    assert all(_same(last[k], got[k][-1:, -1:]) for k in got)
+
+
+@pytest.mark.parametrize("limits", ["chain", "off"])
+@pytest.mark.parametrize("max_step", [0.5, 0.05])
+def test_ik_shrink_step_for_step(V, max_step, limits):
+    """Targets 0.6 m further away (ik_cases.far_case): four steps in five are longer than 0.5 rad in some joint, nine in ten
+    longer than 0.05, in both directions.  Four steps a point at ``tol = 0`` against the definition, and the definition's own steps
+    show that the shrink decided them."""
+    model = _model(V)
+    c = IC.far_case(limits)
+    r64, r32, steps = IC.far_refs(limits, max_step)
+    assert IC.shrink_is_active(steps, max_step), "the shrink is not active"
+    got = _ik(model, c, n_iters=4, tol=0.0, max_step=max_step)
+    assert (got["status"] == 1).all() and (got["iterations"] == 4).all() and (r64["status"] == 1).all()
+    for k in ("trajectory", "residual"):
+        own, err = IC.rel_err(r32[k], r64[k]), IC.rel_err(got[k], r64[k])
+        print("ik far max_step=%g limits=%s %s: kernel %.3e, restatement %.3e (bound 4x)" % (max_step, limits, k, err, own))
+        assert np.isfinite(got[k]).all() and err <= 4.0 * own, k
+    if limits == "chain":
+        assert (got["trajectory"] >= c["limits"][:, 0]).all() and (got["trajectory"] <= c["limits"][:, 1]).all()
+
+
+def _seed_residual_pair(c, got, r32):
+    """the reported residuals of a run that took no step, kernel and restatement, against the float64 residual of the seed"""
+    true = _residual64(c, np.broadcast_to(c["seed"][:, None, :], got["trajectory"].shape).astype(np.float64))
+    return IC.rel_err(got["residual"], true), IC.rel_err(r32["residual"], true)
+
+
+@pytest.mark.parametrize("D", [2, 3])
+def test_ik_status_2_by_a_pivot_that_is_zero(V, D):
+    """The planar arm, position only, ``damping = 1e-30``: damping^2 is 0 in float32 and the third pivot exactly 0, on any
+    hardware.  Rows 0 and 2 end every point with status 2 after 0 steps with the seed's bits and the seed's residual; row 1 starts
+    on its target and is done (status 0) before the solve is tried, in the same wave.  Statuses, iterations and angles are the
+    restatement's to the bit; float64 has no underflow here and is not the oracle."""
+    model = _model(V)
+    c = IC.on_target(IC.planar_case(D), rows=[1])
+    r32 = IC.solve(c, np.float32, damping=1e-30)
+    got = _ik(model, c, damping=1e-30)
+    assert (got["status"][[0, 2]] == 2).all() and (got["status"][1] == 0).all() and (got["iterations"] == 0).all()
+    assert all(_same(got["trajectory"][:, t], c["seed"]) for t in range(got["trajectory"].shape[1]))
+    assert all(_same(got[k], r32[k]) for k in ("trajectory", "iterations", "status"))
+    err, own = _seed_residual_pair(c, got, r32)
+    print("ik planar D=%d damping=1e-30: status 2 after 0 steps, seed residual kernel %.3e, restatement %.3e (bound 4x)" % (D, err, own))
+    assert np.isfinite(got["residual"]).all() and err <= 4.0 * own and (got["residual"][1] < 1e-5).all()
+    assert (got["residual"][[0, 2]] > 1e-3).all() and (IC.solve(c, np.float64, damping=1e-30)["status"] != 2).all()
+    # the Python call is the C call, and says so
+    py = model.motion_ik(c["path"], c["chain"], c["seed"], damping=1e-30)
+    assert all(_same(py[k], got[k]) for k in OUTPUTS if got[k] is not None)
+    assert not py["converged"][[0, 2]].any() and py["converged"][1].all()
+
+
+@pytest.mark.parametrize("limits", ["chain", "off"])
+@pytest.mark.parametrize("D", [2, 3])
+def test_ik_status_2_by_a_step_that_is_not_finite(V, D, limits):
+    """The planar arm with targets 0.1 m above its plane and ``damping = 1e-20``: damping^2 is a subnormal number, the pivot
+    passes, e_z / damping^2 overflows and inf * 0 makes every dq NaN.  fmaxf drops the NaN and the clamp would turn it into lo =
+    -3: the step must not be taken.  Status 2 after 0 steps, finite angles that are the carried q (the seed) to the bit and never
+    lo, the seed's residual; everything equal to the restatement."""
+    model = _model(V)
+    c = IC.planar_case(D, lifted=True, limits=limits)
+    r32 = IC.solve(c, np.float32, damping=1e-20)
+    got = _ik(model, c, damping=1e-20)
+    assert np.isfinite(got["trajectory"]).all() and np.isfinite(got["residual"]).all()
+    assert (got["status"] == 2).all() and (got["iterations"] == 0).all() and (r32["status"] == 2).all()
+    assert all(_same(got["trajectory"][:, t], c["seed"]) for t in range(got["trajectory"].shape[1]))
+    assert (got["trajectory"] != np.float32(-3.0)).all() and (got["trajectory"] != np.float32(3.0)).all()
+    assert all(_same(got[k], r32[k]) for k in ("trajectory", "iterations", "status"))
+    err, own = _seed_residual_pair(c, got, r32)
+    print("ik planar lifted D=%d limits=%s damping=1e-20: status 2 after 0 steps, seed residual kernel %.3e, restatement %.3e "
+          "(bound 4x)" % (D, limits, err, own))
+    assert err <= 4.0 * own and (got["residual"] >= 0.1).all()
+    py = model.motion_ik(c["path"], c["chain"], c["seed"], damping=1e-20, limits=True if limits == "chain" else None)
+    assert all(_same(py[k], got[k]) for k in OUTPUTS if got[k] is not None) and not py["converged"].any()
+    # a damping that float32 can square takes its steps on the same case: nothing finite is refused
+    assert (_ik(model, c, damping=1e-3)["iterations"] == 20).all()
+
+
+HUGE = (3, 40, 1)           # (row, point, coordinate) of case((5, 100, 7)) that is made huge
+
+
+def _with_target(base, value):
+    c = dict(base, path=base["path"].copy())
+    c["path"][HUGE] = value
+    return c
+
+
+def _rest_of_the_row_carries_on(model, c, got, clean):
+    """the points before the huge one are the clean run's, the points after it the run that starts from the angles the huge point
+    ended with, and the other rows keep their bits"""
+    r, t, _ = HUGE
+    tail = _ik(model, dict(c, path=c["path"][r:r + 1, t + 1:], seed=got["trajectory"][r:r + 1, t]))
+    keep = [i for i in range(c["path"].shape[0]) if i != r]
+    for k in OUTPUTS:
+        if clean[k] is not None:
+            assert _same(got[k][r:r + 1, t + 1:], tail[k]) and _same(got[k][r, :t], clean[k][r, :t]), k
+            assert _same(got[k][keep], clean[k][keep]), k
+
+
+def test_ik_status_2_by_a_huge_target_stays_at_its_point(V):
+    """One coordinate of one target is 1e36: M^-1 e overflows.  The steps before that are finite and are taken (each cut to
+    max_step: the restatement takes 2 here), the first one that is not ends the point: status 2, finite angles, an infinite
+    residual.  The carried angles are the last good q, so the rest of the row is, to the bit, the run that starts from the angles
+    this point returned -- and converges; it is not the run on the path without the point, which would start from the angles of
+    the point before.  The other rows keep their bits."""
+    model = _model(V)
+    base = IC.case((5, 100, 7))
+    clean = _ik(model, base)
+    c = _with_target(base, 1e36)
+    r32 = IC.solve(dict(c, shape=("huge", 1e36)), np.float32)
+    got = _ik(model, c)
+    r, t, _ = HUGE
+    print("ik target 1e36: status %d after %d steps (restatement: %d after %d)"
+          % (got["status"][r, t], got["iterations"][r, t], r32["status"][r, t], r32["iterations"][r, t]))
+    assert got["status"][r, t] == 2 and r32["status"][r, t] == 2 and 0 <= got["iterations"][r, t] < 20
+    assert np.isfinite(got["trajectory"]).all() and np.isinf(got["residual"][r, t])
+    assert (np.delete(got["status"], t, axis=1) == 0).all() and np.isfinite(np.delete(got["residual"], t, axis=1)).all()
+    _rest_of_the_row_carries_on(model, c, got, clean)
+    # a point that fails before its first step is a deleted point: the largest float32 overflows e / L[0][0] or the next division
+    c = _with_target(base, float(np.finfo(np.float32).max))
+    got = _ik(model, c)
+    assert got["status"][r, t] == 2 and got["iterations"][r, t] == 0 and np.isfinite(got["trajectory"]).all()
+    assert _same(got["trajectory"][r, t], got["trajectory"][r, t - 1])
+    _rest_of_the_row_carries_on(model, c, got, clean)
+    cut = _ik(model, dict(base, path=np.delete(base["path"][r:r + 1], t, axis=1), seed=base["seed"][r:r + 1]))
+    assert all(_same(np.delete(got[k][r:r + 1], t, axis=1), cut[k]) for k in OUTPUTS if cut[k] is not None)
+
+
+def test_ik_huge_but_finite_targets_end_at_the_cap(V):
+    """1e30 overflows nothing but the residual (e^2): twenty steps of max_step, status 1, finite angles, the residual inf; the
+    following points converge from wherever that left the arm, and the other rows keep their bits."""
+    model = _model(V)
+    base = IC.case((5, 100, 7))
+    clean = _ik(model, base)
+    c = _with_target(base, 1e30)
+    got = _ik(model, c)
+    r, t, _ = HUGE
+    assert got["status"][r, t] == 1 and got["iterations"][r, t] == 20 and np.isinf(got["residual"][r, t])
+    assert np.isfinite(got["trajectory"]).all() and (got["trajectory"] >= c["limits"][:, 0]).all()
+    assert (got["trajectory"] <= c["limits"][:, 1]).all()
+    assert (np.delete(got["status"], t, axis=1) == 0).all(), "the following points do not converge"
+    _rest_of_the_row_carries_on(model, c, got, clean)
+
+
+def test_ik_zero_steps_and_a_seed_on_the_target(V):
+    """``n_iters = 0``: status 1 after 0 steps with the seed's bits and the seed's residual at every point.  A seed on the target:
+    status 0 after 0 steps, whatever ``n_iters`` is -- done is tested before the cap."""
+    model = _model(V)
+    base = IC.case((5, 100, 7))
+    got, r32 = _ik(model, base, n_iters=0), IC.solve(base, np.float32, n_iters=0)
+    assert (got["status"] == 1).all() and (got["iterations"] == 0).all()
+    assert all(_same(got["trajectory"][:, t], base["seed"]) for t in range(100))
+    err, own = _seed_residual_pair(base, got, r32)
+    print("ik n_iters=0: seed residual kernel %.3e, restatement %.3e (bound 4x)" % (err, own))
+    assert err <= 4.0 * own
+    there = IC.on_target(base)
+    for n in (0, 20):
+        got = _ik(model, there, n_iters=n)
+        assert (got["status"] == 0).all() and (got["iterations"] == 0).all() and (got["residual"] < 1e-5).all()
+        assert all(_same(got["trajectory"][:, t], there["seed"]) for t in range(100))
+
+
+def test_ik_limits_pinned_joint_and_seed_outside_the_box(V):
+    """``lo == hi`` pins a joint: from the first step on its angle is lo to the bit, and the other six still reach every target at
+    the defaults.  A seed outside the box is returned as it is after zero steps (the clamp belongs to the step) and is inside the
+    box after one."""
+    model = _model(V)
+    c = IC.pinned_case()
+    j, pin = IC.PIN_JOINT, c["limits"][IC.PIN_JOINT, 0]
+    assert (IC.solve(c, np.float32)["status"] == 0).all(), "the pinned case is not reachable at the defaults"
+    got = _ik(model, c)
+    assert (got["status"] == 0).all() and (got["iterations"] >= 1).all() and _same(got["trajectory"][..., j], np.full((5, 100), pin))
+    got = _steps_against_the_definition(model, c, "pinned", ("none", "pinned"))
+    assert _same(got["trajectory"][..., j], np.full((5, 100), pin))
+    base = IC.case((5, 100, 7))
+    lo, hi = base["limits"][:, 0], base["limits"][:, 1]
+    out_of = dict(base, seed=base["seed"].copy(), shape=("outside",) + base["shape"])
+    out_of["seed"][:, 0], out_of["seed"][:, 3] = hi[0] + np.float32(0.3), lo[3] - np.float32(0.2)
+    got = _ik(model, out_of, n_iters=0)
+    assert (got["status"] == 1).all() and all(_same(got["trajectory"][:, t], out_of["seed"]) for t in range(100))
+    got = _steps_against_the_definition(model, out_of, "seed outside the box", ("none", "chain"), ns=(1,))
+    assert (got["trajectory"] >= lo).all() and (got["trajectory"] <= hi).all()
+    assert (got["trajectory"][:, 0, 0] == hi[0]).any() or (got["trajectory"][:, 0, 3] == lo[3]).any()

@@ -161,6 +161,139 @@ def test_a_one_joint_chain_follows_its_circle():
     assert np.abs(np.linalg.norm(chain.forward(out["trajectory"]) - chain.forward(q), axis=-1)).max() < 1e-6
 
 
+# ------------------------------------------------------------------------------------------------ what the branch tests lean on
+def _ref(c, dt, **options):
+    return K.ik(c["path"], c["frames"], c["axes"], c["seed"], c["orient"], c["limits"], dt=dt, **options)
+
+
+@pytest.mark.parametrize("D", [2, 3])
+def test_the_planar_chain_has_an_exactly_zero_z_row_and_column(D):
+    """What makes status 2 deterministic: no rounding can put anything into the third row of J_v, so M[2][:] = M[:][2] = 0 exactly
+    and the third pivot is damping^2 to the bit -- 0 when that underflows"""
+    c = IC.planar_case(D)
+    assert np.array_equal(c["frames"][:, 2], np.tile(np.float32([0, 0, 1, 0]), (D + 1, 1))) and not c["frames"][:, :2, 2].any()
+    assert np.array_equal(c["axes"], np.tile(np.float32([0, 0, 1]), (D, 1))) and not c["path"][..., 2].any()
+    for dt in (np.float32, np.float64):
+        q = np.concatenate([c["seed"], c["truth"].reshape(-1, D)])
+        J = K.pose(q, c["frames"], c["axes"], dt)["jacobian"][:, :3]
+        M = J @ np.swapaxes(J, 1, 2)
+        assert not J[:, 2].any() and not M[:, 2].any() and not M[:, :, 2].any() and (np.linalg.eigvalsh(M[:, :2, :2]) > 1e-4).all()
+    assert (IC.planar_case(D, lifted=True)["path"][..., 2] == np.float32(0.1)).all()
+
+
+def test_fmaxf_and_fminf_are_the_c_functions_on_nan():
+    nan, one = np.float32("nan"), np.float32(1.0)
+    for f in (K.fmaxf, K.fminf):
+        assert f(nan, one) == one and f(one, nan) == one and np.isnan(f(nan, nan)) and f(one, one).dtype == np.float32
+    assert K.fmaxf(np.float32(0.0), np.abs(nan)) == 0.0                                   # the fold of the largest |dq| drops a NaN
+    assert K.fminf(K.fmaxf(nan, np.float32(-3.0)), np.float32(3.0)) == -3.0              # the clamp turns a NaN into lo
+    assert np.isnan(np.maximum(nan, one)) and np.isnan(np.minimum(np.maximum(nan, np.float32(-3.0)), np.float32(3.0)))
+    a, b = np.float32([1.0, np.nan, -2.0, np.nan]), np.float32([np.nan, 3.0, -5.0, np.nan])
+    assert np.array_equal(K.fmaxf(a, b), np.float32([1.0, 3.0, -2.0, np.nan]), equal_nan=True)
+    assert np.array_equal(K.fminf(a, b), np.float32([1.0, 3.0, -5.0, np.nan]), equal_nan=True)
+
+
+@pytest.mark.parametrize("D", [2, 3])
+def test_restatement_ends_a_failed_solve_with_status_2_and_the_last_good_angles(D):
+    """Both ways into status 2 on the planar arm, in float32.  A pivot that is exactly 0 (damping^2 underflows to 0); a step that
+    is not finite (damping^2 a subnormal number: the pivot passes, e_z / damping^2 overflows, inf * 0 is NaN).  Either way no step
+    is taken: 0 iterations, the seed's bits at every point, the seed's residual, never NaN and never lo.  A row that starts on its
+    target is done before the solve is tried.  In float64 neither happens: the definition is no oracle here."""
+    flat = IC.on_target(IC.planar_case(D), rows=[1])
+    out = _ref(flat, np.float32, damping=1e-30)
+    assert (out["status"][[0, 2]] == 2).all() and (out["status"][1] == 0).all() and (out["iterations"] == 0).all()
+    assert all(np.array_equal(out["trajectory"][:, t], flat["seed"]) for t in range(flat["path"].shape[1]))
+    assert (_ref(flat, np.float64, damping=1e-30)["status"] != 2).all()
+    for limits in ("chain", "off"):
+        c = IC.planar_case(D, lifted=True, limits=limits)
+        out = _ref(c, np.float32, damping=1e-20)
+        assert (out["status"] == 2).all() and (out["iterations"] == 0).all() and np.isfinite(out["residual"]).all()
+        assert all(np.array_equal(out["trajectory"][:, t], c["seed"]) for t in range(c["path"].shape[1]))
+        assert (out["residual"] > 0.1).all() and (out["trajectory"] != np.float32(-3.0)).all()
+        assert (_ref(c, np.float64, damping=1e-20)["status"] == 1).all()
+        # with a damping that is representable the same case takes its steps: the rule refuses nothing that is finite
+        assert (_ref(c, np.float32, damping=1e-3)["iterations"] == 20).all()
+
+
+@pytest.mark.parametrize("dt,huge", [(np.float32, 1e36), (np.float64, 1e306)])
+def test_restatement_refuses_a_step_that_is_not_finite_in_both_dtypes(dt, huge):
+    """A finite target so far away that M^-1 e overflows (1e36 in float32, 1e306 in float64): the steps that are finite are taken
+    (each cut to max_step), the first one that is not ends the point with status 2, finite angles and the steps taken so far, and
+    the rest of the row is the run that starts from those angles.  The other rows keep their bits."""
+    base = IC.case((5, 12, 7))
+    path = base["path"].astype(dt)
+    path[3, 4, 1] = huge
+    kw = dict(limits=base["limits"], dt=dt)
+    out = K.ik(path, base["frames"], base["axes"], base["seed"], **kw)
+    clean = K.ik(base["path"], base["frames"], base["axes"], base["seed"], **kw)
+    assert out["status"][3, 4] == 2 and 0 < out["iterations"][3, 4] < 20 and np.isfinite(out["trajectory"]).all()
+    assert np.isinf(out["residual"][3, 4]) and (np.delete(out["status"], 4, axis=1) == 0).all()
+    tail = K.ik(path[3:4, 5:], base["frames"], base["axes"], out["trajectory"][3:4, 4], **kw)
+    for k in ("trajectory", "residual", "iterations", "status"):
+        assert np.array_equal(out[k][3:4, 5:], tail[k]) and np.array_equal(out[k][3, :4], clean[k][3, :4]), k
+        assert np.array_equal(np.delete(out[k], 3, axis=0), np.delete(clean[k], 3, axis=0)), k
+    if dt == np.float32:                                         # 1e30 stays finite: the cap, an infinite residual, and on it goes
+        path[3, 4, 1] = 1e30
+        out = K.ik(path, base["frames"], base["axes"], base["seed"], **kw)
+        assert out["status"][3, 4] == 1 and out["iterations"][3, 4] == 20 and np.isinf(out["residual"][3, 4])
+        assert np.isfinite(out["trajectory"]).all() and np.isfinite(np.delete(out["residual"], 4, axis=1)).all()
+        assert all(np.array_equal(np.delete(out[k], 3, axis=0), np.delete(clean[k], 3, axis=0)) for k in ("trajectory", "status"))
+
+
+def test_zero_steps_and_a_seed_on_the_target():
+    base = IC.case((5, 12, 7))
+    for dt in (np.float32, np.float64):
+        out = _ref(base, dt, n_iters=0)
+        assert (out["status"] == 1).all() and (out["iterations"] == 0).all()
+        assert all(np.array_equal(out["trajectory"][:, t], base["seed"].astype(dt)) for t in range(12))
+        there = IC.on_target(base)
+        for n in (0, 20):
+            out = _ref(there, dt, n_iters=n)
+            assert (out["status"] == 0).all() and (out["iterations"] == 0).all() and (out["residual"] < 2e-6).all()
+            assert all(np.array_equal(out["trajectory"][:, t], there["seed"].astype(dt)) for t in range(12))
+    # a seed outside the box comes back as it is after zero steps and inside the box after one
+    out_of = dict(base, seed=base["seed"].copy())
+    out_of["seed"][:, 0] = base["limits"][0, 1] + np.float32(0.3)
+    lo, hi = base["limits"][:, 0], base["limits"][:, 1]
+    assert np.array_equal(_ref(out_of, np.float32, n_iters=0)["trajectory"][:, 0], out_of["seed"])
+    one = _ref(out_of, np.float32, n_iters=1, tol=0.0)["trajectory"]
+    assert (one >= lo).all() and (one <= hi).all() and (one[..., 0] == hi[0]).any()
+
+
+def test_the_class_shapes_build_and_the_pinned_joint_stays_pinned():
+    for shape in IC.IK_CLASS_SHAPES:
+        for variant in IC.VARIANTS:
+            c = IC.case(shape, *variant)
+            assert c["path"].shape == shape[:2] + (3,) and c["seed"].shape == (shape[0], shape[2])
+            assert c["chain"].n_dof == shape[2] and c["frames"].shape == (shape[2] + 1, 3, 4)
+        if shape[1] <= 4:
+            c = IC.case(shape)
+            opt = dict(n_iters=4, tol=0.0)
+            own = IC.rel_err(IC.solve(c, np.float32, **opt)["trajectory"], IC.solve(c, np.float64, **opt)["trajectory"])
+            print("class shape %s: restatement %.3e from the definition after 4 steps" % (shape, own))
+            assert 0.0 < own < 1e-5
+    for shape in IC.POSE_CLASS_SHAPES:
+        c, r64, r32 = IC.pose_refs(shape)
+        assert c["traj"].shape == shape and r64["jacobian"].shape == shape[:2] + (6, shape[2]) and r32["position"].dtype == np.float32
+    c = IC.pinned_case()
+    j, pin = IC.PIN_JOINT, c["limits"][IC.PIN_JOINT, 0]
+    assert c["limits"][j, 0] == c["limits"][j, 1] and (np.abs(c["seed"][:, j] - pin) > 0.05).all()
+    out = IC.solve(c, np.float32)
+    assert (out["status"] == 0).all() and (out["iterations"] >= 1).all() and (out["trajectory"][..., j] == pin).all()
+
+
+@pytest.mark.parametrize("limits", ["chain", "off"])
+@pytest.mark.parametrize("max_step", [0.5, 0.05])
+def test_the_far_case_shrinks(max_step, limits):
+    r64, r32, steps = IC.far_refs(limits, max_step)
+    own = IC.rel_err(r32["trajectory"], r64["trajectory"])
+    print("far case max_step=%g limits=%s: restatement %.3e from the definition, %d of %d steps cut"
+          % (max_step, limits, own, sum(int(s["shrunk"].sum()) for s in steps), sum(s["shrunk"].size for s in steps)))
+    assert IC.shrink_is_active(steps, max_step) and (r64["status"] == 1).all() and (r64["iterations"] == 4).all() and own < 2e-5
+    loose = _ref(IC.far_case(limits), np.float64, n_iters=4, tol=0.0, max_step=100.0)
+    assert np.abs(loose["trajectory"] - r64["trajectory"]).max() > 0.05                  # and the shrink decides where the arm ends up
+
+
 # ------------------------------------------------------------------------------------------------ the validators
 def test_motion_pose_and_ik_validators_refuse_with_value_errors():
     chain = IC.fixture_chain()

@@ -25,11 +25,15 @@
 //         L[i][j] = (M[i][j] - L[i][0] L[j][0] - ...) / L[j][j]
 //     y[i] = (e[i] - L[i][0] y[0] - ...) / L[i][i]  (i ascending);   x[i] = (y[i] - L[m-1][i] x[m-1] - ...) / L[i][i]  (i descending,
 //         the subtrahends k descending)
-//     dq[c] = sum_i J[i][c] x[i] (i ascending);  s = max_c |dq[c]|;  s > max_step:  dq[c] = dq[c] * (max_step / s)
-//     q[c] = q[c] + dq[c];  with limits  q[c] = fminf(fmaxf(q[c], lo[c]), hi[c])
-//   sqrtf and the divisions are IEEE.  A non-finite target point: NaN angles and residuals, 0 iterations, status 3, the carried q
-//   untouched; a non-finite seed: that for every point of the row.  A lane that is done at a point sits out the wave's remaining
-//   trips with its registers unchanged.
+//     dq[c] = sum_i J[i][c] x[i] (i ascending);  s = fmaxf(.. fmaxf(fmaxf(0, |dq[0]|), |dq[1]|) ..) (C's fmaxf: a NaN operand is
+//         dropped);  s > max_step:  dq[c] = dq[c] * (max_step / s)
+//     n[c] = q[c] + dq[c];  a step is committed only when every n[c] is finite:  !(sum_c n[c] * 0 == 0) -> status 2 with q as it
+//         was;  else  q[c] = n[c],  with limits  q[c] = fminf(fmaxf(n[c], lo[c]), hi[c])
+//   sqrtf and the divisions are IEEE.  Status 2 is "the solve failed", by a pivot or by a non-finite step (damping^2 that underflows,
+//   a target so far away that M^-1 e overflows): the point ends with the last good q, its residuals and the steps taken so far, and
+//   the next point starts from that q.  A non-finite target point: NaN angles and residuals, 0 iterations, status 3, the carried q
+//   untouched; a non-finite seed: that for every point of the row.  So the carried q is finite whenever the seed is.  A lane that is
+//   done at a point sits out the wave's remaining trips with its registers unchanged.
 //   D and m (3 without a goal, 6 with one) are template arguments, so that every array is indexed at compile time: the classes
 //   D <= 4, <= 8, <= 16 (a joint c >= D is skipped by a uniform branch) times m = 3, 6.
 //   Resources (k_motion_ik<DC, m>, the compiler's resource report): VGPRs / LDS bytes / scratch bytes

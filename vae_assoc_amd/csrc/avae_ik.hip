@@ -271,11 +271,23 @@ __global__ __launch_bounds__(kIkThreads) void k_motion_ik(const IkArgs a) {
 #undef AVAE_IK_J
                 const bool shrink = big > a.max_step;
                 const float f = a.max_step / big;
+                // dq <- q + dq; the step is committed only when every new angle is finite (fmaxf above drops a NaN and the
+                // clamp below would turn one into lo: neither may decide).  x * 0 is +-0 for a finite x and NaN otherwise, so
+                // one running sum tests them all: a flag per angle costs <16, 3> its second wave per SIMD (256 + 20 AGPRs)
+                float zero = 0.0f;
 #pragma unroll
                 for (int c = 0; c < DC; ++c) {
                     if (c < D) {
                         const float v = shrink ? dq[c] * f : dq[c];
-                        float x = q[c] + v;
+                        dq[c] = q[c] + v;
+                        zero = zero + dq[c] * 0.0f;
+                    }
+                }
+                if (!(zero == 0.0f)) { status = 2; break; }
+#pragma unroll
+                for (int c = 0; c < DC; ++c) {
+                    if (c < D) {
+                        float x = dq[c];
                         if (clamp) x = fminf(fmaxf(x, lim_s[2 * c]), lim_s[2 * c + 1]);
                         q[c] = x;
                     }

@@ -2309,9 +2309,11 @@ class AssocVariationalAutoEncoder(object):
         or ``[n_dof, 2]``.
 
         Returns a dict: ``trajectory [N, T, n_dof]``, ``residual`` / ``rot_residual [N, T]`` (the errors at the returned angles;
-        ``rot_residual`` None without a goal), ``iterations`` and ``status [N, T]`` (int32; 0 converged, 1 iteration cap, 2 a
-        failed Cholesky pivot, 3 a non-finite target or seed: NaN angles, and the next point starts as if that point were not
-        there) and ``converged = status == 0``.  NumPy in gives NumPy out, device tensors in give device tensors out."""
+        ``rot_residual`` None without a goal), ``iterations`` and ``status [N, T]`` (int32; 0 converged, 1 iteration cap, 2 the
+        solve failed -- a Cholesky pivot that is not > 0 or a step with a non-finite angle, which is not taken: the point keeps
+        its last good angles and the next point starts from them -- 3 a non-finite target or seed: NaN angles, and the next
+        point starts as if that point were not there) and ``converged = status == 0``.  NumPy in gives NumPy out, device
+        tensors in give device tensors out."""
         p, frames, axes, s, orient, lim, opts, was_np = motion_ik_args(path, chain, seed, orientation, n_iters, tol, rot_tol,
                                                                        damping, max_step, limits, self.device)
         conv = self._like_input(was_np)
