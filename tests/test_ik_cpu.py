@@ -8,7 +8,7 @@ import torch
 import ik_cases as IC
 import ik_reference as K
 import render_reference as R
-from vae_assoc_amd import _marshal as M
+from vae_assoc_amd import _args as M
 from vae_assoc_amd.kinematics import KinematicChain, StrokeCanvas
 from vae_assoc_amd.motion import MotionBasis
 

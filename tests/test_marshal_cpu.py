@@ -154,6 +154,74 @@ def test_eps_forms_and_the_optional_pointer():
         Mh.dev_dense3(np.zeros((3, 5)), (3, 2, 5), CPU)
 
 
+# ----------------------------------------------------------------------------- one scalar
+def refusal(call, *args):
+    with pytest.raises(ValueError) as e:
+        call(*args)
+    return str(e.value)
+
+
+@pytest.mark.parametrize("v", [0, 7, np.int8(7), np.uint64(7), np.int64(0)])
+def test_as_int_and_as_index_take_python_and_numpy_integers(v):
+    assert Mh.as_int(v, "n", 0) == int(v) and type(Mh.as_int(v, "n", 0, 7)) is int
+    assert Mh.as_index(v, "m", 8) == int(v) and type(Mh.as_index(v, "m", 8)) is int
+    assert Mh.as_int(2 ** 64 - 1, "seed", 0, 2 ** 64 - 1) == 2 ** 64 - 1 and Mh.as_int(-3, "n", -3) == -3
+
+
+@pytest.mark.parametrize("bad", [True, np.bool_(False), 1.0, np.float32(2), "1", None, [1], -1, 9], ids=repr)
+def test_as_int_and_as_index_refuse_with_the_shared_wording(bad):
+    assert refusal(Mh.as_int, bad, "n_iters", 0, 8) == "n_iters must be an integer in [0, 8], got %r" % (bad,)
+    assert refusal(Mh.as_index, bad, "modality", 9) == "modality must be an index in [0, 9), got %r" % (bad,)
+    if not isinstance(bad, int) or isinstance(bad, bool) or bad < 0:
+        assert refusal(Mh.as_int, bad, "state: iteration", 0) == "state: iteration must be an integer >= 0, got %r" % (bad,)
+
+
+def test_as_int_formats_a_64_bit_upper_end_and_a_tuple_value():
+    assert refusal(Mh.as_int, 2 ** 64, "seed", 0, 2 ** 64 - 1) == "seed must be an integer in [0, 18446744073709551615], got 18446744073709551616"
+    assert refusal(Mh.as_int, (1, 2), "k", 1) == "k must be an integer >= 1, got (1, 2)"
+    assert refusal(Mh.as_index, 0, "source", 0) == "source must be an index in [0, 0), got 0"
+
+
+def test_need_type_names_the_class_and_the_type_it_got():
+    from vae_assoc_amd.motion import MotionBasis
+    assert Mh.need_type(MotionBasis(n_basis=3, n_dof=2, n_points=5), MotionBasis, "basis") is None
+    assert refusal(Mh.need_type, "basis", MotionBasis, "basis") == "basis must be a MotionBasis, got 'str'"
+    assert refusal(Mh.need_type, None, dict, "state") == "state must be a dict, got 'NoneType'"
+
+
+def test_to_device32_gives_a_contiguous_float32_copy():
+    t = Mh.to_device32(np.arange(6, dtype=np.float64).reshape(2, 3).T, CPU)
+    assert t.dtype == torch.float32 and t.is_contiguous() and t.tolist() == [[0.0, 3.0], [1.0, 4.0], [2.0, 5.0]]
+
+
+def test_posterior_rows_concatenates_in_list_order_and_masks_non_finite_rows():
+    from vae_assoc_amd._args import posterior_rows
+    mu, lv = np.arange(12, dtype=np.float32).reshape(3, 4), np.zeros((3, 4), np.float32)
+    m, l, fin, was_np = posterior_rows((mu, lv), 4, CPU, True)
+    assert was_np and l is not None and np.array_equal(m.numpy(), mu) and fin.tolist() == [True] * 3
+    m, l, fin, was_np = posterior_rows((torch.from_numpy(mu), None), 4, CPU, False)
+    assert not was_np and l is None and m.data_ptr() == torch.from_numpy(mu).data_ptr()              # one pair: no copy
+    mu2, lv2 = mu[:2].copy(), lv[:2].copy()
+    mu2[0, 1], lv2[1, 3] = np.nan, np.inf
+    m, l, fin, was_np = posterior_rows([(torch.from_numpy(mu), torch.from_numpy(lv)), (mu2, lv2)], 4, CPU, True)
+    assert not was_np and m.shape == l.shape == (5, 4) and m.is_contiguous() and fin.tolist() == [True, True, True, False, False]
+    assert np.array_equal(m.numpy()[:3], mu) and np.array_equal(l.numpy()[3:], lv2)
+    m, l, fin, _ = posterior_rows([(mu, lv), (mu2, lv2)], 4, CPU, False)                              # logvar not looked at
+    assert l is None and fin.tolist() == [True, True, True, False, True]
+    assert posterior_rows((mu[:0], None), 4, CPU, False)[2].shape == (0,)
+
+
+def test_posterior_rows_refusals():
+    from vae_assoc_amd._args import posterior_rows
+    mu = np.zeros((3, 4), np.float32)
+    for bad in ([], mu, [(mu, mu), mu], None, ((mu, mu, mu),)):
+        assert refusal(posterior_rows, bad, 4, CPU, True) == ("posteriors must be a (mu, logvar) pair or a non-empty list of such "
+                                                              "pairs, got %r" % type(bad).__name__)
+    assert refusal(posterior_rows, [(mu, mu), (mu, mu[:2])], 4, CPU, True) == "posteriors[1]: logvar must be [3 (as mu), 4], got (2, 4)"
+    assert refusal(posterior_rows, (np.zeros((3, 5)), None), 4, CPU, False) == "posteriors[0]: expected a [rows, 4] array, got (3, 5)"
+    assert posterior_rows([(mu, mu), (mu, mu[:2])], 4, CPU, False)[0].shape == (6, 4)
+
+
 # ----------------------------------------------------------------------------- the initial draw
 IMG = dict(scope='image', hidden_conv=False, n_hidden_recog_1=96, n_hidden_recog_2=80,
            n_hidden_gener_1=96, n_hidden_gener_2=80, n_input=784, n_z=20)

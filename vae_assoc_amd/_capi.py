@@ -26,6 +26,7 @@ GMM_MAX_COMPONENTS = 64
 EMBED_MAX_ROWS = 65536
 MOTION_MAX_DOF, MOTION_MAX_KB, MOTION_MAX_POINTS, MOTION_MAX_ANCHORS = 16, 64, 1024, 4
 RENDER_MAX_SIZE, RENDER_SUPERSAMPLES = 64, (1, 2, 4, 8)
+IK_MAX_ITERS = 1000
 
 ACT_IDS = {"identity": 0, "relu": 1, "softplus": 2, "sigmoid": 3, "tanh": 4}
 DTYPE_IDS = {"fp32": 0, "f32": 0, "float32": 0, "bf16": 1, "bfloat16": 1}

@@ -2,11 +2,39 @@
 ``c_void_p[M]`` pointers, ``c_int32[M]`` leading dimensions, uint8 presence bytes and dense eps blocks.
 
 Every entry point of ``vae_assoc.AssocVariationalAutoEncoder`` marshals through these functions.  They take the device and the
-widths as arguments and touch neither a model nor the library, so they run on CPU tensors (``device="cpu"``) in the tests."""
+widths as arguments and touch neither a model nor the library, so they run on CPU tensors (``device="cpu"``) in the tests.
+
+Next to the arrays stand the checks of one scalar that every validator words alike (``as_int``, ``as_index``, ``need_type``) and
+the fields of the training options (corruption, clipping, averaging, schedules).  The validators of the entry points themselves
+are in ``_args``.  This module imports nothing from the package but ``_capi``, and that only inside ``schedule_struct``."""
 import ctypes as C
 
 import numpy as np
 import torch
+
+
+def as_int(v, name, lo, hi=None):
+    """A whole number in [lo, hi] (``hi`` None: no upper end) -> int.  ``bool`` and ``np.bool_`` are no numbers here."""
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < lo or (hi is not None and v > hi):
+        raise ValueError("%s must be an integer %s, got %r" % (name, ">= %d" % lo if hi is None else "in [%d, %d]" % (lo, hi), v))
+    return int(v)
+
+
+def as_index(v, name, n):
+    """An index into a list of ``n`` entries -> int"""
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not 0 <= v < n:
+        raise ValueError("%s must be an index in [0, %d), got %r" % (name, n, v))
+    return int(v)
+
+
+def need_type(obj, cls, name):
+    if not isinstance(obj, cls):
+        raise ValueError("%s must be a %s, got %r" % (name, cls.__name__, type(obj).__name__))
+
+
+def to_device32(a, device):
+    """Host array -> contiguous float32 tensor on ``device``"""
+    return torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).to(device)
 
 
 def ptr(t):
@@ -367,157 +395,3 @@ def dev_block3(a, tail, device, name, rows=None):
         want = ", ".join(["rows" if rows is None else "%d" % rows] + ["any" if w is None else "%d" % w for w in tail])
         raise ValueError("%s must be [%s], got %s" % (name, want, tuple(t.shape)))
     return t.to(device=device, dtype=torch.float32).contiguous(), was_np
-
-
-# ---------------------------------------------------------------------------------------------------- inverse kinematics
-IK_MAX_ITERS = 1000
-
-
-def motion_pose_args(trajectories, chain, jacobian, device):
-    """The arguments of ``motion_pose`` -> (trajectories [N, T, n_dof], frames, axes, want_jacobian, was_numpy); ``ValueError``
-    ahead of any launch, usable with ``device="cpu"``."""
-    from .vae_assoc import motion_fk_args
-    if not isinstance(jacobian, (bool, np.bool_)):
-        raise ValueError("jacobian must be True or False, got %r" % (jacobian,))
-    t, frames, axes, was_np = motion_fk_args(trajectories, chain, device)
-    return t, frames, axes, bool(jacobian), was_np
-
-
-def ik_options(n_iters=20, tol=1e-5, rot_tol=1e-4, damping=0.01, max_step=0.5):
-    """The solver options of ``motion_ik`` checked -> (n_iters, tol, rot_tol, damping, max_step), the four numbers as the float32
-    values the kernel uses.  The ranges are avae_motion_ik's."""
-    if isinstance(n_iters, (bool, np.bool_)) or not isinstance(n_iters, (int, np.integer)) or not 0 <= n_iters <= IK_MAX_ITERS:
-        raise ValueError("n_iters must be an integer in [0, %d], got %r" % (IK_MAX_ITERS, n_iters))
-
-    def number(v, name, positive):
-        if not _is_number(v) or not np.isfinite(v) or not np.isfinite(np.float32(v)):
-            raise ValueError("%s must be a finite number, got %r" % (name, v))
-        v = float(np.float32(v))
-        if (positive and not v > 0.0) or v < 0.0:
-            raise ValueError("%s must be %s as float32, got %r" % (name, "> 0" if positive else ">= 0", v))
-        return v
-    return (int(n_iters), number(tol, "tol", False), number(rot_tol, "rot_tol", False), number(damping, "damping", True),
-            number(max_step, "max_step", True))
-
-
-def motion_ik_args(path, chain, seed, orientation, n_iters, tol, rot_tol, damping, max_step, limits, device):
-    """The arguments of ``motion_ik`` -> (path [N, T, 3], frames, axes, seed [N, n_dof], orientation, limits [n_dof, 2] or None,
-    options, was_numpy); ``ValueError`` ahead of any launch, usable with ``device="cpu"``.  ``orientation`` comes back as None, a
-    ``[1, 3, 3]`` or ``[N, 3, 3]`` tensor, or the string 'seed' where the seed is a device tensor (its pose is then taken on the
-    device); a seed given as host data is folded here, in float64."""
-    from .kinematics import MAX_POINTS
-    from .vae_assoc import chain_matrices
-    frames, axes = chain_matrices(chain, device)
-    D = chain.n_dof
-    p, was_np = dev_block3(path, (None, 3), device, "path")
-    N = int(p.shape[0])
-    if not 1 <= p.shape[1] <= MAX_POINTS:
-        raise ValueError("path must hold 1 to %d points, got %d" % (MAX_POINTS, p.shape[1]))
-    opts = ik_options(n_iters, tol, rot_tol, damping, max_step)
-    if seed is None:
-        raise ValueError("seed is None: the solver needs the angles to start from ([%d] or [%d, %d])" % (D, N, D))
-    seed_on_host = not torch.is_tensor(seed)
-    s = torch.as_tensor(np.asarray(seed, dtype=np.float64)) if seed_on_host else seed
-    if tuple(s.shape) not in ((D,), (N, D)):
-        raise ValueError("seed must be [%d] or [%d, %d], got %s" % (D, N, D, tuple(s.shape)))
-    seed64 = s.numpy() if seed_on_host else None
-    s = s.to(device=device, dtype=torch.float32)
-    s = (s.reshape(1, D).expand(N, D) if s.dim() == 1 else s).contiguous()
-    orient = None
-    if isinstance(orientation, str):
-        if orientation != "seed":
-            raise ValueError("orientation must be None, 'seed', [3, 3] or [%d, 3, 3], got %r" % (N, orientation))
-        if seed_on_host:
-            rot = chain.pose(np.where(np.isfinite(seed64), seed64, 0.0))[1]
-            orient = torch.as_tensor(np.ascontiguousarray(rot.reshape(-1, 3, 3), dtype=np.float32)).to(device)
-        else:
-            orient = "seed"
-    elif orientation is not None:
-        o = orientation if torch.is_tensor(orientation) else torch.as_tensor(np.asarray(orientation, dtype=np.float32))
-        if tuple(o.shape) not in ((3, 3), (N, 3, 3)):
-            raise ValueError("orientation must be None, 'seed', [3, 3] or [%d, 3, 3], got shape %s" % (N, tuple(o.shape)))
-        orient = o.to(device=device, dtype=torch.float32).reshape(-1, 3, 3).contiguous()
-    lim = None
-    if limits is True:
-        lim = chain.limits
-    elif limits is not None and limits is not False:
-        lim = np.asarray(limits.cpu() if torch.is_tensor(limits) else limits, dtype=np.float64)
-        if lim.shape != (D, 2) or np.isnan(lim).any() or (lim[:, 0] > lim[:, 1]).any():
-            raise ValueError("limits must be True, None or [%d, 2] (lower <= upper), got %r" % (D, limits))
-    if lim is not None:
-        key = ("device limits", str(device), lim.tobytes())
-        if key not in chain._cache:
-            chain._cache[key] = torch.as_tensor(np.ascontiguousarray(lim, dtype=np.float32)).to(device)
-        lim = chain._cache[key]
-    return p, frames, axes, s, orient, lim, opts, was_np
-
-
-IK_OPTION_NAMES = ("orientation", "n_iters", "tol", "rot_tol", "damping", "max_step", "limits")
-IK_DEFAULTS = dict(orientation=None, n_iters=20, tol=1e-5, rot_tol=1e-4, damping=0.01, max_step=0.5, limits=True)
-
-
-def split_ik_options(options, also=()):
-    """``**options`` of a composed call -> (motion_ik's own with their defaults filled in, the rest); a key that is neither an
-    inverse-kinematics option nor one of ``also`` is refused."""
-    extra = set(options) - set(IK_OPTION_NAMES) - set(also)
-    if extra:
-        raise ValueError("unknown option(s) %s (%s)" % (", ".join(sorted(map(str, extra))), ", ".join(IK_OPTION_NAMES + tuple(also))))
-    ik = dict(IK_DEFAULTS)
-    ik.update({k: v for k, v in options.items() if k in IK_OPTION_NAMES})
-    return ik, {k: v for k, v in options.items() if k not in IK_OPTION_NAMES}
-
-
-def _check_writer(basis, chain, canvas):
-    """the three objects a composed writer call takes, and that basis and chain speak of the same joints"""
-    from .kinematics import KinematicChain, StrokeCanvas
-    from .motion import MotionBasis
-    if not isinstance(basis, MotionBasis):
-        raise ValueError("basis must be a MotionBasis, got %r" % (type(basis).__name__,))
-    if not isinstance(chain, KinematicChain):
-        raise ValueError("chain must be a KinematicChain, got %r" % (type(chain).__name__,))
-    if not isinstance(canvas, StrokeCanvas):
-        raise ValueError("canvas must be a StrokeCanvas, got %r" % (type(canvas).__name__,))
-    if chain.n_dof != basis.n_dof:
-        raise ValueError("chain.n_dof = %d must be basis.n_dof = %d" % (chain.n_dof, basis.n_dof))
-
-
-def strokes_to_motion_args(strokes, basis, chain, canvas, center, seed, height, options, device):
-    """The arguments of ``strokes_to_motion`` -> (``motion_ik_args``' tuple for the lifted path [N, T, 3], was_numpy of the
-    strokes); ``ValueError`` ahead of any launch, usable with ``device="cpu"``.  The lift runs on the host in float64 and is
-    rounded once."""
-    from .kinematics import MAX_POINTS
-    _check_writer(basis, chain, canvas)
-    s = np.asarray(strokes.cpu() if torch.is_tensor(strokes) else strokes, dtype=np.float64)
-    if s.ndim != 3 or s.shape[2] != 2 or not 1 <= s.shape[1] <= MAX_POINTS:
-        raise ValueError("strokes must be [N, T, 2] with T in [1, %d], got %s" % (MAX_POINTS, s.shape))
-    ik, _ = split_ik_options(options)
-    path = np.ascontiguousarray(canvas.lift(s, center, height), dtype=np.float32)
-    if basis.n_points != s.shape[1]:
-        raise ValueError("basis.n_points = %d must be the strokes' %d points" % (basis.n_points, s.shape[1]))
-    args = motion_ik_args(path, chain, seed, ik["orientation"], ik["n_iters"], ik["tol"], ik["rot_tol"], ik["damping"],
-                          ik["max_step"], ik["limits"], device)
-    return args[:-1], not torch.is_tensor(strokes)
-
-
-SEARCH_OPTION_NAMES = ("eliteness", "weighting", "cov_update", "learning_rate", "covar_bounds", "tol_search", "seed")
-
-
-def refine_pen_path_args(basis, chain, canvas, n_rollouts, options, widths, image_modality, modality):
-    """``refine_pen_path``'s own arguments checked -> (motion_ik's options with their defaults, search's options).  The search's
-    ``tol`` is spelled ``tol_search`` here: ``tol`` is the solver's."""
-    _check_writer(basis, chain, canvas)
-    for name, m in (("image_modality", image_modality), ("modality", modality)):
-        if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or not 0 <= m < len(widths):
-            raise ValueError("%s must be an index in [0, %d), got %r" % (name, len(widths), m))
-    if canvas.n_pixels != widths[image_modality]:
-        raise ValueError("the canvas draws %d pixels, modality %d holds %d" % (canvas.n_pixels, image_modality, widths[image_modality]))
-    if basis.n_params != widths[modality]:
-        raise ValueError("basis.n_params = %d must be n_input = %d of modality %d" % (basis.n_params, widths[modality], modality))
-    if isinstance(n_rollouts, (bool, np.bool_)) or not isinstance(n_rollouts, (int, np.integer)) or n_rollouts < 1:
-        raise ValueError("n_rollouts must be an integer >= 1, got %r" % (n_rollouts,))
-    if np.linalg.matrix_rank(canvas.plane) < 3:
-        raise ValueError("plane is singular: its rows u, v, n do not span the space")
-    ik, rest = split_ik_options(options, SEARCH_OPTION_NAMES)
-    ik_options(ik["n_iters"], ik["tol"], ik["rot_tol"], ik["damping"], ik["max_step"])
-    search = {("tol" if k == "tol_search" else k): v for k, v in rest.items()}
-    return ik, search

@@ -4722,16 +4722,22 @@ int avae_latent_stats(avae_handle* h, int32_t n_mod, const float* const* mu_dev,
 }
 
 // ---- motion decoding (include/avae.h, avae_motion.h)
+static void check_range(const std::string& w, const char* name, int v, int lo, int hi) {
+    if (v < lo || v > hi)
+        throw Err(w + ": " + name + " = " + std::to_string(v) + " must be in [" + std::to_string(lo) + ", " + std::to_string(hi) + "]");
+}
+
+// "must be finite and > 0" (strict) / ">= 0" for a float or double option
+static void check_finite(const std::string& w, const char* name, double v, bool strict) {
+    if (!std::isfinite(v) || (strict ? !(v > 0.0) : v < 0.0)) throw Err(w + ": " + name + " must be finite and " + (strict ? "> 0" : ">= 0"));
+}
+
 static void check_motion_shape(const std::string& w, int32_t rows, int32_t D, int32_t Kb, int32_t T, int32_t nc) {
-    auto range = [&](const char* name, int v, int lo, int hi) {
-        if (v < lo || v > hi)
-            throw Err(w + ": " + name + " = " + std::to_string(v) + " must be in [" + std::to_string(lo) + ", " + std::to_string(hi) + "]");
-    };
     check_rows(w, rows, "rows");
-    range("D", D, 1, kMotionMaxD);
-    range("Kb", Kb, 1, kMotionMaxKb);
-    range("T", T, 1, kMotionMaxT);
-    range("nc", nc, 0, kMotionMaxNc);
+    check_range(w, "D", D, 1, kMotionMaxD);
+    check_range(w, "Kb", Kb, 1, kMotionMaxKb);
+    check_range(w, "T", T, 1, kMotionMaxT);
+    check_range(w, "nc", nc, 0, kMotionMaxNc);
 }
 
 static MotionArgs motion_args(const std::string& w, const float* params, int32_t rows, int32_t S, int32_t D, int32_t Kb, int32_t T,
@@ -4805,11 +4811,6 @@ int avae_motion_moments(avae_handle* h, const float* samples_dev, int32_t rows, 
 }
 
 // ---- pen-path kinematics and stroke rendering (include/avae.h, avae_render.h)
-static void check_range(const std::string& w, const char* name, int v, int lo, int hi) {
-    if (v < lo || v > hi)
-        throw Err(w + ": " + name + " = " + std::to_string(v) + " must be in [" + std::to_string(lo) + ", " + std::to_string(hi) + "]");
-}
-
 int avae_motion_fk(avae_handle* h, const float* traj_dev, int32_t rows, int32_t T, int32_t D,
                    const float* frames_dev, const float* axes_dev, float* path_dev, void* stream) {
     return guarded(h, [&] {
@@ -4837,8 +4838,8 @@ int avae_stroke_render(avae_handle* h, const float* path_dev, int32_t rows, int3
         check_range(w, "T", T, 1, kRenderMaxT);
         check_range(w, "H", H, 1, kRenderMaxH);
         if (ss != 1 && ss != 2 && ss != 4 && ss != 8) throw Err(w + ": ss = " + std::to_string(ss) + " must be 1, 2, 4 or 8");
-        if (!(half_width > 0.0f) || !std::isfinite(half_width)) throw Err(w + ": half_width must be finite and > 0");
-        if (!(margin >= 0.0f) || !std::isfinite(margin)) throw Err(w + ": margin must be finite and >= 0");
+        check_finite(w, "half_width", half_width, true);
+        check_finite(w, "margin", margin, false);
         need(w, path_dev, "path_dev"); need(w, plane_dev, "plane_dev");
         if (!image_dev && !window_dev && !img_l2_dev && !height_l2_dev) throw Err(w + ": every output is NULL");
         if (img_l2_dev && !target_dev) throw Err(w + ": img_l2_dev needs target_dev");
@@ -4888,10 +4889,10 @@ int avae_motion_ik(avae_handle* h, const float* path_dev, int32_t rows, int32_t 
         check_range(w, "T", T, 1, kIkMaxT);
         check_range(w, "D", D, 1, kIkMaxD);
         check_range(w, "n_iters", n_iters, 0, kIkMaxIters);
-        if (!(damping > 0.0f) || !std::isfinite(damping)) throw Err(w + ": damping must be finite and > 0");
-        if (!(max_step > 0.0f) || !std::isfinite(max_step)) throw Err(w + ": max_step must be finite and > 0");
-        if (!(tol >= 0.0f) || !std::isfinite(tol)) throw Err(w + ": tol must be finite and >= 0");
-        if (!(rot_tol >= 0.0f) || !std::isfinite(rot_tol)) throw Err(w + ": rot_tol must be finite and >= 0");
+        check_finite(w, "damping", damping, true);
+        check_finite(w, "max_step", max_step, true);
+        check_finite(w, "tol", tol, false);
+        check_finite(w, "rot_tol", rot_tol, false);
         if (orient_dev && orient_rows != 1 && orient_rows != rows)
             throw Err(w + ": orient_rows = " + std::to_string(orient_rows) + " must be 1 or rows = " + std::to_string(rows));
         need(w, path_dev, "path_dev"); need(w, frames_dev, "frames_dev"); need(w, axes_dev, "axes_dev");
@@ -4956,14 +4957,14 @@ int avae_search_update(avae_handle* h, const float* x_dev, const float* cost_dev
             throw Err(w + ": weighting = " + std::to_string(opt->weighting) + " is none of AVAE_SEARCH_PIBB, _CEM, _CMAES");
         if (opt->cov_update != AVAE_SEARCH_PIBB && opt->cov_update != AVAE_SEARCH_CEM)
             throw Err(w + ": cov_update = " + std::to_string(opt->cov_update) + " is neither AVAE_SEARCH_PIBB nor AVAE_SEARCH_CEM");
-        if (!std::isfinite(opt->eliteness) || opt->eliteness < 0.0) throw Err(w + ": eliteness must be finite and >= 0");
+        check_finite(w, "eliteness", opt->eliteness, false);
         if (opt->weighting != AVAE_SEARCH_PIBB && (opt->eliteness < 1.0 || opt->eliteness > 1e9 || opt->eliteness != std::floor(opt->eliteness)))
             throw Err(w + ": eliteness must be a whole number >= 1 for CEM / CMA-ES weighting (the number of rollouts kept)");
         if (!(opt->learning_rate >= 0.0 && opt->learning_rate <= 1.0)) throw Err(w + ": learning_rate must be in [0, 1]");
         if (!std::isfinite(opt->rel_lower) || !std::isfinite(opt->abs_lower) || !std::isfinite(opt->abs_upper))
             throw Err(w + ": rel_lower, abs_lower and abs_upper must be finite (negative: off)");
         if (opt->rel_lower > 1.0) throw Err(w + ": rel_lower must be <= 1");
-        if (!std::isfinite(opt->tol) || opt->tol < 0.0) throw Err(w + ": tol must be finite and >= 0");
+        check_finite(w, "tol", opt->tol, false);
         need(w, x_dev, "x_dev"); need(w, cost_dev, "cost_dev"); need(w, mean_dev, "mean_dev"); need(w, var_dev, "var_dev");
         need(w, n_applied_dev, "n_applied_dev"); need(w, frozen_dev, "frozen_dev");
         need(w, best_cost_dev, "best_cost_dev"); need(w, best_x_dev, "best_x_dev");

@@ -8,8 +8,8 @@ baxter_vae_assoc_writer.py:448-449) and draws it with matplotlib, crops it to th
 float64 and needs no GPU."""
 import numpy as np
 
-MAX_DOF, MAX_POINTS, MAX_SIZE = 16, 1024, 64
-SUPERSAMPLES = (1, 2, 4, 8)
+from ._capi import MOTION_MAX_DOF as MAX_DOF, MOTION_MAX_POINTS as MAX_POINTS, RENDER_MAX_SIZE as MAX_SIZE
+from ._capi import RENDER_SUPERSAMPLES as SUPERSAMPLES
 
 
 def _vec3(a, name, unit=False):

@@ -7,7 +7,7 @@ include/avae.h): the features at the phase points, the tru
 matrices of a linear equality constraint.  Everything here is NumPy float64 and needs no GPU."""
 import numpy as np
 
-MAX_KB, MAX_DOF, MAX_POINTS, MAX_ANCHORS = 64, 16, 1024, 4
+from ._capi import MOTION_MAX_ANCHORS as MAX_ANCHORS, MOTION_MAX_DOF as MAX_DOF, MOTION_MAX_KB as MAX_KB, MOTION_MAX_POINTS as MAX_POINTS
 
 
 def _whole(x, name, lo):

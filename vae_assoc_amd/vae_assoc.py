@@ -6,6 +6,10 @@ and the module function ``train`` (:498-583), same argument names, defaults and 
 Everything numerical happens in hand-written gfx950 kernels behind the C ABI of
 include/avae.h; PyTorch-ROCm tensors only hold device memory.  There is no CPU path.
 
+This module holds the constructor's host code (``build_config``, ``initial_params``, ``create_replica``), the class, whose
+methods are library calls on checked arguments, and ``train``.  The checks are one validator per entry point in ``_args``,
+over the array marshalling of ``_marshal``; their names are imported here and stay part of this module's surface.
+
 Deliberate, documented differences from the reference:
   * ``transfer_fct`` is a name ('relu', 'softplus', ...) or any callable whose ``__name__`` is
     one (``tf.nn.relu`` would qualify); the reference passes TF callables (:26,:502).
@@ -27,10 +31,15 @@ import numpy as np
 import torch
 
 from . import _capi
-from ._marshal import (corruption_fields, ema_fields, ema_kwargs, grad_clip_fields, grad_clip_kwargs, dev_array, dev_block3, dev_dense, dev_dense3, dev_flags, dev_inputs, dev_modalities, dev_row_args,
-                       ld_of, ptr, schedule_kwargs, schedule_struct)
+from ._args import (SEARCH_STATE_KEYS, _is_pair, _same_joints, agg_args, canvas_args, chain_matrices, draw_args,  # noqa: F401
+                    embed_args, impute_args, latent_prior_args, latent_score_args, latent_stats_args, motion_eval_args,
+                    motion_fit_args, motion_fk_args, motion_ik_args, motion_matrices, motion_moments_args, motion_pose_args,
+                    predict_motion_args, prior_arrays, refine_motion_args, refine_pen_path_args, render_args, search_args,
+                    strokes_to_motion_args, topk_args, writing_cost_args)      # (the validators are part of this module's surface)
+from ._marshal import (as_index, corruption_fields, ema_fields, ema_kwargs, grad_clip_fields, grad_clip_kwargs, dev_array, dev_block3, dev_dense, dev_dense3, dev_flags, dev_inputs, dev_modalities, dev_row_args,  # noqa: F401
+                       ld_of, ptr, schedule_kwargs, schedule_struct, to_device32)
 from ._marshal import cyclical, exponential_decay, linear_warmup  # noqa: F401  (schedule helpers, part of this module's surface)
-from ._marshal import motion_ik_args, motion_pose_args, refine_pen_path_args, strokes_to_motion_args
+from .motion import MotionBasis
 from .parallel import GradSync, dp_bucket_schedule, dp_train_step_bucketed
 
 _ARCH_KEYS = ("scope", "hidden_conv", "n_hidden_recog_1", "n_hidden_recog_2",
@@ -265,634 +274,6 @@ def create_replica(L, cfg, sync, comm, device, agree_dev):
             rc = L.avae_create(C.byref(cfg), C.byref(h))
     _capi.check(None, rc, "avae_create")
     return h, comm, ws, buckets
-
-
-def impute_args(X, present, n_samples, eps, widths, n_z, device):
-    """The arguments of ``impute`` checked and marshalled -> (tensors, N, was_numpy, ptrs, lds, presence or None, K, eps or None).
-    Every shape or ``n_samples`` error is a ``ValueError`` raised here, ahead of any launch; touches neither a model nor the
-    library (``device="cpu"`` works)."""
-    if isinstance(n_samples, bool) or not isinstance(n_samples, (int, np.integer)) or n_samples < 0:
-        raise ValueError("n_samples must be an integer >= 0, got %r" % (n_samples,))
-    K = int(n_samples)
-    if present is None:
-        ts, rows, was_np, ptrs, lds = dev_modalities(X, widths, device, allow_none=True)
-        if rows is None:
-            raise ValueError("every modality is None and there is no present array: the row count is unknown")
-        p = None
-    else:
-        ts, rows, was_np, ptrs, lds, p = dev_row_args(X, widths, device, present)
-    if K == 0 and eps is not None:
-        raise ValueError("eps needs n_samples >= 1 (n_samples = 0 decodes the fused mean, without noise)")
-    e = dev_dense3(eps, (rows, K, n_z), device)
-    return ts, rows, was_np, ptrs, lds, p, K, e
-
-
-def topk_args(query, gallery, k, metric, n_z, device):
-    """The arguments of ``latent_topk`` checked and marshalled -> (q_mu, q_logvar or None, g_mu, g_logvar or None, k, metric id,
-    was_numpy).  ``query`` and ``gallery`` are ``(mu, logvar)`` pairs of ``[rows, n_z]`` arrays or tensors; ``logvar`` may be None
-    under ``metric="l2"``, which never reads it.  Every shape, ``k`` or metric error is a ``ValueError`` raised here, ahead of any
-    launch; touches neither a model nor the library (``device="cpu"`` works)."""
-    if not isinstance(metric, str) or metric.lower() not in _capi.METRIC_IDS:
-        raise ValueError("metric must be 'symkl' or 'l2', got %r" % (metric,))
-    mid = _capi.METRIC_IDS[metric.lower()]
-    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= _capi.TOPK_MAX:
-        raise ValueError("k must be an integer in [1, %d], got %r" % (_capi.TOPK_MAX, k))
-    out, was_np = [], None
-    for name, pair in (("query", query), ("gallery", gallery)):
-        if not isinstance(pair, (tuple, list)) or len(pair) != 2:
-            raise ValueError("%s must be a (mu, logvar) pair, got %r" % (name, type(pair).__name__))
-        mu, lv = pair
-        if mu is None:
-            raise ValueError("%s: mu is None" % name)
-        if lv is None and mid == _capi.METRIC_SYMKL:
-            raise ValueError("%s: logvar is None, and metric='symkl' reads the log-variances (metric='l2' does not)" % name)
-        try:
-            t = dev_dense(mu, n_z, device, name="%s mu" % name)
-            if was_np is None:
-                was_np = not torch.is_tensor(mu)
-            rows = t.shape[0]
-            lt = None if mid == _capi.METRIC_L2 else dev_dense(lv, n_z, device, rows, "as mu", name="%s logvar" % name)
-        except ValueError as e:
-            raise ValueError("%s: %s" % (name, e))
-        out += [t, lt]
-    return out[0], out[1], out[2], out[3], int(k), mid, was_np
-
-
-def agg_args(z, gallery, exclude, marginals, n_z, device):
-    """The arguments of ``aggregate_log_density`` checked and marshalled -> (z, g_mu, g_logvar, exclude or None, marginals,
-    was_numpy).  ``z`` is ``[N, n_z]``, ``gallery`` a ``(mu, logvar)`` pair of ``[G, n_z]`` arrays or tensors, ``exclude`` None or
-    ``[N]`` integers.  Every shape or type error is a ``ValueError`` raised here, ahead of any launch; touches neither a model nor
-    the library (``device="cpu"`` works)."""
-    if z is None:
-        raise ValueError("z is None")
-    if not isinstance(gallery, (tuple, list)) or len(gallery) != 2:
-        raise ValueError("gallery must be a (mu, logvar) pair, got %r" % type(gallery).__name__)
-    mu, lv = gallery
-    if mu is None or lv is None:
-        raise ValueError("gallery: %s is None: the density reads both" % ("mu" if mu is None else "logvar"))
-    zt = dev_dense(z, n_z, device, name="z")
-    try:
-        gm = dev_dense(mu, n_z, device, name="mu")
-        gl = dev_dense(lv, n_z, device, gm.shape[0], "as mu", name="logvar")
-    except ValueError as e:
-        raise ValueError("gallery: %s" % e)
-    ex = None
-    if exclude is not None:
-        ex = torch.as_tensor(exclude if torch.is_tensor(exclude) else np.asarray(exclude))
-        if ex.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
-            raise ValueError("exclude must hold integers (gallery row numbers), got %s" % ex.dtype)
-        if tuple(ex.shape) != (zt.shape[0],):
-            raise ValueError("exclude must be [%d] (one gallery row per row of z), got %s" % (zt.shape[0], tuple(ex.shape)))
-        big = torch.iinfo(torch.int32).max
-        ex = ex.to(device=device, dtype=torch.int64).clamp(-1, big).to(torch.int32).contiguous()      # (anything outside the gallery excludes nothing)
-    return zt, gm, gl, ex, bool(marginals), not torch.is_tensor(z)
-
-
-def _is_pair(x):
-    """a ``(mu, logvar)`` pair of arrays or tensors (``logvar`` may be None), as opposed to a list of such pairs"""
-    return isinstance(x, (tuple, list)) and len(x) == 2 and hasattr(x[0], "shape") and (x[1] is None or hasattr(x[1], "shape"))
-
-
-def prior_arrays(prior, n_z, device, name="prior", n_components=None):
-    """A mixture prior checked and marshalled -> (weights [K], means [K, n_z], logvars [K, n_z] contiguous float32 tensors on
-    ``device``, was_numpy).  ``prior`` is a dict with the keys ``weights``, ``means`` and ``logvars`` (what ``fit_latent_prior``
-    returns; further keys are ignored).  Every error is a ``ValueError``; touches neither a model nor the library."""
-    if not isinstance(prior, dict) or any(k not in prior for k in ("weights", "means", "logvars")):
-        raise ValueError("%s must be a dict with the keys weights, means and logvars, got %r"
-                         % (name, sorted(prior) if isinstance(prior, dict) else type(prior).__name__))
-    w, was_np = prior["weights"], not torch.is_tensor(prior["weights"])
-    w = torch.as_tensor(np.asarray(w, dtype=np.float32) if was_np else w).to(device=device, dtype=torch.float32).contiguous()
-    if w.dim() != 1 or not 1 <= w.shape[0] <= _capi.GMM_MAX_COMPONENTS:
-        raise ValueError("%s: weights must be [K] with 1 <= K <= %d, got %s" % (name, _capi.GMM_MAX_COMPONENTS, tuple(w.shape)))
-    K = int(w.shape[0])
-    if n_components is not None and K != n_components:
-        raise ValueError("%s: weights must be [%d] (n_components), got %s" % (name, n_components, tuple(w.shape)))
-    if not bool(torch.isfinite(w).all()) or bool((w < 0).any()) or not float(w.sum()) > 0:
-        raise ValueError("%s: weights must be finite, non-negative and not all zero" % name)
-    try:
-        m = dev_dense(prior["means"], n_z, device, K, "as weights", name="means")
-        lv = dev_dense(prior["logvars"], n_z, device, K, "as weights", name="logvars")
-    except ValueError as e:
-        raise ValueError("%s: %s" % (name, e))
-    if m is None or lv is None:
-        raise ValueError("%s: %s is None" % (name, "means" if m is None else "logvars"))
-    return w, m, lv, was_np
-
-
-def latent_prior_args(posteriors, n_components, n_iters, init, seed, var_floor, n_z, device):
-    """The arguments of ``fit_latent_prior`` checked and marshalled -> (mu, logvar or None, K, n_iters, var_floor, init, seed_rows,
-    was_numpy).  ``posteriors`` is a ``(mu, logvar)`` pair of ``[N, n_z]`` arrays or tensors (``logvar`` may be None: points) or
-    a list of such pairs, whose rows are concatenated in list order (every pair with a logvar, or none).  ``init`` comes back as
-    the ``(weights, means, logvars)`` tensors of the given dict (copies: the fit works in place) and ``seed_rows`` as None, or,
-    for ``init=None``, ``init`` is None and ``seed_rows`` a LongTensor of the K rows the means start from:
-    ``np.random.default_rng(seed).permutation(F)[:K]`` over the F rows without a non-finite entry, in row order.  Every shape or
-    value error is a ``ValueError`` raised here, ahead of any launch; touches neither a model nor the library (``device="cpu"``
-    works)."""
-    if isinstance(n_components, bool) or not isinstance(n_components, (int, np.integer)) \
-            or not 1 <= n_components <= _capi.GMM_MAX_COMPONENTS:
-        raise ValueError("n_components must be an integer in [1, %d], got %r" % (_capi.GMM_MAX_COMPONENTS, n_components))
-    if isinstance(n_iters, bool) or not isinstance(n_iters, (int, np.integer)) or n_iters < 0:
-        raise ValueError("n_iters must be an integer >= 0, got %r" % (n_iters,))
-    try:
-        vf = float(var_floor)
-    except (TypeError, ValueError):
-        raise ValueError("var_floor must be a positive finite number, got %r" % (var_floor,))
-    if not (vf > 0.0 and np.isfinite(vf) and float(np.float32(vf)) > 0.0 and np.isfinite(np.float32(vf))):
-        raise ValueError("var_floor must be a positive finite number (in float32), got %r" % (var_floor,))
-    K = int(n_components)
-    pairs = [posteriors] if _is_pair(posteriors) else posteriors
-    if not isinstance(pairs, (list, tuple)) or not pairs or not all(_is_pair(p) for p in pairs):
-        raise ValueError("posteriors must be a (mu, logvar) pair or a non-empty list of such pairs, got %r" % type(posteriors).__name__)
-    if len({p[1] is None for p in pairs}) != 1:
-        raise ValueError("posteriors: every pair needs a logvar, or none may have one (points)")
-    mus, lvs = [], []
-    for i, (mu, lv) in enumerate(pairs):
-        try:
-            t = dev_dense(mu, n_z, device, name="mu")
-            mus.append(t)
-            if lv is not None:
-                lvs.append(dev_dense(lv, n_z, device, t.shape[0], "as mu", name="logvar"))
-        except ValueError as e:
-            raise ValueError("posteriors[%d]: %s" % (i, e))
-    was_np = not torch.is_tensor(pairs[0][0])
-    mu = mus[0] if len(mus) == 1 else torch.cat(mus).contiguous()
-    lv = None if not lvs else (lvs[0] if len(lvs) == 1 else torch.cat(lvs).contiguous())
-    if init is not None:
-        w, m, s, _ = prior_arrays(init, n_z, device, name="init", n_components=K)
-        return mu, lv, K, int(n_iters), vf, (w.clone(), m.clone(), s.clone()), None, was_np
-    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or seed < 0:
-        raise ValueError("seed must be an integer >= 0, got %r" % (seed,))
-    fin = torch.isfinite(mu).all(dim=1)
-    if lv is not None:
-        fin &= torch.isfinite(lv).all(dim=1)
-    rows = torch.nonzero(fin).reshape(-1).cpu()
-    F = int(rows.shape[0])
-    if K > F:
-        raise ValueError("n_components = %d is more than the %d rows without a non-finite entry that the means are drawn from" % (K, F))
-    pick = np.random.default_rng(int(seed)).permutation(F)[:K]
-    return mu, lv, K, int(n_iters), vf, None, rows[torch.from_numpy(pick.astype(np.int64))], was_np
-
-
-def embed_args(posteriors, perplexity, n_iters, metric, learning_rate, early_exaggeration, exaggeration_iters, momentum, init,
-               seed, state, n_z, device):
-    """The arguments of ``embed_latents`` checked and marshalled -> dict(mu, logvar (None under ``metric="l2"``), metric id, rows,
-    n_used, perplexity, n_iters, learning_rate, early_exaggeration, exaggeration_iters, momentum, y, vel, gain, it0, calibration
-    (None: to be computed), was_numpy).  ``posteriors`` is a ``(mu, logvar)`` pair of ``[N, n_z]`` arrays or tensors or a list of
-    such pairs, concatenated in list order, as in ``latent_prior_args``; ``logvar=None`` needs ``metric="l2"``.  ``y`` is a copy of
-    ``init`` or, for ``init=None``, ``np.random.default_rng(seed).normal(0, 1e-4, (N, 2))``; ``state`` (what ``embed_latents``
-    returned) replaces velocity, gains, iteration number and calibration, and ``init`` then defaults to its embedding.
-    ``learning_rate="auto"`` is ``max(F / 48, 50)`` over the F rows without a non-finite entry.  Every shape or value error is a
-    ``ValueError`` raised here, ahead of any launch; touches neither a model nor the library (``device="cpu"`` works)."""
-    if not isinstance(metric, str) or metric.lower() not in _capi.METRIC_IDS:
-        raise ValueError("metric must be 'symkl' or 'l2', got %r" % (metric,))
-    mid = _capi.METRIC_IDS[metric.lower()]
-    if isinstance(n_iters, bool) or not isinstance(n_iters, (int, np.integer)) or n_iters < 0:
-        raise ValueError("n_iters must be an integer >= 0, got %r" % (n_iters,))
-    if isinstance(exaggeration_iters, bool) or not isinstance(exaggeration_iters, (int, np.integer)) or exaggeration_iters < 0:
-        raise ValueError("exaggeration_iters must be an integer >= 0, got %r" % (exaggeration_iters,))
-
-    def number(x, name, lo=None):
-        try:
-            v = float(x)
-        except (TypeError, ValueError):
-            v = float("nan")
-        if isinstance(x, bool) or not np.isfinite(v) or not np.isfinite(np.float32(v)) or (lo is not None and not v > lo):
-            raise ValueError("%s must be a finite number%s, got %r" % (name, "" if lo is None else " > %g" % lo, x))
-        return v
-    ee = number(early_exaggeration, "early_exaggeration", 0.0)
-    if not isinstance(momentum, (tuple, list)) or len(momentum) != 2:
-        raise ValueError("momentum must be a pair (during the early exaggeration, after it), got %r" % (momentum,))
-    mom = (number(momentum[0], "momentum[0]"), number(momentum[1], "momentum[1]"))
-    pairs = [posteriors] if _is_pair(posteriors) else posteriors
-    if not isinstance(pairs, (list, tuple)) or not pairs or not all(_is_pair(p) for p in pairs):
-        raise ValueError("posteriors must be a (mu, logvar) pair or a non-empty list of such pairs, got %r" % type(posteriors).__name__)
-    if mid == _capi.METRIC_SYMKL and any(p[1] is None for p in pairs):
-        raise ValueError("posteriors: logvar is None, and metric='symkl' reads the log-variances (metric='l2' does not)")
-    mus, lvs = [], []
-    for i, (mu, lv) in enumerate(pairs):
-        try:
-            t = dev_dense(mu, n_z, device, name="mu")
-            mus.append(t)
-            if mid == _capi.METRIC_SYMKL:
-                lvs.append(dev_dense(lv, n_z, device, t.shape[0], "as mu", name="logvar"))
-        except ValueError as e:
-            raise ValueError("posteriors[%d]: %s" % (i, e))
-    was_np = not torch.is_tensor(pairs[0][0])
-    mu = mus[0] if len(mus) == 1 else torch.cat(mus).contiguous()
-    lv = None if not lvs else (lvs[0] if len(lvs) == 1 else torch.cat(lvs).contiguous())
-    N = int(mu.shape[0])
-    if N > _capi.EMBED_MAX_ROWS:
-        raise ValueError("%d rows are more than the %d one map takes (the work is quadratic in the rows)" % (N, _capi.EMBED_MAX_ROWS))
-    fin = torch.isfinite(mu).all(dim=1)
-    if lv is not None:
-        fin &= torch.isfinite(lv).all(dim=1)
-    F = int(fin.sum().item())
-    perp = number(perplexity, "perplexity")
-    if N < 2 or not 1.0 <= perp <= F - 1:
-        raise ValueError("perplexity = %r must be in [1, F - 1] for the F = %d rows without a non-finite entry (of %d rows)"
-                         % (perplexity, F, N))
-    if isinstance(learning_rate, str):
-        if learning_rate != "auto":
-            raise ValueError("learning_rate must be 'auto' or a positive number, got %r" % (learning_rate,))
-        lr = max(F / 48.0, 50.0)
-    else:
-        lr = number(learning_rate, "learning_rate", 0.0)
-
-    def map_array(x, name):
-        t = dev_dense(x, 2, device, N, "as the posteriors", name=name)
-        if t is None:
-            raise ValueError("%s is None" % name)
-        return t.clone()
-
-    def row_vector(x, name):
-        t = torch.as_tensor(x if torch.is_tensor(x) else np.asarray(x, dtype=np.float32)).to(device=device, dtype=torch.float32)
-        if tuple(t.shape) != (N,):
-            raise ValueError("%s must be [%d] (as the posteriors), got %s" % (name, N, tuple(t.shape)))
-        return t.contiguous().clone()
-    it0, calib, vel, gain = 0, None, None, None
-    if state is not None:
-        keys = ("velocity", "gains", "iteration", "beta", "shift", "norm")
-        if not isinstance(state, dict) or any(k not in state for k in keys + ("embedding",)):
-            raise ValueError("state must be the state dict embed_latents returned (keys embedding, %s), got %r"
-                             % (", ".join(keys), sorted(state) if isinstance(state, dict) else type(state).__name__))
-        it0 = state["iteration"]
-        if isinstance(it0, bool) or not isinstance(it0, (int, np.integer)) or it0 < 0:
-            raise ValueError("state: iteration must be an integer >= 0, got %r" % (it0,))
-        try:
-            vel, gain = map_array(state["velocity"], "velocity"), map_array(state["gains"], "gains")
-            calib = tuple(row_vector(state[k], k) for k in ("beta", "shift", "norm"))
-            if init is None:
-                init = state["embedding"]
-        except ValueError as e:
-            raise ValueError("state: %s" % e)
-    if init is None:
-        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or seed < 0:
-            raise ValueError("seed must be an integer >= 0, got %r" % (seed,))
-        y = torch.from_numpy(np.random.default_rng(int(seed)).normal(0.0, 1e-4, (N, 2)).astype(np.float32)).to(device)
-    else:
-        try:
-            y = map_array(init, "init")
-        except ValueError as e:
-            raise ValueError("init: %s" % e)
-    if vel is None:
-        vel = torch.zeros((N, 2), dtype=torch.float32, device=device)
-        gain = torch.ones((N, 2), dtype=torch.float32, device=device)
-    return {"mu": mu, "logvar": lv, "metric": mid, "rows": N, "n_used": F, "perplexity": perp, "n_iters": int(n_iters),
-            "learning_rate": lr, "early_exaggeration": ee, "exaggeration_iters": int(exaggeration_iters), "momentum": mom,
-            "y": y, "vel": vel, "gain": gain, "it0": int(it0), "calibration": calib, "was_numpy": was_np}
-
-
-def latent_score_args(z, prior, n_z, device):
-    """The arguments of ``latent_prior_score`` checked and marshalled -> (mu, logvar or None, weights, means, logvars,
-    was_numpy).  ``z`` is a ``[N, n_z]`` array or tensor (points) or a ``(mu, logvar)`` pair."""
-    if z is None:
-        raise ValueError("z is None")
-    mu, lv = z if _is_pair(z) else (z, None)
-    try:
-        mt = dev_dense(mu, n_z, device, name="mu" if _is_pair(z) else "z")
-        lt = dev_dense(lv, n_z, device, mt.shape[0], "as mu", name="logvar")
-    except ValueError as e:
-        raise ValueError("z: %s" % e)
-    w, m, s, _ = prior_arrays(prior, n_z, device)
-    return mt, lt, w, m, s, not torch.is_tensor(mu)
-
-
-def latent_stats_args(posteriors, present, n_z, device):
-    """The arguments of ``latent_stats`` checked and marshalled -> (mus, logvars, rows, presence or None, was_numpy): two lists
-    over the modalities of ``[rows, n_z]`` tensors, None where the modality is absent everywhere.  ``posteriors`` is a list of 1 to
-    4 ``(mu, logvar)`` pairs or None; ``present`` [rows, M] flags or None.  Every shape error is a ``ValueError`` raised here, ahead
-    of any launch; touches neither a model nor the library (``device="cpu"`` works)."""
-    if not isinstance(posteriors, (list, tuple)) or not 1 <= len(posteriors) <= _capi.AVAE_MAX_MODALITIES:
-        raise ValueError("posteriors must be a list over 1 to %d modalities of (mu, logvar) pairs or None, got %r"
-                         % (_capi.AVAE_MAX_MODALITIES, type(posteriors).__name__ if not isinstance(posteriors, (list, tuple))
-                            else len(posteriors)))
-    M = len(posteriors)
-    p = None if present is None else dev_flags(present, M, device)
-    rows, what = (None, None) if p is None else (int(p.shape[0]), "as present")
-    mus, lvs, was_np = [], [], None
-    for m, pair in enumerate(posteriors):
-        if pair is None:
-            mus.append(None)
-            lvs.append(None)
-            continue
-        if not isinstance(pair, (tuple, list)) or len(pair) != 2:
-            raise ValueError("posteriors[%d] must be a (mu, logvar) pair or None, got %r" % (m, type(pair).__name__))
-        mu, lv = pair
-        if mu is None:
-            raise ValueError("posteriors[%d]: mu is None (None in place of the pair marks a modality absent everywhere)" % m)
-        if lv is None:
-            raise ValueError("posteriors[%d]: logvar is None: a mu needs its logvar" % m)
-        try:
-            t = dev_dense(mu, n_z, device, rows, what, name="mu")
-            if rows is None:
-                rows, what = t.shape[0], "as posteriors[%d]" % m
-            lt = dev_dense(lv, n_z, device, rows, "as mu", name="logvar")
-        except ValueError as e:
-            raise ValueError("posteriors[%d]: %s" % (m, e))
-        if was_np is None:
-            was_np = not torch.is_tensor(mu)
-        mus.append(t)
-        lvs.append(lt)
-    if rows is None:
-        raise ValueError("every modality is None and there is no present array: the row count is unknown")
-    return mus, lvs, rows, p, (not torch.is_tensor(present)) if was_np is None else was_np
-
-
-def motion_matrices(basis, device, anchor=None, rows=None, T=None):
-    """A ``MotionBasis`` (and an optional anchor) -> the device matrices of the motion calls: dict of ``phi [T, Kb]``, ``scale``,
-    ``shift [P]`` or None, ``limits [D, 2]`` or None, ``gain [T, n_c]`` and ``target [rows, D, n_c]`` or None, ``nc``.  ``anchor`` is
-    None or ``dict(phases=[...], target=[rows, D, n_c])``: the trajectories are those of the parameters projected onto
-    ``features(phases) theta == target`` (1 to 4 phases).  The matrices are cached on the basis per device, phases and T."""
-    from .motion import MotionBasis
-    if not isinstance(basis, MotionBasis):
-        raise ValueError("basis must be a MotionBasis, got %r" % (type(basis).__name__,))
-    phases = target = None
-    if anchor is not None:
-        if not isinstance(anchor, dict) or set(anchor) != {"phases", "target"}:
-            raise ValueError("anchor must be None or dict(phases=, target=)")
-        phases = np.atleast_1d(np.asarray(anchor["phases"], dtype=np.float64))
-        basis.constraint(phases)                       # (checks the phases)
-        target, _ = dev_block3(anchor["target"], (basis.n_dof, len(phases)), device, "anchor target", rows)
-    key = ("device", str(device), None if phases is None else phases.tobytes(), T)
-    if key not in basis._cache:
-        def up(a):
-            return None if a is None else torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).to(device)
-        phi, gain = basis.eval_matrices(phases, T)
-        sc, sh = basis.scale_shift()
-        basis._cache[key] = dict(phi=up(phi), gain=up(gain), scale=up(sc), shift=up(sh), limits=up(basis.limits))
-    out = dict(basis._cache[key])
-    out.update(target=target, nc=0 if phases is None else len(phases))
-    return out
-
-
-def motion_eval_args(params, basis, anchor, reference, reference_params, device):
-    """The arguments of ``motion_eval`` checked and marshalled -> (params [N, P], matrices, reference trajectory or None, reference
-    parameters or None, was_numpy).  Every shape error is a ``ValueError`` raised here, ahead of any launch; touches neither a model
-    nor the library (``device="cpu"`` works)."""
-    from .motion import MotionBasis
-    if not isinstance(basis, MotionBasis):
-        raise ValueError("basis must be a MotionBasis, got %r" % (type(basis).__name__,))
-    if reference is not None and reference_params is not None:
-        raise ValueError("reference and reference_params are both given: pass one reference")
-    p, was_np = dev_array(params, basis.n_params, device)
-    p = p.contiguous()
-    rows = p.shape[0]
-    mats = motion_matrices(basis, device, anchor, rows)
-    ref = None if reference is None else dev_block3(reference, (basis.n_points, basis.n_dof), device, "reference", rows)[0]
-    refp = dev_dense(reference_params, basis.n_params, device, rows, "as params", name="reference_params")
-    return p, mats, ref, refp, was_np
-
-
-def motion_fit_args(trajectories, basis, device):
-    """The arguments of ``motion_fit`` -> (trajectories [N, T, D], pinv [Kb, T], scale, shift, was_numpy); ``ValueError`` ahead of
-    any launch, usable with ``device="cpu"``."""
-    from .motion import MAX_POINTS, MotionBasis
-    if not isinstance(basis, MotionBasis):
-        raise ValueError("basis must be a MotionBasis, got %r" % (type(basis).__name__,))
-    t, was_np = dev_block3(trajectories, (None, basis.n_dof), device, "trajectories")
-    T = int(t.shape[1])
-    if not 1 <= T <= MAX_POINTS:
-        raise ValueError("trajectories must hold 1 to %d time points, got %d" % (MAX_POINTS, T))
-    key = ("device pinv", str(device), T)
-    if key not in basis._cache:
-        basis._cache[key] = torch.as_tensor(np.ascontiguousarray(basis.pinv(T), dtype=np.float32)).to(device)
-    mats = motion_matrices(basis, device)
-    return t, basis._cache[key], mats["scale"], mats["shift"], was_np
-
-
-def motion_moments_args(samples, basis, anchor, device):
-    """The arguments of ``motion_moments`` -> (samples [N, S, P], matrices, was_numpy); ``ValueError`` ahead of any launch, usable
-    with ``device="cpu"``."""
-    from .motion import MotionBasis
-    if not isinstance(basis, MotionBasis):
-        raise ValueError("basis must be a MotionBasis, got %r" % (type(basis).__name__,))
-    t, was_np = dev_block3(samples, (None, basis.n_params), device, "samples")
-    if t.shape[1] < 1:
-        raise ValueError("samples must hold at least one sample per row, got %s" % (tuple(t.shape),))
-    return t, motion_matrices(basis, device, anchor, int(t.shape[0])), was_np
-
-
-def predict_motion_args(X, basis, modality, present, n_samples, eps, anchor, widths, n_z, device):
-    """The arguments of ``predict_motion`` -> (``impute_args``' tuple with K = 0 and the eps block [N, S, n_z] or None in its last
-    two places, matrices); ``ValueError`` ahead of any launch, usable with ``device="cpu"``."""
-    from .motion import MotionBasis
-    if not isinstance(basis, MotionBasis):
-        raise ValueError("basis must be a MotionBasis, got %r" % (type(basis).__name__,))
-    if isinstance(modality, bool) or not isinstance(modality, (int, np.integer)) or not 0 <= modality < len(widths):
-        raise ValueError("modality must be an index in [0, %d), got %r" % (len(widths), modality))
-    if basis.n_params != widths[modality]:
-        raise ValueError("basis.n_params = %d must be n_input = %d of modality %d" % (basis.n_params, widths[modality], modality))
-    ts, rows, was_np, xp, lds, p, S, e = impute_args(X, present, n_samples, eps, widths, n_z, device)
-    return (ts, rows, was_np, xp, lds, p, S, e), motion_matrices(basis, device, anchor, rows)
-
-
-def chain_matrices(chain, device):
-    """A ``KinematicChain`` -> (``frames [n_dof + 1, 3, 4]``, ``axes [n_dof, 3]``) as float32 tensors on ``device``, cached on the
-    chain per device."""
-    from .kinematics import KinematicChain
-    if not isinstance(chain, KinematicChain):
-        raise ValueError("chain must be a KinematicChain, got %r" % (type(chain).__name__,))
-    key = ("device", str(device))
-    if key not in chain._cache:
-        chain._cache[key] = tuple(torch.as_tensor(a).to(device) for a in chain.packed())
-    return chain._cache[key]
-
-
-def motion_fk_args(trajectories, chain, device):
-    """The arguments of ``motion_fk`` -> (trajectories [N, T, n_dof], frames, axes, was_numpy); ``ValueError`` ahead of any launch,
-    usable with ``device="cpu"``."""
-    from .kinematics import MAX_POINTS
-    frames, axes = chain_matrices(chain, device)
-    t, was_np = dev_block3(trajectories, (None, chain.n_dof), device, "trajectories")
-    if not 1 <= t.shape[1] <= MAX_POINTS:
-        raise ValueError("trajectories must hold 1 to %d time points, got %d" % (MAX_POINTS, t.shape[1]))
-    return t, frames, axes, was_np
-
-
-def canvas_args(canvas, rows, target, height, device):
-    """A ``StrokeCanvas`` and the optional inputs of a drawing of ``rows`` rows -> (plane [3, 3], target [rows, H * H] or None,
-    height [rows] or None) on ``device`` (the plane cached on the canvas per device).  ``target`` may be one picture ``[H * H]`` for
-    every row, ``height`` one number."""
-    from .kinematics import StrokeCanvas
-    if not isinstance(canvas, StrokeCanvas):
-        raise ValueError("canvas must be a StrokeCanvas, got %r" % (type(canvas).__name__,))
-    key = ("device", str(device))
-    if key not in canvas._cache:
-        canvas._cache[key] = torch.as_tensor(np.ascontiguousarray(canvas.plane, dtype=np.float32)).to(device)
-    plane = canvas._cache[key]
-    if target is not None:
-        t = target if torch.is_tensor(target) else torch.as_tensor(np.asarray(target, dtype=np.float32))
-        if t.dim() == 1:
-            t = t.reshape(1, -1).expand(rows, -1)
-        target = dev_dense(t, canvas.n_pixels, device, rows, "as the paths", name="target")
-    if height is not None:
-        h = height if torch.is_tensor(height) else torch.as_tensor(np.asarray(height, dtype=np.float32))
-        if h.dim() == 0:
-            h = h.reshape(1).expand(rows)
-        if h.dim() != 1 or h.shape[0] != rows:
-            raise ValueError("height must be a number or [%d] (as the paths), got %s" % (rows, tuple(h.shape)))
-        height = h.to(device=device, dtype=torch.float32).contiguous()
-    return plane, target, height
-
-
-def render_args(path, canvas, target, height, device):
-    """The arguments of ``render_strokes`` -> (path [N, T, 3], plane [3, 3], target [N, H * H] or None, height [N] or None,
-    was_numpy); ``ValueError`` ahead of any launch, usable with ``device="cpu"``."""
-    from .kinematics import MAX_POINTS
-    p, was_np = dev_block3(path, (None, 3), device, "path")
-    if not 1 <= p.shape[1] <= MAX_POINTS:
-        raise ValueError("path must hold 1 to %d points, got %d" % (MAX_POINTS, p.shape[1]))
-    return (p,) + canvas_args(canvas, int(p.shape[0]), target, height, device) + (was_np,)
-
-
-def draw_args(params, basis, chain, canvas, anchor, target, height, device):
-    """The arguments of ``draw_motion`` -> (params [N, P], matrices, frames, axes, plane, target, height, was_numpy)"""
-    p, mats, _, _, was_np = motion_eval_args(params, basis, anchor, None, None, device)
-    frames, axes = chain_matrices(chain, device)
-    if chain.n_dof != basis.n_dof:
-        raise ValueError("chain.n_dof = %d must be basis.n_dof = %d" % (chain.n_dof, basis.n_dof))
-    return (p, mats, frames, axes) + canvas_args(canvas, int(p.shape[0]), target, height, device) + (was_np,)
-
-
-def writing_cost_args(weights, image_modality, canvas, widths):
-    """``writing_cost``'s own arguments checked -> the three weights as floats"""
-    from .kinematics import StrokeCanvas
-    if not isinstance(canvas, StrokeCanvas):
-        raise ValueError("canvas must be a StrokeCanvas, got %r" % (type(canvas).__name__,))
-    if isinstance(image_modality, bool) or not isinstance(image_modality, (int, np.integer)) or not 0 <= image_modality < len(widths):
-        raise ValueError("image_modality must be an index in [0, %d), got %r" % (len(widths), image_modality))
-    if canvas.n_pixels != widths[image_modality]:
-        raise ValueError("the canvas draws %d pixels, modality %d holds %d" % (canvas.n_pixels, image_modality, widths[image_modality]))
-    try:
-        w = [float(x) for x in weights]
-    except (TypeError, ValueError):
-        raise ValueError("weights must be three numbers (image, height, latent), got %r" % (weights,))
-    if len(w) != 3 or not all(np.isfinite(w)):
-        raise ValueError("weights must be three finite numbers (image, height, latent), got %r" % (weights,))
-    return w
-
-
-SEARCH_STATE_KEYS = ("mean", "var", "n_applied", "frozen", "best_cost", "best_x", "iteration")
-
-
-def search_args(x0, var0, n_rollouts, n_iters, eliteness, weighting, cov_update, learning_rate, covar_bounds, tol, project, seed,
-                state, device):
-    """The arguments of ``search`` checked and marshalled -> (state: a fresh one from ``x0`` / ``var0`` or a copy of ``state``,
-    ``_capi.SearchOptions``, n_rollouts, n_iters, (A, b, G, g) or None, seed, was_numpy).  Every error is a ``ValueError`` raised
-    here, ahead of any launch; touches neither a model nor the library (``device="cpu"`` works).  Values of device tensors are not
-    looked at: that would be a host round trip."""
-    def whole(v, name, lo, hi=None):
-        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < lo or (hi is not None and v > hi):
-            raise ValueError("%s must be an integer %s, got %r" % (name, ">= %d" % lo if hi is None else "in [%d, %d]" % (lo, hi), v))
-        return int(v)
-
-    def number(v, name, lo=None, hi=None):
-        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
-            raise ValueError("%s must be a finite number, got %r" % (name, v))
-        if (lo is not None and v < lo) or (hi is not None and v > hi):
-            raise ValueError("%s must be in [%s, %s], got %r" % (name, "-inf" if lo is None else lo, "inf" if hi is None else hi, v))
-        return float(v)
-    R = whole(n_rollouts, "n_rollouts", 1, _capi.SEARCH_MAX_ROLLOUTS)
-    n_iters = whole(n_iters, "n_iters", 0, 1 << 30)
-    seed = whole(seed, "seed", 0, (1 << 64) - 1)
-    if weighting not in _capi.SEARCH_IDS:
-        raise ValueError("weighting must be 'PI-BB', 'CEM' or 'CMA-ES', got %r" % (weighting,))
-    if cov_update not in ("PI-BB", "CEM"):
-        raise ValueError("cov_update must be 'PI-BB' or 'CEM', got %r" % (cov_update,))
-    opt = _capi.SearchOptions()
-    opt.weighting, opt.cov_update = _capi.SEARCH_IDS[weighting], _capi.SEARCH_IDS[cov_update]
-    opt.eliteness = number(eliteness, "eliteness", 0.0)
-    if weighting != "PI-BB" and (opt.eliteness < 1 or opt.eliteness != int(opt.eliteness)):
-        raise ValueError("eliteness must be a whole number >= 1 with %s weighting (the candidates kept), got %r" % (weighting, eliteness))
-    opt.learning_rate = number(learning_rate, "learning_rate", 0.0, 1.0)
-    opt.tol = number(tol, "tol", 0.0)
-    bounds = [] if covar_bounds is None else list(np.atleast_1d(covar_bounds))
-    if len(bounds) > 3:
-        raise ValueError("covar_bounds must be None or up to three numbers (relative lower, absolute lower, absolute upper), got %r"
-                         % (covar_bounds,))
-    bounds = [number(b, "covar_bounds[%d]" % i) for i, b in enumerate(bounds)] + [-1.0] * (3 - len(bounds))
-    if bounds[0] > 1.0:
-        raise ValueError("covar_bounds[0] (the relative lower bound) must be <= 1, got %r" % (bounds[0],))
-    opt.rel_lower, opt.abs_lower, opt.abs_upper = [b if b >= 0 else -1.0 for b in bounds]
-
-    def f32(a, name):
-        t = a if torch.is_tensor(a) else torch.as_tensor(np.asarray(a, dtype=np.float32))
-        if t.dtype not in (torch.float32, torch.float64, torch.float16, torch.bfloat16):
-            raise ValueError("%s must hold floating-point values, got %s" % (name, t.dtype))
-        return t.to(device=device, dtype=torch.float32)
-    if state is None:
-        if x0 is None or var0 is None:
-            raise ValueError("x0 and var0 are needed where there is no state to continue")
-        was_np = not torch.is_tensor(x0)
-        mean = f32(x0, "x0")
-        if mean.dim() != 2 or not 1 <= mean.shape[1] <= _capi.SEARCH_MAX_DIMS:
-            raise ValueError("x0 must be [P, n] with n in [1, %d], got %s" % (_capi.SEARCH_MAX_DIMS, tuple(mean.shape)))
-        P, n = int(mean.shape[0]), int(mean.shape[1])
-        if not torch.is_tensor(var0) and not (np.all(np.isfinite(var0)) and np.all(np.asarray(var0) >= 0)):
-            raise ValueError("var0 must be finite and >= 0")
-        if isinstance(var0, (int, float, np.integer, np.floating)):      # (filled on the device: no copy from the host)
-            var = torch.full((), float(var0), dtype=torch.float32, device=device)
-        else:
-            var = f32(var0, "var0")
-        if tuple(var.shape) not in ((), (n,), (P, n)):
-            raise ValueError("var0 must be a number, [%d] or [%d, %d], got %s" % (n, P, n, tuple(var.shape)))
-        st = dict(mean=mean.clone().contiguous(), var=var.expand(P, n).clone().contiguous(),
-                  n_applied=torch.zeros(P, dtype=torch.int32, device=device), frozen=torch.zeros(P, dtype=torch.int32, device=device),
-                  best_cost=torch.full((P,), float("inf"), dtype=torch.float32, device=device),
-                  best_x=torch.zeros((P, n), dtype=torch.float32, device=device), iteration=0)
-    else:
-        if not isinstance(state, dict) or set(state) != set(SEARCH_STATE_KEYS):
-            raise ValueError("state must be the dict a search returned (keys %s)" % ", ".join(SEARCH_STATE_KEYS))
-        was_np = False
-        if not torch.is_tensor(state["mean"]) or state["mean"].dim() != 2:
-            raise ValueError("state['mean'] must be a [P, n] tensor")
-        P, n = int(state["mean"].shape[0]), int(state["mean"].shape[1])
-        st = {"iteration": whole(state["iteration"], "state['iteration']", 0)}
-        for k, shape, dt in (("mean", (P, n), torch.float32), ("var", (P, n), torch.float32), ("best_x", (P, n), torch.float32),
-                             ("best_cost", (P,), torch.float32), ("n_applied", (P,), torch.int32), ("frozen", (P,), torch.int32)):
-            t = state[k]
-            if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dt:
-                raise ValueError("state[%r] must be a %s tensor of shape %s" % (k, dt, shape))
-            st[k] = t.to(device).clone().contiguous()
-    if st["iteration"] + n_iters >= 1 << 31:
-        raise ValueError("the run's iterations must stay below 2^31")
-    proj = None
-    if project is not None:
-        if not isinstance(project, (tuple, list)) or len(project) != 2:
-            raise ValueError("project must be None or (A [G, g, g], b [P, n])")
-        A, b = f32(project[0], "project A").contiguous(), f32(project[1], "project b").contiguous()
-        if A.dim() != 3 or A.shape[1] != A.shape[2] or A.shape[0] * A.shape[1] != n or not 1 <= A.shape[1] <= _capi.SEARCH_MAX_GROUP:
-            raise ValueError("project A must be [G, g, g] with G * g = n = %d and g <= %d, got %s"
-                             % (n, _capi.SEARCH_MAX_GROUP, tuple(A.shape)))
-        if tuple(b.shape) != (P, n):
-            raise ValueError("project b must be [%d, %d], got %s" % (P, n, tuple(b.shape)))
-        proj = (A, b, int(A.shape[0]), int(A.shape[1]))
-    return st, opt, R, n_iters, proj, seed, was_np
-
-
-def refine_motion_args(basis, chain, space, n_rollouts, modality, search_options, widths):
-    """``refine_motion``'s own arguments checked -> (n_rollouts with the space's default, the options passed on to ``search``)"""
-    from .kinematics import KinematicChain
-    from .motion import MotionBasis
-    if not isinstance(basis, MotionBasis):
-        raise ValueError("basis must be a MotionBasis, got %r" % (type(basis).__name__,))
-    if not isinstance(chain, KinematicChain):
-        raise ValueError("chain must be a KinematicChain, got %r" % (type(chain).__name__,))
-    if chain.n_dof != basis.n_dof:
-        raise ValueError("chain.n_dof = %d must be basis.n_dof = %d" % (chain.n_dof, basis.n_dof))
-    if space not in ("latent", "params"):
-        raise ValueError("space must be 'latent' or 'params', got %r" % (space,))
-    if isinstance(modality, bool) or not isinstance(modality, (int, np.integer)) or not 0 <= modality < len(widths):
-        raise ValueError("modality must be an index in [0, %d), got %r" % (len(widths), modality))
-    if basis.n_params != widths[modality]:
-        raise ValueError("basis.n_params = %d must be n_input = %d of modality %d" % (basis.n_params, widths[modality], modality))
-    allowed = {"eliteness", "weighting", "cov_update", "learning_rate", "covar_bounds", "tol", "seed"}
-    extra = set(search_options) - allowed
-    if extra:
-        raise ValueError("unknown option(s) %s (search takes %s)" % (", ".join(sorted(map(str, extra))), ", ".join(sorted(allowed))))
-    if n_rollouts is None:
-        n_rollouts = 10 if space == "latent" else 20
-    return n_rollouts, dict(search_options)
 
 
 class AssocVariationalAutoEncoder(object):
@@ -1921,6 +1302,15 @@ class AssocVariationalAutoEncoder(object):
                                                      self._ptrs(mean), None, self._stream()), "avae_impute")
         return mu, lv, mean[modality]
 
+    def _decode(self, modality, z, out=None):
+        """avae_decode on device tensors: latents ``z [rows, n_z]`` -> the parameters of ``modality`` (into ``out`` if given)"""
+        if out is None:
+            out = self._new(z.shape[0], self._widths[modality])
+        if z.shape[0]:
+            _capi.check(self._h, self._L.avae_decode(self._h, modality, z.data_ptr(), z.shape[0], out.data_ptr(), self._stream()),
+                        "avae_decode")
+        return out
+
     def predict_motion(self, X, basis, modality=1, present=None, n_samples=0, eps=None, anchor=None):
         """From the modalities each row has to the joint trajectory of modality ``modality`` (the writer's
         ``derive_robot_motion_from_img``, baxter_vae_assoc_writer.py:439-458, up to the trajectory): ``impute``'s fused posterior,
@@ -1955,8 +1345,7 @@ class AssocVariationalAutoEncoder(object):
         for r0 in range(0, rows, chunk):
             n = min(chunk, rows - r0)
             z = (mu[r0:r0 + n, None, :] + sd[r0:r0 + n, None, :] * e[r0:r0 + n]).reshape(n * S, self.n_z).contiguous()
-            _capi.check(self._h, self._L.avae_decode(self._h, modality, z.data_ptr(), n * S, dec.data_ptr(), self._stream()),
-                        "avae_decode")
+            self._decode(modality, z, dec)
             m = dict(mats, target=None if target is None else target[r0:r0 + n])
             self._motion_moments(dec, n, S, m, basis, traj[r0:r0 + n], var[r0:r0 + n], frac[r0:r0 + n])
         out.update(trajectory=conv(traj), var=conv(var), saturated_frac=conv(frac))
@@ -1968,8 +1357,7 @@ class AssocVariationalAutoEncoder(object):
         ``rmse`` and ``max_abs [N, n_dof]`` over the time points -- ``motion_eval(impute(only source)["mean"][modality], basis,
         reference_params=X[modality])``."""
         M = len(self._widths)
-        if isinstance(source, bool) or not isinstance(source, (int, np.integer)) or not 0 <= source < M:
-            raise ValueError("source must be an index in [0, %d), got %r" % (M, source))
+        as_index(source, "source", M)
         if len(X) != M:
             raise ValueError("expected a list of %d modalities, got %d" % (M, len(X)))
         only = [X[m] if m == source else None for m in range(M)]
@@ -2174,16 +1562,9 @@ class AssocVariationalAutoEncoder(object):
         frames, axes = chain_matrices(chain, self.device)
         plane = canvas_args(canvas, P, None, None, self.device)[0]
         zt = self._encode(image_modality, tg)
-
-        def decode(z):
-            out = self._new(z.shape[0], basis.n_params)
-            if z.shape[0]:
-                _capi.check(self._h, self._L.avae_decode(self._h, modality, z.data_ptr(), z.shape[0], out.data_ptr(),
-                                                         self._stream()), "avae_decode")
-            return out
         if latent or start is None:
             z0 = zt.clone() if start is None else start
-            p0 = decode(z0)
+            p0 = self._decode(modality, z0)
         else:
             p0 = start
         first = self._writing_cost(p0, mats, basis, frames, axes, plane, canvas, tg, None, zt, w, image_modality)
@@ -2198,14 +1579,14 @@ class AssocVariationalAutoEncoder(object):
                 v0 = 0.001 if basis.param_std is None else 0.001 / basis.param_std ** 2
             if anchor_start:
                 A, b = basis.projection([0.0], first["trajectory"][:, 0, :].reshape(P, basis.n_dof, 1).cpu().numpy())
-                project = (torch.as_tensor(A.astype(np.float32)).to(self.device), torch.as_tensor(b.astype(np.float32)).to(self.device))
+                project = (to_device32(A, self.device), to_device32(b, self.device))
 
         def price(cand, pidx):
-            return self._writing_cost(decode(cand) if latent else cand, mats, basis, frames, axes, plane, canvas,
+            return self._writing_cost(self._decode(modality, cand) if latent else cand, mats, basis, frames, axes, plane, canvas,
                                       tg.index_select(0, pidx), h0.index_select(0, pidx), zt.index_select(0, pidx), w,
                                       image_modality)["cost"]
         res = self.search(price, x0, v0, n_rollouts=R, n_iters=n_iters, project=project, **extra)
-        params = decode(res["mean"]) if latent else res["mean"]
+        params = self._decode(modality, res["mean"]) if latent else res["mean"]
         last = self._writing_cost(params, mats, basis, frames, axes, plane, canvas, tg, h0, zt, w, image_modality)
         conv = self._like_input(was_np)
         terms = ("cost", "img_l2", "height_l2", "latent_l2")
@@ -2221,8 +1602,7 @@ class AssocVariationalAutoEncoder(object):
         recorded parameters: the floor set by the renderer and the data.  Returns ``dict(predicted=dict(img_l2, latent_l2, image),
         own=dict(...) or None)``."""
         M = len(self._widths)
-        if isinstance(source, bool) or not isinstance(source, (int, np.integer)) or not 0 <= source < M:
-            raise ValueError("source must be an index in [0, %d), got %r" % (M, source))
+        as_index(source, "source", M)
         if len(X) != M:
             raise ValueError("expected a list of %d modalities, got %d" % (M, len(X)))
         writing_cost_args((0.0, 0.0, 0.0), source, canvas, self._widths)
@@ -2230,8 +1610,7 @@ class AssocVariationalAutoEncoder(object):
         (ts, rows, was_np, xp, lds, p, _, _), mats = predict_motion_args(only, basis, modality, None, 0, None, None, self._widths,
                                                                         self.n_z, self.device)
         frames, axes = chain_matrices(chain, self.device)
-        if chain.n_dof != basis.n_dof:
-            raise ValueError("chain.n_dof = %d must be basis.n_dof = %d" % (chain.n_dof, basis.n_dof))
+        _same_joints(basis, chain)
         own_p = None if X[modality] is None else dev_dense(X[modality], basis.n_params, self.device, rows, "as X[%d]" % source,
                                                            name="X[%d]" % modality)
         seen = ts[source].contiguous()
@@ -2364,7 +1743,6 @@ class AssocVariationalAutoEncoder(object):
         Returns ``search``'s dict and ``path [P, T, 3]`` (the refined pen path), ``trajectory [P, T, n_dof]``, ``params
         [P, n_params]`` (bitwise ``motion_fit(motion_ik(path, ...)["trajectory"], basis)``), ``converged [P]``, ``initial`` and
         ``final`` (dicts of ``img_l2 [P]`` of the initial path and of ``path``) and ``image``, the drawing of ``path``."""
-        from .motion import MotionBasis
         ik, search_options = refine_pen_path_args(basis, chain, canvas, n_rollouts, dict(options, n_iters=ik_n_iters), self._widths,
                                                   image_modality, modality)
         if target_image is None:
@@ -2373,17 +1751,13 @@ class AssocVariationalAutoEncoder(object):
         tg = tg.contiguous()
         P, T = int(tg.shape[0]), basis.n_points
         if init is None:
-            z0 = self._encode(image_modality, tg)
-            p0 = self._new(P, basis.n_params)
-            if P:
-                _capi.check(self._h, self._L.avae_decode(self._h, modality, z0.data_ptr(), P, p0.data_ptr(), self._stream()),
-                            "avae_decode")
+            p0 = self._decode(modality, self._encode(image_modality, tg))
         else:
             p0 = dev_dense(init, basis.n_params, self.device, P, "as target_image", name="init")
         mats = motion_matrices(basis, self.device)
         frames, axes = chain_matrices(chain, self.device)
         plane = canvas_args(canvas, P, None, None, self.device)[0]
-        back = torch.as_tensor(np.ascontiguousarray(np.linalg.inv(canvas.plane).T, dtype=np.float32)).to(self.device)
+        back = to_device32(np.linalg.inv(canvas.plane).T, self.device)
         traj0 = self._motion_eval(p0, mats, basis)[0]
         path0 = self._motion_fk(traj0, frames, axes)
         uvn = path0 @ plane.T                                                       # [P, T, 3]: in-plane u, v and the height n
@@ -2394,7 +1768,7 @@ class AssocVariationalAutoEncoder(object):
         project = None
         if anchor_start and P:
             A, b = flat.projection([0.0], uv0[:, 0, :].reshape(P, 2, 1).cpu().numpy())
-            project = (torch.as_tensor(A.astype(np.float32)).to(self.device), torch.as_tensor(b.astype(np.float32)).to(self.device))
+            project = (to_device32(A, self.device), to_device32(b, self.device))
         seed = traj0[:, 0, :] if seed_angles is None else seed_angles
 
         def pen_path(x, height):
