@@ -919,6 +919,65 @@ int avae_motion_ik(avae_handle* h, const float* path_dev, int32_t rows, int32_t 
                    float* traj_dev, float* residual_dev, float* rot_residual_dev, int32_t* iterations_dev, int32_t* status_dev,
                    void* stream);
 
+/* ---- sigma-lognormal strokes: batched evaluation, perturbed sampling and fitting on the device.  The
+ * reference diversifies its handwriting data by fitting every letter with a sum of lognormal velocity components
+ * (pytrajkin_rxzero.rxzero_train), perturbing each component's amplitude, start angle and straightness and evaluating the stroke
+ * again (extend_data_with_lognormal_sampling, utils.py:311-359; the model: pytrajkin_rxzero.py:241-292, 356-388).  These calls are
+ * the project's own statement of that model and a Levenberg-Marquardt fit of it, not a bit copy of the reference's optimiser.
+ * Dense device fp32 everywhere but count_dev / iterations_dev / accepted_dev / status_dev (int32), loss0_dev / loss_dev (double) and
+ * free_dev (uint8).  A stroke of row r is count[r] components p_c = (D, t0, mu, sigma, theta_s, theta_e) out of params[r][C][6]
+ * (count_dev NULL: all C; components c >= count[r] are never read), evaluated at t_k = k dt, k < T, from start[r] = (x0, y0):
+ *     tau = t_k - t0,  sg = max(sigma, 1e-6),  on = tau >= 1e-6,  tc = max(tau, 1e-6),  z = (ln tc - mu) / sg
+ *     amp = on ? D exp(-z^2 / 2) / (sg sqrt(2 pi) (tc + 1e-5)) : 0,   phi = theta_s + (theta_e - theta_s) / 2 (1 + erf z)
+ *     v_k = sum_c |amp| (cos phi, sin phi)  (c ascending),   path_k = start + dt sum_(j <= k) v_j  (inclusive)
+ *   in fp32, with ln, exp, erf, sin and cos taken in double on the float argument and rounded once (the correctly rounded float
+ *   result: the bits do not depend on a math library's choice within its ulp).
+ * avae_lognormal_eval: path[r][k] and, unless NULL, velocity[r][k] = v_k.  A row with a non-finite start or parameter (c < count)
+ *   is NaN everywhere and touches no other row.
+ * avae_lognormal_sample: for row r, sample s and component c one Philox4x32-10 block of the library's stream,
+ *     counter = (row_offset + r, s, c, 0),  key = (seed lo, seed hi ^ 0x736c676e 'slgn'),
+ *   whose first three Box-Muller normals divided by 3 are (n0, n1, n2);  D' = D + n0 amplitude D,  theta_s' = theta_s + n1 angle,
+ *   theta_e' = theta_e + n1 angle + n2 straightness (theta_e - theta_s), the rest unchanged.  strokes[r][s] is what
+ *   avae_lognormal_eval gives for those parameters, bit for bit; with shift_mean the sample's own mean point is subtracted.
+ *   perturbed[r][s][c] (may be NULL) are the perturbed components, zeros for c >= count[r].  Nothing of size rows * S * C * 6 is
+ *   stored otherwise.  The handle's draw counter is neither read nor advanced: a caller who samples rows in chunks passes each
+ *   chunk's first row as row_offset and gets the bits of the whole.
+ * avae_lognormal_fit: fits count[r] components to target[r][T][2] from init[r][C][6], the whole loop of a row inside one launch.
+ *     V_0 = (P_0 - start) / dt,  V_k = (P_k - P_(k-1)) / dt;   the loss  L = wp sum |path - P|^2 + wv sum |v - V|^2;
+ *     model values and Jacobian entries are fp32;  M = J^T W J, g = J^T W e and L are accumulated in double.
+ *     free_dev (NULL: every parameter free; [6], free_per_row 0; or [rows][C][6], free_per_row 1; nonzero = free) takes parameters
+ *     out: their rows and columns of M are 0 with a 1 on the diagonal, and 0 in g.  With d = diag(M) of the free parameters:
+ *     M += diag(lam d + 1e-12 (max d + 1));  a Cholesky in double (a pivot not > 0, or a non-finite solution, rejects the step);
+ *     new = p - M^-1 g rounded to float, sigma clipped into [1e-3, 3], then into [lo_dev[j], hi_dev[j]] (each [6] or NULL);
+ *     L(new) < L accepts: lam = max(lam / 3, 1e-9), and the row ends with status 0 when L - L(new) < tol L;
+ *     else lam = min(4 lam, 1e9) and p stays.  lam starts at 1e-3.
+ *     8 rejected tries in a row end the row as well: the damping has grown 65536-fold and nothing lowers the loss, which is how every
+ *     fit ends that reaches the floor of fp32 (a loss near 1e-12 on strokes of extent 1) -- status 0 when a step was accepted
+ *     before them, status 2 (the row cannot improve) when none ever was.
+ *   status: 0 converged, 1 n_iters tries made, 2 no step accepted at all in 8 tries, 3 a non-finite target, start or initial
+ *   parameter (c < count): that row's params, loss0 and loss are NaN, 0 iterations, and nothing else is touched.  count 0: nothing
+ *   to fit, 0 iterations, status 0, loss = loss0 that of standing still.  params[r][c] = 0 for c >= count[r].  loss0 the loss at
+ *   init, iterations the tries made, accepted the steps taken.  Every output but params_dev may be NULL.
+ *   csrc/avae_lognormal.h writes every operation and the order of every sum down.
+ * rows == 0 is a no-op.  Errors (message in avae_last_error, nothing launched): rows < 0, C outside [1, 16], T outside [1, 1024],
+ * dt not > 0, S outside [1, 2^20] or rows * S >= 2^31, row_offset < 0 or row_offset + rows > 2^32, amplitude, angle, straightness,
+ * wp, wv or tol negative or not finite, n_iters outside [0, 10000], a NULL required pointer.
+ * One launch each, no atomics, no scratch, nothing of the handle is read or written: a row's outputs are a pure function of its
+ * bits and the arguments -- the same alone or among other rows, on any stream, on repetition and whichever optional outputs are
+ * asked for -- and the calls work on any replica and inside avae_use_averaged. */
+int avae_lognormal_eval(avae_handle* h, const float* params_dev, const int32_t* count_dev, const float* start_dev,
+                        int32_t rows, int32_t C, int32_t T, float dt, float* path_dev, float* velocity_dev, void* stream);
+int avae_lognormal_sample(avae_handle* h, const float* params_dev, const int32_t* count_dev, const float* start_dev,
+                          int32_t rows, int32_t S, int32_t C, int32_t T, float dt, uint64_t seed, int64_t row_offset,
+                          float amplitude, float angle, float straightness, int32_t shift_mean,
+                          float* strokes_dev, float* perturbed_dev, void* stream);
+int avae_lognormal_fit(avae_handle* h, const float* target_dev, const float* init_dev, const int32_t* count_dev,
+                       const float* start_dev, int32_t rows, int32_t C, int32_t T, float dt, int32_t n_iters,
+                       double wp, double wv, double tol, const uint8_t* free_dev, int32_t free_per_row,
+                       const float* lo_dev, const float* hi_dev,
+                       float* params_dev, double* loss0_dev, double* loss_dev, int32_t* iterations_dev, int32_t* accepted_dev,
+                       int32_t* status_dev, void* stream);
+
 /* ---- black-box search around a cost: batched PI-BB / CEM iterations on the device.  The reference refines a
  * predicted motion by drawing rollouts from a Gaussian, pricing each and refitting the Gaussian to the cost-weighted rollouts
  * (pygcem.py:28-151, driven from baxter_vae_assoc_writer.py:259-342).  Here P such searches ("problems") advance at once: problem p

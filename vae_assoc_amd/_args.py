@@ -737,3 +737,142 @@ def refine_pen_path_args(basis, chain, canvas, n_rollouts, options, widths, imag
     ik_options(ik["n_iters"], ik["tol"], ik["rot_tol"], ik["damping"], ik["max_step"])
     search = {("tol" if k == "tol_search" else k): v for k, v in rest.items()}
     return ik, search
+
+
+# ---------------------------------------------------------------------------------------------------- sigma-lognormal strokes
+LN_MAX_C, LN_MAX_T, LN_MAX_ITERS = _capi.LOGNORMAL_MAX_COMPONENTS, _capi.LOGNORMAL_MAX_POINTS, _capi.LOGNORMAL_MAX_ITERS
+
+
+def _ln_number(v, name, positive):
+    """a finite float32 number, > 0 (``positive``) or >= 0 -> the float32 value as a float"""
+    if not _is_number(v) or not np.isfinite(v) or not np.isfinite(np.float32(v)):
+        raise ValueError("%s must be a finite number, got %r" % (name, v))
+    v32 = float(np.float32(v))
+    if (positive and not v32 > 0.0) or v32 < 0.0:
+        raise ValueError("%s must be %s as float32, got %r" % (name, "> 0" if positive else ">= 0", v))
+    return v32
+
+
+def _ln_dt(dt, T):
+    if dt is None:
+        if T == 1:
+            raise ValueError("dt is None and there is one time point: the default 1 / (T - 1) needs T >= 2")
+        dt = 1.0 / (T - 1)
+    return _ln_number(dt, "dt", True)
+
+
+def _ln_params(params, count, device, name="params"):
+    """params [N, C, 6] and count (None or [N] integers in [0, C]) -> (float32 tensor, int32 tensor [N], was_numpy)"""
+    if params is None:
+        raise ValueError("%s is None" % name)
+    p, was_np = dev_block3(params, (None, 6), device, name)
+    N, Cn = int(p.shape[0]), int(p.shape[1])
+    if not 1 <= Cn <= LN_MAX_C:
+        raise ValueError("%s must hold 1 to %d components (C), got %d" % (name, LN_MAX_C, Cn))
+    if count is None:
+        cnt = torch.full((N,), Cn, dtype=torch.int32, device=device)
+    else:
+        c = count if torch.is_tensor(count) else torch.as_tensor(np.asarray(count))
+        if c.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
+            raise ValueError("count must hold integers, got %s" % c.dtype)
+        if tuple(c.shape) != (N,):
+            raise ValueError("count must be [%d] (one per row of %s), got %s" % (N, name, tuple(c.shape)))
+        if N and (int(c.min()) < 0 or int(c.max()) > Cn):
+            raise ValueError("count must lie in [0, C = %d], got %d .. %d" % (Cn, int(c.min()), int(c.max())))
+        cnt = c.to(device=device, dtype=torch.int32).contiguous()
+    return p, cnt, was_np
+
+
+def _ln_start(start, N, device, default=None):
+    """start None (``default`` [N, 2] or the origin), [2] or [N, 2] -> float32 tensor [N, 2]"""
+    if start is None:
+        return torch.zeros((N, 2), dtype=torch.float32, device=device) if default is None else default.contiguous()
+    s = start if torch.is_tensor(start) else torch.as_tensor(np.asarray(start, dtype=np.float32))
+    if tuple(s.shape) not in ((2,), (N, 2)):
+        raise ValueError("start must be [2] or [%d, 2], got %s" % (N, tuple(s.shape)))
+    s = s.to(device=device, dtype=torch.float32)
+    return (s.reshape(1, 2).expand(N, 2) if s.dim() == 1 else s).contiguous()
+
+
+def _ln_strokes(strokes, device):
+    s, was_np = dev_block3(strokes, (None, 2), device, "strokes")
+    if not 1 <= s.shape[1] <= LN_MAX_T:
+        raise ValueError("strokes must hold 1 to %d points (T), got %d" % (LN_MAX_T, s.shape[1]))
+    return s, was_np
+
+
+def lognormal_eval_args(params, n_points, count, start, dt, device):
+    """The arguments of ``lognormal_eval`` -> (params [N, C, 6], count [N] int32, start [N, 2], T, dt, was_numpy)"""
+    p, cnt, was_np = _ln_params(params, count, device)
+    T = as_int(n_points, "n_points", 1, LN_MAX_T)
+    return p, cnt, _ln_start(start, int(p.shape[0]), device), T, _ln_dt(dt, T), was_np
+
+
+def lognormal_sample_options(n_samples, seed, amplitude, angle, straightness):
+    """-> (S, seed, amplitude, angle, straightness), the three scales as the float32 values the kernel uses"""
+    return (as_int(n_samples, "n_samples", 1, 1 << 20), as_int(seed, "seed", 0, (1 << 64) - 1),
+            _ln_number(amplitude, "amplitude", False), _ln_number(angle, "angle", False),
+            _ln_number(straightness, "straightness", False))
+
+
+def lognormal_fit_args(strokes, init, count, start, dt, max_components, n_iters, weights, free, bounds, tol, device):
+    """The arguments of ``lognormal_fit`` -> (strokes [N, T, 2], init [N, C, 6], count [N] int32, start [N, 2], dt, (n_iters, wp,
+    wv, tol), free (None or a uint8 tensor [6] or [N, C, 6]), lo, hi (None or float32 [6]), was_numpy).  ``init=None`` runs
+    ``lognormal_initial_guess`` on the host: the strokes are read back for it."""
+    from .lognormal import lognormal_initial_guess
+    if strokes is None:
+        raise ValueError("strokes is None")
+    s, was_np = _ln_strokes(strokes, device)
+    N, T = int(s.shape[0]), int(s.shape[1])
+    dt32 = _ln_dt(dt, T)
+    st = _ln_start(start, N, device, default=s[:, 0, :])
+    n_iters = as_int(n_iters, "n_iters", 0, LN_MAX_ITERS)
+    if not isinstance(weights, (tuple, list)) or len(weights) != 2 or not all(_is_number(w) and np.isfinite(w) and w >= 0 for w in weights):
+        raise ValueError("weights must be (position, velocity), two finite numbers >= 0, got %r" % (weights,))
+    if not _is_number(tol) or not np.isfinite(tol) or tol < 0:
+        raise ValueError("tol must be a finite number >= 0, got %r" % (tol,))
+    if init is None:
+        if count is not None:
+            raise ValueError("count goes with init: the initial guess finds its own")
+        as_int(max_components, "max_components", 1, LN_MAX_C)
+        guess, cnt = lognormal_initial_guess(s.cpu().numpy(), st.cpu().numpy(), dt32, max_components=max_components)
+        p, cnt, _ = _ln_params(guess.astype(np.float32), cnt, device, "init")
+    else:
+        p, cnt, _ = _ln_params(init, count, device, "init")
+        if p.shape[0] != N:
+            raise ValueError("init must hold the strokes' %d rows, got %d" % (N, p.shape[0]))
+    Cn = int(p.shape[1])
+    fr = None
+    if free is not None:
+        f = free if torch.is_tensor(free) else torch.as_tensor(np.asarray(free))
+        if tuple(f.shape) not in ((6,), (N, Cn, 6)):
+            raise ValueError("free must be None, [6] or [%d, %d, 6], got %s" % (N, Cn, tuple(f.shape)))
+        fr = (f != 0).to(device=device, dtype=torch.uint8).contiguous()
+    lo = hi = None
+    if bounds is not None:
+        if not isinstance(bounds, (tuple, list)) or len(bounds) != 2:
+            raise ValueError("bounds must be None or (lo, hi), each None or [6]")
+        out = []
+        for name, b in zip(("lo", "hi"), bounds):
+            if b is None:
+                out.append(None)
+                continue
+            b = np.asarray(b.cpu() if torch.is_tensor(b) else b, dtype=np.float64)
+            if b.shape != (6,) or np.isnan(b).any():
+                raise ValueError("bounds: %s must be [6] without NaN (an infinity leaves a parameter unbounded), got %r" % (name, b))
+            out.append(b)
+        if out[0] is not None and out[1] is not None and (out[0] > out[1]).any():
+            raise ValueError("bounds: lo must be <= hi")
+        lo, hi = (None if b is None else to_device32(b, device) for b in out)
+    return s, p, cnt, st, dt32, (n_iters, float(weights[0]), float(weights[1]), float(tol)), fr, lo, hi, was_np
+
+
+def lognormal_augment_args(strokes, params, count, start, dt, n_points, device):
+    """Which way ``lognormal_augment`` goes: exactly one of ``strokes`` (fit first) and ``params`` (given components, with
+    ``n_points``) -> 'strokes' or 'params'"""
+    if (strokes is None) == (params is None):
+        raise ValueError("give exactly one of strokes (fitted first) and params (perturbed as they are), got %s"
+                         % ("both" if strokes is not None else "neither"))
+    if params is not None and n_points is None:
+        raise ValueError("params needs n_points: the number of time points to evaluate")
+    return "strokes" if strokes is not None else "params"

@@ -7,6 +7,7 @@
 #include "avae_motion.h"
 #include "avae_render.h"
 #include "avae_ik.h"
+#include "avae_lognormal.h"
 #include "avae_search.h"
 #include "avae_gmm.h"
 #include "avae_embed.h"
@@ -4906,6 +4907,81 @@ int avae_motion_ik(avae_handle* h, const float* path_dev, int32_t rows, int32_t 
         a.rows = rows; a.T = T; a.D = D; a.n_iters = n_iters; a.orient_per_row = orient_dev && orient_rows == rows && rows > 1 ? 1 : 0;
         hipStream_t s = on_stream(h, stream);
         timed_launch(h, s, "motion_ik", [&] { launch_motion_ik(a, s); });
+    });
+}
+
+// ---- sigma-lognormal strokes (include/avae.h, avae_lognormal.h)
+static void check_lognormal_shape(const std::string& w, int32_t rows, int32_t C, int32_t T, float dt) {
+    check_rows(w, rows, "rows");
+    check_range(w, "C", C, 1, kLnMaxC);
+    check_range(w, "T", T, 1, kLnMaxT);
+    check_finite(w, "dt", dt, true);
+}
+
+int avae_lognormal_eval(avae_handle* h, const float* params_dev, const int32_t* count_dev, const float* start_dev,
+                        int32_t rows, int32_t C, int32_t T, float dt, float* path_dev, float* velocity_dev, void* stream) {
+    return guarded(h, [&] {
+        const std::string w = "avae_lognormal_eval";
+        check_lognormal_shape(w, rows, C, T, dt);
+        need(w, params_dev, "params_dev"); need(w, start_dev, "start_dev"); need(w, path_dev, "path_dev");
+        if (rows == 0) return;
+        LnEvalArgs a = zeroed<LnEvalArgs>();
+        a.params = params_dev; a.count = count_dev; a.start = start_dev; a.path = path_dev; a.velocity = velocity_dev;
+        a.dt = dt; a.rows = rows; a.C = C; a.T = T;
+        hipStream_t s = on_stream(h, stream);
+        timed_launch(h, s, "lognormal_eval", [&] { launch_lognormal_eval(a, s); });
+    });
+}
+
+int avae_lognormal_sample(avae_handle* h, const float* params_dev, const int32_t* count_dev, const float* start_dev,
+                          int32_t rows, int32_t S, int32_t C, int32_t T, float dt, uint64_t seed, int64_t row_offset,
+                          float amplitude, float angle, float straightness, int32_t shift_mean,
+                          float* strokes_dev, float* perturbed_dev, void* stream) {
+    return guarded(h, [&] {
+        const std::string w = "avae_lognormal_sample";
+        check_lognormal_shape(w, rows, C, T, dt);
+        check_range(w, "S", S, 1, 1 << 20);
+        if ((long long)rows * S > 0x7fffffffLL) throw Err(w + ": rows * S is too large for one launch");
+        if (row_offset < 0 || row_offset + (int64_t)rows > ((int64_t)1 << 32))
+            throw Err(w + ": row_offset = " + std::to_string(row_offset) + " must be >= 0 and row_offset + rows <= 2^32");
+        check_finite(w, "amplitude", amplitude, false);
+        check_finite(w, "angle", angle, false);
+        check_finite(w, "straightness", straightness, false);
+        need(w, params_dev, "params_dev"); need(w, start_dev, "start_dev"); need(w, strokes_dev, "strokes_dev");
+        if (rows == 0) return;
+        LnSampleArgs a = zeroed<LnSampleArgs>();
+        a.params = params_dev; a.count = count_dev; a.start = start_dev; a.strokes = strokes_dev; a.perturbed = perturbed_dev;
+        a.seed = seed; a.row0 = (unsigned)row_offset; a.dt = dt; a.amplitude = amplitude; a.angle = angle; a.straightness = straightness;
+        a.rows = rows; a.S = S; a.C = C; a.T = T; a.shift_mean = shift_mean ? 1 : 0;
+        hipStream_t s = on_stream(h, stream);
+        timed_launch(h, s, "lognormal_sample", [&] { launch_lognormal_sample(a, s); });
+    });
+}
+
+int avae_lognormal_fit(avae_handle* h, const float* target_dev, const float* init_dev, const int32_t* count_dev,
+                       const float* start_dev, int32_t rows, int32_t C, int32_t T, float dt, int32_t n_iters,
+                       double wp, double wv, double tol, const uint8_t* free_dev, int32_t free_per_row,
+                       const float* lo_dev, const float* hi_dev,
+                       float* params_dev, double* loss0_dev, double* loss_dev, int32_t* iterations_dev, int32_t* accepted_dev,
+                       int32_t* status_dev, void* stream) {
+    return guarded(h, [&] {
+        const std::string w = "avae_lognormal_fit";
+        check_lognormal_shape(w, rows, C, T, dt);
+        check_range(w, "n_iters", n_iters, 0, kLnMaxIters);
+        check_finite(w, "wp", wp, false);
+        check_finite(w, "wv", wv, false);
+        check_finite(w, "tol", tol, false);
+        need(w, target_dev, "target_dev"); need(w, init_dev, "init_dev"); need(w, start_dev, "start_dev");
+        need(w, params_dev, "params_dev");
+        if (rows == 0) return;
+        LnFitArgs a = zeroed<LnFitArgs>();
+        a.target = target_dev; a.init = init_dev; a.count = count_dev; a.start = start_dev; a.free_mask = free_dev;
+        a.lo = lo_dev; a.hi = hi_dev; a.params = params_dev; a.loss0 = loss0_dev; a.loss = loss_dev;
+        a.iterations = iterations_dev; a.accepted = accepted_dev; a.status = status_dev;
+        a.wp = wp; a.wv = wv; a.tol = tol; a.dt = dt;
+        a.rows = rows; a.C = C; a.T = T; a.n_iters = n_iters; a.free_per_row = free_dev && free_per_row ? 1 : 0;
+        hipStream_t s = on_stream(h, stream);
+        timed_launch(h, s, "lognormal_fit", [&] { launch_lognormal_fit(a, s); });
     });
 }
 

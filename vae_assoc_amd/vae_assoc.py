@@ -32,7 +32,8 @@ import torch
 
 from . import _capi
 from ._args import (SEARCH_STATE_KEYS, _is_pair, _same_joints, agg_args, canvas_args, chain_matrices, draw_args,  # noqa: F401
-                    embed_args, impute_args, latent_prior_args, latent_score_args, latent_stats_args, motion_eval_args,
+                    embed_args, impute_args, latent_prior_args, latent_score_args, latent_stats_args, lognormal_augment_args,
+                    lognormal_eval_args, lognormal_fit_args, lognormal_sample_options, motion_eval_args,
                     motion_fit_args, motion_fk_args, motion_ik_args, motion_matrices, motion_moments_args, motion_pose_args,
                     predict_motion_args, prior_arrays, refine_motion_args, refine_pen_path_args, render_args, search_args,
                     strokes_to_motion_args, topk_args, writing_cost_args)      # (the validators are part of this module's surface)
@@ -1791,6 +1792,135 @@ class AssocVariationalAutoEncoder(object):
                    converged=conv(sol["converged"].all(1)), image=conv(last["image"]),
                    initial={"img_l2": conv(first["img_l2"])}, final={"img_l2": conv(last["img_l2"])})
         return out
+
+    # ------------------------------------------------------------------ sigma-lognormal strokes
+    _lognormal_chunk = 16384   # rows (eval, fit) or rows x samples (sample) one launch takes
+
+    def _lognormal_eval(self, p, cnt, st, T, dt, velocity=True):
+        """avae_lognormal_eval on device tensors, in chunks of rows (rows are independent: the chunk changes no bit) ->
+        (path [N, T, 2], velocity [N, T, 2] or None)"""
+        N, Cn = int(p.shape[0]), int(p.shape[1])
+        path = torch.empty((N, T, 2), dtype=torch.float32, device=self.device)
+        vel = torch.empty((N, T, 2), dtype=torch.float32, device=self.device) if velocity else None
+        chunk = max(1, int(self._lognormal_chunk))
+        for r0 in range(0, N, chunk):
+            n = min(chunk, N - r0)
+            _capi.check(self._h, self._L.avae_lognormal_eval(
+                self._h, p[r0:r0 + n].data_ptr(), cnt[r0:r0 + n].data_ptr(), st[r0:r0 + n].data_ptr(), n, Cn, T, dt,
+                path[r0:r0 + n].data_ptr(), None if vel is None else vel[r0:r0 + n].data_ptr(), self._stream()),
+                "avae_lognormal_eval")
+        return path, vel
+
+    def lognormal_eval(self, params, n_points, count=None, start=None, dt=None):
+        """Sigma-lognormal components ``params [N, C, 6]`` (``D, t0, mu, sigma, theta_s, theta_e`` per component, C <= 16) -> the
+        strokes they draw (avae_lognormal_eval in include/avae.h; the reference's ``rxzero_traj_eval``, pytrajkin_rxzero.py:241-292,
+        for N strokes at once).  Row n uses its first ``count[n]`` components (default: all C) and starts from ``start`` (``[2]``,
+        ``[N, 2]``; default the origin); the ``n_points`` (<= 1024) time points are ``k * dt`` (``dt`` defaults to
+        ``1 / (n_points - 1)``).  Returns a dict: ``path [N, n_points, 2]`` and ``velocity [N, n_points, 2]``.  A row with a
+        non-finite parameter or start is NaN.  NumPy in gives NumPy out, device tensors in give device tensors out."""
+        p, cnt, st, T, dt32, was_np = lognormal_eval_args(params, n_points, count, start, dt, self.device)
+        path, vel = self._lognormal_eval(p, cnt, st, T, dt32)
+        conv = self._like_input(was_np)
+        return {"path": conv(path), "velocity": conv(vel)}
+
+    def _lognormal_fit(self, s, p, cnt, st, dt, opts, fr, lo, hi):
+        """avae_lognormal_fit on device tensors, in chunks of rows -> dict of device tensors"""
+        N, T, Cn = int(s.shape[0]), int(s.shape[1]), int(p.shape[1])
+        n_iters, wp, wv, tol = opts
+        out = torch.empty((N, Cn, 6), dtype=torch.float32, device=self.device)
+        l0, l1 = (torch.empty((N,), dtype=torch.float64, device=self.device) for _ in range(2))
+        its, acc, stt = (torch.empty((N,), dtype=torch.int32, device=self.device) for _ in range(3))
+        per_row = fr is not None and fr.dim() == 3
+        chunk = max(1, int(self._lognormal_chunk))
+        for r0 in range(0, N, chunk):
+            n = min(chunk, N - r0)
+            f = None if fr is None else (fr[r0:r0 + n] if per_row else fr)
+            _capi.check(self._h, self._L.avae_lognormal_fit(
+                self._h, s[r0:r0 + n].data_ptr(), p[r0:r0 + n].data_ptr(), cnt[r0:r0 + n].data_ptr(), st[r0:r0 + n].data_ptr(),
+                n, Cn, T, dt, n_iters, wp, wv, tol, ptr(f), 1 if per_row else 0, ptr(lo), ptr(hi),
+                out[r0:r0 + n].data_ptr(), l0[r0:r0 + n].data_ptr(), l1[r0:r0 + n].data_ptr(), its[r0:r0 + n].data_ptr(),
+                acc[r0:r0 + n].data_ptr(), stt[r0:r0 + n].data_ptr(), self._stream()), "avae_lognormal_fit")
+        return {"params": out, "count": cnt, "loss0": l0, "loss": l1, "iterations": its, "accepted": acc, "status": stt}
+
+    def lognormal_fit(self, strokes, init=None, count=None, start=None, dt=None, max_components=8, n_iters=40,
+                      weights=(1.0, 1e-3), free=None, bounds=None, tol=1e-9):
+        """Fits sigma-lognormal components to ``strokes [N, T, 2]`` by Levenberg-Marquardt, every row's whole loop inside one
+        launch (avae_lognormal_fit in include/avae.h): the project's own stand-in for the reference's ``rxzero_train``, not a copy
+        of its three-stage optimiser.
+
+        ``init [N, C, 6]`` with ``count [N]`` are the components to start from.  ``init=None`` runs ``lognormal_initial_guess``
+        (at most ``max_components`` speed peaks per stroke) on the host: that is the call's one host read of the strokes.
+        ``start`` defaults to each stroke's first point, ``dt`` to ``1 / (T - 1)``.  The loss is ``weights[0]`` times the squared
+        position error plus ``weights[1]`` times the squared velocity error.  ``free`` (``[6]`` or ``[N, C, 6]``, nonzero = free)
+        takes parameters out of the fit; ``bounds = (lo, hi)``, each None or ``[6]``, clips a step (``sigma`` always stays in
+        [1e-3, 3]).  A row stops after ``n_iters`` tries, or when an accepted step lowers the loss by less than ``tol`` times it.
+
+        Returns a dict: ``params [N, C, 6]``, ``count [N]``, ``loss0`` and ``loss [N]`` (float64, at the start and the end),
+        ``iterations``, ``accepted``, ``status [N]`` (int32; 0 converged -- by ``tol``, or 8 tries in a row rejected after an
+        accepted step: the floor of float32 --, 1 iteration cap, 2 no step accepted at all in 8 tries: the row cannot improve, 3 a non-finite stroke, start or initial parameter: NaN outputs), ``path [N, T, 2]`` (``lognormal_eval`` of the
+        fitted components) and ``rmse [N]`` (root mean squared distance of ``path`` from the stroke)."""
+        s, p, cnt, st, dt32, opts, fr, lo, hi, was_np = lognormal_fit_args(strokes, init, count, start, dt, max_components, n_iters,
+                                                                             weights, free, bounds, tol, self.device)
+        out = self._lognormal_fit(s, p, cnt, st, dt32, opts, fr, lo, hi)
+        path = self._lognormal_eval(out["params"], cnt, st, int(s.shape[1]), dt32, velocity=False)[0]
+        out["path"] = path
+        out["rmse"] = torch.sqrt(((path - s) ** 2).sum(dim=2).mean(dim=1))
+        conv = self._like_input(was_np)
+        return {k: conv(v) for k, v in out.items()}
+
+    def _lognormal_sample(self, p, cnt, st, T, dt, S, seed, amplitude, angle, straightness, shift_mean, want_params=True):
+        """avae_lognormal_sample on device tensors, in chunks of rows whose first row is the call's row_offset (the chunk changes
+        no bit) -> (strokes [N, S, T, 2], perturbed [N, S, C, 6] or None)"""
+        N, Cn = int(p.shape[0]), int(p.shape[1])
+        out = torch.empty((N, S, T, 2), dtype=torch.float32, device=self.device)
+        pert = torch.empty((N, S, Cn, 6), dtype=torch.float32, device=self.device) if want_params else None
+        chunk = max(1, int(self._lognormal_chunk) // S)
+        for r0 in range(0, N, chunk):
+            n = min(chunk, N - r0)
+            _capi.check(self._h, self._L.avae_lognormal_sample(
+                self._h, p[r0:r0 + n].data_ptr(), cnt[r0:r0 + n].data_ptr(), st[r0:r0 + n].data_ptr(), n, S, Cn, T, dt, seed, r0,
+                amplitude, angle, straightness, 1 if shift_mean else 0, out[r0:r0 + n].data_ptr(),
+                None if pert is None else pert[r0:r0 + n].data_ptr(), self._stream()), "avae_lognormal_sample")
+        return out, pert
+
+    def lognormal_augment(self, strokes=None, params=None, count=None, n_samples=10, seed=0, amplitude=0.2, angle=np.pi / 9,
+                          straightness=0.1, shift_mean=True, start=None, dt=None, n_points=None, **fit_options):
+        """The reference's ``extend_data_with_lognormal_sampling_helper`` (utils.py:331-359) for N strokes at once: every
+        component's amplitude, start angle and straightness are perturbed by a third of a normal draw times ``amplitude`` (of
+        ``D``), ``angle`` (radians, both angles) and ``straightness`` (of ``theta_e - theta_s``), and the stroke is evaluated
+        again -- ``n_samples`` times per row, perturbation and evaluation fused in one launch (avae_lognormal_sample in
+        include/avae.h).  With ``shift_mean`` every sample has its own mean point subtracted.
+
+        Given ``strokes [N, T, 2]`` the components are fitted first (``lognormal_fit`` with ``fit_options``: init, max_components,
+        n_iters, weights, free, bounds, tol); given ``params [N, C, 6]`` (with ``count``, ``n_points`` and optionally ``start``,
+        ``dt``) they are perturbed as they are.  The draws depend on ``seed`` and the row's index alone.
+
+        Returns a dict: ``strokes [N, n_samples, T, 2]``, ``params [N, C, 6]`` and ``count [N]`` (the components perturbed),
+        ``perturbed [N, n_samples, C, 6]`` and ``status [N]`` (the fit's; zeros without one).  A row whose fit ended with status 2
+        or 3 returns its samples as NaN (the reference drops such a letter with a message): ``status`` names it."""
+        way = lognormal_augment_args(strokes, params, count, start, dt, n_points, self.device)
+        S, seed, amplitude, angle, straightness = lognormal_sample_options(n_samples, seed, amplitude, angle, straightness)
+        if way == "strokes":
+            extra = set(fit_options) - {"init", "max_components", "n_iters", "weights", "free", "bounds", "tol"}
+            if extra:
+                raise ValueError("unknown option(s) %s (lognormal_fit takes init, max_components, n_iters, weights, free, bounds, "
+                                 "tol)" % ", ".join(sorted(map(str, extra))))
+            s, p0, cnt, st, dt32, opts, fr, lo, hi, was_np = lognormal_fit_args(
+                strokes, fit_options.get("init"), count, start, dt, fit_options.get("max_components", 8),
+                fit_options.get("n_iters", 40), fit_options.get("weights", (1.0, 1e-3)), fit_options.get("free"),
+                fit_options.get("bounds"), fit_options.get("tol", 1e-9), self.device)
+            fit = self._lognormal_fit(s, p0, cnt, st, dt32, opts, fr, lo, hi)
+            p, status, T = fit["params"], fit["status"], int(s.shape[1])
+        else:
+            if fit_options:
+                raise ValueError("fit options (%s) need strokes to fit" % ", ".join(sorted(map(str, fit_options))))
+            p, cnt, st, T, dt32, was_np = lognormal_eval_args(params, n_points, count, start, dt, self.device)
+            status = torch.zeros((int(p.shape[0]),), dtype=torch.int32, device=self.device)
+        out, pert = self._lognormal_sample(p, cnt, st, T, dt32, S, seed, amplitude, angle, straightness, bool(shift_mean))
+        failed = status >= 2
+        out = torch.where(failed[:, None, None, None], torch.full_like(out, float("nan")), out)
+        conv = self._like_input(was_np)
+        return {"strokes": conv(out), "params": conv(p), "count": conv(cnt), "perturbed": conv(pert), "status": conv(status)}
 
     def save_model(self, fname=None):
         """reference vae_assoc.py:427-435 (default name: timestamp + batch size)."""
