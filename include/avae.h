@@ -926,7 +926,8 @@ int avae_motion_ik(avae_handle* h, const float* path_dev, int32_t rows, int32_t 
  * the project's own statement of that model and a Levenberg-Marquardt fit of it, not a bit copy of the reference's optimiser.
  * Dense device fp32 everywhere but count_dev / iterations_dev / accepted_dev / status_dev (int32), loss0_dev / loss_dev (double) and
  * free_dev (uint8).  A stroke of row r is count[r] components p_c = (D, t0, mu, sigma, theta_s, theta_e) out of params[r][C][6]
- * (count_dev NULL: all C; components c >= count[r] are never read), evaluated at t_k = k dt, k < T, from start[r] = (x0, y0):
+ * (count_dev NULL: all C; components c >= count[r] are never read; a count[r] outside [0, C] is read as clamped into it, in all
+ * three calls), evaluated at t_k = k dt, k < T, from start[r] = (x0, y0):
  *     tau = t_k - t0,  sg = max(sigma, 1e-6),  on = tau >= 1e-6,  tc = max(tau, 1e-6),  z = (ln tc - mu) / sg
  *     amp = on ? D exp(-z^2 / 2) / (sg sqrt(2 pi) (tc + 1e-5)) : 0,   phi = theta_s + (theta_e - theta_s) / 2 (1 + erf z)
  *     v_k = sum_c |amp| (cos phi, sin phi)  (c ascending),   path_k = start + dt sum_(j <= k) v_j  (inclusive)

@@ -279,8 +279,10 @@ def _pass32(p, tgt, start, dt, wp, wv, jac):
     return L, M, g
 
 
-def _solve(M, g):
-    """the kernel's Cholesky and substitutions in double, its order -> x or None (a pivot not > 0, a non-finite x)"""
+def _solve(M, g, why=None):
+    """the kernel's Cholesky and substitutions in double, its order -> x or None (a pivot not > 0, a non-finite x); ``why`` (a
+    list) gets "ok", "pivot" or "x" appended: which of the two rejections a failed solve took"""
+    why = [] if why is None else why
     n = len(g)
     L = np.zeros((n, n))
     with np.errstate(all="ignore"):
@@ -289,6 +291,7 @@ def _solve(M, g):
             for k in range(j):
                 s = s - L[j, k] * L[j, k]
             if not s > 0.0:
+                why.append("pivot")
                 return None
             L[j, j] = np.sqrt(s)
             v = M[j + 1:, j].copy()
@@ -302,20 +305,22 @@ def _solve(M, g):
         for j in range(n - 1, -1, -1):
             y[j] = y[j] / L[j, j]
             y[:j] = y[:j] - L[j, :j] * y[j]
+    why.append("ok" if np.isfinite(y).all() else "x")
     return y if np.isfinite(y).all() else None
 
 
 def fit_row(tgt, init, start, dt, n_iters=40, weights=DEFAULT_WEIGHTS, free=None, lo=None, hi=None, tol=1e-9, restated=False):
     """avae_lognormal_fit for one row: tgt [T, 2], init [count, 6], free None or bool [count, 6] -> dict(params [count, 6], loss0,
-    loss, iterations, accepted, status, tries: [(L, L(new) or None)] per try).  ``restated``: float32 parameters, model values and
-    Jacobian in the kernel's orders; else everything in float64."""
+    loss, iterations, accepted, status, tries: [(L, L(new) or None)] per try, solves: "ok", "pivot" or "x" per try).  ``restated``:
+    float32 parameters, model values and Jacobian in the kernel's orders; else everything in float64."""
     f = F32 if restated else F64
     run = _pass32 if restated else _pass64
     wp, wv = float(weights[0]), float(weights[1])
     tgt, start = np.asarray(tgt, dtype=f), np.asarray(start, dtype=f)
     p = np.asarray(init, dtype=f).reshape(-1, 6).copy()
     cnt = len(p)
-    out = dict(params=np.full((cnt, 6), np.nan, dtype=f), loss0=np.nan, loss=np.nan, iterations=0, accepted=0, status=3, tries=[])
+    out = dict(params=np.full((cnt, 6), np.nan, dtype=f), loss0=np.nan, loss=np.nan, iterations=0, accepted=0, status=3, tries=[],
+               solves=[])
     if not (np.isfinite(tgt).all() and np.isfinite(start).all() and np.isfinite(p).all()):
         return out
     fr = np.ones(6 * cnt, dtype=bool) if free is None else np.broadcast_to(np.asarray(free, dtype=bool), (cnt, 6)).reshape(-1)
@@ -333,7 +338,7 @@ def fit_row(tgt, init, start, dt, n_iters=40, weights=DEFAULT_WEIGHTS, free=None
         d = np.where(fr, np.diag(M), 0.0)
         md = max(0.0, d.max()) if len(d) else 0.0
         M[np.arange(6 * cnt)[fr], np.arange(6 * cnt)[fr]] += lam * d[fr] + 1e-12 * (md + 1.0)
-        x = _solve(M, g)
+        x = _solve(M, g, out["solves"])
         Ln = None
         if x is not None:
             new = (p.reshape(-1).astype(F64) - x).astype(f).reshape(cnt, 6)
@@ -367,7 +372,7 @@ def fit(target, init, count, start, dt, free=None, **opt):
     N, C = init.shape[0], init.shape[1]
     cnt = _counts(init, count)
     res = dict(params=np.zeros((N, C, 6)), loss0=np.zeros(N), loss=np.zeros(N), iterations=np.zeros(N, np.int32),
-               accepted=np.zeros(N, np.int32), status=np.zeros(N, np.int32), tries=[])
+               accepted=np.zeros(N, np.int32), status=np.zeros(N, np.int32), tries=[], solves=[])
     for n in range(N):
         fr = None if free is None else (np.asarray(free)[n, :cnt[n]] if np.asarray(free).ndim == 3 else np.asarray(free))
         r = fit_row(target[n], init[n, :cnt[n]], start[n], dt, free=fr, **opt)
@@ -378,6 +383,7 @@ def fit(target, init, count, start, dt, free=None, **opt):
         for k in ("loss0", "loss", "iterations", "accepted", "status"):
             res[k][n] = r[k]
         res["tries"].append(r["tries"])
+        res["solves"].append(r["solves"])
     return res
 
 
@@ -431,17 +437,17 @@ def contract_stroke(C, seed):
     return separated_stroke(C, np.random.default_rng(100 * C + seed))
 
 
-def step_case(N, C, seed, counts=None):
-    """A step-for-step case: N strokes of C separated components (row n: counts[n] of them), the float64 stroke rounded to
-    float32 as the target, and the true parameters perturbed by up to 10 % as the start -> dict(target [N, T, 2], init [N, C, 6],
-    count [N], start [N, 2], true [N, C, 6]) in float32 / int32"""
+def step_case(N, C, seed, counts=None, T=T_CASE, dt=DT_CASE):
+    """A step-for-step case: N strokes of C separated components (row n: counts[n] of them) at T points dt apart, the float64
+    stroke rounded to float32 as the target, and the true parameters perturbed by up to 10 % as the start -> dict(target
+    [N, T, 2], init [N, C, 6], count [N], start [N, 2], true [N, C, 6]) in float32 / int32"""
     rng = np.random.default_rng(seed)
     counts = [C] * N if counts is None else list(counts)
-    true, tgt = np.zeros((N, C, 6)), np.zeros((N, T_CASE, 2))
+    true, tgt = np.zeros((N, C, 6)), np.zeros((N, T, 2))
     for n, c in enumerate(counts):
         if c:
             true[n, :c] = separated_params(c, rng)
-        tgt[n] = stroke(true[n, :c], START_CASE, T_CASE, DT_CASE)[0]
+        tgt[n] = stroke(true[n, :c], START_CASE, T, dt)[0]
     init = true * (1.0 + 0.1 * rng.uniform(-1.0, 1.0, true.shape))
     return dict(target=tgt.astype(F32), init=init.astype(F32), count=np.asarray(counts, dtype=np.int32),
                 start=np.tile(np.asarray(START_CASE, dtype=F32), (N, 1)), true=true.astype(F32))

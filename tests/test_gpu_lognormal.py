@@ -4,7 +4,9 @@ lognormal_augment) on a real MI355X (include/avae.h) again
 1. eval, 2. the sampler and 3. the fit step for step (``tol = 0``, after 1 and 4 tries) against the float64 definition, within 4x
 the float32 restatement's own worst error over the same inputs (the rule of test_gpu_motion.py; |err| / (|ref| + 1), paths of
 fitted parameters as |err| / extent); 4. the fit's contract at the default options; 5. bit reproducibility and independence;
-6. ``lognormal_augment`` end to end into ``strokes_to_motion``.  The measured pairs are in README.md and DESIGN.md section 28."""
+6. ``lognormal_augment`` end to end into ``strokes_to_motion``; 7. to 11. the second pass (tests/lognormal_cases.py): the fit
+inside every tile and component class, the exits of its loop, its clips and weights, count NULL and out of range, the sampler's
+edges.  The measured pairs are in README.md and DESIGN.md section 28."""
 import ctypes as C
 
 import numpy as np
@@ -12,6 +14,7 @@ import pytest
 import torch
 
 import ik_cases as IC
+import lognormal_cases as LC
 import lognormal_reference as LR
 import render_reference as R
 from conftest import make_arch
@@ -74,44 +77,61 @@ def _err(model):
     return model._L.avae_last_error(model._h).decode()
 
 
-def _eval(model, params, count, start, T, dt, velocity=True, stream=None):
-    """avae_lognormal_eval -> (path, velocity or None) as NumPy, prefilled with -7"""
+class _Out:
+    """an output of -7s with ``guard`` rows of -7 before and behind it; ``t`` is what the call writes"""
+
+    def __init__(self, model, shape, guard=0, dtype=torch.float32):
+        self.whole = torch.full((shape[0] + 2 * guard,) + tuple(shape[1:]), -7, device=model.device, dtype=dtype)
+        self.t = self.whole[guard:guard + shape[0]]
+        self.guard = guard
+
+    def numpy(self):
+        g, w = self.guard, self.whole.cpu().numpy()
+        assert (w[:g] == -7).all() and (w[len(w) - g:] == -7).all(), "an element outside the output was written"
+        return w[g:len(w) - g]
+
+
+def _eval(model, params, count, start, T, dt, velocity=True, stream=None, guard=0):
+    """avae_lognormal_eval -> (path, velocity or None) as NumPy, prefilled with -7 (``count`` None: NULL; ``guard``: rows of -7
+    around every output, asserted untouched)"""
     N, Cn = params.shape[0], params.shape[1]
     ts = [_dev(model, params), _dev(model, count, torch.int32), _dev(model, start)]
-    path = torch.full((N, T, 2), -7.0, device=model.device)
-    vel = torch.full((N, T, 2), -7.0, device=model.device) if velocity else None
+    path_o, vel_o = _Out(model, (N, T, 2), guard), _Out(model, (N, T, 2), guard) if velocity else None
+    path, vel = path_o.t, vel_o.t if velocity else None
     torch.cuda.synchronize()                             # (the inputs and the prefill are there before another stream reads them)
     rc = model._L.avae_lognormal_eval(model._h, _p(ts[0]), _p(ts[1]), _p(ts[2]), N, Cn, T, dt, _p(path), _p(vel), _stream(model, stream))
     torch.cuda.synchronize()
     assert rc == 0, _err(model)
-    return path.cpu().numpy(), None if vel is None else vel.cpu().numpy()
+    return path_o.numpy(), None if vel is None else vel_o.numpy()
 
 
 def _sample(model, params, count, start, T, dt, S, seed, shift, offset=0, want_params=True, stream=None,
-            scales=(0.2, np.pi / 9, 0.1)):
+            scales=(0.2, np.pi / 9, 0.1), guard=0):
     """avae_lognormal_sample -> (strokes [N, S, T, 2], perturbed [N, S, C, 6] or None) as NumPy, prefilled with -7"""
     N, Cn = params.shape[0], params.shape[1]
     ts = [_dev(model, params), _dev(model, count, torch.int32), _dev(model, start)]
-    out = torch.full((N, S, T, 2), -7.0, device=model.device)
-    pert = torch.full((N, S, Cn, 6), -7.0, device=model.device) if want_params else None
+    out_o, pert_o = _Out(model, (N, S, T, 2), guard), _Out(model, (N, S, Cn, 6), guard) if want_params else None
+    out, pert = out_o.t, pert_o.t if want_params else None
     torch.cuda.synchronize()
     rc = model._L.avae_lognormal_sample(model._h, _p(ts[0]), _p(ts[1]), _p(ts[2]), N, S, Cn, T, dt, seed, offset, scales[0],
                                         scales[1], scales[2], 1 if shift else 0, _p(out), _p(pert), _stream(model, stream))
     torch.cuda.synchronize()
     assert rc == 0, _err(model)
-    return out.cpu().numpy(), None if pert is None else pert.cpu().numpy()
+    return out_o.numpy(), None if pert is None else pert_o.numpy()
 
 
 def _fit(model, target, init, count, start, dt, n_iters=40, weights=LR.DEFAULT_WEIGHTS, tol=1e-9, free=None, bounds=None,
-         want=FIT_OUTPUTS, stream=None):
-    """avae_lognormal_fit -> dict of the NumPy outputs asked for (``params`` always), prefilled with -7"""
+         want=FIT_OUTPUTS, stream=None, guard=0):
+    """avae_lognormal_fit -> dict of the NumPy outputs asked for (``params`` always), prefilled with -7 (``bounds``: None or
+    (lo, hi), either of them None for NULL)"""
     N, T, Cn = target.shape[0], target.shape[1], init.shape[1]
     ts = [_dev(model, target), _dev(model, init), _dev(model, count, torch.int32), _dev(model, start)]
     fr = _dev(model, free, torch.uint8)
-    lo, hi = (None, None) if bounds is None else (_dev(model, np.asarray(b, dtype=np.float32)) for b in bounds)
+    lo, hi = (None, None) if bounds is None else (None if b is None else _dev(model, np.asarray(b, dtype=np.float32)) for b in bounds)
     dts = dict(params=torch.float32, loss0=torch.float64, loss=torch.float64, iterations=torch.int32, accepted=torch.int32,
                status=torch.int32)
-    out = {k: torch.full((N, Cn, 6) if k == "params" else (N,), -7, device=model.device, dtype=dts[k]) for k in want}
+    outs = {k: _Out(model, (N, Cn, 6) if k == "params" else (N,), guard, dts[k]) for k in want}
+    out = {k: v.t for k, v in outs.items()}
     torch.cuda.synchronize()
     rc = model._L.avae_lognormal_fit(model._h, _p(ts[0]), _p(ts[1]), _p(ts[2]), _p(ts[3]), N, Cn, T, dt, n_iters, weights[0],
                                      weights[1], tol, _p(fr), 1 if (fr is not None and fr.dim() == 3) else 0, _p(lo), _p(hi),
@@ -119,7 +139,7 @@ def _fit(model, target, init, count, start, dt, n_iters=40, weights=LR.DEFAULT_W
                                      _p(out.get("accepted")), _p(out.get("status")), _stream(model, stream))
     torch.cuda.synchronize()
     assert rc == 0, _err(model)
-    return {k: v.cpu().numpy() for k, v in out.items()}
+    return {k: v.numpy() for k, v in outs.items()}
 
 
 def _random_rows(N, Cn, seed):
@@ -459,3 +479,332 @@ def test_augment_end_to_end_into_strokes_to_motion(V):
     rows = model.strokes_to_motion(letters, basis, chain, StrokeCanvas(), fx["block_center"], fx["seed_pos"], orientation="seed")
     assert rows["params"].shape == (20, 147) and rows["image"].shape[0] == 20
     assert np.isfinite(rows["params"]).all() and np.isfinite(rows["image"]).all() and np.isfinite(rows["trajectory"]).all()
+
+
+# ================================================================================================ the second pass (HISTORY section R20)
+# 7. the fit inside its tile and component classes; 8. the exits of its loop; 9. the step's clips and the weights; 10. count NULL
+# and out of range; 11. the sampler's edges.  The cases and their seeds: tests/lognormal_cases.py; the conditions they lean on:
+# tests/test_lognormal_cpu.py.  Every pair is printed with its ratio; the worst ratio of a run is printed as it grows.
+_WORST = {"ratio": 0.0, "where": ""}
+
+
+def _pair(label, err, own):
+    """print a measured pair and assert the 4x rule (an exact restatement asks for an exact kernel)"""
+    ratio = err / own if own > 0 else (0.0 if err == 0 else np.inf)
+    if ratio > _WORST["ratio"]:
+        _WORST.update(ratio=ratio, where=label)
+    print("%s: kernel %.3e, restatement %.3e, ratio %.2f (bound 4x; worst so far %.2f at %s)"
+          % (label, err, own, ratio, _WORST["ratio"], _WORST["where"]))
+    assert err <= 4.0 * own, label
+
+
+def _path_err_at(params, count, ref_params, start, T, dt):
+    """``_path_err`` at the case's own T and dt"""
+    worst = 0.0
+    for n in range(len(params)):
+        a = LR.stroke(params[n, :count[n]], start[n], T, dt)[0]
+        b = LR.stroke(ref_params[n, :count[n]], start[n], T, dt)[0]
+        worst = max(worst, float(np.abs(a - b).max() / max(LR.extent(b), 1e-30)))
+    return worst
+
+
+def _fit_case(model, case, n_iters, count="case", rows=None, guard=0, **over):
+    opt = dict(tol=0.0)
+    opt.update(case["opt"])
+    opt.update(over)
+    rows = slice(None) if rows is None else list(rows)
+    free = opt.get("free")
+    if free is not None and np.asarray(free).ndim == 3:
+        free = np.asarray(free)[rows]
+    bounds = None if opt.get("lo") is None and opt.get("hi") is None else (opt.get("lo"), opt.get("hi"))
+    return _fit(model, case["target"][rows], case["init"][rows], case["count"][rows] if isinstance(count, str) else count,
+                case["start"][rows], case["dt"], n_iters=n_iters, weights=opt.get("weights", LR.DEFAULT_WEIGHTS), tol=opt["tol"],
+                free=free, bounds=bounds, guard=guard)
+
+
+def _check_against_refs(model, name, case, refs):
+    """The comparison rule at every try count of ``refs``: a clear decision margin, the restatement deciding as the definition
+    does, the integer outputs equal to the definition's, losses and the returned parameters' float64 path within 4x the
+    restatement's own error; zeros above count and a masked parameter's bits kept.  -> {n_iters: the kernel's outputs}"""
+    N, Cn, cnt = case["init"].shape[0], case["init"].shape[1], case["count"]
+    free = case["opt"].get("free")
+    out = {}
+    for it, (r64, r32) in refs.items():
+        assert LC.margin(r64) > 1e-3 and LC.decisions_agree(r64, r32)
+        got = out[it] = _fit_case(model, case, it)
+        for k in ("iterations", "accepted", "status"):
+            assert np.array_equal(got[k], r64[k]), (k, got[k], r64[k])
+        for k in ("loss0", "loss"):
+            _pair("fit %s, %d tries, %s" % (name, it, k), LR.rel_err(got[k], r64[k]), LR.rel_err(r32[k], r64[k]))
+        _pair("fit %s, %d tries, path / extent" % (name, it),
+              _path_err_at(got["params"], cnt, r64["params"], case["start"], case["T"], case["dt"]),
+              _path_err_at(r32["params"], cnt, r64["params"], case["start"], case["T"], case["dt"]))
+        for n in range(N):
+            assert not got["params"][n, cnt[n]:].any()
+            if free is not None:
+                fr = np.broadcast_to(free if free.ndim == 3 else free[None, None, :], (N, Cn, 6))[n, :cnt[n]] != 0
+                assert _same(got["params"][n, :cnt[n]][~fr], case["init"][n, :cnt[n]][~fr])
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ 7. tile and component classes
+@pytest.mark.parametrize("shape", LC.TILE_SHAPES, ids=["C%d-T%d" % s for s in LC.TILE_SHAPES])
+def test_fit_inside_the_tile_and_component_classes(V, shape):
+    """Two rows, ``tol = 0``, after 1 and 4 tries, with T below, at, one past and a multiple of the tile of the class (64 / 32 / 8
+    points at C <= 4 / 8 / 16), T = 2 and the limit 1024.  At T = 1 every component is still off at t = 0: the loss is exactly 0,
+    no try is accepted, and that is asserted as such."""
+    model = _model(V)
+    Cn, T = shape
+    case, refs = LC.tile_case(Cn, T)
+    got = _check_against_refs(model, "C = %d, T = %d" % shape, case, refs)
+    if T == 1:
+        for it in LC.TRIES:
+            g = got[it]
+            assert not g["loss"].any() and not g["loss0"].any() and _same(g["params"], case["init"])
+            assert (g["status"] == 1).all() and (g["iterations"] == it).all() and not g["accepted"].any()
+
+
+@pytest.mark.parametrize("name", sorted(LC.RAGGED_CASES))
+def test_fit_ragged_counts_in_the_smallest_and_widest_class(V, name):
+    """counts (4, 2, 1, 0) at C = 4, (12, 9, 5, 0) at C = 12, and a mask per row at C = 12 with counts (12, 9, 5)"""
+    case, refs = LC.ragged_case(name)
+    _check_against_refs(_model(V), name, case, refs)
+
+
+# ------------------------------------------------------------------------------------------------ 8. the exits of the loop
+@pytest.mark.parametrize("which", ("pivot", "x"))
+def test_fit_status_2_by_a_solve_that_fails(V, which):
+    """A finite D near the top of float32.  "pivot": D = 3e38 in row 1 of three; the amplitude overflows, loss0 is not finite, M is
+    NaN and every try ends at the first pivot (``LR._solve`` says so, tests/test_lognormal_cpu.py asserts it).  "x": one
+    component with only sigma free and D = 1e37; M is the 1 x 1 infinity, the pivot passes and the solution is not finite.  The
+    float64 definition does not overflow there, so the row is compared with the restatement: status 2 after 8 tries, none
+    accepted, the parameters init's bits, and the other rows bitwise the run without that row."""
+    model = _model(V)
+    case = LC.overflow_case() if which == "pivot" else LC.x_reject_case()
+    row = LC.OVERFLOW_ROW
+    free = case["opt"].get("free")
+    r32 = LR.fit_row(case["target"][row], case["init"][row], case["start"][row], case["dt"], n_iters=40, tol=case["opt"]["tol"],
+                     free=free, restated=True)
+    assert r32["solves"] == [which] * 8 and (r32["status"], r32["iterations"], r32["accepted"]) == (2, 8, 0)
+    got = _fit_case(model, case, 40)
+    print("fit solve failure (%s): status %s, tries %s, accepted %s, loss0 %s, loss %s" % (which, got["status"], got["iterations"],
+          got["accepted"], got["loss0"], got["loss"]))
+    assert (got["status"][row], got["iterations"][row], got["accepted"][row]) == (2, 8, 0)
+    assert _same(got["params"][row], case["init"][row])
+    assert not np.isfinite(got["loss0"][row]) and not np.isfinite(got["loss"][row])
+    assert not np.isfinite(r32["loss0"]) and not np.isfinite(r32["loss"])
+    others = [n for n in range(len(case["init"])) if n != row]
+    alone = _fit_case(model, case, 40, rows=others)
+    assert all(_same(alone[k], got[k][others]) for k in FIT_OUTPUTS)
+    assert np.isin(alone["status"], (0, 1)).all() and alone["accepted"].all()
+
+
+@pytest.mark.parametrize("name", sorted(LC.TOL_CASES))
+def test_fit_tol_ends_a_row_in_the_definitions_try(V, name):
+    """``tol`` > 0 on rows where definition and restatement end in the same try and every convergence decision has a margin
+    |(L - L(new)) - tol L| > 1e-3 tol L: tries, accepted steps and status equal the definition's"""
+    model = _model(V)
+    case, refs = LC.tol_case(name)
+    r64, r32 = refs[LC.TOL_TRIES]
+    tol = case["opt"]["tol"]
+    assert all(LC.conv_margin(t, tol) > 1e-3 for t in r64["tries"])
+    for k in ("iterations", "accepted", "status"):
+        assert np.array_equal(r32[k], r64[k])
+    assert (r64["status"] == 0).all() and (r64["iterations"] < LC.TOL_TRIES).all()
+    got = _fit_case(model, case, LC.TOL_TRIES)
+    print("fit %s: tries %s, accepted %s" % (name, got["iterations"], got["accepted"]))
+    for k in ("iterations", "accepted", "status"):
+        assert np.array_equal(got[k], r64[k]), (k, got[k], r64[k])
+    for k in ("loss0", "loss"):
+        _pair("fit %s, %s" % (name, k), LR.rel_err(got[k], r64[k]), LR.rel_err(r32[k], r64[k]))
+    _pair("fit %s, path / extent" % name,
+          _path_err_at(got["params"], case["count"], r64["params"], case["start"], case["T"], case["dt"]),
+          _path_err_at(r32["params"], case["count"], r64["params"], case["start"], case["T"], case["dt"]))
+
+
+def test_fit_with_zero_tries(V):
+    """``n_iters = 0``: status 1 (0 where count = 0), no try, the parameters init's bits, loss = loss0 that of init"""
+    model = _model(V)
+    case = LC.make(4, 3, 21, (3, 2, 1, 0))
+    r64, r32 = LC.run(case, 0, False), LC.run(case, 0, True)
+    got = _fit_case(model, case, 0)
+    assert got["status"].tolist() == [1, 1, 1, 0] == r64["status"].tolist()
+    assert not got["iterations"].any() and not got["accepted"].any()
+    init = case["init"].copy()
+    for n in range(4):
+        init[n, case["count"][n]:] = 0.0
+    assert _same(got["params"], init) and _same(got["loss"], got["loss0"])
+    _pair("fit, zero tries, loss0", LR.rel_err(got["loss0"], r64["loss0"]), LR.rel_err(r32["loss0"], r64["loss0"]))
+
+
+# ------------------------------------------------------------------------------------------------ 9. clips and weights
+@pytest.mark.parametrize("name", sorted(LC.CLIP_CASES))
+def test_fit_sigma_clip_without_bounds(V, name):
+    """An initial sigma of 0.002: within four tries a sigma of that row ends on the clip [1e-3, 3] in the definition and in the
+    restatement; the kernel returns the clip value's bits there"""
+    model = _model(V)
+    case, refs = LC.clip_case(name)
+    _, row, _, clip = LC.CLIP_CASES[name]
+    got = _check_against_refs(model, name, case, refs)
+    on64 = refs[4][0]["params"][row, :, 3] == clip
+    on32 = refs[4][1]["params"][row, :, 3] == np.float32(clip)
+    assert on64.any() and np.array_equal(on64, on32)
+    assert _same(got[4]["params"][row, on64, 3], np.full(int(on64.sum()), clip, dtype=np.float32))
+
+
+@pytest.mark.parametrize("name", sorted(LC.BOUND_CASES))
+def test_fit_one_bound_alone(V, name):
+    """``lo`` without ``hi`` and ``hi`` without ``lo``, each binding: where the definition's parameter sits on the bound the
+    kernel returns the bound's bits, and no moved parameter is beyond it"""
+    model = _model(V)
+    case, refs = LC.bound_case(name)
+    got = _check_against_refs(model, name, case, refs)
+    side = "lo" if "lo" in case["opt"] else "hi"
+    bound = np.asarray(case["opt"][side], dtype=np.float32)
+    on = np.isfinite(bound)[None, None, :] & (refs[4][0]["params"] == np.asarray(case["opt"][side], dtype=np.float64)[None, None, :])
+    assert on.any()
+    assert _same(got[4]["params"][on], np.broadcast_to(bound, on.shape)[on])
+    moved = got[4]["params"] != case["init"]
+    assert (got[4]["params"] >= bound if side == "lo" else got[4]["params"] <= bound)[moved].all()
+
+
+@pytest.mark.parametrize("w", LC.WEIGHTS, ids=["wp%g-wv%g" % w for w in LC.WEIGHTS])
+@pytest.mark.parametrize("shape", LC.WEIGHT_SHAPES, ids=["%dx%d" % s for s in LC.WEIGHT_SHAPES])
+def test_fit_weights(V, shape, w):
+    case, refs = LC.weight_case(shape[0], shape[1], w)
+    _check_against_refs(_model(V), "%dx%d weights %s" % (shape + (w,)), case, refs)
+
+
+@pytest.mark.parametrize("shape", LC.WEIGHT_SHAPES, ids=["%dx%d" % s for s in LC.WEIGHT_SHAPES])
+def test_fit_with_both_weights_zero(V, shape):
+    """the loss is 0 everywhere: no try is accepted, status 2 after 8 tries, the parameters init's bits"""
+    model = _model(V)
+    case = LC.make(shape[0], shape[1], 1000, weights=(0.0, 0.0))
+    got = _fit_case(model, case, 40, tol=1e-9)
+    r64 = LC.run(case, 40, False, tol=1e-9)
+    for k in ("iterations", "accepted", "status"):
+        assert np.array_equal(got[k], r64[k])
+    assert (got["status"] == 2).all() and (got["iterations"] == 8).all() and not got["accepted"].any()
+    assert not got["loss"].any() and not got["loss0"].any() and _same(got["params"], case["init"])
+
+
+# ------------------------------------------------------------------------------------------------ 10. count
+def _three_calls(model, params, count, start, target, T, dt, guard=0):
+    """eval, sample (shift_mean on and off) and four fit tries -> the list of every output"""
+    ev = _eval(model, params, count, start, T, dt, guard=guard)
+    sm = [_sample(model, params, count, start, T, dt, 2, 11, shift, guard=guard) for shift in (True, False)]
+    ft = _fit(model, target, params, count, start, dt, n_iters=4, tol=0.0, guard=guard)
+    return list(ev) + [a for pair in sm for a in pair] + [ft[k] for k in FIT_OUTPUTS]
+
+
+@pytest.mark.parametrize("Cn", (3, 6, 12))
+def test_a_null_count_is_count_c_everywhere(V, Cn):
+    model = _model(V)
+    case = LC.make(2, Cn, 1000, T=70)
+    full = _three_calls(model, case["init"], case["count"], case["start"], case["target"], 70, case["dt"])
+    null = _three_calls(model, case["init"], None, case["start"], case["target"], 70, case["dt"])
+    assert (case["count"] == Cn).all() and len(null) == len(full) == 12
+    assert all(_same(a, b) for a, b in zip(null, full))
+    assert np.abs(full[1]).max() > 0 and full[-3].any()                # (something moved, and tries were made)
+
+
+@pytest.mark.parametrize("Cn", (3, 6, 12))
+def test_counts_out_of_range_are_clamped(V, Cn):
+    """counts (-3, 0, C, C + 5) give the bits of (0, 0, C, C) in all three calls, and two guard rows of -7 before and behind every
+    output stay as they were"""
+    model = _model(V)
+    case = LC.make(4, Cn, 1000, T=70)
+    wild = np.array([-3, 0, Cn, Cn + 5], dtype=np.int32)
+    tame = np.array([0, 0, Cn, Cn], dtype=np.int32)
+    a = _three_calls(model, case["init"], wild, case["start"], case["target"], 70, case["dt"], guard=2)
+    b = _three_calls(model, case["init"], tame, case["start"], case["target"], 70, case["dt"], guard=2)
+    assert all(_same(x, y) for x, y in zip(a, b))
+    assert not a[-6][:2].any() and a[-6][2:].any() and a[-1].tolist()[:2] == [0, 0]      # params and status of the fit
+
+
+# ------------------------------------------------------------------------------------------------ 11. the sampler's edges
+@pytest.mark.parametrize("shape", LC.SAMPLE_EDGE_SHAPES, ids=["%dx%dx%dx%d" % s for s in LC.SAMPLE_EDGE_SHAPES])
+def test_sample_edges_against_the_definition(V, shape):
+    """T = 1024 (the whole of the staged stroke) with counts (16, 0, 9) and negative D; N = S = C = T = 1; one sample of an exact
+    two chunks.  shift_mean on and off; the count = 0 row with shift_mean is start minus the butterfly mean of start, about
+    3e-8 and not 0: the restatement's bits."""
+    model = _model(V)
+    N, S, Cn, T = shape
+    params, count, start, dt = LC.sample_edge(shape)
+    seed = 0x1234567855
+    for shift in (False, True):
+        r64 = LR.sample(params, count, start, T, dt, S, seed, shift_mean=shift)
+        r32 = LR.sample_restated(params, count, start, T, dt, S, seed, shift_mean=shift)
+        got = _sample(model, params, count, start, T, dt, S, seed, shift, guard=1)
+        for k, what in enumerate(("strokes", "perturbed")):
+            assert got[k].shape == r64[k].shape
+            _pair("sample edge %s shift_mean %s %s" % (shape, shift, what), LR.rel_err(got[k], r64[k]), LR.rel_err(r32[k], r64[k]))
+        ev = _eval(model, got[1].reshape(N * S, Cn, 6), np.repeat(count, S), np.repeat(start, S, axis=0), T, dt, velocity=False)[0]
+        ev = ev.reshape(N, S, T, 2)
+        if shift:
+            mean = np.stack([[LR.mean_restated(ev[n, s]) for s in range(S)] for n in range(N)])
+            assert _same(got[0], (ev - mean[:, :, None, :]).astype(np.float32))
+        else:
+            assert _same(got[0], ev)
+        for n in np.flatnonzero(count == 0):
+            assert _same(got[0][n], r32[0][n]) and not got[1][n].any()
+            if shift:
+                assert np.abs(got[0][n]).max() < 1e-6
+            else:
+                assert _same(got[0][n], np.broadcast_to(start[n], (S, T, 2)).copy())
+
+
+def test_sample_scales_and_a_seed_with_high_bits(V):
+    model = _model(V)
+    N, S, Cn, T, dt, scales = 2, 3, 4, 100, 0.01, (0.5, 1.0, 0.7)
+    params, start = _random_rows(N, Cn, 17), np.tile(START, (N, 1))
+    count = np.array([4, 3], dtype=np.int32)
+    r64 = LR.sample(params, count, start, T, dt, S, LC.HIGH_SEED, *scales, shift_mean=True)
+    r32 = LR.sample_restated(params, count, start, T, dt, S, LC.HIGH_SEED, *scales, shift_mean=True)
+    got = _sample(model, params, count, start, T, dt, S, LC.HIGH_SEED, True, scales=scales)
+    for k, what in enumerate(("strokes", "perturbed")):
+        _pair("sample scales %s, seed %#x, %s" % (scales, LC.HIGH_SEED, what), LR.rel_err(got[k], r64[k]), LR.rel_err(r32[k], r64[k]))
+    # the high word of the seed and each scale reach the draw
+    low = _sample(model, params, count, start, T, dt, S, LC.HIGH_SEED & 0xFFFFFFFF, True, scales=scales)
+    assert not np.array_equal(low[1][..., 0], got[1][..., 0])
+    default = _sample(model, params, count, start, T, dt, S, LC.HIGH_SEED, True)
+    for j in (0, 4, 5):
+        assert not np.array_equal(default[1][..., j], got[1][..., j])
+
+
+@pytest.mark.parametrize("shift", (False, True))
+def test_sample_a_nan_row_is_nan_and_alone(V, shift):
+    model = _model(V)
+    N, S, Cn, T, dt, seed = 4, 2, 3, 100, 0.01, 5
+    params, start, count = _random_rows(N, Cn, 23), np.tile(START, (N, 1)), np.array([3, 3, 2, 3], dtype=np.int32)
+    good = _sample(model, params, count, start, T, dt, S, seed, shift)
+    assert np.isfinite(good[0]).all()
+    bad_p, bad_s = params.copy(), start.copy()
+    bad_p[1, 2, 1] = np.nan
+    bad_p[2, 2, 3] = np.nan                               # beyond count: never read
+    bad_s[3, 0] = np.nan
+    got = _sample(model, bad_p, count, bad_s, T, dt, S, seed, shift)
+    assert np.isnan(got[0][1]).all() and np.isnan(got[0][3]).all()
+    assert _same(got[0][[0, 2]], good[0][[0, 2]]) and _same(got[1][[0, 2, 3]], good[1][[0, 2, 3]])
+
+
+def test_sample_at_the_last_row_offset(V):
+    """``row_offset = 2^32 - N``: the counter's first word is one short of wrapping in the last row"""
+    model = _model(V)
+    N, S, Cn, T, dt, seed = 3, 2, 4, 100, 0.01, 99
+    params, start, count = _random_rows(N, Cn, 29), np.tile(START, (N, 1)), np.array([4, 3, 4], dtype=np.int32)
+    off = 2 ** 32 - N
+    r64 = LR.sample(params, count, start, T, dt, S, seed, shift_mean=True, row_offset=off)
+    r32 = LR.sample_restated(params, count, start, T, dt, S, seed, shift_mean=True, row_offset=off)
+    got = _sample(model, params, count, start, T, dt, S, seed, True, offset=off)
+    for k, what in enumerate(("strokes", "perturbed")):
+        _pair("sample row_offset 2^32 - %d %s" % (N, what), LR.rel_err(got[k], r64[k]), LR.rel_err(r32[k], r64[k]))
+    part = _sample(model, params[1:], count[1:], start[1:], T, dt, S, seed, True, offset=off + 1)
+    assert _same(part[0], got[0][1:]) and _same(part[1], got[1][1:])
+    assert not np.array_equal(_sample(model, params, count, start, T, dt, S, seed, True)[1][..., 0], got[1][..., 0])
+    ts = [_dev(model, params), _dev(model, count, torch.int32), _dev(model, start)]
+    out = torch.full((N, S, T, 2), -7.0, device=model.device)
+    rc = model._L.avae_lognormal_sample(model._h, _p(ts[0]), _p(ts[1]), _p(ts[2]), N, S, Cn, T, dt, seed, off + 1, 0.2, 0.3, 0.1, 1,
+                                        _p(out), None, _stream(model))
+    torch.cuda.synchronize()
+    assert rc != 0 and "row_offset" in _err(model) and (out == -7).all()

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+import lognormal_cases as LC
 import lognormal_reference as LR
 from vae_assoc_amd import _args as M
 from vae_assoc_amd.lognormal import balanced_sample_counts, lognormal_initial_guess
@@ -136,6 +137,132 @@ def test_step_cases_have_a_decision_margin():
         r = LR.run_step_case(case, variant, 4, False)
         assert min(LR.margins(t) for t in r["tries"]) > 1e-3, name
         assert (r["iterations"][case["count"] > 0] == 4).all() and (r["iterations"][case["count"] == 0] == 0).all()
+
+
+# ------------------------------------------------------------------------------------------------ the second pass's conditions
+def _clear_and_agreed(case, refs):
+    for it, (r64, r32) in refs.items():
+        assert LC.margin(r64) > 1e-3 and LC.decisions_agree(r64, r32), it
+        assert np.array_equal(r64["iterations"], r32["iterations"]) and np.array_equal(r64["accepted"], r32["accepted"])
+        assert (r64["iterations"] == np.where(case["count"] > 0, it, 0)).all()
+
+
+@pytest.mark.parametrize("C", (3, 6, 9, 12, 15))
+def test_tile_cases_have_a_decision_margin_and_an_agreeing_restatement(C):
+    """every (C, T) of LC.TILE_SHAPES, after 1 and 4 tries; at T = 1 the loss is exactly 0 and nothing is accepted"""
+    shapes = [s for s in LC.TILE_SHAPES if s[0] == C]
+    assert len(shapes) in (6, 7) and len(LC.TILE_SHAPES) == 33
+    for _, T in shapes:
+        case, refs = LC.tile_case(C, T)
+        assert case["target"].shape == (2, T, 2) and case["dt"] == float(np.float32(0.01 if T == 1 else 1.0 / (T - 1)))
+        _clear_and_agreed(case, refs)
+        if T == 1:
+            for it in LC.TRIES:
+                for r in refs[it]:
+                    assert not r["loss"].any() and not r["loss0"].any() and not r["accepted"].any() and (r["status"] == 1).all()
+                    assert np.array_equal(r["params"], case["init"].astype(np.float64))
+
+
+def test_step_case_keeps_its_bits_at_the_default_t_and_dt():
+    a, b = LR.step_case(3, 3, 1000), LR.step_case(3, 3, 1000, None, LR.T_CASE, LR.DT_CASE)
+    assert all(np.array_equal(a[k], b[k]) for k in a) and a["target"].shape == (3, LR.T_CASE, 2)
+    assert LR.step_case(2, 3, 1000, T=17, dt=0.05)["target"].shape == (2, 17, 2)
+
+
+@pytest.mark.parametrize("name", sorted(LC.RAGGED_CASES))
+def test_ragged_cases_have_a_decision_margin(name):
+    case, refs = LC.ragged_case(name)
+    _clear_and_agreed(case, refs)
+    assert (case["count"] < case["init"].shape[1]).any() and case["init"].shape[1] in (4, 12)
+    if name == "per-row-12":
+        assert case["opt"]["free"].shape == (3, 12, 6) and 0 < case["opt"]["free"].mean() < 1
+
+
+def test_overflow_rows_take_one_rejection_each():
+    """D = 3e38: every try of the restatement ends at a pivot that is not > 0; one component, only sigma free, D = 1e37: every
+    pivot passes and the solution is not finite.  Status 2 after 8 tries, none accepted, no finite loss; the float64 definition
+    does not overflow on either row (which is why those rows are compared with the restatement)."""
+    for case, which in ((LC.overflow_case(), "pivot"), (LC.x_reject_case(), "x")):
+        n = LC.OVERFLOW_ROW
+        kw = dict(n_iters=40, tol=case["opt"]["tol"], free=case["opt"].get("free"))
+        with np.errstate(all="ignore"):
+            r32 = LR.fit_row(case["target"][n], case["init"][n], case["start"][n], case["dt"], restated=True, **kw)
+        r64 = LR.fit_row(case["target"][n], case["init"][n], case["start"][n], case["dt"], **kw)
+        assert np.isfinite(case["init"]).all()
+        assert r32["solves"] == [which] * 8 and all(ln is None for _, ln in r32["tries"])
+        assert (r32["status"], r32["iterations"], r32["accepted"]) == (2, 8, 0)
+        assert not np.isfinite(r32["loss0"]) and not np.isfinite(r32["loss"])
+        assert np.array_equal(r32["params"], case["init"][n])
+        assert np.isfinite(r64["loss0"]) and set(r64["solves"]) == {"ok"}
+
+
+def test_solve_says_which_rejection_it_took():
+    why = []
+    assert LR._solve(np.array([[4.0, 2.0], [2.0, 1.0]]), np.ones(2), why) is None and why == ["pivot"]
+    assert LR._solve(np.array([[np.inf]]), np.array([np.inf]), why) is None and why == ["pivot", "x"]
+    assert np.allclose(LR._solve(np.array([[4.0, 2.0], [2.0, 3.0]]), np.array([2.0, 1.0]), why), [0.5, 0.0]) and why[-1] == "ok"
+    assert LR._solve(np.array([[np.nan]]), np.ones(1)) is None
+
+
+@pytest.mark.parametrize("name", sorted(LC.TOL_CASES))
+def test_tol_cases_end_in_the_same_try_with_a_convergence_margin(name):
+    case, refs = LC.tol_case(name)
+    r64, r32 = refs[LC.TOL_TRIES]
+    tol = case["opt"]["tol"]
+    for k in ("iterations", "accepted", "status"):
+        assert np.array_equal(r64[k], r32[k]), k
+    assert (r64["status"] == 0).all() and (r64["iterations"] < LC.TOL_TRIES).all()
+    for n, tries in enumerate(r64["tries"]):
+        print("%s row %d: %d tries, convergence margin %.3f, accept margin %.5f" % (name, n, len(tries), LC.conv_margin(tries, tol),
+                                                                                   LR.margins(tries)))
+        assert LC.conv_margin(tries, tol) > 1e-3
+        l, ln = tries[-1]
+        assert ln < l and l - ln < tol * l                                      # the last try is the one that converged
+        if name in LC.TOL_BETWEEN:                                              # tol L(new) <= L - L(new) < tol L, both clearly
+            assert l - ln > 1.01 * tol * ln and l - ln < 0.99 * tol * l
+            assert all((x - y) > 1.01 * tol * y for x, y in tries if y is not None and y < x)
+    assert tol <= 1e-2 or name.startswith("tol-0.5")
+
+
+def test_clip_bound_and_weight_cases():
+    for name, (_, row, _, clip) in LC.CLIP_CASES.items():
+        case, refs = LC.clip_case(name)
+        _clear_and_agreed(case, refs)
+        on64, on32 = refs[4][0]["params"][row, :, 3] == clip, refs[4][1]["params"][row, :, 3] == np.float32(clip)
+        assert on64.any() and np.array_equal(on64, on32), name
+    for name in LC.BOUND_CASES:
+        case, refs = LC.bound_case(name)
+        _clear_and_agreed(case, refs)
+        side = "lo" if "lo" in case["opt"] else "hi"
+        assert (side == "lo") == ("hi" not in case["opt"])
+        assert (refs[4][0]["params"] == np.asarray(case["opt"][side])[None, None, :]).any(), name      # the bound binds
+    for N, C in LC.WEIGHT_SHAPES:
+        for w in LC.WEIGHTS:
+            case, refs = LC.weight_case(N, C, w)
+            _clear_and_agreed(case, refs)
+        for restated in (False, True):
+            r = LC.run(LC.make(N, C, 1000, weights=(0.0, 0.0)), 40, restated, tol=1e-9)
+            assert (r["status"] == 2).all() and (r["iterations"] == 8).all() and not r["accepted"].any() and not r["loss"].any()
+
+
+def test_sampler_edges_in_the_reference():
+    """what tests/test_gpu_lognormal.py section 11 leans on: the stream at row_offset = 2^32 - N, a count = 0 row under shift_mean
+    (start minus the butterfly mean of start: tiny, not 0), and T = 1"""
+    N = 3
+    off = 2 ** 32 - N
+    w = LR.words(99, N, 2, 4, row_offset=off)
+    assert np.array_equal(w[1:], LR.words(99, N - 1, 2, 4, row_offset=off + 1)) and not np.array_equal(w, LR.words(99, N, 2, 4))
+    for shape in LC.SAMPLE_EDGE_SHAPES:
+        params, count, start, dt = LC.sample_edge(shape)
+        Nn, S, C, T = shape
+        for shift in (False, True):
+            a = LR.sample(params, count, start, T, dt, S, 7, shift_mean=shift)
+            b = LR.sample_restated(params, count, start, T, dt, S, 7, shift_mean=shift)
+            assert a[0].shape == (Nn, S, T, 2) and np.isfinite(a[0]).all() and np.isfinite(b[0]).all()
+            assert LR.rel_err(b[0], a[0]) < 1e-4
+            for n in np.flatnonzero(count == 0):
+                assert np.abs(b[0][n]).max() < 1e-6 if shift else np.array_equal(b[0][n], np.broadcast_to(start[n], (S, T, 2)))
+    assert (LC.sample_edge(LC.SAMPLE_EDGE_SHAPES[0])[0][..., 0] < 0).any()
 
 
 # ------------------------------------------------------------------------------------------------ the validators
