@@ -979,6 +979,52 @@ int avae_lognormal_fit(avae_handle* h, const float* target_dev, const float* ini
                        float* params_dev, double* loss0_dev, double* loss_dev, int32_t* iterations_dev, int32_t* accepted_dev,
                        int32_t* status_dev, void* stream);
 
+/* ---- joint-trajectory synthesis: batched iLQR on a double-integrator joint model.  The reference builds its
+ * smooth joint-modality rows by taking the point-by-point IK solution as a first guess and running 25 iLQR iterations that trade
+ * Cartesian tracking against control effort (BaxterWriter.derive_ilqr_trajectory, baxter_writer.py:106-145).  This call is the
+ * project's own statement of that solver -- Gauss-Newton linearisation of the tracking cost, a Riccati recursion regularised on the
+ * control, full steps accepted or rejected by the cost -- not a bit copy of it.  Dense device fp32 everywhere but cost0_dev /
+ * cost_dev (double) and iterations_dev / accepted_dev / status_dev (int32).  The chain is avae_motion_fk's; p(q) is the tip of
+ * avae_motion_pose's walk, J_v the linear rows of its Jacobian.
+ *   Row r has states x_t = (q_t, v_t), t < T, and controls u_t, t < T - 1:  q_(t+1) = q_t + dt v_t,  v_(t+1) = v_t + dt u_t,
+ *   x_0 = (init[r][0], 0).  The first controls:  v0_0 = 0,  v0_t = (init_t - init_(t-1)) / dt,  u_t = (v0_(t+1) - v0_t) / dt.
+ *   The cost  J = sum_t |w (p(q_t) - path_t)|^2 + sum_(t < T-1) u_t^T S u_t + wl sum_t sum_j max(0, q_tj - hi_j, lo_j - q_tj)^2,
+ *   w = track_w[3] (host memory),  S = R E^T E with effort_dev = E [D][D], S = R I with NULL;  the limit term only with
+ *   limits_dev [D][2] and limit_weight = wl > 0.
+ *   A try at the damping lam:  l_q = 2 J_v^T w^2 e (+ 2 wl viol),  l_qq = 2 J_v^T w^2 J_v (+ 2 wl on violated diagonals),
+ *   l_u = 2 S u,  l_uu = 2 S (no second derivatives of the kinematics);  backwards from V_x = l_x(T-1), V_xx = l_xx(T-1):
+ *     Q_x = l_x + A^T V_x,  Q_u = l_u + B^T V_x,  Q_xx = l_xx + A^T V_xx A,  Q_ux = B^T V_xx A,  Q_uu = l_uu + B^T V_xx B + lam I,
+ *     k = -Q_uu^-1 Q_u,  K = -Q_uu^-1 Q_ux  (Cholesky; a pivot not > 0 or a non-finite gain rejects the try without a rollout),
+ *     V_x = Q_x + K^T Q_uu k + K^T Q_u + Q_ux^T k,   V_xx = Q_xx + K^T Q_uu K + K^T Q_ux + Q_ux^T K, symmetrised;
+ *   forwards  u'_t = u_t + k_t + K_t (x'_t - x_t), a full step.  J' < J accepts the try: lam = max(lam / factor, lam_min), and the
+ *   row ends with status 0 when J - J' < tol J (strict: tol = 0 never stops).  Otherwise lam = lam factor and the trajectory
+ *   stays; the row ends when lam > lam_max, with status 0 if a try was ever accepted and status 2 if none was.  Status 1: n_iters
+ *   tries made.  T = 1: no controls, traj = init[0], 0 tries, status 0, cost = cost0.  Status 3: a non-finite path point, init
+ *   value or (used) limit: that row's traj, controls, cost0, cost and track_rmse are NaN, 0 tries, and nothing else is touched.
+ *   The walk, the Jacobian, l_q and l_qq are fp32 in avae_motion_pose's order (its sines and cosines taken in double on the
+ *   float angle and rounded once, so that the bits do not depend on a math library's choice within its ulp); J, the whole value
+ *   recursion, the Cholesky, the gains' formation and the rollout are double; the stored gains, traj and controls are rounded
+ *   once to float.  csrc/avae_track.h writes every operation and the order of every sum down.
+ *   Outputs: traj [rows][T][D] (required); controls [rows][T-1][D], cost0 (J of the first trajectory), cost, track_rmse
+ *   (sqrt(mean_t |p(q_t) - path_t|^2) of the returned trajectory), iterations (tries made), accepted, status: each may be NULL.
+ *   workspace_dev (8-byte aligned) holds the gains and the row's trajectories: avae_motion_track_plan gives its size,
+ *   rows * roundup(T (10 D^2 + 58 D), 256) bytes (host only, no handle, works without a GPU; its message goes to
+ *   avae_last_error(NULL)).  Its contents after the call are unspecified.
+ * rows == 0 is a no-op.  Errors (message in avae_last_error, nothing launched): rows < 0, D outside [1, 16], T outside [1, 1024],
+ * dt, factor - 1, lam0 or lam_min not > 0, lam_max < lam0, a track weight, R, limit_weight or tol negative or not finite, n_iters
+ * outside [0, 1000], workspace_bytes below the plan's, a NULL required pointer.
+ * One launch, no atomics, no scratch memory, nothing of the handle is read or written: a row's outputs are a pure function of its
+ * bits and the arguments -- the same alone or among other rows, on any stream, on repetition, whichever optional outputs are asked
+ * for and however large the workspace -- and the call works on any replica and inside avae_use_averaged. */
+int avae_motion_track_plan(int32_t rows, int32_t T, int32_t D, size_t* workspace_bytes);
+int avae_motion_track(avae_handle* h, const float* path_dev, const float* init_dev, int32_t rows, int32_t T, int32_t D,
+                      const float* frames_dev, const float* axes_dev, float dt, const float* track_w, float R,
+                      const float* effort_dev, const float* limits_dev, float limit_weight,
+                      int32_t n_iters, double lam0, double factor, double lam_min, double lam_max, double tol,
+                      void* workspace_dev, size_t workspace_bytes,
+                      float* traj_dev, float* controls_dev, double* cost0_dev, double* cost_dev, float* track_rmse_dev,
+                      int32_t* iterations_dev, int32_t* accepted_dev, int32_t* status_dev, void* stream);
+
 /* ---- black-box search around a cost: batched PI-BB / CEM iterations on the device.  The reference refines a
  * predicted motion by drawing rollouts from a Gaussian, pricing each and refitting the Gaussian to the cost-weighted rollouts
  * (pygcem.py:28-151, driven from baxter_vae_assoc_writer.py:259-342).  Here P such searches ("problems") advance at once: problem p

@@ -672,6 +672,13 @@ def motion_ik_args(path, chain, seed, orientation, n_iters, tol, rot_tol, dampin
         if tuple(o.shape) not in ((3, 3), (N, 3, 3)):
             raise ValueError("orientation must be None, 'seed', [3, 3] or [%d, 3, 3], got shape %s" % (N, tuple(o.shape)))
         orient = o.to(device=device, dtype=torch.float32).reshape(-1, 3, 3).contiguous()
+    return p, frames, axes, s, orient, _device_limits(chain, limits, device), opts, was_np
+
+
+def _device_limits(chain, limits, device):
+    """``limits``: True (the chain's own, if every joint has them), None / False or [n_dof, 2] -> float32 tensor on ``device``
+    (cached on the chain) or None"""
+    D = chain.n_dof
     lim = None
     if limits is True:
         lim = chain.limits
@@ -684,7 +691,7 @@ def motion_ik_args(path, chain, seed, orientation, n_iters, tol, rot_tol, dampin
         if key not in chain._cache:
             chain._cache[key] = to_device32(lim, device)
         lim = chain._cache[key]
-    return p, frames, axes, s, orient, lim, opts, was_np
+    return lim
 
 
 IK_OPTION_NAMES = ("orientation", "n_iters", "tol", "rot_tol", "damping", "max_step", "limits")
@@ -737,6 +744,91 @@ def refine_pen_path_args(basis, chain, canvas, n_rollouts, options, widths, imag
     ik_options(ik["n_iters"], ik["tol"], ik["rot_tol"], ik["damping"], ik["max_step"])
     search = {("tol" if k == "tol_search" else k): v for k, v in rest.items()}
     return ik, search
+
+
+# ---------------------------------------------------------------------------------------------------- iLQR trajectory synthesis
+TRACK_MAX_ITERS = _capi.TRACK_MAX_ITERS
+TRACK_FACTOR, TRACK_LAM_MIN, TRACK_LAM_MAX = 10.0, 1e-6, 1e6           # the damping's schedule: motion_track does not expose it
+TRACK_WORKSPACE_BYTES = 512 << 20                                      # the bound of motion_track's workspace (one row at least)
+TRACK_DEFAULTS = dict(dt=0.01, track_weights=(10.0, 10.0, 50.0), effort_weight=0.01, effort=None, limits=True, limit_weight=0.0,
+                      n_iters=25, lam0=1.0, tol=1e-6)
+TRACK_OPTION_NAMES = tuple(TRACK_DEFAULTS)
+SOLVERS = ("ik", "ilqr")
+
+
+def track_options(dt=0.01, track_weights=(10.0, 10.0, 50.0), effort_weight=0.01, limit_weight=0.0, n_iters=25, lam0=1.0, tol=1e-6):
+    """The solver options of ``motion_track`` checked -> (dt, (w0, w1, w2), effort_weight, limit_weight, n_iters, lam0, tol), the
+    first four as the float32 values the kernel uses.  The ranges are avae_motion_track's."""
+    dt = _ln_number(dt, "dt", True)
+    try:
+        w = tuple(track_weights)
+    except TypeError:
+        w = ()
+    if len(w) != 3:
+        raise ValueError("track_weights must be three numbers >= 0, got %r" % (track_weights,))
+    w = tuple(_ln_number(v, "track_weights[%d]" % i, False) for i, v in enumerate(w))
+    R = _ln_number(effort_weight, "effort_weight", False)
+    wl = _ln_number(limit_weight, "limit_weight", False)
+    n_iters = as_int(n_iters, "n_iters", 0, TRACK_MAX_ITERS)
+    if not _is_number(lam0) or not TRACK_LAM_MIN <= float(lam0) <= TRACK_LAM_MAX:
+        raise ValueError("lam0 must be a number in [%g, %g], got %r" % (TRACK_LAM_MIN, TRACK_LAM_MAX, lam0))
+    if not _is_number(tol) or not np.isfinite(tol) or tol < 0:
+        raise ValueError("tol must be a finite number >= 0, got %r" % (tol,))
+    return dt, w, R, wl, n_iters, float(lam0), float(tol)
+
+
+def split_track_options(options):
+    """``track_options`` of a composed call (None or a dict) -> motion_track's options with their defaults filled in; an unknown
+    key is refused"""
+    if options is None:
+        options = {}
+    if not isinstance(options, dict):
+        raise ValueError("track_options must be None or a dict, got %r" % (type(options).__name__,))
+    extra = set(options) - set(TRACK_OPTION_NAMES)
+    if extra:
+        raise ValueError("unknown option(s) %s (motion_track takes %s)" % (", ".join(sorted(map(str, extra))),
+                                                                          ", ".join(TRACK_OPTION_NAMES)))
+    return dict(TRACK_DEFAULTS, **options)
+
+
+def check_solver(solver, options):
+    """``solver`` and ``track_options`` of ``strokes_to_motion`` / ``refine_pen_path`` -> motion_track's options (checked) under
+    'ilqr', None under 'ik'"""
+    if solver not in SOLVERS:
+        raise ValueError("solver must be 'ik' or 'ilqr', got %r" % (solver,))
+    if solver == "ik":
+        if options is not None:
+            raise ValueError("track_options goes with solver='ilqr'")
+        return None
+    tr = split_track_options(options)
+    track_options(tr["dt"], tr["track_weights"], tr["effort_weight"], tr["limit_weight"], tr["n_iters"], tr["lam0"], tr["tol"])
+    return tr
+
+
+def track_rows_per_call(T, D):
+    """rows one avae_motion_track call takes under ``TRACK_WORKSPACE_BYTES`` (the plan's bytes per row: avae_motion_track_plan)"""
+    per_row = (T * (10 * D * D + 58 * D) + 255) // 256 * 256
+    return max(1, TRACK_WORKSPACE_BYTES // per_row), per_row
+
+
+def motion_track_args(path, chain, init, dt, track_weights, effort_weight, effort, limits, limit_weight, n_iters, lam0, tol, device):
+    """The arguments of ``motion_track`` but the first guess's own -> (path [N, T, 3], frames, axes, init [N, T, n_dof] or None,
+    effort [n_dof, n_dof] or None, limits [n_dof, 2] or None, options, was_numpy)."""
+    frames, axes = chain_matrices(chain, device)
+    D = chain.n_dof
+    p, was_np = dev_block3(path, (None, 3), device, "path")
+    N, T = int(p.shape[0]), int(p.shape[1])
+    if not 1 <= T <= _capi.MOTION_MAX_POINTS:
+        raise ValueError("path must hold 1 to %d points, got %d" % (_capi.MOTION_MAX_POINTS, T))
+    opts = track_options(dt, track_weights, effort_weight, limit_weight, n_iters, lam0, tol)
+    q0 = None if init is None else dev_block3(init, (T, D), device, "init", rows=N)[0]
+    E = None
+    if effort is not None:
+        E = effort if torch.is_tensor(effort) else torch.as_tensor(np.asarray(effort, dtype=np.float32))
+        if tuple(E.shape) != (D, D) or not bool(torch.isfinite(E.to(torch.float32)).all()):
+            raise ValueError("effort must be a finite [%d, %d] matrix, got shape %s" % (D, D, tuple(E.shape)))
+        E = E.to(device=device, dtype=torch.float32).contiguous()
+    return p, frames, axes, q0, E, _device_limits(chain, limits, device), opts, was_np
 
 
 # ---------------------------------------------------------------------------------------------------- sigma-lognormal strokes

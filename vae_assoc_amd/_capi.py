@@ -28,6 +28,7 @@ MOTION_MAX_DOF, MOTION_MAX_KB, MOTION_MAX_POINTS, MOTION_MAX_ANCHORS = 16, 64, 1
 RENDER_MAX_SIZE, RENDER_SUPERSAMPLES = 64, (1, 2, 4, 8)
 IK_MAX_ITERS = 1000
 LOGNORMAL_MAX_COMPONENTS, LOGNORMAL_MAX_POINTS, LOGNORMAL_MAX_ITERS = 16, 1024, 10000
+TRACK_MAX_ITERS = 1000
 
 ACT_IDS = {"identity": 0, "relu": 1, "softplus": 2, "sigmoid": 3, "tanh": 4}
 DTYPE_IDS = {"fp32": 0, "f32": 0, "float32": 0, "bf16": 1, "bfloat16": 1}
@@ -56,6 +57,7 @@ SYMBOLS = [
     "avae_motion_fk", "avae_stroke_render",
     "avae_motion_pose", "avae_motion_ik",
     "avae_lognormal_eval", "avae_lognormal_sample", "avae_lognormal_fit",
+    "avae_motion_track", "avae_motion_track_plan",
     "avae_search_sample", "avae_search_update",
     "avae_synchronize", "avae_timing_enable", "avae_timing_report", "avae_debug_fetch", "avae_comm_allreduce",
 ]
@@ -203,6 +205,10 @@ def lib():
                                                 C.c_float, C.c_float, i32, vp, vp, vp]
             L.avae_lognormal_fit.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, C.c_float, i32, C.c_double, C.c_double, C.c_double,
                                              vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+            L.avae_motion_track_plan.argtypes = [i32, i32, i32, C.POINTER(sz)]
+            L.avae_motion_track.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, C.c_float, C.POINTER(C.c_float), C.c_float, vp, vp,
+                                            C.c_float, i32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, vp, sz,
+                                            vp, vp, vp, vp, vp, vp, vp, vp, vp]
             L.avae_search_sample.argtypes =[vp, vp, vp, i32, i32, i32, C.c_uint64, i32, C.c_int64, vp, vp, i32, i32, vp, vp]
             L.avae_search_update.argtypes = [vp, vp, vp, i32, i32, i32, C.POINTER(SearchOptions), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
             L.avae_save.argtypes = [vp, C.c_char_p]

@@ -8,6 +8,7 @@
 #include "avae_render.h"
 #include "avae_ik.h"
 #include "avae_lognormal.h"
+#include "avae_track.h"
 #include "avae_search.h"
 #include "avae_gmm.h"
 #include "avae_embed.h"
@@ -4982,6 +4983,68 @@ int avae_lognormal_fit(avae_handle* h, const float* target_dev, const float* ini
         a.rows = rows; a.C = C; a.T = T; a.n_iters = n_iters; a.free_per_row = free_dev && free_per_row ? 1 : 0;
         hipStream_t s = on_stream(h, stream);
         timed_launch(h, s, "lognormal_fit", [&] { launch_lognormal_fit(a, s); });
+    });
+}
+
+// ---- joint-trajectory synthesis by iLQR (include/avae.h, avae_track.h)
+static void check_track_shape(const std::string& w, int32_t rows, int32_t T, int32_t D) {
+    check_rows(w, rows, "rows");
+    check_range(w, "T", T, 1, kTrackMaxT);
+    check_range(w, "D", D, 1, kTrackMaxD);
+}
+
+int avae_motion_track_plan(int32_t rows, int32_t T, int32_t D, size_t* workspace_bytes) {
+    try {
+        const std::string w = "avae_motion_track_plan";
+        check_track_shape(w, rows, T, D);
+        need(w, workspace_bytes, "workspace_bytes");
+        *workspace_bytes = (size_t)rows * track_row_bytes(T, D);
+        return 0;
+    } catch (const std::exception& e) { g_create_error = e.what(); return 2; }
+}
+
+int avae_motion_track(avae_handle* h, const float* path_dev, const float* init_dev, int32_t rows, int32_t T, int32_t D,
+                      const float* frames_dev, const float* axes_dev, float dt, const float* track_w, float R,
+                      const float* effort_dev, const float* limits_dev, float limit_weight,
+                      int32_t n_iters, double lam0, double factor, double lam_min, double lam_max, double tol,
+                      void* workspace_dev, size_t workspace_bytes,
+                      float* traj_dev, float* controls_dev, double* cost0_dev, double* cost_dev, float* track_rmse_dev,
+                      int32_t* iterations_dev, int32_t* accepted_dev, int32_t* status_dev, void* stream) {
+    return guarded(h, [&] {
+        const std::string w = "avae_motion_track";
+        check_track_shape(w, rows, T, D);
+        check_range(w, "n_iters", n_iters, 0, kTrackMaxIters);
+        check_finite(w, "dt", dt, true);
+        need(w, track_w, "track_w");
+        for (int i = 0; i < 3; ++i) check_finite(w, "track_w", track_w[i], false);
+        check_finite(w, "R", R, false);
+        check_finite(w, "limit_weight", limit_weight, false);
+        check_finite(w, "lam0", lam0, true);
+        check_finite(w, "factor - 1", factor - 1.0, true);
+        check_finite(w, "lam_min", lam_min, true);
+        if (!std::isfinite(lam_max) || lam_max < lam0) throw Err(w + ": lam_max must be finite and >= lam0");
+        check_finite(w, "tol", tol, false);
+        need(w, path_dev, "path_dev"); need(w, init_dev, "init_dev"); need(w, frames_dev, "frames_dev"); need(w, axes_dev, "axes_dev");
+        need(w, traj_dev, "traj_dev");
+        if (rows == 0) return;
+        const size_t row_bytes = track_row_bytes(T, D);
+        need(w, workspace_dev, "workspace_dev");
+        if (workspace_bytes < (size_t)rows * row_bytes)
+            throw Err(w + ": workspace_bytes = " + std::to_string(workspace_bytes) + " is below the " +
+                      std::to_string((size_t)rows * row_bytes) + " bytes avae_motion_track_plan gives");
+        if (reinterpret_cast<uintptr_t>(workspace_dev) % 8 != 0) throw Err(w + ": workspace_dev must be aligned to 8 bytes");
+        TrackArgs a = zeroed<TrackArgs>();
+        a.path = path_dev; a.init = init_dev; a.frames = frames_dev; a.axes = axes_dev; a.effort = effort_dev;
+        a.limits = limit_weight > 0.0f ? limits_dev : nullptr;                                       // (limits nobody reads)
+        a.workspace = static_cast<unsigned char*>(workspace_dev);
+        a.traj = traj_dev; a.controls = controls_dev; a.cost0 = cost0_dev; a.cost = cost_dev; a.rmse = track_rmse_dev;
+        a.iterations = iterations_dev; a.accepted = accepted_dev; a.status = status_dev;
+        a.lam0 = lam0; a.factor = factor; a.lam_min = lam_min; a.lam_max = lam_max; a.tol = tol;
+        a.row_bytes = row_bytes;
+        a.dt = dt; a.w[0] = track_w[0]; a.w[1] = track_w[1]; a.w[2] = track_w[2]; a.R = R; a.limit_weight = limit_weight;
+        a.rows = rows; a.T = T; a.D = D; a.n_iters = n_iters;
+        hipStream_t s = on_stream(h, stream);
+        timed_launch(h, s, "motion_track", [&] { launch_motion_track(a, s); });
     });
 }
 

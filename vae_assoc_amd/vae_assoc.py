@@ -36,7 +36,8 @@ from ._args import (SEARCH_STATE_KEYS, _is_pair, _same_joints, agg_args, canvas_
                     lognormal_eval_args, lognormal_fit_args, lognormal_sample_options, motion_eval_args,
                     motion_fit_args, motion_fk_args, motion_ik_args, motion_matrices, motion_moments_args, motion_pose_args,
                     predict_motion_args, prior_arrays, refine_motion_args, refine_pen_path_args, render_args, search_args,
-                    strokes_to_motion_args, topk_args, writing_cost_args)      # (the validators are part of this module's surface)
+                    strokes_to_motion_args, topk_args, writing_cost_args,      # (the validators are part of this module's surface)
+                    check_solver, motion_track_args, track_rows_per_call, TRACK_FACTOR, TRACK_LAM_MAX, TRACK_LAM_MIN)
 from ._marshal import (as_index, corruption_fields, ema_fields, ema_kwargs, grad_clip_fields, grad_clip_kwargs, dev_array, dev_block3, dev_dense, dev_dense3, dev_flags, dev_inputs, dev_modalities, dev_row_args,  # noqa: F401
                        ld_of, ptr, schedule_kwargs, schedule_struct, to_device32)
 from ._marshal import cyclical, exponential_decay, linear_warmup  # noqa: F401  (schedule helpers, part of this module's surface)
@@ -1699,32 +1700,117 @@ class AssocVariationalAutoEncoder(object):
         conv = self._like_input(was_np)
         return {k: None if v is None else conv(v) for k, v in self._motion_ik(p, frames, axes, s, orient, lim, opts).items()}
 
-    def strokes_to_motion(self, strokes, basis, chain, canvas, center, seed, height=0.0, **ik_options):
+    # ------------------------------------------------------------------ iLQR trajectory synthesis
+    _track_chunk = None        # rows one avae_motion_track call takes; None: what fits the workspace bound (track_rows_per_call)
+
+    def _motion_track(self, p, frames, axes, q0, E, lim, opts):
+        """avae_motion_track on device tensors -> dict of device tensors.  Rows go in chunks of ``track_rows_per_call`` rows, so
+        the workspace stays below ``_args.TRACK_WORKSPACE_BYTES`` (512 MiB) or one row's bytes (rows are independent: the chunk
+        changes no bit)."""
+        N, T, D = int(q0.shape[0]), int(q0.shape[1]), int(q0.shape[2])
+        dt, w, R, wl, n_iters, lam0, tol = opts
+        chunk, per_row = track_rows_per_call(T, D)
+        if self._track_chunk is not None:
+            chunk = max(1, min(chunk, int(self._track_chunk)))
+        traj = torch.empty((N, T, D), dtype=torch.float32, device=self.device)
+        ctrl = torch.empty((N, T - 1, D), dtype=torch.float32, device=self.device)
+        c0, c1 = (torch.empty((N,), dtype=torch.float64, device=self.device) for _ in range(2))
+        rm = torch.empty((N,), dtype=torch.float32, device=self.device)
+        its, acc, st = (torch.empty((N,), dtype=torch.int32, device=self.device) for _ in range(3))
+        ws = torch.empty((min(chunk, N) * per_row,), dtype=torch.uint8, device=self.device)
+        wv = (C.c_float * 3)(*w)
+        for r0 in range(0, N, chunk):
+            n = min(chunk, N - r0)
+            _capi.check(self._h, self._L.avae_motion_track(
+                self._h, p[r0:r0 + n].data_ptr(), q0[r0:r0 + n].data_ptr(), n, T, D, frames.data_ptr(), axes.data_ptr(), dt, wv, R,
+                ptr(E), ptr(lim), wl, n_iters, lam0, TRACK_FACTOR, TRACK_LAM_MIN, TRACK_LAM_MAX, tol, ws.data_ptr(), n * per_row,
+                traj[r0:r0 + n].data_ptr(), ctrl[r0:r0 + n].data_ptr() if T > 1 else None, c0[r0:r0 + n].data_ptr(),
+                c1[r0:r0 + n].data_ptr(), rm[r0:r0 + n].data_ptr(), its[r0:r0 + n].data_ptr(), acc[r0:r0 + n].data_ptr(),
+                st[r0:r0 + n].data_ptr(), self._stream()), "avae_motion_track")
+        return {"trajectory": traj, "controls": ctrl, "cost0": c0, "cost": c1, "track_rmse": rm, "iterations": its,
+                "accepted": acc, "status": st}
+
+    def motion_track(self, path, chain, seed=None, init=None, orientation=None, dt=0.01, track_weights=(10.0, 10.0, 50.0),
+                     effort_weight=0.01, effort=None, limits=True, limit_weight=0.0, n_iters=25, lam0=1.0, tol=1e-6,
+                     ik_options=None):
+        """Pen paths ``[N, T, 3]`` -> smooth joint trajectories that follow them (avae_motion_track in include/avae.h): the
+        reference's ``derive_ilqr_trajectory`` (baxter_writer.py:106-145) for N paths at once -- iLQR on a double-integrator joint
+        model (``q' = q + dt v``, ``v' = v + dt u``) whose cost trades the tip's distance from the path, weighted per axis by
+        ``track_weights``, against the control effort ``effort_weight |E u|^2`` -- the project's own definition of that solver, not
+        a bit copy of it.
+
+        The first guess is ``init [N, T, n_dof]`` or, with ``init=None``, ``motion_ik(path, chain, seed, orientation,
+        **ik_options)``: the reference's way.  ``effort`` is None (the identity) or a constant ``[n_dof, n_dof]`` matrix E, for
+        example the square root of the arm's inertia at the seed pose (the chain carries no masses).  ``limits`` (True: the
+        chain's own, None or ``[n_dof, 2]``) enter as a quadratic penalty ``limit_weight`` on what an angle lies outside them,
+        and not at all at ``limit_weight=0``.  A try solves the Riccati recursion at the damping ``lam`` (``lam0`` at first, a
+        tenth after an accepted try, tenfold after a rejected one, between 1e-6 and 1e6) and takes the full step if it lowers the
+        cost; a row ends after ``n_iters`` tries, when an accepted try gains less than ``tol`` of the cost, or when ``lam`` passes
+        1e6.  Rows go to the device in chunks whose workspace stays below 512 MiB (or one row's).
+
+        Returns a dict: ``trajectory [N, T, n_dof]``, ``controls [N, T - 1, n_dof]`` (joint accelerations), ``cost0`` and ``cost
+        [N]`` (float64; of the first guess's rollout and of the result), ``track_rmse [N]`` (metres, unweighted), ``iterations``
+        and ``accepted [N]`` (tries made and taken) and ``status [N]`` (int32; 0 converged, 1 ``n_iters`` tries made, 2 no try
+        was ever accepted, 3 a non-finite path point, first guess or limit: NaN outputs).  NumPy in gives NumPy out, device
+        tensors in give device tensors out."""
+        p, frames, axes, q0, E, lim, opts, was_np = motion_track_args(path, chain, init, dt, track_weights, effort_weight, effort,
+                                                                      limits, limit_weight, n_iters, lam0, tol, self.device)
+        if q0 is None:
+            extra = set(ik_options or {}) - {"n_iters", "tol", "rot_tol", "damping", "max_step", "limits"}
+            if extra:
+                raise ValueError("unknown ik_options %s" % ", ".join(sorted(map(str, extra))))
+            ik = dict(dict(n_iters=20, tol=1e-5, rot_tol=1e-4, damping=0.01, max_step=0.5, limits=True), **(ik_options or {}))
+            a = motion_ik_args(p, chain, seed, orientation, ik["n_iters"], ik["tol"], ik["rot_tol"], ik["damping"], ik["max_step"],
+                               ik["limits"], self.device)
+            q0 = self._motion_ik(*a[:7])["trajectory"]
+        elif seed is not None or orientation is not None or ik_options is not None:
+            raise ValueError("seed, orientation and ik_options belong to the first guess motion_ik makes: leave them out with init")
+        conv = self._like_input(was_np)
+        return {k: conv(v) for k, v in self._motion_track(p, frames, axes, q0, E, lim, opts).items()}
+
+    def _smoothed(self, p, chain, traj, tr):
+        """``_motion_track`` from the trajectory ``traj`` with the options dict ``tr`` (``check_solver``'s)"""
+        p, frames, axes, q0, E, lim, opts, _ = motion_track_args(p, chain, traj, tr["dt"], tr["track_weights"], tr["effort_weight"],
+                                                                 tr["effort"], tr["limits"], tr["limit_weight"], tr["n_iters"],
+                                                                 tr["lam0"], tr["tol"], self.device)
+        return self._motion_track(p, frames, axes, q0, E, lim, opts)
+
+    def strokes_to_motion(self, strokes, basis, chain, canvas, center, seed, height=0.0, solver="ik", track_options=None,
+                          **ik_options):
         """The reference's data pipeline (``build_ik_joint_traj_for_chars`` and ``build_fa_for_joint_trajs``,
         baxter_writer.py:147-196) for N strokes at once: ``strokes [N, T, 2]`` in the canvas' plane units are lifted around
         ``center`` at ``height`` above the paper (``canvas.lift``), followed by the arm (``motion_ik`` from ``seed`` with
         ``ik_options``), fitted (``motion_fit`` with ``basis``, whose ``n_points`` must be T) and drawn (``render_strokes``).
+        With ``solver='ilqr'`` the inverse-kinematics solution is the first guess of ``motion_track`` (``track_options``: a dict
+        of its dt, track_weights, effort_weight, effort, limits, limit_weight, n_iters, lam0, tol), the reference's
+        ``build_ilqr_joint_traj_for_chars`` (baxter_writer.py:166-184), and the smoothed motion is what is fitted.
 
         Returns a dict: ``path [N, T, 3]``, ``trajectory [N, T, n_dof]``, ``params [N, n_params]`` (a joint-modality row),
-        ``image [N, n_pixels]`` (the image-modality row), ``converged [N]`` (every point of the row), ``fit_rmse [N, n_dof]``
-        (``motion_eval`` of the fitted parameters against the trajectory) and ``tip_error [N]`` (the worst distance of the pen
-        tip of the fitted motion from the path: what approximator and solver lose together).  Every piece is bitwise what the
-        separate calls give."""
+        ``image [N, n_pixels]`` (the image-modality row), ``converged [N]`` (every point of the row, of ``motion_ik``),
+        ``fit_rmse [N, n_dof]`` (``motion_eval`` of the fitted parameters against the trajectory) and ``tip_error [N]`` (the
+        worst distance of the pen tip of the fitted motion from the path: what approximator and solver lose together); under
+        ``'ilqr'`` also ``track_status`` and ``track_cost [N]``.  Every piece is bitwise what the separate calls give."""
+        tr = check_solver(solver, track_options)
         (p, frames, axes, s, orient, lim, opts), was_np = strokes_to_motion_args(strokes, basis, chain, canvas, center, seed, height,
                                                                                  ik_options, self.device)
         ik = self._motion_ik(p, frames, axes, s, orient, lim, opts)
-        t, pinv, sc, sh, _ = motion_fit_args(ik["trajectory"], basis, self.device)
+        sm = None if tr is None else self._smoothed(p, chain, ik["trajectory"], tr)
+        t, pinv, sc, sh, _ = motion_fit_args(ik["trajectory"] if sm is None else sm["trajectory"], basis, self.device)
         params = self._motion_fit(t, pinv, sc, sh, basis)
         ev, _, rmse, _ = self._motion_eval(params, motion_matrices(basis, self.device), basis, ref=t)
         tip = torch.linalg.vector_norm(self._motion_fk(ev, frames, axes) - p, dim=2).amax(1)
         plane = canvas_args(canvas, int(p.shape[0]), None, None, self.device)[0]
         image = self._render(p, plane, canvas, None, None)["image"]
         conv = self._like_input(was_np)
-        return {"path": conv(p), "trajectory": conv(t), "params": conv(params), "image": conv(image),
-                "converged": conv(ik["converged"].all(1)), "fit_rmse": conv(rmse), "tip_error": conv(tip)}
+        out = {"path": conv(p), "trajectory": conv(t), "params": conv(params), "image": conv(image),
+               "converged": conv(ik["converged"].all(1)), "fit_rmse": conv(rmse), "tip_error": conv(tip)}
+        if sm is not None:
+            out.update(track_status=conv(sm["status"]), track_cost=conv(sm["cost"]))
+        return out
 
     def refine_pen_path(self, target_image, basis, chain, canvas, init=None, n_rollouts=50, n_iters=20, var0=1e-5,
-                        anchor_start=True, seed_angles=None, image_modality=0, modality=1, ik_n_iters=20, **options):
+                        anchor_start=True, seed_angles=None, image_modality=0, modality=1, ik_n_iters=20, solver="ik",
+                        track_options=None, **options):
         """The reference's Cartesian refinement (``derive_robot_motion_from_img_posterior_rl_cartesian``,
         baxter_vae_assoc_writer.py:182-257) for P pictures at once: a ``search`` over the pen path's own approximator parameters
         and the way back to joint space.
@@ -1743,7 +1829,11 @@ class AssocVariationalAutoEncoder(object):
 
         Returns ``search``'s dict and ``path [P, T, 3]`` (the refined pen path), ``trajectory [P, T, n_dof]``, ``params
         [P, n_params]`` (bitwise ``motion_fit(motion_ik(path, ...)["trajectory"], basis)``), ``converged [P]``, ``initial`` and
-        ``final`` (dicts of ``img_l2 [P]`` of the initial path and of ``path``) and ``image``, the drawing of ``path``."""
+        ``final`` (dicts of ``img_l2 [P]`` of the initial path and of ``path``) and ``image``, the drawing of ``path``.  With
+        ``solver='ilqr'`` the way back to joint space goes on through ``motion_track`` (``track_options``: a dict of its options)
+        from the inverse-kinematics solution: ``trajectory`` and ``params`` are those of the smoothed motion, and the dict also
+        holds ``track_status`` and ``track_cost [P]``."""
+        tr = check_solver(solver, track_options)
         ik, search_options = refine_pen_path_args(basis, chain, canvas, n_rollouts, dict(options, n_iters=ik_n_iters), self._widths,
                                                   image_modality, modality)
         if target_image is None:
@@ -1784,6 +1874,9 @@ class AssocVariationalAutoEncoder(object):
                                                                   ik["rot_tol"], ik["damping"], ik["max_step"], ik["limits"],
                                                                   self.device)
         sol = self._motion_ik(p, frames, axes, s, orient, lim, opts)
+        sm = None if tr is None else self._smoothed(p, chain, sol["trajectory"], tr)
+        if sm is not None:
+            sol = dict(sol, trajectory=sm["trajectory"])
         params = self._motion_fit(*motion_fit_args(sol["trajectory"], basis, self.device)[:4], basis)
         last = self._render(path, plane, canvas, tg, None)
         conv = self._like_input(was_np)
@@ -1791,6 +1884,8 @@ class AssocVariationalAutoEncoder(object):
         out.update(path=conv(path), trajectory=conv(sol["trajectory"]), params=conv(params),
                    converged=conv(sol["converged"].all(1)), image=conv(last["image"]),
                    initial={"img_l2": conv(first["img_l2"])}, final={"img_l2": conv(last["img_l2"])})
+        if sm is not None:
+            out.update(track_status=conv(sm["status"]), track_cost=conv(sm["cost"]))
         return out
 
     # ------------------------------------------------------------------ sigma-lognormal strokes
