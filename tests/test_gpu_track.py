@@ -121,7 +121,9 @@ def test_tries_against_the_definition(V, name, tries):
     """(1, 1, 1): no controls; (3, 2, 3): one control that cannot move the pen; (3, 3, 3); (5, 100, 7) on the fixture arm ('figure');
     (2, 257, 16): five strides of the wave over T in the widest class; (65, 8, 7), (300, 3, 3): many workgroups; T = 63, 64, 65:
     the edges of a stride; D = 5, 9, 12, 15: the classes from the inside; an effort matrix; R = 0 with lam carrying the solve;
-    binding limits."""
+    binding limits.  D = 4, 8, 16 (also at T = 2): the tops of the classes, where the walk's uniform c < D branch is never taken;
+    D = 6, 10, 13, 14; T = 127, 128, 129: the second stride's edges; 192, 193: a whole third stride; 1024 = kTrackMaxT; (1, 513,
+    16): nine strides in the widest class (the third of its four tries is rejected)."""
     model = _model(V)
     c, opt = TC.named(name)
     opt = dict(opt, n_iters=tries, tol=0.0)

@@ -134,6 +134,69 @@ def test_restatement_takes_the_definitions_decisions():
         assert all(d == ("a" if moving else "") + "r" * 13 for d in r64["decisions"])
     assert (TC.refs(TC.figure_case(TC.TOL_FIGURES, "ik"), tol=1e-5)[0]["iterations"] == 6).all()
     TC.refs(TC.named("smooth-65-8-7")[0], n_iters=0)
+    # tests/test_gpu_track_edges.py
+    TC.refs(TC.smooth_case(TC.LONGEST), n_iters=1, tol=0.0)
+    for name in TC.TERM_CASES:
+        c, opt = TC.named(name)
+        for n in (1, 4):
+            r64, r32 = TC.refs(c, n_iters=n, tol=0.0, **opt)
+            assert all(d == "a" * n for d in r64["decisions"]), (name, r64["decisions"])
+            if name in TC.BOXED_CASES:                            # both branches of the limit term are live, before and after
+                assert all(TC.outside(c, c["init"])), name
+                for r in (r64, r32):
+                    live = TC.outside(c, r["trajectory"])
+                    assert live[0] and live[1] and live[3], (name, live)
+    for label, make, opt, decisions, status in TC.ABI_RUNS:
+        r64, _ = TC.refs(make(), **opt)
+        assert all(d == decisions for d in r64["decisions"]) and (r64["status"] == status).all(), (label, r64["decisions"])
+        if label == "tol 0.3":                                    # the gain that tells tol J from tol J' (track_cases.ABI_RUNS)
+            gain = (r64["cost0"] - r64["cost"]) / r64["cost0"]
+            assert (gain > 0.3 / 1.3 + 0.02).all() and (gain < 0.3 - 0.02).all(), gain
+
+
+def test_backward_pass_rejections_in_both_precisions():
+    """a gain that is finite as double and not as float rejects the try in the definition too (avae_track.h's rule); the recorded
+    decisions of ``track_cases.subnormal_case``, ``huge_case`` and the overflowing track weights"""
+    c = TC.subnormal_case()
+    runs = tuple((dict(TC.SUBNORMAL, **opt), d, s) for opt, d, s in TC.SUBNORMAL_RUNS) + ((TC.OVERFLOW, "ppppp", 1),)
+    for opt, decisions, status in runs:
+        r64, r32 = TC.refs(c, **opt)
+        z64, z32 = TC.refs(c, **dict(opt, n_iters=0))
+        for r, z in ((r64, z64), (r32, z32)):
+            assert r["decisions"] == [decisions] * 3 and (r["status"] == status).all() and (r["iterations"] == len(decisions)).all()
+            assert (r["accepted"] == 0).all() and np.array_equal(r["cost"], r["cost0"]) and np.isfinite(r["cost"]).all()
+            assert np.array_equal(r["trajectory"], z["trajectory"]) and np.array_equal(r["controls"], z["controls"])
+            assert np.isfinite(r["controls"]).all()
+    for value, decisions in ((1e36, "pap"), (1e35, "aap")):
+        c = TC.huge_case(value)
+        r64, r32 = TC.refs(c, **TC.HUGE)
+        assert r64["decisions"] == ["aaa", decisions, "aaa"]
+        assert np.isfinite(r64["cost"]).all() and TC.rel_err(r32["cost"], r64["cost"]) < 1e-4
+        assert np.isinf(r32["controls"][1]).any() and np.isfinite(r32["controls"][[0, 2]]).all()
+        clean = TC.refs(TC.smooth_case((3, 5, 3)), **TC.HUGE)[1]
+        assert all(np.array_equal(r32[k][[0, 2]], clean[k][[0, 2]]) for k in ("trajectory", "controls", "cost"))
+
+
+def test_which_exit_the_overflowing_weights_take():
+    """``track_cases.OVERFLOW``: the restatement's l_qq is not finite and its tries end at a pivot, with no gain written before it
+    that is not finite; the definition's is finite and its tries end at a gain, after finite pivots"""
+    c, o = TC.subnormal_case(), TC.OVERFLOW
+    dt, w = float(F32(o["dt"])), np.asarray(o["track_weights"], dtype=F32).astype(np.float64)
+    Se = TR.effort_matrix(3, 0.0, None)
+    u = TR.first_controls(c["init"], dt)
+    x = TR.rollout(np.concatenate([c["init"][:, 0].astype(np.float64), np.zeros((3, 3))], axis=1), u, dt)
+    for prec in (np.float64, F32):
+        with np.errstate(all="ignore"):
+            _, _, lq, lqq = TR.points(x[:, :, :3], u, c["path"], c["frames"], c["axes"], w, Se, None, 0.0, prec)
+            exits = []
+            _, _, ok = TR.backward(u, lq, lqq, Se, dt, np.full(3, o["lam0"]), prec, exits=exits)
+        assert not ok.any()
+        pivots = np.array([p for _, p, _ in exits])
+        gains = np.array([g for _, _, g in exits])
+        if prec == F32:
+            assert not np.isfinite(lqq).all() and not pivots.any() and gains.all()
+        else:
+            assert np.isfinite(lqq).all() and pivots.all() and gains[0].all() and not gains[1:].any()
 
 
 def test_non_finite_rows_in_the_definition():

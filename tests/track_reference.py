@@ -139,9 +139,10 @@ def _solve(L, Y):
     return X
 
 
-def backward(u, lq, lqq, Se, dt, lam, prec):
+def backward(u, lq, lqq, Se, dt, lam, prec, exits=None):
     """THE BACKWARD PASS for n rows at their own lam [n] -> (k [n, T - 1, D], K [n, T - 1, D, 2 D] as the forward pass uses them,
-    ok [n])"""
+    ok [n]).  ``exits``: a list that gets, per step from T - 2 down, (t, the rows whose pivots were > 0, the rows whose gains were
+    finite): which of the kernel's exits a rejected row takes and where."""
     n, Tm, D = u.shape
     A = np.eye(2 * D)
     A[:D, D:] = dt * np.eye(D)
@@ -163,11 +164,16 @@ def backward(u, lq, lqq, Se, dt, lam, prec):
         Qux = B.T @ V @ A
         Quu = 2.0 * Se + B.T @ V @ B + lam[:, None, None] * np.eye(D)
         L, good = _cholesky(Quu)
+        pivots = good.copy()
         sol = -_solve(L, np.concatenate([Qu[:, :, None], Qux], axis=2))
         k, Kt = sol[:, :, 0], sol[:, :, 1:]
-        stored_k, stored_K = (k, Kt) if prec == np.float64 else (k.astype(F32).astype(np.float64), Kt.astype(F32).astype(np.float64))
-        good &= np.isfinite(stored_k).all(axis=1) & np.isfinite(stored_K).all(axis=(1, 2))
+        kf, Kf = k.astype(F32), Kt.astype(F32)
+        stored_k, stored_K = (k, Kt) if prec == np.float64 else (kf.astype(np.float64), Kf.astype(np.float64))
+        # not finite as double or as float rejects the try (avae_track.h): the definition's rule too, though it uses the doubles
+        good &= np.isfinite(k).all(axis=1) & np.isfinite(Kt).all(axis=(1, 2)) & np.isfinite(kf).all(axis=1) & np.isfinite(Kf).all(axis=(1, 2))
         ok &= good
+        if exits is not None:
+            exits.append((t, pivots, good | ~pivots))
         ks[:, t], Ks[:, t] = stored_k, stored_K
         KT = np.swapaxes(Kt, 1, 2)
         vx = Qx + (KT @ (Quu @ k[:, :, None] + Qu[:, :, None]))[:, :, 0] + (np.swapaxes(Qux, 1, 2) @ k[:, :, None])[:, :, 0]
