@@ -874,6 +874,53 @@ int avae_stroke_render(avae_handle* h, const float* path_dev, int32_t rows, int3
                        const float* target_dev, const float* height_dev,
                        float* image_dev, float* window_dev, float* img_l2_dev, float* height_l2_dev, void* stream);
 
+/* ---- letter thumbnails: from camera frames or drawing-pad canvases to the size x size pictures the image encoders were trained on
+ * (DESIGN.md section 30).  The reference does this on the host for every input it is shown: the camera path thresholds the grey
+ * frame at 108, inverts it and crops it to the ink (drawing_pad.py:185-193, writing_image_reader.py:64-97), the drawing pad converts
+ * its RGBA canvas to grey and inverts it (drawing_pad.py:282-299, 311-322), and both -- like the data set (utils.py:46-107, 259-268)
+ * -- hand the result to get_char_img_thumbnail_helper (utils.py:208-258): bounding box of the ink, pasted into a square canvas whose
+ * side is the longer edge plus 60 %, cv2.resize(.., (28, 28), INTER_AREA).  This call is the project's own definition of that
+ * picture, in integers throughout, so that its result is exact:
+ *   frames_dev uint8 [rows][Hf][Wf][C], C = 1, 3 or 4; pixel (n, y, x) starts at byte n frame_stride + y row_stride + x C.  Bytes of
+ *   a row behind Wf C and of a frame behind its last row are padding: never loaded.
+ *   grey  v = the byte (C = 1), else (4899 R + 9617 G + 1868 B + 8192) >> 14; the bytes of a pixel are R, G, B (, A) or with
+ *         AVAE_THUMB_BGR B, G, R (, A); the fourth byte is ignored.
+ *   ink   threshold = -1 (none): g = 255 - v with AVAE_THUMB_INVERT, else v;  threshold in [0, 255]: t = v > threshold ? 255 : 0,
+ *         g = 255 - t with AVAE_THUMB_INVERT, else t.  The camera path is threshold 108 with AVAE_THUMB_INVERT, the drawing pad no
+ *         threshold with AVAE_THUMB_INVERT.
+ *   box[n] = (x, y, w, h), the bounding box of the pixels with g != 0 (w, h counts of pixels), ink[n] their number.  A frame without
+ *         ink is blank: box = (0, 0, Wf, Hf), ink = 0, every image pixel +0.
+ *   window: L = max(w, h), b = 3 L / 5 (= int(0.6 L)), S = L + b, oy = b / 2 + (L - h) / 2, ox = b / 2 + (L - w) / 2 (integer
+ *         divisions): frame pixel (y + r, x + c), r < h, c < w, is cell (oy + r, ox + c) of an S x S canvas of zeros.
+ *         window[n] = (x - ox, y - oy, S): the canvas in frame coordinates.
+ *   image[n][i size + j] = the mean of the canvas over [i S / size, (i + 1) S / size) x [j S / size, (j + 1) S / size), over 255:
+ *         sum = sum over cells of g wy(i, row) wx(j, col),  wx(j, k) = max(0, min((j + 1) S, (k + 1) size) - max(j S, k size)), wy
+ *         likewise -- an exact integer -- and image = (float)((double)sum / (double)(255 S S)), one division and one rounding.  The
+ *         same rule holds for S < size (cv2.INTER_AREA interpolates there).
+ * Differences from the reference: ink on the outermost pixels of the frame counts (cv2.findContours ignores it); the area mean is
+ * kept for S < size; the grey value is the fixed-point formula above, not a bit copy of OpenCV's or PIL's; localize_img followed by
+ * the helper is one pass (the second bounding box is the first one shifted).
+ * avae_letter_thumbnail_plan (host only): slabs = the number of row bands a frame is scanned in (they tile Hf exactly, a function of
+ *   Hf and Wf), workspace_bytes = what a call of `rows` frames needs.  Either output may be NULL, not both.
+ * avae_letter_thumbnail: workspace_dev (16-byte aligned, at least the planned size, any contents: every byte read is written first
+ *   by the same call).  Each of image_dev [rows][size size] float, box_dev [rows][4], window_dev [rows][3], ink_dev [rows] int32
+ *   may be NULL, not all four.
+ * rows == 0 is a no-op once the arguments have passed: it needs no workspace, but frames_dev and one output must still be non-NULL
+ * (as avae_stroke_render asks).
+ * Errors (message in avae_last_error, nothing launched): rows < 0 or > 2^24, Hf or Wf outside [1, 4096], C not 1, 3 or 4, size outside [1, 64], threshold outside [-1, 255], unknown flags, row_stride outside [Wf C, 2^26], frame_stride outside
+ * [(Hf - 1) row_stride + Wf C, 2^38], frames_dev or workspace_dev NULL, every output NULL, a workspace below the plan or misaligned.
+ * Two launches, no atomics, no scratch.  No model state is read or written -- of the handle the call takes the lock, the stream
+ * bookkeeping and, in timing mode, the launch timers, as every entry point does: a frame's outputs are a pure function of its
+ * bytes and the arguments -- the same alone or among other frames, on any stream, on repetition, with any workspace and whichever
+ * outputs are asked for -- and the call works on any replica and inside avae_use_averaged. */
+#define AVAE_THUMB_INVERT 1
+#define AVAE_THUMB_BGR 2
+int avae_letter_thumbnail_plan(int32_t rows, int32_t Hf, int32_t Wf, int32_t* slabs, size_t* workspace_bytes);
+int avae_letter_thumbnail(avae_handle* h, const uint8_t* frames_dev, int32_t rows, int32_t Hf, int32_t Wf, int32_t C,
+                          int64_t row_stride, int64_t frame_stride, int32_t flags, int32_t threshold, int32_t size,
+                          void* workspace_dev, size_t workspace_bytes,
+                          float* image_dev, int32_t* box_dev, int32_t* window_dev, int32_t* ink_dev, void* stream);
+
 /* ---- pose, Jacobian and inverse kinematics: from a pen path back to joint angles.  The reference builds every
  * joint-modality row it trains on by solving one PyKDL inverse_kinematics per time point of a stroke, each seeded with the previous
  * point's solution (derive_ik_trajectory, baxter_writer.py:84-96), and returns from its Cartesian refinement to joint space the same

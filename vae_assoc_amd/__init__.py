@@ -8,6 +8,7 @@ from . import dataset  # noqa: F401
 _LAZY = {"AssocVariationalAutoEncoder": "vae_assoc", "train": "vae_assoc", "xavier_init": "vae_assoc",
          "GradSync": "parallel", "dp_train_step": "parallel",
          "linear_warmup": "_marshal", "cyclical": "_marshal", "exponential_decay": "_marshal",
+         "occlude_quadrant": "vae_assoc",
          "MotionBasis": "motion", "KinematicChain": "kinematics", "StrokeCanvas": "kinematics"}
 
 

@@ -8,8 +8,8 @@ import numpy as np
 import torch
 
 from . import _capi
-from ._marshal import (_is_number, as_index, as_int, dev_array, dev_block3, dev_dense, dev_dense3, dev_flags, dev_modalities,
-                       dev_row_args, need_type, to_device32)
+from ._marshal import (_is_number, as_index, as_int, dev_array, dev_block3, dev_dense, dev_dense3, dev_flags, dev_frames,
+                       dev_modalities, dev_row_args, need_type, to_device32)
 from .kinematics import KinematicChain, StrokeCanvas
 from .motion import MotionBasis
 
@@ -474,6 +474,53 @@ def render_args(path, canvas, target, height, device):
     if not 1 <= p.shape[1] <= _capi.MOTION_MAX_POINTS:
         raise ValueError("path must hold 1 to %d points, got %d" % (_capi.MOTION_MAX_POINTS, p.shape[1]))
     return (p,) + canvas_args(canvas, int(p.shape[0]), target, height, device) + (was_np,)
+
+
+THUMBNAIL_CAMERA = dict(threshold=108, invert=True)     # the reference's camera path (drawing_pad.py:185-193)
+THUMBNAIL_CANVAS = dict(invert=True)                    # its drawing pad (drawing_pad.py:282-299)
+
+
+def letter_thumbnail_args(frames, size, threshold, invert, channel_order, device):
+    """The arguments of ``letter_thumbnails`` -> (frames uint8 [N, Hf, Wf, C], row stride, frame stride, flags, threshold (-1:
+    none), size, was_numpy)."""
+    size = as_int(size, "size", 1, _capi.THUMB_MAX_SIZE)
+    thr = -1 if threshold is None else as_int(threshold, "threshold", 0, 255)
+    if not isinstance(invert, (bool, np.bool_)):
+        raise ValueError("invert must be True or False, got %r" % (invert,))
+    if channel_order not in ("rgb", "bgr"):
+        raise ValueError("channel_order must be 'rgb' or 'bgr', got %r" % (channel_order,))
+    t, row, frame, was_np = dev_frames(frames, device)
+    N, Hf, Wf, Cn = (int(s) for s in t.shape)
+    if Cn not in (1, 3, 4):
+        raise ValueError("frames must hold 1, 3 or 4 channels (grey, RGB, RGBA), got %d" % Cn)
+    if not (1 <= Hf <= _capi.THUMB_MAX_FRAME and 1 <= Wf <= _capi.THUMB_MAX_FRAME):
+        raise ValueError("frames must be 1 to %d pixels high and wide, got %d x %d" % (_capi.THUMB_MAX_FRAME, Hf, Wf))
+    flags = (_capi.THUMB_INVERT if invert else 0) | (_capi.THUMB_BGR if channel_order == "bgr" else 0)
+    return t, row, frame, flags, thr, size, was_np
+
+
+def occlude_quadrant(images, quadrant):
+    """The drawing pad's incomplete picture (drawing_pad.py:324-328): square pictures ``[N, H * H]`` (H even) with one quadrant
+    set to 0 -> (the occluded pictures, the ``observed`` element mask ``complete()`` takes: uint8 [N, H * H], 0 inside the
+    quadrant).  ``quadrant = (row half, column half)``, each 0 or 1 -- the reference's ``fraction_idx`` -- for every row, or an
+    ``[N, 2]`` array with one pair per row.  NumPy in gives NumPy out, tensors in give tensors on the same device."""
+    was_np = not torch.is_tensor(images)
+    x = torch.as_tensor(np.asarray(images)) if was_np else images
+    H = int(round(float(x.shape[1]) ** 0.5)) if x.dim() == 2 else 0
+    if x.dim() != 2 or H * H != x.shape[1] or H % 2:
+        raise ValueError("images must be [N, H * H] with H even, got %s" % (tuple(x.shape),))
+    q = torch.as_tensor(np.asarray(quadrant) if not torch.is_tensor(quadrant) else quadrant.cpu().numpy())
+    if q.dim() == 1:
+        q = q.reshape(1, -1).expand(x.shape[0], -1)
+    if tuple(q.shape) != (x.shape[0], 2) or q.dtype not in (torch.int32, torch.int64, torch.uint8, torch.bool) \
+            or bool(((q != 0) & (q != 1)).any()):
+        raise ValueError("quadrant must be (row half, column half) with halves 0 or 1, or [%d, 2] of them, got %r" % (x.shape[0], quadrant))
+    q = q.to(device=x.device, dtype=torch.int64)
+    half = torch.arange(H, device=x.device) // (H // 2)                                   # 0 for the first half, 1 for the second
+    inside = (half[None, :, None] == q[:, 0, None, None]) & (half[None, None, :] == q[:, 1, None, None])      # [N, H, H]
+    observed = (~inside).reshape(x.shape[0], H * H)
+    out, observed = x * observed.to(x.dtype), observed.to(torch.uint8)
+    return (out.numpy(), observed.numpy()) if was_np else (out, observed)
 
 
 def draw_args(params, basis, chain, canvas, anchor, target, height, device):

@@ -29,6 +29,7 @@ RENDER_MAX_SIZE, RENDER_SUPERSAMPLES = 64, (1, 2, 4, 8)
 IK_MAX_ITERS = 1000
 LOGNORMAL_MAX_COMPONENTS, LOGNORMAL_MAX_POINTS, LOGNORMAL_MAX_ITERS = 16, 1024, 10000
 TRACK_MAX_ITERS = 1000
+THUMB_MAX_FRAME, THUMB_MAX_SIZE, THUMB_INVERT, THUMB_BGR = 4096, 64, 1, 2
 
 ACT_IDS = {"identity": 0, "relu": 1, "softplus": 2, "sigmoid": 3, "tanh": 4}
 DTYPE_IDS = {"fp32": 0, "f32": 0, "float32": 0, "bf16": 1, "bfloat16": 1}
@@ -55,6 +56,7 @@ SYMBOLS = [
     "avae_embed_calibrate", "avae_embed_iterate", "avae_embed_plan",
     "avae_motion_eval", "avae_motion_fit", "avae_motion_moments",
     "avae_motion_fk", "avae_stroke_render",
+    "avae_letter_thumbnail", "avae_letter_thumbnail_plan",
     "avae_motion_pose", "avae_motion_ik",
     "avae_lognormal_eval", "avae_lognormal_sample", "avae_lognormal_fit",
     "avae_motion_track", "avae_motion_track_plan",
@@ -197,6 +199,8 @@ def lib():
             L.avae_motion_moments.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
             L.avae_motion_fk.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp]
             L.avae_stroke_render.argtypes = [vp, vp, i32, i32, vp, C.c_float, C.c_float, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+            L.avae_letter_thumbnail_plan.argtypes = [i32, i32, i32, C.POINTER(i32), C.POINTER(sz)]
+            L.avae_letter_thumbnail.argtypes = [vp, vp, i32, i32, i32, i32, C.c_int64, C.c_int64, i32, i32, i32, vp, sz, vp, vp, vp, vp, vp]
             L.avae_motion_pose.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]
             L.avae_motion_ik.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, i32, vp, i32, C.c_float, C.c_float, C.c_float,
                                          C.c_float, vp, vp, vp, vp, vp, vp]

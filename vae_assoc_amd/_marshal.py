@@ -386,6 +386,34 @@ def dev_dense3(a, shape, device, name="eps"):
     return t.to(device=device, dtype=torch.float32).contiguous()
 
 
+def dev_frames(a, device, name="frames"):
+    """uint8 frames ``[N, Hf, Wf]`` or ``[N, Hf, Wf, C]`` -> (uint8 tensor [N, Hf, Wf, C] on ``device``, row stride, frame stride
+    in bytes, was_numpy).  A tensor whose pixels are dense (channel stride 1, pixel stride C) and whose rows and frames do not
+    overlap passes through with its strides -- a crop of wider frames, padded rows -- without a copy; anything else is copied
+    once.  Other dtypes are refused: the thresholds and the grey formula are those of 8-bit pixels."""
+    was_np = not torch.is_tensor(a)
+    t = torch.as_tensor(np.asarray(a)) if was_np else a
+    if t.dtype != torch.uint8:
+        raise ValueError("%s must be uint8 (8-bit pixels, 0 .. 255), got %s: scale and round float frames first"
+                         % (name, str(t.dtype).replace("torch.", "")))
+    if t.dim() == 3:
+        t = t.unsqueeze(3)
+    if t.dim() != 4:
+        raise ValueError("%s must be [N, Hf, Wf] or [N, Hf, Wf, C], got %s" % (name, tuple(t.shape)))
+    t = t.to(device)
+    N, Hf, Wf, Cn = (int(s) for s in t.shape)
+    if N and Hf and Wf and Cn:
+        row = t.stride(1) if Hf > 1 else Wf * Cn          # (the stride of a single row or frame is arbitrary)
+        frame = t.stride(0) if N > 1 else (Hf - 1) * row + Wf * Cn
+        dense = (Cn == 1 or t.stride(3) == 1) and (Wf == 1 or t.stride(2) == Cn)
+        if not dense or row < Wf * Cn or frame < (Hf - 1) * row + Wf * Cn:
+            t = t.contiguous()
+            row, frame = Wf * Cn, Hf * Wf * Cn
+    else:
+        row, frame = Wf * Cn, Hf * Wf * Cn
+    return t, row, frame, was_np
+
+
 def dev_block3(a, tail, device, name, rows=None):
     """[rows, tail[0], tail[1]] block (None in ``tail`` = any size) -> (contiguous float32 tensor on ``device``, was_numpy)"""
     was_np = not torch.is_tensor(a)

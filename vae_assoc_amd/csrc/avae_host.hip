@@ -6,6 +6,7 @@
 #include "avae_latent_stats.h"
 #include "avae_motion.h"
 #include "avae_render.h"
+#include "avae_thumbnail.h"
 #include "avae_ik.h"
 #include "avae_lognormal.h"
 #include "avae_track.h"
@@ -4855,6 +4856,69 @@ int avae_stroke_render(avae_handle* h, const float* path_dev, int32_t rows, int3
         a.half_width = half_width; a.margin = margin; a.T = T; a.H = H; a.ss = ss;
         hipStream_t s = on_stream(h, stream);
         timed_launch(h, s, "stroke_render", [&] { launch_stroke_render(a, rows, s); });
+    });
+}
+
+// ---- letter thumbnails (include/avae.h, avae_thumbnail.h)
+static void check_thumb_frame(const std::string& w, int32_t rows, int32_t Hf, int32_t Wf) {
+    check_rows(w, rows, "rows");
+    if (rows > kThumbMaxRows) throw Err(w + ": rows = " + std::to_string(rows) + " must be at most " + std::to_string(kThumbMaxRows));
+    check_range(w, "Hf", Hf, 1, kThumbMaxFrame);
+    check_range(w, "Wf", Wf, 1, kThumbMaxFrame);
+}
+
+int avae_letter_thumbnail_plan(int32_t rows, int32_t Hf, int32_t Wf, int32_t* slabs, size_t* workspace_bytes) {
+    try {
+        const std::string w = "avae_letter_thumbnail_plan";
+        check_thumb_frame(w, rows, Hf, Wf);
+        if (!slabs && !workspace_bytes) throw Err(w + ": every output is NULL");
+        const ThumbPlan p = thumb_plan(Hf, Wf);
+        if (slabs) *slabs = p.slabs;
+        if (workspace_bytes) *workspace_bytes = thumb_workspace_bytes(rows, p.slabs);
+        return 0;
+    } catch (const std::exception& e) { g_create_error = e.what(); return 2; }
+}
+
+int avae_letter_thumbnail(avae_handle* h, const uint8_t* frames_dev, int32_t rows, int32_t Hf, int32_t Wf, int32_t C,
+                          int64_t row_stride, int64_t frame_stride, int32_t flags, int32_t threshold, int32_t size,
+                          void* workspace_dev, size_t workspace_bytes,
+                          float* image_dev, int32_t* box_dev, int32_t* window_dev, int32_t* ink_dev, void* stream) {
+    return guarded(h, [&] {
+        const std::string w = "avae_letter_thumbnail";
+        check_thumb_frame(w, rows, Hf, Wf);
+        if (C != 1 && C != 3 && C != 4) throw Err(w + ": C = " + std::to_string(C) + " must be 1, 3 or 4");
+        check_range(w, "size", size, 1, kThumbMaxSize);
+        check_range(w, "threshold", threshold, -1, 255);
+        if (flags & ~(AVAE_THUMB_INVERT | AVAE_THUMB_BGR))
+            throw Err(w + ": flags = " + std::to_string(flags) + " holds bits other than AVAE_THUMB_INVERT | AVAE_THUMB_BGR");
+        const long long row_bytes = (long long)Wf * C;
+        if (row_stride < row_bytes || row_stride > kThumbMaxRowStride)
+            throw Err(w + ": row_stride = " + std::to_string(row_stride) + " must be in [Wf * C = " + std::to_string(row_bytes) + ", " +
+                      std::to_string(kThumbMaxRowStride) + "]");
+        const long long frame_bytes = (long long)(Hf - 1) * row_stride + row_bytes;      // (row_stride <= 2^26: below 2^38)
+        if (frame_stride < frame_bytes || frame_stride > kThumbMaxFrameStride)
+            throw Err(w + ": frame_stride = " + std::to_string(frame_stride) + " must be in [(Hf - 1) * row_stride + Wf * C = " +
+                      std::to_string(frame_bytes) + ", " + std::to_string(kThumbMaxFrameStride) + "]");
+        need(w, frames_dev, "frames_dev");
+        if (!image_dev && !box_dev && !window_dev && !ink_dev) throw Err(w + ": every output is NULL");
+        if (rows == 0) return;
+        const ThumbPlan p = thumb_plan(Hf, Wf);
+        const size_t want = thumb_workspace_bytes(rows, p.slabs);
+        need(w, workspace_dev, "workspace_dev");
+        if (workspace_bytes < want)
+            throw Err(w + ": workspace_bytes = " + std::to_string(workspace_bytes) + " is below the " + std::to_string(want) +
+                      " bytes avae_letter_thumbnail_plan gives");
+        if (reinterpret_cast<uintptr_t>(workspace_dev) % 16 != 0) throw Err(w + ": workspace_dev must be aligned to 16 bytes");
+        ThumbArgs a = zeroed<ThumbArgs>();
+        a.frames = frames_dev; a.row_stride = row_stride; a.frame_stride = frame_stride;
+        a.records = static_cast<int32_t*>(workspace_dev);
+        a.image = image_dev; a.box = box_dev; a.window = window_dev; a.ink = ink_dev;
+        a.Hf = Hf; a.Wf = Wf; a.C = C;
+        a.invert = (flags & AVAE_THUMB_INVERT) ? 1 : 0; a.bgr = (flags & AVAE_THUMB_BGR) ? 1 : 0; a.threshold = threshold;
+        a.size = size; a.slab_rows = p.slab_rows; a.slabs = p.slabs;
+        hipStream_t s = on_stream(h, stream);
+        timed_launch(h, s, "ink_box", [&] { launch_ink_box(a, rows, s); });
+        timed_launch(h, s, "thumbnail", [&] { launch_thumbnail(a, rows, s); });
     });
 }
 

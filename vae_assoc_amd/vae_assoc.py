@@ -37,6 +37,7 @@ from ._args import (SEARCH_STATE_KEYS, _is_pair, _same_joints, agg_args, canvas_
                     motion_fit_args, motion_fk_args, motion_ik_args, motion_matrices, motion_moments_args, motion_pose_args,
                     predict_motion_args, prior_arrays, refine_motion_args, refine_pen_path_args, render_args, search_args,
                     strokes_to_motion_args, topk_args, writing_cost_args,      # (the validators are part of this module's surface)
+                    letter_thumbnail_args, occlude_quadrant, THUMBNAIL_CAMERA, THUMBNAIL_CANVAS,
                     check_solver, motion_track_args, track_rows_per_call, TRACK_FACTOR, TRACK_LAM_MAX, TRACK_LAM_MIN)
 from ._marshal import (as_index, corruption_fields, ema_fields, ema_kwargs, grad_clip_fields, grad_clip_kwargs, dev_array, dev_block3, dev_dense, dev_dense3, dev_flags, dev_inputs, dev_modalities, dev_row_args,  # noqa: F401
                        ld_of, ptr, schedule_kwargs, schedule_struct, to_device32)
@@ -1467,6 +1468,66 @@ class AssocVariationalAutoEncoder(object):
         cost = w[0] * (out["img_l2"] + w[1] * out["height_l2"]) + w[2] * lat
         return {"cost": cost, "img_l2": out["img_l2"], "height_l2": out["height_l2"], "latent_l2": lat, "image": out["image"],
                 "path": path, "trajectory": traj, "height": hg}
+
+    # ------------------------------------------------------------------ letter thumbnails
+    def _letter_thumbnails(self, t, row, frame, flags, thr, size):
+        """avae_letter_thumbnail on a device uint8 tensor [N, Hf, Wf, C] -> dict of device tensors"""
+        N, Hf, Wf, Cn = (int(s) for s in t.shape)
+        image = self._new(N, size * size)
+        box, window, ink = (torch.empty(s, dtype=torch.int32, device=self.device) for s in ((N, 4), (N, 3), (N,)))
+        if N:
+            need = C.c_size_t(0)
+            if self._L.avae_letter_thumbnail_plan(N, Hf, Wf, None, C.byref(need)) != 0:
+                raise RuntimeError("avae_letter_thumbnail_plan failed: %s" % self._L.avae_last_error(None).decode("utf-8", "replace"))
+            ws = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+            _capi.check(self._h, self._L.avae_letter_thumbnail(
+                self._h, t.data_ptr(), N, Hf, Wf, Cn, row, frame, flags, thr, size, ws.data_ptr(), need.value,
+                image.data_ptr(), box.data_ptr(), window.data_ptr(), ink.data_ptr(), self._stream()), "avae_letter_thumbnail")
+        return {"image": image, "box": box, "window": window, "ink": ink}
+
+    def letter_thumbnails(self, frames, size=28, threshold=None, invert=False, channel_order="rgb"):
+        """Camera frames or drawing-pad canvases -> the ``size x size`` pictures the image encoders were trained on
+        (avae_letter_thumbnail in include/avae.h): the reference's ``get_char_img_thumbnail_helper`` (utils.py:208-258) with the
+        steps its callers put in front of it, on the device and in exact integer arithmetic.
+
+        ``frames`` is uint8, ``[N, Hf, Wf]`` or ``[N, Hf, Wf, C]`` with C = 1, 3 (RGB) or 4 (RGBA, the fourth channel ignored);
+        ``channel_order='bgr'`` reads OpenCV's order.  A device tensor that is a crop or a padded view of a larger one is read in
+        place.  ``threshold`` (0 .. 255) makes the grey value binary first, ``invert`` turns dark ink on a bright ground into
+        bright ink; ``**letter_thumbnails.CAMERA`` is the reference's camera path (threshold 108, inverted),
+        ``**letter_thumbnails.CANVAS`` its drawing pad (inverted).
+
+        Returns a dict: ``image [N, size * size]`` float32 in [0, 1], ``box [N, 4]`` (x, y, w, h of the ink), ``window [N, 3]``
+        (x, y and side of the square that was shrunk, in frame pixels; it may reach outside the frame) and ``ink [N]`` (pixels
+        with ink), int32.  A frame without ink gives a picture of zeros, the whole frame as its box and ``ink = 0``."""
+        t, row, frame, flags, thr, size, was_np = letter_thumbnail_args(frames, size, threshold, invert, channel_order, self.device)
+        conv = self._like_input(was_np)
+        return {k: conv(v) for k, v in self._letter_thumbnails(t, row, frame, flags, thr, size).items()}
+
+    letter_thumbnails.CAMERA = THUMBNAIL_CAMERA
+    letter_thumbnails.CANVAS = THUMBNAIL_CANVAS
+
+    def frames_to_motion(self, frames, basis, image_modality=0, modality=1, **thumbnail_options):
+        """From camera frames to joint trajectories without leaving the device: ``letter_thumbnails(frames,
+        **thumbnail_options)``, then ``predict_motion`` with the picture as the only present modality -- bitwise those two calls.
+        The thumbnail's ``size * size`` must be modality ``image_modality``'s ``n_input``.  Returns ``predict_motion``'s dict with
+        ``image``, ``box``, ``window`` and ``ink`` added."""
+        as_index(image_modality, "image_modality", len(self._widths))
+        t, row, frame, flags, thr, size, was_np = letter_thumbnail_args(
+            frames, thumbnail_options.pop("size", 28), thumbnail_options.pop("threshold", None),
+            thumbnail_options.pop("invert", False), thumbnail_options.pop("channel_order", "rgb"), self.device)
+        if thumbnail_options:
+            raise ValueError("unknown thumbnail option(s) %s (size, threshold, invert, channel_order)"
+                             % ", ".join(sorted(map(str, thumbnail_options))))
+        if size * size != self._widths[image_modality]:
+            raise ValueError("thumbnails of %d x %d pixels do not fit modality %d, which holds %d"
+                             % (size, size, image_modality, self._widths[image_modality]))
+        thumbs = self._letter_thumbnails(t, row, frame, flags, thr, size)
+        X = [None] * len(self._widths)
+        X[image_modality] = thumbs["image"]
+        out = self.predict_motion(X, basis, modality=modality)
+        out.update(thumbs)
+        conv = self._like_input(was_np)
+        return {k: None if v is None else conv(v) for k, v in out.items()}
 
     # ------------------------------------------------------------------ black-box search (DESIGN.md section 25)
     def _search_sample(self, st, R, seed, iteration, proj, x):
