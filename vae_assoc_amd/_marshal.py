@@ -48,6 +48,15 @@ def ld_of(t):
     return t.stride(0) if t.shape[0] > 1 else t.shape[1]
 
 
+def row_chunks(N, chunk):
+    """Rows [0, N) in chunks of at most ``chunk`` rows (at least 1) -> (r0, n, at) per chunk, in order: ``at(t)`` is the data
+    pointer of rows r0 .. r0 + n of the tensor ``t``, None (NULL) for None.  ``N == 0`` yields nothing."""
+    chunk = max(1, int(chunk))
+    for r0 in range(0, N, chunk):
+        n = min(chunk, N - r0)
+        yield r0, n, lambda t, r0=r0, n=n: None if t is None else t[r0:r0 + n].data_ptr()
+
+
 def dev_array(a, cols, device):
     """-> (float32 tensor [rows, cols] on ``device`` with unit column stride, was_numpy).  A view whose rows do not overlap (a
     column slice of a wider matrix) passes through without a copy."""
