@@ -874,6 +874,56 @@ int avae_stroke_render(avae_handle* h, const float* path_dev, int32_t rows, int3
                        const float* target_dev, const float* height_dev,
                        float* image_dev, float* window_dev, float* img_l2_dev, float* height_l2_dev, void* stream);
 
+/* ---- gradients through the writing chain: the vector-Jacobian products of avae_stroke_render, avae_motion_fk
+ * and avae_motion_eval, and a batched Adam step, so that a motion can be moved towards the picture it should write by descent instead
+ * of by search.  Dense device fp32 everywhere but t_dev / status_dev (int32).
+ * avae_stroke_render_vjp: the inputs of avae_stroke_render and the cotangents g_image_dev [rows][H * H], g_img_l2_dev [rows],
+ *   g_height_l2_dev [rows] (each optional) -> grad_path_dev [rows][T][3], the gradient of  sum g_image . image + g_img_l2 img_l2 +
+ *   g_height_l2 height_l2  with respect to the path.  In the notation above (alpha_b = (b + 1/2) / (H ss) - 1/2):
+ *   a pixel's cotangent is g_image + g_img_l2 (image - target) / img_l2 (the second term 0 where img_l2 == 0), a sample's g_cov that
+ *   over ss^2.  A sample counts only in the open linear zone 0 < x < 1 of x = 1/2 + (half_width - d) / delta; there g_d = -g_cov /
+ *   delta, and -(half_width - d) / delta^2 g_cov goes to g_delta.  With j the first segment that attains the sample's distance, tau
+ *   its clamped foot parameter (0 for a segment that is a point) and n = (sample - foot) / d (0 where d == 0):  g_s = g_d n,
+ *   c_j gets -(1 - tau) g_s, c_{j+1} gets -tau g_s, g_ctr = sum g_s, g_W = sum (g_s.u alpha_b - g_s.v alpha_a) + g_delta / (H ss).
+ *   g_ctr / 2 goes to the first point with the largest and to the first with the smallest c on each axis, (1 + margin) g_W to the
+ *   first argmax of the longer axis and its negative to the first argmin (u on a tie).  grad_path_t = g_c[t] . (u, v) + g_height_l2
+ *   (n . p_t - height) / height_l2 n (0 where height_l2 == 0); the mean drops out because sum_t g_c[t] = 0.  T = 1: the image part is
+ *   exactly 0.  image_dev, window_dev, img_l2_dev, height_l2_dev (each optional) receive the forward outputs, bitwise
+ *   avae_stroke_render's; objective_dev [rows] (optional) g_img_l2 img_l2 + g_height_l2 height_l2.  A row with a non-finite
+ *   coordinate is NaN in its own outputs; a non-finite cotangent makes the image part of its own row NaN.  The per-point sums are
+ *   64-bit fixed-point integers at a scale taken from the row's own cotangents (csrc/avae_grad.h): a row's grad_path is the same
+ *   bits alone or among other rows, on any stream, on repetition and whichever optional outputs are asked for.
+ * avae_motion_fk_vjp: grad_traj[r][t][j] = (a_j x (tip - o_j)) . grad_path[r][t], a_j joint j's axis and o_j its origin in the base
+ *   frame -- the position rows of avae_motion_pose's Jacobian contracted on the fly; the [rows][T][6][D] tensor is never formed.
+ * avae_motion_eval_vjp: grad_params[r][d * Kb + k] = scale[d * Kb + k] sum_t phi[t][k] pass[r][t][d] grad_traj[r][t][d], pass = 1 where
+ *   the unclamped q of avae_motion_eval satisfies lo_d <= q <= hi_d (everywhere without limits_dev, and for a joint whose hi <= lo);
+ *   one fma chain over t per output.  The anchor term is constant in the parameters.
+ * avae_rows_adam: P independent problems of n <= 1024 dimensions, one launch.  With cost_dev [P]: where cost < best_cost, x is
+ *   copied into best_x and cost into best_cost first (x is where the cost was taken).  A row whose g holds a NaN or Inf then stays as
+ *   it is (x, m, v, t) and gets status 2.  Otherwise g is scaled by min(1, max_norm / |g|_2) (max_norm <= 0: not at all), t = t + 1,
+ *   m = beta1 m + (1 - beta1) g, v = beta2 v + (1 - beta2) g^2, x = x - lr (m / (1 - beta1^t)) / (sqrt(v / (1 - beta2^t)) + eps),
+ *   status 0.
+ * rows == 0 (P == 0) is a no-op.  Errors: as avae_stroke_render / avae_motion_fk / avae_motion_eval for the shared arguments; a NULL
+ * required pointer; a cotangent or an output of img_l2 / height_l2 without target_dev / height_dev; n outside [1, 1024], lr < 0,
+ * eps <= 0, beta outside [0, 1), cost_dev without best_cost_dev and best_x_dev.
+ * One launch each, no floating-point atomics, no scratch, nothing of the handle is read or written: the calls work on any replica and
+ * inside avae_use_averaged. */
+int avae_stroke_render_vjp(avae_handle* h, const float* path_dev, int32_t rows, int32_t T, const float* plane_dev,
+                           float half_width, float margin, int32_t H, int32_t ss,
+                           const float* target_dev, const float* height_dev,
+                           const float* g_image_dev, const float* g_img_l2_dev, const float* g_height_l2_dev,
+                           float* grad_path_dev, float* image_dev, float* window_dev, float* img_l2_dev, float* height_l2_dev,
+                           float* objective_dev, void* stream);
+int avae_motion_fk_vjp(avae_handle* h, const float* traj_dev, int32_t rows, int32_t T, int32_t D,
+                       const float* frames_dev, const float* axes_dev, const float* grad_path_dev, float* grad_traj_dev, void* stream);
+int avae_motion_eval_vjp(avae_handle* h, const float* params_dev, int32_t rows, int32_t D, int32_t Kb, int32_t T,
+                         const float* phi_dev, const float* scale_dev, const float* shift_dev, const float* limits_dev,
+                         const float* anchor_gain_dev, const float* anchor_target_dev, int32_t nc,
+                         const float* grad_traj_dev, float* grad_params_dev, void* stream);
+int avae_rows_adam(avae_handle* h, float* x_dev, const float* g_dev, float* m_dev, float* v_dev, int32_t* t_dev, int32_t* status_dev,
+                   int32_t P, int32_t n, float lr, float beta1, float beta2, float eps, float max_norm,
+                   const float* cost_dev, float* best_cost_dev, float* best_x_dev, void* stream);
+
 /* ---- letter thumbnails: from camera frames or drawing-pad canvases to the size x size pictures the image encoders were trained on
  * (DESIGN.md section 30).  The reference does this on the host for every input it is shown: the camera path thresholds the grey
  * frame at 108, inverts it and crops it to the ink (drawing_pad.py:185-193, writing_image_reader.py:64-97), the drawing pad converts

@@ -9,6 +9,8 @@ _LAZY = {"AssocVariationalAutoEncoder": "vae_assoc", "train": "vae_assoc", "xavi
          "GradSync": "parallel", "dp_train_step": "parallel",
          "linear_warmup": "_marshal", "cyclical": "_marshal", "exponential_decay": "_marshal",
          "occlude_quadrant": "vae_assoc",
+         "render_strokes_vjp": "vae_assoc", "motion_fk_vjp": "vae_assoc", "motion_eval_vjp": "vae_assoc", "rows_adam": "vae_assoc",
+         "writing_cost_grad": "vae_assoc", "descend_motion": "vae_assoc",
          "MotionBasis": "motion", "KinematicChain": "kinematics", "StrokeCanvas": "kinematics"}
 
 

@@ -656,6 +656,157 @@ def refine_motion_args(basis, chain, space, n_rollouts, modality, search_options
     return n_rollouts, dict(search_options)
 
 
+# ---------------------------------------------------------------------------------------------------- gradients of the writing chain
+def _row_values(v, rows, device, name):
+    """An optional per-row number: None, one number for every row or ``[rows]`` -> contiguous float32 tensor [rows] or None"""
+    if v is None:
+        return None
+    t = v if torch.is_tensor(v) else torch.as_tensor(np.asarray(v, dtype=np.float32))
+    if t.dim() == 0:
+        t = t.reshape(1).expand(rows)
+    if t.dim() != 1 or t.shape[0] != rows:
+        raise ValueError("%s must be a number or [%d] (as the paths), got %s" % (name, rows, tuple(t.shape)))
+    return t.to(device=device, dtype=torch.float32).contiguous()
+
+
+def render_vjp_args(path, canvas, target, height, g_image, g_img_l2, g_height_l2, device):
+    """The arguments of ``render_strokes_vjp`` -> (path [N, T, 3], plane, target, height, g_image [N, H * H], g_img_l2 [N],
+    g_height_l2 [N] (each or None), was_numpy).  A cotangent of a distance needs that distance's input."""
+    p, plane, tg, hg, was_np = render_args(path, canvas, target, height, device)
+    rows = int(p.shape[0])
+    if g_image is None and g_img_l2 is None and g_height_l2 is None:
+        raise ValueError("g_image, g_img_l2 and g_height_l2 are all None: there is nothing to differentiate")
+    if g_img_l2 is not None and tg is None:
+        raise ValueError("g_img_l2 needs target: img_l2 is the distance from it")
+    if g_height_l2 is not None and hg is None:
+        raise ValueError("g_height_l2 needs height: height_l2 is the distance from it")
+    gi = dev_dense(g_image, canvas.n_pixels, device, rows, "as the paths", name="g_image")
+    return p, plane, tg, hg, gi, _row_values(g_img_l2, rows, device, "g_img_l2"), _row_values(g_height_l2, rows, device, "g_height_l2"), was_np
+
+
+def motion_fk_vjp_args(trajectories, chain, grad_path, device):
+    """The arguments of ``motion_fk_vjp`` -> (trajectories [N, T, n_dof], frames, axes, grad_path [N, T, 3], was_numpy)."""
+    t, frames, axes, was_np = motion_fk_args(trajectories, chain, device)
+    if grad_path is None:
+        raise ValueError("grad_path is None: the cotangent of the pen path is needed")
+    g, _ = dev_block3(grad_path, (int(t.shape[1]), 3), device, "grad_path", int(t.shape[0]))
+    return t, frames, axes, g, was_np
+
+
+def motion_eval_vjp_args(params, basis, anchor, grad_trajectory, device):
+    """The arguments of ``motion_eval_vjp`` -> (params [N, P], matrices, grad_trajectory [N, n_points, n_dof], was_numpy)."""
+    p, mats, _, _, was_np = motion_eval_args(params, basis, anchor, None, None, device)
+    if grad_trajectory is None:
+        raise ValueError("grad_trajectory is None: the cotangent of the trajectory is needed")
+    g, _ = dev_block3(grad_trajectory, (basis.n_points, basis.n_dof), device, "grad_trajectory", int(p.shape[0]))
+    return p, mats, g, was_np
+
+
+def cost_weights(weights):
+    """The two weights of the differentiable writing cost ``w0 (img_l2 + w1 height_l2)`` -> floats"""
+    try:
+        w = [float(x) for x in weights]
+    except (TypeError, ValueError):
+        raise ValueError("weights must be two numbers (image, height), got %r" % (weights,))
+    if len(w) != 2 or not all(np.isfinite(w)):
+        raise ValueError("weights must be two finite numbers (image, height), got %r" % (weights,))
+    return w
+
+
+ADAM_STATE_KEYS = ("m", "v", "t", "best_x", "best_cost")
+
+
+def adam_options(lr, betas, eps, max_norm):
+    """The options of ``rows_adam`` checked -> (lr, beta1, beta2, eps, max_norm; 0 = no clipping) as floats"""
+    def number(v, name):
+        if not _is_number(v) or not np.isfinite(v):
+            raise ValueError("%s must be a finite number, got %r" % (name, v))
+        return float(v)
+    lr = number(lr, "lr")
+    if lr < 0:
+        raise ValueError("lr must be >= 0, got %r" % (lr,))
+    if not isinstance(betas, (tuple, list)) or len(betas) != 2:
+        raise ValueError("betas must be two numbers in [0, 1), got %r" % (betas,))
+    b1, b2 = number(betas[0], "betas[0]"), number(betas[1], "betas[1]")
+    if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0) or float(np.float32(b1)) >= 1.0 or float(np.float32(b2)) >= 1.0:
+        raise ValueError("betas must be two numbers in [0, 1), got %r" % (betas,))
+    eps = number(eps, "eps")
+    if eps <= 0:
+        raise ValueError("eps must be > 0, got %r" % (eps,))
+    mn = 0.0
+    if max_norm is not None:
+        mn = number(max_norm, "max_norm")
+        if mn <= 0:
+            raise ValueError("max_norm must be None or > 0, got %r" % (max_norm,))
+    return lr, b1, b2, eps, mn
+
+
+def rows_adam_args(x, grad, state, cost, device):
+    """The arrays of ``rows_adam`` -> (x [P, n] (a copy), grad [P, n], state: a fresh one or a copy of ``state``, cost [P] or None,
+    was_numpy).  Values of device tensors are not looked at."""
+    was_np = not torch.is_tensor(x)
+    xt = torch.as_tensor(np.asarray(x, dtype=np.float32)) if was_np else x
+    if xt.dim() != 2 or not 1 <= xt.shape[1] <= _capi.ROWS_ADAM_MAX_DIMS:
+        raise ValueError("x must be [P, n] with n in [1, %d], got %s" % (_capi.ROWS_ADAM_MAX_DIMS, tuple(xt.shape)))
+    xt = xt.to(device=device, dtype=torch.float32).clone().contiguous()
+    P, n = int(xt.shape[0]), int(xt.shape[1])
+    g = dev_dense(grad, n, device, P, "as x", name="grad")
+    if g is None:
+        raise ValueError("grad is None: the step needs the gradient")
+    c = _row_values(cost, P, device, "cost")
+    if state is None:
+        st = dict(m=torch.zeros((P, n), dtype=torch.float32, device=device), v=torch.zeros((P, n), dtype=torch.float32, device=device),
+                  t=torch.zeros(P, dtype=torch.int32, device=device), best_x=xt.clone(),
+                  best_cost=torch.full((P,), float("inf"), dtype=torch.float32, device=device))
+    else:
+        if not isinstance(state, dict) or set(state) != set(ADAM_STATE_KEYS):
+            raise ValueError("state must be the dict a rows_adam step returned (keys %s)" % ", ".join(ADAM_STATE_KEYS))
+        st = {}
+        for k, shape, dt in (("m", (P, n), torch.float32), ("v", (P, n), torch.float32), ("best_x", (P, n), torch.float32),
+                             ("best_cost", (P,), torch.float32), ("t", (P,), torch.int32)):
+            t = state[k]
+            if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dt:
+                raise ValueError("state[%r] must be a %s tensor of shape %s" % (k, dt, shape))
+            st[k] = t.to(device).clone().contiguous()
+    return xt, g, st, c, was_np
+
+
+DESCENT_STATE_KEYS = ("params", "adam", "height", "anchor", "iteration")
+
+
+def descend_motion_args(basis, chain, canvas, n_iters, lr, max_norm, anchor_start, weights, modality, image_modality, widths):
+    """``descend_motion``'s own arguments checked -> (n_iters, Adam options, the two weights)"""
+    _check_writer(basis, chain, canvas)
+    as_index(modality, "modality", len(widths))
+    as_index(image_modality, "image_modality", len(widths))
+    _fits_params(basis, modality, widths)
+    _fits_pixels(canvas, image_modality, widths)
+    if basis.n_params > _capi.ROWS_ADAM_MAX_DIMS:
+        raise ValueError("basis.n_params = %d must be at most %d" % (basis.n_params, _capi.ROWS_ADAM_MAX_DIMS))
+    if not isinstance(anchor_start, (bool, np.bool_)):
+        raise ValueError("anchor_start must be True or False, got %r" % (anchor_start,))
+    return as_int(n_iters, "n_iters", 0, 1 << 30), adam_options(lr, (0.9, 0.999), 1e-8, max_norm), cost_weights(weights)
+
+
+def descent_state(state, P, basis, device):
+    """The ``state`` a ``descend_motion`` returned, checked -> a copy of it on ``device``"""
+    if not isinstance(state, dict) or set(state) != set(DESCENT_STATE_KEYS):
+        raise ValueError("state must be the dict a descend_motion returned (keys %s)" % ", ".join(DESCENT_STATE_KEYS))
+    n, D = basis.n_params, basis.n_dof
+    out = {"iteration": as_int(state["iteration"], "state['iteration']", 0)}
+    for k, shape in (("params", (P, n)), ("height", (P,))):
+        t = state[k]
+        if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != torch.float32:
+            raise ValueError("state[%r] must be a float32 tensor of shape %s" % (k, shape))
+        out[k] = t.to(device).clone().contiguous()
+    a = state["anchor"]
+    if a is not None and (not torch.is_tensor(a) or tuple(a.shape) != (P, D, 1) or a.dtype != torch.float32):
+        raise ValueError("state['anchor'] must be None or a float32 tensor of shape %s" % ((P, D, 1),))
+    out["anchor"] = None if a is None else a.to(device).clone().contiguous()
+    out["adam"] = rows_adam_args(out["params"], out["params"], state["adam"], None, device)[2]
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------- inverse kinematics
 IK_MAX_ITERS = _capi.IK_MAX_ITERS
 

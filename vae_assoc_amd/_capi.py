@@ -56,6 +56,7 @@ SYMBOLS = [
     "avae_embed_calibrate", "avae_embed_iterate", "avae_embed_plan",
     "avae_motion_eval", "avae_motion_fit", "avae_motion_moments",
     "avae_motion_fk", "avae_stroke_render",
+    "avae_stroke_render_vjp", "avae_motion_fk_vjp", "avae_motion_eval_vjp", "avae_rows_adam",
     "avae_letter_thumbnail", "avae_letter_thumbnail_plan",
     "avae_motion_pose", "avae_motion_ik",
     "avae_lognormal_eval", "avae_lognormal_sample", "avae_lognormal_fit",
@@ -105,6 +106,7 @@ class LatentStatsOut(C.Structure):
 
 
 SEARCH_MAX_DIMS, SEARCH_MAX_ROLLOUTS, SEARCH_MAX_GROUP = 1024, 1024, 64
+ROWS_ADAM_MAX_DIMS = 1024
 SEARCH_IDS = {"PI-BB": 0, "CEM": 1, "CMA-ES": 2}
 
 
@@ -199,6 +201,12 @@ def lib():
             L.avae_motion_moments.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
             L.avae_motion_fk.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp]
             L.avae_stroke_render.argtypes = [vp, vp, i32, i32, vp, C.c_float, C.c_float, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+            L.avae_stroke_render_vjp.argtypes = [vp, vp, i32, i32, vp, C.c_float, C.c_float, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                 vp, vp]
+            L.avae_motion_fk_vjp.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]
+            L.avae_motion_eval_vjp.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]
+            L.avae_rows_adam.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                         vp, vp, vp, vp]
             L.avae_letter_thumbnail_plan.argtypes = [i32, i32, i32, C.POINTER(i32), C.POINTER(sz)]
             L.avae_letter_thumbnail.argtypes = [vp, vp, i32, i32, i32, i32, C.c_int64, C.c_int64, i32, i32, i32, vp, sz, vp, vp, vp, vp, vp]
             L.avae_motion_pose.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]

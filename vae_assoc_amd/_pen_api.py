@@ -4,18 +4,23 @@ strokes.
 
 ``PenAPI`` is a mixin of ``vae_assoc.AssocVariationalAutoEncoder``: its methods reach the model through ``self`` alone
 (``_encode``, ``_decode``, ``_fused_decode``, ``_call``, ``_out``, ``_like_input``), and this module imports nothing from
-``vae_assoc``.  They are what the reference's writer scripts do around the model, for many rows at once."""
+``vae_assoc``.  They are what the reference's writer scripts do around the model, for many rows at once.
+
+The gradients of the writing chain stand behind the class as functions of a model: ``render_strokes_vjp``,
+``motion_fk_vjp``, ``motion_eval_vjp``, ``rows_adam``, ``writing_cost_grad``, ``descend_motion``."""
 import ctypes as C
 
 import numpy as np
 import torch
 
-from ._args import (THUMBNAIL_CAMERA, THUMBNAIL_CANVAS, TRACK_FACTOR, TRACK_LAM_MAX, TRACK_LAM_MIN, _same_joints, canvas_args,
-                    chain_matrices, check_solver, draw_args, letter_thumbnail_args, lognormal_augment_args, lognormal_eval_args,
-                    lognormal_fit_args, lognormal_sample_options, motion_eval_args, motion_fit_args, motion_fk_args, motion_ik_args,
-                    motion_matrices, motion_moments_args, motion_pose_args, motion_track_args, predict_motion_args,
-                    refine_motion_args, refine_pen_path_args, render_args, search_args, strokes_to_motion_args,
-                    track_rows_per_call, writing_cost_args)
+from ._args import (THUMBNAIL_CAMERA, THUMBNAIL_CANVAS, TRACK_FACTOR, TRACK_LAM_MAX, TRACK_LAM_MIN, _same_joints,
+                    adam_options, canvas_args, chain_matrices, check_solver, cost_weights, descend_motion_args,
+                    descent_state, draw_args, letter_thumbnail_args, lognormal_augment_args, lognormal_eval_args,
+                    lognormal_fit_args, lognormal_sample_options, motion_eval_args, motion_eval_vjp_args, motion_fit_args,
+                    motion_fk_args, motion_fk_vjp_args, motion_ik_args, motion_matrices, motion_moments_args,
+                    motion_pose_args, motion_track_args, predict_motion_args, refine_motion_args, refine_pen_path_args,
+                    render_args, render_vjp_args, rows_adam_args, search_args, strokes_to_motion_args, track_rows_per_call,
+                    writing_cost_args)
 from ._marshal import as_index, dev_array, dev_dense, ptr, row_chunks, to_device32
 from .motion import MotionBasis
 
@@ -821,3 +826,194 @@ class PenAPI(object):
         out = torch.where(failed[:, None, None, None], torch.full_like(out, float("nan")), out)
         conv = self._like_input(was_np)
         return {"strokes": conv(out), "params": conv(p), "count": conv(cnt), "perturbed": conv(pert), "status": conv(status)}
+
+
+# ---------------------------------------------------------------------- gradients of the writing chain
+# Functions of a model, not methods: the class's surface is pinned name by name (tests/test_surface_cpu.py), and these reach the
+# model through the same few members the mixin's methods use (``_call``, ``_out``, ``_like_input``, ``_motion_eval``, ``_motion_fk``,
+# ``_render``, ``_encode``, ``_decode``).  ``vae_assoc_amd.vae_assoc`` and the package export the six public ones.
+def _render_vjp(model, p, plane, canvas, target, height, g_image, g_img_l2, g_height_l2, objective=None):
+    """avae_stroke_render_vjp on device tensors -> dict of device tensors: ``grad_path`` and the forward outputs (``img_l2`` /
+    ``height_l2`` None without their input); ``objective [N]`` is filled in place where given"""
+    N, T, H = p.shape[0], p.shape[1], canvas.size
+    grad = model._out((N, T, 3))
+    image, window = model._out((N, H * H)), model._out((N, 3))
+    l2 = None if target is None else model._out(N)
+    hl2 = None if height is None else model._out(N)
+    if N:
+        model._call("avae_stroke_render_vjp", p.data_ptr(), N, T, plane.data_ptr(), canvas.half_width, canvas.margin, H,
+                    canvas.supersample, ptr(target), ptr(height), ptr(g_image), ptr(g_img_l2), ptr(g_height_l2), grad.data_ptr(),
+                    image.data_ptr(), window.data_ptr(), ptr(l2), ptr(hl2), ptr(objective))
+    return {"grad_path": grad, "image": image, "window": window, "img_l2": l2, "height_l2": hl2}
+
+
+def _motion_fk_vjp(model, t, frames, axes, g):
+    """avae_motion_fk_vjp on device tensors: trajectories [N, T, D] and the path's cotangent [N, T, 3] -> [N, T, D]"""
+    N, T, D = t.shape
+    out = model._out((N, T, D))
+    if N:
+        model._call("avae_motion_fk_vjp", t.data_ptr(), N, T, D, frames.data_ptr(), axes.data_ptr(), g.data_ptr(), out.data_ptr())
+    return out
+
+
+def _motion_eval_vjp(model, p, mats, basis, g):
+    """avae_motion_eval_vjp on device tensors: parameters [N, P] and the trajectory's cotangent [N, T, D] -> [N, P]"""
+    N = p.shape[0]
+    out = model._out((N, basis.n_params))
+    if N:
+        model._call("avae_motion_eval_vjp", p.data_ptr(), N, basis.n_dof, basis.n_kb, basis.n_points, mats["phi"].data_ptr(),
+                    ptr(mats["scale"]), ptr(mats["shift"]), ptr(mats["limits"]), ptr(mats["gain"]), ptr(mats["target"]), mats["nc"],
+                    g.data_ptr(), out.data_ptr())
+    return out
+
+
+def _rows_adam(model, x, g, st, status, opts, cost=None):
+    """avae_rows_adam in place on ``x [P, n]`` and the state ``st`` (``rows_adam_args``'); ``cost [P]`` feeds the best-so-far"""
+    P, n = x.shape
+    lr, b1, b2, eps, mn = opts
+    if P:
+        model._call("avae_rows_adam", x.data_ptr(), g.data_ptr(), st["m"].data_ptr(), st["v"].data_ptr(), st["t"].data_ptr(),
+                    status.data_ptr(), P, n, lr, b1, b2, eps, mn, ptr(cost), ptr(None if cost is None else st["best_cost"]),
+                    ptr(None if cost is None else st["best_x"]))
+
+
+def render_strokes_vjp(model, path, canvas, g_image=None, g_img_l2=None, g_height_l2=None, target=None, height=None):
+    """The vector-Jacobian product of ``render_strokes`` (avae_stroke_render_vjp in include/avae.h): the gradient of
+    ``sum g_image . image + g_img_l2 img_l2 + g_height_l2 height_l2`` with respect to ``path [N, T, 3]``.  ``g_image`` is
+    ``[N, size * size]``, ``g_img_l2`` and ``g_height_l2`` ``[N]`` or one number; each may be None, and a distance's cotangent
+    needs ``target`` / ``height`` as ``render_strokes`` takes them.  The renderer is piecewise smooth: the gradient is the one
+    of the piece the path lies in (which segment is nearest to a sample, which points are the outermost, which samples lie on
+    the edge ramp).  Returns ``render_strokes``' dict with ``grad_path [N, T, 3]`` added; the forward outputs are bitwise
+    ``render_strokes``'.  A row's gradient is the same bits alone or among other rows and on repetition."""
+    p, plane, tg, hg, gi, gl, gh, was_np = render_vjp_args(path, canvas, target, height, g_image, g_img_l2, g_height_l2,
+                                                           model.device)
+    conv = model._like_input(was_np)
+    return {k: conv(v) for k, v in _render_vjp(model, p, plane, canvas, tg, hg, gi, gl, gh).items()}
+
+
+def motion_fk_vjp(model, trajectories, chain, grad_path):
+    """The vector-Jacobian product of ``motion_fk`` (avae_motion_fk_vjp): the pen path's cotangent ``grad_path [N, T, 3]`` ->
+    the joint angles' ``[N, T, chain.n_dof]``, ``(axis_j x (tip - origin_j)) . grad_path`` per joint -- the position rows of
+    ``motion_pose``'s Jacobian, contracted without ever forming them."""
+    t, frames, axes, g, was_np = motion_fk_vjp_args(trajectories, chain, grad_path, model.device)
+    return model._like_input(was_np)(_motion_fk_vjp(model, t, frames, axes, g))
+
+
+def motion_eval_vjp(model, params, basis, grad_trajectory, anchor=None):
+    """The vector-Jacobian product of ``motion_eval`` (avae_motion_eval_vjp): the trajectory's cotangent ``grad_trajectory
+    [N, n_points, n_dof]`` -> the standardised parameters' ``[N, basis.n_params]``.  A point the joint limits clamped passes
+    nothing on; ``anchor`` as in ``motion_eval`` (its target is a constant of the parameters)."""
+    p, mats, g, was_np = motion_eval_vjp_args(params, basis, anchor, grad_trajectory, model.device)
+    return model._like_input(was_np)(_motion_eval_vjp(model, p, mats, basis, g))
+
+
+def rows_adam(model, x, grad, state=None, lr=0.05, betas=(0.9, 0.999), eps=1e-8, max_norm=None, cost=None):
+    """One Adam step for P independent problems at once (avae_rows_adam): ``x`` and ``grad`` are ``[P, n]``, n <= 1024.  A row
+    whose gradient holds a NaN or Inf is left as it is (status 2); otherwise the gradient is scaled by ``min(1, max_norm /
+    |grad|)`` (``max_norm`` None: not at all) and the bias-corrected update uses the row's own step count.  ``cost [P]`` is the
+    cost at ``x``: where it is below the state's ``best_cost``, ``x`` is kept as ``best_x`` first.  Returns a dict of ``x`` (the
+    new point; the input is not changed), ``status [P]`` (int32) and ``state`` (``m``, ``v``, ``t``, ``best_x``, ``best_cost`` on
+    the device) to pass to the next step."""
+    opts = adam_options(lr, betas, eps, max_norm)
+    xt, g, st, c, was_np = rows_adam_args(x, grad, state, cost, model.device)
+    status = torch.zeros(xt.shape[0], dtype=torch.int32, device=model.device)
+    _rows_adam(model, xt, g, st, status, opts, c)
+    conv = model._like_input(was_np)
+    return {"x": conv(xt), "status": conv(status), "state": st}
+
+
+def _cost_cotangents(model, w, N):
+    """the cotangents of ``img_l2`` and ``height_l2`` under ``cost = w0 (img_l2 + w1 height_l2)``, [N] each"""
+    return (torch.full((N,), w[0], dtype=torch.float32, device=model.device),
+            torch.full((N,), w[0] * w[1], dtype=torch.float32, device=model.device))
+
+
+def writing_cost_grad(model, params, basis, chain, canvas, target_image, height=None, weights=(0.3, 10.0), anchor=None):
+    """The differentiable part of ``writing_cost`` and its gradient: ``cost = w0 (img_l2 + w1 height_l2)`` of the drawing of
+    each row of ``params`` against ``target_image``, and ``grad [N, n_params]``, its derivative with respect to the
+    standardised parameters -- ``motion_eval``, ``motion_fk`` and the three reverse launches, at about the price of two
+    drawings.  ``height=None`` is the row's own mean height, as in ``writing_cost`` (the mean's own derivative vanishes: the
+    residuals sum to 0).  The latent term of ``writing_cost`` is not part of this cost: its gradient needs the encoder's
+    derivative with respect to its input, which no launch of the library forms.  Returns a dict of ``cost``, ``img_l2``,
+    ``height_l2 [N]``, ``grad`` and ``image``; the three forward pieces are bitwise ``draw_motion``'s."""
+    w = cost_weights(weights)
+    if target_image is None:
+        raise ValueError("target_image is None: the cost needs the picture to compare with")
+    p, mats, frames, axes, plane, tg, hg, was_np = draw_args(params, basis, chain, canvas, anchor, target_image, height,
+                                                             model.device)
+    traj = model._motion_eval(p, mats, basis)[0]
+    path = model._motion_fk(traj, frames, axes)
+    if hg is None:
+        hg = (path @ plane[2]).mean(1).contiguous()
+    gl, gh = _cost_cotangents(model, w, int(p.shape[0]))
+    out = _render_vjp(model, path, plane, canvas, tg, hg, None, gl, gh)
+    grad = _motion_eval_vjp(model, p, mats, basis, _motion_fk_vjp(model, traj, frames, axes, out["grad_path"]))
+    cost = w[0] * (out["img_l2"] + w[1] * out["height_l2"])
+    conv = model._like_input(was_np)
+    return {"cost": conv(cost), "img_l2": conv(out["img_l2"]), "height_l2": conv(out["height_l2"]), "grad": conv(grad),
+            "image": conv(out["image"])}
+
+
+def descend_motion(model, target_image, basis, chain, canvas, init=None, n_iters=50, lr=0.05, max_norm=None, anchor_start=True,
+                   weights=(0.3, 10.0), modality=1, state=None, image_modality=0):
+    """Gradient refinement of a written motion for P pictures at once: Adam on ``writing_cost_grad``'s cost, the descent
+    ``refine_motion(space='params')`` searches for.
+
+    It starts where that search starts: the motion decoded from the encoding of ``target_image [P, n_pixels]`` (or ``init
+    [P, n_params]``), priced at the mean pen height of that first motion; with ``anchor_start`` the parameters are read
+    through the projection onto starting where the first trajectory starts (``motion_eval``'s ``anchor``).  An iteration is
+    six launches -- ``motion_eval``, ``motion_fk``, the three reverse passes and ``rows_adam`` (``lr``, ``max_norm``) -- and
+    nothing is read back to the host inside the loop.
+
+    Returns a dict: ``params`` (after the last step) and ``best_params [P, n_params]`` (the cheapest point visited, the
+    last included), ``cost``, ``img_l2``, ``height_l2`` and ``image`` at ``params``, ``best_cost [P]`` and ``best_image``,
+    ``history [n_iters + 1, P]`` (the cost before every step and after the last), ``status [P]`` (int32, of the last step:
+    0, or 2 where the gradient was not finite and the row stayed), ``height [P]`` and ``state``.
+    ``descend_motion(..., state=state)`` continues the run (``init`` is then ignored): k iterations and then m more are the
+    bits of k + m.  NumPy in gives NumPy out (``state`` stays on the device)."""
+    n_iters, opts, w = descend_motion_args(basis, chain, canvas, n_iters, lr, max_norm, anchor_start, weights, modality,
+                                           image_modality, model._widths)
+    if target_image is None:
+        raise ValueError("target_image is None: the refinement needs the pictures to write")
+    tg, was_np = dev_array(target_image, canvas.n_pixels, model.device)
+    tg = tg.contiguous()
+    P = int(tg.shape[0])
+    frames, axes = chain_matrices(chain, model.device)
+    plane = canvas_args(canvas, P, None, None, model.device)[0]
+    if state is None:
+        p0 = dev_dense(init, basis.n_params, model.device, P, "as target_image", name="init")
+        if p0 is None:
+            p0 = model._decode(modality, model._encode(image_modality, tg))
+        traj0 = model._motion_eval(p0, motion_matrices(basis, model.device), basis)[0]
+        h0 = (model._motion_fk(traj0, frames, axes) @ plane[2]).mean(1).contiguous()
+        st = dict(params=p0.clone().contiguous(), height=h0, iteration=0,
+                  anchor=traj0[:, 0, :].reshape(P, basis.n_dof, 1).contiguous() if anchor_start else None,
+                  adam=rows_adam_args(p0, p0, None, None, model.device)[2])
+    else:
+        st = descent_state(state, P, basis, model.device)
+    anchor = None if st["anchor"] is None else dict(phases=[0.0], target=st["anchor"])
+    mats = motion_matrices(basis, model.device, anchor, P)
+    x, h0, adam = st["params"], st["height"], st["adam"]
+    gl, gh = _cost_cotangents(model, w, P)
+    hist = torch.full((n_iters + 1, P), float("nan"), dtype=torch.float32, device=model.device)
+    status = torch.zeros(P, dtype=torch.int32, device=model.device)
+
+    def reverse(i):
+        traj = model._motion_eval(x, mats, basis)[0]
+        out = _render_vjp(model, model._motion_fk(traj, frames, axes), plane, canvas, tg, h0, None, gl, gh, hist[i])
+        return traj, out
+    for i in range(n_iters if P else 0):
+        traj, out = reverse(i)
+        g = _motion_eval_vjp(model, x, mats, basis, _motion_fk_vjp(model, traj, frames, axes, out["grad_path"]))
+        _rows_adam(model, x, g, adam, status, opts, hist[i])
+    st["iteration"] += n_iters
+    _, last = reverse(n_iters)
+    better = hist[n_iters] < adam["best_cost"]
+    best_x = torch.where(better[:, None], x, adam["best_x"])
+    best_cost = torch.where(better, hist[n_iters], adam["best_cost"])
+    best = model._render(model._motion_fk(model._motion_eval(best_x, mats, basis)[0], frames, axes), plane, canvas, None, None)
+    conv = model._like_input(was_np)
+    return {"params": conv(x.clone()), "best_params": conv(best_x), "cost": conv(hist[n_iters].clone()),
+            "img_l2": conv(last["img_l2"]), "height_l2": conv(last["height_l2"]), "image": conv(last["image"]),
+            "best_cost": conv(best_cost), "best_image": conv(best["image"]), "history": conv(hist), "status": conv(status),
+            "height": conv(h0), "state": st}

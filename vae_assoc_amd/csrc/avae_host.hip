@@ -6,6 +6,7 @@
 #include "avae_latent_stats.h"
 #include "avae_motion.h"
 #include "avae_render.h"
+#include "avae_grad.h"
 #include "avae_thumbnail.h"
 #include "avae_ik.h"
 #include "avae_lognormal.h"
@@ -4856,6 +4857,103 @@ int avae_stroke_render(avae_handle* h, const float* path_dev, int32_t rows, int3
         a.half_width = half_width; a.margin = margin; a.T = T; a.H = H; a.ss = ss;
         hipStream_t s = on_stream(h, stream);
         timed_launch(h, s, "stroke_render", [&] { launch_stroke_render(a, rows, s); });
+    });
+}
+
+// ---- gradients through the writing chain (include/avae.h, avae_grad.h)
+int avae_stroke_render_vjp(avae_handle* h, const float* path_dev, int32_t rows, int32_t T, const float* plane_dev,
+                           float half_width, float margin, int32_t H, int32_t ss,
+                           const float* target_dev, const float* height_dev,
+                           const float* g_image_dev, const float* g_img_l2_dev, const float* g_height_l2_dev,
+                           float* grad_path_dev, float* image_dev, float* window_dev, float* img_l2_dev, float* height_l2_dev,
+                           float* objective_dev, void* stream) {
+    return guarded(h, [&] {
+        const std::string w = "avae_stroke_render_vjp";
+        check_rows(w, rows, "rows");
+        check_range(w, "T", T, 1, kRenderMaxT);
+        check_range(w, "H", H, 1, kRenderMaxH);
+        if (ss != 1 && ss != 2 && ss != 4 && ss != 8) throw Err(w + ": ss = " + std::to_string(ss) + " must be 1, 2, 4 or 8");
+        check_finite(w, "half_width", half_width, true);
+        check_finite(w, "margin", margin, false);
+        need(w, path_dev, "path_dev"); need(w, plane_dev, "plane_dev"); need(w, grad_path_dev, "grad_path_dev");
+        if ((img_l2_dev || g_img_l2_dev) && !target_dev) throw Err(w + ": img_l2_dev and g_img_l2_dev need target_dev");
+        if ((height_l2_dev || g_height_l2_dev) && !height_dev) throw Err(w + ": height_l2_dev and g_height_l2_dev need height_dev");
+        if (render_vjp_lds_bytes(T, H) > kMaxDynLds) throw Err("internal error: " + w + " plans more LDS than its bound");
+        if (rows == 0) return;
+        RenderVjpArgs a = zeroed<RenderVjpArgs>();
+        a.f.path = path_dev; a.f.plane = plane_dev; a.f.target = (img_l2_dev || g_img_l2_dev) ? target_dev : nullptr;
+        a.f.height = (height_l2_dev || g_height_l2_dev) ? height_dev : nullptr;
+        a.f.image = image_dev; a.f.window = window_dev; a.f.img_l2 = img_l2_dev; a.f.height_l2 = height_l2_dev;
+        a.f.half_width = half_width; a.f.margin = margin; a.f.T = T; a.f.H = H; a.f.ss = ss;
+        a.g_image = g_image_dev; a.g_img_l2 = g_img_l2_dev; a.g_height_l2 = g_height_l2_dev;
+        a.grad_path = grad_path_dev; a.objective = objective_dev;
+        hipStream_t s = on_stream(h, stream);
+        timed_launch(h, s, "stroke_render_vjp", [&] { launch_stroke_render_vjp(a, rows, s); });
+    });
+}
+
+int avae_motion_fk_vjp(avae_handle* h, const float* traj_dev, int32_t rows, int32_t T, int32_t D,
+                       const float* frames_dev, const float* axes_dev, const float* grad_path_dev, float* grad_traj_dev, void* stream) {
+    return guarded(h, [&] {
+        const std::string w = "avae_motion_fk_vjp";
+        check_rows(w, rows, "rows");
+        check_range(w, "T", T, 1, kRenderMaxT);
+        check_range(w, "D", D, 1, kFkMaxD);
+        need(w, traj_dev, "traj_dev"); need(w, frames_dev, "frames_dev"); need(w, axes_dev, "axes_dev");
+        need(w, grad_path_dev, "grad_path_dev"); need(w, grad_traj_dev, "grad_traj_dev");
+        if (rows == 0) return;
+        FkVjpArgs a = zeroed<FkVjpArgs>();
+        a.traj = traj_dev; a.frames = frames_dev; a.axes = axes_dev; a.grad_path = grad_path_dev; a.grad_traj = grad_traj_dev;
+        a.points = (long long)rows * T; a.D = D;
+        hipStream_t s = on_stream(h, stream);
+        timed_launch(h, s, "motion_fk_vjp", [&] { launch_motion_fk_vjp(a, s); });
+    });
+}
+
+int avae_motion_eval_vjp(avae_handle* h, const float* params_dev, int32_t rows, int32_t D, int32_t Kb, int32_t T,
+                         const float* phi_dev, const float* scale_dev, const float* shift_dev, const float* limits_dev,
+                         const float* anchor_gain_dev, const float* anchor_target_dev, int32_t nc,
+                         const float* grad_traj_dev, float* grad_params_dev, void* stream) {
+    return guarded(h, [&] {
+        const std::string w = "avae_motion_eval_vjp";
+        check_motion_shape(w, rows, D, Kb, T, nc);
+        need(w, params_dev, "params_dev"); need(w, phi_dev, "phi_dev");
+        need(w, grad_traj_dev, "grad_traj_dev"); need(w, grad_params_dev, "grad_params_dev");
+        if (nc > 0 && !anchor_gain_dev) throw Err(w + ": anchor_gain_dev is NULL with nc > 0");
+        if (nc > 0 && !anchor_target_dev) throw Err(w + ": anchor_target_dev is NULL with nc > 0");
+        if (rows == 0) return;
+        static_assert(kFitSlab * kMotionMaxNc <= 1024 && kMotionMaxD * kMotionMaxKb % kMotionThreads == 0, "k_motion_eval_vjp's tiles");
+        MotionVjpArgs a = zeroed<MotionVjpArgs>();
+        a.params = params_dev; a.phi = phi_dev; a.scale = scale_dev; a.shift = shift_dev; a.limits = limits_dev;
+        a.gain = nc > 0 ? anchor_gain_dev : nullptr; a.target = nc > 0 ? anchor_target_dev : nullptr;
+        a.grad_traj = grad_traj_dev; a.grad_params = grad_params_dev;
+        a.rows = rows; a.D = D; a.Kb = Kb; a.T = T; a.nc = nc;
+        hipStream_t s = on_stream(h, stream);
+        timed_launch(h, s, "motion_eval_vjp", [&] { launch_motion_eval_vjp(a, s); });
+    });
+}
+
+int avae_rows_adam(avae_handle* h, float* x_dev, const float* g_dev, float* m_dev, float* v_dev, int32_t* t_dev, int32_t* status_dev,
+                   int32_t P, int32_t n, float lr, float beta1, float beta2, float eps, float max_norm,
+                   const float* cost_dev, float* best_cost_dev, float* best_x_dev, void* stream) {
+    return guarded(h, [&] {
+        const std::string w = "avae_rows_adam";
+        check_rows(w, P, "P");
+        check_range(w, "n", n, 1, kRowsAdamMaxN);
+        check_finite(w, "lr", lr, false);
+        check_finite(w, "eps", eps, true);
+        if (!(beta1 >= 0.0f && beta1 < 1.0f) || !(beta2 >= 0.0f && beta2 < 1.0f)) throw Err(w + ": beta1 and beta2 must be in [0, 1)");
+        if (std::isnan(max_norm)) throw Err(w + ": max_norm must not be NaN (<= 0: no clipping)");
+        need(w, x_dev, "x_dev"); need(w, g_dev, "g_dev"); need(w, m_dev, "m_dev"); need(w, v_dev, "v_dev");
+        need(w, t_dev, "t_dev"); need(w, status_dev, "status_dev");
+        if (cost_dev && (!best_cost_dev || !best_x_dev)) throw Err(w + ": cost_dev needs best_cost_dev and best_x_dev");
+        if (P == 0) return;
+        RowsAdamArgs a = zeroed<RowsAdamArgs>();
+        a.x = x_dev; a.g = g_dev; a.m = m_dev; a.v = v_dev; a.t = t_dev; a.status = status_dev;
+        a.cost = cost_dev; a.best_cost = cost_dev ? best_cost_dev : nullptr; a.best_x = cost_dev ? best_x_dev : nullptr;
+        a.n = n; a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.max_norm = max_norm;
+        hipStream_t s = on_stream(h, stream);
+        timed_launch(h, s, "rows_adam", [&] { launch_rows_adam(a, P, s); });
     });
 }
 

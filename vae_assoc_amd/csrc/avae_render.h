@@ -36,7 +36,8 @@
 //   that is not inked would get +0 from every sample, which is what the image holds from the start.
 //   LDS: 28 T + 6 H^2 bytes + 6.8 KiB (14.3 KiB at T = 100, H = 28: the 32 waves of a CU, not LDS, bound its 8 workgroups; 59.0 KiB
 //   at T = 1024, H = 64), 39 / 39 / 45 / 49 VGPRs at ss = 1 / 2 / 4 / 8, no scratch.
-// Neither kernel uses atomics or scratch memory or reads or writes anything of the handle.
+// Neither kernel uses atomics or scratch memory or reads or writes anything of the handle.  k_stroke_render's device code lives in
+// avae_render_dev.h (render_row), which the reverse pass of avae_grad.hip runs too.
 #pragma once
 #include "avae_latent_common.h"
 
