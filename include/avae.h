@@ -1016,6 +1016,34 @@ int avae_motion_ik(avae_handle* h, const float* path_dev, int32_t rows, int32_t 
                    float* traj_dev, float* residual_dev, float* rot_residual_dev, int32_t* iterations_dev, int32_t* status_dev,
                    void* stream);
 
+/* ---- joint-space inertia and inverse dynamics of the chain.  The reference takes inertia(q), coriolis(q, v) and
+ * gravity(q) from KDL's ChainDynParam (baxter_dynamics, baxter_pykdl_revised.py:218-296) and prices a control u_t of its iLQR by
+ * |M(q_t) u_t|^2 (baxter_writer.py:112-126).  This call is the project's own statement of the rigid-body dynamics of a serial chain
+ * of revolute joints, for every (row, time point) at once, not a copy of KDL's.  Dense device fp32; gravity is a host vector.
+ * The chain is avae_motion_pose's (frames_dev [D + 1][3][4], axes_dev [D][3]) with its walk:  o_j, z_j = R_j axis_j ahead of joint j's
+ * rotation, R_j^+ behind it.  bodies_dev [D][10] holds per joint k (m, c[3], Ixx, Ixy, Ixz, Iyy, Iyz, Izz): mass, centre of mass
+ * and inertia about it of everything that turns with joint k and not with joint k + 1, in the frame behind joint k's rotation
+ * (KinematicChain.bodies); a mass of 0 is allowed.  With r_k = R_k^+ c_k and I_k^w = R_k^+ I_k R_k^+T, by value:
+ *     M(q)    = sum_k [ m_k Jv_k^T Jv_k + Jw_k^T I_k^w Jw_k ],   Jv_k[:, j] = z_j x (o_k + r_k - o_j),  Jw_k[:, j] = z_j  (j <= k, else 0)
+ *     g(q)    = dV/dq,   V = -sum_k m_k grav . (o_k + r_k)
+ *     c(q, v) = the Christoffel terms of M:  c_i = sum_jk (dM_ij/dq_k - 1/2 dM_jk/dq_i) v_j v_k
+ *     tau     = M a + c + g
+ *   traj / vel / acc are [rows][T][D]; vel_dev NULL means v = 0, acc_dev NULL a = 0.  inertia[r][t] = M [D][D], symmetric bit for bit;
+ *   gravity[r][t] = g [D];  coriolis[r][t] = c [D] (the torque at a = 0 and grav = 0);  torque[r][t] = M a + c + g [D].  Each output
+ *   may be NULL, not all four.  With vel_dev NULL and gravity = 0, torque is the reference's M(q_t) u_t for acc = u.
+ *   As computed: recursive Newton-Euler in base-frame coordinates, one pass per output and D unit-acceleration passes for M (the
+ *   upper triangle of each column kept and mirrored); csrc/avae_dynamics.h writes every operation and its order down.  A point with
+ *   a non-finite angle, speed or acceleration has NaN in all its outputs and touches no other point.
+ * rows == 0 is a no-op.  Errors (message in avae_last_error, nothing launched): rows < 0, D outside [1, 16], T outside [1, 1024], a
+ * non-finite gravity, a NULL required pointer (traj_dev, frames_dev, axes_dev, bodies_dev, gravity), every output NULL.
+ * One launch, no atomics, no scratch, nothing of the handle is read or written: a point's outputs are a pure function of its bits and
+ * the arguments -- the same alone or among other points, on any stream, on repetition and whichever outputs are asked for -- and the
+ * call works on any replica and inside avae_use_averaged. */
+int avae_motion_dynamics(avae_handle* h, const float* traj_dev, const float* vel_dev, const float* acc_dev,
+                         int32_t rows, int32_t T, int32_t D, const float* frames_dev, const float* axes_dev,
+                         const float* bodies_dev, const float* gravity,
+                         float* inertia_dev, float* gravity_dev, float* coriolis_dev, float* torque_dev, void* stream);
+
 /* ---- sigma-lognormal strokes: batched evaluation, perturbed sampling and fitting on the device.  The
  * reference diversifies its handwriting data by fitting every letter with a sum of lognormal velocity components
  * (pytrajkin_rxzero.rxzero_train), perturbing each component's amplitude, start angle and straightness and evaluating the stroke

@@ -11,6 +11,7 @@ _LAZY = {"AssocVariationalAutoEncoder": "vae_assoc", "train": "vae_assoc", "xavi
          "occlude_quadrant": "vae_assoc",
          "render_strokes_vjp": "vae_assoc", "motion_fk_vjp": "vae_assoc", "motion_eval_vjp": "vae_assoc", "rows_adam": "vae_assoc",
          "writing_cost_grad": "vae_assoc", "descend_motion": "vae_assoc",
+         "motion_dynamics": "vae_assoc", "motion_effort": "vae_assoc",
          "MotionBasis": "motion", "KinematicChain": "kinematics", "StrokeCanvas": "kinematics"}
 
 

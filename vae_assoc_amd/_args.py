@@ -819,6 +819,71 @@ def motion_pose_args(trajectories, chain, jacobian, device):
     return t, frames, axes, bool(jacobian), was_np
 
 
+# ---------------------------------------------------------------------------------------------------- rigid-body dynamics
+def chain_bodies(chain, device):
+    """A ``KinematicChain`` with inertial data -> ``bodies [n_dof, 10]`` as a float32 tensor on ``device``, cached on the chain per
+    device"""
+    need_type(chain, KinematicChain, "chain")
+    if not chain.has_inertia:
+        raise ValueError("chain carries no inertial data for every moving link (mass, com, com_rpy, inertia): dynamics need them")
+    key = ("device bodies", str(device))
+    if key not in chain._cache:
+        chain._cache[key] = torch.as_tensor(chain.bodies()).to(device)
+    return chain._cache[key]
+
+
+def _gravity3(gravity):
+    try:
+        g = np.array(gravity, dtype=np.float64)
+    except (TypeError, ValueError):
+        g = np.zeros(0)
+    with np.errstate(over="ignore"):
+        ok = g.shape == (3,) and np.isfinite(g).all() and np.isfinite(g.astype(np.float32)).all()
+    if not ok:
+        raise ValueError("gravity must be three finite numbers (m / s^2, base frame), got %r" % (gravity,))
+    return tuple(float(x) for x in g.astype(np.float32))
+
+
+def _step(dt, allow_none):
+    if dt is None and allow_none:
+        return None
+    if not _is_number(dt) or not np.isfinite(dt) or not float(np.float32(dt)) > 0.0 or not np.isfinite(np.float32(dt)):
+        raise ValueError("dt must be a finite number > 0 as float32, got %r" % (dt,))
+    return float(np.float32(dt))
+
+
+def motion_dynamics_args(trajectories, chain, velocities, accelerations, dt, gravity, inertia, device):
+    """The arguments of ``motion_dynamics`` -> (trajectories [N, T, n_dof], velocities and accelerations (the same shape, or None),
+    dt or None, frames, axes, bodies, gravity (three floats), effort limits [n_dof] on ``device`` or None, want_inertia,
+    was_numpy).  ``dt`` asks for finite differences and goes with neither ``velocities`` nor ``accelerations``."""
+    bodies = chain_bodies(chain, device)
+    if not isinstance(inertia, (bool, np.bool_)):
+        raise ValueError("inertia must be True or False, got %r" % (inertia,))
+    t, frames, axes, was_np = motion_fk_args(trajectories, chain, device)
+    dt = _step(dt, True)
+    if dt is not None and (velocities is not None or accelerations is not None):
+        raise ValueError("dt asks for finite differences of the trajectory: leave velocities and accelerations out with it")
+    rest = []
+    for x, name in ((velocities, "velocities"), (accelerations, "accelerations")):
+        if x is not None:
+            x = dev_block3(x, (int(t.shape[1]), chain.n_dof), device, name, rows=int(t.shape[0]))[0]
+        rest.append(x)
+    lim = chain.effort_limits
+    if lim is not None:
+        key = ("device effort", str(device))
+        if key not in chain._cache:
+            chain._cache[key] = to_device32(lim, device)
+        lim = chain._cache[key]
+    return t, rest[0], rest[1], dt, frames, axes, bodies, _gravity3(gravity), lim, bool(inertia), was_np
+
+
+def motion_effort_args(trajectories, chain, dt, device):
+    """The arguments of ``motion_effort`` -> (trajectories [N, T, n_dof], dt, frames, axes, bodies, was_numpy)"""
+    bodies = chain_bodies(chain, device)
+    t, frames, axes, was_np = motion_fk_args(trajectories, chain, device)
+    return t, _step(dt, False), frames, axes, bodies, was_np
+
+
 def ik_options(n_iters=20, tol=1e-5, rot_tol=1e-4, damping=0.01, max_step=0.5):
     """The solver options of ``motion_ik`` checked -> (n_iters, tol, rot_tol, damping, max_step), the four numbers as the float32
     values the kernel uses.  The ranges are avae_motion_ik's."""

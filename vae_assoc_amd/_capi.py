@@ -58,7 +58,7 @@ SYMBOLS = [
     "avae_motion_fk", "avae_stroke_render",
     "avae_stroke_render_vjp", "avae_motion_fk_vjp", "avae_motion_eval_vjp", "avae_rows_adam",
     "avae_letter_thumbnail", "avae_letter_thumbnail_plan",
-    "avae_motion_pose", "avae_motion_ik",
+    "avae_motion_pose", "avae_motion_ik", "avae_motion_dynamics",
     "avae_lognormal_eval", "avae_lognormal_sample", "avae_lognormal_fit",
     "avae_motion_track", "avae_motion_track_plan",
     "avae_search_sample", "avae_search_update",
@@ -212,6 +212,7 @@ def lib():
             L.avae_motion_pose.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]
             L.avae_motion_ik.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, i32, vp, i32, C.c_float, C.c_float, C.c_float,
                                          C.c_float, vp, vp, vp, vp, vp, vp]
+            L.avae_motion_dynamics.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, C.POINTER(C.c_float), vp, vp, vp, vp, vp]
             L.avae_lognormal_eval.argtypes = [vp, vp, vp, vp, i32, i32, i32, C.c_float, vp, vp, vp]
             L.avae_lognormal_sample.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, C.c_float, C.c_uint64, C.c_int64, C.c_float,
                                                 C.c_float, C.c_float, i32, vp, vp, vp]

@@ -7,7 +7,8 @@ strokes.
 ``vae_assoc``.  They are what the reference's writer scripts do around the model, for many rows at once.
 
 The gradients of the writing chain stand behind the class as functions of a model: ``render_strokes_vjp``,
-``motion_fk_vjp``, ``motion_eval_vjp``, ``rows_adam``, ``writing_cost_grad``, ``descend_motion``."""
+``motion_fk_vjp``, ``motion_eval_vjp``, ``rows_adam``, ``writing_cost_grad``, ``descend_motion``; so do the rigid-body dynamics
+of the arm (section 32): ``motion_dynamics``, ``motion_effort``."""
 import ctypes as C
 
 import numpy as np
@@ -16,7 +17,8 @@ import torch
 from ._args import (THUMBNAIL_CAMERA, THUMBNAIL_CANVAS, TRACK_FACTOR, TRACK_LAM_MAX, TRACK_LAM_MIN, _same_joints,
                     adam_options, canvas_args, chain_matrices, check_solver, cost_weights, descend_motion_args,
                     descent_state, draw_args, letter_thumbnail_args, lognormal_augment_args, lognormal_eval_args,
-                    lognormal_fit_args, lognormal_sample_options, motion_eval_args, motion_eval_vjp_args, motion_fit_args,
+                    lognormal_fit_args, lognormal_sample_options, motion_dynamics_args, motion_effort_args, motion_eval_args,
+                    motion_eval_vjp_args, motion_fit_args,
                     motion_fk_args, motion_fk_vjp_args, motion_ik_args, motion_matrices, motion_moments_args,
                     motion_pose_args, motion_track_args, predict_motion_args, refine_motion_args, refine_pen_path_args,
                     render_args, render_vjp_args, rows_adam_args, search_args, strokes_to_motion_args, track_rows_per_call,
@@ -565,8 +567,9 @@ class PenAPI(object):
 
         The first guess is ``init [N, T, n_dof]`` or, with ``init=None``, ``motion_ik(path, chain, seed, orientation,
         **ik_options)``: the reference's way.  ``effort`` is None (the identity) or a constant ``[n_dof, n_dof]`` matrix E, for
-        example the square root of the arm's inertia at the seed pose (the chain carries no masses).  ``limits`` (True: the
-        chain's own, None or ``[n_dof, 2]``) enter as a quadratic penalty ``limit_weight`` on what an angle lies outside them,
+        example ``chain.mass_matrix(seed)``, the arm's inertia at the seed pose: ``effort_weight |M(seed) u|^2`` is the reference's
+        effort term with its ``M(q_t)`` frozen at one pose (``motion_effort`` prices a result with the moving one).  ``limits``
+        (True: the chain's own, None or ``[n_dof, 2]``) enter as a quadratic penalty ``limit_weight`` on what an angle lies outside them,
         and not at all at ``limit_weight=0``.  A try solves the Riccati recursion at the damping ``lam`` (``lam0`` at first, a
         tenth after an accepted try, tenfold after a rejected one, between 1e-6 and 1e6) and takes the full step if it lowers the
         cost; a row ends after ``n_iters`` tries, when an accepted try gains less than ``tol`` of the cost, or when ``lam`` passes
@@ -1017,3 +1020,73 @@ def descend_motion(model, target_image, basis, chain, canvas, init=None, n_iters
             "img_l2": conv(last["img_l2"]), "height_l2": conv(last["height_l2"]), "image": conv(last["image"]),
             "best_cost": conv(best_cost), "best_image": conv(best["image"]), "history": conv(hist), "status": conv(status),
             "height": conv(h0), "state": st}
+
+
+# ---------------------------------------------------------------------------------------------------- rigid-body dynamics (section 32)
+def _motion_dynamics(model, t, v, a, frames, axes, bodies, gravity, inertia=False, gravity_torque=True, coriolis=True, torque=True):
+    """avae_motion_dynamics on device tensors: trajectories, speeds and accelerations [N, T, D] (the last two may be None) ->
+    (inertia [N, T, D, D], gravity, coriolis, torque [N, T, D]), None for an output that is not asked for"""
+    N, T, D = t.shape
+
+    def new(want, *tail):
+        return model._out((N, T, D) + tail) if want else None
+    M, g, c, tau = new(inertia, D), new(gravity_torque), new(coriolis), new(torque)
+    if N:
+        model._call("avae_motion_dynamics", t.data_ptr(), ptr(v), ptr(a), N, T, D, frames.data_ptr(), axes.data_ptr(),
+                    bodies.data_ptr(), (C.c_float * 3)(*gravity), ptr(M), ptr(g), ptr(c), ptr(tau))
+    return M, g, c, tau
+
+
+def _differences(t, dt):
+    """``motion_track``'s finite differences of trajectories [N, T, D] on the device -> (v, a): ``v_0 = 0``, ``v_t = (q_t -
+    q_(t-1)) / dt``, ``a_t = (v_(t+1) - v_t) / dt``, ``a_(T-1) = 0``, float32 differences and divisions (``dt`` as a device
+    scalar: a host scalar would turn the division into a product with 1 / dt)"""
+    v, a = torch.zeros_like(t), torch.zeros_like(t)
+    dt = torch.full((), dt, dtype=t.dtype, device=t.device)
+    v[:, 1:] = (t[:, 1:] - t[:, :-1]) / dt
+    a[:, :-1] = (v[:, 1:] - v[:, :-1]) / dt
+    return v, a
+
+
+def motion_dynamics(model, trajectories, chain, velocities=None, accelerations=None, dt=None, gravity=(0.0, 0.0, -9.81),
+                    inertia=False):
+    """The joint torques a motion asks of the arm (avae_motion_dynamics in include/avae.h): the reference's ``baxter_dynamics``
+    (``inertia``, ``coriolis``, ``gravity`` of baxter_pykdl_revised.py:218-296) for every point of N trajectories ``[N, T,
+    chain.n_dof]`` in one launch.  ``chain`` must carry inertial data (``KinematicChain.has_inertia``).  ``velocities`` and
+    ``accelerations`` (the trajectories' shape; None: zeros) are the joint speeds and accelerations at each point; with ``dt``
+    given and neither of them they are ``motion_track``'s finite differences of the trajectory (``v_0 = 0``, ``v_t = (q_t -
+    q_(t-1)) / dt``, ``a_t = (v_(t+1) - v_t) / dt``, ``a_(T-1) = 0``), formed on the device.  ``gravity`` is the acceleration
+    of free fall in the base frame.
+
+    Returns a dict: ``torque [N, T, n_dof]`` (``M a + c + g``), ``gravity`` (g alone) and ``coriolis`` (c alone: the torque at
+    ``a = 0`` without gravity), with ``inertia=True`` also ``inertia [N, T, n_dof, n_dof]`` (M, symmetric bit for bit), and,
+    when every joint of the chain has an effort limit, ``peak_torque [N, n_dof]`` (``max_t |torque|``) and ``torque_ratio
+    [N, n_dof]`` (that over the limit: a motion stays within the arm's torques where it is at most 1).  A point with a
+    non-finite angle, speed or acceleration is NaN in its own outputs.  NumPy in gives NumPy out, device tensors in give
+    device tensors out."""
+    t, v, a, dt, frames, axes, bodies, grav, lim, want, was_np = motion_dynamics_args(trajectories, chain, velocities, accelerations,
+                                                                                      dt, gravity, inertia, model.device)
+    if dt is not None:
+        v, a = _differences(t, dt)
+    M, g, c, tau = _motion_dynamics(model, t, v, a, frames, axes, bodies, grav, inertia=want)
+    conv = model._like_input(was_np)
+    out = {"torque": conv(tau), "gravity": conv(g), "coriolis": conv(c)}
+    if want:
+        out["inertia"] = conv(M)
+    if lim is not None:
+        peak = tau.abs().amax(1) if tau.shape[0] else tau.new_zeros((0, tau.shape[2]))
+        out.update(peak_torque=conv(peak), torque_ratio=conv(peak / lim))
+    return out
+
+
+def motion_effort(model, trajectories, chain, dt=0.01):
+    """The reference's control effort of N trajectories ``[N, T, chain.n_dof]``, whoever made them (``ctrl_effort``,
+    baxter_writer.py:112-126): ``effort [N] = sum_(t < T - 1) |M(q_t) u_t|^2`` with ``M`` the joint-space inertia at the pose of
+    time point t and ``u_t`` ``motion_track``'s controls of the trajectory, the finite differences ``motion_dynamics`` forms
+    with ``dt``.  ``M(q_t) u_t`` is one ``avae_motion_dynamics`` launch (speeds left out, no gravity); squares and sums are
+    torch reductions on the device.  Returns a dict of ``effort [N]`` and ``controls [N, T - 1, n_dof]``."""
+    t, dt, frames, axes, bodies, was_np = motion_effort_args(trajectories, chain, dt, model.device)
+    u = _differences(t, dt)[1]
+    tau = _motion_dynamics(model, t, None, u, frames, axes, bodies, (0.0, 0.0, 0.0), gravity_torque=False, coriolis=False)[3]
+    conv = model._like_input(was_np)
+    return {"effort": conv((tau[:, :-1] * tau[:, :-1]).sum((1, 2))), "controls": conv(u[:, :-1].contiguous())}

@@ -9,6 +9,7 @@
 #include "avae_grad.h"
 #include "avae_thumbnail.h"
 #include "avae_ik.h"
+#include "avae_dynamics.h"
 #include "avae_lognormal.h"
 #include "avae_track.h"
 #include "avae_search.h"
@@ -5070,6 +5071,32 @@ int avae_motion_ik(avae_handle* h, const float* path_dev, int32_t rows, int32_t 
         a.rows = rows; a.T = T; a.D = D; a.n_iters = n_iters; a.orient_per_row = orient_dev && orient_rows == rows && rows > 1 ? 1 : 0;
         hipStream_t s = on_stream(h, stream);
         timed_launch(h, s, "motion_ik", [&] { launch_motion_ik(a, s); });
+    });
+}
+
+// ---- joint-space inertia and inverse dynamics (include/avae.h, avae_dynamics.h)
+int avae_motion_dynamics(avae_handle* h, const float* traj_dev, const float* vel_dev, const float* acc_dev,
+                         int32_t rows, int32_t T, int32_t D, const float* frames_dev, const float* axes_dev,
+                         const float* bodies_dev, const float* gravity,
+                         float* inertia_dev, float* gravity_dev, float* coriolis_dev, float* torque_dev, void* stream) {
+    return guarded(h, [&] {
+        const std::string w = "avae_motion_dynamics";
+        check_rows(w, rows, "rows");
+        check_range(w, "T", T, 1, kIkMaxT);
+        check_range(w, "D", D, 1, kIkMaxD);
+        need(w, traj_dev, "traj_dev"); need(w, frames_dev, "frames_dev"); need(w, axes_dev, "axes_dev");
+        need(w, bodies_dev, "bodies_dev"); need(w, gravity, "gravity");
+        for (int i = 0; i < 3; ++i)
+            if (!std::isfinite(gravity[i])) throw Err(w + ": gravity[" + std::to_string(i) + "] must be finite");
+        if (!inertia_dev && !gravity_dev && !coriolis_dev && !torque_dev) throw Err(w + ": every output is NULL");
+        if (rows == 0) return;
+        DynArgs a = zeroed<DynArgs>();
+        a.traj = traj_dev; a.vel = vel_dev; a.acc = acc_dev; a.frames = frames_dev; a.axes = axes_dev; a.bodies = bodies_dev;
+        a.inertia = inertia_dev; a.gravity = gravity_dev; a.coriolis = coriolis_dev; a.torque = torque_dev;
+        a.points = (long long)rows * T; a.D = D;
+        for (int i = 0; i < 3; ++i) a.g[i] = -gravity[i];
+        hipStream_t s = on_stream(h, stream);
+        timed_launch(h, s, "motion_dynamics", [&] { launch_motion_dynamics(a, s); });
     });
 }
 

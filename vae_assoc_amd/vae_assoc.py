@@ -45,7 +45,8 @@ from ._args import (SEARCH_STATE_KEYS, _is_pair, _same_joints, agg_args, canvas_
                     letter_thumbnail_args, occlude_quadrant, THUMBNAIL_CAMERA, THUMBNAIL_CANVAS,
                     check_solver, motion_track_args, track_rows_per_call, TRACK_FACTOR, TRACK_LAM_MAX, TRACK_LAM_MIN,
                     ADAM_STATE_KEYS, DESCENT_STATE_KEYS, adam_options, cost_weights, descend_motion_args, descent_state,
-                    motion_eval_vjp_args, motion_fk_vjp_args, render_vjp_args, rows_adam_args)
+                    motion_eval_vjp_args, motion_fk_vjp_args, render_vjp_args, rows_adam_args,
+                    chain_bodies, motion_dynamics_args, motion_effort_args)
 from ._marshal import (as_index, corruption_fields, ema_fields, ema_kwargs, grad_clip_fields, grad_clip_kwargs, dev_array, dev_block3, dev_dense, dev_dense3, dev_flags, dev_inputs, dev_modalities, dev_row_args,  # noqa: F401
                        ld_of, ptr, schedule_kwargs, schedule_struct, to_device32)
 from ._marshal import cyclical, exponential_decay, linear_warmup  # noqa: F401  (schedule helpers, part of this module's surface)
@@ -53,6 +54,7 @@ from ._latent_api import LatentAPI
 from ._pen_api import PenAPI
 from ._pen_api import (descend_motion, motion_eval_vjp, motion_fk_vjp, render_strokes_vjp, rows_adam,  # noqa: F401
                        writing_cost_grad)      # (functions of a model: DESIGN.md section 31)
+from ._pen_api import motion_dynamics, motion_effort  # noqa: F401  (functions of a model: DESIGN.md section 32)
 from .motion import MotionBasis  # noqa: F401
 from .parallel import GradSync, dp_bucket_schedule, dp_train_step_bucketed
 
